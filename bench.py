@@ -5,7 +5,7 @@ Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line o
 A step = one launch of eval_c! + jac_c! over every knot of every problem of the rank's shard, with
 inputs and outputs resident in HBM.  Default workload = BASELINE.json configs[2] (0-based: B=65536, N=40,
 k_trans=14, FP64 -- "config 3" of BASELINE.md): the HBM-bound regime the metric's roofline half is quoted on;
-configs[1] (B=1024, launch-latency regime) is timed beside it and reported under "other".  The --workload names
+configs[1] (B=1024, launch-latency regime) is timed beside it with --full and reported under "other".  The --workload names
 config2/config3/config4 follow BASELINE.md's 1-based table, i.e. configs[1]/[2]/[3].
 
 ONE measurement for every N.  Whatever N is and however the N GPUs are driven, the line is produced the same way:
@@ -23,6 +23,11 @@ Two drivers produce that line: 'ranks' = one process per GPU (the driver's torch
 `python bench.py` at N = 1), RCCL through qln_comm_* -- torch.distributed (gloo) only carries RCCL's 128-byte id;
 'single-process' = this process drives all N devices through qln_multi_* (one host thread per device issues its
 launches).  `config.driver`, `config.workload_data` and `config.timing` say which produced the line.
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed launches, the outputs of the last one when
+--dump-outputs is given, the line (with its roofline, priced from the same K launches).  Everything else -- the end-of-job
+tail (gather_ms, gather_c_ms), the other entry points, formats, sizes and solves under `other`, the CPU baselines -- runs
+with --full only.
 """
 import argparse
 import json
@@ -238,14 +243,55 @@ def stamped_profile_ms(key, placed):
     return e.get("kernel_avg_ms_rocprof_placed" if placed else "kernel_avg_ms_rocprof_plain"), e.get("build_id")
 
 
+DUMP_PROBLEMS, DUMP_SEED, DUMP_MAX_BYTES = 128, 0, 64 * 10**6
+
+
+def dump_outputs(out_dir, handle, B, c, vals):
+    """--dump-outputs: what the timed launch hands its caller -- the constraint vector c and the Jacobian values -- for a
+    fixed, seeded sample of the handle's problems (the whole buffers are 0.4 / 6.6 GB at the default workload).  Every
+    sampled problem's segments are taken whole (c_off[b] + [0, m_nlp), j_off[b] + [0, nnz)), without the padding between
+    segments, and concatenated in problem order: DIR/c.npy, DIR/jac_vals.npy, float64."""
+    import ctypes as C
+
+    import torch
+    from quadruped_landing_amd import _lib
+
+    L = _lib.lib()
+    c_off, j_off = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
+    lp = C.POINTER(C.c_int64)
+    _lib.check(L.qln_get_offsets(handle, c_off.ctypes.data_as(lp), j_off.ctypes.data_as(lp)))
+    problems = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=min(B, DUMP_PROBLEMS), replace=False))
+    mm, nz = C.c_int32(), C.c_int32()
+    c_idx, j_idx = [], []
+    for b in problems:
+        _lib.check(L.qln_problem_dims(handle, int(b), C.byref(mm), C.byref(nz)))
+        c_idx.append(np.arange(c_off[b], c_off[b] + mm.value))
+        j_idx.append(np.arange(j_off[b], j_off[b] + nz.value))
+    arrays = {}
+    for name, t, idx in (("c", c, c_idx), ("jac_vals", vals, j_idx)):
+        arrays[name] = t.index_select(0, torch.from_numpy(np.concatenate(idx)).to(t.device)).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="config3", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the end-of-job tail, the `other` entries and the CPU baselines (a plain run times the "
+                         "K launches only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
+    ap.add_argument("--no-other", action="store_true", help="with --full: leave out the `other` entries")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed launches, write what the last one computed (c and the Jacobian values of a fixed, "
+                         "seeded sample of rank 0's / shard 0's problems) as DIR/c.npy and DIR/jac_vals.npy (float64)")
     ap.add_argument("--jac-format", default="dense_blocks", choices=["dense_blocks", "structural"],
                     help="layout of the step blocks in vals: the reference's dense 15x20 blocks (the unit SURVEY.md 8d "
                          "prices) or only their structurally non-zero entries (priced at the strict byte count)")
@@ -261,6 +307,10 @@ def main():
                          "drives all N devices through qln_multi_* (include/qln_multi.h); auto = ranks under a launcher, "
                          "else single-process when --gpus > 1")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is not None and int(env_world) != args.gpus:
@@ -346,10 +396,11 @@ def roofline_record(args, batch, ms_each):
                            "frac": strict_achieved / HBM_PEAK_GBS}}
 
 
-def tail_note():
+def tail_note(full):
     return ("value = knot evals / wall clock of the K-launch region only (barrier + device sync on both sides); the end-of-job "
-            "tail (eval_f + constraint violation + gather of the per-problem results to GPU 0) follows it and is reported as "
-            "gather_ms -- the same for every N and both drivers")
+            "tail (eval_f + constraint violation + gather of the per-problem results to GPU 0) "
+            + ("follows it and is reported as gather_ms" if full else "is measured with --full only (gather_ms)")
+            + " -- the same for every N and both drivers")
 
 
 def run_single_process(args):
@@ -395,44 +446,50 @@ def run_single_process(args):
     m.alloc_vals(placed=args.placement_trials > 1)
     K, W = args.steps, args.warmup
     what = multi.GATHER_F | multi.GATHER_VIOL
-    m.time_c_and_jac(0, max(W, 1))  # warm-up launches, and one tail so that RCCL is initialised
-    m.eval_f()
-    m.constraint_violation()
-    m.gather(what)
+    m.time_c_and_jac(0, max(W, 1))  # warm-up launches
+    if args.full:                    # and one tail so that RCCL is initialised
+        m.eval_f()
+        m.constraint_violation()
+        m.gather(what)
     m.synchronize()
     # ---- the timed region: K launches per device, nothing else.  qln_multi_time_* synchronises every device, releases
     # one issue thread per device together and returns when all devices are idle; its own host clock brackets exactly that.
     ms_dev, wall_ms = m.time_c_and_jac(0, K)
     elapsed = wall_ms * 1e-3
-    # ---- the end-of-job tail
-    tg = time.perf_counter()
-    m.eval_f()
-    m.constraint_violation()
-    m.gather(what)                   # the single end-of-job exchange (RCCL over xGMI)
-    m.synchronize()
-    t_gather = time.perf_counter() - tg
-    m.gather(multi.GATHER_C)         # for the record: the full (ragged) constraint vectors to device 0
-    m.synchronize()
-    tg = time.perf_counter()
-    m.gather(multi.GATHER_C)
-    m.synchronize()
-    t_gather_c = time.perf_counter() - tg
+    if args.dump_outputs:
+        s0 = m.shard(0)
+        dump_outputs(args.dump_outputs, s0["handle"], s0["end"] - s0["begin"], m.shard_tensor(0, "c"), m.shard_tensor(0, "vals"))
+    if args.full:
+        # ---- the end-of-job tail
+        tg = time.perf_counter()
+        m.eval_f()
+        m.constraint_violation()
+        m.gather(what)                   # the single end-of-job exchange (RCCL over xGMI)
+        m.synchronize()
+        t_gather = time.perf_counter() - tg
+        m.gather(multi.GATHER_C)         # for the record: the full (ragged) constraint vectors to device 0
+        m.synchronize()
+        tg = time.perf_counter()
+        m.gather(multi.GATHER_C)
+        m.synchronize()
+        t_gather_c = time.perf_counter() - tg
     total_B = B * n
     out = base_record(args, total_B * N * K / elapsed, n, elapsed, B, N, m.z_stride,
                       {"driver": "one process, one issue thread per device, qln_multi_* (include/qln_multi.h)"
                                  + (f"; REHEARSAL: all {n} shards on device 0 (qln_multi_create_on_one_device, gather by device copies) -- "
                                     "control flow only, not a multi-GPU measurement" if rehearse else ""),
                        "jacobian_buffer": "qln_vals_alloc_placed per device" if args.placement_trials > 1 else "plain allocation",
-                       "workload_data": data_how, "timing": tail_note(),
+                       "workload_data": data_how, "timing": tail_note(args.full),
                        "multi_gpu_status": multi_gpu_status(n)})
     per_dev = [float(x) / K for x in ms_dev]
     out["roofline"] = roofline_record(args, shard0, np.array([max(per_dev)]))
     out["roofline"]["launch_ms_avg_per_device"] = per_dev
     out["roofline"]["launch_ms_source"] = "HIP events on each device's stream around its K launches; the slowest device is the one priced"
-    out["gather_ms"] = t_gather * 1e3
-    out["gather_c_ms"] = t_gather_c * 1e3
-    f, viol, _ = m.gathered()
-    assert f.shape == (total_B,) and np.all(np.isfinite(f)) and np.all(np.isfinite(viol))
+    if args.full:
+        out["gather_ms"] = t_gather * 1e3
+        out["gather_c_ms"] = t_gather_c * 1e3
+        f, viol, _ = m.gathered()
+        assert f.shape == (total_B,) and np.all(np.isfinite(f)) and np.all(np.isfinite(viol))
     m.close()
     return out
 
@@ -533,7 +590,6 @@ def run_ranks(args):
     data_how = build.last_data
     placement_ms = list(build.last_trials)
     placement_how = build.last_placement
-    f, viol = nlp.new_f(), nlp.new_f()
     K, W = args.steps, args.warmup
     structural = args.jac_format == "structural"
 
@@ -549,13 +605,15 @@ def run_ranks(args):
             return comm.gather(t)[0]
         return t.clone()
 
-    # warmup (untimed): W launches (HIP events around each: the per-launch spread reported beside the average), one objective
-    # pass, and one gather so RCCL's channels exist
+    # warmup (untimed): W launches (HIP events around each: the per-launch spread reported beside the average); with --full,
+    # one objective pass and one gather so RCCL's channels exist for the tail
     ms_warm = nlp.time_c_and_jac(Z, c, vals, warmup=0, iters=max(W, 1))
-    nlp.eval_f(Z, f)
-    nlp.constraint_violation(c, viol)
-    gather1(f)
-    gather1(viol)
+    if args.full:
+        f, viol = nlp.new_f(), nlp.new_f()
+        nlp.eval_f(Z, f)
+        nlp.constraint_violation(c, viol)
+        gather1(f)
+        gather1(viol)
     barrier()
 
     # ---- the timed region: K launches, nothing else, bracketed by barrier + device synchronisation on both sides
@@ -567,27 +625,31 @@ def run_ranks(args):
     barrier()
     elapsed = time.perf_counter() - t0
     ms_each = np.array([ms_total / K])
-    # ---- the end-of-job tail (the same for every N): per-problem results, then the single gather to rank 0
-    tg = time.perf_counter()
-    nlp.eval_f(Z, f)
-    nlp.constraint_violation(c, viol)
-    f_all = gather1(f)               # RCCL over xGMI when there is more than one rank
-    viol_all = gather1(viol)
-    torch.cuda.synchronize()
-    t_gather = time.perf_counter() - tg
-    barrier()
-    gather1(c)                       # for the record: the full (ragged) constraint vectors to rank 0
-    barrier()
-    tg = time.perf_counter()
-    gather1(c)
-    torch.cuda.synchronize()
-    t_gather_c = time.perf_counter() - tg
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, nlp._h, batch.B, c, vals)
+    if args.full:
+        # ---- the end-of-job tail (the same for every N): per-problem results, then the single gather to rank 0
+        tg = time.perf_counter()
+        nlp.eval_f(Z, f)
+        nlp.constraint_violation(c, viol)
+        f_all = gather1(f)               # RCCL over xGMI when there is more than one rank
+        viol_all = gather1(viol)
+        torch.cuda.synchronize()
+        t_gather = time.perf_counter() - tg
+        barrier()
+        gather1(c)                       # for the record: the full (ragged) constraint vectors to rank 0
+        barrier()
+        tg = time.perf_counter()
+        gather1(c)
+        torch.cuda.synchronize()
+        t_gather_c = time.perf_counter() - tg
     launch_avg = float(np.mean(ms_each))
     launch_avgs = [launch_avg]
     if comm is not None:
         elapsed = comm.max(elapsed)
-        t_gather = comm.max(t_gather)
-        t_gather_c = comm.max(t_gather_c)
+        if args.full:
+            t_gather = comm.max(t_gather)
+            t_gather_c = comm.max(t_gather_c)
         slowest = comm.max(launch_avg)   # the roofline prices the slowest GPU's launches
         launch_avgs = [launch_avg] if world == 1 else [launch_avg, slowest]
 
@@ -598,17 +660,18 @@ def run_ranks(args):
                                                           else ", RCCL through qln_comm_* (include/qln_multi.h)" if rccl_error is None
                                                           else f", RCCL UNAVAILABLE ({rccl_error}): end-of-job gather over gloo (host memory)"),
                            "jacobian_buffer": placement_how, "placement_trials_ms": placement_ms, "workload_data": data_how + ", seed = rank",
-                           "timing": tail_note(), "multi_gpu_status": multi_gpu_status(world)})
+                           "timing": tail_note(args.full), "multi_gpu_status": multi_gpu_status(world)})
         out["roofline"] = roofline_record(args, batch, ms_each if len(launch_avgs) == 1 else np.array([launch_avgs[1]]))
         out["roofline"]["launch_ms_min"] = float(np.min(ms_warm))
         out["roofline"]["launch_ms_warmup_each"] = [float(x) for x in ms_warm]
         out["roofline"]["launch_ms_source"] = ("one pair of HIP events on the rank's stream around the K back-to-back launches of the timed region, / K "
                                                "(launch_ms_min / launch_ms_warmup_each: events around each warm-up launch); rank 0's average"
                                                + ("" if len(launch_avgs) == 1 else f" {launch_avgs[0]:.4f} ms, slowest rank's {launch_avgs[1]:.4f} ms (priced)"))
-        assert f_all.numel() == batch.B * world and viol_all.numel() == batch.B * world
-        out["gather_ms"] = t_gather * 1e3        # eval_f + constraint violation + their gather: the end-of-job tail, after the timed region
-        out["gather_c_ms"] = t_gather_c * 1e3    # full c (c_total doubles per rank)
-        if world == 1 and not args.no_other:
+        if args.full:
+            assert f_all.numel() == batch.B * world and viol_all.numel() == batch.B * world
+            out["gather_ms"] = t_gather * 1e3        # eval_f + constraint violation + their gather: the end-of-job tail, after the timed region
+            out["gather_c_ms"] = t_gather_c * 1e3    # full c (c_total doubles per rank)
+        if args.full and world == 1 and not args.no_other:
             # all four callbacks of an NLP iteration from one read of Z in one launch (qln_eval_all): same workload, same buffers
             gg = nlp.new_Z()
             for _ in range(3):
@@ -640,7 +703,7 @@ def run_ranks(args):
             out["other"]["objective_and_constraint_one_launch"] = {
                 "launch_ms_avg": ms_fc, "achieved_GBs": fc_bytes / (ms_fc * 1e-3) / 1e9, "roofline_frac": fc_bytes / (ms_fc * 1e-3) / 1e9 / HBM_PEAK_GBS,
                 "note": "qln_eval_objective_and_constraint: eval_f + eval_c! from one read of Z (no derivatives); bytes = Z read + c and f written"}
-        if world == 1 and not args.no_other and not structural:
+        if args.full and world == 1 and not args.no_other and not structural:
             # same workload, structural format (only the non-zeros of every step block are written)
             del vals
             bs, ns, Zs, cs, vs = build(args.workload, seed=rank, device=local_rank, placement_trials=min(2, args.placement_trials), jac_format="structural")
@@ -653,7 +716,7 @@ def run_ranks(args):
                 "note": "jac_format=structural (QLN_JAC_FORMAT_STRUCTURAL): 71/56/57 values per step block instead of "
                         "300; priced at SURVEY.md 8d's strict byte count"}
             del bs, ns, Zs, cs, vs
-        if world == 1 and not args.no_other and args.workload != "config2":
+        if args.full and world == 1 and not args.no_other and args.workload != "config2":
             b2, n2, Z2, c2, v2 = build("config2", seed=0, device=local_rank, jac_format=args.jac_format)
             ms2 = n2.time_c_and_jac(Z2, c2, v2, warmup=5, iters=50)
             alg2 = float(np.sum((strict_bytes if structural else algorithmic_bytes)(b2.N, b2.k_trans)))
@@ -703,7 +766,7 @@ def run_ranks(args):
                     "violation_max": float(sviol.max()), "objective_median": float(np.median(si[:, 2])),
                     "note": "the same on the bench workload's own problems (its drop states, the notebook's initial guess)"}
                 del Zs, sinfo
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             one, allc = cpu_baseline(batch, nlp, Z)
             out["cpu_baseline"] = one
             out["cpu_baseline_all_cores"] = allc

@@ -1,9 +1,13 @@
-"""The JSON line bench.py prints (the committed line of the round's final run, profiles/r03_bench.json) carries every
-field of the driver's contract, and its numbers are consistent with each other and with SURVEY.md 8d's byte counts."""
+"""The JSON line `bench.py --full` prints (the committed line of the round's final run, profiles/r03_bench.json) carries
+every field of the driver's contract, and its numbers are consistent with each other and with SURVEY.md 8d's byte counts;
+a plain run reports the headline alone and dumps what its last timed launch computed."""
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
+import pytest
 
 import bench
 
@@ -75,3 +79,36 @@ def test_kernel_build_id_is_stable_and_traffic_lookup_refuses_other_builds(tmp_p
     assert t is None and "not quoted" in why
     t, why = bench.measured_traffic("config2")
     assert t is None and "no PMC profile" in why
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_only_and_dumps_the_same_outputs_every_run(tmp_path):
+    """Without --full the line holds the headline of exactly --steps launches and nothing measured beside it; --dump-outputs
+    writes c and the Jacobian values of the last launch for a fixed sample of problems, the same bits in a second run."""
+    B, N, kt, S = 1024, 40, 14, bench.DUMP_PROBLEMS
+    runs = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload",
+               "config2", "--placement-trials", "1", "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f64" and d["unit"] == "knot-evals/s"
+        assert d["config"]["problems_per_gpu"] == B and d["config"]["knots"] == N
+        assert abs(d["value"] - B * N / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        for k in ("other", "cpu_baseline", "cpu_baseline_all_cores", "gather_ms", "gather_c_ms"):
+            assert k not in d, k
+        assert sorted(os.listdir(out)) == ["c.npy", "jac_vals.npy"]
+        a = {k: np.load(out / (k + ".npy")) for k in ("c", "jac_vals")}
+        assert all(v.dtype == np.float64 and v.ndim == 1 for v in a.values())
+        assert sum(v.nbytes for v in a.values()) <= bench.DUMP_MAX_BYTES
+        # whole segments of S problems: m_nlp = 18 N - k_trans + 16 constraints, the dense-block value count of each
+        assert a["c"].size == S * (18 * N - kt + 16)
+        assert a["jac_vals"].size == S * (300 * (N - 1) + N + 435 + 15 * (N - 1) + 3 * N - kt + 3)
+        assert np.count_nonzero(a["c"]) > 0 and np.count_nonzero(a["jac_vals"]) > 0
+        runs.append(a)
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k], equal_nan=True), k

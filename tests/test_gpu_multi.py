@@ -196,7 +196,7 @@ def test_bench_two_rank_control_flow_rehearsal_on_one_gpu(tmp_path):
     env = dict(os.environ, QLN_BENCH_REHEARSE_ON_DEVICE0="1", QLN_BENCH_SIMULATE_RCCL_FAILURE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29547", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--workload",
-           "config2", "--placement-trials", "1"]
+           "config2", "--placement-trials", "1", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -223,7 +223,7 @@ def test_bench_single_process_driver_rehearsed_with_n_shards_on_one_gpu(workload
 
     env = dict(os.environ, QLN_BENCH_REHEARSE_ON_DEVICE0="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "single-process", "--gpus", str(n), "--steps", "4", "--warmup", "1",
-           "--workload", workload, "--placement-trials", "1", "--no-cpu-baseline", "--no-other"]
+           "--workload", workload, "--placement-trials", "1", "--full", "--no-cpu-baseline", "--no-other"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
