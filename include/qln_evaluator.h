@@ -168,6 +168,42 @@ int qln_jacobian_init_constants(qln_handle* h, double* vals);
  * Device pointers, stream-ordered. */
 int qln_eval_constraint_jvp(qln_handle* h, const double* Z, const double* v, double* y);
 int qln_eval_constraint_vjp(qln_handle* h, const double* Z, const double* lam, double* g);
+/* The Hessian of the Lagrangian -- the second-order callback of an MOI.AbstractNLPEvaluator (:Hess), which the reference
+ * does not offer (src/moi.jl:26-28 declares [:Grad, :Jac], so Ipopt runs L-BFGS).  For problem b, with a scalar sigma_b
+ * and multipliers mu in the layout of c:
+ *
+ *   H_b = sigma_b d2 eval_f(Z) + sum_i mu_i d2 c_i(Z),  returned as the lower triangle (row >= col) in a fixed sparse pattern.
+ *
+ * H_b is block-diagonal over knots (dynamics row block k is linear in x_{k+1}; the objective is a sum over knots of
+ * h_k l_k(x_k, u_k); clearance row k involves only theta_k; the initial, terminal, contact and final-control rows are linear).
+ *   Step block k = 1..N-1, variables z_k = Z[20(k-1) .. 20(k-1)+19] = (x_k[0..14], F1x, F1y, F2x, F2y, h_k):
+ *     H_k = sigma d2(h_k l_k) + d2(mu_dyn,k . M_k rk4_mode(k)(x_k, u_k)) + mu_clr,k c''(theta_k) e2 e2'
+ *     M_k = the jump mask JUMP_DIAG (quirk Q1) at the transition knot k_trans-1, the identity elsewhere: multipliers on
+ *     masked rows contribute nothing.
+ *   Objective part (u_k[4] = h_k; Q, R, q, r of the knot's 41-double cost record): h Q_i on the x diagonal, h R_i on the
+ *     force diagonal (i < 4), Q_i x_i + q_i in (h, x_i), R_i u_i + r_i in (h, F_i), 2(R_4 h + r_4) + h R_4 in (h, h).
+ *     This is the Hessian of eval_f, the FUNCTION -- not the Jacobian of grad_f!: quirk Q2 drops d(h l)/dh from the
+ *     gradient, and the Jacobian of that gradient is not symmetric.
+ *   Terminal block: the diagonal of x_N, sigma Qf_i, plus the clearance term at i = 2.
+ *   Clearance c = y_b - (lb/2)|sin theta|: its second derivative is taken on the branch quirk Q3's Jacobian takes --
+ *     +(lb/2) sin theta for theta > 0, -(lb/2) sin theta otherwise: the derivative of the entry jac_c! writes.
+ *   Only the dynamics rows and the clearance rows of mu are read; the other rows are linear and never read.
+ * The step's second derivatives are few (the polynomial step of qln_kernels.hip: no force x force and no theta-coupled
+ * term survives), so a step block has 55 lower-triangle entries whatever the mode: 34 of mu . M rk4 and the objective's
+ * diagonal and h row.
+ * Layout: problem b at hvals + b*h_stride, h_stride = nnz = 55(N-1)+15 rounded up to desc.align (N is shared and the
+ * pattern depends neither on k_trans nor on the mode, so the layout is uniform).  Inside a segment the N-1 step blocks come
+ * first, with global indices (20(k-1)+r, 20(k-1)+c) and their 55 values in column-major order of the pattern, then the 15
+ * terminal diagonal values.  An entry that is structurally zero in a knot's mode is an exact zero.  A buffer of
+ * (B-1)*h_stride + nnz doubles holds the batch (no padding behind the last problem). */
+#define QLN_HESS_STEP_NNZ 55
+#define QLN_HESS_TERM_NNZ 15
+/* device-free: nnz of one problem and the stride between problems for `desc` (desc->N and desc->align are read) */
+int qln_hessian_layout(const qln_batch_desc* desc, int32_t* nnz, int64_t* h_stride);
+/* device-free: 0-based (row, col), row >= col, of the nnz entries of a segment, in the order of the values */
+int qln_hessian_structure(int32_t N, int32_t* rows, int32_t* cols);
+/* device pointers, stream-ordered; sigma: [B] or NULL (= 1.0 for every problem); mu: layout of c.  Needs a cost table. */
+int qln_eval_hessian_lagrangian(qln_handle* h, const double* Z, const double* sigma, const double* mu, double* hvals);
 /* One Gauss-Newton step on the constraint violation for every problem of the batch (the solver
  * iteration on the GPU, consuming the Jacobian where it is produced).  For problem b
  *     dZ_b = D x,  x = the minimum-norm minimiser of || A D x + rho ||_2   (subject to ||x|| <= radius[b] if given),
@@ -327,6 +363,8 @@ int qln_eval_objective_host(qln_handle* h, const double* Z, double* f);
 int qln_eval_objective_gradient_host(qln_handle* h, const double* Z, double* grad);
 int qln_eval_constraint_host(qln_handle* h, const double* Z, double* c);
 int qln_eval_constraint_jacobian_host(qln_handle* h, const double* Z, double* vals);
+/* MOI mode of qln_eval_hessian_lagrangian: host pointers, synchronous, same layouts (staged through device memory) */
+int qln_eval_hessian_lagrangian_host(qln_handle* h, const double* Z, const double* sigma, const double* mu, double* hvals);
 /* Reference-compatible dense Jacobian of ONE problem (src/moi.jl:15-24): `jac` is a host,
  * column-major m_nlp x n_nlp buffer; exactly the jac_c! write-set is assigned (explicit zeros of
  * the identity blocks included), every other entry is left untouched.  `b` selects the problem. */

@@ -32,11 +32,12 @@ mutable struct HybridNLPHIP <: MOI.AbstractNLPEvaluator
     lb::Vector{Float64}; ub::Vector{Float64}      # fields solve() reads (src/moi.jl:69)
     n_nlp::Int; m_nlp::Int
     use_sparse_jacobian::Bool
+    exact_hessian::Bool                           # offer :Hess (the reference offers none: Ipopt falls back to L-BFGS)
 end
 
 # HybridNLP(model, obj, init_mode, k_trans, N, x0, xf) -- src/nlp.jl:34-37.  `obj` is the reference's
 # Vector{QuadraticCost}; it is flattened to the 41-double records [Q(15) R(5) q(15) r(5) c].
-function HybridNLPHIP(model, obj, init_mode, k_trans, N, x0, xf; use_sparse_jacobian=false, device=0)
+function HybridNLPHIP(model, obj, init_mode, k_trans, N, x0, xf; use_sparse_jacobian=false, device=0, exact_hessian=false)
     # a sparse solve wants only the entries that can be non-zero; the dense callback needs neither format in particular
     jac_format = use_sparse_jacobian ? 1 : 0
     cost = vcat([[diag(o.Q); diag(o.R); o.q; o.r; o.c] for o in obj]...)
@@ -51,7 +52,7 @@ function HybridNLPHIP(model, obj, init_mode, k_trans, N, x0, xf; use_sparse_jaco
     qln_check(ccall((:qln_problem_dims, LIBQLN), Cint, (Ptr{Cvoid}, Int32, Ref{Int32}, Ref{Int32}), h[], 0, m, nnz))
     lb = zeros(m[]); ub = zeros(m[])
     qln_check(ccall((:qln_constraint_bounds, LIBQLN), Cint, (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}), h[], 0, lb, ub))
-    nlp = HybridNLPHIP(h[], N, k_trans, init_mode, lb, ub, 20N - 5, m[], use_sparse_jacobian)
+    nlp = HybridNLPHIP(h[], N, k_trans, init_mode, lb, ub, 20N - 5, m[], use_sparse_jacobian, exact_hessian)
     finalizer(p -> ccall((:qln_destroy, LIBQLN), Cint, (Ptr{Cvoid},), p.handle), nlp)
 end
 
@@ -79,7 +80,8 @@ function MOI.eval_constraint_jacobian(prob::HybridNLPHIP, vec, x)       # src/mo
     end
     return nothing
 end
-MOI.features_available(prob::HybridNLPHIP) = [:Grad, :Jac]              # src/moi.jl:26-28
+# src/moi.jl:26-28 offers [:Grad, :Jac]; with exact_hessian=true :Hess too, and Ipopt stops forcing L-BFGS by itself
+MOI.features_available(prob::HybridNLPHIP) = prob.exact_hessian ? [:Grad, :Jac, :Hess] : [:Grad, :Jac]
 MOI.initialize(prob::HybridNLPHIP, features) = nothing                  # src/moi.jl:30
 function MOI.jacobian_structure(nlp::HybridNLPHIP)                      # src/moi.jl:31-33
     if !nlp.use_sparse_jacobian
@@ -90,6 +92,22 @@ function MOI.jacobian_structure(nlp::HybridNLPHIP)                      # src/mo
     rows = zeros(Int32, nnz[]); cols = zeros(Int32, nnz[])
     qln_check(ccall((:qln_jacobian_structure, LIBQLN), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int32}), nlp.handle, 0, rows, cols))
     return [(Int(r) + 1, Int(c) + 1) for (r, c) in zip(rows, cols)]     # the ABI is 0-based
+end
+
+# The Hessian of the Lagrangian, sigma d2 eval_f + sum_i mu_i d2 c_i, as the lower triangle of a block-diagonal pattern
+# (55 entries per step block, 15 for x_N).  Its objective part is the Hessian of eval_f, the function -- not the Jacobian
+# of grad_f!, which has no d(h l)/dh (quirk Q2) and is not symmetric.
+function MOI.hessian_lagrangian_structure(nlp::HybridNLPHIP)
+    nnz = 55 * (nlp.N - 1) + 15
+    rows = zeros(Int32, nnz); cols = zeros(Int32, nnz)
+    qln_check(ccall((:qln_hessian_structure, LIBQLN), Cint, (Int32, Ptr{Int32}, Ptr{Int32}), nlp.N, rows, cols))
+    return [(Int(r) + 1, Int(c) + 1) for (r, c) in zip(rows, cols)]     # the ABI is 0-based
+end
+function MOI.eval_hessian_lagrangian(prob::HybridNLPHIP, H, x, sigma, mu)
+    s = Ref{Cdouble}(sigma)
+    qln_check(ccall((:qln_eval_hessian_lagrangian_host, LIBQLN), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, x, s, mu, H))
+    return nothing
 end
 
 # ---- beyond the evaluator: the same NLP solved on the GPU in place of `solve(Z0, nlp)` (src/moi.jl:46-103) -------------

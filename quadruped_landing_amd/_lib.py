@@ -23,6 +23,7 @@ QLN_JAC_FORMAT_STRUCTURAL = 1
 
 NX, NU, NZ, COST_STRIDE = 15, 5, 20, 41
 GN_INFO_STRIDE = 8
+HESS_STEP_NNZ, HESS_TERM_NNZ = 55, 15
 
 
 class QlnModel(C.Structure):
@@ -135,6 +136,10 @@ SIGNATURES = {
     "qln_jacobian_init_constants": (C.c_int, [_vp, _dp]),
     "qln_eval_constraint_jvp": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_eval_constraint_vjp": (C.c_int, [_vp, _dp, _dp, _dp]),
+    "qln_hessian_layout": (C.c_int, [C.POINTER(QlnBatchDesc), _i32p, _i64p]),
+    "qln_hessian_structure": (C.c_int, [C.c_int32, _i32p, _i32p]),
+    "qln_eval_hessian_lagrangian": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
+    "qln_eval_hessian_lagrangian_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     "qln_gauss_newton_step": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, C.c_double, _dp, _dp, _dp]),
     "qln_eval_kinematic_constraint": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_kinematic_bounds": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

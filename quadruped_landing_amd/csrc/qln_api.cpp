@@ -18,6 +18,7 @@
 
 #include "../../include/qln_evaluator.h"
 #include "qln_device.h"
+#include "qln_hessian.h"
 
 namespace {
 
@@ -36,6 +37,10 @@ int fail(int code, const std::string& msg) {
     } while (0)
 
 int64_t round_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+
+// Lagrangian Hessian: 55 values per step block, 15 for the terminal diagonal; segments h_stride apart
+int32_t hessian_nnz(int32_t N) { return QLN_HESS_STEP_NNZ * (N - 1) + QLN_HESS_TERM_NNZ; }
+int64_t hessian_stride(int32_t N, int32_t align) { return round_up(hessian_nnz(N), align ? align : 16); }
 
 // Whether a placed buffer's virtual range is handed back (hipMemAddressFree) when the buffer is released.
 // It is NOT: on this stack (ROCm 7.2 user space, the pool's host driver) a virtual address that has been unmapped
@@ -94,6 +99,10 @@ struct qln_handle {
     double* s_vals = nullptr;
     double* s_f = nullptr;
     double* s_grad = nullptr;
+    double* s_sigma = nullptr;  // Lagrangian Hessian (qln_eval_hessian_lagrangian_host): sigma and the multipliers in,
+    double* s_mu = nullptr;     // the values out
+    double* s_hvals = nullptr;
+    int64_t h_stride = 0;       // doubles between consecutive problems' Hessian segments (qln_hessian_layout)
     std::vector<double> h_vals_one;
     // zero-copy MOI mode (small batches): pinned host buffers mapped into the device's address space -- the kernels read
     // Z from and write their results to host memory directly, so a callback is one launch and one synchronisation
@@ -256,6 +265,7 @@ int qln_create(const qln_batch_desc* d, int device, qln_handle** out) {
     h->j_off = std::move(j_off);
     h->dims = lay;
     qln_dims& D = h->dims;
+    h->h_stride = hessian_stride(d->N, d->align);
 
     int rc = QLN_OK;
     auto bail = [&](int code) {
@@ -340,7 +350,8 @@ int qln_destroy(qln_handle* h) {
     }
     for (qln_handle::Mapped* m : {&h->m_Z, &h->m_c, &h->m_vals, &h->m_f, &h->m_grad})
         if (m->host) (void)hipHostFree(m->host);
-    void* bufs[] = {h->d_desc, h->d_bnd, h->d_cost, h->s_Z, h->s_c, h->s_vals, h->s_f, h->s_grad, h->solve_scratch};
+    void* bufs[] = {h->d_desc, h->d_bnd, h->d_cost, h->s_Z, h->s_c, h->s_vals, h->s_f, h->s_grad, h->solve_scratch,
+                    h->s_sigma, h->s_mu, h->s_hvals};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     delete h;
@@ -850,6 +861,56 @@ int qln_initial_guess(qln_handle* h, double* Z) {
     return QLN_OK;
 }
 
+// ------------------------------------------------------------------ Lagrangian Hessian
+
+int qln_hessian_layout(const qln_batch_desc* d, int32_t* nnz, int64_t* h_stride) {
+    if (!d || !nnz || !h_stride) return fail(QLN_ERR_INVALID_ARGUMENT, "qln_hessian_layout: null argument");
+    if (d->N < 2) return fail(QLN_ERR_INVALID_ARGUMENT, "qln_hessian_layout: N must be >= 2");
+    if (d->N > 50000000 / 20) return fail(QLN_ERR_INVALID_ARGUMENT, "qln_hessian_layout: N too large for 32-bit indices");
+    if (d->align < 0) return fail(QLN_ERR_INVALID_ARGUMENT, "qln_hessian_layout: align must be >= 1");
+    *nnz = hessian_nnz(d->N);
+    *h_stride = hessian_stride(d->N, d->align);
+    return QLN_OK;
+}
+
+int qln_hessian_structure(int32_t N, int32_t* rows, int32_t* cols) {
+    if (N < 2) return fail(QLN_ERR_INVALID_ARGUMENT, "qln_hessian_structure: N must be >= 2");
+    if (N > 50000000 / 20) return fail(QLN_ERR_INVALID_ARGUMENT, "qln_hessian_structure: N too large for 32-bit indices");
+    if (!rows || !cols) return fail(QLN_ERR_INVALID_ARGUMENT, "qln_hessian_structure: null pointer");
+    int32_t rb[QLN_HESS_STEP_NNZ], cb[QLN_HESS_STEP_NNZ];
+    int n = 0;
+    for (int c = 0; c < 20; ++c)
+        for (int r = c; r < 20; ++r)
+            if (qln::hess_entry_present(r, c)) {
+                rb[n] = r;
+                cb[n] = c;
+                ++n;
+            }
+    int64_t at = 0;
+    for (int32_t k = 0; k < N - 1; ++k)
+        for (int e = 0; e < QLN_HESS_STEP_NNZ; ++e, ++at) {
+            rows[at] = 20 * k + rb[e];
+            cols[at] = 20 * k + cb[e];
+        }
+    for (int i = 0; i < QLN_HESS_TERM_NNZ; ++i, ++at) rows[at] = cols[at] = 20 * (N - 1) + i;
+    return QLN_OK;
+}
+
+static int check_hessian_args(const qln_handle* h, const double* Z, const double* mu, const double* hvals, const char* who) {
+    if (int rc = check_handle(h)) return rc;
+    if (int rc = check_cost(h)) return rc;
+    if (!Z || !mu || !hvals) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    if (reinterpret_cast<uintptr_t>(hvals) % 8) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": hvals must be 8-byte aligned");
+    return QLN_OK;
+}
+
+int qln_eval_hessian_lagrangian(qln_handle* h, const double* Z, const double* sigma, const double* mu, double* hvals) {
+    if (int rc = check_hessian_args(h, Z, mu, hvals, "qln_eval_hessian_lagrangian")) return rc;
+    if (int rc = bind_device(h)) return rc;
+    QLN_HIP(qln::launch_hessian_lagrangian(h->p, Z, sigma, mu, hvals, h->h_stride, h->stream));
+    return QLN_OK;
+}
+
 // ------------------------------------------------------------------ host-pointer (MOI) mode
 
 int qln_eval_objective_host(qln_handle* h, const double* Z, double* f) {
@@ -941,6 +1002,26 @@ int qln_eval_constraint_jacobian_host(qln_handle* h, const double* Z, double* va
     QLN_HIP(qln::launch_constraint_jacobian(h->p, 0, h->p.B, h->s_Z, nullptr, h->s_vals, QLN_JAC_WRITE_CONSTANTS,
                                             h->stream));
     QLN_HIP(hipMemcpyAsync(vals, h->s_vals, h->dims.j_total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QLN_HIP(hipStreamSynchronize(h->stream));
+    return QLN_OK;
+}
+
+int qln_eval_hessian_lagrangian_host(qln_handle* h, const double* Z, const double* sigma, const double* mu, double* hvals) {
+    if (int rc = check_hessian_args(h, Z, mu, hvals, "qln_eval_hessian_lagrangian_host")) return rc;
+    if (int rc = bind_device(h)) return rc;
+    // no padding behind the last problem: for B == 1 the caller's buffer is exactly the nnz of the structure
+    const int64_t total = (int64_t)(h->dims.B - 1) * h->h_stride + hessian_nnz(h->dims.N);
+    if (int rc = ensure(&h->s_Z, h->dims.z_total)) return rc;
+    if (int rc = ensure(&h->s_mu, h->dims.c_total)) return rc;
+    if (int rc = ensure(&h->s_hvals, total)) return rc;
+    if (sigma)
+        if (int rc = ensure(&h->s_sigma, h->dims.B)) return rc;
+    QLN_HIP(hipMemcpyAsync(h->s_Z, Z, h->dims.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    QLN_HIP(hipMemcpyAsync(h->s_mu, mu, h->dims.c_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (sigma) QLN_HIP(hipMemcpyAsync(h->s_sigma, sigma, h->dims.B * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    QLN_HIP(qln::launch_hessian_lagrangian(h->p, h->s_Z, sigma ? h->s_sigma : nullptr, h->s_mu, h->s_hvals, h->h_stride,
+                                           h->stream));
+    QLN_HIP(hipMemcpyAsync(hvals, h->s_hvals, total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     QLN_HIP(hipStreamSynchronize(h->stream));
     return QLN_OK;
 }

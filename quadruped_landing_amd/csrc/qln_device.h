@@ -144,6 +144,9 @@ hipError_t launch_constraint_violation(const BatchParams& p, const double* c, do
 // y = J(Z) v and g = J(Z)^T lam with the constraint Jacobian re-derived in registers (qln_solver_kernels.hip)
 hipError_t launch_constraint_jvp(const BatchParams& p, const double* Z, const double* v, double* y, hipStream_t stream);
 hipError_t launch_constraint_vjp(const BatchParams& p, const double* Z, const double* lam, double* g, hipStream_t stream);
+// H = sigma d2 f + sum mu_i d2 c_i, the 55 + 15 values per knot of qln_hessian.h's pattern (qln_hessian_kernels.hip)
+hipError_t launch_hessian_lagrangian(const BatchParams& p, const double* Z, const double* sigma, const double* mu, double* hvals,
+                                     int64_t h_stride, hipStream_t stream);
 // batched Gauss-Newton step on the constraint violation, CGLS per problem in LDS (qln_solver_kernels.hip)
 size_t gauss_newton_lds_bytes(int32_t N);
 hipError_t launch_gauss_newton_step(const BatchParams& p, const double* Z, const double* c, double* dZ, int max_iters,

@@ -56,7 +56,9 @@ def eval_constraint_jacobian(prob, vec, x, b: int = 0):
 
 
 def features_available(prob):
-    """src/moi.jl:26-28"""
+    """src/moi.jl:26-28; "Hess" only for a problem built with exact_hessian=True (the reference offers none)."""
+    if getattr(prob, "exact_hessian", False):
+        return ["Grad", "Jac", "Hess"]
     return ["Grad", "Jac"]
 
 
@@ -78,3 +80,22 @@ def sparse_jacobian_structure(prob, b: int = 0):
     what `use_sparse_jacobian=true` (src/nlp.jl:35,75-76) was meant to hand to Ipopt."""
     rows, cols = prob.jacobian_structure(b)
     return list(zip((rows + 1).tolist(), (cols + 1).tolist()))
+
+
+def hessian_lagrangian_structure(prob):
+    """MOI.hessian_lagrangian_structure: 1-based (row, col) pairs, row >= col, of one problem's Lagrangian Hessian in the
+    order eval_hessian_lagrangian fills them (block-diagonal over knots, 55 per step block, 15 for x_N)."""
+    rows, cols = prob.hessian_structure()
+    return list(zip((rows + 1).tolist(), (cols + 1).tolist()))
+
+
+def eval_hessian_lagrangian(prob, H, x, sigma, mu):
+    """MOI.eval_hessian_lagrangian (in place): H[j] = value of entry j of hessian_lagrangian_structure for
+    sigma * d2 f(x) + sum_i mu[i] d2 c_i(x).  For a batch, x / mu / H hold every problem (mu in the layout of c, H problem b
+    at b * h_stride) and sigma may be a scalar or a (B,) array."""
+    out = np.asarray(H).reshape(-1)
+    vals = prob.hess_lag_host(x, np.broadcast_to(np.asarray(sigma, dtype=np.float64), (prob.B,)), mu)
+    if out.size < vals.size:
+        raise ValueError(f"H has {out.size} entries, expected {vals.size}")
+    out[: vals.size] = vals
+    return None

@@ -81,6 +81,16 @@ def unpackZ(N: int, Z):
 # ----------------------------------------------------------------------------- evaluator
 
 
+def hessian_structure(N: int):
+    """0-based (rows, cols), row >= col, of the Lagrangian Hessian of one problem with N knots (qln_hessian_structure):
+    N-1 step blocks of 55 entries, column-major inside a block, then the 15 terminal diagonal entries.  No device."""
+    n = _lib.HESS_STEP_NNZ * (int(N) - 1) + _lib.HESS_TERM_NNZ
+    rows, cols = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    ip = C.POINTER(C.c_int32)
+    _lib.check(_lib.lib().qln_hessian_structure(int(N), rows.ctypes.data_as(ip), cols.ctypes.data_as(ip)))
+    return rows, cols
+
+
 def _torch():
     import torch
 
@@ -124,8 +134,11 @@ class HybridNLP:
     """
 
     def __init__(self, model: PlanarQuadruped, obj, init_mode, k_trans, N: int, x0, xf, *,
-                 device: int = 0, z_stride: int = 0, align: int = 16, stream=None, jac_format: str = "dense_blocks"):
+                 device: int = 0, z_stride: int = 0, align: int = 16, stream=None, jac_format: str = "dense_blocks",
+                 exact_hessian: bool = False):
         self.model = model
+        # opt-in: offer the exact Lagrangian Hessian (moi.features_available then lists "Hess")
+        self.exact_hessian = bool(exact_hessian)
         if jac_format not in JAC_FORMATS:
             raise ValueError(f"jac_format must be one of {sorted(JAC_FORMATS)}")
         self.jac_format = jac_format
@@ -173,6 +186,10 @@ class HybridNLP:
         self.j_off = np.zeros(B, dtype=np.int64)
         lp = C.POINTER(C.c_int64)
         _lib.check(L.qln_get_offsets(self._h, self.c_off.ctypes.data_as(lp), self.j_off.ctypes.data_as(lp)))
+        hn, hs = C.c_int32(), C.c_int64()
+        _lib.check(L.qln_hessian_layout(C.byref(d), C.byref(hn), C.byref(hs)))
+        self.h_nnz, self.h_stride = hn.value, hs.value
+        self.h_total = (B - 1) * self.h_stride + self.h_nnz  # no padding behind the last problem
         if stream is not None:
             self.set_stream(stream)
 
@@ -423,6 +440,46 @@ class HybridNLP:
         self._check(out, self.dims.z_total, "out")
         _lib.check(_lib.lib().qln_eval_constraint_vjp(self._h, Z.data_ptr(), lam.data_ptr(), out.data_ptr()))
         return out
+
+    # -- Lagrangian Hessian ---------------------------------------------------------------------
+    def hessian_structure(self):
+        """0-based (rows, cols), row >= col, of one problem's Hessian segment in the order of its values."""
+        return hessian_structure(self.N)
+
+    def new_hvals(self):
+        return _torch().zeros(self.h_total, dtype=_torch().float64, device=self._dev())
+
+    def hess_lag(self, Z, sigma, mu, out=None):
+        """Lower triangle of sigma_b d2 f + sum_i mu_i d2 c_i for every problem (problem b at b * h_stride).  Z, mu (layout
+        of c) and out are device tensors; sigma a (B,) device tensor or None (1.0 for every problem)."""
+        out = self.new_hvals() if out is None else out
+        sp = None if sigma is None else self._check(sigma, self.B, "sigma")
+        _lib.check(_lib.lib().qln_eval_hessian_lagrangian(
+            self._h, self._check(Z, self.dims.z_total, "Z"), sp, self._check(mu, self.dims.c_total, "mu"),
+            self._check(out, self.h_total, "hvals")))
+        return out
+
+    def hess_lag_host(self, Z, sigma, mu):
+        """The same with host arrays (MOI mode): returns an (h_total,) numpy array."""
+        Z = self._host_Z(Z)
+        mu = np.ascontiguousarray(np.asarray(mu, dtype=np.float64).reshape(-1))
+        if mu.size != self.dims.c_total:
+            raise ValueError(f"mu has {mu.size} entries, expected {self.dims.c_total}")
+        sp = None
+        if sigma is not None:
+            sigma = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (self.B,)))
+            sp = sigma.ctypes.data
+        out = np.zeros(self.h_total)
+        _lib.check(_lib.lib().qln_eval_hessian_lagrangian_host(self._h, Z.ctypes.data, sp, mu.ctypes.data, out.ctypes.data))
+        return out
+
+    def split_hvals(self, hvals):
+        """(h_total,) values -> (step blocks (B, N-1, 55), terminal diagonals (B, 15)) as numpy arrays."""
+        h = hvals.detach().cpu().numpy() if hasattr(hvals, "detach") else np.asarray(hvals)
+        h = h.reshape(-1)
+        seg = np.stack([h[b * self.h_stride: b * self.h_stride + self.h_nnz] for b in range(self.B)])
+        steps = seg[:, : _lib.HESS_STEP_NNZ * (self.N - 1)].reshape(self.B, self.N - 1, _lib.HESS_STEP_NNZ)
+        return steps, seg[:, _lib.HESS_STEP_NNZ * (self.N - 1):]
 
     def gauss_newton_step(self, Z, c, out=None, max_iters: int = 200, rel_tol: float = 1e-10, radius=None,
                           col_scale=None, info=None):
