@@ -204,6 +204,23 @@ int qln_hessian_layout(const qln_batch_desc* desc, int32_t* nnz, int64_t* h_stri
 int qln_hessian_structure(int32_t N, int32_t* rows, int32_t* cols);
 /* device pointers, stream-ordered; sigma: [B] or NULL (= 1.0 for every problem); mu: layout of c.  Needs a cost table. */
 int qln_eval_hessian_lagrangian(qln_handle* h, const double* Z, const double* sigma, const double* mu, double* hvals);
+/* The Hessian-vector product of the Lagrangian -- the matrix-free second-order callback of an MOI.AbstractNLPEvaluator
+ * (:HessVec, eval_hessian_lagrangian_product), which Newton-CG, trust-region Steihaug and matrix-free SQP ask for.  For
+ * problem b, with v and y in the layout of Z (z_stride), a scalar sigma_b and multipliers mu in the layout of c:
+ *
+ *   y_b = (sigma_b d2 eval_f(Z_b) + sum_i mu_i d2 c_i(Z_b)) v_b
+ *
+ * The operator is the one qln_eval_hessian_lagrangian returns, with the same conventions: the objective part is the
+ * Hessian of eval_f, the FUNCTION (quirk Q2), the jump mask (quirk Q1) zeroes the multipliers of the transition knot's
+ * masked rows, the clearance curvature takes quirk Q3's branch, and only the dynamics and clearance rows of mu are read.
+ * Nothing is stored: each knot's 55 step-block values are formed in registers and contracted with v there.
+ *   Step block k acts on z_k = Z[20(k-1) .. 20(k-1)+19] (y's entries of the same range); the terminal block is the
+ *   15-entry diagonal on x_N = Z[20(N-1) .. 20(N-1)+14].
+ * Every entry of y below n_nlp is written (an exact zero where H's row is empty for this v); entries from n_nlp to
+ * z_stride are never written, and the entries of Z and v there are never read.
+ * Device pointers, stream-ordered; sigma: [B] or NULL (= 1.0 for every problem).  Needs a cost table. */
+int qln_eval_hessian_lagrangian_product(qln_handle* h, const double* Z, const double* sigma, const double* mu,
+                                        const double* v, double* y);
 /* One Gauss-Newton step on the constraint violation for every problem of the batch (the solver
  * iteration on the GPU, consuming the Jacobian where it is produced).  For problem b
  *     dZ_b = D x,  x = the minimum-norm minimiser of || A D x + rho ||_2   (subject to ||x|| <= radius[b] if given),
@@ -365,6 +382,13 @@ int qln_eval_constraint_host(qln_handle* h, const double* Z, double* c);
 int qln_eval_constraint_jacobian_host(qln_handle* h, const double* Z, double* vals);
 /* MOI mode of qln_eval_hessian_lagrangian: host pointers, synchronous, same layouts (staged through device memory) */
 int qln_eval_hessian_lagrangian_host(qln_handle* h, const double* Z, const double* sigma, const double* mu, double* hvals);
+/* MOI mode of qln_eval_hessian_lagrangian_product (:HessVec) and of qln_eval_constraint_jvp / _vjp (:JacVec,
+ * eval_constraint_jacobian_product / _transpose_product): host pointers, synchronous, same layouts.  The padding of an
+ * output's layout (past n_nlp, between problems of c) comes back as zeros. */
+int qln_eval_hessian_lagrangian_product_host(qln_handle* h, const double* Z, const double* sigma, const double* mu,
+                                             const double* v, double* y);
+int qln_eval_constraint_jvp_host(qln_handle* h, const double* Z, const double* v, double* y);
+int qln_eval_constraint_vjp_host(qln_handle* h, const double* Z, const double* lam, double* g);
 /* Reference-compatible dense Jacobian of ONE problem (src/moi.jl:15-24): `jac` is a host,
  * column-major m_nlp x n_nlp buffer; exactly the jac_c! write-set is assigned (explicit zeros of
  * the identity blocks included), every other entry is left untouched.  `b` selects the problem. */

@@ -33,11 +33,13 @@ mutable struct HybridNLPHIP <: MOI.AbstractNLPEvaluator
     n_nlp::Int; m_nlp::Int
     use_sparse_jacobian::Bool
     exact_hessian::Bool                           # offer :Hess (the reference offers none: Ipopt falls back to L-BFGS)
+    matrix_free::Bool                             # offer :JacVec and :HessVec (products, nothing stored)
 end
 
 # HybridNLP(model, obj, init_mode, k_trans, N, x0, xf) -- src/nlp.jl:34-37.  `obj` is the reference's
 # Vector{QuadraticCost}; it is flattened to the 41-double records [Q(15) R(5) q(15) r(5) c].
-function HybridNLPHIP(model, obj, init_mode, k_trans, N, x0, xf; use_sparse_jacobian=false, device=0, exact_hessian=false)
+function HybridNLPHIP(model, obj, init_mode, k_trans, N, x0, xf; use_sparse_jacobian=false, device=0, exact_hessian=false,
+                      matrix_free=false)
     # a sparse solve wants only the entries that can be non-zero; the dense callback needs neither format in particular
     jac_format = use_sparse_jacobian ? 1 : 0
     cost = vcat([[diag(o.Q); diag(o.R); o.q; o.r; o.c] for o in obj]...)
@@ -52,7 +54,7 @@ function HybridNLPHIP(model, obj, init_mode, k_trans, N, x0, xf; use_sparse_jaco
     qln_check(ccall((:qln_problem_dims, LIBQLN), Cint, (Ptr{Cvoid}, Int32, Ref{Int32}, Ref{Int32}), h[], 0, m, nnz))
     lb = zeros(m[]); ub = zeros(m[])
     qln_check(ccall((:qln_constraint_bounds, LIBQLN), Cint, (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}), h[], 0, lb, ub))
-    nlp = HybridNLPHIP(h[], N, k_trans, init_mode, lb, ub, 20N - 5, m[], use_sparse_jacobian, exact_hessian)
+    nlp = HybridNLPHIP(h[], N, k_trans, init_mode, lb, ub, 20N - 5, m[], use_sparse_jacobian, exact_hessian, matrix_free)
     finalizer(p -> ccall((:qln_destroy, LIBQLN), Cint, (Ptr{Cvoid},), p.handle), nlp)
 end
 
@@ -81,7 +83,11 @@ function MOI.eval_constraint_jacobian(prob::HybridNLPHIP, vec, x)       # src/mo
     return nothing
 end
 # src/moi.jl:26-28 offers [:Grad, :Jac]; with exact_hessian=true :Hess too, and Ipopt stops forcing L-BFGS by itself
-MOI.features_available(prob::HybridNLPHIP) = prob.exact_hessian ? [:Grad, :Jac, :Hess] : [:Grad, :Jac]
+# and with matrix_free=true :JacVec, :HessVec after them
+function MOI.features_available(prob::HybridNLPHIP)
+    feats = prob.exact_hessian ? [:Grad, :Jac, :Hess] : [:Grad, :Jac]
+    return prob.matrix_free ? vcat(feats, [:JacVec, :HessVec]) : feats
+end
 MOI.initialize(prob::HybridNLPHIP, features) = nothing                  # src/moi.jl:30
 function MOI.jacobian_structure(nlp::HybridNLPHIP)                      # src/moi.jl:31-33
     if !nlp.use_sparse_jacobian
@@ -107,6 +113,25 @@ function MOI.eval_hessian_lagrangian(prob::HybridNLPHIP, H, x, sigma, mu)
     s = Ref{Cdouble}(sigma)
     qln_check(ccall((:qln_eval_hessian_lagrangian_host, LIBQLN), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
                     prob.handle, x, s, mu, H))
+    return nothing
+end
+
+# Matrix-free products (:JacVec, :HessVec): the Jacobian and the Hessian of the Lagrangian are re-derived per knot on the
+# GPU and contracted there, never stored.  y = J(x) w (m_nlp), y = J(x)' w (n_nlp), h = (sigma d2 f + sum mu_i d2 c_i) v.
+function MOI.eval_constraint_jacobian_product(prob::HybridNLPHIP, y, x, w)
+    qln_check(ccall((:qln_eval_constraint_jvp_host, LIBQLN), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, x, w, y))
+    return nothing
+end
+function MOI.eval_constraint_jacobian_transpose_product(prob::HybridNLPHIP, y, x, w)
+    qln_check(ccall((:qln_eval_constraint_vjp_host, LIBQLN), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, x, w, y))
+    return nothing
+end
+function MOI.eval_hessian_lagrangian_product(prob::HybridNLPHIP, h, x, v, sigma, mu)
+    s = Ref{Cdouble}(sigma)
+    qln_check(ccall((:qln_eval_hessian_lagrangian_product_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}), prob.handle, x, s, mu, v, h))
     return nothing
 end
 

@@ -140,6 +140,10 @@ SIGNATURES = {
     "qln_hessian_structure": (C.c_int, [C.c_int32, _i32p, _i32p]),
     "qln_eval_hessian_lagrangian": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     "qln_eval_hessian_lagrangian_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
+    "qln_eval_hessian_lagrangian_product": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp]),
+    "qln_eval_hessian_lagrangian_product_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp]),
+    "qln_eval_constraint_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp]),
+    "qln_eval_constraint_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_gauss_newton_step": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, C.c_double, _dp, _dp, _dp]),
     "qln_eval_kinematic_constraint": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_kinematic_bounds": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -103,6 +103,8 @@ struct qln_handle {
     double* s_mu = nullptr;     // the values out
     double* s_hvals = nullptr;
     int64_t h_stride = 0;       // doubles between consecutive problems' Hessian segments (qln_hessian_layout)
+    double* s_v = nullptr;      // products (qln_eval_*_product_host, qln_eval_constraint_jvp/vjp_host): the vector in the
+    double* s_zout = nullptr;   // layout of Z, a result in the layout of Z
     std::vector<double> h_vals_one;
     // zero-copy MOI mode (small batches): pinned host buffers mapped into the device's address space -- the kernels read
     // Z from and write their results to host memory directly, so a callback is one launch and one synchronisation
@@ -111,6 +113,7 @@ struct qln_handle {
         double* dev = nullptr;
     };
     Mapped m_Z, m_c, m_vals, m_f, m_grad;
+    Mapped m_v, m_mu, m_sigma, m_zout;  // the products' inputs (v, mu / lam, sigma) and their result in the layout of Z
     bool zero_copy = false;
     // dense MOI scatter: per problem, where each value of the vals segment goes in the column-major matrix, and the
     // write-set's explicit zeros (built on first use)
@@ -348,10 +351,10 @@ int qln_destroy(qln_handle* h) {
         for (auto& p : h->placed)
             if (int r = release_placed(p); r != QLN_OK && rc == QLN_OK) rc = r;
     }
-    for (qln_handle::Mapped* m : {&h->m_Z, &h->m_c, &h->m_vals, &h->m_f, &h->m_grad})
+    for (qln_handle::Mapped* m : {&h->m_Z, &h->m_c, &h->m_vals, &h->m_f, &h->m_grad, &h->m_v, &h->m_mu, &h->m_sigma, &h->m_zout})
         if (m->host) (void)hipHostFree(m->host);
     void* bufs[] = {h->d_desc, h->d_bnd, h->d_cost, h->s_Z, h->s_c, h->s_vals, h->s_f, h->s_grad, h->solve_scratch,
-                    h->s_sigma, h->s_mu, h->s_hvals};
+                    h->s_sigma, h->s_mu, h->s_hvals, h->s_v, h->s_zout};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     delete h;
@@ -911,6 +914,22 @@ int qln_eval_hessian_lagrangian(qln_handle* h, const double* Z, const double* si
     return QLN_OK;
 }
 
+static int check_hessian_product_args(const qln_handle* h, const double* Z, const double* mu, const double* v, const double* y,
+                                      const char* who) {
+    if (int rc = check_handle(h)) return rc;
+    if (int rc = check_cost(h)) return rc;
+    if (!Z || !mu || !v || !y) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    return QLN_OK;
+}
+
+int qln_eval_hessian_lagrangian_product(qln_handle* h, const double* Z, const double* sigma, const double* mu, const double* v,
+                                        double* y) {
+    if (int rc = check_hessian_product_args(h, Z, mu, v, y, "qln_eval_hessian_lagrangian_product")) return rc;
+    if (int rc = bind_device(h)) return rc;
+    QLN_HIP(qln::launch_hessian_lagrangian_product(h->p, Z, sigma, mu, v, y, h->stream));
+    return QLN_OK;
+}
+
 // ------------------------------------------------------------------ host-pointer (MOI) mode
 
 int qln_eval_objective_host(qln_handle* h, const double* Z, double* f) {
@@ -1022,6 +1041,101 @@ int qln_eval_hessian_lagrangian_host(qln_handle* h, const double* Z, const doubl
     QLN_HIP(qln::launch_hessian_lagrangian(h->p, h->s_Z, sigma ? h->s_sigma : nullptr, h->s_mu, h->s_hvals, h->h_stride,
                                            h->stream));
     QLN_HIP(hipMemcpyAsync(hvals, h->s_hvals, total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QLN_HIP(hipStreamSynchronize(h->stream));
+    return QLN_OK;
+}
+
+// The products in MOI mode: every input is copied into a mapped pinned buffer (zero_copy) or staged in device memory, one
+// launch, the result copied back.  The padding of an output's layout is never written by the kernels: zeros.
+int qln_eval_hessian_lagrangian_product_host(qln_handle* h, const double* Z, const double* sigma, const double* mu,
+                                             const double* v, double* y) {
+    if (int rc = check_hessian_product_args(h, Z, mu, v, y, "qln_eval_hessian_lagrangian_product_host")) return rc;
+    if (int rc = bind_device(h)) return rc;
+    const qln_dims& D = h->dims;
+    if (h->zero_copy) {
+        if (int rc = ensure_mapped(&h->m_Z, D.z_total)) return rc;
+        if (int rc = ensure_mapped(&h->m_v, D.z_total)) return rc;
+        if (int rc = ensure_mapped(&h->m_mu, D.c_total)) return rc;
+        if (int rc = ensure_mapped(&h->m_zout, D.z_total)) return rc;
+        if (sigma)
+            if (int rc = ensure_mapped(&h->m_sigma, D.B)) return rc;
+        std::memcpy(h->m_Z.host, Z, D.z_total * sizeof(double));
+        std::memcpy(h->m_v.host, v, D.z_total * sizeof(double));
+        std::memcpy(h->m_mu.host, mu, D.c_total * sizeof(double));
+        if (sigma) std::memcpy(h->m_sigma.host, sigma, D.B * sizeof(double));
+        QLN_HIP(qln::launch_hessian_lagrangian_product(h->p, h->m_Z.dev, sigma ? h->m_sigma.dev : nullptr, h->m_mu.dev,
+                                                       h->m_v.dev, h->m_zout.dev, h->stream));
+        QLN_HIP(hipStreamSynchronize(h->stream));
+        std::memcpy(y, h->m_zout.host, D.z_total * sizeof(double));
+        return QLN_OK;
+    }
+    if (int rc = ensure(&h->s_Z, D.z_total)) return rc;
+    if (int rc = ensure(&h->s_v, D.z_total)) return rc;
+    if (int rc = ensure(&h->s_mu, D.c_total)) return rc;
+    if (int rc = ensure(&h->s_zout, D.z_total)) return rc;
+    if (sigma)
+        if (int rc = ensure(&h->s_sigma, D.B)) return rc;
+    QLN_HIP(hipMemcpyAsync(h->s_Z, Z, D.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    QLN_HIP(hipMemcpyAsync(h->s_v, v, D.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    QLN_HIP(hipMemcpyAsync(h->s_mu, mu, D.c_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (sigma) QLN_HIP(hipMemcpyAsync(h->s_sigma, sigma, D.B * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    QLN_HIP(qln::launch_hessian_lagrangian_product(h->p, h->s_Z, sigma ? h->s_sigma : nullptr, h->s_mu, h->s_v, h->s_zout,
+                                                   h->stream));
+    QLN_HIP(hipMemcpyAsync(y, h->s_zout, D.z_total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QLN_HIP(hipStreamSynchronize(h->stream));
+    return QLN_OK;
+}
+
+int qln_eval_constraint_jvp_host(qln_handle* h, const double* Z, const double* v, double* y) {
+    if (int rc = check_handle(h)) return rc;
+    if (!Z || !v || !y) return fail(QLN_ERR_INVALID_ARGUMENT, "qln_eval_constraint_jvp_host: null pointer");
+    if (int rc = bind_device(h)) return rc;
+    const qln_dims& D = h->dims;
+    if (h->zero_copy) {
+        if (int rc = ensure_mapped(&h->m_Z, D.z_total)) return rc;
+        if (int rc = ensure_mapped(&h->m_v, D.z_total)) return rc;
+        if (int rc = ensure_mapped(&h->m_c, D.c_total)) return rc;
+        std::memcpy(h->m_Z.host, Z, D.z_total * sizeof(double));
+        std::memcpy(h->m_v.host, v, D.z_total * sizeof(double));
+        QLN_HIP(qln::launch_constraint_jvp(h->p, h->m_Z.dev, h->m_v.dev, h->m_c.dev, h->stream));
+        QLN_HIP(hipStreamSynchronize(h->stream));
+        std::memcpy(y, h->m_c.host, D.c_total * sizeof(double));
+        return QLN_OK;
+    }
+    if (int rc = ensure(&h->s_Z, D.z_total)) return rc;
+    if (int rc = ensure(&h->s_v, D.z_total)) return rc;
+    if (int rc = ensure(&h->s_c, D.c_total)) return rc;
+    QLN_HIP(hipMemcpyAsync(h->s_Z, Z, D.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    QLN_HIP(hipMemcpyAsync(h->s_v, v, D.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    QLN_HIP(qln::launch_constraint_jvp(h->p, h->s_Z, h->s_v, h->s_c, h->stream));
+    QLN_HIP(hipMemcpyAsync(y, h->s_c, D.c_total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QLN_HIP(hipStreamSynchronize(h->stream));
+    return QLN_OK;
+}
+
+int qln_eval_constraint_vjp_host(qln_handle* h, const double* Z, const double* lam, double* g) {
+    if (int rc = check_handle(h)) return rc;
+    if (!Z || !lam || !g) return fail(QLN_ERR_INVALID_ARGUMENT, "qln_eval_constraint_vjp_host: null pointer");
+    if (int rc = bind_device(h)) return rc;
+    const qln_dims& D = h->dims;
+    if (h->zero_copy) {
+        if (int rc = ensure_mapped(&h->m_Z, D.z_total)) return rc;
+        if (int rc = ensure_mapped(&h->m_mu, D.c_total)) return rc;
+        if (int rc = ensure_mapped(&h->m_zout, D.z_total)) return rc;
+        std::memcpy(h->m_Z.host, Z, D.z_total * sizeof(double));
+        std::memcpy(h->m_mu.host, lam, D.c_total * sizeof(double));
+        QLN_HIP(qln::launch_constraint_vjp(h->p, h->m_Z.dev, h->m_mu.dev, h->m_zout.dev, h->stream));
+        QLN_HIP(hipStreamSynchronize(h->stream));
+        std::memcpy(g, h->m_zout.host, D.z_total * sizeof(double));
+        return QLN_OK;
+    }
+    if (int rc = ensure(&h->s_Z, D.z_total)) return rc;
+    if (int rc = ensure(&h->s_mu, D.c_total)) return rc;
+    if (int rc = ensure(&h->s_zout, D.z_total)) return rc;
+    QLN_HIP(hipMemcpyAsync(h->s_Z, Z, D.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    QLN_HIP(hipMemcpyAsync(h->s_mu, lam, D.c_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    QLN_HIP(qln::launch_constraint_vjp(h->p, h->s_Z, h->s_mu, h->s_zout, h->stream));
+    QLN_HIP(hipMemcpyAsync(g, h->s_zout, D.z_total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     QLN_HIP(hipStreamSynchronize(h->stream));
     return QLN_OK;
 }

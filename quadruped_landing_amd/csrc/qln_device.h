@@ -147,6 +147,9 @@ hipError_t launch_constraint_vjp(const BatchParams& p, const double* Z, const do
 // H = sigma d2 f + sum mu_i d2 c_i, the 55 + 15 values per knot of qln_hessian.h's pattern (qln_hessian_kernels.hip)
 hipError_t launch_hessian_lagrangian(const BatchParams& p, const double* Z, const double* sigma, const double* mu, double* hvals,
                                      int64_t h_stride, hipStream_t stream);
+// y = H v with the same H, contracted in registers (qln_hessian_kernels.hip); v and y in the layout of Z
+hipError_t launch_hessian_lagrangian_product(const BatchParams& p, const double* Z, const double* sigma, const double* mu,
+                                             const double* v, double* y, hipStream_t stream);
 // batched Gauss-Newton step on the constraint violation, CGLS per problem in LDS (qln_solver_kernels.hip)
 size_t gauss_newton_lds_bytes(int32_t N);
 hipError_t launch_gauss_newton_step(const BatchParams& p, const double* Z, const double* c, double* dZ, int max_iters,

@@ -55,11 +55,55 @@ def eval_constraint_jacobian(prob, vec, x, b: int = 0):
     return None
 
 
+def _fill_z(prob, out, z):
+    """Copy a result in the handle's Z layout into `out`: one problem's n_nlp entries per problem if that is its size,
+    the whole layout otherwise."""
+    out = np.asarray(out).reshape(-1)
+    if out.size == prob.B * prob.n_nlp:
+        out[:] = z.reshape(prob.B, prob.z_stride)[:, : prob.n_nlp].reshape(-1)
+    elif out.size == z.size:
+        out[:] = z
+    else:
+        raise ValueError(f"output has {out.size} entries; expected {prob.B * prob.n_nlp} or {z.size}")
+
+
+def _fill_c(prob, out, c):
+    out = np.asarray(out).reshape(-1)
+    if out.size != c.size:
+        raise ValueError(f"output has {out.size} entries; expected {c.size}")
+    out[:] = c
+
+
+def eval_constraint_jacobian_product(prob, y, x, w):
+    """MOI.eval_constraint_jacobian_product (in place): y = J(x) w.  For B == 1 x and w are n_nlp vectors and y the m_nlp
+    constraint rows; for a batch x and w hold every problem (n_nlp each or the handle's Z layout) and y is in the layout
+    of c.  The Jacobian is re-derived on the GPU, never stored."""
+    _fill_c(prob, y, prob.jac_vec_host(x, w))
+    return None
+
+
+def eval_constraint_jacobian_transpose_product(prob, y, x, w):
+    """MOI.eval_constraint_jacobian_transpose_product (in place): y = J(x)' w, w in the layout of c (m_nlp for B == 1),
+    y like x."""
+    _fill_z(prob, y, prob.jac_t_vec_host(x, w))
+    return None
+
+
+def eval_hessian_lagrangian_product(prob, h, x, v, sigma, mu):
+    """MOI.eval_hessian_lagrangian_product (in place): h = (sigma d2 f(x) + sum_i mu[i] d2 c_i(x)) v, the operator
+    eval_hessian_lagrangian returns, never stored.  x, v and h: n_nlp vectors for B == 1, or every problem (n_nlp each or
+    the handle's Z layout); mu in the layout of c; sigma a scalar or a (B,) array."""
+    _fill_z(prob, h, prob.hess_lag_vec_host(x, np.broadcast_to(np.asarray(sigma, dtype=np.float64), (prob.B,)), mu, v))
+    return None
+
+
 def features_available(prob):
-    """src/moi.jl:26-28; "Hess" only for a problem built with exact_hessian=True (the reference offers none)."""
-    if getattr(prob, "exact_hessian", False):
-        return ["Grad", "Jac", "Hess"]
-    return ["Grad", "Jac"]
+    """src/moi.jl:26-28; "Hess" only for a problem built with exact_hessian=True (the reference offers none), and
+    "JacVec", "HessVec" after them only for one built with matrix_free=True."""
+    feats = ["Grad", "Jac", "Hess"] if getattr(prob, "exact_hessian", False) else ["Grad", "Jac"]
+    if getattr(prob, "matrix_free", False):
+        feats += ["JacVec", "HessVec"]
+    return feats
 
 
 def initialize(prob, features):

@@ -135,10 +135,12 @@ class HybridNLP:
 
     def __init__(self, model: PlanarQuadruped, obj, init_mode, k_trans, N: int, x0, xf, *,
                  device: int = 0, z_stride: int = 0, align: int = 16, stream=None, jac_format: str = "dense_blocks",
-                 exact_hessian: bool = False):
+                 exact_hessian: bool = False, matrix_free: bool = False):
         self.model = model
         # opt-in: offer the exact Lagrangian Hessian (moi.features_available then lists "Hess")
         self.exact_hessian = bool(exact_hessian)
+        # opt-in: offer the Jacobian and Hessian-of-the-Lagrangian products (moi.features_available: "JacVec", "HessVec")
+        self.matrix_free = bool(matrix_free)
         if jac_format not in JAC_FORMATS:
             raise ValueError(f"jac_format must be one of {sorted(JAC_FORMATS)}")
         self.jac_format = jac_format
@@ -473,6 +475,29 @@ class HybridNLP:
         _lib.check(_lib.lib().qln_eval_hessian_lagrangian_host(self._h, Z.ctypes.data, sp, mu.ctypes.data, out.ctypes.data))
         return out
 
+    def hess_lag_vec(self, Z, sigma, mu, v, out=None):
+        """y = (sigma_b d2 f + sum_i mu_i d2 c_i) v for every problem, the Hessian never stored.  Z, v and out in Z's layout,
+        mu in c's, all device tensors; sigma a (B,) device tensor or None (1.0 for every problem).  out's entries past
+        n_nlp are not written."""
+        out = self.new_Z() if out is None else out
+        sp = None if sigma is None else self._check(sigma, self.B, "sigma")
+        _lib.check(_lib.lib().qln_eval_hessian_lagrangian_product(
+            self._h, self._check(Z, self.dims.z_total, "Z"), sp, self._check(mu, self.dims.c_total, "mu"),
+            self._check(v, self.dims.z_total, "v"), self._check(out, self.dims.z_total, "out")))
+        return out
+
+    def hess_lag_vec_host(self, Z, sigma, mu, v):
+        """The same with host arrays (MOI mode): returns a (z_total,) numpy array (zeros past n_nlp)."""
+        Z, v, mu = self._host_Z(Z), self._host_Z(v, "v"), self._host_c(mu, "mu")
+        sp = None
+        if sigma is not None:
+            sigma = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (self.B,)))
+            sp = sigma.ctypes.data
+        out = np.zeros(self.dims.z_total)
+        _lib.check(_lib.lib().qln_eval_hessian_lagrangian_product_host(
+            self._h, Z.ctypes.data, sp, mu.ctypes.data, v.ctypes.data, out.ctypes.data))
+        return out
+
     def split_hvals(self, hvals):
         """(h_total,) values -> (step blocks (B, N-1, 55), terminal diagonals (B, 15)) as numpy arrays."""
         h = hvals.detach().cpu().numpy() if hasattr(hvals, "detach") else np.asarray(hvals)
@@ -611,7 +636,7 @@ class HybridNLP:
         return float(ms.value)
 
     # -- host-pointer (MOI) mode ------------------------------------------------------------------
-    def _host_Z(self, Z):
+    def _host_Z(self, Z, name="Z"):
         Z = np.asarray(Z, dtype=np.float64)
         if Z.size == self.B * self.n_nlp and self.z_stride != self.n_nlp:
             buf = np.zeros((self.B, self.z_stride))
@@ -619,8 +644,14 @@ class HybridNLP:
             Z = buf
         Z = np.ascontiguousarray(Z.reshape(-1))
         if Z.size != self.dims.z_total:
-            raise ValueError(f"Z has {Z.size} entries, expected {self.dims.z_total}")
+            raise ValueError(f"{name} has {Z.size} entries, expected {self.dims.z_total}")
         return Z
+
+    def _host_c(self, c, name):
+        c = np.ascontiguousarray(np.asarray(c, dtype=np.float64).reshape(-1))
+        if c.size != self.dims.c_total:
+            raise ValueError(f"{name} has {c.size} entries, expected {self.dims.c_total}")
+        return c
 
     def eval_f_host(self, Z):
         Z = self._host_Z(Z)
@@ -645,6 +676,20 @@ class HybridNLP:
         v = np.zeros(self.dims.j_total)
         _lib.check(_lib.lib().qln_eval_constraint_jacobian_host(self._h, Z.ctypes.data, v.ctypes.data))
         return v
+
+    def jac_vec_host(self, Z, v):
+        """jac_vec with host arrays (MOI mode): returns a (c_total,) numpy array."""
+        Z, v = self._host_Z(Z), self._host_Z(v, "v")
+        y = np.zeros(self.dims.c_total)
+        _lib.check(_lib.lib().qln_eval_constraint_jvp_host(self._h, Z.ctypes.data, v.ctypes.data, y.ctypes.data))
+        return y
+
+    def jac_t_vec_host(self, Z, lam):
+        """jac_t_vec with host arrays (MOI mode): returns a (z_total,) numpy array (zeros past n_nlp)."""
+        Z, lam = self._host_Z(Z), self._host_c(lam, "lam")
+        g = np.zeros(self.dims.z_total)
+        _lib.check(_lib.lib().qln_eval_constraint_vjp_host(self._h, Z.ctypes.data, lam.ctypes.data, g.ctypes.data))
+        return g
 
     def jac_c_dense_host(self, Z_b, jac, b: int = 0):
         """Reference-compatible dense Jacobian of problem b: `jac` is a Fortran-ordered
