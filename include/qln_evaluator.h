@@ -357,6 +357,40 @@ int qln_sample_drop_states(qln_handle* h, const qln_drop_state_sampler* s);
  * all, as in numpy.)  Needs no handle. */
 int qln_sample_bounded_integers(int device, const uint64_t pcg_state[2], const uint64_t pcg_inc[2], int64_t draw_offset, int32_t low,
                                 int32_t high /* exclusive */, int64_t count, int32_t* out, int64_t* rejected);
+/* Time-varying LQR tracking (TVLQR) along a batch of reference trajectories, and the closed-loop roll-out under its gains.
+ * For problem b the reference is its slice of Zref (layout of Z, z_stride): x_ref,k, k = 1..N, and
+ * u_ref,k = (F1x, F1y, F2x, F2y, h_k), k = 1..N-1.  Deviations dx_k = x_k - x_ref,k.  Only the four forces are fed back,
+ * du_k = -K_k dx_k; the step length h_k stays at the reference's value (the contact schedule is indexed by knot, as in
+ * the NLP).
+ *   A_k = d x_{k+1} / d x_k (15x15) and B_k = d x_{k+1} / d F_k (15x4) at (x_ref,k, u_ref,k), of the map the roll-out
+ *   applies: the knot's RK4 step followed, at the transition knot k_trans-1, by the jump map.  That is the evaluator's dense
+ *   step block, columns 0..18, with one deliberate exception: quirk Q1's mask zeroes row 14 (the clock) at the jump knot,
+ *   but the jump map keeps x[14], so A_k's row 14 there is the true derivative (1 on the diagonal).  This changes only
+ *   P[14][14] at knots 1..k_trans-1 and never K: the clock feeds no other state and no force feeds the clock.
+ *   Weights are shared by the batch and diagonal: Q (15), R (4), Qf (15), not scaled by h_k; R_i > 0, Q_i >= 0,
+ *   Qf_i >= 0, all finite (else QLN_ERR_INVALID_ARGUMENT).
+ *   J = sum_{k=1}^{N-1} (dx_k' Q dx_k + du_k' R du_k) + dx_N' Qf dx_N   (no 1/2 factors)
+ *   P_N = Qf;  Quu = R + B'P_{k+1}B,  Qux = B'P_{k+1}A,  K_k = Quu^-1 Qux,  P_k = Q + A'P_{k+1}A - Qux'K_k, formed on the
+ *   lower triangle (P_k is exactly symmetric).  dx_1' P_1 dx_1 is the optimal cost of the linearised problem.
+ * Every N >= 2 and every k_trans in [1, N+1] is supported (the sweep keeps one knot at a time: no limit on N). */
+#define QLN_TRACK_NU 4       /* fed-back controls: the four contact forces */
+#define QLN_TRACK_P_NNZ 120  /* packed lower triangle of a 15x15 cost-to-go */
+/* K: [B][N-1][4][15] row-major; P (may be NULL: not written): [B][N][120], row i >= j at i(i+1)/2 + j.
+ * Zref, K, P: device pointers, stream-ordered.  Qdiag / Rdiag / Qfdiag: HOST arrays, passed by value in the kernel
+ * arguments (no upload).  Needs no cost table. */
+int qln_tracking_lqr(qln_handle* h, const double* Zref, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
+                     double* K, double* P);
+/* Closed-loop roll-out of the nonlinear hybrid system under the handle's mode schedule:
+ *   x_1 = x0[b] (NULL: the handle's x0), F_k = F_ref,k - K_k (x_k - x_ref,k), h_k = h_ref,k,
+ *   x_{k+1} = the evaluator's RK4 step + jump map (bit for bit the step qln_solve's roll-out takes).
+ * Zout gets the states and the applied controls (h included) in the layout of Z; it can be handed to qln_eval_constraint /
+ * qln_eval_objective / qln_constraint_violation.  Entries from n_nlp to z_stride are never written.  K == NULL is the
+ * open-loop roll-out of Zref's controls.  Zout must not overlap Zref.  x0: device [B][15] or NULL.  Stream-ordered. */
+int qln_tracking_rollout(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout);
+/* the same with HOST pointers, synchronous (staged through device memory) */
+int qln_tracking_lqr_host(qln_handle* h, const double* Zref, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
+                          double* K, double* P);
+int qln_tracking_rollout_host(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout);
 /* Z <- Z + N(0, sigma^2) on every entry, step lengths h then clipped to [h_min, h_max] (redraw_h = 0) or redrawn
  * U(h_min, h_max) (redraw_h != 0) -- the evaluation point of SURVEY.md 8d from qln_initial_guess's Z0.  The normal
  * draws are Box-Muller on the sampler's stream from `stream_offset`: the recipe's distribution, not numpy's numbers. */

@@ -161,6 +161,28 @@ function solve_hip(x0, prob::HybridNLPHIP; c_tol=1.0e-6)
     return Z, info
 end
 
+# ---- TVLQR tracking along solved trajectories (include/qln_evaluator.h, DESIGN.md 4.11) -----------------------------------
+# Zref: the problem's reference in the layout of Z; Q, Qf: 15 diagonal weights, R: 4 (the forces).  Returns K as a
+# (15, 4, N-1) array (K[:, m, k] = row m of knot k's gain) and P as (120, N) packed lower triangles (or nothing).
+function tracking_lqr(prob::HybridNLPHIP, Zref::Vector{Float64}, Q::Vector{Float64}, R::Vector{Float64}, Qf::Vector{Float64};
+                      with_cost_to_go::Bool=true)
+    N = prob.N
+    K = zeros(15, 4, N - 1)
+    P = with_cost_to_go ? zeros(120, N) : nothing
+    qln_check(ccall((:qln_tracking_lqr_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, Q, R, Qf, K, P === nothing ? C_NULL : P))
+    return K, P
+end
+# closed-loop roll-out (K = nothing: open loop) from x0 (15 values, nothing: the problem's own x0); returns Zout
+function tracking_rollout(prob::HybridNLPHIP, Zref::Vector{Float64}; K=nothing, x0=nothing)
+    Zout = zeros(length(Zref))
+    qln_check(ccall((:qln_tracking_rollout_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, K === nothing ? C_NULL : K, x0 === nothing ? C_NULL : x0, Zout))
+    return Zout
+end
+
 # ---- the reference's Ipopt solve, for this evaluator type: a method of `solve` (src/moi.jl:46-103) ------------------------
 # Same generic function, same keyword arguments and defaults, same five things handed to Ipopt.  What differs from the
 # HybridNLP method, on purpose:

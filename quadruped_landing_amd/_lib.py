@@ -24,6 +24,7 @@ QLN_JAC_FORMAT_STRUCTURAL = 1
 NX, NU, NZ, COST_STRIDE = 15, 5, 20, 41
 GN_INFO_STRIDE = 8
 HESS_STEP_NNZ, HESS_TERM_NNZ = 55, 15
+TRACK_NU, TRACK_P_NNZ = 4, 120
 
 
 class QlnModel(C.Structure):
@@ -142,6 +143,10 @@ SIGNATURES = {
     "qln_eval_hessian_lagrangian_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     "qln_eval_hessian_lagrangian_product": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp]),
     "qln_eval_hessian_lagrangian_product_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp]),
+    "qln_tracking_lqr": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "qln_tracking_rollout": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
+    "qln_tracking_lqr_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "qln_tracking_rollout_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     "qln_eval_constraint_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_eval_constraint_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_gauss_newton_step": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, C.c_double, _dp, _dp, _dp]),

@@ -105,6 +105,9 @@ struct qln_handle {
     int64_t h_stride = 0;       // doubles between consecutive problems' Hessian segments (qln_hessian_layout)
     double* s_v = nullptr;      // products (qln_eval_*_product_host, qln_eval_constraint_jvp/vjp_host): the vector in the
     double* s_zout = nullptr;   // layout of Z, a result in the layout of Z
+    double* s_trK = nullptr;    // TVLQR tracking (qln_tracking_*_host): gains, cost-to-go, initial states
+    double* s_trP = nullptr;
+    double* s_trx0 = nullptr;
     std::vector<double> h_vals_one;
     // zero-copy MOI mode (small batches): pinned host buffers mapped into the device's address space -- the kernels read
     // Z from and write their results to host memory directly, so a callback is one launch and one synchronisation
@@ -114,6 +117,7 @@ struct qln_handle {
     };
     Mapped m_Z, m_c, m_vals, m_f, m_grad;
     Mapped m_v, m_mu, m_sigma, m_zout;  // the products' inputs (v, mu / lam, sigma) and their result in the layout of Z
+    Mapped m_trK, m_trP, m_trx0;        // TVLQR tracking: gains, cost-to-go, initial states
     bool zero_copy = false;
     // dense MOI scatter: per problem, where each value of the vals segment goes in the column-major matrix, and the
     // write-set's explicit zeros (built on first use)
@@ -351,10 +355,11 @@ int qln_destroy(qln_handle* h) {
         for (auto& p : h->placed)
             if (int r = release_placed(p); r != QLN_OK && rc == QLN_OK) rc = r;
     }
-    for (qln_handle::Mapped* m : {&h->m_Z, &h->m_c, &h->m_vals, &h->m_f, &h->m_grad, &h->m_v, &h->m_mu, &h->m_sigma, &h->m_zout})
+    for (qln_handle::Mapped* m : {&h->m_Z, &h->m_c, &h->m_vals, &h->m_f, &h->m_grad, &h->m_v, &h->m_mu, &h->m_sigma, &h->m_zout,
+                                 &h->m_trK, &h->m_trP, &h->m_trx0})
         if (m->host) (void)hipHostFree(m->host);
     void* bufs[] = {h->d_desc, h->d_bnd, h->d_cost, h->s_Z, h->s_c, h->s_vals, h->s_f, h->s_grad, h->solve_scratch,
-                    h->s_sigma, h->s_mu, h->s_hvals, h->s_v, h->s_zout};
+                    h->s_sigma, h->s_mu, h->s_hvals, h->s_v, h->s_zout, h->s_trK, h->s_trP, h->s_trx0};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     delete h;
@@ -927,6 +932,125 @@ int qln_eval_hessian_lagrangian_product(qln_handle* h, const double* Z, const do
     if (int rc = check_hessian_product_args(h, Z, mu, v, y, "qln_eval_hessian_lagrangian_product")) return rc;
     if (int rc = bind_device(h)) return rc;
     QLN_HIP(qln::launch_hessian_lagrangian_product(h->p, Z, sigma, mu, v, y, h->stream));
+    return QLN_OK;
+}
+
+// ------------------------------------------------------------------ TVLQR tracking (qln_tracking_kernels.hip)
+
+static int check_tracking_weights(const double* Q, const double* R, const double* Qf, const std::string& w) {
+    if (!Q || !R || !Qf) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null weights");
+    for (int i = 0; i < QLN_NX; ++i)
+        if (!(std::isfinite(Q[i]) && Q[i] >= 0.0 && std::isfinite(Qf[i]) && Qf[i] >= 0.0))
+            return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Q and Qf must be finite and >= 0 (entry " + std::to_string(i) + ")");
+    for (int i = 0; i < QLN_TRACK_NU; ++i)
+        if (!(std::isfinite(R[i]) && R[i] > 0.0))
+            return fail(QLN_ERR_INVALID_ARGUMENT, w + ": R must be finite and > 0 (entry " + std::to_string(i) + ")");
+    return QLN_OK;
+}
+
+static int check_tracking_lqr_args(const qln_handle* h, const double* Zref, const double* Q, const double* R, const double* Qf,
+                                   const double* K, const char* who) {
+    if (int rc = check_handle(h)) return rc;
+    if (!Zref || !K) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null Zref or K");
+    return check_tracking_weights(Q, R, Qf, who);
+}
+
+static int check_tracking_rollout_args(const qln_handle* h, const double* Zref, const double* Zout, const char* who) {
+    if (int rc = check_handle(h)) return rc;
+    if (!Zref || !Zout) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null Zref or Zout");
+    const uintptr_t a = reinterpret_cast<uintptr_t>(Zref), o = reinterpret_cast<uintptr_t>(Zout);
+    const uintptr_t n = (uintptr_t)h->dims.z_total * sizeof(double);
+    if (a < o + n && o < a + n) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": Zout overlaps Zref");
+    return QLN_OK;
+}
+
+static int64_t tracking_k_total(const qln_dims& D) { return (int64_t)D.B * (D.N - 1) * QLN_TRACK_NU * QLN_NX; }
+static int64_t tracking_p_total(const qln_dims& D) { return (int64_t)D.B * D.N * QLN_TRACK_P_NNZ; }
+
+int qln_tracking_lqr(qln_handle* h, const double* Zref, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
+                     double* K, double* P) {
+    if (int rc = check_tracking_lqr_args(h, Zref, Qdiag, Rdiag, Qfdiag, K, "qln_tracking_lqr")) return rc;
+    if (int rc = bind_device(h)) return rc;
+    QLN_HIP(qln::launch_tracking_lqr(h->p, Qdiag, Rdiag, Qfdiag, Zref, K, P, h->stream));
+    return QLN_OK;
+}
+
+int qln_tracking_rollout(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout) {
+    if (int rc = check_tracking_rollout_args(h, Zref, Zout, "qln_tracking_rollout")) return rc;
+    if (int rc = bind_device(h)) return rc;
+    QLN_HIP(qln::launch_tracking_rollout(h->p, Zref, K, x0, Zout, h->stream));
+    return QLN_OK;
+}
+
+// The host forms: inputs copied into mapped pinned buffers (zero_copy, small batches) or into the handle's device staging,
+// one launch, the results copied back -- the buffers are allocated on first use and kept until qln_destroy.
+int qln_tracking_lqr_host(qln_handle* h, const double* Zref, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
+                          double* K, double* P) {
+    if (int rc = check_tracking_lqr_args(h, Zref, Qdiag, Rdiag, Qfdiag, K, "qln_tracking_lqr_host")) return rc;
+    if (int rc = bind_device(h)) return rc;
+    const qln_dims& D = h->dims;
+    const int64_t nk = tracking_k_total(D), np = tracking_p_total(D);
+    if (h->zero_copy) {
+        if (int rc = ensure_mapped(&h->m_Z, D.z_total)) return rc;
+        if (int rc = ensure_mapped(&h->m_trK, nk)) return rc;
+        if (P)
+            if (int rc = ensure_mapped(&h->m_trP, np)) return rc;
+        std::memcpy(h->m_Z.host, Zref, D.z_total * sizeof(double));
+        QLN_HIP(qln::launch_tracking_lqr(h->p, Qdiag, Rdiag, Qfdiag, h->m_Z.dev, h->m_trK.dev, P ? h->m_trP.dev : nullptr,
+                                         h->stream));
+        QLN_HIP(hipStreamSynchronize(h->stream));
+        std::memcpy(K, h->m_trK.host, nk * sizeof(double));
+        if (P) std::memcpy(P, h->m_trP.host, np * sizeof(double));
+        return QLN_OK;
+    }
+    if (int rc = ensure(&h->s_Z, D.z_total)) return rc;
+    if (int rc = ensure(&h->s_trK, nk)) return rc;
+    if (P)
+        if (int rc = ensure(&h->s_trP, np)) return rc;
+    QLN_HIP(hipMemcpyAsync(h->s_Z, Zref, D.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    QLN_HIP(qln::launch_tracking_lqr(h->p, Qdiag, Rdiag, Qfdiag, h->s_Z, h->s_trK, P ? h->s_trP : nullptr, h->stream));
+    QLN_HIP(hipMemcpyAsync(K, h->s_trK, nk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (P) QLN_HIP(hipMemcpyAsync(P, h->s_trP, np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QLN_HIP(hipStreamSynchronize(h->stream));
+    return QLN_OK;
+}
+
+// Zout's entries past n_nlp are never written by the kernel: they come back as whatever the caller's buffer held there.
+int qln_tracking_rollout_host(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout) {
+    if (int rc = check_tracking_rollout_args(h, Zref, Zout, "qln_tracking_rollout_host")) return rc;
+    if (int rc = bind_device(h)) return rc;
+    const qln_dims& D = h->dims;
+    const int64_t nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX;
+    if (h->zero_copy) {
+        if (int rc = ensure_mapped(&h->m_Z, D.z_total)) return rc;
+        if (int rc = ensure_mapped(&h->m_zout, D.z_total)) return rc;
+        if (K)
+            if (int rc = ensure_mapped(&h->m_trK, nk)) return rc;
+        if (x0)
+            if (int rc = ensure_mapped(&h->m_trx0, nx)) return rc;
+        std::memcpy(h->m_Z.host, Zref, D.z_total * sizeof(double));
+        std::memcpy(h->m_zout.host, Zout, D.z_total * sizeof(double));
+        if (K) std::memcpy(h->m_trK.host, K, nk * sizeof(double));
+        if (x0) std::memcpy(h->m_trx0.host, x0, nx * sizeof(double));
+        QLN_HIP(qln::launch_tracking_rollout(h->p, h->m_Z.dev, K ? h->m_trK.dev : nullptr, x0 ? h->m_trx0.dev : nullptr,
+                                             h->m_zout.dev, h->stream));
+        QLN_HIP(hipStreamSynchronize(h->stream));
+        std::memcpy(Zout, h->m_zout.host, D.z_total * sizeof(double));
+        return QLN_OK;
+    }
+    if (int rc = ensure(&h->s_Z, D.z_total)) return rc;
+    if (int rc = ensure(&h->s_zout, D.z_total)) return rc;
+    if (K)
+        if (int rc = ensure(&h->s_trK, nk)) return rc;
+    if (x0)
+        if (int rc = ensure(&h->s_trx0, nx)) return rc;
+    QLN_HIP(hipMemcpyAsync(h->s_Z, Zref, D.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    QLN_HIP(hipMemcpyAsync(h->s_zout, Zout, D.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (K) QLN_HIP(hipMemcpyAsync(h->s_trK, K, nk * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (x0) QLN_HIP(hipMemcpyAsync(h->s_trx0, x0, nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    QLN_HIP(qln::launch_tracking_rollout(h->p, h->s_Z, K ? h->s_trK : nullptr, x0 ? h->s_trx0 : nullptr, h->s_zout, h->stream));
+    QLN_HIP(hipMemcpyAsync(Zout, h->s_zout, D.z_total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QLN_HIP(hipStreamSynchronize(h->stream));
     return QLN_OK;
 }
 

@@ -150,6 +150,12 @@ hipError_t launch_hessian_lagrangian(const BatchParams& p, const double* Z, cons
 // y = H v with the same H, contracted in registers (qln_hessian_kernels.hip); v and y in the layout of Z
 hipError_t launch_hessian_lagrangian_product(const BatchParams& p, const double* Z, const double* sigma, const double* mu,
                                              const double* v, double* y, hipStream_t stream);
+// TVLQR gains (and cost-to-go, P may be null) along the reference trajectories Zref; closed-loop roll-out under K (null:
+// open loop) from x0 (null: the handle's x0) (qln_tracking_kernels.hip).  Qd / Rd / Qfd are host arrays.
+hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const double* Rd, const double* Qfd, const double* Zref,
+                               double* K, double* P, hipStream_t stream);
+hipError_t launch_tracking_rollout(const BatchParams& p, const double* Zref, const double* K, const double* x0, double* Zout,
+                                   hipStream_t stream);
 // batched Gauss-Newton step on the constraint violation, CGLS per problem in LDS (qln_solver_kernels.hip)
 size_t gauss_newton_lds_bytes(int32_t N);
 hipError_t launch_gauss_newton_step(const BatchParams& p, const double* Z, const double* c, double* dZ, int max_iters,

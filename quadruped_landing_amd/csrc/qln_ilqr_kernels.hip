@@ -268,29 +268,6 @@ __device__ __forceinline__ void stage_eval(const StageIn& I, const double (&x)[1
     o.viol = viol;
 }
 
-// one dynamics knot of the roll-out: the evaluator's RK4 step + jump map (src/constraints.jl:19-38)
-__device__ __forceinline__ void step_forward(const BatchParams& P, int k, int kt, int im, double Ib, const double (&x)[15],
-                                             const double (&u)[5], double (&xn)[15]) {
-    const int K = k + 1;
-    const int mode = (K <= kt - 1) ? im : 3;
-    const bool jump = (K == kt - 1);
-    const bool f1free = (mode == 2), f2free = (mode == 1);
-    StepConst sc;
-    sc.abx = (u[0] + u[2]) / P.mb;
-    sc.aby = (u[1] + u[3]) / P.mb + P.g;
-    sc.a1x = f1free ? (-u[0] / P.mf) : 0.0;
-    sc.a1y = f1free ? (-u[1] / P.mf + P.g) : 0.0;
-    sc.a2x = f2free ? (-u[2] / P.mf) : 0.0;
-    sc.a2y = f2free ? (-u[3] / P.mf + P.g) : 0.0;
-    rk4_step(x, u, sc, f1free, f2free, Ib, xn);
-    if (jump) {
-        xn[4] = 0.0;
-        xn[6] = 0.0;
-        xn[10] = xn[11] = xn[12] = xn[13] = 0.0;
-    }
-}
-
-
 // The same knot in closed form, for the TRIAL roll-outs.  With zero-order-hold forces every acceleration but the body's
 // angular one is constant over the step, and RK4 reproduces p+ = p + h v + h^2 a/2, v+ = v + h a, and the cubic / quartic
 // in h for omega / theta (file header of qln_kernels.hip) up to rounding: 1.3e-15 against the RK4 step on random states.

@@ -88,6 +88,28 @@ __device__ __forceinline__ void rk4_step(const double (&x)[15], const double (&u
     xn[14] = x[14] + u[4];
 }
 
+// one dynamics knot of a roll-out (qln_solve's and qln_tracking_rollout's): the evaluator's RK4 step + jump map (src/constraints.jl:19-38)
+__device__ __forceinline__ void step_forward(const BatchParams& P, int k, int kt, int im, double Ib, const double (&x)[15],
+                                             const double (&u)[5], double (&xn)[15]) {
+    const int K = k + 1;
+    const int mode = (K <= kt - 1) ? im : 3;
+    const bool jump = (K == kt - 1);
+    const bool f1free = (mode == 2), f2free = (mode == 1);
+    StepConst sc;
+    sc.abx = (u[0] + u[2]) / P.mb;
+    sc.aby = (u[1] + u[3]) / P.mb + P.g;
+    sc.a1x = f1free ? (-u[0] / P.mf) : 0.0;
+    sc.a1y = f1free ? (-u[1] / P.mf + P.g) : 0.0;
+    sc.a2x = f2free ? (-u[2] / P.mf) : 0.0;
+    sc.a2y = f2free ? (-u[3] / P.mf + P.g) : 0.0;
+    rk4_step(x, u, sc, f1free, f2free, Ib, xn);
+    if (jump) {
+        xn[4] = 0.0;
+        xn[6] = 0.0;
+        xn[10] = xn[11] = xn[12] = xn[13] = 0.0;
+    }
+}
+
 // Base quantities of a step block (closed form in qln_kernels.hip's header) from the knot's state x[0..13], forces
 // F1x..F2y, step h, the mode flags f1free / f2free / jump and the model constants g, mb, mf, Ib in scope.  Defines
 // everything QLN_STEP_ENTRIES() refers to.  Column 19 (hc[]), the eight force-column entries of the theta/omega rows

@@ -1,0 +1,372 @@
+// qln_tracking_kernels.hip -- time-varying LQR tracking along a batch of reference trajectories (qln_tracking_lqr) and the
+// closed-loop roll-out of the nonlinear hybrid system under the gains (qln_tracking_rollout).  Semantics: the comment
+// above the declarations in include/qln_evaluator.h.
+//
+// k_tracking_lqr: the backward Riccati sweep is serial in the knots, so the parallelism is across problems and inside a
+// knot's 15x15 products.  One problem per row of sixteen lanes, four problems per wave; lane j < 15 keeps row j of
+// P_{k+1} (= column j) in registers, lane 15 shadows lane 14 and stores nothing.  A_k, B_k are the evaluator's closed
+// form (QLN_STEP_BASE / QLN_STEP_ENTRIES), formed for the knot by every lane of the row alike from the reference's
+// (x_k, u_k): what a lane needs at compile-time positions (every column of A for T = P A, every column of B for
+// S = P B and B'S) is in registers, what it needs at its own runtime position (column j of A for A'T, column j of Qux)
+// comes from a per-row LDS table in the compact four-entries-per-column form of the solver's sweep (ac_slot of
+// qln_ilqr_kernels.hip): A(c,c), A(2,c), A(9,c) and the position <- velocity coupling A(c-7,c).
+// Per knot, three LDS hand-offs inside the wave (no s_barrier, wave_lds_sync):
+//   1. T row j = P row j . A (60 FMAs, structure known at compile time), S row j = P row j . B (24) -> LDS;
+//   2. Qxx row j = A'T (rows 2, 9, j-7 of T from LDS), Quu = R + B'S (every lane, all of S from LDS), Qux column j;
+//      Quu = L D L' (every lane alike), K column j = Quu^-1 Qux column j -> the K tile in LDS;
+//   3. P_k row j, entries c <= j, = Q + Qxx - Qux'K -> the packed lower-triangle tile; every lane reads its full row back
+//      from the tile, so P is exactly symmetric, and the K and P tiles leave as coalesced stores (sixteen lanes, 128 B).
+// The jump knot's A row 14 is the jump map's (the clock is kept), not the Jacobian's masked zero (quirk Q1).
+//
+// k_tracking_rollout: one lane per problem, the solver's step_forward (qln_kernel_common.h) on the fed-back forces.
+#include "qln_kernel_common.h"
+
+#include <cstdlib>
+
+namespace qln {
+namespace {
+
+constexpr int kRows = kWave / 16;  // problems per wave
+// per-row LDS image (doubles): compact A table [16][4] | T [15][16] | S [15][4] | K tile [4][15] | packed P [120] |
+// B table [15][4] (the form-once variant only)
+constexpr int kLAC = 0, kLT = 64, kLS = kLT + 15 * 16, kLK = kLS + 60, kLP = kLK + 60, kLB = kLP + QLN_TRACK_P_NNZ,
+              kLRow = kLB + 60;
+static_assert(kLRow % 2 == 0 && kLS % 2 == 0 && kLK % 2 == 0 && kLP % 2 == 0 && kLB % 2 == 0, "16-byte aligned sections");
+
+__host__ __device__ constexpr int tk_slot(int row, int col) {  // the compact table's slot of A(row, col)
+    return row == col ? 0 : row == 2 ? 1 : row == 9 ? 2 : 3;
+}
+__host__ __device__ constexpr int tk_coupling(int c) {  // the velocity column c's position row, -1 if none
+    return (c == 7 || c == 8 || (c >= 10 && c <= 13)) ? c - 7 : -1;
+}
+// bit s of a_slots(c): slot s of column c can be non-zero in some mode; bit r of b_rows_mask(m): B(r, m) can be
+__host__ __device__ constexpr unsigned a_slots(int c) {
+    unsigned m = 0;
+    for (int r = 0; r < 15; ++r)
+        if (step_union_present(r, c) || (r == 14 && c == 14)) m |= 1u << tk_slot(r, c);
+    return m;
+}
+__host__ __device__ constexpr unsigned b_rows_mask(int m) {
+    unsigned s = 0;
+    for (int r = 0; r < 15; ++r)
+        if (step_union_present(r, 15 + m)) s |= 1u << r;
+    return s;
+}
+__host__ __device__ constexpr bool a_structure_ok() {  // every state column's entries fit the four slots
+    for (int c = 0; c < 15; ++c)
+        for (int r = 0; r < 15; ++r)
+            if (step_union_present(r, c) && !(r == c || r == 2 || r == 9 || r == tk_coupling(c))) return false;
+    return true;
+}
+static_assert(a_structure_ok(), "A has four entries per column: diagonal, rows 2 and 9, and row c-7");
+
+constexpr bool kTrackFormOnceDefault = false;  // which k_tracking_lqr variant the product launches
+
+struct TrackWeights {
+    double Q[15], R[4], Qf[15];
+};
+
+// kFormOnce: the knot's block is formed by lane 0 of the row alone, straight into the LDS tables (A and B), and every lane
+// reads what it needs back from there -- the alternative to forming it in every lane's registers (DESIGN.md 4.11 compares
+// the two).
+template <bool kWantP, bool kFormOnce>
+__global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeights W, const double* __restrict__ Zref,
+                                                        double* __restrict__ Kout, double* __restrict__ Pout) {
+    __shared__ double lds[kRows * kLRow];
+    const int lane = threadIdx.x;
+    const int ln = lane & 15, row = lane >> 4;
+    const int j = ln < 15 ? ln : 14;  // lane 15 shadows row 14 and stores nothing
+    const bool own = ln < 15;
+    const int wave = xcd_contiguous_index(blockIdx.x, (P.B + kRows - 1) / kRows);
+    const int b = wave * kRows + row;
+    const bool valid = b < P.B;
+    const int bc = valid ? b : P.B - 1;
+    const int N = P.N;
+    const ProblemDesc pd = P.desc[bc];
+    const int kt = pd.k_trans, im = pd.init_mode;
+    const double g = P.g, mb = P.mb, mf = P.mf;
+    const double Ib = P.mb * (P.lb * P.lb) / 12;
+    double* __restrict__ L = lds + row * kLRow;
+    const double* __restrict__ Zb = Zref + (int64_t)bc * P.z_stride;
+    const int jp = tk_coupling(j), jq = jp < 0 ? 0 : jp;
+
+    // the compact A table: slots no entry fills stay 0.0
+    for (int i = ln; i < 64; i += 16) L[kLAC + i] = 0.0;
+    if (kFormOnce)
+        for (int i = ln; i < 60; i += 16) L[kLB + i] = 0.0;
+    // P_N = Qf
+    double p[15];
+#pragma unroll
+    for (int c = 0; c < 15; ++c) p[c] = (c == j) ? W.Qf[c] : 0.0;
+    if (kWantP) {
+#pragma unroll
+        for (int c = 0; c < 15; ++c)
+            if (own && c <= j) L[kLP + j * (j + 1) / 2 + c] = p[c];
+        wave_lds_sync();
+        if (valid) {
+            double* __restrict__ Pb = Pout + ((int64_t)b * N + (N - 1)) * QLN_TRACK_P_NNZ;
+            for (int i = ln; i < QLN_TRACK_P_NNZ; i += 16) Pb[i] = L[kLP + i];
+        }
+    }
+    // the reference's (x_k, F_k, h_k) of the knot: requested one knot ahead
+    double zn[19];
+#pragma unroll
+    for (int i = 0; i < 19; ++i) zn[i] = Zb[20 * (N - 2) + (i < 14 ? i : i + 1)];
+
+    for (int k = N - 2; k >= 0; --k) {
+        double x[14];
+#pragma unroll
+        for (int i = 0; i < 14; ++i) x[i] = zn[i];
+        const double F1x = zn[14], F1y = zn[15], F2x = zn[16], F2y = zn[17], h = zn[18];
+        if (k > 0) {
+#pragma unroll
+            for (int i = 0; i < 19; ++i) zn[i] = Zb[20 * (k - 1) + (i < 14 ? i : i + 1)];
+        }
+        const int K = k + 1;
+        const int mode = (K <= kt - 1) ? im : 3;
+        const bool jump = (K == kt - 1), f1free = (mode == 2), f2free = (mode == 1);
+        double Ac[15][4], Bm[15][4];
+#pragma unroll
+        for (int c = 0; c < 15; ++c)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) Ac[c][s] = Bm[c][s] = 0.0;
+        // row 14 of the jump knot: the jump map keeps the clock (its Jacobian's mask zeroes the row, quirk Q1)
+        if constexpr (!kFormOnce) {
+            QLN_STEP_BASE();
+#define JW(row_, col_, val_)                                                                        \
+    {                                                                                               \
+        if constexpr ((col_) < 15) Ac[col_][tk_slot(row_, col_)] = ((row_) == 14) ? 1.0 : (val_);   \
+        else if constexpr ((col_) < 19) Bm[row_][(col_) - 15] = (val_);                             \
+    }
+            QLN_STEP_ENTRIES();
+#undef JW
+            // ---- 1. the knot's A table; T row j = P row j . A, S row j = P row j . B ----
+            if (ln == 0) {
+#pragma unroll
+                for (int c = 0; c < 15; ++c)
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+                        if ((a_slots(c) >> s) & 1u) L[kLAC + 4 * c + s] = Ac[c][s];
+            }
+        } else {
+            if (ln == 0) {
+                QLN_STEP_BASE();
+#define JW(row_, col_, val_)                                                                                 \
+    {                                                                                                        \
+        if constexpr ((col_) < 15) L[kLAC + 4 * (col_) + tk_slot(row_, col_)] = ((row_) == 14) ? 1.0 : (val_); \
+        else if constexpr ((col_) < 19) L[kLB + 4 * (row_) + (col_) - 15] = (val_);                          \
+    }
+                QLN_STEP_ENTRIES();
+#undef JW
+            }
+            wave_lds_sync();
+            // ---- 1. T row j = P row j . A, S row j = P row j . B, with A and B read from the row's tables ----
+#pragma unroll
+            for (int c = 0; c < 15; ++c)
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+                    if ((a_slots(c) >> s) & 1u) Ac[c][s] = L[kLAC + 4 * c + s];
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int r = 0; r < 15; ++r)
+                    if ((b_rows_mask(m) >> r) & 1u) Bm[r][m] = L[kLB + 4 * r + m];
+        }
+        double t[15], sr[4];
+#pragma unroll
+        for (int c = 0; c < 15; ++c) {
+            const unsigned sl = a_slots(c);
+            double acc = p[c] * Ac[c][0];
+            if ((sl >> 1) & 1u) acc = fma(p[2], Ac[c][1], acc);
+            if ((sl >> 2) & 1u) acc = fma(p[9], Ac[c][2], acc);
+            if ((sl >> 3) & 1u) acc = fma(p[tk_coupling(c) < 0 ? 0 : tk_coupling(c)], Ac[c][3], acc);
+            t[c] = acc;
+        }
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            double acc = 0.0;
+            bool first = true;
+#pragma unroll
+            for (int r = 0; r < 15; ++r)
+                if ((b_rows_mask(m) >> r) & 1u) {
+                    acc = first ? p[r] * Bm[r][m] : fma(p[r], Bm[r][m], acc);
+                    first = false;
+                }
+            sr[m] = acc;
+        }
+        if (own) {
+#pragma unroll
+            for (int c = 0; c < 15; ++c) L[kLT + 16 * j + c] = t[c];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) L[kLS + 4 * j + m] = sr[m];
+        }
+        wave_lds_sync();
+        // ---- 2. Qxx row j = A'T, Quu = R + B'S, Qux column j = S'A column j; K column j ----
+        const double a0 = L[kLAC + 4 * j], a2 = L[kLAC + 4 * j + 1], a9 = L[kLAC + 4 * j + 2], ac = L[kLAC + 4 * j + 3];
+        double qx[15];
+#pragma unroll
+        for (int c = 0; c < 15; ++c) {
+            double acc = a0 * t[c];
+            acc = fma(a2, L[kLT + 16 * 2 + c], acc);
+            acc = fma(a9, L[kLT + 16 * 9 + c], acc);
+            acc = fma(ac, L[kLT + 16 * jq + c], acc);
+            qx[c] = acc;
+        }
+        double qu[4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            double acc = a0 * sr[m];
+            acc = fma(a2, L[kLS + 4 * 2 + m], acc);
+            acc = fma(a9, L[kLS + 4 * 9 + m], acc);
+            acc = fma(ac, L[kLS + 4 * jq + m], acc);
+            qu[m] = acc;
+        }
+        double q[4][4];
+#pragma unroll
+        for (int n = 0; n < 4; ++n)
+#pragma unroll
+            for (int m = 0; m <= n; ++m) {
+                double acc = (m == n) ? W.R[m] : 0.0;
+#pragma unroll
+                for (int r = 0; r < 15; ++r)
+                    if ((b_rows_mask(n) >> r) & 1u) acc = fma(L[kLS + 4 * r + m], Bm[r][n], acc);
+                q[n][m] = acc;
+                q[m][n] = acc;
+            }
+        // Quu = L D L' (the same bits in every lane), then K column j = Quu^-1 Qux column j
+        double l[4][4], d[4], dinv[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            double dc = q[c][c];
+#pragma unroll
+            for (int m = 0; m < c; ++m) dc = fma(-l[c][m] * d[m], l[c][m], dc);
+            d[c] = dc;
+            dinv[c] = 1.0 / dc;
+#pragma unroll
+            for (int r = c + 1; r < 4; ++r) {
+                double v = q[r][c];
+#pragma unroll
+                for (int m = 0; m < c; ++m) v = fma(-l[r][m] * d[m], l[c][m], v);
+                l[r][c] = v * dinv[c];
+            }
+        }
+        double kc[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            double v = qu[i];
+#pragma unroll
+            for (int m = 0; m < i; ++m) v = fma(-l[i][m], kc[m], v);
+            kc[i] = v;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) kc[i] *= dinv[i];
+#pragma unroll
+        for (int i = 3; i >= 0; --i) {
+#pragma unroll
+            for (int m = i + 1; m < 4; ++m) kc[i] = fma(-l[m][i], kc[m], kc[i]);
+        }
+        if (own) {
+#pragma unroll
+            for (int m = 0; m < 4; ++m) L[kLK + 15 * m + j] = kc[m];
+        }
+        wave_lds_sync();
+        // ---- 3. P_k row j on the lower triangle: Q + Qxx - Qux'K ----
+#pragma unroll
+        for (int c = 0; c < 15; ++c) {
+            double acc = qx[c];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) acc = fma(-qu[m], L[kLK + 15 * m + c], acc);
+            if (c == j) acc = acc + W.Q[c];
+            if (own && c <= j) L[kLP + j * (j + 1) / 2 + c] = acc;
+        }
+        wave_lds_sync();
+#pragma unroll
+        for (int c = 0; c < 15; ++c) p[c] = L[kLP + ((c <= j) ? j * (j + 1) / 2 + c : c * (c + 1) / 2 + j)];
+        if (valid) {
+            double* __restrict__ Kb = Kout + ((int64_t)b * (N - 1) + k) * (QLN_TRACK_NU * QLN_NX);
+            for (int i = ln; i < QLN_TRACK_NU * QLN_NX; i += 16) Kb[i] = L[kLK + i];
+            if (kWantP) {
+                double* __restrict__ Pb = Pout + ((int64_t)b * N + k) * QLN_TRACK_P_NNZ;
+                for (int i = ln; i < QLN_TRACK_P_NNZ; i += 16) Pb[i] = L[kLP + i];
+            }
+        }
+        // the tiles are read above before the next knot's phase 2 / 3 writes them (two hand-offs later)
+    }
+}
+
+// x_1 = x0[b] (or the handle's x0), F_k = F_ref,k - K_k (x_k - x_ref,k), h_k = h_ref,k, x_{k+1} = step_forward.
+__global__ __launch_bounds__(kWave) void k_tracking_rollout(BatchParams P, const double* __restrict__ Zref,
+                                                            const double* __restrict__ Kg, const double* __restrict__ x0,
+                                                            double* __restrict__ Zout) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= P.B) return;
+    const ProblemDesc pd = P.desc[b];
+    const int N = P.N, kt = pd.k_trans, im = pd.init_mode;
+    const double Ib = P.mb * (P.lb * P.lb) / 12;
+    const double* __restrict__ Zr = Zref + (int64_t)b * P.z_stride;
+    double* __restrict__ Zo = Zout + (int64_t)b * P.z_stride;
+    const double* __restrict__ xs = x0 ? x0 + (int64_t)b * 15 : P.bnd + (int64_t)b * 30;
+    double x[15], u[5], xn[15];
+#pragma unroll
+    for (int i = 0; i < 15; ++i) {
+        x[i] = xs[i];
+        Zo[i] = x[i];
+    }
+    for (int k = 0; k < N - 1; ++k) {
+#pragma unroll
+        for (int i = 0; i < 5; ++i) u[i] = Zr[20 * k + 15 + i];
+        if (Kg) {
+            const double* __restrict__ Kk = Kg + ((int64_t)b * (N - 1) + k) * (QLN_TRACK_NU * QLN_NX);
+            double dx[15];
+#pragma unroll
+            for (int i = 0; i < 15; ++i) dx[i] = x[i] - Zr[20 * k + i];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                double du = Kk[15 * m] * dx[0];
+#pragma unroll
+                for (int i = 1; i < 15; ++i) du = fma(Kk[15 * m + i], dx[i], du);
+                u[m] = u[m] - du;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 5; ++i) Zo[20 * k + 15 + i] = u[i];
+        step_forward(P, k, kt, im, Ib, x, u, xn);
+#pragma unroll
+        for (int i = 0; i < 15; ++i) {
+            x[i] = xn[i];
+            Zo[20 * (k + 1) + i] = xn[i];
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const double* Rd, const double* Qfd, const double* Zref,
+                               double* K, double* P, hipStream_t stream) {
+    TrackWeights w;
+    for (int i = 0; i < 15; ++i) {
+        w.Q[i] = Qd[i];
+        w.Qf[i] = Qfd[i];
+    }
+    for (int i = 0; i < 4; ++i) w.R[i] = Rd[i];
+    const int waves = (p.B + kRows - 1) / kRows;
+    bool form_once = kTrackFormOnceDefault;
+#ifdef QLN_TUNING
+    // tuning build only: QLN_TRACK_FORM_ONCE=0|1 selects the variant for A/B runs (bench/tracking_timing.py)
+    if (const char* e = getenv("QLN_TRACK_FORM_ONCE")) form_once = atoi(e) != 0;
+#endif
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(xcd_grid(waves)), dim3(kWave), 0, stream, p, w, Zref, K, P); };
+    if (form_once)
+        P ? go(k_tracking_lqr<true, true>) : go(k_tracking_lqr<false, true>);
+    else
+        P ? go(k_tracking_lqr<true, false>) : go(k_tracking_lqr<false, false>);
+    return hipGetLastError();
+}
+
+hipError_t launch_tracking_rollout(const BatchParams& p, const double* Zref, const double* K, const double* x0, double* Zout,
+                                   hipStream_t stream) {
+    hipLaunchKernelGGL(k_tracking_rollout, dim3((p.B + kWave - 1) / kWave), dim3(kWave), 0, stream, p, Zref, K, x0, Zout);
+    return hipGetLastError();
+}
+
+}  // namespace qln

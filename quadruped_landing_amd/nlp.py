@@ -91,6 +91,34 @@ def hessian_structure(N: int):
     return rows, cols
 
 
+def tracking_weights(Q, R, Qf):
+    """The diagonal TVLQR weights as contiguous float64 arrays (15, 4, 15); a scalar broadcasts."""
+    Q = np.ascontiguousarray(np.broadcast_to(np.asarray(Q, dtype=np.float64), (n,)))
+    R = np.ascontiguousarray(np.broadcast_to(np.asarray(R, dtype=np.float64), (_lib.TRACK_NU,)))
+    Qf = np.ascontiguousarray(np.broadcast_to(np.asarray(Qf, dtype=np.float64), (n,)))
+    return Q, R, Qf
+
+
+def tracking_k_shape(B: int, N: int):
+    """Shape of the gains of qln_tracking_lqr: (B, N-1, 4, 15), row-major."""
+    return (B, N - 1, _lib.TRACK_NU, n)
+
+
+def tracking_p_shape(B: int, N: int):
+    """Shape of the packed cost-to-go of qln_tracking_lqr: (B, N, 120), row i >= j at i(i+1)/2 + j."""
+    return (B, N, _lib.TRACK_P_NNZ)
+
+
+def unpack_cost_to_go(P):
+    """(..., 120) packed lower triangles -> (..., 15, 15) symmetric numpy matrices."""
+    P = P.detach().cpu().numpy() if hasattr(P, "detach") else np.asarray(P)
+    r, c = np.tril_indices(n)  # row-major over the lower triangle: (i, j) at i(i+1)/2 + j
+    out = np.zeros(P.shape[:-1] + (n, n))
+    out[..., r, c] = P
+    out[..., c, r] = P
+    return out
+
+
 def _torch():
     import torch
 
@@ -496,6 +524,64 @@ class HybridNLP:
         out = np.zeros(self.dims.z_total)
         _lib.check(_lib.lib().qln_eval_hessian_lagrangian_product_host(
             self._h, Z.ctypes.data, sp, mu.ctypes.data, v.ctypes.data, out.ctypes.data))
+        return out
+
+    # -- TVLQR tracking along reference trajectories ---------------------------------------------
+    def tracking_lqr(self, Zref, Q, R, Qf, K=None, P=None, with_cost_to_go=True):
+        """Time-varying LQR gains along the references Zref (device tensor, layout of Z): returns (K, P) with
+        K (B, N-1, 4, 15) and P (B, N, 120) packed lower triangles (None without with_cost_to_go).  Only the four forces
+        are fed back, du_k = -K_k (x_k - x_ref,k); Q (15), R (4), Qf (15) are diagonal weights (qln_evaluator.h)."""
+        T = _torch()
+        Qh, Rh, Qfh = tracking_weights(Q, R, Qf)
+        self._check(Zref, self.dims.z_total, "Zref")
+        if K is None:
+            K = T.empty(tracking_k_shape(self.B, self.N), dtype=T.float64, device=self._dev())
+        self._check(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        if with_cost_to_go and P is None:
+            P = T.empty(tracking_p_shape(self.B, self.N), dtype=T.float64, device=self._dev())
+        if not with_cost_to_go:
+            P = None
+        pp = None if P is None else self._check(P, self.B * self.N * _lib.TRACK_P_NNZ, "P")
+        _lib.check(_lib.lib().qln_tracking_lqr(self._h, Zref.data_ptr(), Qh.ctypes.data, Rh.ctypes.data, Qfh.ctypes.data,
+                                               K.data_ptr(), pp))
+        return K, P
+
+    def tracking_lqr_host(self, Zref, Q, R, Qf, with_cost_to_go=True):
+        """The same with host arrays (synchronous): returns numpy (K, P)."""
+        Zref = self._host_Z(Zref, "Zref")
+        Qh, Rh, Qfh = tracking_weights(Q, R, Qf)
+        K = np.zeros(tracking_k_shape(self.B, self.N))
+        P = np.zeros(tracking_p_shape(self.B, self.N)) if with_cost_to_go else None
+        _lib.check(_lib.lib().qln_tracking_lqr_host(self._h, Zref.ctypes.data, Qh.ctypes.data, Rh.ctypes.data, Qfh.ctypes.data,
+                                                    K.ctypes.data, None if P is None else P.ctypes.data))
+        return K, P
+
+    def tracking_rollout(self, Zref, K=None, x0=None, out=None):
+        """Closed-loop roll-out of the hybrid dynamics from x0 ((B, 15) device tensor, None: the handle's x0) with
+        F_k = F_ref,k - K_k (x_k - x_ref,k) and h_k = h_ref,k; K None is the open-loop roll-out.  Returns Zout in the
+        layout of Z (entries past n_nlp are not written).  out must not overlap Zref."""
+        self._check(Zref, self.dims.z_total, "Zref")
+        out = self.new_Z() if out is None else out
+        self._check(out, self.dims.z_total, "out")
+        kp = None if K is None else self._check(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        xp = None if x0 is None else self._check(x0, self.B * n, "x0")
+        _lib.check(_lib.lib().qln_tracking_rollout(self._h, Zref.data_ptr(), kp, xp, out.data_ptr()))
+        return out
+
+    def tracking_rollout_host(self, Zref, K=None, x0=None):
+        """The same with host arrays (synchronous): returns a (z_total,) numpy array (zeros past n_nlp)."""
+        Zref = self._host_Z(Zref, "Zref")
+        kp = xp = None
+        if K is not None:
+            K = np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(-1))
+            if K.size != self.B * (self.N - 1) * _lib.TRACK_NU * n:
+                raise ValueError(f"K has {K.size} entries, expected {self.B * (self.N - 1) * _lib.TRACK_NU * n}")
+            kp = K.ctypes.data
+        if x0 is not None:
+            x0 = np.ascontiguousarray(np.broadcast_to(np.asarray(x0, dtype=np.float64), (self.B, n)))
+            xp = x0.ctypes.data
+        out = np.zeros(self.dims.z_total)
+        _lib.check(_lib.lib().qln_tracking_rollout_host(self._h, Zref.ctypes.data, kp, xp, out.ctypes.data))
         return out
 
     def split_hvals(self, hvals):

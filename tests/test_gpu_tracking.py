@@ -1,0 +1,267 @@
+"""GPU checks of qln_tracking_lqr / qln_tracking_rollout against the numpy Riccati on the evaluator's own step blocks,
+the quirk-Q1 clock row, roll-out anchors against qln_solve, second-order linearisation and LQ optimality."""
+import numpy as np
+import pytest
+
+from tests import tracking_ref as TR
+
+pytestmark = pytest.mark.gpu
+
+Q = np.array([10.0] * 14 + [0.0])
+R = np.array([1e-3, 1e-2, 1e-3, 1e-2])
+QW = np.array([10.0] * 14 + [0.7])
+QFW = np.array([30.0] * 14 + [2.0])
+
+SHAPES = [  # (B, N, k_trans, init_mode): tests/test_gpu_hessian.py's list
+    (3, 2, 1, 1), (3, 2, 2, 2), (3, 2, 3, 1), (5, 3, 2, 1), (5, 3, 3, 2), (5, 3, 4, 1),
+    (9, 40, 14, 1), (9, 40, 1, 2), (9, 40, 39, 1), (9, 40, 40, 2), (9, 40, 41, 1),
+    (17, 61, 21, 1), (17, 61, 60, 2), (10, 65, 64, 1), (10, 65, 65, 2), (10, 65, 2, 1),
+    (11, 80, 66, 2), (11, 80, 10, 1), (4, 200, 130, 1), (4, 200, 201, 2),
+]
+
+
+def _batch(B, N, k_trans, init_mode, seed=0, ragged=False):
+    from quadruped_landing_amd import problem_gen as PG
+
+    kt_build = min(max(int(k_trans), 2), N - 1) if N > 2 else 2
+    b = PG.make_batch(B, N, kt_build, init_mode, seed=seed, ragged=ragged)
+    if not ragged:
+        b.k_trans[:] = k_trans
+    return b
+
+
+def _nlp(batch, **kw):
+    from quadruped_landing_amd import HybridNLP
+
+    return HybridNLP(batch.model, batch.obj, batch.init_mode, batch.k_trans, batch.N, batch.x0, batch.xf, **kw)
+
+
+def _dense_blocks(nlp, Z):
+    import torch
+
+    vals = nlp.jac_c(Z).cpu().numpy()
+    N = nlp.N
+    out = np.zeros((nlp.B, N - 1, 15, 20))
+    for b in range(nlp.B):
+        seg = vals[nlp.j_off[b]: nlp.j_off[b] + 300 * (N - 1)]
+        out[b] = seg.reshape(N - 1, 20, 15).transpose(0, 2, 1)
+    torch.cuda.synchronize()
+    return out
+
+
+def _ref_gains(nlp, Z, Qw, Rw, Qfw, restore_clock=True):
+    blocks = _dense_blocks(nlp, Z)
+    A = np.zeros((nlp.B, nlp.N - 1, 15, 15))
+    Bm = np.zeros((nlp.B, nlp.N - 1, 15, 4))
+    for b in range(nlp.B):
+        A[b], Bm[b] = TR.blocks_from_dense(blocks[b], int(nlp.k_trans[b]), restore_clock)
+    K, P = TR.riccati(A, Bm, Qw, Rw, Qfw)
+    return A, Bm, K, P
+
+
+def _knot_rel(got, ref):
+    num = np.linalg.norm((got - ref).reshape(got.shape[0], got.shape[1], -1), axis=-1)
+    den = np.linalg.norm(ref.reshape(ref.shape[0], ref.shape[1], -1), axis=-1)
+    return float(np.max(num / np.maximum(den, 1e-300)))
+
+
+def _check_against_numpy(batch, bar=1e-10, **kw):
+    from quadruped_landing_amd import nlp as NL
+
+    nlp = _nlp(batch, **kw)
+    Z = nlp.upload_Z(batch.Z)
+    K, P = nlp.tracking_lqr(Z, QW, R, QFW)
+    _, _, Kr, Pr = _ref_gains(nlp, Z, QW, R, QFW)
+    Kg = K.cpu().numpy()
+    Pg = NL.unpack_cost_to_go(P)
+    ek, ep = _knot_rel(Kg, Kr), _knot_rel(Pg, Pr)
+    assert ek <= bar and ep <= bar, (ek, ep)
+    assert np.array_equal(Pg, np.swapaxes(Pg, -1, -2))
+    return ek, ep
+
+
+@pytest.mark.parametrize("B,N,k_trans,init_mode", SHAPES)
+def test_gains_and_cost_to_go_over_shapes(B, N, k_trans, init_mode):
+    _check_against_numpy(_batch(B, N, k_trans, init_mode, seed=N + k_trans))
+
+
+@pytest.mark.parametrize("N", [12, 40])
+def test_ragged_batch_and_padded_layout(N):
+    _check_against_numpy(_batch(37, N, 5, 1, seed=3, ragged=True))
+    _check_against_numpy(_batch(13, N, 7, 2, seed=4), z_stride=20 * N + 3, align=7)
+
+
+def test_against_the_dual_number_oracle_blocks():
+    b = _batch(6, 12, 5, 2, seed=11)
+    nlp = _nlp(b)
+    Z = nlp.upload_Z(b.Z)
+    K, _ = nlp.tracking_lqr(Z, QW, R, QFW, with_cost_to_go=False)
+    Kg = K.cpu().numpy()
+    for i in range(b.Z.shape[0]):
+        A, Bm = TR.oracle_blocks(12, int(b.k_trans[i]), int(b.init_mode[i]), b.Z[i])
+        Kr, _ = TR.riccati(A, Bm, QW, R, QFW)
+        assert _knot_rel(Kg[i][None], Kr[None]) <= 1e-8
+
+
+@pytest.mark.parametrize("B,N,ragged", [(65536, 40, False), (65536, 80, True)])
+def test_full_size_every_problem(B, N, ragged):
+    from quadruped_landing_amd import problem_gen as PG
+
+    full = PG.make_batch(B, N, 14, 1, seed=2, ragged=ragged)
+    worst = [0.0, 0.0]
+    chunk = 8192
+    for s in range(0, B, chunk):
+        sub = PG.LandingBatch(full.model, N, full.k_trans[s:s + chunk], full.init_mode[s:s + chunk], full.x0[s:s + chunk],
+                              full.xf[s:s + chunk], full.obj if full.obj.ndim == 2 else full.obj[s:s + chunk],
+                              full.Z[s:s + chunk])
+        ek, ep = _check_against_numpy(sub)
+        worst = [max(worst[0], ek), max(worst[1], ep)]
+    print(f"full size B={B} N={N} ragged={ragged}: worst per-knot rel err K {worst[0]:.2e} P {worst[1]:.2e}")
+
+
+def test_clock_weights_and_quirk_Q1():
+    from quadruped_landing_amd import nlp as NL
+
+    b = _batch(9, 40, 14, 1, seed=5)
+    nlp = _nlp(b)
+    Z = nlp.upload_Z(b.Z)
+    q0, qf0 = QW.copy(), QFW.copy()
+    q0[14] = qf0[14] = 0.0
+    K0, P0 = nlp.tracking_lqr(Z, q0, R, qf0)
+    K1, _ = nlp.tracking_lqr(Z, QW, R, QFW)
+    assert np.array_equal(K0.cpu().numpy(), K1.cpu().numpy())
+    # against the Jacobian's masked jump block (row 14 zero): K agrees, P differs only at (14, 14) before the jump
+    _, _, Km, Pm = _ref_gains(nlp, Z, QW, R, QFW, restore_clock=False)
+    Kg, Pg = nlp.tracking_lqr(Z, QW, R, QFW)
+    Kg, Pg = Kg.cpu().numpy(), NL.unpack_cost_to_go(Pg)
+    assert _knot_rel(Kg, Km) <= 1e-10
+    d = np.abs(Pg - Pm) > 1e-10 * np.abs(Pm).max()
+    assert not d[..., :14, :].any() and not d[..., 14, :14].any()
+    kt = 14
+    assert d[:, : kt - 1, 14, 14].all() and not d[:, kt - 1:, 14, 14].any()
+
+
+def test_rollout_anchors_against_qln_solve():
+    import torch
+
+    b = _batch(16, 40, 14, 1, seed=6)
+    nlp = _nlp(b)
+    Z = nlp.upload_Z(b.Z)
+    hcols = 19 + 20 * np.arange(39)
+    Zh = b.Z.copy()
+    Zh[:, hcols] = np.clip(Zh[:, hcols], 0.002, 0.015)
+    Zc = nlp.upload_Z(Zh)
+    Zs = Zc.clone()
+    nlp.solve(Zs, max_outer=0, rescue_outer=0)
+    Zo = nlp.tracking_rollout(Zc)
+    torch.cuda.synchronize()
+    n = nlp.n_nlp
+    a = Zo.view(nlp.B, -1)[:, :n].cpu().numpy()
+    s = Zs.view(nlp.B, -1)[:, :n].cpu().numpy()
+    assert (a == s).all()
+    # the solver's solution rolled out under real gains from its own x_1 comes back bit for bit
+    Zsol = nlp.upload_Z(b.Z)
+    nlp.solve(Zsol)
+    K, _ = nlp.tracking_lqr(Zsol, Q, R, Q)
+    x0 = Zsol.view(nlp.B, -1)[:, :15].contiguous()
+    Zo = nlp.tracking_rollout(Zsol, K, x0)
+    torch.cuda.synchronize()
+    assert (Zo.view(nlp.B, -1)[:, :n] == Zsol.view(nlp.B, -1)[:, :n]).all()
+
+
+def _linear_setup():
+    import torch
+
+    from quadruped_landing_amd import HybridNLP, problem_gen as PG
+
+    nb = PG.notebook_problem()
+    nlp = HybridNLP(nb.model, nb.obj, nb.init_mode, nb.k_trans, nb.N, nb.x0, nb.xf)
+    Zs = nlp.upload_Z(nb.Z)
+    nlp.solve(Zs)
+    torch.cuda.synchronize()
+    return nlp, Zs
+
+
+def test_linearisation_is_second_order_and_closed_loop_is_lq_optimal():
+    import torch
+
+    nlp, Zs = _linear_setup()
+    N = nlp.N
+    K, P = nlp.tracking_lqr(Zs, Q, R, Q)
+    A, Bm, _, _ = _ref_gains(nlp, Zs, Q, R, Q)
+    Kg = K.cpu().numpy()[0]
+    from quadruped_landing_amd import nlp as NL
+
+    P1 = NL.unpack_cost_to_go(P)[0, 0]
+    Zr = Zs.cpu().numpy().reshape(-1)[: nlp.n_nlp]
+    xr = np.stack([Zr[20 * k: 20 * k + 15] for k in range(N)])
+    ur = np.stack([Zr[20 * k + 15: 20 * k + 19] for k in range(N - 1)])
+    rng = np.random.default_rng(0)
+    d = rng.normal(size=15)
+    d[14] = 0.0
+    d /= np.linalg.norm(d)
+    errs = []
+    for eps in (1e-4, 5e-5):
+        x0 = torch.from_numpy((xr[0] + eps * d)[None]).cuda()
+        Zo = nlp.tracking_rollout(Zs, K, x0).cpu().numpy().reshape(-1)
+        xo = np.stack([Zo[20 * k: 20 * k + 15] for k in range(N)])
+        _, dx_lin = TR.closed_loop(A[0], Bm[0], Kg, eps * d)
+        errs.append(np.abs((xo - xr) - dx_lin).max())
+    ratio = errs[0] / errs[1]
+    assert 3.0 <= ratio <= 5.0, (errs, ratio)
+    # optimality at eps = 1e-6 over 64 random directions
+    eps = 1e-6
+    for i in range(64):
+        d = rng.normal(size=15)
+        d[14] = 0.0
+        d /= np.linalg.norm(d)
+        x0 = torch.from_numpy((xr[0] + eps * d)[None]).cuda()
+        zc = nlp.tracking_rollout(Zs, K, x0).cpu().numpy().reshape(-1)
+        zo = nlp.tracking_rollout(Zs, None, x0).cpu().numpy().reshape(-1)
+
+        def cost(z):
+            dx = np.stack([z[20 * k: 20 * k + 15] for k in range(N)]) - xr
+            du = np.stack([z[20 * k + 15: 20 * k + 19] for k in range(N - 1)]) - ur
+            return TR.lq_cost(dx, du, Q, R, Q)
+
+        Jc, Jo, Jp = cost(zc), cost(zo), (eps * d) @ P1 @ (eps * d)
+        assert abs(Jc - Jp) <= 1e-4 * Jp, (i, Jc, Jp)
+        assert Jc <= Jo * (1 + 1e-4), (i, Jc, Jo)
+
+
+@pytest.mark.parametrize("B", [5, 1024])  # mapped pinned buffers (small batch) and staged device copies
+def test_host_forms_and_argument_validation(B):
+    import torch
+
+    from quadruped_landing_amd import _lib
+
+    b = _batch(B, 40, 14, 2, seed=8)
+    nlp = _nlp(b)
+    Z = nlp.upload_Z(b.Z)
+    nlp.solve(Z)  # a solved reference: the perturbed closed-loop roll-outs stay finite
+    Zr = Z.cpu().numpy()
+    K, P = nlp.tracking_lqr(Z, QW, R, QFW)
+    for _ in range(2):  # the second call reuses the handle's buffers
+        Kh, Ph = nlp.tracking_lqr_host(Zr, QW, R, QFW)
+        assert np.array_equal(K.cpu().numpy(), Kh) and np.array_equal(P.cpu().numpy(), Ph)
+    Kh0, Ph0 = nlp.tracking_lqr_host(Zr, QW, R, QFW, with_cost_to_go=False)
+    assert np.array_equal(Kh0, Kh) and Ph0 is None
+    x0 = Zr.reshape(B, -1)[:, :15] + 1e-3
+    Zo = nlp.tracking_rollout(Z, K, torch.from_numpy(x0).cuda()).cpu().numpy()
+    assert np.isfinite(Zo).all()
+    for _ in range(2):
+        assert np.array_equal(Zo, nlp.tracking_rollout_host(Zr, Kh, x0))
+    assert np.array_equal(nlp.tracking_rollout(Z).cpu().numpy(), nlp.tracking_rollout_host(Zr))
+    for bad in ([1.0, 0.0, 1.0, 1.0], [1.0, -1.0, 1.0, 1.0], [1.0, np.nan, 1.0, 1.0]):
+        with pytest.raises(_lib.QlnError):
+            nlp.tracking_lqr(Z, QW, bad, QFW)
+    with pytest.raises(_lib.QlnError):
+        nlp.tracking_lqr(Z, np.where(np.arange(15) == 3, np.inf, QW), R, QFW)
+    with pytest.raises(_lib.QlnError):
+        nlp.tracking_lqr(Z, QW, R, np.where(np.arange(15) == 3, -1.0, QFW))
+    L = _lib.lib()
+    assert L.qln_tracking_lqr(nlp._h, Z.data_ptr(), QW.ctypes.data, R.ctypes.data, QFW.ctypes.data, None, None) == \
+        _lib.QLN_ERR_INVALID_ARGUMENT
+    assert L.qln_tracking_rollout(nlp._h, Z.data_ptr(), None, None, Z.data_ptr() + 8) == _lib.QLN_ERR_INVALID_ARGUMENT
+    if B == 5:  # no limit on N: past the solver's LDS limit the sweep still runs
+        _check_against_numpy(_batch(2, 700, 300, 1, seed=9), bar=1e-9)
