@@ -391,6 +391,38 @@ int qln_tracking_rollout(qln_handle* h, const double* Zref, const double* K, con
 int qln_tracking_lqr_host(qln_handle* h, const double* Zref, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
                           double* K, double* P);
 int qln_tracking_rollout_host(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout);
+/* Reverse-mode derivative (vector-Jacobian product) of qln_tracking_rollout.  Knots are 0-based here, k = 0..N-2 (knot k
+ * is the header's k+1 above).  The forward map is exactly qln_tracking_rollout's:
+ *   u_k = (F_ref,k - K_k (x_k - x_ref,k), h_ref,k),  x_{k+1} = Phi_k(x_k, u_k),  x_0 = x0[b] or the handle's x0,
+ * where Phi_k is the RK4 step followed, at k+1 == k_trans-1, by the jump map.  Given a cotangent Zbar in the layout of Z,
+ * which weights the states and the APPLIED controls (h included) that Zout holds, the reverse sweep is
+ *   lam_{N-1} = Zbar[x_{N-1}]
+ *   for k = N-2 .. 0:
+ *     [A_k B_k] = d Phi_k / d(x_k, u_k) at Zout's (x_k, u_k)        (15 x 20, the h column included)
+ *     ubar_k     = Zbar[u_k] + B_k' lam_{k+1}                         (5)
+ *     Fref_bar_k = ubar_k[0:4],  href_bar_k = ubar_k[4]
+ *     xref_bar_k = K_k' ubar_k[0:4]                                   (0 if K == NULL)
+ *     Kbar_k     = -ubar_k[0:4] (x_k - x_ref,k)'                      (4 x 15)
+ *     lam_k      = Zbar[x_k] + A_k' lam_{k+1} - K_k' ubar_k[0:4]
+ *   x0_bar = lam_0
+ * A_k, B_k are the true derivative of what the roll-out applies: the evaluator's closed-form step block, except that at
+ * the jump knot, where quirk Q1's mask zeroes the clock row, the jump map keeps it -- row 14 there is 1 at x[14] and 1 at
+ * h, as in qln_tracking_lqr (rows 4, 6 and 10-13 are zero).  The linearisation points are Zout's: the roll-out is not
+ * re-run, and nothing checks that Zout is the roll-out of (Zref, K, x0).  The result is the derivative at the trajectory
+ * Zout holds.  With K == NULL it is the reduced gradient of single shooting (controls -> trajectory).
+ * Outputs (each may be NULL: not written; overwritten, not accumulated; none may overlap an input or another output):
+ *   Zref_bar: layout of Z.  Every entry below n_nlp is written -- x_ref slots of knots 0..N-2, F_ref and h_ref slots, and
+ *             exact zeros in the x_ref,N-1 slots, which the roll-out never reads; entries from n_nlp to z_stride never.
+ *   K_bar:    [B][N-1][4][15], the layout of K.  QLN_ERR_INVALID_ARGUMENT if K == NULL and K_bar != NULL.
+ *   x0_bar:   [B][15].
+ * Zref is read for K_bar only (the states x_ref,k); it must still be non-NULL.  Every N >= 2, k_trans in [1, N+1] and
+ * init_mode, as the forward call.  Device pointers, stream-ordered; needs no cost table. */
+int qln_tracking_rollout_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
+                             double* Zref_bar, double* K_bar, double* x0_bar);
+/* the same with HOST pointers, synchronous (staged through the handle's buffers); Zref_bar's entries past n_nlp come back
+ * as the caller's buffer held them */
+int qln_tracking_rollout_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
+                                  double* Zref_bar, double* K_bar, double* x0_bar);
 /* Z <- Z + N(0, sigma^2) on every entry, step lengths h then clipped to [h_min, h_max] (redraw_h = 0) or redrawn
  * U(h_min, h_max) (redraw_h != 0) -- the evaluation point of SURVEY.md 8d from qln_initial_guess's Z0.  The normal
  * draws are Box-Muller on the sampler's stream from `stream_offset`: the recipe's distribution, not numpy's numbers. */

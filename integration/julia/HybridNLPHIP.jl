@@ -182,6 +182,18 @@ function tracking_rollout(prob::HybridNLPHIP, Zref::Vector{Float64}; K=nothing, 
                     prob.handle, Zref, K === nothing ? C_NULL : K, x0 === nothing ? C_NULL : x0, Zout))
     return Zout
 end
+# reverse sweep of tracking_rollout at the trajectory Zout: the cotangent Zbar (layout of Z, weighting Zout's states and applied
+# controls) -> (Zref_bar, K_bar, x0_bar); K = nothing is the shooting gradient (K_bar = nothing).  include/qln_evaluator.h
+function tracking_rollout_vjp(prob::HybridNLPHIP, Zref::Vector{Float64}, Zout::Vector{Float64}, Zbar::Vector{Float64}; K=nothing)
+    Zref_bar = zeros(length(Zref))
+    K_bar = K === nothing ? nothing : zeros(size(K))
+    x0_bar = zeros(15)
+    qln_check(ccall((:qln_tracking_rollout_vjp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, K === nothing ? C_NULL : K, Zout, Zbar, Zref_bar, K_bar === nothing ? C_NULL : K_bar,
+                    x0_bar))
+    return Zref_bar, K_bar, x0_bar
+end
 
 # ---- the reference's Ipopt solve, for this evaluator type: a method of `solve` (src/moi.jl:46-103) ------------------------
 # Same generic function, same keyword arguments and defaults, same five things handed to Ipopt.  What differs from the

@@ -147,6 +147,8 @@ SIGNATURES = {
     "qln_tracking_rollout": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     "qln_tracking_lqr_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "qln_tracking_rollout_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
+    "qln_tracking_rollout_vjp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "qln_tracking_rollout_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "qln_eval_constraint_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_eval_constraint_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_gauss_newton_step": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, C.c_double, _dp, _dp, _dp]),

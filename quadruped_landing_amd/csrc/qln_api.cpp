@@ -108,6 +108,8 @@ struct qln_handle {
     double* s_trK = nullptr;    // TVLQR tracking (qln_tracking_*_host): gains, cost-to-go, initial states
     double* s_trP = nullptr;
     double* s_trx0 = nullptr;
+    double* s_trZbar = nullptr;  // the roll-out's vjp (qln_tracking_rollout_vjp_host): the cotangent in, the gains' cotangent out
+    double* s_trKbar = nullptr;
     std::vector<double> h_vals_one;
     // zero-copy MOI mode (small batches): pinned host buffers mapped into the device's address space -- the kernels read
     // Z from and write their results to host memory directly, so a callback is one launch and one synchronisation
@@ -118,6 +120,7 @@ struct qln_handle {
     Mapped m_Z, m_c, m_vals, m_f, m_grad;
     Mapped m_v, m_mu, m_sigma, m_zout;  // the products' inputs (v, mu / lam, sigma) and their result in the layout of Z
     Mapped m_trK, m_trP, m_trx0;        // TVLQR tracking: gains, cost-to-go, initial states
+    Mapped m_trZbar, m_trKbar;          // the roll-out's vjp: the cotangent in the layout of Z, the gains' cotangent
     bool zero_copy = false;
     // dense MOI scatter: per problem, where each value of the vals segment goes in the column-major matrix, and the
     // write-set's explicit zeros (built on first use)
@@ -356,10 +359,11 @@ int qln_destroy(qln_handle* h) {
             if (int r = release_placed(p); r != QLN_OK && rc == QLN_OK) rc = r;
     }
     for (qln_handle::Mapped* m : {&h->m_Z, &h->m_c, &h->m_vals, &h->m_f, &h->m_grad, &h->m_v, &h->m_mu, &h->m_sigma, &h->m_zout,
-                                 &h->m_trK, &h->m_trP, &h->m_trx0})
+                                 &h->m_trK, &h->m_trP, &h->m_trx0, &h->m_trZbar, &h->m_trKbar})
         if (m->host) (void)hipHostFree(m->host);
     void* bufs[] = {h->d_desc, h->d_bnd, h->d_cost, h->s_Z, h->s_c, h->s_vals, h->s_f, h->s_grad, h->solve_scratch,
-                    h->s_sigma, h->s_mu, h->s_hvals, h->s_v, h->s_zout, h->s_trK, h->s_trP, h->s_trx0};
+                    h->s_sigma, h->s_mu, h->s_hvals, h->s_v, h->s_zout, h->s_trK, h->s_trP, h->s_trx0,
+                    h->s_trZbar, h->s_trKbar};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     delete h;
@@ -1050,6 +1054,106 @@ int qln_tracking_rollout_host(qln_handle* h, const double* Zref, const double* K
     if (x0) QLN_HIP(hipMemcpyAsync(h->s_trx0, x0, nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
     QLN_HIP(qln::launch_tracking_rollout(h->p, h->s_Z, K ? h->s_trK : nullptr, x0 ? h->s_trx0 : nullptr, h->s_zout, h->stream));
     QLN_HIP(hipMemcpyAsync(Zout, h->s_zout, D.z_total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QLN_HIP(hipStreamSynchronize(h->stream));
+    return QLN_OK;
+}
+
+// the roll-out's reverse sweep (k_tracking_rollout_vjp)
+static bool overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
+    if (!a || !b) return false;
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + (uintptr_t)nb * sizeof(double) && y < x + (uintptr_t)na * sizeof(double);
+}
+
+static int check_tracking_vjp_args(const qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                   const double* Zbar, const double* Zref_bar, const double* K_bar, const double* x0_bar,
+                                   const char* who) {
+    if (int rc = check_handle(h)) return rc;
+    const std::string w(who);
+    if (!Zref || !Zout || !Zbar) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref, Zout or Zbar");
+    if (K_bar && !K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_bar needs K (K == NULL has no gains to differentiate)");
+    const qln_dims& D = h->dims;
+    const int64_t nz = D.z_total, nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX;
+    const struct {
+        const double* p;
+        int64_t n;
+    } in[] = {{Zref, nz}, {K, nk}, {Zout, nz}, {Zbar, nz}}, out[] = {{Zref_bar, nz}, {K_bar, nk}, {x0_bar, nx}};
+    for (const auto& o : out) {
+        for (const auto& i : in)
+            if (overlaps(o.p, o.n, i.p, i.n)) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": an output overlaps an input");
+        for (const auto& q : out)
+            if (&q != &o && overlaps(o.p, o.n, q.p, q.n)) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": two outputs overlap");
+    }
+    return QLN_OK;
+}
+
+int qln_tracking_rollout_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
+                             double* Zref_bar, double* K_bar, double* x0_bar) {
+    if (int rc = check_tracking_vjp_args(h, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar, "qln_tracking_rollout_vjp")) return rc;
+    if (int rc = bind_device(h)) return rc;
+    QLN_HIP(qln::launch_tracking_rollout_vjp(h->p, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar, h->stream));
+    return QLN_OK;
+}
+
+// Zref is staged only when K_bar asks for it (the kernel reads it for nothing else).  Zref_bar's entries past n_nlp come
+// back as the caller's buffer held them.
+int qln_tracking_rollout_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
+                                  double* Zref_bar, double* K_bar, double* x0_bar) {
+    if (int rc = check_tracking_vjp_args(h, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar, "qln_tracking_rollout_vjp_host"))
+        return rc;
+    if (int rc = bind_device(h)) return rc;
+    const qln_dims& D = h->dims;
+    const int64_t nz = D.z_total, nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX;
+    if (h->zero_copy) {
+        if (int rc = ensure_mapped(&h->m_v, nz)) return rc;
+        if (int rc = ensure_mapped(&h->m_trZbar, nz)) return rc;
+        if (K_bar)
+            if (int rc = ensure_mapped(&h->m_Z, nz)) return rc;
+        if (K)
+            if (int rc = ensure_mapped(&h->m_trK, nk)) return rc;
+        if (Zref_bar)
+            if (int rc = ensure_mapped(&h->m_zout, nz)) return rc;
+        if (K_bar)
+            if (int rc = ensure_mapped(&h->m_trKbar, nk)) return rc;
+        if (x0_bar)
+            if (int rc = ensure_mapped(&h->m_trx0, nx)) return rc;
+        std::memcpy(h->m_v.host, Zout, nz * sizeof(double));
+        std::memcpy(h->m_trZbar.host, Zbar, nz * sizeof(double));
+        if (K_bar) std::memcpy(h->m_Z.host, Zref, nz * sizeof(double));
+        if (K) std::memcpy(h->m_trK.host, K, nk * sizeof(double));
+        if (Zref_bar) std::memcpy(h->m_zout.host, Zref_bar, nz * sizeof(double));
+        QLN_HIP(qln::launch_tracking_rollout_vjp(h->p, K_bar ? h->m_Z.dev : h->m_v.dev, K ? h->m_trK.dev : nullptr, h->m_v.dev,
+                                                 h->m_trZbar.dev, Zref_bar ? h->m_zout.dev : nullptr,
+                                                 K_bar ? h->m_trKbar.dev : nullptr, x0_bar ? h->m_trx0.dev : nullptr, h->stream));
+        QLN_HIP(hipStreamSynchronize(h->stream));
+        if (Zref_bar) std::memcpy(Zref_bar, h->m_zout.host, nz * sizeof(double));
+        if (K_bar) std::memcpy(K_bar, h->m_trKbar.host, nk * sizeof(double));
+        if (x0_bar) std::memcpy(x0_bar, h->m_trx0.host, nx * sizeof(double));
+        return QLN_OK;
+    }
+    if (int rc = ensure(&h->s_v, nz)) return rc;
+    if (int rc = ensure(&h->s_trZbar, nz)) return rc;
+    if (K_bar)
+        if (int rc = ensure(&h->s_Z, nz)) return rc;
+    if (K)
+        if (int rc = ensure(&h->s_trK, nk)) return rc;
+    if (Zref_bar)
+        if (int rc = ensure(&h->s_zout, nz)) return rc;
+    if (K_bar)
+        if (int rc = ensure(&h->s_trKbar, nk)) return rc;
+    if (x0_bar)
+        if (int rc = ensure(&h->s_trx0, nx)) return rc;
+    QLN_HIP(hipMemcpyAsync(h->s_v, Zout, nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    QLN_HIP(hipMemcpyAsync(h->s_trZbar, Zbar, nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (K_bar) QLN_HIP(hipMemcpyAsync(h->s_Z, Zref, nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (K) QLN_HIP(hipMemcpyAsync(h->s_trK, K, nk * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (Zref_bar) QLN_HIP(hipMemcpyAsync(h->s_zout, Zref_bar, nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    QLN_HIP(qln::launch_tracking_rollout_vjp(h->p, K_bar ? h->s_Z : h->s_v, K ? h->s_trK : nullptr, h->s_v, h->s_trZbar,
+                                             Zref_bar ? h->s_zout : nullptr, K_bar ? h->s_trKbar : nullptr,
+                                             x0_bar ? h->s_trx0 : nullptr, h->stream));
+    if (Zref_bar) QLN_HIP(hipMemcpyAsync(Zref_bar, h->s_zout, nz * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (K_bar) QLN_HIP(hipMemcpyAsync(K_bar, h->s_trKbar, nk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (x0_bar) QLN_HIP(hipMemcpyAsync(x0_bar, h->s_trx0, nx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     QLN_HIP(hipStreamSynchronize(h->stream));
     return QLN_OK;
 }

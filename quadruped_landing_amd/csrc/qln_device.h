@@ -156,6 +156,10 @@ hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const dou
                                double* K, double* P, hipStream_t stream);
 hipError_t launch_tracking_rollout(const BatchParams& p, const double* Zref, const double* K, const double* x0, double* Zout,
                                    hipStream_t stream);
+// the roll-out's reverse sweep at Zout's trajectory: cotangent Zbar -> Zref_bar, K_bar, x0_bar (each may be null; K_bar
+// needs K and reads Zref's states) (qln_tracking_kernels.hip)
+hipError_t launch_tracking_rollout_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
+                                       const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, hipStream_t stream);
 // batched Gauss-Newton step on the constraint violation, CGLS per problem in LDS (qln_solver_kernels.hip)
 size_t gauss_newton_lds_bytes(int32_t N);
 hipError_t launch_gauss_newton_step(const BatchParams& p, const double* Z, const double* c, double* dZ, int max_iters,

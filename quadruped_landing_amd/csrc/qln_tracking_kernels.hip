@@ -19,6 +19,16 @@
 // The jump knot's A row 14 is the jump map's (the clock is kept), not the Jacobian's masked zero (quirk Q1).
 //
 // k_tracking_rollout: one lane per problem, the solver's step_forward (qln_kernel_common.h) on the fed-back forces.
+//
+// k_tracking_rollout_vjp: the reverse sweep of the roll-out.  One problem per row of sixteen lanes, as
+// k_tracking_lqr; lane j < 15 owns lam[j], column j of A_k, row j of B_k and of the h column, and column j of K and K_bar;
+// lane 15 holds lam = 0 and only stores a u slot.  Nothing goes through LDS:
+//   (A'lam)[j] needs lam at rows j, 2, 9 and j-7 -- two DPP row broadcasts and one row shift;
+//   B'lam and the h column are row sums (four DPP steps each).  Rows 2 and 9 (theta, omega) are dense in B and h, but
+//   bilinear in (positions, forces): their share of B'lam is folded into the row sums as lane j's x_j times a sign pattern
+//   (d tau / d x_j d F_m), so no lane forms a whole row;
+//   K_k'ubar and K_bar = -ubar dx' are four FMAs / four products per lane on column j, stored coalesced.
+// The knot's slices (x_k, u_k, Zbar, x_ref and K column j) are loaded one knot ahead.
 #include "qln_kernel_common.h"
 
 #include <cstdlib>
@@ -339,6 +349,166 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout(BatchParams P, const
     }
 }
 
+
+// v from lane (ctrl) of the same DPP row, as two 32-bit moves
+template <int kCtrl>
+__device__ __forceinline__ double dpp_f64(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), kCtrl, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), kCtrl, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+// sum over the sixteen lanes of a row, the same bits in every lane (each step adds a commuted pair)
+__device__ __forceinline__ double row_sum16(double v) {
+    v += dpp_f64<0xB1>(v);   // quad_perm [1,0,3,2]
+    v += dpp_f64<0x4E>(v);   // quad_perm [2,3,0,1]
+    v += dpp_f64<0x141>(v);  // row_half_mirror
+    v += dpp_f64<0x140>(v);  // row_mirror
+    return v;
+}
+
+// One knot's inputs, as lane j of a row reads them: its own x_j, Zbar x_j, x_ref,j and K column j, and the knot's applied
+// controls and their cotangents (the same five values in every lane of the row).
+struct VjpKnot {
+    double x, zb, xr, u[5], ub[5], kc[4];
+};
+
+template <bool kHasK>
+__device__ __forceinline__ void vjp_load(VjpKnot& s, const double* __restrict__ Zo, const double* __restrict__ Zb,
+                                         const double* __restrict__ Zr, const double* __restrict__ Kk, int k, int j) {
+    s.x = Zo[20 * k + j];
+    s.zb = Zb[20 * k + j];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        s.u[i] = Zo[20 * k + 15 + i];
+        s.ub[i] = Zb[20 * k + 15 + i];
+    }
+    s.xr = Zr ? Zr[20 * k + j] : 0.0;
+    if constexpr (kHasK) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) s.kc[m] = Kk[15 * m + j];
+    }
+}
+
+// The reverse sweep of k_tracking_rollout (include/qln_evaluator.h): lam_{N-1} = Zbar[x_{N-1}], then per knot k = N-2..0
+//   ubar = Zbar[u_k] + B_k'lam_{k+1},  lam_k = Zbar[x_k] + A_k'lam_{k+1} - K_k'ubar[0:4],
+// with xref_bar_k = K_k'ubar[0:4], Kbar_k = -ubar[0:4] (x_k - x_ref,k)'.  A_k, B_k and the h column are the derivative of
+// step_forward at Zout's (x_k, u_k): the evaluator's closed form, with the jump knot's clock row kept (1 at x[14] and at h).
+// Zr is read only for Kbar (may be null otherwise).
+template <bool kHasK>
+__global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, const double* __restrict__ Zref,
+                                                                const double* __restrict__ Kg, const double* __restrict__ Zout,
+                                                                const double* __restrict__ Zbar, double* __restrict__ Zref_bar,
+                                                                double* __restrict__ Kbar, double* __restrict__ x0_bar) {
+    const int lane = threadIdx.x;
+    const int ln = lane & 15, row = lane >> 4;
+    const bool own = ln < 15;
+    const int j = own ? ln : 14;  // lane 15 reads lane 14's slots and contributes nothing
+    const int wave = xcd_contiguous_index(blockIdx.x, (P.B + kRows - 1) / kRows);
+    const int b = wave * kRows + row;
+    const bool valid = b < P.B;
+    const int bc = valid ? b : P.B - 1;
+    const int N = P.N;
+    const ProblemDesc pd = P.desc[bc];
+    const int kt = pd.k_trans, im = pd.init_mode;
+    const double g = P.g, imb = 1.0 / P.mb, imf = 1.0 / P.mf;
+    const double iIb = 12.0 / (P.mb * (P.lb * P.lb));
+    const double* __restrict__ Zo = Zout + (int64_t)bc * P.z_stride;
+    const double* __restrict__ Zb = Zbar + (int64_t)bc * P.z_stride;
+    const double* __restrict__ Zr = Kbar ? Zref + (int64_t)bc * P.z_stride : nullptr;
+    const double* __restrict__ Kb = kHasK ? Kg + (int64_t)bc * (N - 1) * (QLN_TRACK_NU * QLN_NX) : nullptr;
+
+    // ---- lane j's constant pattern: what column j of A, row j of B and h_j are built from ----
+    const bool pos = j < 7;                 // position row (h^2/2 in B) or velocity / clock row (h)
+    const int p = pos ? j : j - 7;          // the position index the row belongs to (7: the clock)
+    const int foot = (p == 3 || p == 4) ? 1 : (p == 5 || p == 6) ? 2 : 0;
+    const bool jrow = j == 4 || j == 6 || (j >= 10 && j <= 13);  // rows the jump map zeroes
+    const bool cpl = j >= 7 && j <= 13;     // A(j-7, j) = h (times the foot's flag): velocity -> position
+    const bool kcpl = j == 11 || j == 13;   // ... into a row the jump map zeroes
+    // e[m]: the force columns of B's row j (body rows: F_p and F_{p+2} through 1/mb; foot rows: their foot's F_{p-3});
+    // sg[m]: d^2 tau / d x_p d F_m of the torque tau = r1x F1y - r1y F1x + r2x F2y - r2y F2x (r = foot - body position)
+    double e[4], sg[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        e[m] = ((p <= 1 && (m == p || m == p + 2)) || (foot && m == p - 3)) ? 1.0 : 0.0;
+        sg[m] = 0.0;
+    }
+    if (p == 0) sg[1] = sg[3] = -1.0;
+    if (p == 1) sg[0] = sg[2] = 1.0;
+    if (p == 3) sg[1] = 1.0;
+    if (p == 4) sg[0] = -1.0;
+    if (p == 5) sg[3] = 1.0;
+    if (p == 6) sg[2] = -1.0;
+    // B row j = hpow * inv * e, h_j = hfac * (sum_m e[m] F_m * inv + gy) (the clock: 1)
+    const double inv = (p <= 1) ? imb : foot ? -imf : 0.0;
+    const double gy = (p == 1 || p == 4 || p == 6) ? g : (j == 14) ? 1.0 : 0.0;
+
+    double lam = own ? Zb[20 * (N - 1) + j] : 0.0;
+    if (valid && Zref_bar && own) Zref_bar[(int64_t)b * P.z_stride + 20 * (N - 1) + j] = 0.0;  // x_ref,N-1: never read
+    VjpKnot cur, nxt;
+    vjp_load<kHasK>(nxt, Zo, Zb, Zr, Kb + (kHasK ? (int64_t)(N - 2) * 60 : 0), N - 2, j);
+    for (int k = N - 2; k >= 0; --k) {
+        cur = nxt;
+        if (k > 0) vjp_load<kHasK>(nxt, Zo, Zb, Zr, Kb + (kHasK ? (int64_t)(k - 1) * 60 : 0), k - 1, j);
+        const int K1 = k + 1;
+        const int mode = (K1 <= kt - 1) ? im : 3;
+        const double m1 = (mode == 2) ? 1.0 : 0.0, m2 = (mode == 1) ? 1.0 : 0.0;
+        const double keep = (K1 == kt - 1) ? 0.0 : 1.0;
+        const double F0 = cur.u[0], F1 = cur.u[1], F2 = cur.u[2], F3 = cur.u[3], h = cur.u[4];
+        const double h2 = h * h;
+        const double Aw = h * iIb, At = 0.5 * h2 * iIb, Bt = h2 * h * iIb * (1.0 / 6.0), Ct = h2 * h2 * iIb * (1.0 / 24.0);
+        const double ga1 = g * (1.0 - m1), ga2 = g * (1.0 - m2);
+        const double taua = ga1 * F0 + ga2 * F2;
+        // the lane's masks for this knot
+        const double fm = foot == 1 ? m1 : foot == 2 ? m2 : 1.0;  // the row's foot is free
+        const double km = jrow ? keep : 1.0;
+        const double rmask = fm * km;                           // row j of B and of the h column
+        const double fmv = pos ? 1.0 : fm;                      // w = m foot velocity - body velocity
+        const double cmask = cpl ? fm * (kcpl ? keep : 1.0) : 0.0;
+        // cross-lane lam: rows 2 and 9 (row broadcasts) and j-7 (row shift)
+        const double lam2 = dpp_f64<0x152>(lam), lam9 = dpp_f64<0x159>(lam), lamc = dpp_f64<0x117>(lam);
+        // ---- A'lam, column j: diagonal, rows 2 and 9 (h-power times d tau / d x_j), row j-7 ----
+        const double sF = ((sg[0] * F0 + sg[1] * F1) + sg[2] * F2) + sg[3] * F3;
+        const double phi = fmv * sF;
+        const double alam = fma(h * cmask, lamc, fma((pos ? Aw : At) * phi, lam9, fma((pos ? At : Bt) * phi, lam2, km * lam)));
+        // ---- the lane's shares of B'lam and of the h column ----
+        const double Lr = rmask * lam;
+        const double Fs = ((e[0] * F0 + e[1] * F1) + e[2] * F2) + e[3] * F3;
+        const double bco = (pos ? 0.5 * h2 : h) * inv * Lr;
+        const double al = At * lam2 + Aw * lam9, be = Bt * lam2 + At * lam9, gm = Ct * lam2 + Bt * lam9;
+        const double xs = fmv * cur.x;
+        const double tco = (pos ? al : be) * xs;                // rows 2 and 9 of B, through d tau / d F_m
+        double red[5];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) red[m] = fma(e[m], bco, sg[m] * tco);
+        const double hco = pos ? fma(Aw, lam2, iIb * lam9) : al;  // rows 2 and 9 of the h column, through tau
+        red[4] = fma(cmask * cur.x, lamc, fma(hco * xs, sF, (pos ? h : 1.0) * fma(Fs, inv, gy) * Lr));
+        double ub[5];
+#pragma unroll
+        for (int m = 0; m < 5; ++m) ub[m] = cur.ub[m] + row_sum16(red[m]);
+        ub[0] = fma(gm, ga1, ub[0]);
+        ub[2] = fma(gm, ga2, ub[2]);
+        ub[4] = fma(be, taua, ub[4]);
+        // ---- K'ubar, lam_k, and the outputs of the knot ----
+        double kub = 0.0;
+        if constexpr (kHasK) kub = ((cur.kc[0] * ub[0] + cur.kc[1] * ub[1]) + cur.kc[2] * ub[2]) + cur.kc[3] * ub[3];
+        lam = own ? (cur.zb + alam) - kub : 0.0;
+        if (valid) {
+            if (Zref_bar) {
+                double* __restrict__ o = Zref_bar + (int64_t)b * P.z_stride + 20 * k;
+                o[ln] = own ? kub : ub[0];
+                if (ln < 4) o[16 + ln] = ln == 0 ? ub[1] : ln == 1 ? ub[2] : ln == 2 ? ub[3] : ub[4];
+            }
+            if (kHasK && Kbar && own) {
+                double* __restrict__ o = Kbar + ((int64_t)b * (N - 1) + k) * (QLN_TRACK_NU * QLN_NX);
+                const double dx = cur.x - cur.xr;
+#pragma unroll
+                for (int m = 0; m < 4; ++m) o[15 * m + j] = -ub[m] * dx;
+            }
+        }
+    }
+    if (valid && x0_bar && own) x0_bar[(int64_t)b * QLN_NX + j] = lam;
+}
+
 }  // namespace
 
 hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const double* Rd, const double* Qfd, const double* Zref,
@@ -366,6 +536,16 @@ hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const dou
 hipError_t launch_tracking_rollout(const BatchParams& p, const double* Zref, const double* K, const double* x0, double* Zout,
                                    hipStream_t stream) {
     hipLaunchKernelGGL(k_tracking_rollout, dim3((p.B + kWave - 1) / kWave), dim3(kWave), 0, stream, p, Zref, K, x0, Zout);
+    return hipGetLastError();
+}
+
+hipError_t launch_tracking_rollout_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
+                                       const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, hipStream_t stream) {
+    const int waves = (p.B + kRows - 1) / kRows;
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(xcd_grid(waves)), dim3(kWave), 0, stream, p, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar);
+    };
+    K ? go(k_tracking_rollout_vjp<true>) : go(k_tracking_rollout_vjp<false>);
     return hipGetLastError();
 }
 

@@ -584,6 +584,60 @@ class HybridNLP:
         _lib.check(_lib.lib().qln_tracking_rollout_host(self._h, Zref.ctypes.data, kp, xp, out.ctypes.data))
         return out
 
+    # -- reverse-mode derivative of the closed-loop roll-out ---------------------------------------
+    def _vjp_want(self, K, want):
+        want = ("Zref", "K", "x0") if want is None else tuple(want)
+        bad = set(want) - {"Zref", "K", "x0"}
+        if bad:
+            raise ValueError(f"want: unknown outputs {sorted(bad)} (Zref, K, x0)")
+        if want == ("Zref", "K", "x0") and K is None:
+            want = ("Zref", "x0")  # the default asks for K_bar only where there are gains
+        return want
+
+    def tracking_rollout_vjp(self, Zref, Zout, Zbar, K=None, want=None):
+        """Reverse sweep of tracking_rollout at the trajectory Zout (device tensors, layout of Z): the cotangent Zbar of
+        (Zout's states and applied controls) -> (Zref_bar, K_bar, x0_bar), each None unless named in want (default: all
+        three, K_bar only when K is given).  Zref_bar is laid out like Z (zeros past n_nlp on a fresh buffer), K_bar like K
+        (B, N-1, 4, 15), x0_bar (B, 15).  Stream-ordered; semantics in include/qln_evaluator.h."""
+        T = _torch()
+        want = self._vjp_want(K, want)
+        self._check(Zref, self.dims.z_total, "Zref")
+        self._check(Zout, self.dims.z_total, "Zout")
+        self._check(Zbar, self.dims.z_total, "Zbar")
+        kp = None if K is None else self._check(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        zb = self.new_Z() if "Zref" in want else None
+        kb = T.zeros(tracking_k_shape(self.B, self.N), dtype=T.float64, device=self._dev()) if "K" in want else None
+        xb = T.zeros((self.B, n), dtype=T.float64, device=self._dev()) if "x0" in want else None
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        _lib.check(_lib.lib().qln_tracking_rollout_vjp(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), Zbar.data_ptr(),
+                                                       ptr(zb), ptr(kb), ptr(xb)))
+        return zb, kb, xb
+
+    def tracking_rollout_vjp_host(self, Zref, Zout, Zbar, K=None, want=None):
+        """The same with host arrays (synchronous): numpy (Zref_bar (z_total,), K_bar (B, N-1, 4, 15), x0_bar (B, 15))."""
+        want = self._vjp_want(K, want)
+        Zref, Zout, Zbar = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout"), self._host_Z(Zbar, "Zbar")
+        kp = None
+        if K is not None:
+            K = np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(-1))
+            if K.size != self.B * (self.N - 1) * _lib.TRACK_NU * n:
+                raise ValueError(f"K has {K.size} entries, expected {self.B * (self.N - 1) * _lib.TRACK_NU * n}")
+            kp = K.ctypes.data
+        zb = np.zeros(self.dims.z_total) if "Zref" in want else None
+        kb = np.zeros(tracking_k_shape(self.B, self.N)) if "K" in want else None
+        xb = np.zeros((self.B, n)) if "x0" in want else None
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        _lib.check(_lib.lib().qln_tracking_rollout_vjp_host(self._h, Zref.ctypes.data, kp, Zout.ctypes.data, Zbar.ctypes.data,
+                                                            ptr(zb), ptr(kb), ptr(xb)))
+        return zb, kb, xb
+
+    def differentiable_rollout(self, Zref, K=None, x0=None):
+        """tracking_rollout as a torch autograd op: returns Zout, differentiable in Zref, K and x0 (each a float64 CUDA
+        tensor or None).  The backward pass is one qln_tracking_rollout_vjp launch at the Zout the forward produced."""
+        from .rollout_grad import RolloutFunction
+
+        return RolloutFunction.apply(self, Zref, K, x0)
+
     def split_hvals(self, hvals):
         """(h_total,) values -> (step blocks (B, N-1, 55), terminal diagonals (B, 15)) as numpy arrays."""
         h = hvals.detach().cpu().numpy() if hasattr(hvals, "detach") else np.asarray(hvals)
