@@ -21,6 +21,16 @@
  * buffers; it owns only its handle (descriptor copies and, for MOI mode, lazily allocated staging) and what the
  * caller explicitly asks it to allocate with qln_vals_alloc_placed.
  *
+ * Host forms (the qln_*_host entry points, MOI mode included) take HOST pointers in the layouts of their device form
+ * and are synchronous.  The mode is chosen once, in qln_create: a batch with (z_total + c_total + j_total) * 8 bytes
+ * <= 8 MiB is evaluated on pinned host buffers mapped into the device's address space (the kernels read and write them
+ * directly: one launch, one synchronisation), a larger one is staged through device memory.
+ * qln_eval_hessian_lagrangian_host and qln_solve_host are always staged.  The handle allocates each buffer on first
+ * use, zero-filled, and keeps it until qln_destroy.  Three arguments are in-out and copied in whole, so that their
+ * entries from n_nlp to z_stride come back as the caller's buffer held them: Zout of qln_tracking_rollout_host,
+ * Zref_bar of qln_tracking_rollout_vjp_host and Z of qln_solve_host.  The padding of every other result (past n_nlp in
+ * the layout of Z, between the problems of c, vals and hvals) comes back as zeros.
+ *
  * Layouts (all FP64, all offsets/strides in doubles):
  *   Z     problem b at Z + b*z_stride, length n_nlp = 20N-5,
  *         [x_1 u_1 x_2 u_2 ... x_{N-1} u_{N-1} x_N]           (src/nlp.jl:38-39,94-102)
@@ -292,8 +302,8 @@ int qln_solve_default_options(qln_solve_options* opt);
  * src/main.ipynb:222).  opt = NULL: the defaults, which are the reference's literals.  Needs no handle and no GPU. */
 int qln_variable_bounds(int32_t N, const qln_solve_options* opt /* NULL = defaults */, double* x_l, double* x_u);
 int qln_solve(qln_handle* h, double* Z, const qln_solve_options* opt /* NULL = defaults */, double* info);
-/* the same with HOST pointers (MOI-mode style: Z copied in, solved on the GPU, copied back; synchronous) -- what the
- * Julia veneer calls in place of `solve(Z0, nlp)`.  info (host, may be NULL): [B][QLN_SOLVE_INFO_STRIDE]. */
+/* the same as a host form (see "Host forms" above: Z copied in, solved on the GPU, copied back) -- what the Julia veneer
+ * calls in place of `solve(Z0, nlp)`.  info (host, may be NULL): [B][QLN_SOLVE_INFO_STRIDE]. */
 int qln_solve_host(qln_handle* h, double* Z, const qln_solve_options* opt, double* info);
 /* OPT-IN EXTENSION WITHOUT A REFERENCE ORACLE.  The leg-length ("kinematic") constraint group exists in the reference
  * only as commented-out code (src/constraints.jl:115-138 values, :276-288 Jacobian, src/nlp.jl:60,70 index range and
@@ -387,7 +397,7 @@ int qln_tracking_lqr(qln_handle* h, const double* Zref, const double* Qdiag, con
  * qln_eval_objective / qln_constraint_violation.  Entries from n_nlp to z_stride are never written.  K == NULL is the
  * open-loop roll-out of Zref's controls.  Zout must not overlap Zref.  x0: device [B][15] or NULL.  Stream-ordered. */
 int qln_tracking_rollout(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout);
-/* the same with HOST pointers, synchronous (staged through device memory) */
+/* the same as host forms (see "Host forms" above; Zout is in-out) */
 int qln_tracking_lqr_host(qln_handle* h, const double* Zref, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
                           double* K, double* P);
 int qln_tracking_rollout_host(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout);
@@ -419,8 +429,7 @@ int qln_tracking_rollout_host(qln_handle* h, const double* Zref, const double* K
  * init_mode, as the forward call.  Device pointers, stream-ordered; needs no cost table. */
 int qln_tracking_rollout_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
                              double* Zref_bar, double* K_bar, double* x0_bar);
-/* the same with HOST pointers, synchronous (staged through the handle's buffers); Zref_bar's entries past n_nlp come back
- * as the caller's buffer held them */
+/* the same as a host form (see "Host forms" above; Zref_bar is in-out) */
 int qln_tracking_rollout_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
                                   double* Zref_bar, double* K_bar, double* x0_bar);
 /* Z <- Z + N(0, sigma^2) on every entry, step lengths h then clipped to [h_min, h_max] (redraw_h = 0) or redrawn
@@ -440,17 +449,15 @@ int qln_set_lqr_cost(qln_handle* h, const double* Qdiag, const double* Rdiag, co
 /* Copies the handle's cost table ([cost_batch][N][41]) to a host buffer; cost_batch is returned through *cost_batch. */
 int qln_get_cost(qln_handle* h, double* cost_host, int32_t* cost_batch);
 
-/* MOI mode: HOST pointers, synchronous.  Same layouts.  Batches of up to 8 MB per callback are evaluated on mapped
- * pinned host memory directly (one launch, no copies); larger ones are staged through device memory. */
+/* MOI mode: the host forms of the evaluator (see "Host forms" above) */
 int qln_eval_objective_host(qln_handle* h, const double* Z, double* f);
 int qln_eval_objective_gradient_host(qln_handle* h, const double* Z, double* grad);
 int qln_eval_constraint_host(qln_handle* h, const double* Z, double* c);
 int qln_eval_constraint_jacobian_host(qln_handle* h, const double* Z, double* vals);
-/* MOI mode of qln_eval_hessian_lagrangian: host pointers, synchronous, same layouts (staged through device memory) */
+/* MOI mode of qln_eval_hessian_lagrangian (:Hess) */
 int qln_eval_hessian_lagrangian_host(qln_handle* h, const double* Z, const double* sigma, const double* mu, double* hvals);
 /* MOI mode of qln_eval_hessian_lagrangian_product (:HessVec) and of qln_eval_constraint_jvp / _vjp (:JacVec,
- * eval_constraint_jacobian_product / _transpose_product): host pointers, synchronous, same layouts.  The padding of an
- * output's layout (past n_nlp, between problems of c) comes back as zeros. */
+ * eval_constraint_jacobian_product / _transpose_product) */
 int qln_eval_hessian_lagrangian_product_host(qln_handle* h, const double* Z, const double* sigma, const double* mu,
                                              const double* v, double* y);
 int qln_eval_constraint_jvp_host(qln_handle* h, const double* Z, const double* v, double* y);

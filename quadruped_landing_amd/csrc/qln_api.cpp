@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <limits>
 #include <new>
 #include <string>
@@ -79,6 +80,32 @@ void cinds_of(int32_t N, int32_t kt, int32_t out[14]) {
     }
 }
 
+int64_t tracking_k_total(const qln_dims& D) { return (int64_t)D.B * (D.N - 1) * QLN_TRACK_NU * QLN_NX; }
+int64_t tracking_p_total(const qln_dims& D) { return (int64_t)D.B * D.N * QLN_TRACK_P_NNZ; }
+
+// The buffers of the host forms (qln_*_host), one per role.  A role's size follows from the role and the handle's layout
+// (host_role_size): no form can allocate a buffer that another finds too small.  An in-out argument is copied in whole,
+// padding included, so its role returns no out-only result: that padding would reach the next caller.
+enum HostRole {
+    kZ,      // in: the point Z / Zref (in-out of qln_solve_host)           layout of Z
+    kV,      // in: a direction v, the vjp's Zout                           layout of Z
+    kZbar,   // in: the vjp's cotangent Zbar                                layout of Z
+    kZio,    // in-out: the roll-out's Zout, the vjp's Zref_bar             layout of Z
+    kZout,   // out: H v, J' lam (padding zero)                             layout of Z
+    kGrad,   // out: grad f                                                 layout of Z
+    kC,      // out: c, J v (padding zero)                                  layout of c
+    kMu,     // in: the multipliers mu / lam                                layout of c
+    kVals,   // out: the Jacobian values                                    layout of vals
+    kF,      // out: f                                                      [B]
+    kSigma,  // in: sigma                                                   [B]
+    kHvals,  // out: the Hessian values                                     (B-1) h_stride + nnz
+    kK,      // out of the LQR, in to the roll-out and its vjp: the gains   [B][N-1][4][15]
+    kKbar,   // out: the gains' cotangent                                   layout of K
+    kP,      // out: the cost-to-go                                         [B][N][120]
+    kX0,     // in: the roll-out's x0; out: the vjp's x0_bar                [B][15]
+    kHostRoles
+};
+
 }  // namespace
 
 struct qln_handle {
@@ -93,35 +120,18 @@ struct qln_handle {
     qln::ProblemDesc* d_desc = nullptr;
     double* d_bnd = nullptr;
     double* d_cost = nullptr;
-    // staging for host-pointer mode
-    double* s_Z = nullptr;
-    double* s_c = nullptr;
-    double* s_vals = nullptr;
-    double* s_f = nullptr;
-    double* s_grad = nullptr;
-    double* s_sigma = nullptr;  // Lagrangian Hessian (qln_eval_hessian_lagrangian_host): sigma and the multipliers in,
-    double* s_mu = nullptr;     // the values out
-    double* s_hvals = nullptr;
-    int64_t h_stride = 0;       // doubles between consecutive problems' Hessian segments (qln_hessian_layout)
-    double* s_v = nullptr;      // products (qln_eval_*_product_host, qln_eval_constraint_jvp/vjp_host): the vector in the
-    double* s_zout = nullptr;   // layout of Z, a result in the layout of Z
-    double* s_trK = nullptr;    // TVLQR tracking (qln_tracking_*_host): gains, cost-to-go, initial states
-    double* s_trP = nullptr;
-    double* s_trx0 = nullptr;
-    double* s_trZbar = nullptr;  // the roll-out's vjp (qln_tracking_rollout_vjp_host): the cotangent in, the gains' cotangent out
-    double* s_trKbar = nullptr;
-    std::vector<double> h_vals_one;
-    // zero-copy MOI mode (small batches): pinned host buffers mapped into the device's address space -- the kernels read
-    // Z from and write their results to host memory directly, so a callback is one launch and one synchronisation
+    int64_t h_stride = 0;  // doubles between consecutive problems' Hessian segments (qln_hessian_layout)
+    // the host forms' buffers by HostRole, allocated on first use and kept until qln_destroy: device memory (staged), or
+    // -- zero_copy, small batches -- pinned host memory mapped into the device's address space, which the kernels read
+    // and write directly, so that a callback is one launch and one synchronisation
+    double* staged[kHostRoles] = {};
     struct Mapped {
         double* host = nullptr;
         double* dev = nullptr;
     };
-    Mapped m_Z, m_c, m_vals, m_f, m_grad;
-    Mapped m_v, m_mu, m_sigma, m_zout;  // the products' inputs (v, mu / lam, sigma) and their result in the layout of Z
-    Mapped m_trK, m_trP, m_trx0;        // TVLQR tracking: gains, cost-to-go, initial states
-    Mapped m_trZbar, m_trKbar;          // the roll-out's vjp: the cotangent in the layout of Z, the gains' cotangent
+    Mapped mapped[kHostRoles];
     bool zero_copy = false;
+    std::vector<double> h_vals_one;  // one problem's Jacobian values, staged for the dense scatter
     // dense MOI scatter: per problem, where each value of the vals segment goes in the column-major matrix, and the
     // write-set's explicit zeros (built on first use)
     struct DenseMap {
@@ -153,26 +163,92 @@ int upload(T** dst, const T* src, size_t n) {
     return QLN_OK;
 }
 
-int ensure(double** buf, int64_t n) {
-    if (*buf) return QLN_OK;
-    QLN_HIP(hipMalloc(reinterpret_cast<void**>(buf), std::max<int64_t>(n, 1) * sizeof(double)));
-    // the padding between problems is never written by the kernels: the caller gets zeros there, not stale memory
-    QLN_HIP(hipMemset(*buf, 0, std::max<int64_t>(n, 1) * sizeof(double)));
-    return QLN_OK;
+int64_t host_role_size(const qln_handle* h, HostRole r) {
+    const qln_dims& D = h->dims;
+    switch (r) {
+        case kZ: case kV: case kZbar: case kZio: case kZout: case kGrad: return D.z_total;
+        case kC: case kMu: return D.c_total;
+        case kVals: return D.j_total;
+        case kF: case kSigma: return D.B;
+        case kHvals: return (int64_t)(D.B - 1) * h->h_stride + hessian_nnz(D.N);  // no padding behind the last problem
+        case kK: case kKbar: return tracking_k_total(D);
+        case kP: return tracking_p_total(D);
+        case kX0: return (int64_t)D.B * QLN_NX;
+        case kHostRoles: break;
+    }
+    return 0;
 }
 
-int ensure_mapped(qln_handle::Mapped* m, int64_t n) {
-    if (m->host) return QLN_OK;
+// The role's buffer, mapped or in device memory, allocated on first use and zero-filled: the padding the kernels never
+// write comes back as zeros, not stale memory.
+int acquire(qln_handle* h, HostRole r, bool mapped) {
+    const size_t bytes = std::max<int64_t>(host_role_size(h, r), 1) * sizeof(double);
+    if (!mapped) {
+        double*& buf = h->staged[r];
+        if (buf) return QLN_OK;
+        QLN_HIP(hipMalloc(reinterpret_cast<void**>(&buf), bytes));
+        QLN_HIP(hipMemset(buf, 0, bytes));
+        return QLN_OK;
+    }
+    qln_handle::Mapped& m = h->mapped[r];
+    if (m.host) return QLN_OK;
     void* hp = nullptr;
-    QLN_HIP(hipHostMalloc(&hp, std::max<int64_t>(n, 1) * sizeof(double), hipHostMallocMapped));
-    std::memset(hp, 0, std::max<int64_t>(n, 1) * sizeof(double));  // padding the kernels never write stays zero
+    QLN_HIP(hipHostMalloc(&hp, bytes, hipHostMallocMapped));
+    std::memset(hp, 0, bytes);
     void* dp = nullptr;
     if (hipError_t e = hipHostGetDevicePointer(&dp, hp, 0); e != hipSuccess) {
         (void)hipHostFree(hp);
         return fail(QLN_ERR_HIP, std::string("hipHostGetDevicePointer: ") + hipGetErrorString(e));
     }
-    m->host = static_cast<double*>(hp);
-    m->dev = static_cast<double*>(dp);
+    m.host = static_cast<double*>(hp);
+    m.dev = static_cast<double*>(dp);
+    return QLN_OK;
+}
+
+// One argument of a host form: `n` doubles at `at` in its role's buffer (n < 0: the whole buffer), copied in from src
+// before the launch and back to dst after it.  Neither given: an optional argument the caller left NULL -- no buffer,
+// no copy, and the launch sees NULL.  view (out only): set to where the results can be read, the mapped buffer itself
+// (then nothing is copied to dst) or dst.
+struct HostArg {
+    HostRole role;
+    const double* src;
+    double* dst;
+    int64_t n, at;
+    const double** view;
+};
+HostArg copy_in(HostRole r, const double* p) { return {r, p, nullptr, -1, 0, nullptr}; }
+HostArg copy_out(HostRole r, double* p) { return {r, nullptr, p, -1, 0, nullptr}; }
+HostArg copy_inout(HostRole r, double* p) { return {r, p, p, -1, 0, nullptr}; }
+
+// The one staging path of the host forms.  Mapped (h->zero_copy, unless the form passes may_map = false) or staged, it
+// acquires every passed argument's buffer, copies the inputs in, calls launch(d, mapped) with d[role] the device-visible
+// buffer of each passed argument (NULL for the rest), copies the outputs back and synchronises the stream once.
+template <class Launch>
+int host_call(qln_handle* h, std::initializer_list<HostArg> args, Launch&& launch, bool may_map = true) {
+    const bool mapped = may_map && h->zero_copy;
+    auto bytes = [&](const HostArg& a) { return (a.n < 0 ? host_role_size(h, a.role) : a.n) * sizeof(double); };
+    double* d[kHostRoles] = {};
+    for (const HostArg& a : args)
+        if (a.src || a.dst) {
+            if (int rc = acquire(h, a.role, mapped)) return rc;
+            d[a.role] = mapped ? h->mapped[a.role].dev : h->staged[a.role];
+        }
+    for (const HostArg& a : args) {
+        if (!a.src) continue;
+        if (mapped) std::memcpy(h->mapped[a.role].host + a.at, a.src, bytes(a));
+        else QLN_HIP(hipMemcpyAsync(d[a.role] + a.at, a.src, bytes(a), hipMemcpyHostToDevice, h->stream));
+    }
+    QLN_HIP(launch(d, mapped));
+    if (!mapped)
+        for (const HostArg& a : args)
+            if (a.dst) QLN_HIP(hipMemcpyAsync(a.dst, d[a.role] + a.at, bytes(a), hipMemcpyDeviceToHost, h->stream));
+    QLN_HIP(hipStreamSynchronize(h->stream));
+    for (const HostArg& a : args) {
+        if (!a.dst) continue;
+        const double* v = mapped ? h->mapped[a.role].host + a.at : a.dst;
+        if (a.view) *a.view = v;
+        else if (mapped) std::memcpy(a.dst, v, bytes(a));
+    }
     return QLN_OK;
 }
 
@@ -358,12 +434,11 @@ int qln_destroy(qln_handle* h) {
         for (auto& p : h->placed)
             if (int r = release_placed(p); r != QLN_OK && rc == QLN_OK) rc = r;
     }
-    for (qln_handle::Mapped* m : {&h->m_Z, &h->m_c, &h->m_vals, &h->m_f, &h->m_grad, &h->m_v, &h->m_mu, &h->m_sigma, &h->m_zout,
-                                 &h->m_trK, &h->m_trP, &h->m_trx0, &h->m_trZbar, &h->m_trKbar})
-        if (m->host) (void)hipHostFree(m->host);
-    void* bufs[] = {h->d_desc, h->d_bnd, h->d_cost, h->s_Z, h->s_c, h->s_vals, h->s_f, h->s_grad, h->solve_scratch,
-                    h->s_sigma, h->s_mu, h->s_hvals, h->s_v, h->s_zout, h->s_trK, h->s_trP, h->s_trx0,
-                    h->s_trZbar, h->s_trKbar};
+    for (const qln_handle::Mapped& m : h->mapped)
+        if (m.host) (void)hipHostFree(m.host);
+    for (double* b : h->staged)
+        if (b) (void)hipFree(b);
+    void* bufs[] = {h->d_desc, h->d_bnd, h->d_cost, h->solve_scratch};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     delete h;
@@ -845,14 +920,15 @@ int qln_solve_host(qln_handle* h, double* Z, const qln_solve_options* opt, doubl
     if (int rc = check_handle(h)) return rc;
     if (!Z) return fail(QLN_ERR_INVALID_ARGUMENT, "qln_solve_host: null Z");
     if (int rc = bind_device(h)) return rc;
-    if (int rc = ensure(&h->s_Z, h->dims.z_total)) return rc;
+    if (int rc = acquire(h, kZ, false)) return rc;
+    double* dZ = h->staged[kZ];
     double* d_info = nullptr;
     const size_t ninfo = (size_t)h->dims.B * QLN_SOLVE_INFO_STRIDE;
     if (info) QLN_HIP(hipMalloc(reinterpret_cast<void**>(&d_info), ninfo * sizeof(double)));
     int rc = QLN_OK;
-    hipError_t e = hipMemcpyAsync(h->s_Z, Z, h->dims.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) rc = qln_solve(h, h->s_Z, opt, d_info);
-    if (e == hipSuccess && rc == QLN_OK) e = hipMemcpyAsync(Z, h->s_Z, h->dims.z_total * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    hipError_t e = hipMemcpyAsync(dZ, Z, h->dims.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) rc = qln_solve(h, dZ, opt, d_info);
+    if (e == hipSuccess && rc == QLN_OK) e = hipMemcpyAsync(Z, dZ, h->dims.z_total * sizeof(double), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess && rc == QLN_OK && info) e = hipMemcpyAsync(info, d_info, ninfo * sizeof(double), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess && rc == QLN_OK) e = hipStreamSynchronize(h->stream);
     if (d_info) (void)hipFree(d_info);
@@ -968,9 +1044,6 @@ static int check_tracking_rollout_args(const qln_handle* h, const double* Zref, 
     return QLN_OK;
 }
 
-static int64_t tracking_k_total(const qln_dims& D) { return (int64_t)D.B * (D.N - 1) * QLN_TRACK_NU * QLN_NX; }
-static int64_t tracking_p_total(const qln_dims& D) { return (int64_t)D.B * D.N * QLN_TRACK_P_NNZ; }
-
 int qln_tracking_lqr(qln_handle* h, const double* Zref, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
                      double* K, double* P) {
     if (int rc = check_tracking_lqr_args(h, Zref, Qdiag, Rdiag, Qfdiag, K, "qln_tracking_lqr")) return rc;
@@ -986,76 +1059,22 @@ int qln_tracking_rollout(qln_handle* h, const double* Zref, const double* K, con
     return QLN_OK;
 }
 
-// The host forms: inputs copied into mapped pinned buffers (zero_copy, small batches) or into the handle's device staging,
-// one launch, the results copied back -- the buffers are allocated on first use and kept until qln_destroy.
 int qln_tracking_lqr_host(qln_handle* h, const double* Zref, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
                           double* K, double* P) {
     if (int rc = check_tracking_lqr_args(h, Zref, Qdiag, Rdiag, Qfdiag, K, "qln_tracking_lqr_host")) return rc;
     if (int rc = bind_device(h)) return rc;
-    const qln_dims& D = h->dims;
-    const int64_t nk = tracking_k_total(D), np = tracking_p_total(D);
-    if (h->zero_copy) {
-        if (int rc = ensure_mapped(&h->m_Z, D.z_total)) return rc;
-        if (int rc = ensure_mapped(&h->m_trK, nk)) return rc;
-        if (P)
-            if (int rc = ensure_mapped(&h->m_trP, np)) return rc;
-        std::memcpy(h->m_Z.host, Zref, D.z_total * sizeof(double));
-        QLN_HIP(qln::launch_tracking_lqr(h->p, Qdiag, Rdiag, Qfdiag, h->m_Z.dev, h->m_trK.dev, P ? h->m_trP.dev : nullptr,
-                                         h->stream));
-        QLN_HIP(hipStreamSynchronize(h->stream));
-        std::memcpy(K, h->m_trK.host, nk * sizeof(double));
-        if (P) std::memcpy(P, h->m_trP.host, np * sizeof(double));
-        return QLN_OK;
-    }
-    if (int rc = ensure(&h->s_Z, D.z_total)) return rc;
-    if (int rc = ensure(&h->s_trK, nk)) return rc;
-    if (P)
-        if (int rc = ensure(&h->s_trP, np)) return rc;
-    QLN_HIP(hipMemcpyAsync(h->s_Z, Zref, D.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    QLN_HIP(qln::launch_tracking_lqr(h->p, Qdiag, Rdiag, Qfdiag, h->s_Z, h->s_trK, P ? h->s_trP : nullptr, h->stream));
-    QLN_HIP(hipMemcpyAsync(K, h->s_trK, nk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (P) QLN_HIP(hipMemcpyAsync(P, h->s_trP, np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    QLN_HIP(hipStreamSynchronize(h->stream));
-    return QLN_OK;
+    return host_call(h, {copy_in(kZ, Zref), copy_out(kK, K), copy_out(kP, P)}, [&](double* const* d, bool) {
+        return qln::launch_tracking_lqr(h->p, Qdiag, Rdiag, Qfdiag, d[kZ], d[kK], d[kP], h->stream);
+    });
 }
 
-// Zout's entries past n_nlp are never written by the kernel: they come back as whatever the caller's buffer held there.
 int qln_tracking_rollout_host(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout) {
     if (int rc = check_tracking_rollout_args(h, Zref, Zout, "qln_tracking_rollout_host")) return rc;
     if (int rc = bind_device(h)) return rc;
-    const qln_dims& D = h->dims;
-    const int64_t nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX;
-    if (h->zero_copy) {
-        if (int rc = ensure_mapped(&h->m_Z, D.z_total)) return rc;
-        if (int rc = ensure_mapped(&h->m_zout, D.z_total)) return rc;
-        if (K)
-            if (int rc = ensure_mapped(&h->m_trK, nk)) return rc;
-        if (x0)
-            if (int rc = ensure_mapped(&h->m_trx0, nx)) return rc;
-        std::memcpy(h->m_Z.host, Zref, D.z_total * sizeof(double));
-        std::memcpy(h->m_zout.host, Zout, D.z_total * sizeof(double));
-        if (K) std::memcpy(h->m_trK.host, K, nk * sizeof(double));
-        if (x0) std::memcpy(h->m_trx0.host, x0, nx * sizeof(double));
-        QLN_HIP(qln::launch_tracking_rollout(h->p, h->m_Z.dev, K ? h->m_trK.dev : nullptr, x0 ? h->m_trx0.dev : nullptr,
-                                             h->m_zout.dev, h->stream));
-        QLN_HIP(hipStreamSynchronize(h->stream));
-        std::memcpy(Zout, h->m_zout.host, D.z_total * sizeof(double));
-        return QLN_OK;
-    }
-    if (int rc = ensure(&h->s_Z, D.z_total)) return rc;
-    if (int rc = ensure(&h->s_zout, D.z_total)) return rc;
-    if (K)
-        if (int rc = ensure(&h->s_trK, nk)) return rc;
-    if (x0)
-        if (int rc = ensure(&h->s_trx0, nx)) return rc;
-    QLN_HIP(hipMemcpyAsync(h->s_Z, Zref, D.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    QLN_HIP(hipMemcpyAsync(h->s_zout, Zout, D.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (K) QLN_HIP(hipMemcpyAsync(h->s_trK, K, nk * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (x0) QLN_HIP(hipMemcpyAsync(h->s_trx0, x0, nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    QLN_HIP(qln::launch_tracking_rollout(h->p, h->s_Z, K ? h->s_trK : nullptr, x0 ? h->s_trx0 : nullptr, h->s_zout, h->stream));
-    QLN_HIP(hipMemcpyAsync(Zout, h->s_zout, D.z_total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    QLN_HIP(hipStreamSynchronize(h->stream));
-    return QLN_OK;
+    return host_call(h, {copy_in(kZ, Zref), copy_inout(kZio, Zout), copy_in(kK, K), copy_in(kX0, x0)},
+                     [&](double* const* d, bool) {
+                         return qln::launch_tracking_rollout(h->p, d[kZ], d[kK], d[kX0], d[kZio], h->stream);
+                     });
 }
 
 // the roll-out's reverse sweep (k_tracking_rollout_vjp)
@@ -1095,67 +1114,19 @@ int qln_tracking_rollout_vjp(qln_handle* h, const double* Zref, const double* K,
     return QLN_OK;
 }
 
-// Zref is staged only when K_bar asks for it (the kernel reads it for nothing else).  Zref_bar's entries past n_nlp come
-// back as the caller's buffer held them.
+// Zref is staged only when K_bar asks for it (the kernel reads it for nothing else); otherwise Zout's buffer stands in.
 int qln_tracking_rollout_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
                                   double* Zref_bar, double* K_bar, double* x0_bar) {
     if (int rc = check_tracking_vjp_args(h, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar, "qln_tracking_rollout_vjp_host"))
         return rc;
     if (int rc = bind_device(h)) return rc;
-    const qln_dims& D = h->dims;
-    const int64_t nz = D.z_total, nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX;
-    if (h->zero_copy) {
-        if (int rc = ensure_mapped(&h->m_v, nz)) return rc;
-        if (int rc = ensure_mapped(&h->m_trZbar, nz)) return rc;
-        if (K_bar)
-            if (int rc = ensure_mapped(&h->m_Z, nz)) return rc;
-        if (K)
-            if (int rc = ensure_mapped(&h->m_trK, nk)) return rc;
-        if (Zref_bar)
-            if (int rc = ensure_mapped(&h->m_zout, nz)) return rc;
-        if (K_bar)
-            if (int rc = ensure_mapped(&h->m_trKbar, nk)) return rc;
-        if (x0_bar)
-            if (int rc = ensure_mapped(&h->m_trx0, nx)) return rc;
-        std::memcpy(h->m_v.host, Zout, nz * sizeof(double));
-        std::memcpy(h->m_trZbar.host, Zbar, nz * sizeof(double));
-        if (K_bar) std::memcpy(h->m_Z.host, Zref, nz * sizeof(double));
-        if (K) std::memcpy(h->m_trK.host, K, nk * sizeof(double));
-        if (Zref_bar) std::memcpy(h->m_zout.host, Zref_bar, nz * sizeof(double));
-        QLN_HIP(qln::launch_tracking_rollout_vjp(h->p, K_bar ? h->m_Z.dev : h->m_v.dev, K ? h->m_trK.dev : nullptr, h->m_v.dev,
-                                                 h->m_trZbar.dev, Zref_bar ? h->m_zout.dev : nullptr,
-                                                 K_bar ? h->m_trKbar.dev : nullptr, x0_bar ? h->m_trx0.dev : nullptr, h->stream));
-        QLN_HIP(hipStreamSynchronize(h->stream));
-        if (Zref_bar) std::memcpy(Zref_bar, h->m_zout.host, nz * sizeof(double));
-        if (K_bar) std::memcpy(K_bar, h->m_trKbar.host, nk * sizeof(double));
-        if (x0_bar) std::memcpy(x0_bar, h->m_trx0.host, nx * sizeof(double));
-        return QLN_OK;
-    }
-    if (int rc = ensure(&h->s_v, nz)) return rc;
-    if (int rc = ensure(&h->s_trZbar, nz)) return rc;
-    if (K_bar)
-        if (int rc = ensure(&h->s_Z, nz)) return rc;
-    if (K)
-        if (int rc = ensure(&h->s_trK, nk)) return rc;
-    if (Zref_bar)
-        if (int rc = ensure(&h->s_zout, nz)) return rc;
-    if (K_bar)
-        if (int rc = ensure(&h->s_trKbar, nk)) return rc;
-    if (x0_bar)
-        if (int rc = ensure(&h->s_trx0, nx)) return rc;
-    QLN_HIP(hipMemcpyAsync(h->s_v, Zout, nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    QLN_HIP(hipMemcpyAsync(h->s_trZbar, Zbar, nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (K_bar) QLN_HIP(hipMemcpyAsync(h->s_Z, Zref, nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (K) QLN_HIP(hipMemcpyAsync(h->s_trK, K, nk * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (Zref_bar) QLN_HIP(hipMemcpyAsync(h->s_zout, Zref_bar, nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    QLN_HIP(qln::launch_tracking_rollout_vjp(h->p, K_bar ? h->s_Z : h->s_v, K ? h->s_trK : nullptr, h->s_v, h->s_trZbar,
-                                             Zref_bar ? h->s_zout : nullptr, K_bar ? h->s_trKbar : nullptr,
-                                             x0_bar ? h->s_trx0 : nullptr, h->stream));
-    if (Zref_bar) QLN_HIP(hipMemcpyAsync(Zref_bar, h->s_zout, nz * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (K_bar) QLN_HIP(hipMemcpyAsync(K_bar, h->s_trKbar, nk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (x0_bar) QLN_HIP(hipMemcpyAsync(x0_bar, h->s_trx0, nx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    QLN_HIP(hipStreamSynchronize(h->stream));
-    return QLN_OK;
+    return host_call(h,
+                     {copy_in(kV, Zout), copy_in(kZbar, Zbar), copy_in(kZ, K_bar ? Zref : nullptr), copy_in(kK, K),
+                      copy_inout(kZio, Zref_bar), copy_out(kKbar, K_bar), copy_out(kX0, x0_bar)},
+                     [&](double* const* d, bool) {
+                         return qln::launch_tracking_rollout_vjp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kZbar], d[kZio],
+                                                                 d[kKbar], d[kX0], h->stream);
+                     });
 }
 
 // ------------------------------------------------------------------ host-pointer (MOI) mode
@@ -1165,22 +1136,8 @@ int qln_eval_objective_host(qln_handle* h, const double* Z, double* f) {
     if (int rc = check_cost(h)) return rc;
     if (!Z || !f) return fail(QLN_ERR_INVALID_ARGUMENT, "qln_eval_objective_host: null pointer");
     if (int rc = bind_device(h)) return rc;
-    if (h->zero_copy) {
-        if (int rc = ensure_mapped(&h->m_Z, h->dims.z_total)) return rc;
-        if (int rc = ensure_mapped(&h->m_f, h->dims.B)) return rc;
-        std::memcpy(h->m_Z.host, Z, h->dims.z_total * sizeof(double));
-        QLN_HIP(qln::launch_objective(h->p, h->m_Z.dev, h->m_f.dev, h->stream));
-        QLN_HIP(hipStreamSynchronize(h->stream));
-        std::memcpy(f, h->m_f.host, h->dims.B * sizeof(double));
-        return QLN_OK;
-    }
-    if (int rc = ensure(&h->s_Z, h->dims.z_total)) return rc;
-    if (int rc = ensure(&h->s_f, h->dims.B)) return rc;
-    QLN_HIP(hipMemcpyAsync(h->s_Z, Z, h->dims.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    QLN_HIP(qln::launch_objective(h->p, h->s_Z, h->s_f, h->stream));
-    QLN_HIP(hipMemcpyAsync(f, h->s_f, h->dims.B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    QLN_HIP(hipStreamSynchronize(h->stream));
-    return QLN_OK;
+    return host_call(h, {copy_in(kZ, Z), copy_out(kF, f)},
+                     [&](double* const* d, bool) { return qln::launch_objective(h->p, d[kZ], d[kF], h->stream); });
 }
 
 int qln_eval_objective_gradient_host(qln_handle* h, const double* Z, double* grad) {
@@ -1188,184 +1145,70 @@ int qln_eval_objective_gradient_host(qln_handle* h, const double* Z, double* gra
     if (int rc = check_cost(h)) return rc;
     if (!Z || !grad) return fail(QLN_ERR_INVALID_ARGUMENT, "qln_eval_objective_gradient_host: null pointer");
     if (int rc = bind_device(h)) return rc;
-    if (h->zero_copy) {
-        if (int rc = ensure_mapped(&h->m_Z, h->dims.z_total)) return rc;
-        if (int rc = ensure_mapped(&h->m_grad, h->dims.z_total)) return rc;
-        std::memcpy(h->m_Z.host, Z, h->dims.z_total * sizeof(double));
-        QLN_HIP(qln::launch_objective_gradient(h->p, h->m_Z.dev, h->m_grad.dev, h->stream));
-        QLN_HIP(hipStreamSynchronize(h->stream));
-        std::memcpy(grad, h->m_grad.host, h->dims.z_total * sizeof(double));
-        return QLN_OK;
-    }
-    if (int rc = ensure(&h->s_Z, h->dims.z_total)) return rc;
-    if (int rc = ensure(&h->s_grad, h->dims.z_total)) return rc;
-    QLN_HIP(hipMemcpyAsync(h->s_Z, Z, h->dims.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    QLN_HIP(hipMemsetAsync(h->s_grad, 0, h->dims.z_total * sizeof(double), h->stream));
-    QLN_HIP(qln::launch_objective_gradient(h->p, h->s_Z, h->s_grad, h->stream));
-    QLN_HIP(hipMemcpyAsync(grad, h->s_grad, h->dims.z_total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    QLN_HIP(hipStreamSynchronize(h->stream));
-    return QLN_OK;
+    return host_call(h, {copy_in(kZ, Z), copy_out(kGrad, grad)}, [&](double* const* d, bool mapped) {
+        const hipError_t e = mapped ? hipSuccess : hipMemsetAsync(d[kGrad], 0, h->dims.z_total * sizeof(double), h->stream);
+        return e != hipSuccess ? e : qln::launch_objective_gradient(h->p, d[kZ], d[kGrad], h->stream);
+    });
 }
 
 int qln_eval_constraint_host(qln_handle* h, const double* Z, double* c) {
     if (int rc = check_handle(h)) return rc;
     if (!Z || !c) return fail(QLN_ERR_INVALID_ARGUMENT, "qln_eval_constraint_host: null pointer");
     if (int rc = bind_device(h)) return rc;
-    if (h->zero_copy) {
-        if (int rc = ensure_mapped(&h->m_Z, h->dims.z_total)) return rc;
-        if (int rc = ensure_mapped(&h->m_c, h->dims.c_total)) return rc;
-        std::memcpy(h->m_Z.host, Z, h->dims.z_total * sizeof(double));
-        QLN_HIP(qln::launch_constraint_jacobian(h->p, 0, h->p.B, h->m_Z.dev, h->m_c.dev, nullptr, qln::kLaunchSplit, h->stream));
-        QLN_HIP(hipStreamSynchronize(h->stream));
-        std::memcpy(c, h->m_c.host, h->dims.c_total * sizeof(double));
-        return QLN_OK;
-    }
-    if (int rc = ensure(&h->s_Z, h->dims.z_total)) return rc;
-    if (int rc = ensure(&h->s_c, h->dims.c_total)) return rc;
-    QLN_HIP(hipMemcpyAsync(h->s_Z, Z, h->dims.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    QLN_HIP(qln::launch_constraint_jacobian(h->p, 0, h->p.B, h->s_Z, h->s_c, nullptr, 0, h->stream));
-    QLN_HIP(hipMemcpyAsync(c, h->s_c, h->dims.c_total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    QLN_HIP(hipStreamSynchronize(h->stream));
-    return QLN_OK;
+    return host_call(h, {copy_in(kZ, Z), copy_out(kC, c)}, [&](double* const* d, bool mapped) {
+        return qln::launch_constraint_jacobian(h->p, 0, h->p.B, d[kZ], d[kC], nullptr, mapped ? qln::kLaunchSplit : 0u, h->stream);
+    });
 }
 
 int qln_eval_constraint_jacobian_host(qln_handle* h, const double* Z, double* vals) {
     if (int rc = check_handle(h)) return rc;
     if (!Z || !vals) return fail(QLN_ERR_INVALID_ARGUMENT, "qln_eval_constraint_jacobian_host: null pointer");
     if (int rc = bind_device(h)) return rc;
-    if (h->zero_copy) {
-        if (int rc = ensure_mapped(&h->m_Z, h->dims.z_total)) return rc;
-        if (int rc = ensure_mapped(&h->m_vals, h->dims.j_total)) return rc;
-        std::memcpy(h->m_Z.host, Z, h->dims.z_total * sizeof(double));
-        QLN_HIP(qln::launch_constraint_jacobian(h->p, 0, h->p.B, h->m_Z.dev, nullptr, h->m_vals.dev,
-                                                QLN_JAC_WRITE_CONSTANTS | qln::kLaunchSplit, h->stream));
-        QLN_HIP(hipStreamSynchronize(h->stream));
-        std::memcpy(vals, h->m_vals.host, h->dims.j_total * sizeof(double));
-        return QLN_OK;
-    }
-    if (int rc = ensure(&h->s_Z, h->dims.z_total)) return rc;
-    if (int rc = ensure(&h->s_vals, h->dims.j_total)) return rc;
-    QLN_HIP(hipMemcpyAsync(h->s_Z, Z, h->dims.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    QLN_HIP(qln::launch_constraint_jacobian(h->p, 0, h->p.B, h->s_Z, nullptr, h->s_vals, QLN_JAC_WRITE_CONSTANTS,
-                                            h->stream));
-    QLN_HIP(hipMemcpyAsync(vals, h->s_vals, h->dims.j_total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    QLN_HIP(hipStreamSynchronize(h->stream));
-    return QLN_OK;
+    return host_call(h, {copy_in(kZ, Z), copy_out(kVals, vals)}, [&](double* const* d, bool mapped) {
+        return qln::launch_constraint_jacobian(h->p, 0, h->p.B, d[kZ], nullptr, d[kVals],
+                                               QLN_JAC_WRITE_CONSTANTS | (mapped ? qln::kLaunchSplit : 0u), h->stream);
+    });
 }
 
+// Staged only: a mapped path would change its latency with no measurement behind it.
 int qln_eval_hessian_lagrangian_host(qln_handle* h, const double* Z, const double* sigma, const double* mu, double* hvals) {
     if (int rc = check_hessian_args(h, Z, mu, hvals, "qln_eval_hessian_lagrangian_host")) return rc;
     if (int rc = bind_device(h)) return rc;
-    // no padding behind the last problem: for B == 1 the caller's buffer is exactly the nnz of the structure
-    const int64_t total = (int64_t)(h->dims.B - 1) * h->h_stride + hessian_nnz(h->dims.N);
-    if (int rc = ensure(&h->s_Z, h->dims.z_total)) return rc;
-    if (int rc = ensure(&h->s_mu, h->dims.c_total)) return rc;
-    if (int rc = ensure(&h->s_hvals, total)) return rc;
-    if (sigma)
-        if (int rc = ensure(&h->s_sigma, h->dims.B)) return rc;
-    QLN_HIP(hipMemcpyAsync(h->s_Z, Z, h->dims.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    QLN_HIP(hipMemcpyAsync(h->s_mu, mu, h->dims.c_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (sigma) QLN_HIP(hipMemcpyAsync(h->s_sigma, sigma, h->dims.B * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    QLN_HIP(qln::launch_hessian_lagrangian(h->p, h->s_Z, sigma ? h->s_sigma : nullptr, h->s_mu, h->s_hvals, h->h_stride,
-                                           h->stream));
-    QLN_HIP(hipMemcpyAsync(hvals, h->s_hvals, total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    QLN_HIP(hipStreamSynchronize(h->stream));
-    return QLN_OK;
+    return host_call(h, {copy_in(kZ, Z), copy_in(kMu, mu), copy_out(kHvals, hvals), copy_in(kSigma, sigma)},
+                     [&](double* const* d, bool) {
+                         return qln::launch_hessian_lagrangian(h->p, d[kZ], d[kSigma], d[kMu], d[kHvals], h->h_stride,
+                                                               h->stream);
+                     },
+                     false);
 }
 
-// The products in MOI mode: every input is copied into a mapped pinned buffer (zero_copy) or staged in device memory, one
-// launch, the result copied back.  The padding of an output's layout is never written by the kernels: zeros.
 int qln_eval_hessian_lagrangian_product_host(qln_handle* h, const double* Z, const double* sigma, const double* mu,
                                              const double* v, double* y) {
     if (int rc = check_hessian_product_args(h, Z, mu, v, y, "qln_eval_hessian_lagrangian_product_host")) return rc;
     if (int rc = bind_device(h)) return rc;
-    const qln_dims& D = h->dims;
-    if (h->zero_copy) {
-        if (int rc = ensure_mapped(&h->m_Z, D.z_total)) return rc;
-        if (int rc = ensure_mapped(&h->m_v, D.z_total)) return rc;
-        if (int rc = ensure_mapped(&h->m_mu, D.c_total)) return rc;
-        if (int rc = ensure_mapped(&h->m_zout, D.z_total)) return rc;
-        if (sigma)
-            if (int rc = ensure_mapped(&h->m_sigma, D.B)) return rc;
-        std::memcpy(h->m_Z.host, Z, D.z_total * sizeof(double));
-        std::memcpy(h->m_v.host, v, D.z_total * sizeof(double));
-        std::memcpy(h->m_mu.host, mu, D.c_total * sizeof(double));
-        if (sigma) std::memcpy(h->m_sigma.host, sigma, D.B * sizeof(double));
-        QLN_HIP(qln::launch_hessian_lagrangian_product(h->p, h->m_Z.dev, sigma ? h->m_sigma.dev : nullptr, h->m_mu.dev,
-                                                       h->m_v.dev, h->m_zout.dev, h->stream));
-        QLN_HIP(hipStreamSynchronize(h->stream));
-        std::memcpy(y, h->m_zout.host, D.z_total * sizeof(double));
-        return QLN_OK;
-    }
-    if (int rc = ensure(&h->s_Z, D.z_total)) return rc;
-    if (int rc = ensure(&h->s_v, D.z_total)) return rc;
-    if (int rc = ensure(&h->s_mu, D.c_total)) return rc;
-    if (int rc = ensure(&h->s_zout, D.z_total)) return rc;
-    if (sigma)
-        if (int rc = ensure(&h->s_sigma, D.B)) return rc;
-    QLN_HIP(hipMemcpyAsync(h->s_Z, Z, D.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    QLN_HIP(hipMemcpyAsync(h->s_v, v, D.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    QLN_HIP(hipMemcpyAsync(h->s_mu, mu, D.c_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (sigma) QLN_HIP(hipMemcpyAsync(h->s_sigma, sigma, D.B * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    QLN_HIP(qln::launch_hessian_lagrangian_product(h->p, h->s_Z, sigma ? h->s_sigma : nullptr, h->s_mu, h->s_v, h->s_zout,
-                                                   h->stream));
-    QLN_HIP(hipMemcpyAsync(y, h->s_zout, D.z_total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    QLN_HIP(hipStreamSynchronize(h->stream));
-    return QLN_OK;
+    return host_call(h, {copy_in(kZ, Z), copy_in(kV, v), copy_in(kMu, mu), copy_out(kZout, y), copy_in(kSigma, sigma)},
+                     [&](double* const* d, bool) {
+                         return qln::launch_hessian_lagrangian_product(h->p, d[kZ], d[kSigma], d[kMu], d[kV], d[kZout],
+                                                                       h->stream);
+                     });
 }
 
 int qln_eval_constraint_jvp_host(qln_handle* h, const double* Z, const double* v, double* y) {
     if (int rc = check_handle(h)) return rc;
     if (!Z || !v || !y) return fail(QLN_ERR_INVALID_ARGUMENT, "qln_eval_constraint_jvp_host: null pointer");
     if (int rc = bind_device(h)) return rc;
-    const qln_dims& D = h->dims;
-    if (h->zero_copy) {
-        if (int rc = ensure_mapped(&h->m_Z, D.z_total)) return rc;
-        if (int rc = ensure_mapped(&h->m_v, D.z_total)) return rc;
-        if (int rc = ensure_mapped(&h->m_c, D.c_total)) return rc;
-        std::memcpy(h->m_Z.host, Z, D.z_total * sizeof(double));
-        std::memcpy(h->m_v.host, v, D.z_total * sizeof(double));
-        QLN_HIP(qln::launch_constraint_jvp(h->p, h->m_Z.dev, h->m_v.dev, h->m_c.dev, h->stream));
-        QLN_HIP(hipStreamSynchronize(h->stream));
-        std::memcpy(y, h->m_c.host, D.c_total * sizeof(double));
-        return QLN_OK;
-    }
-    if (int rc = ensure(&h->s_Z, D.z_total)) return rc;
-    if (int rc = ensure(&h->s_v, D.z_total)) return rc;
-    if (int rc = ensure(&h->s_c, D.c_total)) return rc;
-    QLN_HIP(hipMemcpyAsync(h->s_Z, Z, D.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    QLN_HIP(hipMemcpyAsync(h->s_v, v, D.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    QLN_HIP(qln::launch_constraint_jvp(h->p, h->s_Z, h->s_v, h->s_c, h->stream));
-    QLN_HIP(hipMemcpyAsync(y, h->s_c, D.c_total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    QLN_HIP(hipStreamSynchronize(h->stream));
-    return QLN_OK;
+    return host_call(h, {copy_in(kZ, Z), copy_in(kV, v), copy_out(kC, y)}, [&](double* const* d, bool) {
+        return qln::launch_constraint_jvp(h->p, d[kZ], d[kV], d[kC], h->stream);
+    });
 }
 
 int qln_eval_constraint_vjp_host(qln_handle* h, const double* Z, const double* lam, double* g) {
     if (int rc = check_handle(h)) return rc;
     if (!Z || !lam || !g) return fail(QLN_ERR_INVALID_ARGUMENT, "qln_eval_constraint_vjp_host: null pointer");
     if (int rc = bind_device(h)) return rc;
-    const qln_dims& D = h->dims;
-    if (h->zero_copy) {
-        if (int rc = ensure_mapped(&h->m_Z, D.z_total)) return rc;
-        if (int rc = ensure_mapped(&h->m_mu, D.c_total)) return rc;
-        if (int rc = ensure_mapped(&h->m_zout, D.z_total)) return rc;
-        std::memcpy(h->m_Z.host, Z, D.z_total * sizeof(double));
-        std::memcpy(h->m_mu.host, lam, D.c_total * sizeof(double));
-        QLN_HIP(qln::launch_constraint_vjp(h->p, h->m_Z.dev, h->m_mu.dev, h->m_zout.dev, h->stream));
-        QLN_HIP(hipStreamSynchronize(h->stream));
-        std::memcpy(g, h->m_zout.host, D.z_total * sizeof(double));
-        return QLN_OK;
-    }
-    if (int rc = ensure(&h->s_Z, D.z_total)) return rc;
-    if (int rc = ensure(&h->s_mu, D.c_total)) return rc;
-    if (int rc = ensure(&h->s_zout, D.z_total)) return rc;
-    QLN_HIP(hipMemcpyAsync(h->s_Z, Z, D.z_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    QLN_HIP(hipMemcpyAsync(h->s_mu, lam, D.c_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    QLN_HIP(qln::launch_constraint_vjp(h->p, h->s_Z, h->s_mu, h->s_zout, h->stream));
-    QLN_HIP(hipMemcpyAsync(g, h->s_zout, D.z_total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    QLN_HIP(hipStreamSynchronize(h->stream));
-    return QLN_OK;
+    return host_call(h, {copy_in(kZ, Z), copy_in(kMu, lam), copy_out(kZout, g)}, [&](double* const* d, bool) {
+        return qln::launch_constraint_vjp(h->p, d[kZ], d[kMu], d[kZout], h->stream);
+    });
 }
 
 int qln_eval_constraint_jacobian_dense_host(qln_handle* h, int32_t b, const double* Z, double* jac) {
@@ -1378,27 +1221,18 @@ int qln_eval_constraint_jacobian_dense_host(qln_handle* h, int32_t b, const doub
     const int32_t N = h->dims.N, kt = h->k_trans[b];
     const int32_t nnz = nnz_of(N, kt, h->p.jac_format);
     const int64_t m = m_nlp_of(N, kt);
+    // only problem b's n_nlp entries of Z go in; its nnz values are scattered from mapped memory, or staged back first
+    h->h_vals_one.resize(nnz);
     const double* v = nullptr;
-    if (h->zero_copy) {
-        if (int rc = ensure_mapped(&h->m_Z, h->dims.z_total)) return rc;
-        if (int rc = ensure_mapped(&h->m_vals, h->dims.j_total)) return rc;
-        std::memcpy(h->m_Z.host + (int64_t)b * h->dims.z_stride, Z, h->dims.n_nlp * sizeof(double));
-        QLN_HIP(qln::launch_constraint_jacobian(h->p, b, 1, h->m_Z.dev, nullptr, h->m_vals.dev,
-                                                QLN_JAC_WRITE_CONSTANTS | qln::kLaunchSplit, h->stream));
-        QLN_HIP(hipStreamSynchronize(h->stream));
-        v = h->m_vals.host + h->j_off[b];
-    } else {
-        if (int rc = ensure(&h->s_Z, h->dims.z_total)) return rc;
-        if (int rc = ensure(&h->s_vals, h->dims.j_total)) return rc;
-        h->h_vals_one.resize(nnz);
-        QLN_HIP(hipMemcpyAsync(h->s_Z + (int64_t)b * h->dims.z_stride, Z, h->dims.n_nlp * sizeof(double), hipMemcpyHostToDevice,
-                               h->stream));
-        QLN_HIP(qln::launch_constraint_jacobian(h->p, b, 1, h->s_Z, nullptr, h->s_vals, QLN_JAC_WRITE_CONSTANTS, h->stream));
-        QLN_HIP(hipMemcpyAsync(h->h_vals_one.data(), h->s_vals + h->j_off[b], nnz * sizeof(double), hipMemcpyDeviceToHost,
-                               h->stream));
-        QLN_HIP(hipStreamSynchronize(h->stream));
-        v = h->h_vals_one.data();
-    }
+    if (int rc = host_call(h,
+                           {{kZ, Z, nullptr, h->dims.n_nlp, (int64_t)b * h->dims.z_stride, nullptr},
+                            {kVals, nullptr, h->h_vals_one.data(), nnz, h->j_off[b], &v}},
+                           [&](double* const* d, bool mapped) {
+                               return qln::launch_constraint_jacobian(h->p, b, 1, d[kZ], nullptr, d[kVals],
+                                                                      QLN_JAC_WRITE_CONSTANTS | (mapped ? qln::kLaunchSplit : 0u),
+                                                                      h->stream);
+                           }))
+        return rc;
     if (h->dense_map.empty()) h->dense_map.resize((size_t)h->dims.B);
     qln_handle::DenseMap& dm = h->dense_map[(size_t)b];
     if (dm.at.empty()) {

@@ -125,6 +125,11 @@ def _torch():
     return torch
 
 
+def _host_ptr(a):
+    """The address of a host array for the C ABI, None (NULL) for an optional argument left out."""
+    return None if a is None else a.ctypes.data
+
+
 # layout of the step-block section of vals (include/qln_evaluator.h, QLN_JAC_FORMAT_*)
 JAC_FORMATS = {"dense_blocks": _lib.QLN_JAC_FORMAT_DENSE_BLOCKS, "structural": _lib.QLN_JAC_FORMAT_STRUCTURAL}
 
@@ -491,16 +496,10 @@ class HybridNLP:
 
     def hess_lag_host(self, Z, sigma, mu):
         """The same with host arrays (MOI mode): returns an (h_total,) numpy array."""
-        Z = self._host_Z(Z)
-        mu = np.ascontiguousarray(np.asarray(mu, dtype=np.float64).reshape(-1))
-        if mu.size != self.dims.c_total:
-            raise ValueError(f"mu has {mu.size} entries, expected {self.dims.c_total}")
-        sp = None
-        if sigma is not None:
-            sigma = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (self.B,)))
-            sp = sigma.ctypes.data
+        Z, mu, sigma = self._host_Z(Z), self._host_c(mu, "mu"), self._host_sigma(sigma)
         out = np.zeros(self.h_total)
-        _lib.check(_lib.lib().qln_eval_hessian_lagrangian_host(self._h, Z.ctypes.data, sp, mu.ctypes.data, out.ctypes.data))
+        _lib.check(_lib.lib().qln_eval_hessian_lagrangian_host(self._h, Z.ctypes.data, _host_ptr(sigma), mu.ctypes.data,
+                                                               out.ctypes.data))
         return out
 
     def hess_lag_vec(self, Z, sigma, mu, v, out=None):
@@ -516,14 +515,10 @@ class HybridNLP:
 
     def hess_lag_vec_host(self, Z, sigma, mu, v):
         """The same with host arrays (MOI mode): returns a (z_total,) numpy array (zeros past n_nlp)."""
-        Z, v, mu = self._host_Z(Z), self._host_Z(v, "v"), self._host_c(mu, "mu")
-        sp = None
-        if sigma is not None:
-            sigma = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (self.B,)))
-            sp = sigma.ctypes.data
+        Z, v, mu, sigma = self._host_Z(Z), self._host_Z(v, "v"), self._host_c(mu, "mu"), self._host_sigma(sigma)
         out = np.zeros(self.dims.z_total)
         _lib.check(_lib.lib().qln_eval_hessian_lagrangian_product_host(
-            self._h, Z.ctypes.data, sp, mu.ctypes.data, v.ctypes.data, out.ctypes.data))
+            self._h, Z.ctypes.data, _host_ptr(sigma), mu.ctypes.data, v.ctypes.data, out.ctypes.data))
         return out
 
     # -- TVLQR tracking along reference trajectories ---------------------------------------------
@@ -570,18 +565,12 @@ class HybridNLP:
 
     def tracking_rollout_host(self, Zref, K=None, x0=None):
         """The same with host arrays (synchronous): returns a (z_total,) numpy array (zeros past n_nlp)."""
-        Zref = self._host_Z(Zref, "Zref")
-        kp = xp = None
-        if K is not None:
-            K = np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(-1))
-            if K.size != self.B * (self.N - 1) * _lib.TRACK_NU * n:
-                raise ValueError(f"K has {K.size} entries, expected {self.B * (self.N - 1) * _lib.TRACK_NU * n}")
-            kp = K.ctypes.data
+        Zref, K = self._host_Z(Zref, "Zref"), self._host_K(K)
         if x0 is not None:
             x0 = np.ascontiguousarray(np.broadcast_to(np.asarray(x0, dtype=np.float64), (self.B, n)))
-            xp = x0.ctypes.data
         out = np.zeros(self.dims.z_total)
-        _lib.check(_lib.lib().qln_tracking_rollout_host(self._h, Zref.ctypes.data, kp, xp, out.ctypes.data))
+        _lib.check(_lib.lib().qln_tracking_rollout_host(self._h, Zref.ctypes.data, _host_ptr(K), _host_ptr(x0),
+                                                        out.ctypes.data))
         return out
 
     # -- reverse-mode derivative of the closed-loop roll-out ---------------------------------------
@@ -617,18 +606,12 @@ class HybridNLP:
         """The same with host arrays (synchronous): numpy (Zref_bar (z_total,), K_bar (B, N-1, 4, 15), x0_bar (B, 15))."""
         want = self._vjp_want(K, want)
         Zref, Zout, Zbar = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout"), self._host_Z(Zbar, "Zbar")
-        kp = None
-        if K is not None:
-            K = np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(-1))
-            if K.size != self.B * (self.N - 1) * _lib.TRACK_NU * n:
-                raise ValueError(f"K has {K.size} entries, expected {self.B * (self.N - 1) * _lib.TRACK_NU * n}")
-            kp = K.ctypes.data
+        K = self._host_K(K)
         zb = np.zeros(self.dims.z_total) if "Zref" in want else None
         kb = np.zeros(tracking_k_shape(self.B, self.N)) if "K" in want else None
         xb = np.zeros((self.B, n)) if "x0" in want else None
-        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-        _lib.check(_lib.lib().qln_tracking_rollout_vjp_host(self._h, Zref.ctypes.data, kp, Zout.ctypes.data, Zbar.ctypes.data,
-                                                            ptr(zb), ptr(kb), ptr(xb)))
+        _lib.check(_lib.lib().qln_tracking_rollout_vjp_host(self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data,
+                                                            Zbar.ctypes.data, _host_ptr(zb), _host_ptr(kb), _host_ptr(xb)))
         return zb, kb, xb
 
     def differentiable_rollout(self, Zref, K=None, x0=None):
@@ -792,6 +775,22 @@ class HybridNLP:
         if c.size != self.dims.c_total:
             raise ValueError(f"{name} has {c.size} entries, expected {self.dims.c_total}")
         return c
+
+    def _host_sigma(self, sigma):
+        """sigma broadcast to (B,), or None (1.0 for every problem)."""
+        if sigma is None:
+            return None
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (self.B,)))
+
+    def _host_K(self, K):
+        """Gains flattened, or None (the open-loop roll-out)."""
+        if K is None:
+            return None
+        K = np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(-1))
+        nk = self.B * (self.N - 1) * _lib.TRACK_NU * n
+        if K.size != nk:
+            raise ValueError(f"K has {K.size} entries, expected {nk}")
+        return K
 
     def eval_f_host(self, Z):
         Z = self._host_Z(Z)

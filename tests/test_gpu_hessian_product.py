@@ -294,14 +294,21 @@ def test_clearance_curvature_takes_quirk_Q3s_branch():
         assert np.all(y[b, mask] == 0.0)
 
 
+@pytest.mark.parametrize("z_stride", [0, 20 * 61 + 3])
 @pytest.mark.parametrize("B", [7, 64])
-def test_host_forms_give_the_device_bits(B):
-    """B = 7 runs on mapped host memory (zero copy), B = 64 is staged through device memory."""
+def test_host_forms_give_the_device_bits(B, z_stride):
+    """B = 7 runs on mapped host memory (zero copy), B = 64 is staged through device memory.  With a padded z_stride, a
+    roll-out's in-out Zout full of NaN goes through the handle first: none of it may reach the padding of a result."""
     import torch
 
+    from quadruped_landing_amd import _lib
+
     batch = _batch(B, 61, 21, 1, seed=12)
-    nlp = _nlp(batch, matrix_free=True, exact_hessian=True)
+    nlp = _nlp(batch, matrix_free=True, exact_hessian=True, z_stride=z_stride)
     n = nlp.n_nlp
+    zout = np.full(nlp.dims.z_total, np.nan)
+    _lib.check(_lib.lib().qln_tracking_rollout_host(nlp._h, nlp._host_Z(batch.Z).ctypes.data, None, None, zout.ctypes.data))
+    assert np.all(np.isnan(zout.reshape(B, nlp.z_stride)[:, n:]))  # in-out: the padding comes back as it went in
     Z = nlp.upload_Z(batch.Z)
     sigma, mu, sig_d, mu_d = _inputs(nlp, 4)
     v = _vec(nlp, 5, pad=0.0)
