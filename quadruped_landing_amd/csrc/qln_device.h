@@ -34,6 +34,14 @@ struct BatchParams {
     int32_t kt_max;            // largest k_trans of the batch (host-side sizing of the structural format's LDS tile)
 };
 
+// The model constants the kernels compute with (PlanarQuadruped, src/planar_quadruped.jl:11-20)
+struct Model {
+    double g, mb, mf, lb;
+    double Ib;  // mb * lb^2 / 12, src/planar_quadruped.jl:41
+    __host__ __device__ __forceinline__ explicit Model(const BatchParams& P)
+        : g(P.g), mb(P.mb), mf(P.mf), lb(P.lb), Ib(mb * (lb * lb) / 12) {}
+};
+
 // ---------------------------------------------------------------------------------------------
 // Structural non-zeros of the 15x20 step Jacobian d(x+)/d[x;u] (contact*_jacobian,
 // src/planar_quadruped.jl:225-248, times the jump mask of :262-263 at the transition knot).
@@ -111,6 +119,37 @@ static_assert(step_nnz(0) == 71 && step_nnz(1) == 71 && step_nnz(2) == 57 && ste
 __host__ __device__ constexpr int step_category(int K, int k_trans, int init_mode) {
     return (K == k_trans - 1) ? (init_mode == 1 ? 3 : 4) : (K < k_trans - 1) ? (init_mode == 1 ? 0 : 1) : 2;
 }
+
+// The same schedule as the flags the dynamics read: which foot is free during knot K's step (mode 1 = foot 2 free,
+// mode 2 = foot 1 free, mode 3 = both pinned) and whether the jump map (src/planar_quadruped.jl:250-263) follows it.
+// The second argument is the jump knot k_trans - 1, subtracted by the caller: hipcc simplifies a function before it
+// inlines it, and with the subtraction in here it rewrites `K <= k_trans - 1` to `K < k_trans` on its own, where the
+// kernels fold it together with K = lane + 1 -- different integer code, and with it different register tables in the
+// large kernels (profiles/step_block_refactor_resource_usage.txt).
+struct KnotMode {
+    bool f1free, f2free, jump;
+    bool pinned;  // mode 3.  Not derived from the other two where it is used (the structural emission): `mode == 3` is the
+                  // compare the evaluator has always made, and !(f1free || f2free) is two more in 14 of its instantiations
+};
+__host__ __device__ __forceinline__ constexpr KnotMode knot_mode(int K, int k_jump, int im) {
+    const int mode = (K <= k_jump) ? im : 3;
+    return {mode == 2, mode == 1, K == k_jump, mode == 3};
+}
+constexpr bool knot_mode_matches_category() {
+    bool seen[kStepCategories] = {false, false, false, false, false};
+    for (int im = 1; im <= 2; ++im)
+        for (int kt = 1; kt <= 6; ++kt)
+            for (int K = 1; K <= kt + 2; ++K) {
+                const int cat = step_category(K, kt, im);
+                const KnotMode m = knot_mode(K, kt - 1, im);
+                seen[cat] = true;
+                if (m.f1free != (cat == 1 || cat == 4) || m.f2free != (cat == 0 || cat == 3) || m.jump != (cat >= 3) ||
+                    m.pinned != (cat == 2))
+                    return false;
+            }
+    return seen[0] && seen[1] && seen[2] && seen[3] && seen[4];
+}
+static_assert(knot_mode_matches_category(), "knot_mode and step_category state the same schedule, in all five categories");
 
 // Offset (doubles) of 0-based knot k's block inside the step-block section of a problem, structural format:
 // contact knots first (71 each), then the jump knot (56), then mode 3 (57 each).  step_block_offset(N-1) is the

@@ -14,6 +14,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "qln_device.h"
+
 namespace qln {
 
 constexpr int kHessStep = 55;   // QLN_HESS_STEP_NNZ
@@ -54,18 +56,17 @@ __host__ __device__ __forceinline__ double clearance_curvature(double th, double
 //   z:    x_k[0..14], F1x, F1y, F2x, F2y, h
 //   rec:  Q[15] R[5] q[15] r[5] of the knot's cost record (its constant is not needed)
 //   lam:  the knot's 15 dynamics multipliers with the jump mask already applied (masked rows = 0)
-//   f1free / f2free: the contact mode (mode 2 / mode 1); both false in mode 3
+//   md:   the knot's contact mode (its jump flag is not read: the mask is in lam);  M: the model constants
 //   mu_c: the clearance multiplier of the knot; sig: sigma
 // The clearance term is the derivative of the entry jac_c! writes (quirk Q3): (lb/2) sin(theta) for theta > 0,
 // -(lb/2) sin(theta) otherwise.
 template <typename Z, typename R, typename L, typename O>
-__host__ __device__ __forceinline__ void hessian_step_block(const Z& z, const R& rec, const L& lam, bool f1free, bool f2free,
-                                                            double mu_c, double sig, double g, double mb, double mf, double lb,
-                                                            O&& out) {
+__host__ __device__ __forceinline__ void hessian_step_block(const Z& z, const R& rec, const L& lam, KnotMode md, const Model& M,
+                                                            double mu_c, double sig, O&& out) {
+    const double g = M.g, mb = M.mb, mf = M.mf, lb = M.lb;
     const double F1x = z[15], F1y = z[16], F2x = z[17], F2y = z[18], h = z[19];
-    const double m1 = f1free ? 1.0 : 0.0, m2 = f2free ? 1.0 : 0.0;
-    const double Ib = mb * (lb * lb) / 12;
-    const double iIb = 1.0 / Ib;
+    const double m1 = md.f1free ? 1.0 : 0.0, m2 = md.f2free ? 1.0 : 0.0;
+    const double iIb = 1.0 / M.Ib;
     const double h2 = h * h;
     const double Aw = h * iIb, At = 0.5 * h2 * iIb, Bt = h2 * h * iIb * (1.0 / 6.0);
     const double sFx = F1x + F2x, sFy = F1y + F2y;

@@ -8,7 +8,8 @@
 // h_k l_k(x_k, u_k), clearance row k sees theta_k only, and the other constraint groups are linear.  So a step block
 // needs the knot's 20 entries of Z, its 15 dynamics multipliers, its clearance multiplier, sigma and its cost record --
 // the mapping of the evaluator: one 64-lane wavefront (= one workgroup) per problem, lane = dynamics knot, chunks of up to
-// 64 knots.  The 55 values of a block are formed in registers in closed form (~120 flops), put into an LDS tile in the
+// 64 knots.  The 55 values of a block are formed in registers in closed form (hessian_step_block of qln_hessian.h, from
+// the knot's KnotMode and the Model of qln_device.h like the first-order step_block; ~120 flops), put into an LDS tile in the
 // order of the output segment and drained as 16-byte-per-lane stores.
 //
 // Reads: the chunk's slice of Z and its dynamics multipliers are staged in LDS with coalesced 8-byte loads, all issued
@@ -57,7 +58,7 @@ __global__ __launch_bounds__(kWave) void k_hessian_lagrangian(BatchParams P, con
     double* const s_t = s_lds;  // output tile: aliases the staged inputs once every lane holds its own in registers
     const int lane = threadIdx.x;
     const int N = P.N;
-    const double g = P.g, mb = P.mb, mf = P.mf, lb = P.lb;
+    const Model M(P);
     const int per_xcd = (P.B + 7) >> 3, slots = gridDim.x >> 3;
     const int xcd = blockIdx.x & 7;
 
@@ -116,13 +117,12 @@ __global__ __launch_bounds__(kWave) void k_hessian_lagrangian(BatchParams P, con
             const bool valid = lane < nk;
             const int kl = valid ? lane : 0;
             const int K = kc0 + kl + 1;  // 1-based dynamics knot
-            const int mode = (K <= kt - 1) ? im : 3;
-            const bool jump = (K == kt - 1);
+            const KnotMode md = knot_mode(K, kt - 1, im);
             double z[20], lam[15], rec[kCostRec - 1];
 #pragma unroll
             for (int i = 0; i < 20; ++i) z[i] = s_z[20 * kl + i];
 #pragma unroll
-            for (int i = 0; i < 15; ++i) lam[i] = (jump && jump_masked(i)) ? 0.0 : s_mu[15 * kl + i];
+            for (int i = 0; i < 15; ++i) lam[i] = (md.jump && jump_masked(i)) ? 0.0 : s_mu[15 * kl + i];
 #pragma unroll
             for (int i = 0; i < kCostRec - 1; ++i) rec[i] = REC_REGS ? rrec[i] : s_rec[kCostRec * kl + i];
             wave_lds_sync();  // every lane holds its inputs: the tile may overwrite the staged slice
@@ -132,14 +132,14 @@ __global__ __launch_bounds__(kWave) void k_hessian_lagrangian(BatchParams P, con
             const int par = (int)((reinterpret_cast<uintptr_t>(G) >> 3) & 1);
             double* const t = s_t + par;
             if (valid) {
-                hessian_step_block(z, rec, lam, mode == 2, mode == 1, mu_c, sig, g, mb, mf, lb,
+                hessian_step_block(z, rec, lam, md, M, mu_c, sig,
                                    [&](int e, double v) { t[kHessStep * lane + e] = v; });
             }
             const int n = kHessStep * nk + (last_chunk ? kHessTerm : 0);
             if (last_chunk && lane < kHessTerm) {
                 // terminal block: sigma Qf on the diagonal of x_N, the clearance curvature of x_N's row at theta
                 double v = sig * qf;
-                if (lane == 2) v = v + mu_cn * clearance_curvature(th_n, lb);
+                if (lane == 2) v = v + mu_cn * clearance_curvature(th_n, M.lb);
                 t[kHessStep * nk + lane] = v;
             }
             wave_lds_sync();
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(kWave) void k_hessian_lagrangian_product(BatchParam
     double* const s_t = s_lds;  // output slice: written once every lane is done with the staged slices
     const int lane = threadIdx.x;
     const int N = P.N;
-    const double g = P.g, mb = P.mb, mf = P.mf, lb = P.lb;
+    const Model M(P);
     const int per_xcd = (P.B + 7) >> 3, slots = gridDim.x >> 3;
     const int xcd = blockIdx.x & 7;
 
@@ -265,20 +265,19 @@ __global__ __launch_bounds__(kWave) void k_hessian_lagrangian_product(BatchParam
             const bool valid = lane < nk;
             const int kl = valid ? lane : 0;
             const int K = kc0 + kl + 1;  // 1-based dynamics knot
-            const int mode = (K <= kt - 1) ? im : 3;
-            const bool jump = (K == kt - 1);
+            const KnotMode md = knot_mode(K, kt - 1, im);
             double z[20], lam[15], rec[kCostRec - 1], y[20];
 #pragma unroll
             for (int i = 0; i < 20; ++i) z[i] = s_z[20 * kl + i];
 #pragma unroll
-            for (int i = 0; i < 15; ++i) lam[i] = (jump && jump_masked(i)) ? 0.0 : s_mu[15 * kl + i];
+            for (int i = 0; i < 15; ++i) lam[i] = (md.jump && jump_masked(i)) ? 0.0 : s_mu[15 * kl + i];
 #pragma unroll
             for (int i = 0; i < kCostRec - 1; ++i) rec[i] = REC_REGS ? rrec[i] : s_rec[kCostRec * kl + i];
 #pragma unroll
             for (int i = 0; i < 20; ++i) y[i] = 0.0;
             const double* const vk = s_v + 20 * kl;
             if (valid) {
-                hessian_step_block(z, rec, lam, mode == 2, mode == 1, mu_c, sig, g, mb, mf, lb, [&](int e, double h) {
+                hessian_step_block(z, rec, lam, md, M, mu_c, sig, [&](int e, double h) {
                     const int r = kHessEntry.r[e], c = kHessEntry.c[e];
                     y[r] += h * vk[c];
                     if (r != c) y[c] += h * vk[r];
@@ -288,7 +287,7 @@ __global__ __launch_bounds__(kWave) void k_hessian_lagrangian_product(BatchParam
             if (last_chunk && lane < kHessTerm) {
                 // terminal block: the diagonal of k_hessian_lagrangian's last 15 values times x_N's slice of v
                 double h = sig * qf;
-                if (lane == 2) h = h + mu_cn * clearance_curvature(th_n, lb);
+                if (lane == 2) h = h + mu_cn * clearance_curvature(th_n, M.lb);
                 y_n = h * v_n;
             }
             wave_lds_sync();  // every lane is done with the staged slices: their bytes now take the result

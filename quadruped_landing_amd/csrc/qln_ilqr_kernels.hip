@@ -18,8 +18,8 @@
 // (quirk Q2): within an iteration the stage weights h_k are frozen -- the fixed point is the kind of point Ipopt's
 // run tends to with that gradient.  exact_h adds the missing term (a stationary point of the true objective).
 //
-// The step Jacobians A_k, B_k are the closed-form blocks of the evaluator (QLN_STEP_BASE / QLN_STEP_ENTRIES), derived
-// once per sweep by lane = knot and parked in a global scratch.  Per problem that scratch holds the step entries
+// The step Jacobians A_k, B_k are the closed-form blocks of the evaluator (step_block / for_each_step_entry of
+// qln_kernel_common.h), derived once per sweep by lane = knot and parked in a global scratch.  Per problem that scratch holds the step entries
 // (88 N doubles), the feedback law of every knot (80 N), the sixteen trial trajectories (320 N) and the inequality
 // multipliers (6 N); the wave's LDS holds the current trajectory, 9 scalars per knot and the sweep's matrices
 // (29 N + 1.4 k doubles: 20.3 KB at N = 40, eight waves per CU).
@@ -278,10 +278,8 @@ struct FastStep {
 };
 __device__ __forceinline__ void step_fast(const FastStep& C, int k, int kt, int im, const double (&x)[15], const double (&u)[5],
                                           double (&xn)[15]) {
-    const int K = k + 1;
-    const int mode = (K <= kt - 1) ? im : 3;
-    const bool jump = (K == kt - 1);
-    const double m1 = (mode == 2) ? 1.0 : 0.0, m2 = (mode == 1) ? 1.0 : 0.0;
+    const KnotMode md = knot_mode(k + 1, kt - 1, im);
+    const double m1 = md.f1free ? 1.0 : 0.0, m2 = md.f2free ? 1.0 : 0.0;
     const double h = u[4], h2 = h * h, hh2 = 0.5 * h2, h3_6 = h2 * h * (1.0 / 6.0), h4_24 = h2 * h2 * (1.0 / 24.0);
     const double abx = (u[0] + u[2]) * C.imb, aby = (u[1] + u[3]) * C.imb + C.g;
     const double a1x = m1 * (-u[0] * C.imf), a1y = m1 * (-u[1] * C.imf + C.g);
@@ -306,7 +304,7 @@ __device__ __forceinline__ void step_fast(const FastStep& C, int k, int kt, int 
     xn[12] = x[12] + h * a2x;
     xn[13] = x[13] + h * a2y;
     xn[14] = x[14] + h;
-    if (jump) {
+    if (md.jump) {
         xn[4] = 0.0;
         xn[6] = 0.0;
         xn[10] = xn[11] = xn[12] = xn[13] = 0.0;
@@ -408,11 +406,11 @@ __global__ __launch_bounds__(kWave, OCC) void k_al_ilqr(BatchParams P, SolvePara
     const int N = P.N;
     const ProblemDesc pd = P.desc[b];
     const int kt = pd.k_trans, im = pd.init_mode;
-    const double Ib = P.mb * (P.lb * P.lb) / 12;
+    const Model M(P);
     const double mbg = P.mb * P.g;
     const double p_lb = P.lb;
     FastStep FS;
-    FS.imb = 1.0 / P.mb, FS.imf = 1.0 / P.mf, FS.iIb = 1.0 / Ib, FS.g = P.g;
+    FS.imb = 1.0 / P.mb, FS.imf = 1.0 / P.mf, FS.iIb = 1.0 / M.Ib, FS.g = P.g;
     const double h_lo = S.h_lo, h_hi = S.h_hi, th_lo = S.th_lo, th_hi = S.th_hi, h_prox = S.h_prox;
     const double mu0 = S.mu0, mu_min = S.mu_min, mu_max = S.mu_max, tol = S.tol, inner_tol = S.inner_tol;
     const double rho_factor = S.rho_factor, rho_max = S.rho_max;
@@ -439,15 +437,12 @@ __global__ __launch_bounds__(kWave, OCC) void k_al_ilqr(BatchParams P, SolvePara
         for (int i = lane; i < kIneq * N; i += kWave) lamg[i] = 0.0;
         if (lane < 16) L.leq[lane] = 0.0;
         if (lane < 15) L.X[lane] = x0g[lane];
-        // where the p-th entry of a step block's union pattern goes in [A | B] (the value expressions of the
-        // statements are not expanded here: the macro parameter is unused)
-#define JW(row, col, val)                                                                        \
-    {                                                                                            \
-        constexpr int pos_ = step_union_pos(row, col);                                           \
-        if (lane == (pos_ & 63)) L.map[pos_] = ((col) < 15) ? ac_slot(row, col) : kAcB + 5 * (row) + ((col) - 15); \
-    }
-        QLN_STEP_ENTRIES();
-#undef JW
+        // where the p-th entry of a step block's union pattern goes in [A | B]
+        // (L.map by value: a lambda that takes L by reference takes its address, see carve())
+        for_each_step_entry([lane, map = L.map](auto row, auto col) {
+            constexpr int pos_ = step_union_pos(row, col);
+            if (lane == (pos_ & 63)) map[pos_] = (col < 15) ? ac_slot(row, col) : kAcB + 5 * row + (col - 15);
+        });
     }
     wave_lds_sync();
     double xf[15];
@@ -483,7 +478,7 @@ __global__ __launch_bounds__(kWave, OCC) void k_al_ilqr(BatchParams P, SolvePara
         for (int k = 0; k < N - 1; ++k) {
 #pragma unroll
             for (int j = 0; j < 5; ++j) u[j] = L.U[5 * k + j];
-            step_forward(P, k, kt, im, Ib, x, u, xn);
+            step_forward(M, k, kt, im, x, u, xn);
 #pragma unroll
             for (int i = 0; i < 15; ++i) x[i] = xn[i];
             if (lane == 0) {
@@ -589,20 +584,13 @@ __global__ __launch_bounds__(kWave, OCC) void k_al_ilqr(BatchParams P, SolvePara
                     double x[14];
 #pragma unroll
                     for (int i = 0; i < 14; ++i) x[i] = zk[i];
-                    const double F1x = L.U[5 * k], F1y = L.U[5 * k + 1], F2x = L.U[5 * k + 2], F2y = L.U[5 * k + 3], h = L.U[5 * k + 4];
-                    const int K = k + 1;
-                    const int mode = (K <= kt - 1) ? im : 3;
-                    const bool jump = (K == kt - 1), f1free = (mode == 2), f2free = (mode == 1);
-                    const double g = P.g, mb = P.mb, mf = P.mf;
-                    QLN_STEP_BASE();
+                    const double* uk = L.U + 5 * k;
+                    const StepBlock blk = step_block(x, uk[0], uk[1], uk[2], uk[3], uk[4], knot_mode(k + 1, kt - 1, im), M);
                     double* e = ent + (int64_t)k * kEnt;
-#define JW(row, col, val)                              \
-    {                                                  \
-        constexpr int pos_ = step_union_pos(row, col); \
-        e[pos_] = (val);                               \
-    }
-                    QLN_STEP_ENTRIES();
-#undef JW
+                    for_each_step_entry(blk, [&](auto row, auto col, double val) {
+                        constexpr int pos_ = step_union_pos(row, col);
+                        e[pos_] = val;
+                    });
                 }
             }
             __threadfence();  // the entries are read back by other lanes of this wave
@@ -1251,7 +1239,7 @@ __global__ __launch_bounds__(kWave) void k_exact_rollout(BatchParams P, SolvePar
     if (b >= P.B) return;
     const ProblemDesc pd = P.desc[b];
     const int N = P.N, kt = pd.k_trans, im = pd.init_mode;
-    const double Ib = P.mb * (P.lb * P.lb) / 12;
+    const Model M(P);
     double* __restrict__ Zb = Zio + (int64_t)b * P.z_stride;
     const double* __restrict__ x0g = P.bnd + (int64_t)b * 30;
     const double* __restrict__ costg = P.cost + (P.cost_batch > 1 ? (int64_t)b * N * 41 : 0);
@@ -1298,7 +1286,7 @@ __global__ __launch_bounds__(kWave) void k_exact_rollout(BatchParams P, SolvePar
         }
         state_rows(k, x);
         if (k == N - 2) up(fabs(u[1] + u[3] + P.mb * P.g));
-        step_forward(P, k, kt, im, Ib, x, u, xn);
+        step_forward(M, k, kt, im, x, u, xn);
 #pragma unroll
         for (int i = 0; i < 15; ++i) {
             x[i] = xn[i];

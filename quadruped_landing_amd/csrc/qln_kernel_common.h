@@ -1,8 +1,21 @@
-// qln_kernel_common.h -- device helpers shared by the gfx950 kernels (qln_kernels.hip: the evaluator;
-// qln_solver_kernels.hip: Jacobian products and the batched Gauss-Newton step).  Internal.
+// qln_kernel_common.h -- device code shared by the gfx950 kernel files.  Internal.
+//   * wave / dispatch helpers;
+//   * the value path: dynamics, rk4_step, step_forward (one knot of a roll-out), literal restatements of the reference
+//     that round like it;
+//   * the 15 x 20 step Jacobian in closed form, the one statement of it that the evaluator (qln_kernels.hip), J v / J' lam
+//     and the Gauss-Newton step (qln_solver_kernels.hip), the iLQR solve (qln_ilqr_kernels.hip) and the TVLQR sweep
+//     (qln_tracking_kernels.hip) share: StepBlock + step_block() form a knot's base quantities from explicit arguments
+//     (states, forces, h, KnotMode, Model), for_each_step_entry() visits the 85 entries of the union pattern with row and
+//     col as compile-time constants.  A static_assert holds the visit order to step_union_pos().
+// The functions here are compiled under the floating-point contraction mode in force where this header is INCLUDED.
+// qln_solver_kernels.hip sets contract(fast) above the include so that its step blocks fuse; the same then holds for
+// EVERYTHING in this header in that file: a value-path helper (rk4_step, step_forward) called from there would fuse too
+// and no longer round like the reference.  None is called there today.
 #pragma once
 
 #include "qln_device.h"
+
+#include <type_traits>
 
 namespace qln {
 namespace {
@@ -89,113 +102,172 @@ __device__ __forceinline__ void rk4_step(const double (&x)[15], const double (&u
 }
 
 // one dynamics knot of a roll-out (qln_solve's and qln_tracking_rollout's): the evaluator's RK4 step + jump map (src/constraints.jl:19-38)
-__device__ __forceinline__ void step_forward(const BatchParams& P, int k, int kt, int im, double Ib, const double (&x)[15],
-                                             const double (&u)[5], double (&xn)[15]) {
-    const int K = k + 1;
-    const int mode = (K <= kt - 1) ? im : 3;
-    const bool jump = (K == kt - 1);
-    const bool f1free = (mode == 2), f2free = (mode == 1);
+__device__ __forceinline__ void step_forward(const Model& M, int k, int kt, int im, const double (&x)[15], const double (&u)[5],
+                                             double (&xn)[15]) {
+    const KnotMode md = knot_mode(k + 1, kt - 1, im);
     StepConst sc;
-    sc.abx = (u[0] + u[2]) / P.mb;
-    sc.aby = (u[1] + u[3]) / P.mb + P.g;
-    sc.a1x = f1free ? (-u[0] / P.mf) : 0.0;
-    sc.a1y = f1free ? (-u[1] / P.mf + P.g) : 0.0;
-    sc.a2x = f2free ? (-u[2] / P.mf) : 0.0;
-    sc.a2y = f2free ? (-u[3] / P.mf + P.g) : 0.0;
-    rk4_step(x, u, sc, f1free, f2free, Ib, xn);
-    if (jump) {
+    sc.abx = (u[0] + u[2]) / M.mb;
+    sc.aby = (u[1] + u[3]) / M.mb + M.g;
+    sc.a1x = md.f1free ? (-u[0] / M.mf) : 0.0;
+    sc.a1y = md.f1free ? (-u[1] / M.mf + M.g) : 0.0;
+    sc.a2x = md.f2free ? (-u[2] / M.mf) : 0.0;
+    sc.a2y = md.f2free ? (-u[3] / M.mf + M.g) : 0.0;
+    rk4_step(x, u, sc, md.f1free, md.f2free, M.Ib, xn);
+    if (md.jump) {
         xn[4] = 0.0;
         xn[6] = 0.0;
         xn[10] = xn[11] = xn[12] = xn[13] = 0.0;
     }
 }
 
-// Base quantities of a step block (closed form in qln_kernels.hip's header) from the knot's state x[0..13], forces
-// F1x..F2y, step h, the mode flags f1free / f2free / jump and the model constants g, mb, mf, Ib in scope.  Defines
-// everything QLN_STEP_ENTRIES() refers to.  Column 19 (hc[]), the eight force-column entries of the theta/omega rows
-// and a dozen scalars are values; the 30 (weight x force) products of the theta/omega rows are formed where an
-// entry is used, from wAt / wBt / wAw (one multiply each).
-#define QLN_STEP_BASE()                                                                              \
-    const double m1 = f1free ? 1.0 : 0.0, m2 = f2free ? 1.0 : 0.0; \
-    const double keep = jump ? 0.0 : 1.0; \
-    const double km1 = keep * m1, km2 = keep * m2; \
-    const double abx = (F1x + F2x) / mb, aby = (F1y + F2y) / mb + g; \
-    const double a1x = m1 * (-F1x / mf), a1y = m1 * (-F1y / mf + g); \
-    const double a2x = m2 * (-F2x / mf), a2y = m2 * (-F2y / mf + g); \
-    const double h2 = h * h, h3 = h2 * h, h4 = h2 * h2; \
-    const double iIb = 1.0 / Ib; \
-    const double Aw = h * iIb; \
-    const double At = 0.5 * h2 * iIb; \
-    const double Bt = h3 * iIb * (1.0 / 6.0); \
-    const double Ct = h4 * iIb * (1.0 / 24.0); \
-    const double sFx = F1x + F2x, sFy = F1y + F2y; \
-    const double r1x = x[3] - x[0], r1y = x[4] - x[1], r2x = x[5] - x[0], r2y = x[6] - x[1]; \
-    const double w1x = m1 * x[10] - x[7], w1y = m1 * x[11] - x[8]; \
-    const double w2x = m2 * x[12] - x[7], w2y = m2 * x[13] - x[8]; \
-    const double tau0 = r1x * F1y - r1y * F1x + r2x * F2y - r2y * F2x; \
-    const double tauv = w1x * F1y - w1y * F1x + w2x * F2y - w2y * F2x; \
-    const double ga1 = g * (1.0 - m1), ga2 = g * (1.0 - m2); \
-    const double taua = ga1 * F1x + ga2 * F2x; \
-    const double hmb = h / mb, h2mb = 0.5 * h2 / mb, hmf = h / mf, h2mf = 0.5 * h2 / mf; \
-    double hc[15]; \
-    hc[0] = x[7] + h * abx; \
-    hc[1] = x[8] + h * aby; \
-    hc[2] = x[9] + (Aw * tau0 + At * tauv + Bt * taua); \
-    hc[3] = m1 * (x[10] + h * a1x); \
-    hc[4] = km1 * (x[11] + h * a1y); \
-    hc[5] = m2 * (x[12] + h * a2x); \
-    hc[6] = km2 * (x[13] + h * a2y); \
-    hc[7] = abx; \
-    hc[8] = aby; \
-    hc[9] = iIb * (tau0 + h * tauv + 0.5 * h2 * taua); \
-    hc[10] = keep * a1x; \
-    hc[11] = keep * a1y; \
-    hc[12] = keep * a2x; \
-    hc[13] = keep * a2y; \
-    hc[14] = keep; \
-    const double t15 = -At * r1y - Bt * w1y + Ct * ga1, t16 = At * r1x + Bt * w1x; \
-    const double t17 = -At * r2y - Bt * w2y + Ct * ga2, t18 = At * r2x + Bt * w2x; \
-    const double o15 = -Aw * r1y - At * w1y + Bt * ga1, o16 = Aw * r1x + At * w1x; \
-    const double o17 = -Aw * r2y - At * w2y + Bt * ga2, o18 = Aw * r2x + At * w2x; \
-    const double mF1x = m1 * F1x, mF1y = m1 * F1y, mF2x = m2 * F2x, mF2y = m2 * F2y; \
-    const double s_m1h = m1 * h, s_m1h2 = -m1 * h2mf, s_k1h = km1 * h, s_k1h2 = -km1 * h2mf; \
-    const double s_m2h = m2 * h, s_m2h2 = -m2 * h2mf, s_k2h = km2 * h, s_k2h2 = -km2 * h2mf; \
-    const double s_k1f = -km1 * hmf, s_k2f = -km2 * hmf; \
-    double wAt = At, wBt = Bt, wAw = Aw;
+// ---------------------------------------------------------------------------------------------
+// The 15 x 20 step Jacobian in closed form (derivation in qln_kernels.hip's header): the one statement every kernel
+// family forms its blocks from.  step_block() computes the base quantities of a knot, for_each_step_entry() hands out
+// the 85 entries of the union pattern built from them.
+// ---------------------------------------------------------------------------------------------
+// What the 85 entries read.  Column 19 (hc[]), the eight force-column entries of the theta/omega rows and a dozen
+// scalars are values; the 30 (weight x force) products of the theta/omega rows are formed where an entry is used,
+// from wAt / wBt / wAw (one multiply each).  Those three are the h-weights At, Bt, Aw; they are members like the rest,
+// and not const, because the evaluator's dense tile loop passes them through an empty asm to keep the products inside
+// the loop.
+struct StepBlock {
+    double F1x, F1y, F2x, F2y, h;
+    double keep;  // 0 at the jump knot (quirk Q1), else 1
+    double sFx, sFy, mF1x, mF1y, mF2x, mF2y;
+    double hmb, h2mb;
+    double t15, t16, t17, t18, o15, o16, o17, o18;
+    double s_m1h, s_m1h2, s_k1h, s_k1h2, s_m2h, s_m2h2, s_k2h, s_k2h2, s_k1f, s_k2f;
+    double hc[15];
+    double wAt, wBt, wAw;
+};
 
-// The 85 entries of the union pattern of a step block, as JW(row, col, value) statements over the
-// base quantities of the Jacobian phase (closed form in the file header): column 19 (d/dh, dense), row 2
-// (theta) and row 9 (omega), rows 0-1 (body position), rows 3-6 (foot positions; the y rows are masked at
-// the jump), rows 7-8 (body velocity), rows 10-13 (foot velocities) and row 14 (clock), masked at the jump
-// (quirk Q1).  The statements are in column-major order of (row, col) -- the order of the values inside a block
-// in both formats; the structural format's emission relies on it.
-#define QLN_STEP_ENTRIES()                                                                                        \
+// x: the knot's state without the clock; F1x .. F2y, h: its control
+__device__ __forceinline__ StepBlock step_block(const double (&x)[14], double F1x, double F1y, double F2x, double F2y, double h,
+                                                KnotMode md, const Model& M) {
+    const double g = M.g, mb = M.mb, mf = M.mf, Ib = M.Ib;
+    const double m1 = md.f1free ? 1.0 : 0.0, m2 = md.f2free ? 1.0 : 0.0;
+    const double keep = md.jump ? 0.0 : 1.0;
+    const double km1 = keep * m1, km2 = keep * m2;
+    const double abx = (F1x + F2x) / mb, aby = (F1y + F2y) / mb + g;
+    const double a1x = m1 * (-F1x / mf), a1y = m1 * (-F1y / mf + g);
+    const double a2x = m2 * (-F2x / mf), a2y = m2 * (-F2y / mf + g);
+    const double h2 = h * h, h3 = h2 * h, h4 = h2 * h2;
+    const double iIb = 1.0 / Ib;
+    const double Aw = h * iIb;
+    const double At = 0.5 * h2 * iIb;
+    const double Bt = h3 * iIb * (1.0 / 6.0);
+    const double Ct = h4 * iIb * (1.0 / 24.0);
+    const double sFx = F1x + F2x, sFy = F1y + F2y;
+    const double r1x = x[3] - x[0], r1y = x[4] - x[1], r2x = x[5] - x[0], r2y = x[6] - x[1];
+    const double w1x = m1 * x[10] - x[7], w1y = m1 * x[11] - x[8];
+    const double w2x = m2 * x[12] - x[7], w2y = m2 * x[13] - x[8];
+    const double tau0 = r1x * F1y - r1y * F1x + r2x * F2y - r2y * F2x;
+    const double tauv = w1x * F1y - w1y * F1x + w2x * F2y - w2y * F2x;
+    const double ga1 = g * (1.0 - m1), ga2 = g * (1.0 - m2);
+    const double taua = ga1 * F1x + ga2 * F2x;
+    const double hmb = h / mb, h2mb = 0.5 * h2 / mb, hmf = h / mf, h2mf = 0.5 * h2 / mf;
+    StepBlock b;
+    b.F1x = F1x, b.F1y = F1y, b.F2x = F2x, b.F2y = F2y, b.h = h;
+    b.keep = keep;
+    b.sFx = sFx, b.sFy = sFy;
+    b.hmb = hmb, b.h2mb = h2mb;
+    b.hc[0] = x[7] + h * abx;
+    b.hc[1] = x[8] + h * aby;
+    b.hc[2] = x[9] + (Aw * tau0 + At * tauv + Bt * taua);
+    b.hc[3] = m1 * (x[10] + h * a1x);
+    b.hc[4] = km1 * (x[11] + h * a1y);
+    b.hc[5] = m2 * (x[12] + h * a2x);
+    b.hc[6] = km2 * (x[13] + h * a2y);
+    b.hc[7] = abx;
+    b.hc[8] = aby;
+    b.hc[9] = iIb * (tau0 + h * tauv + 0.5 * h2 * taua);
+    b.hc[10] = keep * a1x;
+    b.hc[11] = keep * a1y;
+    b.hc[12] = keep * a2x;
+    b.hc[13] = keep * a2y;
+    b.hc[14] = keep;
+    b.t15 = -At * r1y - Bt * w1y + Ct * ga1, b.t16 = At * r1x + Bt * w1x;
+    b.t17 = -At * r2y - Bt * w2y + Ct * ga2, b.t18 = At * r2x + Bt * w2x;
+    b.o15 = -Aw * r1y - At * w1y + Bt * ga1, b.o16 = Aw * r1x + At * w1x;
+    b.o17 = -Aw * r2y - At * w2y + Bt * ga2, b.o18 = Aw * r2x + At * w2x;
+    b.mF1x = m1 * F1x, b.mF1y = m1 * F1y, b.mF2x = m2 * F2x, b.mF2y = m2 * F2y;
+    b.s_m1h = m1 * h, b.s_m1h2 = -m1 * h2mf, b.s_k1h = km1 * h, b.s_k1h2 = -km1 * h2mf;
+    b.s_m2h = m2 * h, b.s_m2h2 = -m2 * h2mf, b.s_k2h = km2 * h, b.s_k2h2 = -km2 * h2mf;
+    b.s_k1f = -km1 * hmf, b.s_k2f = -km2 * hmf;
+    b.wAt = At, b.wBt = Bt, b.wAw = Aw;
+    return b;
+}
+// the knot as it lies in Z: x_k at zk[0..14], u_k = (F1x, F1y, F2x, F2y, h) behind it
+__device__ __forceinline__ StepBlock step_block(const double* zk, KnotMode md, const Model& M) {
+    double x[14];
+#pragma unroll
+    for (int i = 0; i < 14; ++i) x[i] = zk[i];
+    return step_block(x, zk[15], zk[16], zk[17], zk[18], zk[19], md, M);
+}
+
+// The one list of the 85 entries of the union pattern, E(row, col, value) over a StepBlock b: column 19 (d/dh,
+// dense), row 2 (theta) and row 9 (omega), rows 0-1 (body position), rows 3-6 (foot positions; the y rows are masked
+// at the jump), rows 7-8 (body velocity), rows 10-13 (foot velocities) and row 14 (clock), masked at the jump (quirk
+// Q1).  In column-major order of (row, col) -- the order of the values inside a block in both formats; the structural
+// format's emission and step_union_pos() rely on it, and the static_assert below holds the list to it.  Private to
+// this header: the two visitors below are the interface.
+#define QLN_STEP_ENTRY_LIST(E)                                                                                    \
     /* columns 0-6: positions */                                                                                  \
-    JW(0, 0, 1.0); JW(2, 0, -wAt * sFy); JW(9, 0, -wAw * sFy);                                                    \
-    JW(1, 1, 1.0); JW(2, 1, wAt * sFx); JW(9, 1, wAw * sFx);                                                      \
-    JW(2, 2, 1.0);                                                                                                \
-    JW(2, 3, wAt * F1y); JW(3, 3, 1.0); JW(9, 3, wAw * F1y);                                                      \
-    JW(2, 4, -wAt * F1x); JW(4, 4, keep); JW(9, 4, -wAw * F1x);                                                   \
-    JW(2, 5, wAt * F2y); JW(5, 5, 1.0); JW(9, 5, wAw * F2y);                                                      \
-    JW(2, 6, -wAt * F2x); JW(6, 6, keep); JW(9, 6, -wAw * F2x);                                                   \
+    E(0, 0, 1.0) E(2, 0, -b.wAt * b.sFy) E(9, 0, -b.wAw * b.sFy)                                                  \
+    E(1, 1, 1.0) E(2, 1, b.wAt * b.sFx) E(9, 1, b.wAw * b.sFx)                                                    \
+    E(2, 2, 1.0)                                                                                                  \
+    E(2, 3, b.wAt * b.F1y) E(3, 3, 1.0) E(9, 3, b.wAw * b.F1y)                                                    \
+    E(2, 4, -b.wAt * b.F1x) E(4, 4, b.keep) E(9, 4, -b.wAw * b.F1x)                                               \
+    E(2, 5, b.wAt * b.F2y) E(5, 5, 1.0) E(9, 5, b.wAw * b.F2y)                                                    \
+    E(2, 6, -b.wAt * b.F2x) E(6, 6, b.keep) E(9, 6, -b.wAw * b.F2x)                                               \
     /* columns 7-14: velocities and the clock */                                                                  \
-    JW(0, 7, h); JW(2, 7, -wBt * sFy); JW(7, 7, 1.0); JW(9, 7, -wAt * sFy);                                       \
-    JW(1, 8, h); JW(2, 8, wBt * sFx); JW(8, 8, 1.0); JW(9, 8, wAt * sFx);                                         \
-    JW(2, 9, h); JW(9, 9, 1.0);                                                                                   \
-    JW(2, 10, wBt * mF1y); JW(3, 10, s_m1h); JW(9, 10, wAt * mF1y); JW(10, 10, keep);                             \
-    JW(2, 11, -wBt * mF1x); JW(4, 11, s_k1h); JW(9, 11, -wAt * mF1x); JW(11, 11, keep);                           \
-    JW(2, 12, wBt * mF2y); JW(5, 12, s_m2h); JW(9, 12, wAt * mF2y); JW(12, 12, keep);                             \
-    JW(2, 13, -wBt * mF2x); JW(6, 13, s_k2h); JW(9, 13, -wAt * mF2x); JW(13, 13, keep);                           \
-    JW(14, 14, keep);                                                                                             \
+    E(0, 7, b.h) E(2, 7, -b.wBt * b.sFy) E(7, 7, 1.0) E(9, 7, -b.wAt * b.sFy)                                     \
+    E(1, 8, b.h) E(2, 8, b.wBt * b.sFx) E(8, 8, 1.0) E(9, 8, b.wAt * b.sFx)                                       \
+    E(2, 9, b.h) E(9, 9, 1.0)                                                                                     \
+    E(2, 10, b.wBt * b.mF1y) E(3, 10, b.s_m1h) E(9, 10, b.wAt * b.mF1y) E(10, 10, b.keep)                         \
+    E(2, 11, -b.wBt * b.mF1x) E(4, 11, b.s_k1h) E(9, 11, -b.wAt * b.mF1x) E(11, 11, b.keep)                       \
+    E(2, 12, b.wBt * b.mF2y) E(5, 12, b.s_m2h) E(9, 12, b.wAt * b.mF2y) E(12, 12, b.keep)                         \
+    E(2, 13, -b.wBt * b.mF2x) E(6, 13, b.s_k2h) E(9, 13, -b.wAt * b.mF2x) E(13, 13, b.keep)                       \
+    E(14, 14, b.keep)                                                                                             \
     /* columns 15-18: forces */                                                                                   \
-    JW(0, 15, h2mb); JW(2, 15, t15); JW(3, 15, s_m1h2); JW(7, 15, hmb); JW(9, 15, o15); JW(10, 15, s_k1f);        \
-    JW(1, 16, h2mb); JW(2, 16, t16); JW(4, 16, s_k1h2); JW(8, 16, hmb); JW(9, 16, o16); JW(11, 16, s_k1f);        \
-    JW(0, 17, h2mb); JW(2, 17, t17); JW(5, 17, s_m2h2); JW(7, 17, hmb); JW(9, 17, o17); JW(12, 17, s_k2f);        \
-    JW(1, 18, h2mb); JW(2, 18, t18); JW(6, 18, s_k2h2); JW(8, 18, hmb); JW(9, 18, o18); JW(13, 18, s_k2f);        \
+    E(0, 15, b.h2mb) E(2, 15, b.t15) E(3, 15, b.s_m1h2) E(7, 15, b.hmb) E(9, 15, b.o15) E(10, 15, b.s_k1f)        \
+    E(1, 16, b.h2mb) E(2, 16, b.t16) E(4, 16, b.s_k1h2) E(8, 16, b.hmb) E(9, 16, b.o16) E(11, 16, b.s_k1f)        \
+    E(0, 17, b.h2mb) E(2, 17, b.t17) E(5, 17, b.s_m2h2) E(7, 17, b.hmb) E(9, 17, b.o17) E(12, 17, b.s_k2f)        \
+    E(1, 18, b.h2mb) E(2, 18, b.t18) E(6, 18, b.s_k2h2) E(8, 18, b.hmb) E(9, 18, b.o18) E(13, 18, b.s_k2f)        \
     /* column 19: the step length h */                                                                            \
-    JW(0, 19, hc[0]); JW(1, 19, hc[1]); JW(2, 19, hc[2]); JW(3, 19, hc[3]); JW(4, 19, hc[4]);                     \
-    JW(5, 19, hc[5]); JW(6, 19, hc[6]); JW(7, 19, hc[7]); JW(8, 19, hc[8]); JW(9, 19, hc[9]);                     \
-    JW(10, 19, hc[10]); JW(11, 19, hc[11]); JW(12, 19, hc[12]); JW(13, 19, hc[13]); JW(14, 19, hc[14])
+    E(0, 19, b.hc[0]) E(1, 19, b.hc[1]) E(2, 19, b.hc[2]) E(3, 19, b.hc[3]) E(4, 19, b.hc[4])                     \
+    E(5, 19, b.hc[5]) E(6, 19, b.hc[6]) E(7, 19, b.hc[7]) E(8, 19, b.hc[8]) E(9, 19, b.hc[9])                     \
+    E(10, 19, b.hc[10]) E(11, 19, b.hc[11]) E(12, 19, b.hc[12]) E(13, 19, b.hc[13]) E(14, 19, b.hc[14])
+
+template <int I>
+using Idx = std::integral_constant<int, I>;  // row and col reach a visitor as constants: usable in if constexpr
+
+// f(row, col, value) for the 85 entries of b, in column-major order
+template <typename F>
+__device__ __forceinline__ void for_each_step_entry(const StepBlock& b, F&& f) {
+#define QLN_E(row, col, val) [[clang::always_inline]] f(Idx<row>{}, Idx<col>{}, (val));
+    QLN_STEP_ENTRY_LIST(QLN_E)
+#undef QLN_E
+}
+// f(row, col) for the same entries in the same order, for whoever holds the values elsewhere (or wants none)
+template <typename F>
+__host__ __device__ __forceinline__ constexpr void for_each_step_entry(F&& f) {
+#define QLN_E(row, col, val) [[clang::always_inline]] f(Idx<row>{}, Idx<col>{});
+    QLN_STEP_ENTRY_LIST(QLN_E)
+#undef QLN_E
+}
+#undef QLN_STEP_ENTRY_LIST
+
+constexpr bool step_entries_in_union_order() {
+    int n = 0;
+    bool ok = true;
+    for_each_step_entry([&](auto row, auto col) {
+        ok = ok && step_union_present(row, col) && step_union_pos(row, col) == n;
+        ++n;
+    });
+    return ok && n == kStepUnion;
+}
+static_assert(step_entries_in_union_order(), "the entries are visited at positions 0 .. 84 of step_union_pos, each once");
 
 }  // namespace
 }  // namespace qln

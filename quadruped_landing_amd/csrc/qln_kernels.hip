@@ -7,7 +7,8 @@
 // kc0 + l.  The problem's slice of the decision vector is read with coalesced loads into LDS, each
 // lane picks its (x_k, u_k, x_{k+1}) out of LDS, integrates the RK4 step in registers (literal
 // reference operation order, no FMA contraction, so the residual rounds like the reference) and
-// forms the 85 structurally non-zero entries of the 15x20 step Jacobian in closed form.  The dense
+// forms the 85 structurally non-zero entries of the 15x20 step Jacobian in closed form (step_block /
+// for_each_step_entry of qln_kernel_common.h, which every kernel family shares).  The dense
 // 300-double blocks the reference's Jacobian is made of are then assembled T knots at a time in an
 // LDS tile whose structural zeros are written once, and streamed to HBM as full 16-byte-per-lane,
 // 1-KiB-per-instruction stores.  The kernel is HBM-write bound (2400 B of Jacobian per knot against
@@ -350,8 +351,11 @@ __global__ __launch_bounds__(kWave, W) void k_constraint_jacobian(BatchParams P,
     double* __restrict__ Cb = WITH_C ? C + pd.c_off : nullptr;
     double* __restrict__ Vb = WITH_J ? V + pd.j_off : nullptr;
 
-    const double g = P.g, mb = P.mb, mf = P.mf, lb = P.lb;
-    const double Ib = mb * (lb * lb) / 12;  // mb * lb^2 / 12, src/planar_quadruped.jl:41
+    const Model M(P);
+    // the clearance rows keep the body length in a scalar of its own: with M.lb read inside the chunk loop the compiler
+    // forms both signs of lb / 2 * cos(theta) per lane (one more multiply) instead of selecting the sign of lb / 2.
+    // Nothing but `make resource-usage` and the opcode counts of profiles/step_block_refactor_resource_usage.txt guard this.
+    const double lb = M.lb;
 
     // offsets of the constraint groups inside c (0-based; cinds of src/nlp.jl:48-63)
     const int o_dyn = 29;
@@ -448,10 +452,7 @@ __global__ __launch_bounds__(kWave, W) void k_constraint_jacobian(BatchParams P,
         const int K = k + 1;
         // mode schedule, src/constraints.jl:23-37: K < k_trans-1 -> init mode; K == k_trans-1 ->
         // init mode then jump map; else mode 3.  mode 1 = foot 2 free, mode 2 = foot 1 free.
-        const int mode = (K <= kt - 1) ? im : 3;
-        const bool jump = (K == kt - 1);
-        const bool f1free = (mode == 2);
-        const bool f2free = (mode == 1);
+        const KnotMode md = knot_mode(K, kt - 1, im);
         const double* zl = s_z + 20 * (valid ? lane : 0);
 
         // ---- stage the chunk's slice of Z through LDS (the first one was requested at kernel entry) ----
@@ -473,7 +474,7 @@ __global__ __launch_bounds__(kWave, W) void k_constraint_jacobian(BatchParams P,
                 if (first_chunk && lane < 15) c_put(lane, s_z[lane] - bnd);
                 if (last_chunk) {
                     if (lane >= 15 && lane < 29) c_put(lane, s_z[20 * nk + (lane - 15)] - bnd);
-                    if (lane == 29) c_put(o_fc, s_z[20 * (nk - 1) + 16] + s_z[20 * (nk - 1) + 18] + mb * g);
+                    if (lane == 29) c_put(o_fc, s_z[20 * (nk - 1) + 16] + s_z[20 * (nk - 1) + 18] + M.mb * M.g);
                 }
             }
             if (kc0 == kc_begin) prefetch_later_workgroup();  // the wave's own first slice (and bnd) have arrived
@@ -492,20 +493,20 @@ __global__ __launch_bounds__(kWave, W) void k_constraint_jacobian(BatchParams P,
             for (int i = 0; i < 15; ++i) xnext[i] = zl[20 + i];
 
             StepConst sc;
-            sc.abx = (u[0] + u[2]) / mb;
-            sc.aby = (u[1] + u[3]) / mb + g;
-            sc.a1x = f1free ? (-u[0] / mf) : 0.0;
-            sc.a1y = f1free ? (-u[1] / mf + g) : 0.0;
-            sc.a2x = f2free ? (-u[2] / mf) : 0.0;
-            sc.a2y = f2free ? (-u[3] / mf + g) : 0.0;
+            sc.abx = (u[0] + u[2]) / M.mb;
+            sc.aby = (u[1] + u[3]) / M.mb + M.g;
+            sc.a1x = md.f1free ? (-u[0] / M.mf) : 0.0;
+            sc.a1y = md.f1free ? (-u[1] / M.mf + M.g) : 0.0;
+            sc.a2x = md.f2free ? (-u[2] / M.mf) : 0.0;
+            sc.a2y = md.f2free ? (-u[3] / M.mf + M.g) : 0.0;
             double xn[15];
             if (!QLN_FLOOR_MODE) {
-                rk4_step(x, u, sc, f1free, f2free, Ib, xn);
+                rk4_step(x, u, sc, md.f1free, md.f2free, M.Ib, xn);
             } else {
 #pragma unroll
                 for (int i = 0; i < 15; ++i) xn[i] = x[i];
             }
-            if (jump) {  // jump1_map / jump2_map, src/planar_quadruped.jl:250-260
+            if (md.jump) {  // jump1_map / jump2_map, src/planar_quadruped.jl:250-260
                 xn[4] = 0.0;
                 xn[6] = 0.0;
                 xn[10] = xn[11] = xn[12] = xn[13] = 0.0;
@@ -621,7 +622,7 @@ __global__ __launch_bounds__(kWave, W) void k_constraint_jacobian(BatchParams P,
                 }
             }
             // ---- base quantities of the step block's 85 non-zeros (closed form, see header) ----
-            QLN_STEP_BASE();
+            StepBlock blk = step_block(x, F1x, F1y, F2x, F2y, h, md, M);
 
             QLN_STAMP(3);
             if constexpr (NNZ) {
@@ -646,26 +647,26 @@ __global__ __launch_bounds__(kWave, W) void k_constraint_jacobian(BatchParams P,
                     // execute in order).  Only the transition knot's pattern ends early -- the masked rows 11-15 of
                     // column 19 -- and those five writes are predicated.
                     double* jr = s_j + p0 + (step_block_offset(k, N, kt) - g0);
-                    const int decF = (mode == 3) ? 1 : 0, decJ = jump ? 1 : 0, decFJ = decF + decJ;
+                    const bool jump = md.jump;  // a local: read through md inside emit, the predicated writes below stop sharing a branch (same guard as lb above)
+                    const int decF = md.pinned ? 1 : 0, decJ = jump ? 1 : 0, decFJ = decF + decJ;
                     auto emit = [&](auto catc) {
                         constexpr int CB = decltype(catc)::value;  // contact category of the problem: 0 or 1
                         constexpr int CJ = CB + 3;                 // the same mode followed by the jump
-#define JW(row, col, val)                                                                   \
-    if constexpr (step_entry_present(CB, row, col)) {                                       \
-        constexpr int pos_ = step_entry_pos(CB, row, col);                                  \
-        constexpr bool inF_ = step_entry_present(2, row, col);                              \
-        constexpr bool inJ_ = step_entry_present(CJ, row, col);                             \
-        if constexpr (!inJ_ && step_entry_pos(CJ, row, col) == step_nnz(CJ)) {              \
-            if (!jump) jr[pos_] = (val); /* nothing of the jump pattern follows */          \
-        } else {                                                                            \
-            jr[pos_] = (val);                                                               \
-        }                                                                                   \
-        if constexpr (!inF_ && !inJ_) jr -= decFJ;                                          \
-        else if constexpr (!inF_) jr -= decF;                                               \
-        else if constexpr (!inJ_) jr -= decJ;                                               \
-    }
-                        QLN_STEP_ENTRIES();
-#undef JW
+                        for_each_step_entry(blk, [&](auto row, auto col, double val) {
+                            if constexpr (step_entry_present(CB, row, col)) {
+                                constexpr int pos_ = step_entry_pos(CB, row, col);
+                                constexpr bool inF_ = step_entry_present(2, row, col);
+                                constexpr bool inJ_ = step_entry_present(CJ, row, col);
+                                if constexpr (!inJ_ && step_entry_pos(CJ, row, col) == step_nnz(CJ)) {
+                                    if (!jump) jr[pos_] = val;  // nothing of the jump pattern follows
+                                } else {
+                                    jr[pos_] = val;
+                                }
+                                if constexpr (!inF_ && !inJ_) jr -= decFJ;
+                                else if constexpr (!inF_) jr -= decF;
+                                else if constexpr (!inJ_) jr -= decJ;
+                            }
+                        });
                     };
                     if (im == 1) emit(std::integral_constant<int, 0>{});
                     else emit(std::integral_constant<int, 1>{});
@@ -686,11 +687,9 @@ __global__ __launch_bounds__(kWave, W) void k_constraint_jacobian(BatchParams P,
                 const int nkt = min(T, nk - t * T);  // knots in it
                 if (valid && (lane / T) == t) {
                     double* jr = s_j + (lane - t * T) * kBlk;
-#define JW(row, col, val) jr[(row) + 15 * (col)] = (val)
                     // opaque to loop-invariant code motion (see above)
-                    asm volatile("" : "+v"(wAt), "+v"(wBt), "+v"(wAw));
-                    QLN_STEP_ENTRIES();
-#undef JW
+                    asm volatile("" : "+v"(blk.wAt), "+v"(blk.wBt), "+v"(blk.wAw));
+                    for_each_step_entry(blk, [&](auto row, auto col, double val) { jr[row + 15 * col] = val; });
                 }
                 wave_lds_sync();
                 {
@@ -1142,8 +1141,8 @@ __global__ __launch_bounds__(256) void k_friction_rows(BatchParams P, const doub
     if (t >= (int64_t)P.B * nk) return;
     const int b = (int)(t / nk), k = (int)(t - (int64_t)b * nk);
     const ProblemDesc pd = P.desc[b];
-    const int mode = (k + 1 <= pd.k_trans - 1) ? pd.init_mode : 3;
-    const bool on1 = mode != 2, on2 = mode != 1;  // mode 1: foot 2 in flight; mode 2: foot 1 in flight
+    const KnotMode md = knot_mode(k + 1, pd.k_trans - 1, pd.init_mode);
+    const bool on1 = !md.f1free, on2 = !md.f2free;  // mode 1: foot 2 in flight; mode 2: foot 1 in flight
     const double* u = Z + (int64_t)b * P.z_stride + 20 * k + 15;
     double* d = D + 4 * t;
     d[0] = on1 ? mu * u[1] - u[0] : 0.0;

@@ -11,10 +11,14 @@
 //
 // Mapping as in the evaluator: one 64-lane wavefront (= one workgroup) per problem, lane = knot, chunks of 63
 // dynamics knots so that lane nk is free for the knot behind the chunk (the terminal knot x_N in the last one).
-#include "qln_kernel_common.h"
 
 // Nothing here has to round like the reference (the parity tests hold these kernels to 1e-8), so a*b+c may fuse.
+// Above the include on purpose: a function keeps the contraction mode of the place it is DEFINED, so the header's
+// step_block() and for_each_step_entry() fuse here only if the pragma precedes them.  (The header's value path,
+// rk4_step / step_forward, is not called from this file.)
 #pragma clang fp contract(fast)
+
+#include "qln_kernel_common.h"
 
 namespace qln {
 namespace {
@@ -82,8 +86,7 @@ __global__ __launch_bounds__(kWave) void k_constraint_jvp(BatchParams P, const d
     const double* __restrict__ Zb = Z + (int64_t)b * P.z_stride;
     const double* __restrict__ Vb = V + (int64_t)b * P.z_stride;
     double* __restrict__ Yb = Y + pd.c_off;
-    const double g = P.g, mb = P.mb, mf = P.mf, lb = P.lb;
-    const double Ib = mb * (lb * lb) / 12;
+    const Model M(P);
 
     for (int kc0 = 0; kc0 < N - 1; kc0 += kPC) {
         const int nk = min(kPC, N - 1 - kc0);
@@ -111,7 +114,7 @@ __global__ __launch_bounds__(kWave) void k_constraint_jvp(BatchParams P, const d
         const double* vk = s_v + 20 * (own ? lane : 0);
         {
             // contact rows (:235-256) and clearance rows (:263-274), one per knot
-            const double dth = clearance_dtheta(zk[2], lb);
+            const double dth = clearance_dtheta(zk[2], M.lb);
             if (own) {
                 Yb[pv.o_ci + kk] = pv.init1 ? vk[4] : vk[6];
                 if (K >= kt) Yb[pv.o_co + (K - kt)] = pv.init1 ? vk[6] : vk[4];
@@ -120,21 +123,13 @@ __global__ __launch_bounds__(kWave) void k_constraint_jvp(BatchParams P, const d
         }
         if (valid) {
             // dynamics rows: D[ci, [x_k; u_k]] = J_k (jump-masked at k_trans-1), D[ci, x_{k+1}] = -I (:186-200)
-            double x[14];
-#pragma unroll
-            for (int i = 0; i < 14; ++i) x[i] = zk[i];
-            const double F1x = zk[15], F1y = zk[16], F2x = zk[17], F2y = zk[18], h = zk[19];
-            const int mode = (K <= kt - 1) ? im : 3;
-            const bool jump = (K == kt - 1), f1free = (mode == 2), f2free = (mode == 1);
-            QLN_STEP_BASE();
+            const StepBlock blk = step_block(zk, knot_mode(K, kt - 1, im), M);
             double vin[20], y[15];
 #pragma unroll
             for (int i = 0; i < 20; ++i) vin[i] = vk[i];
 #pragma unroll
             for (int i = 0; i < 15; ++i) y[i] = 0.0;
-#define JW(row, col, val) y[row] += (val) * vin[col]
-            QLN_STEP_ENTRIES();
-#undef JW
+            for_each_step_entry(blk, [&](auto row, auto col, double val) { y[row] += val * vin[col]; });
 #pragma unroll
             for (int i = 0; i < 15; ++i) y[i] -= vk[20 + i];
             wave_lds_sync();  // every lane is done with the staged slice of Z: its bytes now take the product rows
@@ -169,8 +164,7 @@ __global__ __launch_bounds__(kWave) void k_constraint_vjp(BatchParams P, const d
     const double* __restrict__ Zb = Z + (int64_t)b * P.z_stride;
     const double* __restrict__ Lb = L + pd.c_off;
     double* __restrict__ Gb = G + (int64_t)b * P.z_stride;
-    const double g = P.g, mb = P.mb, mf = P.mf, lb = P.lb;
-    const double Ib = mb * (lb * lb) / 12;
+    const Model M(P);
 
     for (int kc0 = 0; kc0 < N - 1; kc0 += kPC) {
         const int nk = min(kPC, N - 1 - kc0);
@@ -214,22 +208,14 @@ __global__ __launch_bounds__(kWave) void k_constraint_vjp(BatchParams P, const d
 #pragma unroll
         for (int i = 0; i < 20; ++i) gk[i] = 0.0;
         if (valid) {
-            double x[14];
-#pragma unroll
-            for (int i = 0; i < 14; ++i) x[i] = zk[i];
-            const double F1x = zk[15], F1y = zk[16], F2x = zk[17], F2y = zk[18], h = zk[19];
-            const int mode = (K <= kt - 1) ? im : 3;
-            const bool jump = (K == kt - 1), f1free = (mode == 2), f2free = (mode == 1);
-            QLN_STEP_BASE();
+            const StepBlock blk = step_block(zk, knot_mode(K, kt - 1, im), M);
             double lam[15];
 #pragma unroll
             for (int i = 0; i < 15; ++i) lam[i] = s_l[15 * (lane + 1) + i];
-#define JW(row, col, val) gk[col] += (val) * lam[row]
-            QLN_STEP_ENTRIES();
-#undef JW
+            for_each_step_entry(blk, [&](auto row, auto col, double val) { gk[col] += val * lam[row]; });
         }
         {
-            const double dth = clearance_dtheta(zk[2], lb);
+            const double dth = clearance_dtheta(zk[2], M.lb);
             if (own) {
                 // -I of the previous dynamics knot (zeros for the first knot)
 #pragma unroll
@@ -279,10 +265,6 @@ __global__ __launch_bounds__(kWave) void k_constraint_vjp(BatchParams P, const d
 // truncation), which is what an outer trust-region loop needs.
 // LDS per problem: (5 n_nlp + 2 m_nlp + N) doubles = 43 KB at N = 40, 87 KB at N = 80; N <= 149 fits the 160 KB of a CU.
 // ---------------------------------------------------------------------------------------------
-struct ModelConst {
-    double g, mb, mf, lb, Ib;
-};
-
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
@@ -298,27 +280,17 @@ struct KnotJac {
     double dth;            // d(clearance)/d(theta)
 };
 
-__device__ __forceinline__ void knot_jacobian(const ProblemView& pv, const ModelConst& M, const double* z, int lane,
+__device__ __forceinline__ void knot_jacobian(const ProblemView& pv, const Model& M, const double* z, int lane,
                                               KnotJac& J) {
     const int N = pv.N, kt = pv.kt, im = pv.im;
-    const double g = M.g, mb = M.mb, mf = M.mf, lb = M.lb, Ib = M.Ib;
     const int kk = lane, K = kk + 1;
-    const double* zk = z + 20 * (kk < N ? kk : 0);
-    J.dth = clearance_dtheta(zk[2], lb);
-    double x[14];
-#pragma unroll
-    for (int i = 0; i < 14; ++i) x[i] = zk[i];
-    const double F1x = zk[15], F1y = zk[16], F2x = zk[17], F2y = zk[18], h = zk[19];  // (unused garbage for kk >= N-1)
-    const int mode = (K <= kt - 1) ? im : 3;
-    const bool jump = (K == kt - 1), f1free = (mode == 2), f2free = (mode == 1);
-    QLN_STEP_BASE();
-#define JW(row, col, val)                                \
-    {                                                    \
-        constexpr int pos_ = step_union_pos(row, col);   \
-        J.e[pos_] = (val);                               \
-    }
-    QLN_STEP_ENTRIES();
-#undef JW
+    const double* zk = z + 20 * (kk < N ? kk : 0);  // (the block of a lane kk >= N-1 is unused garbage)
+    J.dth = clearance_dtheta(zk[2], M.lb);
+    const StepBlock blk = step_block(zk, knot_mode(K, kt - 1, im), M);
+    for_each_step_entry(blk, [&](auto row, auto col, double val) {
+        constexpr int pos_ = step_union_pos(row, col);
+        J.e[pos_] = val;
+    });
 }
 
 // (A D) v with the lane's block in registers (N <= 64)
@@ -345,13 +317,10 @@ __device__ __forceinline__ void lds_jvp_cached(const ProblemView& pv, const Knot
         for (int i = 0; i < 20; ++i) vin[i] = dk[i] * vk[i];
 #pragma unroll
         for (int i = 0; i < 15; ++i) acc[i] = 0.0;
-#define JW(row, col, val)                                \
-    {                                                    \
-        constexpr int pos_ = step_union_pos(row, col);   \
-        acc[row] += J.e[pos_] * vin[col];                \
-    }
-        QLN_STEP_ENTRIES();
-#undef JW
+        for_each_step_entry([&](auto row, auto col) {
+            constexpr int pos_ = step_union_pos(row, col);
+            acc[row] += J.e[pos_] * vin[col];
+        });
 #pragma unroll
         for (int i = 0; i < 15; ++i) y[pv.o_dyn + 15 * kk + i] = acc[i] - dk[20 + i] * vk[20 + i];
     }
@@ -370,13 +339,10 @@ __device__ __forceinline__ void lds_vjp_cached(const ProblemView& pv, const Knot
         double l[15];
 #pragma unroll
         for (int i = 0; i < 15; ++i) l[i] = lam[pv.o_dyn + 15 * kk + i];
-#define JW(row, col, val)                                \
-    {                                                    \
-        constexpr int pos_ = step_union_pos(row, col);   \
-        gk[col] += J.e[pos_] * l[row];                   \
-    }
-        QLN_STEP_ENTRIES();
-#undef JW
+        for_each_step_entry([&](auto row, auto col) {
+            constexpr int pos_ = step_union_pos(row, col);
+            gk[col] += J.e[pos_] * l[row];
+        });
     }
     if (own) {
         if (kk >= 1) {
@@ -412,10 +378,9 @@ __device__ __forceinline__ void lds_vjp_cached(const ProblemView& pv, const Knot
 }
 
 // (A D) v: the columns of A are scaled by dsc (0 = variable held fixed); every block re-derived from z (any N)
-__device__ __forceinline__ void lds_jvp(const ProblemView& pv, const ModelConst& M, const double* z, const double* v,
+__device__ __forceinline__ void lds_jvp(const ProblemView& pv, const Model& M, const double* z, const double* v,
                                         const double* dsc, const double* mask, double* y, int lane) {
     const int N = pv.N, kt = pv.kt, im = pv.im;
-    const double g = M.g, mb = M.mb, mf = M.mf, lb = M.lb, Ib = M.Ib;
     if (lane < 15) y[lane] = dsc[lane] * v[lane];
     if (lane >= 15 && lane < 29) y[lane] = dsc[20 * (N - 1) + (lane - 15)] * v[20 * (N - 1) + (lane - 15)];
     if (lane == 29)
@@ -426,7 +391,7 @@ __device__ __forceinline__ void lds_jvp(const ProblemView& pv, const ModelConst&
         const double* zk = z + 20 * (own ? kk : 0);
         const double* vk = v + 20 * (own ? kk : 0);
         const double* dk = dsc + 20 * (own ? kk : 0);
-        const double dth = clearance_dtheta(zk[2], lb);
+        const double dth = clearance_dtheta(zk[2], M.lb);
         if (own) {
             const double v4 = dk[4] * vk[4], v6 = dk[6] * vk[6];
             y[pv.o_ci + kk] = pv.init1 ? v4 : v6;
@@ -434,21 +399,13 @@ __device__ __forceinline__ void lds_jvp(const ProblemView& pv, const ModelConst&
             y[pv.o_bp + kk] = mask[kk] * (dk[1] * vk[1] + dth * (dk[2] * vk[2]));
         }
         if (valid) {
-            double x[14];
-#pragma unroll
-            for (int i = 0; i < 14; ++i) x[i] = zk[i];
-            const double F1x = zk[15], F1y = zk[16], F2x = zk[17], F2y = zk[18], h = zk[19];
-            const int mode = (K <= kt - 1) ? im : 3;
-            const bool jump = (K == kt - 1), f1free = (mode == 2), f2free = (mode == 1);
-            QLN_STEP_BASE();
+            const StepBlock blk = step_block(zk, knot_mode(K, kt - 1, im), M);
             double vin[20], acc[15];
 #pragma unroll
             for (int i = 0; i < 20; ++i) vin[i] = dk[i] * vk[i];
 #pragma unroll
             for (int i = 0; i < 15; ++i) acc[i] = 0.0;
-#define JW(row, col, val) acc[row] += (val) * vin[col]
-            QLN_STEP_ENTRIES();
-#undef JW
+            for_each_step_entry(blk, [&](auto row, auto col, double val) { acc[row] += val * vin[col]; });
 #pragma unroll
             for (int i = 0; i < 15; ++i) y[pv.o_dyn + 15 * kk + i] = acc[i] - dk[20 + i] * vk[20 + i];
         }
@@ -457,10 +414,9 @@ __device__ __forceinline__ void lds_jvp(const ProblemView& pv, const ModelConst&
 
 // gz = A' lam, all operands in LDS
 // (A D)' lam
-__device__ __forceinline__ void lds_vjp(const ProblemView& pv, const ModelConst& M, const double* z, const double* lam,
+__device__ __forceinline__ void lds_vjp(const ProblemView& pv, const Model& M, const double* z, const double* lam,
                                         const double* dsc, const double* mask, double* gz, int lane) {
     const int N = pv.N, kt = pv.kt, im = pv.im;
-    const double g = M.g, mb = M.mb, mf = M.mf, lb = M.lb, Ib = M.Ib;
     for (int k0 = 0; k0 < N; k0 += kWave) {
         const int kk = k0 + lane, K = kk + 1;
         const bool own = kk < N, valid = kk < N - 1;
@@ -469,21 +425,13 @@ __device__ __forceinline__ void lds_vjp(const ProblemView& pv, const ModelConst&
 #pragma unroll
         for (int i = 0; i < 20; ++i) gk[i] = 0.0;
         if (valid) {
-            double x[14];
-#pragma unroll
-            for (int i = 0; i < 14; ++i) x[i] = zk[i];
-            const double F1x = zk[15], F1y = zk[16], F2x = zk[17], F2y = zk[18], h = zk[19];
-            const int mode = (K <= kt - 1) ? im : 3;
-            const bool jump = (K == kt - 1), f1free = (mode == 2), f2free = (mode == 1);
-            QLN_STEP_BASE();
+            const StepBlock blk = step_block(zk, knot_mode(K, kt - 1, im), M);
             double l[15];
 #pragma unroll
             for (int i = 0; i < 15; ++i) l[i] = lam[pv.o_dyn + 15 * kk + i];
-#define JW(row, col, val) gk[col] += (val) * l[row]
-            QLN_STEP_ENTRIES();
-#undef JW
+            for_each_step_entry(blk, [&](auto row, auto col, double val) { gk[col] += val * l[row]; });
         }
-        const double dth = clearance_dtheta(zk[2], lb);
+        const double dth = clearance_dtheta(zk[2], M.lb);
         if (own) {
             if (kk >= 1) {
 #pragma unroll
@@ -534,9 +482,7 @@ __global__ __launch_bounds__(kWave, 1) void k_gauss_newton_step(BatchParams P, c
     const ProblemDesc pd = P.desc[b];
     const ProblemView pv = view_of(P, pd);
     const int N = pv.N, n = 20 * N - 5, m = 18 * N - pv.kt + 16;
-    ModelConst M;
-    M.g = P.g, M.mb = P.mb, M.mf = P.mf, M.lb = P.lb;
-    M.Ib = P.mb * (P.lb * P.lb) / 12;
+    const Model M(P);
     double* z = lds;        // [n]  decision vector
     double* x = z + n;      // [n]  CGLS solution, in scaled variables: dZ = D x
     double* p = x + n;      // [n]  search direction

@@ -5,7 +5,7 @@
 // k_tracking_lqr: the backward Riccati sweep is serial in the knots, so the parallelism is across problems and inside a
 // knot's 15x15 products.  One problem per row of sixteen lanes, four problems per wave; lane j < 15 keeps row j of
 // P_{k+1} (= column j) in registers, lane 15 shadows lane 14 and stores nothing.  A_k, B_k are the evaluator's closed
-// form (QLN_STEP_BASE / QLN_STEP_ENTRIES), formed for the knot by every lane of the row alike from the reference's
+// form (step_block / for_each_step_entry), formed for the knot by every lane of the row alike from the reference's
 // (x_k, u_k): what a lane needs at compile-time positions (every column of A for T = P A, every column of B for
 // S = P B and B'S) is in registers, what it needs at its own runtime position (column j of A for A'T, column j of Qux)
 // comes from a per-row LDS table in the compact four-entries-per-column form of the solver's sweep (ac_slot of
@@ -94,8 +94,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeig
     const int N = P.N;
     const ProblemDesc pd = P.desc[bc];
     const int kt = pd.k_trans, im = pd.init_mode;
-    const double g = P.g, mb = P.mb, mf = P.mf;
-    const double Ib = P.mb * (P.lb * P.lb) / 12;
+    const Model M(P);
     double* __restrict__ L = lds + row * kLRow;
     const double* __restrict__ Zb = Zref + (int64_t)bc * P.z_stride;
     const int jp = tk_coupling(j), jq = jp < 0 ? 0 : jp;
@@ -132,9 +131,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeig
 #pragma unroll
             for (int i = 0; i < 19; ++i) zn[i] = Zb[20 * (k - 1) + (i < 14 ? i : i + 1)];
         }
-        const int K = k + 1;
-        const int mode = (K <= kt - 1) ? im : 3;
-        const bool jump = (K == kt - 1), f1free = (mode == 2), f2free = (mode == 1);
+        const KnotMode md = knot_mode(k + 1, kt - 1, im);
         double Ac[15][4], Bm[15][4];
 #pragma unroll
         for (int c = 0; c < 15; ++c)
@@ -142,14 +139,11 @@ __global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeig
             for (int s = 0; s < 4; ++s) Ac[c][s] = Bm[c][s] = 0.0;
         // row 14 of the jump knot: the jump map keeps the clock (its Jacobian's mask zeroes the row, quirk Q1)
         if constexpr (!kFormOnce) {
-            QLN_STEP_BASE();
-#define JW(row_, col_, val_)                                                                        \
-    {                                                                                               \
-        if constexpr ((col_) < 15) Ac[col_][tk_slot(row_, col_)] = ((row_) == 14) ? 1.0 : (val_);   \
-        else if constexpr ((col_) < 19) Bm[row_][(col_) - 15] = (val_);                             \
-    }
-            QLN_STEP_ENTRIES();
-#undef JW
+            const StepBlock blk = step_block(x, F1x, F1y, F2x, F2y, h, md, M);
+            for_each_step_entry(blk, [&](auto r, auto c, double val) {
+                if constexpr (c < 15) Ac[c][tk_slot(r, c)] = (r == 14) ? 1.0 : val;
+                else if constexpr (c < 19) Bm[r][c - 15] = val;
+            });
             // ---- 1. the knot's A table; T row j = P row j . A, S row j = P row j . B ----
             if (ln == 0) {
 #pragma unroll
@@ -160,14 +154,11 @@ __global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeig
             }
         } else {
             if (ln == 0) {
-                QLN_STEP_BASE();
-#define JW(row_, col_, val_)                                                                                 \
-    {                                                                                                        \
-        if constexpr ((col_) < 15) L[kLAC + 4 * (col_) + tk_slot(row_, col_)] = ((row_) == 14) ? 1.0 : (val_); \
-        else if constexpr ((col_) < 19) L[kLB + 4 * (row_) + (col_) - 15] = (val_);                          \
-    }
-                QLN_STEP_ENTRIES();
-#undef JW
+                const StepBlock blk = step_block(x, F1x, F1y, F2x, F2y, h, md, M);
+                for_each_step_entry(blk, [L](auto r, auto c, double val) {
+                    if constexpr (c < 15) L[kLAC + 4 * c + tk_slot(r, c)] = (r == 14) ? 1.0 : val;
+                    else if constexpr (c < 19) L[kLB + 4 * r + c - 15] = val;
+                });
             }
             wave_lds_sync();
             // ---- 1. T row j = P row j . A, S row j = P row j . B, with A and B read from the row's tables ----
@@ -312,7 +303,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout(BatchParams P, const
     if (b >= P.B) return;
     const ProblemDesc pd = P.desc[b];
     const int N = P.N, kt = pd.k_trans, im = pd.init_mode;
-    const double Ib = P.mb * (P.lb * P.lb) / 12;
+    const Model M(P);
     const double* __restrict__ Zr = Zref + (int64_t)b * P.z_stride;
     double* __restrict__ Zo = Zout + (int64_t)b * P.z_stride;
     const double* __restrict__ xs = x0 ? x0 + (int64_t)b * 15 : P.bnd + (int64_t)b * 30;
@@ -340,7 +331,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout(BatchParams P, const
         }
 #pragma unroll
         for (int i = 0; i < 5; ++i) Zo[20 * k + 15 + i] = u[i];
-        step_forward(P, k, kt, im, Ib, x, u, xn);
+        step_forward(M, k, kt, im, x, u, xn);
 #pragma unroll
         for (int i = 0; i < 15; ++i) {
             x[i] = xn[i];
@@ -449,10 +440,9 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, c
     for (int k = N - 2; k >= 0; --k) {
         cur = nxt;
         if (k > 0) vjp_load<kHasK>(nxt, Zo, Zb, Zr, Kb + (kHasK ? (int64_t)(k - 1) * 60 : 0), k - 1, j);
-        const int K1 = k + 1;
-        const int mode = (K1 <= kt - 1) ? im : 3;
-        const double m1 = (mode == 2) ? 1.0 : 0.0, m2 = (mode == 1) ? 1.0 : 0.0;
-        const double keep = (K1 == kt - 1) ? 0.0 : 1.0;
+        const KnotMode md = knot_mode(k + 1, kt - 1, im);
+        const double m1 = md.f1free ? 1.0 : 0.0, m2 = md.f2free ? 1.0 : 0.0;
+        const double keep = md.jump ? 0.0 : 1.0;
         const double F0 = cur.u[0], F1 = cur.u[1], F2 = cur.u[2], F3 = cur.u[3], h = cur.u[4];
         const double h2 = h * h;
         const double Aw = h * iIb, At = 0.5 * h2 * iIb, Bt = h2 * h * iIb * (1.0 / 6.0), Ct = h2 * h2 * iIb * (1.0 / 24.0);
