@@ -63,22 +63,10 @@ constexpr bool kReturnVirtualRange = false;
 constexpr uint64_t kVaCapBytes = (uint64_t)64 << 40;  // 64 TiB: half the address space stays for everything else
 std::atomic<uint64_t> g_va_retired{0};
 
-// sizes of src/nlp.jl:48-87
-int32_t m_nlp_of(int32_t N, int32_t kt) { return 18 * N - kt + 16; }
-int32_t nnz_dyn_of(int32_t N, int32_t kt, int32_t fmt) {
-    return (fmt == QLN_JAC_FORMAT_STRUCTURAL ? qln::step_block_offset(N - 1, N, kt) : 300 * (N - 1)) + N;
-}
-int32_t nnz_of(int32_t N, int32_t kt, int32_t fmt) { return nnz_dyn_of(N, kt, fmt) + 435 + 15 * (N - 1) + 3 * N - kt + 3; }
-
-void cinds_of(int32_t N, int32_t kt, int32_t out[14]) {
-    int32_t e = 0;
-    const int32_t len[7] = {15, 14, 15 * (N - 1), N, N - kt + 1, 1, N};
-    for (int i = 0; i < 7; ++i) {
-        out[2 * i] = e + 1;
-        e += len[i];
-        out[2 * i + 1] = e;
-    }
-}
+// sizes of src/nlp.jl:48-87, from the two layouts of qln_device.h
+int32_t m_nlp_of(int32_t N, int32_t kt) { return qln::row_layout(N, kt).m; }
+int32_t nnz_dyn_of(int32_t N, int32_t kt, int32_t fmt) { return qln::vals_layout(N, kt, fmt).o_const; }
+int32_t nnz_of(int32_t N, int32_t kt, int32_t fmt) { return qln::vals_layout(N, kt, fmt).nnz; }
 
 int64_t tracking_k_total(const qln_dims& D) { return (int64_t)D.B * (D.N - 1) * QLN_TRACK_NU * QLN_NX; }
 int64_t tracking_p_total(const qln_dims& D) { return (int64_t)D.B * D.N * QLN_TRACK_P_NNZ; }
@@ -495,7 +483,13 @@ int qln_problem_nnz_dynamic(const qln_handle* h, int32_t b, int32_t* nnz_dynamic
 int qln_constraint_index_ranges(const qln_handle* h, int32_t b, int32_t cinds[14]) {
     if (int rc = check_problem(h, b)) return rc;
     if (!cinds) return fail(QLN_ERR_INVALID_ARGUMENT, "null cinds");
-    cinds_of(h->dims.N, h->k_trans[b], cinds);
+    // 1-based inclusive ranges of the seven groups: a group ends where the next one starts
+    const qln::RowLayout R = qln::row_layout(h->dims.N, h->k_trans[b]);
+    const int32_t start[8] = {R.o_init, R.o_term, R.o_dyn, R.o_ci, R.o_co, R.o_fc, R.o_bp, R.m};
+    for (int i = 0; i < 7; ++i) {
+        cinds[2 * i] = start[i] + 1;
+        cinds[2 * i + 1] = start[i + 1];
+    }
     return QLN_OK;
 }
 
@@ -503,13 +497,12 @@ int qln_constraint_bounds(const qln_handle* h, int32_t b, double* lb, double* ub
     // src/nlp.jl:66-69: lb = ub = 0 except ub[c_body_pos_inds] = Inf
     if (int rc = check_problem(h, b)) return rc;
     if (!lb || !ub) return fail(QLN_ERR_INVALID_ARGUMENT, "null bounds");
-    int32_t ci[14];
-    cinds_of(h->dims.N, h->k_trans[b], ci);
-    for (int32_t i = 0; i < ci[13]; ++i) {
+    const qln::RowLayout R = qln::row_layout(h->dims.N, h->k_trans[b]);
+    for (int32_t i = 0; i < R.m; ++i) {
         lb[i] = 0.0;
         ub[i] = 0.0;
     }
-    for (int32_t i = ci[12]; i <= ci[13]; ++i) ub[i - 1] = std::numeric_limits<double>::infinity();
+    for (int32_t i = R.o_bp; i < R.m; ++i) ub[i] = std::numeric_limits<double>::infinity();
     return QLN_OK;
 }
 
@@ -517,10 +510,8 @@ int qln_jacobian_structure(const qln_handle* h, int32_t b, int32_t* rows, int32_
     if (int rc = check_problem(h, b)) return rc;
     if (!rows || !cols) return fail(QLN_ERR_INVALID_ARGUMENT, "null rows/cols");
     const int32_t N = h->dims.N, kt = h->k_trans[b], im = h->init_mode[b];
-    int32_t ci[14];
-    cinds_of(N, kt, ci);
-    const int32_t r_init = ci[0] - 1, r_term = ci[2] - 1, r_dyn = ci[4] - 1, r_ci = ci[6] - 1, r_co = ci[8] - 1,
-                  r_fc = ci[10] - 1, r_bp = ci[12] - 1;
+    const qln::RowLayout R = qln::row_layout(N, kt);
+    const qln::ValsLayout L = qln::vals_layout(N, kt, h->p.jac_format);
     const int32_t y_init = (im == 1) ? 4 : 6, y_other = (im == 1) ? 6 : 4;
     int64_t e = 0;
     auto put = [&](int32_t r, int32_t c) {
@@ -528,25 +519,39 @@ int qln_jacobian_structure(const qln_handle* h, int32_t b, int32_t* rows, int32_
         cols[e] = c;
         ++e;
     };
+    // each section must start where vals_layout, which the kernels write by, says it does; one that does not is this
+    // function's bug, and is reported instead of handed out as a structure that disagrees with the values
+    bool in_place = true;
+    auto at = [&](int32_t section_start) { in_place = in_place && e == section_start; };
     const bool structural = (h->p.jac_format == QLN_JAC_FORMAT_STRUCTURAL);
     for (int32_t k = 0; k < N - 1; ++k) {  // D[ci, [xi[k]; ui[k]]], src/constraints.jl:186-198
         const int cat = qln::step_category(k + 1, kt, im);
         for (int32_t c = 0; c < 20; ++c)
             for (int32_t r = 0; r < 15; ++r)
-                if (!structural || qln::step_entry_present(cat, r, c)) put(r_dyn + 15 * k + r, 20 * k + c);
+                if (!structural || qln::step_entry_present(cat, r, c)) put(R.o_dyn + 15 * k + r, 20 * k + c);
     }
-    for (int32_t k = 0; k < N; ++k) put(r_bp + k, 20 * k + 2);       // :269-273
-    for (int32_t c = 0; c < 15; ++c)                                  // :228
-        for (int32_t r = 0; r < 15; ++r) put(r_init + r, c);
-    for (int32_t c = 0; c < 15; ++c)                                  // :229
-        for (int32_t r = 0; r < 14; ++r) put(r_term + r, 20 * (N - 1) + c);
-    for (int32_t k = 0; k < N - 1; ++k)                               // :200 (diagonal of -I(n))
-        for (int32_t r = 0; r < 15; ++r) put(r_dyn + 15 * k + r, 20 * (k + 1) + r);
-    for (int32_t k = 0; k < N; ++k) put(r_ci + k, 20 * k + y_init);   // :235-243
-    for (int32_t K = kt; K <= N; ++K) put(r_co + (K - kt), 20 * (K - 1) + y_other);  // :246-256
-    put(r_fc, 20 * (N - 2) + 16);                                     // :259
-    put(r_fc, 20 * (N - 2) + 18);                                     // :260
-    for (int32_t k = 0; k < N; ++k) put(r_bp + k, 20 * k + 1);        // :266
+    at(L.o_clear);
+    for (int32_t k = 0; k < N; ++k) put(R.o_bp + k, 20 * k + 2);       // :269-273
+    at(L.o_init);
+    for (int32_t c = 0; c < 15; ++c)                                    // :228
+        for (int32_t r = 0; r < 15; ++r) put(R.o_init + r, c);
+    at(L.o_term);
+    for (int32_t c = 0; c < 15; ++c)                                    // :229
+        for (int32_t r = 0; r < 14; ++r) put(R.o_term + r, 20 * (N - 1) + c);
+    at(L.o_next);
+    for (int32_t k = 0; k < N - 1; ++k)                                 // :200 (diagonal of -I(n))
+        for (int32_t r = 0; r < 15; ++r) put(R.o_dyn + 15 * k + r, 20 * (k + 1) + r);
+    at(L.o_ci);
+    for (int32_t k = 0; k < N; ++k) put(R.o_ci + k, 20 * k + y_init);   // :235-243
+    at(L.o_co);
+    for (int32_t K = kt; K <= N; ++K) put(R.o_co + (K - kt), 20 * (K - 1) + y_other);  // :246-256
+    at(L.o_fc);
+    put(R.o_fc, 20 * (N - 2) + 16);                                     // :259
+    put(R.o_fc, 20 * (N - 2) + 18);                                     // :260
+    at(L.o_by);
+    for (int32_t k = 0; k < N; ++k) put(R.o_bp + k, 20 * k + 1);        // :266
+    at(L.nnz);
+    if (!in_place) return fail(QLN_ERR_INVALID_ARGUMENT, "qln_jacobian_structure: the sections written do not match vals_layout");
     return QLN_OK;
 }
 
@@ -1241,17 +1246,16 @@ int qln_eval_constraint_jacobian_dense_host(qln_handle* h, int32_t b, const doub
         dm.at.resize(nnz);
         for (int32_t e = 0; e < nnz; ++e) dm.at[e] = rows[e] + m * (int64_t)cols[e];
         // D[ci, xi[k+1]] .= -I(n) assigns the whole 15x15 block (explicit zeros off the diagonal)
-        int32_t ci[14];
-        cinds_of(N, kt, ci);
+        const int32_t o_dyn = qln::row_layout(N, kt).o_dyn;
         for (int32_t k = 0; k < N - 1; ++k)
             for (int32_t c = 0; c < 15; ++c)
                 for (int32_t r = 0; r < 15; ++r)
-                    if (r != c) dm.zeros.push_back((ci[4] - 1 + 15 * k + r) + m * (int64_t)(20 * (k + 1) + c));
+                    if (r != c) dm.zeros.push_back((o_dyn + 15 * k + r) + m * (int64_t)(20 * (k + 1) + c));
         if (h->p.jac_format == QLN_JAC_FORMAT_STRUCTURAL)
             // D[ci, [xi[k]; ui[k]]] .= J assigns the whole 15x20 block: the entries the structural format leaves out are 0
             for (int32_t k = 0; k < N - 1; ++k)
                 for (int32_t c = 0; c < 20; ++c)
-                    for (int32_t r = 0; r < 15; ++r) dm.zeros.push_back((ci[4] - 1 + 15 * k + r) + m * (int64_t)(20 * k + c));
+                    for (int32_t r = 0; r < 15; ++r) dm.zeros.push_back((o_dyn + 15 * k + r) + m * (int64_t)(20 * k + c));
     }
     for (int64_t i : dm.zeros) jac[i] = 0.0;
     for (int32_t e = 0; e < nnz; ++e) jac[dm.at[e]] = v[e];

@@ -160,6 +160,107 @@ __host__ __device__ constexpr int step_block_offset(int k, int N, int k_trans) {
     return (k <= nc) ? 71 * k : 71 * nc + 56 * nj + 57 * (k - nc - nj);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Where the rows of one problem's constraint vector c are, and where the sections of its vals segment are (the "Layouts"
+// comment of include/qln_evaluator.h is the public statement).  These two functions are the only statement of either in
+// the library: the kernels, the size and structure queries of qln_api.cpp and the launch code take every row offset,
+// every section offset and every count from them.  Both structs are returned and passed by value: one whose address is
+// taken lives in scratch memory (carve() in qln_ilqr_kernels.hip).
+// ---------------------------------------------------------------------------------------------
+
+// Rows of c, 0-based (cinds of src/nlp.jl:48-63): initial state (15), terminal state (14), dynamics (15 per step),
+// contact-init (N), contact-other (N - k_trans + 1), final control (1), clearance (N; the only inequality rows).
+struct RowLayout {
+    int o_init, o_term, o_dyn, o_ci, o_co, o_fc, o_bp, m;
+};
+__host__ __device__ __forceinline__ constexpr RowLayout row_layout(int N, int k_trans) {
+    RowLayout r{};
+    r.o_init = 0;
+    r.o_term = r.o_init + 15;
+    r.o_dyn = r.o_term + 14;
+    r.o_ci = r.o_dyn + 15 * (N - 1);
+    r.o_co = r.o_ci + N;
+    r.o_fc = r.o_co + (N - k_trans + 1);
+    r.o_bp = r.o_fc + 1;
+    r.m = r.o_bp + N;
+    return r;
+}
+
+// Sections of vals, in the write order of jac_c! (src/constraints.jl:186-274): the step blocks [0, dyn) -- 300 values per
+// step, or the patterns' values in QLN_JAC_FORMAT_STRUCTURAL --, the N clearance d/dtheta entries at o_clear (with the
+// step blocks the values that depend on Z: nnz_dynamic = o_const), then the constants from o_const on: I(15) of the
+// initial rows (225 values), the 15 x 14 block of the terminal rows (210), the diagonal -1 of -I(n) (15 per step), the
+// contact-init ones (N), the contact-other ones (N - k_trans + 1), the two final-control entries, the clearance d/dy ones (N).
+struct ValsLayout {
+    int dyn, o_clear, o_const, o_init, o_term, o_next, o_ci, o_co, o_fc, o_by, nnz;
+};
+__host__ __device__ __forceinline__ constexpr ValsLayout vals_layout(int N, int k_trans, int jac_format) {
+    ValsLayout v{};
+    v.dyn = (jac_format == QLN_JAC_FORMAT_STRUCTURAL) ? step_block_offset(N - 1, N, k_trans) : 300 * (N - 1);
+    v.o_clear = v.dyn;
+    v.o_const = v.o_clear + N;
+    // The constants, counted from o_const first and in this order of summation: hipcc simplifies this function before it
+    // inlines it, and with the sections summed one after the other from `dyn` on, the count of constants reaches the kernels
+    // in another shape than the `i < c_ci` test of jac_const_value() -- different integer code in every instantiation that
+    // writes the Jacobian (profiles/row_layout_refactor_resource_usage.txt).
+    const int c_next = 15 * 15 + 15 * 14;
+    const int c_ci = c_next + 15 * (N - 1);
+    const int n_const = c_ci + 3 * N - k_trans + 3;
+    v.o_init = v.o_const;
+    v.o_term = v.o_const + 15 * 15;
+    v.o_next = v.o_const + c_next;
+    v.o_ci = v.o_const + c_ci;
+    v.o_co = v.o_ci + N;
+    v.o_fc = v.o_co + (N - k_trans + 1);
+    v.o_by = v.o_fc + 2;
+    v.nnz = v.o_const + n_const;
+    return v;
+}
+// Value of constant i, counted from o_const: column-major I(15), the column-major 15 x 14 block of I(15)'s first 14 rows,
+// then -1 up to o_ci and +1 behind it.
+__host__ __device__ __forceinline__ constexpr double jac_const_value(const ValsLayout& L, int i) {
+    const int n_init = L.o_term - L.o_const, n_term = L.o_next - L.o_const;
+    if (i < n_init) return (i % 15 == i / 15) ? 1.0 : 0.0;
+    if (i < n_term) return ((i - n_init) % 14 == (i - n_init) / 14) ? 1.0 : 0.0;
+    if (i < L.o_ci - L.o_const) return -1.0;
+    return 1.0;
+}
+
+constexpr bool layouts_match_reference() {
+    for (int N : {2, 12, 40, 61, 80, 130})
+        for (int kt : {1, 2, N - 1, N, N + 1}) {
+            const RowLayout r = row_layout(N, kt);
+            if (r.o_init != 0 || r.o_term - r.o_init != 15 || r.o_dyn - r.o_term != 14 || r.o_ci - r.o_dyn != 15 * (N - 1) ||
+                r.o_co - r.o_ci != N || r.o_fc - r.o_co != N - kt + 1 || r.o_bp - r.o_fc != 1 || r.m - r.o_bp != N ||
+                r.m != 18 * N - kt + 16)
+                return false;
+            for (int fmt : {QLN_JAC_FORMAT_DENSE_BLOCKS, QLN_JAC_FORMAT_STRUCTURAL}) {
+                const ValsLayout v = vals_layout(N, kt, fmt);
+                const int dyn = (fmt == QLN_JAC_FORMAT_STRUCTURAL) ? step_block_offset(N - 1, N, kt) : 300 * (N - 1);
+                if (v.dyn != dyn || v.o_clear != v.dyn || v.o_const - v.o_clear != N || v.o_init != v.o_const ||
+                    v.o_term - v.o_init != 225 || v.o_next - v.o_term != 210 || v.o_ci - v.o_next != 15 * (N - 1) ||
+                    v.o_co - v.o_ci != N || v.o_fc - v.o_co != N - kt + 1 || v.o_by - v.o_fc != 2 || v.nnz - v.o_by != N ||
+                    v.nnz != dyn + 435 + 15 * (N - 1) + 4 * N - kt + 3)
+                    return false;
+                // first and last constant of each kind: the two identity blocks (column-major), the -1 of -I(n), the ones
+                const int c_ci = v.o_ci - v.o_const, n_const = v.nnz - v.o_const;
+                if (jac_const_value(v, 0) != 1.0 || jac_const_value(v, 1) != 0.0 || jac_const_value(v, 224) != 1.0 ||
+                    jac_const_value(v, 225) != 1.0 || jac_const_value(v, 226) != 0.0 || jac_const_value(v, 225 + 13 * 14 + 13) != 1.0 ||
+                    jac_const_value(v, 434) != 0.0 || jac_const_value(v, 435) != -1.0 || jac_const_value(v, c_ci - 1) != -1.0 ||
+                    jac_const_value(v, c_ci) != 1.0 || jac_const_value(v, n_const - 1) != 1.0)
+                    return false;
+            }
+        }
+    return true;
+}
+static_assert(layouts_match_reference(), "group lengths of cinds (src/nlp.jl:48-63) and section lengths of jac_c!'s write order");
+constexpr bool notebook_ranges_match() {  // N = 61, k_trans = 21: the 1-based ranges of the notebook's problem (src/main.ipynb)
+    const RowLayout r = row_layout(61, 21);
+    return r.o_init == 0 && r.o_term == 15 && r.o_dyn == 29 && r.o_ci == 929 && r.o_co == 990 && r.o_fc == 1031 && r.o_bp == 1032 &&
+           r.m == 1093;
+}
+static_assert(notebook_ranges_match(), "(1,15) (16,29) (30,929) (930,990) (991,1031) (1032,1032) (1033,1093)");
+
 // internal launch flag (bit 0 is QLN_JAC_WRITE_CONSTANTS): prefer latency over throughput for a small batch
 constexpr uint32_t kLaunchSplit = 2u;
 // L2 prefetch for a later workgroup of the XCD (k_constraint_jacobian): distance in problems in bits 8..28 of the flags (0 = off),

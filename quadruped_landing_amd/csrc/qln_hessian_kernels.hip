@@ -77,7 +77,7 @@ __global__ __launch_bounds__(kWave) void k_hessian_lagrangian(BatchParams P, con
         const double* __restrict__ Zb = Z + (int64_t)b * P.z_stride;
         const double* __restrict__ Mb = MU + pd.c_off;
         const double* __restrict__ Cb = P.cost + (P.cost_batch == 1 ? 0 : (int64_t)b * N * kCostRec);
-        const int o_bp = 29 + 15 * (N - 1) + N + (N - kt + 1) + 1;  // clearance rows (cinds, src/nlp.jl:48-63)
+        const RowLayout R = row_layout(N, kt);
         const double sig = S ? S[b] : 1.0;
         double* __restrict__ Hb = H + (int64_t)b * h_stride;
 
@@ -92,9 +92,9 @@ __global__ __launch_bounds__(kWave) void k_hessian_lagrangian(BatchParams P, con
 #pragma unroll
                 for (int it = 0; it < kZIters; ++it) zr[it] = Zb[20 * kc0 + min(it * kWave + lane, nz - 1)];
 #pragma unroll
-                for (int it = 0; it < kMuIters; ++it) mr[it] = Mb[29 + 15 * kc0 + min(it * kWave + lane, nm - 1)];
-                mu_c = Mb[o_bp + kc0 + min(lane, nk - 1)];
-                mu_cn = Mb[o_bp + N - 1];
+                for (int it = 0; it < kMuIters; ++it) mr[it] = Mb[R.o_dyn + 15 * kc0 + min(it * kWave + lane, nm - 1)];
+                mu_c = Mb[R.o_bp + kc0 + min(lane, nk - 1)];
+                mu_cn = Mb[R.o_bp + N - 1];
                 th_n = Zb[20 * (N - 1) + 2];
                 qf = Cb[kCostRec * (N - 1) + min(lane, 14)];
                 if constexpr (!REC_REGS) {
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(kWave) void k_hessian_lagrangian_product(BatchParam
         const double* __restrict__ Vb = V + (int64_t)b * P.z_stride;
         const double* __restrict__ Mb = MU + pd.c_off;
         const double* __restrict__ Cb = P.cost + (P.cost_batch == 1 ? 0 : (int64_t)b * N * kCostRec);
-        const int o_bp = 29 + 15 * (N - 1) + N + (N - kt + 1) + 1;  // clearance rows (cinds, src/nlp.jl:48-63)
+        const RowLayout R = row_layout(N, kt);
         const double sig = S ? S[b] : 1.0;
         double* __restrict__ Yb = Y + (int64_t)b * P.z_stride;
 
@@ -237,9 +237,9 @@ __global__ __launch_bounds__(kWave) void k_hessian_lagrangian_product(BatchParam
 #pragma unroll
                 for (int it = 0; it < kZIters; ++it) vr[it] = Vb[20 * kc0 + min(it * kWave + lane, nz - 1)];
 #pragma unroll
-                for (int it = 0; it < kMuIters; ++it) mr[it] = Mb[29 + 15 * kc0 + min(it * kWave + lane, nm - 1)];
-                mu_c = Mb[o_bp + kc0 + min(lane, nk - 1)];
-                mu_cn = Mb[o_bp + N - 1];
+                for (int it = 0; it < kMuIters; ++it) mr[it] = Mb[R.o_dyn + 15 * kc0 + min(it * kWave + lane, nm - 1)];
+                mu_c = Mb[R.o_bp + kc0 + min(lane, nk - 1)];
+                mu_cn = Mb[R.o_bp + N - 1];
                 th_n = Zb[20 * (N - 1) + 2];
                 qf = Cb[kCostRec * (N - 1) + min(lane, 14)];
                 v_n = Vb[20 * (N - 1) + min(lane, 14)];

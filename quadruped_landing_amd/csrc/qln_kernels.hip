@@ -358,18 +358,13 @@ __global__ __launch_bounds__(kWave, W) void k_constraint_jacobian(BatchParams P,
     const double lb = M.lb;
 
     // offsets of the constraint groups inside c (0-based; cinds of src/nlp.jl:48-63)
-    const int o_dyn = 29;
-    const int o_ci = o_dyn + 15 * (N - 1);
-    const int o_co = o_ci + N;
-    const int o_fc = o_co + (N - kt + 1);
-    const int o_bp = o_fc + 1;
+    const RowLayout R = row_layout(N, kt);
     const bool init1 = (im == 1);  // foot 1 touches first: contact-init row is y1, contact-other is y2
     // every row of c goes through here.  (Measured and not adopted, profiles/r03_structural_floor.txt: the whole constraint
     // vector assembled in LDS behind the slice and written as ONE aligned 16-byte-per-lane stream instead of these short
     // 8-byte-per-lane stores -- no difference in the structural format's fused launch, 0.36 ms either way.)
     auto c_put = [&](int idx, double v) { Cb[idx] = v; };
-    // length of the step-block section of vals
-    const int dyn_blocks = NNZ ? step_block_offset(N - 1, N, kt) : kBlk * (N - 1);
+    const ValsLayout L = vals_layout(N, kt, NNZ ? QLN_JAC_FORMAT_STRUCTURAL : QLN_JAC_FORMAT_DENSE_BLOCKS);
     double J_obj = 0.0;  // WITH_F: eval_f accumulated over the chunks, in knot order
     // L2 prefetch for a LATER workgroup of this XCD (flags >> 8 = how many problems ahead on the XCD; 0 = off): one 4-byte load
     // per 64 bytes of that problem's slice, issued once this wave's own slice has arrived (loads return in order: a wait
@@ -406,22 +401,12 @@ __global__ __launch_bounds__(kWave, W) void k_constraint_jacobian(BatchParams P,
 
     if (WITH_J && (flags & 1u) && kc_begin == 0) {
         // constant entries of jac_c! (src/constraints.jl:228-229, :200, :235-265)
-        double* Vc = Vb + dyn_blocks + N;
-        const int n_const = 435 + 15 * (N - 1) + 3 * N - kt + 3;
-        for (int i = lane; i < n_const; i += kWave) {
-            double v;
-            if (i < 225) {
-                v = (i % 15 == i / 15) ? 1.0 : 0.0;
-            } else if (i < 435) {
-                const int j = i - 225;
-                v = (j % 14 == j / 14) ? 1.0 : 0.0;
-            } else if (i < 435 + 15 * (N - 1)) {
-                v = -1.0;
-            } else {
-                v = 1.0;
-            }
-            Vc[i] = v;
-        }
+        // o_const, reached in two steps as `Vb + dyn_blocks + N` always was: from `Vb + L.o_const` the compiler extends one 32-bit
+        // sum, one 64-bit add fewer and other register tables in all 24 instantiations that write the Jacobian
+        // (profiles/row_layout_refactor_resource_usage.txt)
+        double* Vc = Vb + L.o_clear + (L.o_const - L.o_clear);
+        const int n_const = L.nnz - L.o_const;
+        for (int i = lane; i < n_const; i += kWave) Vc[i] = jac_const_value(L, i);
     }
 
     // eval_f (src/costs.jl:6-16) of one chunk: lane = knot, the terminal knot x_N rides on lane nk of the last chunk (a second
@@ -474,7 +459,7 @@ __global__ __launch_bounds__(kWave, W) void k_constraint_jacobian(BatchParams P,
                 if (first_chunk && lane < 15) c_put(lane, s_z[lane] - bnd);
                 if (last_chunk) {
                     if (lane >= 15 && lane < 29) c_put(lane, s_z[20 * nk + (lane - 15)] - bnd);
-                    if (lane == 29) c_put(o_fc, s_z[20 * (nk - 1) + 16] + s_z[20 * (nk - 1) + 18] + M.mb * M.g);
+                    if (lane == 29) c_put(R.o_fc, s_z[20 * (nk - 1) + 16] + s_z[20 * (nk - 1) + 18] + M.mb * M.g);
                 }
             }
             if (kc0 == kc_begin) prefetch_later_workgroup();  // the wave's own first slice (and bnd) have arrived
@@ -513,11 +498,11 @@ __global__ __launch_bounds__(kWave, W) void k_constraint_jacobian(BatchParams P,
             }
             // per-knot scalar rows: contact (src/constraints.jl:48-91) and clearance (:98-113)
             if (valid) {
-                c_put(o_ci + k, init1 ? x[4] : x[6]);
-                if (K >= kt) c_put(o_co + (K - kt), init1 ? x[6] : x[4]);
+                c_put(R.o_ci + k, init1 ? x[4] : x[6]);
+                if (K >= kt) c_put(R.o_co + (K - kt), init1 ? x[6] : x[4]);
                 if (k == N - 2) {  // this lane also holds the terminal knot x_N
-                    c_put(o_ci + k + 1, init1 ? xnext[4] : xnext[6]);
-                    if (K + 1 >= kt) c_put(o_co + (K + 1 - kt), init1 ? xnext[6] : xnext[4]);
+                    c_put(R.o_ci + k + 1, init1 ? xnext[4] : xnext[6]);
+                    if (K + 1 >= kt) c_put(R.o_co + (K + 1 - kt), init1 ? xnext[6] : xnext[4]);
                 }
                 // dynamics residuals: 15 per knot, knot-major and contiguous in c
                 // (src/constraints.jl:14-18); transposed through LDS so the store is coalesced
@@ -534,19 +519,19 @@ __global__ __launch_bounds__(kWave, W) void k_constraint_jacobian(BatchParams P,
                 else if constexpr (WITH_J) sincos(zk[2], &sth, &cos_th);  // the Jacobian phase needs cos(theta_k) (one call)
                 else sth = sin(zk[2]);
                 const double cl = zk[1] - lb / 2 * fabs(sth);
-                if (own) c_put(o_bp + kc0 + lane, cl);
+                if (own) c_put(R.o_bp + kc0 + lane, cl);
                 if (last_chunk && nk == kWave) {  // wave-uniform: a full last chunk has no lane left for x_N
                     const double* zn = s_z + 20 * nk;
                     double stn;
                     if constexpr (WITH_J) sincos(zn[2], &stn, &cos_tn);
                     else stn = sin(zn[2]);
                     const double cn = zn[1] - lb / 2 * fabs(stn);
-                    if (lane == 0) c_put(o_bp + kc0 + nk, cn);
+                    if (lane == 0) c_put(R.o_bp + kc0 + nk, cn);
                 }
             }
             wave_lds_sync();
             {
-                double* __restrict__ dst = Cb + o_dyn + 15 * kc0;
+                double* __restrict__ dst = Cb + R.o_dyn + 15 * kc0;
                 const int np = nk * 15;
                 constexpr int kCIters = (KC * 15 + kWave - 1) / kWave;
                 double cr[kCIters];
@@ -604,11 +589,11 @@ __global__ __launch_bounds__(kWave, W) void k_constraint_jacobian(BatchParams P,
                 const bool own = valid || (last_chunk && lane == nk);
                 const double th = s_z[20 * (own ? lane : 0) + 2];
                 const double cth = WITH_C ? cos_th : cos(th);
-                if (own) Vb[dyn_blocks + kc0 + lane] = (th > 0) ? (-lb / 2 * cth) : (lb / 2 * cth);
+                if (own) Vb[L.o_clear + kc0 + lane] = (th > 0) ? (-lb / 2 * cth) : (lb / 2 * cth);
                 if (last_chunk && nk == kWave) {  // wave-uniform: a full last chunk has no lane left for x_N
                     const double tn = s_z[20 * nk + 2];
                     const double ctn = WITH_C ? cos_tn : cos(tn);
-                    if (lane == 0) Vb[dyn_blocks + kc0 + nk] = (tn > 0) ? (-lb / 2 * ctn) : (lb / 2 * ctn);
+                    if (lane == 0) Vb[L.o_clear + kc0 + nk] = (tn > 0) ? (-lb / 2 * ctn) : (lb / 2 * ctn);
                 }
             }
             wave_lds_sync();
@@ -739,23 +724,10 @@ __global__ __launch_bounds__(kWave) void k_jacobian_constants(BatchParams P, dou
     if (b >= P.B) return;
     const int N = P.N;
     const int kt = P.desc[b].k_trans;
-    const int dyn_blocks = (P.jac_format == QLN_JAC_FORMAT_STRUCTURAL) ? step_block_offset(N - 1, N, kt) : kBlk * (N - 1);
-    double* Vc = V + P.desc[b].j_off + dyn_blocks + N;
-    const int n_const = 435 + 15 * (N - 1) + 3 * N - kt + 3;
-    for (int i = lane; i < n_const; i += kWave) {
-        double v;
-        if (i < 225) {
-            v = (i % 15 == i / 15) ? 1.0 : 0.0;
-        } else if (i < 435) {
-            const int j = i - 225;
-            v = (j % 14 == j / 14) ? 1.0 : 0.0;
-        } else if (i < 435 + 15 * (N - 1)) {
-            v = -1.0;
-        } else {
-            v = 1.0;
-        }
-        Vc[i] = v;
-    }
+    const ValsLayout L = vals_layout(N, kt, P.jac_format);
+    double* Vc = V + P.desc[b].j_off + L.o_clear + (L.o_const - L.o_clear);
+    const int n_const = L.nnz - L.o_const;
+    for (int i = lane; i < n_const; i += kWave) Vc[i] = jac_const_value(L, i);
 }
 
 // Objective (src/costs.jl:6-16): objective_term / add_terms_in_order are defined above the fused kernel, which uses them too.
@@ -1040,8 +1012,8 @@ __global__ __launch_bounds__(kWave) void k_constraint_violation(BatchParams P, c
     if (b >= P.B) return;
     const ProblemDesc pd = P.desc[b];
     const int N = P.N;
-    const int m = 18 * N - pd.k_trans + 16;
-    const int m_eq = m - N;
+    const RowLayout R = row_layout(N, pd.k_trans);
+    const int m = R.m, m_eq = R.o_bp;  // the clearance rows, the only inequalities, are the last group
     const double* __restrict__ cb = C + pd.c_off;
     double v = 0.0;
     bool bad = false;
@@ -1170,7 +1142,7 @@ inline size_t nnz_lds_bytes(const BatchParams& p, int KC, int sub, bool with_f) 
             // x of the run's knots lie before the transition knot at the batch's largest k_trans (71 values each), and no
             // problem of the batch has more of them; every other knot has at most 57: 57 nkt + 14 x bounds every problem's run
             const int x = std::min(nkt, std::max(0, std::min(kt - 2, N - 1) - (kc0 + t0)));
-            longest = std::max(longest, 57 * nkt + 14 * x);
+            longest = std::max(longest, step_nnz(2) * nkt + (step_nnz(0) - step_nnz(2)) * x);
         }
     }
     const int z_slice = KC * 20 + 15, c_stage = (z_slice + 1) & ~1;
@@ -1225,7 +1197,7 @@ hipError_t launch_cj_t(const BatchParams& p, int32_t b_begin, int32_t nb, const 
 #endif
     if (!SPLIT) flags = (flags & 0xffu) | prefetch_flags(prefetch_ahead);
     // outputs larger than the caches are streamed (non-temporal stores); small ones stay cacheable
-    const bool stream_out = (int64_t)nb * (p.N - 1) * (NNZ ? 71 : kBlk) * 8 > ((int64_t)512 << 20);
+    const bool stream_out = (int64_t)nb * (p.N - 1) * (NNZ ? step_nnz(0) : kBlk) * 8 > ((int64_t)512 << 20);
     auto go = [&](auto with_c, auto with_j, auto streamed) {
         constexpr bool WC = decltype(with_c)::value, WJ = decltype(with_j)::value, ST = decltype(streamed)::value;
         const unsigned lds = (NNZ ? (unsigned)nnz_lds_bytes(p, KC, T > 0 ? T : KC, false) : 0u) + ((WC && WJ) ? pad : 0u);
@@ -1244,7 +1216,7 @@ hipError_t launch_cj_t(const BatchParams& p, int32_t b_begin, int32_t nb, const 
 template <int T, int KC, int W>
 hipError_t launch_c_only_t(const BatchParams& p, int32_t b_begin, int32_t nb, const double* Z, double* c, hipStream_t stream) {
     dim3 grid(xcd_grid(nb)), block(kWave);
-    const bool stream_out = (int64_t)nb * (18 * p.N + 16) * 8 > ((int64_t)512 << 20);
+    const bool stream_out = (int64_t)nb * row_layout(p.N, 0).m * 8 > ((int64_t)512 << 20);  // k_trans = 0: more rows than any problem has
     if (stream_out) hipLaunchKernelGGL((k_constraint_jacobian<T, KC, W, true, false, false, false, true>), grid, block, 0, stream, p, b_begin, nb, Z, c, nullptr, prefetch_flags(0));
     else hipLaunchKernelGGL((k_constraint_jacobian<T, KC, W, true, false, false, false, false>), grid, block, 0, stream, p, b_begin, nb, Z, c, nullptr, prefetch_flags(0));
     return hipGetLastError();
@@ -1361,7 +1333,7 @@ hipError_t launch_eval_all(const BatchParams& p, const double* Z, double* f, dou
     const int nb = p.B;
     dim3 grid(xcd_grid(nb)), block(kWave);
     const bool structural = p.jac_format == QLN_JAC_FORMAT_STRUCTURAL;
-    const bool stream_out = (int64_t)nb * (p.N - 1) * (structural ? 71 : kBlk) * 8 > ((int64_t)512 << 20);
+    const bool stream_out = (int64_t)nb * (p.N - 1) * (structural ? step_nnz(0) : kBlk) * 8 > ((int64_t)512 << 20);
     // dense one-chunk problems prefetch like the fused launch, and the later problem's boundary vectors and descriptor with the
     // slice: 1.18-1.20 -> 1.11-1.15 ms at config 3 (the slice alone: 1.16-1.19; for the fused launch WITHOUT the objective the two
     // extras cost what the slice gains -- profiles/r03_prefetch_ahead.txt)
@@ -1383,7 +1355,7 @@ hipError_t launch_eval_all(const BatchParams& p, const double* Z, double* f, dou
 hipError_t launch_objective_and_constraint(const BatchParams& p, const double* Z, double* f, double* c, hipStream_t stream) {
     const int nb = p.B;
     dim3 grid(xcd_grid(nb)), block(kWave);
-    const bool stream_out = (int64_t)nb * (18 * p.N + 16) * 8 > ((int64_t)512 << 20);
+    const bool stream_out = (int64_t)nb * row_layout(p.N, 0).m * 8 > ((int64_t)512 << 20);  // k_trans = 0: more rows than any problem has
     const int knots = p.N - 1;
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, stream, p, 0, nb, Z, c, nullptr, 0u, f, nullptr); };
     if ((knots + 39) / 40 == (knots + 63) / 64) {  // chunk size as for the constraint-only launch

@@ -28,7 +28,7 @@ constexpr int kPZ = 20 * kPC + 15;        // doubles of Z (or of a vector in Z's
 
 struct ProblemView {
     int N, kt, im;
-    int o_dyn, o_ci, o_co, o_fc, o_bp;    // 0-based offsets of the constraint groups (cinds, src/nlp.jl:48-63)
+    RowLayout R;  // rows of c
     bool init1;
 };
 
@@ -37,11 +37,7 @@ __device__ __forceinline__ ProblemView view_of(const BatchParams& P, const Probl
     v.N = P.N;
     v.kt = pd.k_trans;
     v.im = pd.init_mode;
-    v.o_dyn = 29;
-    v.o_ci = v.o_dyn + 15 * (P.N - 1);
-    v.o_co = v.o_ci + P.N;
-    v.o_fc = v.o_co + (P.N - v.kt + 1);
-    v.o_bp = v.o_fc + 1;
+    v.R = row_layout(P.N, v.kt);
     v.init1 = (v.im == 1);
     return v;
 }
@@ -105,7 +101,7 @@ __global__ __launch_bounds__(kWave) void k_constraint_jvp(BatchParams P, const d
         if (first_chunk && lane < 15) Yb[lane] = s_v[lane];
         if (last_chunk) {
             if (lane >= 15 && lane < 29) Yb[lane] = s_v[20 * nk + (lane - 15)];
-            if (lane == 29) Yb[pv.o_fc] = s_v[20 * (nk - 1) + 16] + s_v[20 * (nk - 1) + 18];
+            if (lane == 29) Yb[pv.R.o_fc] = s_v[20 * (nk - 1) + 16] + s_v[20 * (nk - 1) + 18];
         }
         const bool valid = lane < nk;
         const bool own = valid || (last_chunk && lane == nk);  // lane nk of the last chunk holds x_N
@@ -116,9 +112,9 @@ __global__ __launch_bounds__(kWave) void k_constraint_jvp(BatchParams P, const d
             // contact rows (:235-256) and clearance rows (:263-274), one per knot
             const double dth = clearance_dtheta(zk[2], M.lb);
             if (own) {
-                Yb[pv.o_ci + kk] = pv.init1 ? vk[4] : vk[6];
-                if (K >= kt) Yb[pv.o_co + (K - kt)] = pv.init1 ? vk[6] : vk[4];
-                Yb[pv.o_bp + kk] = vk[1] + dth * vk[2];
+                Yb[pv.R.o_ci + kk] = pv.init1 ? vk[4] : vk[6];
+                if (K >= kt) Yb[pv.R.o_co + (K - kt)] = pv.init1 ? vk[6] : vk[4];
+                Yb[pv.R.o_bp + kk] = vk[1] + dth * vk[2];
             }
         }
         if (valid) {
@@ -139,7 +135,7 @@ __global__ __launch_bounds__(kWave) void k_constraint_jvp(BatchParams P, const d
             wave_lds_sync();
         }
         wave_lds_sync();
-        for (int i = lane; i < 15 * nk; i += kWave) Yb[pv.o_dyn + 15 * kc0 + i] = s_y[i];
+        for (int i = lane; i < 15 * nk; i += kWave) Yb[pv.R.o_dyn + 15 * kc0 + i] = s_y[i];
     }
 }
 
@@ -180,17 +176,17 @@ __global__ __launch_bounds__(kWave) void k_constraint_vjp(BatchParams P, const d
             for (int it = 0; it < kLamIters; ++it) {
                 const int i = min(it * kWave + lane, nl - 1);
                 const int j = 15 * (kc0 - 1) + i;  // index into the dynamics rows; knot -1 has no multipliers
-                lr[it] = Lb[pv.o_dyn + max(j, 0)];
+                lr[it] = Lb[pv.R.o_dyn + max(j, 0)];
                 if (j < 0) lr[it] = 0.0;
             }
             // Every multiplier a lane adds behind the products -- contact, final-control and clearance rows of its knot, the
             // initial-state / terminal rows -- is requested HERE, with the slices, unconditionally (clamped indices): requested
             // where it is used, inside the lane's branches, each was a memory round trip of its own at the end of the wave's life.
             const int kq = min(kc0 + lane, N - 1);
-            l_ci = Lb[pv.o_ci + kq];
-            l_co = Lb[pv.o_co + min(max(kq + 1 - kt, 0), N - kt)];
-            l_bp = Lb[pv.o_bp + kq];
-            l_fc = Lb[pv.o_fc];
+            l_ci = Lb[pv.R.o_ci + kq];
+            l_co = Lb[pv.R.o_co + min(max(kq + 1 - kt, 0), N - kt)];
+            l_bp = Lb[pv.R.o_bp + kq];
+            l_fc = Lb[pv.R.o_fc];
             const double l_b = Lb[min(lane, 28)];
             wave_lds_sync();  // the previous chunk's readers are done
             stage_store(s_z, zr, lane);
@@ -300,16 +296,16 @@ __device__ __forceinline__ void lds_jvp_cached(const ProblemView& pv, const Knot
     if (lane < 15) y[lane] = dsc[lane] * v[lane];
     if (lane >= 15 && lane < 29) y[lane] = dsc[20 * (N - 1) + (lane - 15)] * v[20 * (N - 1) + (lane - 15)];
     if (lane == 29)
-        y[pv.o_fc] = dsc[20 * (N - 2) + 16] * v[20 * (N - 2) + 16] + dsc[20 * (N - 2) + 18] * v[20 * (N - 2) + 18];
+        y[pv.R.o_fc] = dsc[20 * (N - 2) + 16] * v[20 * (N - 2) + 16] + dsc[20 * (N - 2) + 18] * v[20 * (N - 2) + 18];
     const int kk = lane, K = kk + 1;
     const bool own = kk < N, valid = kk < N - 1;
     const double* vk = v + 20 * (own ? kk : 0);
     const double* dk = dsc + 20 * (own ? kk : 0);
     if (own) {
         const double v4 = dk[4] * vk[4], v6 = dk[6] * vk[6];
-        y[pv.o_ci + kk] = pv.init1 ? v4 : v6;
-        if (K >= kt) y[pv.o_co + (K - kt)] = pv.init1 ? v6 : v4;
-        y[pv.o_bp + kk] = mask[kk] * (dk[1] * vk[1] + J.dth * (dk[2] * vk[2]));
+        y[pv.R.o_ci + kk] = pv.init1 ? v4 : v6;
+        if (K >= kt) y[pv.R.o_co + (K - kt)] = pv.init1 ? v6 : v4;
+        y[pv.R.o_bp + kk] = mask[kk] * (dk[1] * vk[1] + J.dth * (dk[2] * vk[2]));
     }
     if (valid) {
         double vin[20], acc[15];
@@ -322,7 +318,7 @@ __device__ __forceinline__ void lds_jvp_cached(const ProblemView& pv, const Knot
             acc[row] += J.e[pos_] * vin[col];
         });
 #pragma unroll
-        for (int i = 0; i < 15; ++i) y[pv.o_dyn + 15 * kk + i] = acc[i] - dk[20 + i] * vk[20 + i];
+        for (int i = 0; i < 15; ++i) y[pv.R.o_dyn + 15 * kk + i] = acc[i] - dk[20 + i] * vk[20 + i];
     }
 }
 
@@ -338,7 +334,7 @@ __device__ __forceinline__ void lds_vjp_cached(const ProblemView& pv, const Knot
     if (valid) {
         double l[15];
 #pragma unroll
-        for (int i = 0; i < 15; ++i) l[i] = lam[pv.o_dyn + 15 * kk + i];
+        for (int i = 0; i < 15; ++i) l[i] = lam[pv.R.o_dyn + 15 * kk + i];
         for_each_step_entry([&](auto row, auto col) {
             constexpr int pos_ = step_union_pos(row, col);
             gk[col] += J.e[pos_] * l[row];
@@ -347,7 +343,7 @@ __device__ __forceinline__ void lds_vjp_cached(const ProblemView& pv, const Knot
     if (own) {
         if (kk >= 1) {
 #pragma unroll
-            for (int i = 0; i < 15; ++i) gk[i] -= lam[pv.o_dyn + 15 * (kk - 1) + i];
+            for (int i = 0; i < 15; ++i) gk[i] -= lam[pv.R.o_dyn + 15 * (kk - 1) + i];
         } else {
 #pragma unroll
             for (int i = 0; i < 15; ++i) gk[i] += lam[i];
@@ -356,16 +352,16 @@ __device__ __forceinline__ void lds_vjp_cached(const ProblemView& pv, const Knot
 #pragma unroll
             for (int i = 0; i < 14; ++i) gk[i] += lam[15 + i];
         }
-        const double l_ci = lam[pv.o_ci + kk];
-        const double l_co = (K >= kt) ? lam[pv.o_co + (K - kt)] : 0.0;
+        const double l_ci = lam[pv.R.o_ci + kk];
+        const double l_co = (K >= kt) ? lam[pv.R.o_co + (K - kt)] : 0.0;
         gk[4] += pv.init1 ? l_ci : l_co;
         gk[6] += pv.init1 ? l_co : l_ci;
         if (kk == N - 2) {
-            const double l_fc = lam[pv.o_fc];
+            const double l_fc = lam[pv.R.o_fc];
             gk[16] += l_fc;
             gk[18] += l_fc;
         }
-        const double l_bp = mask[kk] * lam[pv.o_bp + kk];
+        const double l_bp = mask[kk] * lam[pv.R.o_bp + kk];
         gk[1] += l_bp;
         gk[2] += J.dth * l_bp;
 #pragma unroll
@@ -384,7 +380,7 @@ __device__ __forceinline__ void lds_jvp(const ProblemView& pv, const Model& M, c
     if (lane < 15) y[lane] = dsc[lane] * v[lane];
     if (lane >= 15 && lane < 29) y[lane] = dsc[20 * (N - 1) + (lane - 15)] * v[20 * (N - 1) + (lane - 15)];
     if (lane == 29)
-        y[pv.o_fc] = dsc[20 * (N - 2) + 16] * v[20 * (N - 2) + 16] + dsc[20 * (N - 2) + 18] * v[20 * (N - 2) + 18];
+        y[pv.R.o_fc] = dsc[20 * (N - 2) + 16] * v[20 * (N - 2) + 16] + dsc[20 * (N - 2) + 18] * v[20 * (N - 2) + 18];
     for (int k0 = 0; k0 < N; k0 += kWave) {
         const int kk = k0 + lane, K = kk + 1;
         const bool own = kk < N, valid = kk < N - 1;
@@ -394,9 +390,9 @@ __device__ __forceinline__ void lds_jvp(const ProblemView& pv, const Model& M, c
         const double dth = clearance_dtheta(zk[2], M.lb);
         if (own) {
             const double v4 = dk[4] * vk[4], v6 = dk[6] * vk[6];
-            y[pv.o_ci + kk] = pv.init1 ? v4 : v6;
-            if (K >= kt) y[pv.o_co + (K - kt)] = pv.init1 ? v6 : v4;
-            y[pv.o_bp + kk] = mask[kk] * (dk[1] * vk[1] + dth * (dk[2] * vk[2]));
+            y[pv.R.o_ci + kk] = pv.init1 ? v4 : v6;
+            if (K >= kt) y[pv.R.o_co + (K - kt)] = pv.init1 ? v6 : v4;
+            y[pv.R.o_bp + kk] = mask[kk] * (dk[1] * vk[1] + dth * (dk[2] * vk[2]));
         }
         if (valid) {
             const StepBlock blk = step_block(zk, knot_mode(K, kt - 1, im), M);
@@ -407,7 +403,7 @@ __device__ __forceinline__ void lds_jvp(const ProblemView& pv, const Model& M, c
             for (int i = 0; i < 15; ++i) acc[i] = 0.0;
             for_each_step_entry(blk, [&](auto row, auto col, double val) { acc[row] += val * vin[col]; });
 #pragma unroll
-            for (int i = 0; i < 15; ++i) y[pv.o_dyn + 15 * kk + i] = acc[i] - dk[20 + i] * vk[20 + i];
+            for (int i = 0; i < 15; ++i) y[pv.R.o_dyn + 15 * kk + i] = acc[i] - dk[20 + i] * vk[20 + i];
         }
     }
 }
@@ -428,14 +424,14 @@ __device__ __forceinline__ void lds_vjp(const ProblemView& pv, const Model& M, c
             const StepBlock blk = step_block(zk, knot_mode(K, kt - 1, im), M);
             double l[15];
 #pragma unroll
-            for (int i = 0; i < 15; ++i) l[i] = lam[pv.o_dyn + 15 * kk + i];
+            for (int i = 0; i < 15; ++i) l[i] = lam[pv.R.o_dyn + 15 * kk + i];
             for_each_step_entry(blk, [&](auto row, auto col, double val) { gk[col] += val * l[row]; });
         }
         const double dth = clearance_dtheta(zk[2], M.lb);
         if (own) {
             if (kk >= 1) {
 #pragma unroll
-                for (int i = 0; i < 15; ++i) gk[i] -= lam[pv.o_dyn + 15 * (kk - 1) + i];
+                for (int i = 0; i < 15; ++i) gk[i] -= lam[pv.R.o_dyn + 15 * (kk - 1) + i];
             } else {
 #pragma unroll
                 for (int i = 0; i < 15; ++i) gk[i] += lam[i];
@@ -444,16 +440,16 @@ __device__ __forceinline__ void lds_vjp(const ProblemView& pv, const Model& M, c
 #pragma unroll
                 for (int i = 0; i < 14; ++i) gk[i] += lam[15 + i];
             }
-            const double l_ci = lam[pv.o_ci + kk];
-            const double l_co = (K >= kt) ? lam[pv.o_co + (K - kt)] : 0.0;
+            const double l_ci = lam[pv.R.o_ci + kk];
+            const double l_co = (K >= kt) ? lam[pv.R.o_co + (K - kt)] : 0.0;
             gk[4] += pv.init1 ? l_ci : l_co;
             gk[6] += pv.init1 ? l_co : l_ci;
             if (kk == N - 2) {
-                const double l_fc = lam[pv.o_fc];
+                const double l_fc = lam[pv.R.o_fc];
                 gk[16] += l_fc;
                 gk[18] += l_fc;
             }
-            const double l_bp = mask[kk] * lam[pv.o_bp + kk];
+            const double l_bp = mask[kk] * lam[pv.R.o_bp + kk];
             gk[1] += l_bp;
             gk[2] += dth * l_bp;
 #pragma unroll
@@ -481,7 +477,7 @@ __global__ __launch_bounds__(kWave, 1) void k_gauss_newton_step(BatchParams P, c
     if (b >= P.B) return;  // wave-uniform
     const ProblemDesc pd = P.desc[b];
     const ProblemView pv = view_of(P, pd);
-    const int N = pv.N, n = 20 * N - 5, m = 18 * N - pv.kt + 16;
+    const int N = pv.N, n = 20 * N - 5, m = pv.R.m;
     const Model M(P);
     double* z = lds;        // [n]  decision vector
     double* x = z + n;      // [n]  CGLS solution, in scaled variables: dZ = D x
@@ -523,11 +519,11 @@ __global__ __launch_bounds__(kWave, 1) void k_gauss_newton_step(BatchParams P, c
             const int i = i0 + u * kWave + lane;
             if (i < m) {
                 const double ci = ct[u];
-                const bool ineq = i >= pv.o_bp;
+                const bool ineq = i >= pv.R.o_bp;
                 const double rho = (ineq && !(ci < 0)) ? 0.0 : ci;  // a NaN in c propagates
                 r[i] = -rho;
                 phi0 += rho * rho;
-                if (ineq) mask[i - pv.o_bp] = (ci < 0 || ci != ci) ? 1.0 : 0.0;
+                if (ineq) mask[i - pv.R.o_bp] = (ci < 0 || ci != ci) ? 1.0 : 0.0;
             }
         }
     }
@@ -634,7 +630,7 @@ hipError_t launch_constraint_vjp(const BatchParams& p, const double* Z, const do
 }
 
 // LDS bytes one problem of the Gauss-Newton step needs (largest m_nlp is at k_trans = 1)
-size_t gauss_newton_lds_bytes(int32_t N) { return sizeof(double) * (size_t)(5 * (20 * N - 5) + 2 * (18 * N + 15) + N); }
+size_t gauss_newton_lds_bytes(int32_t N) { return sizeof(double) * (size_t)(5 * (20 * N - 5) + 2 * row_layout(N, 1).m + N); }
 
 hipError_t launch_gauss_newton_step(const BatchParams& p, const double* Z, const double* c, double* dZ, int max_iters,
                                     double rel_tol, const double* radius, const double* col_scale, double* info,

@@ -20,6 +20,43 @@ def test_index_maps_match_oracle(N, kt):
     assert np.array_equal(lb, lo) and np.array_equal(ub, uo)
 
 
+@pytest.mark.parametrize("init_mode", [1, 2])
+@pytest.mark.parametrize("jac_format", ["dense_blocks", "structural"])
+@pytest.mark.parametrize("N,kt", [(61, 21), (40, 14), (2, 2), (80, 79), (80, 2), (12, 13), (12, 1)])
+def test_library_layout_sizes_match_oracle(N, kt, jac_format, init_mode):
+    """qln_layout is device-free: the sizes it derives from the library's row and vals layouts (row_layout / vals_layout of
+    csrc/qln_device.h) for one problem are the oracle's -- m_nlp; in dense blocks nnz and 300 (N-1) + N; in the structural
+    format the non-zero step-block values of jac_c_coo at a generic point plus N, and that plus the oracle's constant tail."""
+    import ctypes as C
+
+    from quadruped_landing_amd import _lib
+
+    rng = np.random.default_rng(7)
+    o = O.OracleNLP(N, kt, init_mode, rng.normal(size=15), rng.normal(size=15), np.zeros((N, 41)))
+    Z = rng.normal(size=o.n_nlp)
+    Z[19::20] = 0.01
+    dense_dyn = 300 * (N - 1)
+    tail = o.nnz - dense_dyn - N
+    if jac_format == "dense_blocks":
+        fmt, want_dyn = _lib.QLN_JAC_FORMAT_DENSE_BLOCKS, dense_dyn + N
+    else:
+        fmt, want_dyn = _lib.QLN_JAC_FORMAT_STRUCTURAL, int(np.count_nonzero(o.jac_c_coo(Z)[:dense_dyn])) + N
+    d = _lib.QlnBatchDesc()
+    d.B, d.N = 1, N
+    k, m = np.array([kt], dtype=np.int32), np.array([init_mode], dtype=np.int32)
+    d.k_trans = k.ctypes.data_as(C.POINTER(C.c_int32))
+    d.init_mode = m.ctypes.data_as(C.POINTER(C.c_int32))
+    d.cost_batch, d.z_stride, d.align, d.jac_format = 1, 0, 16, fmt
+    dims = _lib.QlnDims()
+    i64 = C.POINTER(C.c_int64)
+    co, jo = np.full(1, -1, dtype=np.int64), np.full(1, -1, dtype=np.int64)
+    assert _lib.lib().qln_layout(C.byref(d), C.byref(dims), co.ctypes.data_as(i64), jo.ctypes.data_as(i64)) == _lib.QLN_OK
+    assert (dims.m_nlp_max, dims.c_total) == (o.m_nlp, o.m_nlp)
+    assert dims.nnz_dynamic == want_dyn
+    assert (dims.nnz_max, dims.j_total) == (want_dyn + tail, want_dyn + tail)
+    assert (co[0], jo[0]) == (0, 0)
+
+
 def test_xinds_uinds_are_the_references():
     # src/nlp.jl:38-39: xinds[k] = (k-1)*20 + (1:15), uinds[k] = (k-1)*20 + (16:20)
     xi, ui = NLP.xinds(61), NLP.uinds(61)
