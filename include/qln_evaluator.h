@@ -432,6 +432,38 @@ int qln_tracking_rollout_vjp(qln_handle* h, const double* Zref, const double* K,
 /* the same as a host form (see "Host forms" above; Zref_bar is in-out) */
 int qln_tracking_rollout_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
                                   double* Zref_bar, double* K_bar, double* x0_bar);
+/* Covariance propagation through the closed-loop roll-out: the linear-Gaussian forward sweep along the trajectory Zout
+ * holds.  Knots are 0-based, k = 0..N-2, as in qln_tracking_rollout_vjp.
+ *   A_k (15x15), B_k (15x4) = d Phi_k / d(x_k, F_k) at Zout's (x_k, u_k): exactly the blocks qln_tracking_rollout_vjp uses --
+ *   the evaluator's closed-form step block, except that at the jump knot row 14 is the jump map's (1 at x[14]).  The h
+ *   column is not used: step lengths are not perturbed.  Nothing checks that Zout is a roll-out; for the nominal case pass
+ *   the reference itself.
+ *   Sigma_0 = Sigma0,  Sigma_{k+1} = Acl_k Sigma_k Acl_k' + diag(W),  Acl_k = A_k - B_k K_k  (K == NULL: Acl_k = A_k, open loop)
+ *   W is added after every step, the jump knot included.  Every Sigma_k is formed on its lower triangle and is exactly
+ *   symmetric; positive semi-definiteness is not enforced.
+ * Inputs:
+ *   Sigma0: device, [sigma0_batch][120], packed lower triangle, row i >= j at i(i+1)/2 + j (the layout of P);
+ *           sigma0_batch is 1 (shared by every problem) or B, else QLN_ERR_INVALID_ARGUMENT (as cost_batch).
+ *   Wdiag:  a HOST array of 15 entries, passed by value in the kernel arguments; every entry finite and >= 0, else
+ *           QLN_ERR_INVALID_ARGUMENT; NULL means zeros.
+ *   K:      device, [B][N-1][4][15], or NULL.
+ * Outputs (at least one non-NULL, else QLN_ERR_INVALID_ARGUMENT; overwritten, not accumulated; which of them is asked for
+ * does not change the other's bits; none may overlap an input or the other):
+ *   Sigma: [B][N][120] packed.
+ *   marg:  [B][N][QLN_TRACK_MARG_STRIDE], per knot
+ *     [0]    the variance of the clearance row, a' Sigma_k a with a = e_yb + c'(theta_k) e_theta, c' the derivative entry
+ *            jac_c! writes (quirk Q3's branch at theta == 0);
+ *     [1..4] the variances of the four applied forces, diag(K_k Sigma_k K_k'): exact zeros when K == NULL and at knot N-1;
+ *     [5],[6] Sigma_k[4][4] and Sigma_k[6][6], the two foot heights;
+ *     [7]    trace Sigma_k.
+ * Every N >= 2, every k_trans in [1, N+1] and both init_modes, as the other tracking calls.  Device pointers,
+ * stream-ordered; needs no cost table. */
+#define QLN_TRACK_MARG_STRIDE 8
+int qln_tracking_covariance(qln_handle* h, const double* Zout, const double* K, const double* Sigma0, int32_t sigma0_batch,
+                            const double* Wdiag, double* Sigma, double* marg);
+/* the same as a host form (see "Host forms" above; Wdiag is a host array in both; nothing is in-out) */
+int qln_tracking_covariance_host(qln_handle* h, const double* Zout, const double* K, const double* Sigma0,
+                                 int32_t sigma0_batch, const double* Wdiag, double* Sigma, double* marg);
 /* Z <- Z + N(0, sigma^2) on every entry, step lengths h then clipped to [h_min, h_max] (redraw_h = 0) or redrawn
  * U(h_min, h_max) (redraw_h != 0) -- the evaluation point of SURVEY.md 8d from qln_initial_guess's Z0.  The normal
  * draws are Box-Muller on the sampler's stream from `stream_offset`: the recipe's distribution, not numpy's numbers. */

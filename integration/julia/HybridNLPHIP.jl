@@ -194,6 +194,21 @@ function tracking_rollout_vjp(prob::HybridNLPHIP, Zref::Vector{Float64}, Zout::V
                     x0_bar))
     return Zref_bar, K_bar, x0_bar
 end
+# covariance of the roll-out's states along the trajectory Zout (for the nominal case: the reference itself):
+# Sigma_0 = Sigma0, Sigma_{k+1} = (A_k - B_k K_k) Sigma_k (A_k - B_k K_k)' + diag(W); K = nothing is the open loop.
+# Sigma0: a 15x15 matrix (its lower triangle is read); W: 15 variances or nothing (zeros).  Returns Sigma as (120, N) packed
+# lower triangles (row i >= j at i(i+1)/2 + j, 0-based) and marg as (8, N): the clearance row's variance, the four force
+# variances, the two foot-height variances and the trace, per knot.  include/qln_evaluator.h, DESIGN.md 4.13
+function tracking_covariance(prob::HybridNLPHIP, Zout::Vector{Float64}, Sigma0::Matrix{Float64}; K=nothing, W=nothing)
+    N = prob.N
+    packed = Float64[Sigma0[i, j] for i in 1:15 for j in 1:i]
+    Sigma = zeros(120, N)
+    marg = zeros(8, N)
+    qln_check(ccall((:qln_tracking_covariance_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zout, K === nothing ? C_NULL : K, packed, Int32(1), W === nothing ? C_NULL : W, Sigma, marg))
+    return Sigma, marg
+end
 
 # ---- the reference's Ipopt solve, for this evaluator type: a method of `solve` (src/moi.jl:46-103) ------------------------
 # Same generic function, same keyword arguments and defaults, same five things handed to Ipopt.  What differs from the

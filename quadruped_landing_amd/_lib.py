@@ -25,6 +25,7 @@ NX, NU, NZ, COST_STRIDE = 15, 5, 20, 41
 GN_INFO_STRIDE = 8
 HESS_STEP_NNZ, HESS_TERM_NNZ = 55, 15
 TRACK_NU, TRACK_P_NNZ = 4, 120
+TRACK_MARG_STRIDE = 8
 
 
 class QlnModel(C.Structure):
@@ -149,6 +150,8 @@ SIGNATURES = {
     "qln_tracking_rollout_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     "qln_tracking_rollout_vjp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "qln_tracking_rollout_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "qln_tracking_covariance": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp]),
+    "qln_tracking_covariance_host": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp]),
     "qln_eval_constraint_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_eval_constraint_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_gauss_newton_step": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, C.c_double, _dp, _dp, _dp]),

@@ -70,6 +70,7 @@ int32_t nnz_of(int32_t N, int32_t kt, int32_t fmt) { return qln::vals_layout(N, 
 
 int64_t tracking_k_total(const qln_dims& D) { return (int64_t)D.B * (D.N - 1) * QLN_TRACK_NU * QLN_NX; }
 int64_t tracking_p_total(const qln_dims& D) { return (int64_t)D.B * D.N * QLN_TRACK_P_NNZ; }
+int64_t tracking_marg_total(const qln_dims& D) { return (int64_t)D.B * D.N * QLN_TRACK_MARG_STRIDE; }
 
 // The buffers of the host forms (qln_*_host), one per role.  A role's size follows from the role and the handle's layout
 // (host_role_size): no form can allocate a buffer that another finds too small.  An in-out argument is copied in whole,
@@ -91,6 +92,9 @@ enum HostRole {
     kKbar,   // out: the gains' cotangent                                   layout of K
     kP,      // out: the cost-to-go                                         [B][N][120]
     kX0,     // in: the roll-out's x0; out: the vjp's x0_bar                [B][15]
+    kCov0,   // in: the covariance sweep's Sigma0 (1 or B tiles used)       [B][120]
+    kCov,    // out: the covariances                                        layout of P
+    kMarg,   // out: the marginals                                          [B][N][8]
     kHostRoles
 };
 
@@ -160,7 +164,9 @@ int64_t host_role_size(const qln_handle* h, HostRole r) {
         case kF: case kSigma: return D.B;
         case kHvals: return (int64_t)(D.B - 1) * h->h_stride + hessian_nnz(D.N);  // no padding behind the last problem
         case kK: case kKbar: return tracking_k_total(D);
-        case kP: return tracking_p_total(D);
+        case kP: case kCov: return tracking_p_total(D);
+        case kCov0: return (int64_t)D.B * QLN_TRACK_P_NNZ;
+        case kMarg: return tracking_marg_total(D);
         case kX0: return (int64_t)D.B * QLN_NX;
         case kHostRoles: break;
     }
@@ -1131,6 +1137,57 @@ int qln_tracking_rollout_vjp_host(qln_handle* h, const double* Zref, const doubl
                      [&](double* const* d, bool) {
                          return qln::launch_tracking_rollout_vjp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kZbar], d[kZio],
                                                                  d[kKbar], d[kX0], h->stream);
+                     });
+}
+
+// the covariance sweep (k_tracking_covariance).  The checks that need no handle come first.
+static int check_tracking_covariance_args(const qln_handle* h, const double* Zout, const double* K, const double* Sigma0,
+                                          int32_t sigma0_batch, const double* Wdiag, const double* Sigma, const double* marg,
+                                          const char* who) {
+    const std::string w(who);
+    if (!Sigma && !marg) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Sigma and marg are both NULL (nothing to compute)");
+    if (Wdiag)
+        for (int i = 0; i < QLN_NX; ++i)
+            if (!(std::isfinite(Wdiag[i]) && Wdiag[i] >= 0.0))
+                return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Wdiag must be finite and >= 0 (entry " + std::to_string(i) + ")");
+    if (sigma0_batch < 1) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
+    if (int rc = check_handle(h)) return rc;
+    const qln_dims& D = h->dims;
+    if (sigma0_batch != 1 && sigma0_batch != D.B) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
+    if (!Zout || !Sigma0) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zout or Sigma0");
+    const struct {
+        const double* p;
+        int64_t n;
+    } in[] = {{Zout, D.z_total}, {K, tracking_k_total(D)}, {Sigma0, (int64_t)sigma0_batch * QLN_TRACK_P_NNZ}},
+      out[] = {{Sigma, tracking_p_total(D)}, {marg, tracking_marg_total(D)}};
+    for (const auto& o : out)
+        for (const auto& i : in)
+            if (overlaps(o.p, o.n, i.p, i.n)) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": an output overlaps an input");
+    if (overlaps(out[0].p, out[0].n, out[1].p, out[1].n)) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Sigma overlaps marg");
+    return QLN_OK;
+}
+
+int qln_tracking_covariance(qln_handle* h, const double* Zout, const double* K, const double* Sigma0, int32_t sigma0_batch,
+                            const double* Wdiag, double* Sigma, double* marg) {
+    if (int rc = check_tracking_covariance_args(h, Zout, K, Sigma0, sigma0_batch, Wdiag, Sigma, marg, "qln_tracking_covariance"))
+        return rc;
+    if (int rc = bind_device(h)) return rc;
+    QLN_HIP(qln::launch_tracking_covariance(h->p, Zout, K, Sigma0, sigma0_batch, Wdiag, Sigma, marg, h->stream));
+    return QLN_OK;
+}
+
+int qln_tracking_covariance_host(qln_handle* h, const double* Zout, const double* K, const double* Sigma0,
+                                 int32_t sigma0_batch, const double* Wdiag, double* Sigma, double* marg) {
+    if (int rc = check_tracking_covariance_args(h, Zout, K, Sigma0, sigma0_batch, Wdiag, Sigma, marg,
+                                                "qln_tracking_covariance_host"))
+        return rc;
+    if (int rc = bind_device(h)) return rc;
+    HostArg s0 = copy_in(kCov0, Sigma0);
+    s0.n = (int64_t)sigma0_batch * QLN_TRACK_P_NNZ;  // the tiles the call reads, of the role's B
+    return host_call(h, {copy_in(kV, Zout), copy_in(kK, K), s0, copy_out(kCov, Sigma), copy_out(kMarg, marg)},
+                     [&](double* const* d, bool) {
+                         return qln::launch_tracking_covariance(h->p, d[kV], d[kK], d[kCov0], sigma0_batch, Wdiag, d[kCov],
+                                                                d[kMarg], h->stream);
                      });
 }
 

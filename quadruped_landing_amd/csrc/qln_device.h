@@ -300,6 +300,10 @@ hipError_t launch_tracking_rollout(const BatchParams& p, const double* Zref, con
 // needs K and reads Zref's states) (qln_tracking_kernels.hip)
 hipError_t launch_tracking_rollout_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
                                        const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, hipStream_t stream);
+// Sigma_{k+1} = (A_k - B_k K_k) Sigma_k (A_k - B_k K_k)' + diag(Wd) along Zout (K null: open loop); Sigma0 [sigma0_batch][120],
+// Wd a host array (null: zeros); Sigma [B][N][120] and marg [B][N][8], either may be null (qln_tracking_kernels.hip)
+hipError_t launch_tracking_covariance(const BatchParams& p, const double* Zout, const double* K, const double* Sigma0,
+                                      int sigma0_batch, const double* Wd, double* Sigma, double* marg, hipStream_t stream);
 // batched Gauss-Newton step on the constraint violation, CGLS per problem in LDS (qln_solver_kernels.hip)
 size_t gauss_newton_lds_bytes(int32_t N);
 hipError_t launch_gauss_newton_step(const BatchParams& p, const double* Z, const double* c, double* dZ, int max_iters,

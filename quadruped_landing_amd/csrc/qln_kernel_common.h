@@ -2,6 +2,8 @@
 //   * wave / dispatch helpers;
 //   * the value path: dynamics, rk4_step, step_forward (one knot of a roll-out), literal restatements of the reference
 //     that round like it;
+//   * clearance_dtheta, the one derivative entry of the clearance rows (the J v / J' lam products and the covariance
+//     sweep's clearance marginal read it);
 //   * the 15 x 20 step Jacobian in closed form, the one statement of it that the evaluator (qln_kernels.hip), J v / J' lam
 //     and the Gauss-Newton step (qln_solver_kernels.hip), the iLQR solve (qln_ilqr_kernels.hip) and the TVLQR sweep
 //     (qln_tracking_kernels.hip) share: StepBlock + step_block() form a knot's base quantities from explicit arguments
@@ -118,6 +120,12 @@ __device__ __forceinline__ void step_forward(const Model& M, int k, int kt, int 
         xn[6] = 0.0;
         xn[10] = xn[11] = xn[12] = xn[13] = 0.0;
     }
+}
+
+// d(clearance_k)/d(theta_k), src/constraints.jl:269-273 (theta == 0 takes the + branch, quirk Q3)
+__device__ __forceinline__ double clearance_dtheta(double th, double lb) {
+    const double cth = cos(th);
+    return (th > 0) ? (-lb / 2 * cth) : (lb / 2 * cth);
 }
 
 // ---------------------------------------------------------------------------------------------

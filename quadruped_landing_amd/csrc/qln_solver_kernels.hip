@@ -42,12 +42,6 @@ __device__ __forceinline__ ProblemView view_of(const BatchParams& P, const Probl
     return v;
 }
 
-// d(clearance_k)/d(theta_k), src/constraints.jl:269-273 (theta == 0 takes the + branch, quirk Q3)
-__device__ __forceinline__ double clearance_dtheta(double th, double lb) {
-    const double cth = cos(th);
-    return (th > 0) ? (-lb / 2 * cth) : (lb / 2 * cth);
-}
-
 // Coalesced copy of n <= kPZ doubles global -> LDS by one wave, every load in flight before the first wait (a plain
 // copy loop is one memory round trip per 64 doubles).  Indices past n are clamped, not predicated; dst has room for
 // kStageIters * 64 doubles.

@@ -29,6 +29,20 @@
 //   (d tau / d x_j d F_m), so no lane forms a whole row;
 //   K_k'ubar and K_bar = -ubar dx' are four FMAs / four products per lane on column j, stored coalesced.
 // The knot's slices (x_k, u_k, Zbar, x_ref and K column j) are loaded one knot ahead.
+//
+// k_tracking_covariance: the forward sweep Sigma_{k+1} = Acl_k Sigma_k Acl_k' + diag(W), Acl_k = A_k - B_k K_k (DESIGN.md
+// 4.13).  The mapping of k_tracking_lqr: one problem per row of sixteen lanes, lane j < 15 keeps column j of Sigma_k
+// (= row j) in registers, and every lane forms the knot's StepBlock alike.  No dense Acl: a lane applies Acl to a vector v as
+// A v - B (K v) -- the visitor's entries of A (four per column) and of B (24) at compile-time positions, K read row by row
+// from a per-row LDS tile -- and the knot is two such applications with a transpose between them, Sigma' = Acl (Acl Sigma)':
+//   1. V column j = Acl Sigma column j -> row j of the padded image (stride 17) in LDS; g = K Sigma column j on the way,
+//      whose row sums against K column j are the force variances (diag of M = G K');
+//   2. lane j reads row j of V back (consecutive addresses) and forms column j of Sigma' = Acl V row j' + W_j e_j, stored
+//      as row j of the image.  From there on only the image's lower triangle is read -- by the lanes for their next column,
+//      by the marginals and by the packed tile's coalesced stores -- so every Sigma_k is exactly symmetric.
+// Expanded, that is A Sigma A' - (A G')B' - B (G A') + B M B' with G = K Sigma and M = G K', grouped so that nothing but
+// K v crosses lanes.  Zout's knot (two coalesced loads, handed out through LDS) and the K tile are loaded one knot ahead;
+// the clearance row's cosine is taken for sixteen knots at a time, one per lane.
 #include "qln_kernel_common.h"
 
 #include <cstdlib>
@@ -499,6 +513,229 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, c
     if (valid && x0_bar && own) x0_bar[(int64_t)b * QLN_NX + j] = lam;
 }
 
+
+// ---- k_tracking_covariance ----
+// per-row LDS image (doubles): Sigma / V image [15][17] (one region: V lives there between the two applications) | K [4][16] |
+// the knot's 20 entries of Zout | the clearance derivatives of sixteen knots
+constexpr int kCStr = 17, kCImg = 0, kCK = 256, kCZ = kCK + 4 * 16, kCD = kCZ + 20, kCRow = kCD + 16;
+static_assert(15 * kCStr <= kCK && kCK % 2 == 0 && kCZ % 2 == 0 && kCD % 2 == 0 && kCRow % 2 == 0,
+              "the image fits; 16-byte aligned sections");
+
+// row_sum16 with bound_ctrl set: every lane of these four permutations has a source, so no old value has to be prepared
+template <int kCtrl>
+__device__ __forceinline__ double dpp_f64_bc(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), kCtrl, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), kCtrl, 0xf, 0xf, true);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double row_sum16_bc(double v) {
+    v += dpp_f64_bc<0xB1>(v);   // quad_perm [1,0,3,2]
+    v += dpp_f64_bc<0x4E>(v);   // quad_perm [2,3,0,1]
+    v += dpp_f64_bc<0x141>(v);  // row_half_mirror
+    v += dpp_f64_bc<0x140>(v);  // row_mirror
+    return v;
+}
+
+struct CovNoise {
+    double w[15];
+};
+
+// out = Acl v = A v - B (K v); g = K v (4).  The block's entries are formed where they are used (the weight x force
+// products of rows 2 and 9 included): what stays live between the knot's two applications is the StepBlock, not 70 entries.
+template <bool kHasK>
+__device__ __forceinline__ void cov_apply(const StepBlock& blk, const double* Kl, const double (&v)[15],
+                                          double (&out)[15], double (&g)[4]) {
+#pragma unroll
+    for (int i = 0; i < 15; ++i) out[i] = 0.0;
+    if constexpr (kHasK) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            double acc = Kl[16 * m] * v[0];
+#pragma unroll
+            for (int c = 1; c < 15; ++c) acc = fma(Kl[16 * m + c], v[c], acc);
+            // one row of K in flight at a time: the empty asm holds this row's sum in front of the next row's reads (left
+            // to itself the compiler issues all four rows' reads first, 120 registers)
+            asm volatile("" : "+v"(acc) : : "memory");
+            g[m] = acc;
+        }
+    } else {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) g[m] = 0.0;
+    }
+    // the h-weights pass through an empty asm, as in the evaluator's tile loop: the 25 weight x force products are then
+    // formed here, in each application, instead of living in 50 registers across both
+    StepBlock bk = blk;
+    asm volatile("" : "+v"(bk.wAt), "+v"(bk.wBt), "+v"(bk.wAw));
+    // row 14 of the jump knot: the jump map keeps the clock (its Jacobian's mask zeroes the row, quirk Q1)
+    for_each_step_entry(bk, [&](auto r, auto c, double val) {
+        if constexpr (c < 15) out[r] = fma((r == 14) ? 1.0 : val, v[c], out[r]);
+        else if constexpr (kHasK && c < 19) out[r] = fma(-val, g[c - 15], out[r]);
+    });
+}
+
+// Sigma_0 = Sigma0[b] (or the shared one), Sigma_{k+1} = Acl_k Sigma_k Acl_k' + diag(W) at Zout's knots; Sig gets every
+// Sigma_k packed, mg the eight marginals of every knot (include/qln_evaluator.h).  Either may be null; which one is does
+// not change the arithmetic of the other.
+template <bool kHasK>
+__global__ __launch_bounds__(kWave) void k_tracking_covariance(BatchParams P, CovNoise Wn, const double* __restrict__ Zout,
+                                                               const double* __restrict__ Kg, const double* __restrict__ Sigma0,
+                                                               int sigma0_batch, double* __restrict__ Sig,
+                                                               double* __restrict__ mg) {
+    __shared__ double lds[kRows * kCRow];
+    const int lane = threadIdx.x;
+    const int ln = lane & 15, row = lane >> 4;
+    const int j = ln < 15 ? ln : 14;  // lane 15 shadows column 14 and writes nothing to the image
+    const bool own = ln < 15;
+    const int wave = xcd_contiguous_index(blockIdx.x, (P.B + kRows - 1) / kRows);
+    const int b = wave * kRows + row;
+    const bool valid = b < P.B;
+    const int bc = valid ? b : P.B - 1;
+    const int N = P.N;
+    const ProblemDesc pd = P.desc[bc];
+    const int kt = pd.k_trans, im = pd.init_mode;
+    const Model M(P);
+    double* L = lds + row * kCRow;
+    const double* __restrict__ Zb = Zout + (int64_t)bc * P.z_stride;
+    const double* __restrict__ Kb = kHasK ? Kg + (int64_t)bc * (N - 1) * (QLN_TRACK_NU * QLN_NX) : nullptr;
+    double* __restrict__ Sb = Sig ? Sig + (int64_t)bc * N * QLN_TRACK_P_NNZ : nullptr;
+    double* __restrict__ Mb = mg ? mg + (int64_t)bc * N * QLN_TRACK_MARG_STRIDE : nullptr;
+
+    // where the packed entries ln + 16 t lie in the image's lower triangle, the K entries ln + 16 t in the K tile (rows
+    // padded to 16); sym(c): entry (max(c, j), min(c, j)) of the lane's column -- the lower triangle is the one that is read
+    int po[8], ko[4];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const int i = min(ln + 16 * t, QLN_TRACK_P_NNZ - 1);
+        int r = 0;
+#pragma unroll
+        for (int q = 1; q < 15; ++q) r += (i >= q * (q + 1) / 2) ? 1 : 0;
+        po[t] = kCImg + kCStr * r + (i - r * (r + 1) / 2);
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int i = min(ln + 16 * t, QLN_TRACK_NU * QLN_NX - 1);
+        const int m = i / 15;
+        ko[t] = kCK + 16 * m + (i - 15 * m);
+    }
+    const int rowj = kCImg + kCStr * j, colj = kCImg + j;
+    auto sym = [&](int c) { return (c <= j) ? rowj + c : colj + kCStr * c; };
+    double wj = 0.0;
+#pragma unroll
+    for (int i = 0; i < 15; ++i) wj = (i == j) ? Wn.w[i] : wj;
+
+    // Sigma_0: the packed tile into the image's lower triangle
+    {
+        const double* __restrict__ S0 = Sigma0 + (int64_t)(sigma0_batch == 1 ? 0 : bc) * QLN_TRACK_P_NNZ;
+#pragma unroll
+        for (int t = 0; t < 8; ++t)
+            if (ln + 16 * t < QLN_TRACK_P_NNZ) L[po[t]] = S0[ln + 16 * t];
+    }
+    wave_lds_sync();
+    double s[15];
+#pragma unroll
+    for (int c = 0; c < 15; ++c) s[c] = L[sym(c)];
+
+    // the clearance row's derivative entry needs a cosine: lane ln takes knot k0 + ln, once every sixteen knots
+    auto clearance_derivatives = [&](int k0) {
+        L[kCD + ln] = clearance_dtheta(Zb[20 * min(k0 + ln, N - 1) + 2], M.lb);
+    };
+    // Sigma_k and its marginals leave from the image's lower triangle; fv: the knot's force variances
+    auto emit = [&](int k, const double (&fv)[4]) {
+        if (Sb && valid) {
+            double* __restrict__ o = Sb + (int64_t)k * QLN_TRACK_P_NNZ;
+#pragma unroll
+            for (int t = 0; t < 8; ++t)
+                if (ln + 16 * t < QLN_TRACK_P_NNZ) o[ln + 16 * t] = L[po[t]];
+        }
+        if (Mb) {
+            const double dth = L[kCD + (k & 15)];
+            const double s11 = L[kCImg + kCStr * 1 + 1], s21 = L[kCImg + kCStr * 2 + 1], s22 = L[kCImg + kCStr * 2 + 2];
+            double mv[QLN_TRACK_MARG_STRIDE];
+            mv[0] = fma(dth, fma(dth, s22, 2.0 * s21), s11);  // a' Sigma a, a = e_yb + dth e_theta
+#pragma unroll
+            for (int m = 0; m < 4; ++m) mv[1 + m] = fv[m];
+            mv[5] = L[kCImg + (kCStr + 1) * 4];
+            mv[6] = L[kCImg + (kCStr + 1) * 6];
+            const double dj = L[kCImg + (kCStr + 1) * j];
+            mv[7] = row_sum16_bc(own ? dj : 0.0);
+            double v = mv[0];
+#pragma unroll
+            for (int q = 1; q < QLN_TRACK_MARG_STRIDE; ++q) v = (ln == q) ? mv[q] : v;
+            if (valid && ln < QLN_TRACK_MARG_STRIDE) Mb[(int64_t)k * QLN_TRACK_MARG_STRIDE + ln] = v;
+        }
+    };
+
+    // Zout's knot (20 entries: lane ln takes ln and ln + 16) and the knot's K entries: requested one knot ahead
+    double zn[2], kn[4];
+    zn[0] = Zb[ln];
+    zn[1] = Zb[16 + (ln & 3)];
+    if constexpr (kHasK) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) kn[t] = Kb[min(ln + 16 * t, QLN_TRACK_NU * QLN_NX - 1)];
+    }
+
+    for (int k = 0; k < N - 1; ++k) {
+        if (Mb && (k & 15) == 0) clearance_derivatives(k);
+        L[kCZ + ln] = zn[0];
+        if (ln < 4) L[kCZ + 16 + ln] = zn[1];
+        if constexpr (kHasK) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (ln + 16 * t < QLN_TRACK_NU * QLN_NX) L[ko[t]] = kn[t];
+        }
+        if (k + 1 < N - 1) {
+            zn[0] = Zb[20 * (k + 1) + ln];
+            zn[1] = Zb[20 * (k + 1) + 16 + (ln & 3)];
+            if constexpr (kHasK) {
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                    kn[t] = Kb[(int64_t)(k + 1) * (QLN_TRACK_NU * QLN_NX) + min(ln + 16 * t, QLN_TRACK_NU * QLN_NX - 1)];
+            }
+        }
+        wave_lds_sync();  // the knot and the K tile are in place
+        const StepBlock blk = step_block(L + kCZ, knot_mode(k + 1, kt - 1, im), M);
+        // ---- 1. V column j = Acl Sigma column j; the force variances; Sigma_k leaves ----
+        double out[15], g[4], fv[4];
+        cov_apply<kHasK>(blk, L + kCK, s, out, g);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            fv[m] = 0.0;
+            if constexpr (kHasK) {
+                if (Mb) fv[m] = row_sum16_bc(own ? L[kCK + 16 * m + j] * g[m] : 0.0);
+            }
+        }
+        emit(k, fv);
+        wave_lds_sync();  // the image has been read: V may overwrite it
+        if (own) {
+#pragma unroll
+            for (int i = 0; i < 15; ++i) L[kCImg + kCStr * j + i] = out[i];
+        }
+        wave_lds_sync();
+        // ---- 2. column j of Sigma_{k+1} = Acl (row j of V)' + W_j e_j, stored as row j of the image ----
+        double vt[15];
+#pragma unroll
+        for (int c = 0; c < 15; ++c) vt[c] = L[kCImg + kCStr * c + j];
+        cov_apply<kHasK>(blk, L + kCK, vt, out, g);
+        wave_lds_sync();  // every lane holds its row of V: Sigma_{k+1} may overwrite the image
+        if (own) {
+#pragma unroll
+            for (int i = 0; i < 15; ++i) L[kCImg + kCStr * j + i] = out[i];
+            L[kCImg + (kCStr + 1) * j] = L[kCImg + (kCStr + 1) * j] + wj;
+        }
+        wave_lds_sync();
+        // only the lower triangle is read from here on: Sigma_{k+1} is exactly symmetric
+#pragma unroll
+        for (int c = 0; c < 15; ++c) s[c] = L[sym(c)];
+        // the K tile and the knot are rewritten at the top of the next knot, after this knot's last read of them
+    }
+    if (Mb && ((N - 1) & 15) == 0) {
+        clearance_derivatives(N - 1);
+        wave_lds_sync();
+    }
+    const double fv0[4] = {0.0, 0.0, 0.0, 0.0};
+    emit(N - 1, fv0);
+}
+
 }  // namespace
 
 hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const double* Rd, const double* Qfd, const double* Zref,
@@ -536,6 +773,18 @@ hipError_t launch_tracking_rollout_vjp(const BatchParams& p, const double* Zref,
         hipLaunchKernelGGL(kern, dim3(xcd_grid(waves)), dim3(kWave), 0, stream, p, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar);
     };
     K ? go(k_tracking_rollout_vjp<true>) : go(k_tracking_rollout_vjp<false>);
+    return hipGetLastError();
+}
+
+hipError_t launch_tracking_covariance(const BatchParams& p, const double* Zout, const double* K, const double* Sigma0,
+                                      int sigma0_batch, const double* Wd, double* Sigma, double* marg, hipStream_t stream) {
+    CovNoise w;
+    for (int i = 0; i < 15; ++i) w.w[i] = Wd ? Wd[i] : 0.0;
+    const int waves = (p.B + kRows - 1) / kRows;
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(xcd_grid(waves)), dim3(kWave), 0, stream, p, w, Zout, K, Sigma0, sigma0_batch, Sigma, marg);
+    };
+    K ? go(k_tracking_covariance<true>) : go(k_tracking_covariance<false>);
     return hipGetLastError();
 }
 

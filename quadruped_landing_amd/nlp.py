@@ -119,6 +119,43 @@ def unpack_cost_to_go(P):
     return out
 
 
+def unpack_covariance(Sigma):
+    """(..., 120) packed lower triangles of qln_tracking_covariance -> (..., 15, 15) symmetric numpy matrices (the layout
+    of the cost-to-go)."""
+    return unpack_cost_to_go(Sigma)
+
+
+def pack_covariance(Sigma):
+    """(..., 15, 15) matrices -> (..., 120) packed lower triangles, row i >= j at i(i+1)/2 + j (the lower triangle is what
+    is kept)."""
+    Sigma = np.asarray(Sigma, dtype=np.float64)
+    r, c = np.tril_indices(n)
+    return np.ascontiguousarray(Sigma[..., r, c])
+
+
+def tracking_sigma0(Sigma0, B: int):
+    """The initial covariance of qln_tracking_covariance in any of its forms -> (packed (sigma0_batch, 120), sigma0_batch):
+    a 15-vector of variances, a 15x15 matrix, (B, 15, 15), or already packed (120,), (1, 120) or (B, 120)."""
+    S = np.asarray(Sigma0, dtype=np.float64)
+    if S.shape == (n,):
+        S = np.diag(S)
+    if S.shape[-2:] == (n, n) and S.ndim in (2, 3):
+        S = pack_covariance(S)
+    if S.ndim == 1:
+        S = S[None]
+    if S.ndim != 2 or S.shape[1] != _lib.TRACK_P_NNZ or S.shape[0] not in (1, B):
+        raise ValueError(f"Sigma0 of shape {np.shape(Sigma0)}: expected (15,), (15, 15), ({B}, 15, 15), (120,), (1, 120) or "
+                         f"({B}, 120)")
+    return np.ascontiguousarray(S), int(S.shape[0])
+
+
+def tracking_noise(W):
+    """The diagonal process noise as a contiguous (15,) array, or None (zeros); a scalar broadcasts."""
+    if W is None:
+        return None
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(W, dtype=np.float64), (n,)))
+
+
 def _torch():
     import torch
 
@@ -613,6 +650,55 @@ class HybridNLP:
         _lib.check(_lib.lib().qln_tracking_rollout_vjp_host(self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data,
                                                             Zbar.ctypes.data, _host_ptr(zb), _host_ptr(kb), _host_ptr(xb)))
         return zb, kb, xb
+
+    # -- covariance propagation through the closed-loop roll-out -----------------------------------
+    def tracking_covariance(self, Zout, K=None, Sigma0=None, W=None, with_sigma=True, with_marginals=True, Sigma=None,
+                            marg=None):
+        """Sigma_{k+1} = (A_k - B_k K_k) Sigma_k (A_k - B_k K_k)' + diag(W) along the trajectory Zout (device tensor, layout
+        of Z; for the nominal case the reference itself), K None for the open loop.  Sigma0: a 15-vector of variances, a
+        15x15 matrix, (B, 15, 15), or packed (numpy or a CUDA tensor of packed tiles).  Returns (Sigma, marg): Sigma
+        (B, N, 120) packed lower triangles (unpack_covariance), marg (B, N, 8) = clearance variance, four force variances,
+        the two foot-height variances, trace; each None unless asked for (Sigma / marg: buffers to write into instead of
+        fresh ones).  Stream-ordered (qln_evaluator.h)."""
+        T = _torch()
+        if Sigma0 is None:
+            raise ValueError("Sigma0 is required")
+        self._check(Zout, self.dims.z_total, "Zout")
+        kp = None if K is None else self._check(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        if isinstance(Sigma0, T.Tensor) and Sigma0.is_cuda:
+            nb = Sigma0.numel() // _lib.TRACK_P_NNZ
+            if Sigma0.numel() != nb * _lib.TRACK_P_NNZ or nb not in (1, self.B):
+                raise ValueError("a device Sigma0 must hold 1 or B packed tiles of 120")
+            s0 = Sigma0
+        else:
+            host, nb = tracking_sigma0(Sigma0, self.B)
+            s0 = T.from_numpy(host).to(self._dev())
+        self._check(s0, nb * _lib.TRACK_P_NNZ, "Sigma0")
+        Wh = tracking_noise(W)
+        S = mg = None
+        if with_sigma:
+            S = T.empty(tracking_p_shape(self.B, self.N), dtype=T.float64, device=self._dev()) if Sigma is None else Sigma
+            self._check(S, self.B * self.N * _lib.TRACK_P_NNZ, "Sigma")
+        if with_marginals:
+            mg = T.empty((self.B, self.N, _lib.TRACK_MARG_STRIDE), dtype=T.float64, device=self._dev()) if marg is None else marg
+            self._check(mg, self.B * self.N * _lib.TRACK_MARG_STRIDE, "marg")
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        _lib.check(_lib.lib().qln_tracking_covariance(self._h, Zout.data_ptr(), kp, s0.data_ptr(), nb, _host_ptr(Wh), ptr(S),
+                                                      ptr(mg)))
+        return S, mg
+
+    def tracking_covariance_host(self, Zout, K=None, Sigma0=None, W=None, with_sigma=True, with_marginals=True):
+        """The same with host arrays (synchronous): numpy (Sigma (B, N, 120), marg (B, N, 8))."""
+        if Sigma0 is None:
+            raise ValueError("Sigma0 is required")
+        Zout, K = self._host_Z(Zout, "Zout"), self._host_K(K)
+        s0, nb = tracking_sigma0(Sigma0, self.B)
+        Wh = tracking_noise(W)
+        S = np.zeros(tracking_p_shape(self.B, self.N)) if with_sigma else None
+        mg = np.zeros((self.B, self.N, _lib.TRACK_MARG_STRIDE)) if with_marginals else None
+        _lib.check(_lib.lib().qln_tracking_covariance_host(self._h, Zout.ctypes.data, _host_ptr(K), s0.ctypes.data, nb,
+                                                           _host_ptr(Wh), _host_ptr(S), _host_ptr(mg)))
+        return S, mg
 
     def differentiable_rollout(self, Zref, K=None, x0=None):
         """tracking_rollout as a torch autograd op: returns Zout, differentiable in Zref, K and x0 (each a float64 CUDA

@@ -1,0 +1,309 @@
+"""GPU checks of qln_tracking_covariance: the numpy recursion on the evaluator's own blocks and on complex-step blocks over
+the tracking shapes and at full size, the duality with qln_tracking_rollout_vjp, the bit-for-bit parts of the contract, a
+Monte Carlo roll-out of 4 096 perturbed drops, and the host forms."""
+import faulthandler
+
+import numpy as np
+import pytest
+
+from tests import rollout_vjp_ref as RV
+from tests import tracking_cov_ref as CR
+from tests.test_gpu_rollout_vjp import _inputs
+from tests.test_gpu_tracking import SHAPES, _batch, _dense_blocks, _nlp
+
+pytestmark = pytest.mark.gpu
+
+Q = np.array([10.0] * 14 + [0.0])
+R = np.array([1e-3, 1e-2, 1e-3, 1e-2])
+BAR = 1e-10  # the project's bar for K and P (tests/test_gpu_tracking.py); the yardstick's own rounding is ~1e-14
+
+
+@pytest.fixture(autouse=True)
+def _time_limit():
+    """Every test here is a GPU step with a time limit of its own: a hang ends the process with a traceback."""
+    faulthandler.dump_traceback_later(900, exit=True)
+    yield
+    faulthandler.cancel_dump_traceback_later()
+
+
+def _setup(batch, seed, with_gains, **kw):
+    """A handle, a roll-out Zout near the batch's Z under random gains (or open loop), per-problem random Sigma0 and W."""
+    nlp = _nlp(batch, **kw)
+    _, K, _, Zout, _ = _inputs(nlp, batch, seed, with_gains)
+    rng = np.random.default_rng(seed + 100)
+    S0 = CR.random_psd(rng, shape=(nlp.B,))
+    W = rng.uniform(0.0, 1e-2, size=15)
+    return nlp, K, Zout, S0, W
+
+
+def _host(nlp, t):
+    return t.view(nlp.B, -1)[:, : nlp.n_nlp].cpu().numpy()
+
+
+def _reference(nlp, K, Zout, S0, W, blocks):
+    """numpy (Sigma (B, N, 15, 15), marg (B, N, 8)) on blocks(b, zo) (N-1, 15, 20) per problem"""
+    zo = _host(nlp, Zout)
+    Kh = None if K is None else K.cpu().numpy()
+    N = nlp.N
+    Sr = np.zeros((nlp.B, N, 15, 15))
+    mr = np.zeros((nlp.B, N, 8))
+    for b in range(nlp.B):
+        F = blocks(b, zo[b])
+        Sr[b] = CR.propagate(F[:, :, :15], F[:, :, 15:19], None if Kh is None else Kh[b], S0[b] if S0.ndim == 3 else S0, W)
+        theta = zo[b][2 + 20 * np.arange(N)]
+        mr[b] = CR.marginals(Sr[b], None if Kh is None else Kh[b], theta, nlp.model.lb)
+    return Sr, mr
+
+
+def _evaluator_blocks(nlp, Zout):
+    dense = _dense_blocks(nlp, Zout)
+    return lambda b, zo: RV.evaluator_blocks(dense[b], int(nlp.k_trans[b]))
+
+
+def _cs_blocks(nlp):
+    return lambda b, zo: RV.complex_step_blocks(nlp.N, int(nlp.k_trans[b]), int(nlp.init_mode[b]), zo)
+
+
+def _errors(nlp, K, Zout, S0, W, blocks):
+    from quadruped_landing_amd import nlp as NL
+
+    S, mg = nlp.tracking_covariance(Zout, K, S0, W)
+    Sg, mgg = NL.unpack_covariance(S), mg.cpu().numpy()
+    assert np.array_equal(Sg, np.swapaxes(Sg, -1, -2))
+    Sr, mr = _reference(nlp, K, Zout, S0, W, blocks)
+    if K is None:
+        assert not mgg[:, :, 1:5].any()
+    assert not mgg[:, -1, 1:5].any()
+    return CR.knot_rel(Sg, Sr), CR.entry_rel(mgg, mr)
+
+
+@pytest.mark.parametrize("B,N,k_trans,init_mode", SHAPES)
+@pytest.mark.parametrize("with_gains", [False, True])
+def test_matches_numpy_recursion_over_shapes(B, N, k_trans, init_mode, with_gains):
+    batch = _batch(B, N, k_trans, init_mode, seed=N + k_trans)
+    nlp, K, Zout, S0, W = _setup(batch, N + 3 * k_trans, with_gains)
+    es, em = _errors(nlp, K, Zout, S0, W, _evaluator_blocks(nlp, Zout))
+    print(f"B={B} N={N} k_trans={k_trans} mode={init_mode} K={with_gains}: Sigma {es:.2e}, marg {em:.2e}")
+    assert es <= BAR and em <= BAR, (es, em)
+
+
+@pytest.mark.parametrize("N", [12, 40])
+@pytest.mark.parametrize("with_gains", [False, True])
+def test_ragged_batch_and_padded_layout(N, with_gains):
+    for batch, kw in ((_batch(37, N, 5, 1, seed=3, ragged=True), {}),
+                      (_batch(13, N, 7, 2, seed=4), {"z_stride": 20 * N + 3, "align": 7})):
+        nlp, K, Zout, S0, W = _setup(batch, 5, with_gains, **kw)
+        es, em = _errors(nlp, K, Zout, S0, W, _evaluator_blocks(nlp, Zout))
+        print(f"N={N} K={with_gains} {kw}: Sigma {es:.2e}, marg {em:.2e}")
+        assert es <= BAR and em <= BAR, (es, em)
+
+
+@pytest.mark.parametrize("B,N,k_trans,init_mode", [(3, 2, 2, 2), (5, 3, 3, 2), (9, 40, 14, 1), (9, 40, 41, 1), (10, 65, 2, 1)])
+@pytest.mark.parametrize("with_gains", [False, True])
+def test_against_complex_step_blocks(B, N, k_trans, init_mode, with_gains):
+    """the bar the VJP tests hold this block source to (tests/test_gpu_rollout_vjp.py)"""
+    batch = _batch(B, N, k_trans, init_mode, seed=N + k_trans)
+    nlp, K, Zout, S0, W = _setup(batch, N + 3 * k_trans, with_gains)
+    es, em = _errors(nlp, K, Zout, S0, W, _cs_blocks(nlp))
+    print(f"complex step B={B} N={N} k_trans={k_trans} K={with_gains}: Sigma {es:.2e}, marg {em:.2e}")
+    assert es <= 1e-8 and em <= 1e-8, (es, em)
+
+
+def test_duality_with_the_rollout_vjp():
+    """W = 0: w' Sigma_k w = x0_bar' Sigma_0 x0_bar with x0_bar the VJP of the cotangent w on x_k -- both kernels on the same
+    blocks, neither needs an oracle."""
+    import torch
+
+    from quadruped_landing_amd import nlp as NL
+
+    batch = _batch(9, 40, 14, 1, seed=61)
+    nlp = _nlp(batch)
+    Zref, K, _, Zout, _ = _inputs(nlp, batch, 61, True)
+    rng = np.random.default_rng(62)
+    S0 = CR.random_psd(rng, shape=(nlp.B,))
+    S, _ = nlp.tracking_covariance(Zout, K, S0)
+    Sg = NL.unpack_covariance(S)
+    worst = 0.0
+    for k in (5, 20, nlp.N - 1):  # before the jump knot (12), after it, and the end
+        w = rng.normal(size=(nlp.B, 15))
+        zbar = np.zeros((nlp.B, nlp.n_nlp))
+        zbar[:, 20 * k: 20 * k + 15] = w
+        _, _, xb = nlp.tracking_rollout_vjp(Zref, Zout, nlp.upload_Z(zbar), K, want=("x0",))
+        torch.cuda.synchronize()
+        xb = xb.cpu().numpy()
+        lhs = np.einsum("bi,bij,bj->b", w, Sg[:, k], w)
+        rhs = np.einsum("bi,bij,bj->b", xb, S0, xb)
+        worst = max(worst, float(np.max(np.abs(lhs - rhs) / np.abs(rhs))))
+    print(f"duality with the VJP: worst relative difference {worst:.2e}")
+    assert worst <= 1e-10, worst
+
+
+def test_exactness():
+    import torch
+
+    from quadruped_landing_amd import _lib
+
+    B, N = 13, 12
+    batch = _batch(B, N, 7, 2, seed=71)
+    nlp, K, Zout, S0, W = _setup(batch, 71, True, z_stride=20 * N + 3)
+    L = _lib.lib()
+    # Sigma0 = 0, W = 0: exact zeros everywhere
+    S, mg = nlp.tracking_covariance(Zout, K, np.zeros(15))
+    assert not S.cpu().numpy().any() and not mg.cpu().numpy().any()
+    # K == NULL: exact-zero force variances (and none elsewhere: the other marginals are positive)
+    So, mo = nlp.tracking_covariance(Zout, None, S0, W)
+    assert not mo[:, :, 1:5].cpu().numpy().any() and (mo[:, :, [0, 5, 6, 7]].cpu().numpy()[:, 0] > 0).all()
+    # one shared Sigma0 and the same matrix tiled B times: the same bits
+    S1, m1 = nlp.tracking_covariance(Zout, K, S0[0], W)
+    St, mt = nlp.tracking_covariance(Zout, K, np.broadcast_to(S0[0], (B, 15, 15)), W)
+    assert torch.equal(S1, St) and torch.equal(m1, mt)
+    # either output alone: the same bits as together
+    Sb, mb = nlp.tracking_covariance(Zout, K, S0, W)
+    Sa, none = nlp.tracking_covariance(Zout, K, S0, W, with_marginals=False)
+    assert none is None and torch.equal(Sa, Sb)
+    none, ma = nlp.tracking_covariance(Zout, K, S0, W, with_sigma=False)
+    assert none is None and torch.equal(ma, mb)
+    # W is added behind every step
+    S0w, _ = nlp.tracking_covariance(Zout, K, S0)
+    assert torch.equal(S0w[:, 0], Sb[:, 0]) and not torch.equal(S0w[:, 1], Sb[:, 1])
+    # entries beyond the outputs' extents are untouched
+    ns, nm, pad = B * N * 120, B * N * 8, 257
+    big_s = torch.full((ns + pad,), 7.0, dtype=torch.float64, device="cuda")
+    big_m = torch.full((nm + pad,), 7.0, dtype=torch.float64, device="cuda")
+    s0 = torch.from_numpy(CR.pack(S0)).cuda()
+    _lib.check(L.qln_tracking_covariance(nlp._h, Zout.data_ptr(), K.data_ptr(), s0.data_ptr(), B, W.ctypes.data,
+                                         big_s.data_ptr(), big_m.data_ptr()))
+    torch.cuda.synchronize()
+    assert (big_s[ns:] == 7.0).all() and (big_m[nm:] == 7.0).all()
+    assert torch.equal(big_s[:ns].view(B, N, 120), Sb) and torch.equal(big_m[:nm].view(B, N, 8), mb)
+    # a device tensor of packed tiles is taken as it is
+    Sd, md = nlp.tracking_covariance(Zout, K, s0, W)
+    assert torch.equal(Sd, Sb) and torch.equal(md, mb)
+
+
+def test_argument_validation_on_a_handle():
+    import torch
+
+    from quadruped_landing_amd import _lib
+
+    B, N = 5, 12
+    batch = _batch(B, N, 5, 1, seed=81)
+    nlp, K, Zout, S0, W = _setup(batch, 81, True)
+    L = _lib.lib()
+    bad = _lib.QLN_ERR_INVALID_ARGUMENT
+    s0 = torch.from_numpy(CR.pack(S0)).cuda()
+    S = torch.zeros(B, N, 120, dtype=torch.float64, device="cuda")
+    args = lambda **kw: [kw.get(n, d) for n, d in (("h", nlp._h), ("Z", Zout.data_ptr()), ("K", K.data_ptr()),  # noqa: E731
+                                                    ("s0", s0.data_ptr()), ("nb", B), ("W", W.ctypes.data),
+                                                    ("S", S.data_ptr()), ("m", None))]
+    assert L.qln_tracking_covariance(*args()) == _lib.QLN_OK
+    for nb in (2, B - 1, B + 1):
+        assert L.qln_tracking_covariance(*args(nb=nb)) == bad and b"sigma0_batch" in L.qln_last_error()
+    assert L.qln_tracking_covariance(*args(S=None)) == bad
+    assert L.qln_tracking_covariance(*args(Z=None)) == bad
+    assert L.qln_tracking_covariance(*args(s0=None)) == bad
+    assert L.qln_tracking_covariance(*args(S=s0.data_ptr())) == bad and b"overlaps" in L.qln_last_error()
+    Wb = W.copy()
+    Wb[7] = -1.0
+    with pytest.raises(_lib.QlnError):
+        nlp.tracking_covariance(Zout, K, S0, Wb)
+    with pytest.raises(_lib.QlnError):
+        nlp.tracking_covariance_host(Zout.cpu().numpy(), K.cpu().numpy(), S0, np.where(np.arange(15) == 2, np.nan, W))
+    with pytest.raises(_lib.QlnError):
+        nlp.tracking_covariance(Zout, K, S0, W, with_sigma=False, with_marginals=False)
+    torch.cuda.synchronize()
+
+
+def test_monte_carlo_of_4096_perturbed_drops():
+    """The notebook problem solved by qln_solve, tiled S = 4 096 times, drop states drawn from N(x0, Sigma_0), rolled out
+    closed loop.  For each of 32 fixed directions w the sample variance of w'x_N over w' Sigma_N w is a chi-square variance
+    estimate with relative standard deviation sqrt(2/(S-1)): all 32 ratios lie within 1 +- 5 sqrt(2/(S-1)) = 1 +- 0.1105.
+    Sigma_0 = 1e-8 (G G'/15 + 0.1 I) (standard deviations ~1e-4): on the CPU, with the numpy roll-out and the numpy
+    recursion at the reference's own solution (tests/golden/data_6.csv), this seed gives ratios in [0.952, 1.012], and a
+    Sigma_0 a hundred times larger moves them by 2e-4 -- the second-order terms are three orders below the band."""
+    import torch
+
+    from quadruped_landing_amd import HybridNLP, nlp as NL, problem_gen as PG
+
+    S = 4096
+    nb = PG.notebook_problem()
+    one = HybridNLP(nb.model, nb.obj, nb.init_mode, nb.k_trans, nb.N, nb.x0, nb.xf)
+    Zs = one.upload_Z(nb.Z)
+    one.solve(Zs)
+    K1, _ = one.tracking_lqr(Zs, Q, R, Q)
+    rng = np.random.default_rng(2024)
+    S0 = 1e-8 * (CR.random_psd(rng) + 0.1 * np.eye(15))
+    z = rng.normal(size=(S, 15))
+    W32 = rng.normal(size=(32, 15))
+    Sig, _ = one.tracking_covariance(Zs, K1, S0)
+    SN = NL.unpack_covariance(Sig)[0, -1]
+    torch.cuda.synchronize()
+    zs = Zs.cpu().numpy()[: one.n_nlp]
+    x0 = zs[:15] + z @ np.linalg.cholesky(S0).T
+    rep = lambda a: np.repeat(np.asarray(a), S, axis=0)  # noqa: E731
+    many = HybridNLP(nb.model, nb.obj, rep(nb.init_mode), rep(nb.k_trans), nb.N, rep(nb.x0), rep(nb.xf))
+    Zt = many.upload_Z(np.tile(zs, (S, 1)))
+    Kt = K1.expand(S, -1, -1, -1).contiguous()
+    Zo = many.tracking_rollout(Zt, Kt, torch.from_numpy(x0).cuda())
+    torch.cuda.synchronize()
+    xN = Zo.view(S, -1)[:, 20 * (nb.N - 1): 20 * (nb.N - 1) + 15].cpu().numpy()
+    assert np.isfinite(xN).all()
+    band = 5.0 * np.sqrt(2.0 / (S - 1))
+    ratio = np.array([np.var(xN @ w, ddof=1) / (w @ SN @ w) for w in W32])
+    print(f"Monte Carlo: ratios in [{ratio.min():.4f}, {ratio.max():.4f}], band 1 +- {band:.4f}")
+    assert (np.abs(ratio - 1.0) <= band).all(), ratio
+
+
+@pytest.mark.parametrize("B,N,ragged", [(65536, 40, False), (65536, 80, True)])
+def test_full_size_every_problem(B, N, ragged):
+    from quadruped_landing_amd import nlp as NL, problem_gen as PG
+
+    full = PG.make_batch(B, N, 14, 1, seed=2, ragged=ragged)
+    worst = [0.0, 0.0]
+    chunk = 4096
+    for s in range(0, B, chunk):
+        sub = PG.LandingBatch(full.model, N, full.k_trans[s:s + chunk], full.init_mode[s:s + chunk], full.x0[s:s + chunk],
+                              full.xf[s:s + chunk], full.obj if full.obj.ndim == 2 else full.obj[s:s + chunk],
+                              full.Z[s:s + chunk])
+        nlp, K, Zout, S0, W = _setup(sub, s, True)
+        S, mg = nlp.tracking_covariance(Zout, K, S0, W)
+        Sg, mgg = NL.unpack_covariance(S), mg.cpu().numpy()
+        # the recursion vectorised over the chunk
+        F = _dense_blocks(nlp, Zout)
+        kj = nlp.k_trans.astype(int) - 2
+        for b in np.nonzero((kj >= 0) & (kj < N - 1))[0]:
+            F[b, kj[b], 14, 14] = 1.0
+        Kh = K.cpu().numpy()
+        Sr = CR.propagate(F[..., :15], F[..., 15:19], Kh, S0, W)
+        theta = _host(nlp, Zout)[:, 2 + 20 * np.arange(N)]
+        mr = CR.marginals(Sr, Kh, theta, nlp.model.lb)
+        worst = [max(worst[0], CR.knot_rel(Sg, Sr)), max(worst[1], CR.entry_rel(mgg, mr))]
+        assert np.array_equal(Sg, np.swapaxes(Sg, -1, -2))
+        del nlp, F, Sr
+    print(f"full size B={B} N={N} ragged={ragged}: worst per-knot rel err Sigma {worst[0]:.2e}, worst marg entry {worst[1]:.2e}")
+    assert worst[0] <= BAR and worst[1] <= BAR, worst
+
+
+@pytest.mark.parametrize("B", [5, 1024])  # mapped pinned buffers (small batch) and staged device copies
+def test_host_forms_give_the_device_forms_bits(B):
+    N = 12
+    batch = _batch(B, N, 5, 2, seed=91)
+    nlp, K, Zout, S0, W = _setup(batch, 91, True, z_stride=20 * N + 3)
+    S, mg = nlp.tracking_covariance(Zout, K, S0, W)
+    So, mo = nlp.tracking_covariance(Zout, None, S0[0], W)
+    Sd, md, Sod, mod = (t.cpu().numpy() for t in (S, mg, So, mo))
+    zo, Kh = Zout.cpu().numpy(), K.cpu().numpy()
+    # other host entry points first, on NaN inputs: their result buffers now hold NaN, and none of it may come back here
+    nan_z = np.full(nlp.dims.z_total, np.nan)
+    Kn, Pn = nlp.tracking_lqr_host(nan_z, Q, R, Q)
+    zb, kb, xb = nlp.tracking_rollout_vjp_host(nan_z, nan_z, nan_z, np.full(Kh.shape, np.nan))
+    assert np.isnan(Kn).all() and np.isnan(Pn[:, :-1]).all() and np.isnan(kb).all() and np.isnan(xb).all()  # P_N = Qf
+    for _ in range(2):  # the second call reuses the handle's buffers
+        Sh, mh = nlp.tracking_covariance_host(zo, Kh, S0, W)
+        assert np.array_equal(Sh, Sd) and np.array_equal(mh, md)
+        Sh, mh = nlp.tracking_covariance_host(zo, None, S0[0], W)
+        assert np.array_equal(Sh, Sod) and np.array_equal(mh, mod)
+    Sh, none = nlp.tracking_covariance_host(zo, Kh, S0, W, with_marginals=False)
+    assert none is None and np.array_equal(Sh, Sd)
+    none, mh = nlp.tracking_covariance_host(zo, Kh, S0, W, with_sigma=False)
+    assert none is None and np.array_equal(mh, md)
