@@ -26,10 +26,11 @@
  * <= 8 MiB is evaluated on pinned host buffers mapped into the device's address space (the kernels read and write them
  * directly: one launch, one synchronisation), a larger one is staged through device memory.
  * qln_eval_hessian_lagrangian_host and qln_solve_host are always staged.  The handle allocates each buffer on first
- * use, zero-filled, and keeps it until qln_destroy.  Three arguments are in-out and copied in whole, so that their
+ * use, zero-filled, and keeps it until qln_destroy.  Four arguments are in-out and copied in whole, so that their
  * entries from n_nlp to z_stride come back as the caller's buffer held them: Zout of qln_tracking_rollout_host,
- * Zref_bar of qln_tracking_rollout_vjp_host and Z of qln_solve_host.  The padding of every other result (past n_nlp in
- * the layout of Z, between the problems of c, vals and hvals) comes back as zeros.
+ * Zref_bar of qln_tracking_rollout_vjp_host, Zout_dot of qln_tracking_rollout_jvp_host and Z of qln_solve_host.  The
+ * padding of every other result (past n_nlp in the layout of Z, between the problems of c, vals and hvals) comes back as
+ * zeros.
  *
  * Layouts (all FP64, all offsets/strides in doubles):
  *   Z     problem b at Z + b*z_stride, length n_nlp = 20N-5,
@@ -432,6 +433,34 @@ int qln_tracking_rollout_vjp(qln_handle* h, const double* Zref, const double* K,
 /* the same as a host form (see "Host forms" above; Zref_bar is in-out) */
 int qln_tracking_rollout_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
                                   double* Zref_bar, double* K_bar, double* x0_bar);
+/* Forward-mode derivative (Jacobian-vector product) of qln_tracking_rollout: the tangent of Zout along a direction
+ * (Zref_dot, K_dot, x0_dot) of the inputs, at the trajectory Zout holds.  Knots are 0-based, k = 0..N-2, and the forward map,
+ * Phi_k and the blocks are those of qln_tracking_rollout_vjp: [A_k B_k] = d Phi_k / d(x_k, u_k) at Zout's (x_k, u_k) is the
+ * evaluator's closed-form 15 x 20 step block, the h column included, and at the jump knot row 14 is the jump map's (1 at
+ * x[14] and 1 at h), not quirk Q1's masked zero.  The linearisation points are Zout's: the roll-out is not re-run, and
+ * nothing checks that Zout is the roll-out of (Zref, K, x0).  The sweep is
+ *   dx_0 = x0_dot[b]                                                  (zeros if x0_dot == NULL)
+ *   for k = 0 .. N-2:
+ *     e_k  = x_k - x_ref,k                                            (Zout's x_k, Zref's x_ref,k)
+ *     dF_k = Fref_dot_k - K_k (dx_k - xref_dot_k) - Kdot_k e_k        (4)
+ *     dh_k = href_dot_k
+ *     Zout_dot[u_k] = (dF_k, dh_k)
+ *     dx_{k+1} = A_k dx_k + B_k (dF_k, dh_k)
+ *   Zout_dot[x_k] = dx_k,  k = 0..N-1
+ * where every term with K, K_dot, Zref_dot or x0_dot equal to NULL is an exact zero, and xref_dot_{N-1} is never read.  It
+ * is the exact adjoint of qln_tracking_rollout_vjp: <Zbar, Zout_dot> = <Zref_bar, Zref_dot> + <K_bar, K_dot> + <x0_bar, x0_dot>.
+ * Tangents (each may be NULL; all three NULL is QLN_ERR_INVALID_ARGUMENT):
+ *   Zref_dot: layout of Z (entries from n_nlp to z_stride are not read).
+ *   K_dot:    [B][N-1][4][15], the layout of K.  QLN_ERR_INVALID_ARGUMENT if K == NULL and K_dot != NULL.
+ *   x0_dot:   [B][15].
+ * Zout_dot: layout of Z.  Every entry below n_nlp is written; entries from n_nlp to z_stride never.  It must overlap no
+ * input.  Zref is read for K_dot only (the states x_ref,k); it must still be non-NULL.  Every N >= 2, k_trans in [1, N+1]
+ * and init_mode, as the forward call.  Device pointers, stream-ordered; needs no cost table. */
+int qln_tracking_rollout_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zref_dot,
+                             const double* K_dot, const double* x0_dot, double* Zout_dot);
+/* the same as a host form (see "Host forms" above; Zout_dot is in-out) */
+int qln_tracking_rollout_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                  const double* Zref_dot, const double* K_dot, const double* x0_dot, double* Zout_dot);
 /* Covariance propagation through the closed-loop roll-out: the linear-Gaussian forward sweep along the trajectory Zout
  * holds.  Knots are 0-based, k = 0..N-2, as in qln_tracking_rollout_vjp.
  *   A_k (15x15), B_k (15x4) = d Phi_k / d(x_k, F_k) at Zout's (x_k, u_k): exactly the blocks qln_tracking_rollout_vjp uses --

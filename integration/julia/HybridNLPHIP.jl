@@ -194,6 +194,18 @@ function tracking_rollout_vjp(prob::HybridNLPHIP, Zref::Vector{Float64}, Zout::V
                     x0_bar))
     return Zref_bar, K_bar, x0_bar
 end
+# forward sweep of tracking_rollout at the trajectory Zout: the tangents Zref_dot (layout of Z), K_dot (size of K, needs K) and
+# x0_dot (15 values) -- each nothing for zero, at least one given -- -> Zout_dot, the tangent of Zout's states and applied
+# controls.  The adjoint of tracking_rollout_vjp.  include/qln_evaluator.h, DESIGN.md 4.14
+function tracking_rollout_jvp(prob::HybridNLPHIP, Zref::Vector{Float64}, Zout::Vector{Float64}; K=nothing, Zref_dot=nothing,
+                              K_dot=nothing, x0_dot=nothing)
+    Zout_dot = zeros(length(Zref))
+    qln_check(ccall((:qln_tracking_rollout_jvp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, K === nothing ? C_NULL : K, Zout, Zref_dot === nothing ? C_NULL : Zref_dot,
+                    K_dot === nothing ? C_NULL : K_dot, x0_dot === nothing ? C_NULL : x0_dot, Zout_dot))
+    return Zout_dot
+end
 # covariance of the roll-out's states along the trajectory Zout (for the nominal case: the reference itself):
 # Sigma_0 = Sigma0, Sigma_{k+1} = (A_k - B_k K_k) Sigma_k (A_k - B_k K_k)' + diag(W); K = nothing is the open loop.
 # Sigma0: a 15x15 matrix (its lower triangle is read); W: 15 variances or nothing (zeros).  Returns Sigma as (120, N) packed

@@ -150,6 +150,8 @@ SIGNATURES = {
     "qln_tracking_rollout_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     "qln_tracking_rollout_vjp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "qln_tracking_rollout_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "qln_tracking_rollout_jvp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "qln_tracking_rollout_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "qln_tracking_covariance": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp]),
     "qln_tracking_covariance_host": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp]),
     "qln_eval_constraint_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp]),

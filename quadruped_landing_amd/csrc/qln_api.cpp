@@ -79,7 +79,8 @@ enum HostRole {
     kZ,      // in: the point Z / Zref (in-out of qln_solve_host)           layout of Z
     kV,      // in: a direction v, the vjp's Zout                           layout of Z
     kZbar,   // in: the vjp's cotangent Zbar                                layout of Z
-    kZio,    // in-out: the roll-out's Zout, the vjp's Zref_bar             layout of Z
+    kZio,    // in-out: the roll-out's Zout, the vjp's Zref_bar, the jvp's Zout_dot  layout of Z
+    kZdot,   // in: the jvp's tangent Zref_dot                              layout of Z
     kZout,   // out: H v, J' lam (padding zero)                             layout of Z
     kGrad,   // out: grad f                                                 layout of Z
     kC,      // out: c, J v (padding zero)                                  layout of c
@@ -90,6 +91,7 @@ enum HostRole {
     kHvals,  // out: the Hessian values                                     (B-1) h_stride + nnz
     kK,      // out of the LQR, in to the roll-out and its vjp: the gains   [B][N-1][4][15]
     kKbar,   // out: the gains' cotangent                                   layout of K
+    kKdot,   // in: the jvp's tangent K_dot                                 layout of K
     kP,      // out: the cost-to-go                                         [B][N][120]
     kX0,     // in: the roll-out's x0; out: the vjp's x0_bar                [B][15]
     kCov0,   // in: the covariance sweep's Sigma0 (1 or B tiles used)       [B][120]
@@ -158,12 +160,12 @@ int upload(T** dst, const T* src, size_t n) {
 int64_t host_role_size(const qln_handle* h, HostRole r) {
     const qln_dims& D = h->dims;
     switch (r) {
-        case kZ: case kV: case kZbar: case kZio: case kZout: case kGrad: return D.z_total;
+        case kZ: case kV: case kZbar: case kZio: case kZdot: case kZout: case kGrad: return D.z_total;
         case kC: case kMu: return D.c_total;
         case kVals: return D.j_total;
         case kF: case kSigma: return D.B;
         case kHvals: return (int64_t)(D.B - 1) * h->h_stride + hessian_nnz(D.N);  // no padding behind the last problem
-        case kK: case kKbar: return tracking_k_total(D);
+        case kK: case kKbar: case kKdot: return tracking_k_total(D);
         case kP: case kCov: return tracking_p_total(D);
         case kCov0: return (int64_t)D.B * QLN_TRACK_P_NNZ;
         case kMarg: return tracking_marg_total(D);
@@ -1137,6 +1139,51 @@ int qln_tracking_rollout_vjp_host(qln_handle* h, const double* Zref, const doubl
                      [&](double* const* d, bool) {
                          return qln::launch_tracking_rollout_vjp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kZbar], d[kZio],
                                                                  d[kKbar], d[kX0], h->stream);
+                     });
+}
+
+// the roll-out's forward sweep (k_tracking_rollout_jvp).  The checks that need no handle come first.
+static int check_tracking_jvp_args(const qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                   const double* Zref_dot, const double* K_dot, const double* x0_dot, const double* Zout_dot,
+                                   const char* who) {
+    const std::string w(who);
+    if (!Zref_dot && !K_dot && !x0_dot)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Zref_dot, K_dot and x0_dot are all NULL (no direction)");
+    if (K_dot && !K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_dot needs K (K == NULL has no gains to perturb)");
+    if (!Zref || !Zout || !Zout_dot) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref, Zout or Zout_dot");
+    if (int rc = check_handle(h)) return rc;
+    const qln_dims& D = h->dims;
+    const int64_t nz = D.z_total, nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX;
+    const struct {
+        const double* p;
+        int64_t n;
+    } in[] = {{Zref, nz}, {K, nk}, {Zout, nz}, {Zref_dot, nz}, {K_dot, nk}, {x0_dot, nx}};
+    for (const auto& i : in)
+        if (overlaps(Zout_dot, nz, i.p, i.n)) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Zout_dot overlaps an input");
+    return QLN_OK;
+}
+
+int qln_tracking_rollout_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zref_dot,
+                             const double* K_dot, const double* x0_dot, double* Zout_dot) {
+    if (int rc = check_tracking_jvp_args(h, Zref, K, Zout, Zref_dot, K_dot, x0_dot, Zout_dot, "qln_tracking_rollout_jvp"))
+        return rc;
+    if (int rc = bind_device(h)) return rc;
+    QLN_HIP(qln::launch_tracking_rollout_jvp(h->p, Zref, K, Zout, Zref_dot, K_dot, x0_dot, Zout_dot, h->stream));
+    return QLN_OK;
+}
+
+// Zref is staged only when K_dot is given (the kernel reads it for nothing else); otherwise Zout's buffer stands in.
+int qln_tracking_rollout_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                  const double* Zref_dot, const double* K_dot, const double* x0_dot, double* Zout_dot) {
+    if (int rc = check_tracking_jvp_args(h, Zref, K, Zout, Zref_dot, K_dot, x0_dot, Zout_dot, "qln_tracking_rollout_jvp_host"))
+        return rc;
+    if (int rc = bind_device(h)) return rc;
+    return host_call(h,
+                     {copy_in(kV, Zout), copy_in(kZ, K_dot ? Zref : nullptr), copy_in(kK, K), copy_in(kZdot, Zref_dot),
+                      copy_in(kKdot, K_dot), copy_in(kX0, x0_dot), copy_inout(kZio, Zout_dot)},
+                     [&](double* const* d, bool) {
+                         return qln::launch_tracking_rollout_jvp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kZdot], d[kKdot],
+                                                                 d[kX0], d[kZio], h->stream);
                      });
 }
 

@@ -300,6 +300,11 @@ hipError_t launch_tracking_rollout(const BatchParams& p, const double* Zref, con
 // needs K and reads Zref's states) (qln_tracking_kernels.hip)
 hipError_t launch_tracking_rollout_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
                                        const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, hipStream_t stream);
+// the roll-out's forward (tangent) sweep at Zout's trajectory: tangents Zref_dot, K_dot, x0_dot (each may be null: zero; K_dot
+// needs K and reads Zref's states) -> Zout_dot in the layout of Z (qln_tracking_kernels.hip)
+hipError_t launch_tracking_rollout_jvp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
+                                       const double* Zref_dot, const double* K_dot, const double* x0_dot, double* Zout_dot,
+                                       hipStream_t stream);
 // Sigma_{k+1} = (A_k - B_k K_k) Sigma_k (A_k - B_k K_k)' + diag(Wd) along Zout (K null: open loop); Sigma0 [sigma0_batch][120],
 // Wd a host array (null: zeros); Sigma [B][N][120] and marg [B][N][8], either may be null (qln_tracking_kernels.hip)
 hipError_t launch_tracking_covariance(const BatchParams& p, const double* Zout, const double* K, const double* Sigma0,

@@ -43,9 +43,16 @@
 // Expanded, that is A Sigma A' - (A G')B' - B (G A') + B M B' with G = K Sigma and M = G K', grouped so that nothing but
 // K v crosses lanes.  Zout's knot (two coalesced loads, handed out through LDS) and the K tile are loaded one knot ahead;
 // the clearance row's cosine is taken for sixteen knots at a time, one per lane.
+//
+// k_tracking_rollout_jvp: the forward (tangent) sweep of the roll-out, the adjoint of the reverse sweep in
+// its mapping: one problem per row of sixteen lanes, lane j < 15 owns dx[j], row j of [A_k B_k] and column j of K and Kdot;
+// nothing goes through LDS.  Every lane forms the knot's StepBlock (Zout's knot: two coalesced loads, handed round by DPP
+// row broadcasts) and picks its row's entries from the visitor; (A dx)[j] is the diagonal, the coupling A(j, j+7) through a
+// row shift, and for the dense rows 2 and 9 two row sums; K (dx - xref_dot) + Kdot e is four more.
 #include "qln_kernel_common.h"
 
 #include <cstdlib>
+#include <utility>
 
 namespace qln {
 namespace {
@@ -736,6 +743,150 @@ __global__ __launch_bounds__(kWave) void k_tracking_covariance(BatchParams P, Co
     emit(N - 1, fv0);
 }
 
+
+// ---- k_tracking_rollout_jvp ----
+// v from lane i of the same DPP row (row_newbcast), in every lane of the row
+template <int kLaneInRow>
+__device__ __forceinline__ double row_bcast(double v) {
+    return dpp_f64_bc<0x150 + kLaneInRow>(v);
+}
+template <int... I>
+__device__ __forceinline__ void row_bcast_first(double v, double (&out)[sizeof...(I)], std::integer_sequence<int, I...>) {
+    ((out[I] = row_bcast<I>(v)), ...);
+}
+
+// One knot's inputs, as lane ln of a row loads them.  z0 / zd0: entry ln of the knot's twenty in Zout / Zref_dot (lane
+// j < 15: x_j, lane 15: F1x); z1 / zd1: entry 16 + (ln & 3) (F1y, F2x, F2y, h in lanes 0-3).  xr: x_ref,j; kc, kd: column j
+// of K_k and of Kdot_k.
+struct JvpKnot {
+    double z0, z1, zd0, zd1, xr, kc[4], kd[4];
+};
+
+template <bool kHasK, bool kHasKd, bool kHasZd>
+__device__ __forceinline__ void jvp_load(JvpKnot& s, const double* __restrict__ Zo, const double* __restrict__ Zd,
+                                         const double* __restrict__ Zr, const double* __restrict__ Kk,
+                                         const double* __restrict__ Kdk, int k, int ln, int j) {
+    s.z0 = Zo[20 * k + ln];
+    s.z1 = Zo[20 * k + 16 + (ln & 3)];
+    if constexpr (kHasZd) {
+        s.zd0 = Zd[20 * k + ln];
+        s.zd1 = Zd[20 * k + 16 + (ln & 3)];
+    }
+    if constexpr (kHasK) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) s.kc[m] = Kk[60 * (int64_t)k + 15 * m + j];
+    }
+    if constexpr (kHasKd) {
+        s.xr = Zr[20 * k + j];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) s.kd[m] = Kdk[60 * (int64_t)k + 15 * m + j];
+    }
+}
+
+// The forward (tangent) sweep of k_tracking_rollout (include/qln_evaluator.h): dx_0 = x0_dot, then per knot k = 0..N-2
+//   dF_k = Fref_dot_k - K_k (dx_k - xref_dot_k) - Kdot_k (x_k - x_ref,k),  dh_k = href_dot_k,
+//   dx_{k+1} = A_k dx_k + B_k (dF_k, dh_k),
+// with the blocks of the reverse sweep: the evaluator's closed form at Zout's (x_k, u_k), the jump knot's clock row kept.
+// One problem per row of sixteen lanes; lane j < 15 owns dx[j], row j of [A_k B_k] and column j of K_k and Kdot_k, lane 15
+// holds dx = 0 and only stores a u slot.  Every lane of the row forms the knot's StepBlock alike -- Zout's knot arrives as two
+// coalesced loads and is handed round by DPP row broadcasts -- and picks its row's entries from the visitor: the diagonal
+// and the velocity coupling A(j, j+7) (dx[j+7] by a row shift), B row j, and the h column's entry.  Rows 2 and 9 of A are
+// dense: lane c contributes A(2, c) dx_c and A(9, c) dx_c to two row sums; K (dx - xref_dot) + Kdot e is four more.
+// Template flags say which inputs exist: nothing that is absent is read (Zref only with Kdot).
+template <bool kHasK, bool kHasKd, bool kHasZd>
+__global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, const double* __restrict__ Zref,
+                                                                const double* __restrict__ Kg, const double* __restrict__ Zout,
+                                                                const double* __restrict__ Zref_dot,
+                                                                const double* __restrict__ Kdot,
+                                                                const double* __restrict__ x0_dot,
+                                                                double* __restrict__ Zout_dot) {
+    static_assert(kHasK || !kHasKd, "Kdot needs K");
+    const int lane = threadIdx.x;
+    const int ln = lane & 15, row = lane >> 4;
+    const bool own = ln < 15;
+    const int j = own ? ln : 14;  // lane 15 reads lane 14's slots and contributes nothing
+    const int wave = xcd_contiguous_index(blockIdx.x, (P.B + kRows - 1) / kRows);
+    const int b = wave * kRows + row;
+    const bool valid = b < P.B;
+    const int bc = valid ? b : P.B - 1;
+    const int N = P.N;
+    const ProblemDesc pd = P.desc[bc];
+    const int kt = pd.k_trans, im = pd.init_mode;
+    const Model M(P);
+    const int64_t zo = (int64_t)bc * P.z_stride, ko = (int64_t)bc * (N - 1) * (QLN_TRACK_NU * QLN_NX);
+    const double* __restrict__ Zo = Zout + zo;
+    const double* __restrict__ Zd = kHasZd ? Zref_dot + zo : nullptr;
+    const double* __restrict__ Zr = kHasKd ? Zref + zo : nullptr;
+    const double* __restrict__ Kb = kHasK ? Kg + ko : nullptr;
+    const double* __restrict__ Kdb = kHasKd ? Kdot + ko : nullptr;
+    double* __restrict__ Od = Zout_dot + zo;
+
+    double dx = (own && x0_dot) ? x0_dot[(int64_t)bc * QLN_NX + j] : 0.0;
+    JvpKnot cur, nxt;
+    jvp_load<kHasK, kHasKd, kHasZd>(nxt, Zo, Zd, Zr, Kb, Kdb, 0, ln, j);
+    for (int k = 0; k < N - 1; ++k) {
+        cur = nxt;
+        if (k + 1 < N - 1) jvp_load<kHasK, kHasKd, kHasZd>(nxt, Zo, Zd, Zr, Kb, Kdb, k + 1, ln, j);
+        // ---- the knot's block, in every lane ----
+        double x[14];
+        row_bcast_first(cur.z0, x, std::make_integer_sequence<int, 14>{});
+        const double F1x = row_bcast<15>(cur.z0), F1y = row_bcast<0>(cur.z1), F2x = row_bcast<1>(cur.z1),
+                     F2y = row_bcast<2>(cur.z1), h = row_bcast<3>(cur.z1);
+        const StepBlock blk = step_block(x, F1x, F1y, F2x, F2y, h, knot_mode(k + 1, kt - 1, im), M);
+        // ---- the applied controls' tangent: dF = Fref_dot - K (dx - xref_dot) - Kdot e, dh = href_dot ----
+        double dF[4], dh = 0.0, xrd = 0.0;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) dF[m] = 0.0;
+        if constexpr (kHasZd) {
+            xrd = cur.zd0;
+            dF[0] = row_bcast<15>(cur.zd0);
+            dF[1] = row_bcast<0>(cur.zd1);
+            dF[2] = row_bcast<1>(cur.zd1);
+            dF[3] = row_bcast<2>(cur.zd1);
+            dh = row_bcast<3>(cur.zd1);
+        }
+        if constexpr (kHasK) {
+            const double d = dx - xrd;
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                double t = cur.kc[m] * d;
+                if constexpr (kHasKd) t = fma(cur.kd[m], cur.z0 - cur.xr, t);
+                dF[m] = dF[m] - row_sum16_bc(own ? t : 0.0);
+            }
+        }
+        // ---- row j of [A B]: the visitor's entries at the lane's row (rows 2 and 9 of A: at the lane's column) ----
+        // row 14 of the jump knot: the jump map keeps the clock (its Jacobian's mask zeroes the row, quirk Q1)
+        double a2 = 0.0, a9 = 0.0, dg = 0.0, cp = 0.0, bj[4] = {0.0, 0.0, 0.0, 0.0}, hj = 0.0;
+        for_each_step_entry(blk, [&](auto r, auto c, double val) {
+            if constexpr (c < 15) {
+                if constexpr (r == 2) a2 = (j == c) ? val : a2;
+                else if constexpr (r == 9) a9 = (j == c) ? val : a9;
+                else if constexpr (r == c) dg = (j == r) ? ((r == 14) ? 1.0 : val) : dg;
+                else cp = (j == r) ? val : cp;  // r == c - 7 (a_structure_ok)
+            } else if constexpr (kHasK || kHasZd) {
+                if constexpr (c < 19) bj[c - 15] = (j == r) ? val : bj[c - 15];
+                else hj = (j == r) ? ((r == 14) ? 1.0 : val) : hj;
+            }
+        });
+        const double dxc = dpp_f64_bc<0x107>(dx);  // row_shl:7, dx[j+7] (0 past the row's end: bound_ctrl)
+        const double s2 = row_sum16_bc(own ? a2 * dx : 0.0), s9 = row_sum16_bc(own ? a9 * dx : 0.0);
+        double acc = (j == 2) ? s2 : (j == 9) ? s9 : fma(cp, dxc, dg * dx);
+        if constexpr (kHasK || kHasZd) {
+#pragma unroll
+            for (int m = 0; m < 4; ++m) acc = fma(bj[m], dF[m], acc);
+            if constexpr (kHasZd) acc = fma(hj, dh, acc);
+        }
+        // ---- the knot's twenty entries of Zout_dot: dx_k and (dF_k, dh_k) ----
+        if (valid) {
+            double* __restrict__ o = Od + 20 * k;
+            o[ln] = own ? dx : dF[0];
+            if (ln < 4) o[16 + ln] = ln == 0 ? dF[1] : ln == 1 ? dF[2] : ln == 2 ? dF[3] : dh;
+        }
+        dx = own ? acc : 0.0;
+    }
+    if (valid && own) Od[20 * (N - 1) + j] = dx;
+}
+
 }  // namespace
 
 hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const double* Rd, const double* Qfd, const double* Zref,
@@ -773,6 +924,24 @@ hipError_t launch_tracking_rollout_vjp(const BatchParams& p, const double* Zref,
         hipLaunchKernelGGL(kern, dim3(xcd_grid(waves)), dim3(kWave), 0, stream, p, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar);
     };
     K ? go(k_tracking_rollout_vjp<true>) : go(k_tracking_rollout_vjp<false>);
+    return hipGetLastError();
+}
+
+hipError_t launch_tracking_rollout_jvp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
+                                       const double* Zref_dot, const double* K_dot, const double* x0_dot, double* Zout_dot,
+                                       hipStream_t stream) {
+    if (K_dot && !K) return hipErrorInvalidValue;
+    const int waves = (p.B + kRows - 1) / kRows;
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(xcd_grid(waves)), dim3(kWave), 0, stream, p, Zref, K, Zout, Zref_dot, K_dot, x0_dot,
+                           Zout_dot);
+    };
+    if (K_dot)
+        Zref_dot ? go(k_tracking_rollout_jvp<true, true, true>) : go(k_tracking_rollout_jvp<true, true, false>);
+    else if (K)
+        Zref_dot ? go(k_tracking_rollout_jvp<true, false, true>) : go(k_tracking_rollout_jvp<true, false, false>);
+    else
+        Zref_dot ? go(k_tracking_rollout_jvp<false, false, true>) : go(k_tracking_rollout_jvp<false, false, false>);
     return hipGetLastError();
 }
 

@@ -651,6 +651,39 @@ class HybridNLP:
                                                             Zbar.ctypes.data, _host_ptr(zb), _host_ptr(kb), _host_ptr(xb)))
         return zb, kb, xb
 
+    # -- forward-mode derivative of the closed-loop roll-out ---------------------------------------
+    def tracking_rollout_jvp(self, Zref, Zout, K=None, Zref_dot=None, K_dot=None, x0_dot=None, out=None):
+        """Forward sweep of tracking_rollout at the trajectory Zout (device tensors): the tangents Zref_dot (layout of Z),
+        K_dot (B, N-1, 4, 15) and x0_dot (B, 15) -- each None for zero, at least one given, K_dot only with K -- to the
+        tangent Zout_dot of Zout's states and applied controls, in the layout of Z (zeros past n_nlp on a fresh buffer; out
+        must overlap no input).  Stream-ordered; semantics in include/qln_evaluator.h."""
+        nk = self.B * (self.N - 1) * _lib.TRACK_NU * n
+        self._check(Zref, self.dims.z_total, "Zref")
+        self._check(Zout, self.dims.z_total, "Zout")
+        kp = None if K is None else self._check(K, nk, "K")
+        zd = None if Zref_dot is None else self._check(Zref_dot, self.dims.z_total, "Zref_dot")
+        kd = None if K_dot is None else self._check(K_dot, nk, "K_dot")
+        xd = None if x0_dot is None else self._check(x0_dot, self.B * n, "x0_dot")
+        out = self.new_Z() if out is None else out
+        self._check(out, self.dims.z_total, "out")
+        _lib.check(_lib.lib().qln_tracking_rollout_jvp(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), zd, kd, xd,
+                                                       out.data_ptr()))
+        return out
+
+    def tracking_rollout_jvp_host(self, Zref, Zout, K=None, Zref_dot=None, K_dot=None, x0_dot=None):
+        """The same with host arrays (synchronous): returns a (z_total,) numpy array (zeros past n_nlp)."""
+        Zref, Zout = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout")
+        K, K_dot = self._host_K(K), self._host_K(K_dot)
+        if Zref_dot is not None:
+            Zref_dot = self._host_Z(Zref_dot, "Zref_dot")
+        if x0_dot is not None:
+            x0_dot = np.ascontiguousarray(np.broadcast_to(np.asarray(x0_dot, dtype=np.float64), (self.B, n)))
+        out = np.zeros(self.dims.z_total)
+        _lib.check(_lib.lib().qln_tracking_rollout_jvp_host(self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data,
+                                                            _host_ptr(Zref_dot), _host_ptr(K_dot), _host_ptr(x0_dot),
+                                                            out.ctypes.data))
+        return out
+
     # -- covariance propagation through the closed-loop roll-out -----------------------------------
     def tracking_covariance(self, Zout, K=None, Sigma0=None, W=None, with_sigma=True, with_marginals=True, Sigma=None,
                             marg=None):
@@ -702,7 +735,8 @@ class HybridNLP:
 
     def differentiable_rollout(self, Zref, K=None, x0=None):
         """tracking_rollout as a torch autograd op: returns Zout, differentiable in Zref, K and x0 (each a float64 CUDA
-        tensor or None).  The backward pass is one qln_tracking_rollout_vjp launch at the Zout the forward produced."""
+        tensor or None).  The backward pass is one qln_tracking_rollout_vjp launch at the Zout the forward produced, a
+        forward-mode tangent (torch.autograd.forward_ad, torch.func.jvp) one qln_tracking_rollout_jvp launch."""
         from .rollout_grad import RolloutFunction
 
         return RolloutFunction.apply(self, Zref, K, x0)

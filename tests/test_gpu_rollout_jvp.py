@@ -1,0 +1,278 @@
+"""GPU checks of qln_tracking_rollout_jvp and the forward-mode side of HybridNLP.differentiable_rollout: the numpy forward
+sweep on the evaluator's own blocks and on complex-step blocks over the tracking shapes and at full size, the adjoint
+identity with the shipped reverse sweep, central differences of the GPU roll-out entry by entry, the duality with the
+covariance sweep, torch forward-mode AD, and the call's contract."""
+import numpy as np
+import pytest
+
+from tests import rollout_jvp_ref as RJ
+from tests import rollout_vjp_ref as RV
+from tests.test_gpu_rollout_vjp import _cs_blocks, _evaluator_blocks, _gains, _inputs
+from tests.test_gpu_tracking import SHAPES, _batch, _dense_blocks, _nlp
+
+pytestmark = pytest.mark.gpu
+
+
+def _tangents(nlp, seed, with_gains, scale=(1.0, 1.0, 1.0)):
+    """Random tangents of Zref (zero past n_nlp), K (None without gains) and x0, as device tensors."""
+    import torch
+
+    rng = np.random.default_rng(seed)
+    zd = nlp.upload_Z(scale[0] * rng.normal(size=(nlp.B, nlp.n_nlp)))
+    kd = torch.from_numpy(scale[1] * rng.normal(size=(nlp.B, nlp.N - 1, 4, 15))).cuda() if with_gains else None
+    xd = torch.from_numpy(scale[2] * rng.normal(size=(nlp.B, 15))).cuda()
+    return zd, kd, xd
+
+
+def _rows(nlp, t):
+    return t.view(nlp.B, -1)[:, :nlp.n_nlp].cpu().numpy()
+
+
+def _per_problem(nlp, Zref, K, Zout, zd, kd, xd, got, blocks):
+    """worst per-problem relative norm of Zout_dot against the numpy sweep on blocks(b, Zout_b)"""
+    zr, zo, g = _rows(nlp, Zref), _rows(nlp, Zout), _rows(nlp, got)
+    zdh = None if zd is None else _rows(nlp, zd)
+    Kh, kdh, xdh = (None if t is None else t.cpu().numpy() for t in (K, kd, xd))
+    worst = 0.0
+    for b in range(nlp.B):
+        ref = RJ.sweep(blocks(b, zo[b]), zr[b], None if Kh is None else Kh[b], zo[b], None if zdh is None else zdh[b],
+                       None if kdh is None else kdh[b], None if xdh is None else xdh[b])
+        worst = max(worst, RV.rel(g[b], ref))
+    return worst
+
+
+@pytest.mark.parametrize("B,N,k_trans,init_mode", SHAPES)
+@pytest.mark.parametrize("with_gains", [False, True])
+def test_matches_numpy_sweep_over_shapes(B, N, k_trans, init_mode, with_gains):
+    batch = _batch(B, N, k_trans, init_mode, seed=N + k_trans)
+    nlp = _nlp(batch)
+    Zref, K, x0, Zout, _ = _inputs(nlp, batch, N + 3 * k_trans, with_gains)
+    zd, kd, xd = _tangents(nlp, N + 5 * k_trans, with_gains)
+    got = nlp.tracking_rollout_jvp(Zref, Zout, K, zd, kd, xd)
+    ev = _per_problem(nlp, Zref, K, Zout, zd, kd, xd, got, _evaluator_blocks(nlp, Zout))
+    cs = _per_problem(nlp, Zref, K, Zout, zd, kd, xd, got, _cs_blocks(nlp))
+    print(f"B={B} N={N} k_trans={k_trans} mode={init_mode} K={with_gains}: evaluator blocks {ev:.2e}, complex step {cs:.2e}")
+    assert ev <= 1e-12 and cs <= 1e-8, (ev, cs)
+
+
+@pytest.mark.parametrize("with_gains", [False, True])
+def test_ragged_batch_and_padded_layout(with_gains):
+    for batch, kw in ((_batch(37, 12, 5, 1, seed=3, ragged=True), {}),
+                      (_batch(13, 12, 7, 2, seed=4), {"z_stride": 20 * 12 + 3, "align": 7})):
+        nlp = _nlp(batch, **kw)
+        Zref, K, x0, Zout, _ = _inputs(nlp, batch, 5, with_gains)
+        zd, kd, xd = _tangents(nlp, 6, with_gains)
+        got = nlp.tracking_rollout_jvp(Zref, Zout, K, zd, kd, xd)
+        ev = _per_problem(nlp, Zref, K, Zout, zd, kd, xd, got, _evaluator_blocks(nlp, Zout))
+        print(f"ragged / padded, K={with_gains}: {ev:.2e}")
+        assert ev <= 1e-12, ev
+
+
+@pytest.mark.parametrize("B,N,ragged", [(65536, 40, False), (65536, 80, True)])
+def test_full_size_every_problem(B, N, ragged):
+    from quadruped_landing_amd import problem_gen as PG
+
+    full = PG.make_batch(B, N, 14, 1, seed=2, ragged=ragged)
+    worst = 0.0
+    chunk = 4096
+    for s in range(0, B, chunk):
+        sub = PG.LandingBatch(full.model, N, full.k_trans[s:s + chunk], full.init_mode[s:s + chunk], full.x0[s:s + chunk],
+                              full.xf[s:s + chunk], full.obj if full.obj.ndim == 2 else full.obj[s:s + chunk],
+                              full.Z[s:s + chunk])
+        nlp = _nlp(sub)
+        Zref, K, x0, Zout, _ = _inputs(nlp, sub, s, True)
+        zd, kd, xd = _tangents(nlp, s + 1, True)
+        got = _rows(nlp, nlp.tracking_rollout_jvp(Zref, Zout, K, zd, kd, xd))
+        dense = _dense_blocks(nlp, Zout)
+        F = dense.copy()
+        kj = nlp.k_trans.astype(int) - 2
+        for b in np.nonzero((kj >= 0) & (kj < N - 1))[0]:
+            F[b] = RV.evaluator_blocks(dense[b], nlp.k_trans[b])
+        ref = RJ.sweep_batch(F, _rows(nlp, Zref), K.cpu().numpy(), _rows(nlp, Zout), _rows(nlp, zd), kd.cpu().numpy(),
+                             xd.cpu().numpy())
+        e = np.linalg.norm(got - ref, axis=1) / np.maximum(np.linalg.norm(ref, axis=1), 1e-300)
+        worst = max(worst, float(e.max()))
+        del nlp
+    print(f"full size B={B} N={N} ragged={ragged}: worst per-problem rel err {worst:.2e}")
+    assert worst <= 1e-12, worst
+
+
+@pytest.mark.parametrize("B,N,k_trans,init_mode", SHAPES)
+@pytest.mark.parametrize("with_gains", [False, True])
+def test_adjoint_identity_with_the_shipped_vjp(B, N, k_trans, init_mode, with_gains):
+    """<Zbar, J d> = <J' Zbar, d> between the two kernels: no oracle involved."""
+    import torch
+
+    batch = _batch(B, N, k_trans, init_mode, seed=N + k_trans)
+    nlp = _nlp(batch)
+    Zref, K, x0, Zout, Zbar = _inputs(nlp, batch, N + 3 * k_trans, with_gains)
+    zd, kd, xd = _tangents(nlp, N + 7 * k_trans, with_gains)
+    got = nlp.tracking_rollout_jvp(Zref, Zout, K, zd, kd, xd)
+    zb, kb, xb = nlp.tracking_rollout_vjp(Zref, Zout, Zbar, K)
+    lhs = float(torch.dot(Zbar, got))
+    rhs = float(torch.dot(zb, zd) + torch.dot(xb.view(-1), xd.view(-1)))
+    if with_gains:
+        rhs += float(torch.dot(kb.view(-1), kd.view(-1)))
+    print(f"B={B} N={N} k_trans={k_trans} mode={init_mode} K={with_gains}: <Zbar, J d> {lhs:.15e}, <J' Zbar, d> {rhs:.15e}, "
+          f"difference {abs(lhs - rhs) / (abs(lhs) + abs(rhs)):.2e}")
+    assert abs(lhs - rhs) <= 1e-12 * (abs(lhs) + abs(rhs)), (lhs, rhs)
+
+
+def test_central_differences_of_the_gpu_rollout_entry_by_entry():
+    """(rollout(p + eps d) - rollout(p - eps d)) / (2 eps) against Zout_dot, per-problem relative norm, on the VJP test's
+    batch, direction scalings and eps.  The bar is ten times what the same difference quotient of the numpy roll-out
+    (RV.rollout) leaves against the numpy sweep for the same inputs: the error of the quotient itself."""
+    batch = _batch(8, 40, 14, 1, seed=21)
+    nlp = _nlp(batch)
+    Zref, K, x0, Zout, _ = _inputs(nlp, batch, 21, True)
+    zr, Kh, x0h = _rows(nlp, Zref), K.cpu().numpy(), x0.cpu().numpy()
+    eps = 1e-4
+    N = nlp.N
+    worst_gpu = worst_cpu = 0.0
+    for t in range(3):
+        zd, kd, xd = _tangents(nlp, 22 + t, True, scale=(1e-3, 1e-2, 1e-3))
+        got = _rows(nlp, nlp.tracking_rollout_jvp(Zref, Zout, K, zd, kd, xd))
+        plus = _rows(nlp, nlp.tracking_rollout(Zref + eps * zd, K + eps * kd, x0 + eps * xd))
+        minus = _rows(nlp, nlp.tracking_rollout(Zref - eps * zd, K - eps * kd, x0 - eps * xd))
+        fd = (plus - minus) / (2 * eps)
+        zdh, kdh, xdh = _rows(nlp, zd), kd.cpu().numpy(), xd.cpu().numpy()
+        for b in range(nlp.B):
+            worst_gpu = max(worst_gpu, RV.rel(fd[b], got[b]))
+            kt, im = int(nlp.k_trans[b]), int(nlp.init_mode[b])
+            roll = lambda s: RV.rollout(N, kt, im, zr[b] + s * zdh[b], Kh[b] + s * kdh[b], x0h[b] + s * xdh[b])  # noqa: E731
+            zo = roll(0.0)
+            ref = RJ.sweep(RV.complex_step_blocks(N, kt, im, zo), zr[b], Kh[b], zo, zdh[b], kdh[b], xdh[b])
+            worst_cpu = max(worst_cpu, RV.rel((roll(eps) - roll(-eps)) / (2 * eps), ref))
+    bar = 10.0 * worst_cpu
+    print(f"central differences, eps {eps:g}: GPU quotient against Zout_dot {worst_gpu:.2e}; numpy quotient against the numpy "
+          f"sweep {worst_cpu:.2e}; bar {bar:.2e}")
+    assert worst_gpu <= bar, (worst_gpu, bar)
+
+
+def test_duality_with_the_covariance_sweep():
+    """W = 0, Sigma_0 = G G': the x0 columns of the JVP, dx_k^(i) = Phi_k G[:, i], give Sigma_k = sum_i dx_k^(i) dx_k^(i)'."""
+    import torch
+
+    from quadruped_landing_amd import nlp as NL
+
+    batch = _batch(9, 40, 14, 1, seed=61)
+    nlp = _nlp(batch)
+    Zref, K, _, Zout, _ = _inputs(nlp, batch, 61, True)
+    rng = np.random.default_rng(63)
+    G = rng.normal(size=(nlp.B, 15, 15)) / 4.0
+    S0 = np.einsum("bij,bkj->bik", G, G)
+    S, _ = nlp.tracking_covariance(Zout, K, S0)
+    Sg = NL.unpack_covariance(S)
+    cols = [_rows(nlp, nlp.tracking_rollout_jvp(Zref, Zout, K, x0_dot=torch.from_numpy(np.ascontiguousarray(G[:, :, i])).cuda()))
+            for i in range(15)]
+    worst = 0.0
+    for k in (5, 20, nlp.N - 1):  # before the jump knot (12), after it, and the end
+        dx = np.stack([c[:, 20 * k: 20 * k + 15] for c in cols], axis=2)  # (B, 15, 15): column i is dx_k^(i)
+        Sk = np.einsum("bij,bkj->bik", dx, dx)
+        err = np.linalg.norm((Sk - Sg[:, k]).reshape(nlp.B, -1), axis=1) / np.linalg.norm(Sg[:, k].reshape(nlp.B, -1), axis=1)
+        worst = max(worst, float(err.max()))
+    print(f"duality with the covariance sweep: worst relative Frobenius difference {worst:.2e}")
+    assert worst <= 1e-10, worst
+
+
+def test_forward_mode_autograd():
+    import torch
+
+    batch = _batch(2, 6, 4, 1, seed=31)
+    nlp = _nlp(batch)
+    Zref = nlp.upload_Z(batch.Z).requires_grad_(True)
+    K = _gains(nlp, 32, scale=0.02).requires_grad_(True)
+    x0 = torch.from_numpy(batch.Z[:, :15].copy()).cuda().requires_grad_(True)
+    assert torch.autograd.gradcheck(lambda z, k, x: nlp.differentiable_rollout(z, k, x), (Zref, K, x0), eps=1e-6,
+                                    atol=1e-7, rtol=1e-6, check_forward_ad=True)
+    # torch.func.jvp is the direct call, bit for bit
+    z, k, x = Zref.detach(), K.detach(), x0.detach()
+    zd, kd, xd = _tangents(nlp, 33, True)
+    out, tangent = torch.func.jvp(lambda a, b_, c: nlp.differentiable_rollout(a, b_, c), (z, k, x), (zd, kd, xd))
+    Zout = nlp.tracking_rollout(z, k, x)
+    assert torch.equal(out, Zout) and torch.equal(tangent, nlp.tracking_rollout_jvp(z, Zout, k, zd, kd, xd))
+    # one tangent alone, through torch.autograd.forward_ad; K = None
+    import torch.autograd.forward_ad as fwAD
+
+    with fwAD.dual_level():
+        t = fwAD.unpack_dual(nlp.differentiable_rollout(z, None, fwAD.make_dual(x, xd))).tangent
+    assert torch.equal(t, nlp.tracking_rollout_jvp(z, nlp.tracking_rollout(z, None, x), None, x0_dot=xd))
+    # the reverse mode is what it was
+    z2 = z.clone().requires_grad_(True)
+    k2 = k.clone().requires_grad_(True)
+    out = nlp.differentiable_rollout(z2, k2, x)
+    w = torch.from_numpy(np.random.default_rng(34).normal(size=out.shape)).cuda()
+    out.backward(w)
+    zb, kb, _ = nlp.tracking_rollout_vjp(z, Zout, w, k, want=("Zref", "K"))
+    assert torch.equal(z2.grad, zb) and torch.equal(k2.grad, kb)
+
+
+@pytest.mark.parametrize("B", [5, 1024])  # mapped pinned buffers (small batch) and staged device copies
+def test_contract_sentinels_linearity_null_tangents_refusals_and_host_forms(B):
+    import torch
+
+    from quadruped_landing_amd import _lib
+
+    N = 12
+    batch = _batch(B, N, 5, 2, seed=51)
+    nlp = _nlp(batch, z_stride=20 * N + 3)
+    Zref, K, x0, Zout, _ = _inputs(nlp, batch, 51, True)
+    zd, kd, xd = _tangents(nlp, 52, True)
+    L = _lib.lib()
+    n, zs = nlp.n_nlp, nlp.z_stride
+    got = nlp.tracking_rollout_jvp(Zref, Zout, K, zd, kd, xd)
+    # a NaN sentinel survives in the padding, and every entry below n_nlp is overwritten
+    s = torch.full((B * zs,), float("nan"), dtype=torch.float64, device="cuda")
+    assert nlp.tracking_rollout_jvp(Zref, Zout, K, zd, kd, xd, out=s) is s
+    v = s.view(B, zs)
+    assert torch.isnan(v[:, n:]).all() and torch.equal(v[:, :n], got.view(B, zs)[:, :n])
+    assert (got.view(B, zs)[:, n:] == 0.0).all()
+    # NaN in what the call must not read: Zref_dot's padding and xref_dot_{N-1}; Zref without K_dot
+    zd_nan = zd.clone().view(B, zs)
+    zd_nan[:, 20 * (N - 1):] = float("nan")
+    assert torch.equal(nlp.tracking_rollout_jvp(Zref, Zout, K, zd_nan.view(-1), kd, xd), got)
+    nan_z = torch.full_like(Zref, float("nan"))
+    assert torch.equal(nlp.tracking_rollout_jvp(nan_z, Zout, K, zd, None, xd), nlp.tracking_rollout_jvp(Zref, Zout, K, zd, None, xd))
+    # linearity in the tangent
+    zd2, kd2, xd2 = _tangents(nlp, 53, True)
+    got2 = nlp.tracking_rollout_jvp(Zref, Zout, K, zd2, kd2, xd2)
+    got3 = nlp.tracking_rollout_jvp(Zref, Zout, K, 2.0 * zd - 3.0 * zd2, 2.0 * kd - 3.0 * kd2, 2.0 * xd - 3.0 * xd2)
+    ref = 2.0 * got - 3.0 * got2
+    assert float((got3 - ref).norm() / ref.norm()) <= 1e-13
+    # each NULL tangent is the zero tangent, bit for bit (with gains and without)
+    z0, k0, x0z = torch.zeros_like(zd), torch.zeros_like(kd), torch.zeros_like(xd)
+    for dots, zeros in (((None, kd, xd), (z0, kd, xd)), ((zd, None, xd), (zd, k0, xd)), ((zd, kd, None), (zd, kd, x0z)),
+                        ((None, None, xd), (z0, k0, xd)), ((zd, None, None), (zd, k0, x0z)), ((None, kd, None), (z0, kd, x0z))):
+        assert torch.equal(nlp.tracking_rollout_jvp(Zref, Zout, K, *dots), nlp.tracking_rollout_jvp(Zref, Zout, K, *zeros)), dots
+    for dots, zeros in (((None, None, xd), (z0, None, xd)), ((zd, None, None), (zd, None, x0z))):
+        assert torch.equal(nlp.tracking_rollout_jvp(Zref, Zout, None, *dots), nlp.tracking_rollout_jvp(Zref, Zout, None, *zeros))
+    # refusals: no direction, K_dot without K (device and host form), an output that overlaps an input
+    with pytest.raises(_lib.QlnError):
+        nlp.tracking_rollout_jvp(Zref, Zout, K)
+    with pytest.raises(_lib.QlnError):
+        nlp.tracking_rollout_jvp(Zref, Zout, None, zd, kd, xd)
+    h = {name: t.cpu().numpy() for name, t in (("Zref", Zref), ("K", K), ("Zout", Zout), ("zd", zd), ("kd", kd), ("xd", xd))}
+    with pytest.raises(_lib.QlnError):
+        nlp.tracking_rollout_jvp_host(h["Zref"], h["Zout"], h["K"])
+    with pytest.raises(_lib.QlnError):
+        nlp.tracking_rollout_jvp_host(h["Zref"], h["Zout"], None, K_dot=h["kd"])
+    for bad in (zd, Zref, Zout):
+        with pytest.raises(_lib.QlnError):
+            _lib.check(L.qln_tracking_rollout_jvp(nlp._h, Zref.data_ptr(), K.data_ptr(), Zout.data_ptr(), zd.data_ptr(), None,
+                                                  None, bad.data_ptr()))
+    assert L.qln_tracking_rollout_jvp(nlp._h, Zref.data_ptr(), K.data_ptr(), Zout.data_ptr(), zd.data_ptr(), None, None,
+                                      None) == _lib.QLN_ERR_INVALID_ARGUMENT
+    # host forms equal the device forms bit for bit, after the other tracking host entry points ran on NaN on this handle
+    nan_h = np.full(nlp.dims.z_total, np.nan)
+    nan_k = np.full(h["K"].shape, np.nan)
+    nlp.tracking_lqr_host(nan_h, np.ones(15), np.ones(4), np.ones(15))
+    nlp.tracking_rollout_host(nan_h, nan_k, np.full((B, 15), np.nan))
+    nlp.tracking_rollout_vjp_host(nan_h, nan_h, nan_h, nan_k)
+    nlp.tracking_covariance_host(nan_h, nan_k, np.full((15, 15), np.nan))
+    x_only = nlp.tracking_rollout_jvp(Zref, Zout, K, x0_dot=xd).cpu().numpy()
+    open_loop = nlp.tracking_rollout_jvp(Zref, Zout, None, zd, None, xd).cpu().numpy()
+    for _ in range(2):  # the second call reuses the handle's buffers
+        assert np.array_equal(nlp.tracking_rollout_jvp_host(h["Zref"], h["Zout"], h["K"], h["zd"], h["kd"], h["xd"]),
+                              got.cpu().numpy())
+        assert np.array_equal(nlp.tracking_rollout_jvp_host(h["Zref"], h["Zout"], h["K"], x0_dot=h["xd"]), x_only)
+        assert np.array_equal(nlp.tracking_rollout_jvp_host(h["Zref"], h["Zout"], None, h["zd"], None, h["xd"]), open_loop)
