@@ -3,9 +3,7 @@ launches after 3 warm-ups) at B = 65 536, N = 40 and N = 61, against two floors:
 once; K, and P when asked for, written once; the roll-out reads Zref and K and writes Zout) and the FP64 FMAs of the sparse
 sweep (~3.5 k per knot and problem) over the chip's vector FP64 rate (profiles/r01_fp64_rate.txt: 16 FMA/clk/SIMD, 1024
 SIMDs, 2.4 GHz).  The share of peak is taken against the larger of the two.  Prints one JSON line.
-   python bench/tracking_timing.py [B]
-The A/B of the two k_tracking_lqr variants runs this on the tuning build:
-   QLN_LIB_PATH=quadruped_landing_amd/csrc/libqln_hip_tuning.so QLN_TRACK_FORM_ONCE=0|1 python bench/tracking_timing.py"""
+   python bench/tracking_timing.py [B]"""
 import json
 import os
 import sys
@@ -64,4 +62,4 @@ def run(B, N, k_trans):
 if __name__ == "__main__":
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
     print(json.dumps({"iters": 20, "warmup": 3, "lib": os.path.basename(os.environ.get("QLN_LIB_PATH", "libqln_hip.so")),
-                      "QLN_TRACK_FORM_ONCE": os.environ.get("QLN_TRACK_FORM_ONCE"), "configs": [run(B, 40, 14), run(B, 61, 21)]}))
+                      "configs": [run(B, 40, 14), run(B, 61, 21)]}))

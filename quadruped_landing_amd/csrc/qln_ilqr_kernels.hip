@@ -26,7 +26,7 @@
 //
 // The reference holds nothing to compare the iterates with (it hands its callbacks to Ipopt 3.13 + MUMPS); the result
 // is checked by the evaluator itself: constraint violation and objective of the returned Z (tests/test_gpu_solve.py).
-#include "qln_kernel_common.h"
+#include "qln_row16.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -52,7 +52,7 @@ constexpr int kKn = 9;         // per-knot scalars kept in LDS
 constexpr int kLd = 17;        // leading dimension of the sweep's LDS matrices: 16 columns + 1 (a stride of 16 doubles puts a column in two LDS banks)
 constexpr int kKg = 80;        // doubles per knot of the feedback law in the scratch: 5 rows of [15 gains, feed-forward]
 // The sweep needs four entries of A = d x+/d x per column c -- the diagonal A(c, c), A(2, c), A(9, c) and the coupling
-// A(c-7, c) (step_structure_ok below) -- in T = P A by column and in Qxx = .. + A'T by row, the same four either way.  Its LDS
+// A(c-7, c) (a_slot / a_structure_ok of qln_row16.h) -- in T = P A by column and in Qxx = .. + A'T by row, the same four either way.  Its LDS
 // image is therefore not the 15x15 matrix but the compact table AC[16][4] = {A(c,c), A(2,c) (0 for c = 2), A(9,c) (0 for c = 9),
 // A(c-7,c) (0 where there is no coupling)}: a column's four are two 16-byte reads at one address instead of four reads at four
 // computed ones.  Row 15 and the slots no step block fills hold 0.0 for the whole sweep, as does B(1, 0) of the B image
@@ -61,40 +61,13 @@ constexpr int kKg = 80;        // doubles per knot of the feedback law in the sc
 constexpr int kAcB = 64;       // offset of the B image behind the table
 constexpr int kAZero = 60;     // AC[15][0]
 constexpr int kBZero = 5;      // B(1, 0)
-__host__ __device__ constexpr int ac_slot(int row, int col) {  // where A(row, col) lies in the table (see above)
-    return 4 * col + (row == col ? 0 : row == 2 ? 1 : row == 9 ? 2 : 3);
-}
+__host__ __device__ constexpr int ac_slot(int row, int col) { return 4 * col + a_slot(row, col); }  // A(row, col) in the table
 
 // per-knot scalars (lane = knot phase -> backward sweep)
 enum { KN_W = 0, KN_T0 = 1, /* t0..t5 = max(0, lam + rho g); the row is active where t > 0 */ KN_CQ = 7 /* (lb/2) cos(theta) */, KN_ELL = 8 };
 // (the final-control row's lam + rho e lives in leq[15])
 
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-    return v;
-}
 __device__ __forceinline__ double act(double t) { return t > 0 ? 1.0 : 0.0; }
-// sum over the four lanes of a quad (all four active), the same bits in each of them
-template <int CTRL>
-__device__ __forceinline__ double dpp_quad_perm(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double quad_sum(double v) {
-    v += dpp_quad_perm<0xB1>(v);  // quad_perm [1, 0, 3, 2]
-    v += dpp_quad_perm<0x4E>(v);  // quad_perm [2, 3, 0, 1]
-    return v;
-}
-// lane I of each row of sixteen lanes, in every lane of that row (DPP row_newbcast: one v_mov_b64_dpp, no LDS, no wait).
-// The source lane must be enabled.
-template <int I>
-__device__ __forceinline__ double row_bcast(double v) {
-    static_assert(I >= 0 && I < 16, "a lane of the row");
-    return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + I, 0xf, 0xf, false);
-}
 // u[j] += K[j](lane I of the row) * dx for the five rows of a feedback law: v_fmac_f64 with the DPP operand -- the broadcast
 // costs no instruction of its own (hipcc does not fold a v_mov_b64_dpp into the multiply-add, hence the assembly; fused like
 // fma()).  The block opens with the wait states an instruction with a DPP operand needs after one of its registers (two) or
@@ -312,10 +285,8 @@ __device__ __forceinline__ void step_fast(const FastStep& C, int k, int kt, int 
 }
 
 // Structure of a step block that the Riccati sweep relies on (checked against the union pattern of qln_device.h):
-//   d x+/d x (15x15): the diagonal, rows 2 (theta) and 9 (omega), and (c-7, c) for c in {7, 8, 10, 11, 12, 13}
-//                     (a position picks up h times its velocity);
+//   d x+/d x (15x15): four entries per column -- a_slot / a_coupling / a_structure_ok of qln_row16.h;
 //   d x+/d F (columns 15-18): six rows each -- b_rows(j);   d x+/d h (column 19): dense.
-__host__ __device__ constexpr int a_coupling(int c) { return (c == 7 || c == 8 || (c >= 10 && c <= 13)) ? c - 7 : -1; }
 __host__ __device__ constexpr void b_rows(int j, int (&rows)[6]) {
     rows[0] = j & 1;
     rows[1] = 2;
@@ -324,10 +295,8 @@ __host__ __device__ constexpr void b_rows(int j, int (&rows)[6]) {
     rows[4] = 9;
     rows[5] = 10 + j;
 }
-constexpr bool step_structure_ok() {
-    for (int r = 0; r < 15; ++r) {
-        for (int c = 0; c < 15; ++c)
-            if (step_union_present(r, c) && !(r == c || r == 2 || r == 9 || r == a_coupling(c))) return false;
+constexpr bool b_structure_ok() {
+    for (int r = 0; r < 15; ++r)
         for (int j = 0; j < 4; ++j) {
             int rows[6] = {0, 0, 0, 0, 0, 0};
             b_rows(j, rows);
@@ -335,10 +304,9 @@ constexpr bool step_structure_ok() {
             for (int q = 0; q < 6; ++q) in = in || rows[q] == r;
             if (step_union_present(r, 15 + j) && !in) return false;
         }
-    }
     return true;
 }
-static_assert(step_structure_ok(), "the sparse products of the Riccati sweep cover every possible non-zero of a step block");
+static_assert(b_structure_ok(), "the sparse products of the Riccati sweep cover every possible non-zero of a force column");
 static_assert(!step_union_present(1, 15), "the zero slot of the B image is outside the union pattern");
 
 struct Lds {
@@ -550,7 +518,7 @@ __global__ __launch_bounds__(kWave, OCC) void k_al_ilqr(BatchParams P, SolvePara
                 vl = fmax(vl, o.viol);
             }
         }
-        J = wsum(Jl);
+        J = wave_sum(Jl);
         vmax = wmax(vl);
         wave_lds_sync();
     };
@@ -713,7 +681,7 @@ __global__ __launch_bounds__(kWave, OCC) void k_al_ilqr(BatchParams P, SolvePara
                 const double h12 = (k >= 1) ? -rho * (act(kn[KN_T0 + 0]) - act(kn[KN_T0 + 1])) * kn[KN_CQ] : 0.0;  // d2/d(yb)d(theta)
                 const double hfc = (k == N - 2) ? rho : 0.0;                              // d2/d(F1y)d(F2y)
                 // The products of the sweep use the structure of the step blocks instead of dense 15-term sums (see
-                // step_structure_ok above): A = diagonal + rows 2 (theta) and 9 (omega) + the six position <- velocity
+                // a_structure_ok): A = diagonal + rows 2 (theta) and 9 (omega) + the six position <- velocity
                 // couplings (c-7, c); a force column of B has six rows; only the h column of B is dense -- its 15-term
                 // sums are split over the four lanes of a quad (terms i = p, p+4, p+8, p+12) and added up by DPP.
                 // In the one-wave-per-SIMD build every phase below does ALL its reads and arithmetic first and its (predicated) stores
@@ -1200,8 +1168,8 @@ __global__ __launch_bounds__(kWave, OCC) void k_al_ilqr(BatchParams P, SolvePara
                 if (k < N - 1) hs += hk;
             }
         }
-        f = wsum(f);
-        hs = wsum(hs);
+        f = wave_sum(f);
+        hs = wave_sum(hs);
         if (info && lane == 0) {
             double* o = info + 16 * (int64_t)b;
             o[0] = (double)outer;

@@ -1,5 +1,5 @@
 // qln_kernel_common.h -- device code shared by the gfx950 kernel files.  Internal.
-//   * wave / dispatch helpers;
+//   * wave / dispatch helpers (xcd_contiguous_index, wave_lds_sync, wave_sum);
 //   * the value path: dynamics, rk4_step, step_forward (one knot of a roll-out), literal restatements of the reference
 //     that round like it;
 //   * clearance_dtheta, the one derivative entry of the clearance rows (the J v / J' lam products and the covariance
@@ -8,7 +8,8 @@
 //     and the Gauss-Newton step (qln_solver_kernels.hip), the iLQR solve (qln_ilqr_kernels.hip) and the TVLQR sweep
 //     (qln_tracking_kernels.hip) share: StepBlock + step_block() form a knot's base quantities from explicit arguments
 //     (states, forces, h, KnotMode, Model), for_each_step_entry() visits the 85 entries of the union pattern with row and
-//     col as compile-time constants.  A static_assert holds the visit order to step_union_pos().
+//     col as compile-time constants, for_each_rollout_entry() the same with the roll-out's clock row.  A static_assert
+//     holds the visit order to step_union_pos().
 // The functions here are compiled under the floating-point contraction mode in force where this header is INCLUDED.
 // qln_solver_kernels.hip sets contract(fast) above the include so that its step blocks fuse; the same then holds for
 // EVERYTHING in this header in that file: a value-path helper (rk4_step, step_forward) called from there would fuse too
@@ -46,6 +47,12 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// sum over the wave's 64 lanes, the same bits in every lane
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+    return v;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -254,6 +261,17 @@ using Idx = std::integral_constant<int, I>;  // row and col reach a visitor as c
 template <typename F>
 __device__ __forceinline__ void for_each_step_entry(const StepBlock& b, F&& f) {
 #define QLN_E(row, col, val) [[clang::always_inline]] f(Idx<row>{}, Idx<col>{}, (val));
+    QLN_STEP_ENTRY_LIST(QLN_E)
+#undef QLN_E
+}
+// The block of a ROLL-OUT's knot (the TVLQR sweep, the covariance and tangent sweeps of qln_tracking_kernels.hip): the
+// same entries with row 14 replaced by 1.0.  Row 14 is the clock, t+ = t + h: 1 at x[14] and at h.  The evaluator's
+// block carries the reference's jump mask there, which zeroes the row at the jump knot (quirk Q1: keep = 0); the
+// roll-out's step_forward applies the jump map itself, which keeps the clock, so the derivative of what the roll-out
+// computes has the 1 at every knot.  Nothing else differs between the two blocks.
+template <typename F>
+__device__ __forceinline__ void for_each_rollout_entry(const StepBlock& b, F&& f) {
+#define QLN_E(row, col, val) [[clang::always_inline]] f(Idx<row>{}, Idx<col>{}, (row == 14) ? 1.0 : (val));
     QLN_STEP_ENTRY_LIST(QLN_E)
 #undef QLN_E
 }

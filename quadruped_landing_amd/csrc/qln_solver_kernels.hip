@@ -255,12 +255,6 @@ __global__ __launch_bounds__(kWave) void k_constraint_vjp(BatchParams P, const d
 // truncation), which is what an outer trust-region loop needs.
 // LDS per problem: (5 n_nlp + 2 m_nlp + N) doubles = 43 KB at N = 40, 87 KB at N = 80; N <= 149 fits the 160 KB of a CU.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-    return v;
-}
-
 // y = A v, all operands in LDS (z, v: layout of Z; y: layout of c; mask[k] = 1 if clearance row k is active)
 // The step block of a knot does not change during a Gauss-Newton step, so when every lane owns at most one knot
 // (N <= 64) its 85 entries are computed once and kept in registers (170 VGPRs; the kernel runs one wave per SIMD

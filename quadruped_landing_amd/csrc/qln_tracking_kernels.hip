@@ -8,15 +8,16 @@
 // form (step_block / for_each_step_entry), formed for the knot by every lane of the row alike from the reference's
 // (x_k, u_k): what a lane needs at compile-time positions (every column of A for T = P A, every column of B for
 // S = P B and B'S) is in registers, what it needs at its own runtime position (column j of A for A'T, column j of Qux)
-// comes from a per-row LDS table in the compact four-entries-per-column form of the solver's sweep (ac_slot of
-// qln_ilqr_kernels.hip): A(c,c), A(2,c), A(9,c) and the position <- velocity coupling A(c-7,c).
+// comes from a per-row LDS table in the compact four-entries-per-column form of the solver's sweep (a_slot of
+// qln_row16.h): A(c,c), A(2,c), A(9,c) and the position <- velocity coupling A(c-7,c).
 // Per knot, three LDS hand-offs inside the wave (no s_barrier, wave_lds_sync):
 //   1. T row j = P row j . A (60 FMAs, structure known at compile time), S row j = P row j . B (24) -> LDS;
 //   2. Qxx row j = A'T (rows 2, 9, j-7 of T from LDS), Quu = R + B'S (every lane, all of S from LDS), Qux column j;
 //      Quu = L D L' (every lane alike), K column j = Quu^-1 Qux column j -> the K tile in LDS;
 //   3. P_k row j, entries c <= j, = Q + Qxx - Qux'K -> the packed lower-triangle tile; every lane reads its full row back
 //      from the tile, so P is exactly symmetric, and the K and P tiles leave as coalesced stores (sixteen lanes, 128 B).
-// The jump knot's A row 14 is the jump map's (the clock is kept), not the Jacobian's masked zero (quirk Q1).
+// Every kernel here that needs the roll-out's A_k, B_k takes them from for_each_rollout_entry (qln_kernel_common.h): the
+// evaluator's block with the jump map's clock row.  The mapping, the DPP moves and the knot's load / store are qln_row16.h's.
 //
 // k_tracking_rollout: one lane per problem, the solver's step_forward (qln_kernel_common.h) on the fed-back forces.
 //
@@ -49,32 +50,22 @@
 // nothing goes through LDS.  Every lane forms the knot's StepBlock (Zout's knot: two coalesced loads, handed round by DPP
 // row broadcasts) and picks its row's entries from the visitor; (A dx)[j] is the diagonal, the coupling A(j, j+7) through a
 // row shift, and for the dense rows 2 and 9 two row sums; K (dx - xref_dot) + Kdot e is four more.
-#include "qln_kernel_common.h"
+#include "qln_row16.h"
 
-#include <cstdlib>
 #include <utility>
 
 namespace qln {
 namespace {
 
-constexpr int kRows = kWave / 16;  // problems per wave
-// per-row LDS image (doubles): compact A table [16][4] | T [15][16] | S [15][4] | K tile [4][15] | packed P [120] |
-// B table [15][4] (the form-once variant only)
-constexpr int kLAC = 0, kLT = 64, kLS = kLT + 15 * 16, kLK = kLS + 60, kLP = kLK + 60, kLB = kLP + QLN_TRACK_P_NNZ,
-              kLRow = kLB + 60;
-static_assert(kLRow % 2 == 0 && kLS % 2 == 0 && kLK % 2 == 0 && kLP % 2 == 0 && kLB % 2 == 0, "16-byte aligned sections");
+// per-row LDS image (doubles): compact A table [16][4] | T [15][16] | S [15][4] | K tile [4][15] | packed P [120]
+constexpr int kLAC = 0, kLT = 64, kLS = kLT + 15 * 16, kLK = kLS + 60, kLP = kLK + 60, kLRow = kLP + QLN_TRACK_P_NNZ;
+static_assert(kLRow % 2 == 0 && kLS % 2 == 0 && kLK % 2 == 0 && kLP % 2 == 0, "16-byte aligned sections");
 
-__host__ __device__ constexpr int tk_slot(int row, int col) {  // the compact table's slot of A(row, col)
-    return row == col ? 0 : row == 2 ? 1 : row == 9 ? 2 : 3;
-}
-__host__ __device__ constexpr int tk_coupling(int c) {  // the velocity column c's position row, -1 if none
-    return (c == 7 || c == 8 || (c >= 10 && c <= 13)) ? c - 7 : -1;
-}
 // bit s of a_slots(c): slot s of column c can be non-zero in some mode; bit r of b_rows_mask(m): B(r, m) can be
 __host__ __device__ constexpr unsigned a_slots(int c) {
     unsigned m = 0;
     for (int r = 0; r < 15; ++r)
-        if (step_union_present(r, c) || (r == 14 && c == 14)) m |= 1u << tk_slot(r, c);
+        if (step_union_present(r, c)) m |= 1u << a_slot(r, c);
     return m;
 }
 __host__ __device__ constexpr unsigned b_rows_mask(int m) {
@@ -83,47 +74,27 @@ __host__ __device__ constexpr unsigned b_rows_mask(int m) {
         if (step_union_present(r, 15 + m)) s |= 1u << r;
     return s;
 }
-__host__ __device__ constexpr bool a_structure_ok() {  // every state column's entries fit the four slots
-    for (int c = 0; c < 15; ++c)
-        for (int r = 0; r < 15; ++r)
-            if (step_union_present(r, c) && !(r == c || r == 2 || r == 9 || r == tk_coupling(c))) return false;
-    return true;
-}
-static_assert(a_structure_ok(), "A has four entries per column: diagonal, rows 2 and 9, and row c-7");
-
-constexpr bool kTrackFormOnceDefault = false;  // which k_tracking_lqr variant the product launches
 
 struct TrackWeights {
     double Q[15], R[4], Qf[15];
 };
 
-// kFormOnce: the knot's block is formed by lane 0 of the row alone, straight into the LDS tables (A and B), and every lane
-// reads what it needs back from there -- the alternative to forming it in every lane's registers (DESIGN.md 4.11 compares
-// the two).
-template <bool kWantP, bool kFormOnce>
+// The knot's block is formed in every lane's registers; forming it once per row into LDS tables was measured slower
+// (profiles/tracking_variants.txt).
+template <bool kWantP>
 __global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeights W, const double* __restrict__ Zref,
                                                         double* __restrict__ Kout, double* __restrict__ Pout) {
     __shared__ double lds[kRows * kLRow];
-    const int lane = threadIdx.x;
-    const int ln = lane & 15, row = lane >> 4;
-    const int j = ln < 15 ? ln : 14;  // lane 15 shadows row 14 and stores nothing
-    const bool own = ln < 15;
-    const int wave = xcd_contiguous_index(blockIdx.x, (P.B + kRows - 1) / kRows);
-    const int b = wave * kRows + row;
-    const bool valid = b < P.B;
-    const int bc = valid ? b : P.B - 1;
-    const int N = P.N;
-    const ProblemDesc pd = P.desc[bc];
-    const int kt = pd.k_trans, im = pd.init_mode;
-    const Model M(P);
-    double* __restrict__ L = lds + row * kLRow;
+    const Row16 r16 = row16_of(P);  // lane 15 shadows row 14 and stores nothing
+    const int ln = r16.ln, j = r16.j, b = r16.b, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
+    const bool own = r16.own, valid = r16.valid;
+    const Model& M = r16.M;
+    double* __restrict__ L = lds + r16.row * kLRow;
     const double* __restrict__ Zb = Zref + (int64_t)bc * P.z_stride;
-    const int jp = tk_coupling(j), jq = jp < 0 ? 0 : jp;
+    const int jp = a_coupling(j), jq = jp < 0 ? 0 : jp;
 
     // the compact A table: slots no entry fills stay 0.0
     for (int i = ln; i < 64; i += 16) L[kLAC + i] = 0.0;
-    if (kFormOnce)
-        for (int i = ln; i < 60; i += 16) L[kLB + i] = 0.0;
     // P_N = Qf
     double p[15];
 #pragma unroll
@@ -158,41 +129,18 @@ __global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeig
         for (int c = 0; c < 15; ++c)
 #pragma unroll
             for (int s = 0; s < 4; ++s) Ac[c][s] = Bm[c][s] = 0.0;
-        // row 14 of the jump knot: the jump map keeps the clock (its Jacobian's mask zeroes the row, quirk Q1)
-        if constexpr (!kFormOnce) {
-            const StepBlock blk = step_block(x, F1x, F1y, F2x, F2y, h, md, M);
-            for_each_step_entry(blk, [&](auto r, auto c, double val) {
-                if constexpr (c < 15) Ac[c][tk_slot(r, c)] = (r == 14) ? 1.0 : val;
-                else if constexpr (c < 19) Bm[r][c - 15] = val;
-            });
-            // ---- 1. the knot's A table; T row j = P row j . A, S row j = P row j . B ----
-            if (ln == 0) {
-#pragma unroll
-                for (int c = 0; c < 15; ++c)
-#pragma unroll
-                    for (int s = 0; s < 4; ++s)
-                        if ((a_slots(c) >> s) & 1u) L[kLAC + 4 * c + s] = Ac[c][s];
-            }
-        } else {
-            if (ln == 0) {
-                const StepBlock blk = step_block(x, F1x, F1y, F2x, F2y, h, md, M);
-                for_each_step_entry(blk, [L](auto r, auto c, double val) {
-                    if constexpr (c < 15) L[kLAC + 4 * c + tk_slot(r, c)] = (r == 14) ? 1.0 : val;
-                    else if constexpr (c < 19) L[kLB + 4 * r + c - 15] = val;
-                });
-            }
-            wave_lds_sync();
-            // ---- 1. T row j = P row j . A, S row j = P row j . B, with A and B read from the row's tables ----
+        const StepBlock blk = step_block(x, F1x, F1y, F2x, F2y, h, md, M);
+        for_each_rollout_entry(blk, [&](auto r, auto c, double val) {
+            if constexpr (c < 15) Ac[c][a_slot(r, c)] = val;
+            else if constexpr (c < 19) Bm[r][c - 15] = val;
+        });
+        // ---- 1. the knot's A table; T row j = P row j . A, S row j = P row j . B ----
+        if (ln == 0) {
 #pragma unroll
             for (int c = 0; c < 15; ++c)
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
-                    if ((a_slots(c) >> s) & 1u) Ac[c][s] = L[kLAC + 4 * c + s];
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int r = 0; r < 15; ++r)
-                    if ((b_rows_mask(m) >> r) & 1u) Bm[r][m] = L[kLB + 4 * r + m];
+                    if ((a_slots(c) >> s) & 1u) L[kLAC + 4 * c + s] = Ac[c][s];
         }
         double t[15], sr[4];
 #pragma unroll
@@ -201,7 +149,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeig
             double acc = p[c] * Ac[c][0];
             if ((sl >> 1) & 1u) acc = fma(p[2], Ac[c][1], acc);
             if ((sl >> 2) & 1u) acc = fma(p[9], Ac[c][2], acc);
-            if ((sl >> 3) & 1u) acc = fma(p[tk_coupling(c) < 0 ? 0 : tk_coupling(c)], Ac[c][3], acc);
+            if ((sl >> 3) & 1u) acc = fma(p[a_coupling(c) < 0 ? 0 : a_coupling(c)], Ac[c][3], acc);
             t[c] = acc;
         }
 #pragma unroll
@@ -361,23 +309,6 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout(BatchParams P, const
     }
 }
 
-
-// v from lane (ctrl) of the same DPP row, as two 32-bit moves
-template <int kCtrl>
-__device__ __forceinline__ double dpp_f64(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), kCtrl, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), kCtrl, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-// sum over the sixteen lanes of a row, the same bits in every lane (each step adds a commuted pair)
-__device__ __forceinline__ double row_sum16(double v) {
-    v += dpp_f64<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp_f64<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += dpp_f64<0x141>(v);  // row_half_mirror
-    v += dpp_f64<0x140>(v);  // row_mirror
-    return v;
-}
-
 // One knot's inputs, as lane j of a row reads them: its own x_j, Zbar x_j, x_ref,j and K column j, and the knot's applied
 // controls and their cotangents (the same five values in every lane of the row).
 struct VjpKnot {
@@ -411,17 +342,9 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, c
                                                                 const double* __restrict__ Kg, const double* __restrict__ Zout,
                                                                 const double* __restrict__ Zbar, double* __restrict__ Zref_bar,
                                                                 double* __restrict__ Kbar, double* __restrict__ x0_bar) {
-    const int lane = threadIdx.x;
-    const int ln = lane & 15, row = lane >> 4;
-    const bool own = ln < 15;
-    const int j = own ? ln : 14;  // lane 15 reads lane 14's slots and contributes nothing
-    const int wave = xcd_contiguous_index(blockIdx.x, (P.B + kRows - 1) / kRows);
-    const int b = wave * kRows + row;
-    const bool valid = b < P.B;
-    const int bc = valid ? b : P.B - 1;
-    const int N = P.N;
-    const ProblemDesc pd = P.desc[bc];
-    const int kt = pd.k_trans, im = pd.init_mode;
+    const Row16 r16 = row16_of(P);  // lane 15 reads lane 14's slots and contributes nothing
+    const int j = r16.j, b = r16.b, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
+    const bool own = r16.own, valid = r16.valid;
     const double g = P.g, imb = 1.0 / P.mb, imf = 1.0 / P.mf;
     const double iIb = 12.0 / (P.mb * (P.lb * P.lb));
     const double* __restrict__ Zo = Zout + (int64_t)bc * P.z_stride;
@@ -476,7 +399,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, c
         const double fmv = pos ? 1.0 : fm;                      // w = m foot velocity - body velocity
         const double cmask = cpl ? fm * (kcpl ? keep : 1.0) : 0.0;
         // cross-lane lam: rows 2 and 9 (row broadcasts) and j-7 (row shift)
-        const double lam2 = dpp_f64<0x152>(lam), lam9 = dpp_f64<0x159>(lam), lamc = dpp_f64<0x117>(lam);
+        const double lam2 = dpp_f64<0x152>(lam), lam9 = dpp_f64<0x159>(lam), lamc = row_shr7(lam);
         // ---- A'lam, column j: diagonal, rows 2 and 9 (h-power times d tau / d x_j), row j-7 ----
         const double sF = ((sg[0] * F0 + sg[1] * F1) + sg[2] * F2) + sg[3] * F3;
         const double phi = fmv * sF;
@@ -504,11 +427,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, c
         if constexpr (kHasK) kub = ((cur.kc[0] * ub[0] + cur.kc[1] * ub[1]) + cur.kc[2] * ub[2]) + cur.kc[3] * ub[3];
         lam = own ? (cur.zb + alam) - kub : 0.0;
         if (valid) {
-            if (Zref_bar) {
-                double* __restrict__ o = Zref_bar + (int64_t)b * P.z_stride + 20 * k;
-                o[ln] = own ? kub : ub[0];
-                if (ln < 4) o[16 + ln] = ln == 0 ? ub[1] : ln == 1 ? ub[2] : ln == 2 ? ub[3] : ub[4];
-            }
+            if (Zref_bar) knot_store(Zref_bar + (int64_t)b * P.z_stride + 20 * k, r16, kub, ub);
             if (kHasK && Kbar && own) {
                 double* __restrict__ o = Kbar + ((int64_t)b * (N - 1) + k) * (QLN_TRACK_NU * QLN_NX);
                 const double dx = cur.x - cur.xr;
@@ -527,21 +446,6 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, c
 constexpr int kCStr = 17, kCImg = 0, kCK = 256, kCZ = kCK + 4 * 16, kCD = kCZ + 20, kCRow = kCD + 16;
 static_assert(15 * kCStr <= kCK && kCK % 2 == 0 && kCZ % 2 == 0 && kCD % 2 == 0 && kCRow % 2 == 0,
               "the image fits; 16-byte aligned sections");
-
-// row_sum16 with bound_ctrl set: every lane of these four permutations has a source, so no old value has to be prepared
-template <int kCtrl>
-__device__ __forceinline__ double dpp_f64_bc(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), kCtrl, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), kCtrl, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double row_sum16_bc(double v) {
-    v += dpp_f64_bc<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp_f64_bc<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += dpp_f64_bc<0x141>(v);  // row_half_mirror
-    v += dpp_f64_bc<0x140>(v);  // row_mirror
-    return v;
-}
 
 struct CovNoise {
     double w[15];
@@ -573,9 +477,8 @@ __device__ __forceinline__ void cov_apply(const StepBlock& blk, const double* Kl
     // formed here, in each application, instead of living in 50 registers across both
     StepBlock bk = blk;
     asm volatile("" : "+v"(bk.wAt), "+v"(bk.wBt), "+v"(bk.wAw));
-    // row 14 of the jump knot: the jump map keeps the clock (its Jacobian's mask zeroes the row, quirk Q1)
-    for_each_step_entry(bk, [&](auto r, auto c, double val) {
-        if constexpr (c < 15) out[r] = fma((r == 14) ? 1.0 : val, v[c], out[r]);
+    for_each_rollout_entry(bk, [&](auto r, auto c, double val) {
+        if constexpr (c < 15) out[r] = fma(val, v[c], out[r]);
         else if constexpr (kHasK && c < 19) out[r] = fma(-val, g[c - 15], out[r]);
     });
 }
@@ -589,19 +492,11 @@ __global__ __launch_bounds__(kWave) void k_tracking_covariance(BatchParams P, Co
                                                                int sigma0_batch, double* __restrict__ Sig,
                                                                double* __restrict__ mg) {
     __shared__ double lds[kRows * kCRow];
-    const int lane = threadIdx.x;
-    const int ln = lane & 15, row = lane >> 4;
-    const int j = ln < 15 ? ln : 14;  // lane 15 shadows column 14 and writes nothing to the image
-    const bool own = ln < 15;
-    const int wave = xcd_contiguous_index(blockIdx.x, (P.B + kRows - 1) / kRows);
-    const int b = wave * kRows + row;
-    const bool valid = b < P.B;
-    const int bc = valid ? b : P.B - 1;
-    const int N = P.N;
-    const ProblemDesc pd = P.desc[bc];
-    const int kt = pd.k_trans, im = pd.init_mode;
-    const Model M(P);
-    double* L = lds + row * kCRow;
+    const Row16 r16 = row16_of(P);  // lane 15 shadows column 14 and writes nothing to the image
+    const int ln = r16.ln, j = r16.j, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
+    const bool own = r16.own, valid = r16.valid;
+    const Model& M = r16.M;
+    double* L = lds + r16.row * kCRow;
     const double* __restrict__ Zb = Zout + (int64_t)bc * P.z_stride;
     const double* __restrict__ Kb = kHasK ? Kg + (int64_t)bc * (N - 1) * (QLN_TRACK_NU * QLN_NX) : nullptr;
     double* __restrict__ Sb = Sig ? Sig + (int64_t)bc * N * QLN_TRACK_P_NNZ : nullptr;
@@ -664,7 +559,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_covariance(BatchParams P, Co
             mv[5] = L[kCImg + (kCStr + 1) * 4];
             mv[6] = L[kCImg + (kCStr + 1) * 6];
             const double dj = L[kCImg + (kCStr + 1) * j];
-            mv[7] = row_sum16_bc(own ? dj : 0.0);
+            mv[7] = row_sum16(own ? dj : 0.0);
             double v = mv[0];
 #pragma unroll
             for (int q = 1; q < QLN_TRACK_MARG_STRIDE; ++q) v = (ln == q) ? mv[q] : v;
@@ -674,8 +569,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_covariance(BatchParams P, Co
 
     // Zout's knot (20 entries: lane ln takes ln and ln + 16) and the knot's K entries: requested one knot ahead
     double zn[2], kn[4];
-    zn[0] = Zb[ln];
-    zn[1] = Zb[16 + (ln & 3)];
+    knot_load(Zb, ln, zn[0], zn[1]);
     if constexpr (kHasK) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) kn[t] = Kb[min(ln + 16 * t, QLN_TRACK_NU * QLN_NX - 1)];
@@ -691,8 +585,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_covariance(BatchParams P, Co
                 if (ln + 16 * t < QLN_TRACK_NU * QLN_NX) L[ko[t]] = kn[t];
         }
         if (k + 1 < N - 1) {
-            zn[0] = Zb[20 * (k + 1) + ln];
-            zn[1] = Zb[20 * (k + 1) + 16 + (ln & 3)];
+            knot_load(Zb + 20 * (k + 1), ln, zn[0], zn[1]);
             if constexpr (kHasK) {
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
@@ -708,7 +601,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_covariance(BatchParams P, Co
         for (int m = 0; m < 4; ++m) {
             fv[m] = 0.0;
             if constexpr (kHasK) {
-                if (Mb) fv[m] = row_sum16_bc(own ? L[kCK + 16 * m + j] * g[m] : 0.0);
+                if (Mb) fv[m] = row_sum16(own ? L[kCK + 16 * m + j] * g[m] : 0.0);
             }
         }
         emit(k, fv);
@@ -745,11 +638,6 @@ __global__ __launch_bounds__(kWave) void k_tracking_covariance(BatchParams P, Co
 
 
 // ---- k_tracking_rollout_jvp ----
-// v from lane i of the same DPP row (row_newbcast), in every lane of the row
-template <int kLaneInRow>
-__device__ __forceinline__ double row_bcast(double v) {
-    return dpp_f64_bc<0x150 + kLaneInRow>(v);
-}
 template <int... I>
 __device__ __forceinline__ void row_bcast_first(double v, double (&out)[sizeof...(I)], std::integer_sequence<int, I...>) {
     ((out[I] = row_bcast<I>(v)), ...);
@@ -766,12 +654,8 @@ template <bool kHasK, bool kHasKd, bool kHasZd>
 __device__ __forceinline__ void jvp_load(JvpKnot& s, const double* __restrict__ Zo, const double* __restrict__ Zd,
                                          const double* __restrict__ Zr, const double* __restrict__ Kk,
                                          const double* __restrict__ Kdk, int k, int ln, int j) {
-    s.z0 = Zo[20 * k + ln];
-    s.z1 = Zo[20 * k + 16 + (ln & 3)];
-    if constexpr (kHasZd) {
-        s.zd0 = Zd[20 * k + ln];
-        s.zd1 = Zd[20 * k + 16 + (ln & 3)];
-    }
+    knot_load(Zo + 20 * k, ln, s.z0, s.z1);
+    if constexpr (kHasZd) knot_load(Zd + 20 * k, ln, s.zd0, s.zd1);
     if constexpr (kHasK) {
 #pragma unroll
         for (int m = 0; m < 4; ++m) s.kc[m] = Kk[60 * (int64_t)k + 15 * m + j];
@@ -801,18 +685,10 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, c
                                                                 const double* __restrict__ x0_dot,
                                                                 double* __restrict__ Zout_dot) {
     static_assert(kHasK || !kHasKd, "Kdot needs K");
-    const int lane = threadIdx.x;
-    const int ln = lane & 15, row = lane >> 4;
-    const bool own = ln < 15;
-    const int j = own ? ln : 14;  // lane 15 reads lane 14's slots and contributes nothing
-    const int wave = xcd_contiguous_index(blockIdx.x, (P.B + kRows - 1) / kRows);
-    const int b = wave * kRows + row;
-    const bool valid = b < P.B;
-    const int bc = valid ? b : P.B - 1;
-    const int N = P.N;
-    const ProblemDesc pd = P.desc[bc];
-    const int kt = pd.k_trans, im = pd.init_mode;
-    const Model M(P);
+    const Row16 r16 = row16_of(P);  // lane 15 reads lane 14's slots and contributes nothing
+    const int ln = r16.ln, j = r16.j, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
+    const bool own = r16.own, valid = r16.valid;
+    const Model& M = r16.M;
     const int64_t zo = (int64_t)bc * P.z_stride, ko = (int64_t)bc * (N - 1) * (QLN_TRACK_NU * QLN_NX);
     const double* __restrict__ Zo = Zout + zo;
     const double* __restrict__ Zd = kHasZd ? Zref_dot + zo : nullptr;
@@ -851,25 +727,24 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, c
             for (int m = 0; m < 4; ++m) {
                 double t = cur.kc[m] * d;
                 if constexpr (kHasKd) t = fma(cur.kd[m], cur.z0 - cur.xr, t);
-                dF[m] = dF[m] - row_sum16_bc(own ? t : 0.0);
+                dF[m] = dF[m] - row_sum16(own ? t : 0.0);
             }
         }
         // ---- row j of [A B]: the visitor's entries at the lane's row (rows 2 and 9 of A: at the lane's column) ----
-        // row 14 of the jump knot: the jump map keeps the clock (its Jacobian's mask zeroes the row, quirk Q1)
         double a2 = 0.0, a9 = 0.0, dg = 0.0, cp = 0.0, bj[4] = {0.0, 0.0, 0.0, 0.0}, hj = 0.0;
-        for_each_step_entry(blk, [&](auto r, auto c, double val) {
+        for_each_rollout_entry(blk, [&](auto r, auto c, double val) {
             if constexpr (c < 15) {
                 if constexpr (r == 2) a2 = (j == c) ? val : a2;
                 else if constexpr (r == 9) a9 = (j == c) ? val : a9;
-                else if constexpr (r == c) dg = (j == r) ? ((r == 14) ? 1.0 : val) : dg;
+                else if constexpr (r == c) dg = (j == r) ? val : dg;
                 else cp = (j == r) ? val : cp;  // r == c - 7 (a_structure_ok)
             } else if constexpr (kHasK || kHasZd) {
                 if constexpr (c < 19) bj[c - 15] = (j == r) ? val : bj[c - 15];
-                else hj = (j == r) ? ((r == 14) ? 1.0 : val) : hj;
+                else hj = (j == r) ? val : hj;
             }
         });
-        const double dxc = dpp_f64_bc<0x107>(dx);  // row_shl:7, dx[j+7] (0 past the row's end: bound_ctrl)
-        const double s2 = row_sum16_bc(own ? a2 * dx : 0.0), s9 = row_sum16_bc(own ? a9 * dx : 0.0);
+        const double dxc = row_shl7(dx);  // dx[j+7], 0 past the row's end
+        const double s2 = row_sum16(own ? a2 * dx : 0.0), s9 = row_sum16(own ? a9 * dx : 0.0);
         double acc = (j == 2) ? s2 : (j == 9) ? s9 : fma(cp, dxc, dg * dx);
         if constexpr (kHasK || kHasZd) {
 #pragma unroll
@@ -877,11 +752,9 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, c
             if constexpr (kHasZd) acc = fma(hj, dh, acc);
         }
         // ---- the knot's twenty entries of Zout_dot: dx_k and (dF_k, dh_k) ----
-        if (valid) {
-            double* __restrict__ o = Od + 20 * k;
-            o[ln] = own ? dx : dF[0];
-            if (ln < 4) o[16 + ln] = ln == 0 ? dF[1] : ln == 1 ? dF[2] : ln == 2 ? dF[3] : dh;
-        }
+        // (dF, dh) become one array only here: held as one through the knot it costs up to 8 VGPRs
+        // (profiles/row16_refactor_resource_usage.txt)
+        if (valid) knot_store(Od + 20 * k, r16, dx, {dF[0], dF[1], dF[2], dF[3], dh});
         dx = own ? acc : 0.0;
     }
     if (valid && own) Od[20 * (N - 1) + j] = dx;
@@ -897,17 +770,8 @@ hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const dou
         w.Qf[i] = Qfd[i];
     }
     for (int i = 0; i < 4; ++i) w.R[i] = Rd[i];
-    const int waves = (p.B + kRows - 1) / kRows;
-    bool form_once = kTrackFormOnceDefault;
-#ifdef QLN_TUNING
-    // tuning build only: QLN_TRACK_FORM_ONCE=0|1 selects the variant for A/B runs (bench/tracking_timing.py)
-    if (const char* e = getenv("QLN_TRACK_FORM_ONCE")) form_once = atoi(e) != 0;
-#endif
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(xcd_grid(waves)), dim3(kWave), 0, stream, p, w, Zref, K, P); };
-    if (form_once)
-        P ? go(k_tracking_lqr<true, true>) : go(k_tracking_lqr<false, true>);
-    else
-        P ? go(k_tracking_lqr<true, false>) : go(k_tracking_lqr<false, false>);
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, w, Zref, K, P); };
+    P ? go(k_tracking_lqr<true>) : go(k_tracking_lqr<false>);
     return hipGetLastError();
 }
 
@@ -919,9 +783,8 @@ hipError_t launch_tracking_rollout(const BatchParams& p, const double* Zref, con
 
 hipError_t launch_tracking_rollout_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
                                        const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, hipStream_t stream) {
-    const int waves = (p.B + kRows - 1) / kRows;
     auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(xcd_grid(waves)), dim3(kWave), 0, stream, p, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar);
+        hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar);
     };
     K ? go(k_tracking_rollout_vjp<true>) : go(k_tracking_rollout_vjp<false>);
     return hipGetLastError();
@@ -931,9 +794,8 @@ hipError_t launch_tracking_rollout_jvp(const BatchParams& p, const double* Zref,
                                        const double* Zref_dot, const double* K_dot, const double* x0_dot, double* Zout_dot,
                                        hipStream_t stream) {
     if (K_dot && !K) return hipErrorInvalidValue;
-    const int waves = (p.B + kRows - 1) / kRows;
     auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(xcd_grid(waves)), dim3(kWave), 0, stream, p, Zref, K, Zout, Zref_dot, K_dot, x0_dot,
+        hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, Zref, K, Zout, Zref_dot, K_dot, x0_dot,
                            Zout_dot);
     };
     if (K_dot)
@@ -949,9 +811,8 @@ hipError_t launch_tracking_covariance(const BatchParams& p, const double* Zout, 
                                       int sigma0_batch, const double* Wd, double* Sigma, double* marg, hipStream_t stream) {
     CovNoise w;
     for (int i = 0; i < 15; ++i) w.w[i] = Wd ? Wd[i] : 0.0;
-    const int waves = (p.B + kRows - 1) / kRows;
     auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(xcd_grid(waves)), dim3(kWave), 0, stream, p, w, Zout, K, Sigma0, sigma0_batch, Sigma, marg);
+        hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, w, Zout, K, Sigma0, sigma0_batch, Sigma, marg);
     };
     K ? go(k_tracking_covariance<true>) : go(k_tracking_covariance<false>);
     return hipGetLastError();
