@@ -23,9 +23,12 @@
 // accelerations.  Differentiating these gives every entry of ForwardDiff.jacobian of the RK4 step
 // (src/planar_quadruped.jl:225-248) up to rounding.
 #include "qln_kernel_common.h"
+#include "qln_launch_plan.h"
 
 #include <algorithm>
+#include <tuple>
 #include <type_traits>
+#include <utility>
 
 #if defined(QLN_TUNING) || defined(QLN_PREFETCH_KNOB)
 #include <cstdlib>
@@ -262,12 +265,12 @@ __global__ __launch_bounds__(kWave, W) void k_constraint_jacobian(BatchParams P,
     // hold the staged Z slice (20*64+15 doubles at offset 0) and, behind it, the chunk's dynamics
     // residuals (64*15 doubles at offset kCStage).
     static_assert(KC <= kWave, "one lane per knot of a chunk");
-    constexpr int kZSlice = KC * 20 + 15;
-    constexpr int kCStage = (kZSlice + 1) & ~1;
+    constexpr int kZSlice = chunk_z_slice(KC);
+    constexpr int kCStage = chunk_c_stage(KC);
     // structural format: up to 71 values per knot of the chunk, +1 so that the LDS image can start at the parity of
     // its global offset (16-byte pieces then line up on both sides)
     // Dense blocks: a static tile of T blocks.  Structural format: the tile is DYNAMIC LDS sized by the host for the batch
-    // (nnz_lds_doubles below: the longest run a sub-tile of this batch can have, the staged slice and the residual stage) --
+    // (nnz_lds_bytes, qln_launch_plan.h: the longest run a sub-tile of this batch can have, the staged slice and the residual stage) --
     // 71 values per knot is the worst case, a batch whose problems spend most knots in mode 3 (57) needs less, and what a
     // workgroup does not reserve another can: config 3's problems take 19.1 KB instead of 22.7 KB, 8 waves per CU instead of 7.
     constexpr int kTile = NNZ ? 2 : T * kBlk;
@@ -1128,99 +1131,101 @@ __global__ __launch_bounds__(256) void k_friction_rows(BatchParams P, const doub
     }
 }
 
-// Dynamic LDS of the structural-format instantiations (bytes): the longest run of vals a sub-tile of `sub` knots can be
-// in this batch -- a chunk's run grows with k_trans (71 values per knot before the transition, 57 after), so the batch's
-// largest k_trans bounds it -- plus the parity slot, and never less than what aliases the tile: the staged slice of Z
-// (written unpredicated in whole wave-rows), the residual stage and, for qln_eval_all, the objective terms.
-inline size_t nnz_lds_bytes(const BatchParams& p, int KC, int sub, bool with_f) {
-    const int N = p.N, kt = std::min(std::max(p.kt_max, 1), N + 1);
-    int longest = 0;
-    for (int kc0 = 0; kc0 < N - 1; kc0 += KC) {
-        const int nk = std::min(KC, N - 1 - kc0);
-        for (int t0 = 0; t0 < nk; t0 += sub) {
-            const int nkt = std::min(sub, nk - t0);
-            // x of the run's knots lie before the transition knot at the batch's largest k_trans (71 values each), and no
-            // problem of the batch has more of them; every other knot has at most 57: 57 nkt + 14 x bounds every problem's run
-            const int x = std::min(nkt, std::max(0, std::min(kt - 2, N - 1) - (kc0 + t0)));
-            longest = std::max(longest, step_nnz(2) * nkt + (step_nnz(0) - step_nnz(2)) * x);
-        }
-    }
-    const int z_slice = KC * 20 + 15, c_stage = (z_slice + 1) & ~1;
-    int need = std::max(c_stage + KC * 15 + (with_f ? kWave : 0), ((z_slice + kWave - 1) / kWave) * kWave);
-    need = std::max(need, longest + 2);
-    return (size_t)((need + 1) & ~1) * sizeof(double);
-}
+// Launch of k_constraint_jacobian.  plan_launch() (qln_launch_plan.h) says which instantiation runs, with what grid, LDS
+// and prefetch; here are the list of the instantiations the library holds and the one place that launches them.
+static_assert(kStageRow == kWave && kBlk == 300, "qln_launch_plan.h sizes the LDS and the outputs with the kernel's constants");
+
+template <int T, int KC, int W, bool WITH_C, bool WITH_J, bool NNZ, bool SPLIT, bool WITH_F>
+struct Shape {};
+
+// Every instantiation the product ships, each in both STREAM values: 17 shapes, 34 kernels.  A plan that names another
+// shape is refused (hipErrorInvalidValue): a new rule in plan_launch() needs its entry here.
+//    T  KC  W  WITH_C WITH_J NNZ    SPLIT  WITH_F
+using ShippedShapes = std::tuple<
+    Shape<12, 64, 1, true, true, false, false, false>, Shape<12, 64, 1, false, true, false, false, false>,  // dense c + J (the headline), J
+    Shape<0, 40, 1, true, true, true, false, false>, Shape<0, 40, 1, false, true, true, false, false>,      // structural, 40-knot chunks
+    Shape<0, 64, 1, true, true, true, false, false>, Shape<0, 64, 1, false, true, true, false, false>,      // structural, 64-knot chunks
+    Shape<5, 40, 2, true, false, false, false, false>, Shape<8, 64, 2, true, false, false, false, false>,   // c alone
+    Shape<5, 40, 2, true, false, false, false, true>, Shape<8, 64, 2, true, false, false, false, true>,     // f + c
+    Shape<16, 64, 1, true, true, false, false, true>, Shape<0, 40, 1, true, true, true, false, true>,       // qln_eval_all: dense, structural
+    // one workgroup per chunk: dense (c alone in either format), structural
+    Shape<16, 16, 1, true, true, false, true, false>, Shape<16, 16, 1, false, true, false, true, false>, Shape<16, 16, 1, true, false, false, true, false>,
+    Shape<0, 16, 2, true, true, true, true, false>, Shape<0, 16, 2, false, true, true, true, false>>;
 
 #ifdef QLN_TUNING
-inline void apply_floor_mode() {
-    static const int done = [] {
-        const char* e = getenv("QLN_FLOOR");
-        const int v = e ? atoi(e) : 0;
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_floor_mode), &v, sizeof v);
-        return 1;
-    }();
-    (void)done;
-}
-#endif
-
-// bits 8.. of the kernel's flags: how many problems ahead on its XCD a workgroup prefetches into L2 (0 = off).  The knob
-// builds (make tuning / prefetchknob) let QLN_PREFETCH_AHEAD override the caller's choice (bench/prefetch_ahead.py).
-inline uint32_t prefetch_flags(uint32_t ahead_default, uint32_t what_default = 0u) {
-#if defined(QLN_TUNING) || defined(QLN_PREFETCH_KNOB)
-    static const int ahead = [] {
-        const char* e = getenv("QLN_PREFETCH_AHEAD");
-        return e ? atoi(e) : -1;
-    }();
-    static const int mask = [] {  // QLN_PREFETCH_MASK: 1 = slice of Z, 2 = boundary vectors, 4 = descriptor
-        const char* e = getenv("QLN_PREFETCH_MASK");
-        return e ? atoi(e) : -1;
-    }();
-    if (ahead >= 0) ahead_default = (uint32_t)ahead;
-    if (mask >= 0) what_default = ((mask & 1) ? 0u : kPrefetchNoZ) | ((mask & 2) ? kPrefetchBnd : 0u) | ((mask & 4) ? kPrefetchDesc : 0u);
-#endif
-    return (ahead_default << 8) | what_default;
-}
-
-template <int T, int KC, int W, bool NNZ = false, bool SPLIT = false>
-hipError_t launch_cj_t(const BatchParams& p, int32_t b_begin, int32_t nb, const double* Z, double* c, double* vals,
-                       uint32_t flags, hipStream_t stream, uint32_t prefetch_ahead = 0) {
-    dim3 grid(xcd_grid(SPLIT ? nb * ((p.N - 2) / KC + 1) : nb)), block(kWave);
-#ifdef QLN_TUNING
-    apply_floor_mode();
-    // tuning build only: extra (unused) dynamic LDS per workgroup lowers the number of resident waves
-    static const unsigned pad = [] {
-        const char* e = getenv("QLN_PAD_LDS");
-        return e ? (unsigned)atoi(e) : 0u;
-    }();
+// the tuning build adds kVariants' rows: c + J, J and c alone of each, as far as the row serves them (nothing otherwise)
+template <size_t I, bool WITH_C, bool WITH_J>
+using VariantShapes = std::conditional_t<kVariants[I].when == kNoVals ? !WITH_J : (kVariants[I].when != kStructuralVals || WITH_J),
+                                         std::tuple<Shape<kVariants[I].shape.T, kVariants[I].shape.KC, kVariants[I].shape.W, WITH_C, WITH_J,
+                                                          kVariants[I].shape.nnz, kVariants[I].shape.split, false>>,
+                                         std::tuple<>>;
+template <size_t... I>
+auto variant_shapes(std::index_sequence<I...>)
+    -> decltype(std::tuple_cat(VariantShapes<I, true, true>{}..., VariantShapes<I, false, true>{}..., VariantShapes<I, true, false>{}...));
+using LaunchableShapes = decltype(std::tuple_cat(ShippedShapes{}, variant_shapes(std::make_index_sequence<std::size(kVariants)>{})));
 #else
-    constexpr unsigned pad = 0;
+using LaunchableShapes = ShippedShapes;
 #endif
-    if (!SPLIT) flags = (flags & 0xffu) | prefetch_flags(prefetch_ahead);
-    // outputs larger than the caches are streamed (non-temporal stores); small ones stay cacheable
-    const bool stream_out = (int64_t)nb * (p.N - 1) * (NNZ ? step_nnz(0) : kBlk) * 8 > ((int64_t)512 << 20);
-    auto go = [&](auto with_c, auto with_j, auto streamed) {
-        constexpr bool WC = decltype(with_c)::value, WJ = decltype(with_j)::value, ST = decltype(streamed)::value;
-        const unsigned lds = (NNZ ? (unsigned)nnz_lds_bytes(p, KC, T > 0 ? T : KC, false) : 0u) + ((WC && WJ) ? pad : 0u);
-        hipLaunchKernelGGL((k_constraint_jacobian<T, KC, W, WC, WJ, NNZ, SPLIT, ST>), grid, block, lds, stream, p,
-                           b_begin, nb, Z, c, vals, flags);
-    };
-    using yes = std::true_type;
-    using no = std::false_type;
-    if (c && vals) stream_out ? go(yes{}, yes{}, yes{}) : go(yes{}, yes{}, no{});
-    else if (c) stream_out ? go(yes{}, no{}, yes{}) : go(yes{}, no{}, no{});
-    else stream_out ? go(no{}, yes{}, yes{}) : go(no{}, yes{}, no{});
-    return hipGetLastError();
+
+// go(kernel) for the plan's instantiation if this shape is the plan's
+template <int T, int KC, int W, bool WITH_C, bool WITH_J, bool NNZ, bool SPLIT, bool WITH_F, class Go>
+bool launch_if_planned(Shape<T, KC, W, WITH_C, WITH_J, NNZ, SPLIT, WITH_F>, const LaunchPlan& pl, Go& go) {
+    if (pl.T != T || pl.KC != KC || pl.W != W || pl.with_c != WITH_C || pl.with_j != WITH_J || pl.nnz != NNZ || pl.split != SPLIT ||
+        pl.with_f != WITH_F)
+        return false;
+    pl.stream ? go(k_constraint_jacobian<T, KC, W, WITH_C, WITH_J, NNZ, SPLIT, true, WITH_F>)
+              : go(k_constraint_jacobian<T, KC, W, WITH_C, WITH_J, NNZ, SPLIT, false, WITH_F>);
+    return true;
+}
+template <class... S, class Go>
+bool launch_planned(std::tuple<S...>, const LaunchPlan& pl, Go& go) { return (launch_if_planned(S{}, pl, go) || ...); }
+
+// a knob of the tuning builds from the environment; the product reads none
+inline int env_knob(const char* name, int unset = 0) {
+#if defined(QLN_TUNING) || defined(QLN_PREFETCH_KNOB)
+    if (const char* e = getenv(name)) return atoi(e);
+#endif
+    return unset;
 }
 
-// constraint-only launch of one instantiation (eval_c! alone: what a line search or Ipopt's eval_constraint callback asks for)
-template <int T, int KC, int W>
-hipError_t launch_c_only_t(const BatchParams& p, int32_t b_begin, int32_t nb, const double* Z, double* c, hipStream_t stream) {
-    dim3 grid(xcd_grid(nb)), block(kWave);
-    const bool stream_out = (int64_t)nb * row_layout(p.N, 0).m * 8 > ((int64_t)512 << 20);  // k_trans = 0: more rows than any problem has
-    if (stream_out) hipLaunchKernelGGL((k_constraint_jacobian<T, KC, W, true, false, false, false, true>), grid, block, 0, stream, p, b_begin, nb, Z, c, nullptr, prefetch_flags(0));
-    else hipLaunchKernelGGL((k_constraint_jacobian<T, KC, W, true, false, false, false, false>), grid, block, 0, stream, p, b_begin, nb, Z, c, nullptr, prefetch_flags(0));
-    return hipGetLastError();
+// fill the request, plan, launch
+hipError_t launch_fused(const BatchParams& p, int32_t b_begin, int32_t nb, const double* Z, double* c, double* vals, double* f,
+                        double* grad, uint32_t flags, hipStream_t stream) {
+    LaunchRequest r;
+    r.nb = nb, r.N = p.N, r.jac_format = p.jac_format, r.kt_max = p.kt_max, r.prefer_latency = (flags & kLaunchSplit) != 0;
+    r.c = c != nullptr, r.vals = vals != nullptr, r.f = f != nullptr, r.grad = grad != nullptr;
+#if defined(QLN_TUNING) || defined(QLN_PREFETCH_KNOB)
+    static const int ahead = env_knob("QLN_PREFETCH_AHEAD", -1), mask = env_knob("QLN_PREFETCH_MASK", -1);
+    r.prefetch_ahead = ahead, r.prefetch_mask = mask;
+#endif
+#ifdef QLN_TUNING
+    // QLN_FLOOR is set once, by the first launch of any family (it used to be set by c / J launches only, never by eval_all or f + c)
+    static const int variant = env_knob("QLN_VARIANT"), pad = env_knob("QLN_PAD_LDS"), floor_mode = env_knob("QLN_FLOOR");
+    [[maybe_unused]] static const hipError_t floor_set = hipMemcpyToSymbol(HIP_SYMBOL(g_floor_mode), &floor_mode, sizeof floor_mode);
+    r.variant = variant, r.pad_lds = (unsigned)pad;
+#endif
+    const LaunchPlan pl = plan_launch(r);
+    flags = kernel_flags(pl, (flags & QLN_JAC_WRITE_CONSTANTS) != 0);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(xcd_grid(pl.workgroups)), dim3(kWave), pl.lds_bytes, stream, p, b_begin, nb, Z, c, vals, flags, f, grad);
+    };
+    return launch_planned(LaunchableShapes{}, pl, go) ? hipGetLastError() : hipErrorInvalidValue;
 }
+
+// One shared cost table, a horizon of at most one lane per knot and a batch that fills the chip: the objective and its
+// gradient then run persistent waves with lane = knot's cost record in registers (k_objective_shared and
+// k_objective_gradient_shared<KI>, KI = 16-byte loads per lane and slice of Z: 1 .. 10)
+inline bool shared_cost_table(const BatchParams& p) { return p.cost_batch == 1 && p.N <= kWave && p.B >= 4096; }
+inline int slice_loads(int N) { return ((20 * N - 6) / 2 + kWave - 1) / kWave; }
+
+// what fn(std::integral_constant<int, ki>{}) returns, for ki in 1 .. 10 (kSliceLoads); hipErrorInvalidValue for any other ki
+template <class Fn, int... I>
+hipError_t with_slice_loads(int ki, Fn&& fn, std::integer_sequence<int, I...>) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((ki == I + 1 && (e = fn(std::integral_constant<int, I + 1>{}), true)) || ...);
+    return e;
+}
+constexpr std::make_integer_sequence<int, 10> kSliceLoads{};
 
 }  // namespace
 
@@ -1234,138 +1239,18 @@ extern "C" int qln_diag_set_stamps(void* dev_ptr) {
 hipError_t launch_constraint_jacobian(const BatchParams& p, int32_t b_begin, int32_t nb, const double* Z, double* c,
                                       double* vals, uint32_t flags, hipStream_t stream) {
     if (nb <= 0 || (!c && !vals)) return hipSuccess;
-    // Latency-bound callers (the host-pointer MOI mode: one problem or a handful) ask for one workgroup per 16-knot
-    // chunk instead of per problem: the launch is then as long as one chunk (profiles/r01_small_batch_split.txt: it
-    // pays below ~256 problems only, so the batched entry points never ask for it).
-    if (flags & kLaunchSplit) {
-        flags &= ~kLaunchSplit;
-        if (nb <= 256 && p.N > 17) {
-            if (vals && p.jac_format == QLN_JAC_FORMAT_STRUCTURAL) return launch_cj_t<0, 16, 2, true, true>(p, b_begin, nb, Z, c, vals, flags, stream);
-            return launch_cj_t<16, 16, 1, false, true>(p, b_begin, nb, Z, c, vals, flags, stream);
-        }
-    }
-    // Shipping configuration: T=12 (28.8 KB tile; 256 VGPRs + 17 AGPRs => one wave per SIMD, 4 waves per CU) when the Jacobian is written (below), 40- or 64-knot chunks
-    // with two waves per SIMD for the constraint-only launch (profiles/r01_variants.txt, r03_dense_floor.txt, r03_c_only_variants.txt).
-#ifdef QLN_TUNING
-    // tuning build only (make tuning -> libqln_hip_tuning.so): QLN_VARIANT selects other instantiations for A/B runs
-    static const int variant = [] {
-        const char* e = getenv("QLN_VARIANT");
-        return e ? atoi(e) : 0;
-    }();
-    switch (variant) {
-        case 1: return launch_cj_t<8, 64, 2>(p, b_begin, nb, Z, c, vals, flags, stream);
-        case 2: return launch_cj_t<12, 64, 1>(p, b_begin, nb, Z, c, vals, flags, stream);
-        case 3: return launch_cj_t<16, 64, 1>(p, b_begin, nb, Z, c, vals, flags, stream);
-        // the shipping tile with the prefetch, register budget of one / two waves per SIMD (4 / 5 waves per CU; two: 104 B of scratch)
-        case 4: return launch_cj_t<12, 64, 1>(p, b_begin, nb, Z, c, vals, flags, stream, (c && p.N - 1 <= 64) ? kDensePrefetchAhead : 0u);
-        case 5: return launch_cj_t<12, 64, 2>(p, b_begin, nb, Z, c, vals, flags, stream, (c && p.N - 1 <= 64) ? kDensePrefetchAhead : 0u);
-        case 6: return launch_cj_t<10, 64, 2>(p, b_begin, nb, Z, c, vals, flags, stream, (c && p.N - 1 <= 64) ? kDensePrefetchAhead : 0u);
-        // 40-knot chunks: 13 staging registers instead of 21 -- the fused instantiation then fits the two-waves-per-SIMD budget
-        case 7: return launch_cj_t<12, 40, 2>(p, b_begin, nb, Z, c, vals, flags, stream, (c && p.N - 1 <= 40) ? kDensePrefetchAhead : 0u);
-        case 8: return launch_cj_t<8, 40, 2>(p, b_begin, nb, Z, c, vals, flags, stream, (c && p.N - 1 <= 40) ? kDensePrefetchAhead : 0u);
-        case 9: return launch_cj_t<16, 40, 2>(p, b_begin, nb, Z, c, vals, flags, stream, (c && p.N - 1 <= 40) ? kDensePrefetchAhead : 0u);
-        case 10: return launch_cj_t<10, 40, 2>(p, b_begin, nb, Z, c, vals, flags, stream, (c && p.N - 1 <= 40) ? kDensePrefetchAhead : 0u);
-        default: break;
-    }
-    if (!vals) switch (variant) {  // constraint-only launch: chunk size / tile (= LDS) / register budget
-        case 31: return launch_c_only_t<5, 40, 2>(p, b_begin, nb, Z, c, stream);
-        case 32: return launch_c_only_t<5, 40, 3>(p, b_begin, nb, Z, c, stream);
-        case 33: return launch_c_only_t<5, 40, 4>(p, b_begin, nb, Z, c, stream);
-        case 34: return launch_c_only_t<8, 64, 3>(p, b_begin, nb, Z, c, stream);
-        case 35: return launch_c_only_t<8, 64, 4>(p, b_begin, nb, Z, c, stream);
-        case 36: return launch_c_only_t<4, 32, 3>(p, b_begin, nb, Z, c, stream);
-        case 37: return launch_c_only_t<4, 32, 4>(p, b_begin, nb, Z, c, stream);
-        default: break;
-    }
-    switch (variant) {  // small-batch launches: one workgroup per chunk
-        case 21: if (p.jac_format == QLN_JAC_FORMAT_DENSE_BLOCKS) return launch_cj_t<16, 16, 1, false, true>(p, b_begin, nb, Z, c, vals, flags, stream); break;
-        case 22: if (p.jac_format == QLN_JAC_FORMAT_DENSE_BLOCKS) return launch_cj_t<8, 8, 2, false, true>(p, b_begin, nb, Z, c, vals, flags, stream); break;
-        case 23: if (p.jac_format == QLN_JAC_FORMAT_DENSE_BLOCKS) return launch_cj_t<10, 10, 2, false, true>(p, b_begin, nb, Z, c, vals, flags, stream); break;
-        case 24: if (p.jac_format == QLN_JAC_FORMAT_STRUCTURAL && vals) return launch_cj_t<0, 16, 2, true, true>(p, b_begin, nb, Z, c, vals, flags, stream); break;
-        case 25: if (p.jac_format == QLN_JAC_FORMAT_STRUCTURAL && vals) return launch_cj_t<0, 8, 2, true, true>(p, b_begin, nb, Z, c, vals, flags, stream); break;
-        default: break;
-    }
-    if (vals && p.jac_format == QLN_JAC_FORMAT_STRUCTURAL) switch (variant) {
-        case 11: return launch_cj_t<0, 32, 2, true>(p, b_begin, nb, Z, c, vals, flags, stream);
-        case 12: return launch_cj_t<0, 40, 2, true>(p, b_begin, nb, Z, c, vals, flags, stream);
-        case 13: return launch_cj_t<0, 32, 1, true>(p, b_begin, nb, Z, c, vals, flags, stream);
-        case 14: return launch_cj_t<0, 64, 1, true>(p, b_begin, nb, Z, c, vals, flags, stream);
-        case 15: return launch_cj_t<0, 64, 2, true>(p, b_begin, nb, Z, c, vals, flags, stream);
-        case 16: return launch_cj_t<20, 40, 3, true>(p, b_begin, nb, Z, c, vals, flags, stream);  // two sub-tiles, three waves per SIMD
-        case 17: return launch_cj_t<20, 40, 2, true>(p, b_begin, nb, Z, c, vals, flags, stream);
-        case 18: return launch_cj_t<0, 40, 2, true>(p, b_begin, nb, Z, c, vals, flags, stream);
-        case 19: return launch_cj_t<14, 40, 3, true>(p, b_begin, nb, Z, c, vals, flags, stream);
-        default: break;
-    }
-#endif
-    if (!vals) {
-        // constraint-only launch (eval_c! alone: a line search's or Ipopt's eval_constraint call): no tile to fill, so the LDS holds
-        // only the staged slice and the residual stage.  40-knot chunks (12 KB of LDS, 13 staging registers per lane) where
-        // they make no more passes than 64-knot chunks would (N <= 41, 66 <= N <= 81, ...): 0.157 -> 0.149 ms at config 3
-        // (profiles/r03_c_only_variants.txt; three or four waves per SIMD need <= 168 / 128 VGPRs and spill: 0.18 / 0.30 ms)
-        const int knots = p.N - 1;
-        if ((knots + 39) / 40 == (knots + 63) / 64) return launch_c_only_t<5, 40, 2>(p, b_begin, nb, Z, c, stream);
-        return launch_c_only_t<8, 64, 2>(p, b_begin, nb, Z, c, stream);
-    }
-    // structural format: 40-knot chunks (dynamic LDS sized for the batch, 19.1 KB at config 3; 2 waves per SIMD; profiles/r01_structural_variants.txt)
-    // Horizons that 64-knot chunks cover in fewer passes (N - 1 = 41 .. 64, 81 .. 128, ...) take those: N = 65 0.378 against 0.410 ms
-    // for the same knot points as config 3 (bench/packing_probe.py, profiles/r03_packing_probe.txt)
-    if (p.jac_format == QLN_JAC_FORMAT_STRUCTURAL) {
-        const int knots = p.N - 1;
-        if ((knots + 39) / 40 == (knots + 63) / 64) return launch_cj_t<0, 40, 1, true>(p, b_begin, nb, Z, c, vals, flags, stream);
-        return launch_cj_t<0, 64, 1, true>(p, b_begin, nb, Z, c, vals, flags, stream);
-    }
-    // dense blocks: a 12-block tile (28.8 KB of LDS would admit 5 waves per CU; the fused instantiation with 64-knot chunks takes
-    // 256 VGPRs + 17 AGPRs, i.e. one wave per SIMD = 4 waves per CU.  40-knot chunks fit the two-waves-per-SIMD budget without scratch
-    // -- 5 / 6 / 8 waves per CU with T = 12 / 10 / 8 -- and are no faster: 1.044-1.047 / 1.076-1.078 / 1.070-1.072 ms against
-    // 1.047 ms, same box: more concurrent write fronts cost, profiles/r03_dense_floor.txt).  All tile sizes sit on the launch's floor;
-    // on region-placed buffers T = 12 is the fastest by 0.5-1 % (config 3: 1.060-1.063 against 1.069-1.074 ms for T = 16, config 4:
-    // 2.155-2.162 against 2.168-2.174 ms; round 1 chose T = 16 on buffers lying in one region)
-    // One-chunk problems (N <= 65) prefetch the slice of the workgroup 64 problems ahead on the XCD into L2 (kDensePrefetchAhead):
-    // config 3 1.056-1.068 -> 1.031-1.040 ms for every distance from 16 to 1024, same box (profiles/r03_prefetch_ahead.txt);
-    // two-chunk problems (config 4), the structural format and the constraint-only launch do not gain and stay without.
-    return launch_cj_t<12, 64, 1>(p, b_begin, nb, Z, c, vals, flags, stream, (c && p.N - 1 <= 64) ? kDensePrefetchAhead : 0u);
+    return launch_fused(p, b_begin, nb, Z, c, vals, nullptr, nullptr, flags, stream);
 }
 
 // f, grad, c and the Jacobian values of the whole batch from ONE read of Z (qln_eval_all)
 hipError_t launch_eval_all(const BatchParams& p, const double* Z, double* f, double* grad, double* c, double* vals, uint32_t flags,
                            hipStream_t stream) {
-    const int nb = p.B;
-    dim3 grid(xcd_grid(nb)), block(kWave);
-    const bool structural = p.jac_format == QLN_JAC_FORMAT_STRUCTURAL;
-    const bool stream_out = (int64_t)nb * (p.N - 1) * (structural ? step_nnz(0) : kBlk) * 8 > ((int64_t)512 << 20);
-    // dense one-chunk problems prefetch like the fused launch, and the later problem's boundary vectors and descriptor with the
-    // slice: 1.18-1.20 -> 1.11-1.15 ms at config 3 (the slice alone: 1.16-1.19; for the fused launch WITHOUT the objective the two
-    // extras cost what the slice gains -- profiles/r03_prefetch_ahead.txt)
-    flags = (flags & QLN_JAC_WRITE_CONSTANTS) |
-            ((!structural && p.N - 1 <= 64) ? prefetch_flags(kDensePrefetchAhead, kPrefetchBnd | kPrefetchDesc) : prefetch_flags(0));
-    if (structural) {
-        const unsigned lds = (unsigned)nnz_lds_bytes(p, 40, 40, true);
-        if (stream_out) hipLaunchKernelGGL((k_constraint_jacobian<0, 40, 1, true, true, true, false, true, true>), grid, block, lds, stream, p, 0, nb, Z, c, vals, flags, f, grad);
-        else hipLaunchKernelGGL((k_constraint_jacobian<0, 40, 1, true, true, true, false, false, true>), grid, block, lds, stream, p, 0, nb, Z, c, vals, flags, f, grad);
-    } else {
-        if (stream_out) hipLaunchKernelGGL((k_constraint_jacobian<16, 64, 1, true, true, false, false, true, true>), grid, block, 0, stream, p, 0, nb, Z, c, vals, flags, f, grad);
-        else hipLaunchKernelGGL((k_constraint_jacobian<16, 64, 1, true, true, false, false, false, true>), grid, block, 0, stream, p, 0, nb, Z, c, vals, flags, f, grad);
-    }
-    return hipGetLastError();
+    return launch_fused(p, 0, p.B, Z, c, vals, f, grad, flags & QLN_JAC_WRITE_CONSTANTS, stream);
 }
 
-// eval_f + eval_c! of the whole batch from ONE read of Z (qln_eval_objective_and_constraint): what a line search, or Ipopt's
-// filter at a trial point, asks for -- objective and constraints, no derivatives
+// eval_f + eval_c! of the whole batch from ONE read of Z (qln_eval_objective_and_constraint): what a line search asks for
 hipError_t launch_objective_and_constraint(const BatchParams& p, const double* Z, double* f, double* c, hipStream_t stream) {
-    const int nb = p.B;
-    dim3 grid(xcd_grid(nb)), block(kWave);
-    const bool stream_out = (int64_t)nb * row_layout(p.N, 0).m * 8 > ((int64_t)512 << 20);  // k_trans = 0: more rows than any problem has
-    const int knots = p.N - 1;
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, stream, p, 0, nb, Z, c, nullptr, 0u, f, nullptr); };
-    if ((knots + 39) / 40 == (knots + 63) / 64) {  // chunk size as for the constraint-only launch
-        if (stream_out) go(k_constraint_jacobian<5, 40, 2, true, false, false, false, true, true>);
-        else go(k_constraint_jacobian<5, 40, 2, true, false, false, false, false, true>);
-    } else {
-        if (stream_out) go(k_constraint_jacobian<8, 64, 2, true, false, false, false, true, true>);
-        else go(k_constraint_jacobian<8, 64, 2, true, false, false, false, false, true>);
-    }
-    return hipGetLastError();
+    return launch_fused(p, 0, p.B, Z, c, nullptr, f, nullptr, 0u, stream);
 }
 
 hipError_t launch_kinematic_rows(const BatchParams& p, const double* Z, double* d, double* jac_vals, hipStream_t stream) {
@@ -1387,41 +1272,25 @@ hipError_t launch_jacobian_constants(const BatchParams& p, double* vals, hipStre
 }
 
 hipError_t launch_objective(const BatchParams& p, const double* Z, double* f, hipStream_t stream) {
-    if (p.cost_batch == 1 && p.N <= kWave && p.B >= 4096) {
-        // one shared cost table: persistent waves with lane = knot's cost record in registers, two per SIMD
-        const int ki_ = ((20 * p.N - 6) / 2 + kWave - 1) / kWave;
-        const size_t lds = (size_t)((ki_ * 2 * kWave * 21) / 20 + 2 + kWave) * sizeof(double);
-        const int ki = ((20 * p.N - 6) / 2 + kWave - 1) / kWave;  // 16-byte load instructions per slice: 1 .. 10
-        int per_cu = 8;
-#ifdef QLN_TUNING
-        static const int var = [] { const char* e = getenv("QLN_OBJ_VARIANT"); return e ? atoi(e) : 0; }();
-        static const int pc = [] { const char* e = getenv("QLN_OBJ_PER_CU"); return e ? atoi(e) : 0; }();
-        if (pc) per_cu = pc;
-        const int g_ = std::min(256 * per_cu, p.B);
-#define OBJ_LAUNCH(...) hipLaunchKernelGGL((k_objective_shared<__VA_ARGS__>), dim3(g_), dim3(kWave), lds, stream, p, Z, f); return hipGetLastError()
-        if (ki == 7) {
-            switch (var) {
-                case 1: OBJ_LAUNCH(7, false, 2, 2);
-                case 2: OBJ_LAUNCH(7, true, 1, 2);
-                case 3: OBJ_LAUNCH(7, true, 1, 3);
-                case 4: OBJ_LAUNCH(7, false, 1, 3);
-                case 5: OBJ_LAUNCH(7, true, 3, 2);
-                default: break;
-            }
-        }
-#endif
-        const int grid = std::min(256 * per_cu, p.B);
-#define OBJ_CASE(K) case K: hipLaunchKernelGGL((k_objective_shared<K, true, 2, 2>), dim3(grid), dim3(kWave), lds, stream, p, Z, f); break
-        switch (ki) {
-            OBJ_CASE(1); OBJ_CASE(2); OBJ_CASE(3); OBJ_CASE(4); OBJ_CASE(5);
-            OBJ_CASE(6); OBJ_CASE(7); OBJ_CASE(8); OBJ_CASE(9); OBJ_CASE(10);
-            default: return hipErrorInvalidValue;
-        }
-#undef OBJ_CASE
+    if (!shared_cost_table(p)) {
+        hipLaunchKernelGGL(k_objective, dim3(xcd_grid(p.B)), dim3(kWave), 0, stream, p, Z, f);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(k_objective, dim3(xcd_grid(p.B)), dim3(kWave), 0, stream, p, Z, f);
-    return hipGetLastError();
+    const int ki = slice_loads(p.N);
+    const size_t lds = (size_t)((ki * 2 * kWave * 21) / 20 + 2 + kWave) * sizeof(double);
+    [[maybe_unused]] static const int var = env_knob("QLN_OBJ_VARIANT"), pc = env_knob("QLN_OBJ_PER_CU"), per_cu = pc ? pc : 8;  // two waves per SIMD
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(std::min(256 * per_cu, p.B)), dim3(kWave), lds, stream, p, Z, f);
+        return hipGetLastError();
+    };
+#ifdef QLN_TUNING
+    if (ki == 7 && var == 1) return go(k_objective_shared<7, false, 2, 2>);
+    if (ki == 7 && var == 2) return go(k_objective_shared<7, true, 1, 2>);
+    if (ki == 7 && var == 3) return go(k_objective_shared<7, true, 1, 3>);
+    if (ki == 7 && var == 4) return go(k_objective_shared<7, false, 1, 3>);
+    if (ki == 7 && var == 5) return go(k_objective_shared<7, true, 3, 2>);
+#endif
+    return with_slice_loads(ki, [&](auto k) { return go(k_objective_shared<decltype(k)::value, true, 2, 2>); }, kSliceLoads);
 }
 
 hipError_t launch_constraint_violation(const BatchParams& p, const double* c, double* viol, hipStream_t stream) {
@@ -1444,40 +1313,26 @@ hipError_t launch_initial_guess(const BatchParams& p, double* Z, hipStream_t str
 }
 
 hipError_t launch_objective_gradient(const BatchParams& p, const double* Z, double* grad, hipStream_t stream) {
-    if (p.cost_batch == 1 && p.N <= kWave && p.B >= 4096) {
-        const int ki = ((20 * p.N - 6) / 2 + kWave - 1) / kWave;  // 16-byte pieces per lane and slice: 1 .. 10
-        int per_cu = 8;
-#ifdef QLN_TUNING
-        static const int var = [] { const char* e = getenv("QLN_GRAD_VARIANT"); return e ? atoi(e) : 0; }();
-        static const int pc = [] { const char* e = getenv("QLN_GRAD_PER_CU"); return e ? atoi(e) : 0; }();
-        if (pc) per_cu = pc;
-        const int g_ = std::min(256 * per_cu, p.B);
-#define GRAD_LAUNCH(...) hipLaunchKernelGGL((k_objective_gradient_shared<__VA_ARGS__>), dim3(g_), dim3(kWave), 0, stream, p, Z, grad); return hipGetLastError()
-        if (ki == 7) {
-            switch (var) {
-                case 1: GRAD_LAUNCH(7, 2, 2);
-                case 2: GRAD_LAUNCH(7, 2, 3);
-                case 3: GRAD_LAUNCH(7, 1, 3);
-                case 4: GRAD_LAUNCH(7, 3, 2);
-                case 5: GRAD_LAUNCH(7, 1, 4);
-                default: break;
-            }
-        }
-#endif
-        const int grid = std::min(256 * per_cu, p.B);
-#define GRAD_CASE(K) case K: hipLaunchKernelGGL((k_objective_gradient_shared<K, 1, 2>), dim3(grid), dim3(kWave), 0, stream, p, Z, grad); break
-        switch (ki) {
-            GRAD_CASE(1); GRAD_CASE(2); GRAD_CASE(3); GRAD_CASE(4); GRAD_CASE(5);
-            GRAD_CASE(6); GRAD_CASE(7); GRAD_CASE(8); GRAD_CASE(9); GRAD_CASE(10);
-            default: return hipErrorInvalidValue;
-        }
-#undef GRAD_CASE
+    if (!shared_cost_table(p)) {
+        const int64_t total = (int64_t)p.B * (20 * p.N - 5);
+        const int ntiles = (int)((total + kGradU * 256 - 1) / (kGradU * 256));
+        hipLaunchKernelGGL(k_objective_gradient, dim3(xcd_grid(ntiles)), dim3(256), 0, stream, p, Z, grad, total, ntiles);
         return hipGetLastError();
     }
-    const int64_t total = (int64_t)p.B * (20 * p.N - 5);
-    const int ntiles = (int)((total + kGradU * 256 - 1) / (kGradU * 256));
-    hipLaunchKernelGGL(k_objective_gradient, dim3(xcd_grid(ntiles)), dim3(256), 0, stream, p, Z, grad, total, ntiles);
-    return hipGetLastError();
+    const int ki = slice_loads(p.N);
+    [[maybe_unused]] static const int var = env_knob("QLN_GRAD_VARIANT"), pc = env_knob("QLN_GRAD_PER_CU"), per_cu = pc ? pc : 8;
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(std::min(256 * per_cu, p.B)), dim3(kWave), 0, stream, p, Z, grad);
+        return hipGetLastError();
+    };
+#ifdef QLN_TUNING
+    if (ki == 7 && var == 1) return go(k_objective_gradient_shared<7, 2, 2>);
+    if (ki == 7 && var == 2) return go(k_objective_gradient_shared<7, 2, 3>);
+    if (ki == 7 && var == 3) return go(k_objective_gradient_shared<7, 1, 3>);
+    if (ki == 7 && var == 4) return go(k_objective_gradient_shared<7, 3, 2>);
+    if (ki == 7 && var == 5) return go(k_objective_gradient_shared<7, 1, 4>);
+#endif
+    return with_slice_loads(ki, [&](auto k) { return go(k_objective_gradient_shared<decltype(k)::value, 1, 2>); }, kSliceLoads);
 }
 
 }  // namespace qln
