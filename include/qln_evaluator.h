@@ -306,6 +306,56 @@ int qln_solve(qln_handle* h, double* Z, const qln_solve_options* opt /* NULL = d
 /* the same as a host form (see "Host forms" above: Z copied in, solved on the GPU, copied back) -- what the Julia veneer
  * calls in place of `solve(Z0, nlp)`.  info (host, may be NULL): [B][QLN_SOLVE_INFO_STRIDE]. */
 int qln_solve_host(qln_handle* h, double* Z, const qln_solve_options* opt, double* info);
+/* Least-squares estimate of the Lagrange multipliers of every problem at ANY point Z, and its KKT residual: what says
+ * whether a trajectory -- qln_solve's, Ipopt's, a file's -- is a stationary point and not only a feasible one, and what
+ * a caller that keeps Ipopt hands it as the dual start.  Convention: MOI's and Ipopt's, the one
+ * qln_eval_hessian_lagrangian uses: L = f + lam' c, stationarity reads grad f + J' lam - z_L + z_U = 0.  For problem b
+ *   active rows   every equality row; clearance row i (the last N rows of c) iff !(c_i > act_tol), so a NaN is active.
+ *                 A = jac_c(Z) restricted to them.
+ *   fixed         with bound_tol >= 0, variable j iff Z_j <= l_j + bound_tol or Z_j >= u_j - bound_tol, (l, u) exactly
+ *                 what qln_variable_bounds(N, bounds) returns (theta, h, and quirk Q6's entries when q6_bounds != 0; only
+ *                 h_min, h_max, theta_min, theta_max and q6_bounds of `bounds` are read).  bound_tol < 0: none is fixed.
+ *                 D = diag(free), entries 0 or 1.
+ *   row scaling   row_scaling != 0: w_i = the 2-norm of row i of A D (1 where that is 0); row_scaling == 0: w = 1.
+ *                 T = (A D)' W^-1, an n x m operator.
+ *   solve         min_y || T y + D g ||_2 by CGLS started at 0 (r = -D g, s = T' r, p = s, gamma = s.s; then q = T p,
+ *                 alpha = gamma / q.q, y += alpha p, r -= alpha q, s = T' r, beta = gamma_new / gamma, p = s + beta p),
+ *                 stopped at max_iters or once gamma <= rel_tol^2 gamma_0.  Started at 0 the iterates converge to the
+ *                 minimum-norm y although T is rank deficient (at a solved landing the stacked Jacobian is: most h on a
+ *                 bound, x1 on quirk Q6's); the residual is unique either way.  Row scaling cuts the iteration count
+ *                 several times over and is what a caller wants unless it compares iterates.
+ *   lam           = W^-1 y, in the layout of c; an exact 0 on the inactive rows.
+ *   lag           = g + A' lam, in the layout of Z (may be NULL): the dual infeasibility on the free columns, the bound
+ *                 multipliers z_L - z_U on the fixed ones.  Formed by one more transposed product with D = I, not from the
+ *                 recurrence's r.  Every entry below n_nlp is written, entries from n_nlp to z_stride never.
+ *   info          (may be NULL) QLN_MULT_INFO_STRIDE doubles per problem, the counts exact integers: {0 iterations done,
+ *                 1 ||D g||^2, 2 gamma at exit, 3 ||r||^2 of the recurrence, 4 max |lag_j| over the free columns, 5 active
+ *                 clearance rows, 6 fixed variables, 7 active clearance rows with lam_i > 0 (the wrong sign for c_i >= 0:
+ *                 reported, not projected), 8 fixed variables whose lag_j contradicts their bound (< 0 at a lower, > 0 at
+ *                 an upper; never counted when both bounds are within bound_tol), 9 max |lam_i c_i| over the active
+ *                 clearance rows, 10 max |lam_i|, 11 max |g_j| over the free columns, 12-15 zero}.  The four maxima (4,
+ *                 9, 10, 11) ignore a NaN entry (fmax from 0); the sums 1, 2 and 3 carry it, so they are what tells a
+ *                 non-finite g or Z.
+ * g is the caller's, in the layout of Z, so no cost table is needed.  qln_eval_objective_gradient gives the reference's
+ * grad_f!, which is what Ipopt sees; by quirk Q2 it has no d(h l)/dh, so with it the h-columns of lag measure
+ * stationarity against that field and not against the gradient of eval_f.  A caller may pass the exact gradient instead.
+ * c = eval_c!(Z) as written by qln_eval_constraint; only its clearance rows are read.
+ * One wavefront per problem with every vector in LDS, the Jacobian re-derived from Z inside the products and never
+ * stored, as in qln_gauss_newton_step: (4 n_nlp + 4 m_nlp + N) doubles per problem with m_nlp taken at k_trans = 1,
+ * QLN_ERR_UNSUPPORTED if that does not fit the 160 KB of LDS of a CU (the bound follows from the count; with today's
+ * layout 153 N + 40 doubles, so N > 133).  QLN_ERR_INVALID_ARGUMENT, without touching a GPU, for a NULL h, Z, c, g or
+ * lam, max_iters < 0, a negative or non-finite act_tol or rel_tol, a non-finite bound_tol, or bounds with min > max.
+ * Device pointers, stream-ordered. */
+#define QLN_MULT_INFO_STRIDE 16
+int qln_estimate_multipliers(qln_handle* h, const double* Z, const double* c, const double* g,
+                             const qln_solve_options* bounds /* NULL = defaults; only the bound fields are read */,
+                             double act_tol, double bound_tol, int32_t row_scaling, int32_t max_iters, double rel_tol,
+                             double* lam, double* lag /* may be NULL */, double* info /* [B][QLN_MULT_INFO_STRIDE] or NULL */);
+/* the same as a host form (see "Host forms" above): Z, c, g copied in, lam and -- where asked for -- lag and info copied
+ * back, through the one staging path; the padding of lam and lag comes back as zeros. */
+int qln_estimate_multipliers_host(qln_handle* h, const double* Z, const double* c, const double* g,
+                                  const qln_solve_options* bounds, double act_tol, double bound_tol, int32_t row_scaling,
+                                  int32_t max_iters, double rel_tol, double* lam, double* lag, double* info);
 /* OPT-IN EXTENSION WITHOUT A REFERENCE ORACLE.  The leg-length ("kinematic") constraint group exists in the reference
  * only as commented-out code (src/constraints.jl:115-138 values, :276-288 Jacobian, src/nlp.jl:60,70 index range and
  * bounds): the reference never computes it, so nothing can be compared with it, and it is NOT part of c / vals above.

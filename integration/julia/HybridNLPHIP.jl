@@ -161,6 +161,26 @@ function solve_hip(x0, prob::HybridNLPHIP; c_tol=1.0e-6)
     return Z, info
 end
 
+# ---- is a trajectory optimal?  Least-squares multipliers and the KKT residual (include/qln_evaluator.h, DESIGN.md 4.15) ----
+# At any Z (qln_solve's, Ipopt's, a file's): lam over the active set (every equality row, clearance rows with c_i <= act_tol,
+# variables within bound_tol of a bound of solve() held fixed), MOI's convention L = f + lam'c.  Returns (lam, lag, info):
+# lag = g + J'lam is the dual infeasibility on the free variables and z_L - z_U on the fixed ones, info the 16-entry report
+# (info[1] iterations, info[5] max |lag| over the free variables, info[8] / info[9] the wrong-sign counts; 1-based here).
+# g = nothing: the reference's grad_f!, what Ipopt sees (no d(h l)/dh, quirk Q2); pass the exact gradient to measure that.
+function estimate_multipliers(prob::HybridNLPHIP, Z; g=nothing, act_tol=1.0e-6, bound_tol=1.0e-8, row_scaling::Bool=true,
+                              max_iters=20000, rel_tol=1.0e-8)
+    x = collect(Float64, Z)
+    c = zeros(num_duals(prob)); MOI.eval_constraint(prob, c, x)
+    grad = zeros(num_primals(prob))
+    g === nothing ? MOI.eval_objective_gradient(prob, grad, x) : copyto!(grad, g)
+    lam = zeros(num_duals(prob)); lag = zeros(num_primals(prob)); info = zeros(16)
+    qln_check(ccall((:qln_estimate_multipliers_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{QlnSolveOptions}, Cdouble, Cdouble, Int32, Int32,
+                     Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, x, c, grad, C_NULL, act_tol, bound_tol, Int32(row_scaling), Int32(max_iters), rel_tol, lam, lag, info))
+    return lam, lag, info
+end
+
 # ---- TVLQR tracking along solved trajectories (include/qln_evaluator.h, DESIGN.md 4.11) -----------------------------------
 # Zref: the problem's reference in the layout of Z; Q, Qf: 15 diagonal weights, R: 4 (the forces).  Returns K as a
 # (15, 4, N-1) array (K[:, m, k] = row m of knot k's gain) and P as (120, N) packed lower triangles (or nothing).

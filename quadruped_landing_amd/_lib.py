@@ -99,6 +99,7 @@ class QlnDropStateSampler(C.Structure):
 
 
 SOLVE_INFO_STRIDE = 16
+MULT_INFO_STRIDE = 16
 
 
 class QlnError(RuntimeError):
@@ -165,6 +166,10 @@ SIGNATURES = {
     "qln_variable_bounds": (C.c_int, [C.c_int32, C.POINTER(QlnSolveOptions), _dp, _dp]),
     "qln_solve": (C.c_int, [_vp, _dp, C.POINTER(QlnSolveOptions), _dp]),
     "qln_solve_host": (C.c_int, [_vp, _dp, C.POINTER(QlnSolveOptions), _dp]),
+    "qln_estimate_multipliers": (C.c_int, [_vp, _dp, _dp, _dp, C.POINTER(QlnSolveOptions), C.c_double, C.c_double, C.c_int32, C.c_int32,
+                                          C.c_double, _dp, _dp, _dp]),
+    "qln_estimate_multipliers_host": (C.c_int, [_vp, _dp, _dp, _dp, C.POINTER(QlnSolveOptions), C.c_double, C.c_double, C.c_int32,
+                                               C.c_int32, C.c_double, _dp, _dp, _dp]),
     "qln_initial_guess": (C.c_int, [_vp, _dp]),
     "qln_sample_drop_states": (C.c_int, [_vp, C.POINTER(QlnDropStateSampler)]),
     "qln_sample_bounded_integers": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int64, C.c_int32, C.c_int32, C.c_int64,

@@ -97,6 +97,7 @@ enum HostRole {
     kCov0,   // in: the covariance sweep's Sigma0 (1 or B tiles used)       [B][120]
     kCov,    // out: the covariances                                        layout of P
     kMarg,   // out: the marginals                                          [B][N][8]
+    kMultInfo,  // out: the multiplier estimate's report                    [B][16]
     kHostRoles
 };
 
@@ -170,6 +171,7 @@ int64_t host_role_size(const qln_handle* h, HostRole r) {
         case kCov0: return (int64_t)D.B * QLN_TRACK_P_NNZ;
         case kMarg: return tracking_marg_total(D);
         case kX0: return (int64_t)D.B * QLN_NX;
+        case kMultInfo: return (int64_t)D.B * QLN_MULT_INFO_STRIDE;
         case kHostRoles: break;
     }
     return 0;
@@ -844,6 +846,60 @@ int qln_solve(qln_handle* h, double* Z, const qln_solve_options* opt, double* in
     sp.rescue_outer = o.rescue_outer;
     QLN_HIP(qln::launch_al_ilqr(h->p, sp, Z, info, h->solve_scratch, h->stream));
     return QLN_OK;
+}
+
+// Everything qln_estimate_multipliers decides before it touches a device.
+static int check_multiplier_args(const qln_handle* h, const double* Z, const double* c, const double* g,
+                                 const qln_solve_options* bounds, double act_tol, double bound_tol, int32_t row_scaling,
+                                 int32_t max_iters, double rel_tol, const double* lam, const char* who, qln::MultiplierParams* mp) {
+    const std::string w = std::string(who) + ": ";
+    if (int rc = check_handle(h)) return rc;
+    if (!Z || !c || !g || !lam) return fail(QLN_ERR_INVALID_ARGUMENT, w + "null pointer");
+    if (max_iters < 0) return fail(QLN_ERR_INVALID_ARGUMENT, w + "max_iters < 0");
+    if (!(std::isfinite(act_tol) && act_tol >= 0.0 && std::isfinite(rel_tol) && rel_tol >= 0.0))
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + "act_tol and rel_tol must be finite and >= 0");
+    if (!std::isfinite(bound_tol)) return fail(QLN_ERR_INVALID_ARGUMENT, w + "bound_tol must be finite");
+    qln_solve_options o;
+    qln_solve_default_options(&o);
+    if (bounds) o = *bounds;
+    if (!(o.h_max >= o.h_min) || !(o.theta_max >= o.theta_min)) return fail(QLN_ERR_INVALID_ARGUMENT, w + "bounds with min > max");
+    if (qln::multiplier_lds_bytes(h->dims.N) > 160 * 1024)
+        return fail(QLN_ERR_UNSUPPORTED, w + "N = " + std::to_string(h->dims.N) +
+                                             " does not fit one problem in the 160 KB of LDS of a CU");
+    mp->th_lo = o.theta_min, mp->th_hi = o.theta_max, mp->h_lo = o.h_min, mp->h_hi = o.h_max, mp->q6 = o.q6_bounds;
+    mp->act_tol = act_tol, mp->bound_tol = bound_tol, mp->row_scaling = row_scaling, mp->max_iters = max_iters;
+    mp->rel_tol = rel_tol;
+    return QLN_OK;
+}
+
+int qln_estimate_multipliers(qln_handle* h, const double* Z, const double* c, const double* g, const qln_solve_options* bounds,
+                             double act_tol, double bound_tol, int32_t row_scaling, int32_t max_iters, double rel_tol,
+                             double* lam, double* lag, double* info) {
+    qln::MultiplierParams mp;
+    if (int rc = check_multiplier_args(h, Z, c, g, bounds, act_tol, bound_tol, row_scaling, max_iters, rel_tol, lam,
+                                       "qln_estimate_multipliers", &mp))
+        return rc;
+    if (int rc = bind_device(h)) return rc;
+    QLN_HIP(qln::launch_estimate_multipliers(h->p, mp, Z, c, g, lam, lag, info, h->stream));
+    return QLN_OK;
+}
+
+// Staged only: a mapped path would keep the second read of g on the host link with no measurement behind it.
+int qln_estimate_multipliers_host(qln_handle* h, const double* Z, const double* c, const double* g,
+                                  const qln_solve_options* bounds, double act_tol, double bound_tol, int32_t row_scaling,
+                                  int32_t max_iters, double rel_tol, double* lam, double* lag, double* info) {
+    qln::MultiplierParams mp;
+    if (int rc = check_multiplier_args(h, Z, c, g, bounds, act_tol, bound_tol, row_scaling, max_iters, rel_tol, lam,
+                                       "qln_estimate_multipliers_host", &mp))
+        return rc;
+    if (int rc = bind_device(h)) return rc;
+    return host_call(h, {copy_in(kZ, Z), copy_in(kMu, c), copy_in(kV, g), copy_out(kC, lam), copy_out(kZout, lag),
+                         copy_out(kMultInfo, info)},
+                     [&](double* const* d, bool) {
+                         return qln::launch_estimate_multipliers(h->p, mp, d[kZ], d[kMu], d[kV], d[kC], d[kZout], d[kMultInfo],
+                                                                 h->stream);
+                     },
+                     false);
 }
 
 static qln::DropStateSampler sampler_of(const qln_drop_state_sampler* s) {

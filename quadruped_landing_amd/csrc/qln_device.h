@@ -314,6 +314,17 @@ size_t gauss_newton_lds_bytes(int32_t N);
 hipError_t launch_gauss_newton_step(const BatchParams& p, const double* Z, const double* c, double* dZ, int max_iters,
                                     double rel_tol, const double* radius, const double* col_scale, double* info,
                                     hipStream_t stream);
+// least-squares multiplier estimate and KKT report, CGLS per problem in LDS (qln_solver_kernels.hip)
+struct MultiplierParams {
+    double th_lo, th_hi, h_lo, h_hi;  // bounds on theta (every knot) and h (every dynamics knot), src/moi.jl:54-61
+    int q6;                           // quirk Q6's lower bounds 0 on yb_{k+1}, x1_{k+1} (src/moi.jl:64-65)
+    double act_tol, bound_tol;        // bound_tol < 0: no variable is fixed
+    int row_scaling, max_iters;
+    double rel_tol;
+};
+size_t multiplier_lds_bytes(int32_t N);
+hipError_t launch_estimate_multipliers(const BatchParams& p, const MultiplierParams& mp, const double* Z, const double* c,
+                                       const double* g, double* lam, double* lag, double* info, hipStream_t stream);
 // device-side generator of the synthetic workload (qln_sampler_kernels.hip)
 struct DropStateSampler {
     unsigned long long state_hi, state_lo, inc_hi, inc_lo;  // numpy.random.PCG64(seed).state

@@ -605,6 +605,306 @@ __global__ __launch_bounds__(kWave, 1) void k_gauss_newton_step(BatchParams P, c
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Least-squares Lagrange multipliers and the KKT residual of every problem (include/qln_evaluator.h,
+// qln_estimate_multipliers): with A = the active rows of jac_c(Z) (every equality row; clearance row i unless
+// c_i > act_tol), D = diag(free) the 0/1 mask of the variables that sit on no bound, and W = diag(w) the norms of the
+// rows of A D,
+//     y = the minimum-norm minimiser of || T y + D g ||_2,   T = (A D)' W^-1  (n x m),   lam = W^-1 y,
+// by CGLS started at 0, and lag = g + A' lam.  The operator is the Gauss-Newton step's, transposed: the same in-LDS
+// products, with dsc = the problem's own free mask and mask = its active clearance rows, so T p is lds_vjp and T' r is
+// lds_jvp.  One wavefront owns one problem and keeps everything in LDS; an iteration touches no global memory.
+// The bounds are those of qln_variable_bounds, derived here from four scalars and a flag: no table is read.
+// LDS per problem: (4 n_nlp + 4 m_nlp + N) doubles (multiplier_lds_bytes) = 48 KB at N = 40.
+// HBM traffic of a call: read Z, the clearance rows of c, g (once for the right-hand side, once more behind the loop
+// for lag: g D loses the fixed columns and LDS has no room for a fifth n-vector); write lam, lag, info.
+// ---------------------------------------------------------------------------------------------
+// max over the wave's 64 lanes, the same bits in every lane (fmax: a NaN loses)
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, kWave));
+    return v;
+}
+
+// which bound entry j of Z sits on, to bound_tol: bit 0 = the lower, bit 1 = the upper (a NaN sits on neither)
+__device__ __forceinline__ int bound_side(const MultiplierParams& mp, int N, int j, double zj) {
+    if (mp.bound_tol < 0.0) return 0;
+    const int kk = j / 20, e = j - 20 * kk;
+    double lo, hi;
+    if (e == 2) {
+        lo = mp.th_lo, hi = mp.th_hi;
+    } else if (e == 19) {  // (only dynamics knots have an entry 19: n_nlp = 20 N - 5)
+        lo = mp.h_lo, hi = mp.h_hi;
+    } else if (mp.q6 && kk >= 1 && (e == 1 || e == 3)) {
+        lo = 0.0, hi = HUGE_VAL;
+    } else {
+        return 0;
+    }
+    return (zj <= lo + mp.bound_tol ? 1 : 0) | (zj >= hi - mp.bound_tol ? 2 : 0);
+}
+
+// nrm2[i] = sum of the squares of the entries of row i of A D, all operands in LDS: the shape of lds_jvp with every
+// product replaced by its square (CACHED: the lane's block in registers, N <= 64; otherwise re-derived from z)
+template <bool CACHED>
+__device__ __forceinline__ void lds_row_sqnorms(const ProblemView& pv, const Model& M, const KnotJac& J, const double* z,
+                                                const double* dsc, const double* mask, double* nrm2, int lane) {
+    const int N = pv.N, kt = pv.kt, im = pv.im;
+    auto sq = [](double a) { return a * a; };
+    if (lane < 15) nrm2[lane] = sq(dsc[lane]);
+    if (lane >= 15 && lane < 29) nrm2[lane] = sq(dsc[20 * (N - 1) + (lane - 15)]);
+    if (lane == 29) nrm2[pv.R.o_fc] = sq(dsc[20 * (N - 2) + 16]) + sq(dsc[20 * (N - 2) + 18]);
+    for (int k0 = 0; k0 < (CACHED ? 1 : N); k0 += kWave) {
+        const int kk = k0 + lane, K = kk + 1;
+        const bool own = kk < N, valid = kk < N - 1;
+        const double* zk = z + 20 * (own ? kk : 0);
+        const double* dk = dsc + 20 * (own ? kk : 0);
+        double dth;
+        if constexpr (CACHED) dth = J.dth;
+        else dth = clearance_dtheta(zk[2], M.lb);
+        if (own) {
+            const double d4 = sq(dk[4]), d6 = sq(dk[6]);
+            nrm2[pv.R.o_ci + kk] = pv.init1 ? d4 : d6;
+            if (K >= kt) nrm2[pv.R.o_co + (K - kt)] = pv.init1 ? d6 : d4;
+            nrm2[pv.R.o_bp + kk] = mask[kk] * (sq(dk[1]) + sq(dth * dk[2]));
+        }
+        if (valid) {
+            double din[20], acc[15];
+#pragma unroll
+            for (int i = 0; i < 20; ++i) din[i] = dk[i];
+#pragma unroll
+            for (int i = 0; i < 15; ++i) acc[i] = sq(dk[20 + i]);
+            if constexpr (CACHED) {
+                for_each_step_entry([&](auto row, auto col) {
+                    constexpr int pos_ = step_union_pos(row, col);
+                    acc[row] += sq(J.e[pos_] * din[col]);
+                });
+            } else {
+                const StepBlock blk = step_block(zk, knot_mode(K, kt - 1, im), M);
+                for_each_step_entry(blk, [&](auto row, auto col, double val) { acc[row] += sq(val * din[col]); });
+            }
+#pragma unroll
+            for (int i = 0; i < 15; ++i) nrm2[pv.R.o_dyn + 15 * kk + i] = acc[i];
+        }
+    }
+}
+
+// info[b][16]: see QLN_MULT_INFO_STRIDE in include/qln_evaluator.h
+template <bool CACHED>
+__global__ __launch_bounds__(kWave, 1) void k_estimate_multipliers(BatchParams P, MultiplierParams mp,
+                                                                   const double* __restrict__ Z,
+                                                                   const double* __restrict__ C,
+                                                                   const double* __restrict__ G,
+                                                                   double* __restrict__ LAM, double* __restrict__ LAG,
+                                                                   double* __restrict__ info) {
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x;
+    const int b = xcd_contiguous_index(blockIdx.x, P.B);
+    if (b >= P.B) return;  // wave-uniform
+    const ProblemDesc pd = P.desc[b];
+    const ProblemView pv = view_of(P, pd);
+    const int N = pv.N, n = 20 * N - 5, m = pv.R.m;
+    const Model M(P);
+    double* z = lds;        // [n]  decision vector
+    double* dsc = z + n;    // [n]  D: 1 = free, 0 = on a bound
+    double* r = dsc + n;    // [n]  residual -(D g + T y); behind the loop A' lam
+    double* q = r + n;      // [n]  T p; behind the loop the ones of D = I
+    double* y = q + n;      // [m]  CGLS solution, lam = W^-1 y
+    double* p = y + m;      // [m]  search direction
+    double* s = p + m;      // [m]  T' r; in front of T p the operand W^-1 p; behind the loop lam
+    double* wi = s + m;     // [m]  1 / w
+    double* mask = wi + m;  // [N]  1 = clearance row active
+    const double* __restrict__ Zb = Z + (int64_t)b * P.z_stride;
+    const double* __restrict__ Gb = G + (int64_t)b * P.z_stride;
+    const double* __restrict__ Cb = C + pd.c_off + pv.R.o_bp;  // the clearance rows: the only values of c that are read
+    // eight 512-byte loads in flight per round trip (clamped indices, predicated LDS writes)
+    constexpr int kU = 8;
+    double dg2 = 0.0, gmax = 0.0, nfixed = 0.0, nact = 0.0;
+    for (int i0 = 0; i0 < n; i0 += kU * kWave) {
+        double zt[kU], gt[kU];
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int i = min(i0 + u * kWave + lane, n - 1);
+            zt[u] = Zb[i];
+            gt[u] = Gb[i];
+        }
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int i = i0 + u * kWave + lane;
+            if (i < n) {
+                const bool is_free = bound_side(mp, N, i, zt[u]) == 0;
+                z[i] = zt[u];
+                dsc[i] = is_free ? 1.0 : 0.0;
+                r[i] = is_free ? -gt[u] : 0.0;
+                if (is_free) {
+                    dg2 += gt[u] * gt[u];
+                    gmax = fmax(gmax, fabs(gt[u]));
+                } else {
+                    nfixed += 1.0;
+                }
+            }
+        }
+    }
+    for (int i0 = 0; i0 < N; i0 += kU * kWave) {
+        double ct[kU];
+#pragma unroll
+        for (int u = 0; u < kU; ++u) ct[u] = Cb[min(i0 + u * kWave + lane, N - 1)];
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int i = i0 + u * kWave + lane;
+            if (i < N) {
+                const bool active = !(ct[u] > mp.act_tol);  // a NaN in c makes the row active
+                mask[i] = active ? 1.0 : 0.0;
+                if (active) nact += 1.0;
+            }
+        }
+    }
+    for (int i = lane; i < m; i += kWave) {
+        y[i] = 0.0;
+        wi[i] = 1.0;
+    }
+    dg2 = wave_sum(dg2);
+    nfixed = wave_sum(nfixed);
+    nact = wave_sum(nact);
+    wave_lds_sync();
+    KnotJac J;
+    if constexpr (CACHED) knot_jacobian(pv, M, z, lane, J);
+    if (mp.row_scaling) {
+        lds_row_sqnorms<CACHED>(pv, M, J, z, dsc, mask, wi, lane);
+        wave_lds_sync();
+        for (int i = lane; i < m; i += kWave) {
+            const double w2 = wi[i];
+            wi[i] = (w2 > 0.0) ? 1.0 / sqrt(w2) : 1.0;  // an empty row (and a NaN) keeps w = 1
+        }
+    }
+    wave_lds_sync();  // the one barrier behind either way of filling wi (ones above, or 1 / w here)
+    // T' v = W^-1 (A D) v is lds_jvp followed by the scaling; T u = (A D)' (W^-1 u) is lds_vjp of the scaled operand
+#define QLN_APPLY_AD(v_, y_)                                              \
+    do {                                                                  \
+        if constexpr (CACHED) lds_jvp_cached(pv, J, v_, dsc, mask, y_, lane); \
+        else lds_jvp(pv, M, z, v_, dsc, mask, y_, lane);                  \
+    } while (0)
+#define QLN_APPLY_ADT(l_, d_, g_)                                         \
+    do {                                                                  \
+        if constexpr (CACHED) lds_vjp_cached(pv, J, l_, d_, mask, g_, lane); \
+        else lds_vjp(pv, M, z, l_, d_, mask, g_, lane);                   \
+    } while (0)
+    QLN_APPLY_AD(r, s);
+    wave_lds_sync();
+    double gamma = 0.0;
+    for (int i = lane; i < m; i += kWave) {
+        const double si = wi[i] * s[i];
+        p[i] = si;
+        gamma += si * si;
+    }
+    gamma = wave_sum(gamma);
+    const double gamma0 = gamma;
+    const double gamma_stop = mp.rel_tol * mp.rel_tol * gamma0;
+    int it = 0;
+    while (it < mp.max_iters && gamma > gamma_stop) {  // wave-uniform; false for NaN
+        for (int i = lane; i < m; i += kWave) s[i] = wi[i] * p[i];
+        wave_lds_sync();
+        QLN_APPLY_ADT(s, dsc, q);
+        wave_lds_sync();
+        double qq = 0.0;
+        for (int i = lane; i < n; i += kWave) qq += q[i] * q[i];
+        qq = wave_sum(qq);
+        if (!(qq > 0.0)) break;
+        const double alpha = gamma / qq;
+        for (int i = lane; i < m; i += kWave) y[i] += alpha * p[i];
+        for (int i = lane; i < n; i += kWave) r[i] -= alpha * q[i];
+        wave_lds_sync();
+        QLN_APPLY_AD(r, s);
+        wave_lds_sync();
+        double gnew = 0.0;
+        for (int i = lane; i < m; i += kWave) {
+            const double si = wi[i] * s[i];
+            s[i] = si;
+            gnew += si * si;
+        }
+        gnew = wave_sum(gnew);
+        const double beta = gnew / gamma;
+        for (int i = lane; i < m; i += kWave) p[i] = s[i] + beta * p[i];
+        gamma = gnew;
+        ++it;
+    }
+    double rr = 0.0, lmax = 0.0;
+    for (int i = lane; i < n; i += kWave) rr += r[i] * r[i];
+    rr = wave_sum(rr);
+    // lam = W^-1 y, an exact 0 on the inactive rows
+    double* __restrict__ Lb = LAM + pd.c_off;
+    for (int i = lane; i < m; i += kWave) {
+        const bool inactive = i >= pv.R.o_bp && mask[i - pv.R.o_bp] == 0.0;
+        const double li = inactive ? 0.0 : wi[i] * y[i];
+        s[i] = li;
+        Lb[i] = li;
+        lmax = fmax(lmax, fabs(li));
+    }
+    if (!LAG && !info) return;  // wave-uniform
+    // lag = g + A' lam: one more transposed product, with D = I
+    for (int i = lane; i < n; i += kWave) q[i] = 1.0;
+    wave_lds_sync();
+    QLN_APPLY_ADT(s, q, r);
+    wave_lds_sync();
+#undef QLN_APPLY_AD
+#undef QLN_APPLY_ADT
+    double* __restrict__ Gl = LAG ? LAG + (int64_t)b * P.z_stride : nullptr;
+    double lagmax = 0.0, nbound_wrong = 0.0;
+    for (int i0 = 0; i0 < n; i0 += kU * kWave) {
+        double gt[kU];
+#pragma unroll
+        for (int u = 0; u < kU; ++u) gt[u] = Gb[min(i0 + u * kWave + lane, n - 1)];
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int i = i0 + u * kWave + lane;
+            if (i < n) {
+                const double li = gt[u] + r[i];
+                if (Gl) Gl[i] = li;
+                const int side = bound_side(mp, N, i, z[i]);
+                if (side == 0) lagmax = fmax(lagmax, fabs(li));
+                if ((side == 1 && li < 0.0) || (side == 2 && li > 0.0)) nbound_wrong += 1.0;
+            }
+        }
+    }
+    double nsign_wrong = 0.0, compl_max = 0.0;
+    for (int i0 = 0; i0 < N; i0 += kU * kWave) {
+        double ct[kU];
+#pragma unroll
+        for (int u = 0; u < kU; ++u) ct[u] = Cb[min(i0 + u * kWave + lane, N - 1)];
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int i = i0 + u * kWave + lane;
+            if (i < N && mask[i] != 0.0) {
+                const double li = s[pv.R.o_bp + i];
+                if (li > 0.0) nsign_wrong += 1.0;
+                compl_max = fmax(compl_max, fabs(li * ct[u]));
+            }
+        }
+    }
+    if (!info) return;
+    lagmax = wave_max(lagmax);
+    lmax = wave_max(lmax);
+    gmax = wave_max(gmax);
+    compl_max = wave_max(compl_max);
+    nbound_wrong = wave_sum(nbound_wrong);
+    nsign_wrong = wave_sum(nsign_wrong);
+    if (lane == 0) {
+        double* o = info + QLN_MULT_INFO_STRIDE * (int64_t)b;
+        o[0] = (double)it;
+        o[1] = dg2;
+        o[2] = gamma;
+        o[3] = rr;
+        o[4] = lagmax;
+        o[5] = nact;
+        o[6] = nfixed;
+        o[7] = nsign_wrong;
+        o[8] = nbound_wrong;
+        o[9] = compl_max;
+        o[10] = lmax;
+        o[11] = gmax;
+        o[12] = o[13] = o[14] = o[15] = 0.0;
+    }
+}
+
 }  // namespace
 
 hipError_t launch_constraint_jvp(const BatchParams& p, const double* Z, const double* v, double* y, hipStream_t stream) {
@@ -634,6 +934,23 @@ hipError_t launch_gauss_newton_step(const BatchParams& p, const double* Z, const
     };
     // one knot per lane: the step blocks stay in registers for the whole step
     return (p.N <= kWave) ? go(k_gauss_newton_step<true>) : go(k_gauss_newton_step<false>);
+}
+
+// LDS bytes one problem of the multiplier estimate needs (largest m_nlp is at k_trans = 1)
+size_t multiplier_lds_bytes(int32_t N) { return sizeof(double) * (size_t)(4 * (20 * N - 5) + 4 * row_layout(N, 1).m + N); }
+
+hipError_t launch_estimate_multipliers(const BatchParams& p, const MultiplierParams& mp, const double* Z, const double* c,
+                                       const double* g, double* lam, double* lag, double* info, hipStream_t stream) {
+    const size_t lds = multiplier_lds_bytes(p.N);
+    auto go = [&](auto kernel) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, dim3(xcd_grid(p.B)), dim3(kWave), lds, stream, p, mp, Z, c, g, lam, lag, info);
+        return hipGetLastError();
+    };
+    // one knot per lane: the step blocks stay in registers for the whole solve
+    return (p.N <= kWave) ? go(k_estimate_multipliers<true>) : go(k_estimate_multipliers<false>);
 }
 
 }  // namespace qln

@@ -766,6 +766,44 @@ class HybridNLP:
                                                     ptr(info, _lib.GN_INFO_STRIDE * self.B, "info")))
         return out
 
+    def _bound_options(self, bounds):
+        """qln_solve_options at their defaults with the given bound fields set (h_min, h_max, theta_min, theta_max, q6_bounds)."""
+        opt = _lib.QlnSolveOptions()
+        _lib.check(_lib.lib().qln_solve_default_options(C.byref(opt)))
+        for k, v in bounds.items():
+            if k not in ("h_min", "h_max", "theta_min", "theta_max", "q6_bounds"):
+                raise TypeError(f"unknown bound option {k!r}")
+            setattr(opt, k, v)
+        return opt
+
+    def estimate_multipliers(self, Z, c=None, g=None, *, act_tol: float = 1e-6, bound_tol: float = 1e-8, row_scaling: bool = True,
+                             max_iters: int = 20000, rel_tol: float = 1e-8, lam=None, lag=None, info=None, **bounds):
+        """Least-squares Lagrange multipliers of every problem at Z and the KKT residual (qln_estimate_multipliers; CGLS in
+        LDS, one wave per problem).  `c` = eval_c(Z) and `g` = grad_f(Z) when not given (a caller may pass another
+        gradient, e.g. the exact one: by quirk Q2 grad_f has no d(h l)/dh).  Convention L = f + lam'c.  `bounds`: h_min,
+        h_max, theta_min, theta_max, q6_bounds of qln_solve_options.  Returns (lam, lag, info): lam in the layout of c (0
+        on inactive clearance rows), lag = g + A'lam in the layout of Z (dual infeasibility on the free columns, z_L - z_U
+        on the fixed ones), info a (B, 16) tensor {iterations, |Dg|^2, gamma, |r|^2, max |lag| free, active clearance rows,
+        fixed variables, wrong-sign clearance multipliers, wrong-sign bound multipliers, max |lam_i c_i|, max |lam|,
+        max |g| free, 0...}.  `lag=False` / `info=False`: not computed (None is returned in its place)."""
+        t = _torch()
+        self._check(Z, self.dims.z_total, "Z")
+        c = self.eval_c(Z) if c is None else c
+        g = self.grad_f(Z) if g is None else g
+        lam = self.new_c() if lam is None else lam
+        lag = self.new_Z() if lag is None else lag
+        if info is None:
+            info = t.zeros(self.B * _lib.MULT_INFO_STRIDE, dtype=t.float64, device=self._dev())
+        ptr = lambda a, total, name: None if a is False else self._check(a, total, name)
+        opt = self._bound_options(bounds)
+        _lib.check(_lib.lib().qln_estimate_multipliers(
+            self._h, Z.data_ptr(), self._check(c, self.dims.c_total, "c"), self._check(g, self.dims.z_total, "g"), C.byref(opt),
+            float(act_tol), float(bound_tol), int(bool(row_scaling)), int(max_iters), float(rel_tol),
+            self._check(lam, self.dims.c_total, "lam"), ptr(lag, self.dims.z_total, "lag"),
+            ptr(info, self.B * _lib.MULT_INFO_STRIDE, "info")))
+        return (lam, None if lag is False else lag,
+                None if info is False else info.view(-1)[: self.B * _lib.MULT_INFO_STRIDE].view(self.B, _lib.MULT_INFO_STRIDE))
+
     def solve(self, Z, info=None, **options):
         """Batched solve of the reference NLP (solve(), src/moi.jl:46-103) on the GPU, in place on `Z` (device tensor,
         layout of Z; the controls of the guess are used, the states are rolled out from x0).  `options`: fields of
@@ -950,6 +988,23 @@ class HybridNLP:
         _lib.check(_lib.lib().qln_eval_constraint_vjp_host(self._h, Z.ctypes.data, lam.ctypes.data, g.ctypes.data))
         return g
 
+    def estimate_multipliers_host(self, Z, c=None, g=None, *, act_tol: float = 1e-6, bound_tol: float = 1e-8,
+                                  row_scaling: bool = True, max_iters: int = 20000, rel_tol: float = 1e-8, want_lag: bool = True,
+                                  want_info: bool = True, **bounds):
+        """estimate_multipliers with host arrays (MOI mode): returns numpy (lam (c_total,), lag (z_total,) or None,
+        info (B, 16) or None)."""
+        Z = self._host_Z(Z)
+        c = self.eval_c_host(Z) if c is None else self._host_c(c, "c")
+        g = self.grad_f_host(Z) if g is None else self._host_Z(g, "g")
+        lam = np.zeros(self.dims.c_total)
+        lag = np.zeros(self.dims.z_total) if want_lag else None
+        info = np.zeros((self.B, _lib.MULT_INFO_STRIDE)) if want_info else None
+        opt = self._bound_options(bounds)
+        _lib.check(_lib.lib().qln_estimate_multipliers_host(
+            self._h, Z.ctypes.data, c.ctypes.data, g.ctypes.data, C.byref(opt), float(act_tol), float(bound_tol),
+            int(bool(row_scaling)), int(max_iters), float(rel_tol), lam.ctypes.data, _host_ptr(lag), _host_ptr(info)))
+        return lam, lag, info
+
     def jac_c_dense_host(self, Z_b, jac, b: int = 0):
         """Reference-compatible dense Jacobian of problem b: `jac` is a Fortran-ordered
         (m_nlp, n_nlp) float64 array; only the jac_c! write-set is assigned."""
@@ -1007,6 +1062,24 @@ def _variable_bounds(N: int, quirk_Q6: bool):
 def variable_bounds_forces(N: int):
     """The bounds the comment in src/moi.jl:63 describes (F1y, F2y >= 0) -- not what the reference does."""
     return _variable_bounds(N, False)
+
+
+def split_bound_multipliers(lag, Z, x_l=None, x_u=None, *, bound_tol: float = 1e-8):
+    """(z_L, z_U) of Ipopt's convention (grad f + J'lam - z_L + z_U = 0) from the fixed columns of `lag` = g + A'lam as
+    estimate_multipliers returns it: lag_j = z_L_j - z_U_j where Z_j is within bound_tol of a bound, so z_L = max(lag, 0)
+    at a lower bound and z_U = max(-lag, 0) at an upper one; both are >= 0 where the sign is right and 0 where it is not
+    (info[8] counts those) and on every free column.  `lag`, `Z`: (..., n_nlp) arrays of the same shape; x_l, x_u default to
+    variable_bounds(N)."""
+    lag, Z = np.asarray(lag, dtype=np.float64), np.asarray(Z, dtype=np.float64)
+    if x_l is None or x_u is None:
+        x_l, x_u = variable_bounds((Z.shape[-1] + 5) // 20)
+    with np.errstate(invalid="ignore"):
+        at_l, at_u = Z <= x_l + bound_tol, Z >= x_u - bound_tol
+    if bound_tol < 0:
+        at_l, at_u = np.zeros_like(at_l), np.zeros_like(at_u)
+    z_L = np.where(at_l & ~at_u, np.maximum(lag, 0.0), 0.0)
+    z_U = np.where(at_u & ~at_l, np.maximum(-lag, 0.0), 0.0)
+    return z_L, z_U
 
 
 def ipopt_initial_point(Z0, x_l, x_u, *, bound_push: float = 1e-2, bound_frac: float = 1e-2,
