@@ -8,10 +8,32 @@ Im f(z + i*eps*e_j)/eps is its exact derivative up to rounding.
 """
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 
 G, MB, MF, LB = -9.81, 10.0, 0.1, 0.5  # src/planar_quadruped.jl:11-20
 IB = MB * LB**2 / 12
+
+
+@contextlib.contextmanager
+def model(g, mb, mf, lb):
+    """Evaluate with another robot model inside the `with` block: G, MB, MF, LB and IB are set to the given values and
+    put back on exit, also when the block raises.  Everything below reads them at call time, so callers of this module
+    (tests/rollout_vjp_ref.py, tests/hessian_sym.py, ...) follow without a parameter of their own.  Not thread-safe."""
+    global G, MB, MF, LB, IB
+    saved = (G, MB, MF, LB, IB)
+    G, MB, MF, LB = float(g), float(mb), float(mf), float(lb)
+    IB = MB * LB**2 / 12
+    try:
+        yield
+    finally:
+        G, MB, MF, LB, IB = saved
+
+
+def constants():
+    """(G, MB, MF, LB) as they stand now: what a cache of anything derived from this module must be keyed on."""
+    return G, MB, MF, LB
 
 
 def dynamics(mode, s, u):

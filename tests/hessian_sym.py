@@ -26,9 +26,15 @@ COST_SYMS = sp.symbols("c0:41")
 CASES = [(mode, jump) for mode in (1, 2, 3) for jump in (False, True) if not (mode == 3 and jump)]
 
 
-@functools.lru_cache(maxsize=None)
 def lagrangian_hessian(mode: int, jump: bool):
-    """Lower triangle {(row, col): expression} of the knot's Lagrangian without the clearance term."""
+    """Lower triangle {(row, col): expression} of the knot's Lagrangian without the clearance term, for the model
+    constants np_oracle holds at the time of the call (they are part of the cache key: the expansions bake them in)."""
+    return _lagrangian_hessian(mode, jump, npo.constants())
+
+
+@functools.lru_cache(maxsize=None)
+def _lagrangian_hessian(mode: int, jump: bool, consts):
+    assert consts == npo.constants()
     z = np.array(Z_SYMS, dtype=object)
     x, u = z[:15], z[15:]
     step = npo.rk4(mode, x, u)
@@ -55,15 +61,21 @@ def step_pattern():
     return sorted(ent, key=lambda rc: (rc[1], rc[0]))
 
 
-@functools.lru_cache(maxsize=None)
 def _lambdified(mode: int, jump: bool):
-    H = lagrangian_hessian(mode, jump)
+    return _lambdified_for(mode, jump, npo.constants())
+
+
+@functools.lru_cache(maxsize=None)
+def _lambdified_for(mode: int, jump: bool, consts):
+    H = _lagrangian_hessian(mode, jump, consts)
     args = list(Z_SYMS) + list(MU_SYMS) + [SIGMA] + list(COST_SYMS)
     return {rc: sp.lambdify(args, e, "numpy") for rc, e in H.items()}
 
 
-def clearance_curvature(theta, lb=npo.LB):
-    """d/dtheta of jac_c!'s clearance entry (quirk Q3): +(lb/2) sin(theta) for theta > 0, -(lb/2) sin(theta) otherwise."""
+def clearance_curvature(theta, lb=None):
+    """d/dtheta of jac_c!'s clearance entry (quirk Q3): +(lb/2) sin(theta) for theta > 0, -(lb/2) sin(theta) otherwise;
+    lb = None reads np_oracle's LB at the time of the call."""
+    lb = npo.LB if lb is None else lb
     theta = np.asarray(theta, dtype=np.float64)
     return np.where(theta > 0, (lb / 2) * np.sin(theta), -((lb / 2) * np.sin(theta)))
 
