@@ -6,7 +6,9 @@ in LDS where the step keeps five.  The per-iteration figure is the launch time o
 loads, the row norms) and, for the estimate, the epilogue (one more transposed product, the second read of g).
 Also reports the second figure that separates the two: the same launches with 200 iterations, so that
 (t200 - t100) / 100 is the cost of an iteration alone.  Prints one JSON line.
-   python bench/multiplier_timing.py [B ...]"""
+N = 40 keeps every knot's step block in registers; --N above 64 (the tests use 80) times the variants that re-derive it.
+   python bench/multiplier_timing.py [--N N] [B ...]"""
+import argparse
 import json
 import os
 import sys
@@ -58,6 +60,9 @@ def run(B, N=40, k_trans=14):
 
 
 if __name__ == "__main__":
-    Bs = [int(a) for a in sys.argv[1:]] or [1024, 65536]
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--N", type=int, default=40, help="knots per problem (above 64: the variants that re-derive the step blocks)")
+    ap.add_argument("B", type=int, nargs="*", default=[1024, 65536], help="batch sizes")
+    args = ap.parse_args()
     print(json.dumps({"kernel": "qln_estimate_multipliers vs qln_gauss_newton_step", "launches": 5, "warmup": 2,
-                      "results": [run(B) for B in Bs]}))
+                      "results": [run(B, args.N) for B in args.B]}))

@@ -148,11 +148,6 @@ __device__ __forceinline__ double read_lane(double v, int src) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), src), hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
     return __hiloint2double(hi, lo);
 }
-__device__ __forceinline__ double wmax(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, kWave));
-    return v;
-}
 
 struct StageIn {
     const double* rec;   // cost record [41] (global, wave-uniform address)
@@ -519,7 +514,7 @@ __global__ __launch_bounds__(kWave, OCC) void k_al_ilqr(BatchParams P, SolvePara
             }
         }
         J = wave_sum(Jl);
-        vmax = wmax(vl);
+        vmax = wave_max(vl);
         wave_lds_sync();
     };
 

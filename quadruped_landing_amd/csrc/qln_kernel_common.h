@@ -1,5 +1,5 @@
 // qln_kernel_common.h -- device code shared by the gfx950 kernel files.  Internal.
-//   * wave / dispatch helpers (xcd_contiguous_index, wave_lds_sync, wave_sum);
+//   * wave / dispatch helpers (xcd_contiguous_index, wave_lds_sync, wave_sum, wave_max);
 //   * the value path: dynamics, rk4_step, step_forward (one knot of a roll-out), literal restatements of the reference
 //     that round like it;
 //   * clearance_dtheta, the one derivative entry of the clearance rows (the J v / J' lam products and the covariance
@@ -52,6 +52,12 @@ __device__ __forceinline__ void wave_lds_sync() {
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+    return v;
+}
+// max over the wave's 64 lanes, the same bits in every lane (fmax: a NaN loses)
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, kWave));
     return v;
 }
 

@@ -396,7 +396,6 @@ __device__ __forceinline__ void lds_jvp(const ProblemView& pv, const Model& M, c
     }
 }
 
-// gz = A' lam, all operands in LDS
 // (A D)' lam
 __device__ __forceinline__ void lds_vjp(const ProblemView& pv, const Model& M, const double* z, const double* lam,
                                         const double* dsc, const double* mask, double* gz, int lane) {
@@ -619,13 +618,6 @@ __global__ __launch_bounds__(kWave, 1) void k_gauss_newton_step(BatchParams P, c
 // HBM traffic of a call: read Z, the clearance rows of c, g (once for the right-hand side, once more behind the loop
 // for lag: g D loses the fixed columns and LDS has no room for a fifth n-vector); write lam, lag, info.
 // ---------------------------------------------------------------------------------------------
-// max over the wave's 64 lanes, the same bits in every lane (fmax: a NaN loses)
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, kWave));
-    return v;
-}
-
 // which bound entry j of Z sits on, to bound_tol: bit 0 = the lower, bit 1 = the upper (a NaN sits on neither)
 __device__ __forceinline__ int bound_side(const MultiplierParams& mp, int N, int j, double zj) {
     if (mp.bound_tol < 0.0) return 0;
@@ -917,20 +909,25 @@ hipError_t launch_constraint_vjp(const BatchParams& p, const double* Z, const do
     return hipGetLastError();
 }
 
+// One wave per problem with `lds` bytes of dynamic LDS each (more than the 64 KB a kernel may have without asking)
+template <class K, class... Args>
+static hipError_t launch_in_lds(K kernel, size_t lds, hipStream_t stream, const BatchParams& p, Args... args) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(xcd_grid(p.B)), dim3(kWave), lds, stream, p, args...);
+    return hipGetLastError();
+}
+
 // LDS bytes one problem of the Gauss-Newton step needs (largest m_nlp is at k_trans = 1)
 size_t gauss_newton_lds_bytes(int32_t N) { return sizeof(double) * (size_t)(5 * (20 * N - 5) + 2 * row_layout(N, 1).m + N); }
 
 hipError_t launch_gauss_newton_step(const BatchParams& p, const double* Z, const double* c, double* dZ, int max_iters,
                                     double rel_tol, const double* radius, const double* col_scale, double* info,
                                     hipStream_t stream) {
-    const size_t lds = gauss_newton_lds_bytes(p.N);
     auto go = [&](auto kernel) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel, dim3(xcd_grid(p.B)), dim3(kWave), lds, stream, p, Z, c, dZ, max_iters, rel_tol, radius,
-                           col_scale, info);
-        return hipGetLastError();
+        return launch_in_lds(kernel, gauss_newton_lds_bytes(p.N), stream, p, Z, c, dZ, max_iters, rel_tol, radius, col_scale,
+                             info);
     };
     // one knot per lane: the step blocks stay in registers for the whole step
     return (p.N <= kWave) ? go(k_gauss_newton_step<true>) : go(k_gauss_newton_step<false>);
@@ -941,13 +938,8 @@ size_t multiplier_lds_bytes(int32_t N) { return sizeof(double) * (size_t)(4 * (2
 
 hipError_t launch_estimate_multipliers(const BatchParams& p, const MultiplierParams& mp, const double* Z, const double* c,
                                        const double* g, double* lam, double* lag, double* info, hipStream_t stream) {
-    const size_t lds = multiplier_lds_bytes(p.N);
     auto go = [&](auto kernel) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel, dim3(xcd_grid(p.B)), dim3(kWave), lds, stream, p, mp, Z, c, g, lam, lag, info);
-        return hipGetLastError();
+        return launch_in_lds(kernel, multiplier_lds_bytes(p.N), stream, p, mp, Z, c, g, lam, lag, info);
     };
     // one knot per lane: the step blocks stay in registers for the whole solve
     return (p.N <= kWave) ? go(k_estimate_multipliers<true>) : go(k_estimate_multipliers<false>);

@@ -64,7 +64,8 @@ def _setup(batch):
     return torch, nlp, Z, c
 
 
-@pytest.mark.parametrize("B,N,ragged", [(3, 40, False), (5, 17, True), (2, 80, True), (2, 3, False)])
+@pytest.mark.parametrize("B,N,ragged", [(3, 40, False), (5, 17, True), (2, 80, True), (2, 3, False), (2, 64, True),
+                                        (2, 65, True)])
 def test_iterates_follow_numpy_cgls_on_the_oracle_jacobian(B, N, ragged):
     from quadruped_landing_amd import problem_gen as PG
 

@@ -74,7 +74,8 @@ def _against_restatement(nlp, batch, out, problems=None, tol=1e-8, **kw):
 
 
 @pytest.mark.parametrize("row_scaling", [False, True])
-@pytest.mark.parametrize("B,N,ragged", [(3, 40, False), (5, 17, True), (2, 80, True), (2, 3, False), (2, 2, False)])
+@pytest.mark.parametrize("B,N,ragged", [(3, 40, False), (5, 17, True), (2, 80, True), (2, 3, False), (2, 2, False), (2, 64, True),
+                                        (2, 65, True)])
 def test_iterates_follow_the_numpy_restatement_on_the_oracle_jacobian(B, N, ragged, row_scaling):
     from quadruped_landing_amd import problem_gen as PG
 
