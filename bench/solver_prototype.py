@@ -2,7 +2,9 @@
 GPU: augmented-Lagrangian iLQR ("Riccati sweep per problem") for the reference NLP of src/moi.jl:46-103.
 
 Development aid only -- run here to choose the algorithm and its constants before writing kernels; not imported by the
-product, not a test.  The dynamics / Jacobians come from the oracle (test infrastructure).
+product, not a test.  It is NOT the current statement of the method: it still has the kinked clearance row, eight step
+lengths with an Armijo test and no h_prox.  tests/ilqr_ref.py is -- the restatement the kernel's iterates are held to
+(tests/test_gpu_ilqr_iterates.py).  The dynamics / Jacobians come from the oracle (test infrastructure).
 
   python bench/solver_prototype.py [notebook|random N kt seed] [reference|exact]
 """

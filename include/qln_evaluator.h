@@ -268,8 +268,12 @@ int qln_gauss_newton_step(qln_handle* h, const double* Z, const double* c, doubl
  * stop test on its own closed-form roll-out of the same controls, which differs from it by rounding (1e-15 per step): with
  * status = 0 the reported violation can exceed tol_violation by that much.  max_outer = 0 and rescue_outer = 0 make the
  * call a roll-out-and-report of the given controls (status 1).
- * There is no reference oracle for the iterates (the reference hands its callbacks to Ipopt); the result is judged by
- * this evaluator: qln_eval_constraint + qln_constraint_violation and qln_eval_objective on the returned Z.
+ * The reference holds nothing to compare the iterates with (it hands its callbacks to Ipopt); the result is judged by
+ * this evaluator: qln_eval_constraint + qln_constraint_violation and qln_eval_objective on the returned Z.  The iterates
+ * themselves are held to a numpy restatement of the method run in double and in 80-bit extended precision
+ * (tests/ilqr_ref.py, tests/test_gpu_ilqr_iterates.py): controls, counts, step lengths, mu and rho of single and of twelve
+ * iterations.  The sweep differentiates the step the roll-out takes: the clock x[14] is kept through the jump, so a cost
+ * with a weight on it is handled consistently.
  * Needs a cost table.  QLN_ERR_UNSUPPORTED if a problem does not fit the LDS of a CU (N > ~650).  Stream-ordered.
  * The first call on a handle allocates the solver's device scratch, 494 N doubles per problem (158 KB at N = 40: step
  * entries, feedback laws, the sixteen trial trajectories, multipliers), kept until qln_destroy -- a 10-GB hipMalloc at

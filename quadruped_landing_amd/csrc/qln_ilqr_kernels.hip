@@ -18,14 +18,18 @@
 // (quirk Q2): within an iteration the stage weights h_k are frozen -- the fixed point is the kind of point Ipopt's
 // run tends to with that gradient.  exact_h adds the missing term (a stationary point of the true objective).
 //
-// The step Jacobians A_k, B_k are the closed-form blocks of the evaluator (step_block / for_each_step_entry of
-// qln_kernel_common.h), derived once per sweep by lane = knot and parked in a global scratch.  Per problem that scratch holds the step entries
+// The step Jacobians A_k, B_k are the closed-form blocks of the roll-out (step_block / for_each_rollout_entry of
+// qln_kernel_common.h: the evaluator's blocks with the clock row kept at the jump, which is what the roll-out does), derived
+// once per sweep by lane = knot and parked in a global scratch.  Per problem that scratch holds the step entries
 // (88 N doubles), the feedback law of every knot (80 N), the sixteen trial trajectories (320 N) and the inequality
 // multipliers (6 N); the wave's LDS holds the current trajectory, 9 scalars per knot and the sweep's matrices
 // (29 N + 1.4 k doubles: 20.3 KB at N = 40, eight waves per CU).
 //
-// The reference holds nothing to compare the iterates with (it hands its callbacks to Ipopt 3.13 + MUMPS); the result
-// is checked by the evaluator itself: constraint violation and objective of the returned Z (tests/test_gpu_solve.py).
+// The reference holds nothing to compare the iterates with (it hands its callbacks to Ipopt 3.13 + MUMPS).  The result
+// is checked by the evaluator itself: constraint violation and objective of the returned Z (tests/test_gpu_solve.py); the
+// iterates are held to tests/ilqr_ref.py, a numpy restatement of the method above run in float64 and in 80-bit long double:
+// single iterations, chained first iterations and twelve-iteration runs agree with it control by control within 100 times
+// the two precisions' own distance, and in every count, step length, mu and rho (tests/test_gpu_ilqr_iterates.py).
 #include "qln_row16.h"
 
 #include <cmath>
@@ -550,7 +554,12 @@ __global__ __launch_bounds__(kWave, OCC) void k_al_ilqr(BatchParams P, SolvePara
                     const double* uk = L.U + 5 * k;
                     const StepBlock blk = step_block(x, uk[0], uk[1], uk[2], uk[3], uk[4], knot_mode(k + 1, kt - 1, im), M);
                     double* e = ent + (int64_t)k * kEnt;
-                    for_each_step_entry(blk, [&](auto row, auto col, double val) {
+                    // The ROLL-OUT's block, not the evaluator's: step_fast / step_forward keep the clock through the jump, the
+                    // evaluator's block carries the reference's jump mask on the clock row (quirk Q1).  With a weight on x[14]
+                    // (set_lqr_cost takes any Q) the masked row makes the sweep differentiate another cost than the one the
+                    // line search evaluates; with the default weight 0, P[:, 14] and pv[14] are exact zeros and the two
+                    // blocks give the same iterates (tests/test_gpu_ilqr_iterates.py).
+                    for_each_rollout_entry(blk, [&](auto row, auto col, double val) {
                         constexpr int pos_ = step_union_pos(row, col);
                         e[pos_] = val;
                     });

@@ -1,0 +1,515 @@
+"""numpy yardstick of qln_solve's iterates: augmented-Lagrangian iLQR as the file header of
+quadruped_landing_amd/csrc/qln_ilqr_kernels.hip and include/qln_evaluator.h (qln_solve) state the method, generic in the
+dtype so that the same statement runs in np.float64 and in np.longdouble (80-bit).  TEST INFRASTRUCTURE ONLY, no GPU.
+
+It is written from the method, not from the lane code:
+
+  step         oracle.np_oracle.rk4, then jump_map at the jump knot (1-based knot k_trans - 1).  That module honours
+               np_oracle.model(...), and so does everything here (the model is read when a function is called).
+  derivative   the step is polynomial in [x; u]: its 15 x 20 derivative is the complex step in the working precision, all
+               knots at once.  It is the derivative of what the roll-out computes, so it keeps the clock row (row 14) at
+               the jump.  clock_row="masked" zeroes that row at the jump knot, which is what the evaluator's block (the
+               reference's jump mask, quirk Q1) carries there: a diagnostic switch, not the method.
+  stage cost   w_k l_k(x, u) + sum_j (t_j^2 - lam_j^2) / (2 rho), t = max(0, lam + rho g), over the inequality rows g <= 0 of
+               the knots after the first: the two smooth clearance rows -(yb -+ (lb/2) sin theta), the theta bounds, and
+               with q6_bounds the rows -yb and -x1; lam e + rho e^2 / 2 for the final-control row F1y + F2y + mb g at the last
+               control knot and for the terminal rows x_N[0:14] - xf[0:14].
+  derivatives  gradient and Gauss-Newton Hessian of those terms (rho a a' for an active row or an equality row with
+               gradient a), the cost record's diagonal times the weight.  The weights w_k = h_k are frozen at the current
+               trajectory during the line search unless exact_h_gradient is set, which adds l_k to the h gradient and
+               weighs the trial cost with the trial's own h.
+  sweep        Quu = Huu + B'PB + mu I, + h_prox on (h, h);  d = -Quu^-1 Qu, K = -Quu^-1 Qux by a hand-written LDL'
+               (np.linalg.solve does not take longdouble); the box on h: where h_k + d_h leaves [h_min, h_max] the
+               feed-forward is clamped, the free 4 x 4 solved again and the gain row of h zeroed;
+               P <- sym(Qxx + Qux'K), pv <- Qx + Qux'd.
+  forward      sixteen closed-loop roll-outs u = u_k + alpha d_k + K_k (x - x_k), h clipped, alpha = 2^-a; the lowest cost
+               below the current one is taken, ties to the smaller a.
+  control flow qln_ilqr_kernels.hip, k_al_ilqr: mu reset to mu0 per outer iteration, mu x 10 when the factorisation or the
+               line search fails (stalled at mu_max), mu / 3 on acceptance, the inner_tol break, the stop test on the
+               violation, multipliers lam <- max(0, lam + rho g) / lam + rho e, rho x rho_factor while the violation is above
+               a quarter of the previous one, status 0 / 1 / 2.  The rescue phase is left out (rescue_outer = 0).
+
+MU0, MU_MIN, MU_MAX are the constants qln_solve() puts into SolveParams (quadruped_landing_amd/csrc/qln_api.cpp,
+"sp.mu0 = 1e-6; sp.mu_min = 1e-8; sp.mu_max = 1e6;").
+
+Every discrete decision of a run is recorded with its margin (Result.margins), so that a caller can tell a disagreement of
+the code under test from a decision that the arithmetic cannot settle.
+"""
+from __future__ import annotations
+
+import dataclasses
+import math
+
+import numpy as np
+
+from oracle import np_oracle as NP
+
+MU0, MU_MIN, MU_MAX = 1e-6, 1e-8, 1e6  # qln_api.cpp, qln_solve(): sp.mu0 / sp.mu_min / sp.mu_max
+N_ALPHA = 16
+PIVOT_MIN = 1e-300  # a pivot of Quu's factorisation has to exceed this
+JUMP_ROWS = [4, 6, 10, 11, 12, 13]
+
+
+def require_extended_precision():
+    """np.longdouble has to be the 80-bit type: a platform where it is a plain double would compare float64 with itself."""
+    eps = np.finfo(np.longdouble).eps
+    assert eps < 1.1e-19, f"np.longdouble is not the 80-bit extended type here (eps = {eps})"
+
+
+@dataclasses.dataclass(frozen=True)
+class Options:
+    """fields and defaults of qln_solve_options (qln_solve_default_options), without the rescue phase"""
+    max_outer: int = 80
+    max_inner: int = 6
+    tol_violation: float = 1e-6
+    inner_tol: float = 1e-7
+    rho0: float = 3.0
+    rho_factor: float = 5.0
+    rho_max: float = 1e8
+    h_min: float = 0.001
+    h_max: float = 0.02
+    theta_min: float = -math.pi / 2
+    theta_max: float = math.pi / 2
+    q6_bounds: int = 1
+    exact_h_gradient: int = 0
+    h_prox: float = 1e4
+
+    def gpu_kwargs(self):
+        return dict(dataclasses.asdict(self), rescue_outer=0)
+
+
+@dataclasses.dataclass
+class Problem:
+    N: int
+    k_trans: int
+    init_mode: int
+    x0: np.ndarray    # (15,)
+    xf: np.ndarray    # (15,)
+    cost: np.ndarray  # (N, 41)
+
+    def __post_init__(self):
+        self.N, self.k_trans, self.init_mode = int(self.N), int(self.k_trans), int(self.init_mode)
+        assert self.N >= 2 and self.cost.shape == (self.N, 41)
+        self.mode, self.jump = NP.knot_modes(self.N, self.k_trans, self.init_mode)
+
+    @classmethod
+    def of_batch(cls, batch, b, cost=None):
+        cost = batch.obj if cost is None else cost
+        return cls(batch.N, batch.k_trans[b], batch.init_mode[b], batch.x0[b], batch.xf[b], cost[b] if cost.ndim == 3 else cost)
+
+
+def controls_of(Z, N):
+    """(N-1, 5) controls of a decision vector (20 N - 5,)"""
+    return np.array([Z[20 * k + 15: 20 * k + 20] for k in range(N - 1)])
+
+
+# ---- dynamics -----------------------------------------------------------------------------------------------------------
+def step(p, k, x, u):
+    """x_{k+1} of 0-based knot k; x (..., 15), u (..., 5)"""
+    xn = NP.rk4(int(p.mode[k]), x, u)
+    return NP.jump_map(xn) if p.jump[k] else xn
+
+
+def rollout(p, U, T):
+    X = np.zeros((p.N, 15), dtype=T)
+    X[0] = np.asarray(p.x0, dtype=T)
+    for k in range(p.N - 1):
+        X[k + 1] = step(p, k, X[k], U[k])
+    return X
+
+
+def step_blocks(p, X, U, T, clock_row="rollout"):
+    """(N-1, 15, 20) derivatives of step() at (X[k], U[k]) by complex-step differentiation in the precision of T"""
+    assert clock_row in ("rollout", "masked")
+    n1 = p.N - 1
+    C = np.clongdouble if T is np.longdouble else np.complex128
+    eps = T(1e-30)
+    z = np.concatenate([X[:-1], U], axis=1).astype(C)
+    Zp = np.repeat(z[:, None, :], 20, axis=1)  # [knot, perturbed entry, entry]
+    idx = np.arange(20)
+    Zp[:, idx, idx] += C(1j) * eps
+    J = np.zeros((n1, 15, 20), dtype=T)
+    for m in np.unique(p.mode):
+        sel = p.mode == m
+        out = NP.rk4(int(m), Zp[sel][..., :15], Zp[sel][..., 15:])
+        J[sel] = np.swapaxes(out.imag / eps, 1, 2)
+    for k in np.nonzero(p.jump)[0]:
+        J[k, JUMP_ROWS, :] = 0
+        if clock_row == "masked":
+            J[k, 14, :] = 0
+    return J
+
+
+# ---- augmented stage cost -----------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class Terms:
+    J: np.ndarray      # augmented cost (...)
+    viol: np.ndarray   # largest violation (...)
+    ell: np.ndarray    # l_k (..., N)
+    g: np.ndarray      # inequality rows (..., N, 6), g <= 0 is feasible
+    t: np.ndarray      # max(0, lam + rho g) where the row is live, else 0
+    e_fc: np.ndarray   # final-control residual (...)
+    e_T: np.ndarray    # terminal residuals (..., 14)
+
+
+def live_rows(p, o):
+    on = np.zeros((p.N, 6), dtype=bool)
+    on[1:, :4] = True
+    if o.q6_bounds:
+        on[1:, 4:] = True
+    return on
+
+
+def inequality_rows(X, o, T):
+    lb2 = T(NP.LB) / 2
+    yb, th, x1 = X[..., 1], X[..., 2], X[..., 3]
+    s = np.sin(th)
+    return np.stack([-(yb - lb2 * s), -(yb + lb2 * s), th - T(o.theta_max), T(o.theta_min) - th, -yb, -x1], axis=-1)
+
+
+def stage_terms(p, o, X, U, lam, leq, rho, W, T):
+    """X (..., N, 15), U (..., N-1, 5), lam (N, 6), leq (15,): multipliers of the terminal rows [0:14] and of the
+    final-control row [14]; W (..., N-1): the weights on l_k of the control knots (the terminal knot has weight 1)."""
+    N = p.N
+    rec = np.asarray(p.cost, dtype=T)
+    D, R, q, r, c = rec[:, :15], rec[:-1, 15:20], rec[:, 20:35], rec[:-1, 35:40], rec[:, 40]
+    ell = c + np.sum(T(0.5) * D * X * X + q * X, axis=-1)
+    ell[..., :-1] += np.sum(T(0.5) * R * U * U + r * U, axis=-1)
+    on = live_rows(p, o)
+    g = inequality_rows(X, o, T)
+    t = np.where(on, np.maximum(T(0), lam + rho * g), T(0))
+    pen = np.where(on, (t * t - lam * lam) / (2 * rho), T(0))
+    e_fc = U[..., N - 2, 1] + U[..., N - 2, 3] + T(NP.MB) * T(NP.G)
+    e_T = X[..., N - 1, :14] - np.asarray(p.xf, dtype=T)[:14]
+    J = np.sum(W * ell[..., :-1], axis=-1) + ell[..., -1] + np.sum(pen, axis=(-1, -2))
+    J = J + leq[14] * e_fc + T(0.5) * rho * e_fc * e_fc + np.sum(leq[:14] * e_T + T(0.5) * rho * e_T * e_T, axis=-1)
+    viol = np.maximum(np.max(np.where(on, g, T(0)), axis=(-1, -2)), T(0))
+    viol = np.maximum(viol, np.maximum(np.abs(e_fc), np.max(np.abs(e_T), axis=-1)))
+    return Terms(J, viol, ell, g, t, e_fc, e_T)
+
+
+def stage_derivatives(p, o, X, U, leq, rho, tm, T):
+    """gradient gz (N, 20) and Gauss-Newton Hessian Hzz (N, 20, 20) of the augmented cost in z_k = [x_k; u_k] at the current
+    trajectory, weights frozen at W = h_k; tm = stage_terms(...) there."""
+    N = p.N
+    rec = np.asarray(p.cost, dtype=T)
+    w = np.concatenate([U[:, 4], [T(1)]])
+    z = np.zeros((N, 20), dtype=T)
+    z[:, :15] = X
+    z[:-1, 15:] = U
+    Dz = rec[:, :20].copy()
+    dz = rec[:, 20:40].copy()
+    Dz[-1, 15:] = 0  # the terminal knot has no control
+    dz[-1, 15:] = 0
+    gz = w[:, None] * (Dz * z + dz)
+    Hzz = np.zeros((N, 20, 20), dtype=T)
+    Hzz[:, np.arange(20), np.arange(20)] = w[:, None] * Dz
+    # inequality rows: gradient a_j of g_j in x
+    cq = (T(NP.LB) / 2) * np.cos(X[:, 2])
+    a = np.zeros((N, 6, 20), dtype=T)
+    a[:, 0, 1], a[:, 0, 2] = -1, cq
+    a[:, 1, 1], a[:, 1, 2] = -1, -cq
+    a[:, 2, 2], a[:, 3, 2] = 1, -1
+    a[:, 4, 1] = -1
+    a[:, 5, 3] = -1
+    active = (tm.t > 0).astype(T)
+    gz += np.einsum("kj,kjz->kz", tm.t, a)
+    Hzz += rho * np.einsum("kj,kjz,kjy->kzy", active, a, a)
+    # final-control row at the last control knot
+    afc = np.zeros(20, dtype=T)
+    afc[16] = afc[18] = 1
+    gz[N - 2] += (leq[14] + rho * tm.e_fc) * afc
+    Hzz[N - 2] += rho * np.outer(afc, afc)
+    # terminal rows
+    gz[N - 1, :14] += leq[:14] + rho * tm.e_T
+    Hzz[N - 1, np.arange(14), np.arange(14)] += rho
+    if o.exact_h_gradient:
+        gz[:-1, 19] += tm.ell[:-1]
+    return gz, Hzz
+
+
+# ---- 5 x 5 elimination --------------------------------------------------------------------------------------------------
+def ldl(Q):
+    """Q = L D L' without pivoting -> (L, D); D's entries are the pivots"""
+    n = Q.shape[0]
+    L = np.eye(n, dtype=Q.dtype)
+    Dv = np.zeros(n, dtype=Q.dtype)
+    for j in range(n):
+        Dv[j] = Q[j, j] - np.sum(L[j, :j] * L[j, :j] * Dv[:j])
+        for i in range(j + 1, n):
+            L[i, j] = (Q[i, j] - np.sum(L[i, :j] * L[j, :j] * Dv[:j])) / Dv[j]
+    return L, Dv
+
+
+def ldl_solve(L, Dv, rhs):
+    """solve (L D L') y = rhs, rhs (n, m)"""
+    n = L.shape[0]
+    y = np.array(rhs, copy=True)
+    for i in range(n):
+        y[i] -= L[i, :i] @ y[:i]
+    y /= Dv[:, None]
+    for i in range(n - 1, -1, -1):
+        y[i] -= L[i + 1:, i] @ y[i + 1:]
+    return y
+
+
+# ---- backward sweep -----------------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class Sweep:
+    ok: bool
+    K: np.ndarray = None        # (N-1, 5, 15)
+    d: np.ndarray = None        # (N-1, 5)
+    Qu: np.ndarray = None       # (N-1, 5)
+    clamped: np.ndarray = None  # (N-1,) -1 / 0 / +1: clamped from below / free / from above
+    clamp_margin: float = math.inf  # smallest distance of an unclamped h + d_h from the bound it was tested against / h_max
+    pivot_min: float = math.inf
+
+
+def backward(p, o, U, gz, Hzz, blocks, mu, T):
+    N = p.N
+    P = Hzz[N - 1, :15, :15].copy()
+    pv = gz[N - 1, :15].copy()
+    sw = Sweep(True, np.zeros((N - 1, 5, 15), dtype=T), np.zeros((N - 1, 5), dtype=T), np.zeros((N - 1, 5), dtype=T),
+               np.zeros(N - 1, dtype=int))
+    h_lo, h_hi = T(o.h_min), T(o.h_max)
+    for k in range(N - 2, -1, -1):
+        A, B = blocks[k][:, :15], blocks[k][:, 15:]
+        Qxx = Hzz[k, :15, :15] + A.T @ P @ A
+        Qux = Hzz[k, 15:, :15] + B.T @ P @ A
+        Quu = Hzz[k, 15:, 15:] + B.T @ P @ B + T(mu) * np.eye(5, dtype=T)
+        Quu[4, 4] += T(o.h_prox)
+        Qx = gz[k, :15] + A.T @ pv
+        Qu = gz[k, 15:] + B.T @ pv
+        L, Dv = ldl(Quu)
+        sw.pivot_min = min(sw.pivot_min, float(np.min(Dv)) if np.all(np.isfinite(Dv)) else -math.inf)
+        if not np.all(Dv > PIVOT_MIN):
+            sw.ok = False
+            return sw
+        sol = ldl_solve(L, Dv, -np.concatenate([Qux, Qu[:, None]], axis=1))
+        K, d = sol[:, :15], sol[:, 15]
+        lo, hi = h_lo - U[k, 4], h_hi - U[k, 4]
+        if d[4] < lo or d[4] > hi:
+            sw.clamped[k] = -1 if d[4] < lo else 1
+            hc = min(max(d[4], lo), hi)
+            sol4 = ldl_solve(L[:4, :4], Dv[:4], -np.concatenate([Qux[:4], (Qu[:4] + Quu[:4, 4] * hc)[:, None]], axis=1))
+            K = np.zeros((5, 15), dtype=T)
+            K[:4] = sol4[:, :15]
+            d = np.concatenate([sol4[:, 15], [hc]])
+        sw.clamp_margin = min(sw.clamp_margin, float(min(abs(sol[4, 15] - lo), abs(sol[4, 15] - hi)) / h_hi))
+        sw.K[k], sw.d[k], sw.Qu[k] = K, d, Qu
+        P = Qxx + Qux.T @ K
+        P = T(0.5) * (P + P.T)
+        pv = Qx + Qux.T @ d
+    return sw
+
+
+# ---- forward pass -------------------------------------------------------------------------------------------------------
+def trial_rollouts(p, o, X, U, sw, alphas, T):
+    """closed-loop roll-outs for the step lengths `alphas` (n,) -> Xt (n, N, 15), Ut (n, N-1, 5)"""
+    alphas = np.asarray(alphas, dtype=T)
+    n = len(alphas)
+    Xt = np.zeros((n, p.N, 15), dtype=T)
+    Ut = np.zeros((n, p.N - 1, 5), dtype=T)
+    Xt[:, 0] = X[0]
+    for k in range(p.N - 1):
+        u = U[k] + alphas[:, None] * sw.d[k] + (Xt[:, k] - X[k]) @ sw.K[k].T
+        u[:, 4] = np.minimum(np.maximum(u[:, 4], T(o.h_min)), T(o.h_max))
+        Ut[:, k] = u
+        Xt[:, k + 1] = step(p, k, Xt[:, k], u)
+    return Xt, Ut
+
+
+def trial_costs(p, o, X, U, sw, alphas, lam, leq, rho, T):
+    Xt, Ut = trial_rollouts(p, o, X, U, sw, alphas, T)
+    W = Ut[..., 4] if o.exact_h_gradient else U[:, 4]
+    return stage_terms(p, o, Xt, Ut, lam, leq, rho, W, T).J, Xt, Ut
+
+
+# ---- the solve ----------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class Iteration:
+    """one pass of the inner loop (it counts in `iters` whether or not it ends in an accepted step)"""
+    outer: int
+    rho: float
+    mu: float                      # the mu the sweep ran with
+    J_cur: float
+    swept: bool                    # the factorisation went through
+    clamped: tuple = ()
+    active: bytes = b""            # which inequality rows were active in the Hessian, packed (active_rows: (N, 6) bool)
+    active_rows: np.ndarray = None
+    a_star: int = -1               # accepted step length 2^-a_star, -1: none
+    J_try: np.ndarray = None       # (16,)
+    U_try: np.ndarray = None       # (16, N-1, 5)
+    inner_break: bool = False
+    forced: bool = False
+    sweep: Sweep = None            # K, d, Qu, clamps of this iteration's sweep: the per-knot intermediates for a diagnosis
+
+
+@dataclasses.dataclass
+class Result:
+    U: np.ndarray
+    X: np.ndarray
+    outer: int
+    iters: int
+    rho: float
+    status: int
+    J: float
+    alpha: float
+    mu: float
+    viol: float
+    lam: np.ndarray
+    leq: np.ndarray
+    iterations: list
+    margins: list      # (iteration index or -1 for the outer loop, kind, relative margin)
+    outer_decisions: list
+
+    def info(self):
+        """what info[0, 1, 4, 5, 6, 7, 9] of qln_solve report"""
+        return np.array([self.outer, self.iters, self.rho, self.status, self.J, self.alpha, self.mu], dtype=np.float64)
+
+    def decisions(self):
+        """every discrete decision of the run, comparable between two precisions"""
+        its = [(i.outer, float(i.rho), float(i.mu), i.swept, i.clamped, i.active, i.a_star, i.inner_break) for i in self.iterations]
+        return its, self.outer_decisions, (self.outer, self.iters, float(self.rho), self.status, float(self.alpha), float(self.mu))
+
+    def min_margin(self):
+        return min((m for _, _, m in self.margins), default=math.inf)
+
+
+def _rel(a, b):
+    """relative distance of a from b, for a margin"""
+    s = max(abs(float(a)), abs(float(b)))
+    return abs(float(a) - float(b)) / s if s > 0 else math.inf
+
+
+def solve(p, U0, o=Options(), dtype=np.float64, clock_row="rollout", force_alpha=None, lam0=None, leq0=None, keep_trials=True):
+    """Run the method from the controls U0 (N-1, 5).  force_alpha: {iteration index: a} takes that trial instead of the
+    best one (for comparing against a run that chose another of two equally good step lengths)."""
+    T = dtype
+    if T is np.longdouble:
+        require_extended_precision()
+    N = p.N
+    U = np.array(U0, dtype=T)
+    U[:, 4] = np.minimum(np.maximum(U[:, 4], T(o.h_min)), T(o.h_max))
+    X = rollout(p, U, T)
+    lam = np.zeros((N, 6), dtype=T) if lam0 is None else np.array(lam0, dtype=T)
+    leq = np.zeros(15, dtype=T) if leq0 is None else np.array(leq0, dtype=T)
+    rho, mu = float(o.rho0), MU0  # the schedule is stated in double in either precision, as the kernel's parameters are
+    tol, inner_tol = T(o.tol_violation), T(o.inner_tol)
+    prev_viol = T(np.inf)
+    status, iters, outer, last_alpha = 1, 0, 0, T(0)
+    on = live_rows(p, o)
+    alphas = T(2) ** (-np.arange(N_ALPHA, dtype=T))
+    iterations, margins, outer_decisions = [], [], []
+    force_alpha = force_alpha or {}
+
+    def terms():
+        return stage_terms(p, o, X, U, lam, leq, T(rho), U[:, 4], T)
+
+    tm = terms()
+    while outer < o.max_outer:
+        mu = MU0
+        stalled = False
+        for _ in range(o.max_inner):
+            tm = terms()
+            J_cur = tm.J
+            iters += 1
+            idx = len(iterations)
+            it = Iteration(outer, rho, mu, float(J_cur), False)
+            iterations.append(it)
+            it.active_rows = tm.t > 0
+            it.active = np.packbits(it.active_rows).tobytes()
+            s = lam + T(rho) * tm.g
+            for k, j in zip(*np.nonzero(on)):
+                if not (s[k, j] == 0 and tm.g[k, j] == 0):  # (an exact zero of a pinned coordinate is structural: inactive)
+                    margins.append((idx, "active", abs(float(s[k, j])) / max(abs(float(lam[k, j])) + float(rho) * abs(float(tm.g[k, j])), 1e-300)))
+            gz, Hzz = stage_derivatives(p, o, X, U, leq, T(rho), tm, T)
+            blocks = step_blocks(p, X, U, T, clock_row)
+            sw = backward(p, o, U, gz, Hzz, blocks, mu, T)
+            it.sweep = sw
+            if not sw.ok:
+                margins.append((idx, "pivot", abs(sw.pivot_min)))
+                mu = min(mu * 10.0, MU_MAX)
+                if mu >= MU_MAX:
+                    stalled = True
+                    break
+                continue
+            it.swept = True
+            it.clamped = tuple(int(c) for c in sw.clamped)
+            margins.append((idx, "clamp", sw.clamp_margin))
+            J_try, Xt, Ut = trial_costs(p, o, X, U, sw, alphas, lam, leq, T(rho), T)
+            it.J_try = J_try
+            if keep_trials:
+                it.U_try = Ut
+            cand = np.where(np.isfinite(J_try) & (J_try < J_cur), J_try, T(np.inf))
+            a_star = int(np.argmin(cand))  # the first of equal minima: the smaller a
+            if idx in force_alpha:
+                a_star, it.forced = int(force_alpha[idx]), True
+                cand[a_star] = J_try[a_star]
+            if not cand[a_star] < J_cur:
+                margins.append((idx, "descent", _rel(np.min(J_try[np.isfinite(J_try)], initial=np.inf), J_cur)))
+                mu = min(mu * 10.0, MU_MAX)
+                if mu >= MU_MAX:
+                    stalled = True
+                    break
+                continue
+            J_new = J_try[a_star]
+            others = np.delete(J_try, a_star)
+            others = others[np.isfinite(others)]
+            if len(others):
+                margins.append((idx, "best", _rel(np.min(others), J_new)))
+            margins.append((idx, "descent", _rel(J_new, J_cur)))
+            it.a_star = a_star
+            last_alpha = alphas[a_star]
+            X, U = Xt[a_star].copy(), Ut[a_star].copy()
+            mu = max(mu / 3.0, MU_MIN)
+            dJ, thr = J_cur - J_new, inner_tol * (1 + abs(J_new))
+            if thr > 0:
+                margins.append((idx, "inner_tol", _rel(dJ, thr)))
+            if dJ < thr:
+                it.inner_break = True
+                break
+        tm = terms()
+        viol = tm.viol
+        margins.append((-1, "tol", _rel(viol, tol)))
+        if viol <= tol:
+            status = 0
+            outer += 1
+            outer_decisions.append((True, False))
+            break
+        lam = np.where(on, tm.t, lam)
+        leq[:14] += T(rho) * tm.e_T
+        leq[14] += T(rho) * tm.e_fc
+        grow = bool(viol > T(0.25) * prev_viol)
+        if np.isfinite(prev_viol):
+            margins.append((-1, "stall", _rel(viol, T(0.25) * prev_viol)))
+        if grow:
+            rho = min(rho * float(o.rho_factor), float(o.rho_max))
+        prev_viol = viol
+        if stalled and rho >= o.rho_max:
+            status = 2
+        outer_decisions.append((False, grow))
+        outer += 1
+    return Result(U, X, outer, iters, float(rho), status, float(tm.J), float(last_alpha), float(mu), float(tm.viol), lam, leq,
+                  iterations, margins, outer_decisions)
+
+
+# ---- measures -----------------------------------------------------------------------------------------------------------
+def control_error(Ua, V, h_max):
+    """e(U, V) = max_j max_k |U[k, j] - V[k, j]| / s_j with s_j = 1 + max_k |V[k, j]| for the forces and s_4 = h_max"""
+    Ua, V = np.asarray(Ua, dtype=np.longdouble), np.asarray(V, dtype=np.longdouble)
+    if Ua.size == 0:
+        return 0.0
+    s = 1 + np.max(np.abs(V), axis=0)
+    s[4] = h_max
+    d = np.abs(Ua - V)
+    if not np.all(np.isfinite(d)):
+        return math.inf
+    return float(np.max(d / s))
+
+
+def relative_error(a, b):
+    a, b = np.longdouble(a), np.longdouble(b)
+    if not (np.isfinite(a) and np.isfinite(b)):
+        return math.inf
+    return float(abs(a - b) / max(abs(b), np.longdouble(1e-300)))

@@ -1,0 +1,186 @@
+"""qln_solve's ITERATES against tests/ilqr_ref.py, the numpy restatement of the method run in float64 and in 80-bit
+longdouble (tests/test_ilqr_ref_host.py holds that restatement to evidence of its own).  tests/test_gpu_solve.py looks at the
+end of a solve only, and a line search turns a wrong term in the sweep into a few more iterations; here single iterations,
+chained first iterations and twelve-iteration runs are compared control by control.
+
+Measure    e(U, V) = max_j max_k |U[k, j] - V[k, j]| / s_j,  s_j = 1 + max_k |V[k, j]| for the forces, s_4 = h_max.
+Tolerance  per problem 100 x e(U_float64, U_longdouble), floored at 1e-13, against U_longdouble; info[6] (the augmented cost)
+           relatively by the same construction; outer, iters, rho, status, alpha, mu equal to the float64 run's exactly.
+           The margin of 100 stands for the kernel's other summation order, its fused multiply-adds and refined reciprocal:
+           an error of the kind and size of the float64 run's own.  A wrong term moves the controls by 1e-3 or more.
+The returned controls are the accepted trial's; the states are replaced by an RK4 roll-out and are not compared."""
+import dataclasses
+
+import numpy as np
+import pytest
+
+from tests import ilqr_cases as IC
+from tests import ilqr_ref as IR
+
+pytestmark = pytest.mark.gpu
+
+INFO = [0, 1, 4, 5, 6, 7, 9]  # outer, iters, rho, status, J, alpha, mu
+DISCRETE = [0, 1, 2, 3, 5, 6]  # positions of the discrete entries in INFO
+
+
+def _solve_gpu(batch, o, Zh=None):
+    """-> (controls (B, N-1, 5), info (B, 16), returned Z (B, n_nlp)) of HybridNLP.solve(..., rescue_outer=0)"""
+    import torch
+    from quadruped_landing_amd import HybridNLP
+
+    assert batch.B <= 8
+    nlp = HybridNLP(batch.model, batch.obj, batch.init_mode, batch.k_trans, batch.N, batch.x0, batch.xf)
+    Z, info = nlp.solve(nlp.upload_Z(batch.Z if Zh is None else Zh), **o.gpu_kwargs())
+    torch.cuda.synchronize()
+    Zo = Z.cpu().numpy().reshape(batch.B, -1)[:, : nlp.n_nlp].copy()
+    U = np.stack([IR.controls_of(Zo[b], batch.N) for b in range(batch.B)])
+    return U, info.cpu().numpy().copy(), Zo
+
+
+def _hold(label, batch, o, gpu, U0=None, model=None, multi=False, witness=None):
+    """Compare the GPU's result with the yardstick problem by problem; returns the worst ratio of the GPU's error to the
+    float64 run's own.  witness(iteration 0 of the longdouble run) -> bool: the case exercises what it is there for."""
+    Ug, info, _ = gpu
+    worst_e, worst_ratio, left_out, seen = 0.0, 0.0, 0, False
+    with IC.np_model(model):
+        P, Uguess = IC.problems(batch)
+        for b in range(batch.B):
+            u0 = Uguess[b] if U0 is None else U0[b]
+            r64, r80 = IC.reference_pair(P[b], u0, o)
+            if multi and IC.ambiguous(r64, r80):
+                left_out += 1
+                print(f"{label} b={b}: left out as ambiguous (smallest margin {r80.min_margin():.2e})")
+                continue
+            gi = info[b, INFO]
+            if not multi and r80.iterations:
+                # a step length as good as the best within the tolerance on J is the same decision
+                it = r80.iterations[0]
+                a_gpu = int(round(-np.log2(gi[5]))) if gi[5] > 0 else -1
+                if a_gpu != it.a_star:
+                    assert a_gpu >= 0 and it.a_star >= 0, (label, b, a_gpu, it.a_star)
+                    tol_j = IC.tolerances(r64, r80, o)[1]
+                    assert IR.relative_error(it.J_try[a_gpu], it.J_try[it.a_star]) <= tol_j, (label, b, a_gpu, it.a_star)
+                    r64, r80 = IC.reference_pair(P[b], u0, o, force_alpha={0: a_gpu})
+            if witness is not None and r80.iterations:
+                seen = seen or bool(witness(r80.iterations[0]))
+            tol_u, tol_j, eu, ej = IC.tolerances(r64, r80, o)
+            e = IR.control_error(Ug[b], r80.U, o.h_max)
+            ej_gpu = IR.relative_error(gi[4], r80.J)
+            ratio = e / (tol_u / IC.TOL_MARGIN)
+            print(f"{label} b={b}: e(U_gpu, U_ld) = {e:.2e}, float64 spread {eu:.2e}, ratio {ratio:.2f} (bound {IC.TOL_MARGIN:g}); J rel "
+                  f"{ej_gpu:.2e} (tolerance {tol_j:.1e}); outer/iters/rho/status/alpha/mu = {gi[DISCRETE].tolist()}")
+            worst_e, worst_ratio = max(worst_e, e), max(worst_ratio, ratio)
+            assert np.array_equal(gi[DISCRETE], r64.info()[DISCRETE]), (label, b, gi.tolist(), r64.info().tolist())
+            assert e <= tol_u, (label, b, e, tol_u)
+            assert ej_gpu <= tol_j, (label, b, ej_gpu, tol_j)
+    print(f"{label}: worst e = {worst_e:.2e}, worst ratio to the float64 spread = {worst_ratio:.2f}, left out {left_out} of {batch.B}")
+    assert left_out * 8 <= batch.B, f"{label}: {left_out} of {batch.B} problems ambiguous"
+    assert witness is None or seen, f"{label}: no problem of the batch exercises the term"
+    return worst_ratio
+
+
+# ---- a: one iteration ---------------------------------------------------------------------------------------------------
+SHAPES = ["N12-kt5", "N40-kt14", "N17-ragged", "N65", "N70-ragged", "N3", "N2", "kt-extremes"]
+
+
+@pytest.mark.parametrize("exact_h", [0, 1])
+@pytest.mark.parametrize("name", SHAPES)
+def test_one_iteration(name, exact_h):
+    batch = IC.shape(name)
+    o = dataclasses.replace(IC.ONE, exact_h_gradient=exact_h)
+    _hold(f"one iteration {name} exact_h={exact_h}", batch, o, _solve_gpu(batch, o))
+
+
+# ---- b: options that switch terms on ------------------------------------------------------------------------------------
+def _moved_by(batch, o, base=IC.ONE):
+    """the option changes the first iteration of the yardstick itself, in some problem of the batch"""
+    P, U0 = IC.problems(batch)
+    return max(IR.control_error(IR.solve(P[b], U0[b], o).U, IR.solve(P[b], U0[b], base).U, o.h_max) for b in range(batch.B))
+
+
+def test_option_theta_bound_active_from_the_drop_state():
+    batch = IC.shape("N12-kt5")  # drop states have theta in [-40, -10] degrees: below -0.3 rad for most
+    o = dataclasses.replace(IC.ONE, theta_min=-0.3)
+    _hold("theta_min=-0.3", batch, o, _solve_gpu(batch, o), witness=lambda it: it.active_rows[:, 3].any())
+
+
+def test_option_q6_bounds_off():
+    batch = IC.shape("N17-ragged")  # init_mode 2 starts with x1 = -lb: the Q6 row x1 >= 0 is active when it is on
+    P, U0 = IC.problems(batch)
+    assert any(IR.solve(P[b], U0[b], IC.ONE).iterations[0].active_rows[:, 4:].any() for b in range(batch.B))
+    o = dataclasses.replace(IC.ONE, q6_bounds=0)
+    assert _moved_by(batch, o) > 1e-3
+    _hold("q6_bounds=0", batch, o, _solve_gpu(batch, o), witness=lambda it: not it.active_rows[:, 4:].any())
+
+
+def test_option_h_box_clamps_from_both_sides():
+    batch = IC.shape("N17-ragged")  # h ~ U(0.001, 0.02) in the guess
+    o = dataclasses.replace(IC.ONE, h_min=0.006, h_max=0.014)
+    h = np.stack([IR.controls_of(batch.Z[b], batch.N)[:, 4] for b in range(batch.B)])
+    assert (h > o.h_max).any(axis=1).all() and (h < o.h_min).any(axis=1).all()  # the guess is clipped at both ends on load
+    _hold("h box [0.006, 0.014]", batch, o, _solve_gpu(batch, o), witness=lambda it: any(it.clamped))  # ... and the sweep takes a clamp
+
+
+def test_option_h_prox_zero():
+    batch = IC.shape("N12-kt5")
+    o = dataclasses.replace(IC.ONE, h_prox=0.0)
+    assert _moved_by(batch, o) > 1e-3
+    _hold("h_prox=0", batch, o, _solve_gpu(batch, o))
+
+
+def test_option_rho0_100():
+    batch = IC.shape("N17-ragged")
+    o = dataclasses.replace(IC.ONE, rho0=100.0)
+    assert _moved_by(batch, o) > 1e-3
+    _hold("rho0=100", batch, o, _solve_gpu(batch, o), witness=lambda it: it.active_rows.any())
+
+
+# ---- c: a weight on the clock ------------------------------------------------------------------------------------------
+def test_clock_weight_one_iteration():
+    """Q[14] = Qf[14] = 10 (tests/test_ilqr_ref_host.py::test_clock_weight_case_has_teeth shows this case sees the jump knot's
+    clock row): the sweep has to differentiate the step the roll-out takes, which keeps the clock through the jump."""
+    batch = IC.clock_case()
+    _hold("clock weight", batch, IC.ONE, _solve_gpu(batch, IC.ONE))
+
+
+# ---- d: twelve iterations -----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["N12-kt5", "N17-ragged"])
+def test_twelve_iterations(name):
+    """max_outer = 4, max_inner = 3: the multiplier update, the penalty and mu schedules and the counts"""
+    batch = IC.shape(name)
+    _hold(f"twelve iterations {name}", batch, IC.TWELVE, _solve_gpu(batch, IC.TWELVE), multi=True)
+
+
+# ---- e: the second robot model ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,o", [("N12-kt5", IC.ONE), ("N17-ragged", IC.ONE), ("N12-kt5", IC.TWELVE)],
+                         ids=["one-N12-kt5", "one-N17-ragged", "twelve-N12-kt5"])
+def test_second_model(name, o):
+    """1 / mb, 1 / mf, 1 / Ib of the closed-form trial step cannot be told apart under the default model"""
+    batch = IC.shape(name, IC.SECOND_MODEL)
+    _hold(f"second model {name} x{o.max_outer * o.max_inner}", batch, o, _solve_gpu(batch, o), model=IC.SECOND_MODEL, multi=o is IC.TWELVE)
+
+
+# ---- f: chained first iterations ----------------------------------------------------------------------------------------
+def test_chained_first_iterations():
+    """The result of one iteration fed back three times (every call starts at lam = 0, rho0): the sweep at trajectories away
+    from the guess; the yardstick starts each link from the GPU's own previous controls, so nothing accumulates."""
+    batch = IC.shape("N12-kt5")
+    Zh, U0 = batch.Z, None
+    for link in range(4):
+        gpu = _solve_gpu(batch, IC.ONE, Zh)
+        _hold(f"chained link {link}", batch, IC.ONE, gpu, U0=U0)
+        U0, Zh = gpu[0], gpu[2]
+
+
+# ---- g: one NaN control -------------------------------------------------------------------------------------------------
+def test_one_nan_control_stays_in_its_problem():
+    batch = IC.shape("N12-kt5")
+    o = dataclasses.replace(IC.TWELVE, max_outer=2)
+    _, info, Z = _solve_gpu(batch, o)
+    Zn = batch.Z.copy()
+    Zn[3, 20 * 4 + 16] = np.nan
+    _, info_n, Z_n = _solve_gpu(batch, o, Zn)
+    others = [b for b in range(batch.B) if b != 3]
+    assert np.array_equal(Z_n[others], Z[others])
+    assert np.array_equal(info_n[others, :10], info[others, :10])
+    assert np.isnan(Z_n[3]).any()
