@@ -28,7 +28,8 @@
  * qln_eval_hessian_lagrangian_host and qln_solve_host are always staged.  The handle allocates each buffer on first
  * use, zero-filled, and keeps it until qln_destroy.  Four arguments are in-out and copied in whole, so that their
  * entries from n_nlp to z_stride come back as the caller's buffer held them: Zout of qln_tracking_rollout_host,
- * Zref_bar of qln_tracking_rollout_vjp_host, Zout_dot of qln_tracking_rollout_jvp_host and Z of qln_solve_host.  The
+ * Zref_bar of qln_tracking_rollout_vjp_host, Zout_dot of qln_tracking_rollout_jvp_host (each also in its _model_ form,
+ * qln_tracking_rollout_model_host and its two sweeps) and Z of qln_solve_host.  The
  * padding of every other result (past n_nlp in the layout of Z, between the problems of c, vals and hvals) comes back as
  * zeros.
  *
@@ -515,6 +516,44 @@ int qln_tracking_rollout_jvp(qln_handle* h, const double* Zref, const double* K,
 /* the same as a host form (see "Host forms" above; Zout_dot is in-out) */
 int qln_tracking_rollout_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                   const double* Zref_dot, const double* K_dot, const double* x0_dot, double* Zout_dot);
+/* The closed-loop roll-out with a per-problem PLANT model, and its two sweeps.  The gains, the references and the mode
+ * schedule are the handle's; what differs per problem is the model the dynamics read while rolling out:
+ *   theta_b = model[b] = (g, mb, mf, lb), in this order (QLN_MODEL_NP doubles); Ib = mb * (lb * lb) / 12 per problem, formed as
+ *   for the handle's model.  l1 and l2 enter only the kinematic rows and are not part of it.
+ *   x_{k+1} = Phi_k(x_k, u_k; theta_b),  u_k = (F_ref,k - K_k (x_k - x_ref,k), h_ref,k)     (knots 0-based, k = 0..N-2)
+ * Everything else -- layouts, NULL conventions of K and x0, overlap rules, what is written -- is qln_tracking_rollout's and
+ * its sweeps', which these calls reduce to: with model == NULL (the handle's model for every problem), or with model[b]
+ * equal to the handle's four values, qln_tracking_rollout_model's Zout is bit for bit qln_tracking_rollout's.
+ * qln_tracking_lqr and qln_tracking_covariance keep the handle's model: the design model does not follow the plant.
+ *   model: device, [B][QLN_MODEL_NP], or NULL.  The device forms do not validate it; a NaN in model[b] stays in problem b's
+ *          outputs.  The host forms refuse a non-finite entry and mb, mf or lb <= 0 with QLN_ERR_INVALID_ARGUMENT.
+ * Forward sweep (qln_tracking_rollout_model_jvp): qln_tracking_rollout_jvp's recursion with the model's tangent,
+ *   dx_{k+1} = A_k dx_k + B_k (dF_k, dh_k) + G_k model_dot[b],   G_k = d Phi_k / d theta (15 x 4) at Zout's (x_k, u_k) and theta_b;
+ *   A_k and B_k are formed at theta_b too, and dF_k is unchanged (the gains do not depend on the plant).  Rows 4, 6 and
+ *   10-13 of G_k are zero at the jump knot, as A_k's; row 14 (the clock) always.  All four tangents NULL is
+ *   QLN_ERR_INVALID_ARGUMENT; a NULL tangent equals a zero tensor in every value.  model_dot: device [B][QLN_MODEL_NP] or NULL.
+ * Reverse sweep (qln_tracking_rollout_model_vjp): qln_tracking_rollout_vjp's recursion at theta_b, and
+ *   model_bar[b] = sum_k G_k' lam_{k+1}       ([B][QLN_MODEL_NP] or NULL: not written; overwritten, not accumulated)
+ *   It is the exact adjoint of the forward sweep:
+ *   <Zbar, Zout_dot> = <Zref_bar, Zref_dot> + <K_bar, K_dot> + <x0_bar, x0_dot> + <model_bar, model_dot>.
+ * Device pointers, stream-ordered; needs no cost table. */
+#define QLN_MODEL_NP 4 /* g, mb, mf, lb: what the dynamics read */
+int qln_tracking_rollout_model(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
+                               double* Zout);
+int qln_tracking_rollout_model_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
+                                   const double* Zref_dot, const double* K_dot, const double* x0_dot, const double* model_dot,
+                                   double* Zout_dot);
+int qln_tracking_rollout_model_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
+                                   const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar);
+/* the same as host forms (see "Host forms" above; Zout, Zout_dot and Zref_bar are in-out as in the forms without a model) */
+int qln_tracking_rollout_model_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
+                                    double* Zout);
+int qln_tracking_rollout_model_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                        const double* model, const double* Zref_dot, const double* K_dot, const double* x0_dot,
+                                        const double* model_dot, double* Zout_dot);
+int qln_tracking_rollout_model_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                        const double* model, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
+                                        double* model_bar);
 /* Covariance propagation through the closed-loop roll-out: the linear-Gaussian forward sweep along the trajectory Zout
  * holds.  Knots are 0-based, k = 0..N-2, as in qln_tracking_rollout_vjp.
  *   A_k (15x15), B_k (15x4) = d Phi_k / d(x_k, F_k) at Zout's (x_k, u_k): exactly the blocks qln_tracking_rollout_vjp uses --

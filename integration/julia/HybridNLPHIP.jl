@@ -226,6 +226,42 @@ function tracking_rollout_jvp(prob::HybridNLPHIP, Zref::Vector{Float64}, Zout::V
                     K_dot === nothing ? C_NULL : K_dot, x0_dot === nothing ? C_NULL : x0_dot, Zout_dot))
     return Zout_dot
 end
+# The roll-out and its two sweeps with a PLANT model of the problem's own (include/qln_evaluator.h, DESIGN.md 4.16): model is
+# (g, mb, mf, lb), four values, or nothing (the handle's model); the gains and the reference stay what they are.
+# tracking_rollout_model_jvp takes a fourth tangent model_dot (four values), tracking_rollout_model_vjp returns a fourth
+# cotangent model_bar (four values).
+function tracking_rollout_model(prob::HybridNLPHIP, Zref::Vector{Float64}; K=nothing, x0=nothing, model=nothing)
+    Zout = zeros(length(Zref))
+    qln_check(ccall((:qln_tracking_rollout_model_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, K === nothing ? C_NULL : K, x0 === nothing ? C_NULL : x0,
+                    model === nothing ? C_NULL : model, Zout))
+    return Zout
+end
+function tracking_rollout_model_jvp(prob::HybridNLPHIP, Zref::Vector{Float64}, Zout::Vector{Float64}; K=nothing, model=nothing,
+                                    Zref_dot=nothing, K_dot=nothing, x0_dot=nothing, model_dot=nothing)
+    Zout_dot = zeros(length(Zref))
+    qln_check(ccall((:qln_tracking_rollout_model_jvp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, K === nothing ? C_NULL : K, Zout, model === nothing ? C_NULL : model,
+                    Zref_dot === nothing ? C_NULL : Zref_dot, K_dot === nothing ? C_NULL : K_dot,
+                    x0_dot === nothing ? C_NULL : x0_dot, model_dot === nothing ? C_NULL : model_dot, Zout_dot))
+    return Zout_dot
+end
+function tracking_rollout_model_vjp(prob::HybridNLPHIP, Zref::Vector{Float64}, Zout::Vector{Float64}, Zbar::Vector{Float64};
+                                    K=nothing, model=nothing)
+    Zref_bar = zeros(length(Zref))
+    K_bar = K === nothing ? nothing : zeros(size(K))
+    x0_bar = zeros(15)
+    model_bar = zeros(4)
+    qln_check(ccall((:qln_tracking_rollout_model_vjp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, K === nothing ? C_NULL : K, Zout, model === nothing ? C_NULL : model, Zbar, Zref_bar,
+                    K_bar === nothing ? C_NULL : K_bar, x0_bar, model_bar))
+    return Zref_bar, K_bar, x0_bar, model_bar
+end
 # covariance of the roll-out's states along the trajectory Zout (for the nominal case: the reference itself):
 # Sigma_0 = Sigma0, Sigma_{k+1} = (A_k - B_k K_k) Sigma_k (A_k - B_k K_k)' + diag(W); K = nothing is the open loop.
 # Sigma0: a 15x15 matrix (its lower triangle is read); W: 15 variances or nothing (zeros).  Returns Sigma as (120, N) packed

@@ -26,6 +26,7 @@ GN_INFO_STRIDE = 8
 HESS_STEP_NNZ, HESS_TERM_NNZ = 55, 15
 TRACK_NU, TRACK_P_NNZ = 4, 120
 TRACK_MARG_STRIDE = 8
+MODEL_NP = 4  # g, mb, mf, lb: a per-problem plant model of the tracking roll-out
 
 
 class QlnModel(C.Structure):
@@ -153,6 +154,12 @@ SIGNATURES = {
     "qln_tracking_rollout_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "qln_tracking_rollout_jvp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "qln_tracking_rollout_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "qln_tracking_rollout_model": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp]),
+    "qln_tracking_rollout_model_jvp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "qln_tracking_rollout_model_vjp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "qln_tracking_rollout_model_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp]),
+    "qln_tracking_rollout_model_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "qln_tracking_rollout_model_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "qln_tracking_covariance": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp]),
     "qln_tracking_covariance_host": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp]),
     "qln_eval_constraint_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp]),

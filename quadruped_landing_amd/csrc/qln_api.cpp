@@ -98,6 +98,8 @@ enum HostRole {
     kCov,    // out: the covariances                                        layout of P
     kMarg,   // out: the marginals                                          [B][N][8]
     kMultInfo,  // out: the multiplier estimate's report                    [B][16]
+    kModel,  // in: the per-problem plant models                            [B][4]
+    kModelD, // in: the model jvp's model_dot; out: the model vjp's model_bar  [B][4]
     kHostRoles
 };
 
@@ -172,6 +174,7 @@ int64_t host_role_size(const qln_handle* h, HostRole r) {
         case kMarg: return tracking_marg_total(D);
         case kX0: return (int64_t)D.B * QLN_NX;
         case kMultInfo: return (int64_t)D.B * QLN_MULT_INFO_STRIDE;
+        case kModel: case kModelD: return (int64_t)D.B * QLN_MODEL_NP;
         case kHostRoles: break;
     }
     return 0;
@@ -1240,6 +1243,140 @@ int qln_tracking_rollout_jvp_host(qln_handle* h, const double* Zref, const doubl
                      [&](double* const* d, bool) {
                          return qln::launch_tracking_rollout_jvp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kZdot], d[kKdot],
                                                                  d[kX0], d[kZio], h->stream);
+                     });
+}
+
+// the roll-out and its sweeps with a per-problem plant (the same kernels, instantiated with kModel).  The argument checks are
+// those of the forms without a model, with model as one more input, model_dot as a fourth tangent and model_bar as a
+// fourth output.  The checks that need no handle come first, as above.
+static int check_tracking_model_jvp_args(const qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                         const double* model, const double* Zref_dot, const double* K_dot, const double* x0_dot,
+                                         const double* model_dot, const double* Zout_dot, const char* who) {
+    const std::string w(who);
+    if (!Zref_dot && !K_dot && !x0_dot && !model_dot)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Zref_dot, K_dot, x0_dot and model_dot are all NULL (no direction)");
+    if (K_dot && !K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_dot needs K (K == NULL has no gains to perturb)");
+    if (!Zref || !Zout || !Zout_dot) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref, Zout or Zout_dot");
+    if (int rc = check_handle(h)) return rc;
+    const qln_dims& D = h->dims;
+    const int64_t nz = D.z_total, nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX, nm = (int64_t)D.B * QLN_MODEL_NP;
+    const struct {
+        const double* p;
+        int64_t n;
+    } in[] = {{Zref, nz}, {K, nk}, {Zout, nz}, {model, nm}, {Zref_dot, nz}, {K_dot, nk}, {x0_dot, nx}, {model_dot, nm}};
+    for (const auto& i : in)
+        if (overlaps(Zout_dot, nz, i.p, i.n)) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Zout_dot overlaps an input");
+    return QLN_OK;
+}
+
+static int check_tracking_model_vjp_args(const qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                         const double* model, const double* Zbar, const double* Zref_bar, const double* K_bar,
+                                         const double* x0_bar, const double* model_bar, const char* who) {
+    if (int rc = check_tracking_vjp_args(h, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar, who)) return rc;
+    const qln_dims& D = h->dims;
+    const int64_t nz = D.z_total, nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX, nm = (int64_t)D.B * QLN_MODEL_NP;
+    const struct {
+        const double* p;
+        int64_t n;
+    } other[] = {{Zref, nz}, {K, nk}, {Zout, nz}, {Zbar, nz}, {model, nm}, {Zref_bar, nz}, {K_bar, nk}, {x0_bar, nx}},
+      out[] = {{Zref_bar, nz}, {K_bar, nk}, {x0_bar, nx}};
+    for (const auto& o : other)
+        if (overlaps(model_bar, nm, o.p, o.n))
+            return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": model_bar overlaps an input or another output");
+    for (const auto& o : out)
+        if (overlaps(o.p, o.n, model, nm)) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": an output overlaps model");
+    return QLN_OK;
+}
+
+// host forms only: every entry finite, and mb, mf, lb > 0 (the device forms do not look at the values)
+static int check_host_models(const qln_handle* h, const double* model, const char* who) {
+    if (!model) return QLN_OK;
+    for (int64_t b = 0; b < h->dims.B; ++b) {
+        const double* th = model + b * QLN_MODEL_NP;
+        for (int p = 0; p < QLN_MODEL_NP; ++p)
+            if (!std::isfinite(th[p]) || (p > 0 && !(th[p] > 0.0)))
+                return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": model[" + std::to_string(b) + "][" + std::to_string(p) +
+                                                          "] is not finite, or a mass or the body length is not positive");
+    }
+    return QLN_OK;
+}
+
+int qln_tracking_rollout_model(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
+                               double* Zout) {
+    if (int rc = check_tracking_rollout_args(h, Zref, Zout, "qln_tracking_rollout_model")) return rc;
+    if (int rc = bind_device(h)) return rc;
+    QLN_HIP(qln::launch_tracking_rollout_model(h->p, Zref, K, x0, model, Zout, h->stream));
+    return QLN_OK;
+}
+
+int qln_tracking_rollout_model_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
+                                    double* Zout) {
+    if (int rc = check_tracking_rollout_args(h, Zref, Zout, "qln_tracking_rollout_model_host")) return rc;
+    if (int rc = check_host_models(h, model, "qln_tracking_rollout_model_host")) return rc;
+    if (int rc = bind_device(h)) return rc;
+    return host_call(h, {copy_in(kZ, Zref), copy_inout(kZio, Zout), copy_in(kK, K), copy_in(kX0, x0), copy_in(kModel, model)},
+                     [&](double* const* d, bool) {
+                         return qln::launch_tracking_rollout_model(h->p, d[kZ], d[kK], d[kX0], d[kModel], d[kZio], h->stream);
+                     });
+}
+
+int qln_tracking_rollout_model_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
+                                   const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar) {
+    if (int rc = check_tracking_model_vjp_args(h, Zref, K, Zout, model, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
+                                               "qln_tracking_rollout_model_vjp"))
+        return rc;
+    if (int rc = bind_device(h)) return rc;
+    QLN_HIP(qln::launch_tracking_rollout_model_vjp(h->p, Zref, K, Zout, model, Zbar, Zref_bar, K_bar, x0_bar, model_bar, h->stream));
+    return QLN_OK;
+}
+
+int qln_tracking_rollout_model_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                        const double* model, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
+                                        double* model_bar) {
+    if (int rc = check_tracking_model_vjp_args(h, Zref, K, Zout, model, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
+                                               "qln_tracking_rollout_model_vjp_host"))
+        return rc;
+    if (int rc = check_host_models(h, model, "qln_tracking_rollout_model_vjp_host")) return rc;
+    if (int rc = bind_device(h)) return rc;
+    return host_call(h,
+                     {copy_in(kV, Zout), copy_in(kZbar, Zbar), copy_in(kZ, K_bar ? Zref : nullptr), copy_in(kK, K),
+                      copy_in(kModel, model), copy_inout(kZio, Zref_bar), copy_out(kKbar, K_bar), copy_out(kX0, x0_bar),
+                      copy_out(kModelD, model_bar)},
+                     [&](double* const* d, bool) {
+                         return qln::launch_tracking_rollout_model_vjp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kModel],
+                                                                       d[kZbar], d[kZio], d[kKbar], d[kX0], d[kModelD],
+                                                                       h->stream);
+                     });
+}
+
+int qln_tracking_rollout_model_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
+                                   const double* Zref_dot, const double* K_dot, const double* x0_dot, const double* model_dot,
+                                   double* Zout_dot) {
+    if (int rc = check_tracking_model_jvp_args(h, Zref, K, Zout, model, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
+                                               "qln_tracking_rollout_model_jvp"))
+        return rc;
+    if (int rc = bind_device(h)) return rc;
+    QLN_HIP(qln::launch_tracking_rollout_model_jvp(h->p, Zref, K, Zout, model, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
+                                                   h->stream));
+    return QLN_OK;
+}
+
+int qln_tracking_rollout_model_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                        const double* model, const double* Zref_dot, const double* K_dot, const double* x0_dot,
+                                        const double* model_dot, double* Zout_dot) {
+    if (int rc = check_tracking_model_jvp_args(h, Zref, K, Zout, model, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
+                                               "qln_tracking_rollout_model_jvp_host"))
+        return rc;
+    if (int rc = check_host_models(h, model, "qln_tracking_rollout_model_jvp_host")) return rc;
+    if (int rc = bind_device(h)) return rc;
+    return host_call(h,
+                     {copy_in(kV, Zout), copy_in(kZ, K_dot ? Zref : nullptr), copy_in(kK, K), copy_in(kModel, model),
+                      copy_in(kZdot, Zref_dot), copy_in(kKdot, K_dot), copy_in(kX0, x0_dot), copy_in(kModelD, model_dot),
+                      copy_inout(kZio, Zout_dot)},
+                     [&](double* const* d, bool) {
+                         return qln::launch_tracking_rollout_model_jvp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kModel],
+                                                                       d[kZdot], d[kKdot], d[kX0], d[kModelD], d[kZio],
+                                                                       h->stream);
                      });
 }
 

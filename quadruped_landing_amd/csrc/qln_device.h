@@ -40,6 +40,9 @@ struct Model {
     double Ib;  // mb * lb^2 / 12, src/planar_quadruped.jl:41
     __host__ __device__ __forceinline__ explicit Model(const BatchParams& P)
         : g(P.g), mb(P.mb), mf(P.mf), lb(P.lb), Ib(mb * (lb * lb) / 12) {}
+    // one problem's own model: th = (g, mb, mf, lb), QLN_MODEL_NP doubles (the plant of qln_tracking_rollout_model)
+    __host__ __device__ __forceinline__ explicit Model(const double* th)
+        : g(th[0]), mb(th[1]), mf(th[2]), lb(th[3]), Ib(mb * (lb * lb) / 12) {}
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -305,6 +308,18 @@ hipError_t launch_tracking_rollout_vjp(const BatchParams& p, const double* Zref,
 hipError_t launch_tracking_rollout_jvp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
                                        const double* Zref_dot, const double* K_dot, const double* x0_dot, double* Zout_dot,
                                        hipStream_t stream);
+// the roll-out and its two sweeps with a per-problem plant: model [B][QLN_MODEL_NP] = (g, mb, mf, lb) per problem (null: the
+// handle's), the model's tangent model_dot and cotangent model_bar in the same layout (each may be null)
+// (qln_tracking_kernels.hip, the same kernels instantiated with kModel)
+hipError_t launch_tracking_rollout_model(const BatchParams& p, const double* Zref, const double* K, const double* x0,
+                                         const double* model, double* Zout, hipStream_t stream);
+hipError_t launch_tracking_rollout_model_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
+                                             const double* model, const double* Zbar, double* Zref_bar, double* K_bar,
+                                             double* x0_bar, double* model_bar, hipStream_t stream);
+hipError_t launch_tracking_rollout_model_jvp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
+                                             const double* model, const double* Zref_dot, const double* K_dot,
+                                             const double* x0_dot, const double* model_dot, double* Zout_dot,
+                                             hipStream_t stream);
 // Sigma_{k+1} = (A_k - B_k K_k) Sigma_k (A_k - B_k K_k)' + diag(Wd) along Zout (K null: open loop); Sigma0 [sigma0_batch][120],
 // Wd a host array (null: zeros); Sigma [B][N][120] and marg [B][N][8], either may be null (qln_tracking_kernels.hip)
 hipError_t launch_tracking_covariance(const BatchParams& p, const double* Zout, const double* K, const double* Sigma0,

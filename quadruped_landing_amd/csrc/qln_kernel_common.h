@@ -9,7 +9,10 @@
 //     (qln_tracking_kernels.hip) share: StepBlock + step_block() form a knot's base quantities from explicit arguments
 //     (states, forces, h, KnotMode, Model), for_each_step_entry() visits the 85 entries of the union pattern with row and
 //     col as compile-time constants, for_each_rollout_entry() the same with the roll-out's clock row.  A static_assert
-//     holds the visit order to step_union_pos().
+//     holds the visit order to step_union_pos();
+//   * the 15 x 4 derivative of a roll-out's knot with respect to the model (g, mb, mf, lb), in closed form from the same
+//     base quantities: ModelBlock + model_block() and for_each_model_entry() over its 24 entries (the roll-out's tangent
+//     and reverse sweeps with a per-problem plant, qln_tracking_kernels.hip).
 // The functions here are compiled under the floating-point contraction mode in force where this header is INCLUDED.
 // qln_solver_kernels.hip sets contract(fast) above the include so that its step blocks fuse; the same then holds for
 // EVERYTHING in this header in that file: a value-path helper (rk4_step, step_forward) called from there would fuse too
@@ -300,6 +303,125 @@ constexpr bool step_entries_in_union_order() {
     return ok && n == kStepUnion;
 }
 static_assert(step_entries_in_union_order(), "the entries are visited at positions 0 .. 84 of step_union_pos, each once");
+
+// ---------------------------------------------------------------------------------------------
+// G = d x+ / d theta, theta = (g, mb, mf, lb) (QLN_MODEL_NP): the 15 x 4 derivative of a roll-out's knot -- RK4 step and jump
+// map -- with respect to the model its dynamics read, in closed form from the base quantities of step_block() above.  The
+// step is polynomial in h: body and feet move under the constant accelerations ab = sF / mb + g e_y and a_i = m_i (-F_i / mf
+// + g e_y), and only theta and omega see the state, through tau / Ib with tau(t) = tau0 + t tauv + t^2/2 taua:
+//   theta+ = theta + h omega + dth,  dth = At tau0 + Bt tauv + Ct taua,     omega+ = omega + dom,  dom = Aw tau0 + At tauv + Bt taua.
+// Which entries can be non-zero, from that derivation (24 of the 60):
+//   column g:  the y rows -- 1, 8 (body), 4, 11 and 6, 13 (a free foot; zero at the jump) -- and rows 2, 9 through taua = g dga;
+//   column mb: rows 0, 1, 7, 8 through ab, and rows 2, 9 through Ib alone (d (1/Ib) / d mb = -1 / (Ib mb));
+//   column mf: the rows of a free foot, 3 .. 6 and 10 .. 13 (4, 6, 10 .. 13 zero at the jump);
+//   column lb: rows 2, 9 through Ib alone (d (1/Ib) / d lb = -2 / (Ib lb)).
+// mf does not reach theta / omega, and mb reaches them through Ib only: the accelerations enter tau as
+// sum_i (a_i - ab) x F_i, where F_i x F_i / mf and sF x sF / mb vanish identically.  A numerical derivative of the RK4 stages
+// leaves rounding (~1e-17) in those four places; the pattern here is the algebraic one.  Row 14, the clock, reads no model.
+// ---------------------------------------------------------------------------------------------
+struct ModelBlock {
+    double h, h2h;                              // h and h^2/2: column g of the body's y rows
+    double k1, k2;                              // keep * m1, keep * m2: the y rows and velocities of a free foot
+    double g2, g9;                              // column g of theta, omega: Ct dga, Bt dga
+    double b0, b1, b7, b8;                      // column mb of the body rows
+    double dth, dom, nimb, nilb2;               // rows 2, 9 of columns mb and lb: dth, dom times -1/mb and -2/lb
+    double f3, f4, f5, f6, f10, f11, f12, f13;  // column mf
+};
+
+// the arguments of step_block(): the block is G at the same knot
+__device__ __forceinline__ ModelBlock model_block(const double (&x)[14], double F1x, double F1y, double F2x, double F2y, double h,
+                                                  KnotMode md, const Model& M) {
+    const double g = M.g, mb = M.mb, mf = M.mf, Ib = M.Ib;
+    const double m1 = md.f1free ? 1.0 : 0.0, m2 = md.f2free ? 1.0 : 0.0;
+    const double keep = md.jump ? 0.0 : 1.0;
+    const double km1 = keep * m1, km2 = keep * m2;
+    const double h2 = h * h, h3 = h2 * h, h4 = h2 * h2;
+    const double iIb = 1.0 / Ib;
+    const double Aw = h * iIb;
+    const double At = 0.5 * h2 * iIb;
+    const double Bt = h3 * iIb * (1.0 / 6.0);
+    const double Ct = h4 * iIb * (1.0 / 24.0);
+    const double sFx = F1x + F2x, sFy = F1y + F2y;
+    const double r1x = x[3] - x[0], r1y = x[4] - x[1], r2x = x[5] - x[0], r2y = x[6] - x[1];
+    const double w1x = m1 * x[10] - x[7], w1y = m1 * x[11] - x[8];
+    const double w2x = m2 * x[12] - x[7], w2y = m2 * x[13] - x[8];
+    const double tau0 = r1x * F1y - r1y * F1x + r2x * F2y - r2y * F2x;
+    const double tauv = w1x * F1y - w1y * F1x + w2x * F2y - w2y * F2x;
+    const double dga = (1.0 - m1) * F1x + (1.0 - m2) * F2x;  // d taua / d g
+    const double taua = g * dga;
+    const double h2h = 0.5 * h2;
+    const double imb = 1.0 / mb, imb2 = imb * imb, imf2 = 1.0 / (mf * mf);
+    const double ph = h2h * imf2, vh = h * imf2;  // d (h^2/2 a_i) / d mf and d (h a_i) / d mf per unit of F_i
+    ModelBlock b;
+    b.h = h, b.h2h = h2h;
+    b.k1 = km1, b.k2 = km2;
+    b.g2 = Ct * dga, b.g9 = Bt * dga;
+    b.b0 = -(h2h * imb2) * sFx, b.b1 = -(h2h * imb2) * sFy, b.b7 = -(h * imb2) * sFx, b.b8 = -(h * imb2) * sFy;
+    b.dth = At * tau0 + Bt * tauv + Ct * taua;
+    b.dom = Aw * tau0 + At * tauv + Bt * taua;
+    b.nimb = -imb, b.nilb2 = -2.0 / M.lb;
+    b.f3 = m1 * ph * F1x, b.f4 = km1 * ph * F1y, b.f5 = m2 * ph * F2x, b.f6 = km2 * ph * F2y;
+    b.f10 = km1 * vh * F1x, b.f11 = km1 * vh * F1y, b.f12 = km2 * vh * F2x, b.f13 = km2 * vh * F2y;
+    return b;
+}
+
+// The one list of G's 24 entries, E(row, param, value) over a ModelBlock b, column-major like the step block's.
+#define QLN_MODEL_ENTRY_LIST(E)                                                                                    \
+    /* g */                                                                                                        \
+    E(1, 0, b.h2h) E(2, 0, b.g2) E(4, 0, b.k1 * b.h2h) E(6, 0, b.k2 * b.h2h)                                       \
+    E(8, 0, b.h) E(9, 0, b.g9) E(11, 0, b.k1 * b.h) E(13, 0, b.k2 * b.h)                                           \
+    /* mb */                                                                                                       \
+    E(0, 1, b.b0) E(1, 1, b.b1) E(2, 1, b.dth * b.nimb) E(7, 1, b.b7) E(8, 1, b.b8) E(9, 1, b.dom * b.nimb)        \
+    /* mf */                                                                                                       \
+    E(3, 2, b.f3) E(4, 2, b.f4) E(5, 2, b.f5) E(6, 2, b.f6) E(10, 2, b.f10) E(11, 2, b.f11) E(12, 2, b.f12)        \
+    E(13, 2, b.f13)                                                                                                \
+    /* lb */                                                                                                       \
+    E(2, 3, b.dth * b.nilb2) E(9, 3, b.dom * b.nilb2)
+
+constexpr int kModelNnz = 24;
+// f(row, param, value) for the 24 entries of b, row and param as compile-time constants
+template <typename F>
+__device__ __forceinline__ void for_each_model_entry(const ModelBlock& b, F&& f) {
+#define QLN_E(row, col, val) [[clang::always_inline]] f(Idx<row>{}, Idx<col>{}, (val));
+    QLN_MODEL_ENTRY_LIST(QLN_E)
+#undef QLN_E
+}
+// f(row, param) for the same entries in the same order
+template <typename F>
+__host__ __device__ __forceinline__ constexpr void for_each_model_entry(F&& f) {
+#define QLN_E(row, col, val) [[clang::always_inline]] f(Idx<row>{}, Idx<col>{});
+    QLN_MODEL_ENTRY_LIST(QLN_E)
+#undef QLN_E
+}
+#undef QLN_MODEL_ENTRY_LIST
+
+// The pattern the derivation gives, stated a second time as a rule, and the list held to it: every entry once, in
+// column-major order, none in the clock's row.
+__host__ __device__ constexpr bool model_entry_present(int row, int p) {
+    const bool tw = row == 2 || row == 9;
+    switch (p) {
+        case 0: return tw || row == 1 || row == 8 || row == 4 || row == 11 || row == 6 || row == 13;
+        case 1: return tw || row == 0 || row == 1 || row == 7 || row == 8;
+        case 2: return (row >= 3 && row <= 6) || (row >= 10 && row <= 13);
+        case 3: return tw;
+        default: return false;
+    }
+}
+constexpr bool model_entries_in_order() {
+    int n = 0, last = -1;
+    bool ok = true;
+    for_each_model_entry([&](auto row, auto p) {
+        const int at = 15 * p + row;
+        ok = ok && model_entry_present(row, p) && at > last && p < QLN_MODEL_NP;
+        last = at;
+        ++n;
+    });
+    int present = 0;
+    for (int p = 0; p < QLN_MODEL_NP; ++p)
+        for (int r = 0; r < 15; ++r) present += model_entry_present(r, p) ? 1 : 0;
+    return ok && n == kModelNnz && present == kModelNnz;
+}
+static_assert(model_entries_in_order(), "G's 24 entries, each once, in column-major order");
 
 }  // namespace
 }  // namespace qln

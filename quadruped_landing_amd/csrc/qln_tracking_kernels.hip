@@ -50,6 +50,10 @@
 // nothing goes through LDS.  Every lane forms the knot's StepBlock (Zout's knot: two coalesced loads, handed round by DPP
 // row broadcasts) and picks its row's entries from the visitor; (A dx)[j] is the diagonal, the coupling A(j, j+7) through a
 // row shift, and for the dense rows 2 and 9 two row sums; K (dx - xref_dot) + Kdot e is four more.
+//
+// The roll-out and its two sweeps also exist with a per-problem plant (qln_tracking_rollout_model and its _jvp / _vjp, DESIGN.md
+// 4.16): the same three kernels with the flag kModel, which read the problem's (g, mb, mf, lb) instead of the handle's and add
+// the term of G_k = d Phi_k / d model (ModelBlock / for_each_model_entry of qln_kernel_common.h) in the mapping they have.
 #include "qln_row16.h"
 
 #include <utility>
@@ -73,6 +77,21 @@ __host__ __device__ constexpr unsigned b_rows_mask(int m) {
     for (int r = 0; r < 15; ++r)
         if (step_union_present(r, 15 + m)) s |= 1u << r;
     return s;
+}
+
+// The model a problem's roll-out and sweeps compute with: the handle's, or (kModel, model given) the problem's own four
+// doubles, Ib formed as Model's constructor forms it.  Chosen scalar by scalar and constructed once: a Model selected between
+// two whole structs was laid out in scratch memory (profiles/rollout_model_resource_usage.txt).
+template <bool kModel>
+__device__ __forceinline__ Model plant_model(const BatchParams& P, const double* __restrict__ model, int b) {
+    double th[QLN_MODEL_NP] = {P.g, P.mb, P.mf, P.lb};
+    if constexpr (kModel) {
+        if (model) {
+#pragma unroll
+            for (int p = 0; p < QLN_MODEL_NP; ++p) th[p] = model[(int64_t)QLN_MODEL_NP * b + p];
+        }
+    }
+    return Model(th);
 }
 
 struct TrackWeights {
@@ -265,14 +284,17 @@ __global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeig
 }
 
 // x_1 = x0[b] (or the handle's x0), F_k = F_ref,k - K_k (x_k - x_ref,k), h_k = h_ref,k, x_{k+1} = step_forward.
+// kModel: the plant of problem b is model[b] = (g, mb, mf, lb) instead of the handle's model (qln_tracking_rollout_model);
+// the same step_forward on it, so equal models give equal bits.
+template <bool kModel>
 __global__ __launch_bounds__(kWave) void k_tracking_rollout(BatchParams P, const double* __restrict__ Zref,
                                                             const double* __restrict__ Kg, const double* __restrict__ x0,
-                                                            double* __restrict__ Zout) {
+                                                            double* __restrict__ Zout, const double* __restrict__ model) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= P.B) return;
     const ProblemDesc pd = P.desc[b];
     const int N = P.N, kt = pd.k_trans, im = pd.init_mode;
-    const Model M(P);
+    const Model M = plant_model<kModel>(P, model, b);
     const double* __restrict__ Zr = Zref + (int64_t)b * P.z_stride;
     double* __restrict__ Zo = Zout + (int64_t)b * P.z_stride;
     const double* __restrict__ xs = x0 ? x0 + (int64_t)b * 15 : P.bnd + (int64_t)b * 30;
@@ -309,6 +331,12 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout(BatchParams P, const
     }
 }
 
+// lanes 0 .. n-1 of a row, in every lane of it
+template <int... I>
+__device__ __forceinline__ void row_bcast_first(double v, double (&out)[sizeof...(I)], std::integer_sequence<int, I...>) {
+    ((out[I] = row_bcast<I>(v)), ...);
+}
+
 // One knot's inputs, as lane j of a row reads them: its own x_j, Zbar x_j, x_ref,j and K column j, and the knot's applied
 // controls and their cotangents (the same five values in every lane of the row).
 struct VjpKnot {
@@ -337,16 +365,23 @@ __device__ __forceinline__ void vjp_load(VjpKnot& s, const double* __restrict__ 
 // with xref_bar_k = K_k'ubar[0:4], Kbar_k = -ubar[0:4] (x_k - x_ref,k)'.  A_k, B_k and the h column are the derivative of
 // step_forward at Zout's (x_k, u_k): the evaluator's closed form, with the jump knot's clock row kept (1 at x[14] and at h).
 // Zr is read only for Kbar (may be null otherwise).
-template <bool kHasK>
+// kModel (qln_tracking_rollout_model_vjp): the blocks are formed at problem b's own model (model, null: the handle's), and
+// model_bar[b] = sum_k G_k'lam_{k+1} with G_k = d Phi_k / d (g, mb, mf, lb) of qln_kernel_common.h: every lane forms the knot's
+// ModelBlock (Zout's states handed round by DPP row broadcasts), lane j accumulates G_k[j][p] lam_{k+1}[j] over the knots,
+// and the four row sums are taken once, after the loop.
+template <bool kHasK, bool kModel>
 __global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, const double* __restrict__ Zref,
                                                                 const double* __restrict__ Kg, const double* __restrict__ Zout,
                                                                 const double* __restrict__ Zbar, double* __restrict__ Zref_bar,
-                                                                double* __restrict__ Kbar, double* __restrict__ x0_bar) {
+                                                                double* __restrict__ Kbar, double* __restrict__ x0_bar,
+                                                                const double* __restrict__ model,
+                                                                double* __restrict__ model_bar) {
     const Row16 r16 = row16_of(P);  // lane 15 reads lane 14's slots and contributes nothing
     const int j = r16.j, b = r16.b, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
     const bool own = r16.own, valid = r16.valid;
-    const double g = P.g, imb = 1.0 / P.mb, imf = 1.0 / P.mf;
-    const double iIb = 12.0 / (P.mb * (P.lb * P.lb));
+    const Model M = plant_model<kModel>(P, model, bc);
+    const double g = M.g, imb = 1.0 / M.mb, imf = 1.0 / M.mf;
+    const double iIb = 12.0 / (M.mb * (M.lb * M.lb));
     const double* __restrict__ Zo = Zout + (int64_t)bc * P.z_stride;
     const double* __restrict__ Zb = Zbar + (int64_t)bc * P.z_stride;
     const double* __restrict__ Zr = Kbar ? Zref + (int64_t)bc * P.z_stride : nullptr;
@@ -377,6 +412,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, c
     const double inv = (p <= 1) ? imb : foot ? -imf : 0.0;
     const double gy = (p == 1 || p == 4 || p == 6) ? g : (j == 14) ? 1.0 : 0.0;
 
+    double mbar[QLN_MODEL_NP] = {0.0, 0.0, 0.0, 0.0};  // lane j's share of model_bar
     double lam = own ? Zb[20 * (N - 1) + j] : 0.0;
     if (valid && Zref_bar && own) Zref_bar[(int64_t)b * P.z_stride + 20 * (N - 1) + j] = 0.0;  // x_ref,N-1: never read
     VjpKnot cur, nxt;
@@ -398,6 +434,14 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, c
         const double rmask = fm * km;                           // row j of B and of the h column
         const double fmv = pos ? 1.0 : fm;                      // w = m foot velocity - body velocity
         const double cmask = cpl ? fm * (kcpl ? keep : 1.0) : 0.0;
+        if constexpr (kModel) {
+            if (model_bar) {
+                double xk[14];
+                row_bcast_first(cur.x, xk, std::make_integer_sequence<int, 14>{});
+                const ModelBlock mblk = model_block(xk, F0, F1, F2, F3, h, md, M);
+                for_each_model_entry(mblk, [&](auto r, auto q, double val) { mbar[q] = (j == r) ? fma(val, lam, mbar[q]) : mbar[q]; });
+            }
+        }
         // cross-lane lam: rows 2 and 9 (row broadcasts) and j-7 (row shift)
         const double lam2 = dpp_f64<0x152>(lam), lam9 = dpp_f64<0x159>(lam), lamc = row_shr7(lam);
         // ---- A'lam, column j: diagonal, rows 2 and 9 (h-power times d tau / d x_j), row j-7 ----
@@ -437,6 +481,17 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, c
         }
     }
     if (valid && x0_bar && own) x0_bar[(int64_t)b * QLN_NX + j] = lam;
+    if constexpr (kModel) {
+        if (model_bar) {
+            double out = 0.0;
+#pragma unroll
+            for (int q = 0; q < QLN_MODEL_NP; ++q) {
+                const double sq = row_sum16(mbar[q]);
+                out = (r16.ln == q) ? sq : out;
+            }
+            if (valid && r16.ln < QLN_MODEL_NP) model_bar[(int64_t)b * QLN_MODEL_NP + r16.ln] = out;
+        }
+    }
 }
 
 
@@ -638,11 +693,6 @@ __global__ __launch_bounds__(kWave) void k_tracking_covariance(BatchParams P, Co
 
 
 // ---- k_tracking_rollout_jvp ----
-template <int... I>
-__device__ __forceinline__ void row_bcast_first(double v, double (&out)[sizeof...(I)], std::integer_sequence<int, I...>) {
-    ((out[I] = row_bcast<I>(v)), ...);
-}
-
 // One knot's inputs, as lane ln of a row loads them.  z0 / zd0: entry ln of the knot's twenty in Zout / Zref_dot (lane
 // j < 15: x_j, lane 15: F1x); z1 / zd1: entry 16 + (ln & 3) (F1y, F2x, F2y, h in lanes 0-3).  xr: x_ref,j; kc, kd: column j
 // of K_k and of Kdot_k.
@@ -677,18 +727,22 @@ __device__ __forceinline__ void jvp_load(JvpKnot& s, const double* __restrict__ 
 // and the velocity coupling A(j, j+7) (dx[j+7] by a row shift), B row j, and the h column's entry.  Rows 2 and 9 of A are
 // dense: lane c contributes A(2, c) dx_c and A(9, c) dx_c to two row sums; K (dx - xref_dot) + Kdot e is four more.
 // Template flags say which inputs exist: nothing that is absent is read (Zref only with Kdot).
-template <bool kHasK, bool kHasKd, bool kHasZd>
+// kModel (qln_tracking_rollout_model_jvp): [A_k B_k] at problem b's own model (model, null: the handle's), and the model's
+// tangent enters as + G_k model_dot[b], lane j picking row j of G_k from for_each_model_entry (model_dot null: no term).
+template <bool kHasK, bool kHasKd, bool kHasZd, bool kModel>
 __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, const double* __restrict__ Zref,
                                                                 const double* __restrict__ Kg, const double* __restrict__ Zout,
                                                                 const double* __restrict__ Zref_dot,
                                                                 const double* __restrict__ Kdot,
                                                                 const double* __restrict__ x0_dot,
-                                                                double* __restrict__ Zout_dot) {
+                                                                double* __restrict__ Zout_dot,
+                                                                const double* __restrict__ model,
+                                                                const double* __restrict__ model_dot) {
     static_assert(kHasK || !kHasKd, "Kdot needs K");
     const Row16 r16 = row16_of(P);  // lane 15 reads lane 14's slots and contributes nothing
     const int ln = r16.ln, j = r16.j, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
     const bool own = r16.own, valid = r16.valid;
-    const Model& M = r16.M;
+    const Model M = plant_model<kModel>(P, model, bc);
     const int64_t zo = (int64_t)bc * P.z_stride, ko = (int64_t)bc * (N - 1) * (QLN_TRACK_NU * QLN_NX);
     const double* __restrict__ Zo = Zout + zo;
     const double* __restrict__ Zd = kHasZd ? Zref_dot + zo : nullptr;
@@ -697,6 +751,13 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, c
     const double* __restrict__ Kdb = kHasKd ? Kdot + ko : nullptr;
     double* __restrict__ Od = Zout_dot + zo;
 
+    double md4[QLN_MODEL_NP] = {0.0, 0.0, 0.0, 0.0};
+    if constexpr (kModel) {
+        if (model_dot) {
+#pragma unroll
+            for (int q = 0; q < QLN_MODEL_NP; ++q) md4[q] = model_dot[(int64_t)bc * QLN_MODEL_NP + q];
+        }
+    }
     double dx = (own && x0_dot) ? x0_dot[(int64_t)bc * QLN_NX + j] : 0.0;
     JvpKnot cur, nxt;
     jvp_load<kHasK, kHasKd, kHasZd>(nxt, Zo, Zd, Zr, Kb, Kdb, 0, ln, j);
@@ -708,7 +769,8 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, c
         row_bcast_first(cur.z0, x, std::make_integer_sequence<int, 14>{});
         const double F1x = row_bcast<15>(cur.z0), F1y = row_bcast<0>(cur.z1), F2x = row_bcast<1>(cur.z1),
                      F2y = row_bcast<2>(cur.z1), h = row_bcast<3>(cur.z1);
-        const StepBlock blk = step_block(x, F1x, F1y, F2x, F2y, h, knot_mode(k + 1, kt - 1, im), M);
+        const KnotMode md = knot_mode(k + 1, kt - 1, im);
+        const StepBlock blk = step_block(x, F1x, F1y, F2x, F2y, h, md, M);
         // ---- the applied controls' tangent: dF = Fref_dot - K (dx - xref_dot) - Kdot e, dh = href_dot ----
         double dF[4], dh = 0.0, xrd = 0.0;
 #pragma unroll
@@ -751,6 +813,15 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, c
             for (int m = 0; m < 4; ++m) acc = fma(bj[m], dF[m], acc);
             if constexpr (kHasZd) acc = fma(hj, dh, acc);
         }
+        if constexpr (kModel) {
+            if (model_dot) {
+                const ModelBlock mblk = model_block(x, F1x, F1y, F2x, F2y, h, md, M);
+                double gj[QLN_MODEL_NP] = {0.0, 0.0, 0.0, 0.0};
+                for_each_model_entry(mblk, [&](auto r, auto q, double val) { gj[q] = (j == r) ? val : gj[q]; });
+#pragma unroll
+                for (int q = 0; q < QLN_MODEL_NP; ++q) acc = fma(gj[q], md4[q], acc);
+            }
+        }
         // ---- the knot's twenty entries of Zout_dot: dx_k and (dF_k, dh_k) ----
         // (dF, dh) become one array only here: held as one through the knot it costs up to 8 VGPRs
         // (profiles/row16_refactor_resource_usage.txt)
@@ -775,36 +846,86 @@ hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const dou
     return hipGetLastError();
 }
 
+namespace {
+
+// The launches with and without a per-problem plant: kModel picks the instantiation, and the handle's-model entry points
+// pass null for what only the model forms have.
+template <bool kModel>
+hipError_t go_tracking_rollout(const BatchParams& p, const double* Zref, const double* K, const double* x0, double* Zout,
+                               const double* model, hipStream_t stream) {
+    hipLaunchKernelGGL(k_tracking_rollout<kModel>, dim3((p.B + kWave - 1) / kWave), dim3(kWave), 0, stream, p, Zref, K, x0, Zout,
+                       model);
+    return hipGetLastError();
+}
+
+template <bool kModel>
+hipError_t go_tracking_rollout_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
+                                   const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, const double* model,
+                                   double* model_bar, hipStream_t stream) {
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar,
+                           model, model_bar);
+    };
+    K ? go(k_tracking_rollout_vjp<true, kModel>) : go(k_tracking_rollout_vjp<false, kModel>);
+    return hipGetLastError();
+}
+
+template <bool kModel>
+hipError_t go_tracking_rollout_jvp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
+                                   const double* Zref_dot, const double* K_dot, const double* x0_dot, double* Zout_dot,
+                                   const double* model, const double* model_dot, hipStream_t stream) {
+    if (K_dot && !K) return hipErrorInvalidValue;
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, Zref, K, Zout, Zref_dot, K_dot, x0_dot,
+                           Zout_dot, model, model_dot);
+    };
+    if (K_dot)
+        Zref_dot ? go(k_tracking_rollout_jvp<true, true, true, kModel>) : go(k_tracking_rollout_jvp<true, true, false, kModel>);
+    else if (K)
+        Zref_dot ? go(k_tracking_rollout_jvp<true, false, true, kModel>) : go(k_tracking_rollout_jvp<true, false, false, kModel>);
+    else
+        Zref_dot ? go(k_tracking_rollout_jvp<false, false, true, kModel>) : go(k_tracking_rollout_jvp<false, false, false, kModel>);
+    return hipGetLastError();
+}
+
+}  // namespace
+
 hipError_t launch_tracking_rollout(const BatchParams& p, const double* Zref, const double* K, const double* x0, double* Zout,
                                    hipStream_t stream) {
-    hipLaunchKernelGGL(k_tracking_rollout, dim3((p.B + kWave - 1) / kWave), dim3(kWave), 0, stream, p, Zref, K, x0, Zout);
-    return hipGetLastError();
+    return go_tracking_rollout<false>(p, Zref, K, x0, Zout, nullptr, stream);
+}
+hipError_t launch_tracking_rollout_model(const BatchParams& p, const double* Zref, const double* K, const double* x0,
+                                         const double* model, double* Zout, hipStream_t stream) {
+    return model ? go_tracking_rollout<true>(p, Zref, K, x0, Zout, model, stream)
+                 : go_tracking_rollout<false>(p, Zref, K, x0, Zout, nullptr, stream);
 }
 
 hipError_t launch_tracking_rollout_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
                                        const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, hipStream_t stream) {
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar);
-    };
-    K ? go(k_tracking_rollout_vjp<true>) : go(k_tracking_rollout_vjp<false>);
-    return hipGetLastError();
+    return go_tracking_rollout_vjp<false>(p, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar, nullptr, nullptr, stream);
+}
+hipError_t launch_tracking_rollout_model_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
+                                             const double* model, const double* Zbar, double* Zref_bar, double* K_bar,
+                                             double* x0_bar, double* model_bar, hipStream_t stream) {
+    // nothing of the model asked for: the sweep at the handle's model, on the instantiation without the flag
+    if (!model && !model_bar)
+        return go_tracking_rollout_vjp<false>(p, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar, nullptr, nullptr, stream);
+    return go_tracking_rollout_vjp<true>(p, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar, model, model_bar, stream);
 }
 
 hipError_t launch_tracking_rollout_jvp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
                                        const double* Zref_dot, const double* K_dot, const double* x0_dot, double* Zout_dot,
                                        hipStream_t stream) {
-    if (K_dot && !K) return hipErrorInvalidValue;
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, Zref, K, Zout, Zref_dot, K_dot, x0_dot,
-                           Zout_dot);
-    };
-    if (K_dot)
-        Zref_dot ? go(k_tracking_rollout_jvp<true, true, true>) : go(k_tracking_rollout_jvp<true, true, false>);
-    else if (K)
-        Zref_dot ? go(k_tracking_rollout_jvp<true, false, true>) : go(k_tracking_rollout_jvp<true, false, false>);
-    else
-        Zref_dot ? go(k_tracking_rollout_jvp<false, false, true>) : go(k_tracking_rollout_jvp<false, false, false>);
-    return hipGetLastError();
+    return go_tracking_rollout_jvp<false>(p, Zref, K, Zout, Zref_dot, K_dot, x0_dot, Zout_dot, nullptr, nullptr, stream);
+}
+hipError_t launch_tracking_rollout_model_jvp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
+                                             const double* model, const double* Zref_dot, const double* K_dot,
+                                             const double* x0_dot, const double* model_dot, double* Zout_dot,
+                                             hipStream_t stream) {
+    // nothing of the model given: the sweep at the handle's model, on the instantiation without the flag
+    if (!model && !model_dot)
+        return go_tracking_rollout_jvp<false>(p, Zref, K, Zout, Zref_dot, K_dot, x0_dot, Zout_dot, nullptr, nullptr, stream);
+    return go_tracking_rollout_jvp<true>(p, Zref, K, Zout, Zref_dot, K_dot, x0_dot, Zout_dot, model, model_dot, stream);
 }
 
 hipError_t launch_tracking_covariance(const BatchParams& p, const double* Zout, const double* K, const double* Sigma0,

@@ -684,6 +684,124 @@ class HybridNLP:
                                                             out.ctypes.data))
         return out
 
+    # -- the roll-out and its sweeps with a per-problem plant model --------------------------------
+    def plant_models(self, models=None):
+        """(B, 4) float64 device tensor of per-problem plant models (g, mb, mf, lb): a PlanarQuadruped tiled over the batch
+        (None: the handle's own model), or a sequence of B of them."""
+        from .planar_quadruped import plant_models
+
+        return _torch().from_numpy(plant_models(self.model if models is None else models, self.B)).to(self._dev())
+
+    def _host_model(self, m, name="model"):
+        if m is None:
+            return None
+        m = np.ascontiguousarray(np.asarray(m, dtype=np.float64).reshape(-1))
+        if m.size != self.B * _lib.MODEL_NP:
+            raise ValueError(f"{name} has {m.size} entries, expected {self.B * _lib.MODEL_NP}")
+        return m
+
+    def _model_vjp_want(self, K, want):
+        want = ("Zref", "K", "x0", "model") if want is None else tuple(want)
+        bad = set(want) - {"Zref", "K", "x0", "model"}
+        if bad:
+            raise ValueError(f"want: unknown outputs {sorted(bad)} (Zref, K, x0, model)")
+        if want == ("Zref", "K", "x0", "model") and K is None:
+            want = ("Zref", "x0", "model")  # the default asks for K_bar only where there are gains
+        return want
+
+    def tracking_rollout_model(self, Zref, K=None, x0=None, model=None, out=None):
+        """tracking_rollout with a per-problem PLANT: model is a (B, 4) float64 device tensor of (g, mb, mf, lb) rows
+        (plant_models; None: the handle's model, then bit for bit tracking_rollout).  The gains and the references stay
+        what they are: only the dynamics that are rolled out read the problem's model (qln_evaluator.h)."""
+        self._check(Zref, self.dims.z_total, "Zref")
+        out = self.new_Z() if out is None else out
+        self._check(out, self.dims.z_total, "out")
+        kp = None if K is None else self._check(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        xp = None if x0 is None else self._check(x0, self.B * n, "x0")
+        mp = None if model is None else self._check(model, self.B * _lib.MODEL_NP, "model")
+        _lib.check(_lib.lib().qln_tracking_rollout_model(self._h, Zref.data_ptr(), kp, xp, mp, out.data_ptr()))
+        return out
+
+    def tracking_rollout_model_host(self, Zref, K=None, x0=None, model=None):
+        """The same with host arrays (synchronous): returns a (z_total,) numpy array (zeros past n_nlp).  A non-finite
+        model entry, or mb, mf or lb <= 0, is refused."""
+        Zref, K, model = self._host_Z(Zref, "Zref"), self._host_K(K), self._host_model(model)
+        if x0 is not None:
+            x0 = np.ascontiguousarray(np.broadcast_to(np.asarray(x0, dtype=np.float64), (self.B, n)))
+        out = np.zeros(self.dims.z_total)
+        _lib.check(_lib.lib().qln_tracking_rollout_model_host(self._h, Zref.ctypes.data, _host_ptr(K), _host_ptr(x0),
+                                                              _host_ptr(model), out.ctypes.data))
+        return out
+
+    def tracking_rollout_model_vjp(self, Zref, Zout, Zbar, K=None, model=None, want=None):
+        """Reverse sweep of tracking_rollout_model at the trajectory Zout: tracking_rollout_vjp with the blocks at each
+        problem's model, and a fourth output model_bar (B, 4), the cotangent of `model`.  Returns (Zref_bar, K_bar, x0_bar,
+        model_bar), each None unless named in want (default: all, K_bar only when K is given)."""
+        T = _torch()
+        want = self._model_vjp_want(K, want)
+        self._check(Zref, self.dims.z_total, "Zref")
+        self._check(Zout, self.dims.z_total, "Zout")
+        self._check(Zbar, self.dims.z_total, "Zbar")
+        kp = None if K is None else self._check(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        mp = None if model is None else self._check(model, self.B * _lib.MODEL_NP, "model")
+        zb = self.new_Z() if "Zref" in want else None
+        kb = T.zeros(tracking_k_shape(self.B, self.N), dtype=T.float64, device=self._dev()) if "K" in want else None
+        xb = T.zeros((self.B, n), dtype=T.float64, device=self._dev()) if "x0" in want else None
+        mb = T.zeros((self.B, _lib.MODEL_NP), dtype=T.float64, device=self._dev()) if "model" in want else None
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        _lib.check(_lib.lib().qln_tracking_rollout_model_vjp(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), mp, Zbar.data_ptr(),
+                                                             ptr(zb), ptr(kb), ptr(xb), ptr(mb)))
+        return zb, kb, xb, mb
+
+    def tracking_rollout_model_vjp_host(self, Zref, Zout, Zbar, K=None, model=None, want=None):
+        """The same with host arrays (synchronous): numpy (Zref_bar, K_bar, x0_bar, model_bar (B, 4))."""
+        want = self._model_vjp_want(K, want)
+        Zref, Zout, Zbar = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout"), self._host_Z(Zbar, "Zbar")
+        K, model = self._host_K(K), self._host_model(model)
+        zb = np.zeros(self.dims.z_total) if "Zref" in want else None
+        kb = np.zeros(tracking_k_shape(self.B, self.N)) if "K" in want else None
+        xb = np.zeros((self.B, n)) if "x0" in want else None
+        mb = np.zeros((self.B, _lib.MODEL_NP)) if "model" in want else None
+        _lib.check(_lib.lib().qln_tracking_rollout_model_vjp_host(
+            self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data, _host_ptr(model), Zbar.ctypes.data, _host_ptr(zb),
+            _host_ptr(kb), _host_ptr(xb), _host_ptr(mb)))
+        return zb, kb, xb, mb
+
+    def tracking_rollout_model_jvp(self, Zref, Zout, K=None, model=None, Zref_dot=None, K_dot=None, x0_dot=None,
+                                   model_dot=None, out=None):
+        """Forward sweep of tracking_rollout_model at the trajectory Zout: tracking_rollout_jvp with the blocks at each
+        problem's model and a fourth tangent model_dot (B, 4) -- each tangent None for zero, at least one given."""
+        nk = self.B * (self.N - 1) * _lib.TRACK_NU * n
+        self._check(Zref, self.dims.z_total, "Zref")
+        self._check(Zout, self.dims.z_total, "Zout")
+        kp = None if K is None else self._check(K, nk, "K")
+        mp = None if model is None else self._check(model, self.B * _lib.MODEL_NP, "model")
+        zd = None if Zref_dot is None else self._check(Zref_dot, self.dims.z_total, "Zref_dot")
+        kd = None if K_dot is None else self._check(K_dot, nk, "K_dot")
+        xd = None if x0_dot is None else self._check(x0_dot, self.B * n, "x0_dot")
+        md = None if model_dot is None else self._check(model_dot, self.B * _lib.MODEL_NP, "model_dot")
+        out = self.new_Z() if out is None else out
+        self._check(out, self.dims.z_total, "out")
+        _lib.check(_lib.lib().qln_tracking_rollout_model_jvp(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), mp, zd, kd, xd, md,
+                                                             out.data_ptr()))
+        return out
+
+    def tracking_rollout_model_jvp_host(self, Zref, Zout, K=None, model=None, Zref_dot=None, K_dot=None, x0_dot=None,
+                                        model_dot=None):
+        """The same with host arrays (synchronous): returns a (z_total,) numpy array (zeros past n_nlp)."""
+        Zref, Zout = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout")
+        K, K_dot = self._host_K(K), self._host_K(K_dot)
+        model, model_dot = self._host_model(model), self._host_model(model_dot, "model_dot")
+        if Zref_dot is not None:
+            Zref_dot = self._host_Z(Zref_dot, "Zref_dot")
+        if x0_dot is not None:
+            x0_dot = np.ascontiguousarray(np.broadcast_to(np.asarray(x0_dot, dtype=np.float64), (self.B, n)))
+        out = np.zeros(self.dims.z_total)
+        _lib.check(_lib.lib().qln_tracking_rollout_model_jvp_host(
+            self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data, _host_ptr(model), _host_ptr(Zref_dot), _host_ptr(K_dot),
+            _host_ptr(x0_dot), _host_ptr(model_dot), out.ctypes.data))
+        return out
+
     # -- covariance propagation through the closed-loop roll-out -----------------------------------
     def tracking_covariance(self, Zout, K=None, Sigma0=None, W=None, with_sigma=True, with_marginals=True, Sigma=None,
                             marg=None):
@@ -733,13 +851,17 @@ class HybridNLP:
                                                            _host_ptr(Wh), _host_ptr(S), _host_ptr(mg)))
         return S, mg
 
-    def differentiable_rollout(self, Zref, K=None, x0=None):
+    def differentiable_rollout(self, Zref, K=None, x0=None, model=None):
         """tracking_rollout as a torch autograd op: returns Zout, differentiable in Zref, K and x0 (each a float64 CUDA
         tensor or None).  The backward pass is one qln_tracking_rollout_vjp launch at the Zout the forward produced, a
-        forward-mode tangent (torch.autograd.forward_ad, torch.func.jvp) one qln_tracking_rollout_jvp launch."""
-        from .rollout_grad import RolloutFunction
+        forward-mode tangent (torch.autograd.forward_ad, torch.func.jvp) one qln_tracking_rollout_jvp launch.
+        With model, a (B, 4) tensor of per-problem plant models (plant_models), it is tracking_rollout_model, differentiable
+        in model too, through the _model_ forms of the two sweeps."""
+        from .rollout_grad import ModelRolloutFunction, RolloutFunction
 
-        return RolloutFunction.apply(self, Zref, K, x0)
+        if model is None:
+            return RolloutFunction.apply(self, Zref, K, x0)
+        return ModelRolloutFunction.apply(self, Zref, K, x0, model)
 
     def split_hvals(self, hvals):
         """(h_total,) values -> (step blocks (B, N-1, 55), terminal diagonals (B, 15)) as numpy arrays."""
