@@ -1107,12 +1107,26 @@ static int check_tracking_lqr_args(const qln_handle* h, const double* Zref, cons
     return check_tracking_weights(Q, R, Qf, who);
 }
 
-static int check_tracking_rollout_args(const qln_handle* h, const double* Zref, const double* Zout, const char* who) {
-    if (int rc = check_handle(h)) return rc;
-    if (!Zref || !Zout) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null Zref or Zout");
-    const uintptr_t a = reinterpret_cast<uintptr_t>(Zref), o = reinterpret_cast<uintptr_t>(Zout);
-    const uintptr_t n = (uintptr_t)h->dims.z_total * sizeof(double);
-    if (a < o + n && o < a + n) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": Zout overlaps Zref");
+// n doubles at p, an argument's buffer; a null p is an argument left out and overlaps nothing
+struct Span {
+    const double* p;
+    int64_t n;
+};
+
+static bool overlaps(Span a, Span b) {
+    if (!a.p || !b.p) return false;
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a.p), y = reinterpret_cast<uintptr_t>(b.p);
+    return x < y + (uintptr_t)b.n * sizeof(double) && y < x + (uintptr_t)a.n * sizeof(double);
+}
+
+// The one overlap rule of the entry points: no output may overlap an input or another output.
+static int check_no_overlap(std::initializer_list<Span> out, std::initializer_list<Span> in, const std::string& w) {
+    for (const Span& o : out) {
+        for (const Span& i : in)
+            if (overlaps(o, i)) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": an output overlaps an input");
+        for (const Span& q : out)
+            if (&q != &o && overlaps(o, q)) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": two outputs overlap");
+    }
     return QLN_OK;
 }
 
@@ -1121,13 +1135,6 @@ int qln_tracking_lqr(qln_handle* h, const double* Zref, const double* Qdiag, con
     if (int rc = check_tracking_lqr_args(h, Zref, Qdiag, Rdiag, Qfdiag, K, "qln_tracking_lqr")) return rc;
     if (int rc = bind_device(h)) return rc;
     QLN_HIP(qln::launch_tracking_lqr(h->p, Qdiag, Rdiag, Qfdiag, Zref, K, P, h->stream));
-    return QLN_OK;
-}
-
-int qln_tracking_rollout(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout) {
-    if (int rc = check_tracking_rollout_args(h, Zref, Zout, "qln_tracking_rollout")) return rc;
-    if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout(h->p, Zref, K, x0, Zout, h->stream));
     return QLN_OK;
 }
 
@@ -1140,154 +1147,9 @@ int qln_tracking_lqr_host(qln_handle* h, const double* Zref, const double* Qdiag
     });
 }
 
-int qln_tracking_rollout_host(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout) {
-    if (int rc = check_tracking_rollout_args(h, Zref, Zout, "qln_tracking_rollout_host")) return rc;
-    if (int rc = bind_device(h)) return rc;
-    return host_call(h, {copy_in(kZ, Zref), copy_inout(kZio, Zout), copy_in(kK, K), copy_in(kX0, x0)},
-                     [&](double* const* d, bool) {
-                         return qln::launch_tracking_rollout(h->p, d[kZ], d[kK], d[kX0], d[kZio], h->stream);
-                     });
-}
-
-// the roll-out's reverse sweep (k_tracking_rollout_vjp)
-static bool overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
-    if (!a || !b) return false;
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + (uintptr_t)nb * sizeof(double) && y < x + (uintptr_t)na * sizeof(double);
-}
-
-static int check_tracking_vjp_args(const qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                   const double* Zbar, const double* Zref_bar, const double* K_bar, const double* x0_bar,
-                                   const char* who) {
-    if (int rc = check_handle(h)) return rc;
-    const std::string w(who);
-    if (!Zref || !Zout || !Zbar) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref, Zout or Zbar");
-    if (K_bar && !K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_bar needs K (K == NULL has no gains to differentiate)");
-    const qln_dims& D = h->dims;
-    const int64_t nz = D.z_total, nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX;
-    const struct {
-        const double* p;
-        int64_t n;
-    } in[] = {{Zref, nz}, {K, nk}, {Zout, nz}, {Zbar, nz}}, out[] = {{Zref_bar, nz}, {K_bar, nk}, {x0_bar, nx}};
-    for (const auto& o : out) {
-        for (const auto& i : in)
-            if (overlaps(o.p, o.n, i.p, i.n)) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": an output overlaps an input");
-        for (const auto& q : out)
-            if (&q != &o && overlaps(o.p, o.n, q.p, q.n)) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": two outputs overlap");
-    }
-    return QLN_OK;
-}
-
-int qln_tracking_rollout_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
-                             double* Zref_bar, double* K_bar, double* x0_bar) {
-    if (int rc = check_tracking_vjp_args(h, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar, "qln_tracking_rollout_vjp")) return rc;
-    if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout_vjp(h->p, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar, h->stream));
-    return QLN_OK;
-}
-
-// Zref is staged only when K_bar asks for it (the kernel reads it for nothing else); otherwise Zout's buffer stands in.
-int qln_tracking_rollout_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
-                                  double* Zref_bar, double* K_bar, double* x0_bar) {
-    if (int rc = check_tracking_vjp_args(h, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar, "qln_tracking_rollout_vjp_host"))
-        return rc;
-    if (int rc = bind_device(h)) return rc;
-    return host_call(h,
-                     {copy_in(kV, Zout), copy_in(kZbar, Zbar), copy_in(kZ, K_bar ? Zref : nullptr), copy_in(kK, K),
-                      copy_inout(kZio, Zref_bar), copy_out(kKbar, K_bar), copy_out(kX0, x0_bar)},
-                     [&](double* const* d, bool) {
-                         return qln::launch_tracking_rollout_vjp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kZbar], d[kZio],
-                                                                 d[kKbar], d[kX0], h->stream);
-                     });
-}
-
-// the roll-out's forward sweep (k_tracking_rollout_jvp).  The checks that need no handle come first.
-static int check_tracking_jvp_args(const qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                   const double* Zref_dot, const double* K_dot, const double* x0_dot, const double* Zout_dot,
-                                   const char* who) {
-    const std::string w(who);
-    if (!Zref_dot && !K_dot && !x0_dot)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Zref_dot, K_dot and x0_dot are all NULL (no direction)");
-    if (K_dot && !K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_dot needs K (K == NULL has no gains to perturb)");
-    if (!Zref || !Zout || !Zout_dot) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref, Zout or Zout_dot");
-    if (int rc = check_handle(h)) return rc;
-    const qln_dims& D = h->dims;
-    const int64_t nz = D.z_total, nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX;
-    const struct {
-        const double* p;
-        int64_t n;
-    } in[] = {{Zref, nz}, {K, nk}, {Zout, nz}, {Zref_dot, nz}, {K_dot, nk}, {x0_dot, nx}};
-    for (const auto& i : in)
-        if (overlaps(Zout_dot, nz, i.p, i.n)) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Zout_dot overlaps an input");
-    return QLN_OK;
-}
-
-int qln_tracking_rollout_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zref_dot,
-                             const double* K_dot, const double* x0_dot, double* Zout_dot) {
-    if (int rc = check_tracking_jvp_args(h, Zref, K, Zout, Zref_dot, K_dot, x0_dot, Zout_dot, "qln_tracking_rollout_jvp"))
-        return rc;
-    if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout_jvp(h->p, Zref, K, Zout, Zref_dot, K_dot, x0_dot, Zout_dot, h->stream));
-    return QLN_OK;
-}
-
-// Zref is staged only when K_dot is given (the kernel reads it for nothing else); otherwise Zout's buffer stands in.
-int qln_tracking_rollout_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                  const double* Zref_dot, const double* K_dot, const double* x0_dot, double* Zout_dot) {
-    if (int rc = check_tracking_jvp_args(h, Zref, K, Zout, Zref_dot, K_dot, x0_dot, Zout_dot, "qln_tracking_rollout_jvp_host"))
-        return rc;
-    if (int rc = bind_device(h)) return rc;
-    return host_call(h,
-                     {copy_in(kV, Zout), copy_in(kZ, K_dot ? Zref : nullptr), copy_in(kK, K), copy_in(kZdot, Zref_dot),
-                      copy_in(kKdot, K_dot), copy_in(kX0, x0_dot), copy_inout(kZio, Zout_dot)},
-                     [&](double* const* d, bool) {
-                         return qln::launch_tracking_rollout_jvp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kZdot], d[kKdot],
-                                                                 d[kX0], d[kZio], h->stream);
-                     });
-}
-
-// the roll-out and its sweeps with a per-problem plant (the same kernels, instantiated with kModel).  The argument checks are
-// those of the forms without a model, with model as one more input, model_dot as a fourth tangent and model_bar as a
-// fourth output.  The checks that need no handle come first, as above.
-static int check_tracking_model_jvp_args(const qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                         const double* model, const double* Zref_dot, const double* K_dot, const double* x0_dot,
-                                         const double* model_dot, const double* Zout_dot, const char* who) {
-    const std::string w(who);
-    if (!Zref_dot && !K_dot && !x0_dot && !model_dot)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Zref_dot, K_dot, x0_dot and model_dot are all NULL (no direction)");
-    if (K_dot && !K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_dot needs K (K == NULL has no gains to perturb)");
-    if (!Zref || !Zout || !Zout_dot) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref, Zout or Zout_dot");
-    if (int rc = check_handle(h)) return rc;
-    const qln_dims& D = h->dims;
-    const int64_t nz = D.z_total, nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX, nm = (int64_t)D.B * QLN_MODEL_NP;
-    const struct {
-        const double* p;
-        int64_t n;
-    } in[] = {{Zref, nz}, {K, nk}, {Zout, nz}, {model, nm}, {Zref_dot, nz}, {K_dot, nk}, {x0_dot, nx}, {model_dot, nm}};
-    for (const auto& i : in)
-        if (overlaps(Zout_dot, nz, i.p, i.n)) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Zout_dot overlaps an input");
-    return QLN_OK;
-}
-
-static int check_tracking_model_vjp_args(const qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                         const double* model, const double* Zbar, const double* Zref_bar, const double* K_bar,
-                                         const double* x0_bar, const double* model_bar, const char* who) {
-    if (int rc = check_tracking_vjp_args(h, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar, who)) return rc;
-    const qln_dims& D = h->dims;
-    const int64_t nz = D.z_total, nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX, nm = (int64_t)D.B * QLN_MODEL_NP;
-    const struct {
-        const double* p;
-        int64_t n;
-    } other[] = {{Zref, nz}, {K, nk}, {Zout, nz}, {Zbar, nz}, {model, nm}, {Zref_bar, nz}, {K_bar, nk}, {x0_bar, nx}},
-      out[] = {{Zref_bar, nz}, {K_bar, nk}, {x0_bar, nx}};
-    for (const auto& o : other)
-        if (overlaps(model_bar, nm, o.p, o.n))
-            return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": model_bar overlaps an input or another output");
-    for (const auto& o : out)
-        if (overlaps(o.p, o.n, model, nm)) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": an output overlaps model");
-    return QLN_OK;
-}
-
+// The roll-out and its two sweeps (k_tracking_rollout, _vjp, _jvp): one argument check and one body per operation and memory
+// form, with the per-problem plant as optional arguments.  The entry points without a model pass null for model, model_dot
+// and model_bar, and the launch then takes the kernels without their kModel flag.
 // host forms only: every entry finite, and mb, mf, lb > 0 (the device forms do not look at the values)
 static int check_host_models(const qln_handle* h, const double* model, const char* who) {
     if (!model) return QLN_OK;
@@ -1301,83 +1163,171 @@ static int check_host_models(const qln_handle* h, const double* model, const cha
     return QLN_OK;
 }
 
-int qln_tracking_rollout_model(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
-                               double* Zout) {
-    if (int rc = check_tracking_rollout_args(h, Zref, Zout, "qln_tracking_rollout_model")) return rc;
+static int check_tracking_rollout_args(const qln_handle* h, const double* Zref, const double* Zout, const char* who) {
+    if (int rc = check_handle(h)) return rc;
+    if (!Zref || !Zout) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null Zref or Zout");
+    return check_no_overlap({{Zout, h->dims.z_total}}, {{Zref, h->dims.z_total}}, who);  // K, x0 and model are not looked at
+}
+
+static int tracking_rollout(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
+                            double* Zout, const char* who) {
+    if (int rc = check_tracking_rollout_args(h, Zref, Zout, who)) return rc;
     if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout_model(h->p, Zref, K, x0, model, Zout, h->stream));
+    QLN_HIP(qln::launch_tracking_rollout(h->p, Zref, K, x0, model, Zout, h->stream));
     return QLN_OK;
 }
 
-int qln_tracking_rollout_model_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
-                                    double* Zout) {
-    if (int rc = check_tracking_rollout_args(h, Zref, Zout, "qln_tracking_rollout_model_host")) return rc;
-    if (int rc = check_host_models(h, model, "qln_tracking_rollout_model_host")) return rc;
+static int tracking_rollout_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
+                                 double* Zout, const char* who) {
+    if (int rc = check_tracking_rollout_args(h, Zref, Zout, who)) return rc;
+    if (int rc = check_host_models(h, model, who)) return rc;
     if (int rc = bind_device(h)) return rc;
     return host_call(h, {copy_in(kZ, Zref), copy_inout(kZio, Zout), copy_in(kK, K), copy_in(kX0, x0), copy_in(kModel, model)},
                      [&](double* const* d, bool) {
-                         return qln::launch_tracking_rollout_model(h->p, d[kZ], d[kK], d[kX0], d[kModel], d[kZio], h->stream);
+                         return qln::launch_tracking_rollout(h->p, d[kZ], d[kK], d[kX0], d[kModel], d[kZio], h->stream);
                      });
 }
 
-int qln_tracking_rollout_model_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
-                                   const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar) {
-    if (int rc = check_tracking_model_vjp_args(h, Zref, K, Zout, model, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
-                                               "qln_tracking_rollout_model_vjp"))
-        return rc;
+// the reverse sweep: the handle first
+static int check_tracking_vjp_args(const qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                   const double* model, const double* Zbar, const double* Zref_bar, const double* K_bar,
+                                   const double* x0_bar, const double* model_bar, const char* who) {
+    if (int rc = check_handle(h)) return rc;
+    const std::string w(who);
+    if (!Zref || !Zout || !Zbar) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref, Zout or Zbar");
+    if (K_bar && !K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_bar needs K (K == NULL has no gains to differentiate)");
+    const qln_dims& D = h->dims;
+    const int64_t nz = D.z_total, nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX, nm = (int64_t)D.B * QLN_MODEL_NP;
+    return check_no_overlap({{Zref_bar, nz}, {K_bar, nk}, {x0_bar, nx}, {model_bar, nm}},
+                            {{Zref, nz}, {K, nk}, {Zout, nz}, {Zbar, nz}, {model, nm}}, w);
+}
+
+static int tracking_rollout_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
+                                const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar,
+                                const char* who) {
+    if (int rc = check_tracking_vjp_args(h, Zref, K, Zout, model, Zbar, Zref_bar, K_bar, x0_bar, model_bar, who)) return rc;
     if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout_model_vjp(h->p, Zref, K, Zout, model, Zbar, Zref_bar, K_bar, x0_bar, model_bar, h->stream));
+    QLN_HIP(qln::launch_tracking_rollout_vjp(h->p, Zref, K, Zout, model, Zbar, Zref_bar, K_bar, x0_bar, model_bar, h->stream));
     return QLN_OK;
 }
 
-int qln_tracking_rollout_model_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                        const double* model, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
-                                        double* model_bar) {
-    if (int rc = check_tracking_model_vjp_args(h, Zref, K, Zout, model, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
-                                               "qln_tracking_rollout_model_vjp_host"))
-        return rc;
-    if (int rc = check_host_models(h, model, "qln_tracking_rollout_model_vjp_host")) return rc;
+// Zref is staged only when K_bar asks for it (the kernel reads it for nothing else); otherwise Zout's buffer stands in.
+static int tracking_rollout_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                     const double* model, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
+                                     double* model_bar, const char* who) {
+    if (int rc = check_tracking_vjp_args(h, Zref, K, Zout, model, Zbar, Zref_bar, K_bar, x0_bar, model_bar, who)) return rc;
+    if (int rc = check_host_models(h, model, who)) return rc;
     if (int rc = bind_device(h)) return rc;
     return host_call(h,
                      {copy_in(kV, Zout), copy_in(kZbar, Zbar), copy_in(kZ, K_bar ? Zref : nullptr), copy_in(kK, K),
                       copy_in(kModel, model), copy_inout(kZio, Zref_bar), copy_out(kKbar, K_bar), copy_out(kX0, x0_bar),
                       copy_out(kModelD, model_bar)},
                      [&](double* const* d, bool) {
-                         return qln::launch_tracking_rollout_model_vjp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kModel],
-                                                                       d[kZbar], d[kZio], d[kKbar], d[kX0], d[kModelD],
-                                                                       h->stream);
+                         return qln::launch_tracking_rollout_vjp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kModel], d[kZbar],
+                                                                 d[kZio], d[kKbar], d[kX0], d[kModelD], h->stream);
                      });
 }
 
-int qln_tracking_rollout_model_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
-                                   const double* Zref_dot, const double* K_dot, const double* x0_dot, const double* model_dot,
-                                   double* Zout_dot) {
-    if (int rc = check_tracking_model_jvp_args(h, Zref, K, Zout, model, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
-                                               "qln_tracking_rollout_model_jvp"))
-        return rc;
+// the forward sweep: the checks that need no handle come first
+static int check_tracking_jvp_args(const qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                   const double* model, const double* Zref_dot, const double* K_dot, const double* x0_dot,
+                                   const double* model_dot, const double* Zout_dot, const char* who) {
+    const std::string w(who);
+    if (!Zref_dot && !K_dot && !x0_dot && !model_dot)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every tangent is NULL (no direction)");
+    if (K_dot && !K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_dot needs K (K == NULL has no gains to perturb)");
+    if (!Zref || !Zout || !Zout_dot) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref, Zout or Zout_dot");
+    if (int rc = check_handle(h)) return rc;
+    const qln_dims& D = h->dims;
+    const int64_t nz = D.z_total, nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX, nm = (int64_t)D.B * QLN_MODEL_NP;
+    return check_no_overlap({{Zout_dot, nz}}, {{Zref, nz}, {K, nk}, {Zout, nz}, {model, nm}, {Zref_dot, nz}, {K_dot, nk},
+                                               {x0_dot, nx}, {model_dot, nm}}, w);
+}
+
+static int tracking_rollout_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
+                                const double* Zref_dot, const double* K_dot, const double* x0_dot, const double* model_dot,
+                                double* Zout_dot, const char* who) {
+    if (int rc = check_tracking_jvp_args(h, Zref, K, Zout, model, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot, who)) return rc;
     if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout_model_jvp(h->p, Zref, K, Zout, model, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
-                                                   h->stream));
+    QLN_HIP(qln::launch_tracking_rollout_jvp(h->p, Zref, K, Zout, model, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
+                                             h->stream));
     return QLN_OK;
 }
 
-int qln_tracking_rollout_model_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                        const double* model, const double* Zref_dot, const double* K_dot, const double* x0_dot,
-                                        const double* model_dot, double* Zout_dot) {
-    if (int rc = check_tracking_model_jvp_args(h, Zref, K, Zout, model, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
-                                               "qln_tracking_rollout_model_jvp_host"))
-        return rc;
-    if (int rc = check_host_models(h, model, "qln_tracking_rollout_model_jvp_host")) return rc;
+// Zref is staged only when K_dot is given (the kernel reads it for nothing else); otherwise Zout's buffer stands in.
+static int tracking_rollout_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                     const double* model, const double* Zref_dot, const double* K_dot, const double* x0_dot,
+                                     const double* model_dot, double* Zout_dot, const char* who) {
+    if (int rc = check_tracking_jvp_args(h, Zref, K, Zout, model, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot, who)) return rc;
+    if (int rc = check_host_models(h, model, who)) return rc;
     if (int rc = bind_device(h)) return rc;
     return host_call(h,
                      {copy_in(kV, Zout), copy_in(kZ, K_dot ? Zref : nullptr), copy_in(kK, K), copy_in(kModel, model),
                       copy_in(kZdot, Zref_dot), copy_in(kKdot, K_dot), copy_in(kX0, x0_dot), copy_in(kModelD, model_dot),
                       copy_inout(kZio, Zout_dot)},
                      [&](double* const* d, bool) {
-                         return qln::launch_tracking_rollout_model_jvp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kModel],
-                                                                       d[kZdot], d[kKdot], d[kX0], d[kModelD], d[kZio],
-                                                                       h->stream);
+                         return qln::launch_tracking_rollout_jvp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kModel], d[kZdot],
+                                                                 d[kKdot], d[kX0], d[kModelD], d[kZio], h->stream);
                      });
+}
+
+// the twelve entry points: the forms without a model are the same path with null model arguments
+int qln_tracking_rollout(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout) {
+    return tracking_rollout(h, Zref, K, x0, nullptr, Zout, "qln_tracking_rollout");
+}
+int qln_tracking_rollout_host(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout) {
+    return tracking_rollout_host(h, Zref, K, x0, nullptr, Zout, "qln_tracking_rollout_host");
+}
+int qln_tracking_rollout_model(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
+                               double* Zout) {
+    return tracking_rollout(h, Zref, K, x0, model, Zout, "qln_tracking_rollout_model");
+}
+int qln_tracking_rollout_model_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
+                                    double* Zout) {
+    return tracking_rollout_host(h, Zref, K, x0, model, Zout, "qln_tracking_rollout_model_host");
+}
+
+int qln_tracking_rollout_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
+                             double* Zref_bar, double* K_bar, double* x0_bar) {
+    return tracking_rollout_vjp(h, Zref, K, Zout, nullptr, Zbar, Zref_bar, K_bar, x0_bar, nullptr, "qln_tracking_rollout_vjp");
+}
+int qln_tracking_rollout_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
+                                  double* Zref_bar, double* K_bar, double* x0_bar) {
+    return tracking_rollout_vjp_host(h, Zref, K, Zout, nullptr, Zbar, Zref_bar, K_bar, x0_bar, nullptr,
+                                     "qln_tracking_rollout_vjp_host");
+}
+int qln_tracking_rollout_model_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
+                                   const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar) {
+    return tracking_rollout_vjp(h, Zref, K, Zout, model, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
+                                "qln_tracking_rollout_model_vjp");
+}
+int qln_tracking_rollout_model_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                        const double* model, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
+                                        double* model_bar) {
+    return tracking_rollout_vjp_host(h, Zref, K, Zout, model, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
+                                     "qln_tracking_rollout_model_vjp_host");
+}
+
+int qln_tracking_rollout_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zref_dot,
+                             const double* K_dot, const double* x0_dot, double* Zout_dot) {
+    return tracking_rollout_jvp(h, Zref, K, Zout, nullptr, Zref_dot, K_dot, x0_dot, nullptr, Zout_dot, "qln_tracking_rollout_jvp");
+}
+int qln_tracking_rollout_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                  const double* Zref_dot, const double* K_dot, const double* x0_dot, double* Zout_dot) {
+    return tracking_rollout_jvp_host(h, Zref, K, Zout, nullptr, Zref_dot, K_dot, x0_dot, nullptr, Zout_dot,
+                                     "qln_tracking_rollout_jvp_host");
+}
+int qln_tracking_rollout_model_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
+                                   const double* Zref_dot, const double* K_dot, const double* x0_dot, const double* model_dot,
+                                   double* Zout_dot) {
+    return tracking_rollout_jvp(h, Zref, K, Zout, model, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
+                                "qln_tracking_rollout_model_jvp");
+}
+int qln_tracking_rollout_model_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                        const double* model, const double* Zref_dot, const double* K_dot, const double* x0_dot,
+                                        const double* model_dot, double* Zout_dot) {
+    return tracking_rollout_jvp_host(h, Zref, K, Zout, model, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
+                                     "qln_tracking_rollout_model_jvp_host");
 }
 
 // the covariance sweep (k_tracking_covariance).  The checks that need no handle come first.
@@ -1395,16 +1345,8 @@ static int check_tracking_covariance_args(const qln_handle* h, const double* Zou
     const qln_dims& D = h->dims;
     if (sigma0_batch != 1 && sigma0_batch != D.B) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
     if (!Zout || !Sigma0) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zout or Sigma0");
-    const struct {
-        const double* p;
-        int64_t n;
-    } in[] = {{Zout, D.z_total}, {K, tracking_k_total(D)}, {Sigma0, (int64_t)sigma0_batch * QLN_TRACK_P_NNZ}},
-      out[] = {{Sigma, tracking_p_total(D)}, {marg, tracking_marg_total(D)}};
-    for (const auto& o : out)
-        for (const auto& i : in)
-            if (overlaps(o.p, o.n, i.p, i.n)) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": an output overlaps an input");
-    if (overlaps(out[0].p, out[0].n, out[1].p, out[1].n)) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Sigma overlaps marg");
-    return QLN_OK;
+    return check_no_overlap({{Sigma, tracking_p_total(D)}, {marg, tracking_marg_total(D)}},
+                            {{Zout, D.z_total}, {K, tracking_k_total(D)}, {Sigma0, (int64_t)sigma0_batch * QLN_TRACK_P_NNZ}}, w);
 }
 
 int qln_tracking_covariance(qln_handle* h, const double* Zout, const double* K, const double* Sigma0, int32_t sigma0_batch,

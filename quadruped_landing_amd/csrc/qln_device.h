@@ -293,33 +293,23 @@ hipError_t launch_hessian_lagrangian(const BatchParams& p, const double* Z, cons
 // y = H v with the same H, contracted in registers (qln_hessian_kernels.hip); v and y in the layout of Z
 hipError_t launch_hessian_lagrangian_product(const BatchParams& p, const double* Z, const double* sigma, const double* mu,
                                              const double* v, double* y, hipStream_t stream);
-// TVLQR gains (and cost-to-go, P may be null) along the reference trajectories Zref; closed-loop roll-out under K (null:
-// open loop) from x0 (null: the handle's x0) (qln_tracking_kernels.hip).  Qd / Rd / Qfd are host arrays.
+// TVLQR gains (and cost-to-go, P may be null) along the reference trajectories Zref (qln_tracking_kernels.hip).  Qd / Rd / Qfd
+// are host arrays.
 hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const double* Rd, const double* Qfd, const double* Zref,
                                double* K, double* P, hipStream_t stream);
-hipError_t launch_tracking_rollout(const BatchParams& p, const double* Zref, const double* K, const double* x0, double* Zout,
-                                   hipStream_t stream);
-// the roll-out's reverse sweep at Zout's trajectory: cotangent Zbar -> Zref_bar, K_bar, x0_bar (each may be null; K_bar
-// needs K and reads Zref's states) (qln_tracking_kernels.hip)
+// The roll-out from x0 (null: the handle's x0) and its two sweeps at Zout's trajectory, with a per-problem plant: model
+// [B][QLN_MODEL_NP] = (g, mb, mf, lb) per problem (null: the handle's), its tangent model_dot and cotangent model_bar in the same
+// layout.  Reverse: cotangent Zbar -> Zref_bar, K_bar, x0_bar, model_bar (each may be null).  Forward: tangents Zref_dot, K_dot,
+// x0_dot, model_dot (each may be null: zero) -> Zout_dot in the layout of Z.  K_bar and K_dot need K and read Zref's states.
+// With nothing of the model passed the kernels run without their kModel flag (qln_tracking_kernels.hip).
+hipError_t launch_tracking_rollout(const BatchParams& p, const double* Zref, const double* K, const double* x0,
+                                   const double* model, double* Zout, hipStream_t stream);
 hipError_t launch_tracking_rollout_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
-                                       const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, hipStream_t stream);
-// the roll-out's forward (tangent) sweep at Zout's trajectory: tangents Zref_dot, K_dot, x0_dot (each may be null: zero; K_dot
-// needs K and reads Zref's states) -> Zout_dot in the layout of Z (qln_tracking_kernels.hip)
+                                       const double* model, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
+                                       double* model_bar, hipStream_t stream);
 hipError_t launch_tracking_rollout_jvp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
-                                       const double* Zref_dot, const double* K_dot, const double* x0_dot, double* Zout_dot,
-                                       hipStream_t stream);
-// the roll-out and its two sweeps with a per-problem plant: model [B][QLN_MODEL_NP] = (g, mb, mf, lb) per problem (null: the
-// handle's), the model's tangent model_dot and cotangent model_bar in the same layout (each may be null)
-// (qln_tracking_kernels.hip, the same kernels instantiated with kModel)
-hipError_t launch_tracking_rollout_model(const BatchParams& p, const double* Zref, const double* K, const double* x0,
-                                         const double* model, double* Zout, hipStream_t stream);
-hipError_t launch_tracking_rollout_model_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
-                                             const double* model, const double* Zbar, double* Zref_bar, double* K_bar,
-                                             double* x0_bar, double* model_bar, hipStream_t stream);
-hipError_t launch_tracking_rollout_model_jvp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
-                                             const double* model, const double* Zref_dot, const double* K_dot,
-                                             const double* x0_dot, const double* model_dot, double* Zout_dot,
-                                             hipStream_t stream);
+                                       const double* model, const double* Zref_dot, const double* K_dot, const double* x0_dot,
+                                       const double* model_dot, double* Zout_dot, hipStream_t stream);
 // Sigma_{k+1} = (A_k - B_k K_k) Sigma_k (A_k - B_k K_k)' + diag(Wd) along Zout (K null: open loop); Sigma0 [sigma0_batch][120],
 // Wd a host array (null: zeros); Sigma [B][N][120] and marg [B][N][8], either may be null (qln_tracking_kernels.hip)
 hipError_t launch_tracking_covariance(const BatchParams& p, const double* Zout, const double* K, const double* Sigma0,

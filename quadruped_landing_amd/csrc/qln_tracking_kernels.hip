@@ -846,86 +846,55 @@ hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const dou
     return hipGetLastError();
 }
 
-namespace {
-
-// The launches with and without a per-problem plant: kModel picks the instantiation, and the handle's-model entry points
-// pass null for what only the model forms have.
-template <bool kModel>
-hipError_t go_tracking_rollout(const BatchParams& p, const double* Zref, const double* K, const double* x0, double* Zout,
-                               const double* model, hipStream_t stream) {
-    hipLaunchKernelGGL(k_tracking_rollout<kModel>, dim3((p.B + kWave - 1) / kWave), dim3(kWave), 0, stream, p, Zref, K, x0, Zout,
-                       model);
+// The roll-out and its two sweeps.  kModel is on only where something of the model is passed: the forms at the handle's model
+// pass null and run the instantiation without the flag.
+hipError_t launch_tracking_rollout(const BatchParams& p, const double* Zref, const double* K, const double* x0,
+                                   const double* model, double* Zout, hipStream_t stream) {
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((p.B + kWave - 1) / kWave), dim3(kWave), 0, stream, p, Zref, K, x0, Zout, model);
+    };
+    model ? go(k_tracking_rollout<true>) : go(k_tracking_rollout<false>);
     return hipGetLastError();
 }
 
-template <bool kModel>
-hipError_t go_tracking_rollout_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
-                                   const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, const double* model,
-                                   double* model_bar, hipStream_t stream) {
+hipError_t launch_tracking_rollout_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
+                                       const double* model, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
+                                       double* model_bar, hipStream_t stream) {
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar,
                            model, model_bar);
     };
-    K ? go(k_tracking_rollout_vjp<true, kModel>) : go(k_tracking_rollout_vjp<false, kModel>);
+    if (model || model_bar)
+        K ? go(k_tracking_rollout_vjp<true, true>) : go(k_tracking_rollout_vjp<false, true>);
+    else
+        K ? go(k_tracking_rollout_vjp<true, false>) : go(k_tracking_rollout_vjp<false, false>);
     return hipGetLastError();
 }
 
-template <bool kModel>
-hipError_t go_tracking_rollout_jvp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
-                                   const double* Zref_dot, const double* K_dot, const double* x0_dot, double* Zout_dot,
-                                   const double* model, const double* model_dot, hipStream_t stream) {
+hipError_t launch_tracking_rollout_jvp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
+                                       const double* model, const double* Zref_dot, const double* K_dot, const double* x0_dot,
+                                       const double* model_dot, double* Zout_dot, hipStream_t stream) {
     if (K_dot && !K) return hipErrorInvalidValue;
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, Zref, K, Zout, Zref_dot, K_dot, x0_dot,
                            Zout_dot, model, model_dot);
     };
+    // kHasK, kHasKd, kHasZd as compile-time flags, then kModel
+    auto pick = [&](auto hasK, auto hasKd, auto hasZd) {
+        if (model || model_dot)
+            go(k_tracking_rollout_jvp<hasK(), hasKd(), hasZd(), true>);
+        else
+            go(k_tracking_rollout_jvp<hasK(), hasKd(), hasZd(), false>);
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
     if (K_dot)
-        Zref_dot ? go(k_tracking_rollout_jvp<true, true, true, kModel>) : go(k_tracking_rollout_jvp<true, true, false, kModel>);
+        Zref_dot ? pick(yes, yes, yes) : pick(yes, yes, no);
     else if (K)
-        Zref_dot ? go(k_tracking_rollout_jvp<true, false, true, kModel>) : go(k_tracking_rollout_jvp<true, false, false, kModel>);
+        Zref_dot ? pick(yes, no, yes) : pick(yes, no, no);
     else
-        Zref_dot ? go(k_tracking_rollout_jvp<false, false, true, kModel>) : go(k_tracking_rollout_jvp<false, false, false, kModel>);
+        Zref_dot ? pick(no, no, yes) : pick(no, no, no);
     return hipGetLastError();
-}
-
-}  // namespace
-
-hipError_t launch_tracking_rollout(const BatchParams& p, const double* Zref, const double* K, const double* x0, double* Zout,
-                                   hipStream_t stream) {
-    return go_tracking_rollout<false>(p, Zref, K, x0, Zout, nullptr, stream);
-}
-hipError_t launch_tracking_rollout_model(const BatchParams& p, const double* Zref, const double* K, const double* x0,
-                                         const double* model, double* Zout, hipStream_t stream) {
-    return model ? go_tracking_rollout<true>(p, Zref, K, x0, Zout, model, stream)
-                 : go_tracking_rollout<false>(p, Zref, K, x0, Zout, nullptr, stream);
-}
-
-hipError_t launch_tracking_rollout_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
-                                       const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, hipStream_t stream) {
-    return go_tracking_rollout_vjp<false>(p, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar, nullptr, nullptr, stream);
-}
-hipError_t launch_tracking_rollout_model_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
-                                             const double* model, const double* Zbar, double* Zref_bar, double* K_bar,
-                                             double* x0_bar, double* model_bar, hipStream_t stream) {
-    // nothing of the model asked for: the sweep at the handle's model, on the instantiation without the flag
-    if (!model && !model_bar)
-        return go_tracking_rollout_vjp<false>(p, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar, nullptr, nullptr, stream);
-    return go_tracking_rollout_vjp<true>(p, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar, model, model_bar, stream);
-}
-
-hipError_t launch_tracking_rollout_jvp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
-                                       const double* Zref_dot, const double* K_dot, const double* x0_dot, double* Zout_dot,
-                                       hipStream_t stream) {
-    return go_tracking_rollout_jvp<false>(p, Zref, K, Zout, Zref_dot, K_dot, x0_dot, Zout_dot, nullptr, nullptr, stream);
-}
-hipError_t launch_tracking_rollout_model_jvp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
-                                             const double* model, const double* Zref_dot, const double* K_dot,
-                                             const double* x0_dot, const double* model_dot, double* Zout_dot,
-                                             hipStream_t stream) {
-    // nothing of the model given: the sweep at the handle's model, on the instantiation without the flag
-    if (!model && !model_dot)
-        return go_tracking_rollout_jvp<false>(p, Zref, K, Zout, Zref_dot, K_dot, x0_dot, Zout_dot, nullptr, nullptr, stream);
-    return go_tracking_rollout_jvp<true>(p, Zref, K, Zout, Zref_dot, K_dot, x0_dot, Zout_dot, model, model_dot, stream);
 }
 
 hipError_t launch_tracking_covariance(const BatchParams& p, const double* Zout, const double* K, const double* Sigma0,

@@ -588,109 +588,19 @@ class HybridNLP:
                                                     K.ctypes.data, None if P is None else P.ctypes.data))
         return K, P
 
-    def tracking_rollout(self, Zref, K=None, x0=None, out=None):
-        """Closed-loop roll-out of the hybrid dynamics from x0 ((B, 15) device tensor, None: the handle's x0) with
-        F_k = F_ref,k - K_k (x_k - x_ref,k) and h_k = h_ref,k; K None is the open-loop roll-out.  Returns Zout in the
-        layout of Z (entries past n_nlp are not written).  out must not overlap Zref."""
-        self._check(Zref, self.dims.z_total, "Zref")
-        out = self.new_Z() if out is None else out
-        self._check(out, self.dims.z_total, "out")
-        kp = None if K is None else self._check(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
-        xp = None if x0 is None else self._check(x0, self.B * n, "x0")
-        _lib.check(_lib.lib().qln_tracking_rollout(self._h, Zref.data_ptr(), kp, xp, out.data_ptr()))
-        return out
+    # -- the closed-loop roll-out and its two sweeps ------------------------------------------------
+    # One implementation per operation and memory form, with the per-problem plant as optional arguments.  `m` picks the
+    # entry point: the _model_ one, which takes model / model_dot / model_bar, or the one at the handle's model without them.
+    def _rollout_fn(self, op, m, host):
+        return getattr(_lib.lib(), "qln_tracking_rollout" + ("_model" if m else "") + op + ("_host" if host else ""))
 
-    def tracking_rollout_host(self, Zref, K=None, x0=None):
-        """The same with host arrays (synchronous): returns a (z_total,) numpy array (zeros past n_nlp)."""
-        Zref, K = self._host_Z(Zref, "Zref"), self._host_K(K)
-        if x0 is not None:
-            x0 = np.ascontiguousarray(np.broadcast_to(np.asarray(x0, dtype=np.float64), (self.B, n)))
-        out = np.zeros(self.dims.z_total)
-        _lib.check(_lib.lib().qln_tracking_rollout_host(self._h, Zref.ctypes.data, _host_ptr(K), _host_ptr(x0),
-                                                        out.ctypes.data))
-        return out
+    def _check_opt(self, t, total, name):
+        return None if t is None else self._check(t, total, name)
 
-    # -- reverse-mode derivative of the closed-loop roll-out ---------------------------------------
-    def _vjp_want(self, K, want):
-        want = ("Zref", "K", "x0") if want is None else tuple(want)
-        bad = set(want) - {"Zref", "K", "x0"}
-        if bad:
-            raise ValueError(f"want: unknown outputs {sorted(bad)} (Zref, K, x0)")
-        if want == ("Zref", "K", "x0") and K is None:
-            want = ("Zref", "x0")  # the default asks for K_bar only where there are gains
-        return want
-
-    def tracking_rollout_vjp(self, Zref, Zout, Zbar, K=None, want=None):
-        """Reverse sweep of tracking_rollout at the trajectory Zout (device tensors, layout of Z): the cotangent Zbar of
-        (Zout's states and applied controls) -> (Zref_bar, K_bar, x0_bar), each None unless named in want (default: all
-        three, K_bar only when K is given).  Zref_bar is laid out like Z (zeros past n_nlp on a fresh buffer), K_bar like K
-        (B, N-1, 4, 15), x0_bar (B, 15).  Stream-ordered; semantics in include/qln_evaluator.h."""
-        T = _torch()
-        want = self._vjp_want(K, want)
-        self._check(Zref, self.dims.z_total, "Zref")
-        self._check(Zout, self.dims.z_total, "Zout")
-        self._check(Zbar, self.dims.z_total, "Zbar")
-        kp = None if K is None else self._check(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
-        zb = self.new_Z() if "Zref" in want else None
-        kb = T.zeros(tracking_k_shape(self.B, self.N), dtype=T.float64, device=self._dev()) if "K" in want else None
-        xb = T.zeros((self.B, n), dtype=T.float64, device=self._dev()) if "x0" in want else None
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        _lib.check(_lib.lib().qln_tracking_rollout_vjp(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), Zbar.data_ptr(),
-                                                       ptr(zb), ptr(kb), ptr(xb)))
-        return zb, kb, xb
-
-    def tracking_rollout_vjp_host(self, Zref, Zout, Zbar, K=None, want=None):
-        """The same with host arrays (synchronous): numpy (Zref_bar (z_total,), K_bar (B, N-1, 4, 15), x0_bar (B, 15))."""
-        want = self._vjp_want(K, want)
-        Zref, Zout, Zbar = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout"), self._host_Z(Zbar, "Zbar")
-        K = self._host_K(K)
-        zb = np.zeros(self.dims.z_total) if "Zref" in want else None
-        kb = np.zeros(tracking_k_shape(self.B, self.N)) if "K" in want else None
-        xb = np.zeros((self.B, n)) if "x0" in want else None
-        _lib.check(_lib.lib().qln_tracking_rollout_vjp_host(self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data,
-                                                            Zbar.ctypes.data, _host_ptr(zb), _host_ptr(kb), _host_ptr(xb)))
-        return zb, kb, xb
-
-    # -- forward-mode derivative of the closed-loop roll-out ---------------------------------------
-    def tracking_rollout_jvp(self, Zref, Zout, K=None, Zref_dot=None, K_dot=None, x0_dot=None, out=None):
-        """Forward sweep of tracking_rollout at the trajectory Zout (device tensors): the tangents Zref_dot (layout of Z),
-        K_dot (B, N-1, 4, 15) and x0_dot (B, 15) -- each None for zero, at least one given, K_dot only with K -- to the
-        tangent Zout_dot of Zout's states and applied controls, in the layout of Z (zeros past n_nlp on a fresh buffer; out
-        must overlap no input).  Stream-ordered; semantics in include/qln_evaluator.h."""
-        nk = self.B * (self.N - 1) * _lib.TRACK_NU * n
-        self._check(Zref, self.dims.z_total, "Zref")
-        self._check(Zout, self.dims.z_total, "Zout")
-        kp = None if K is None else self._check(K, nk, "K")
-        zd = None if Zref_dot is None else self._check(Zref_dot, self.dims.z_total, "Zref_dot")
-        kd = None if K_dot is None else self._check(K_dot, nk, "K_dot")
-        xd = None if x0_dot is None else self._check(x0_dot, self.B * n, "x0_dot")
-        out = self.new_Z() if out is None else out
-        self._check(out, self.dims.z_total, "out")
-        _lib.check(_lib.lib().qln_tracking_rollout_jvp(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), zd, kd, xd,
-                                                       out.data_ptr()))
-        return out
-
-    def tracking_rollout_jvp_host(self, Zref, Zout, K=None, Zref_dot=None, K_dot=None, x0_dot=None):
-        """The same with host arrays (synchronous): returns a (z_total,) numpy array (zeros past n_nlp)."""
-        Zref, Zout = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout")
-        K, K_dot = self._host_K(K), self._host_K(K_dot)
-        if Zref_dot is not None:
-            Zref_dot = self._host_Z(Zref_dot, "Zref_dot")
-        if x0_dot is not None:
-            x0_dot = np.ascontiguousarray(np.broadcast_to(np.asarray(x0_dot, dtype=np.float64), (self.B, n)))
-        out = np.zeros(self.dims.z_total)
-        _lib.check(_lib.lib().qln_tracking_rollout_jvp_host(self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data,
-                                                            _host_ptr(Zref_dot), _host_ptr(K_dot), _host_ptr(x0_dot),
-                                                            out.ctypes.data))
-        return out
-
-    # -- the roll-out and its sweeps with a per-problem plant model --------------------------------
-    def plant_models(self, models=None):
-        """(B, 4) float64 device tensor of per-problem plant models (g, mb, mf, lb): a PlanarQuadruped tiled over the batch
-        (None: the handle's own model), or a sequence of B of them."""
-        from .planar_quadruped import plant_models
-
-        return _torch().from_numpy(plant_models(self.model if models is None else models, self.B)).to(self._dev())
+    def _host_x0(self, x0):
+        if x0 is None:
+            return None
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(x0, dtype=np.float64), (self.B, n)))
 
     def _host_model(self, m, name="model"):
         if m is None:
@@ -700,107 +610,166 @@ class HybridNLP:
             raise ValueError(f"{name} has {m.size} entries, expected {self.B * _lib.MODEL_NP}")
         return m
 
-    def _model_vjp_want(self, K, want):
-        want = ("Zref", "K", "x0", "model") if want is None else tuple(want)
-        bad = set(want) - {"Zref", "K", "x0", "model"}
+    def _vjp_want(self, K, want, names):
+        want = names if want is None else tuple(want)
+        bad = set(want) - set(names)
         if bad:
-            raise ValueError(f"want: unknown outputs {sorted(bad)} (Zref, K, x0, model)")
-        if want == ("Zref", "K", "x0", "model") and K is None:
-            want = ("Zref", "x0", "model")  # the default asks for K_bar only where there are gains
+            raise ValueError(f"want: unknown outputs {sorted(bad)} ({', '.join(names)})")
+        if want == names and K is None:
+            want = tuple(w for w in names if w != "K")  # the default asks for K_bar only where there are gains
         return want
 
-    def tracking_rollout_model(self, Zref, K=None, x0=None, model=None, out=None):
-        """tracking_rollout with a per-problem PLANT: model is a (B, 4) float64 device tensor of (g, mb, mf, lb) rows
-        (plant_models; None: the handle's model, then bit for bit tracking_rollout).  The gains and the references stay
-        what they are: only the dynamics that are rolled out read the problem's model (qln_evaluator.h)."""
+    def _rollout(self, m, Zref, K, x0, model, out):
         self._check(Zref, self.dims.z_total, "Zref")
         out = self.new_Z() if out is None else out
         self._check(out, self.dims.z_total, "out")
-        kp = None if K is None else self._check(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
-        xp = None if x0 is None else self._check(x0, self.B * n, "x0")
-        mp = None if model is None else self._check(model, self.B * _lib.MODEL_NP, "model")
-        _lib.check(_lib.lib().qln_tracking_rollout_model(self._h, Zref.data_ptr(), kp, xp, mp, out.data_ptr()))
+        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        xp = self._check_opt(x0, self.B * n, "x0")
+        mp = (self._check_opt(model, self.B * _lib.MODEL_NP, "model"),) if m else ()
+        _lib.check(self._rollout_fn("", m, False)(self._h, Zref.data_ptr(), kp, xp, *mp, out.data_ptr()))
         return out
 
-    def tracking_rollout_model_host(self, Zref, K=None, x0=None, model=None):
-        """The same with host arrays (synchronous): returns a (z_total,) numpy array (zeros past n_nlp).  A non-finite
-        model entry, or mb, mf or lb <= 0, is refused."""
-        Zref, K, model = self._host_Z(Zref, "Zref"), self._host_K(K), self._host_model(model)
-        if x0 is not None:
-            x0 = np.ascontiguousarray(np.broadcast_to(np.asarray(x0, dtype=np.float64), (self.B, n)))
+    def _rollout_host(self, m, Zref, K, x0, model):
+        Zref, K, x0 = self._host_Z(Zref, "Zref"), self._host_K(K), self._host_x0(x0)
+        mp = (_host_ptr(self._host_model(model)),) if m else ()
         out = np.zeros(self.dims.z_total)
-        _lib.check(_lib.lib().qln_tracking_rollout_model_host(self._h, Zref.ctypes.data, _host_ptr(K), _host_ptr(x0),
-                                                              _host_ptr(model), out.ctypes.data))
+        _lib.check(self._rollout_fn("", m, True)(self._h, Zref.ctypes.data, _host_ptr(K), _host_ptr(x0), *mp, out.ctypes.data))
         return out
 
-    def tracking_rollout_model_vjp(self, Zref, Zout, Zbar, K=None, model=None, want=None):
-        """Reverse sweep of tracking_rollout_model at the trajectory Zout: tracking_rollout_vjp with the blocks at each
-        problem's model, and a fourth output model_bar (B, 4), the cotangent of `model`.  Returns (Zref_bar, K_bar, x0_bar,
-        model_bar), each None unless named in want (default: all, K_bar only when K is given)."""
+    def _rollout_vjp(self, m, Zref, Zout, Zbar, K, model, want):
         T = _torch()
-        want = self._model_vjp_want(K, want)
+        want = self._vjp_want(K, want, ("Zref", "K", "x0", "model") if m else ("Zref", "K", "x0"))
         self._check(Zref, self.dims.z_total, "Zref")
         self._check(Zout, self.dims.z_total, "Zout")
         self._check(Zbar, self.dims.z_total, "Zbar")
-        kp = None if K is None else self._check(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
-        mp = None if model is None else self._check(model, self.B * _lib.MODEL_NP, "model")
+        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
         zb = self.new_Z() if "Zref" in want else None
         kb = T.zeros(tracking_k_shape(self.B, self.N), dtype=T.float64, device=self._dev()) if "K" in want else None
         xb = T.zeros((self.B, n), dtype=T.float64, device=self._dev()) if "x0" in want else None
         mb = T.zeros((self.B, _lib.MODEL_NP), dtype=T.float64, device=self._dev()) if "model" in want else None
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        _lib.check(_lib.lib().qln_tracking_rollout_model_vjp(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), mp, Zbar.data_ptr(),
-                                                             ptr(zb), ptr(kb), ptr(xb), ptr(mb)))
+        m_in, m_out = ((mp,), (ptr(mb),)) if m else ((), ())
+        _lib.check(self._rollout_fn("_vjp", m, False)(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), *m_in, Zbar.data_ptr(),
+                                                      ptr(zb), ptr(kb), ptr(xb), *m_out))
         return zb, kb, xb, mb
 
-    def tracking_rollout_model_vjp_host(self, Zref, Zout, Zbar, K=None, model=None, want=None):
-        """The same with host arrays (synchronous): numpy (Zref_bar, K_bar, x0_bar, model_bar (B, 4))."""
-        want = self._model_vjp_want(K, want)
+    def _rollout_vjp_host(self, m, Zref, Zout, Zbar, K, model, want):
+        want = self._vjp_want(K, want, ("Zref", "K", "x0", "model") if m else ("Zref", "K", "x0"))
         Zref, Zout, Zbar = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout"), self._host_Z(Zbar, "Zbar")
         K, model = self._host_K(K), self._host_model(model)
         zb = np.zeros(self.dims.z_total) if "Zref" in want else None
         kb = np.zeros(tracking_k_shape(self.B, self.N)) if "K" in want else None
         xb = np.zeros((self.B, n)) if "x0" in want else None
         mb = np.zeros((self.B, _lib.MODEL_NP)) if "model" in want else None
-        _lib.check(_lib.lib().qln_tracking_rollout_model_vjp_host(
-            self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data, _host_ptr(model), Zbar.ctypes.data, _host_ptr(zb),
-            _host_ptr(kb), _host_ptr(xb), _host_ptr(mb)))
+        m_in, m_out = ((_host_ptr(model),), (_host_ptr(mb),)) if m else ((), ())
+        _lib.check(self._rollout_fn("_vjp", m, True)(self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data, *m_in,
+                                                     Zbar.ctypes.data, _host_ptr(zb), _host_ptr(kb), _host_ptr(xb), *m_out))
         return zb, kb, xb, mb
+
+    def _rollout_jvp(self, m, Zref, Zout, K, model, Zref_dot, K_dot, x0_dot, model_dot, out):
+        nk = self.B * (self.N - 1) * _lib.TRACK_NU * n
+        self._check(Zref, self.dims.z_total, "Zref")
+        self._check(Zout, self.dims.z_total, "Zout")
+        kp = self._check_opt(K, nk, "K")
+        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
+        zd = self._check_opt(Zref_dot, self.dims.z_total, "Zref_dot")
+        kd = self._check_opt(K_dot, nk, "K_dot")
+        xd = self._check_opt(x0_dot, self.B * n, "x0_dot")
+        md = self._check_opt(model_dot, self.B * _lib.MODEL_NP, "model_dot")
+        out = self.new_Z() if out is None else out
+        self._check(out, self.dims.z_total, "out")
+        m_in, m_dot = ((mp,), (md,)) if m else ((), ())
+        _lib.check(self._rollout_fn("_jvp", m, False)(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), *m_in, zd, kd, xd, *m_dot,
+                                                      out.data_ptr()))
+        return out
+
+    def _rollout_jvp_host(self, m, Zref, Zout, K, model, Zref_dot, K_dot, x0_dot, model_dot):
+        Zref, Zout = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout")
+        K, K_dot, x0_dot = self._host_K(K), self._host_K(K_dot), self._host_x0(x0_dot)
+        model, model_dot = self._host_model(model), self._host_model(model_dot, "model_dot")
+        if Zref_dot is not None:
+            Zref_dot = self._host_Z(Zref_dot, "Zref_dot")
+        out = np.zeros(self.dims.z_total)
+        m_in, m_dot = ((_host_ptr(model),), (_host_ptr(model_dot),)) if m else ((), ())
+        _lib.check(self._rollout_fn("_jvp", m, True)(self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data, *m_in,
+                                                     _host_ptr(Zref_dot), _host_ptr(K_dot), _host_ptr(x0_dot), *m_dot,
+                                                     out.ctypes.data))
+        return out
+
+    def tracking_rollout(self, Zref, K=None, x0=None, out=None):
+        """Closed-loop roll-out of the hybrid dynamics from x0 ((B, 15) device tensor, None: the handle's x0) with
+        F_k = F_ref,k - K_k (x_k - x_ref,k) and h_k = h_ref,k; K None is the open-loop roll-out.  Returns Zout in the
+        layout of Z (entries past n_nlp are not written).  out must not overlap Zref."""
+        return self._rollout(False, Zref, K, x0, None, out)
+
+    def tracking_rollout_host(self, Zref, K=None, x0=None):
+        """The same with host arrays (synchronous): returns a (z_total,) numpy array (zeros past n_nlp)."""
+        return self._rollout_host(False, Zref, K, x0, None)
+
+    # -- reverse-mode derivative of the closed-loop roll-out ---------------------------------------
+    def tracking_rollout_vjp(self, Zref, Zout, Zbar, K=None, want=None):
+        """Reverse sweep of tracking_rollout at the trajectory Zout (device tensors, layout of Z): the cotangent Zbar of
+        (Zout's states and applied controls) -> (Zref_bar, K_bar, x0_bar), each None unless named in want (default: all
+        three, K_bar only when K is given).  Zref_bar is laid out like Z (zeros past n_nlp on a fresh buffer), K_bar like K
+        (B, N-1, 4, 15), x0_bar (B, 15).  Stream-ordered; semantics in include/qln_evaluator.h."""
+        return self._rollout_vjp(False, Zref, Zout, Zbar, K, None, want)[:3]
+
+    def tracking_rollout_vjp_host(self, Zref, Zout, Zbar, K=None, want=None):
+        """The same with host arrays (synchronous): numpy (Zref_bar (z_total,), K_bar (B, N-1, 4, 15), x0_bar (B, 15))."""
+        return self._rollout_vjp_host(False, Zref, Zout, Zbar, K, None, want)[:3]
+
+    # -- forward-mode derivative of the closed-loop roll-out ---------------------------------------
+    def tracking_rollout_jvp(self, Zref, Zout, K=None, Zref_dot=None, K_dot=None, x0_dot=None, out=None):
+        """Forward sweep of tracking_rollout at the trajectory Zout (device tensors): the tangents Zref_dot (layout of Z),
+        K_dot (B, N-1, 4, 15) and x0_dot (B, 15) -- each None for zero, at least one given, K_dot only with K -- to the
+        tangent Zout_dot of Zout's states and applied controls, in the layout of Z (zeros past n_nlp on a fresh buffer; out
+        must overlap no input).  Stream-ordered; semantics in include/qln_evaluator.h."""
+        return self._rollout_jvp(False, Zref, Zout, K, None, Zref_dot, K_dot, x0_dot, None, out)
+
+    def tracking_rollout_jvp_host(self, Zref, Zout, K=None, Zref_dot=None, K_dot=None, x0_dot=None):
+        """The same with host arrays (synchronous): returns a (z_total,) numpy array (zeros past n_nlp)."""
+        return self._rollout_jvp_host(False, Zref, Zout, K, None, Zref_dot, K_dot, x0_dot, None)
+
+    # -- the roll-out and its sweeps with a per-problem plant model --------------------------------
+    def plant_models(self, models=None):
+        """(B, 4) float64 device tensor of per-problem plant models (g, mb, mf, lb): a PlanarQuadruped tiled over the batch
+        (None: the handle's own model), or a sequence of B of them."""
+        from .planar_quadruped import plant_models
+
+        return _torch().from_numpy(plant_models(self.model if models is None else models, self.B)).to(self._dev())
+
+    def tracking_rollout_model(self, Zref, K=None, x0=None, model=None, out=None):
+        """tracking_rollout with a per-problem PLANT: model is a (B, 4) float64 device tensor of (g, mb, mf, lb) rows
+        (plant_models; None: the handle's model, then bit for bit tracking_rollout).  The gains and the references stay
+        what they are: only the dynamics that are rolled out read the problem's model (qln_evaluator.h)."""
+        return self._rollout(True, Zref, K, x0, model, out)
+
+    def tracking_rollout_model_host(self, Zref, K=None, x0=None, model=None):
+        """The same with host arrays (synchronous): returns a (z_total,) numpy array (zeros past n_nlp).  A non-finite
+        model entry, or mb, mf or lb <= 0, is refused."""
+        return self._rollout_host(True, Zref, K, x0, model)
+
+    def tracking_rollout_model_vjp(self, Zref, Zout, Zbar, K=None, model=None, want=None):
+        """Reverse sweep of tracking_rollout_model at the trajectory Zout: tracking_rollout_vjp with the blocks at each
+        problem's model, and a fourth output model_bar (B, 4), the cotangent of `model`.  Returns (Zref_bar, K_bar, x0_bar,
+        model_bar), each None unless named in want (default: all, K_bar only when K is given)."""
+        return self._rollout_vjp(True, Zref, Zout, Zbar, K, model, want)
+
+    def tracking_rollout_model_vjp_host(self, Zref, Zout, Zbar, K=None, model=None, want=None):
+        """The same with host arrays (synchronous): numpy (Zref_bar, K_bar, x0_bar, model_bar (B, 4))."""
+        return self._rollout_vjp_host(True, Zref, Zout, Zbar, K, model, want)
 
     def tracking_rollout_model_jvp(self, Zref, Zout, K=None, model=None, Zref_dot=None, K_dot=None, x0_dot=None,
                                    model_dot=None, out=None):
         """Forward sweep of tracking_rollout_model at the trajectory Zout: tracking_rollout_jvp with the blocks at each
         problem's model and a fourth tangent model_dot (B, 4) -- each tangent None for zero, at least one given."""
-        nk = self.B * (self.N - 1) * _lib.TRACK_NU * n
-        self._check(Zref, self.dims.z_total, "Zref")
-        self._check(Zout, self.dims.z_total, "Zout")
-        kp = None if K is None else self._check(K, nk, "K")
-        mp = None if model is None else self._check(model, self.B * _lib.MODEL_NP, "model")
-        zd = None if Zref_dot is None else self._check(Zref_dot, self.dims.z_total, "Zref_dot")
-        kd = None if K_dot is None else self._check(K_dot, nk, "K_dot")
-        xd = None if x0_dot is None else self._check(x0_dot, self.B * n, "x0_dot")
-        md = None if model_dot is None else self._check(model_dot, self.B * _lib.MODEL_NP, "model_dot")
-        out = self.new_Z() if out is None else out
-        self._check(out, self.dims.z_total, "out")
-        _lib.check(_lib.lib().qln_tracking_rollout_model_jvp(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), mp, zd, kd, xd, md,
-                                                             out.data_ptr()))
-        return out
+        return self._rollout_jvp(True, Zref, Zout, K, model, Zref_dot, K_dot, x0_dot, model_dot, out)
 
     def tracking_rollout_model_jvp_host(self, Zref, Zout, K=None, model=None, Zref_dot=None, K_dot=None, x0_dot=None,
                                         model_dot=None):
         """The same with host arrays (synchronous): returns a (z_total,) numpy array (zeros past n_nlp)."""
-        Zref, Zout = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout")
-        K, K_dot = self._host_K(K), self._host_K(K_dot)
-        model, model_dot = self._host_model(model), self._host_model(model_dot, "model_dot")
-        if Zref_dot is not None:
-            Zref_dot = self._host_Z(Zref_dot, "Zref_dot")
-        if x0_dot is not None:
-            x0_dot = np.ascontiguousarray(np.broadcast_to(np.asarray(x0_dot, dtype=np.float64), (self.B, n)))
-        out = np.zeros(self.dims.z_total)
-        _lib.check(_lib.lib().qln_tracking_rollout_model_jvp_host(
-            self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data, _host_ptr(model), _host_ptr(Zref_dot), _host_ptr(K_dot),
-            _host_ptr(x0_dot), _host_ptr(model_dot), out.ctypes.data))
-        return out
+        return self._rollout_jvp_host(True, Zref, Zout, K, model, Zref_dot, K_dot, x0_dot, model_dot)
 
     # -- covariance propagation through the closed-loop roll-out -----------------------------------
     def tracking_covariance(self, Zout, K=None, Sigma0=None, W=None, with_sigma=True, with_marginals=True, Sigma=None,

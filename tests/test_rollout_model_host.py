@@ -139,6 +139,17 @@ def test_entry_points_reject_bad_arguments_without_a_device():
         assert fn(None, p(z), None, p(z), p(m), p(z), None, p(k), None, p(m)) == _lib.QLN_ERR_INVALID_ARGUMENT
     for fn in (L.qln_tracking_rollout_model, L.qln_tracking_rollout_model_host):
         assert fn(None, p(z), None, None, p(m), p(o)) == _lib.QLN_ERR_INVALID_ARGUMENT
+    # the forms without a model: the same refusals, with no model arguments to give
+    for fn in (L.qln_tracking_rollout_jvp, L.qln_tracking_rollout_jvp_host):
+        # all three tangents NULL; K_dot without K; a NULL Zout_dot; a NULL handle
+        assert fn(None, p(z), p(k), p(z), None, None, None, p(o)) == _lib.QLN_ERR_INVALID_ARGUMENT
+        assert fn(None, p(z), None, p(z), None, p(kd), None, p(o)) == _lib.QLN_ERR_INVALID_ARGUMENT
+        assert fn(None, p(z), p(k), p(z), None, None, p(x), None) == _lib.QLN_ERR_INVALID_ARGUMENT
+        assert fn(None, p(z), p(k), p(z), p(z), p(kd), p(x), p(o)) == _lib.QLN_ERR_INVALID_ARGUMENT
+    for fn in (L.qln_tracking_rollout_vjp, L.qln_tracking_rollout_vjp_host):
+        assert fn(None, p(z), None, p(z), p(z), None, p(k), None) == _lib.QLN_ERR_INVALID_ARGUMENT
+    for fn in (L.qln_tracking_rollout, L.qln_tracking_rollout_host):
+        assert fn(None, p(z), p(k), p(x), p(o)) == _lib.QLN_ERR_INVALID_ARGUMENT
 
 
 def test_ctypes_table_and_helper():
