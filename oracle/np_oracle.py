@@ -20,7 +20,7 @@ IB = MB * LB**2 / 12
 def model(g, mb, mf, lb):
     """Evaluate with another robot model inside the `with` block: G, MB, MF, LB and IB are set to the given values and
     put back on exit, also when the block raises.  Everything below reads them at call time, so callers of this module
-    (tests/rollout_vjp_ref.py, tests/hessian_sym.py, ...) follow without a parameter of their own.  Not thread-safe."""
+    (tests/rollout_ref.py, tests/hessian_sym.py, ...) follow without a parameter of their own.  Not thread-safe."""
     global G, MB, MF, LB, IB
     saved = (G, MB, MF, LB, IB)
     G, MB, MF, LB = float(g), float(mb), float(mf), float(lb)

@@ -11,8 +11,7 @@ from quadruped_landing_amd.planar_quadruped import PlanarQuadruped
 from quadruped_landing_amd.quadratic_cost import lqr_objective
 from quadruped_landing_amd.ref_traj import reference_trajectory
 from tests import ilqr_ref as IR
-
-SECOND_MODEL = PlanarQuadruped(g=-9.1, mb=8.7, mf=0.13, lb=0.46, l1=0.27, l2=0.22)  # tests/test_gpu_model.py's
+from tests.tracking_cases import SECOND_MODEL  # noqa: F401  (the cases' users take it from here)
 
 ONE = IR.Options(max_outer=1, max_inner=1)
 TWELVE = IR.Options(max_outer=4, max_inner=3)

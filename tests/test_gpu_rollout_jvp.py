@@ -5,65 +5,36 @@ covariance sweep, torch forward-mode AD, and the call's contract."""
 import numpy as np
 import pytest
 
-from tests import rollout_jvp_ref as RJ
-from tests import rollout_vjp_ref as RV
-from tests.test_gpu_rollout_vjp import _cs_blocks, _evaluator_blocks, _gains, _inputs
-from tests.test_gpu_tracking import SHAPES, _batch, _dense_blocks, _nlp
+from tests import rollout_ref as RR
+from tests import tracking_cases as TC
+from tests.tracking_cases import SHAPES
 
 pytestmark = pytest.mark.gpu
-
-
-def _tangents(nlp, seed, with_gains, scale=(1.0, 1.0, 1.0)):
-    """Random tangents of Zref (zero past n_nlp), K (None without gains) and x0, as device tensors."""
-    import torch
-
-    rng = np.random.default_rng(seed)
-    zd = nlp.upload_Z(scale[0] * rng.normal(size=(nlp.B, nlp.n_nlp)))
-    kd = torch.from_numpy(scale[1] * rng.normal(size=(nlp.B, nlp.N - 1, 4, 15))).cuda() if with_gains else None
-    xd = torch.from_numpy(scale[2] * rng.normal(size=(nlp.B, 15))).cuda()
-    return zd, kd, xd
-
-
-def _rows(nlp, t):
-    return t.view(nlp.B, -1)[:, :nlp.n_nlp].cpu().numpy()
-
-
-def _per_problem(nlp, Zref, K, Zout, zd, kd, xd, got, blocks):
-    """worst per-problem relative norm of Zout_dot against the numpy sweep on blocks(b, Zout_b)"""
-    zr, zo, g = _rows(nlp, Zref), _rows(nlp, Zout), _rows(nlp, got)
-    zdh = None if zd is None else _rows(nlp, zd)
-    Kh, kdh, xdh = (None if t is None else t.cpu().numpy() for t in (K, kd, xd))
-    worst = 0.0
-    for b in range(nlp.B):
-        ref = RJ.sweep(blocks(b, zo[b]), zr[b], None if Kh is None else Kh[b], zo[b], None if zdh is None else zdh[b],
-                       None if kdh is None else kdh[b], None if xdh is None else xdh[b])
-        worst = max(worst, RV.rel(g[b], ref))
-    return worst
 
 
 @pytest.mark.parametrize("B,N,k_trans,init_mode", SHAPES)
 @pytest.mark.parametrize("with_gains", [False, True])
 def test_matches_numpy_sweep_over_shapes(B, N, k_trans, init_mode, with_gains):
-    batch = _batch(B, N, k_trans, init_mode, seed=N + k_trans)
-    nlp = _nlp(batch)
-    Zref, K, x0, Zout, _ = _inputs(nlp, batch, N + 3 * k_trans, with_gains)
-    zd, kd, xd = _tangents(nlp, N + 5 * k_trans, with_gains)
+    batch = TC.batch(B, N, k_trans, init_mode, seed=N + k_trans)
+    nlp = TC.nlp(batch)
+    Zref, K, x0, Zout, _ = TC.inputs(nlp, batch, N + 3 * k_trans, with_gains)
+    zd, kd, xd = TC.tangents(nlp, N + 5 * k_trans, with_gains)
     got = nlp.tracking_rollout_jvp(Zref, Zout, K, zd, kd, xd)
-    ev = _per_problem(nlp, Zref, K, Zout, zd, kd, xd, got, _evaluator_blocks(nlp, Zout))
-    cs = _per_problem(nlp, Zref, K, Zout, zd, kd, xd, got, _cs_blocks(nlp))
+    ev = TC.jvp_per_problem(nlp, Zref, K, Zout, zd, kd, xd, got, TC.evaluator_blocks(nlp, Zout))
+    cs = TC.jvp_per_problem(nlp, Zref, K, Zout, zd, kd, xd, got, TC.cs_blocks(nlp))
     print(f"B={B} N={N} k_trans={k_trans} mode={init_mode} K={with_gains}: evaluator blocks {ev:.2e}, complex step {cs:.2e}")
     assert ev <= 1e-12 and cs <= 1e-8, (ev, cs)
 
 
 @pytest.mark.parametrize("with_gains", [False, True])
 def test_ragged_batch_and_padded_layout(with_gains):
-    for batch, kw in ((_batch(37, 12, 5, 1, seed=3, ragged=True), {}),
-                      (_batch(13, 12, 7, 2, seed=4), {"z_stride": 20 * 12 + 3, "align": 7})):
-        nlp = _nlp(batch, **kw)
-        Zref, K, x0, Zout, _ = _inputs(nlp, batch, 5, with_gains)
-        zd, kd, xd = _tangents(nlp, 6, with_gains)
+    for batch, kw in ((TC.batch(37, 12, 5, 1, seed=3, ragged=True), {}),
+                      (TC.batch(13, 12, 7, 2, seed=4), {"z_stride": 20 * 12 + 3, "align": 7})):
+        nlp = TC.nlp(batch, **kw)
+        Zref, K, x0, Zout, _ = TC.inputs(nlp, batch, 5, with_gains)
+        zd, kd, xd = TC.tangents(nlp, 6, with_gains)
         got = nlp.tracking_rollout_jvp(Zref, Zout, K, zd, kd, xd)
-        ev = _per_problem(nlp, Zref, K, Zout, zd, kd, xd, got, _evaluator_blocks(nlp, Zout))
+        ev = TC.jvp_per_problem(nlp, Zref, K, Zout, zd, kd, xd, got, TC.evaluator_blocks(nlp, Zout))
         print(f"ragged / padded, K={with_gains}: {ev:.2e}")
         assert ev <= 1e-12, ev
 
@@ -79,16 +50,16 @@ def test_full_size_every_problem(B, N, ragged):
         sub = PG.LandingBatch(full.model, N, full.k_trans[s:s + chunk], full.init_mode[s:s + chunk], full.x0[s:s + chunk],
                               full.xf[s:s + chunk], full.obj if full.obj.ndim == 2 else full.obj[s:s + chunk],
                               full.Z[s:s + chunk])
-        nlp = _nlp(sub)
-        Zref, K, x0, Zout, _ = _inputs(nlp, sub, s, True)
-        zd, kd, xd = _tangents(nlp, s + 1, True)
-        got = _rows(nlp, nlp.tracking_rollout_jvp(Zref, Zout, K, zd, kd, xd))
-        dense = _dense_blocks(nlp, Zout)
+        nlp = TC.nlp(sub)
+        Zref, K, x0, Zout, _ = TC.inputs(nlp, sub, s, True)
+        zd, kd, xd = TC.tangents(nlp, s + 1, True)
+        got = TC.rows(nlp, nlp.tracking_rollout_jvp(Zref, Zout, K, zd, kd, xd))
+        dense = TC.dense_blocks(nlp, Zout)
         F = dense.copy()
         kj = nlp.k_trans.astype(int) - 2
         for b in np.nonzero((kj >= 0) & (kj < N - 1))[0]:
-            F[b] = RV.evaluator_blocks(dense[b], nlp.k_trans[b])
-        ref = RJ.sweep_batch(F, _rows(nlp, Zref), K.cpu().numpy(), _rows(nlp, Zout), _rows(nlp, zd), kd.cpu().numpy(),
+            F[b] = RR.evaluator_blocks(dense[b], nlp.k_trans[b])
+        ref = RR.sweep_jvp(F, TC.rows(nlp, Zref), K.cpu().numpy(), TC.rows(nlp, Zout), TC.rows(nlp, zd), kd.cpu().numpy(),
                              xd.cpu().numpy())
         e = np.linalg.norm(got - ref, axis=1) / np.maximum(np.linalg.norm(ref, axis=1), 1e-300)
         worst = max(worst, float(e.max()))
@@ -103,10 +74,10 @@ def test_adjoint_identity_with_the_shipped_vjp(B, N, k_trans, init_mode, with_ga
     """<Zbar, J d> = <J' Zbar, d> between the two kernels: no oracle involved."""
     import torch
 
-    batch = _batch(B, N, k_trans, init_mode, seed=N + k_trans)
-    nlp = _nlp(batch)
-    Zref, K, x0, Zout, Zbar = _inputs(nlp, batch, N + 3 * k_trans, with_gains)
-    zd, kd, xd = _tangents(nlp, N + 7 * k_trans, with_gains)
+    batch = TC.batch(B, N, k_trans, init_mode, seed=N + k_trans)
+    nlp = TC.nlp(batch)
+    Zref, K, x0, Zout, Zbar = TC.inputs(nlp, batch, N + 3 * k_trans, with_gains)
+    zd, kd, xd = TC.tangents(nlp, N + 7 * k_trans, with_gains)
     got = nlp.tracking_rollout_jvp(Zref, Zout, K, zd, kd, xd)
     zb, kb, xb = nlp.tracking_rollout_vjp(Zref, Zout, Zbar, K)
     lhs = float(torch.dot(Zbar, got))
@@ -121,28 +92,28 @@ def test_adjoint_identity_with_the_shipped_vjp(B, N, k_trans, init_mode, with_ga
 def test_central_differences_of_the_gpu_rollout_entry_by_entry():
     """(rollout(p + eps d) - rollout(p - eps d)) / (2 eps) against Zout_dot, per-problem relative norm, on the VJP test's
     batch, direction scalings and eps.  The bar is ten times what the same difference quotient of the numpy roll-out
-    (RV.rollout) leaves against the numpy sweep for the same inputs: the error of the quotient itself."""
-    batch = _batch(8, 40, 14, 1, seed=21)
-    nlp = _nlp(batch)
-    Zref, K, x0, Zout, _ = _inputs(nlp, batch, 21, True)
-    zr, Kh, x0h = _rows(nlp, Zref), K.cpu().numpy(), x0.cpu().numpy()
+    (rollout_ref.rollout) leaves against the numpy sweep for the same inputs: the error of the quotient itself."""
+    batch = TC.batch(8, 40, 14, 1, seed=21)
+    nlp = TC.nlp(batch)
+    Zref, K, x0, Zout, _ = TC.inputs(nlp, batch, 21, True)
+    zr, Kh, x0h = TC.rows(nlp, Zref), K.cpu().numpy(), x0.cpu().numpy()
     eps = 1e-4
     N = nlp.N
     worst_gpu = worst_cpu = 0.0
     for t in range(3):
-        zd, kd, xd = _tangents(nlp, 22 + t, True, scale=(1e-3, 1e-2, 1e-3))
-        got = _rows(nlp, nlp.tracking_rollout_jvp(Zref, Zout, K, zd, kd, xd))
-        plus = _rows(nlp, nlp.tracking_rollout(Zref + eps * zd, K + eps * kd, x0 + eps * xd))
-        minus = _rows(nlp, nlp.tracking_rollout(Zref - eps * zd, K - eps * kd, x0 - eps * xd))
+        zd, kd, xd = TC.tangents(nlp, 22 + t, True, scale=(1e-3, 1e-2, 1e-3))
+        got = TC.rows(nlp, nlp.tracking_rollout_jvp(Zref, Zout, K, zd, kd, xd))
+        plus = TC.rows(nlp, nlp.tracking_rollout(Zref + eps * zd, K + eps * kd, x0 + eps * xd))
+        minus = TC.rows(nlp, nlp.tracking_rollout(Zref - eps * zd, K - eps * kd, x0 - eps * xd))
         fd = (plus - minus) / (2 * eps)
-        zdh, kdh, xdh = _rows(nlp, zd), kd.cpu().numpy(), xd.cpu().numpy()
+        zdh, kdh, xdh = TC.rows(nlp, zd), kd.cpu().numpy(), xd.cpu().numpy()
         for b in range(nlp.B):
-            worst_gpu = max(worst_gpu, RV.rel(fd[b], got[b]))
+            worst_gpu = max(worst_gpu, RR.rel(fd[b], got[b]))
             kt, im = int(nlp.k_trans[b]), int(nlp.init_mode[b])
-            roll = lambda s: RV.rollout(N, kt, im, zr[b] + s * zdh[b], Kh[b] + s * kdh[b], x0h[b] + s * xdh[b])  # noqa: E731
+            roll = lambda s: RR.rollout(N, kt, im, zr[b] + s * zdh[b], Kh[b] + s * kdh[b], x0h[b] + s * xdh[b])  # noqa: E731
             zo = roll(0.0)
-            ref = RJ.sweep(RV.complex_step_blocks(N, kt, im, zo), zr[b], Kh[b], zo, zdh[b], kdh[b], xdh[b])
-            worst_cpu = max(worst_cpu, RV.rel((roll(eps) - roll(-eps)) / (2 * eps), ref))
+            ref = RR.sweep_jvp(RR.complex_step_blocks(N, kt, im, zo), zr[b], Kh[b], zo, zdh[b], kdh[b], xdh[b])
+            worst_cpu = max(worst_cpu, RR.rel((roll(eps) - roll(-eps)) / (2 * eps), ref))
     bar = 10.0 * worst_cpu
     print(f"central differences, eps {eps:g}: GPU quotient against Zout_dot {worst_gpu:.2e}; numpy quotient against the numpy "
           f"sweep {worst_cpu:.2e}; bar {bar:.2e}")
@@ -155,15 +126,15 @@ def test_duality_with_the_covariance_sweep():
 
     from quadruped_landing_amd import nlp as NL
 
-    batch = _batch(9, 40, 14, 1, seed=61)
-    nlp = _nlp(batch)
-    Zref, K, _, Zout, _ = _inputs(nlp, batch, 61, True)
+    batch = TC.batch(9, 40, 14, 1, seed=61)
+    nlp = TC.nlp(batch)
+    Zref, K, _, Zout, _ = TC.inputs(nlp, batch, 61, True)
     rng = np.random.default_rng(63)
     G = rng.normal(size=(nlp.B, 15, 15)) / 4.0
     S0 = np.einsum("bij,bkj->bik", G, G)
     S, _ = nlp.tracking_covariance(Zout, K, S0)
     Sg = NL.unpack_covariance(S)
-    cols = [_rows(nlp, nlp.tracking_rollout_jvp(Zref, Zout, K, x0_dot=torch.from_numpy(np.ascontiguousarray(G[:, :, i])).cuda()))
+    cols = [TC.rows(nlp, nlp.tracking_rollout_jvp(Zref, Zout, K, x0_dot=torch.from_numpy(np.ascontiguousarray(G[:, :, i])).cuda()))
             for i in range(15)]
     worst = 0.0
     for k in (5, 20, nlp.N - 1):  # before the jump knot (12), after it, and the end
@@ -178,16 +149,16 @@ def test_duality_with_the_covariance_sweep():
 def test_forward_mode_autograd():
     import torch
 
-    batch = _batch(2, 6, 4, 1, seed=31)
-    nlp = _nlp(batch)
+    batch = TC.batch(2, 6, 4, 1, seed=31)
+    nlp = TC.nlp(batch)
     Zref = nlp.upload_Z(batch.Z).requires_grad_(True)
-    K = _gains(nlp, 32, scale=0.02).requires_grad_(True)
+    K = TC.gains(nlp, 32, scale=0.02).requires_grad_(True)
     x0 = torch.from_numpy(batch.Z[:, :15].copy()).cuda().requires_grad_(True)
     assert torch.autograd.gradcheck(lambda z, k, x: nlp.differentiable_rollout(z, k, x), (Zref, K, x0), eps=1e-6,
                                     atol=1e-7, rtol=1e-6, check_forward_ad=True)
     # torch.func.jvp is the direct call, bit for bit
     z, k, x = Zref.detach(), K.detach(), x0.detach()
-    zd, kd, xd = _tangents(nlp, 33, True)
+    zd, kd, xd = TC.tangents(nlp, 33, True)
     out, tangent = torch.func.jvp(lambda a, b_, c: nlp.differentiable_rollout(a, b_, c), (z, k, x), (zd, kd, xd))
     Zout = nlp.tracking_rollout(z, k, x)
     assert torch.equal(out, Zout) and torch.equal(tangent, nlp.tracking_rollout_jvp(z, Zout, k, zd, kd, xd))
@@ -214,10 +185,10 @@ def test_contract_sentinels_linearity_null_tangents_refusals_and_host_forms(B):
     from quadruped_landing_amd import _lib
 
     N = 12
-    batch = _batch(B, N, 5, 2, seed=51)
-    nlp = _nlp(batch, z_stride=20 * N + 3)
-    Zref, K, x0, Zout, _ = _inputs(nlp, batch, 51, True)
-    zd, kd, xd = _tangents(nlp, 52, True)
+    batch = TC.batch(B, N, 5, 2, seed=51)
+    nlp = TC.nlp(batch, z_stride=20 * N + 3)
+    Zref, K, x0, Zout, _ = TC.inputs(nlp, batch, 51, True)
+    zd, kd, xd = TC.tangents(nlp, 52, True)
     L = _lib.lib()
     n, zs = nlp.n_nlp, nlp.z_stride
     got = nlp.tracking_rollout_jvp(Zref, Zout, K, zd, kd, xd)
@@ -234,7 +205,7 @@ def test_contract_sentinels_linearity_null_tangents_refusals_and_host_forms(B):
     nan_z = torch.full_like(Zref, float("nan"))
     assert torch.equal(nlp.tracking_rollout_jvp(nan_z, Zout, K, zd, None, xd), nlp.tracking_rollout_jvp(Zref, Zout, K, zd, None, xd))
     # linearity in the tangent
-    zd2, kd2, xd2 = _tangents(nlp, 53, True)
+    zd2, kd2, xd2 = TC.tangents(nlp, 53, True)
     got2 = nlp.tracking_rollout_jvp(Zref, Zout, K, zd2, kd2, xd2)
     got3 = nlp.tracking_rollout_jvp(Zref, Zout, K, 2.0 * zd - 3.0 * zd2, 2.0 * kd - 3.0 * kd2, 2.0 * xd - 3.0 * xd2)
     ref = 2.0 * got - 3.0 * got2

@@ -1,16 +1,15 @@
 """GPU checks of qln_tracking_rollout_model and its two sweeps (the closed-loop roll-out with a per-problem plant model):
 the forward call bit for bit against handles created with the models; both sweeps against the numpy sweeps on complex-step
-blocks [A B G] and against a complex step of the whole numpy roll-out (tests/rollout_model_ref.py); the adjoint identity
+blocks [A B G] and against a complex step of the whole numpy roll-out (tests/rollout_ref.py); the adjoint identity
 between the two kernels; central differences of the GPU roll-out in the model; the reduction to the calls without a model;
 per-problem indexing; the contract; torch autograd in the model; full size; and examples/identify_model.py.  Per-problem
-models are drawn +-10 % around the second model of tests/test_gpu_model.py, never the default."""
+models are drawn +-10 % around the second model (tests/tracking_cases.py), never the default."""
 import numpy as np
 import pytest
 
-from tests import rollout_model_ref as MR
-from tests.test_gpu_model import SECOND_MODEL
-from tests.test_gpu_rollout_vjp import _gains
-from tests.test_gpu_tracking import SHAPES, _batch
+from tests import rollout_ref as RR
+from tests import tracking_cases as TC
+from tests.tracking_cases import SECOND_MODEL, SHAPES
 
 pytestmark = pytest.mark.gpu
 
@@ -19,59 +18,30 @@ BAR = 1e-8  # the project's bar for comparisons against a complex step
 
 def _nlp(batch, model=SECOND_MODEL, **kw):
     """The handle's (design) model is the second model unless a test says otherwise."""
-    from quadruped_landing_amd import HybridNLP
-
-    return HybridNLP(model, batch.obj, batch.init_mode, batch.k_trans, batch.N, batch.x0, batch.xf, **kw)
+    return TC.nlp(batch, model, **kw)
 
 
 def _models(nlp, seed):
     import torch
 
-    return torch.from_numpy(MR.draw_models(nlp.B, seed)).cuda()
+    return torch.from_numpy(RR.draw_models(nlp.B, seed, TC.SECOND)).cuda()
 
 
 def _inputs(nlp, batch, seed, with_gains):
     """A reference, gains (or None), x0 near the reference's x_0, per-problem models, the GPU roll-out and a cotangent."""
-    import torch
-
-    rng = np.random.default_rng(seed)
-    Zref = nlp.upload_Z(batch.Z)
-    K = _gains(nlp, seed + 1) if with_gains else None
-    x0 = torch.from_numpy(batch.Z[:, :15] + 1e-2 * rng.normal(size=(nlp.B, 15))).cuda()
     model = _models(nlp, seed + 2)
-    Zout = nlp.tracking_rollout_model(Zref, K, x0, model)
-    Zbar = nlp.upload_Z(rng.normal(size=(nlp.B, nlp.n_nlp)))
+    Zref, K, x0, Zout, Zbar = TC.inputs(nlp, batch, seed, with_gains, model)
     return Zref, K, x0, model, Zout, Zbar
-
-
-def _tangents(nlp, model, seed, with_gains, scale=(1.0, 1.0, 1.0, 1.0)):
-    """Random tangents of Zref, K (None without gains), x0 and the model (relative to each parameter's size)."""
-    import torch
-
-    rng = np.random.default_rng(seed)
-    zd = nlp.upload_Z(scale[0] * rng.normal(size=(nlp.B, nlp.n_nlp)))
-    kd = torch.from_numpy(scale[1] * rng.normal(size=(nlp.B, nlp.N - 1, 4, 15))).cuda() if with_gains else None
-    xd = torch.from_numpy(scale[2] * rng.normal(size=(nlp.B, 15))).cuda()
-    md = model * torch.from_numpy(scale[3] * rng.normal(size=(nlp.B, 4))).cuda()
-    return zd, kd, xd, md
-
-
-def _rows(nlp, t):
-    return t.view(nlp.B, -1)[:, :nlp.n_nlp].cpu().numpy()
-
-
-def _np(t):
-    return None if t is None else t.cpu().numpy()
 
 
 def _blocks(nlp, Zout, model):
     """complex-step [A B G] of every problem at the GPU's Zout: (B, N-1, 15, 24).  One mode schedule per batch."""
     assert np.all(nlp.k_trans == nlp.k_trans[0]) and np.all(nlp.init_mode == nlp.init_mode[0])
-    return MR.complex_step_blocks(nlp.N, int(nlp.k_trans[0]), int(nlp.init_mode[0]), _rows(nlp, Zout), _np(model))
+    return RR.complex_step_blocks(nlp.N, int(nlp.k_trans[0]), int(nlp.init_mode[0]), TC.rows(nlp, Zout), TC.to_np(model))
 
 
 def _per_problem(got, ref):
-    return max(MR.rel(g, r) for g, r in zip(got, ref))
+    return max(RR.rel(g, r) for g, r in zip(got, ref))
 
 
 # ---- 1. forward, bitwise ------------------------------------------------------------------------------------------------
@@ -82,7 +52,7 @@ def test_forward_is_bitwise_the_rollout_of_handles_created_with_the_models(B, N,
 
     from quadruped_landing_amd import PlanarQuadruped
 
-    batch = _batch(B, N, k_trans, init_mode, seed=N + k_trans)
+    batch = TC.batch(B, N, k_trans, init_mode, seed=N + k_trans)
     other = PlanarQuadruped(g=-9.6, mb=9.3, mf=0.117, lb=0.43)
     nlp, nlp_a, nlp_b = _nlp(batch, PlanarQuadruped()), _nlp(batch, SECOND_MODEL), _nlp(batch, other)
     Zref, K, x0, _, _, _ = _inputs(nlp, batch, N + 3 * k_trans, with_gains)
@@ -103,8 +73,8 @@ def test_forward_ragged_batch_and_padded_layout():
     from quadruped_landing_amd import PlanarQuadruped
 
     other = PlanarQuadruped(g=-9.6, mb=9.3, mf=0.117, lb=0.43)
-    for batch, kw in ((_batch(37, 12, 5, 1, seed=3, ragged=True), {}),
-                      (_batch(13, 12, 7, 2, seed=4, ragged=True), {"z_stride": 20 * 12 + 3, "align": 7})):
+    for batch, kw in ((TC.batch(37, 12, 5, 1, seed=3, ragged=True), {}),
+                      (TC.batch(13, 12, 7, 2, seed=4, ragged=True), {"z_stride": 20 * 12 + 3, "align": 7})):
         nlp, nlp_a, nlp_b = _nlp(batch, PlanarQuadruped(), **kw), _nlp(batch, SECOND_MODEL, **kw), _nlp(batch, other, **kw)
         Zref, K, x0, _, _, _ = _inputs(nlp, batch, 5, True)
         B = nlp.B
@@ -121,18 +91,18 @@ def test_jvp_matches_complex_step_and_numpy_sweep(B, N, k_trans, init_mode, with
     """Per-problem relative norm against (a) the complex step of the whole numpy roll-out in the direction (Zref_dot, K_dot,
     x0_dot, model_dot) and (b) the numpy sweep on complex-step [A B G] at the GPU's Zout; also with model_dot alone.  The two
     references must agree ten times better than the bar for the comparison to mean anything."""
-    batch = _batch(B, N, k_trans, init_mode, seed=N + k_trans)
+    batch = TC.batch(B, N, k_trans, init_mode, seed=N + k_trans)
     nlp = _nlp(batch)
     Zref, K, x0, model, Zout, _ = _inputs(nlp, batch, N + 3 * k_trans, with_gains)
-    zd, kd, xd, md = _tangents(nlp, model, N + 5 * k_trans, with_gains)
+    zd, kd, xd, md = TC.tangents(nlp, N + 5 * k_trans, with_gains, model=model)
     F = _blocks(nlp, Zout, model)
-    zr, zo, Kh, x0h, th = _rows(nlp, Zref), _rows(nlp, Zout), _np(K), _np(x0), _np(model)
+    zr, zo, Kh, x0h, th = TC.rows(nlp, Zref), TC.rows(nlp, Zout), TC.to_np(K), TC.to_np(x0), TC.to_np(model)
     for dots in ((zd, kd, xd, md), (None, None, None, md)):
-        got = _rows(nlp, nlp.tracking_rollout_model_jvp(Zref, Zout, K, model, *dots))
-        zdh = None if dots[0] is None else _rows(nlp, dots[0])
-        kdh, xdh, mdh = _np(dots[1]), _np(dots[2]), _np(dots[3])
-        sw = MR.sweep_jvp(F, zr, Kh, zo, zdh, kdh, xdh, mdh)
-        cs = MR.jvp_complex_step(N, k_trans, init_mode, zr, Kh, x0h, th, zdh, kdh, xdh, mdh)
+        got = TC.rows(nlp, nlp.tracking_rollout_model_jvp(Zref, Zout, K, model, *dots))
+        zdh = None if dots[0] is None else TC.rows(nlp, dots[0])
+        kdh, xdh, mdh = TC.to_np(dots[1]), TC.to_np(dots[2]), TC.to_np(dots[3])
+        sw = RR.sweep_jvp(F, zr, Kh, zo, zdh, kdh, xdh, mdh)
+        cs = RR.jvp_complex_step(N, k_trans, init_mode, zr, Kh, x0h, th, zdh, kdh, xdh, mdh)
         e_sw, e_cs, between = _per_problem(got, sw), _per_problem(got, cs), _per_problem(sw, cs)
         print(f"B={B} N={N} k_trans={k_trans} mode={init_mode} K={with_gains} model_dot alone={dots[0] is None}: sweep "
               f"{e_sw:.2e}, complex step {e_cs:.2e}, between the two references {between:.2e}")
@@ -143,20 +113,20 @@ def test_jvp_matches_complex_step_and_numpy_sweep(B, N, k_trans, init_mode, with
 @pytest.mark.parametrize("B,N,k_trans,init_mode", SHAPES)
 @pytest.mark.parametrize("with_gains", [False, True])
 def test_vjp_matches_numpy_reverse_sweep(B, N, k_trans, init_mode, with_gains):
-    batch = _batch(B, N, k_trans, init_mode, seed=N + k_trans)
+    batch = TC.batch(B, N, k_trans, init_mode, seed=N + k_trans)
     nlp = _nlp(batch)
     Zref, K, x0, model, Zout, Zbar = _inputs(nlp, batch, N + 3 * k_trans, with_gains)
     zb, kb, xb, mb = nlp.tracking_rollout_model_vjp(Zref, Zout, Zbar, K, model)
     F = _blocks(nlp, Zout, model)
-    zr, zo, zbar, Kh = _rows(nlp, Zref), _rows(nlp, Zout), _rows(nlp, Zbar), _np(K)
+    zr, zo, zbar, Kh = TC.rows(nlp, Zref), TC.rows(nlp, Zout), TC.rows(nlp, Zbar), TC.to_np(K)
     worst = {"Zref": 0.0, "K": 0.0, "x0": 0.0, "model": 0.0}
     for b in range(B):
-        r_z, r_k, r_x, r_m = MR.sweep_vjp(F[b], zr[b], None if Kh is None else Kh[b], zo[b], zbar[b])
-        worst["Zref"] = max(worst["Zref"], MR.rel(_rows(nlp, zb)[b], r_z))
-        worst["x0"] = max(worst["x0"], MR.rel(_np(xb)[b], r_x))
-        worst["model"] = max(worst["model"], MR.rel(_np(mb)[b], r_m))
+        r_z, r_k, r_x, r_m = RR.sweep_vjp(F[b], zr[b], None if Kh is None else Kh[b], zo[b], zbar[b])
+        worst["Zref"] = max(worst["Zref"], RR.rel(TC.rows(nlp, zb)[b], r_z))
+        worst["x0"] = max(worst["x0"], RR.rel(TC.to_np(xb)[b], r_x))
+        worst["model"] = max(worst["model"], RR.rel(TC.to_np(mb)[b], r_m))
         if with_gains:
-            worst["K"] = max(worst["K"], MR.rel(_np(kb)[b], r_k))
+            worst["K"] = max(worst["K"], RR.rel(TC.to_np(kb)[b], r_k))
     print(f"B={B} N={N} k_trans={k_trans} mode={init_mode} K={with_gains}: " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
     assert max(worst.values()) <= BAR, worst
     assert (kb is None) == (not with_gains)
@@ -166,7 +136,7 @@ def test_vjp_planted_one_hot_cotangent_reads_a_row_of_the_accumulated_sensitivit
     """Zbar one-hot on one state of one knot: model_bar is that row of d Zout / d model, which four JVP calls give."""
     import torch
 
-    batch = _batch(9, 40, 14, 1, seed=71)
+    batch = TC.batch(9, 40, 14, 1, seed=71)
     nlp = _nlp(batch)
     Zref, K, x0, model, Zout, _ = _inputs(nlp, batch, 71, True)
     B, zs = nlp.B, nlp.z_stride
@@ -194,10 +164,10 @@ def test_vjp_planted_one_hot_cotangent_reads_a_row_of_the_accumulated_sensitivit
 def test_adjoint_identity_between_the_two_model_sweeps(B, N, k_trans, init_mode, with_gains):
     import torch
 
-    batch = _batch(B, N, k_trans, init_mode, seed=N + k_trans)
+    batch = TC.batch(B, N, k_trans, init_mode, seed=N + k_trans)
     nlp = _nlp(batch)
     Zref, K, x0, model, Zout, Zbar = _inputs(nlp, batch, N + 3 * k_trans, with_gains)
-    zd, kd, xd, md = _tangents(nlp, model, N + 7 * k_trans, with_gains)
+    zd, kd, xd, md = TC.tangents(nlp, N + 7 * k_trans, with_gains, model=model)
     got = nlp.tracking_rollout_model_jvp(Zref, Zout, K, model, zd, kd, xd, md)
     zb, kb, xb, mb = nlp.tracking_rollout_model_vjp(Zref, Zout, Zbar, K, model)
     lhs = float(torch.dot(Zbar, got))
@@ -216,24 +186,24 @@ def test_central_differences_of_the_gpu_rollout_in_the_model_entry_by_entry():
     inputs: the error of the quotient itself."""
     import torch
 
-    batch = _batch(8, 40, 14, 1, seed=21)
+    batch = TC.batch(8, 40, 14, 1, seed=21)
     nlp = _nlp(batch)
     Zref, K, x0, model, Zout, _ = _inputs(nlp, batch, 21, True)
-    zr, Kh, x0h, th = _rows(nlp, Zref), _np(K), _np(x0), _np(model)
+    zr, Kh, x0h, th = TC.rows(nlp, Zref), TC.to_np(K), TC.to_np(x0), TC.to_np(model)
     N, eps = nlp.N, 1e-5
     worst_gpu = worst_cpu = 0.0
     for p in range(4):
         md = torch.zeros_like(model)
         md[:, p] = model[:, p]
-        got = _rows(nlp, nlp.tracking_rollout_model_jvp(Zref, Zout, K, model, model_dot=md))
-        plus = _rows(nlp, nlp.tracking_rollout_model(Zref, K, x0, model + eps * md))
-        minus = _rows(nlp, nlp.tracking_rollout_model(Zref, K, x0, model - eps * md))
+        got = TC.rows(nlp, nlp.tracking_rollout_model_jvp(Zref, Zout, K, model, model_dot=md))
+        plus = TC.rows(nlp, nlp.tracking_rollout_model(Zref, K, x0, model + eps * md))
+        minus = TC.rows(nlp, nlp.tracking_rollout_model(Zref, K, x0, model - eps * md))
         fd = (plus - minus) / (2 * eps)
-        mdh = _np(md)
+        mdh = TC.to_np(md)
         kt, im = int(nlp.k_trans[0]), int(nlp.init_mode[0])
-        roll = lambda s: MR.rollout(N, kt, im, zr, Kh, x0h, th + s * mdh)  # noqa: E731
+        roll = lambda s: RR.rollout(N, kt, im, zr, Kh, x0h, th + s * mdh)  # noqa: E731
         zo = roll(0.0)
-        ref = MR.sweep_jvp(MR.complex_step_blocks(N, kt, im, zo, th), zr, Kh, zo, model_dot=mdh)
+        ref = RR.sweep_jvp(RR.complex_step_blocks(N, kt, im, zo, th), zr, Kh, zo, model_dot=mdh)
         quot = (roll(eps) - roll(-eps)) / (2 * eps)
         worst_gpu = max(worst_gpu, _per_problem(fd, got))
         worst_cpu = max(worst_cpu, _per_problem(quot, ref))
@@ -250,12 +220,12 @@ def test_reduction_to_the_calls_without_a_model(B, N, k_trans, init_mode, with_g
     """model = the handle's, model_dot = model_bar = NULL: the existing sweeps (the same kernels: bit for bit)."""
     import torch
 
-    batch = _batch(B, N, k_trans, init_mode, seed=N + k_trans)
+    batch = TC.batch(B, N, k_trans, init_mode, seed=N + k_trans)
     nlp = _nlp(batch)
     Zref, K, x0, model, _, Zbar = _inputs(nlp, batch, N + 3 * k_trans, with_gains)
     own = nlp.plant_models()
     Zout = nlp.tracking_rollout(Zref, K, x0)
-    zd, kd, xd, _ = _tangents(nlp, model, N + 5 * k_trans, with_gains)
+    zd, kd, xd, _ = TC.tangents(nlp, N + 5 * k_trans, with_gains, model=model)
     ref = nlp.tracking_rollout_jvp(Zref, Zout, K, zd, kd, xd)
     for m in (own, None):
         got = nlp.tracking_rollout_model_jvp(Zref, Zout, K, m, zd, kd, xd, None)
@@ -275,7 +245,7 @@ def test_permuting_the_problems_permutes_the_outputs_and_a_nan_model_stays_in_it
     import torch
 
     B, N = 5, 12
-    batch = _batch(B, N, 5, 2, seed=81)  # one schedule and, below, one reference for every problem: only the models differ
+    batch = TC.batch(B, N, 5, 2, seed=81)  # one schedule and, below, one reference for every problem: only the models differ
     batch.Z[:] = batch.Z[0]
     batch.x0[:] = batch.x0[0]
     batch.xf[:] = batch.xf[0]
@@ -284,7 +254,7 @@ def test_permuting_the_problems_permutes_the_outputs_and_a_nan_model_stays_in_it
     K[:] = K[0].clone()
     x0[:] = x0[0].clone()
     Zbar.view(B, -1)[:] = Zbar.view(B, -1)[0].clone()
-    zd, kd, xd, md = _tangents(nlp, model, 82, True)
+    zd, kd, xd, md = TC.tangents(nlp, 82, True, model=model)
     zd.view(B, -1)[:] = zd.view(B, -1)[0].clone()
     kd[:] = kd[0].clone()
     xd[:] = xd[0].clone()
@@ -316,10 +286,10 @@ def test_contract_sentinels_overwrite_null_tangents_refusals_and_host_forms(B):
     from quadruped_landing_amd import _lib
 
     N = 12
-    batch = _batch(B, N, 5, 2, seed=51)
+    batch = TC.batch(B, N, 5, 2, seed=51)
     nlp = _nlp(batch, z_stride=20 * N + 3)
     Zref, K, x0, model, Zout, Zbar = _inputs(nlp, batch, 51, True)
-    zd, kd, xd, md = _tangents(nlp, model, 52, True)
+    zd, kd, xd, md = TC.tangents(nlp, 52, True, model=model)
     n, zs = nlp.n_nlp, nlp.z_stride
     nan_z = lambda: torch.full((B * zs,), float("nan"), dtype=torch.float64, device="cuda")  # noqa: E731
     # sentinels past n_nlp stay; everything below is overwritten, whatever the buffer held
@@ -361,7 +331,7 @@ def test_contract_sentinels_overwrite_null_tangents_refusals_and_host_forms(B):
                                             None, md.data_ptr(), model.data_ptr()) == _lib.QLN_ERR_INVALID_ARGUMENT
     assert L.qln_tracking_rollout_model_vjp(nlp._h, Zref.data_ptr(), K.data_ptr(), Zout.data_ptr(), model.data_ptr(),
                                             Zbar.data_ptr(), None, None, model.data_ptr(), None) == _lib.QLN_ERR_INVALID_ARGUMENT
-    h = {name: _np(t) for name, t in (("Zref", Zref), ("K", K), ("x0", x0), ("model", model), ("Zout", Zout), ("Zbar", Zbar),
+    h = {name: TC.to_np(t) for name, t in (("Zref", Zref), ("K", K), ("x0", x0), ("model", model), ("Zout", Zout), ("Zbar", Zbar),
                                       ("zd", zd), ("kd", kd), ("xd", xd), ("md", md))}
     with pytest.raises(_lib.QlnError):
         nlp.tracking_rollout_model_jvp_host(h["Zref"], h["Zout"], h["K"], h["model"])
@@ -399,17 +369,17 @@ def test_autograd_in_the_model():
 
     from quadruped_landing_amd import rollout_grad
 
-    batch = _batch(2, 6, 4, 1, seed=31)
+    batch = TC.batch(2, 6, 4, 1, seed=31)
     nlp = _nlp(batch)
     Zref = nlp.upload_Z(batch.Z).requires_grad_(True)
-    K = _gains(nlp, 32, scale=0.02).requires_grad_(True)
+    K = TC.gains(nlp, 32, scale=0.02).requires_grad_(True)
     x0 = torch.from_numpy(batch.Z[:, :15].copy()).cuda().requires_grad_(True)
     model = _models(nlp, 33).requires_grad_(True)
     assert torch.autograd.gradcheck(lambda z, k, x, m: nlp.differentiable_rollout(z, k, x, m), (Zref, K, x0, model), eps=1e-6,
                                     atol=1e-7, rtol=1e-6, check_forward_ad=True)
     # the direct calls, bit for bit, through backward and torch.func.jvp
     z, k, x, m = (t.detach() for t in (Zref, K, x0, model))
-    zd, kd, xd, md = _tangents(nlp, m, 34, True)
+    zd, kd, xd, md = TC.tangents(nlp, 34, True, model=m)
     out, tangent = torch.func.jvp(lambda a, b_, c, d: nlp.differentiable_rollout(a, b_, c, d), (z, k, x, m), (zd, kd, xd, md))
     Zout = nlp.tracking_rollout_model(z, k, x, m)
     assert torch.equal(out, Zout) and torch.equal(tangent, nlp.tracking_rollout_model_jvp(z, Zout, k, m, zd, kd, xd, md))
@@ -446,7 +416,7 @@ def test_full_size_adjoint_identity_and_model_tangent():
     batch = PG.make_batch(B, N, 14, 1, seed=2)
     nlp = _nlp(batch)
     Zref, K, x0, model, Zout, Zbar = _inputs(nlp, batch, 2, True)
-    zd, kd, xd, md = _tangents(nlp, model, 3, True)
+    zd, kd, xd, md = TC.tangents(nlp, 3, True, model=model)
     got = nlp.tracking_rollout_model_jvp(Zref, Zout, K, model, zd, kd, xd, md)
     v = lambda t: t.view(B, -1)  # noqa: E731
 
@@ -467,11 +437,11 @@ def test_full_size_adjoint_identity_and_model_tangent():
     adj_terms = float((diff / terms).max())
     sample = np.random.default_rng(4).choice(B, size=256, replace=False)
     st = torch.from_numpy(sample).cuda()
-    only = _rows(nlp, nlp.tracking_rollout_model_jvp(Zref, Zout, K, model, model_dot=md))[sample]
-    zo, th = _rows(nlp, Zout)[sample], _np(model[st])
+    only = TC.rows(nlp, nlp.tracking_rollout_model_jvp(Zref, Zout, K, model, model_dot=md))[sample]
+    zo, th = TC.rows(nlp, Zout)[sample], TC.to_np(model[st])
     assert np.all(nlp.k_trans == nlp.k_trans[0]) and np.all(nlp.init_mode == nlp.init_mode[0])
-    F = MR.complex_step_blocks(N, int(nlp.k_trans[0]), int(nlp.init_mode[0]), zo, th)
-    ref = MR.sweep_jvp(F, _rows(nlp, Zref)[sample], _np(K[st]), zo, model_dot=_np(md[st]))
+    F = RR.complex_step_blocks(N, int(nlp.k_trans[0]), int(nlp.init_mode[0]), zo, th)
+    ref = RR.sweep_jvp(F, TC.rows(nlp, Zref)[sample], TC.to_np(K[st]), zo, model_dot=TC.to_np(md[st]))
     err = float((np.linalg.norm(only - ref, axis=1) / np.linalg.norm(ref, axis=1)).max())
     print(f"full size B={B} N={N}: adjoint identity per problem, of |lhs| + |rhs|: {adj_sq:.2e} with Zbar = Zout_dot (all problems), "
           f"{adj_kept:.2e} with a random Zbar on the {int(kept.sum())} problems that keep a hundredth of their terms (all "
@@ -500,14 +470,14 @@ def test_example_recovers_the_masses():
     zr, Kh, x0h, target, n = r["Zref"], r["K"], r["x0"], r["target"], 20 * r["N"] - 5
 
     def zout_of(th):
-        return MR.rollout(N, kt, im, zr, Kh, x0h, th)
+        return RR.rollout(N, kt, im, zr, Kh, x0h, th)
 
     def sens(th):
         zo = zout_of(th)
-        F = MR.complex_step_blocks(N, kt, im, zo, th)
-        return np.stack([MR.sweep_jvp(F, zr, Kh, zo, model_dot=np.tile(np.eye(4)[p], (len(th), 1))) for p in range(4)], axis=2)
+        F = RR.complex_step_blocks(N, kt, im, zo, th)
+        return np.stack([RR.sweep_jvp(F, zr, Kh, zo, model_dot=np.tile(np.eye(4)[p], (len(th), 1))) for p in range(4)], axis=2)
 
-    th_np = MR.identify_model(sens, zout_of, target[:, :n], r["nominal"], iters=r["iterations"])
+    th_np = RR.identify_model(sens, zout_of, target[:, :n], r["nominal"], iters=r["iterations"])
     err_np = float(np.abs(th_np[:, 1:3] / r["truth"][:, 1:3] - 1.0).max())
     err_gpu = float(np.abs(r["recovered"][:, 1:3] / r["truth"][:, 1:3] - 1.0).max())
     print(f"recovery of (mb, mf) at 64 landings: GPU Gauss-Newton {err_gpu:.2e}, numpy Gauss-Newton {err_np:.2e}, bar {10 * err_np:.2e}")

@@ -4,81 +4,34 @@ differences of the GPU roll-out, torch gradcheck, the anchor 2 P_0 dx_0 of the T
 import numpy as np
 import pytest
 
-from tests import rollout_vjp_ref as RV
-from tests.test_gpu_tracking import SHAPES, _batch, _dense_blocks, _nlp
+from tests import rollout_ref as RR
+from tests import tracking_cases as TC
+from tests.tracking_cases import SHAPES, Q, R
 
 pytestmark = pytest.mark.gpu
-
-Q = np.array([10.0] * 14 + [0.0])
-R = np.array([1e-3, 1e-2, 1e-3, 1e-2])
-
-
-def _gains(nlp, seed, scale=0.05):
-    import torch
-
-    rng = np.random.default_rng(seed)
-    return torch.from_numpy(scale * rng.normal(size=(nlp.B, nlp.N - 1, 4, 15))).cuda()
-
-
-def _inputs(nlp, batch, seed, with_gains):
-    """A reference, gains (or None), x0 near the reference's x_0, the GPU roll-out and a random cotangent."""
-    import torch
-
-    rng = np.random.default_rng(seed)
-    Zref = nlp.upload_Z(batch.Z)
-    K = _gains(nlp, seed + 1) if with_gains else None
-    x0 = torch.from_numpy(batch.Z[:, :15] + 1e-2 * rng.normal(size=(nlp.B, 15))).cuda()
-    Zout = nlp.tracking_rollout(Zref, K, x0)
-    Zbar = nlp.upload_Z(rng.normal(size=(nlp.B, nlp.n_nlp)))
-    return Zref, K, x0, Zout, Zbar
-
-
-def _per_problem(nlp, Zref, K, Zout, Zbar, zb, kb, xb, blocks):
-    """worst per-problem relative norm of (Zref_bar, K_bar, x0_bar) against the numpy sweep on blocks(b, Zout_b)"""
-    n = nlp.n_nlp
-    f = lambda t: t.view(nlp.B, -1)[:, :n].cpu().numpy()  # noqa: E731
-    zr, zo, zbar, zg = f(Zref), f(Zout), f(Zbar), f(zb)
-    Kh = None if K is None else K.cpu().numpy()
-    kg = None if kb is None else kb.cpu().numpy()
-    xg = xb.cpu().numpy()
-    worst = 0.0
-    for b in range(nlp.B):
-        r_z, r_k, r_x = RV.sweep(blocks(b, zo[b]), zr[b], None if Kh is None else Kh[b], zo[b], zbar[b])
-        e = [RV.rel(zg[b], r_z), RV.rel(xg[b], r_x)] + ([] if kg is None else [RV.rel(kg[b], r_k)])
-        worst = max(worst, *e)
-    return worst
-
-
-def _evaluator_blocks(nlp, Zout):
-    dense = _dense_blocks(nlp, Zout)
-    return lambda b, zo: RV.evaluator_blocks(dense[b], int(nlp.k_trans[b]))
-
-
-def _cs_blocks(nlp):
-    return lambda b, zo: RV.complex_step_blocks(nlp.N, int(nlp.k_trans[b]), int(nlp.init_mode[b]), zo)
 
 
 @pytest.mark.parametrize("B,N,k_trans,init_mode", SHAPES)
 @pytest.mark.parametrize("with_gains", [False, True])
 def test_matches_numpy_sweep_over_shapes(B, N, k_trans, init_mode, with_gains):
-    batch = _batch(B, N, k_trans, init_mode, seed=N + k_trans)
-    nlp = _nlp(batch)
-    Zref, K, x0, Zout, Zbar = _inputs(nlp, batch, N + 3 * k_trans, with_gains)
+    batch = TC.batch(B, N, k_trans, init_mode, seed=N + k_trans)
+    nlp = TC.nlp(batch)
+    Zref, K, x0, Zout, Zbar = TC.inputs(nlp, batch, N + 3 * k_trans, with_gains)
     zb, kb, xb = nlp.tracking_rollout_vjp(Zref, Zout, Zbar, K)
-    ev = _per_problem(nlp, Zref, K, Zout, Zbar, zb, kb, xb, _evaluator_blocks(nlp, Zout))
-    cs = _per_problem(nlp, Zref, K, Zout, Zbar, zb, kb, xb, _cs_blocks(nlp))
+    ev = TC.vjp_per_problem(nlp, Zref, K, Zout, Zbar, zb, kb, xb, TC.evaluator_blocks(nlp, Zout))
+    cs = TC.vjp_per_problem(nlp, Zref, K, Zout, Zbar, zb, kb, xb, TC.cs_blocks(nlp))
     print(f"B={B} N={N} k_trans={k_trans} mode={init_mode} K={with_gains}: evaluator blocks {ev:.2e}, complex step {cs:.2e}")
     assert ev <= 1e-12 and cs <= 1e-8, (ev, cs)
 
 
 @pytest.mark.parametrize("with_gains", [False, True])
 def test_ragged_batch_and_padded_layout(with_gains):
-    for batch, kw in ((_batch(37, 12, 5, 1, seed=3, ragged=True), {}),
-                      (_batch(13, 12, 7, 2, seed=4), {"z_stride": 20 * 12 + 3, "align": 7})):
-        nlp = _nlp(batch, **kw)
-        Zref, K, x0, Zout, Zbar = _inputs(nlp, batch, 5, with_gains)
+    for batch, kw in ((TC.batch(37, 12, 5, 1, seed=3, ragged=True), {}),
+                      (TC.batch(13, 12, 7, 2, seed=4), {"z_stride": 20 * 12 + 3, "align": 7})):
+        nlp = TC.nlp(batch, **kw)
+        Zref, K, x0, Zout, Zbar = TC.inputs(nlp, batch, 5, with_gains)
         zb, kb, xb = nlp.tracking_rollout_vjp(Zref, Zout, Zbar, K)
-        assert _per_problem(nlp, Zref, K, Zout, Zbar, zb, kb, xb, _evaluator_blocks(nlp, Zout)) <= 1e-12
+        assert TC.vjp_per_problem(nlp, Zref, K, Zout, Zbar, zb, kb, xb, TC.evaluator_blocks(nlp, Zout)) <= 1e-12
 
 
 @pytest.mark.parametrize("B,N,ragged", [(65536, 40, False), (65536, 80, True)])
@@ -92,10 +45,10 @@ def test_full_size_every_problem(B, N, ragged):
         sub = PG.LandingBatch(full.model, N, full.k_trans[s:s + chunk], full.init_mode[s:s + chunk], full.x0[s:s + chunk],
                               full.xf[s:s + chunk], full.obj if full.obj.ndim == 2 else full.obj[s:s + chunk],
                               full.Z[s:s + chunk])
-        nlp = _nlp(sub)
-        Zref, K, x0, Zout, Zbar = _inputs(nlp, sub, s, True)
+        nlp = TC.nlp(sub)
+        Zref, K, x0, Zout, Zbar = TC.inputs(nlp, sub, s, True)
         zb, kb, xb = nlp.tracking_rollout_vjp(Zref, Zout, Zbar, K)
-        dense = _dense_blocks(nlp, Zout)
+        dense = TC.dense_blocks(nlp, Zout)
         n = nlp.n_nlp
         f = lambda t: t.view(nlp.B, -1)[:, :n].cpu().numpy()  # noqa: E731
         zr, zo, zbar, zg = f(Zref), f(Zout), f(Zbar), f(zb)
@@ -105,7 +58,7 @@ def test_full_size_every_problem(B, N, ragged):
         F = dense.copy()
         kj = nlp.k_trans.astype(int) - 2
         for b in np.nonzero((kj >= 0) & (kj < N - 1))[0]:
-            F[b] = RV.evaluator_blocks(dense[b], nlp.k_trans[b])
+            F[b] = RR.evaluator_blocks(dense[b], nlp.k_trans[b])
         lam = zbar[:, 20 * (N - 1): 20 * (N - 1) + 15]
         r_z = np.zeros_like(zg)
         r_k = np.zeros_like(kg)
@@ -127,9 +80,9 @@ def test_full_size_every_problem(B, N, ragged):
 def test_adjoint_identity_against_central_differences():
     import torch
 
-    batch = _batch(8, 40, 14, 1, seed=21)
-    nlp = _nlp(batch)
-    Zref, K, x0, Zout, Zbar = _inputs(nlp, batch, 21, True)
+    batch = TC.batch(8, 40, 14, 1, seed=21)
+    nlp = TC.nlp(batch)
+    Zref, K, x0, Zout, Zbar = TC.inputs(nlp, batch, 21, True)
     zb, kb, xb = nlp.tracking_rollout_vjp(Zref, Zout, Zbar, K)
     rng = np.random.default_rng(22)
     n = nlp.n_nlp
@@ -153,10 +106,10 @@ def test_adjoint_identity_against_central_differences():
 def test_autograd_gradcheck():
     import torch
 
-    batch = _batch(2, 6, 4, 1, seed=31)
-    nlp = _nlp(batch)
+    batch = TC.batch(2, 6, 4, 1, seed=31)
+    nlp = TC.nlp(batch)
     Zref = nlp.upload_Z(batch.Z).requires_grad_(True)
-    K = _gains(nlp, 32, scale=0.02).requires_grad_(True)
+    K = TC.gains(nlp, 32, scale=0.02).requires_grad_(True)
     x0 = torch.from_numpy(batch.Z[:, :15].copy()).cuda().requires_grad_(True)
     assert torch.autograd.gradcheck(lambda z, k, x: nlp.differentiable_rollout(z, k, x), (Zref, K, x0), eps=1e-6,
                                     atol=1e-7, rtol=1e-6)
@@ -213,9 +166,9 @@ def test_contract_sentinels_linearity_refusal_and_host_forms(B):
     from quadruped_landing_amd import _lib
 
     N = 12
-    batch = _batch(B, N, 5, 2, seed=51)
-    nlp = _nlp(batch, z_stride=20 * N + 3)
-    Zref, K, x0, Zout, Zbar = _inputs(nlp, batch, 51, True)
+    batch = TC.batch(B, N, 5, 2, seed=51)
+    nlp = TC.nlp(batch, z_stride=20 * N + 3)
+    Zref, K, x0, Zout, Zbar = TC.inputs(nlp, batch, 51, True)
     zb, kb, xb = nlp.tracking_rollout_vjp(Zref, Zout, Zbar, K)
     L = _lib.lib()
     n, zs = nlp.n_nlp, nlp.z_stride

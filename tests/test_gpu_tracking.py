@@ -3,104 +3,35 @@ the quirk-Q1 clock row, roll-out anchors against qln_solve, second-order lineari
 import numpy as np
 import pytest
 
+from tests import tracking_cases as TC
+from tests import tracking_cov_ref as CR
 from tests import tracking_ref as TR
+from tests.tracking_cases import QFW, QW, SHAPES, Q, R
 
 pytestmark = pytest.mark.gpu
-
-Q = np.array([10.0] * 14 + [0.0])
-R = np.array([1e-3, 1e-2, 1e-3, 1e-2])
-QW = np.array([10.0] * 14 + [0.7])
-QFW = np.array([30.0] * 14 + [2.0])
-
-SHAPES = [  # (B, N, k_trans, init_mode): tests/test_gpu_hessian.py's list
-    (3, 2, 1, 1), (3, 2, 2, 2), (3, 2, 3, 1), (5, 3, 2, 1), (5, 3, 3, 2), (5, 3, 4, 1),
-    (9, 40, 14, 1), (9, 40, 1, 2), (9, 40, 39, 1), (9, 40, 40, 2), (9, 40, 41, 1),
-    (17, 61, 21, 1), (17, 61, 60, 2), (10, 65, 64, 1), (10, 65, 65, 2), (10, 65, 2, 1),
-    (11, 80, 66, 2), (11, 80, 10, 1), (4, 200, 130, 1), (4, 200, 201, 2),
-]
-
-
-def _batch(B, N, k_trans, init_mode, seed=0, ragged=False):
-    from quadruped_landing_amd import problem_gen as PG
-
-    kt_build = min(max(int(k_trans), 2), N - 1) if N > 2 else 2
-    b = PG.make_batch(B, N, kt_build, init_mode, seed=seed, ragged=ragged)
-    if not ragged:
-        b.k_trans[:] = k_trans
-    return b
-
-
-def _nlp(batch, **kw):
-    from quadruped_landing_amd import HybridNLP
-
-    return HybridNLP(batch.model, batch.obj, batch.init_mode, batch.k_trans, batch.N, batch.x0, batch.xf, **kw)
-
-
-def _dense_blocks(nlp, Z):
-    import torch
-
-    vals = nlp.jac_c(Z).cpu().numpy()
-    N = nlp.N
-    out = np.zeros((nlp.B, N - 1, 15, 20))
-    for b in range(nlp.B):
-        seg = vals[nlp.j_off[b]: nlp.j_off[b] + 300 * (N - 1)]
-        out[b] = seg.reshape(N - 1, 20, 15).transpose(0, 2, 1)
-    torch.cuda.synchronize()
-    return out
-
-
-def _ref_gains(nlp, Z, Qw, Rw, Qfw, restore_clock=True):
-    blocks = _dense_blocks(nlp, Z)
-    A = np.zeros((nlp.B, nlp.N - 1, 15, 15))
-    Bm = np.zeros((nlp.B, nlp.N - 1, 15, 4))
-    for b in range(nlp.B):
-        A[b], Bm[b] = TR.blocks_from_dense(blocks[b], int(nlp.k_trans[b]), restore_clock)
-    K, P = TR.riccati(A, Bm, Qw, Rw, Qfw)
-    return A, Bm, K, P
-
-
-def _knot_rel(got, ref):
-    num = np.linalg.norm((got - ref).reshape(got.shape[0], got.shape[1], -1), axis=-1)
-    den = np.linalg.norm(ref.reshape(ref.shape[0], ref.shape[1], -1), axis=-1)
-    return float(np.max(num / np.maximum(den, 1e-300)))
-
-
-def _check_against_numpy(batch, bar=1e-10, **kw):
-    from quadruped_landing_amd import nlp as NL
-
-    nlp = _nlp(batch, **kw)
-    Z = nlp.upload_Z(batch.Z)
-    K, P = nlp.tracking_lqr(Z, QW, R, QFW)
-    _, _, Kr, Pr = _ref_gains(nlp, Z, QW, R, QFW)
-    Kg = K.cpu().numpy()
-    Pg = NL.unpack_cost_to_go(P)
-    ek, ep = _knot_rel(Kg, Kr), _knot_rel(Pg, Pr)
-    assert ek <= bar and ep <= bar, (ek, ep)
-    assert np.array_equal(Pg, np.swapaxes(Pg, -1, -2))
-    return ek, ep
 
 
 @pytest.mark.parametrize("B,N,k_trans,init_mode", SHAPES)
 def test_gains_and_cost_to_go_over_shapes(B, N, k_trans, init_mode):
-    _check_against_numpy(_batch(B, N, k_trans, init_mode, seed=N + k_trans))
+    TC.check_gains_against_numpy(TC.batch(B, N, k_trans, init_mode, seed=N + k_trans))
 
 
 @pytest.mark.parametrize("N", [12, 40])
 def test_ragged_batch_and_padded_layout(N):
-    _check_against_numpy(_batch(37, N, 5, 1, seed=3, ragged=True))
-    _check_against_numpy(_batch(13, N, 7, 2, seed=4), z_stride=20 * N + 3, align=7)
+    TC.check_gains_against_numpy(TC.batch(37, N, 5, 1, seed=3, ragged=True))
+    TC.check_gains_against_numpy(TC.batch(13, N, 7, 2, seed=4), z_stride=20 * N + 3, align=7)
 
 
 def test_against_the_dual_number_oracle_blocks():
-    b = _batch(6, 12, 5, 2, seed=11)
-    nlp = _nlp(b)
+    b = TC.batch(6, 12, 5, 2, seed=11)
+    nlp = TC.nlp(b)
     Z = nlp.upload_Z(b.Z)
     K, _ = nlp.tracking_lqr(Z, QW, R, QFW, with_cost_to_go=False)
     Kg = K.cpu().numpy()
     for i in range(b.Z.shape[0]):
         A, Bm = TR.oracle_blocks(12, int(b.k_trans[i]), int(b.init_mode[i]), b.Z[i])
         Kr, _ = TR.riccati(A, Bm, QW, R, QFW)
-        assert _knot_rel(Kg[i][None], Kr[None]) <= 1e-8
+        assert CR.knot_rel(Kg[i][None], Kr[None]) <= 1e-8
 
 
 @pytest.mark.parametrize("B,N,ragged", [(65536, 40, False), (65536, 80, True)])
@@ -114,7 +45,7 @@ def test_full_size_every_problem(B, N, ragged):
         sub = PG.LandingBatch(full.model, N, full.k_trans[s:s + chunk], full.init_mode[s:s + chunk], full.x0[s:s + chunk],
                               full.xf[s:s + chunk], full.obj if full.obj.ndim == 2 else full.obj[s:s + chunk],
                               full.Z[s:s + chunk])
-        ek, ep = _check_against_numpy(sub)
+        ek, ep = TC.check_gains_against_numpy(sub)
         worst = [max(worst[0], ek), max(worst[1], ep)]
     print(f"full size B={B} N={N} ragged={ragged}: worst per-knot rel err K {worst[0]:.2e} P {worst[1]:.2e}")
 
@@ -122,8 +53,8 @@ def test_full_size_every_problem(B, N, ragged):
 def test_clock_weights_and_quirk_Q1():
     from quadruped_landing_amd import nlp as NL
 
-    b = _batch(9, 40, 14, 1, seed=5)
-    nlp = _nlp(b)
+    b = TC.batch(9, 40, 14, 1, seed=5)
+    nlp = TC.nlp(b)
     Z = nlp.upload_Z(b.Z)
     q0, qf0 = QW.copy(), QFW.copy()
     q0[14] = qf0[14] = 0.0
@@ -131,10 +62,10 @@ def test_clock_weights_and_quirk_Q1():
     K1, _ = nlp.tracking_lqr(Z, QW, R, QFW)
     assert np.array_equal(K0.cpu().numpy(), K1.cpu().numpy())
     # against the Jacobian's masked jump block (row 14 zero): K agrees, P differs only at (14, 14) before the jump
-    _, _, Km, Pm = _ref_gains(nlp, Z, QW, R, QFW, restore_clock=False)
+    _, _, Km, Pm = TC.ref_gains(nlp, Z, QW, R, QFW, restore_clock=False)
     Kg, Pg = nlp.tracking_lqr(Z, QW, R, QFW)
     Kg, Pg = Kg.cpu().numpy(), NL.unpack_cost_to_go(Pg)
-    assert _knot_rel(Kg, Km) <= 1e-10
+    assert CR.knot_rel(Kg, Km) <= 1e-10
     d = np.abs(Pg - Pm) > 1e-10 * np.abs(Pm).max()
     assert not d[..., :14, :].any() and not d[..., 14, :14].any()
     kt = 14
@@ -144,8 +75,8 @@ def test_clock_weights_and_quirk_Q1():
 def test_rollout_anchors_against_qln_solve():
     import torch
 
-    b = _batch(16, 40, 14, 1, seed=6)
-    nlp = _nlp(b)
+    b = TC.batch(16, 40, 14, 1, seed=6)
+    nlp = TC.nlp(b)
     Z = nlp.upload_Z(b.Z)
     hcols = 19 + 20 * np.arange(39)
     Zh = b.Z.copy()
@@ -188,7 +119,7 @@ def test_linearisation_is_second_order_and_closed_loop_is_lq_optimal():
     nlp, Zs = _linear_setup()
     N = nlp.N
     K, P = nlp.tracking_lqr(Zs, Q, R, Q)
-    A, Bm, _, _ = _ref_gains(nlp, Zs, Q, R, Q)
+    A, Bm, _, _ = TC.ref_gains(nlp, Zs, Q, R, Q)
     Kg = K.cpu().numpy()[0]
     from quadruped_landing_amd import nlp as NL
 
@@ -235,8 +166,8 @@ def test_host_forms_and_argument_validation(B):
 
     from quadruped_landing_amd import _lib
 
-    b = _batch(B, 40, 14, 2, seed=8)
-    nlp = _nlp(b)
+    b = TC.batch(B, 40, 14, 2, seed=8)
+    nlp = TC.nlp(b)
     Z = nlp.upload_Z(b.Z)
     nlp.solve(Z)  # a solved reference: the perturbed closed-loop roll-outs stay finite
     Zr = Z.cpu().numpy()
@@ -264,4 +195,4 @@ def test_host_forms_and_argument_validation(B):
         _lib.QLN_ERR_INVALID_ARGUMENT
     assert L.qln_tracking_rollout(nlp._h, Z.data_ptr(), None, None, Z.data_ptr() + 8) == _lib.QLN_ERR_INVALID_ARGUMENT
     if B == 5:  # no limit on N: past the solver's LDS limit the sweep still runs
-        _check_against_numpy(_batch(2, 700, 300, 1, seed=9), bar=1e-9)
+        TC.check_gains_against_numpy(TC.batch(2, 700, 300, 1, seed=9), bar=1e-9)

@@ -6,15 +6,12 @@ import faulthandler
 import numpy as np
 import pytest
 
-from tests import rollout_vjp_ref as RV
+from tests import tracking_cases as TC
 from tests import tracking_cov_ref as CR
-from tests.test_gpu_rollout_vjp import _inputs
-from tests.test_gpu_tracking import SHAPES, _batch, _dense_blocks, _nlp
+from tests.tracking_cases import SHAPES, Q, R
 
 pytestmark = pytest.mark.gpu
 
-Q = np.array([10.0] * 14 + [0.0])
-R = np.array([1e-3, 1e-2, 1e-3, 1e-2])
 BAR = 1e-10  # the project's bar for K and P (tests/test_gpu_tracking.py); the yardstick's own rounding is ~1e-14
 
 
@@ -26,63 +23,12 @@ def _time_limit():
     faulthandler.cancel_dump_traceback_later()
 
 
-def _setup(batch, seed, with_gains, **kw):
-    """A handle, a roll-out Zout near the batch's Z under random gains (or open loop), per-problem random Sigma0 and W."""
-    nlp = _nlp(batch, **kw)
-    _, K, _, Zout, _ = _inputs(nlp, batch, seed, with_gains)
-    rng = np.random.default_rng(seed + 100)
-    S0 = CR.random_psd(rng, shape=(nlp.B,))
-    W = rng.uniform(0.0, 1e-2, size=15)
-    return nlp, K, Zout, S0, W
-
-
-def _host(nlp, t):
-    return t.view(nlp.B, -1)[:, : nlp.n_nlp].cpu().numpy()
-
-
-def _reference(nlp, K, Zout, S0, W, blocks):
-    """numpy (Sigma (B, N, 15, 15), marg (B, N, 8)) on blocks(b, zo) (N-1, 15, 20) per problem"""
-    zo = _host(nlp, Zout)
-    Kh = None if K is None else K.cpu().numpy()
-    N = nlp.N
-    Sr = np.zeros((nlp.B, N, 15, 15))
-    mr = np.zeros((nlp.B, N, 8))
-    for b in range(nlp.B):
-        F = blocks(b, zo[b])
-        Sr[b] = CR.propagate(F[:, :, :15], F[:, :, 15:19], None if Kh is None else Kh[b], S0[b] if S0.ndim == 3 else S0, W)
-        theta = zo[b][2 + 20 * np.arange(N)]
-        mr[b] = CR.marginals(Sr[b], None if Kh is None else Kh[b], theta, nlp.model.lb)
-    return Sr, mr
-
-
-def _evaluator_blocks(nlp, Zout):
-    dense = _dense_blocks(nlp, Zout)
-    return lambda b, zo: RV.evaluator_blocks(dense[b], int(nlp.k_trans[b]))
-
-
-def _cs_blocks(nlp):
-    return lambda b, zo: RV.complex_step_blocks(nlp.N, int(nlp.k_trans[b]), int(nlp.init_mode[b]), zo)
-
-
-def _errors(nlp, K, Zout, S0, W, blocks):
-    from quadruped_landing_amd import nlp as NL
-
-    S, mg = nlp.tracking_covariance(Zout, K, S0, W)
-    Sg, mgg = NL.unpack_covariance(S), mg.cpu().numpy()
-    assert np.array_equal(Sg, np.swapaxes(Sg, -1, -2))
-    Sr, mr = _reference(nlp, K, Zout, S0, W, blocks)
-    if K is None:
-        assert not mgg[:, :, 1:5].any()
-    assert not mgg[:, -1, 1:5].any()
-    return CR.knot_rel(Sg, Sr), CR.entry_rel(mgg, mr)
-
-
 @pytest.mark.parametrize("B,N,k_trans,init_mode", SHAPES)
 @pytest.mark.parametrize("with_gains", [False, True])
 def test_matches_numpy_recursion_over_shapes(B, N, k_trans, init_mode, with_gains):
-    batch = _batch(B, N, k_trans, init_mode, seed=N + k_trans)
-    nlp, K, Zout, S0, W = _setup(batch, N + 3 * k_trans, with_gains)
-    es, em = _errors(nlp, K, Zout, S0, W, _evaluator_blocks(nlp, Zout))
+    batch = TC.batch(B, N, k_trans, init_mode, seed=N + k_trans)
+    nlp, K, Zout, S0, W = TC.cov_setup(batch, N + 3 * k_trans, with_gains)
+    es, em = TC.cov_errors(nlp, K, Zout, S0, W, TC.evaluator_blocks(nlp, Zout))
     print(f"B={B} N={N} k_trans={k_trans} mode={init_mode} K={with_gains}: Sigma {es:.2e}, marg {em:.2e}")
     assert es <= BAR and em <= BAR, (es, em)
 
@@ -90,10 +36,10 @@ def test_matches_numpy_recursion_over_shapes(B, N, k_trans, init_mode, with_gain
 @pytest.mark.parametrize("N", [12, 40])
 @pytest.mark.parametrize("with_gains", [False, True])
 def test_ragged_batch_and_padded_layout(N, with_gains):
-    for batch, kw in ((_batch(37, N, 5, 1, seed=3, ragged=True), {}),
-                      (_batch(13, N, 7, 2, seed=4), {"z_stride": 20 * N + 3, "align": 7})):
-        nlp, K, Zout, S0, W = _setup(batch, 5, with_gains, **kw)
-        es, em = _errors(nlp, K, Zout, S0, W, _evaluator_blocks(nlp, Zout))
+    for batch, kw in ((TC.batch(37, N, 5, 1, seed=3, ragged=True), {}),
+                      (TC.batch(13, N, 7, 2, seed=4), {"z_stride": 20 * N + 3, "align": 7})):
+        nlp, K, Zout, S0, W = TC.cov_setup(batch, 5, with_gains, **kw)
+        es, em = TC.cov_errors(nlp, K, Zout, S0, W, TC.evaluator_blocks(nlp, Zout))
         print(f"N={N} K={with_gains} {kw}: Sigma {es:.2e}, marg {em:.2e}")
         assert es <= BAR and em <= BAR, (es, em)
 
@@ -102,9 +48,9 @@ def test_ragged_batch_and_padded_layout(N, with_gains):
 @pytest.mark.parametrize("with_gains", [False, True])
 def test_against_complex_step_blocks(B, N, k_trans, init_mode, with_gains):
     """the bar the VJP tests hold this block source to (tests/test_gpu_rollout_vjp.py)"""
-    batch = _batch(B, N, k_trans, init_mode, seed=N + k_trans)
-    nlp, K, Zout, S0, W = _setup(batch, N + 3 * k_trans, with_gains)
-    es, em = _errors(nlp, K, Zout, S0, W, _cs_blocks(nlp))
+    batch = TC.batch(B, N, k_trans, init_mode, seed=N + k_trans)
+    nlp, K, Zout, S0, W = TC.cov_setup(batch, N + 3 * k_trans, with_gains)
+    es, em = TC.cov_errors(nlp, K, Zout, S0, W, TC.cs_blocks(nlp))
     print(f"complex step B={B} N={N} k_trans={k_trans} K={with_gains}: Sigma {es:.2e}, marg {em:.2e}")
     assert es <= 1e-8 and em <= 1e-8, (es, em)
 
@@ -116,9 +62,9 @@ def test_duality_with_the_rollout_vjp():
 
     from quadruped_landing_amd import nlp as NL
 
-    batch = _batch(9, 40, 14, 1, seed=61)
-    nlp = _nlp(batch)
-    Zref, K, _, Zout, _ = _inputs(nlp, batch, 61, True)
+    batch = TC.batch(9, 40, 14, 1, seed=61)
+    nlp = TC.nlp(batch)
+    Zref, K, _, Zout, _ = TC.inputs(nlp, batch, 61, True)
     rng = np.random.default_rng(62)
     S0 = CR.random_psd(rng, shape=(nlp.B,))
     S, _ = nlp.tracking_covariance(Zout, K, S0)
@@ -144,8 +90,8 @@ def test_exactness():
     from quadruped_landing_amd import _lib
 
     B, N = 13, 12
-    batch = _batch(B, N, 7, 2, seed=71)
-    nlp, K, Zout, S0, W = _setup(batch, 71, True, z_stride=20 * N + 3)
+    batch = TC.batch(B, N, 7, 2, seed=71)
+    nlp, K, Zout, S0, W = TC.cov_setup(batch, 71, True, z_stride=20 * N + 3)
     L = _lib.lib()
     # Sigma0 = 0, W = 0: exact zeros everywhere
     S, mg = nlp.tracking_covariance(Zout, K, np.zeros(15))
@@ -187,8 +133,8 @@ def test_argument_validation_on_a_handle():
     from quadruped_landing_amd import _lib
 
     B, N = 5, 12
-    batch = _batch(B, N, 5, 1, seed=81)
-    nlp, K, Zout, S0, W = _setup(batch, 81, True)
+    batch = TC.batch(B, N, 5, 1, seed=81)
+    nlp, K, Zout, S0, W = TC.cov_setup(batch, 81, True)
     L = _lib.lib()
     bad = _lib.QLN_ERR_INVALID_ARGUMENT
     s0 = torch.from_numpy(CR.pack(S0)).cuda()
@@ -265,17 +211,17 @@ def test_full_size_every_problem(B, N, ragged):
         sub = PG.LandingBatch(full.model, N, full.k_trans[s:s + chunk], full.init_mode[s:s + chunk], full.x0[s:s + chunk],
                               full.xf[s:s + chunk], full.obj if full.obj.ndim == 2 else full.obj[s:s + chunk],
                               full.Z[s:s + chunk])
-        nlp, K, Zout, S0, W = _setup(sub, s, True)
+        nlp, K, Zout, S0, W = TC.cov_setup(sub, s, True)
         S, mg = nlp.tracking_covariance(Zout, K, S0, W)
         Sg, mgg = NL.unpack_covariance(S), mg.cpu().numpy()
         # the recursion vectorised over the chunk
-        F = _dense_blocks(nlp, Zout)
+        F = TC.dense_blocks(nlp, Zout)
         kj = nlp.k_trans.astype(int) - 2
         for b in np.nonzero((kj >= 0) & (kj < N - 1))[0]:
             F[b, kj[b], 14, 14] = 1.0
         Kh = K.cpu().numpy()
         Sr = CR.propagate(F[..., :15], F[..., 15:19], Kh, S0, W)
-        theta = _host(nlp, Zout)[:, 2 + 20 * np.arange(N)]
+        theta = TC.rows(nlp, Zout)[:, 2 + 20 * np.arange(N)]
         mr = CR.marginals(Sr, Kh, theta, nlp.model.lb)
         worst = [max(worst[0], CR.knot_rel(Sg, Sr)), max(worst[1], CR.entry_rel(mgg, mr))]
         assert np.array_equal(Sg, np.swapaxes(Sg, -1, -2))
@@ -287,8 +233,8 @@ def test_full_size_every_problem(B, N, ragged):
 @pytest.mark.parametrize("B", [5, 1024])  # mapped pinned buffers (small batch) and staged device copies
 def test_host_forms_give_the_device_forms_bits(B):
     N = 12
-    batch = _batch(B, N, 5, 2, seed=91)
-    nlp, K, Zout, S0, W = _setup(batch, 91, True, z_stride=20 * N + 3)
+    batch = TC.batch(B, N, 5, 2, seed=91)
+    nlp, K, Zout, S0, W = TC.cov_setup(batch, 91, True, z_stride=20 * N + 3)
     S, mg = nlp.tracking_covariance(Zout, K, S0, W)
     So, mo = nlp.tracking_covariance(Zout, None, S0[0], W)
     Sd, md, Sod, mod = (t.cpu().numpy() for t in (S, mg, So, mo))

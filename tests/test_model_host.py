@@ -16,7 +16,8 @@ from oracle import oracle as O
 from quadruped_landing_amd import problem_gen as PG
 from quadruped_landing_amd.planar_quadruped import PlanarQuadruped
 from tests.helpers import oracle_model
-from tests.test_gpu_model import SECOND_MODEL as M, np_model
+from tests.ilqr_cases import np_model
+from tests.tracking_cases import SECOND_MODEL as M
 
 
 def _distinguished(m):

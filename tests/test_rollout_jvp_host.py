@@ -4,10 +4,9 @@ entry points that needs no device, and the ctypes table."""
 import numpy as np
 import pytest
 
-from tests import rollout_jvp_ref as RJ
-from tests import rollout_vjp_ref as RV
-from tests.test_gpu_tracking import SHAPES
-from tests.test_rollout_vjp_host import CASES, _problem
+from tests import rollout_ref as RR
+from tests import tracking_cases as TC
+from tests.tracking_cases import CASES, SHAPES
 
 # (N, k_trans): the notebook problem's shape and a few of the tracking shapes
 ADJOINT_SHAPES = [(61, 21)] + [(N, kt) for _, N, kt, _ in (SHAPES[0], SHAPES[4], SHAPES[6], SHAPES[12], SHAPES[18])]
@@ -19,13 +18,13 @@ def test_sweep_is_the_adjoint_of_the_reverse_sweep(N, k_trans, with_gains):
     """<Zbar, J d> = <J' Zbar, d> on random blocks, trajectories and directions: neither side needs an oracle."""
     rng = np.random.default_rng(100 * N + k_trans)
     n = 20 * N - 5
-    F = RV.evaluator_blocks(rng.normal(size=(N - 1, 15, 20)) / 4.0, k_trans)
+    F = RR.evaluator_blocks(rng.normal(size=(N - 1, 15, 20)) / 4.0, k_trans)
     Zref, Zout, Zbar, zd = (rng.normal(size=n) for _ in range(4))
     K = 0.05 * rng.normal(size=(N - 1, 4, 15)) if with_gains else None
     kd = rng.normal(size=(N - 1, 4, 15)) if with_gains else None
     xd = rng.normal(size=15)
-    zb, kb, xb = RV.sweep(F, Zref, K, Zout, Zbar)
-    out = RJ.sweep(F, Zref, K, Zout, zd, kd, xd)
+    zb, kb, xb, _ = RR.sweep_vjp(F, Zref, K, Zout, Zbar)
+    out = RR.sweep_jvp(F, Zref, K, Zout, zd, kd, xd)
     lhs = float(Zbar @ out)
     rhs = float(zb @ zd + xb @ xd + (0.0 if kb is None else kb.reshape(-1) @ kd.reshape(-1)))
     assert abs(lhs - rhs) <= 1e-12 * (abs(lhs) + abs(rhs)), (lhs, rhs)
@@ -34,22 +33,22 @@ def test_sweep_is_the_adjoint_of_the_reverse_sweep(N, k_trans, with_gains):
 @pytest.mark.parametrize("N,k_trans,init_mode", CASES)
 @pytest.mark.parametrize("with_gains", [False, True])
 def test_sweep_matches_complex_step_of_the_whole_rollout(N, k_trans, init_mode, with_gains):
-    Zref, K, x0, _ = _problem(N, k_trans, init_mode, seed=10 * N + k_trans)
+    Zref, K, x0, _ = TC.problem(N, k_trans, init_mode, seed=10 * N + k_trans)
     K = K if with_gains else None
     rng = np.random.default_rng(7 * N + k_trans)
     zd = rng.normal(size=20 * N - 5)
     kd = rng.normal(size=(N - 1, 4, 15)) if with_gains else None
     xd = rng.normal(size=15)
-    Zout = RV.rollout(N, k_trans, init_mode, Zref, K, x0)
-    F = RV.complex_step_blocks(N, k_trans, init_mode, Zout)
+    Zout = RR.rollout(N, k_trans, init_mode, Zref, K, x0)
+    F = RR.complex_step_blocks(N, k_trans, init_mode, Zout)
     for dots in ((zd, kd, xd), (None, None, xd), (zd, None, None)) + (((None, kd, None),) if with_gains else ()):
-        got = RJ.sweep(F, Zref, K, Zout, *dots)
-        ref = RJ.jvp_complex_step(N, k_trans, init_mode, Zref, K, x0, *dots)
-        assert RV.rel(got, ref) <= 1e-8, RV.rel(got, ref)
+        got = RR.sweep_jvp(F, Zref, K, Zout, *dots)
+        ref = RR.jvp_complex_step(N, k_trans, init_mode, Zref, K, x0, None, *dots)
+        assert RR.rel(got, ref) <= 1e-8, RR.rel(got, ref)
     # xref_dot_{N-1} is never read
     zd2 = zd.copy()
     zd2[20 * (N - 1):] += 1.0
-    assert np.array_equal(RJ.sweep(F, Zref, K, Zout, zd2, kd, xd), RJ.sweep(F, Zref, K, Zout, zd, kd, xd))
+    assert np.array_equal(RR.sweep_jvp(F, Zref, K, Zout, zd2, kd, xd), RR.sweep_jvp(F, Zref, K, Zout, zd, kd, xd))
 
 
 def test_entry_points_reject_bad_arguments_without_a_device():

@@ -2,14 +2,14 @@
 oracle's roll-out under np_oracle.model(...) exactly; its complex-step blocks [A B G] against central differences on single
 steps of every mode; both sweeps against a complex step of the whole roll-out in a model direction; the adjoint identity of
 the two numpy sweeps; G's structural pattern; argument validation that needs no device and the ctypes table.  The models are
-drawn around the second model of tests/test_gpu_model.py, never the default: there 1/mb == mf and lb*lb == lb/2 hold bit for
+drawn around the second model (tests/tracking_cases.py), never the default: there 1/mb == mf and lb*lb == lb/2 hold bit for
 bit, and a confused parameter passes."""
 import numpy as np
 import pytest
 
-from tests import rollout_model_ref as MR
-from tests import rollout_vjp_ref as RV
-from tests.test_rollout_vjp_host import CASES, _problem
+from tests import rollout_ref as RR
+from tests import tracking_cases as TC
+from tests.tracking_cases import CASES
 
 # G's pattern from the derivation (DESIGN.md 4.16): (row, parameter) pairs that can be non-zero in some mode
 PATTERN = ({(r, 0) for r in (1, 2, 4, 6, 8, 9, 11, 13)} | {(r, 1) for r in (0, 1, 2, 7, 8, 9)}
@@ -17,7 +17,7 @@ PATTERN = ({(r, 0) for r in (1, 2, 4, 6, 8, 9, 11, 13)} | {(r, 1) for r in (0, 1
 
 
 def _model(seed):
-    return MR.draw_models(1, seed)[0]
+    return RR.draw_models(1, seed, TC.SECOND)[0]
 
 
 @pytest.mark.parametrize("N,k_trans,init_mode", CASES)
@@ -25,20 +25,20 @@ def _model(seed):
 def test_restatement_equals_the_oracle_rollout_under_the_model_exactly(N, k_trans, init_mode, with_gains):
     from oracle import np_oracle as O
 
-    Zref, K, x0, _ = _problem(N, k_trans, init_mode, seed=10 * N + k_trans)
+    Zref, K, x0, _ = TC.problem(N, k_trans, init_mode, seed=10 * N + k_trans)
     K = K if with_gains else None
     th = _model(N + k_trans)
     with O.model(*th):
-        ref = RV.rollout(N, k_trans, init_mode, Zref, K, x0)
-        F_ref = RV.complex_step_blocks(N, k_trans, init_mode, ref)
-    got = MR.rollout(N, k_trans, init_mode, Zref, K, x0, th)
+        ref = RR.rollout(N, k_trans, init_mode, Zref, K, x0)
+        F_ref = RR.complex_step_blocks(N, k_trans, init_mode, ref)
+    got = RR.rollout(N, k_trans, init_mode, Zref, K, x0, th)
     assert np.array_equal(got, ref)
-    assert not np.array_equal(got, RV.rollout(N, k_trans, init_mode, Zref, K, x0))  # and the model is read
+    assert not np.array_equal(got, RR.rollout(N, k_trans, init_mode, Zref, K, x0))  # and the model is read
     # the [A B] part of the blocks is the oracle's (to rounding: a complex model makes tau / Ib a complex division), with
     # the same zeros, and a batch of blocks is the single ones stacked
-    F = MR.complex_step_blocks(N, k_trans, init_mode, got, th)
-    assert MR.rel(F[:, :, :20], F_ref) <= 1e-14 and np.array_equal(F[:, :, :20] == 0.0, F_ref == 0.0)
-    Fb = MR.complex_step_blocks(N, k_trans, init_mode, np.stack([got, got]), np.stack([th, MR.SECOND]))
+    F = RR.complex_step_blocks(N, k_trans, init_mode, got, th)
+    assert RR.rel(F[:, :, :20], F_ref) <= 1e-14 and np.array_equal(F[:, :, :20] == 0.0, F_ref == 0.0)
+    Fb = RR.complex_step_blocks(N, k_trans, init_mode, np.stack([got, got]), np.stack([th, TC.SECOND]))
     assert np.array_equal(Fb[0], F)
 
 
@@ -57,20 +57,20 @@ def test_G_by_complex_step_against_central_differences_and_its_pattern(mode, jum
     # A landing's knots behind the touchdown, where both feet carry force, stepped under every mode's flags (the closed
     # loop's feedback puts force on a free foot too).  The 1/mf^2 entries then lead the block; where the lb column leads, its
     # own truncation error, 2 rel^2 of the entry for a 1/lb^2 law, is the whole of the bar.
-    Zref, _, _, _ = _problem(8, 5, 1, seed=10 * mode + jump)
+    Zref, _, _, _ = TC.problem(8, 5, 1, seed=10 * mode + jump)
     worst = bar = 0.0
     for k in (4, 5, 6):
         x, u = Zref[20 * k: 20 * k + 15], Zref[20 * k + 15: 20 * k + 20]
-        th = MR.SECOND
+        th = TC.SECOND
         z = np.concatenate([x, u])
         # one knot as a two-knot trajectory: k_trans = 2 puts the jump at knot 0, a later k_trans none
         kt, im = (2, mode) if jump else ((3, mode) if mode != 3 else (1, 1))
         Zo = np.concatenate([z, np.zeros(15)])
-        G = MR.complex_step_blocks(2, kt, im, Zo, th)[0][:, 20:]
-        fd = MR.central_difference_G(mode, jump, x, u, th, rel=1e-5)
+        G = RR.complex_step_blocks(2, kt, im, Zo, th)[0][:, 20:]
+        fd = RR.central_difference_G(mode, jump, x, u, th, rel=1e-5)
         scale = np.abs(G).max()
         worst = max(worst, float(np.abs(G - fd).max() / scale))
-        xn = MR.step(mode, jump, x, u, th)
+        xn = RR.model_step(mode, jump, x, u, th)
         bar = max(bar, 2.0 * 1e-5**2 + 2.0 * np.finfo(float).eps * np.abs(xn).max() / (2 * 1e-5 * np.abs(th).min()) / scale)
         for r in range(15):
             for p in range(4):
@@ -94,7 +94,7 @@ def test_G_by_complex_step_against_central_differences_and_its_pattern(mode, jum
 @pytest.mark.parametrize("N,k_trans,init_mode", CASES)
 @pytest.mark.parametrize("with_gains", [False, True])
 def test_sweeps_match_complex_step_of_the_whole_rollout_in_a_model_direction(N, k_trans, init_mode, with_gains):
-    Zref, K, x0, Zbar = _problem(N, k_trans, init_mode, seed=10 * N + k_trans)
+    Zref, K, x0, Zbar = TC.problem(N, k_trans, init_mode, seed=10 * N + k_trans)
     K = K if with_gains else None
     th = _model(3 * N + k_trans)
     rng = np.random.default_rng(7 * N + k_trans)
@@ -102,23 +102,50 @@ def test_sweeps_match_complex_step_of_the_whole_rollout_in_a_model_direction(N, 
     kd = rng.normal(size=(N - 1, 4, 15)) if with_gains else None
     xd = rng.normal(size=15)
     md = th * rng.normal(size=4)
-    Zout = MR.rollout(N, k_trans, init_mode, Zref, K, x0, th)
-    F = MR.complex_step_blocks(N, k_trans, init_mode, Zout, th)
+    Zout = RR.rollout(N, k_trans, init_mode, Zref, K, x0, th)
+    F = RR.complex_step_blocks(N, k_trans, init_mode, Zout, th)
     for dots in ((zd, kd, xd, md), (None, None, None, md), (zd, kd, xd, None)):
-        got = MR.sweep_jvp(F, Zref, K, Zout, *dots)
-        ref = MR.jvp_complex_step(N, k_trans, init_mode, Zref, K, x0, th, *dots)
-        assert MR.rel(got, ref) <= 1e-8, MR.rel(got, ref)
+        got = RR.sweep_jvp(F, Zref, K, Zout, *dots)
+        ref = RR.jvp_complex_step(N, k_trans, init_mode, Zref, K, x0, th, *dots)
+        assert RR.rel(got, ref) <= 1e-8, RR.rel(got, ref)
     # the reverse sweep: model_bar by one complex roll-out per parameter, the other three as without a model
-    zb, kb, xb, mb = MR.sweep_vjp(F, Zref, K, Zout, Zbar)
-    mc = np.array([MR.jvp_complex_step(N, k_trans, init_mode, Zref, K, x0, th, model_dot=e) @ Zbar for e in np.eye(4)])
-    assert MR.rel(mb, mc) <= 1e-8, MR.rel(mb, mc)
-    z0, k0, x0b = RV.sweep(F[:, :, :20], Zref, K, Zout, Zbar)
+    zb, kb, xb, mb = RR.sweep_vjp(F, Zref, K, Zout, Zbar)
+    mc = np.array([RR.jvp_complex_step(N, k_trans, init_mode, Zref, K, x0, th, model_dot=e) @ Zbar for e in np.eye(4)])
+    assert RR.rel(mb, mc) <= 1e-8, RR.rel(mb, mc)
+    z0, k0, x0b, _ = RR.sweep_vjp(F[:, :, :20], Zref, K, Zout, Zbar)
     assert np.array_equal(zb, z0) and np.array_equal(xb, x0b) and (kb is None or np.array_equal(kb, k0))
     # and the two sweeps are adjoint
-    out = MR.sweep_jvp(F, Zref, K, Zout, zd, kd, xd, md)
+    out = RR.sweep_jvp(F, Zref, K, Zout, zd, kd, xd, md)
     lhs = float(Zbar @ out)
     rhs = float(zb @ zd + xb @ xd + mb @ md + (0.0 if kb is None else kb.reshape(-1) @ kd.reshape(-1)))
     assert abs(lhs - rhs) <= 1e-12 * (abs(lhs) + abs(rhs)), (lhs, rhs)
+
+
+@pytest.mark.parametrize("N,k_trans,init_mode", CASES)
+@pytest.mark.parametrize("with_gains", [False, True])
+def test_sweeps_on_blocks_with_G_reduce_to_the_sweeps_without_it_exactly(N, k_trans, init_mode, with_gains):
+    """One statement of each sweep serves blocks with and without G: on [A B G] whose [A B] is a set of 20-column blocks,
+    the reverse sweep's first three outputs, and the forward sweep with model_dot None or all zeros, are the 20-column
+    sweeps' bit for bit."""
+    Zref, K, x0, Zbar = TC.problem(N, k_trans, init_mode, seed=10 * N + k_trans)
+    K = K if with_gains else None
+    th = _model(3 * N + k_trans)
+    rng = np.random.default_rng(7 * N + k_trans)
+    zd = rng.normal(size=20 * N - 5)
+    kd = rng.normal(size=(N - 1, 4, 15)) if with_gains else None
+    xd = rng.normal(size=15)
+    Zout = RR.rollout(N, k_trans, init_mode, Zref, K, x0, th)
+    F20 = RR.complex_step_blocks(N, k_trans, init_mode, Zout)
+    F24 = np.concatenate([F20, RR.complex_step_blocks(N, k_trans, init_mode, Zout, th)[:, :, 20:]], axis=2)
+    assert F24.shape == (N - 1, 15, 24) and np.array_equal(F24[:, :, :20], F20) and F24[:, :, 20:].any()
+    zb, kb, xb, mb = RR.sweep_vjp(F24, Zref, K, Zout, Zbar)
+    z0, k0, x0b, m0 = RR.sweep_vjp(F20, Zref, K, Zout, Zbar)
+    assert m0 is None and mb.any()
+    assert np.array_equal(zb, z0) and np.array_equal(xb, x0b) and ((kb is None and k0 is None) or np.array_equal(kb, k0))
+    ref = RR.sweep_jvp(F20, Zref, K, Zout, zd, kd, xd)
+    assert np.array_equal(RR.sweep_jvp(F24, Zref, K, Zout, zd, kd, xd, None), ref)
+    assert np.array_equal(RR.sweep_jvp(F24, Zref, K, Zout, zd, kd, xd, np.zeros(4)), ref)
+    assert not np.array_equal(RR.sweep_jvp(F24, Zref, K, Zout, zd, kd, xd, th), ref)  # and G is read
 
 
 def test_entry_points_reject_bad_arguments_without_a_device():
@@ -172,7 +199,7 @@ def test_ctypes_table_and_helper():
             params = [q.strip() for q in proto.group(1).split(",")]
             assert len(params) == n and params[0].startswith("qln_handle*")
     second = PlanarQuadruped(g=-9.1, mb=8.7, mf=0.13, lb=0.46)
-    assert np.array_equal(plant_models(second, 3), np.tile(MR.SECOND, (3, 1)))
-    assert np.array_equal(plant_models([second, PlanarQuadruped()], 2), np.array([MR.SECOND, [-9.81, 10.0, 0.1, 0.5]]))
+    assert np.array_equal(plant_models(second, 3), np.tile(TC.SECOND, (3, 1)))
+    assert np.array_equal(plant_models([second, PlanarQuadruped()], 2), np.array([TC.SECOND, [-9.81, 10.0, 0.1, 0.5]]))
     with pytest.raises(ValueError):
         plant_models([second], 2)
