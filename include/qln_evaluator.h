@@ -27,8 +27,8 @@
  * directly: one launch, one synchronisation), a larger one is staged through device memory.
  * qln_eval_hessian_lagrangian_host and qln_solve_host are always staged.  The handle allocates each buffer on first
  * use, zero-filled, and keeps it until qln_destroy.  Four arguments are in-out and copied in whole, so that their
- * entries from n_nlp to z_stride come back as the caller's buffer held them: Zout of qln_tracking_rollout_host,
- * Zref_bar of qln_tracking_rollout_vjp_host, Zout_dot of qln_tracking_rollout_jvp_host (each also in its _model_ form,
+ * entries from n_nlp to z_stride come back as the caller's buffer held them: Zout of qln_tracking_rollout_host (and of
+ * qln_tracking_rollout_guarded_host), Zref_bar of qln_tracking_rollout_vjp_host, Zout_dot of qln_tracking_rollout_jvp_host (each also in its _model_ form,
  * qln_tracking_rollout_model_host and its two sweeps) and Z of qln_solve_host.  The
  * padding of every other result (past n_nlp in the layout of Z, between the problems of c, vals and hvals) comes back as
  * zeros.
@@ -554,6 +554,55 @@ int qln_tracking_rollout_model_jvp_host(qln_handle* h, const double* Zref, const
 int qln_tracking_rollout_model_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                         const double* model, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
                                         double* model_bar);
+/* The closed-loop roll-out with GUARD-TRIGGERED touchdown: contact begins when the free foot reaches the ground, not at a
+ * knot index.  qln_tracking_rollout switches mode at the handle's k_trans whatever the state is, which is the NLP's
+ * schedule; a drop that is not the planned one (higher, or with another foot mass) lands earlier or later than that, and
+ * this call simulates it.  Zref, K, x0, model and Zout mean what they mean for qln_tracking_rollout_model: K == NULL is the
+ * open-loop roll-out, x0 == NULL the handle's x0, model == NULL the handle's model for every problem; Zout must not overlap
+ * Zref, and entries from n_nlp to z_stride are never written.  Knots are 0-based, k = 0..N-2.
+ *   F_k = F_ref,k - K_k (x_k - x_ref,k), h_k = h_ref,k, the product formed as in qln_tracking_rollout.  Gains and reference
+ *   stay indexed by knot, that is by time: they are the controller under test.
+ * Read from the handle: N, each problem's init_mode, x0 and the model.  k_trans is NOT read.
+ * Mode schedule: problem b starts in mode init_mode (one foot stands, the other is free); after touchdown it is in mode 3
+ * for the rest of the roll-out.  There is no lift-off.
+ * Guard, at a knot k that starts in a single-stance mode: y, v are the free foot's height and vertical velocity (mode 1:
+ * x[6], x[13]; mode 2: x[4], x[11]), a = -F_y / mf + g with that foot's applied vertical force (mode 1: u[3]; mode 2: u[1]),
+ * h = u[4].  With the forces held the height over the step is y + v t + a t^2 / 2 exactly, and the first tau in [0, h] at which
+ * it is <= 0 is
+ *     if (y <= 0)                         tau = 0
+ *     else  disc = v*v - 2*a*y;  den = -v + sqrt(disc)
+ *           if (disc >= 0 && den > 0) { tau = 2*y/den;  touchdown iff tau <= h }   else none
+ *   The comparisons are written so that a NaN never triggers a touchdown.  The one expression is the smaller positive root
+ *   for every sign of a and v, in its cancellation-free form (a == 0: -y/v).  sqrt and the division are correctly rounded.
+ * The touchdown step is composite, the applied forces held: (1) an RK4 step of length tau in the flight mode, (2) the jump
+ * map of the knot-scheduled roll-out (y1 = y2 = 0, all four foot velocities 0), (3) an RK4 step of length h - tau in mode 3,
+ * (4) the clock advances by h: x_{k+1}[14] = x_k[14] + h.  Zout's x_{k+1} is the state after the whole composite step, Zout's
+ * u_k is (F_k, h_k) as always.  A step without touchdown is bit for bit the knot-scheduled roll-out's step of that mode.
+ * event (may be NULL: not written; Zout is the same), QLN_TOUCHDOWN_INFO_STRIDE doubles per problem:
+ *   0     the 0-based knot k whose step contains the touchdown, an exact integer; -1 if there is none, and then entries
+ *         1-5 are 0
+ *   1     tau
+ *   2     the clock at touchdown, x_k[14] + tau
+ *   3     the free foot's x at touchdown
+ *   4, 5  its velocity (vx, vy) just before the jump map
+ *   6     the smallest applied vertical force over all knots and over the feet standing at the knot's start (fmin from
+ *         +inf); negative: the ground pulled
+ *   7     0
+ * Two consequences.  A guarded Zout is NOT a trajectory of the handle's knot schedule: qln_tracking_rollout_jvp / _vjp and
+ * qln_tracking_covariance "at the trajectory Zout" do not apply to it, and its dynamics rows under qln_eval_constraint are
+ * non-zero at the touchdown knot.  And under sampled feedback the closed-loop map is DISCONTINUOUS in the initial state
+ * where the touchdown moves from the end of one step to the start of the next: the control of that knot is computed from
+ * the pre-impact state in one case and from the post-impact state in the other.  Open loop (K == NULL) it is continuous.
+ * Derivatives through the event (the saltation term) are not provided; the record holds what they need, the knot and tau.
+ * Device pointers, stream-ordered; needs no cost table.  The device form does not validate model; the host form refuses a
+ * non-finite entry and mb, mf or lb <= 0.  A NULL h, Zref or Zout, or an overlap, is QLN_ERR_INVALID_ARGUMENT. */
+#define QLN_TOUCHDOWN_INFO_STRIDE 8
+int qln_tracking_rollout_guarded(qln_handle* h, const double* Zref, const double* K, const double* x0,
+                                 const double* model /* [B][QLN_MODEL_NP] (g, mb, mf, lb) or NULL = the handle's */,
+                                 double* Zout, double* event /* [B][QLN_TOUCHDOWN_INFO_STRIDE] or NULL */);
+/* the same as a host form (see "Host forms" above; Zout is in-out) */
+int qln_tracking_rollout_guarded_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
+                                      double* Zout, double* event);
 /* Covariance propagation through the closed-loop roll-out: the linear-Gaussian forward sweep along the trajectory Zout
  * holds.  Knots are 0-based, k = 0..N-2, as in qln_tracking_rollout_vjp.
  *   A_k (15x15), B_k (15x4) = d Phi_k / d(x_k, F_k) at Zout's (x_k, u_k): exactly the blocks qln_tracking_rollout_vjp uses --

@@ -262,6 +262,20 @@ function tracking_rollout_model_vjp(prob::HybridNLPHIP, Zref::Vector{Float64}, Z
                     K_bar === nothing ? C_NULL : K_bar, x0_bar, model_bar))
     return Zref_bar, K_bar, x0_bar, model_bar
 end
+# The roll-out with guard-triggered touchdown (include/qln_evaluator.h, DESIGN.md 4.17): contact begins when the free foot
+# reaches the ground, not at the problem's k_trans, which is not read.  Returns (Zout, events); events holds 8 values: the
+# 0-based knot whose step contains the touchdown (-1: none), tau, the clock at touchdown, the foot's x, its (vx, vy) before the
+# jump map, the smallest vertical force under a standing foot, 0.  Zout is not a trajectory of the knot schedule: the jvp / vjp
+# / covariance calls do not apply to it.
+function tracking_rollout_guarded(prob::HybridNLPHIP, Zref::Vector{Float64}; K=nothing, x0=nothing, model=nothing)
+    Zout = zeros(length(Zref))
+    events = zeros(8)
+    qln_check(ccall((:qln_tracking_rollout_guarded_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, K === nothing ? C_NULL : K, x0 === nothing ? C_NULL : x0,
+                    model === nothing ? C_NULL : model, Zout, events))
+    return Zout, events
+end
 # covariance of the roll-out's states along the trajectory Zout (for the nominal case: the reference itself):
 # Sigma_0 = Sigma0, Sigma_{k+1} = (A_k - B_k K_k) Sigma_k (A_k - B_k K_k)' + diag(W); K = nothing is the open loop.
 # Sigma0: a 15x15 matrix (its lower triangle is read); W: 15 variances or nothing (zeros).  Returns Sigma as (120, N) packed

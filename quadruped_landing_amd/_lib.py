@@ -101,6 +101,7 @@ class QlnDropStateSampler(C.Structure):
 
 SOLVE_INFO_STRIDE = 16
 MULT_INFO_STRIDE = 16
+TOUCHDOWN_INFO_STRIDE = 8
 
 
 class QlnError(RuntimeError):
@@ -160,6 +161,8 @@ SIGNATURES = {
     "qln_tracking_rollout_model_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp]),
     "qln_tracking_rollout_model_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "qln_tracking_rollout_model_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "qln_tracking_rollout_guarded": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "qln_tracking_rollout_guarded_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "qln_tracking_covariance": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp]),
     "qln_tracking_covariance_host": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp]),
     "qln_eval_constraint_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp]),

@@ -100,6 +100,7 @@ enum HostRole {
     kMultInfo,  // out: the multiplier estimate's report                    [B][16]
     kModel,  // in: the per-problem plant models                            [B][4]
     kModelD, // in: the model jvp's model_dot; out: the model vjp's model_bar  [B][4]
+    kEvent,  // out: the guarded roll-out's touchdown records               [B][8]
     kHostRoles
 };
 
@@ -175,6 +176,7 @@ int64_t host_role_size(const qln_handle* h, HostRole r) {
         case kX0: return (int64_t)D.B * QLN_NX;
         case kMultInfo: return (int64_t)D.B * QLN_MULT_INFO_STRIDE;
         case kModel: case kModelD: return (int64_t)D.B * QLN_MODEL_NP;
+        case kEvent: return (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
         case kHostRoles: break;
     }
     return 0;
@@ -1163,28 +1165,36 @@ static int check_host_models(const qln_handle* h, const double* model, const cha
     return QLN_OK;
 }
 
-static int check_tracking_rollout_args(const qln_handle* h, const double* Zref, const double* Zout, const char* who) {
+// event: the guarded roll-out's records (null: none asked for)
+static int check_tracking_rollout_args(const qln_handle* h, const double* Zref, const double* Zout, const double* event,
+                                       const char* who) {
     if (int rc = check_handle(h)) return rc;
     if (!Zref || !Zout) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null Zref or Zout");
-    return check_no_overlap({{Zout, h->dims.z_total}}, {{Zref, h->dims.z_total}}, who);  // K, x0 and model are not looked at
+    const int64_t ne = (int64_t)h->dims.B * QLN_TOUCHDOWN_INFO_STRIDE;
+    // K, x0 and model are not looked at
+    return check_no_overlap({{Zout, h->dims.z_total}, {event, ne}}, {{Zref, h->dims.z_total}}, who);
 }
 
+// guarded: qln_tracking_rollout_guarded's touchdown by the free foot's height, with its event records (may be null)
 static int tracking_rollout(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
-                            double* Zout, const char* who) {
-    if (int rc = check_tracking_rollout_args(h, Zref, Zout, who)) return rc;
+                            double* Zout, bool guarded, double* event, const char* who) {
+    if (int rc = check_tracking_rollout_args(h, Zref, Zout, event, who)) return rc;
     if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout(h->p, Zref, K, x0, model, Zout, h->stream));
+    QLN_HIP(qln::launch_tracking_rollout(h->p, Zref, K, x0, model, Zout, guarded, event, h->stream));
     return QLN_OK;
 }
 
 static int tracking_rollout_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
-                                 double* Zout, const char* who) {
-    if (int rc = check_tracking_rollout_args(h, Zref, Zout, who)) return rc;
+                                 double* Zout, bool guarded, double* event, const char* who) {
+    if (int rc = check_tracking_rollout_args(h, Zref, Zout, event, who)) return rc;
     if (int rc = check_host_models(h, model, who)) return rc;
     if (int rc = bind_device(h)) return rc;
-    return host_call(h, {copy_in(kZ, Zref), copy_inout(kZio, Zout), copy_in(kK, K), copy_in(kX0, x0), copy_in(kModel, model)},
+    return host_call(h,
+                     {copy_in(kZ, Zref), copy_inout(kZio, Zout), copy_in(kK, K), copy_in(kX0, x0), copy_in(kModel, model),
+                      copy_out(kEvent, event)},
                      [&](double* const* d, bool) {
-                         return qln::launch_tracking_rollout(h->p, d[kZ], d[kK], d[kX0], d[kModel], d[kZio], h->stream);
+                         return qln::launch_tracking_rollout(h->p, d[kZ], d[kK], d[kX0], d[kModel], d[kZio], guarded, d[kEvent],
+                                                             h->stream);
                      });
 }
 
@@ -1273,20 +1283,28 @@ static int tracking_rollout_jvp_host(qln_handle* h, const double* Zref, const do
 
 // the twelve entry points: the forms without a model are the same path with null model arguments
 int qln_tracking_rollout(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout) {
-    return tracking_rollout(h, Zref, K, x0, nullptr, Zout, "qln_tracking_rollout");
+    return tracking_rollout(h, Zref, K, x0, nullptr, Zout, false, nullptr, "qln_tracking_rollout");
 }
 int qln_tracking_rollout_host(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout) {
-    return tracking_rollout_host(h, Zref, K, x0, nullptr, Zout, "qln_tracking_rollout_host");
+    return tracking_rollout_host(h, Zref, K, x0, nullptr, Zout, false, nullptr, "qln_tracking_rollout_host");
 }
 int qln_tracking_rollout_model(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
                                double* Zout) {
-    return tracking_rollout(h, Zref, K, x0, model, Zout, "qln_tracking_rollout_model");
+    return tracking_rollout(h, Zref, K, x0, model, Zout, false, nullptr, "qln_tracking_rollout_model");
 }
 int qln_tracking_rollout_model_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
                                     double* Zout) {
-    return tracking_rollout_host(h, Zref, K, x0, model, Zout, "qln_tracking_rollout_model_host");
+    return tracking_rollout_host(h, Zref, K, x0, model, Zout, false, nullptr, "qln_tracking_rollout_model_host");
 }
 
+int qln_tracking_rollout_guarded(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
+                                 double* Zout, double* event) {
+    return tracking_rollout(h, Zref, K, x0, model, Zout, true, event, "qln_tracking_rollout_guarded");
+}
+int qln_tracking_rollout_guarded_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
+                                      double* Zout, double* event) {
+    return tracking_rollout_host(h, Zref, K, x0, model, Zout, true, event, "qln_tracking_rollout_guarded_host");
+}
 int qln_tracking_rollout_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
                              double* Zref_bar, double* K_bar, double* x0_bar) {
     return tracking_rollout_vjp(h, Zref, K, Zout, nullptr, Zbar, Zref_bar, K_bar, x0_bar, nullptr, "qln_tracking_rollout_vjp");

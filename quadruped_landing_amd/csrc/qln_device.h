@@ -302,8 +302,9 @@ hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const dou
 // layout.  Reverse: cotangent Zbar -> Zref_bar, K_bar, x0_bar, model_bar (each may be null).  Forward: tangents Zref_dot, K_dot,
 // x0_dot, model_dot (each may be null: zero) -> Zout_dot in the layout of Z.  K_bar and K_dot need K and read Zref's states.
 // With nothing of the model passed the kernels run without their kModel flag (qln_tracking_kernels.hip).
+// guarded: touchdown by the free foot's height instead of the knot schedule; event [B][QLN_TOUCHDOWN_INFO_STRIDE] or null
 hipError_t launch_tracking_rollout(const BatchParams& p, const double* Zref, const double* K, const double* x0,
-                                   const double* model, double* Zout, hipStream_t stream);
+                                   const double* model, double* Zout, bool guarded, double* event, hipStream_t stream);
 hipError_t launch_tracking_rollout_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
                                        const double* model, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
                                        double* model_bar, hipStream_t stream);

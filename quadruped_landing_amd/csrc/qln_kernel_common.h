@@ -1,6 +1,6 @@
 // qln_kernel_common.h -- device code shared by the gfx950 kernel files.  Internal.
 //   * wave / dispatch helpers (xcd_contiguous_index, wave_lds_sync, wave_sum, wave_max);
-//   * the value path: dynamics, rk4_step, step_forward (one knot of a roll-out), literal restatements of the reference
+//   * the value path: dynamics, rk4_step, step_mode / step_forward (one knot of a roll-out), literal restatements of the reference
 //     that round like it;
 //   * clearance_dtheta, the one derivative entry of the clearance rows (the J v / J' lam products and the covariance
 //     sweep's clearance marginal read it);
@@ -95,10 +95,10 @@ __device__ __forceinline__ void dynamics(const double (&s)[14], const double (&u
     f[13] = k.a2y;
 }
 
-// contact*_dynamics_rk4 (src/planar_quadruped.jl:189-221)
-__device__ __forceinline__ void rk4_step(const double (&x)[15], const double (&u)[5], const StepConst& k, bool f1free,
+// contact*_dynamics_rk4 (src/planar_quadruped.jl:189-221) over a step of length h, which need not be u[4]: the guarded
+// roll-out splits a knot's step at the touchdown and holds the forces over both parts
+__device__ __forceinline__ void rk4_step(const double (&x)[15], const double (&u)[5], double h, const StepConst& k, bool f1free,
                                          bool f2free, double Ib, double (&xn)[15]) {
-    const double h = u[4];
     const double hh = 0.5 * h;
     double s0[14], s[14], f1[14], f2[14], f3[14], f4[14];
 #pragma unroll
@@ -116,13 +116,24 @@ __device__ __forceinline__ void rk4_step(const double (&x)[15], const double (&u
     const double h6 = h / 6.0;
 #pragma unroll
     for (int i = 0; i < 14; ++i) xn[i] = s0[i] + h6 * (((f1[i] + 2 * f2[i]) + 2 * f3[i]) + f4[i]);
-    xn[14] = x[14] + u[4];
+    xn[14] = x[14] + h;
+}
+__device__ __forceinline__ void rk4_step(const double (&x)[15], const double (&u)[5], const StepConst& k, bool f1free,
+                                         bool f2free, double Ib, double (&xn)[15]) {
+    rk4_step(x, u, u[4], k, f1free, f2free, Ib, xn);
 }
 
-// one dynamics knot of a roll-out (qln_solve's and qln_tracking_rollout's): the evaluator's RK4 step + jump map (src/constraints.jl:19-38)
-__device__ __forceinline__ void step_forward(const Model& M, int k, int kt, int im, const double (&x)[15], const double (&u)[5],
-                                             double (&xn)[15]) {
-    const KnotMode md = knot_mode(k + 1, kt - 1, im);
+// the jump map of a touchdown (src/constraints.jl:19-38): both feet on the ground and at rest; the clock is kept
+__device__ __forceinline__ void jump_map(double (&xn)[15]) {
+    xn[4] = 0.0;
+    xn[6] = 0.0;
+    xn[10] = xn[11] = xn[12] = xn[13] = 0.0;
+}
+
+// The RK4 step of length h in the contact mode md with the forces u[0..3] held, then md's jump map: step_forward's body with
+// the mode and the step length as arguments (the guarded roll-out takes the parts of a touchdown step with it).
+__device__ __forceinline__ void step_mode(const Model& M, const KnotMode md, double h, const double (&x)[15],
+                                          const double (&u)[5], double (&xn)[15]) {
     StepConst sc;
     sc.abx = (u[0] + u[2]) / M.mb;
     sc.aby = (u[1] + u[3]) / M.mb + M.g;
@@ -130,12 +141,14 @@ __device__ __forceinline__ void step_forward(const Model& M, int k, int kt, int 
     sc.a1y = md.f1free ? (-u[1] / M.mf + M.g) : 0.0;
     sc.a2x = md.f2free ? (-u[2] / M.mf) : 0.0;
     sc.a2y = md.f2free ? (-u[3] / M.mf + M.g) : 0.0;
-    rk4_step(x, u, sc, md.f1free, md.f2free, M.Ib, xn);
-    if (md.jump) {
-        xn[4] = 0.0;
-        xn[6] = 0.0;
-        xn[10] = xn[11] = xn[12] = xn[13] = 0.0;
-    }
+    rk4_step(x, u, h, sc, md.f1free, md.f2free, M.Ib, xn);
+    if (md.jump) jump_map(xn);
+}
+
+// one dynamics knot of a roll-out (qln_solve's and qln_tracking_rollout's): the evaluator's RK4 step + jump map (src/constraints.jl:19-38)
+__device__ __forceinline__ void step_forward(const Model& M, int k, int kt, int im, const double (&x)[15], const double (&u)[5],
+                                             double (&xn)[15]) {
+    step_mode(M, knot_mode(k + 1, kt - 1, im), u[4], x, u, xn);
 }
 
 // d(clearance_k)/d(theta_k), src/constraints.jl:269-273 (theta == 0 takes the + branch, quirk Q3)

@@ -19,7 +19,9 @@
 // Every kernel here that needs the roll-out's A_k, B_k takes them from for_each_rollout_entry (qln_kernel_common.h): the
 // evaluator's block with the jump map's clock row.  The mapping, the DPP moves and the knot's load / store are qln_row16.h's.
 //
-// k_tracking_rollout: one lane per problem, the solver's step_forward (qln_kernel_common.h) on the fed-back forces.
+// k_tracking_rollout: one lane per problem, the solver's step_forward (qln_kernel_common.h) on the fed-back forces.  With
+// the flag kGuard (qln_tracking_rollout_guarded) the contact mode is the lane's own state instead of the
+// handle's knot schedule: touchdown happens in the step in which the free foot reaches the ground, located in closed form.
 //
 // k_tracking_rollout_vjp: the reverse sweep of the roll-out.  One problem per row of sixteen lanes, as
 // k_tracking_lqr; lane j < 15 owns lam[j], column j of A_k, row j of B_k and of the h column, and column j of K and K_bar;
@@ -283,13 +285,69 @@ __global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeig
     }
 }
 
+// what the guarded roll-out reports of a problem's touchdown (entries 0..6 of its event record, include/qln_evaluator.h)
+struct Touchdown {
+    double knot, tau, clock, px, vx, vy, fmin;
+};
+
+// One knot of the guarded roll-out, started in `mode` (1, 2: one foot free; 3: both standing; updated).  The free foot's
+// height under held forces is y + v t + a t^2 / 2, a = -F_y / mf + g; its first root in [0, h] is taken in the
+// cancellation-free form 2 y / (-v + sqrt(v^2 - 2 a y)), and every comparison is false on a NaN.  Without a touchdown the
+// step is step_forward's of the flight mode (the same bits); with one it is RK4 over tau in the flight mode, the jump map,
+// RK4 over h - tau in mode 3, the forces held, and the clock advanced by h.  y, v and F_y are selected, never indexed: a
+// private array indexed at run time is laid out in scratch memory.
+__device__ __forceinline__ void guarded_step(const Model& M, int k, int& mode, const double (&x)[15], const double (&u)[5],
+                                             double (&xn)[15], Touchdown& td) {
+    const double h = u[4];
+    const bool m1 = mode == 1, m3 = mode == 3;
+    // the feet standing at the knot's start: foot 1 in mode 1, foot 2 in mode 2, both in mode 3
+    td.fmin = fmin(td.fmin, m3 ? fmin(u[1], u[3]) : m1 ? u[1] : u[3]);
+    bool hit = false;
+    double tau = 0.0;
+    if (!m3) {
+        const double y = m1 ? x[6] : x[4], v = m1 ? x[13] : x[11], Fy = m1 ? u[3] : u[1];
+        const double a = -Fy / M.mf + M.g;
+        if (y <= 0.0) {
+            hit = true;
+        } else {
+            const double disc = v * v - 2 * a * y;
+            const double den = -v + sqrt(disc);
+            if (disc >= 0.0 && den > 0.0) {
+                tau = 2 * y / den;
+                hit = tau <= h;
+            }
+        }
+    }
+    const KnotMode md = {mode == 2, m1, false, m3};
+    step_mode(M, md, hit ? tau : h, x, u, xn);
+    if (hit) {
+        td.knot = (double)k;
+        td.tau = tau;
+        td.clock = x[14] + tau;
+        td.px = m1 ? xn[5] : xn[3];
+        td.vx = m1 ? xn[12] : xn[10];
+        td.vy = m1 ? xn[13] : xn[11];
+        double xm[15];
+#pragma unroll
+        for (int i = 0; i < 15; ++i) xm[i] = xn[i];
+        jump_map(xm);
+        step_mode(M, KnotMode{false, false, false, true}, h - tau, xm, u, xn);
+        xn[14] = x[14] + h;
+        mode = 3;
+    }
+}
+
 // x_1 = x0[b] (or the handle's x0), F_k = F_ref,k - K_k (x_k - x_ref,k), h_k = h_ref,k, x_{k+1} = step_forward.
 // kModel: the plant of problem b is model[b] = (g, mb, mf, lb) instead of the handle's model (qln_tracking_rollout_model);
 // the same step_forward on it, so equal models give equal bits.
-template <bool kModel>
+// kGuard (qln_tracking_rollout_guarded): the handle's k_trans is not read.  The problem stays in init_mode until its free
+// foot reaches the ground; the knot in which it does takes the composite step of guarded_step, and every later knot is in
+// mode 3.  event (null: not written) gets the problem's QLN_TOUCHDOWN_INFO_STRIDE doubles after the last knot.
+template <bool kModel, bool kGuard>
 __global__ __launch_bounds__(kWave) void k_tracking_rollout(BatchParams P, const double* __restrict__ Zref,
                                                             const double* __restrict__ Kg, const double* __restrict__ x0,
-                                                            double* __restrict__ Zout, const double* __restrict__ model) {
+                                                            double* __restrict__ Zout, const double* __restrict__ model,
+                                                            double* __restrict__ event) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= P.B) return;
     const ProblemDesc pd = P.desc[b];
@@ -304,6 +362,8 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout(BatchParams P, const
         x[i] = xs[i];
         Zo[i] = x[i];
     }
+    int mode = im;
+    Touchdown td = {-1.0, 0.0, 0.0, 0.0, 0.0, 0.0, __builtin_inf()};
     for (int k = 0; k < N - 1; ++k) {
 #pragma unroll
         for (int i = 0; i < 5; ++i) u[i] = Zr[20 * k + 15 + i];
@@ -322,11 +382,25 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout(BatchParams P, const
         }
 #pragma unroll
         for (int i = 0; i < 5; ++i) Zo[20 * k + 15 + i] = u[i];
-        step_forward(M, k, kt, im, x, u, xn);
+        if constexpr (kGuard) guarded_step(M, k, mode, x, u, xn, td);
+        else step_forward(M, k, kt, im, x, u, xn);
 #pragma unroll
         for (int i = 0; i < 15; ++i) {
             x[i] = xn[i];
             Zo[20 * (k + 1) + i] = xn[i];
+        }
+    }
+    if constexpr (kGuard) {
+        if (event) {
+            double* __restrict__ ev = event + (int64_t)QLN_TOUCHDOWN_INFO_STRIDE * b;
+            ev[0] = td.knot;
+            ev[1] = td.tau;
+            ev[2] = td.clock;
+            ev[3] = td.px;
+            ev[4] = td.vx;
+            ev[5] = td.vy;
+            ev[6] = td.fmin;
+            ev[7] = 0.0;
         }
     }
 }
@@ -849,11 +923,14 @@ hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const dou
 // The roll-out and its two sweeps.  kModel is on only where something of the model is passed: the forms at the handle's model
 // pass null and run the instantiation without the flag.
 hipError_t launch_tracking_rollout(const BatchParams& p, const double* Zref, const double* K, const double* x0,
-                                   const double* model, double* Zout, hipStream_t stream) {
+                                   const double* model, double* Zout, bool guarded, double* event, hipStream_t stream) {
     auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3((p.B + kWave - 1) / kWave), dim3(kWave), 0, stream, p, Zref, K, x0, Zout, model);
+        hipLaunchKernelGGL(kern, dim3((p.B + kWave - 1) / kWave), dim3(kWave), 0, stream, p, Zref, K, x0, Zout, model, event);
     };
-    model ? go(k_tracking_rollout<true>) : go(k_tracking_rollout<false>);
+    if (guarded)
+        model ? go(k_tracking_rollout<true, true>) : go(k_tracking_rollout<false, true>);
+    else
+        model ? go(k_tracking_rollout<true, false>) : go(k_tracking_rollout<false, false>);
     return hipGetLastError();
 }
 

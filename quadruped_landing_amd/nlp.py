@@ -771,6 +771,37 @@ class HybridNLP:
         """The same with host arrays (synchronous): returns a (z_total,) numpy array (zeros past n_nlp)."""
         return self._rollout_jvp_host(True, Zref, Zout, K, model, Zref_dot, K_dot, x0_dot, model_dot)
 
+    # -- the roll-out with guard-triggered touchdown -------------------------------------------------
+    def tracking_rollout_guarded(self, Zref, K=None, x0=None, model=None, out=None, with_events=True):
+        """tracking_rollout_model with touchdown when the free foot reaches the ground instead of at the handle's k_trans
+        (which is not read): the event is located inside its step in closed form, the step is split there, and the problem
+        is in mode 3 from then on.  Returns (Zout, events): events is a (B, 8) float64 device tensor of {knot (-1: none),
+        tau, clock at touchdown, the foot's x, its (vx, vy) before the jump map, the smallest standing-foot vertical force,
+        0}, None without with_events.  Zout is not a trajectory of the handle's schedule: the jvp / vjp / covariance calls
+        do not apply to it (qln_evaluator.h)."""
+        T = _torch()
+        self._check(Zref, self.dims.z_total, "Zref")
+        out = self.new_Z() if out is None else out
+        self._check(out, self.dims.z_total, "out")
+        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        xp = self._check_opt(x0, self.B * n, "x0")
+        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
+        ev = T.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE), dtype=T.float64, device=self._dev()) if with_events else None
+        _lib.check(_lib.lib().qln_tracking_rollout_guarded(self._h, Zref.data_ptr(), kp, xp, mp, out.data_ptr(),
+                                                           None if ev is None else ev.data_ptr()))
+        return out, ev
+
+    def tracking_rollout_guarded_host(self, Zref, K=None, x0=None, model=None, with_events=True):
+        """The same with host arrays (synchronous): returns numpy (Zout (z_total,), zeros past n_nlp, events (B, 8) or None).
+        A non-finite model entry, or mb, mf or lb <= 0, is refused."""
+        Zref, K, x0 = self._host_Z(Zref, "Zref"), self._host_K(K), self._host_x0(x0)
+        model = self._host_model(model)
+        out = np.zeros(self.dims.z_total)
+        ev = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if with_events else None
+        _lib.check(_lib.lib().qln_tracking_rollout_guarded_host(self._h, Zref.ctypes.data, _host_ptr(K), _host_ptr(x0),
+                                                                _host_ptr(model), out.ctypes.data, _host_ptr(ev)))
+        return out, ev
+
     # -- covariance propagation through the closed-loop roll-out -----------------------------------
     def tracking_covariance(self, Zout, K=None, Sigma0=None, W=None, with_sigma=True, with_marginals=True, Sigma=None,
                             marg=None):
