@@ -588,12 +588,14 @@ int qln_tracking_rollout_model_vjp_host(qln_handle* h, const double* Zref, const
  *   6     the smallest applied vertical force over all knots and over the feet standing at the knot's start (fmin from
  *         +inf); negative: the ground pulled
  *   7     0
- * Two consequences.  A guarded Zout is NOT a trajectory of the handle's knot schedule: qln_tracking_rollout_jvp / _vjp and
- * qln_tracking_covariance "at the trajectory Zout" do not apply to it, and its dynamics rows under qln_eval_constraint are
- * non-zero at the touchdown knot.  And under sampled feedback the closed-loop map is DISCONTINUOUS in the initial state
+ * Two consequences.  A guarded Zout is NOT a trajectory of the handle's knot schedule: its derivatives are
+ * qln_tracking_rollout_guarded_jvp / _vjp below, which take the event record; qln_tracking_rollout_jvp / _vjp, their _model_
+ * forms and qln_tracking_covariance "at the trajectory Zout" do not apply to it, and its dynamics rows under
+ * qln_eval_constraint are non-zero at the touchdown knot.  And under sampled feedback the closed-loop map is DISCONTINUOUS in the initial state
  * where the touchdown moves from the end of one step to the start of the next: the control of that knot is computed from
  * the pre-impact state in one case and from the post-impact state in the other.  Open loop (K == NULL) it is continuous.
- * Derivatives through the event (the saltation term) are not provided; the record holds what they need, the knot and tau.
+ * Derivatives through the event, the saltation term included, are qln_tracking_rollout_guarded_jvp / _vjp: they read the knot
+ * and tau from the record.
  * Device pointers, stream-ordered; needs no cost table.  The device form does not validate model; the host form refuses a
  * non-finite entry and mb, mf or lb <= 0.  A NULL h, Zref or Zout, or an overlap, is QLN_ERR_INVALID_ARGUMENT. */
 #define QLN_TOUCHDOWN_INFO_STRIDE 8
@@ -603,6 +605,56 @@ int qln_tracking_rollout_guarded(qln_handle* h, const double* Zref, const double
 /* the same as a host form (see "Host forms" above; Zout is in-out) */
 int qln_tracking_rollout_guarded_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
                                       double* Zout, double* event);
+/* Forward and reverse sweeps THROUGH the guard-triggered touchdown: the derivative of qln_tracking_rollout_guarded at the
+ * trajectory Zout holds, at FIXED touchdown knot.  Knots are 0-based, k = 0..N-2.  The arguments are those of
+ * qln_tracking_rollout_model_jvp / _vjp plus
+ *   event: device, [B][QLN_TOUCHDOWN_INFO_STRIDE], the record the guarded roll-out wrote.  Required.  Only entries 0 (the knot
+ *          k*) and 1 (tau) are read; k* < 0 or beyond N-2 means no touchdown.
+ * k_trans is not read.  As with the other sweeps nothing is re-run, and nothing checks that Zout / event are the roll-out of
+ * the inputs.  m is the problem's init_mode, theta_b its model (model == NULL: the handle's).
+ * Block per knot, at Zout's (x_k, u_k) and theta_b:
+ *   k < k*, or no touchdown:  [A_k B_k G_k] of mode m, no jump;
+ *   k > k*:                    the same in mode 3;
+ *   k == k*: the composite step.  The forces F = u_k[0:4] are held and h = u_k[4]; y, v, F_y are the free foot's, selected as
+ *     by the guard above, a = -F_y / mf + g.
+ *       x- = RK4_m(x_k, F; tau), recomputed as the forward call forms it; w = x-[iv], the foot's vertical velocity before the
+ *            jump map;
+ *       dtau = -(dy + tau dv + (tau^2 / 2) da) / w,   da = -dF_y / mf + (F_y / mf^2) dmf + dg;
+ *              dtau = 0 where the guard's first branch was taken (x_k[iy] <= 0, tau = 0);
+ *       dx- = A_m dx_k + B_m dF + b_m dtau + G_m dtheta    (mode m's block at step length tau; b is the block's h column)
+ *       dx+ = dx- with entries 4, 6, 10-13 set to zero      (the jump map)
+ *       dx_{k+1} = A_3 dx+ + B_3 dF + b_3 (dh - dtau) + G_3 dtheta    (the mode-3 block at (x+, F, h - tau))
+ *     The clock rows of the two legs add up to dx_k[14] + dh by themselves.
+ * Forward sweep (qln_tracking_rollout_guarded_jvp): qln_tracking_rollout_model_jvp's recursion on these blocks; tangents,
+ *   NULL rules, Zout_dot and overlap rules are the same.  One optional output more,
+ *   event_dot: [B][QLN_TOUCHDOWN_INFO_STRIDE] or NULL (not written).  Entry 1 is dtau, entry 2 is dx_{k*}[14] + dtau, the
+ *              tangent of the touchdown clock; every other entry is 0, and the whole record is 0 without a touchdown.
+ * Reverse sweep (qln_tracking_rollout_guarded_vjp): qln_tracking_rollout_model_vjp's recursion; at k* the exact transpose of
+ *   the sequence above.  Through the mode-3 leg lam+ = A_3' lam, ubar_F += B_3' lam, hbar += b_3' lam, taubar = -b_3' lam,
+ *   model_bar += G_3' lam; through the jump map the six entries of lam+ are zeroed; through the flight leg the same with
+ *   taubar += b_m' lam-.  taubar is then distributed by dtau's coefficients onto lam_k[iy] and lam_k[iv], onto the free foot's
+ *   ubar_F_y -- before that ubar enters K_k' ubar, K_bar and Zref_bar -- and onto model_bar[g] and model_bar[mf].  It is the
+ *   exact adjoint of the forward sweep on (Zref, K, x0, model) -> Zout:
+ *   <Zbar, Zout_dot> = <Zref_bar, Zref_dot> + <K_bar, K_dot> + <x0_bar, x0_dot> + <model_bar, model_dot>.
+ *   event_dot has no cotangent.
+ * Limits.  The result is the derivative at fixed touchdown knot: where the knot changes the closed-loop map is discontinuous
+ * (above) and no derivative exists.  It scales with 1 / |w|: a grazing touchdown has no useful derivative.
+ * Errors: a NULL event is QLN_ERR_INVALID_ARGUMENT; the other NULL combinations are the _model_ sweeps'.  The device forms
+ * do not validate event; the host forms refuse a knot that is not an integer in [-1, N-2] and a tau that is not finite or is
+ * negative.  event and event_dot take part in the overlap rule.  Device pointers, stream-ordered; needs no cost table. */
+int qln_tracking_rollout_guarded_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
+                                     const double* event, const double* Zref_dot, const double* K_dot, const double* x0_dot,
+                                     const double* model_dot, double* Zout_dot, double* event_dot);
+int qln_tracking_rollout_guarded_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
+                                     const double* event, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
+                                     double* model_bar);
+/* the same as host forms (see "Host forms" above; Zout_dot and Zref_bar are in-out as in the _model_ forms) */
+int qln_tracking_rollout_guarded_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                          const double* model, const double* event, const double* Zref_dot, const double* K_dot,
+                                          const double* x0_dot, const double* model_dot, double* Zout_dot, double* event_dot);
+int qln_tracking_rollout_guarded_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                          const double* model, const double* event, const double* Zbar, double* Zref_bar,
+                                          double* K_bar, double* x0_bar, double* model_bar);
 /* Covariance propagation through the closed-loop roll-out: the linear-Gaussian forward sweep along the trajectory Zout
  * holds.  Knots are 0-based, k = 0..N-2, as in qln_tracking_rollout_vjp.
  *   A_k (15x15), B_k (15x4) = d Phi_k / d(x_k, F_k) at Zout's (x_k, u_k): exactly the blocks qln_tracking_rollout_vjp uses --

@@ -265,8 +265,8 @@ end
 # The roll-out with guard-triggered touchdown (include/qln_evaluator.h, DESIGN.md 4.17): contact begins when the free foot
 # reaches the ground, not at the problem's k_trans, which is not read.  Returns (Zout, events); events holds 8 values: the
 # 0-based knot whose step contains the touchdown (-1: none), tau, the clock at touchdown, the foot's x, its (vx, vy) before the
-# jump map, the smallest vertical force under a standing foot, 0.  Zout is not a trajectory of the knot schedule: the jvp / vjp
-# / covariance calls do not apply to it.
+# jump map, the smallest vertical force under a standing foot, 0.  Zout is not a trajectory of the knot schedule: its
+# derivatives are tracking_rollout_guarded_jvp / _vjp below; the other jvp / vjp / covariance calls do not apply to it.
 function tracking_rollout_guarded(prob::HybridNLPHIP, Zref::Vector{Float64}; K=nothing, x0=nothing, model=nothing)
     Zout = zeros(length(Zref))
     events = zeros(8)
@@ -275,6 +275,36 @@ function tracking_rollout_guarded(prob::HybridNLPHIP, Zref::Vector{Float64}; K=n
                     prob.handle, Zref, K === nothing ? C_NULL : K, x0 === nothing ? C_NULL : x0,
                     model === nothing ? C_NULL : model, Zout, events))
     return Zout, events
+end
+# The sweeps through the guard-triggered touchdown (include/qln_evaluator.h, DESIGN.md 4.18): the derivative of
+# tracking_rollout_guarded at the (Zout, events) it returned, at fixed touchdown knot, with the derivative of the touchdown
+# time.  Tangents and cotangents are tracking_rollout_model_jvp's / _vjp's; the forward sweep also returns event_dot (8 values:
+# d tau in entry 2, the touchdown clock's tangent in entry 3, 1-based, zeros elsewhere).
+function tracking_rollout_guarded_jvp(prob::HybridNLPHIP, Zref::Vector{Float64}, Zout::Vector{Float64}, events::Vector{Float64};
+                                      K=nothing, model=nothing, Zref_dot=nothing, K_dot=nothing, x0_dot=nothing,
+                                      model_dot=nothing)
+    Zout_dot = zeros(length(Zref))
+    event_dot = zeros(8)
+    qln_check(ccall((:qln_tracking_rollout_guarded_jvp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, K === nothing ? C_NULL : K, Zout, model === nothing ? C_NULL : model, events,
+                    Zref_dot === nothing ? C_NULL : Zref_dot, K_dot === nothing ? C_NULL : K_dot,
+                    x0_dot === nothing ? C_NULL : x0_dot, model_dot === nothing ? C_NULL : model_dot, Zout_dot, event_dot))
+    return Zout_dot, event_dot
+end
+function tracking_rollout_guarded_vjp(prob::HybridNLPHIP, Zref::Vector{Float64}, Zout::Vector{Float64}, events::Vector{Float64},
+                                      Zbar::Vector{Float64}; K=nothing, model=nothing)
+    Zref_bar = zeros(length(Zref))
+    K_bar = K === nothing ? nothing : zeros(size(K))
+    x0_bar = zeros(15)
+    model_bar = zeros(4)
+    qln_check(ccall((:qln_tracking_rollout_guarded_vjp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, K === nothing ? C_NULL : K, Zout, model === nothing ? C_NULL : model, events, Zbar,
+                    Zref_bar, K_bar === nothing ? C_NULL : K_bar, x0_bar, model_bar))
+    return Zref_bar, K_bar, x0_bar, model_bar
 end
 # covariance of the roll-out's states along the trajectory Zout (for the nominal case: the reference itself):
 # Sigma_0 = Sigma0, Sigma_{k+1} = (A_k - B_k K_k) Sigma_k (A_k - B_k K_k)' + diag(W); K = nothing is the open loop.

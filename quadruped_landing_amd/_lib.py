@@ -163,6 +163,10 @@ SIGNATURES = {
     "qln_tracking_rollout_model_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "qln_tracking_rollout_guarded": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "qln_tracking_rollout_guarded_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "qln_tracking_rollout_guarded_jvp": (C.c_int, [_vp] + [_dp] * 11),
+    "qln_tracking_rollout_guarded_vjp": (C.c_int, [_vp] + [_dp] * 10),
+    "qln_tracking_rollout_guarded_jvp_host": (C.c_int, [_vp] + [_dp] * 11),
+    "qln_tracking_rollout_guarded_vjp_host": (C.c_int, [_vp] + [_dp] * 10),
     "qln_tracking_covariance": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp]),
     "qln_tracking_covariance_host": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp]),
     "qln_eval_constraint_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp]),

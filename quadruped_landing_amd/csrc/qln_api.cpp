@@ -100,7 +100,8 @@ enum HostRole {
     kMultInfo,  // out: the multiplier estimate's report                    [B][16]
     kModel,  // in: the per-problem plant models                            [B][4]
     kModelD, // in: the model jvp's model_dot; out: the model vjp's model_bar  [B][4]
-    kEvent,  // out: the guarded roll-out's touchdown records               [B][8]
+    kEvent,  // out: the guarded roll-out's touchdown records; in: the same for its sweeps  [B][8]
+    kEventD, // out: the guarded jvp's event_dot                            [B][8]
     kHostRoles
 };
 
@@ -176,7 +177,7 @@ int64_t host_role_size(const qln_handle* h, HostRole r) {
         case kX0: return (int64_t)D.B * QLN_NX;
         case kMultInfo: return (int64_t)D.B * QLN_MULT_INFO_STRIDE;
         case kModel: case kModelD: return (int64_t)D.B * QLN_MODEL_NP;
-        case kEvent: return (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
+        case kEvent: case kEventD: return (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
         case kHostRoles: break;
     }
     return 0;
@@ -1199,50 +1200,75 @@ static int tracking_rollout_host(qln_handle* h, const double* Zref, const double
 }
 
 // the reverse sweep: the handle first
+// guarded: the sweeps through the guard-triggered touchdown, which need the roll-out's event records
 static int check_tracking_vjp_args(const qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                   const double* model, const double* Zbar, const double* Zref_bar, const double* K_bar,
-                                   const double* x0_bar, const double* model_bar, const char* who) {
+                                   const double* model, bool guarded, const double* event, const double* Zbar,
+                                   const double* Zref_bar, const double* K_bar, const double* x0_bar, const double* model_bar,
+                                   const char* who) {
     if (int rc = check_handle(h)) return rc;
     const std::string w(who);
     if (!Zref || !Zout || !Zbar) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref, Zout or Zbar");
+    if (guarded && !event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
     if (K_bar && !K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_bar needs K (K == NULL has no gains to differentiate)");
     const qln_dims& D = h->dims;
     const int64_t nz = D.z_total, nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX, nm = (int64_t)D.B * QLN_MODEL_NP;
+    const int64_t ne = (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
     return check_no_overlap({{Zref_bar, nz}, {K_bar, nk}, {x0_bar, nx}, {model_bar, nm}},
-                            {{Zref, nz}, {K, nk}, {Zout, nz}, {Zbar, nz}, {model, nm}}, w);
+                            {{Zref, nz}, {K, nk}, {Zout, nz}, {Zbar, nz}, {model, nm}, {event, ne}}, w);
+}
+
+// host forms only: the knot an integer in [-1, N-2], tau finite and >= 0 (the device forms do not look at the values)
+static int check_host_events(const qln_handle* h, const double* event, const char* who) {
+    if (!event) return QLN_OK;
+    for (int64_t b = 0; b < h->dims.B; ++b) {
+        const double knot = event[b * QLN_TOUCHDOWN_INFO_STRIDE], tau = event[b * QLN_TOUCHDOWN_INFO_STRIDE + 1];
+        if (!(knot >= -1.0 && knot <= (double)(h->dims.N - 2)) || knot != std::floor(knot))
+            return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": event[" + std::to_string(b) +
+                                                      "][0] is not a knot of the roll-out (an integer in [-1, N-2])");
+        if (!std::isfinite(tau) || tau < 0.0)
+            return fail(QLN_ERR_INVALID_ARGUMENT,
+                        std::string(who) + ": event[" + std::to_string(b) + "][1] (tau) is not finite or is negative");
+    }
+    return QLN_OK;
 }
 
 static int tracking_rollout_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
-                                const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar,
-                                const char* who) {
-    if (int rc = check_tracking_vjp_args(h, Zref, K, Zout, model, Zbar, Zref_bar, K_bar, x0_bar, model_bar, who)) return rc;
+                                bool guarded, const double* event, const double* Zbar, double* Zref_bar, double* K_bar,
+                                double* x0_bar, double* model_bar, const char* who) {
+    if (int rc = check_tracking_vjp_args(h, Zref, K, Zout, model, guarded, event, Zbar, Zref_bar, K_bar, x0_bar, model_bar, who))
+        return rc;
     if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout_vjp(h->p, Zref, K, Zout, model, Zbar, Zref_bar, K_bar, x0_bar, model_bar, h->stream));
+    QLN_HIP(qln::launch_tracking_rollout_vjp(h->p, Zref, K, Zout, model, event, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
+                                             h->stream));
     return QLN_OK;
 }
 
 // Zref is staged only when K_bar asks for it (the kernel reads it for nothing else); otherwise Zout's buffer stands in.
 static int tracking_rollout_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                     const double* model, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
-                                     double* model_bar, const char* who) {
-    if (int rc = check_tracking_vjp_args(h, Zref, K, Zout, model, Zbar, Zref_bar, K_bar, x0_bar, model_bar, who)) return rc;
+                                     const double* model, bool guarded, const double* event, const double* Zbar,
+                                     double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar, const char* who) {
+    if (int rc = check_tracking_vjp_args(h, Zref, K, Zout, model, guarded, event, Zbar, Zref_bar, K_bar, x0_bar, model_bar, who))
+        return rc;
     if (int rc = check_host_models(h, model, who)) return rc;
+    if (int rc = check_host_events(h, event, who)) return rc;
     if (int rc = bind_device(h)) return rc;
     return host_call(h,
                      {copy_in(kV, Zout), copy_in(kZbar, Zbar), copy_in(kZ, K_bar ? Zref : nullptr), copy_in(kK, K),
-                      copy_in(kModel, model), copy_inout(kZio, Zref_bar), copy_out(kKbar, K_bar), copy_out(kX0, x0_bar),
-                      copy_out(kModelD, model_bar)},
+                      copy_in(kModel, model), copy_in(kEvent, event), copy_inout(kZio, Zref_bar), copy_out(kKbar, K_bar),
+                      copy_out(kX0, x0_bar), copy_out(kModelD, model_bar)},
                      [&](double* const* d, bool) {
-                         return qln::launch_tracking_rollout_vjp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kModel], d[kZbar],
-                                                                 d[kZio], d[kKbar], d[kX0], d[kModelD], h->stream);
+                         return qln::launch_tracking_rollout_vjp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kModel], d[kEvent],
+                                                                 d[kZbar], d[kZio], d[kKbar], d[kX0], d[kModelD], h->stream);
                      });
 }
 
 // the forward sweep: the checks that need no handle come first
 static int check_tracking_jvp_args(const qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                   const double* model, const double* Zref_dot, const double* K_dot, const double* x0_dot,
-                                   const double* model_dot, const double* Zout_dot, const char* who) {
+                                   const double* model, bool guarded, const double* event, const double* Zref_dot,
+                                   const double* K_dot, const double* x0_dot, const double* model_dot, const double* Zout_dot,
+                                   const double* event_dot, const char* who) {
     const std::string w(who);
+    if (guarded && !event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
     if (!Zref_dot && !K_dot && !x0_dot && !model_dot)
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every tangent is NULL (no direction)");
     if (K_dot && !K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_dot needs K (K == NULL has no gains to perturb)");
@@ -1250,38 +1276,48 @@ static int check_tracking_jvp_args(const qln_handle* h, const double* Zref, cons
     if (int rc = check_handle(h)) return rc;
     const qln_dims& D = h->dims;
     const int64_t nz = D.z_total, nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX, nm = (int64_t)D.B * QLN_MODEL_NP;
-    return check_no_overlap({{Zout_dot, nz}}, {{Zref, nz}, {K, nk}, {Zout, nz}, {model, nm}, {Zref_dot, nz}, {K_dot, nk},
-                                               {x0_dot, nx}, {model_dot, nm}}, w);
+    const int64_t ne = (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
+    return check_no_overlap({{Zout_dot, nz}, {event_dot, ne}},
+                            {{Zref, nz}, {K, nk}, {Zout, nz}, {model, nm}, {event, ne}, {Zref_dot, nz}, {K_dot, nk}, {x0_dot, nx},
+                             {model_dot, nm}}, w);
 }
 
 static int tracking_rollout_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
-                                const double* Zref_dot, const double* K_dot, const double* x0_dot, const double* model_dot,
-                                double* Zout_dot, const char* who) {
-    if (int rc = check_tracking_jvp_args(h, Zref, K, Zout, model, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot, who)) return rc;
+                                bool guarded, const double* event, const double* Zref_dot, const double* K_dot,
+                                const double* x0_dot, const double* model_dot, double* Zout_dot, double* event_dot,
+                                const char* who) {
+    if (int rc = check_tracking_jvp_args(h, Zref, K, Zout, model, guarded, event, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
+                                         event_dot, who))
+        return rc;
     if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout_jvp(h->p, Zref, K, Zout, model, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
-                                             h->stream));
+    QLN_HIP(qln::launch_tracking_rollout_jvp(h->p, Zref, K, Zout, model, event, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
+                                             event_dot, h->stream));
     return QLN_OK;
 }
 
 // Zref is staged only when K_dot is given (the kernel reads it for nothing else); otherwise Zout's buffer stands in.
 static int tracking_rollout_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                     const double* model, const double* Zref_dot, const double* K_dot, const double* x0_dot,
-                                     const double* model_dot, double* Zout_dot, const char* who) {
-    if (int rc = check_tracking_jvp_args(h, Zref, K, Zout, model, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot, who)) return rc;
+                                     const double* model, bool guarded, const double* event, const double* Zref_dot,
+                                     const double* K_dot, const double* x0_dot, const double* model_dot, double* Zout_dot,
+                                     double* event_dot, const char* who) {
+    if (int rc = check_tracking_jvp_args(h, Zref, K, Zout, model, guarded, event, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
+                                         event_dot, who))
+        return rc;
     if (int rc = check_host_models(h, model, who)) return rc;
+    if (int rc = check_host_events(h, event, who)) return rc;
     if (int rc = bind_device(h)) return rc;
     return host_call(h,
                      {copy_in(kV, Zout), copy_in(kZ, K_dot ? Zref : nullptr), copy_in(kK, K), copy_in(kModel, model),
-                      copy_in(kZdot, Zref_dot), copy_in(kKdot, K_dot), copy_in(kX0, x0_dot), copy_in(kModelD, model_dot),
-                      copy_inout(kZio, Zout_dot)},
+                      copy_in(kEvent, event), copy_in(kZdot, Zref_dot), copy_in(kKdot, K_dot), copy_in(kX0, x0_dot),
+                      copy_in(kModelD, model_dot), copy_inout(kZio, Zout_dot), copy_out(kEventD, event_dot)},
                      [&](double* const* d, bool) {
-                         return qln::launch_tracking_rollout_jvp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kModel], d[kZdot],
-                                                                 d[kKdot], d[kX0], d[kModelD], d[kZio], h->stream);
+                         return qln::launch_tracking_rollout_jvp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kModel], d[kEvent],
+                                                                 d[kZdot], d[kKdot], d[kX0], d[kModelD], d[kZio], d[kEventD],
+                                                                 h->stream);
                      });
 }
 
-// the twelve entry points: the forms without a model are the same path with null model arguments
+// the sixteen entry points: the forms without a model are the same path with null model arguments
 int qln_tracking_rollout(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout) {
     return tracking_rollout(h, Zref, K, x0, nullptr, Zout, false, nullptr, "qln_tracking_rollout");
 }
@@ -1307,45 +1343,72 @@ int qln_tracking_rollout_guarded_host(qln_handle* h, const double* Zref, const d
 }
 int qln_tracking_rollout_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
                              double* Zref_bar, double* K_bar, double* x0_bar) {
-    return tracking_rollout_vjp(h, Zref, K, Zout, nullptr, Zbar, Zref_bar, K_bar, x0_bar, nullptr, "qln_tracking_rollout_vjp");
+    return tracking_rollout_vjp(h, Zref, K, Zout, nullptr, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, nullptr, "qln_tracking_rollout_vjp");
 }
 int qln_tracking_rollout_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
                                   double* Zref_bar, double* K_bar, double* x0_bar) {
-    return tracking_rollout_vjp_host(h, Zref, K, Zout, nullptr, Zbar, Zref_bar, K_bar, x0_bar, nullptr,
+    return tracking_rollout_vjp_host(h, Zref, K, Zout, nullptr, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, nullptr,
                                      "qln_tracking_rollout_vjp_host");
 }
 int qln_tracking_rollout_model_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
                                    const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar) {
-    return tracking_rollout_vjp(h, Zref, K, Zout, model, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
+    return tracking_rollout_vjp(h, Zref, K, Zout, model, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
                                 "qln_tracking_rollout_model_vjp");
 }
 int qln_tracking_rollout_model_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                         const double* model, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
                                         double* model_bar) {
-    return tracking_rollout_vjp_host(h, Zref, K, Zout, model, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
+    return tracking_rollout_vjp_host(h, Zref, K, Zout, model, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
                                      "qln_tracking_rollout_model_vjp_host");
 }
 
 int qln_tracking_rollout_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zref_dot,
                              const double* K_dot, const double* x0_dot, double* Zout_dot) {
-    return tracking_rollout_jvp(h, Zref, K, Zout, nullptr, Zref_dot, K_dot, x0_dot, nullptr, Zout_dot, "qln_tracking_rollout_jvp");
+    return tracking_rollout_jvp(h, Zref, K, Zout, nullptr, false, nullptr, Zref_dot, K_dot, x0_dot, nullptr, Zout_dot, nullptr,
+                                "qln_tracking_rollout_jvp");
 }
 int qln_tracking_rollout_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                   const double* Zref_dot, const double* K_dot, const double* x0_dot, double* Zout_dot) {
-    return tracking_rollout_jvp_host(h, Zref, K, Zout, nullptr, Zref_dot, K_dot, x0_dot, nullptr, Zout_dot,
-                                     "qln_tracking_rollout_jvp_host");
+    return tracking_rollout_jvp_host(h, Zref, K, Zout, nullptr, false, nullptr, Zref_dot, K_dot, x0_dot, nullptr, Zout_dot,
+                                     nullptr, "qln_tracking_rollout_jvp_host");
 }
 int qln_tracking_rollout_model_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
                                    const double* Zref_dot, const double* K_dot, const double* x0_dot, const double* model_dot,
                                    double* Zout_dot) {
-    return tracking_rollout_jvp(h, Zref, K, Zout, model, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
+    return tracking_rollout_jvp(h, Zref, K, Zout, model, false, nullptr, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot, nullptr,
                                 "qln_tracking_rollout_model_jvp");
 }
 int qln_tracking_rollout_model_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                         const double* model, const double* Zref_dot, const double* K_dot, const double* x0_dot,
                                         const double* model_dot, double* Zout_dot) {
-    return tracking_rollout_jvp_host(h, Zref, K, Zout, model, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
-                                     "qln_tracking_rollout_model_jvp_host");
+    return tracking_rollout_jvp_host(h, Zref, K, Zout, model, false, nullptr, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
+                                     nullptr, "qln_tracking_rollout_model_jvp_host");
+}
+
+// the sweeps through the guard-triggered touchdown: the same path with the roll-out's event records
+int qln_tracking_rollout_guarded_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
+                                     const double* event, const double* Zref_dot, const double* K_dot, const double* x0_dot,
+                                     const double* model_dot, double* Zout_dot, double* event_dot) {
+    return tracking_rollout_jvp(h, Zref, K, Zout, model, true, event, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot, event_dot,
+                                "qln_tracking_rollout_guarded_jvp");
+}
+int qln_tracking_rollout_guarded_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                          const double* model, const double* event, const double* Zref_dot, const double* K_dot,
+                                          const double* x0_dot, const double* model_dot, double* Zout_dot, double* event_dot) {
+    return tracking_rollout_jvp_host(h, Zref, K, Zout, model, true, event, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
+                                     event_dot, "qln_tracking_rollout_guarded_jvp_host");
+}
+int qln_tracking_rollout_guarded_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
+                                     const double* event, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
+                                     double* model_bar) {
+    return tracking_rollout_vjp(h, Zref, K, Zout, model, true, event, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
+                                "qln_tracking_rollout_guarded_vjp");
+}
+int qln_tracking_rollout_guarded_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                          const double* model, const double* event, const double* Zbar, double* Zref_bar,
+                                          double* K_bar, double* x0_bar, double* model_bar) {
+    return tracking_rollout_vjp_host(h, Zref, K, Zout, model, true, event, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
+                                     "qln_tracking_rollout_guarded_vjp_host");
 }
 
 // the covariance sweep (k_tracking_covariance).  The checks that need no handle come first.

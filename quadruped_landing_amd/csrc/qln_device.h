@@ -305,12 +305,15 @@ hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const dou
 // guarded: touchdown by the free foot's height instead of the knot schedule; event [B][QLN_TOUCHDOWN_INFO_STRIDE] or null
 hipError_t launch_tracking_rollout(const BatchParams& p, const double* Zref, const double* K, const double* x0,
                                    const double* model, double* Zout, bool guarded, double* event, hipStream_t stream);
+// event (null: the knot-scheduled sweeps): the guarded roll-out's records, whose knot and tau the sweeps through the
+// touchdown read (qln_tracking_rollout_guarded_vjp / _jvp); event_dot [B][QLN_TOUCHDOWN_INFO_STRIDE] or null, with event only.
 hipError_t launch_tracking_rollout_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
-                                       const double* model, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
-                                       double* model_bar, hipStream_t stream);
+                                       const double* model, const double* event, const double* Zbar, double* Zref_bar,
+                                       double* K_bar, double* x0_bar, double* model_bar, hipStream_t stream);
 hipError_t launch_tracking_rollout_jvp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
-                                       const double* model, const double* Zref_dot, const double* K_dot, const double* x0_dot,
-                                       const double* model_dot, double* Zout_dot, hipStream_t stream);
+                                       const double* model, const double* event, const double* Zref_dot, const double* K_dot,
+                                       const double* x0_dot, const double* model_dot, double* Zout_dot, double* event_dot,
+                                       hipStream_t stream);
 // Sigma_{k+1} = (A_k - B_k K_k) Sigma_k (A_k - B_k K_k)' + diag(Wd) along Zout (K null: open loop); Sigma0 [sigma0_batch][120],
 // Wd a host array (null: zeros); Sigma [B][N][120] and marg [B][N][8], either may be null (qln_tracking_kernels.hip)
 hipError_t launch_tracking_covariance(const BatchParams& p, const double* Zout, const double* K, const double* Sigma0,

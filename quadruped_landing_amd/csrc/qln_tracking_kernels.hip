@@ -56,6 +56,12 @@
 // The roll-out and its two sweeps also exist with a per-problem plant (qln_tracking_rollout_model and its _jvp / _vjp, DESIGN.md
 // 4.16): the same three kernels with the flag kModel, which read the problem's (g, mb, mf, lb) instead of the handle's and add
 // the term of G_k = d Phi_k / d model (ModelBlock / for_each_model_entry of qln_kernel_common.h) in the mapping they have.
+//
+// The two sweeps also exist through the guarded roll-out's touchdown (qln_tracking_rollout_guarded_jvp / _vjp): the
+// flag kGuard, on the kModel path only.  The modes come from the problem's touchdown knot in the event record, and that knot
+// takes the composite step's derivative: the row / column of [A B G] applied twice (jvp_apply_row, vjp_apply_column), at
+// (x_k, tau) in the flight mode and at (x+, h - tau) in mode 3, the jump map's zeros between them and the derivative of tau,
+// which scales with one over the foot's vertical velocity at the touchdown.
 #include "qln_row16.h"
 
 #include <utility>
@@ -434,6 +440,98 @@ __device__ __forceinline__ void vjp_load(VjpKnot& s, const double* __restrict__ 
     }
 }
 
+// The contact mode of knot k in a guarded roll-out whose touchdown knot is ks (< 0: none): the problem's init_mode up to and
+// including ks (the flight leg of the touchdown knot), mode 3 behind it.  No knot carries the jump in its block: the sweeps
+// apply the jump map between the two legs of the touchdown knot themselves.
+__device__ __forceinline__ KnotMode guard_mode(int k, int ks, int im) {
+    const int mode = (ks < 0 || k <= ks) ? im : 3;
+    return {mode == 2, mode == 1, false, mode == 3};
+}
+// a problem's touchdown knot from its event record: anything that is not a knot of the roll-out means none
+__device__ __forceinline__ int guard_knot(double knot, int N) { return (knot >= 0.0 && knot <= (double)(N - 2)) ? (int)knot : -1; }
+// entry j of a state held in registers, chosen by compares: an array indexed at run time is laid out in scratch memory
+// (profiles/rollout_guarded_sweeps_resource_usage.txt)
+__device__ __forceinline__ double pick15(const double (&v)[15], int j) {
+    double o = v[0];
+#pragma unroll
+    for (int i = 1; i < 15; ++i) {
+        double t = v[i];
+        asm volatile("" : "+v"(t));  // opaque: left visible, the chain of selects is turned back into v[j]
+        o = (j == i) ? t : o;
+    }
+    return o;
+}
+
+// lane j's constant pattern in the reverse sweep, its scalars: what column j of A, row j of B and h_j are built from (the
+// kernel forms them, with the row's two sign patterns e[4] and sg[4], before its loop)
+struct VjpLane {
+    int j;
+    bool pos;        // position row (h^2/2 in B) or velocity / clock row (h)
+    int foot;        // the foot the row belongs to (0: body, theta or clock)
+    bool jrow;       // a row the jump map zeroes
+    bool cpl, kcpl;  // A(j-7, j) = h (times the foot's flag): velocity -> position; ... into a row the jump map zeroes
+    double inv, gy;  // B row j = hpow * inv * e, h_j = hfac * (sum_m e[m] F_m * inv + gy) (the clock: 1)
+    double g, iIb;
+};
+
+// Column j of [A B G]' applied to lam, for one step of length h in mode md at the state whose entry j is xj: returns
+// (A'lam)[j], ub = ub0 + (B'lam, the h column's product), and (kModel, want_mbar) adds lane j's share of G'lam to mbar.  The
+// knot of the guarded reverse sweep, which its touchdown knot calls twice, once per leg; the statement is the knot-scheduled
+// sweep's own, kept there in place (see the kernel).
+template <bool kModel>
+__device__ __forceinline__ double vjp_apply_column(const VjpLane& c, const double (&e)[4], const double (&sg)[4], double xj,
+                                                   double F0, double F1, double F2, double F3, double h, const KnotMode& md,
+                                                   const Model& M, double lam, bool want_mbar, double (&mbar)[QLN_MODEL_NP],
+                                                   const double (&ub0)[5], double (&ub)[5]) {
+    const int j = c.j;
+    const bool pos = c.pos;
+    const double g = c.g, iIb = c.iIb;
+    const double m1 = md.f1free ? 1.0 : 0.0, m2 = md.f2free ? 1.0 : 0.0;
+    const double keep = md.jump ? 0.0 : 1.0;
+    const double h2 = h * h;
+    const double Aw = h * iIb, At = 0.5 * h2 * iIb, Bt = h2 * h * iIb * (1.0 / 6.0), Ct = h2 * h2 * iIb * (1.0 / 24.0);
+    const double ga1 = g * (1.0 - m1), ga2 = g * (1.0 - m2);
+    const double taua = ga1 * F0 + ga2 * F2;
+    // the lane's masks for this knot
+    const double fm = c.foot == 1 ? m1 : c.foot == 2 ? m2 : 1.0;  // the row's foot is free
+    const double km = c.jrow ? keep : 1.0;
+    const double rmask = fm * km;                           // row j of B and of the h column
+    const double fmv = pos ? 1.0 : fm;                      // w = m foot velocity - body velocity
+    const double cmask = c.cpl ? fm * (c.kcpl ? keep : 1.0) : 0.0;
+    if constexpr (kModel) {
+        if (want_mbar) {
+            double xk[14];
+            row_bcast_first(xj, xk, std::make_integer_sequence<int, 14>{});
+            const ModelBlock mblk = model_block(xk, F0, F1, F2, F3, h, md, M);
+            for_each_model_entry(mblk, [&](auto r, auto q, double val) { mbar[q] = (j == r) ? fma(val, lam, mbar[q]) : mbar[q]; });
+        }
+    }
+    // cross-lane lam: rows 2 and 9 (row broadcasts) and j-7 (row shift)
+    const double lam2 = dpp_f64<0x152>(lam), lam9 = dpp_f64<0x159>(lam), lamc = row_shr7(lam);
+    // ---- A'lam, column j: diagonal, rows 2 and 9 (h-power times d tau / d x_j), row j-7 ----
+    const double sF = ((sg[0] * F0 + sg[1] * F1) + sg[2] * F2) + sg[3] * F3;
+    const double phi = fmv * sF;
+    const double alam = fma(h * cmask, lamc, fma((pos ? Aw : At) * phi, lam9, fma((pos ? At : Bt) * phi, lam2, km * lam)));
+    // ---- the lane's shares of B'lam and of the h column ----
+    const double Lr = rmask * lam;
+    const double Fs = ((e[0] * F0 + e[1] * F1) + e[2] * F2) + e[3] * F3;
+    const double bco = (pos ? 0.5 * h2 : h) * c.inv * Lr;
+    const double al = At * lam2 + Aw * lam9, be = Bt * lam2 + At * lam9, gm = Ct * lam2 + Bt * lam9;
+    const double xs = fmv * xj;
+    const double tco = (pos ? al : be) * xs;                // rows 2 and 9 of B, through d tau / d F_m
+    double red[5];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) red[m] = fma(e[m], bco, sg[m] * tco);
+    const double hco = pos ? fma(Aw, lam2, iIb * lam9) : al;  // rows 2 and 9 of the h column, through tau
+    red[4] = fma(cmask * xj, lamc, fma(hco * xs, sF, (pos ? h : 1.0) * fma(Fs, c.inv, c.gy) * Lr));
+#pragma unroll
+    for (int m = 0; m < 5; ++m) ub[m] = ub0[m] + row_sum16(red[m]);
+    ub[0] = fma(gm, ga1, ub[0]);
+    ub[2] = fma(gm, ga2, ub[2]);
+    ub[4] = fma(be, taua, ub[4]);
+    return alam;
+}
+
 // The reverse sweep of k_tracking_rollout (include/qln_evaluator.h): lam_{N-1} = Zbar[x_{N-1}], then per knot k = N-2..0
 //   ubar = Zbar[u_k] + B_k'lam_{k+1},  lam_k = Zbar[x_k] + A_k'lam_{k+1} - K_k'ubar[0:4],
 // with xref_bar_k = K_k'ubar[0:4], Kbar_k = -ubar[0:4] (x_k - x_ref,k)'.  A_k, B_k and the h column are the derivative of
@@ -443,13 +541,20 @@ __device__ __forceinline__ void vjp_load(VjpKnot& s, const double* __restrict__ 
 // model_bar[b] = sum_k G_k'lam_{k+1} with G_k = d Phi_k / d (g, mb, mf, lb) of qln_kernel_common.h: every lane forms the knot's
 // ModelBlock (Zout's states handed round by DPP row broadcasts), lane j accumulates G_k[j][p] lam_{k+1}[j] over the knots,
 // and the four row sums are taken once, after the loop.
-template <bool kHasK, bool kModel>
+// kGuard (qln_tracking_rollout_guarded_vjp, with kModel): the modes are guard_mode's of the problem's touchdown knot ks, read
+// with tau from event.  At ks the transpose of the composite step: vjp_apply_column through the mode-3 leg at (x+, h - tau),
+// the jump map's zeros, vjp_apply_column through the flight leg at (x_k, tau); what the two h columns leave for tau goes, by
+// d tau's coefficients, onto lam[iy], lam[iv], the free foot's ubar_F_y and the model's g and mf.  x- and x+ are recomputed by
+// every lane of the row with step_mode, as the roll-out forms them.
+template <bool kHasK, bool kModel, bool kGuard>
 __global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, const double* __restrict__ Zref,
                                                                 const double* __restrict__ Kg, const double* __restrict__ Zout,
                                                                 const double* __restrict__ Zbar, double* __restrict__ Zref_bar,
                                                                 double* __restrict__ Kbar, double* __restrict__ x0_bar,
                                                                 const double* __restrict__ model,
-                                                                double* __restrict__ model_bar) {
+                                                                double* __restrict__ model_bar,
+                                                                const double* __restrict__ event) {
+    static_assert(kModel || !kGuard, "the guarded sweep runs on the kModel path");
     const Row16 r16 = row16_of(P);  // lane 15 reads lane 14's slots and contributes nothing
     const int j = r16.j, b = r16.b, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
     const bool own = r16.own, valid = r16.valid;
@@ -460,6 +565,12 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, c
     const double* __restrict__ Zb = Zbar + (int64_t)bc * P.z_stride;
     const double* __restrict__ Zr = Kbar ? Zref + (int64_t)bc * P.z_stride : nullptr;
     const double* __restrict__ Kb = kHasK ? Kg + (int64_t)bc * (N - 1) * (QLN_TRACK_NU * QLN_NX) : nullptr;
+    [[maybe_unused]] int ks = -1;
+    [[maybe_unused]] double tau = 0.0;
+    if constexpr (kGuard) {
+        ks = guard_knot(event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc], N);
+        tau = event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + 1];
+    }
 
     // ---- lane j's constant pattern: what column j of A, row j of B and h_j are built from ----
     const bool pos = j < 7;                 // position row (h^2/2 in B) or velocity / clock row (h)
@@ -485,6 +596,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, c
     // B row j = hpow * inv * e, h_j = hfac * (sum_m e[m] F_m * inv + gy) (the clock: 1)
     const double inv = (p <= 1) ? imb : foot ? -imf : 0.0;
     const double gy = (p == 1 || p == 4 || p == 6) ? g : (j == 14) ? 1.0 : 0.0;
+    [[maybe_unused]] const VjpLane lc = {j, pos, foot, jrow, cpl, kcpl, inv, gy, g, iIb};
 
     double mbar[QLN_MODEL_NP] = {0.0, 0.0, 0.0, 0.0};  // lane j's share of model_bar
     double lam = own ? Zb[20 * (N - 1) + j] : 0.0;
@@ -494,52 +606,102 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, c
     for (int k = N - 2; k >= 0; --k) {
         cur = nxt;
         if (k > 0) vjp_load<kHasK>(nxt, Zo, Zb, Zr, Kb + (kHasK ? (int64_t)(k - 1) * 60 : 0), k - 1, j);
-        const KnotMode md = knot_mode(k + 1, kt - 1, im);
-        const double m1 = md.f1free ? 1.0 : 0.0, m2 = md.f2free ? 1.0 : 0.0;
-        const double keep = md.jump ? 0.0 : 1.0;
+        KnotMode md;
+        if constexpr (kGuard) md = guard_mode(k, ks, im);
+        else md = knot_mode(k + 1, kt - 1, im);
         const double F0 = cur.u[0], F1 = cur.u[1], F2 = cur.u[2], F3 = cur.u[3], h = cur.u[4];
-        const double h2 = h * h;
-        const double Aw = h * iIb, At = 0.5 * h2 * iIb, Bt = h2 * h * iIb * (1.0 / 6.0), Ct = h2 * h2 * iIb * (1.0 / 24.0);
-        const double ga1 = g * (1.0 - m1), ga2 = g * (1.0 - m2);
-        const double taua = ga1 * F0 + ga2 * F2;
-        // the lane's masks for this knot
-        const double fm = foot == 1 ? m1 : foot == 2 ? m2 : 1.0;  // the row's foot is free
-        const double km = jrow ? keep : 1.0;
-        const double rmask = fm * km;                           // row j of B and of the h column
-        const double fmv = pos ? 1.0 : fm;                      // w = m foot velocity - body velocity
-        const double cmask = cpl ? fm * (kcpl ? keep : 1.0) : 0.0;
-        if constexpr (kModel) {
-            if (model_bar) {
-                double xk[14];
-                row_bcast_first(cur.x, xk, std::make_integer_sequence<int, 14>{});
-                const ModelBlock mblk = model_block(xk, F0, F1, F2, F3, h, md, M);
-                for_each_model_entry(mblk, [&](auto r, auto q, double val) { mbar[q] = (j == r) ? fma(val, lam, mbar[q]) : mbar[q]; });
-            }
-        }
-        // cross-lane lam: rows 2 and 9 (row broadcasts) and j-7 (row shift)
-        const double lam2 = dpp_f64<0x152>(lam), lam9 = dpp_f64<0x159>(lam), lamc = row_shr7(lam);
-        // ---- A'lam, column j: diagonal, rows 2 and 9 (h-power times d tau / d x_j), row j-7 ----
-        const double sF = ((sg[0] * F0 + sg[1] * F1) + sg[2] * F2) + sg[3] * F3;
-        const double phi = fmv * sF;
-        const double alam = fma(h * cmask, lamc, fma((pos ? Aw : At) * phi, lam9, fma((pos ? At : Bt) * phi, lam2, km * lam)));
-        // ---- the lane's shares of B'lam and of the h column ----
-        const double Lr = rmask * lam;
-        const double Fs = ((e[0] * F0 + e[1] * F1) + e[2] * F2) + e[3] * F3;
-        const double bco = (pos ? 0.5 * h2 : h) * inv * Lr;
-        const double al = At * lam2 + Aw * lam9, be = Bt * lam2 + At * lam9, gm = Ct * lam2 + Bt * lam9;
-        const double xs = fmv * cur.x;
-        const double tco = (pos ? al : be) * xs;                // rows 2 and 9 of B, through d tau / d F_m
-        double red[5];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) red[m] = fma(e[m], bco, sg[m] * tco);
-        const double hco = pos ? fma(Aw, lam2, iIb * lam9) : al;  // rows 2 and 9 of the h column, through tau
-        red[4] = fma(cmask * cur.x, lamc, fma(hco * xs, sF, (pos ? h : 1.0) * fma(Fs, inv, gy) * Lr));
         double ub[5];
+        double alam;
+        if constexpr (kGuard) {
+            const bool td = k == ks;
+            double lamA = lam, hA = h, hb3 = 0.0, w = 1.0, y = 0.0;
+            double ubA[5] = {cur.ub[0], cur.ub[1], cur.ub[2], cur.ub[3], cur.ub[4]};
+            if (td) {
+                double xk[15], xm[15];
+                row_bcast_first(cur.x, xk, std::make_integer_sequence<int, 15>{});
+                const double u5[5] = {F0, F1, F2, F3, h};
+                step_mode(M, md, tau, xk, u5, xm);
+                y = md.f2free ? xk[6] : xk[4];
+                w = md.f2free ? xm[13] : xm[11];
+                jump_map(xm);
+                // the mode-3 leg at (x+, F, h - tau)
+                ubA[4] = 0.0;
+                double ub3[5];
+                const double a3 = vjp_apply_column<kModel>(lc, e, sg, pick15(xm, j), F0, F1, F2, F3, h - tau,
+                                                           KnotMode{false, false, false, true}, M, lam, model_bar != nullptr, mbar, ubA,
+                                                           ub3);
 #pragma unroll
-        for (int m = 0; m < 5; ++m) ub[m] = cur.ub[m] + row_sum16(red[m]);
-        ub[0] = fma(gm, ga1, ub[0]);
-        ub[2] = fma(gm, ga2, ub[2]);
-        ub[4] = fma(be, taua, ub[4]);
+                for (int m = 0; m < 4; ++m) ubA[m] = ub3[m];
+                hb3 = ub3[4];
+                lamA = (own && !lc.jrow) ? a3 : 0.0;  // the jump map
+                hA = tau;
+            }
+            alam = vjp_apply_column<kModel>(lc, e, sg, cur.x, F0, F1, F2, F3, hA, md, M, lamA, model_bar != nullptr, mbar, ubA, ub);
+            if (td) {
+                // tau's cotangent, and d tau = -(dy + tau dv + tau^2/2 da) / w with da = -dF_y / mf + F_y / mf^2 dmf + dg
+                const double taubar = ub[4] - hb3;
+                ub[4] = cur.ub[4] + hb3;
+                const bool f2 = md.f2free;
+                const double cw = (y <= 0.0) ? 0.0 : -taubar / w, ca = cw * (0.5 * tau * tau);
+                const int iy = f2 ? 6 : 4, iv = f2 ? 13 : 11;
+                alam = (j == iy) ? alam + cw : (j == iv) ? fma(cw, tau, alam) : alam;
+                const double Fy = f2 ? F3 : F1, cf = -ca / M.mf;
+                ub[1] = f2 ? ub[1] : ub[1] + cf;
+                ub[3] = f2 ? ub[3] + cf : ub[3];
+                if (r16.ln == 0) {
+                    mbar[0] += ca;
+                    mbar[2] = fma(ca, Fy / (M.mf * M.mf), mbar[2]);
+                }
+            }
+        } else {
+            // The knot-scheduled sweeps keep their own statement of the knot, the one vjp_apply_column restates: routed through
+            // the function, all four of them were allocated 2 to 6 VGPRs differently
+            // (profiles/rollout_guarded_sweeps_resource_usage.txt).  A guarded sweep of a batch that never lands is bit for bit
+            // the _model_ sweep (tests/test_gpu_rollout_guarded_sweeps.py), which holds the two statements to each other.
+            const double m1 = md.f1free ? 1.0 : 0.0, m2 = md.f2free ? 1.0 : 0.0;
+            const double keep = md.jump ? 0.0 : 1.0;
+            const double h2 = h * h;
+            const double Aw = h * iIb, At = 0.5 * h2 * iIb, Bt = h2 * h * iIb * (1.0 / 6.0), Ct = h2 * h2 * iIb * (1.0 / 24.0);
+            const double ga1 = g * (1.0 - m1), ga2 = g * (1.0 - m2);
+            const double taua = ga1 * F0 + ga2 * F2;
+            // the lane's masks for this knot
+            const double fm = foot == 1 ? m1 : foot == 2 ? m2 : 1.0;  // the row's foot is free
+            const double km = jrow ? keep : 1.0;
+            const double rmask = fm * km;                           // row j of B and of the h column
+            const double fmv = pos ? 1.0 : fm;                      // w = m foot velocity - body velocity
+            const double cmask = cpl ? fm * (kcpl ? keep : 1.0) : 0.0;
+            if constexpr (kModel) {
+                if (model_bar) {
+                    double xk[14];
+                    row_bcast_first(cur.x, xk, std::make_integer_sequence<int, 14>{});
+                    const ModelBlock mblk = model_block(xk, F0, F1, F2, F3, h, md, M);
+                    for_each_model_entry(mblk, [&](auto r, auto q, double val) { mbar[q] = (j == r) ? fma(val, lam, mbar[q]) : mbar[q]; });
+                }
+            }
+            // cross-lane lam: rows 2 and 9 (row broadcasts) and j-7 (row shift)
+            const double lam2 = dpp_f64<0x152>(lam), lam9 = dpp_f64<0x159>(lam), lamc = row_shr7(lam);
+            // ---- A'lam, column j: diagonal, rows 2 and 9 (h-power times d tau / d x_j), row j-7 ----
+            const double sF = ((sg[0] * F0 + sg[1] * F1) + sg[2] * F2) + sg[3] * F3;
+            const double phi = fmv * sF;
+            alam = fma(h * cmask, lamc, fma((pos ? Aw : At) * phi, lam9, fma((pos ? At : Bt) * phi, lam2, km * lam)));
+            // ---- the lane's shares of B'lam and of the h column ----
+            const double Lr = rmask * lam;
+            const double Fs = ((e[0] * F0 + e[1] * F1) + e[2] * F2) + e[3] * F3;
+            const double bco = (pos ? 0.5 * h2 : h) * inv * Lr;
+            const double al = At * lam2 + Aw * lam9, be = Bt * lam2 + At * lam9, gm = Ct * lam2 + Bt * lam9;
+            const double xs = fmv * cur.x;
+            const double tco = (pos ? al : be) * xs;                // rows 2 and 9 of B, through d tau / d F_m
+            double red[5];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) red[m] = fma(e[m], bco, sg[m] * tco);
+            const double hco = pos ? fma(Aw, lam2, iIb * lam9) : al;  // rows 2 and 9 of the h column, through tau
+            red[4] = fma(cmask * cur.x, lamc, fma(hco * xs, sF, (pos ? h : 1.0) * fma(Fs, inv, gy) * Lr));
+#pragma unroll
+            for (int m = 0; m < 5; ++m) ub[m] = cur.ub[m] + row_sum16(red[m]);
+            ub[0] = fma(gm, ga1, ub[0]);
+            ub[2] = fma(gm, ga2, ub[2]);
+            ub[4] = fma(be, taua, ub[4]);
+        }
         // ---- K'ubar, lam_k, and the outputs of the knot ----
         double kub = 0.0;
         if constexpr (kHasK) kub = ((cur.kc[0] * ub[0] + cur.kc[1] * ub[1]) + cur.kc[2] * ub[2]) + cur.kc[3] * ub[3];
@@ -791,6 +953,52 @@ __device__ __forceinline__ void jvp_load(JvpKnot& s, const double* __restrict__ 
     }
 }
 
+// Row j of [A B G] applied to the knot's tangents, for one step of length h in mode md at the state x: returns
+// (A dx + B (dF, dh) + G md4)[j].  blk is step_block() of the same arguments, formed by every lane of the row alike; the lane
+// picks its row's entries from the visitor (rows 2 and 9 of A: at the lane's column, summed over the row).  kWantB: the force columns exist (some dF can be non-zero);
+// kWantH: the h column is formed, and applied where use_h says.  The tangent sweep's knot; the touchdown knot of the guarded
+// sweep calls it twice, once per leg.
+template <bool kWantB, bool kWantH, bool kModel>
+__device__ __forceinline__ double jvp_apply_row(int j, bool own, const StepBlock& blk, const double (&x)[14], double F1x,
+                                                double F1y, double F2x, double F2y, double h, const KnotMode md, const Model& M,
+                                                double dx, const double (&dF)[4], double dh, bool use_h, bool want_model,
+                                                const double (&md4)[QLN_MODEL_NP]) {
+    // ---- row j of [A B]: the visitor's entries at the lane's row (rows 2 and 9 of A: at the lane's column) ----
+    double a2 = 0.0, a9 = 0.0, dg = 0.0, cp = 0.0, bj[4] = {0.0, 0.0, 0.0, 0.0}, hj = 0.0;
+    for_each_rollout_entry(blk, [&](auto r, auto c, double val) {
+        if constexpr (c < 15) {
+            if constexpr (r == 2) a2 = (j == c) ? val : a2;
+            else if constexpr (r == 9) a9 = (j == c) ? val : a9;
+            else if constexpr (r == c) dg = (j == r) ? val : dg;
+            else cp = (j == r) ? val : cp;  // r == c - 7 (a_structure_ok)
+        } else if constexpr (c < 19) {
+            if constexpr (kWantB) bj[c - 15] = (j == r) ? val : bj[c - 15];
+        } else if constexpr (kWantH) {
+            hj = (j == r) ? val : hj;
+        }
+    });
+    const double dxc = row_shl7(dx);  // dx[j+7], 0 past the row's end
+    const double s2 = row_sum16(own ? a2 * dx : 0.0), s9 = row_sum16(own ? a9 * dx : 0.0);
+    double acc = (j == 2) ? s2 : (j == 9) ? s9 : fma(cp, dxc, dg * dx);
+    if constexpr (kWantB) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) acc = fma(bj[m], dF[m], acc);
+    }
+    if constexpr (kWantH) {
+        if (use_h) acc = fma(hj, dh, acc);
+    }
+    if constexpr (kModel) {
+        if (want_model) {
+            const ModelBlock mblk = model_block(x, F1x, F1y, F2x, F2y, h, md, M);
+            double gj[QLN_MODEL_NP] = {0.0, 0.0, 0.0, 0.0};
+            for_each_model_entry(mblk, [&](auto r, auto q, double val) { gj[q] = (j == r) ? val : gj[q]; });
+#pragma unroll
+            for (int q = 0; q < QLN_MODEL_NP; ++q) acc = fma(gj[q], md4[q], acc);
+        }
+    }
+    return acc;
+}
+
 // The forward (tangent) sweep of k_tracking_rollout (include/qln_evaluator.h): dx_0 = x0_dot, then per knot k = 0..N-2
 //   dF_k = Fref_dot_k - K_k (dx_k - xref_dot_k) - Kdot_k (x_k - x_ref,k),  dh_k = href_dot_k,
 //   dx_{k+1} = A_k dx_k + B_k (dF_k, dh_k),
@@ -803,7 +1011,12 @@ __device__ __forceinline__ void jvp_load(JvpKnot& s, const double* __restrict__ 
 // Template flags say which inputs exist: nothing that is absent is read (Zref only with Kdot).
 // kModel (qln_tracking_rollout_model_jvp): [A_k B_k] at problem b's own model (model, null: the handle's), and the model's
 // tangent enters as + G_k model_dot[b], lane j picking row j of G_k from for_each_model_entry (model_dot null: no term).
-template <bool kHasK, bool kHasKd, bool kHasZd, bool kModel>
+// kGuard (qln_tracking_rollout_guarded_jvp, with kModel): the modes are guard_mode's of the problem's touchdown knot ks, read
+// with tau from event.  At ks the composite step: d tau from dy, dv, dF_y (row broadcasts of dx; dF is in every lane) and the
+// model's tangent over w, the foot's vertical velocity in x- = step_mode(x_k; tau), which every lane of the row recomputes;
+// jvp_apply_row through the flight leg at (x_k, tau) with d tau in the place of dh, the jump map's zeros, jvp_apply_row
+// through the mode-3 leg at (x+, h - tau) with dh - d tau.  event_dot (null: not written) gets d tau and the clock's tangent.
+template <bool kHasK, bool kHasKd, bool kHasZd, bool kModel, bool kGuard>
 __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, const double* __restrict__ Zref,
                                                                 const double* __restrict__ Kg, const double* __restrict__ Zout,
                                                                 const double* __restrict__ Zref_dot,
@@ -811,8 +1024,11 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, c
                                                                 const double* __restrict__ x0_dot,
                                                                 double* __restrict__ Zout_dot,
                                                                 const double* __restrict__ model,
-                                                                const double* __restrict__ model_dot) {
+                                                                const double* __restrict__ model_dot,
+                                                                const double* __restrict__ event,
+                                                                double* __restrict__ event_dot) {
     static_assert(kHasK || !kHasKd, "Kdot needs K");
+    static_assert(kModel || !kGuard, "the guarded sweep runs on the kModel path");
     const Row16 r16 = row16_of(P);  // lane 15 reads lane 14's slots and contributes nothing
     const int ln = r16.ln, j = r16.j, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
     const bool own = r16.own, valid = r16.valid;
@@ -824,6 +1040,12 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, c
     const double* __restrict__ Kb = kHasK ? Kg + ko : nullptr;
     const double* __restrict__ Kdb = kHasKd ? Kdot + ko : nullptr;
     double* __restrict__ Od = Zout_dot + zo;
+    [[maybe_unused]] int ks = -1;
+    [[maybe_unused]] double tau = 0.0, e_tau = 0.0, e_clock = 0.0;
+    if constexpr (kGuard) {
+        ks = guard_knot(event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc], N);
+        tau = event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + 1];
+    }
 
     double md4[QLN_MODEL_NP] = {0.0, 0.0, 0.0, 0.0};
     if constexpr (kModel) {
@@ -838,13 +1060,17 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, c
     for (int k = 0; k < N - 1; ++k) {
         cur = nxt;
         if (k + 1 < N - 1) jvp_load<kHasK, kHasKd, kHasZd>(nxt, Zo, Zd, Zr, Kb, Kdb, k + 1, ln, j);
-        // ---- the knot's block, in every lane ----
+        // ---- the knot's state and controls, in every lane ----
         double x[14];
         row_bcast_first(cur.z0, x, std::make_integer_sequence<int, 14>{});
         const double F1x = row_bcast<15>(cur.z0), F1y = row_bcast<0>(cur.z1), F2x = row_bcast<1>(cur.z1),
                      F2y = row_bcast<2>(cur.z1), h = row_bcast<3>(cur.z1);
-        const KnotMode md = knot_mode(k + 1, kt - 1, im);
-        const StepBlock blk = step_block(x, F1x, F1y, F2x, F2y, h, md, M);
+        KnotMode md;
+        if constexpr (kGuard) md = guard_mode(k, ks, im);
+        else md = knot_mode(k + 1, kt - 1, im);
+        // the knot's block, in every lane; the guarded sweep forms its blocks where it applies them, at each leg's step length
+        StepBlock blk;
+        if constexpr (!kGuard) blk = step_block(x, F1x, F1y, F2x, F2y, h, md, M);
         // ---- the applied controls' tangent: dF = Fref_dot - K (dx - xref_dot) - Kdot e, dh = href_dot ----
         double dF[4], dh = 0.0, xrd = 0.0;
 #pragma unroll
@@ -866,35 +1092,48 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, c
                 dF[m] = dF[m] - row_sum16(own ? t : 0.0);
             }
         }
-        // ---- row j of [A B]: the visitor's entries at the lane's row (rows 2 and 9 of A: at the lane's column) ----
-        double a2 = 0.0, a9 = 0.0, dg = 0.0, cp = 0.0, bj[4] = {0.0, 0.0, 0.0, 0.0}, hj = 0.0;
-        for_each_rollout_entry(blk, [&](auto r, auto c, double val) {
-            if constexpr (c < 15) {
-                if constexpr (r == 2) a2 = (j == c) ? val : a2;
-                else if constexpr (r == 9) a9 = (j == c) ? val : a9;
-                else if constexpr (r == c) dg = (j == r) ? val : dg;
-                else cp = (j == r) ? val : cp;  // r == c - 7 (a_structure_ok)
-            } else if constexpr (kHasK || kHasZd) {
-                if constexpr (c < 19) bj[c - 15] = (j == r) ? val : bj[c - 15];
-                else hj = (j == r) ? val : hj;
-            }
-        });
-        const double dxc = row_shl7(dx);  // dx[j+7], 0 past the row's end
-        const double s2 = row_sum16(own ? a2 * dx : 0.0), s9 = row_sum16(own ? a9 * dx : 0.0);
-        double acc = (j == 2) ? s2 : (j == 9) ? s9 : fma(cp, dxc, dg * dx);
-        if constexpr (kHasK || kHasZd) {
+        // ---- row j of [A B G] on the knot's tangents ----
+        double acc;
+        if constexpr (kGuard) {
+            const bool td = k == ks;
+            double hA = h, dhA = dh, dtau = 0.0;
+            double xm[15];
+            if (td) {
+                const bool f2 = md.f2free;  // mode 1: foot 2 is the free one
+                double xk[15];
 #pragma unroll
-            for (int m = 0; m < 4; ++m) acc = fma(bj[m], dF[m], acc);
-            if constexpr (kHasZd) acc = fma(hj, dh, acc);
-        }
-        if constexpr (kModel) {
-            if (model_dot) {
-                const ModelBlock mblk = model_block(x, F1x, F1y, F2x, F2y, h, md, M);
-                double gj[QLN_MODEL_NP] = {0.0, 0.0, 0.0, 0.0};
-                for_each_model_entry(mblk, [&](auto r, auto q, double val) { gj[q] = (j == r) ? val : gj[q]; });
-#pragma unroll
-                for (int q = 0; q < QLN_MODEL_NP; ++q) acc = fma(gj[q], md4[q], acc);
+                for (int i = 0; i < 14; ++i) xk[i] = x[i];
+                xk[14] = 0.0;  // the clock feeds nothing
+                const double u5[5] = {F1x, F1y, F2x, F2y, h};
+                step_mode(M, md, tau, xk, u5, xm);
+                const double y = f2 ? x[6] : x[4], Fy = f2 ? F2y : F1y, w = f2 ? xm[13] : xm[11];
+                const double dy4 = row_bcast<4>(dx), dy6 = row_bcast<6>(dx), dv11 = row_bcast<11>(dx), dv13 = row_bcast<13>(dx);
+                const double dy = f2 ? dy6 : dy4, dv = f2 ? dv13 : dv11, dFy = f2 ? dF[3] : dF[1];
+                const double da = (-dFy / M.mf + (Fy / (M.mf * M.mf)) * md4[2]) + md4[0];
+                dtau = (y <= 0.0) ? 0.0 : -((dy + tau * dv) + (0.5 * tau * tau) * da) / w;
+                e_tau = dtau;
+                e_clock = row_bcast<14>(dx) + dtau;
+                hA = tau;
+                dhA = dtau;
             }
+            blk = step_block(x, F1x, F1y, F2x, F2y, hA, md, M);
+            acc = jvp_apply_row<kHasK || kHasZd, true, kModel>(j, own, blk, x, F1x, F1y, F2x, F2y, hA, md, M, dx, dF, dhA,
+                                                               kHasZd || td, model_dot != nullptr, md4);
+            if (td) {
+                const bool jrow = j == 4 || j == 6 || (j >= 10 && j <= 13);
+                const double dxm = (own && !jrow) ? acc : 0.0;  // the jump map
+                jump_map(xm);
+                double xp[14];
+#pragma unroll
+                for (int i = 0; i < 14; ++i) xp[i] = xm[i];
+                const KnotMode m3 = {false, false, false, true};
+                blk = step_block(xp, F1x, F1y, F2x, F2y, h - tau, m3, M);
+                acc = jvp_apply_row<kHasK || kHasZd, true, kModel>(j, own, blk, xp, F1x, F1y, F2x, F2y, h - tau, m3, M, dxm, dF,
+                                                                   dh - dtau, true, model_dot != nullptr, md4);
+            }
+        } else {
+            acc = jvp_apply_row<kHasK || kHasZd, kHasZd, kModel>(j, own, blk, x, F1x, F1y, F2x, F2y, h, md, M, dx, dF, dh, true,
+                                                                 model_dot != nullptr, md4);
         }
         // ---- the knot's twenty entries of Zout_dot: dx_k and (dF_k, dh_k) ----
         // (dF, dh) become one array only here: held as one through the knot it costs up to 8 VGPRs
@@ -903,6 +1142,11 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, c
         dx = own ? acc : 0.0;
     }
     if (valid && own) Od[20 * (N - 1) + j] = dx;
+    if constexpr (kGuard) {
+        // the record's tangent: d tau and the touchdown clock's, zeros elsewhere and without a touchdown
+        if (event_dot && valid && ln < QLN_TOUCHDOWN_INFO_STRIDE)
+            event_dot[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + ln] = (ln == 1) ? e_tau : (ln == 2) ? e_clock : 0.0;
+    }
 }
 
 }  // namespace
@@ -934,34 +1178,42 @@ hipError_t launch_tracking_rollout(const BatchParams& p, const double* Zref, con
     return hipGetLastError();
 }
 
+// event (the guarded roll-out's records) sends the two sweeps to their kGuard instantiations, which exist on the kModel path
+// only: a null model there is the handle's four values.  2 of the reverse sweep (K or not) and 6 of the tangent sweep (the six
+// combinations of K, K_dot and Zref_dot that exist without the flag).
 hipError_t launch_tracking_rollout_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
-                                       const double* model, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
-                                       double* model_bar, hipStream_t stream) {
+                                       const double* model, const double* event, const double* Zbar, double* Zref_bar,
+                                       double* K_bar, double* x0_bar, double* model_bar, hipStream_t stream) {
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar,
-                           model, model_bar);
+                           model, model_bar, event);
     };
-    if (model || model_bar)
-        K ? go(k_tracking_rollout_vjp<true, true>) : go(k_tracking_rollout_vjp<false, true>);
+    if (event)
+        K ? go(k_tracking_rollout_vjp<true, true, true>) : go(k_tracking_rollout_vjp<false, true, true>);
+    else if (model || model_bar)
+        K ? go(k_tracking_rollout_vjp<true, true, false>) : go(k_tracking_rollout_vjp<false, true, false>);
     else
-        K ? go(k_tracking_rollout_vjp<true, false>) : go(k_tracking_rollout_vjp<false, false>);
+        K ? go(k_tracking_rollout_vjp<true, false, false>) : go(k_tracking_rollout_vjp<false, false, false>);
     return hipGetLastError();
 }
 
 hipError_t launch_tracking_rollout_jvp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
-                                       const double* model, const double* Zref_dot, const double* K_dot, const double* x0_dot,
-                                       const double* model_dot, double* Zout_dot, hipStream_t stream) {
+                                       const double* model, const double* event, const double* Zref_dot, const double* K_dot,
+                                       const double* x0_dot, const double* model_dot, double* Zout_dot, double* event_dot,
+                                       hipStream_t stream) {
     if (K_dot && !K) return hipErrorInvalidValue;
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, Zref, K, Zout, Zref_dot, K_dot, x0_dot,
-                           Zout_dot, model, model_dot);
+                           Zout_dot, model, model_dot, event, event_dot);
     };
-    // kHasK, kHasKd, kHasZd as compile-time flags, then kModel
+    // kHasK, kHasKd, kHasZd as compile-time flags, then kModel and kGuard
     auto pick = [&](auto hasK, auto hasKd, auto hasZd) {
-        if (model || model_dot)
-            go(k_tracking_rollout_jvp<hasK(), hasKd(), hasZd(), true>);
+        if (event)
+            go(k_tracking_rollout_jvp<hasK(), hasKd(), hasZd(), true, true>);
+        else if (model || model_dot)
+            go(k_tracking_rollout_jvp<hasK(), hasKd(), hasZd(), true, false>);
         else
-            go(k_tracking_rollout_jvp<hasK(), hasKd(), hasZd(), false>);
+            go(k_tracking_rollout_jvp<hasK(), hasKd(), hasZd(), false, false>);
     };
     constexpr std::true_type yes{};
     constexpr std::false_type no{};

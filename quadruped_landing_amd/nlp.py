@@ -777,8 +777,9 @@ class HybridNLP:
         (which is not read): the event is located inside its step in closed form, the step is split there, and the problem
         is in mode 3 from then on.  Returns (Zout, events): events is a (B, 8) float64 device tensor of {knot (-1: none),
         tau, clock at touchdown, the foot's x, its (vx, vy) before the jump map, the smallest standing-foot vertical force,
-        0}, None without with_events.  Zout is not a trajectory of the handle's schedule: the jvp / vjp / covariance calls
-        do not apply to it (qln_evaluator.h)."""
+        0}, None without with_events.  Zout is not a trajectory of the handle's schedule: its derivatives are
+        tracking_rollout_guarded_jvp / _vjp, which take the events; the other jvp / vjp / covariance calls do not apply to it
+        (qln_evaluator.h)."""
         T = _torch()
         self._check(Zref, self.dims.z_total, "Zref")
         out = self.new_Z() if out is None else out
@@ -801,6 +802,96 @@ class HybridNLP:
         _lib.check(_lib.lib().qln_tracking_rollout_guarded_host(self._h, Zref.ctypes.data, _host_ptr(K), _host_ptr(x0),
                                                                 _host_ptr(model), out.ctypes.data, _host_ptr(ev)))
         return out, ev
+
+    # -- forward and reverse sweeps through the guard-triggered touchdown ----------------------------
+    def _events_ptr(self, events):
+        if events is None:
+            raise ValueError("events is required: the record tracking_rollout_guarded returned with Zout")
+        return self._check(events, self.B * _lib.TOUCHDOWN_INFO_STRIDE, "events")
+
+    def _host_events(self, events):
+        if events is None:
+            raise ValueError("events is required: the record tracking_rollout_guarded_host returned with Zout")
+        e = np.ascontiguousarray(np.asarray(events, dtype=np.float64).reshape(-1))
+        if e.size != self.B * _lib.TOUCHDOWN_INFO_STRIDE:
+            raise ValueError(f"events has {e.size} entries, expected {self.B * _lib.TOUCHDOWN_INFO_STRIDE}")
+        return e
+
+    def tracking_rollout_guarded_jvp(self, Zref, Zout, events, K=None, model=None, Zref_dot=None, K_dot=None, x0_dot=None,
+                                     model_dot=None, out=None, with_event_dot=True):
+        """Forward sweep of tracking_rollout_guarded at the trajectory (Zout, events) it returned, at fixed touchdown knot:
+        tracking_rollout_model_jvp's tangents and rules, with the composite touchdown step and the derivative of tau
+        (qln_evaluator.h).  Returns (Zout_dot, event_dot): event_dot is a (B, 8) device tensor holding d tau in entry 1 and
+        the touchdown clock's tangent in entry 2, zeros elsewhere and for a problem that does not land; None without
+        with_event_dot."""
+        T = _torch()
+        nk = self.B * (self.N - 1) * _lib.TRACK_NU * n
+        self._check(Zref, self.dims.z_total, "Zref")
+        self._check(Zout, self.dims.z_total, "Zout")
+        ep = self._events_ptr(events)
+        kp = self._check_opt(K, nk, "K")
+        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
+        zd = self._check_opt(Zref_dot, self.dims.z_total, "Zref_dot")
+        kd = self._check_opt(K_dot, nk, "K_dot")
+        xd = self._check_opt(x0_dot, self.B * n, "x0_dot")
+        md = self._check_opt(model_dot, self.B * _lib.MODEL_NP, "model_dot")
+        out = self.new_Z() if out is None else out
+        self._check(out, self.dims.z_total, "out")
+        ed = T.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE), dtype=T.float64, device=self._dev()) if with_event_dot else None
+        _lib.check(_lib.lib().qln_tracking_rollout_guarded_jvp(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), mp, ep, zd, kd, xd,
+                                                               md, out.data_ptr(), None if ed is None else ed.data_ptr()))
+        return out, ed
+
+    def tracking_rollout_guarded_jvp_host(self, Zref, Zout, events, K=None, model=None, Zref_dot=None, K_dot=None, x0_dot=None,
+                                          model_dot=None, with_event_dot=True):
+        """The same with host arrays (synchronous): numpy (Zout_dot (z_total,), event_dot (B, 8) or None).  A knot that is
+        not an integer in [-1, N-2], or a tau that is not finite or is negative, is refused."""
+        Zref, Zout, ev = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout"), self._host_events(events)
+        K, K_dot, x0_dot = self._host_K(K), self._host_K(K_dot), self._host_x0(x0_dot)
+        model, model_dot = self._host_model(model), self._host_model(model_dot, "model_dot")
+        if Zref_dot is not None:
+            Zref_dot = self._host_Z(Zref_dot, "Zref_dot")
+        out = np.zeros(self.dims.z_total)
+        ed = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if with_event_dot else None
+        _lib.check(_lib.lib().qln_tracking_rollout_guarded_jvp_host(
+            self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data, _host_ptr(model), ev.ctypes.data, _host_ptr(Zref_dot),
+            _host_ptr(K_dot), _host_ptr(x0_dot), _host_ptr(model_dot), out.ctypes.data, _host_ptr(ed)))
+        return out, ed
+
+    def tracking_rollout_guarded_vjp(self, Zref, Zout, events, Zbar, K=None, model=None, want=None):
+        """Reverse sweep of tracking_rollout_guarded at the trajectory (Zout, events) it returned, the exact adjoint of
+        tracking_rollout_guarded_jvp: tracking_rollout_model_vjp's cotangents and rules.  Returns (Zref_bar, K_bar, x0_bar,
+        model_bar), each None unless named in want (default: all, K_bar only when K is given)."""
+        T = _torch()
+        want = self._vjp_want(K, want, ("Zref", "K", "x0", "model"))
+        self._check(Zref, self.dims.z_total, "Zref")
+        self._check(Zout, self.dims.z_total, "Zout")
+        self._check(Zbar, self.dims.z_total, "Zbar")
+        ep = self._events_ptr(events)
+        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
+        zb = self.new_Z() if "Zref" in want else None
+        kb = T.zeros(tracking_k_shape(self.B, self.N), dtype=T.float64, device=self._dev()) if "K" in want else None
+        xb = T.zeros((self.B, n), dtype=T.float64, device=self._dev()) if "x0" in want else None
+        mb = T.zeros((self.B, _lib.MODEL_NP), dtype=T.float64, device=self._dev()) if "model" in want else None
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        _lib.check(_lib.lib().qln_tracking_rollout_guarded_vjp(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), mp, ep,
+                                                               Zbar.data_ptr(), ptr(zb), ptr(kb), ptr(xb), ptr(mb)))
+        return zb, kb, xb, mb
+
+    def tracking_rollout_guarded_vjp_host(self, Zref, Zout, events, Zbar, K=None, model=None, want=None):
+        """The same with host arrays (synchronous): numpy (Zref_bar, K_bar, x0_bar, model_bar (B, 4))."""
+        want = self._vjp_want(K, want, ("Zref", "K", "x0", "model"))
+        Zref, Zout, Zbar = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout"), self._host_Z(Zbar, "Zbar")
+        K, model, ev = self._host_K(K), self._host_model(model), self._host_events(events)
+        zb = np.zeros(self.dims.z_total) if "Zref" in want else None
+        kb = np.zeros(tracking_k_shape(self.B, self.N)) if "K" in want else None
+        xb = np.zeros((self.B, n)) if "x0" in want else None
+        mb = np.zeros((self.B, _lib.MODEL_NP)) if "model" in want else None
+        _lib.check(_lib.lib().qln_tracking_rollout_guarded_vjp_host(
+            self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data, _host_ptr(model), ev.ctypes.data, Zbar.ctypes.data,
+            _host_ptr(zb), _host_ptr(kb), _host_ptr(xb), _host_ptr(mb)))
+        return zb, kb, xb, mb
 
     # -- covariance propagation through the closed-loop roll-out -----------------------------------
     def tracking_covariance(self, Zout, K=None, Sigma0=None, W=None, with_sigma=True, with_marginals=True, Sigma=None,
@@ -851,14 +942,19 @@ class HybridNLP:
                                                            _host_ptr(Wh), _host_ptr(S), _host_ptr(mg)))
         return S, mg
 
-    def differentiable_rollout(self, Zref, K=None, x0=None, model=None):
+    def differentiable_rollout(self, Zref, K=None, x0=None, model=None, guarded=False):
         """tracking_rollout as a torch autograd op: returns Zout, differentiable in Zref, K and x0 (each a float64 CUDA
         tensor or None).  The backward pass is one qln_tracking_rollout_vjp launch at the Zout the forward produced, a
         forward-mode tangent (torch.autograd.forward_ad, torch.func.jvp) one qln_tracking_rollout_jvp launch.
         With model, a (B, 4) tensor of per-problem plant models (plant_models), it is tracking_rollout_model, differentiable
-        in model too, through the _model_ forms of the two sweeps."""
-        from .rollout_grad import ModelRolloutFunction, RolloutFunction
+        in model too, through the _model_ forms of the two sweeps.
+        With guarded it is tracking_rollout_guarded and returns (Zout, events): Zout is differentiable in Zref, K, x0 and
+        model (None: the handle's, no gradient) through the sweeps through the touchdown, at fixed touchdown knot; events,
+        the (B, 8) record, is not differentiable."""
+        from .rollout_grad import GuardedRolloutFunction, ModelRolloutFunction, RolloutFunction
 
+        if guarded:
+            return GuardedRolloutFunction.apply(self, Zref, K, x0, model)
         if model is None:
             return RolloutFunction.apply(self, Zref, K, x0)
         return ModelRolloutFunction.apply(self, Zref, K, x0, model)

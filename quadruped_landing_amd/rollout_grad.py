@@ -1,7 +1,8 @@
 """torch autograd for the closed-loop roll-out (HybridNLP.differentiable_rollout): the forward pass is
 qln_tracking_rollout, the backward pass its reverse sweep qln_tracking_rollout_vjp and the forward-mode tangent its forward
 sweep qln_tracking_rollout_jvp (include/qln_evaluator.h).  ModelRolloutFunction is the same over the _model_ forms, with the
-per-problem plant model as a fourth differentiable input."""
+per-problem plant model as a fourth differentiable input.  GuardedRolloutFunction is the roll-out with guard-triggered
+touchdown over qln_tracking_rollout_guarded and the two sweeps through the touchdown, which take its event record."""
 from __future__ import annotations
 
 import torch
@@ -72,3 +73,49 @@ class RolloutFunction(torch.autograd.Function):
 class ModelRolloutFunction(RolloutFunction):
     """Zout = rollout(Zref, K, x0, model), model a (B, 4) float64 CUDA tensor of per-problem plant models (g, mb, mf, lb).
     As RolloutFunction, over qln_tracking_rollout_model and its two sweeps; the gradient of model is model_bar."""
+
+
+class GuardedRolloutFunction(torch.autograd.Function):
+    """(Zout, events) = guarded rollout(Zref, K, x0, model): qln_tracking_rollout_guarded.  K, x0 and model may be None
+    (model None: the handle's).  Zout is differentiable in all four through qln_tracking_rollout_guarded_vjp / _jvp at the
+    (Zout, events) the forward produced, that is at fixed touchdown knot; events is marked non-differentiable."""
+
+    @staticmethod
+    def forward(nlp, Zref, K, x0, model):
+        return nlp.tracking_rollout_guarded(*_launchable((Zref, K, x0, model)))
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        nlp, Zref, K, x0, model = inputs
+        Zout, events = output
+        ctx.nlp = nlp
+        ctx.shapes = [None if t is None else t.shape for t in (K, x0, model)]
+        ctx.mark_non_differentiable(events)
+        ctx.save_for_backward(Zref, K, model, Zout, events)
+        ctx.save_for_forward(Zref, K, model, Zout, events)
+
+    @staticmethod
+    def backward(ctx, Zbar, _events_bar):
+        need = ctx.needs_input_grad[1:]
+        Zref, K, model, Zout, events, Zbar = (_plain(t) for t in (*ctx.saved_tensors, Zbar))
+        want = [w for w, on in zip(("Zref", "K", "x0", "model"), need) if on and not (w == "K" and K is None)]
+        if not want:
+            return (None,) * 5
+        with torch._C._DisableFuncTorch():
+            Zref, K, model, Zout, events, Zbar = _launchable((Zref, K, model, Zout, events, Zbar))
+            zb, *bars = ctx.nlp.tracking_rollout_guarded_vjp(Zref, Zout, events, Zbar, K, model, want)
+            bars = [None if b is None or shape is None else b.reshape(shape) for b, shape in zip(bars, ctx.shapes)]
+        return (None, zb, *bars)
+
+    @staticmethod
+    def jvp(ctx, _, *dots):
+        Zref, K, model, Zout, events = (_plain(t) for t in ctx.saved_tensors)
+        with torch._C._DisableFuncTorch():
+            Zref, K, model, Zout, events = _launchable((Zref, K, model, Zout, events))
+            zd, kd, xd, md = _launchable(_plain(t) for t in dots)
+            if K is None:
+                kd = None
+            if all(t is None for t in (zd, kd, xd, md)):
+                return torch.zeros_like(Zout), None
+            out, _ = ctx.nlp.tracking_rollout_guarded_jvp(Zref, Zout, events, K, model, zd, kd, xd, md, with_event_dot=False)
+            return out, None  # events is not differentiable: event_dot is tracking_rollout_guarded_jvp's to ask for
