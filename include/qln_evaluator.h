@@ -589,8 +589,9 @@ int qln_tracking_rollout_model_vjp_host(qln_handle* h, const double* Zref, const
  *         +inf); negative: the ground pulled
  *   7     0
  * Two consequences.  A guarded Zout is NOT a trajectory of the handle's knot schedule: its derivatives are
- * qln_tracking_rollout_guarded_jvp / _vjp below, which take the event record; qln_tracking_rollout_jvp / _vjp, their _model_
- * forms and qln_tracking_covariance "at the trajectory Zout" do not apply to it, and its dynamics rows under
+ * qln_tracking_rollout_guarded_jvp / _vjp below, gains along it are qln_tracking_lqr_guarded's and covariances along it
+ * qln_tracking_covariance_guarded's, all of which take the event record; qln_tracking_rollout_jvp / _vjp, their _model_
+ * forms, qln_tracking_lqr and qln_tracking_covariance "at the trajectory Zout" do not apply to it, and its dynamics rows under
  * qln_eval_constraint are non-zero at the touchdown knot.  And under sampled feedback the closed-loop map is DISCONTINUOUS in the initial state
  * where the touchdown moves from the end of one step to the start of the next: the control of that knot is computed from
  * the pre-impact state in one case and from the post-impact state in the other.  Open loop (K == NULL) it is continuous.
@@ -655,6 +656,29 @@ int qln_tracking_rollout_guarded_jvp_host(qln_handle* h, const double* Zref, con
 int qln_tracking_rollout_guarded_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                           const double* model, const double* event, const double* Zbar, double* Zref_bar,
                                           double* K_bar, double* x0_bar, double* model_bar);
+/* TVLQR gains THROUGH the guard-triggered touchdown: qln_tracking_lqr's recursion, weights, outputs, packing and exact symmetry
+ * of P, on the blocks of qln_tracking_rollout_guarded_jvp at Ztraj's (x_k, u_k) -- the saltation-matrix TVLQR of a hybrid system.
+ *   Ztraj: device, layout of Z: the trajectory to linearise along, as a rule the Zout of a guarded roll-out of the plan;
+ *   model: device, [B][QLN_MODEL_NP] or NULL = the handle's;
+ *   event: device, [B][QLN_TOUCHDOWN_INFO_STRIDE], the record that roll-out wrote.  Required.  Only entries 0 (the knot k*) and
+ *          1 (tau) are read; k* < 0 or beyond N-2 means no touchdown.  k_trans is not read, and nothing is re-run.
+ * [A_k B_k] is mode init_mode's block for k < k* (or without a touchdown) and mode 3's for k > k*, neither with a jump.  At
+ * k* it is the composite step's, with dh = 0 and in the notation of the sweeps above (t_x: dtau's coefficients -1/w at iy and
+ * -tau/w at iv; t_F: (tau^2 / 2) / (mf w) at the free foot's F_y; all zero where tau = 0 came from the guard's first branch):
+ *   A* v + B* f = A_3 J (A_m v + B_m f + b_m s) + B_3 f - b_3 s,   s = t_x . v + t_F . f
+ * Usage: roll the plan out guarded for (Zg, event), design gains along Zg with event, track perturbed drops against
+ * Zref = Zg with those gains, guarded.  For every drop that lands in the same knot they are the first-order optimal gains; a
+ * drop that lands in another knot is outside what a derivative at fixed knot says.
+ * A batch without a touchdown and with model == NULL (or the handle's model passed) gives qln_tracking_lqr's bits for a handle
+ * with k_trans = N + 1.  Errors: a NULL h, Ztraj, K or event, weights as for qln_tracking_lqr, an output that overlaps an
+ * input or the other output: QLN_ERR_INVALID_ARGUMENT.  The device form does not validate model or event; the host form does,
+ * as the guarded sweeps' host forms do.  Device pointers, stream-ordered; needs no cost table. */
+int qln_tracking_lqr_guarded(qln_handle* h, const double* Ztraj, const double* model /* [B][QLN_MODEL_NP] or NULL */,
+                             const double* event /* [B][QLN_TOUCHDOWN_INFO_STRIDE], required */, const double* Qdiag,
+                             const double* Rdiag, const double* Qfdiag, double* K, double* P /* or NULL */);
+/* the same as a host form (see "Host forms" above; the weights are host arrays in both) */
+int qln_tracking_lqr_guarded_host(qln_handle* h, const double* Ztraj, const double* model, const double* event,
+                                  const double* Qdiag, const double* Rdiag, const double* Qfdiag, double* K, double* P);
 /* Covariance propagation through the closed-loop roll-out: the linear-Gaussian forward sweep along the trajectory Zout
  * holds.  Knots are 0-based, k = 0..N-2, as in qln_tracking_rollout_vjp.
  *   A_k (15x15), B_k (15x4) = d Phi_k / d(x_k, F_k) at Zout's (x_k, u_k): exactly the blocks qln_tracking_rollout_vjp uses --
@@ -687,6 +711,24 @@ int qln_tracking_covariance(qln_handle* h, const double* Zout, const double* K, 
 /* the same as a host form (see "Host forms" above; Wdiag is a host array in both; nothing is in-out) */
 int qln_tracking_covariance_host(qln_handle* h, const double* Zout, const double* K, const double* Sigma0,
                                  int32_t sigma0_batch, const double* Wdiag, double* Sigma, double* marg);
+/* Covariance propagation THROUGH the guard-triggered touchdown: qln_tracking_covariance's recursion, inputs, outputs and
+ * marginals on the blocks of qln_tracking_lqr_guarded at a guarded roll-out's (Zout, event), at FIXED touchdown knot:
+ *   Sigma_{k+1} = Acl_k Sigma_k Acl_k' + diag(W),  Acl_k = A_k - B_k K_k,  Acl_{k*} = A* - B* K_{k*}.
+ * model and event as for qln_tracking_lqr_guarded (event required).  One optional output more,
+ *   event_var: [B][2] or NULL (not written).  [0] is the variance of tau, c' Sigma_{k*} c with c = t_x - K_{k*}' t_F (c = t_x
+ *              when K == NULL); [1] is the variance of the touchdown clock x_{k*}[14] + tau, the same with c + e_14.  Both are
+ *              0 without a touchdown, and where tau = 0 came from the guard's first branch [0] is 0.
+ * At least one of Sigma, marg and event_var must be non-NULL; which of them is asked for does not change the others' bits,
+ * and none may overlap an input or another output.  A batch without a touchdown and with model == NULL (or the handle's model
+ * passed) gives qln_tracking_covariance's bits for a handle with k_trans = N + 1.  First order, as the sweeps: the variance of
+ * a touchdown that can move to another knot is not described.  The device form does not validate model or event; the host
+ * form does.  Device pointers, stream-ordered; needs no cost table. */
+int qln_tracking_covariance_guarded(qln_handle* h, const double* Zout, const double* K, const double* model, const double* event,
+                                    const double* Sigma0, int32_t sigma0_batch, const double* Wdiag, double* Sigma, double* marg,
+                                    double* event_var /* [B][2] or NULL */);
+int qln_tracking_covariance_guarded_host(qln_handle* h, const double* Zout, const double* K, const double* model,
+                                         const double* event, const double* Sigma0, int32_t sigma0_batch, const double* Wdiag,
+                                         double* Sigma, double* marg, double* event_var);
 /* Z <- Z + N(0, sigma^2) on every entry, step lengths h then clipped to [h_min, h_max] (redraw_h = 0) or redrawn
  * U(h_min, h_max) (redraw_h != 0) -- the evaluation point of SURVEY.md 8d from qln_initial_guess's Z0.  The normal
  * draws are Box-Muller on the sampler's stream from `stream_offset`: the recipe's distribution, not numpy's numbers. */

@@ -266,7 +266,8 @@ end
 # reaches the ground, not at the problem's k_trans, which is not read.  Returns (Zout, events); events holds 8 values: the
 # 0-based knot whose step contains the touchdown (-1: none), tau, the clock at touchdown, the foot's x, its (vx, vy) before the
 # jump map, the smallest vertical force under a standing foot, 0.  Zout is not a trajectory of the knot schedule: its
-# derivatives are tracking_rollout_guarded_jvp / _vjp below; the other jvp / vjp / covariance calls do not apply to it.
+# derivatives are tracking_rollout_guarded_jvp / _vjp below, gains and covariances along it tracking_lqr_guarded and
+# tracking_covariance_guarded; the other jvp / vjp / lqr / covariance calls do not apply to it.
 function tracking_rollout_guarded(prob::HybridNLPHIP, Zref::Vector{Float64}; K=nothing, x0=nothing, model=nothing)
     Zout = zeros(length(Zref))
     events = zeros(8)
@@ -320,6 +321,35 @@ function tracking_covariance(prob::HybridNLPHIP, Zout::Vector{Float64}, Sigma0::
                     (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
                     prob.handle, Zout, K === nothing ? C_NULL : K, packed, Int32(1), W === nothing ? C_NULL : W, Sigma, marg))
     return Sigma, marg
+end
+# Gains and covariances through the guard-triggered touchdown (include/qln_evaluator.h, DESIGN.md 4.19), on the blocks of the
+# sweeps above: Ztraj / Zout and events are what tracking_rollout_guarded returned.  tracking_lqr_guarded returns (K, P) as
+# tracking_lqr; tracking_covariance_guarded returns (Sigma, marg, event_var) with event_var = (variance of tau, variance of the
+# touchdown clock), zeros without a touchdown.
+function tracking_lqr_guarded(prob::HybridNLPHIP, Ztraj::Vector{Float64}, events::Vector{Float64}, Q::Vector{Float64},
+                              R::Vector{Float64}, Qf::Vector{Float64}; model=nothing, with_cost_to_go::Bool=true)
+    N = prob.N
+    K = zeros(15, 4, N - 1)
+    P = with_cost_to_go ? zeros(120, N) : nothing
+    qln_check(ccall((:qln_tracking_lqr_guarded_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}),
+                    prob.handle, Ztraj, model === nothing ? C_NULL : model, events, Q, R, Qf, K, P === nothing ? C_NULL : P))
+    return K, P
+end
+function tracking_covariance_guarded(prob::HybridNLPHIP, Zout::Vector{Float64}, events::Vector{Float64}, Sigma0::Matrix{Float64};
+                                     K=nothing, W=nothing, model=nothing)
+    N = prob.N
+    packed = Float64[Sigma0[i, j] for i in 1:15 for j in 1:i]
+    Sigma = zeros(120, N)
+    marg = zeros(8, N)
+    event_var = zeros(2)
+    qln_check(ccall((:qln_tracking_covariance_guarded_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zout, K === nothing ? C_NULL : K, model === nothing ? C_NULL : model, events, packed, Int32(1),
+                    W === nothing ? C_NULL : W, Sigma, marg, event_var))
+    return Sigma, marg, event_var
 end
 
 # ---- the reference's Ipopt solve, for this evaluator type: a method of `solve` (src/moi.jl:46-103) ------------------------

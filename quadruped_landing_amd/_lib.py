@@ -169,6 +169,10 @@ SIGNATURES = {
     "qln_tracking_rollout_guarded_vjp_host": (C.c_int, [_vp] + [_dp] * 10),
     "qln_tracking_covariance": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp]),
     "qln_tracking_covariance_host": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp]),
+    "qln_tracking_lqr_guarded": (C.c_int, [_vp] + [_dp] * 8),
+    "qln_tracking_lqr_guarded_host": (C.c_int, [_vp] + [_dp] * 8),
+    "qln_tracking_covariance_guarded": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp, _dp]),
+    "qln_tracking_covariance_guarded_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp, _dp]),
     "qln_eval_constraint_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_eval_constraint_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_gauss_newton_step": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, C.c_double, _dp, _dp, _dp]),

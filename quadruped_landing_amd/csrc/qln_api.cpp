@@ -102,6 +102,7 @@ enum HostRole {
     kModelD, // in: the model jvp's model_dot; out: the model vjp's model_bar  [B][4]
     kEvent,  // out: the guarded roll-out's touchdown records; in: the same for its sweeps  [B][8]
     kEventD, // out: the guarded jvp's event_dot                            [B][8]
+    kEventVar,  // out: the guarded covariance sweep's event_var            [B][2]
     kHostRoles
 };
 
@@ -178,6 +179,7 @@ int64_t host_role_size(const qln_handle* h, HostRole r) {
         case kMultInfo: return (int64_t)D.B * QLN_MULT_INFO_STRIDE;
         case kModel: case kModelD: return (int64_t)D.B * QLN_MODEL_NP;
         case kEvent: case kEventD: return (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
+        case kEventVar: return (int64_t)D.B * 2;
         case kHostRoles: break;
     }
     return 0;
@@ -1103,13 +1105,6 @@ static int check_tracking_weights(const double* Q, const double* R, const double
     return QLN_OK;
 }
 
-static int check_tracking_lqr_args(const qln_handle* h, const double* Zref, const double* Q, const double* R, const double* Qf,
-                                   const double* K, const char* who) {
-    if (int rc = check_handle(h)) return rc;
-    if (!Zref || !K) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null Zref or K");
-    return check_tracking_weights(Q, R, Qf, who);
-}
-
 // n doubles at p, an argument's buffer; a null p is an argument left out and overlaps nothing
 struct Span {
     const double* p;
@@ -1133,26 +1128,22 @@ static int check_no_overlap(std::initializer_list<Span> out, std::initializer_li
     return QLN_OK;
 }
 
-int qln_tracking_lqr(qln_handle* h, const double* Zref, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
-                     double* K, double* P) {
-    if (int rc = check_tracking_lqr_args(h, Zref, Qdiag, Rdiag, Qfdiag, K, "qln_tracking_lqr")) return rc;
-    if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_lqr(h->p, Qdiag, Rdiag, Qfdiag, Zref, K, P, h->stream));
-    return QLN_OK;
+// guarded: the sweep through the guard-triggered touchdown, which needs the roll-out's event records; its outputs may overlap
+// no input and not each other (the sweep on the handle's knot schedule has never looked)
+static int check_tracking_lqr_args(const qln_handle* h, const double* Zref, const double* model, bool guarded, const double* event,
+                                   const double* Q, const double* R, const double* Qf, const double* K, const double* P,
+                                   const char* who) {
+    if (int rc = check_handle(h)) return rc;
+    if (!Zref || !K) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null Zref or K");
+    if (int rc = check_tracking_weights(Q, R, Qf, who)) return rc;
+    if (!guarded) return QLN_OK;
+    if (!event) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null event (the guarded roll-out's records)");
+    const qln_dims& D = h->dims;
+    return check_no_overlap({{K, tracking_k_total(D)}, {P, tracking_p_total(D)}},
+                            {{Zref, D.z_total}, {model, (int64_t)D.B * QLN_MODEL_NP},
+                             {event, (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE}}, who);
 }
 
-int qln_tracking_lqr_host(qln_handle* h, const double* Zref, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
-                          double* K, double* P) {
-    if (int rc = check_tracking_lqr_args(h, Zref, Qdiag, Rdiag, Qfdiag, K, "qln_tracking_lqr_host")) return rc;
-    if (int rc = bind_device(h)) return rc;
-    return host_call(h, {copy_in(kZ, Zref), copy_out(kK, K), copy_out(kP, P)}, [&](double* const* d, bool) {
-        return qln::launch_tracking_lqr(h->p, Qdiag, Rdiag, Qfdiag, d[kZ], d[kK], d[kP], h->stream);
-    });
-}
-
-// The roll-out and its two sweeps (k_tracking_rollout, _vjp, _jvp): one argument check and one body per operation and memory
-// form, with the per-problem plant as optional arguments.  The entry points without a model pass null for model, model_dot
-// and model_bar, and the launch then takes the kernels without their kModel flag.
 // host forms only: every entry finite, and mb, mf, lb > 0 (the device forms do not look at the values)
 static int check_host_models(const qln_handle* h, const double* model, const char* who) {
     if (!model) return QLN_OK;
@@ -1166,6 +1157,66 @@ static int check_host_models(const qln_handle* h, const double* model, const cha
     return QLN_OK;
 }
 
+// host forms only: the knot an integer in [-1, N-2], tau finite and >= 0 (the device forms do not look at the values)
+static int check_host_events(const qln_handle* h, const double* event, const char* who) {
+    if (!event) return QLN_OK;
+    for (int64_t b = 0; b < h->dims.B; ++b) {
+        const double knot = event[b * QLN_TOUCHDOWN_INFO_STRIDE], tau = event[b * QLN_TOUCHDOWN_INFO_STRIDE + 1];
+        if (!(knot >= -1.0 && knot <= (double)(h->dims.N - 2)) || knot != std::floor(knot))
+            return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": event[" + std::to_string(b) +
+                                                      "][0] is not a knot of the roll-out (an integer in [-1, N-2])");
+        if (!std::isfinite(tau) || tau < 0.0)
+            return fail(QLN_ERR_INVALID_ARGUMENT,
+                        std::string(who) + ": event[" + std::to_string(b) + "][1] (tau) is not finite or is negative");
+    }
+    return QLN_OK;
+}
+
+// The Riccati sweep: one body per memory form.  The entry point on the handle's knot schedule passes null for model and
+// event, and the launch then takes the kernel without its kGuard flag.
+static int tracking_lqr(qln_handle* h, const double* Zref, const double* model, bool guarded, const double* event,
+                        const double* Qdiag, const double* Rdiag, const double* Qfdiag, double* K, double* P, const char* who) {
+    if (int rc = check_tracking_lqr_args(h, Zref, model, guarded, event, Qdiag, Rdiag, Qfdiag, K, P, who)) return rc;
+    if (int rc = bind_device(h)) return rc;
+    QLN_HIP(qln::launch_tracking_lqr(h->p, Qdiag, Rdiag, Qfdiag, Zref, model, event, K, P, h->stream));
+    return QLN_OK;
+}
+
+static int tracking_lqr_host(qln_handle* h, const double* Zref, const double* model, bool guarded, const double* event,
+                             const double* Qdiag, const double* Rdiag, const double* Qfdiag, double* K, double* P,
+                             const char* who) {
+    if (int rc = check_tracking_lqr_args(h, Zref, model, guarded, event, Qdiag, Rdiag, Qfdiag, K, P, who)) return rc;
+    if (int rc = check_host_models(h, model, who)) return rc;
+    if (int rc = check_host_events(h, event, who)) return rc;
+    if (int rc = bind_device(h)) return rc;
+    return host_call(h, {copy_in(kZ, Zref), copy_in(kModel, model), copy_in(kEvent, event), copy_out(kK, K), copy_out(kP, P)},
+                     [&](double* const* d, bool) {
+                         return qln::launch_tracking_lqr(h->p, Qdiag, Rdiag, Qfdiag, d[kZ], d[kModel], d[kEvent], d[kK], d[kP],
+                                                         h->stream);
+                     });
+}
+
+int qln_tracking_lqr(qln_handle* h, const double* Zref, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
+                     double* K, double* P) {
+    return tracking_lqr(h, Zref, nullptr, false, nullptr, Qdiag, Rdiag, Qfdiag, K, P, "qln_tracking_lqr");
+}
+int qln_tracking_lqr_host(qln_handle* h, const double* Zref, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
+                          double* K, double* P) {
+    return tracking_lqr_host(h, Zref, nullptr, false, nullptr, Qdiag, Rdiag, Qfdiag, K, P, "qln_tracking_lqr_host");
+}
+int qln_tracking_lqr_guarded(qln_handle* h, const double* Ztraj, const double* model, const double* event, const double* Qdiag,
+                             const double* Rdiag, const double* Qfdiag, double* K, double* P) {
+    return tracking_lqr(h, Ztraj, model, true, event, Qdiag, Rdiag, Qfdiag, K, P, "qln_tracking_lqr_guarded");
+}
+int qln_tracking_lqr_guarded_host(qln_handle* h, const double* Ztraj, const double* model, const double* event,
+                                  const double* Qdiag, const double* Rdiag, const double* Qfdiag, double* K, double* P) {
+    return tracking_lqr_host(h, Ztraj, model, true, event, Qdiag, Rdiag, Qfdiag, K, P, "qln_tracking_lqr_guarded_host");
+}
+
+// The roll-out and its two sweeps (k_tracking_rollout, _vjp, _jvp): one argument check and one body per operation and memory
+// form, with the per-problem plant as optional arguments.  The entry points without a model pass null for model, model_dot
+// and model_bar, and the launch then takes the kernels without their kModel flag.  The host forms validate a model's and an
+// event record's values (check_host_models, check_host_events above); the device forms do not look at them.
 // event: the guarded roll-out's records (null: none asked for)
 static int check_tracking_rollout_args(const qln_handle* h, const double* Zref, const double* Zout, const double* event,
                                        const char* who) {
@@ -1215,21 +1266,6 @@ static int check_tracking_vjp_args(const qln_handle* h, const double* Zref, cons
     const int64_t ne = (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
     return check_no_overlap({{Zref_bar, nz}, {K_bar, nk}, {x0_bar, nx}, {model_bar, nm}},
                             {{Zref, nz}, {K, nk}, {Zout, nz}, {Zbar, nz}, {model, nm}, {event, ne}}, w);
-}
-
-// host forms only: the knot an integer in [-1, N-2], tau finite and >= 0 (the device forms do not look at the values)
-static int check_host_events(const qln_handle* h, const double* event, const char* who) {
-    if (!event) return QLN_OK;
-    for (int64_t b = 0; b < h->dims.B; ++b) {
-        const double knot = event[b * QLN_TOUCHDOWN_INFO_STRIDE], tau = event[b * QLN_TOUCHDOWN_INFO_STRIDE + 1];
-        if (!(knot >= -1.0 && knot <= (double)(h->dims.N - 2)) || knot != std::floor(knot))
-            return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": event[" + std::to_string(b) +
-                                                      "][0] is not a knot of the roll-out (an integer in [-1, N-2])");
-        if (!std::isfinite(tau) || tau < 0.0)
-            return fail(QLN_ERR_INVALID_ARGUMENT,
-                        std::string(who) + ": event[" + std::to_string(b) + "][1] (tau) is not finite or is negative");
-    }
-    return QLN_OK;
 }
 
 static int tracking_rollout_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
@@ -1412,11 +1448,16 @@ int qln_tracking_rollout_guarded_vjp_host(qln_handle* h, const double* Zref, con
 }
 
 // the covariance sweep (k_tracking_covariance).  The checks that need no handle come first.
-static int check_tracking_covariance_args(const qln_handle* h, const double* Zout, const double* K, const double* Sigma0,
-                                          int32_t sigma0_batch, const double* Wdiag, const double* Sigma, const double* marg,
+// guarded: the sweep through the guard-triggered touchdown, which needs the roll-out's event records and may return event_var
+static int check_tracking_covariance_args(const qln_handle* h, const double* Zout, const double* K, const double* model,
+                                          bool guarded, const double* event, const double* Sigma0, int32_t sigma0_batch,
+                                          const double* Wdiag, const double* Sigma, const double* marg, const double* event_var,
                                           const char* who) {
     const std::string w(who);
-    if (!Sigma && !marg) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Sigma and marg are both NULL (nothing to compute)");
+    if (!Sigma && !marg && !event_var)
+        return fail(QLN_ERR_INVALID_ARGUMENT, guarded ? w + ": Sigma, marg and event_var are all NULL (nothing to compute)"
+                                                      : w + ": Sigma and marg are both NULL (nothing to compute)");
+    if (guarded && !event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
     if (Wdiag)
         for (int i = 0; i < QLN_NX; ++i)
             if (!(std::isfinite(Wdiag[i]) && Wdiag[i] >= 0.0))
@@ -1426,32 +1467,64 @@ static int check_tracking_covariance_args(const qln_handle* h, const double* Zou
     const qln_dims& D = h->dims;
     if (sigma0_batch != 1 && sigma0_batch != D.B) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
     if (!Zout || !Sigma0) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zout or Sigma0");
-    return check_no_overlap({{Sigma, tracking_p_total(D)}, {marg, tracking_marg_total(D)}},
-                            {{Zout, D.z_total}, {K, tracking_k_total(D)}, {Sigma0, (int64_t)sigma0_batch * QLN_TRACK_P_NNZ}}, w);
+    return check_no_overlap({{Sigma, tracking_p_total(D)}, {marg, tracking_marg_total(D)}, {event_var, (int64_t)D.B * 2}},
+                            {{Zout, D.z_total}, {K, tracking_k_total(D)}, {Sigma0, (int64_t)sigma0_batch * QLN_TRACK_P_NNZ},
+                             {model, (int64_t)D.B * QLN_MODEL_NP}, {event, (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE}}, w);
+}
+
+static int tracking_covariance(qln_handle* h, const double* Zout, const double* K, const double* model, bool guarded,
+                               const double* event, const double* Sigma0, int32_t sigma0_batch, const double* Wdiag,
+                               double* Sigma, double* marg, double* event_var, const char* who) {
+    if (int rc = check_tracking_covariance_args(h, Zout, K, model, guarded, event, Sigma0, sigma0_batch, Wdiag, Sigma, marg,
+                                                event_var, who))
+        return rc;
+    if (int rc = bind_device(h)) return rc;
+    QLN_HIP(qln::launch_tracking_covariance(h->p, Zout, K, model, event, Sigma0, sigma0_batch, Wdiag, Sigma, marg, event_var,
+                                            h->stream));
+    return QLN_OK;
+}
+
+static int tracking_covariance_host(qln_handle* h, const double* Zout, const double* K, const double* model, bool guarded,
+                                    const double* event, const double* Sigma0, int32_t sigma0_batch, const double* Wdiag,
+                                    double* Sigma, double* marg, double* event_var, const char* who) {
+    if (int rc = check_tracking_covariance_args(h, Zout, K, model, guarded, event, Sigma0, sigma0_batch, Wdiag, Sigma, marg,
+                                                event_var, who))
+        return rc;
+    if (int rc = check_host_models(h, model, who)) return rc;
+    if (int rc = check_host_events(h, event, who)) return rc;
+    if (int rc = bind_device(h)) return rc;
+    HostArg s0 = copy_in(kCov0, Sigma0);
+    s0.n = (int64_t)sigma0_batch * QLN_TRACK_P_NNZ;  // the tiles the call reads, of the role's B
+    return host_call(h,
+                     {copy_in(kV, Zout), copy_in(kK, K), copy_in(kModel, model), copy_in(kEvent, event), s0,
+                      copy_out(kCov, Sigma), copy_out(kMarg, marg), copy_out(kEventVar, event_var)},
+                     [&](double* const* d, bool) {
+                         return qln::launch_tracking_covariance(h->p, d[kV], d[kK], d[kModel], d[kEvent], d[kCov0], sigma0_batch,
+                                                                Wdiag, d[kCov], d[kMarg], d[kEventVar], h->stream);
+                     });
 }
 
 int qln_tracking_covariance(qln_handle* h, const double* Zout, const double* K, const double* Sigma0, int32_t sigma0_batch,
                             const double* Wdiag, double* Sigma, double* marg) {
-    if (int rc = check_tracking_covariance_args(h, Zout, K, Sigma0, sigma0_batch, Wdiag, Sigma, marg, "qln_tracking_covariance"))
-        return rc;
-    if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_covariance(h->p, Zout, K, Sigma0, sigma0_batch, Wdiag, Sigma, marg, h->stream));
-    return QLN_OK;
+    return tracking_covariance(h, Zout, K, nullptr, false, nullptr, Sigma0, sigma0_batch, Wdiag, Sigma, marg, nullptr,
+                               "qln_tracking_covariance");
 }
-
 int qln_tracking_covariance_host(qln_handle* h, const double* Zout, const double* K, const double* Sigma0,
                                  int32_t sigma0_batch, const double* Wdiag, double* Sigma, double* marg) {
-    if (int rc = check_tracking_covariance_args(h, Zout, K, Sigma0, sigma0_batch, Wdiag, Sigma, marg,
-                                                "qln_tracking_covariance_host"))
-        return rc;
-    if (int rc = bind_device(h)) return rc;
-    HostArg s0 = copy_in(kCov0, Sigma0);
-    s0.n = (int64_t)sigma0_batch * QLN_TRACK_P_NNZ;  // the tiles the call reads, of the role's B
-    return host_call(h, {copy_in(kV, Zout), copy_in(kK, K), s0, copy_out(kCov, Sigma), copy_out(kMarg, marg)},
-                     [&](double* const* d, bool) {
-                         return qln::launch_tracking_covariance(h->p, d[kV], d[kK], d[kCov0], sigma0_batch, Wdiag, d[kCov],
-                                                                d[kMarg], h->stream);
-                     });
+    return tracking_covariance_host(h, Zout, K, nullptr, false, nullptr, Sigma0, sigma0_batch, Wdiag, Sigma, marg, nullptr,
+                                    "qln_tracking_covariance_host");
+}
+int qln_tracking_covariance_guarded(qln_handle* h, const double* Zout, const double* K, const double* model, const double* event,
+                                    const double* Sigma0, int32_t sigma0_batch, const double* Wdiag, double* Sigma, double* marg,
+                                    double* event_var) {
+    return tracking_covariance(h, Zout, K, model, true, event, Sigma0, sigma0_batch, Wdiag, Sigma, marg, event_var,
+                               "qln_tracking_covariance_guarded");
+}
+int qln_tracking_covariance_guarded_host(qln_handle* h, const double* Zout, const double* K, const double* model,
+                                         const double* event, const double* Sigma0, int32_t sigma0_batch, const double* Wdiag,
+                                         double* Sigma, double* marg, double* event_var) {
+    return tracking_covariance_host(h, Zout, K, model, true, event, Sigma0, sigma0_batch, Wdiag, Sigma, marg, event_var,
+                                    "qln_tracking_covariance_guarded_host");
 }
 
 // ------------------------------------------------------------------ host-pointer (MOI) mode

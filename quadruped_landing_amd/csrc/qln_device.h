@@ -294,9 +294,10 @@ hipError_t launch_hessian_lagrangian(const BatchParams& p, const double* Z, cons
 hipError_t launch_hessian_lagrangian_product(const BatchParams& p, const double* Z, const double* sigma, const double* mu,
                                              const double* v, double* y, hipStream_t stream);
 // TVLQR gains (and cost-to-go, P may be null) along the reference trajectories Zref (qln_tracking_kernels.hip).  Qd / Rd / Qfd
-// are host arrays.
+// are host arrays.  event (null: the handle's knot schedule and model): the guarded roll-out's records, whose knot and tau the
+// sweep through the touchdown reads (qln_tracking_lqr_guarded), with model [B][QLN_MODEL_NP] (null: the handle's).
 hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const double* Rd, const double* Qfd, const double* Zref,
-                               double* K, double* P, hipStream_t stream);
+                               const double* model, const double* event, double* K, double* P, hipStream_t stream);
 // The roll-out from x0 (null: the handle's x0) and its two sweeps at Zout's trajectory, with a per-problem plant: model
 // [B][QLN_MODEL_NP] = (g, mb, mf, lb) per problem (null: the handle's), its tangent model_dot and cotangent model_bar in the same
 // layout.  Reverse: cotangent Zbar -> Zref_bar, K_bar, x0_bar, model_bar (each may be null).  Forward: tangents Zref_dot, K_dot,
@@ -315,9 +316,11 @@ hipError_t launch_tracking_rollout_jvp(const BatchParams& p, const double* Zref,
                                        const double* x0_dot, const double* model_dot, double* Zout_dot, double* event_dot,
                                        hipStream_t stream);
 // Sigma_{k+1} = (A_k - B_k K_k) Sigma_k (A_k - B_k K_k)' + diag(Wd) along Zout (K null: open loop); Sigma0 [sigma0_batch][120],
-// Wd a host array (null: zeros); Sigma [B][N][120] and marg [B][N][8], either may be null (qln_tracking_kernels.hip)
-hipError_t launch_tracking_covariance(const BatchParams& p, const double* Zout, const double* K, const double* Sigma0,
-                                      int sigma0_batch, const double* Wd, double* Sigma, double* marg, hipStream_t stream);
+// Wd a host array (null: zeros); Sigma [B][N][120] and marg [B][N][8], either may be null (qln_tracking_kernels.hip).
+// event and model as for launch_tracking_lqr (qln_tracking_covariance_guarded); event_var [B][2] or null, with event only.
+hipError_t launch_tracking_covariance(const BatchParams& p, const double* Zout, const double* K, const double* model,
+                                      const double* event, const double* Sigma0, int sigma0_batch, const double* Wd,
+                                      double* Sigma, double* marg, double* event_var, hipStream_t stream);
 // batched Gauss-Newton step on the constraint violation, CGLS per problem in LDS (qln_solver_kernels.hip)
 size_t gauss_newton_lds_bytes(int32_t N);
 hipError_t launch_gauss_newton_step(const BatchParams& p, const double* Z, const double* c, double* dZ, int max_iters,

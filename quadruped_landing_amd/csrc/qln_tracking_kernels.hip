@@ -62,6 +62,11 @@
 // takes the composite step's derivative: the row / column of [A B G] applied twice (jvp_apply_row, vjp_apply_column), at
 // (x_k, tau) in the flight mode and at (x+, h - tau) in mode 3, the jump map's zeros between them and the derivative of tau,
 // which scales with one over the foot's vertical velocity at the touchdown.
+//
+// The Riccati and the covariance sweep exist through that touchdown too (qln_tracking_lqr_guarded, qln_tracking_covariance_guarded,
+// DESIGN.md 4.19): the flags kModel and kGuard on k_tracking_lqr and k_tracking_covariance.  Their lanes hold whole 15-vectors,
+// so the touchdown knot's composite block is applied to them as an operator, stated once (TouchdownBlock, touchdown_apply,
+// touchdown_apply_t): forward in the covariance sweep, transposed in the Riccati sweep.
 #include "qln_row16.h"
 
 #include <utility>
@@ -69,9 +74,9 @@
 namespace qln {
 namespace {
 
-// per-row LDS image (doubles): compact A table [16][4] | T [15][16] | S [15][4] | K tile [4][15] | packed P [120]
-constexpr int kLAC = 0, kLT = 64, kLS = kLT + 15 * 16, kLK = kLS + 60, kLP = kLK + 60, kLRow = kLP + QLN_TRACK_P_NNZ;
-static_assert(kLRow % 2 == 0 && kLS % 2 == 0 && kLK % 2 == 0 && kLP % 2 == 0, "16-byte aligned sections");
+// per-row LDS image (doubles): compact A table [16][4] | T [15][16] | S [15][4] | K tile [4][15] | packed P [120]; the
+// sections behind T are placed in the kernel (the guarded sweep's T has a row stride of kLTGuard)
+constexpr int kLAC = 0, kLT = 64, kLTGuard = 17;
 
 // bit s of a_slots(c): slot s of column c can be non-zero in some mode; bit r of b_rows_mask(m): B(r, m) can be
 __host__ __device__ constexpr unsigned a_slots(int c) {
@@ -102,20 +107,173 @@ __device__ __forceinline__ Model plant_model(const BatchParams& P, const double*
     return Model(th);
 }
 
+// The contact mode of knot k in a guarded roll-out whose touchdown knot is ks (< 0: none): the problem's init_mode up to and
+// including ks (the flight leg of the touchdown knot), mode 3 behind it.  No knot carries the jump in its block: the sweeps
+// apply the jump map between the two legs of the touchdown knot themselves.
+__device__ __forceinline__ KnotMode guard_mode(int k, int ks, int im) {
+    const int mode = (ks < 0 || k <= ks) ? im : 3;
+    return {mode == 2, mode == 1, false, mode == 3};
+}
+// a problem's touchdown knot from its event record: anything that is not a knot of the roll-out means none
+__device__ __forceinline__ int guard_knot(double knot, int N) { return (knot >= 0.0 && knot <= (double)(N - 2)) ? (int)knot : -1; }
+
+// The composite step of a guarded roll-out's touchdown knot as a linear operator, for the lanes that hold a
+// whole 15-vector: the Riccati and the covariance sweep through the touchdown (qln_tracking_lqr_guarded,
+// qln_tracking_covariance_guarded).  In the notation of k_tracking_rollout_jvp: [A_m B_m b_m] is the flight mode's block at
+// (x_k, F, tau), [A_3 B_3 b_3] the mode-3 block at (x+, F, h - tau), J zeroes the entries the jump map zeroes, and
+// d tau = t_x . dx + t_F . dF has three coefficients: on the free foot's height and vertical velocity and on its F_y (all zero
+// where the guard's first branch was taken, tau = 0).  Step lengths are not perturbed (dh = 0).  [A* B*] is not sparse in the
+// four-slots-per-column pattern; it is two sparse blocks, six zeros and a rank-one term, and is applied as such.
+struct TouchdownBlock {
+    double x[14], xp[14];  // x_k and x+ = J x-, without their clocks
+    double F1x, F1y, F2x, F2y;
+    double tau, rest;      // the two legs' lengths: tau and h - tau
+    KnotMode md;           // the flight leg's mode
+    double ty, tv, tF;     // d tau's coefficients on dx[iy], dx[iv] and the free foot's dF_y
+};
+
+// x- and x+ are recomputed with step_mode exactly as the roll-out and its sweeps form them; xk's clock feeds nothing.
+__device__ __forceinline__ TouchdownBlock touchdown_block(const Model& M, const KnotMode md, double tau, const double (&xk)[15],
+                                                          const double (&u)[5]) {
+    TouchdownBlock T;
+    double xm[15];
+    step_mode(M, md, tau, xk, u, xm);
+    const double y = md.f2free ? xk[6] : xk[4], w = md.f2free ? xm[13] : xm[11];
+    jump_map(xm);
+#pragma unroll
+    for (int i = 0; i < 14; ++i) {
+        T.x[i] = xk[i];
+        T.xp[i] = xm[i];
+    }
+    T.F1x = u[0], T.F1y = u[1], T.F2x = u[2], T.F2y = u[3];
+    T.tau = tau, T.rest = u[4] - tau;
+    T.md = md;
+    // d tau = -(dy + tau dv + tau^2/2 da) / w with da = -dF_y / mf, w the foot's vertical velocity in x-
+    const double iw = (y <= 0.0) ? 0.0 : -1.0 / w;
+    T.ty = iw;
+    T.tv = tau * iw;
+    T.tF = -(0.5 * tau * tau) * iw / M.mf;
+    return T;
+}
+// The two legs' blocks are formed where an application uses them, one after the other, from the leg's length passed through
+// an empty asm: what stays live between a knot's applications is the TouchdownBlock, not two StepBlocks of fifty values.
+__device__ __forceinline__ StepBlock touchdown_flight_block(const TouchdownBlock& T, const Model& M) {
+    double h = T.tau;
+    asm volatile("" : "+v"(h));
+    return step_block(T.x, T.F1x, T.F1y, T.F2x, T.F2y, h, T.md, M);
+}
+__device__ __forceinline__ StepBlock touchdown_stance_block(const TouchdownBlock& T, const Model& M) {
+    double h = T.rest;
+    asm volatile("" : "+v"(h));
+    return step_block(T.xp, T.F1x, T.F1y, T.F2x, T.F2y, h, KnotMode{false, false, false, true}, M);
+}
+
+// out = A* v + B* f = A_3 J (A_m v + B_m f + b_m s) + B_3 f - b_3 s,  s = t_x . v + t_F . f   (kHasF false: f = 0)
+template <bool kHasF>
+__device__ __forceinline__ void touchdown_apply(const TouchdownBlock& T, const Model& M, const double (&v)[15],
+                                                const double (&f)[4], double (&out)[15]) {
+    const bool f2 = T.md.f2free;  // mode 1: foot 2 is the free one
+    double s = fma(T.ty, f2 ? v[6] : v[4], T.tv * (f2 ? v[13] : v[11]));
+    if constexpr (kHasF) s = fma(T.tF, f2 ? f[3] : f[1], s);
+    double w[15];
+#pragma unroll
+    for (int i = 0; i < 15; ++i) w[i] = out[i] = 0.0;
+    for_each_rollout_entry(touchdown_flight_block(T, M), [&](auto r, auto c, double val) {
+        if constexpr (c < 15) w[r] = fma(val, v[c], w[r]);
+        else if constexpr (c == 19) w[r] = fma(val, s, w[r]);
+        else if constexpr (kHasF) w[r] = fma(val, f[c - 15], w[r]);
+    });
+    jump_map(w);
+    for_each_rollout_entry(touchdown_stance_block(T, M), [&](auto r, auto c, double val) {
+        if constexpr (c < 15) out[r] = fma(val, w[c], out[r]);
+        else if constexpr (c == 19) out[r] = fma(-val, s, out[r]);
+        else if constexpr (kHasF) out[r] = fma(val, f[c - 15], out[r]);
+    });
+}
+
+// The transposed operator on a vector p:  q = A_3'p,  r = J q,  sigma = b_m . r - b_3 . p,
+//   ax = A*'p = A_m'r + sigma t_x,   bf = B*'p = B_m'r + B_3'p + sigma t_F
+// sigma is what the saltation term hangs on, and as two dot products it cancels: the body moves through the touchdown, so
+// b_m and b_3 agree in its rows and r is close to p there.  A_3 has a unit diagonal (mode 3, no jump), so with
+// dq = (A_3' - I) p and q = p + dq the same number is  sum over the rows J keeps of (b_m - b_3) q + b_3 dq,  less b_3 p over
+// the rows it zeroes: small terms, formed from differences.  The Riccati sweep subtracts Qux'K from Qxx with a factor of
+// about 70 between them and the result (R is small); summed the plain way, sigma's rounding left 1e-13 in P where the numpy
+// recursion leaves 1e-14.
+__device__ __forceinline__ void touchdown_apply_t(const TouchdownBlock& T, const Model& M, const double (&p)[15],
+                                                  double (&ax)[15], double (&bf)[4]) {
+    const bool f2 = T.md.f2free;
+    double q[15], dq[15], b3[15], sigma = 0.0;
+#pragma unroll
+    for (int i = 0; i < 15; ++i) dq[i] = ax[i] = 0.0;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) bf[m] = 0.0;
+    for_each_rollout_entry(touchdown_stance_block(T, M), [&](auto r, auto c, double val) {
+        if constexpr (c < 15) {
+            if constexpr (r != c) dq[c] = fma(val, p[r], dq[c]);  // the diagonal is 1.0
+        } else if constexpr (c == 19) {
+            b3[r] = val;
+        } else {
+            bf[c - 15] = fma(val, p[r], bf[c - 15]);
+        }
+    });
+#pragma unroll
+    for (int i = 0; i < 15; ++i) q[i] = p[i] + dq[i];
+    jump_map(q);
+    for_each_rollout_entry(touchdown_flight_block(T, M), [&](auto r, auto c, double val) {
+        if constexpr (c < 15) {
+            ax[c] = fma(val, q[r], ax[c]);
+        } else if constexpr (c == 19) {
+            constexpr bool zeroed = r == 4 || r == 6 || (r >= 10 && r <= 13);  // the rows of jump_map
+            if constexpr (zeroed) sigma = fma(-b3[r], p[r], sigma);
+            else sigma = fma(val - b3[r], q[r], fma(b3[r], dq[r], sigma));
+        } else {
+            bf[c - 15] = fma(val, q[r], bf[c - 15]);
+        }
+    });
+    const double sy = sigma * T.ty, sv = sigma * T.tv, sF = sigma * T.tF;
+    ax[4] += f2 ? 0.0 : sy;
+    ax[6] += f2 ? sy : 0.0;
+    ax[11] += f2 ? 0.0 : sv;
+    ax[13] += f2 ? sv : 0.0;
+    bf[1] += f2 ? 0.0 : sF;
+    bf[3] += f2 ? sF : 0.0;
+}
+
 struct TrackWeights {
     double Q[15], R[4], Qf[15];
 };
 
 // The knot's block is formed in every lane's registers; forming it once per row into LDS tables was measured slower
 // (profiles/tracking_variants.txt).
-template <bool kWantP>
+// kGuard (qln_tracking_lqr_guarded, with kModel): the blocks of the guarded sweeps at Zref's (x_k, u_k).  The model is the
+// problem's (plant_model), the modes are guard_mode's of the problem's touchdown knot ks, read with tau from event, and every
+// knot but ks is the statement below.  At ks the knot runs on the transposed composite operator (touchdown_apply_t), three
+// kinds of application per lane: (T row j, S row j) = (A*'p_j, B*'p_j) -> LDS; lane j reads column j of T back and applies the
+// operator again, which gives column j of Qxx = A*'T (row j, by symmetry) and column j of Qux = B*'T; B*' on the four columns
+// of S gives Quu, the same in every lane.  The factorisation, the K column, P_k's row and the stores are the same code for
+// every knot; the rows of a wave reach their ks in different iterations, and only the operator applications diverge.  T's
+// image has a row stride of kLTGuard here, so that neither the lanes' row writes nor their column reads share a bank.
+template <bool kWantP, bool kModel, bool kGuard>
 __global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeights W, const double* __restrict__ Zref,
-                                                        double* __restrict__ Kout, double* __restrict__ Pout) {
+                                                        double* __restrict__ Kout, double* __restrict__ Pout,
+                                                        const double* __restrict__ model, const double* __restrict__ event) {
+    static_assert(kModel || !kGuard, "the guarded sweep runs on the kModel path");
+    // T's row stride, and the sections behind it
+    constexpr int kTS = kGuard ? kLTGuard : 16, kLS = kLT + (kGuard ? 16 * 16 : 15 * 16), kLK = kLS + 60, kLP = kLK + 60,
+                  kLRow = kLP + QLN_TRACK_P_NNZ;
+    static_assert(kLRow % 2 == 0 && kLS % 2 == 0 && kLK % 2 == 0 && kLP % 2 == 0 && 15 * kTS <= kLS - kLT, "16-byte aligned sections");
     __shared__ double lds[kRows * kLRow];
     const Row16 r16 = row16_of(P);  // lane 15 shadows row 14 and stores nothing
     const int ln = r16.ln, j = r16.j, b = r16.b, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
     const bool own = r16.own, valid = r16.valid;
-    const Model& M = r16.M;
+    const Model Mp = plant_model<kModel>(P, model, bc);
+    const Model& M = kGuard ? Mp : r16.M;
+    [[maybe_unused]] int ks = -1;
+    [[maybe_unused]] double tau = 0.0;
+    if constexpr (kGuard) {
+        ks = guard_knot(event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc], N);
+        tau = event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + 1];
+    }
     double* __restrict__ L = lds + r16.row * kLRow;
     const double* __restrict__ Zb = Zref + (int64_t)bc * P.z_stride;
     const int jp = a_coupling(j), jq = jp < 0 ? 0 : jp;
@@ -150,86 +308,120 @@ __global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeig
 #pragma unroll
             for (int i = 0; i < 19; ++i) zn[i] = Zb[20 * (k - 1) + (i < 14 ? i : i + 1)];
         }
-        const KnotMode md = knot_mode(k + 1, kt - 1, im);
+        KnotMode md;
+        if constexpr (kGuard) md = guard_mode(k, ks, im);
+        else md = knot_mode(k + 1, kt - 1, im);
+        const bool td = kGuard && k == ks;  // the touchdown knot: the composite operator instead of the block's tables
+        [[maybe_unused]] TouchdownBlock tb;
         double Ac[15][4], Bm[15][4];
+        double t[15], sr[4];
+        if (td) {
+            double xk[15];
 #pragma unroll
-        for (int c = 0; c < 15; ++c)
-#pragma unroll
-            for (int s = 0; s < 4; ++s) Ac[c][s] = Bm[c][s] = 0.0;
-        const StepBlock blk = step_block(x, F1x, F1y, F2x, F2y, h, md, M);
-        for_each_rollout_entry(blk, [&](auto r, auto c, double val) {
-            if constexpr (c < 15) Ac[c][a_slot(r, c)] = val;
-            else if constexpr (c < 19) Bm[r][c - 15] = val;
-        });
-        // ---- 1. the knot's A table; T row j = P row j . A, S row j = P row j . B ----
-        if (ln == 0) {
+            for (int i = 0; i < 14; ++i) xk[i] = x[i];
+            xk[14] = 0.0;  // the clock feeds nothing
+            const double u5[5] = {F1x, F1y, F2x, F2y, h};
+            tb = touchdown_block(M, md, tau, xk, u5);
+            touchdown_apply_t(tb, M, p, t, sr);
+        } else {
 #pragma unroll
             for (int c = 0; c < 15; ++c)
 #pragma unroll
-                for (int s = 0; s < 4; ++s)
-                    if ((a_slots(c) >> s) & 1u) L[kLAC + 4 * c + s] = Ac[c][s];
-        }
-        double t[15], sr[4];
+                for (int s = 0; s < 4; ++s) Ac[c][s] = Bm[c][s] = 0.0;
+            const StepBlock blk = step_block(x, F1x, F1y, F2x, F2y, h, md, M);
+            for_each_rollout_entry(blk, [&](auto r, auto c, double val) {
+                if constexpr (c < 15) Ac[c][a_slot(r, c)] = val;
+                else if constexpr (c < 19) Bm[r][c - 15] = val;
+            });
+            // ---- 1. the knot's A table; T row j = P row j . A, S row j = P row j . B ----
+            if (ln == 0) {
 #pragma unroll
-        for (int c = 0; c < 15; ++c) {
-            const unsigned sl = a_slots(c);
-            double acc = p[c] * Ac[c][0];
-            if ((sl >> 1) & 1u) acc = fma(p[2], Ac[c][1], acc);
-            if ((sl >> 2) & 1u) acc = fma(p[9], Ac[c][2], acc);
-            if ((sl >> 3) & 1u) acc = fma(p[a_coupling(c) < 0 ? 0 : a_coupling(c)], Ac[c][3], acc);
-            t[c] = acc;
-        }
+                for (int c = 0; c < 15; ++c)
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            double acc = 0.0;
-            bool first = true;
+                    for (int s = 0; s < 4; ++s)
+                        if ((a_slots(c) >> s) & 1u) L[kLAC + 4 * c + s] = Ac[c][s];
+            }
 #pragma unroll
-            for (int r = 0; r < 15; ++r)
-                if ((b_rows_mask(m) >> r) & 1u) {
-                    acc = first ? p[r] * Bm[r][m] : fma(p[r], Bm[r][m], acc);
-                    first = false;
-                }
-            sr[m] = acc;
+            for (int c = 0; c < 15; ++c) {
+                const unsigned sl = a_slots(c);
+                double acc = p[c] * Ac[c][0];
+                if ((sl >> 1) & 1u) acc = fma(p[2], Ac[c][1], acc);
+                if ((sl >> 2) & 1u) acc = fma(p[9], Ac[c][2], acc);
+                if ((sl >> 3) & 1u) acc = fma(p[a_coupling(c) < 0 ? 0 : a_coupling(c)], Ac[c][3], acc);
+                t[c] = acc;
+            }
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                double acc = 0.0;
+                bool first = true;
+#pragma unroll
+                for (int r = 0; r < 15; ++r)
+                    if ((b_rows_mask(m) >> r) & 1u) {
+                        acc = first ? p[r] * Bm[r][m] : fma(p[r], Bm[r][m], acc);
+                        first = false;
+                    }
+                sr[m] = acc;
+            }
         }
         if (own) {
 #pragma unroll
-            for (int c = 0; c < 15; ++c) L[kLT + 16 * j + c] = t[c];
+            for (int c = 0; c < 15; ++c) L[kLT + kTS * j + c] = t[c];
 #pragma unroll
             for (int m = 0; m < 4; ++m) L[kLS + 4 * j + m] = sr[m];
         }
         wave_lds_sync();
         // ---- 2. Qxx row j = A'T, Quu = R + B'S, Qux column j = S'A column j; K column j ----
-        const double a0 = L[kLAC + 4 * j], a2 = L[kLAC + 4 * j + 1], a9 = L[kLAC + 4 * j + 2], ac = L[kLAC + 4 * j + 3];
-        double qx[15];
+        double qx[15], qu[4], q[4][4];
+        if (td) {
+            // column j of T, then A*' and B*' on it: column j of Qxx (its row j, by symmetry) and of Qux
+            double tc[15];
 #pragma unroll
-        for (int c = 0; c < 15; ++c) {
-            double acc = a0 * t[c];
-            acc = fma(a2, L[kLT + 16 * 2 + c], acc);
-            acc = fma(a9, L[kLT + 16 * 9 + c], acc);
-            acc = fma(ac, L[kLT + 16 * jq + c], acc);
-            qx[c] = acc;
-        }
-        double qu[4];
+            for (int i = 0; i < 15; ++i) tc[i] = L[kLT + kTS * i + j];
+            touchdown_apply_t(tb, M, tc, qx, qu);
+            // Quu = R + B*'S, column by column
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            double acc = a0 * sr[m];
-            acc = fma(a2, L[kLS + 4 * 2 + m], acc);
-            acc = fma(a9, L[kLS + 4 * 9 + m], acc);
-            acc = fma(ac, L[kLS + 4 * jq + m], acc);
-            qu[m] = acc;
-        }
-        double q[4][4];
+            for (int m = 0; m < 4; ++m) {
+                double sc[15], ax[15], bs[4];
 #pragma unroll
-        for (int n = 0; n < 4; ++n)
+                for (int i = 0; i < 15; ++i) sc[i] = L[kLS + 4 * i + m];
+                touchdown_apply_t(tb, M, sc, ax, bs);
 #pragma unroll
-            for (int m = 0; m <= n; ++m) {
-                double acc = (m == n) ? W.R[m] : 0.0;
-#pragma unroll
-                for (int r = 0; r < 15; ++r)
-                    if ((b_rows_mask(n) >> r) & 1u) acc = fma(L[kLS + 4 * r + m], Bm[r][n], acc);
-                q[n][m] = acc;
-                q[m][n] = acc;
+                for (int n = m; n < 4; ++n) {
+                    const double acc = (m == n) ? W.R[m] + bs[n] : bs[n];
+                    q[n][m] = acc;
+                    q[m][n] = acc;
+                }
             }
+        } else {
+            const double a0 = L[kLAC + 4 * j], a2 = L[kLAC + 4 * j + 1], a9 = L[kLAC + 4 * j + 2], ac = L[kLAC + 4 * j + 3];
+#pragma unroll
+            for (int c = 0; c < 15; ++c) {
+                double acc = a0 * t[c];
+                acc = fma(a2, L[kLT + kTS * 2 + c], acc);
+                acc = fma(a9, L[kLT + kTS * 9 + c], acc);
+                acc = fma(ac, L[kLT + kTS * jq + c], acc);
+                qx[c] = acc;
+            }
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                double acc = a0 * sr[m];
+                acc = fma(a2, L[kLS + 4 * 2 + m], acc);
+                acc = fma(a9, L[kLS + 4 * 9 + m], acc);
+                acc = fma(ac, L[kLS + 4 * jq + m], acc);
+                qu[m] = acc;
+            }
+#pragma unroll
+            for (int n = 0; n < 4; ++n)
+#pragma unroll
+                for (int m = 0; m <= n; ++m) {
+                    double acc = (m == n) ? W.R[m] : 0.0;
+#pragma unroll
+                    for (int r = 0; r < 15; ++r)
+                        if ((b_rows_mask(n) >> r) & 1u) acc = fma(L[kLS + 4 * r + m], Bm[r][n], acc);
+                    q[n][m] = acc;
+                    q[m][n] = acc;
+                }
+        }
         // Quu = L D L' (the same bits in every lane), then K column j = Quu^-1 Qux column j
         double l[4][4], d[4], dinv[4];
 #pragma unroll
@@ -440,15 +632,6 @@ __device__ __forceinline__ void vjp_load(VjpKnot& s, const double* __restrict__ 
     }
 }
 
-// The contact mode of knot k in a guarded roll-out whose touchdown knot is ks (< 0: none): the problem's init_mode up to and
-// including ks (the flight leg of the touchdown knot), mode 3 behind it.  No knot carries the jump in its block: the sweeps
-// apply the jump map between the two legs of the touchdown knot themselves.
-__device__ __forceinline__ KnotMode guard_mode(int k, int ks, int im) {
-    const int mode = (ks < 0 || k <= ks) ? im : 3;
-    return {mode == 2, mode == 1, false, mode == 3};
-}
-// a problem's touchdown knot from its event record: anything that is not a knot of the roll-out means none
-__device__ __forceinline__ int guard_knot(double knot, int N) { return (knot >= 0.0 && knot <= (double)(N - 2)) ? (int)knot : -1; }
 // entry j of a state held in registers, chosen by compares: an array indexed at run time is laid out in scratch memory
 // (profiles/rollout_guarded_sweeps_resource_usage.txt)
 __device__ __forceinline__ double pick15(const double (&v)[15], int j) {
@@ -774,19 +957,54 @@ __device__ __forceinline__ void cov_apply(const StepBlock& blk, const double* Kl
     });
 }
 
+// out = Acl* v = A* v - B* (K v) at the touchdown knot of a guarded roll-out: cov_apply with the composite operator
+// (touchdown_apply) in the block's place, f = -K v; g = K v (4)
+template <bool kHasK>
+__device__ __forceinline__ void cov_apply_touchdown(const TouchdownBlock& tb, const Model& M, const double* Kl, const double (&v)[15],
+                                                    double (&out)[15], double (&g)[4]) {
+    double f[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        double acc = 0.0;
+        if constexpr (kHasK) {
+            acc = Kl[16 * m] * v[0];
+#pragma unroll
+            for (int c = 1; c < 15; ++c) acc = fma(Kl[16 * m + c], v[c], acc);
+            asm volatile("" : "+v"(acc) : : "memory");  // one row of K in flight at a time, as in cov_apply
+        }
+        g[m] = acc;
+        f[m] = -acc;
+    }
+    touchdown_apply<kHasK>(tb, M, v, f, out);
+}
+
 // Sigma_0 = Sigma0[b] (or the shared one), Sigma_{k+1} = Acl_k Sigma_k Acl_k' + diag(W) at Zout's knots; Sig gets every
 // Sigma_k packed, mg the eight marginals of every knot (include/qln_evaluator.h).  Either may be null; which one is does
 // not change the arithmetic of the other.
-template <bool kHasK>
+// kGuard (qln_tracking_covariance_guarded, with kModel): the blocks of the guarded sweeps at Zout's (x_k, u_k) -- the
+// problem's model (plant_model), guard_mode's modes of the touchdown knot ks read with tau from event, and at ks the knot's
+// two applications are the composite operator's (cov_apply_touchdown), Acl* = A* - B* K.  ev_var (null: not written) gets the
+// variance of tau, c' Sigma_ks c with c = t_x - K_ks' t_F, and of the touchdown clock, the same with c + e_14: lane j takes
+// Sigma's column j against c, and the row sum against c_j is the quadratic form.  Both are 0 without a touchdown.
+template <bool kHasK, bool kModel, bool kGuard>
 __global__ __launch_bounds__(kWave) void k_tracking_covariance(BatchParams P, CovNoise Wn, const double* __restrict__ Zout,
                                                                const double* __restrict__ Kg, const double* __restrict__ Sigma0,
                                                                int sigma0_batch, double* __restrict__ Sig,
-                                                               double* __restrict__ mg) {
+                                                               double* __restrict__ mg, const double* __restrict__ model,
+                                                               const double* __restrict__ event, double* __restrict__ ev_var) {
+    static_assert(kModel || !kGuard, "the guarded sweep runs on the kModel path");
     __shared__ double lds[kRows * kCRow];
     const Row16 r16 = row16_of(P);  // lane 15 shadows column 14 and writes nothing to the image
     const int ln = r16.ln, j = r16.j, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
     const bool own = r16.own, valid = r16.valid;
-    const Model& M = r16.M;
+    const Model Mp = plant_model<kModel>(P, model, bc);
+    const Model& M = kGuard ? Mp : r16.M;
+    [[maybe_unused]] int ks = -1;
+    [[maybe_unused]] double tau = 0.0, var_tau = 0.0, var_clock = 0.0;
+    if constexpr (kGuard) {
+        ks = guard_knot(event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc], N);
+        tau = event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + 1];
+    }
     double* L = lds + r16.row * kCRow;
     const double* __restrict__ Zb = Zout + (int64_t)bc * P.z_stride;
     const double* __restrict__ Kb = kHasK ? Kg + (int64_t)bc * (N - 1) * (QLN_TRACK_NU * QLN_NX) : nullptr;
@@ -884,10 +1102,43 @@ __global__ __launch_bounds__(kWave) void k_tracking_covariance(BatchParams P, Co
             }
         }
         wave_lds_sync();  // the knot and the K tile are in place
-        const StepBlock blk = step_block(L + kCZ, knot_mode(k + 1, kt - 1, im), M);
+        KnotMode md;
+        if constexpr (kGuard) md = guard_mode(k, ks, im);
+        else md = knot_mode(k + 1, kt - 1, im);
+        const bool td = kGuard && k == ks;  // the touchdown knot: the composite operator in the block's place
+        [[maybe_unused]] TouchdownBlock tb;
+        StepBlock blk;
         // ---- 1. V column j = Acl Sigma column j; the force variances; Sigma_k leaves ----
         double out[15], g[4], fv[4];
-        cov_apply<kHasK>(blk, L + kCK, s, out, g);
+        if (td) {
+            double xk[15];
+#pragma unroll
+            for (int i = 0; i < 14; ++i) xk[i] = L[kCZ + i];
+            xk[14] = 0.0;  // the clock feeds nothing
+            const double u5[5] = {L[kCZ + 15], L[kCZ + 16], L[kCZ + 17], L[kCZ + 18], L[kCZ + 19]};
+            tb = touchdown_block(M, md, tau, xk, u5);
+            cov_apply_touchdown<kHasK>(tb, M, L + kCK, s, out, g);
+            // the variances of tau and of the touchdown clock: c = t_x - K' t_F on the free foot's force row
+            if (ev_var) {
+                const int iy = md.f2free ? 6 : 4, iv = md.f2free ? 13 : 11;
+                const double* Kf = L + kCK + 16 * (md.f2free ? 3 : 1);
+                double sc = 0.0, cj = 0.0;
+#pragma unroll
+                for (int i = 0; i < 15; ++i) {
+                    double ci = (i == 4 || i == 6) ? ((i == iy) ? tb.ty : 0.0) : (i == 11 || i == 13) ? ((i == iv) ? tb.tv : 0.0) : 0.0;
+                    if constexpr (kHasK) ci = fma(-Kf[i], tb.tF, ci);
+                    sc = fma(s[i], ci, sc);
+                    cj = (i == j) ? ci : cj;
+                }
+                const double s14 = s[14];  // Sigma column j against e_14
+                var_tau = row_sum16(own ? cj * sc : 0.0);
+                // (c + e_14)' Sigma (c + e_14): lane j's share is (c_j + [j == 14]) (sc + Sigma_{14,j})
+                var_clock = row_sum16(own ? (j == 14 ? cj + 1.0 : cj) * (sc + s14) : 0.0);
+            }
+        } else {
+            blk = step_block(L + kCZ, md, M);
+            cov_apply<kHasK>(blk, L + kCK, s, out, g);
+        }
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             fv[m] = 0.0;
@@ -906,7 +1157,8 @@ __global__ __launch_bounds__(kWave) void k_tracking_covariance(BatchParams P, Co
         double vt[15];
 #pragma unroll
         for (int c = 0; c < 15; ++c) vt[c] = L[kCImg + kCStr * c + j];
-        cov_apply<kHasK>(blk, L + kCK, vt, out, g);
+        if (td) cov_apply_touchdown<kHasK>(tb, M, L + kCK, vt, out, g);
+        else cov_apply<kHasK>(blk, L + kCK, vt, out, g);
         wave_lds_sync();  // every lane holds its row of V: Sigma_{k+1} may overwrite the image
         if (own) {
 #pragma unroll
@@ -925,6 +1177,9 @@ __global__ __launch_bounds__(kWave) void k_tracking_covariance(BatchParams P, Co
     }
     const double fv0[4] = {0.0, 0.0, 0.0, 0.0};
     emit(N - 1, fv0);
+    if constexpr (kGuard) {
+        if (ev_var && valid && ln < 2) ev_var[(int64_t)2 * bc + ln] = (ln == 0) ? var_tau : var_clock;
+    }
 }
 
 
@@ -1151,16 +1406,24 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, c
 
 }  // namespace
 
+// event (the guarded roll-out's records) sends the Riccati and the covariance sweep to their kGuard instantiations, which exist
+// on the kModel path only, as the roll-out's sweeps': a null model there is the handle's four values.  Without event, model is
+// not read.
 hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const double* Rd, const double* Qfd, const double* Zref,
-                               double* K, double* P, hipStream_t stream) {
+                               const double* model, const double* event, double* K, double* P, hipStream_t stream) {
     TrackWeights w;
     for (int i = 0; i < 15; ++i) {
         w.Q[i] = Qd[i];
         w.Qf[i] = Qfd[i];
     }
     for (int i = 0; i < 4; ++i) w.R[i] = Rd[i];
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, w, Zref, K, P); };
-    P ? go(k_tracking_lqr<true>) : go(k_tracking_lqr<false>);
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, w, Zref, K, P, model, event);
+    };
+    if (event)
+        P ? go(k_tracking_lqr<true, true, true>) : go(k_tracking_lqr<false, true, true>);
+    else
+        P ? go(k_tracking_lqr<true, false, false>) : go(k_tracking_lqr<false, false, false>);
     return hipGetLastError();
 }
 
@@ -1226,14 +1489,20 @@ hipError_t launch_tracking_rollout_jvp(const BatchParams& p, const double* Zref,
     return hipGetLastError();
 }
 
-hipError_t launch_tracking_covariance(const BatchParams& p, const double* Zout, const double* K, const double* Sigma0,
-                                      int sigma0_batch, const double* Wd, double* Sigma, double* marg, hipStream_t stream) {
+hipError_t launch_tracking_covariance(const BatchParams& p, const double* Zout, const double* K, const double* model,
+                                      const double* event, const double* Sigma0, int sigma0_batch, const double* Wd,
+                                      double* Sigma, double* marg, double* event_var, hipStream_t stream) {
+    if (event_var && !event) return hipErrorInvalidValue;
     CovNoise w;
     for (int i = 0; i < 15; ++i) w.w[i] = Wd ? Wd[i] : 0.0;
     auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, w, Zout, K, Sigma0, sigma0_batch, Sigma, marg);
+        hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, w, Zout, K, Sigma0, sigma0_batch, Sigma, marg,
+                           model, event, event_var);
     };
-    K ? go(k_tracking_covariance<true>) : go(k_tracking_covariance<false>);
+    if (event)
+        K ? go(k_tracking_covariance<true, true, true>) : go(k_tracking_covariance<false, true, true>);
+    else
+        K ? go(k_tracking_covariance<true, false, false>) : go(k_tracking_covariance<false, false, false>);
     return hipGetLastError();
 }
 

@@ -942,6 +942,94 @@ class HybridNLP:
                                                            _host_ptr(Wh), _host_ptr(S), _host_ptr(mg)))
         return S, mg
 
+    # -- gains and covariances through the guard-triggered touchdown --------------------------------
+    def tracking_lqr_guarded(self, Ztraj, events, Q, R, Qf, model=None, K=None, P=None, with_cost_to_go=True):
+        """tracking_lqr through the guarded touchdown: gains along Ztraj, as a rule the Zout tracking_rollout_guarded returned
+        for the plan, with its events (B, 8), on the blocks of tracking_rollout_guarded_jvp -- the composite step with the
+        derivative of tau at the touchdown knot (qln_evaluator.h).  model: (B, 4) device tensor or None (the handle's).
+        Returns (K, P) as tracking_lqr."""
+        T = _torch()
+        Qh, Rh, Qfh = tracking_weights(Q, R, Qf)
+        self._check(Ztraj, self.dims.z_total, "Ztraj")
+        ep = self._events_ptr(events)
+        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
+        if K is None:
+            K = T.empty(tracking_k_shape(self.B, self.N), dtype=T.float64, device=self._dev())
+        self._check(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        if with_cost_to_go and P is None:
+            P = T.empty(tracking_p_shape(self.B, self.N), dtype=T.float64, device=self._dev())
+        if not with_cost_to_go:
+            P = None
+        pp = None if P is None else self._check(P, self.B * self.N * _lib.TRACK_P_NNZ, "P")
+        _lib.check(_lib.lib().qln_tracking_lqr_guarded(self._h, Ztraj.data_ptr(), mp, ep, Qh.ctypes.data, Rh.ctypes.data,
+                                                       Qfh.ctypes.data, K.data_ptr(), pp))
+        return K, P
+
+    def tracking_lqr_guarded_host(self, Ztraj, events, Q, R, Qf, model=None, with_cost_to_go=True):
+        """The same with host arrays (synchronous): returns numpy (K, P).  The events' and the models' values are checked as
+        by the guarded sweeps' host forms."""
+        Ztraj, ev, model = self._host_Z(Ztraj, "Ztraj"), self._host_events(events), self._host_model(model)
+        Qh, Rh, Qfh = tracking_weights(Q, R, Qf)
+        K = np.zeros(tracking_k_shape(self.B, self.N))
+        P = np.zeros(tracking_p_shape(self.B, self.N)) if with_cost_to_go else None
+        _lib.check(_lib.lib().qln_tracking_lqr_guarded_host(self._h, Ztraj.ctypes.data, _host_ptr(model), ev.ctypes.data,
+                                                            Qh.ctypes.data, Rh.ctypes.data, Qfh.ctypes.data, K.ctypes.data,
+                                                            _host_ptr(P)))
+        return K, P
+
+    def tracking_covariance_guarded(self, Zout, events, K=None, Sigma0=None, W=None, model=None, with_sigma=True,
+                                    with_marginals=True, with_event_var=True, Sigma=None, marg=None):
+        """tracking_covariance through the guarded touchdown, at the (Zout, events) tracking_rollout_guarded returned, at fixed
+        touchdown knot.  Returns (Sigma, marg, event_var): the first two as tracking_covariance, event_var a (B, 2) device
+        tensor with the variance of tau and of the touchdown clock (zeros for a problem that does not land); each None
+        unless asked for."""
+        T = _torch()
+        if Sigma0 is None:
+            raise ValueError("Sigma0 is required")
+        self._check(Zout, self.dims.z_total, "Zout")
+        ep = self._events_ptr(events)
+        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
+        if isinstance(Sigma0, T.Tensor) and Sigma0.is_cuda:
+            nb = Sigma0.numel() // _lib.TRACK_P_NNZ
+            if Sigma0.numel() != nb * _lib.TRACK_P_NNZ or nb not in (1, self.B):
+                raise ValueError("a device Sigma0 must hold 1 or B packed tiles of 120")
+            s0 = Sigma0
+        else:
+            host, nb = tracking_sigma0(Sigma0, self.B)
+            s0 = T.from_numpy(host).to(self._dev())
+        self._check(s0, nb * _lib.TRACK_P_NNZ, "Sigma0")
+        Wh = tracking_noise(W)
+        S = mg = ev = None
+        if with_sigma:
+            S = T.empty(tracking_p_shape(self.B, self.N), dtype=T.float64, device=self._dev()) if Sigma is None else Sigma
+            self._check(S, self.B * self.N * _lib.TRACK_P_NNZ, "Sigma")
+        if with_marginals:
+            mg = T.empty((self.B, self.N, _lib.TRACK_MARG_STRIDE), dtype=T.float64, device=self._dev()) if marg is None else marg
+            self._check(mg, self.B * self.N * _lib.TRACK_MARG_STRIDE, "marg")
+        if with_event_var:
+            ev = T.zeros((self.B, 2), dtype=T.float64, device=self._dev())
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        _lib.check(_lib.lib().qln_tracking_covariance_guarded(self._h, Zout.data_ptr(), kp, mp, ep, s0.data_ptr(), nb,
+                                                              _host_ptr(Wh), ptr(S), ptr(mg), ptr(ev)))
+        return S, mg, ev
+
+    def tracking_covariance_guarded_host(self, Zout, events, K=None, Sigma0=None, W=None, model=None, with_sigma=True,
+                                         with_marginals=True, with_event_var=True):
+        """The same with host arrays (synchronous): numpy (Sigma (B, N, 120), marg (B, N, 8), event_var (B, 2))."""
+        if Sigma0 is None:
+            raise ValueError("Sigma0 is required")
+        Zout, K, ev, model = self._host_Z(Zout, "Zout"), self._host_K(K), self._host_events(events), self._host_model(model)
+        s0, nb = tracking_sigma0(Sigma0, self.B)
+        Wh = tracking_noise(W)
+        S = np.zeros(tracking_p_shape(self.B, self.N)) if with_sigma else None
+        mg = np.zeros((self.B, self.N, _lib.TRACK_MARG_STRIDE)) if with_marginals else None
+        var = np.zeros((self.B, 2)) if with_event_var else None
+        _lib.check(_lib.lib().qln_tracking_covariance_guarded_host(self._h, Zout.ctypes.data, _host_ptr(K), _host_ptr(model),
+                                                                   ev.ctypes.data, s0.ctypes.data, nb, _host_ptr(Wh),
+                                                                   _host_ptr(S), _host_ptr(mg), _host_ptr(var)))
+        return S, mg, var
+
     def differentiable_rollout(self, Zref, K=None, x0=None, model=None, guarded=False):
         """tracking_rollout as a torch autograd op: returns Zout, differentiable in Zref, K and x0 (each a float64 CUDA
         tensor or None).  The backward pass is one qln_tracking_rollout_vjp launch at the Zout the forward produced, a
