@@ -679,6 +679,81 @@ int qln_tracking_lqr_guarded(qln_handle* h, const double* Ztraj, const double* m
 /* the same as a host form (see "Host forms" above; the weights are host arrays in both) */
 int qln_tracking_lqr_guarded_host(qln_handle* h, const double* Ztraj, const double* model, const double* event,
                                   const double* Qdiag, const double* Rdiag, const double* Qfdiag, double* K, double* P);
+/* CONTACT-AWARE FORCE LIMITS in the closed-loop roll-out, its sweeps and gains: a foot can only push, and a leg has a force
+ * limit.  The calls above apply F_k = F_ref,k - K_k (x_k - x_ref,k) as computed, whatever its sign and size; these clamp it.
+ * All of it is opt-in: every call above keeps its bits.  Knots are 0-based, k = 0..N-2.
+ * Limits.  lim: a HOST array of QLN_FORCE_LIMITS_N = 8 doubles, passed by value in the kernel arguments as Qdiag is:
+ *     {free_x_lo, free_x_hi, free_y_lo, free_y_hi, stand_x_lo, stand_x_hi, stand_y_lo, stand_y_hi}
+ *   A foot is "standing" or "free" by the contact mode at the START of knot k: in mode 1 foot 1 stands and foot 2 is free, in
+ *   mode 2 the reverse, in mode 3 both stand.  Knot-scheduled calls (guarded == 0) take the mode from the handle's schedule, the
+ *   mode qln_tracking_rollout's step uses for that knot (the jump knot is still in init_mode).  Guarded calls take the
+ *   problem's current mode; in the touchdown knot the landing foot counts as free for the whole step, because the forces are
+ *   held -- the convention of the event record's entry 6.  +-inf is allowed and means no limit on that side; a NaN, or lo > hi,
+ *   is QLN_ERR_INVALID_ARGUMENT.  The limits are the same for every problem.
+ * Clamp.  For channel m (F1x, F1y, F2x, F2y) of F = F_ref,k - K_k e_k, formed exactly as in qln_tracking_rollout (with
+ *   K == NULL the reference's forces are clamped), and {lo, hi} the channel's pair for its foot's contact state:
+ *     s_m = F < lo ? 1 : (F > hi ? 2 : 0),     F_applied = s_m == 1 ? lo : s_m == 2 ? hi : F
+ *   A NaN fails both comparisons and passes through with s_m = 0; F == lo exactly is s_m = 0.  h_k is never clamped.  Zout's
+ *   u_k, the guard's a, the step and the event record's entry 6 all use the applied forces (so entry 6 >= stand_y_lo).  With
+ *   all eight limits infinite the result is bit for bit qln_tracking_rollout_model's (guarded == 0) or _guarded's.
+ * Saturation record.  sat: [B][N-1] doubles; knot k holds the exact integer sum_m s_m 4^m (0..170).  An output of the roll-out
+ *   (may be NULL: not written, Zout is the same); a REQUIRED input of the sweeps and of the gain design, as event is of the
+ *   guarded ones.  It takes part in the overlap rules.  The device forms do not validate it (a value that is no code in
+ *   [0, 170] masks nothing); the host forms refuse a value that is not an integer code with every s_m in {0, 1, 2}.
+ * qln_tracking_rollout_limited: guarded == 0 is qln_tracking_rollout_model on the handle's schedule, and event must be NULL;
+ *   guarded != 0 is qln_tracking_rollout_guarded (event may be NULL).  model == NULL is the handle's model.  The NULL and
+ *   overlap rules are those forms', plus sat.
+ * Derivative at FIXED ACTIVE SET (qln_tracking_rollout_limited_jvp / _vjp).  A channel with s_m != 0 is a constant, so its
+ *   dF_k[m] is zero.  event == NULL selects the blocks of qln_tracking_rollout_model_jvp / _vjp (then event_dot must be NULL),
+ *   a non-NULL event those of qln_tracking_rollout_guarded_jvp / _vjp; the other arguments, NULL rules and outputs are theirs.
+ *   Forward:  dF_k = mask_k .* (Fref_dot_k - K_k (dx_k - xref_dot_k) - Kdot_k e_k), mask_k[m] = (s_m == 0); everything
+ *     downstream, dtau's dF_y at the touchdown knot and Zout_dot's u_k included, uses the masked dF_k.
+ *   Reverse:  ubar_k[0:4] is masked after the touchdown knot's taubar has been distributed onto it and before it enters
+ *     K_k' ubar, K_bar and Zref_bar: the saturated channels' F_ref_bar and rows of K_bar are exact zeros, and Zbar[u_k][m] of a
+ *     saturated channel goes nowhere.
+ *   The h column is untouched.  The two sweeps are exact adjoints, with the duality identity of the guarded sweeps.
+ *   Limits of the statement: where the active set changes the closed-loop map has a kink and the result is a one-sided
+ *   derivative at best (of the side the record describes); the fixed touchdown knot carries the caveat it always did.
+ * Gains at fixed active set (qln_tracking_lqr_limited).  The recursion, weights, packing and exact symmetry of P of
+ *   qln_tracking_lqr (event == NULL; model must then be NULL, that design has no plant model) or qln_tracking_lqr_guarded
+ *   (event given), with the columns of B_k of the saturated channels set to zero.  At the touchdown knot the mask sits at the
+ *   composite operator's force input (f in A* v + B* f), so the rank-one dtau term loses the channel too.  The saturated rows
+ *   of K_k are then exact 0.0 (Quu decouples to R_m on them), and P_k is the cost-to-go of feedback on the free channels only.
+ *   With sat all zero it is the existing call bit for bit.
+ * Covariance needs nothing new: with those zero rows of K, A_k - B_k K_k is already the closed loop of the clamped system, so
+ *   qln_tracking_covariance / _guarded apply as they are.  Gains designed elsewhere get the zero rows from the bindings'
+ *   mask_gains(K, sat).
+ * Errors: a NaN limit or lo > hi, a NULL lim, event with guarded == 0, a NULL sat in a sweep or the design, model without event
+ *   in the design, event_dot without event: QLN_ERR_INVALID_ARGUMENT, besides those of the forms they extend.  Device pointers,
+ *   stream-ordered; needs no cost table. */
+#define QLN_FORCE_LIMITS_N 8
+int qln_tracking_rollout_limited(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
+                                 const double* lim /* host, [QLN_FORCE_LIMITS_N] */, int32_t guarded, double* Zout,
+                                 double* event /* [B][QLN_TOUCHDOWN_INFO_STRIDE] or NULL; NULL if guarded == 0 */,
+                                 double* sat /* [B][N-1] or NULL */);
+int qln_tracking_rollout_limited_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
+                                     const double* event /* or NULL: the knot schedule */, const double* sat /* required */,
+                                     const double* Zref_dot, const double* K_dot, const double* x0_dot, const double* model_dot,
+                                     double* Zout_dot, double* event_dot);
+int qln_tracking_rollout_limited_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
+                                     const double* event /* or NULL: the knot schedule */, const double* sat /* required */,
+                                     const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar);
+int qln_tracking_lqr_limited(qln_handle* h, const double* Ztraj, const double* model, const double* event /* or NULL */,
+                             const double* sat /* required */, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
+                             double* K, double* P /* or NULL */);
+/* the same as host forms (see "Host forms" above; Zout, Zout_dot and Zref_bar are in-out as in the forms they extend; lim and
+ * the weights are host arrays in both) */
+int qln_tracking_rollout_limited_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
+                                      const double* lim, int32_t guarded, double* Zout, double* event, double* sat);
+int qln_tracking_rollout_limited_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                          const double* model, const double* event, const double* sat, const double* Zref_dot,
+                                          const double* K_dot, const double* x0_dot, const double* model_dot, double* Zout_dot,
+                                          double* event_dot);
+int qln_tracking_rollout_limited_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                          const double* model, const double* event, const double* sat, const double* Zbar,
+                                          double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar);
+int qln_tracking_lqr_limited_host(qln_handle* h, const double* Ztraj, const double* model, const double* event, const double* sat,
+                                  const double* Qdiag, const double* Rdiag, const double* Qfdiag, double* K, double* P);
 /* Covariance propagation through the closed-loop roll-out: the linear-Gaussian forward sweep along the trajectory Zout
  * holds.  Knots are 0-based, k = 0..N-2, as in qln_tracking_rollout_vjp.
  *   A_k (15x15), B_k (15x4) = d Phi_k / d(x_k, F_k) at Zout's (x_k, u_k): exactly the blocks qln_tracking_rollout_vjp uses --

@@ -351,6 +351,75 @@ function tracking_covariance_guarded(prob::HybridNLPHIP, Zout::Vector{Float64}, 
                     W === nothing ? C_NULL : W, Sigma, marg, event_var))
     return Sigma, marg, event_var
 end
+# Contact-aware force limits (include/qln_evaluator.h, DESIGN.md 4.20).  limits holds 8 values, {lo, hi} of F_x and of F_y for a
+# free foot, then for a standing one (+-Inf: no limit).  tracking_rollout_limited is tracking_rollout_model (guarded = false) or
+# tracking_rollout_guarded (guarded = true) with the applied forces clamped, and returns (Zout, events, sat): events is nothing
+# when not guarded, sat holds one saturation code per knot, sum_m s_m 4^m with s_m = 1 at the lower and 2 at the upper limit
+# (unpack_saturation).  The sweeps and the gains at that active set take sat, and events for the guarded blocks (nothing: the
+# knot schedule's); a channel that rode a limit has no tangent, a zero row in K_bar and a zero row in the designed K.
+function tracking_rollout_limited(prob::HybridNLPHIP, Zref::Vector{Float64}, limits::Vector{Float64}; K=nothing, x0=nothing,
+                                  model=nothing, guarded::Bool=false)
+    length(limits) == 8 || error("limits: 8 values expected")
+    Zout = zeros(length(Zref))
+    events = guarded ? zeros(8) : nothing
+    sat = zeros(prob.N - 1)
+    qln_check(ccall((:qln_tracking_rollout_limited_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, K === nothing ? C_NULL : K, x0 === nothing ? C_NULL : x0,
+                    model === nothing ? C_NULL : model, limits, Int32(guarded ? 1 : 0), Zout,
+                    events === nothing ? C_NULL : events, sat))
+    return Zout, events, sat
+end
+function tracking_rollout_limited_jvp(prob::HybridNLPHIP, Zref::Vector{Float64}, Zout::Vector{Float64}, sat::Vector{Float64};
+                                      events=nothing, K=nothing, model=nothing, Zref_dot=nothing, K_dot=nothing, x0_dot=nothing,
+                                      model_dot=nothing)
+    Zout_dot = zeros(length(Zref))
+    event_dot = events === nothing ? nothing : zeros(8)
+    qln_check(ccall((:qln_tracking_rollout_limited_jvp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, K === nothing ? C_NULL : K, Zout, model === nothing ? C_NULL : model,
+                    events === nothing ? C_NULL : events, sat, Zref_dot === nothing ? C_NULL : Zref_dot,
+                    K_dot === nothing ? C_NULL : K_dot, x0_dot === nothing ? C_NULL : x0_dot,
+                    model_dot === nothing ? C_NULL : model_dot, Zout_dot, event_dot === nothing ? C_NULL : event_dot))
+    return Zout_dot, event_dot
+end
+function tracking_rollout_limited_vjp(prob::HybridNLPHIP, Zref::Vector{Float64}, Zout::Vector{Float64}, sat::Vector{Float64},
+                                      Zbar::Vector{Float64}; events=nothing, K=nothing, model=nothing)
+    Zref_bar = zeros(length(Zref))
+    K_bar = K === nothing ? nothing : zeros(size(K))
+    x0_bar = zeros(15)
+    model_bar = zeros(4)
+    qln_check(ccall((:qln_tracking_rollout_limited_vjp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, K === nothing ? C_NULL : K, Zout, model === nothing ? C_NULL : model,
+                    events === nothing ? C_NULL : events, sat, Zbar, Zref_bar, K_bar === nothing ? C_NULL : K_bar, x0_bar,
+                    model_bar))
+    return Zref_bar, K_bar, x0_bar, model_bar
+end
+# events = nothing: tracking_lqr's blocks (model must then be nothing); else tracking_lqr_guarded's
+function tracking_lqr_limited(prob::HybridNLPHIP, Ztraj::Vector{Float64}, sat::Vector{Float64}, Q::Vector{Float64},
+                              R::Vector{Float64}, Qf::Vector{Float64}; events=nothing, model=nothing,
+                              with_cost_to_go::Bool=true)
+    N = prob.N
+    K = zeros(15, 4, N - 1)
+    P = with_cost_to_go ? zeros(120, N) : nothing
+    qln_check(ccall((:qln_tracking_lqr_limited_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Ztraj, model === nothing ? C_NULL : model, events === nothing ? C_NULL : events, sat, Q, R, Qf,
+                    K, P === nothing ? C_NULL : P))
+    return K, P
+end
+# saturation codes (N-1) -> (4, N-1) digits per channel (F1x, F1y, F2x, F2y): 0 free, 1 at the lower limit, 2 at the upper
+unpack_saturation(sat::Vector{Float64}) = [(Int(sat[k]) >> (2 * (m - 1))) & 3 for m in 1:4, k in 1:length(sat)]
+# gains K (15, 4, N-1) designed elsewhere, with the rows of the channels that rode a limit set to zero
+function mask_gains(K::Array{Float64,3}, sat::Vector{Float64})
+    s = unpack_saturation(sat)
+    return [s[m, k] == 0 ? K[j, m, k] : 0.0 for j in 1:size(K, 1), m in 1:4, k in 1:length(sat)]
+end
 
 # ---- the reference's Ipopt solve, for this evaluator type: a method of `solve` (src/moi.jl:46-103) ------------------------
 # Same generic function, same keyword arguments and defaults, same five things handed to Ipopt.  What differs from the

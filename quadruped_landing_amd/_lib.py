@@ -102,6 +102,7 @@ class QlnDropStateSampler(C.Structure):
 SOLVE_INFO_STRIDE = 16
 MULT_INFO_STRIDE = 16
 TOUCHDOWN_INFO_STRIDE = 8
+FORCE_LIMITS_N = 8  # {lo, hi} of F_x, F_y for a free foot, then for a standing one
 
 
 class QlnError(RuntimeError):
@@ -171,6 +172,14 @@ SIGNATURES = {
     "qln_tracking_covariance_host": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp]),
     "qln_tracking_lqr_guarded": (C.c_int, [_vp] + [_dp] * 8),
     "qln_tracking_lqr_guarded_host": (C.c_int, [_vp] + [_dp] * 8),
+    "qln_tracking_rollout_limited": (C.c_int, [_vp] + [_dp] * 5 + [C.c_int32] + [_dp] * 3),
+    "qln_tracking_rollout_limited_host": (C.c_int, [_vp] + [_dp] * 5 + [C.c_int32] + [_dp] * 3),
+    "qln_tracking_rollout_limited_jvp": (C.c_int, [_vp] + [_dp] * 12),
+    "qln_tracking_rollout_limited_vjp": (C.c_int, [_vp] + [_dp] * 11),
+    "qln_tracking_rollout_limited_jvp_host": (C.c_int, [_vp] + [_dp] * 12),
+    "qln_tracking_rollout_limited_vjp_host": (C.c_int, [_vp] + [_dp] * 11),
+    "qln_tracking_lqr_limited": (C.c_int, [_vp] + [_dp] * 9),
+    "qln_tracking_lqr_limited_host": (C.c_int, [_vp] + [_dp] * 9),
     "qln_tracking_covariance_guarded": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp, _dp]),
     "qln_tracking_covariance_guarded_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp, _dp]),
     "qln_eval_constraint_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp]),

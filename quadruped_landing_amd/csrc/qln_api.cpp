@@ -71,6 +71,7 @@ int32_t nnz_of(int32_t N, int32_t kt, int32_t fmt) { return qln::vals_layout(N, 
 int64_t tracking_k_total(const qln_dims& D) { return (int64_t)D.B * (D.N - 1) * QLN_TRACK_NU * QLN_NX; }
 int64_t tracking_p_total(const qln_dims& D) { return (int64_t)D.B * D.N * QLN_TRACK_P_NNZ; }
 int64_t tracking_marg_total(const qln_dims& D) { return (int64_t)D.B * D.N * QLN_TRACK_MARG_STRIDE; }
+int64_t tracking_sat_total(const qln_dims& D) { return (int64_t)D.B * (D.N - 1); }
 
 // The buffers of the host forms (qln_*_host), one per role.  A role's size follows from the role and the handle's layout
 // (host_role_size): no form can allocate a buffer that another finds too small.  An in-out argument is copied in whole,
@@ -103,6 +104,7 @@ enum HostRole {
     kEvent,  // out: the guarded roll-out's touchdown records; in: the same for its sweeps  [B][8]
     kEventD, // out: the guarded jvp's event_dot                            [B][8]
     kEventVar,  // out: the guarded covariance sweep's event_var            [B][2]
+    kSat,    // out: the limited roll-out's saturation codes; in: the same for its sweeps and gains  [B][N-1]
     kHostRoles
 };
 
@@ -180,6 +182,7 @@ int64_t host_role_size(const qln_handle* h, HostRole r) {
         case kModel: case kModelD: return (int64_t)D.B * QLN_MODEL_NP;
         case kEvent: case kEventD: return (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
         case kEventVar: return (int64_t)D.B * 2;
+        case kSat: return tracking_sat_total(D);
         case kHostRoles: break;
     }
     return 0;
@@ -1130,18 +1133,28 @@ static int check_no_overlap(std::initializer_list<Span> out, std::initializer_li
 
 // guarded: the sweep through the guard-triggered touchdown, which needs the roll-out's event records; its outputs may overlap
 // no input and not each other (the sweep on the handle's knot schedule has never looked)
+// limited: the design at the limited roll-out's active set, which needs its saturation record sat; event then selects the
+// guarded blocks, and without it the knot schedule's, which have no plant model
 static int check_tracking_lqr_args(const qln_handle* h, const double* Zref, const double* model, bool guarded, const double* event,
-                                   const double* Q, const double* R, const double* Qf, const double* K, const double* P,
-                                   const char* who) {
+                                   bool limited, const double* sat, const double* Q, const double* R, const double* Qf,
+                                   const double* K, const double* P, const char* who) {
+    // the limited form's checks need no handle and come first
+    if (limited && !sat)
+        return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null sat (the limited roll-out's saturation record)");
+    if (limited && !event && model)
+        return fail(QLN_ERR_INVALID_ARGUMENT,
+                    std::string(who) + ": model without event (the knot-scheduled design has no plant model)");
     if (int rc = check_handle(h)) return rc;
     if (!Zref || !K) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null Zref or K");
     if (int rc = check_tracking_weights(Q, R, Qf, who)) return rc;
-    if (!guarded) return QLN_OK;
-    if (!event) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null event (the guarded roll-out's records)");
+    if (!limited) {
+        if (!guarded) return QLN_OK;
+        if (!event) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null event (the guarded roll-out's records)");
+    }
     const qln_dims& D = h->dims;
     return check_no_overlap({{K, tracking_k_total(D)}, {P, tracking_p_total(D)}},
                             {{Zref, D.z_total}, {model, (int64_t)D.B * QLN_MODEL_NP},
-                             {event, (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE}}, who);
+                             {event, (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE}, {sat, tracking_sat_total(D)}}, who);
 }
 
 // host forms only: every entry finite, and mb, mf, lb > 0 (the device forms do not look at the values)
@@ -1172,45 +1185,88 @@ static int check_host_events(const qln_handle* h, const double* event, const cha
     return QLN_OK;
 }
 
+// host forms only: every entry of sat an integer code sum_m s_m 4^m with every digit s_m in {0, 1, 2} (the device forms do not
+// look at the values)
+static int check_host_sat(const qln_handle* h, const double* sat, const char* who) {
+    if (!sat) return QLN_OK;
+    const int64_t n1 = h->dims.N - 1;
+    for (int64_t i = 0; i < tracking_sat_total(h->dims); ++i) {
+        const double c = sat[i];
+        bool ok = c >= 0.0 && c <= 170.0 && c == std::floor(c);
+        for (int m = 0, v = ok ? (int)c : 0; ok && m < QLN_TRACK_NU; ++m, v >>= 2) ok = (v & 3) != 3;
+        if (!ok)
+            return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": sat[" + std::to_string(i / n1) + "][" + std::to_string(i % n1) +
+                                                      "] is not a saturation code (an integer with every base-4 digit in {0, 1, 2})");
+    }
+    return QLN_OK;
+}
+
+// NaN, or lo > hi, in one of the four {lo, hi} pairs of the force limits (+-inf: no limit on that side)
+static int check_force_limits(const double* lim, const char* who) {
+    if (!lim) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null lim");
+    for (int i = 0; i < QLN_FORCE_LIMITS_N; i += 2)
+        if (std::isnan(lim[i]) || std::isnan(lim[i + 1]) || lim[i] > lim[i + 1])
+            return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": lim[" + std::to_string(i) + "], lim[" + std::to_string(i + 1) +
+                                                      "] is not a {lo, hi} pair (a NaN, or lo > hi)");
+    return QLN_OK;
+}
+
 // The Riccati sweep: one body per memory form.  The entry point on the handle's knot schedule passes null for model and
 // event, and the launch then takes the kernel without its kGuard flag.
-static int tracking_lqr(qln_handle* h, const double* Zref, const double* model, bool guarded, const double* event,
-                        const double* Qdiag, const double* Rdiag, const double* Qfdiag, double* K, double* P, const char* who) {
-    if (int rc = check_tracking_lqr_args(h, Zref, model, guarded, event, Qdiag, Rdiag, Qfdiag, K, P, who)) return rc;
+static int tracking_lqr(qln_handle* h, const double* Zref, const double* model, bool guarded, const double* event, bool limited,
+                        const double* sat, const double* Qdiag, const double* Rdiag, const double* Qfdiag, double* K, double* P,
+                        const char* who) {
+    if (int rc = check_tracking_lqr_args(h, Zref, model, guarded, event, limited, sat, Qdiag, Rdiag, Qfdiag, K, P, who)) return rc;
     if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_lqr(h->p, Qdiag, Rdiag, Qfdiag, Zref, model, event, K, P, h->stream));
+    QLN_HIP(qln::launch_tracking_lqr(h->p, Qdiag, Rdiag, Qfdiag, Zref, model, event, sat, K, P, h->stream));
     return QLN_OK;
 }
 
 static int tracking_lqr_host(qln_handle* h, const double* Zref, const double* model, bool guarded, const double* event,
-                             const double* Qdiag, const double* Rdiag, const double* Qfdiag, double* K, double* P,
-                             const char* who) {
-    if (int rc = check_tracking_lqr_args(h, Zref, model, guarded, event, Qdiag, Rdiag, Qfdiag, K, P, who)) return rc;
+                             bool limited, const double* sat, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
+                             double* K, double* P, const char* who) {
+    if (int rc = check_tracking_lqr_args(h, Zref, model, guarded, event, limited, sat, Qdiag, Rdiag, Qfdiag, K, P, who)) return rc;
     if (int rc = check_host_models(h, model, who)) return rc;
     if (int rc = check_host_events(h, event, who)) return rc;
+    if (int rc = check_host_sat(h, sat, who)) return rc;
     if (int rc = bind_device(h)) return rc;
-    return host_call(h, {copy_in(kZ, Zref), copy_in(kModel, model), copy_in(kEvent, event), copy_out(kK, K), copy_out(kP, P)},
+    return host_call(h,
+                     {copy_in(kZ, Zref), copy_in(kModel, model), copy_in(kEvent, event), copy_in(kSat, sat), copy_out(kK, K),
+                      copy_out(kP, P)},
                      [&](double* const* d, bool) {
-                         return qln::launch_tracking_lqr(h->p, Qdiag, Rdiag, Qfdiag, d[kZ], d[kModel], d[kEvent], d[kK], d[kP],
-                                                         h->stream);
+                         return qln::launch_tracking_lqr(h->p, Qdiag, Rdiag, Qfdiag, d[kZ], d[kModel], d[kEvent], d[kSat], d[kK],
+                                                         d[kP], h->stream);
                      });
 }
 
 int qln_tracking_lqr(qln_handle* h, const double* Zref, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
                      double* K, double* P) {
-    return tracking_lqr(h, Zref, nullptr, false, nullptr, Qdiag, Rdiag, Qfdiag, K, P, "qln_tracking_lqr");
+    return tracking_lqr(h, Zref, nullptr, false, nullptr, false, nullptr, Qdiag, Rdiag, Qfdiag, K, P, "qln_tracking_lqr");
 }
 int qln_tracking_lqr_host(qln_handle* h, const double* Zref, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
                           double* K, double* P) {
-    return tracking_lqr_host(h, Zref, nullptr, false, nullptr, Qdiag, Rdiag, Qfdiag, K, P, "qln_tracking_lqr_host");
+    return tracking_lqr_host(h, Zref, nullptr, false, nullptr, false, nullptr, Qdiag, Rdiag, Qfdiag, K, P,
+                             "qln_tracking_lqr_host");
 }
 int qln_tracking_lqr_guarded(qln_handle* h, const double* Ztraj, const double* model, const double* event, const double* Qdiag,
                              const double* Rdiag, const double* Qfdiag, double* K, double* P) {
-    return tracking_lqr(h, Ztraj, model, true, event, Qdiag, Rdiag, Qfdiag, K, P, "qln_tracking_lqr_guarded");
+    return tracking_lqr(h, Ztraj, model, true, event, false, nullptr, Qdiag, Rdiag, Qfdiag, K, P, "qln_tracking_lqr_guarded");
 }
 int qln_tracking_lqr_guarded_host(qln_handle* h, const double* Ztraj, const double* model, const double* event,
                                   const double* Qdiag, const double* Rdiag, const double* Qfdiag, double* K, double* P) {
-    return tracking_lqr_host(h, Ztraj, model, true, event, Qdiag, Rdiag, Qfdiag, K, P, "qln_tracking_lqr_guarded_host");
+    return tracking_lqr_host(h, Ztraj, model, true, event, false, nullptr, Qdiag, Rdiag, Qfdiag, K, P,
+                             "qln_tracking_lqr_guarded_host");
+}
+// the design at the limited roll-out's active set: event selects the guarded blocks
+int qln_tracking_lqr_limited(qln_handle* h, const double* Ztraj, const double* model, const double* event, const double* sat,
+                             const double* Qdiag, const double* Rdiag, const double* Qfdiag, double* K, double* P) {
+    return tracking_lqr(h, Ztraj, model, event != nullptr, event, true, sat, Qdiag, Rdiag, Qfdiag, K, P,
+                        "qln_tracking_lqr_limited");
+}
+int qln_tracking_lqr_limited_host(qln_handle* h, const double* Ztraj, const double* model, const double* event, const double* sat,
+                                  const double* Qdiag, const double* Rdiag, const double* Qfdiag, double* K, double* P) {
+    return tracking_lqr_host(h, Ztraj, model, event != nullptr, event, true, sat, Qdiag, Rdiag, Qfdiag, K, P,
+                             "qln_tracking_lqr_limited_host");
 }
 
 // The roll-out and its two sweeps (k_tracking_rollout, _vjp, _jvp): one argument check and one body per operation and memory
@@ -1218,44 +1274,58 @@ int qln_tracking_lqr_guarded_host(qln_handle* h, const double* Ztraj, const doub
 // and model_bar, and the launch then takes the kernels without their kModel flag.  The host forms validate a model's and an
 // event record's values (check_host_models, check_host_events above); the device forms do not look at them.
 // event: the guarded roll-out's records (null: none asked for)
-static int check_tracking_rollout_args(const qln_handle* h, const double* Zref, const double* Zout, const double* event,
+// limited: the roll-out within the force limits lim, with its saturation record sat (may be null)
+static int check_tracking_rollout_args(const qln_handle* h, const double* Zref, const double* Zout, bool guarded,
+                                       const double* event, bool limited, const double* lim, const double* sat,
                                        const char* who) {
+    if (limited) {
+        if (int rc = check_force_limits(lim, who)) return rc;
+        if (!guarded && event)
+            return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": event with guarded == 0 (the knot schedule has no record)");
+    }
     if (int rc = check_handle(h)) return rc;
     if (!Zref || !Zout) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null Zref or Zout");
     const int64_t ne = (int64_t)h->dims.B * QLN_TOUCHDOWN_INFO_STRIDE;
     // K, x0 and model are not looked at
-    return check_no_overlap({{Zout, h->dims.z_total}, {event, ne}}, {{Zref, h->dims.z_total}}, who);
+    return check_no_overlap({{Zout, h->dims.z_total}, {event, ne}, {sat, tracking_sat_total(h->dims)}},
+                            {{Zref, h->dims.z_total}}, who);
 }
 
 // guarded: qln_tracking_rollout_guarded's touchdown by the free foot's height, with its event records (may be null)
 static int tracking_rollout(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
-                            double* Zout, bool guarded, double* event, const char* who) {
-    if (int rc = check_tracking_rollout_args(h, Zref, Zout, event, who)) return rc;
+                            double* Zout, bool guarded, double* event, bool limited, const double* lim, double* sat,
+                            const char* who) {
+    if (int rc = check_tracking_rollout_args(h, Zref, Zout, guarded, event, limited, lim, sat, who)) return rc;
     if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout(h->p, Zref, K, x0, model, Zout, guarded, event, h->stream));
+    QLN_HIP(qln::launch_tracking_rollout(h->p, Zref, K, x0, model, Zout, guarded, event, limited ? lim : nullptr, sat, h->stream));
     return QLN_OK;
 }
 
 static int tracking_rollout_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
-                                 double* Zout, bool guarded, double* event, const char* who) {
-    if (int rc = check_tracking_rollout_args(h, Zref, Zout, event, who)) return rc;
+                                 double* Zout, bool guarded, double* event, bool limited, const double* lim, double* sat,
+                                 const char* who) {
+    if (int rc = check_tracking_rollout_args(h, Zref, Zout, guarded, event, limited, lim, sat, who)) return rc;
     if (int rc = check_host_models(h, model, who)) return rc;
     if (int rc = bind_device(h)) return rc;
     return host_call(h,
                      {copy_in(kZ, Zref), copy_inout(kZio, Zout), copy_in(kK, K), copy_in(kX0, x0), copy_in(kModel, model),
-                      copy_out(kEvent, event)},
+                      copy_out(kEvent, event), copy_out(kSat, sat)},
                      [&](double* const* d, bool) {
                          return qln::launch_tracking_rollout(h->p, d[kZ], d[kK], d[kX0], d[kModel], d[kZio], guarded, d[kEvent],
-                                                             h->stream);
+                                                             limited ? lim : nullptr, d[kSat], h->stream);
                      });
 }
 
 // the reverse sweep: the handle first
 // guarded: the sweeps through the guard-triggered touchdown, which need the roll-out's event records
+// limited: the sweeps at the limited roll-out's active set, which need its saturation record sat (checked first: it needs no
+// handle); event then selects the guarded blocks
 static int check_tracking_vjp_args(const qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                   const double* model, bool guarded, const double* event, const double* Zbar,
-                                   const double* Zref_bar, const double* K_bar, const double* x0_bar, const double* model_bar,
-                                   const char* who) {
+                                   const double* model, bool guarded, const double* event, bool limited, const double* sat,
+                                   const double* Zbar, const double* Zref_bar, const double* K_bar, const double* x0_bar,
+                                   const double* model_bar, const char* who) {
+    if (limited && !sat)
+        return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null sat (the limited roll-out's saturation record)");
     if (int rc = check_handle(h)) return rc;
     const std::string w(who);
     if (!Zref || !Zout || !Zbar) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref, Zout or Zbar");
@@ -1265,45 +1335,54 @@ static int check_tracking_vjp_args(const qln_handle* h, const double* Zref, cons
     const int64_t nz = D.z_total, nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX, nm = (int64_t)D.B * QLN_MODEL_NP;
     const int64_t ne = (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
     return check_no_overlap({{Zref_bar, nz}, {K_bar, nk}, {x0_bar, nx}, {model_bar, nm}},
-                            {{Zref, nz}, {K, nk}, {Zout, nz}, {Zbar, nz}, {model, nm}, {event, ne}}, w);
+                            {{Zref, nz}, {K, nk}, {Zout, nz}, {Zbar, nz}, {model, nm}, {event, ne}, {sat, tracking_sat_total(D)}},
+                            w);
 }
 
 static int tracking_rollout_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
-                                bool guarded, const double* event, const double* Zbar, double* Zref_bar, double* K_bar,
-                                double* x0_bar, double* model_bar, const char* who) {
-    if (int rc = check_tracking_vjp_args(h, Zref, K, Zout, model, guarded, event, Zbar, Zref_bar, K_bar, x0_bar, model_bar, who))
+                                bool guarded, const double* event, bool limited, const double* sat, const double* Zbar,
+                                double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar, const char* who) {
+    if (int rc = check_tracking_vjp_args(h, Zref, K, Zout, model, guarded, event, limited, sat, Zbar, Zref_bar, K_bar, x0_bar,
+                                         model_bar, who))
         return rc;
     if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout_vjp(h->p, Zref, K, Zout, model, event, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
+    QLN_HIP(qln::launch_tracking_rollout_vjp(h->p, Zref, K, Zout, model, event, sat, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
                                              h->stream));
     return QLN_OK;
 }
 
 // Zref is staged only when K_bar asks for it (the kernel reads it for nothing else); otherwise Zout's buffer stands in.
 static int tracking_rollout_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                     const double* model, bool guarded, const double* event, const double* Zbar,
-                                     double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar, const char* who) {
-    if (int rc = check_tracking_vjp_args(h, Zref, K, Zout, model, guarded, event, Zbar, Zref_bar, K_bar, x0_bar, model_bar, who))
+                                     const double* model, bool guarded, const double* event, bool limited, const double* sat,
+                                     const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar,
+                                     const char* who) {
+    if (int rc = check_tracking_vjp_args(h, Zref, K, Zout, model, guarded, event, limited, sat, Zbar, Zref_bar, K_bar, x0_bar,
+                                         model_bar, who))
         return rc;
     if (int rc = check_host_models(h, model, who)) return rc;
     if (int rc = check_host_events(h, event, who)) return rc;
+    if (int rc = check_host_sat(h, sat, who)) return rc;
     if (int rc = bind_device(h)) return rc;
     return host_call(h,
                      {copy_in(kV, Zout), copy_in(kZbar, Zbar), copy_in(kZ, K_bar ? Zref : nullptr), copy_in(kK, K),
-                      copy_in(kModel, model), copy_in(kEvent, event), copy_inout(kZio, Zref_bar), copy_out(kKbar, K_bar),
-                      copy_out(kX0, x0_bar), copy_out(kModelD, model_bar)},
+                      copy_in(kModel, model), copy_in(kEvent, event), copy_in(kSat, sat), copy_inout(kZio, Zref_bar),
+                      copy_out(kKbar, K_bar), copy_out(kX0, x0_bar), copy_out(kModelD, model_bar)},
                      [&](double* const* d, bool) {
                          return qln::launch_tracking_rollout_vjp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kModel], d[kEvent],
-                                                                 d[kZbar], d[kZio], d[kKbar], d[kX0], d[kModelD], h->stream);
+                                                                 d[kSat], d[kZbar], d[kZio], d[kKbar], d[kX0], d[kModelD],
+                                                                 h->stream);
                      });
 }
 
 // the forward sweep: the checks that need no handle come first
 static int check_tracking_jvp_args(const qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                   const double* model, bool guarded, const double* event, const double* Zref_dot,
-                                   const double* K_dot, const double* x0_dot, const double* model_dot, const double* Zout_dot,
-                                   const double* event_dot, const char* who) {
+                                   const double* model, bool guarded, const double* event, bool limited, const double* sat,
+                                   const double* Zref_dot, const double* K_dot, const double* x0_dot, const double* model_dot,
+                                   const double* Zout_dot, const double* event_dot, const char* who) {
     const std::string w(who);
+    if (limited && !sat) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null sat (the limited roll-out's saturation record)");
+    if (limited && !event && event_dot)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": event_dot without event (the knot-scheduled sweep has no record)");
     if (guarded && !event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
     if (!Zref_dot && !K_dot && !x0_dot && !model_dot)
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every tangent is NULL (no direction)");
@@ -1314,110 +1393,122 @@ static int check_tracking_jvp_args(const qln_handle* h, const double* Zref, cons
     const int64_t nz = D.z_total, nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX, nm = (int64_t)D.B * QLN_MODEL_NP;
     const int64_t ne = (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
     return check_no_overlap({{Zout_dot, nz}, {event_dot, ne}},
-                            {{Zref, nz}, {K, nk}, {Zout, nz}, {model, nm}, {event, ne}, {Zref_dot, nz}, {K_dot, nk}, {x0_dot, nx},
-                             {model_dot, nm}}, w);
+                            {{Zref, nz}, {K, nk}, {Zout, nz}, {model, nm}, {event, ne}, {sat, tracking_sat_total(D)}, {Zref_dot, nz},
+                             {K_dot, nk}, {x0_dot, nx}, {model_dot, nm}}, w);
 }
 
 static int tracking_rollout_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
-                                bool guarded, const double* event, const double* Zref_dot, const double* K_dot,
-                                const double* x0_dot, const double* model_dot, double* Zout_dot, double* event_dot,
-                                const char* who) {
-    if (int rc = check_tracking_jvp_args(h, Zref, K, Zout, model, guarded, event, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
-                                         event_dot, who))
+                                bool guarded, const double* event, bool limited, const double* sat, const double* Zref_dot,
+                                const double* K_dot, const double* x0_dot, const double* model_dot, double* Zout_dot,
+                                double* event_dot, const char* who) {
+    if (int rc = check_tracking_jvp_args(h, Zref, K, Zout, model, guarded, event, limited, sat, Zref_dot, K_dot, x0_dot, model_dot,
+                                         Zout_dot, event_dot, who))
         return rc;
     if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout_jvp(h->p, Zref, K, Zout, model, event, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
+    QLN_HIP(qln::launch_tracking_rollout_jvp(h->p, Zref, K, Zout, model, event, sat, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
                                              event_dot, h->stream));
     return QLN_OK;
 }
 
 // Zref is staged only when K_dot is given (the kernel reads it for nothing else); otherwise Zout's buffer stands in.
 static int tracking_rollout_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                     const double* model, bool guarded, const double* event, const double* Zref_dot,
-                                     const double* K_dot, const double* x0_dot, const double* model_dot, double* Zout_dot,
-                                     double* event_dot, const char* who) {
-    if (int rc = check_tracking_jvp_args(h, Zref, K, Zout, model, guarded, event, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
-                                         event_dot, who))
+                                     const double* model, bool guarded, const double* event, bool limited, const double* sat,
+                                     const double* Zref_dot, const double* K_dot, const double* x0_dot, const double* model_dot,
+                                     double* Zout_dot, double* event_dot, const char* who) {
+    if (int rc = check_tracking_jvp_args(h, Zref, K, Zout, model, guarded, event, limited, sat, Zref_dot, K_dot, x0_dot, model_dot,
+                                         Zout_dot, event_dot, who))
         return rc;
     if (int rc = check_host_models(h, model, who)) return rc;
     if (int rc = check_host_events(h, event, who)) return rc;
+    if (int rc = check_host_sat(h, sat, who)) return rc;
     if (int rc = bind_device(h)) return rc;
     return host_call(h,
                      {copy_in(kV, Zout), copy_in(kZ, K_dot ? Zref : nullptr), copy_in(kK, K), copy_in(kModel, model),
-                      copy_in(kEvent, event), copy_in(kZdot, Zref_dot), copy_in(kKdot, K_dot), copy_in(kX0, x0_dot),
+                      copy_in(kEvent, event), copy_in(kSat, sat), copy_in(kZdot, Zref_dot), copy_in(kKdot, K_dot), copy_in(kX0, x0_dot),
                       copy_in(kModelD, model_dot), copy_inout(kZio, Zout_dot), copy_out(kEventD, event_dot)},
                      [&](double* const* d, bool) {
                          return qln::launch_tracking_rollout_jvp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kModel], d[kEvent],
-                                                                 d[kZdot], d[kKdot], d[kX0], d[kModelD], d[kZio], d[kEventD],
+                                                                 d[kSat], d[kZdot], d[kKdot], d[kX0], d[kModelD], d[kZio], d[kEventD],
                                                                  h->stream);
                      });
 }
 
-// the sixteen entry points: the forms without a model are the same path with null model arguments
+// the entry points: the forms without a model are the same path with null model arguments
 int qln_tracking_rollout(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout) {
-    return tracking_rollout(h, Zref, K, x0, nullptr, Zout, false, nullptr, "qln_tracking_rollout");
+    return tracking_rollout(h, Zref, K, x0, nullptr, Zout, false, nullptr, false, nullptr, nullptr, "qln_tracking_rollout");
 }
 int qln_tracking_rollout_host(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout) {
-    return tracking_rollout_host(h, Zref, K, x0, nullptr, Zout, false, nullptr, "qln_tracking_rollout_host");
+    return tracking_rollout_host(h, Zref, K, x0, nullptr, Zout, false, nullptr, false, nullptr, nullptr, "qln_tracking_rollout_host");
 }
 int qln_tracking_rollout_model(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
                                double* Zout) {
-    return tracking_rollout(h, Zref, K, x0, model, Zout, false, nullptr, "qln_tracking_rollout_model");
+    return tracking_rollout(h, Zref, K, x0, model, Zout, false, nullptr, false, nullptr, nullptr, "qln_tracking_rollout_model");
 }
 int qln_tracking_rollout_model_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
                                     double* Zout) {
-    return tracking_rollout_host(h, Zref, K, x0, model, Zout, false, nullptr, "qln_tracking_rollout_model_host");
+    return tracking_rollout_host(h, Zref, K, x0, model, Zout, false, nullptr, false, nullptr, nullptr, "qln_tracking_rollout_model_host");
 }
 
 int qln_tracking_rollout_guarded(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
                                  double* Zout, double* event) {
-    return tracking_rollout(h, Zref, K, x0, model, Zout, true, event, "qln_tracking_rollout_guarded");
+    return tracking_rollout(h, Zref, K, x0, model, Zout, true, event, false, nullptr, nullptr, "qln_tracking_rollout_guarded");
 }
 int qln_tracking_rollout_guarded_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
                                       double* Zout, double* event) {
-    return tracking_rollout_host(h, Zref, K, x0, model, Zout, true, event, "qln_tracking_rollout_guarded_host");
+    return tracking_rollout_host(h, Zref, K, x0, model, Zout, true, event, false, nullptr, nullptr,
+                                 "qln_tracking_rollout_guarded_host");
+}
+// the roll-out within contact-aware force limits: the knot-scheduled or the guarded one, with its saturation record
+int qln_tracking_rollout_limited(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
+                                 const double* lim, int32_t guarded, double* Zout, double* event, double* sat) {
+    return tracking_rollout(h, Zref, K, x0, model, Zout, guarded != 0, event, true, lim, sat, "qln_tracking_rollout_limited");
+}
+int qln_tracking_rollout_limited_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
+                                      const double* lim, int32_t guarded, double* Zout, double* event, double* sat) {
+    return tracking_rollout_host(h, Zref, K, x0, model, Zout, guarded != 0, event, true, lim, sat,
+                                 "qln_tracking_rollout_limited_host");
 }
 int qln_tracking_rollout_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
                              double* Zref_bar, double* K_bar, double* x0_bar) {
-    return tracking_rollout_vjp(h, Zref, K, Zout, nullptr, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, nullptr, "qln_tracking_rollout_vjp");
+    return tracking_rollout_vjp(h, Zref, K, Zout, nullptr, false, nullptr, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, nullptr, "qln_tracking_rollout_vjp");
 }
 int qln_tracking_rollout_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
                                   double* Zref_bar, double* K_bar, double* x0_bar) {
-    return tracking_rollout_vjp_host(h, Zref, K, Zout, nullptr, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, nullptr,
+    return tracking_rollout_vjp_host(h, Zref, K, Zout, nullptr, false, nullptr, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, nullptr,
                                      "qln_tracking_rollout_vjp_host");
 }
 int qln_tracking_rollout_model_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
                                    const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar) {
-    return tracking_rollout_vjp(h, Zref, K, Zout, model, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
+    return tracking_rollout_vjp(h, Zref, K, Zout, model, false, nullptr, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
                                 "qln_tracking_rollout_model_vjp");
 }
 int qln_tracking_rollout_model_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                         const double* model, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
                                         double* model_bar) {
-    return tracking_rollout_vjp_host(h, Zref, K, Zout, model, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
+    return tracking_rollout_vjp_host(h, Zref, K, Zout, model, false, nullptr, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
                                      "qln_tracking_rollout_model_vjp_host");
 }
 
 int qln_tracking_rollout_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zref_dot,
                              const double* K_dot, const double* x0_dot, double* Zout_dot) {
-    return tracking_rollout_jvp(h, Zref, K, Zout, nullptr, false, nullptr, Zref_dot, K_dot, x0_dot, nullptr, Zout_dot, nullptr,
+    return tracking_rollout_jvp(h, Zref, K, Zout, nullptr, false, nullptr, false, nullptr, Zref_dot, K_dot, x0_dot, nullptr, Zout_dot, nullptr,
                                 "qln_tracking_rollout_jvp");
 }
 int qln_tracking_rollout_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                   const double* Zref_dot, const double* K_dot, const double* x0_dot, double* Zout_dot) {
-    return tracking_rollout_jvp_host(h, Zref, K, Zout, nullptr, false, nullptr, Zref_dot, K_dot, x0_dot, nullptr, Zout_dot,
+    return tracking_rollout_jvp_host(h, Zref, K, Zout, nullptr, false, nullptr, false, nullptr, Zref_dot, K_dot, x0_dot, nullptr, Zout_dot,
                                      nullptr, "qln_tracking_rollout_jvp_host");
 }
 int qln_tracking_rollout_model_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
                                    const double* Zref_dot, const double* K_dot, const double* x0_dot, const double* model_dot,
                                    double* Zout_dot) {
-    return tracking_rollout_jvp(h, Zref, K, Zout, model, false, nullptr, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot, nullptr,
+    return tracking_rollout_jvp(h, Zref, K, Zout, model, false, nullptr, false, nullptr, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot, nullptr,
                                 "qln_tracking_rollout_model_jvp");
 }
 int qln_tracking_rollout_model_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                         const double* model, const double* Zref_dot, const double* K_dot, const double* x0_dot,
                                         const double* model_dot, double* Zout_dot) {
-    return tracking_rollout_jvp_host(h, Zref, K, Zout, model, false, nullptr, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
+    return tracking_rollout_jvp_host(h, Zref, K, Zout, model, false, nullptr, false, nullptr, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
                                      nullptr, "qln_tracking_rollout_model_jvp_host");
 }
 
@@ -1425,26 +1516,53 @@ int qln_tracking_rollout_model_jvp_host(qln_handle* h, const double* Zref, const
 int qln_tracking_rollout_guarded_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
                                      const double* event, const double* Zref_dot, const double* K_dot, const double* x0_dot,
                                      const double* model_dot, double* Zout_dot, double* event_dot) {
-    return tracking_rollout_jvp(h, Zref, K, Zout, model, true, event, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot, event_dot,
+    return tracking_rollout_jvp(h, Zref, K, Zout, model, true, event, false, nullptr, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot, event_dot,
                                 "qln_tracking_rollout_guarded_jvp");
 }
 int qln_tracking_rollout_guarded_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                           const double* model, const double* event, const double* Zref_dot, const double* K_dot,
                                           const double* x0_dot, const double* model_dot, double* Zout_dot, double* event_dot) {
-    return tracking_rollout_jvp_host(h, Zref, K, Zout, model, true, event, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
+    return tracking_rollout_jvp_host(h, Zref, K, Zout, model, true, event, false, nullptr, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
                                      event_dot, "qln_tracking_rollout_guarded_jvp_host");
 }
 int qln_tracking_rollout_guarded_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
                                      const double* event, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
                                      double* model_bar) {
-    return tracking_rollout_vjp(h, Zref, K, Zout, model, true, event, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
+    return tracking_rollout_vjp(h, Zref, K, Zout, model, true, event, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
                                 "qln_tracking_rollout_guarded_vjp");
 }
 int qln_tracking_rollout_guarded_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                           const double* model, const double* event, const double* Zbar, double* Zref_bar,
                                           double* K_bar, double* x0_bar, double* model_bar) {
-    return tracking_rollout_vjp_host(h, Zref, K, Zout, model, true, event, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
+    return tracking_rollout_vjp_host(h, Zref, K, Zout, model, true, event, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
                                      "qln_tracking_rollout_guarded_vjp_host");
+}
+
+// the sweeps at the limited roll-out's active set: the same path with its saturation record; event selects the guarded blocks
+int qln_tracking_rollout_limited_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
+                                     const double* event, const double* sat, const double* Zref_dot, const double* K_dot,
+                                     const double* x0_dot, const double* model_dot, double* Zout_dot, double* event_dot) {
+    return tracking_rollout_jvp(h, Zref, K, Zout, model, event != nullptr, event, true, sat, Zref_dot, K_dot, x0_dot, model_dot,
+                                Zout_dot, event_dot, "qln_tracking_rollout_limited_jvp");
+}
+int qln_tracking_rollout_limited_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                          const double* model, const double* event, const double* sat, const double* Zref_dot,
+                                          const double* K_dot, const double* x0_dot, const double* model_dot, double* Zout_dot,
+                                          double* event_dot) {
+    return tracking_rollout_jvp_host(h, Zref, K, Zout, model, event != nullptr, event, true, sat, Zref_dot, K_dot, x0_dot,
+                                     model_dot, Zout_dot, event_dot, "qln_tracking_rollout_limited_jvp_host");
+}
+int qln_tracking_rollout_limited_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
+                                     const double* event, const double* sat, const double* Zbar, double* Zref_bar, double* K_bar,
+                                     double* x0_bar, double* model_bar) {
+    return tracking_rollout_vjp(h, Zref, K, Zout, model, event != nullptr, event, true, sat, Zbar, Zref_bar, K_bar, x0_bar,
+                                model_bar, "qln_tracking_rollout_limited_vjp");
+}
+int qln_tracking_rollout_limited_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                          const double* model, const double* event, const double* sat, const double* Zbar,
+                                          double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar) {
+    return tracking_rollout_vjp_host(h, Zref, K, Zout, model, event != nullptr, event, true, sat, Zbar, Zref_bar, K_bar, x0_bar,
+                                     model_bar, "qln_tracking_rollout_limited_vjp_host");
 }
 
 // the covariance sweep (k_tracking_covariance).  The checks that need no handle come first.

@@ -296,8 +296,12 @@ hipError_t launch_hessian_lagrangian_product(const BatchParams& p, const double*
 // TVLQR gains (and cost-to-go, P may be null) along the reference trajectories Zref (qln_tracking_kernels.hip).  Qd / Rd / Qfd
 // are host arrays.  event (null: the handle's knot schedule and model): the guarded roll-out's records, whose knot and tau the
 // sweep through the touchdown reads (qln_tracking_lqr_guarded), with model [B][QLN_MODEL_NP] (null: the handle's).
+// sat [B][N-1] (null: none): the limited roll-out's saturation codes, whose channels' columns of B_k are zero
+// (qln_tracking_lqr_limited); the sweeps below take it the same way, and the roll-out writes it (null: not written) when lim, a
+// host array of QLN_FORCE_LIMITS_N doubles, is given (qln_tracking_rollout_limited).
 hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const double* Rd, const double* Qfd, const double* Zref,
-                               const double* model, const double* event, double* K, double* P, hipStream_t stream);
+                               const double* model, const double* event, const double* sat, double* K, double* P,
+                               hipStream_t stream);
 // The roll-out from x0 (null: the handle's x0) and its two sweeps at Zout's trajectory, with a per-problem plant: model
 // [B][QLN_MODEL_NP] = (g, mb, mf, lb) per problem (null: the handle's), its tangent model_dot and cotangent model_bar in the same
 // layout.  Reverse: cotangent Zbar -> Zref_bar, K_bar, x0_bar, model_bar (each may be null).  Forward: tangents Zref_dot, K_dot,
@@ -305,16 +309,17 @@ hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const dou
 // With nothing of the model passed the kernels run without their kModel flag (qln_tracking_kernels.hip).
 // guarded: touchdown by the free foot's height instead of the knot schedule; event [B][QLN_TOUCHDOWN_INFO_STRIDE] or null
 hipError_t launch_tracking_rollout(const BatchParams& p, const double* Zref, const double* K, const double* x0,
-                                   const double* model, double* Zout, bool guarded, double* event, hipStream_t stream);
+                                   const double* model, double* Zout, bool guarded, double* event, const double* lim,
+                                   double* sat, hipStream_t stream);
 // event (null: the knot-scheduled sweeps): the guarded roll-out's records, whose knot and tau the sweeps through the
 // touchdown read (qln_tracking_rollout_guarded_vjp / _jvp); event_dot [B][QLN_TOUCHDOWN_INFO_STRIDE] or null, with event only.
 hipError_t launch_tracking_rollout_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
-                                       const double* model, const double* event, const double* Zbar, double* Zref_bar,
-                                       double* K_bar, double* x0_bar, double* model_bar, hipStream_t stream);
+                                       const double* model, const double* event, const double* sat, const double* Zbar,
+                                       double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar, hipStream_t stream);
 hipError_t launch_tracking_rollout_jvp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
-                                       const double* model, const double* event, const double* Zref_dot, const double* K_dot,
-                                       const double* x0_dot, const double* model_dot, double* Zout_dot, double* event_dot,
-                                       hipStream_t stream);
+                                       const double* model, const double* event, const double* sat, const double* Zref_dot,
+                                       const double* K_dot, const double* x0_dot, const double* model_dot, double* Zout_dot,
+                                       double* event_dot, hipStream_t stream);
 // Sigma_{k+1} = (A_k - B_k K_k) Sigma_k (A_k - B_k K_k)' + diag(Wd) along Zout (K null: open loop); Sigma0 [sigma0_batch][120],
 // Wd a host array (null: zeros); Sigma [B][N][120] and marg [B][N][8], either may be null (qln_tracking_kernels.hip).
 // event and model as for launch_tracking_lqr (qln_tracking_covariance_guarded); event_var [B][2] or null, with event only.

@@ -67,6 +67,11 @@
 // DESIGN.md 4.19): the flags kModel and kGuard on k_tracking_lqr and k_tracking_covariance.  Their lanes hold whole 15-vectors,
 // so the touchdown knot's composite block is applied to them as an operator, stated once (TouchdownBlock, touchdown_apply,
 // touchdown_apply_t): forward in the covariance sweep, transposed in the Riccati sweep.
+//
+// The roll-out, its two sweeps and the Riccati sweep also exist with contact-aware force limits (qln_tracking_rollout_limited and
+// its _jvp / _vjp, qln_tracking_lqr_limited): the flag kLimit.  The roll-out clamps the applied forces by the
+// foot's contact state and records the channels that rode a limit; the sweeps and the Riccati sweep read that record and treat
+// those channels as constants (no tangent, no cotangent, a zero column of B_k).
 #include "qln_row16.h"
 
 #include <utility>
@@ -243,6 +248,44 @@ struct TrackWeights {
     double Q[15], R[4], Qf[15];
 };
 
+// The contact-aware force limits (qln_tracking_rollout_limited): {lo, hi} of F_x and F_y for a free foot, then
+// for a standing one, passed by value in the kernel arguments.
+struct ForceLimits {
+    double v[QLN_FORCE_LIMITS_N];
+};
+
+// Channel m's clamp: s = 1 below lo, 2 above hi, else 0 (a NaN fails both comparisons and passes through); returns 4^m s, the
+// channel's digit of the knot's saturation code.  The limits are selected by the foot's contact state, never indexed: a
+// private array indexed at run time is laid out in scratch memory.
+template <int m>
+__device__ __forceinline__ double clamp_channel(const ForceLimits& lim, bool stand, double& F) {
+    constexpr int ax = 2 * (m & 1);  // F_x or F_y
+    const double lo = stand ? lim.v[4 + ax] : lim.v[ax], hi = stand ? lim.v[5 + ax] : lim.v[1 + ax];
+    const bool below = F < lo, above = F > hi;
+    F = below ? lo : above ? hi : F;
+    return below ? (double)(1 << (2 * m)) : above ? (double)(2 << (2 * m)) : 0.0;
+}
+// the applied forces of a knot within the limits; stand1, stand2: the foot stands at the knot's start.  Returns the code.
+__device__ __forceinline__ double clamp_forces(const ForceLimits& lim, bool stand1, bool stand2, double (&u)[5]) {
+    double code = clamp_channel<0>(lim, stand1, u[0]);
+    code += clamp_channel<1>(lim, stand1, u[1]);
+    code += clamp_channel<2>(lim, stand2, u[2]);
+    code += clamp_channel<3>(lim, stand2, u[3]);
+    return code;
+}
+// A knot's saturation code as the sweeps read it: bit m says channel m rode a limit (digit s_m != 0).  Anything that is not a
+// code (the device forms do not validate sat) is no channel at all.
+__device__ __forceinline__ unsigned limit_mask(double code) {
+    const unsigned c = (code >= 0.0 && code <= 170.0) ? (unsigned)code : 0u;
+    return ((c | (c >> 1)) & 0x55u);
+}
+__device__ __forceinline__ bool limited(unsigned mask, int m) { return (mask >> (2 * m)) & 1u; }
+// v[m] = 0 on the channels of the mask: a clamped force is a constant (selected, so that nothing non-finite survives)
+__device__ __forceinline__ void limit_zero4(unsigned mask, double (&v)[4]) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) v[m] = limited(mask, m) ? 0.0 : v[m];
+}
+
 // The knot's block is formed in every lane's registers; forming it once per row into LDS tables was measured slower
 // (profiles/tracking_variants.txt).
 // kGuard (qln_tracking_lqr_guarded, with kModel): the blocks of the guarded sweeps at Zref's (x_k, u_k).  The model is the
@@ -253,10 +296,15 @@ struct TrackWeights {
 // of S gives Quu, the same in every lane.  The factorisation, the K column, P_k's row and the stores are the same code for
 // every knot; the rows of a wave reach their ks in different iterations, and only the operator applications diverge.  T's
 // image has a row stride of kLTGuard here, so that neither the lanes' row writes nor their column reads share a bank.
-template <bool kWantP, bool kModel, bool kGuard>
+// kLimit (qln_tracking_lqr_limited): the columns of B_k of the channels that rode a limit at knot k (sat, the
+// limited roll-out's record, decoded once per knot) are zero.  On the block's tables that is S = P B's and Quu's; on the composite
+// operator it is B*'p's entries, the mask at the operator's force input, so the rank-one d tau term loses the channel too.
+// Quu then decouples to R_m on those channels and their rows of K are exact zeros.
+template <bool kWantP, bool kModel, bool kGuard, bool kLimit = false>
 __global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeights W, const double* __restrict__ Zref,
                                                         double* __restrict__ Kout, double* __restrict__ Pout,
-                                                        const double* __restrict__ model, const double* __restrict__ event) {
+                                                        const double* __restrict__ model, const double* __restrict__ event,
+                                                        const double* __restrict__ sat) {
     static_assert(kModel || !kGuard, "the guarded sweep runs on the kModel path");
     // T's row stride, and the sections behind it
     constexpr int kTS = kGuard ? kLTGuard : 16, kLS = kLT + (kGuard ? 16 * 16 : 15 * 16), kLK = kLS + 60, kLP = kLK + 60,
@@ -312,6 +360,8 @@ __global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeig
         if constexpr (kGuard) md = guard_mode(k, ks, im);
         else md = knot_mode(k + 1, kt - 1, im);
         const bool td = kGuard && k == ks;  // the touchdown knot: the composite operator instead of the block's tables
+        [[maybe_unused]] unsigned lmask = 0u;
+        if constexpr (kLimit) lmask = limit_mask(sat[(int64_t)bc * (N - 1) + k]);
         [[maybe_unused]] TouchdownBlock tb;
         double Ac[15][4], Bm[15][4];
         double t[15], sr[4];
@@ -323,6 +373,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeig
             const double u5[5] = {F1x, F1y, F2x, F2y, h};
             tb = touchdown_block(M, md, tau, xk, u5);
             touchdown_apply_t(tb, M, p, t, sr);
+            if constexpr (kLimit) limit_zero4(lmask, sr);
         } else {
 #pragma unroll
             for (int c = 0; c < 15; ++c)
@@ -362,6 +413,8 @@ __global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeig
                     }
                 sr[m] = acc;
             }
+            // the masked columns of B, where they show: S = P B here, Quu's rows and columns below (Qux reads S alone)
+            if constexpr (kLimit) limit_zero4(lmask, sr);
         }
         if (own) {
 #pragma unroll
@@ -378,6 +431,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeig
 #pragma unroll
             for (int i = 0; i < 15; ++i) tc[i] = L[kLT + kTS * i + j];
             touchdown_apply_t(tb, M, tc, qx, qu);
+            if constexpr (kLimit) limit_zero4(lmask, qu);
             // Quu = R + B*'S, column by column
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
@@ -385,6 +439,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeig
 #pragma unroll
                 for (int i = 0; i < 15; ++i) sc[i] = L[kLS + 4 * i + m];
                 touchdown_apply_t(tb, M, sc, ax, bs);
+                if constexpr (kLimit) limit_zero4(lmask, bs);
 #pragma unroll
                 for (int n = m; n < 4; ++n) {
                     const double acc = (m == n) ? W.R[m] + bs[n] : bs[n];
@@ -418,6 +473,10 @@ __global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeig
 #pragma unroll
                     for (int r = 0; r < 15; ++r)
                         if ((b_rows_mask(n) >> r) & 1u) acc = fma(L[kLS + 4 * r + m], Bm[r][n], acc);
+                    if constexpr (kLimit) {
+                        if (m != n) acc = (limited(lmask, n) || limited(lmask, m)) ? 0.0 : acc;
+                        else acc = limited(lmask, n) ? W.R[n] : acc;
+                    }
                     q[n][m] = acc;
                     q[m][n] = acc;
                 }
@@ -541,11 +600,16 @@ __device__ __forceinline__ void guarded_step(const Model& M, int k, int& mode, c
 // kGuard (qln_tracking_rollout_guarded): the handle's k_trans is not read.  The problem stays in init_mode until its free
 // foot reaches the ground; the knot in which it does takes the composite step of guarded_step, and every later knot is in
 // mode 3.  event (null: not written) gets the problem's QLN_TOUCHDOWN_INFO_STRIDE doubles after the last knot.
-template <bool kModel, bool kGuard>
+// kLimit (qln_tracking_rollout_limited, DESIGN.md 4.20, with kModel): the forces are clamped to lim before they are stored,
+// before the guard and before the step, with the limits of a standing or of a free foot by the contact mode at the knot's
+// start (the lane's mode, or the knot schedule's); sat (null: not written) gets the knot's code sum_m s_m 4^m.
+template <bool kModel, bool kGuard, bool kLimit = false>
 __global__ __launch_bounds__(kWave) void k_tracking_rollout(BatchParams P, const double* __restrict__ Zref,
                                                             const double* __restrict__ Kg, const double* __restrict__ x0,
                                                             double* __restrict__ Zout, const double* __restrict__ model,
-                                                            double* __restrict__ event) {
+                                                            double* __restrict__ event, ForceLimits lim,
+                                                            double* __restrict__ sat) {
+    static_assert(kModel || !kLimit, "the limited roll-out runs on the kModel path");
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= P.B) return;
     const ProblemDesc pd = P.desc[b];
@@ -577,6 +641,17 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout(BatchParams P, const
                 for (int i = 1; i < 15; ++i) du = fma(Kk[15 * m + i], dx[i], du);
                 u[m] = u[m] - du;
             }
+        }
+        if constexpr (kLimit) {
+            bool stand1, stand2;
+            if constexpr (kGuard) {
+                stand1 = mode != 2, stand2 = mode != 1;
+            } else {
+                const KnotMode md = knot_mode(k + 1, kt - 1, im);
+                stand1 = !md.f1free, stand2 = !md.f2free;
+            }
+            const double code = clamp_forces(lim, stand1, stand2, u);
+            if (sat) sat[(int64_t)b * (N - 1) + k] = code;
         }
 #pragma unroll
         for (int i = 0; i < 5; ++i) Zo[20 * k + 15 + i] = u[i];
@@ -729,15 +804,20 @@ __device__ __forceinline__ double vjp_apply_column(const VjpLane& c, const doubl
 // the jump map's zeros, vjp_apply_column through the flight leg at (x_k, tau); what the two h columns leave for tau goes, by
 // d tau's coefficients, onto lam[iy], lam[iv], the free foot's ubar_F_y and the model's g and mf.  x- and x+ are recomputed by
 // every lane of the row with step_mode, as the roll-out forms them.
-template <bool kHasK, bool kModel, bool kGuard>
+// kLimit (qln_tracking_rollout_limited_vjp, DESIGN.md 4.20, with kModel): a channel that rode a limit at knot k (sat, the limited
+// roll-out's record) was a constant, so its ubar is zeroed -- after the touchdown knot's taubar has been distributed onto it,
+// before it enters K_k'ubar, K_bar and Zref_bar.
+template <bool kHasK, bool kModel, bool kGuard, bool kLimit = false>
 __global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, const double* __restrict__ Zref,
                                                                 const double* __restrict__ Kg, const double* __restrict__ Zout,
                                                                 const double* __restrict__ Zbar, double* __restrict__ Zref_bar,
                                                                 double* __restrict__ Kbar, double* __restrict__ x0_bar,
                                                                 const double* __restrict__ model,
                                                                 double* __restrict__ model_bar,
-                                                                const double* __restrict__ event) {
+                                                                const double* __restrict__ event,
+                                                                const double* __restrict__ sat) {
     static_assert(kModel || !kGuard, "the guarded sweep runs on the kModel path");
+    static_assert(kModel || !kLimit, "the limited sweep runs on the kModel path");
     const Row16 r16 = row16_of(P);  // lane 15 reads lane 14's slots and contributes nothing
     const int j = r16.j, b = r16.b, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
     const bool own = r16.own, valid = r16.valid;
@@ -786,9 +866,17 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, c
     if (valid && Zref_bar && own) Zref_bar[(int64_t)b * P.z_stride + 20 * (N - 1) + j] = 0.0;  // x_ref,N-1: never read
     VjpKnot cur, nxt;
     vjp_load<kHasK>(nxt, Zo, Zb, Zr, Kb + (kHasK ? (int64_t)(N - 2) * 60 : 0), N - 2, j);
+    // the knot's saturation code, loaded with the knot's slices (the same value in every lane of the row)
+    [[maybe_unused]] const double* __restrict__ Sb = kLimit ? sat + (int64_t)bc * (N - 1) : nullptr;
+    [[maybe_unused]] double satc = 0.0, satn = 0.0;
+    if constexpr (kLimit) satn = Sb[N - 2];
     for (int k = N - 2; k >= 0; --k) {
         cur = nxt;
         if (k > 0) vjp_load<kHasK>(nxt, Zo, Zb, Zr, Kb + (kHasK ? (int64_t)(k - 1) * 60 : 0), k - 1, j);
+        if constexpr (kLimit) {
+            satc = satn;
+            if (k > 0) satn = Sb[k - 1];
+        }
         KnotMode md;
         if constexpr (kGuard) md = guard_mode(k, ks, im);
         else md = knot_mode(k + 1, kt - 1, im);
@@ -884,6 +972,11 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, c
             ub[0] = fma(gm, ga1, ub[0]);
             ub[2] = fma(gm, ga2, ub[2]);
             ub[4] = fma(be, taua, ub[4]);
+        }
+        if constexpr (kLimit) {
+            const unsigned lmask = limit_mask(satc);
+#pragma unroll
+            for (int m = 0; m < 4; ++m) ub[m] = limited(lmask, m) ? 0.0 : ub[m];
         }
         // ---- K'ubar, lam_k, and the outputs of the knot ----
         double kub = 0.0;
@@ -1271,7 +1364,9 @@ __device__ __forceinline__ double jvp_apply_row(int j, bool own, const StepBlock
 // model's tangent over w, the foot's vertical velocity in x- = step_mode(x_k; tau), which every lane of the row recomputes;
 // jvp_apply_row through the flight leg at (x_k, tau) with d tau in the place of dh, the jump map's zeros, jvp_apply_row
 // through the mode-3 leg at (x+, h - tau) with dh - d tau.  event_dot (null: not written) gets d tau and the clock's tangent.
-template <bool kHasK, bool kHasKd, bool kHasZd, bool kModel, bool kGuard>
+// kLimit (qln_tracking_rollout_limited_jvp, DESIGN.md 4.20, with kModel): a channel that rode a limit at knot k (sat, the limited
+// roll-out's record) was a constant: its dF is zero, for everything downstream, the touchdown knot's d tau included.
+template <bool kHasK, bool kHasKd, bool kHasZd, bool kModel, bool kGuard, bool kLimit = false>
 __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, const double* __restrict__ Zref,
                                                                 const double* __restrict__ Kg, const double* __restrict__ Zout,
                                                                 const double* __restrict__ Zref_dot,
@@ -1281,8 +1376,10 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, c
                                                                 const double* __restrict__ model,
                                                                 const double* __restrict__ model_dot,
                                                                 const double* __restrict__ event,
-                                                                double* __restrict__ event_dot) {
+                                                                double* __restrict__ event_dot,
+                                                                const double* __restrict__ sat) {
     static_assert(kHasK || !kHasKd, "Kdot needs K");
+    static_assert(kModel || !kLimit, "the limited sweep runs on the kModel path");
     static_assert(kModel || !kGuard, "the guarded sweep runs on the kModel path");
     const Row16 r16 = row16_of(P);  // lane 15 reads lane 14's slots and contributes nothing
     const int ln = r16.ln, j = r16.j, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
@@ -1312,9 +1409,17 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, c
     double dx = (own && x0_dot) ? x0_dot[(int64_t)bc * QLN_NX + j] : 0.0;
     JvpKnot cur, nxt;
     jvp_load<kHasK, kHasKd, kHasZd>(nxt, Zo, Zd, Zr, Kb, Kdb, 0, ln, j);
+    // the knot's saturation code, loaded with the knot's slices (the same value in every lane of the row)
+    [[maybe_unused]] const double* __restrict__ Sb = kLimit ? sat + (int64_t)bc * (N - 1) : nullptr;
+    [[maybe_unused]] double satc = 0.0, satn = 0.0;
+    if constexpr (kLimit) satn = Sb[0];
     for (int k = 0; k < N - 1; ++k) {
         cur = nxt;
         if (k + 1 < N - 1) jvp_load<kHasK, kHasKd, kHasZd>(nxt, Zo, Zd, Zr, Kb, Kdb, k + 1, ln, j);
+        if constexpr (kLimit) {
+            satc = satn;
+            if (k + 1 < N - 1) satn = Sb[k + 1];
+        }
         // ---- the knot's state and controls, in every lane ----
         double x[14];
         row_bcast_first(cur.z0, x, std::make_integer_sequence<int, 14>{});
@@ -1347,6 +1452,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, c
                 dF[m] = dF[m] - row_sum16(own ? t : 0.0);
             }
         }
+        if constexpr (kLimit) limit_zero4(limit_mask(satc), dF);
         // ---- row j of [A B G] on the knot's tangents ----
         double acc;
         if constexpr (kGuard) {
@@ -1409,8 +1515,11 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, c
 // event (the guarded roll-out's records) sends the Riccati and the covariance sweep to their kGuard instantiations, which exist
 // on the kModel path only, as the roll-out's sweeps': a null model there is the handle's four values.  Without event, model is
 // not read.
+// sat (the limited roll-out's saturation record) sends it to the kLimit instantiations: the guarded pair with event, the
+// knot-scheduled pair without.
 hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const double* Rd, const double* Qfd, const double* Zref,
-                               const double* model, const double* event, double* K, double* P, hipStream_t stream) {
+                               const double* model, const double* event, const double* sat, double* K, double* P,
+                               hipStream_t stream) {
     TrackWeights w;
     for (int i = 0; i < 15; ++i) {
         w.Q[i] = Qd[i];
@@ -1418,9 +1527,13 @@ hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const dou
     }
     for (int i = 0; i < 4; ++i) w.R[i] = Rd[i];
     auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, w, Zref, K, P, model, event);
+        hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, w, Zref, K, P, model, event, sat);
     };
-    if (event)
+    if (sat && event)
+        P ? go(k_tracking_lqr<true, true, true, true>) : go(k_tracking_lqr<false, true, true, true>);
+    else if (sat)
+        P ? go(k_tracking_lqr<true, false, false, true>) : go(k_tracking_lqr<false, false, false, true>);
+    else if (event)
         P ? go(k_tracking_lqr<true, true, true>) : go(k_tracking_lqr<false, true, true>);
     else
         P ? go(k_tracking_lqr<true, false, false>) : go(k_tracking_lqr<false, false, false>);
@@ -1430,11 +1543,19 @@ hipError_t launch_tracking_lqr(const BatchParams& p, const double* Qd, const dou
 // The roll-out and its two sweeps.  kModel is on only where something of the model is passed: the forms at the handle's model
 // pass null and run the instantiation without the flag.
 hipError_t launch_tracking_rollout(const BatchParams& p, const double* Zref, const double* K, const double* x0,
-                                   const double* model, double* Zout, bool guarded, double* event, hipStream_t stream) {
+                                   const double* model, double* Zout, bool guarded, double* event, const double* lim,
+                                   double* sat, hipStream_t stream) {
+    ForceLimits fl{};
+    if (lim)
+        for (int i = 0; i < QLN_FORCE_LIMITS_N; ++i) fl.v[i] = lim[i];
     auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3((p.B + kWave - 1) / kWave), dim3(kWave), 0, stream, p, Zref, K, x0, Zout, model, event);
+        hipLaunchKernelGGL(kern, dim3((p.B + kWave - 1) / kWave), dim3(kWave), 0, stream, p, Zref, K, x0, Zout, model, event, fl,
+                           sat);
     };
-    if (guarded)
+    // lim (host, QLN_FORCE_LIMITS_N doubles): the limited roll-out, on the kModel path whether a model is given or not
+    if (lim)
+        guarded ? go(k_tracking_rollout<true, true, true>) : go(k_tracking_rollout<true, false, true>);
+    else if (guarded)
         model ? go(k_tracking_rollout<true, true>) : go(k_tracking_rollout<false, true>);
     else
         model ? go(k_tracking_rollout<true, false>) : go(k_tracking_rollout<false, false>);
@@ -1445,13 +1566,18 @@ hipError_t launch_tracking_rollout(const BatchParams& p, const double* Zref, con
 // only: a null model there is the handle's four values.  2 of the reverse sweep (K or not) and 6 of the tangent sweep (the six
 // combinations of K, K_dot and Zref_dot that exist without the flag).
 hipError_t launch_tracking_rollout_vjp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
-                                       const double* model, const double* event, const double* Zbar, double* Zref_bar,
-                                       double* K_bar, double* x0_bar, double* model_bar, hipStream_t stream) {
+                                       const double* model, const double* event, const double* sat, const double* Zbar,
+                                       double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar, hipStream_t stream) {
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar,
-                           model, model_bar, event);
+                           model, model_bar, event, sat);
     };
-    if (event)
+    // sat (the limited roll-out's saturation record): the kLimit instantiations, on the kModel path
+    if (sat && event)
+        K ? go(k_tracking_rollout_vjp<true, true, true, true>) : go(k_tracking_rollout_vjp<false, true, true, true>);
+    else if (sat)
+        K ? go(k_tracking_rollout_vjp<true, true, false, true>) : go(k_tracking_rollout_vjp<false, true, false, true>);
+    else if (event)
         K ? go(k_tracking_rollout_vjp<true, true, true>) : go(k_tracking_rollout_vjp<false, true, true>);
     else if (model || model_bar)
         K ? go(k_tracking_rollout_vjp<true, true, false>) : go(k_tracking_rollout_vjp<false, true, false>);
@@ -1461,17 +1587,21 @@ hipError_t launch_tracking_rollout_vjp(const BatchParams& p, const double* Zref,
 }
 
 hipError_t launch_tracking_rollout_jvp(const BatchParams& p, const double* Zref, const double* K, const double* Zout,
-                                       const double* model, const double* event, const double* Zref_dot, const double* K_dot,
-                                       const double* x0_dot, const double* model_dot, double* Zout_dot, double* event_dot,
-                                       hipStream_t stream) {
+                                       const double* model, const double* event, const double* sat, const double* Zref_dot,
+                                       const double* K_dot, const double* x0_dot, const double* model_dot, double* Zout_dot,
+                                       double* event_dot, hipStream_t stream) {
     if (K_dot && !K) return hipErrorInvalidValue;
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, Zref, K, Zout, Zref_dot, K_dot, x0_dot,
-                           Zout_dot, model, model_dot, event, event_dot);
+                           Zout_dot, model, model_dot, event, event_dot, sat);
     };
-    // kHasK, kHasKd, kHasZd as compile-time flags, then kModel and kGuard
+    // kHasK, kHasKd, kHasZd as compile-time flags, then kModel and kGuard (and kLimit where sat is given)
     auto pick = [&](auto hasK, auto hasKd, auto hasZd) {
-        if (event)
+        if (sat && event)
+            go(k_tracking_rollout_jvp<hasK(), hasKd(), hasZd(), true, true, true>);
+        else if (sat)
+            go(k_tracking_rollout_jvp<hasK(), hasKd(), hasZd(), true, false, true>);
+        else if (event)
             go(k_tracking_rollout_jvp<hasK(), hasKd(), hasZd(), true, true>);
         else if (model || model_dot)
             go(k_tracking_rollout_jvp<hasK(), hasKd(), hasZd(), true, false>);

@@ -156,6 +156,35 @@ def tracking_noise(W):
     return np.ascontiguousarray(np.broadcast_to(np.asarray(W, dtype=np.float64), (n,)))
 
 
+def force_limits(limits):
+    """The eight force limits {free_x_lo, free_x_hi, free_y_lo, free_y_hi, stand_x_lo, stand_x_hi, stand_y_lo, stand_y_hi} as
+    the contiguous float64 array the limited calls pass; +-inf means no limit on that side.  A NaN, or lo > hi, is refused."""
+    lim = np.ascontiguousarray(np.asarray(limits, dtype=np.float64).reshape(-1))
+    if lim.size != _lib.FORCE_LIMITS_N:
+        raise ValueError(f"limits has {lim.size} entries, expected {_lib.FORCE_LIMITS_N}")
+    if np.isnan(lim).any() or (lim[0::2] > lim[1::2]).any():
+        raise ValueError("limits: a NaN, or a lower limit above its upper limit")
+    return lim
+
+
+def unpack_saturation(sat):
+    """Saturation codes (B, N-1) (numpy or a tensor) -> int8 (B, N-1, 4): per channel (F1x, F1y, F2x, F2y) 0 for a free
+    force, 1 for one held at its lower limit, 2 at its upper limit."""
+    c = (sat.detach().cpu().numpy() if hasattr(sat, "detach") else np.asarray(sat)).astype(np.int64)
+    return ((c[..., None] >> np.array([0, 2, 4, 6])) & 3).astype(np.int8)
+
+
+def mask_gains(K, sat):
+    """Gains K (B, N-1, 4, 15) designed elsewhere, with the rows of the channels that rode a limit (sat, the limited
+    roll-out's record) set to zero: A - B K is then the closed loop of the clamped system, for the covariance calls.  numpy
+    in, numpy out; tensors in, a tensor out."""
+    free = unpack_saturation(sat) == 0
+    if hasattr(K, "detach"):
+        T = _torch()
+        return T.where(T.from_numpy(free).to(K.device).reshape(K.shape[:-1] + (1,)), K, T.zeros((), dtype=K.dtype, device=K.device))
+    return np.where(free[..., None], np.asarray(K), 0.0)
+
+
 def _torch():
     import torch
 
@@ -1030,7 +1059,176 @@ class HybridNLP:
                                                                    _host_ptr(S), _host_ptr(mg), _host_ptr(var)))
         return S, mg, var
 
-    def differentiable_rollout(self, Zref, K=None, x0=None, model=None, guarded=False):
+    # -- contact-aware force limits: the roll-out, its sweeps and the gains at fixed active set ------
+    def _sat_ptr(self, sat):
+        if sat is None:
+            raise ValueError("sat is required: the saturation record tracking_rollout_limited returned with Zout")
+        return self._check(sat, self.B * (self.N - 1), "sat")
+
+    def _host_sat(self, sat):
+        if sat is None:
+            raise ValueError("sat is required: the saturation record tracking_rollout_limited_host returned with Zout")
+        s = np.ascontiguousarray(np.asarray(sat, dtype=np.float64).reshape(-1))
+        if s.size != self.B * (self.N - 1):
+            raise ValueError(f"sat has {s.size} entries, expected {self.B * (self.N - 1)}")
+        return s
+
+    def tracking_rollout_limited(self, Zref, limits, K=None, x0=None, model=None, guarded=False, out=None, with_events=True,
+                                 with_sat=True):
+        """tracking_rollout_model (guarded False: the handle's knot schedule) or tracking_rollout_guarded (guarded True) with
+        the applied forces clamped to `limits`, eight numbers {free_x_lo, free_x_hi, free_y_lo, free_y_hi, stand_x_lo,
+        stand_x_hi, stand_y_lo, stand_y_hi} (force_limits; +-inf: no limit): a foot takes the standing pair where it stands at
+        the knot's start and the free pair otherwise.  Returns (Zout, events, sat): events as tracking_rollout_guarded (None
+        when not guarded or without with_events), sat a (B, N-1) float64 device tensor of saturation codes sum_m s_m 4^m with
+        s_m = 1 at the lower and 2 at the upper limit (unpack_saturation; None without with_sat).  The derivatives at this
+        active set are tracking_rollout_limited_jvp / _vjp and the gains tracking_lqr_limited's, which take sat
+        (qln_evaluator.h)."""
+        T = _torch()
+        lim = force_limits(limits)
+        self._check(Zref, self.dims.z_total, "Zref")
+        out = self.new_Z() if out is None else out
+        self._check(out, self.dims.z_total, "out")
+        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        xp = self._check_opt(x0, self.B * n, "x0")
+        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
+        ev = (T.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE), dtype=T.float64, device=self._dev())
+              if guarded and with_events else None)
+        sat = T.zeros((self.B, self.N - 1), dtype=T.float64, device=self._dev()) if with_sat else None
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        _lib.check(_lib.lib().qln_tracking_rollout_limited(self._h, Zref.data_ptr(), kp, xp, mp, lim.ctypes.data, int(bool(guarded)),
+                                                           out.data_ptr(), ptr(ev), ptr(sat)))
+        return out, ev, sat
+
+    def tracking_rollout_limited_host(self, Zref, limits, K=None, x0=None, model=None, guarded=False, with_events=True,
+                                      with_sat=True):
+        """The same with host arrays (synchronous): numpy (Zout (z_total,), events (B, 8) or None, sat (B, N-1) or None)."""
+        lim = force_limits(limits)
+        Zref, K, x0 = self._host_Z(Zref, "Zref"), self._host_K(K), self._host_x0(x0)
+        model = self._host_model(model)
+        out = np.zeros(self.dims.z_total)
+        ev = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if guarded and with_events else None
+        sat = np.zeros((self.B, self.N - 1)) if with_sat else None
+        _lib.check(_lib.lib().qln_tracking_rollout_limited_host(self._h, Zref.ctypes.data, _host_ptr(K), _host_ptr(x0),
+                                                                _host_ptr(model), lim.ctypes.data, int(bool(guarded)),
+                                                                out.ctypes.data, _host_ptr(ev), _host_ptr(sat)))
+        return out, ev, sat
+
+    def tracking_rollout_limited_jvp(self, Zref, Zout, sat, events=None, K=None, model=None, Zref_dot=None, K_dot=None,
+                                     x0_dot=None, model_dot=None, out=None, with_event_dot=True):
+        """Forward sweep of tracking_rollout_limited at the (Zout, events, sat) it returned, at fixed active set and fixed
+        touchdown knot: the tangent of a force that rode a limit is zero.  events None: the knot-scheduled blocks
+        (tracking_rollout_model_jvp's), else the guarded ones.  Returns (Zout_dot, event_dot), event_dot None without events
+        or with_event_dot."""
+        T = _torch()
+        nk = self.B * (self.N - 1) * _lib.TRACK_NU * n
+        self._check(Zref, self.dims.z_total, "Zref")
+        self._check(Zout, self.dims.z_total, "Zout")
+        sp = self._sat_ptr(sat)
+        ep = None if events is None else self._events_ptr(events)
+        kp = self._check_opt(K, nk, "K")
+        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
+        zd = self._check_opt(Zref_dot, self.dims.z_total, "Zref_dot")
+        kd = self._check_opt(K_dot, nk, "K_dot")
+        xd = self._check_opt(x0_dot, self.B * n, "x0_dot")
+        md = self._check_opt(model_dot, self.B * _lib.MODEL_NP, "model_dot")
+        out = self.new_Z() if out is None else out
+        self._check(out, self.dims.z_total, "out")
+        ed = (T.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE), dtype=T.float64, device=self._dev())
+              if with_event_dot and events is not None else None)
+        _lib.check(_lib.lib().qln_tracking_rollout_limited_jvp(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), mp, ep, sp, zd, kd,
+                                                               xd, md, out.data_ptr(), None if ed is None else ed.data_ptr()))
+        return out, ed
+
+    def tracking_rollout_limited_jvp_host(self, Zref, Zout, sat, events=None, K=None, model=None, Zref_dot=None, K_dot=None,
+                                          x0_dot=None, model_dot=None, with_event_dot=True):
+        """The same with host arrays (synchronous): numpy (Zout_dot (z_total,), event_dot (B, 8) or None).  A sat entry that is
+        not a saturation code is refused."""
+        Zref, Zout, sat = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout"), self._host_sat(sat)
+        ev = None if events is None else self._host_events(events)
+        K, K_dot, x0_dot = self._host_K(K), self._host_K(K_dot), self._host_x0(x0_dot)
+        model, model_dot = self._host_model(model), self._host_model(model_dot, "model_dot")
+        if Zref_dot is not None:
+            Zref_dot = self._host_Z(Zref_dot, "Zref_dot")
+        out = np.zeros(self.dims.z_total)
+        ed = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if with_event_dot and ev is not None else None
+        _lib.check(_lib.lib().qln_tracking_rollout_limited_jvp_host(
+            self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data, _host_ptr(model), _host_ptr(ev), sat.ctypes.data,
+            _host_ptr(Zref_dot), _host_ptr(K_dot), _host_ptr(x0_dot), _host_ptr(model_dot), out.ctypes.data, _host_ptr(ed)))
+        return out, ed
+
+    def tracking_rollout_limited_vjp(self, Zref, Zout, sat, Zbar, events=None, K=None, model=None, want=None):
+        """Reverse sweep of tracking_rollout_limited at the (Zout, events, sat) it returned, the exact adjoint of
+        tracking_rollout_limited_jvp: the rows of K_bar and the force entries of Zref_bar of a channel that rode a limit are
+        exact zeros.  Returns (Zref_bar, K_bar, x0_bar, model_bar), each None unless named in want (default: all, K_bar only
+        when K is given)."""
+        T = _torch()
+        want = self._vjp_want(K, want, ("Zref", "K", "x0", "model"))
+        self._check(Zref, self.dims.z_total, "Zref")
+        self._check(Zout, self.dims.z_total, "Zout")
+        self._check(Zbar, self.dims.z_total, "Zbar")
+        sp = self._sat_ptr(sat)
+        ep = None if events is None else self._events_ptr(events)
+        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
+        zb = self.new_Z() if "Zref" in want else None
+        kb = T.zeros(tracking_k_shape(self.B, self.N), dtype=T.float64, device=self._dev()) if "K" in want else None
+        xb = T.zeros((self.B, n), dtype=T.float64, device=self._dev()) if "x0" in want else None
+        mb = T.zeros((self.B, _lib.MODEL_NP), dtype=T.float64, device=self._dev()) if "model" in want else None
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        _lib.check(_lib.lib().qln_tracking_rollout_limited_vjp(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), mp, ep, sp,
+                                                               Zbar.data_ptr(), ptr(zb), ptr(kb), ptr(xb), ptr(mb)))
+        return zb, kb, xb, mb
+
+    def tracking_rollout_limited_vjp_host(self, Zref, Zout, sat, Zbar, events=None, K=None, model=None, want=None):
+        """The same with host arrays (synchronous): numpy (Zref_bar, K_bar, x0_bar, model_bar (B, 4))."""
+        want = self._vjp_want(K, want, ("Zref", "K", "x0", "model"))
+        Zref, Zout, Zbar = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout"), self._host_Z(Zbar, "Zbar")
+        K, model, sat = self._host_K(K), self._host_model(model), self._host_sat(sat)
+        ev = None if events is None else self._host_events(events)
+        zb = np.zeros(self.dims.z_total) if "Zref" in want else None
+        kb = np.zeros(tracking_k_shape(self.B, self.N)) if "K" in want else None
+        xb = np.zeros((self.B, n)) if "x0" in want else None
+        mb = np.zeros((self.B, _lib.MODEL_NP)) if "model" in want else None
+        _lib.check(_lib.lib().qln_tracking_rollout_limited_vjp_host(
+            self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data, _host_ptr(model), _host_ptr(ev), sat.ctypes.data,
+            Zbar.ctypes.data, _host_ptr(zb), _host_ptr(kb), _host_ptr(xb), _host_ptr(mb)))
+        return zb, kb, xb, mb
+
+    def tracking_lqr_limited(self, Ztraj, sat, Q, R, Qf, events=None, model=None, K=None, P=None, with_cost_to_go=True):
+        """tracking_lqr (events None; model must then be None) or tracking_lqr_guarded (events given) at the active set of a
+        limited roll-out: the columns of B_k of the channels that rode a limit at knot k (sat) are zero, so their rows of K_k
+        are exact zeros and P is the cost-to-go of feedback on the free channels only.  Returns (K, P) as tracking_lqr."""
+        T = _torch()
+        Qh, Rh, Qfh = tracking_weights(Q, R, Qf)
+        self._check(Ztraj, self.dims.z_total, "Ztraj")
+        sp = self._sat_ptr(sat)
+        ep = None if events is None else self._events_ptr(events)
+        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
+        if K is None:
+            K = T.empty(tracking_k_shape(self.B, self.N), dtype=T.float64, device=self._dev())
+        self._check(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        if with_cost_to_go and P is None:
+            P = T.empty(tracking_p_shape(self.B, self.N), dtype=T.float64, device=self._dev())
+        if not with_cost_to_go:
+            P = None
+        pp = None if P is None else self._check(P, self.B * self.N * _lib.TRACK_P_NNZ, "P")
+        _lib.check(_lib.lib().qln_tracking_lqr_limited(self._h, Ztraj.data_ptr(), mp, ep, sp, Qh.ctypes.data, Rh.ctypes.data,
+                                                       Qfh.ctypes.data, K.data_ptr(), pp))
+        return K, P
+
+    def tracking_lqr_limited_host(self, Ztraj, sat, Q, R, Qf, events=None, model=None, with_cost_to_go=True):
+        """The same with host arrays (synchronous): returns numpy (K, P)."""
+        Ztraj, sat, model = self._host_Z(Ztraj, "Ztraj"), self._host_sat(sat), self._host_model(model)
+        ev = None if events is None else self._host_events(events)
+        Qh, Rh, Qfh = tracking_weights(Q, R, Qf)
+        K = np.zeros(tracking_k_shape(self.B, self.N))
+        P = np.zeros(tracking_p_shape(self.B, self.N)) if with_cost_to_go else None
+        _lib.check(_lib.lib().qln_tracking_lqr_limited_host(self._h, Ztraj.ctypes.data, _host_ptr(model), _host_ptr(ev),
+                                                            sat.ctypes.data, Qh.ctypes.data, Rh.ctypes.data, Qfh.ctypes.data,
+                                                            K.ctypes.data, _host_ptr(P)))
+        return K, P
+
+    def differentiable_rollout(self, Zref, K=None, x0=None, model=None, guarded=False, limits=None):
         """tracking_rollout as a torch autograd op: returns Zout, differentiable in Zref, K and x0 (each a float64 CUDA
         tensor or None).  The backward pass is one qln_tracking_rollout_vjp launch at the Zout the forward produced, a
         forward-mode tangent (torch.autograd.forward_ad, torch.func.jvp) one qln_tracking_rollout_jvp launch.
@@ -1038,9 +1236,14 @@ class HybridNLP:
         in model too, through the _model_ forms of the two sweeps.
         With guarded it is tracking_rollout_guarded and returns (Zout, events): Zout is differentiable in Zref, K, x0 and
         model (None: the handle's, no gradient) through the sweeps through the touchdown, at fixed touchdown knot; events,
-        the (B, 8) record, is not differentiable."""
-        from .rollout_grad import GuardedRolloutFunction, ModelRolloutFunction, RolloutFunction
+        the (B, 8) record, is not differentiable.
+        With limits (eight numbers, force_limits) it is tracking_rollout_limited, with or without guarded, and returns
+        (Zout, sat) or (Zout, events, sat): Zout is differentiable in the same four inputs through the sweeps at fixed
+        active set; sat, the (B, N-1) saturation record, is not differentiable."""
+        from .rollout_grad import GuardedRolloutFunction, LimitedRolloutFunction, ModelRolloutFunction, RolloutFunction
 
+        if limits is not None:
+            return LimitedRolloutFunction.apply(self, Zref, K, x0, model, force_limits(limits), bool(guarded))
         if guarded:
             return GuardedRolloutFunction.apply(self, Zref, K, x0, model)
         if model is None:

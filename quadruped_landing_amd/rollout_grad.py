@@ -119,3 +119,55 @@ class GuardedRolloutFunction(torch.autograd.Function):
                 return torch.zeros_like(Zout), None
             out, _ = ctx.nlp.tracking_rollout_guarded_jvp(Zref, Zout, events, K, model, zd, kd, xd, md, with_event_dot=False)
             return out, None  # events is not differentiable: event_dot is tracking_rollout_guarded_jvp's to ask for
+
+
+class LimitedRolloutFunction(torch.autograd.Function):
+    """(Zout, events, sat) = limited rollout(Zref, K, x0, model; limits, guarded): qln_tracking_rollout_limited, without events
+    when not guarded.  limits (eight numbers) and guarded are not tensors.  Zout is differentiable in Zref, K, x0 and model
+    through qln_tracking_rollout_limited_vjp / _jvp at the (Zout, events, sat) the forward produced, that is at fixed active
+    set and fixed touchdown knot; events and sat are marked non-differentiable."""
+
+    @staticmethod
+    def forward(nlp, Zref, K, x0, model, limits, guarded):
+        Zout, events, sat = nlp.tracking_rollout_limited(_launchable((Zref,))[0], limits, *_launchable((K, x0, model)),
+                                                         guarded=guarded)
+        return (Zout, events, sat) if guarded else (Zout, sat)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        nlp, Zref, K, x0, model, _, guarded = inputs
+        Zout, *events, sat = output
+        ctx.nlp, ctx.guarded = nlp, guarded
+        ctx.shapes = [None if t is None else t.shape for t in (K, x0, model)]
+        ctx.mark_non_differentiable(*events, sat)
+        ctx.save_for_backward(Zref, K, model, Zout, sat, *events)
+        ctx.save_for_forward(Zref, K, model, Zout, sat, *events)
+
+    @staticmethod
+    def backward(ctx, Zbar, *_):
+        need = ctx.needs_input_grad[1:5]
+        Zref, K, model, Zout, sat, *events = (_plain(t) for t in ctx.saved_tensors)
+        Zbar = _plain(Zbar)
+        want = [w for w, on in zip(("Zref", "K", "x0", "model"), need) if on and not (w == "K" and K is None)]
+        if not want:
+            return (None,) * 7
+        with torch._C._DisableFuncTorch():
+            Zref, K, model, Zout, sat, Zbar, *events = _launchable((Zref, K, model, Zout, sat, Zbar, *events))
+            zb, *bars = ctx.nlp.tracking_rollout_limited_vjp(Zref, Zout, sat, Zbar, (events or (None,))[0], K, model, want)
+            bars = [None if b is None or shape is None else b.reshape(shape) for b, shape in zip(bars, ctx.shapes)]
+        return (None, zb, *bars, None, None)
+
+    @staticmethod
+    def jvp(ctx, _, *dots):
+        Zref, K, model, Zout, sat, *events = (_plain(t) for t in ctx.saved_tensors)
+        rest = (None,) * (2 if ctx.guarded else 1)
+        with torch._C._DisableFuncTorch():
+            Zref, K, model, Zout, sat, *events = _launchable((Zref, K, model, Zout, sat, *events))
+            zd, kd, xd, md = _launchable(_plain(t) for t in dots[:4])
+            if K is None:
+                kd = None
+            if all(t is None for t in (zd, kd, xd, md)):
+                return (torch.zeros_like(Zout), *rest)
+            out, _ = ctx.nlp.tracking_rollout_limited_jvp(Zref, Zout, sat, (events or (None,))[0], K, model, zd, kd, xd, md,
+                                                          with_event_dot=False)
+            return (out, *rest)
