@@ -804,6 +804,63 @@ int qln_tracking_covariance_guarded(qln_handle* h, const double* Zout, const dou
 int qln_tracking_covariance_guarded_host(qln_handle* h, const double* Zout, const double* K, const double* model,
                                          const double* event, const double* Sigma0, int32_t sigma0_batch, const double* Wdiag,
                                          double* Sigma, double* marg, double* event_var);
+/* Kalman filter gains and the LQG covariance along a tracked landing: qln_tracking_covariance with the controller fed an
+ * ESTIMATE, F_k = F_ref,k - K_k xhat_k|k, built from ny noisy measurements per knot, y_k = H dx_k + v_k, k = 0..N-1.
+ *   A_k, B_k: exactly the blocks of qln_tracking_covariance at Zout's (x_k, u_k) -- the evaluator's closed-form block, row 14
+ *   restored at the jump knot, no h column.
+ *   P^-_0 = Sigma0,  M^-_0 = 0, and for k = 0 .. N-1
+ *     S_k   = H P^-_k H' + diag(V)                    (ny x ny, solved by L D L' without pivoting)
+ *     L_k   = P^-_k H' S_k^-1                         (15 x ny, the filter gain: xhat+ = xhat- + L_k (y_k - H xhat-))
+ *     P^+_k = (I - L_k H) P^-_k (I - L_k H)' + L_k diag(V) L_k'          (Joseph form; the error's covariance)
+ *     M_k   = M^-_k + (P^-_k - P^+_k)                 (the covariance of the estimate xhat_k|k)
+ *     X_k   = M_k + P^+_k                             (the covariance of the true state; estimate and error are orthogonal)
+ *     P^-_{k+1} = A_k P^+_k A_k' + diag(W)            (open loop: the error does not see the gains)
+ *     M^-_{k+1} = Acl_k M_k Acl_k',  Acl_k = A_k - B_k K_k
+ *   Every matrix is formed on its lower triangle and is exactly symmetric; positive semi-definiteness is not enforced.
+ * Inputs:
+ *   H:      device, [ny][15] row-major, shared by every problem and every knot; 1 <= ny <= QLN_TRACK_NY_MAX.  The kernel always
+ *           works on QLN_TRACK_NY_MAX rows: the rows behind ny are zero rows with variance 1, which changes no value, so a
+ *           call gives the bits of the same call with those rows written out.
+ *   Vdiag:  a HOST array of ny measurement variances, every entry finite and > 0.
+ *   Sigma0, sigma0_batch, Wdiag: as for qln_tracking_covariance.
+ *   K:      device, [B][N-1][4][15], or NULL: the filter alone, which returns Lgain and Pest only (Sigma and marg must be
+ *           NULL then).  Gains of qln_tracking_lqr_limited or masked ones are taken as they are: their zero rows already make
+ *           A - B K the clamped loop.
+ * Outputs (each optional, at least one non-NULL; overwritten; which of them is asked for does not change the others' bits, and
+ * the filter alone gives the bits Lgain and Pest have with K; none may overlap an input or another output):
+ *   Lgain: [B][N][15][ny], the gains L_k.
+ *   Pest:  [B][N][120] packed, P^+_k.
+ *   Sigma: [B][N][120] packed, X_k.
+ *   marg:  [B][N][QLN_TRACK_MARG_STRIDE] on X_k: [0] the clearance row's variance, [5], [6] X_k[4][4] and X_k[6][6], [7] the
+ *          trace; [1..4] the variances of the four APPLIED forces, diag(K_k M_k K_k') -- the forces feed back the estimate --
+ *          exact zeros at knot N-1.
+ * Refused with QLN_ERR_INVALID_ARGUMENT: ny outside 1..QLN_TRACK_NY_MAX, a V entry not finite or not > 0, a W entry not
+ * finite or negative, H == NULL, sigma0_batch not 1 or B, no output, Sigma or marg (or event_var) with K == NULL, overlaps.
+ * The device forms do not validate device data; the host forms also refuse a non-finite H.  Device pointers, stream-ordered;
+ * needs no cost table. */
+#define QLN_TRACK_NY_MAX 8
+int qln_tracking_kalman(qln_handle* h, const double* Zout, const double* K /* or NULL */, const double* H, int32_t ny,
+                        const double* Vdiag, const double* Sigma0, int32_t sigma0_batch, const double* Wdiag /* or NULL */,
+                        double* Lgain, double* Pest, double* Sigma, double* marg);
+int qln_tracking_kalman_host(qln_handle* h, const double* Zout, const double* K, const double* H, int32_t ny, const double* Vdiag,
+                             const double* Sigma0, int32_t sigma0_batch, const double* Wdiag, double* Lgain, double* Pest,
+                             double* Sigma, double* marg);
+/* The same THROUGH the guard-triggered touchdown, on the blocks of qln_tracking_covariance_guarded at a guarded roll-out's
+ * (Zout, event), at fixed touchdown knot k*: the knot's two applications are the composite operator's, A* for P and
+ * A* - B* K_{k*} for M.  model and event as for qln_tracking_covariance_guarded (event required).  One optional output more,
+ *   event_var: [B][2] or NULL (not written; needs K).  With t_x, t_F the coefficients of d tau and c = t_x - K_{k*}' t_F,
+ *              [0] = c' M_{k*} c + t_x' P^+_{k*} t_x, the variance of tau; [1] the same with c + e_14 and t_x + e_14, the
+ *              variance of the touchdown clock.  The zero conventions are qln_tracking_covariance_guarded's.
+ * A batch without a touchdown and with model == NULL (or the handle's model passed) gives qln_tracking_kalman's bits for a
+ * handle with k_trans = N + 1.  The device form does not validate model or event; the host form does. */
+int qln_tracking_kalman_guarded(qln_handle* h, const double* Zout, const double* K, const double* model, const double* event,
+                                const double* H, int32_t ny, const double* Vdiag, const double* Sigma0, int32_t sigma0_batch,
+                                const double* Wdiag, double* Lgain, double* Pest, double* Sigma, double* marg,
+                                double* event_var /* [B][2] or NULL */);
+int qln_tracking_kalman_guarded_host(qln_handle* h, const double* Zout, const double* K, const double* model, const double* event,
+                                     const double* H, int32_t ny, const double* Vdiag, const double* Sigma0, int32_t sigma0_batch,
+                                     const double* Wdiag, double* Lgain, double* Pest, double* Sigma, double* marg,
+                                     double* event_var);
 /* Z <- Z + N(0, sigma^2) on every entry, step lengths h then clipped to [h_min, h_max] (redraw_h = 0) or redrawn
  * U(h_min, h_max) (redraw_h != 0) -- the evaluation point of SURVEY.md 8d from qln_initial_guess's Z0.  The normal
  * draws are Box-Muller on the sampler's stream from `stream_offset`: the recipe's distribution, not numpy's numbers. */

@@ -351,6 +351,51 @@ function tracking_covariance_guarded(prob::HybridNLPHIP, Zout::Vector{Float64}, 
                     W === nothing ? C_NULL : W, Sigma, marg, event_var))
     return Sigma, marg, event_var
 end
+# The Kalman filter and the LQG covariance along Zout (include/qln_evaluator.h, DESIGN.md 4.21): tracking_covariance for a
+# controller that feeds back the estimate built from the measurements y_k = H dx_k + v_k.  H: a (ny, 15) matrix, 1 <= ny <= 8;
+# V: ny measurement variances (> 0); Sigma0, W as tracking_covariance.  Returns (L, Pest, Sigma, marg): the filter gains as
+# (ny, 15, N) (column-major: L[r, i, k] is entry (i, r) of L_k), the error covariances P^+_k and the true state's covariances
+# X_k as (120, N) packed lower triangles, marg as (8, N) with the applied-force variances diag(K M K').  K = nothing is the
+# filter alone: Sigma and marg are nothing.  tracking_kalman_guarded is the same through the guard-triggered touchdown at the
+# (Zout, events) of tracking_rollout_guarded, and also returns event_var (nothing without K).
+function tracking_kalman(prob::HybridNLPHIP, Zout::Vector{Float64}, H::Matrix{Float64}, V::Vector{Float64},
+                         Sigma0::Matrix{Float64}; K=nothing, W=nothing)
+    N = prob.N
+    ny = size(H, 1)
+    (1 <= ny <= 8 && size(H, 2) == 15 && length(V) == ny) || error("H: (ny, 15) with 1 <= ny <= 8, V: ny variances")
+    Hrow = Matrix{Float64}(transpose(H))  # row-major [ny][15]
+    packed = Float64[Sigma0[i, j] for i in 1:15 for j in 1:i]
+    L = zeros(ny, 15, N)
+    Pest = zeros(120, N)
+    Sigma = K === nothing ? nothing : zeros(120, N)
+    marg = K === nothing ? nothing : zeros(8, N)
+    qln_check(ccall((:qln_tracking_kalman_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zout, K === nothing ? C_NULL : K, Hrow, Int32(ny), V, packed, Int32(1),
+                    W === nothing ? C_NULL : W, L, Pest, Sigma === nothing ? C_NULL : Sigma, marg === nothing ? C_NULL : marg))
+    return L, Pest, Sigma, marg
+end
+function tracking_kalman_guarded(prob::HybridNLPHIP, Zout::Vector{Float64}, events::Vector{Float64}, H::Matrix{Float64},
+                                 V::Vector{Float64}, Sigma0::Matrix{Float64}; K=nothing, W=nothing, model=nothing)
+    N = prob.N
+    ny = size(H, 1)
+    (1 <= ny <= 8 && size(H, 2) == 15 && length(V) == ny) || error("H: (ny, 15) with 1 <= ny <= 8, V: ny variances")
+    Hrow = Matrix{Float64}(transpose(H))
+    packed = Float64[Sigma0[i, j] for i in 1:15 for j in 1:i]
+    L = zeros(ny, 15, N)
+    Pest = zeros(120, N)
+    Sigma = K === nothing ? nothing : zeros(120, N)
+    marg = K === nothing ? nothing : zeros(8, N)
+    event_var = K === nothing ? nothing : zeros(2)
+    qln_check(ccall((:qln_tracking_kalman_guarded_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble},
+                     Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zout, K === nothing ? C_NULL : K, model === nothing ? C_NULL : model, events, Hrow, Int32(ny), V,
+                    packed, Int32(1), W === nothing ? C_NULL : W, L, Pest, Sigma === nothing ? C_NULL : Sigma,
+                    marg === nothing ? C_NULL : marg, event_var === nothing ? C_NULL : event_var))
+    return L, Pest, Sigma, marg, event_var
+end
 # Contact-aware force limits (include/qln_evaluator.h, DESIGN.md 4.20).  limits holds 8 values, {lo, hi} of F_x and of F_y for a
 # free foot, then for a standing one (+-Inf: no limit).  tracking_rollout_limited is tracking_rollout_model (guarded = false) or
 # tracking_rollout_guarded (guarded = true) with the applied forces clamped, and returns (Zout, events, sat): events is nothing

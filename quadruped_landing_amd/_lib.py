@@ -26,6 +26,7 @@ GN_INFO_STRIDE = 8
 HESS_STEP_NNZ, HESS_TERM_NNZ = 55, 15
 TRACK_NU, TRACK_P_NNZ = 4, 120
 TRACK_MARG_STRIDE = 8
+TRACK_NY_MAX = 8  # measurement rows of qln_tracking_kalman
 MODEL_NP = 4  # g, mb, mf, lb: a per-problem plant model of the tracking roll-out
 
 
@@ -182,6 +183,10 @@ SIGNATURES = {
     "qln_tracking_lqr_limited_host": (C.c_int, [_vp] + [_dp] * 9),
     "qln_tracking_covariance_guarded": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp, _dp]),
     "qln_tracking_covariance_guarded_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp, _dp]),
+    "qln_tracking_kalman": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, C.c_int32] + [_dp] * 5),
+    "qln_tracking_kalman_host": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, C.c_int32] + [_dp] * 5),
+    "qln_tracking_kalman_guarded": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, C.c_int32] + [_dp] * 6),
+    "qln_tracking_kalman_guarded_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, C.c_int32] + [_dp] * 6),
     "qln_eval_constraint_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_eval_constraint_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_gauss_newton_step": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, C.c_double, _dp, _dp, _dp]),

@@ -72,6 +72,7 @@ int64_t tracking_k_total(const qln_dims& D) { return (int64_t)D.B * (D.N - 1) * 
 int64_t tracking_p_total(const qln_dims& D) { return (int64_t)D.B * D.N * QLN_TRACK_P_NNZ; }
 int64_t tracking_marg_total(const qln_dims& D) { return (int64_t)D.B * D.N * QLN_TRACK_MARG_STRIDE; }
 int64_t tracking_sat_total(const qln_dims& D) { return (int64_t)D.B * (D.N - 1); }
+int64_t tracking_gain_total(const qln_dims& D, int ny) { return (int64_t)D.B * D.N * QLN_NX * ny; }
 
 // The buffers of the host forms (qln_*_host), one per role.  A role's size follows from the role and the handle's layout
 // (host_role_size): no form can allocate a buffer that another finds too small.  An in-out argument is copied in whole,
@@ -105,6 +106,9 @@ enum HostRole {
     kEventD, // out: the guarded jvp's event_dot                            [B][8]
     kEventVar,  // out: the guarded covariance sweep's event_var            [B][2]
     kSat,    // out: the limited roll-out's saturation codes; in: the same for its sweeps and gains  [B][N-1]
+    kH,      // in: the Kalman filter's measurement matrix (ny rows used)   [8][15]
+    kLgain,  // out: the filter gains ([B][N][15][ny] used)                 [B][N][15][8]
+    kPest,   // out: the error covariances P^+                              layout of P
     kHostRoles
 };
 
@@ -174,7 +178,7 @@ int64_t host_role_size(const qln_handle* h, HostRole r) {
         case kF: case kSigma: return D.B;
         case kHvals: return (int64_t)(D.B - 1) * h->h_stride + hessian_nnz(D.N);  // no padding behind the last problem
         case kK: case kKbar: case kKdot: return tracking_k_total(D);
-        case kP: case kCov: return tracking_p_total(D);
+        case kP: case kCov: case kPest: return tracking_p_total(D);
         case kCov0: return (int64_t)D.B * QLN_TRACK_P_NNZ;
         case kMarg: return tracking_marg_total(D);
         case kX0: return (int64_t)D.B * QLN_NX;
@@ -183,6 +187,8 @@ int64_t host_role_size(const qln_handle* h, HostRole r) {
         case kEvent: case kEventD: return (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
         case kEventVar: return (int64_t)D.B * 2;
         case kSat: return tracking_sat_total(D);
+        case kH: return (int64_t)QLN_TRACK_NY_MAX * QLN_NX;
+        case kLgain: return tracking_gain_total(D, QLN_TRACK_NY_MAX);
         case kHostRoles: break;
     }
     return 0;
@@ -1643,6 +1649,106 @@ int qln_tracking_covariance_guarded_host(qln_handle* h, const double* Zout, cons
                                          double* Sigma, double* marg, double* event_var) {
     return tracking_covariance_host(h, Zout, K, model, true, event, Sigma0, sigma0_batch, Wdiag, Sigma, marg, event_var,
                                     "qln_tracking_covariance_guarded_host");
+}
+
+// the Kalman filter and the LQG covariance (k_tracking_kalman).  The checks that need no handle come first.
+// guarded: through the guard-triggered touchdown, which needs the roll-out's event records and may return event_var
+static int check_tracking_kalman_args(const qln_handle* h, const double* Zout, const double* K, const double* model, bool guarded,
+                                      const double* event, const double* H, int32_t ny, const double* Vdiag, const double* Sigma0,
+                                      int32_t sigma0_batch, const double* Wdiag, const double* Lgain, const double* Pest,
+                                      const double* Sigma, const double* marg, const double* event_var, const char* who) {
+    const std::string w(who);
+    if (ny < 1 || ny > QLN_TRACK_NY_MAX)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
+    if (!Lgain && !Pest && !Sigma && !marg && !event_var)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every output is NULL (nothing to compute)");
+    if (!K && (Sigma || marg || event_var))
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Sigma, marg and event_var need K (K == NULL is the filter alone: Lgain and Pest)");
+    if (guarded && !event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
+    if (!H || !Vdiag) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null H or Vdiag");
+    for (int i = 0; i < ny; ++i)
+        if (!(std::isfinite(Vdiag[i]) && Vdiag[i] > 0.0))
+            return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Vdiag must be finite and > 0 (entry " + std::to_string(i) + ")");
+    if (Wdiag)
+        for (int i = 0; i < QLN_NX; ++i)
+            if (!(std::isfinite(Wdiag[i]) && Wdiag[i] >= 0.0))
+                return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Wdiag must be finite and >= 0 (entry " + std::to_string(i) + ")");
+    if (sigma0_batch < 1) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
+    if (int rc = check_handle(h)) return rc;
+    const qln_dims& D = h->dims;
+    if (sigma0_batch != 1 && sigma0_batch != D.B) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
+    if (!Zout || !Sigma0) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zout or Sigma0");
+    return check_no_overlap({{Lgain, tracking_gain_total(D, ny)}, {Pest, tracking_p_total(D)}, {Sigma, tracking_p_total(D)},
+                             {marg, tracking_marg_total(D)}, {event_var, (int64_t)D.B * 2}},
+                            {{Zout, D.z_total}, {K, tracking_k_total(D)}, {H, (int64_t)ny * QLN_NX},
+                             {Sigma0, (int64_t)sigma0_batch * QLN_TRACK_P_NNZ}, {model, (int64_t)D.B * QLN_MODEL_NP},
+                             {event, (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE}}, w);
+}
+
+static int tracking_kalman(qln_handle* h, const double* Zout, const double* K, const double* model, bool guarded,
+                           const double* event, const double* H, int32_t ny, const double* Vdiag, const double* Sigma0,
+                           int32_t sigma0_batch, const double* Wdiag, double* Lgain, double* Pest, double* Sigma, double* marg,
+                           double* event_var, const char* who) {
+    if (int rc = check_tracking_kalman_args(h, Zout, K, model, guarded, event, H, ny, Vdiag, Sigma0, sigma0_batch, Wdiag, Lgain,
+                                            Pest, Sigma, marg, event_var, who))
+        return rc;
+    if (int rc = bind_device(h)) return rc;
+    QLN_HIP(qln::launch_tracking_kalman(h->p, Zout, K, model, event, H, ny, Vdiag, Sigma0, sigma0_batch, Wdiag, Lgain, Pest, Sigma,
+                                        marg, event_var, h->stream));
+    return QLN_OK;
+}
+
+static int tracking_kalman_host(qln_handle* h, const double* Zout, const double* K, const double* model, bool guarded,
+                                const double* event, const double* H, int32_t ny, const double* Vdiag, const double* Sigma0,
+                                int32_t sigma0_batch, const double* Wdiag, double* Lgain, double* Pest, double* Sigma, double* marg,
+                                double* event_var, const char* who) {
+    if (int rc = check_tracking_kalman_args(h, Zout, K, model, guarded, event, H, ny, Vdiag, Sigma0, sigma0_batch, Wdiag, Lgain,
+                                            Pest, Sigma, marg, event_var, who))
+        return rc;
+    for (int i = 0; i < ny * QLN_NX; ++i)
+        if (!std::isfinite(H[i]))
+            return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": H is not finite (entry " + std::to_string(i) + ")");
+    if (int rc = check_host_models(h, model, who)) return rc;
+    if (int rc = check_host_events(h, event, who)) return rc;
+    if (int rc = bind_device(h)) return rc;
+    HostArg s0 = copy_in(kCov0, Sigma0), hm = copy_in(kH, H), lg = copy_out(kLgain, Lgain);
+    s0.n = (int64_t)sigma0_batch * QLN_TRACK_P_NNZ;  // the tiles the call reads, of the role's B
+    hm.n = (int64_t)ny * QLN_NX;                     // the rows the call reads, and the gains it writes, of the role's eight
+    lg.n = tracking_gain_total(h->dims, ny);
+    return host_call(h,
+                     {copy_in(kV, Zout), copy_in(kK, K), copy_in(kModel, model), copy_in(kEvent, event), hm, s0, lg,
+                      copy_out(kPest, Pest), copy_out(kCov, Sigma), copy_out(kMarg, marg), copy_out(kEventVar, event_var)},
+                     [&](double* const* d, bool) {
+                         return qln::launch_tracking_kalman(h->p, d[kV], d[kK], d[kModel], d[kEvent], d[kH], ny, Vdiag, d[kCov0],
+                                                            sigma0_batch, Wdiag, d[kLgain], d[kPest], d[kCov], d[kMarg],
+                                                            d[kEventVar], h->stream);
+                     });
+}
+
+int qln_tracking_kalman(qln_handle* h, const double* Zout, const double* K, const double* H, int32_t ny, const double* Vdiag,
+                        const double* Sigma0, int32_t sigma0_batch, const double* Wdiag, double* Lgain, double* Pest,
+                        double* Sigma, double* marg) {
+    return tracking_kalman(h, Zout, K, nullptr, false, nullptr, H, ny, Vdiag, Sigma0, sigma0_batch, Wdiag, Lgain, Pest, Sigma, marg,
+                           nullptr, "qln_tracking_kalman");
+}
+int qln_tracking_kalman_host(qln_handle* h, const double* Zout, const double* K, const double* H, int32_t ny, const double* Vdiag,
+                             const double* Sigma0, int32_t sigma0_batch, const double* Wdiag, double* Lgain, double* Pest,
+                             double* Sigma, double* marg) {
+    return tracking_kalman_host(h, Zout, K, nullptr, false, nullptr, H, ny, Vdiag, Sigma0, sigma0_batch, Wdiag, Lgain, Pest, Sigma,
+                                marg, nullptr, "qln_tracking_kalman_host");
+}
+int qln_tracking_kalman_guarded(qln_handle* h, const double* Zout, const double* K, const double* model, const double* event,
+                                const double* H, int32_t ny, const double* Vdiag, const double* Sigma0, int32_t sigma0_batch,
+                                const double* Wdiag, double* Lgain, double* Pest, double* Sigma, double* marg, double* event_var) {
+    return tracking_kalman(h, Zout, K, model, true, event, H, ny, Vdiag, Sigma0, sigma0_batch, Wdiag, Lgain, Pest, Sigma, marg,
+                           event_var, "qln_tracking_kalman_guarded");
+}
+int qln_tracking_kalman_guarded_host(qln_handle* h, const double* Zout, const double* K, const double* model, const double* event,
+                                     const double* H, int32_t ny, const double* Vdiag, const double* Sigma0, int32_t sigma0_batch,
+                                     const double* Wdiag, double* Lgain, double* Pest, double* Sigma, double* marg,
+                                     double* event_var) {
+    return tracking_kalman_host(h, Zout, K, model, true, event, H, ny, Vdiag, Sigma0, sigma0_batch, Wdiag, Lgain, Pest, Sigma, marg,
+                                event_var, "qln_tracking_kalman_guarded_host");
 }
 
 // ------------------------------------------------------------------ host-pointer (MOI) mode

@@ -326,6 +326,13 @@ hipError_t launch_tracking_rollout_jvp(const BatchParams& p, const double* Zref,
 hipError_t launch_tracking_covariance(const BatchParams& p, const double* Zout, const double* K, const double* model,
                                       const double* event, const double* Sigma0, int sigma0_batch, const double* Wd,
                                       double* Sigma, double* marg, double* event_var, hipStream_t stream);
+// The Kalman filter and the LQG covariance along Zout (qln_tracking_kalman / _guarded): H [ny][15] on the device, Vd (ny) and Wd
+// (15 or null) host arrays; Lgain [B][N][15][ny], Pest, Sigma [B][N][120], marg [B][N][8], event_var [B][2], each may be null;
+// K null: the filter alone (Lgain and Pest only).  model and event as for launch_tracking_covariance.
+hipError_t launch_tracking_kalman(const BatchParams& p, const double* Zout, const double* K, const double* model,
+                                  const double* event, const double* H, int ny, const double* Vd, const double* Sigma0,
+                                  int sigma0_batch, const double* Wd, double* Lgain, double* Pest, double* Sigma, double* marg,
+                                  double* event_var, hipStream_t stream);
 // batched Gauss-Newton step on the constraint violation, CGLS per problem in LDS (qln_solver_kernels.hip)
 size_t gauss_newton_lds_bytes(int32_t N);
 hipError_t launch_gauss_newton_step(const BatchParams& p, const double* Z, const double* c, double* dZ, int max_iters,

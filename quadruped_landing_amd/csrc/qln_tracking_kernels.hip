@@ -72,6 +72,12 @@
 // its _jvp / _vjp, qln_tracking_lqr_limited): the flag kLimit.  The roll-out clamps the applied forces by the
 // foot's contact state and records the channels that rode a limit; the sweeps and the Riccati sweep read that record and treat
 // those channels as constants (no tangent, no cotangent, a zero column of B_k).
+//
+// k_tracking_kalman: the Kalman filter along Zout and the covariance of the loop that feeds back its estimate
+// (qln_tracking_kalman / _guarded), in k_tracking_covariance's mapping and on its blocks, operator and
+// applications (cov_apply, cov_apply_touchdown): per knot a measurement update of the error covariance P -- H P by chains on
+// broadcast LDS reads, S = H P H' + V by row sums, an 8 x 8 L D L' in every lane, the Joseph form through the image -- and two
+// predictions, P's open loop and the estimate covariance M's closed loop, each in an image of its own.
 #include "qln_row16.h"
 
 #include <utility>
@@ -1276,6 +1282,421 @@ __global__ __launch_bounds__(kWave) void k_tracking_covariance(BatchParams P, Co
 }
 
 
+// ---- k_tracking_kalman ----
+// per-row LDS image (doubles): the P image [15][17] | the M image [15][17] | K [4][16] | the knot's 20 entries of Zout | the
+// clearance derivatives of sixteen knots | the H tile [8][16], V in its column 15 | the L tile [15][8]
+constexpr int kKStr = 17, kKP = 0, kKM = 256, kKK = 512, kKZ = kKK + 4 * 16, kKD = kKZ + 20, kKH = kKD + 16,
+              kKL = kKH + QLN_TRACK_NY_MAX * 16, kKRow = kKL + 15 * QLN_TRACK_NY_MAX;
+static_assert(15 * kKStr <= kKM - kKP && 15 * kKStr <= kKK - kKM && kKZ % 2 == 0 && kKD % 2 == 0 && kKH % 2 == 0 && kKL % 2 == 0 &&
+                  kKRow % 2 == 0,
+              "the images fit; 16-byte aligned sections");
+
+// the process variances and the measurement variances; the rows behind ny carry V = 1
+struct KalmanNoise {
+    double w[15], v[QLN_TRACK_NY_MAX];
+};
+
+// The Kalman filter and the LQG covariance along Zout (include/qln_evaluator.h): per knot the measurement update
+// of the error covariance P (gain L_k, Joseph form), the estimate's covariance M_k = M^-_k + (P^-_k - P^+_k), and the two
+// predictions P^-_{k+1} = A P^+ A' + diag(W) (cov_apply<false>) and M^-_{k+1} = Acl M Acl' (cov_apply<true>), on the blocks, the
+// modes and the touchdown operator of k_tracking_covariance and in its mapping: one problem per row of sixteen lanes, lane j
+// owns column j.  P and M each live in a padded image of their own, and the two recursions run one after the other within the
+// knot through the images, so that neither holds the other's column in registers.  The update:
+//   1. lane j forms G[:, j] = H P^-[:, j] (eight chains on broadcast reads of the H tile, one row in flight at a time);
+//   2. S = G H' + diag(V): 36 row sums, the same bits in every lane, factored L D L' (no pivoting) by every lane alike;
+//   3. lane j solves S x = G[:, j]: x is row j of the gain L = P^- H' S^-1, which goes to the L tile;
+//   4. column j of (I - L H) P^- -> row j of the image; lane j reads row j of that back and forms column j of
+//      P^+ = (I - L H) [.]' + L diag(V) L' as v - L (H v - V .* x), stored as row j of the image.  From there on only the lower
+//      triangle is read, as in k_tracking_covariance.
+// The kernel is compiled for eight measurement rows: the rows r >= ny of the H tile are zero rows and carry V = 1.  That
+// changes no value -- S is block diagonal with an identity behind ny, those columns of L are exact zeros, and x + 0.0 * y == x
+// for the finite y here -- and the call with ny rows gives the bits of the call with the zero rows written out.
+// X_k = M_k + P^+_k is never stored in LDS: the packed tile and the marginals add the two images' entries where they leave.
+// Without K (kHasK false) the call is the filter alone: no M image, Lgain and Pest only, and their bits are the same.
+template <bool kHasK, bool kModel, bool kGuard>
+__global__ __launch_bounds__(kWave) void k_tracking_kalman(BatchParams P, KalmanNoise Nz, const double* __restrict__ Zout,
+                                                           const double* __restrict__ Kg, const double* __restrict__ Hg, int ny,
+                                                           const double* __restrict__ Sigma0, int sigma0_batch,
+                                                           double* __restrict__ Lg, double* __restrict__ Pe,
+                                                           double* __restrict__ Sig, double* __restrict__ mg,
+                                                           const double* __restrict__ model, const double* __restrict__ event,
+                                                           double* __restrict__ ev_var) {
+    static_assert(kModel || !kGuard, "the guarded sweep runs on the kModel path");
+    constexpr int NY = QLN_TRACK_NY_MAX;
+    __shared__ double lds[kRows * kKRow];
+    const Row16 r16 = row16_of(P);  // lane 15 shadows column 14 and writes nothing to the images
+    const int ln = r16.ln, j = r16.j, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
+    const bool own = r16.own, valid = r16.valid;
+    const Model Mp = plant_model<kModel>(P, model, bc);
+    const Model& M = kGuard ? Mp : r16.M;
+    [[maybe_unused]] int ks = -1;
+    [[maybe_unused]] double tau = 0.0, var_tau = 0.0, var_clock = 0.0;
+    if constexpr (kGuard) {
+        ks = guard_knot(event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc], N);
+        tau = event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + 1];
+    }
+    double* L = lds + r16.row * kKRow;
+    const double* __restrict__ Zb = Zout + (int64_t)bc * P.z_stride;
+    const double* __restrict__ Kb = kHasK ? Kg + (int64_t)bc * (N - 1) * (QLN_TRACK_NU * QLN_NX) : nullptr;
+    double* __restrict__ Lb = Lg ? Lg + (int64_t)bc * N * (QLN_NX * ny) : nullptr;
+    double* __restrict__ Pb = Pe ? Pe + (int64_t)bc * N * QLN_TRACK_P_NNZ : nullptr;
+    double* __restrict__ Sb = (kHasK && Sig) ? Sig + (int64_t)bc * N * QLN_TRACK_P_NNZ : nullptr;
+    double* __restrict__ Mb = (kHasK && mg) ? mg + (int64_t)bc * N * QLN_TRACK_MARG_STRIDE : nullptr;
+
+    // where the packed entries ln + 16 t lie in an image's lower triangle (relative to the image), the K entries in the K tile
+    // and the entries of a knot's [15][ny] gain in the L tile (rows of eight)
+    int po[8], ko[4], lo[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const int i = min(ln + 16 * t, QLN_TRACK_P_NNZ - 1);
+        int r = 0;
+#pragma unroll
+        for (int q = 1; q < 15; ++q) r += (i >= q * (q + 1) / 2) ? 1 : 0;
+        po[t] = kKStr * r + (i - r * (r + 1) / 2);
+        const int g = min(ln + 16 * t, QLN_NX * ny - 1), gr = g / ny;
+        lo[t] = kKL + NY * gr + (g - ny * gr);
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int i = min(ln + 16 * t, QLN_TRACK_NU * QLN_NX - 1);
+        const int m = i / 15;
+        ko[t] = kKK + 16 * m + (i - 15 * m);
+    }
+    const int rowj = kKStr * j, colj = j;
+    auto sym = [&](int c) { return (c <= j) ? rowj + c : colj + kKStr * c; };  // relative to the image
+    double wj = 0.0;
+#pragma unroll
+    for (int i = 0; i < 15; ++i) wj = (i == j) ? Nz.w[i] : wj;
+
+    // P^-_0 = Sigma0: the packed tile into the image's lower triangle; M^-_0 = 0; the H tile, zero rows behind ny
+    {
+        const double* __restrict__ S0 = Sigma0 + (int64_t)(sigma0_batch == 1 ? 0 : bc) * QLN_TRACK_P_NNZ;
+#pragma unroll
+        for (int t = 0; t < 8; ++t)
+            if (ln + 16 * t < QLN_TRACK_P_NNZ) L[kKP + po[t]] = S0[ln + 16 * t];
+        if constexpr (kHasK) {
+#pragma unroll
+            for (int t = 0; t < 16; ++t) L[kKM + ln + 16 * t] = 0.0;
+        }
+#pragma unroll
+        for (int r = 0; r < NY; ++r) L[kKH + 16 * r + ln] = own ? ((r < ny) ? Hg[15 * r + ln] : 0.0) : Nz.v[r];  // column 15: V
+    }
+    wave_lds_sync();
+
+    auto clearance_derivatives = [&](int k0) {
+        L[kKD + ln] = clearance_dtheta(Zb[20 * min(k0 + ln, N - 1) + 2], M.lb);
+    };
+    // the entry at offset o of X_k = M_k + P^+_k (the filter alone: of P^+_k)
+    auto xat = [&](int o) {
+        if constexpr (kHasK) return L[kKM + o] + L[kKP + o];
+        else return L[kKP + o];
+    };
+    // the knot's outputs leave from the L tile and the images' lower triangles; fv: the knot's force variances
+    auto emit = [&](int k, const double (&fv)[4]) {
+        // the stores' predicates are formed here from an opaque copy of ln: hoisted out of the knot loop, the sixteen lane
+        // masks of the tiles' tails stayed in scalar registers through every knot and pushed other scalars out
+        int le = ln;
+        asm volatile("" : "+v"(le));
+        if (Lb && valid) {
+            double* __restrict__ o = Lb + (int64_t)k * (QLN_NX * ny);
+#pragma unroll
+            for (int t = 0; t < 8; ++t)
+                if (le + 16 * t < QLN_NX * ny) o[ln + 16 * t] = L[lo[t]];
+        }
+        if (Pb && valid) {
+            double* __restrict__ o = Pb + (int64_t)k * QLN_TRACK_P_NNZ;
+#pragma unroll
+            for (int t = 0; t < 8; ++t)
+                if (le + 16 * t < QLN_TRACK_P_NNZ) o[ln + 16 * t] = L[kKP + po[t]];
+        }
+        if constexpr (kHasK) {
+            if (Sb && valid) {
+                double* __restrict__ o = Sb + (int64_t)k * QLN_TRACK_P_NNZ;
+#pragma unroll
+                for (int t = 0; t < 8; ++t)
+                    if (le + 16 * t < QLN_TRACK_P_NNZ) o[ln + 16 * t] = xat(po[t]);
+            }
+            if (Mb) {
+                const double dth = L[kKD + (k & 15)];
+                const double s11 = xat(kKStr * 1 + 1), s21 = xat(kKStr * 2 + 1), s22 = xat(kKStr * 2 + 2);
+                double mv[QLN_TRACK_MARG_STRIDE];
+                mv[0] = fma(dth, fma(dth, s22, 2.0 * s21), s11);  // a' X a, a = e_yb + dth e_theta
+#pragma unroll
+                for (int m = 0; m < 4; ++m) mv[1 + m] = fv[m];
+                mv[5] = xat((kKStr + 1) * 4);
+                mv[6] = xat((kKStr + 1) * 6);
+                const double dj = xat((kKStr + 1) * j);
+                mv[7] = row_sum16(own ? dj : 0.0);
+                double v = mv[0];
+#pragma unroll
+                for (int q = 1; q < QLN_TRACK_MARG_STRIDE; ++q) v = (le == q) ? mv[q] : v;
+                if (valid && le < QLN_TRACK_MARG_STRIDE) Mb[(int64_t)k * QLN_TRACK_MARG_STRIDE + ln] = v;
+            }
+        }
+    };
+
+    // Zout's knot and the knot's K entries: requested one knot ahead, as in k_tracking_covariance
+    double zn[2] = {0.0, 0.0}, kn[4];
+    if (N > 1) knot_load(Zb, ln, zn[0], zn[1]);
+    if constexpr (kHasK) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) kn[t] = Kb[min(ln + 16 * t, QLN_TRACK_NU * QLN_NX - 1)];
+    }
+
+    for (int k = 0; k < N; ++k) {
+        const bool last = k == N - 1;  // the last knot has an update and no step
+        if (Mb && (k & 15) == 0) clearance_derivatives(k);
+        if (!last) {
+            L[kKZ + ln] = zn[0];
+            if (ln < 4) L[kKZ + 16 + ln] = zn[1];
+            if constexpr (kHasK) {
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                    if (ln + 16 * t < QLN_TRACK_NU * QLN_NX) L[ko[t]] = kn[t];
+            }
+            if (k + 1 < N - 1) {
+                knot_load(Zb + 20 * (k + 1), ln, zn[0], zn[1]);
+                if constexpr (kHasK) {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t)
+                        kn[t] = Kb[(int64_t)(k + 1) * (QLN_TRACK_NU * QLN_NX) + min(ln + 16 * t, QLN_TRACK_NU * QLN_NX - 1)];
+                }
+            }
+        }
+        wave_lds_sync();  // the knot and the K tile are in place
+
+        // ---- the measurement update: L_k, P^+_k and M_k ----
+        double p[15], x[NY];
+#pragma unroll
+        for (int c = 0; c < 15; ++c) p[c] = L[kKP + sym(c)];
+        {
+            double G[NY];
+#pragma unroll
+            for (int r = 0; r < NY; ++r) {
+                double acc = L[kKH + 16 * r] * p[0];
+#pragma unroll
+                for (int c = 1; c < 15; ++c) acc = fma(L[kKH + 16 * r + c], p[c], acc);
+                asm volatile("" : "+v"(acc) : : "memory");  // one row of H in flight at a time, as K in cov_apply
+                G[r] = acc;
+            }
+            double S[NY][NY], dd[NY], dinv[NY];  // the lower triangle; below the diagonal it becomes the unit factor
+            double hj[NY];                         // column j of H
+#pragma unroll
+            for (int r = 0; r < NY; ++r) hj[r] = L[kKH + 16 * r + j];
+#pragma unroll
+            for (int a = 0; a < NY; ++a) {
+#pragma unroll
+                for (int b = 0; b <= a; ++b) S[a][b] = row_sum16(own ? G[a] * hj[b] : 0.0);
+                S[a][a] += L[kKH + 16 * a + 15];
+            }
+#pragma unroll
+            for (int c = 0; c < NY; ++c) {
+                double w[NY], d = S[c][c];  // w: row c of the factor times D
+#pragma unroll
+                for (int q = 0; q < c; ++q) {
+                    w[q] = S[c][q] * dd[q];
+                    d = fma(-S[c][q], w[q], d);
+                }
+                dd[c] = d;
+                dinv[c] = 1.0 / d;
+#pragma unroll
+                for (int i = c + 1; i < NY; ++i) {
+                    double t = S[i][c];
+#pragma unroll
+                    for (int q = 0; q < c; ++q) t = fma(-S[i][q], w[q], t);
+                    S[i][c] = t * dinv[c];
+                }
+            }
+            // S x = G[:, j]: forward, the diagonal, backward
+#pragma unroll
+            for (int i = 0; i < NY; ++i) {
+                double t = G[i];
+#pragma unroll
+                for (int q = 0; q < i; ++q) t = fma(-S[i][q], x[q], t);
+                x[i] = t;
+            }
+#pragma unroll
+            for (int i = 0; i < NY; ++i) x[i] *= dinv[i];
+#pragma unroll
+            for (int i = NY - 2; i >= 0; --i) {
+#pragma unroll
+                for (int q = i + 1; q < NY; ++q) x[i] = fma(-S[q][i], x[q], x[i]);
+            }
+            if (own) {
+#pragma unroll
+                for (int r = 0; r < NY; ++r) L[kKL + NY * j + r] = x[r];
+            }
+            wave_lds_sync();  // the L tile is in place, and every lane holds its column of P^-
+            // column j of (I - L H) P^- -> row j of the image
+            double u[15];
+#pragma unroll
+            for (int i = 0; i < 15; ++i) {
+                double acc = p[i];
+#pragma unroll
+                for (int r = 0; r < NY; ++r) acc = fma(-L[kKL + NY * i + r], G[r], acc);
+                asm volatile("" : "+v"(acc) : : "memory");  // one row of L in flight at a time
+                u[i] = acc;
+            }
+            if (own) {
+#pragma unroll
+                for (int i = 0; i < 15; ++i) L[kKP + kKStr * j + i] = u[i];
+            }
+        }
+        wave_lds_sync();
+        {
+            double vt[15], t[NY];
+#pragma unroll
+            for (int c = 0; c < 15; ++c) vt[c] = L[kKP + kKStr * c + j];
+#pragma unroll
+            for (int r = 0; r < NY; ++r) {
+                double acc = L[kKH + 16 * r] * vt[0];
+#pragma unroll
+                for (int c = 1; c < 15; ++c) acc = fma(L[kKH + 16 * r + c], vt[c], acc);
+                asm volatile("" : "+v"(acc) : : "memory");
+                t[r] = fma(-L[kKH + 16 * r + 15], x[r], acc);  // H v - V .* (row j of L): the Joseph form's two terms share L
+            }
+            double out[15];
+#pragma unroll
+            for (int i = 0; i < 15; ++i) {
+                double acc = vt[i];
+#pragma unroll
+                for (int r = 0; r < NY; ++r) acc = fma(-L[kKL + NY * i + r], t[r], acc);
+                asm volatile("" : "+v"(acc) : : "memory");
+                out[i] = acc;
+            }
+            wave_lds_sync();  // every lane holds its row: P^+ may overwrite the image
+            if (own) {
+#pragma unroll
+                for (int i = 0; i < 15; ++i) L[kKP + kKStr * j + i] = out[i];
+            }
+        }
+        wave_lds_sync();
+        // only the lower triangle of P^+_k is read from here on; M_k = M^-_k + (P^-_k - P^+_k), entry by entry
+        if constexpr (kHasK) {
+            double m[15];
+#pragma unroll
+            for (int c = 0; c < 15; ++c) m[c] = L[kKM + sym(c)] + (p[c] - L[kKP + sym(c)]);
+            wave_lds_sync();  // M^- has been read
+            if (own) {
+#pragma unroll
+                for (int i = 0; i < 15; ++i) L[kKM + kKStr * j + i] = m[i];
+            }
+            wave_lds_sync();
+        }
+        const double fv0[4] = {0.0, 0.0, 0.0, 0.0};
+        if (last) {
+            emit(k, fv0);
+            break;
+        }
+
+        KnotMode md;
+        if constexpr (kGuard) md = guard_mode(k, ks, im);
+        else md = knot_mode(k + 1, kt - 1, im);
+        // The two predictions of the knot, M's first (its K m gives the force variances, so the knot's outputs leave in between).
+        // apply(hasK, v, out, g): out = (A - B K) v or A v on the knot's operator.  The knot's body exists once per operator --
+        // the step block's and the touchdown knot's -- so that neither form's values stay live across the other's applications;
+        // the hand-offs through LDS stay inside a row, whose sixteen lanes take the same form.
+        auto predict = [&](auto apply) {
+            double out[15], g[4];
+            if constexpr (kHasK) {
+                double fv[4] = {0.0, 0.0, 0.0, 0.0}, m[15];  // M_k's column, read back: nothing of the update stays live
+#pragma unroll
+                for (int c = 0; c < 15; ++c) m[c] = L[kKM + sym(c)];
+                apply(std::true_type{}, m, out, g);
+                if (Mb) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) fv[q] = row_sum16(own ? L[kKK + 16 * q + j] * g[q] : 0.0);
+                }
+                emit(k, fv);
+                wave_lds_sync();  // the M image has been read
+                if (own) {
+#pragma unroll
+                    for (int i = 0; i < 15; ++i) L[kKM + kKStr * j + i] = out[i];
+                }
+                wave_lds_sync();
+                double vt[15];
+#pragma unroll
+                for (int c = 0; c < 15; ++c) vt[c] = L[kKM + kKStr * c + j];
+                apply(std::true_type{}, vt, out, g);
+                wave_lds_sync();
+                if (own) {
+#pragma unroll
+                    for (int i = 0; i < 15; ++i) L[kKM + kKStr * j + i] = out[i];
+                }
+            } else {
+                emit(k, fv0);
+            }
+            // P^-_{k+1} = A P^+_k A' + diag(W): k_tracking_covariance's open-loop knot
+            double s[15];
+#pragma unroll
+            for (int c = 0; c < 15; ++c) s[c] = L[kKP + sym(c)];
+            apply(std::false_type{}, s, out, g);
+            wave_lds_sync();  // the image has been read
+            if (own) {
+#pragma unroll
+                for (int i = 0; i < 15; ++i) L[kKP + kKStr * j + i] = out[i];
+            }
+            wave_lds_sync();
+#pragma unroll
+            for (int c = 0; c < 15; ++c) s[c] = L[kKP + kKStr * c + j];
+            apply(std::false_type{}, s, out, g);
+            wave_lds_sync();
+            if (own) {
+#pragma unroll
+                for (int i = 0; i < 15; ++i) L[kKP + kKStr * j + i] = out[i];
+                L[kKP + (kKStr + 1) * j] = L[kKP + (kKStr + 1) * j] + wj;
+            }
+        };
+        if (kGuard && k == ks) {  // the touchdown knot: the composite operator in the block's place
+            double xk[15];
+#pragma unroll
+            for (int i = 0; i < 14; ++i) xk[i] = L[kKZ + i];
+            xk[14] = 0.0;  // the clock feeds nothing
+            const double u5[5] = {L[kKZ + 15], L[kKZ + 16], L[kKZ + 17], L[kKZ + 18], L[kKZ + 19]};
+            const TouchdownBlock tb = touchdown_block(M, md, tau, xk, u5);
+            // the variances of tau and of the touchdown clock: c' M c + t_x' P^+ t_x with c = t_x - K' t_F, then with e_14 added
+            // to both; lane j takes column j of M against c and of P^+ against t_x, and the row sums are the quadratic forms
+            if constexpr (kHasK) {
+                if (ev_var) {
+                    const int iy = md.f2free ? 6 : 4, iv = md.f2free ? 13 : 11;
+                    const double* Kf = L + kKK + 16 * (md.f2free ? 3 : 1);
+                    double sc = 0.0, cj = 0.0, sp = 0.0, tj = 0.0, p14 = 0.0, m14 = 0.0;
+                    int je = j;  // an opaque copy, as emit's: the fifteen masks i == j are formed here, not ahead of the loop
+                    asm volatile("" : "+v"(je));
+#pragma unroll
+                    for (int i = 0; i < 15; ++i) {
+                        const double ti = (i == 4 || i == 6) ? ((i == iy) ? tb.ty : 0.0) : (i == 11 || i == 13) ? ((i == iv) ? tb.tv : 0.0) : 0.0;
+                        const double ci = fma(-Kf[i], tb.tF, ti);
+                        const double pi = L[kKP + sym(i)], mi = L[kKM + sym(i)];
+                        sc = fma(mi, ci, sc);
+                        sp = fma(pi, ti, sp);
+                        cj = (i == je) ? ci : cj;
+                        tj = (i == je) ? ti : tj;
+                        p14 = pi;
+                        m14 = mi;
+                    }
+                    const double e14 = (je == 14) ? 1.0 : 0.0;
+                    var_tau = row_sum16(own ? cj * sc : 0.0) + row_sum16(own ? tj * sp : 0.0);
+                    var_clock = row_sum16(own ? (cj + e14) * (sc + m14) : 0.0) + row_sum16(own ? (tj + e14) * (sp + p14) : 0.0);
+                }
+            }
+            predict([&](auto hasK, const double (&v)[15], double (&out)[15], double (&g)[4]) {
+                cov_apply_touchdown<decltype(hasK)::value>(tb, M, L + kKK, v, out, g);
+            });
+        } else {
+            const StepBlock blk = step_block(L + kKZ, md, M);
+            predict([&](auto hasK, const double (&v)[15], double (&out)[15], double (&g)[4]) {
+                cov_apply<decltype(hasK)::value>(blk, L + kKK, v, out, g);
+            });
+        }
+        wave_lds_sync();  // both images hold the priors of knot k + 1; the K tile and the knot may be rewritten
+    }
+    if constexpr (kGuard) {
+        if (kHasK && ev_var && valid && ln < 2) ev_var[(int64_t)2 * bc + ln] = (ln == 0) ? var_tau : var_clock;
+    }
+}
+
+
 // ---- k_tracking_rollout_jvp ----
 // One knot's inputs, as lane ln of a row loads them.  z0 / zd0: entry ln of the knot's twenty in Zout / Zref_dot (lane
 // j < 15: x_j, lane 15: F1x); z1 / zd1: entry 16 + (ln & 3) (F1y, F2x, F2y, h in lanes 0-3).  xr: x_ref,j; kc, kd: column j
@@ -1633,6 +2054,28 @@ hipError_t launch_tracking_covariance(const BatchParams& p, const double* Zout, 
         K ? go(k_tracking_covariance<true, true, true>) : go(k_tracking_covariance<false, true, true>);
     else
         K ? go(k_tracking_covariance<true, false, false>) : go(k_tracking_covariance<false, false, false>);
+    return hipGetLastError();
+}
+
+// The four instantiations of k_tracking_kalman: K or the filter alone, event or the knot schedule (as launch_tracking_covariance).
+hipError_t launch_tracking_kalman(const BatchParams& p, const double* Zout, const double* K, const double* model,
+                                  const double* event, const double* H, int ny, const double* Vd, const double* Sigma0,
+                                  int sigma0_batch, const double* Wd, double* Lgain, double* Pest, double* Sigma, double* marg,
+                                  double* event_var, hipStream_t stream) {
+    if (event_var && !event) return hipErrorInvalidValue;
+    if (!K && (Sigma || marg || event_var)) return hipErrorInvalidValue;
+    if (ny < 1 || ny > QLN_TRACK_NY_MAX || !H || !Vd) return hipErrorInvalidValue;
+    KalmanNoise nz;
+    for (int i = 0; i < 15; ++i) nz.w[i] = Wd ? Wd[i] : 0.0;
+    for (int r = 0; r < QLN_TRACK_NY_MAX; ++r) nz.v[r] = r < ny ? Vd[r] : 1.0;
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, nz, Zout, K, H, ny, Sigma0, sigma0_batch, Lgain,
+                           Pest, Sigma, marg, model, event, event_var);
+    };
+    if (event)
+        K ? go(k_tracking_kalman<true, true, true>) : go(k_tracking_kalman<false, true, true>);
+    else
+        K ? go(k_tracking_kalman<true, false, false>) : go(k_tracking_kalman<false, false, false>);
     return hipGetLastError();
 }
 

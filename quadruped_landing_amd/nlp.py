@@ -156,6 +156,30 @@ def tracking_noise(W):
     return np.ascontiguousarray(np.broadcast_to(np.asarray(W, dtype=np.float64), (n,)))
 
 
+def measurement_model(H, V):
+    """The measurement model y = H dx + v of qln_tracking_kalman as contiguous float64 arrays (H (ny, 15), V (ny,)): H a
+    matrix of 1 to 8 rows of 15 (a 15-vector is one row), V the ny measurement variances (a scalar broadcasts).  A
+    non-finite H, or a V entry that is not finite and > 0, is refused."""
+    H = np.asarray(H, dtype=np.float64)
+    if H.ndim == 1:
+        H = H[None]
+    if H.ndim != 2 or H.shape[1] != n or not 1 <= H.shape[0] <= _lib.TRACK_NY_MAX:
+        raise ValueError(f"H of shape {H.shape}: expected (ny, 15) with 1 <= ny <= {_lib.TRACK_NY_MAX}")
+    if np.ndim(V) > 1 or (np.ndim(V) == 1 and np.shape(V)[0] != H.shape[0]):
+        raise ValueError(f"V of shape {np.shape(V)}: expected a scalar or ({H.shape[0]},)")
+    V = np.ascontiguousarray(np.broadcast_to(np.asarray(V, dtype=np.float64), (H.shape[0],)))
+    if not np.isfinite(H).all():
+        raise ValueError("H is not finite")
+    if not (np.isfinite(V) & (V > 0)).all():
+        raise ValueError("V: every measurement variance must be finite and > 0")
+    return np.ascontiguousarray(H), V
+
+
+def tracking_l_shape(B: int, N: int, ny: int):
+    """Shape of the filter gains of qln_tracking_kalman: (B, N, 15, ny), row-major."""
+    return (B, N, n, ny)
+
+
 def force_limits(limits):
     """The eight force limits {free_x_lo, free_x_hi, free_y_lo, free_y_hi, stand_x_lo, stand_x_hi, stand_y_lo, stand_y_hi} as
     the contiguous float64 array the limited calls pass; +-inf means no limit on that side.  A NaN, or lo > hi, is refused."""
@@ -1058,6 +1082,115 @@ class HybridNLP:
                                                                    ev.ctypes.data, s0.ctypes.data, nb, _host_ptr(Wh),
                                                                    _host_ptr(S), _host_ptr(mg), _host_ptr(var)))
         return S, mg, var
+
+    # -- the Kalman filter and the LQG covariance: the controller feeds back an estimate -------------
+    def _device_sigma0(self, Sigma0):
+        """Sigma0 in any form of tracking_sigma0, or a CUDA tensor of 1 or B packed tiles -> (device tensor, sigma0_batch)."""
+        T = _torch()
+        if Sigma0 is None:
+            raise ValueError("Sigma0 is required")
+        if isinstance(Sigma0, T.Tensor) and Sigma0.is_cuda:
+            nb = Sigma0.numel() // _lib.TRACK_P_NNZ
+            if Sigma0.numel() != nb * _lib.TRACK_P_NNZ or nb not in (1, self.B):
+                raise ValueError("a device Sigma0 must hold 1 or B packed tiles of 120")
+            s0 = Sigma0
+        else:
+            host, nb = tracking_sigma0(Sigma0, self.B)
+            s0 = T.from_numpy(host).to(self._dev())
+        self._check(s0, nb * _lib.TRACK_P_NNZ, "Sigma0")
+        return s0, nb
+
+    def _kalman(self, guarded, Zout, events, K, H, V, Sigma0, W, model, with_gains, with_pest, with_sigma, with_marginals,
+                with_event_var):
+        T = _torch()
+        Hh, Vh = measurement_model(H, V)
+        ny = Hh.shape[0]
+        self._check(Zout, self.dims.z_total, "Zout")
+        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        s0, nb = self._device_sigma0(Sigma0)
+        Wh = tracking_noise(W)
+        Hd = T.from_numpy(Hh).to(self._dev())
+        new = lambda want, shape: T.empty(shape, dtype=T.float64, device=self._dev()) if want else None  # noqa: E731
+        Lg = new(with_gains, tracking_l_shape(self.B, self.N, ny))
+        Pe = new(with_pest, tracking_p_shape(self.B, self.N))
+        S = new(with_sigma, tracking_p_shape(self.B, self.N))
+        mg = new(with_marginals, (self.B, self.N, _lib.TRACK_MARG_STRIDE))
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        if not guarded:
+            _lib.check(_lib.lib().qln_tracking_kalman(self._h, Zout.data_ptr(), kp, Hd.data_ptr(), ny, Vh.ctypes.data,
+                                                      s0.data_ptr(), nb, _host_ptr(Wh), ptr(Lg), ptr(Pe), ptr(S), ptr(mg)))
+            return Lg, Pe, S, mg
+        ep = self._events_ptr(events)
+        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
+        ev = T.zeros((self.B, 2), dtype=T.float64, device=self._dev()) if with_event_var else None
+        _lib.check(_lib.lib().qln_tracking_kalman_guarded(self._h, Zout.data_ptr(), kp, mp, ep, Hd.data_ptr(), ny, Vh.ctypes.data,
+                                                          s0.data_ptr(), nb, _host_ptr(Wh), ptr(Lg), ptr(Pe), ptr(S), ptr(mg),
+                                                          ptr(ev)))
+        return Lg, Pe, S, mg, ev
+
+    def _kalman_host(self, guarded, Zout, events, K, H, V, Sigma0, W, model, with_gains, with_pest, with_sigma, with_marginals,
+                     with_event_var):
+        if Sigma0 is None:
+            raise ValueError("Sigma0 is required")
+        Hh, Vh = measurement_model(H, V)
+        ny = Hh.shape[0]
+        Zout, K = self._host_Z(Zout, "Zout"), self._host_K(K)
+        s0, nb = tracking_sigma0(Sigma0, self.B)
+        Wh = tracking_noise(W)
+        Lg = np.zeros(tracking_l_shape(self.B, self.N, ny)) if with_gains else None
+        Pe = np.zeros(tracking_p_shape(self.B, self.N)) if with_pest else None
+        S = np.zeros(tracking_p_shape(self.B, self.N)) if with_sigma else None
+        mg = np.zeros((self.B, self.N, _lib.TRACK_MARG_STRIDE)) if with_marginals else None
+        if not guarded:
+            _lib.check(_lib.lib().qln_tracking_kalman_host(self._h, Zout.ctypes.data, _host_ptr(K), Hh.ctypes.data, ny,
+                                                           Vh.ctypes.data, s0.ctypes.data, nb, _host_ptr(Wh), _host_ptr(Lg),
+                                                           _host_ptr(Pe), _host_ptr(S), _host_ptr(mg)))
+            return Lg, Pe, S, mg
+        ev, model = self._host_events(events), self._host_model(model)
+        var = np.zeros((self.B, 2)) if with_event_var else None
+        _lib.check(_lib.lib().qln_tracking_kalman_guarded_host(self._h, Zout.ctypes.data, _host_ptr(K), _host_ptr(model),
+                                                               ev.ctypes.data, Hh.ctypes.data, ny, Vh.ctypes.data, s0.ctypes.data,
+                                                               nb, _host_ptr(Wh), _host_ptr(Lg), _host_ptr(Pe), _host_ptr(S),
+                                                               _host_ptr(mg), _host_ptr(var)))
+        return Lg, Pe, S, mg, var
+
+    def tracking_kalman(self, Zout, H, V, K=None, Sigma0=None, W=None, with_gains=True, with_pest=True, with_sigma=None,
+                        with_marginals=None):
+        """The Kalman filter and the LQG covariance along Zout: tracking_covariance for a controller that feeds back the
+        estimate xhat_k|k built from the measurements y_k = H dx_k + v_k, var v = V (measurement_model), at every knot
+        (qln_evaluator.h).  Returns (L, Pest, Sigma, marg): the filter gains (B, N, 15, ny), the error covariances P^+_k and the
+        true state's covariances X_k = M_k + P^+_k as packed (B, N, 120) tiles (unpack_covariance), and marg (B, N, 8) as
+        tracking_covariance's on X_k, with the applied-force variances diag(K M K'); each None unless asked for.  K None is the
+        filter alone: L and Pest only (with_sigma / with_marginals default to K being given).  Stream-ordered."""
+        ws = (K is not None) if with_sigma is None else with_sigma
+        wm = (K is not None) if with_marginals is None else with_marginals
+        return self._kalman(False, Zout, None, K, H, V, Sigma0, W, None, with_gains, with_pest, ws, wm, False)
+
+    def tracking_kalman_host(self, Zout, H, V, K=None, Sigma0=None, W=None, with_gains=True, with_pest=True, with_sigma=None,
+                             with_marginals=None):
+        """The same with host arrays (synchronous): numpy (L, Pest, Sigma, marg)."""
+        ws = (K is not None) if with_sigma is None else with_sigma
+        wm = (K is not None) if with_marginals is None else with_marginals
+        return self._kalman_host(False, Zout, None, K, H, V, Sigma0, W, None, with_gains, with_pest, ws, wm, False)
+
+    def tracking_kalman_guarded(self, Zout, events, H, V, K=None, Sigma0=None, W=None, model=None, with_gains=True,
+                                with_pest=True, with_sigma=None, with_marginals=None, with_event_var=None):
+        """tracking_kalman through the guarded touchdown, at the (Zout, events) tracking_rollout_guarded returned, at fixed
+        touchdown knot.  Returns (L, Pest, Sigma, marg, event_var): the first four as tracking_kalman, event_var a (B, 2)
+        device tensor with the variance of tau and of the touchdown clock under estimate feedback (zeros for a problem that
+        does not land); each None unless asked for."""
+        ws = (K is not None) if with_sigma is None else with_sigma
+        wm = (K is not None) if with_marginals is None else with_marginals
+        we = (K is not None) if with_event_var is None else with_event_var
+        return self._kalman(True, Zout, events, K, H, V, Sigma0, W, model, with_gains, with_pest, ws, wm, we)
+
+    def tracking_kalman_guarded_host(self, Zout, events, H, V, K=None, Sigma0=None, W=None, model=None, with_gains=True,
+                                     with_pest=True, with_sigma=None, with_marginals=None, with_event_var=None):
+        """The same with host arrays (synchronous): numpy (L, Pest, Sigma, marg, event_var)."""
+        ws = (K is not None) if with_sigma is None else with_sigma
+        wm = (K is not None) if with_marginals is None else with_marginals
+        we = (K is not None) if with_event_var is None else with_event_var
+        return self._kalman_host(True, Zout, events, K, H, V, Sigma0, W, model, with_gains, with_pest, ws, wm, we)
 
     # -- contact-aware force limits: the roll-out, its sweeps and the gains at fixed active set ------
     def _sat_ptr(self, sat):
