@@ -861,6 +861,66 @@ int qln_tracking_kalman_guarded_host(qln_handle* h, const double* Zout, const do
                                      const double* H, int32_t ny, const double* Vdiag, const double* Sigma0, int32_t sigma0_batch,
                                      const double* Wdiag, double* Lgain, double* Pest, double* Sigma, double* marg,
                                      double* event_var);
+/* The ESTIMATE-FEEDBACK roll-out: the nonlinear hybrid plant and the estimator rolled out together in one launch, the loop
+ * qln_tracking_kalman designs and predicts.  The roll-outs above feed back the true state; this one feeds back xhat_k|k, built
+ * from ny noisy measurements per knot with the filter gains L_k.  The library draws nothing: the measurement and process noise
+ * are samples the caller supplies, so the call is deterministic.  Knots are 0-based.
+ * Zref, K, x0, model, Zout and event mean what they mean for qln_tracking_rollout_model / _guarded.  x_0 = x0[b] (NULL: the
+ * handle's x0), xhat^-_0 = xhat0[b] (NULL: x_ref,0 -- the estimate starts on the nominal, the design's M^-_0 = 0), and for
+ * k = 0 .. N-1
+ *     y_k      = H (x_k - x_ref,k) + v_k                     v_k = vnoise[b][k]  (NULL: zeros)
+ *     innov_k  = y_k - H (xhat^-_k - x_ref,k)
+ *     xhat_k   = xhat^-_k + L_k innov_k                      L_k = Lgain[b][k], [15][ny]
+ *     if k == N-1: stop
+ *     F_k      = F_ref,k - K_k (xhat_k - x_ref,k),  h_k = h_ref,k          (K == NULL: F_k = F_ref,k)
+ *     x_{k+1}  = Phi_k(x_k, u_k; model[b]) + w_k             w_k = wnoise[b][k]  (NULL: none)
+ *     xhat^-_{k+1} = Phi_k(xhat_k, u_k; the handle's model)
+ *   Every product is formed as qln_tracking_rollout forms K dx: the first product, then fused multiply-adds in index order;
+ *   L_k innov_k is accumulated onto xhat^-_k column by column.
+ * Knot-scheduled form (qln_tracking_rollout_estimated): Phi_k is the step of qln_tracking_rollout_model, for the plant and for
+ *   the estimator alike.
+ * Guarded form (qln_tracking_rollout_estimated_guarded): Phi_k is the guarded step of qln_tracking_rollout_guarded, taken twice.
+ *   The plant and the estimator each carry their own contact mode, their own guard decision and tau and their own touchdown
+ *   record: the estimator lands when its ESTIMATED foot reaches the ground, and the handle's k_trans is not read.  This is the
+ *   loop the saltation term of qln_tracking_kalman_guarded describes; a contact switch shared with the plant would be a
+ *   different filter.
+ * Noise: w_k is added as given, after the whole (composite) step, clock row included.
+ * Estimator model: always the handle's -- the design model does not follow the plant, as for qln_tracking_lqr.
+ * Inputs (device pointers):
+ *   Lgain:  [B][N][15][ny], the layout qln_tracking_kalman writes.  Required.
+ *   H:      [ny][15] row-major, shared by every problem and knot; 1 <= ny <= QLN_TRACK_NY_MAX.  Required.  A call with ny rows
+ *           gives, in Zout and Xhat, the bits of the call with QLN_TRACK_NY_MAX rows whose further H rows and L columns are zero.
+ *   vnoise: [B][N][ny] or NULL.   wnoise: [B][N-1][15] or NULL.   xhat0: [B][15] or NULL.
+ * Outputs (overwritten; which optional ones are asked for does not change the others' bits; none may overlap an input or
+ * another output):
+ *   Zout:      required; the TRUE states and the applied controls in the layout of Z; entries past n_nlp are never written.
+ *   Xhat:      [B][N][15] or NULL; xhat_k|k.
+ *   innov:     [B][N][ny] or NULL.
+ *   event:     guarded only, [B][QLN_TOUCHDOWN_INFO_STRIDE] or NULL: the plant's record.
+ *   event_hat: guarded only, the same shape or NULL: the estimator's record, its entry 6 taken over the same applied forces by the
+ *              estimator's own standing feet.
+ * Reductions: with Lgain = 0, xhat0 == NULL and Zref a qln_tracking_rollout_model / _guarded roll-out (K == NULL) under the
+ * handle's model, the estimate stays on Zref and Zout is bit for bit qln_tracking_rollout_model(Zref, NULL, x0, model),
+ * respectively _guarded and its event record, whatever K is.
+ * Refused with QLN_ERR_INVALID_ARGUMENT: a NULL h, Zref, Zout, Lgain or H; ny outside 1..QLN_TRACK_NY_MAX; an overlap.  The
+ * device forms do not validate device data; the host forms also refuse a non-finite H, and a model as
+ * qln_tracking_rollout_guarded_host does.  Force limits in this loop and sweeps through it do not exist.
+ * Device pointers, stream-ordered; needs no cost table. */
+int qln_tracking_rollout_estimated(qln_handle* h, const double* Zref, const double* K /* or NULL */, const double* Lgain,
+                                   const double* H, int32_t ny, const double* vnoise, const double* wnoise, const double* x0,
+                                   const double* xhat0, const double* model, double* Zout, double* Xhat, double* innov);
+int qln_tracking_rollout_estimated_guarded(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
+                                           int32_t ny, const double* vnoise, const double* wnoise, const double* x0,
+                                           const double* xhat0, const double* model, double* Zout, double* Xhat, double* innov,
+                                           double* event, double* event_hat);
+/* the same as host forms (see "Host forms" above; Zout is in-out) */
+int qln_tracking_rollout_estimated_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
+                                        int32_t ny, const double* vnoise, const double* wnoise, const double* x0,
+                                        const double* xhat0, const double* model, double* Zout, double* Xhat, double* innov);
+int qln_tracking_rollout_estimated_guarded_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                                const double* H, int32_t ny, const double* vnoise, const double* wnoise,
+                                                const double* x0, const double* xhat0, const double* model, double* Zout,
+                                                double* Xhat, double* innov, double* event, double* event_hat);
 /* Z <- Z + N(0, sigma^2) on every entry, step lengths h then clipped to [h_min, h_max] (redraw_h = 0) or redrawn
  * U(h_min, h_max) (redraw_h != 0) -- the evaluation point of SURVEY.md 8d from qln_initial_guess's Z0.  The normal
  * draws are Box-Muller on the sampler's stream from `stream_offset`: the recipe's distribution, not numpy's numbers. */

@@ -396,6 +396,49 @@ function tracking_kalman_guarded(prob::HybridNLPHIP, Zout::Vector{Float64}, even
                     marg === nothing ? C_NULL : marg, event_var === nothing ? C_NULL : event_var))
     return L, Pest, Sigma, marg, event_var
 end
+# The estimate-feedback roll-out (include/qln_evaluator.h, DESIGN.md 4.22): the plant and the estimator flown together, the
+# forces fed back from the estimate xhat_k|k that the filter gains L of tracking_kalman build from y_k = H dx_k + v_k.  L: (ny, 15,
+# N) as tracking_kalman returns it; H: (ny, 15); vnoise: (ny, N) and wnoise: (15, N-1) samples drawn by the caller, nothing for
+# none; x0, xhat0: 15 values or nothing (the problem's x0, the reference's first knot).  Returns (Zout, Xhat, innov): the true
+# states and applied controls, the estimates as (15, N) and the innovations as (ny, N).  tracking_rollout_estimated_guarded lets
+# the plant and the estimator each land by their own guard and also returns (events, events_hat), their touchdown records.
+function tracking_rollout_estimated(prob::HybridNLPHIP, Zref::Vector{Float64}, L::Array{Float64,3}, H::Matrix{Float64};
+                                    K=nothing, vnoise=nothing, wnoise=nothing, x0=nothing, xhat0=nothing, model=nothing)
+    N = prob.N
+    ny = size(H, 1)
+    (1 <= ny <= 8 && size(H, 2) == 15 && size(L) == (ny, 15, N)) || error("H: (ny, 15) with 1 <= ny <= 8, L: (ny, 15, N)")
+    Hrow = Matrix{Float64}(transpose(H))  # row-major [ny][15]
+    Zout = zeros(length(Zref))
+    Xhat = zeros(15, N)
+    innov = zeros(ny, N)
+    qln_check(ccall((:qln_tracking_rollout_estimated_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, K === nothing ? C_NULL : K, L, Hrow, Int32(ny), vnoise === nothing ? C_NULL : vnoise,
+                    wnoise === nothing ? C_NULL : wnoise, x0 === nothing ? C_NULL : x0, xhat0 === nothing ? C_NULL : xhat0,
+                    model === nothing ? C_NULL : model, Zout, Xhat, innov))
+    return Zout, Xhat, innov
+end
+function tracking_rollout_estimated_guarded(prob::HybridNLPHIP, Zref::Vector{Float64}, L::Array{Float64,3}, H::Matrix{Float64};
+                                            K=nothing, vnoise=nothing, wnoise=nothing, x0=nothing, xhat0=nothing, model=nothing)
+    N = prob.N
+    ny = size(H, 1)
+    (1 <= ny <= 8 && size(H, 2) == 15 && size(L) == (ny, 15, N)) || error("H: (ny, 15) with 1 <= ny <= 8, L: (ny, 15, N)")
+    Hrow = Matrix{Float64}(transpose(H))
+    Zout = zeros(length(Zref))
+    Xhat = zeros(15, N)
+    innov = zeros(ny, N)
+    events = zeros(8)
+    events_hat = zeros(8)
+    qln_check(ccall((:qln_tracking_rollout_estimated_guarded_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}),
+                    prob.handle, Zref, K === nothing ? C_NULL : K, L, Hrow, Int32(ny), vnoise === nothing ? C_NULL : vnoise,
+                    wnoise === nothing ? C_NULL : wnoise, x0 === nothing ? C_NULL : x0, xhat0 === nothing ? C_NULL : xhat0,
+                    model === nothing ? C_NULL : model, Zout, Xhat, innov, events, events_hat))
+    return Zout, Xhat, innov, events, events_hat
+end
 # Contact-aware force limits (include/qln_evaluator.h, DESIGN.md 4.20).  limits holds 8 values, {lo, hi} of F_x and of F_y for a
 # free foot, then for a standing one (+-Inf: no limit).  tracking_rollout_limited is tracking_rollout_model (guarded = false) or
 # tracking_rollout_guarded (guarded = true) with the applied forces clamped, and returns (Zout, events, sat): events is nothing

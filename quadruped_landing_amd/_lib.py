@@ -187,6 +187,10 @@ SIGNATURES = {
     "qln_tracking_kalman_host": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, C.c_int32] + [_dp] * 5),
     "qln_tracking_kalman_guarded": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, C.c_int32] + [_dp] * 6),
     "qln_tracking_kalman_guarded_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, C.c_int32] + [_dp] * 6),
+    "qln_tracking_rollout_estimated": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 8),
+    "qln_tracking_rollout_estimated_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 8),
+    "qln_tracking_rollout_estimated_guarded": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 10),
+    "qln_tracking_rollout_estimated_guarded_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 10),
     "qln_eval_constraint_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_eval_constraint_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_gauss_newton_step": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, C.c_double, _dp, _dp, _dp]),

@@ -73,6 +73,7 @@ int64_t tracking_p_total(const qln_dims& D) { return (int64_t)D.B * D.N * QLN_TR
 int64_t tracking_marg_total(const qln_dims& D) { return (int64_t)D.B * D.N * QLN_TRACK_MARG_STRIDE; }
 int64_t tracking_sat_total(const qln_dims& D) { return (int64_t)D.B * (D.N - 1); }
 int64_t tracking_gain_total(const qln_dims& D, int ny) { return (int64_t)D.B * D.N * QLN_NX * ny; }
+int64_t tracking_meas_total(const qln_dims& D, int ny) { return (int64_t)D.B * D.N * ny; }
 
 // The buffers of the host forms (qln_*_host), one per role.  A role's size follows from the role and the handle's layout
 // (host_role_size): no form can allocate a buffer that another finds too small.  An in-out argument is copied in whole,
@@ -109,6 +110,12 @@ enum HostRole {
     kH,      // in: the Kalman filter's measurement matrix (ny rows used)   [8][15]
     kLgain,  // out: the filter gains ([B][N][15][ny] used)                 [B][N][15][8]
     kPest,   // out: the error covariances P^+                              layout of P
+    kXhat0,  // in: the estimated roll-out's xhat0                          [B][15]
+    kVnoise, // in: its measurement noise ([B][N][ny] used)                 [B][N][8]
+    kWnoise, // in: its process noise                                       [B][N-1][15]
+    kXhat,   // out: its estimates xhat_k|k                                 [B][N][15]
+    kInnov,  // out: its innovations ([B][N][ny] used)                      [B][N][8]
+    kEventHat,  // out: the estimator's touchdown records                   [B][8]
     kHostRoles
 };
 
@@ -181,14 +188,17 @@ int64_t host_role_size(const qln_handle* h, HostRole r) {
         case kP: case kCov: case kPest: return tracking_p_total(D);
         case kCov0: return (int64_t)D.B * QLN_TRACK_P_NNZ;
         case kMarg: return tracking_marg_total(D);
-        case kX0: return (int64_t)D.B * QLN_NX;
+        case kX0: case kXhat0: return (int64_t)D.B * QLN_NX;
         case kMultInfo: return (int64_t)D.B * QLN_MULT_INFO_STRIDE;
         case kModel: case kModelD: return (int64_t)D.B * QLN_MODEL_NP;
-        case kEvent: case kEventD: return (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
+        case kEvent: case kEventD: case kEventHat: return (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
         case kEventVar: return (int64_t)D.B * 2;
         case kSat: return tracking_sat_total(D);
         case kH: return (int64_t)QLN_TRACK_NY_MAX * QLN_NX;
         case kLgain: return tracking_gain_total(D, QLN_TRACK_NY_MAX);
+        case kVnoise: case kInnov: return tracking_meas_total(D, QLN_TRACK_NY_MAX);
+        case kWnoise: return (int64_t)D.B * (D.N - 1) * QLN_NX;
+        case kXhat: return (int64_t)D.B * D.N * QLN_NX;
         case kHostRoles: break;
     }
     return 0;
@@ -1749,6 +1759,96 @@ int qln_tracking_kalman_guarded_host(qln_handle* h, const double* Zout, const do
                                      double* event_var) {
     return tracking_kalman_host(h, Zout, K, model, true, event, H, ny, Vdiag, Sigma0, sigma0_batch, Wdiag, Lgain, Pest, Sigma, marg,
                                 event_var, "qln_tracking_kalman_guarded_host");
+}
+
+// the estimate-feedback roll-out (k_tracking_rollout_estimated).  The checks that need no handle come first.
+// guarded: both the plant and the estimator land by their own guards, each with an event record (may be null)
+static int check_tracking_estimated_args(const qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                         const double* H, int32_t ny, const double* vnoise, const double* wnoise,
+                                         const double* x0, const double* xhat0, const double* model, const double* Zout,
+                                         const double* Xhat, const double* innov, const double* event, const double* event_hat,
+                                         const char* who) {
+    const std::string w(who);
+    if (ny < 1 || ny > QLN_TRACK_NY_MAX)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
+    if (!Lgain || !H) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Lgain or H");
+    if (int rc = check_handle(h)) return rc;
+    if (!Zref || !Zout) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref or Zout");
+    const qln_dims& D = h->dims;
+    const int64_t nx = (int64_t)D.B * QLN_NX, ne = (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
+    return check_no_overlap({{Zout, D.z_total}, {Xhat, (int64_t)D.B * D.N * QLN_NX}, {innov, tracking_meas_total(D, ny)},
+                             {event, ne}, {event_hat, ne}},
+                            {{Zref, D.z_total}, {K, tracking_k_total(D)}, {Lgain, tracking_gain_total(D, ny)},
+                             {H, (int64_t)ny * QLN_NX}, {vnoise, tracking_meas_total(D, ny)},
+                             {wnoise, (int64_t)D.B * (D.N - 1) * QLN_NX}, {x0, nx}, {xhat0, nx},
+                             {model, (int64_t)D.B * QLN_MODEL_NP}}, w);
+}
+
+static int tracking_rollout_estimated(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
+                                      int32_t ny, const double* vnoise, const double* wnoise, const double* x0,
+                                      const double* xhat0, const double* model, double* Zout, double* Xhat, double* innov,
+                                      bool guarded, double* event, double* event_hat, const char* who) {
+    if (int rc = check_tracking_estimated_args(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, event,
+                                               event_hat, who))
+        return rc;
+    if (int rc = bind_device(h)) return rc;
+    QLN_HIP(qln::launch_tracking_rollout_estimated(h->p, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov,
+                                                   guarded, event, event_hat, h->stream));
+    return QLN_OK;
+}
+
+static int tracking_rollout_estimated_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                           const double* H, int32_t ny, const double* vnoise, const double* wnoise,
+                                           const double* x0, const double* xhat0, const double* model, double* Zout, double* Xhat,
+                                           double* innov, bool guarded, double* event, double* event_hat, const char* who) {
+    if (int rc = check_tracking_estimated_args(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, event,
+                                               event_hat, who))
+        return rc;
+    for (int i = 0; i < ny * QLN_NX; ++i)
+        if (!std::isfinite(H[i]))
+            return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": H is not finite (entry " + std::to_string(i) + ")");
+    if (int rc = check_host_models(h, model, who)) return rc;
+    if (int rc = bind_device(h)) return rc;
+    HostArg hm = copy_in(kH, H), lg = copy_in(kLgain, Lgain), vn = copy_in(kVnoise, vnoise), in = copy_out(kInnov, innov);
+    hm.n = (int64_t)ny * QLN_NX;  // the rows, gains, samples and innovations of the call's ny, of the roles' eight
+    lg.n = tracking_gain_total(h->dims, ny);
+    vn.n = in.n = tracking_meas_total(h->dims, ny);
+    return host_call(h,
+                     {copy_in(kZ, Zref), copy_inout(kZio, Zout), copy_in(kK, K), lg, hm, vn, copy_in(kWnoise, wnoise),
+                      copy_in(kX0, x0), copy_in(kXhat0, xhat0), copy_in(kModel, model), copy_out(kXhat, Xhat), in,
+                      copy_out(kEvent, event), copy_out(kEventHat, event_hat)},
+                     [&](double* const* d, bool) {
+                         return qln::launch_tracking_rollout_estimated(h->p, d[kZ], d[kK], d[kLgain], d[kH], ny, d[kVnoise],
+                                                                       d[kWnoise], d[kX0], d[kXhat0], d[kModel], d[kZio], d[kXhat],
+                                                                       d[kInnov], guarded, d[kEvent], d[kEventHat], h->stream);
+                     });
+}
+
+int qln_tracking_rollout_estimated(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
+                                   int32_t ny, const double* vnoise, const double* wnoise, const double* x0, const double* xhat0,
+                                   const double* model, double* Zout, double* Xhat, double* innov) {
+    return tracking_rollout_estimated(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, false, nullptr,
+                                      nullptr, "qln_tracking_rollout_estimated");
+}
+int qln_tracking_rollout_estimated_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
+                                        int32_t ny, const double* vnoise, const double* wnoise, const double* x0,
+                                        const double* xhat0, const double* model, double* Zout, double* Xhat, double* innov) {
+    return tracking_rollout_estimated_host(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, false,
+                                           nullptr, nullptr, "qln_tracking_rollout_estimated_host");
+}
+int qln_tracking_rollout_estimated_guarded(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
+                                           int32_t ny, const double* vnoise, const double* wnoise, const double* x0,
+                                           const double* xhat0, const double* model, double* Zout, double* Xhat, double* innov,
+                                           double* event, double* event_hat) {
+    return tracking_rollout_estimated(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, true, event,
+                                      event_hat, "qln_tracking_rollout_estimated_guarded");
+}
+int qln_tracking_rollout_estimated_guarded_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                                const double* H, int32_t ny, const double* vnoise, const double* wnoise,
+                                                const double* x0, const double* xhat0, const double* model, double* Zout,
+                                                double* Xhat, double* innov, double* event, double* event_hat) {
+    return tracking_rollout_estimated_host(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, true, event,
+                                           event_hat, "qln_tracking_rollout_estimated_guarded_host");
 }
 
 // ------------------------------------------------------------------ host-pointer (MOI) mode

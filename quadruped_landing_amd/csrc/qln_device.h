@@ -333,6 +333,14 @@ hipError_t launch_tracking_kalman(const BatchParams& p, const double* Zout, cons
                                   const double* event, const double* H, int ny, const double* Vd, const double* Sigma0,
                                   int sigma0_batch, const double* Wd, double* Lgain, double* Pest, double* Sigma, double* marg,
                                   double* event_var, hipStream_t stream);
+// The roll-out of the plant and the estimator side by side (qln_tracking_rollout_estimated / _guarded): Lgain [B][N][15][ny] and
+// H [ny][15] on the device; vnoise [B][N][ny], wnoise [B][N-1][15], x0, xhat0 [B][15], model and K may be null; Xhat [B][N][15],
+// innov [B][N][ny] may be null; event and event_hat [B][QLN_TOUCHDOWN_INFO_STRIDE] or null, with guarded only.
+hipError_t launch_tracking_rollout_estimated(const BatchParams& p, const double* Zref, const double* K, const double* Lgain,
+                                             const double* H, int ny, const double* vnoise, const double* wnoise,
+                                             const double* x0, const double* xhat0, const double* model, double* Zout,
+                                             double* Xhat, double* innov, bool guarded, double* event, double* event_hat,
+                                             hipStream_t stream);
 // batched Gauss-Newton step on the constraint violation, CGLS per problem in LDS (qln_solver_kernels.hip)
 size_t gauss_newton_lds_bytes(int32_t N);
 hipError_t launch_gauss_newton_step(const BatchParams& p, const double* Z, const double* c, double* dZ, int max_iters,

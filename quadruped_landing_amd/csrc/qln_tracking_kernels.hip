@@ -78,6 +78,10 @@
 // applications (cov_apply, cov_apply_touchdown): per knot a measurement update of the error covariance P -- H P by chains on
 // broadcast LDS reads, S = H P H' + V by row sums, an 8 x 8 L D L' in every lane, the Joseph form through the image -- and two
 // predictions, P's open loop and the estimate covariance M's closed loop, each in an image of its own.
+//
+// k_tracking_rollout_estimated: the loop that filter designs, flown (qln_tracking_rollout_estimated / _guarded):
+// the plant and the estimator rolled out side by side in k_tracking_rollout's mapping, one lane per problem, on its step and its
+// guarded step, the forces fed back from the estimate and the noise read from the caller's samples.
 #include "qln_row16.h"
 
 #include <utility>
@@ -681,6 +685,148 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout(BatchParams P, const
             ev[6] = td.fmin;
             ev[7] = 0.0;
         }
+    }
+}
+
+// The estimate-feedback roll-out (qln_tracking_rollout_estimated / _guarded, include/qln_evaluator.h), in
+// k_tracking_rollout's mapping: one lane per problem, which carries the plant's state x and the estimate xhat side by side.
+// H is uniform over the batch: the block copies its ny rows to LDS once, and every later read of it is a broadcast read at an
+// address the whole wave shares.
+// Per knot: the innovation of ny sensor rows and the update xhat += L_k innov in loops over QLN_TRACK_NY_MAX rows, so that x,
+// xhat and innov stay at compile-time positions; L_k is read row by row, ny consecutive doubles per lane, with a scheduling
+// barrier every three rows -- read column by column a wave's lines of L_k do not fit the L1 and were fetched once per sensor
+// row, and with all 120 loads in flight at once the kernel spilled -- then the forces fed back from xhat, then the
+// same step twice: the plant's on (x, model[b]) and the estimator's on (xhat, the handle's model).  Products are formed as
+// k_tracking_rollout forms K dx: the first product, then fma in index order.
+// kGuard: both steps are guarded_step, each on a contact mode and a Touchdown record of its own.
+template <bool kGuard>
+__global__ __launch_bounds__(kWave) void k_tracking_rollout_estimated(
+    BatchParams P, const double* __restrict__ Hg, int ny, const double* __restrict__ Zref, const double* __restrict__ Kg,
+    const double* __restrict__ Lg, const double* __restrict__ vnoise, const double* __restrict__ wnoise,
+    const double* __restrict__ x0, const double* __restrict__ xhat0, const double* __restrict__ model,
+    double* __restrict__ Zout, double* __restrict__ Xhat, double* __restrict__ innov_out, double* __restrict__ event,
+    double* __restrict__ event_hat) {
+    constexpr int NY = QLN_TRACK_NY_MAX;
+    __shared__ double Hs[NY * 15];
+    for (int i = threadIdx.x; i < 15 * ny; i += kWave) Hs[i] = Hg[i];
+    __syncthreads();
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= P.B) return;
+    const ProblemDesc pd = P.desc[b];
+    const int N = P.N, kt = pd.k_trans, im = pd.init_mode;
+    const Model M = plant_model<true>(P, model, b);     // the plant's
+    const Model Mh = plant_model<true>(P, nullptr, b);  // the estimator's: always the handle's
+    const double* __restrict__ Zr = Zref + (int64_t)b * P.z_stride;
+    double* __restrict__ Zo = Zout + (int64_t)b * P.z_stride;
+    const double* __restrict__ xs = x0 ? x0 + (int64_t)b * 15 : P.bnd + (int64_t)b * 30;
+    const double* __restrict__ hs = xhat0 ? xhat0 + (int64_t)b * 15 : Zr;
+    const double* __restrict__ Lb = Lg + (int64_t)b * N * (15 * ny);
+    const double* __restrict__ vb = vnoise ? vnoise + (int64_t)b * N * ny : nullptr;
+    const double* __restrict__ wb = wnoise ? wnoise + (int64_t)b * (N - 1) * 15 : nullptr;
+    double x[15], xhat[15], u[5], xn[15];
+#pragma unroll
+    for (int i = 0; i < 15; ++i) {
+        x[i] = xs[i];
+        xhat[i] = hs[i];
+        Zo[i] = x[i];
+    }
+    [[maybe_unused]] int mode = im, mode_hat = im;
+    [[maybe_unused]] Touchdown td = {-1.0, 0.0, 0.0, 0.0, 0.0, 0.0, __builtin_inf()}, tdh = td;
+    for (int k = 0; k < N; ++k) {
+        // innov_k = (H (x_k - x_ref,k) + v_k) - H (xhat^-_k - x_ref,k); the rows behind ny are zeros
+        double innov[NY];
+        {
+            double d[15], e[15];
+#pragma unroll
+            for (int i = 0; i < 15; ++i) {
+                const double xr = Zr[20 * k + i];
+                d[i] = x[i] - xr;
+                e[i] = xhat[i] - xr;
+            }
+#pragma unroll
+            for (int r = 0; r < NY; ++r) {
+                innov[r] = 0.0;
+                if (r < ny) {
+                    double y = Hs[15 * r] * d[0], yh = Hs[15 * r] * e[0];
+#pragma unroll
+                    for (int i = 1; i < 15; ++i) {
+                        y = fma(Hs[15 * r + i], d[i], y);
+                        yh = fma(Hs[15 * r + i], e[i], yh);
+                    }
+                    if (vb) y = y + vb[(int64_t)ny * k + r];
+                    innov[r] = y - yh;
+                    if (innov_out) innov_out[((int64_t)b * N + k) * ny + r] = innov[r];
+                }
+            }
+        }
+        // xhat_k = xhat^-_k + L_k innov_k, accumulated column by column onto each entry.  Row i of L_k is ny consecutive doubles,
+        // which the lane reads as whole cache lines; a column behind ny reads the row's last entry against a zero innovation,
+        // which adds an exact zero, so the loop has no branch.  Three rows' loads are in flight at a time.
+        {
+            // the row's address is carried in the lane and hidden from the optimiser after each step: folded into 120 uniform
+            // offsets ny * i + min(r, ny - 1) it took more scalar registers than there are
+            const double* Li = Lb + (int64_t)k * (15 * ny);
+#pragma unroll
+            for (int i = 0; i < 15; ++i) {
+#pragma unroll
+                for (int r = 0; r < NY; ++r) xhat[i] = fma(Li[min(r, ny - 1)], innov[r], xhat[i]);
+                Li += ny;
+                asm volatile("" : "+v"(Li));
+                if (i % 3 == 2) __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        if (Xhat) {
+            double* __restrict__ Xk = Xhat + ((int64_t)b * N + k) * 15;
+#pragma unroll
+            for (int i = 0; i < 15; ++i) Xk[i] = xhat[i];
+        }
+        if (k == N - 1) break;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) u[i] = Zr[20 * k + 15 + i];
+        if (Kg) {
+            const double* __restrict__ Kk = Kg + ((int64_t)b * (N - 1) + k) * (QLN_TRACK_NU * QLN_NX);
+            double dx[15];
+#pragma unroll
+            for (int i = 0; i < 15; ++i) dx[i] = xhat[i] - Zr[20 * k + i];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                double du = Kk[15 * m] * dx[0];
+#pragma unroll
+                for (int i = 1; i < 15; ++i) du = fma(Kk[15 * m + i], dx[i], du);
+                u[m] = u[m] - du;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 5; ++i) Zo[20 * k + 15 + i] = u[i];
+        // the plant's step, then the process noise on the whole state
+        if constexpr (kGuard) guarded_step(M, k, mode, x, u, xn, td);
+        else step_forward(M, k, kt, im, x, u, xn);
+#pragma unroll
+        for (int i = 0; i < 15; ++i) {
+            x[i] = wb ? xn[i] + wb[(int64_t)15 * k + i] : xn[i];
+            Zo[20 * (k + 1) + i] = x[i];
+        }
+        // the estimator's prediction: the same step on the estimate, at the handle's model
+        if constexpr (kGuard) guarded_step(Mh, k, mode_hat, xhat, u, xn, tdh);
+        else step_forward(Mh, k, kt, im, xhat, u, xn);
+#pragma unroll
+        for (int i = 0; i < 15; ++i) xhat[i] = xn[i];
+    }
+    if constexpr (kGuard) {
+        auto put = [&](double* __restrict__ out, const Touchdown& t) {
+            if (!out) return;
+            double* __restrict__ ev = out + (int64_t)QLN_TOUCHDOWN_INFO_STRIDE * b;
+            ev[0] = t.knot;
+            ev[1] = t.tau;
+            ev[2] = t.clock;
+            ev[3] = t.px;
+            ev[4] = t.vx;
+            ev[5] = t.vy;
+            ev[6] = t.fmin;
+            ev[7] = 0.0;
+        };
+        put(event, td);
+        put(event_hat, tdh);
     }
 }
 
@@ -2076,6 +2222,22 @@ hipError_t launch_tracking_kalman(const BatchParams& p, const double* Zout, cons
         K ? go(k_tracking_kalman<true, true, true>) : go(k_tracking_kalman<false, true, true>);
     else
         K ? go(k_tracking_kalman<true, false, false>) : go(k_tracking_kalman<false, false, false>);
+    return hipGetLastError();
+}
+
+// The two instantiations of k_tracking_rollout_estimated: the knot schedule or the guard.
+hipError_t launch_tracking_rollout_estimated(const BatchParams& p, const double* Zref, const double* K, const double* Lgain,
+                                             const double* H, int ny, const double* vnoise, const double* wnoise,
+                                             const double* x0, const double* xhat0, const double* model, double* Zout,
+                                             double* Xhat, double* innov, bool guarded, double* event, double* event_hat,
+                                             hipStream_t stream) {
+    if (ny < 1 || ny > QLN_TRACK_NY_MAX || !H || !Lgain) return hipErrorInvalidValue;
+    if (!guarded && (event || event_hat)) return hipErrorInvalidValue;
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((p.B + kWave - 1) / kWave), dim3(kWave), 0, stream, p, H, ny, Zref, K, Lgain, vnoise,
+                           wnoise, x0, xhat0, model, Zout, Xhat, innov, event, event_hat);
+    };
+    guarded ? go(k_tracking_rollout_estimated<true>) : go(k_tracking_rollout_estimated<false>);
     return hipGetLastError();
 }
 

@@ -1192,6 +1192,91 @@ class HybridNLP:
         we = (K is not None) if with_event_var is None else with_event_var
         return self._kalman_host(True, Zout, events, K, H, V, Sigma0, W, model, with_gains, with_pest, ws, wm, we)
 
+    # -- the estimate-feedback roll-out: the plant and the estimator flown together -------------------
+    @staticmethod
+    def _measurement_rows(H):
+        H = np.asarray(H.detach().cpu().numpy() if hasattr(H, "detach") else H, dtype=np.float64)
+        if H.ndim == 1:
+            H = H[None]
+        if H.ndim != 2 or H.shape[1] != n or not 1 <= H.shape[0] <= _lib.TRACK_NY_MAX:
+            raise ValueError(f"H of shape {H.shape}: expected (ny, 15) with 1 <= ny <= {_lib.TRACK_NY_MAX}")
+        return np.ascontiguousarray(H)
+
+    def tracking_rollout_estimated(self, Zref, K, Lgain, H, vnoise=None, wnoise=None, x0=None, xhat0=None, model=None,
+                                   guarded=False, out=None, with_estimate=True, with_innovations=False, with_events=True):
+        """The closed loop that feeds back an ESTIMATE, flown on the nonlinear hybrid plant: tracking_rollout_model (guarded
+        False) or tracking_rollout_guarded (guarded True) with F_k = F_ref,k - K_k (xhat_k|k - x_ref,k), the estimate updated
+        at every knot from y_k = H (x_k - x_ref,k) + v_k with the filter gains Lgain (B, N, 15, ny) of tracking_kalman and
+        predicted with the handle's model; guarded, the estimator lands by its own estimated foot (qln_evaluator.h).  The
+        noise is the caller's: vnoise (B, N, ny) and wnoise (B, N-1, 15) device tensors of samples, None for none; xhat0
+        (B, 15), None: the reference's first knot.  Returns (Zout, Xhat, innov), and guarded also (events, events_hat), the
+        plant's and the estimator's touchdown records: Xhat (B, N, 15), innov (B, N, ny), each None unless asked for."""
+        T = _torch()
+        Hh = self._measurement_rows(H)
+        ny = Hh.shape[0]
+        Hd = T.from_numpy(Hh).to(self._dev())
+        self._check(Zref, self.dims.z_total, "Zref")
+        out = self.new_Z() if out is None else out
+        self._check(out, self.dims.z_total, "out")
+        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        if Lgain is None:
+            raise ValueError("Lgain is required: the filter gains tracking_kalman returned")
+        lp = self._check(Lgain, self.B * self.N * n * ny, "Lgain")
+        vp = self._check_opt(vnoise, self.B * self.N * ny, "vnoise")
+        wp = self._check_opt(wnoise, self.B * (self.N - 1) * n, "wnoise")
+        xp = self._check_opt(x0, self.B * n, "x0")
+        hp = self._check_opt(xhat0, self.B * n, "xhat0")
+        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
+        new = lambda want, shape: T.zeros(shape, dtype=T.float64, device=self._dev()) if want else None  # noqa: E731
+        Xh = new(with_estimate, (self.B, self.N, n))
+        iv = new(with_innovations, (self.B, self.N, ny))
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        if not guarded:
+            _lib.check(_lib.lib().qln_tracking_rollout_estimated(self._h, Zref.data_ptr(), kp, lp, Hd.data_ptr(), ny, vp, wp, xp,
+                                                                 hp, mp, out.data_ptr(), ptr(Xh), ptr(iv)))
+            return out, Xh, iv
+        ev = new(with_events, (self.B, _lib.TOUCHDOWN_INFO_STRIDE))
+        eh = new(with_events, (self.B, _lib.TOUCHDOWN_INFO_STRIDE))
+        _lib.check(_lib.lib().qln_tracking_rollout_estimated_guarded(self._h, Zref.data_ptr(), kp, lp, Hd.data_ptr(), ny, vp, wp,
+                                                                     xp, hp, mp, out.data_ptr(), ptr(Xh), ptr(iv), ptr(ev),
+                                                                     ptr(eh)))
+        return out, Xh, iv, ev, eh
+
+    def tracking_rollout_estimated_host(self, Zref, K, Lgain, H, vnoise=None, wnoise=None, x0=None, xhat0=None, model=None,
+                                        guarded=False, with_estimate=True, with_innovations=False, with_events=True):
+        """The same with host arrays (synchronous): numpy (Zout (z_total,), zeros past n_nlp, Xhat, innov) and guarded also
+        (events, events_hat).  A non-finite H or model entry, or mb, mf or lb <= 0, is refused."""
+        Hh = self._measurement_rows(H)
+        ny = Hh.shape[0]
+        Zref, K, x0, xhat0 = self._host_Z(Zref, "Zref"), self._host_K(K), self._host_x0(x0), self._host_x0(xhat0)
+        model = self._host_model(model)
+
+        def flat(a, size, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
+            if a.size != size:
+                raise ValueError(f"{name} has {a.size} entries, expected {size}")
+            return a
+
+        if Lgain is None:
+            raise ValueError("Lgain is required: the filter gains tracking_kalman_host returned")
+        Lg = flat(Lgain, self.B * self.N * n * ny, "Lgain")
+        vn = flat(vnoise, self.B * self.N * ny, "vnoise")
+        wn = flat(wnoise, self.B * (self.N - 1) * n, "wnoise")
+        out = np.zeros(self.dims.z_total)
+        Xh = np.zeros((self.B, self.N, n)) if with_estimate else None
+        iv = np.zeros((self.B, self.N, ny)) if with_innovations else None
+        args = (self._h, Zref.ctypes.data, _host_ptr(K), Lg.ctypes.data, Hh.ctypes.data, ny, _host_ptr(vn), _host_ptr(wn),
+                _host_ptr(x0), _host_ptr(xhat0), _host_ptr(model), out.ctypes.data, _host_ptr(Xh), _host_ptr(iv))
+        if not guarded:
+            _lib.check(_lib.lib().qln_tracking_rollout_estimated_host(*args))
+            return out, Xh, iv
+        ev = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if with_events else None
+        eh = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if with_events else None
+        _lib.check(_lib.lib().qln_tracking_rollout_estimated_guarded_host(*args, _host_ptr(ev), _host_ptr(eh)))
+        return out, Xh, iv, ev, eh
+
     # -- contact-aware force limits: the roll-out, its sweeps and the gains at fixed active set ------
     def _sat_ptr(self, sat):
         if sat is None:
