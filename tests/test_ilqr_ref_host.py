@@ -115,9 +115,14 @@ def test_sweep_is_the_dense_kkt_solution_of_its_quadratic_problem(case, b):
     arithmetic by other means, so it is held to 100 times that estimate."""
     batch = IC.clock_case() if case == "clock" else IC.shape(case)
     P, U0 = IC.problems(batch)
-    p, o = P[b], IR.Options(**WIDE)
-    lam, leq = _multipliers(p, U0[b], o)
-    X, U, lam, leq, rho, tm, gz, Hzz, blocks, sw = _linearise(p, U0[b], o, lam, leq)
+    _sweep_against_dense_kkt(f"{case} b={b}", P[b], U0[b])
+
+
+def _sweep_against_dense_kkt(label, p, U0):
+    """the comparison of test_sweep_is_the_dense_kkt_solution_of_its_quadratic_problem on one problem"""
+    o = IR.Options(**WIDE)
+    lam, leq = _multipliers(p, U0, o)
+    X, U, lam, leq, rho, tm, gz, Hzz, blocks, sw = _linearise(p, U0, o, lam, leq)
     assert not sw.clamped.any()
     N = p.N
     nx, nu = 15 * N, 5 * (N - 1)
@@ -150,7 +155,7 @@ def test_sweep_is_the_dense_kkt_solution_of_its_quadratic_problem(case, b):
         dx = blocks[k][:, :15] @ dx + blocks[k][:, 15:] @ du[k]
     e = IR.control_error(U + du, U + du_kkt, 0.02)
     tol = 100 * IR.control_error(U + du_kkt + du_err, U + du_kkt, 0.02)
-    print(f"{case} b={b}: sweep against dense KKT e = {e:.2e}, refinement correction x 100 = {tol:.2e}, step size "
+    print(f"{label}: sweep against dense KKT e = {e:.2e}, refinement correction x 100 = {tol:.2e}, step size "
           f"{IR.control_error(U + du_kkt, U, 0.02):.2e}")
     assert tol < 1e-9  # the estimate itself is small: the dense solve is a usable yardstick
     assert e <= tol

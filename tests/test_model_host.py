@@ -101,10 +101,12 @@ def test_np_oracle_is_back_to_the_defaults_after_the_context_also_after_an_excep
 def _lagrangian_gradient_differences(batch, sigma, mu, eps=1e-6):
     """Dense Hessian of sigma f + mu . c of problem 0 by central differences of the C oracle's sigma grad_f + J' mu.
     grad_f! has no d(h l)/dh term (quirk Q2), so the objective's part takes its step-length ROWS from the symmetric
-    entries; its (h, h) entry is sigma (3 R_h h + 2 r_h), zero for the LQR cost tables of make_batch (asserted)."""
+    entries, and its (h, h) entry, sigma (3 R_h h + 2 r_h), from a central SECOND difference of the oracle's eval_f along
+    h_k.  f is a cubic in h_k, so that difference has no truncation error at any step; with eps_h = 1e-2 its rounding is
+    4 ulp(f) / eps_h^2 = 1e-11 |f|, under the 1e-8 |g| the caller allows.  (The LQR tables of make_batch have
+    R_h = r_h = 0; tests/cost_cases.py's have not.)"""
     N, n = batch.N, 20 * batch.N - 5
     cost = np.asarray(batch.obj).reshape(N, 41)
-    assert not cost[:, 19].any() and not cost[:, 39].any()
     o = O.OracleNLP(N, int(batch.k_trans[0]), int(batch.init_mode[0]), batch.x0[0], batch.xf[0], cost, oracle_model(batch.model))
     rows, cols = o.jac_structure()
     Z = batch.Z[0]
@@ -122,17 +124,25 @@ def _lagrangian_gradient_differences(batch, sigma, mu, eps=1e-6):
         Dobj[:, j], Dcon[:, j] = (gp - gm) / (2 * eps), (jp - jm) / (2 * eps)
     h = np.arange(19, n, 20)
     Dobj[h, :] = Dobj[:, h].T
-    Dobj[h, h] = 0.0
+    eps_h, f0 = 1e-2, o.eval_f(Z)
+    for j in h:
+        e = np.zeros(n)
+        e[j] = eps_h
+        Dobj[j, j] = (o.eval_f(Z + e) - 2 * f0 + o.eval_f(Z - e)) / eps_h**2
     g0, j0 = parts(Z)
     return sigma * Dobj + Dcon, np.abs(sigma * g0 + j0).max()
 
 
-def _hessian_sym_against_differences(model, seed):
+def _hessian_sym_against_differences(model, seed, convex=None):
+    """convex = None: make_batch's table; True / False: that form of tests/cost_cases.generic_cost"""
     from quadruped_landing_amd.nlp import hessian_structure
+    from tests import cost_cases as CC
     from tests import hessian_sym as HS
 
     N, kt = 6, 3
     batch = PG.make_batch(1, N, kt, 1, seed=seed, model=model)
+    if convex is not None:
+        CC.with_generic_cost(batch, seed, False, convex)
     batch.Z[0, 2] = 0.3            # theta > 0 on the first knot and <= 0 on the second: both clearance branches
     batch.Z[0, 22] = -0.2
     rng = np.random.default_rng(seed + 1)

@@ -161,13 +161,15 @@ def ref_gains(nlp, Z, Qw, Rw, Qfw, restore_clock=True):
     return A, Bm, K, P
 
 
-def check_gains_against_numpy(batch, bar=1e-10, **kw):
+def check_gains_against_numpy(batch, bar=1e-10, weights=None, **kw):
+    """weights: (Qdiag, Rdiag, Qfdiag) in place of (QW, R, QFW)"""
     from quadruped_landing_amd import nlp as NL
 
+    Qw, Rw, Qfw = (QW, R, QFW) if weights is None else weights
     h = nlp(batch, **kw)
     Z = h.upload_Z(batch.Z)
-    K, P = h.tracking_lqr(Z, QW, R, QFW)
-    _, _, Kr, Pr = ref_gains(h, Z, QW, R, QFW)
+    K, P = h.tracking_lqr(Z, Qw, Rw, Qfw)
+    _, _, Kr, Pr = ref_gains(h, Z, Qw, Rw, Qfw)
     Kg = K.cpu().numpy()
     Pg = NL.unpack_cost_to_go(P)
     ek, ep = CR.knot_rel(Kg, Kr), CR.knot_rel(Pg, Pr)
