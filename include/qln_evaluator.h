@@ -904,7 +904,8 @@ int qln_tracking_kalman_guarded_host(qln_handle* h, const double* Zout, const do
  * respectively _guarded and its event record, whatever K is.
  * Refused with QLN_ERR_INVALID_ARGUMENT: a NULL h, Zref, Zout, Lgain or H; ny outside 1..QLN_TRACK_NY_MAX; an overlap.  The
  * device forms do not validate device data; the host forms also refuse a non-finite H, and a model as
- * qln_tracking_rollout_guarded_host does.  Force limits in this loop and sweeps through it do not exist.
+ * qln_tracking_rollout_guarded_host does.  Force limits in this loop do not exist.  Its derivatives are
+ * qln_tracking_rollout_estimated_jvp / _vjp below.
  * Device pointers, stream-ordered; needs no cost table. */
 int qln_tracking_rollout_estimated(qln_handle* h, const double* Zref, const double* K /* or NULL */, const double* Lgain,
                                    const double* H, int32_t ny, const double* vnoise, const double* wnoise, const double* x0,
@@ -921,6 +922,109 @@ int qln_tracking_rollout_estimated_guarded_host(qln_handle* h, const double* Zre
                                                 const double* H, int32_t ny, const double* vnoise, const double* wnoise,
                                                 const double* x0, const double* xhat0, const double* model, double* Zout,
                                                 double* Xhat, double* innov, double* event, double* event_hat);
+/* Forward and reverse sweeps THROUGH the estimate-feedback roll-out: the derivative of qln_tracking_rollout_estimated / _guarded
+ * with respect to (Zref, K, Lgain, x0, xhat0, model) at the trajectory (Zout, Xhat, innov) it produced.  vnoise, wnoise and H are
+ * HELD FIXED -- the pathwise derivative at fixed noise samples -- and get no tangent and no cotangent.  Knots are 0-based.
+ * Inputs of both sweeps (device pointers):
+ *   Zref, K (or NULL), Lgain, H, ny, model (or NULL): the roll-out's.
+ *   Zout, Xhat: the trajectory it wrote.  Both required.
+ *   innov:      the innovations it wrote.  Required exactly when a tangent or cotangent of Lgain is asked for (Lgain_dot,
+ *               Lgain_bar); otherwise it may be NULL and is not read.
+ *   event, event_hat (guarded forms): the plant's and the estimator's records.  Both required.  Only entries 0 (the knot) and 1
+ *               (tau) are read, as in qln_tracking_rollout_guarded_jvp.
+ * Nothing is re-run, and nothing checks that the trajectory is the roll-out of the inputs.  The handle's k_trans is read by the
+ * knot-scheduled forms only.
+ * Blocks.  [A^p_k B^p_k G^p_k] is the plant's block at Zout's (x_k, u_k) and model[b]; [A^e_k B^e_k] is the estimator's at
+ * (Xhat_k, Zout's u_k) and the handle's model, which has no tangent.  Knot-scheduled forms: both are the blocks of
+ * qln_tracking_rollout_model_jvp.  Guarded forms: each chain takes the blocks of qln_tracking_rollout_guarded_jvp at its OWN
+ * touchdown knot and tau -- the plant's from event, the estimator's from event_hat -- and the composite step with its own dtau at
+ * that knot; the estimator's dtau depends on dxh and dF, not on dx, and the two chains may land in different knots.
+ * Forward sweep (qln_tracking_rollout_estimated_jvp / _guarded_jvp).  Tangents Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot,
+ * model_dot, each optional (NULL: zero, except xhat0_dot below; all NULL is refused; K_dot needs K):
+ *     dx_0 = x0_dot,   dxm_0 = xhat0_dot       (xhat0_dot == NULL: dxm_0 = x_ref_dot,0, the forward call's xhat0 == NULL case)
+ *     for k = 0 .. N-1:
+ *       dinnov_k = H (dx_k - dxm_k)
+ *       dxh_k    = dxm_k + L_k dinnov_k + Lgain_dot_k innov_k
+ *       if k == N-1: stop
+ *       dF_k = dF_ref,k - K_k (dxh_k - dx_ref,k) - K_dot_k (xhat_k - x_ref,k),   dh_k = dh_ref,k
+ *       dx_{k+1}  = A^p_k dx_k  + B^p_k (dF_k, dh_k) + G^p_k model_dot
+ *       dxm_{k+1} = A^e_k dxh_k + B^e_k (dF_k, dh_k)
+ *   Outputs (overwritten; which optional ones are asked for does not change the others' bits):
+ *     Zout_dot: required, layout of Z: dx_k and (dF_k, dh_k); entries past n_nlp are never written.
+ *     Xhat_dot: [B][N][15] or NULL: dxh_k.     innov_dot: [B][N][ny] or NULL: dinnov_k.
+ *     event_dot, event_hat_dot (guarded): [B][QLN_TOUCHDOWN_INFO_STRIDE] or NULL, with the entries
+ *               qln_tracking_rollout_guarded_jvp defines, for the plant's and for the estimator's touchdown.
+ * Reverse sweep (qln_tracking_rollout_estimated_vjp / _guarded_vjp).  Cotangents Zbar (required, layout of Z), Xhat_bar
+ * [B][N][15] and innov_bar [B][N][ny] (NULL: zero).  The exact transpose of the recursion above, k = N-1 .. 0, with lam and lamm
+ * the cotangents of dx and dxm (zero behind the last knot):
+ *     k < N-1:  ubar = Zbar[u_k] + B^p' lam + B^e' lamm,   ax = A^p' lam,   model_bar += G^p' lam,
+ *               xhb = Xhat_bar_k + A^e' lamm - K_k' ubar[0:4]                  (k == N-1: ax = 0, xhb = Xhat_bar_k)
+ *     ib = innov_bar_k + L_k' xhb,    lam = Zbar[x_k] + ax + H' ib,    lamm = xhb - H' ib
+ *   Outputs, each optional (K_bar needs K):
+ *     Zref_bar:  layout of Z: K_k' ubar[0:4] in the x slots (zero at knot N-1), ubar in the u slots;
+ *     K_bar:     -ubar[0:4] (xhat_k - x_ref,k)';      Lgain_bar: [B][N][15][ny], xhb innov_k';
+ *     x0_bar:    lam after knot 0;                     model_bar: [B][QLN_MODEL_NP];
+ *     xhat0_bar: [B][15], lamm after knot 0.  If it is NULL that cotangent is ADDED to Zref_bar's x_0 slot -- the forward call
+ *                with xhat0 == NULL, whose xhat^-_0 is x_ref,0; if it is non-NULL it is written there and not added.
+ *   In each of the two modes
+ *     <Zbar, Zout_dot> + <Xhat_bar, Xhat_dot> + <innov_bar, innov_dot> = <Zref_bar, Zref_dot> + <K_bar, K_dot>
+ *         + <Lgain_bar, Lgain_dot> + <x0_bar, x0_dot> + <xhat0_bar, xhat0_dot> + <model_bar, model_dot>.
+ * Reductions: with Lgain = 0, Lgain_dot == NULL, xhat0_dot == NULL, Zref_dot == NULL and Xhat on Zref the estimator's chain is
+ * zero, and Zout_dot is bit for bit qln_tracking_rollout_model_jvp's (K == NULL) on (x0_dot, model_dot), respectively
+ * _guarded_jvp's with its event_dot; the reverse sweep's x0_bar and model_bar are those sweeps'.  A call with ny rows gives the
+ * bits of the call with QLN_TRACK_NY_MAX rows whose further H rows and columns of L, Lgain_dot and innov are zero.
+ * Refused with QLN_ERR_INVALID_ARGUMENT: a NULL h, Zref, Lgain, H, Zout, Xhat, Zout_dot or Zbar; ny outside
+ * 1..QLN_TRACK_NY_MAX; a NULL event or event_hat (guarded); Lgain_dot or Lgain_bar without innov; K_dot or K_bar without K; no
+ * tangent at all; an output that overlaps an input or another output.  The device forms do not validate device data; the host
+ * forms also refuse a non-finite H, a model and event records as qln_tracking_rollout_guarded_jvp_host does.
+ * Device pointers, stream-ordered; needs no cost table. */
+int qln_tracking_rollout_estimated_jvp(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
+                                       int32_t ny, const double* model, const double* Zout, const double* Xhat,
+                                       const double* innov, const double* Zref_dot, const double* K_dot, const double* Lgain_dot,
+                                       const double* x0_dot, const double* xhat0_dot, const double* model_dot, double* Zout_dot,
+                                       double* Xhat_dot, double* innov_dot);
+int qln_tracking_rollout_estimated_vjp(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
+                                       int32_t ny, const double* model, const double* Zout, const double* Xhat,
+                                       const double* innov, const double* Zbar, const double* Xhat_bar, const double* innov_bar,
+                                       double* Zref_bar, double* K_bar, double* Lgain_bar, double* x0_bar, double* xhat0_bar,
+                                       double* model_bar);
+int qln_tracking_rollout_estimated_guarded_jvp(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                               const double* H, int32_t ny, const double* model, const double* Zout,
+                                               const double* Xhat, const double* innov, const double* event,
+                                               const double* event_hat, const double* Zref_dot, const double* K_dot,
+                                               const double* Lgain_dot, const double* x0_dot, const double* xhat0_dot,
+                                               const double* model_dot, double* Zout_dot, double* Xhat_dot, double* innov_dot,
+                                               double* event_dot, double* event_hat_dot);
+int qln_tracking_rollout_estimated_guarded_vjp(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                               const double* H, int32_t ny, const double* model, const double* Zout,
+                                               const double* Xhat, const double* innov, const double* event,
+                                               const double* event_hat, const double* Zbar, const double* Xhat_bar,
+                                               const double* innov_bar, double* Zref_bar, double* K_bar, double* Lgain_bar,
+                                               double* x0_bar, double* xhat0_bar, double* model_bar);
+/* the same as host forms (see "Host forms" above; Zout_dot and Zref_bar are in-out as in the _model_ forms) */
+int qln_tracking_rollout_estimated_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                            const double* H, int32_t ny, const double* model, const double* Zout,
+                                            const double* Xhat, const double* innov, const double* Zref_dot, const double* K_dot,
+                                            const double* Lgain_dot, const double* x0_dot, const double* xhat0_dot,
+                                            const double* model_dot, double* Zout_dot, double* Xhat_dot, double* innov_dot);
+int qln_tracking_rollout_estimated_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                            const double* H, int32_t ny, const double* model, const double* Zout,
+                                            const double* Xhat, const double* innov, const double* Zbar, const double* Xhat_bar,
+                                            const double* innov_bar, double* Zref_bar, double* K_bar, double* Lgain_bar,
+                                            double* x0_bar, double* xhat0_bar, double* model_bar);
+int qln_tracking_rollout_estimated_guarded_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                                    const double* H, int32_t ny, const double* model, const double* Zout,
+                                                    const double* Xhat, const double* innov, const double* event,
+                                                    const double* event_hat, const double* Zref_dot, const double* K_dot,
+                                                    const double* Lgain_dot, const double* x0_dot, const double* xhat0_dot,
+                                                    const double* model_dot, double* Zout_dot, double* Xhat_dot,
+                                                    double* innov_dot, double* event_dot, double* event_hat_dot);
+int qln_tracking_rollout_estimated_guarded_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                                    const double* H, int32_t ny, const double* model, const double* Zout,
+                                                    const double* Xhat, const double* innov, const double* event,
+                                                    const double* event_hat, const double* Zbar, const double* Xhat_bar,
+                                                    const double* innov_bar, double* Zref_bar, double* K_bar, double* Lgain_bar,
+                                                    double* x0_bar, double* xhat0_bar, double* model_bar);
 /* Z <- Z + N(0, sigma^2) on every entry, step lengths h then clipped to [h_min, h_max] (redraw_h = 0) or redrawn
  * U(h_min, h_max) (redraw_h != 0) -- the evaluation point of SURVEY.md 8d from qln_initial_guess's Z0.  The normal
  * draws are Box-Muller on the sampler's stream from `stream_offset`: the recipe's distribution, not numpy's numbers. */

@@ -439,6 +439,95 @@ function tracking_rollout_estimated_guarded(prob::HybridNLPHIP, Zref::Vector{Flo
                     model === nothing ? C_NULL : model, Zout, Xhat, innov, events, events_hat))
     return Zout, Xhat, innov, events, events_hat
 end
+# The sweeps through the estimate-feedback roll-out (include/qln_evaluator.h, DESIGN.md 4.23): the derivative of
+# tracking_rollout_estimated / _guarded at the (Zout, Xhat, innov[, events, events_hat]) it returned, with respect to Zref, K, L,
+# x0, xhat0 and model, at FIXED noise samples and fixed H.  Forward: tangents as keywords, nothing for zero -- except xhat0_dot,
+# whose nothing is the roll-out's xhat0 = nothing (the estimate starts on the reference, its tangent is Zref_dot's first knot);
+# returns (Zout_dot, Xhat_dot (15, N), innov_dot (ny, N)) and guarded also (event_dot, event_hat_dot).  Reverse: cotangents Zbar
+# and, as keywords, Xhat_bar (15, N) and innov_bar (ny, N); returns (Zref_bar, K_bar, L_bar, x0_bar, xhat0_bar, model_bar), with
+# with_xhat0 = false xhat0_bar is nothing and its value is added to Zref_bar's first knot.
+_opt(x) = x === nothing ? C_NULL : x
+function _estimated_rows(prob::HybridNLPHIP, L::Array{Float64,3}, H::Matrix{Float64})
+    ny = size(H, 1)
+    (1 <= ny <= 8 && size(H, 2) == 15 && size(L) == (ny, 15, prob.N)) || error("H: (ny, 15) with 1 <= ny <= 8, L: (ny, 15, N)")
+    return ny, Matrix{Float64}(transpose(H))  # row-major [ny][15]
+end
+function tracking_rollout_estimated_jvp(prob::HybridNLPHIP, Zref::Vector{Float64}, L::Array{Float64,3}, H::Matrix{Float64},
+                                        Zout::Vector{Float64}, Xhat::Matrix{Float64}, innov::Matrix{Float64}; K=nothing,
+                                        model=nothing, Zref_dot=nothing, K_dot=nothing, L_dot=nothing, x0_dot=nothing,
+                                        xhat0_dot=nothing, model_dot=nothing)
+    ny, Hrow = _estimated_rows(prob, L, H)
+    Zout_dot = zeros(length(Zref))
+    Xhat_dot = zeros(15, prob.N)
+    innov_dot = zeros(ny, prob.N)
+    qln_check(ccall((:qln_tracking_rollout_estimated_jvp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, _opt(K), L, Hrow, Int32(ny), _opt(model), Zout, Xhat, innov, _opt(Zref_dot), _opt(K_dot),
+                    _opt(L_dot), _opt(x0_dot), _opt(xhat0_dot), _opt(model_dot), Zout_dot, Xhat_dot, innov_dot))
+    return Zout_dot, Xhat_dot, innov_dot
+end
+function tracking_rollout_estimated_guarded_jvp(prob::HybridNLPHIP, Zref::Vector{Float64}, L::Array{Float64,3}, H::Matrix{Float64},
+                                                Zout::Vector{Float64}, Xhat::Matrix{Float64}, innov::Matrix{Float64},
+                                                events::Vector{Float64}, events_hat::Vector{Float64}; K=nothing, model=nothing,
+                                                Zref_dot=nothing, K_dot=nothing, L_dot=nothing, x0_dot=nothing,
+                                                xhat0_dot=nothing, model_dot=nothing)
+    ny, Hrow = _estimated_rows(prob, L, H)
+    Zout_dot = zeros(length(Zref))
+    Xhat_dot = zeros(15, prob.N)
+    innov_dot = zeros(ny, prob.N)
+    event_dot = zeros(8)
+    event_hat_dot = zeros(8)
+    qln_check(ccall((:qln_tracking_rollout_estimated_guarded_jvp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}),
+                    prob.handle, Zref, _opt(K), L, Hrow, Int32(ny), _opt(model), Zout, Xhat, innov, events, events_hat,
+                    _opt(Zref_dot), _opt(K_dot), _opt(L_dot), _opt(x0_dot), _opt(xhat0_dot), _opt(model_dot), Zout_dot, Xhat_dot,
+                    innov_dot, event_dot, event_hat_dot))
+    return Zout_dot, Xhat_dot, innov_dot, event_dot, event_hat_dot
+end
+function tracking_rollout_estimated_vjp(prob::HybridNLPHIP, Zref::Vector{Float64}, L::Array{Float64,3}, H::Matrix{Float64},
+                                        Zout::Vector{Float64}, Xhat::Matrix{Float64}, innov::Matrix{Float64},
+                                        Zbar::Vector{Float64}; K=nothing, model=nothing, Xhat_bar=nothing, innov_bar=nothing,
+                                        with_xhat0::Bool=true)
+    ny, Hrow = _estimated_rows(prob, L, H)
+    Zref_bar = zeros(length(Zref))
+    K_bar = K === nothing ? nothing : zeros(size(K))
+    L_bar = zeros(ny, 15, prob.N)
+    x0_bar = zeros(15)
+    xhat0_bar = with_xhat0 ? zeros(15) : nothing
+    model_bar = zeros(4)
+    qln_check(ccall((:qln_tracking_rollout_estimated_vjp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, _opt(K), L, Hrow, Int32(ny), _opt(model), Zout, Xhat, innov, Zbar, _opt(Xhat_bar),
+                    _opt(innov_bar), Zref_bar, _opt(K_bar), L_bar, x0_bar, _opt(xhat0_bar), model_bar))
+    return Zref_bar, K_bar, L_bar, x0_bar, xhat0_bar, model_bar
+end
+function tracking_rollout_estimated_guarded_vjp(prob::HybridNLPHIP, Zref::Vector{Float64}, L::Array{Float64,3}, H::Matrix{Float64},
+                                                Zout::Vector{Float64}, Xhat::Matrix{Float64}, innov::Matrix{Float64},
+                                                events::Vector{Float64}, events_hat::Vector{Float64}, Zbar::Vector{Float64};
+                                                K=nothing, model=nothing, Xhat_bar=nothing, innov_bar=nothing,
+                                                with_xhat0::Bool=true)
+    ny, Hrow = _estimated_rows(prob, L, H)
+    Zref_bar = zeros(length(Zref))
+    K_bar = K === nothing ? nothing : zeros(size(K))
+    L_bar = zeros(ny, 15, prob.N)
+    x0_bar = zeros(15)
+    xhat0_bar = with_xhat0 ? zeros(15) : nothing
+    model_bar = zeros(4)
+    qln_check(ccall((:qln_tracking_rollout_estimated_guarded_vjp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, _opt(K), L, Hrow, Int32(ny), _opt(model), Zout, Xhat, innov, events, events_hat, Zbar,
+                    _opt(Xhat_bar), _opt(innov_bar), Zref_bar, _opt(K_bar), L_bar, x0_bar, _opt(xhat0_bar), model_bar))
+    return Zref_bar, K_bar, L_bar, x0_bar, xhat0_bar, model_bar
+end
 # Contact-aware force limits (include/qln_evaluator.h, DESIGN.md 4.20).  limits holds 8 values, {lo, hi} of F_x and of F_y for a
 # free foot, then for a standing one (+-Inf: no limit).  tracking_rollout_limited is tracking_rollout_model (guarded = false) or
 # tracking_rollout_guarded (guarded = true) with the applied forces clamped, and returns (Zout, events, sat): events is nothing

@@ -191,6 +191,14 @@ SIGNATURES = {
     "qln_tracking_rollout_estimated_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 8),
     "qln_tracking_rollout_estimated_guarded": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 10),
     "qln_tracking_rollout_estimated_guarded_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 10),
+    "qln_tracking_rollout_estimated_jvp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 13),
+    "qln_tracking_rollout_estimated_vjp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 13),
+    "qln_tracking_rollout_estimated_guarded_jvp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 17),
+    "qln_tracking_rollout_estimated_guarded_vjp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 15),
+    "qln_tracking_rollout_estimated_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 13),
+    "qln_tracking_rollout_estimated_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 13),
+    "qln_tracking_rollout_estimated_guarded_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 17),
+    "qln_tracking_rollout_estimated_guarded_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 15),
     "qln_eval_constraint_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_eval_constraint_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_gauss_newton_step": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, C.c_double, _dp, _dp, _dp]),

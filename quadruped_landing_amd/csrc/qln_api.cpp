@@ -115,7 +115,11 @@ enum HostRole {
     kWnoise, // in: its process noise                                       [B][N-1][15]
     kXhat,   // out: its estimates xhat_k|k                                 [B][N][15]
     kInnov,  // out: its innovations ([B][N][ny] used)                      [B][N][8]
-    kEventHat,  // out: the estimator's touchdown records                   [B][8]
+    kEventHat,  // out: the estimator's touchdown records; in: the same for the sweeps  [B][8]
+    kLgainD, // in: the estimated jvp's Lgain_dot; out: the vjp's Lgain_bar  layout of Lgain
+    kXhatD,  // out: the estimated jvp's Xhat_dot; in: the vjp's Xhat_bar   [B][N][15]
+    kInnovD, // out: the estimated jvp's innov_dot; in: the vjp's innov_bar  [B][N][8]
+    kEventHatD,  // out: the estimated guarded jvp's event_hat_dot          [B][8]
     kHostRoles
 };
 
@@ -191,14 +195,14 @@ int64_t host_role_size(const qln_handle* h, HostRole r) {
         case kX0: case kXhat0: return (int64_t)D.B * QLN_NX;
         case kMultInfo: return (int64_t)D.B * QLN_MULT_INFO_STRIDE;
         case kModel: case kModelD: return (int64_t)D.B * QLN_MODEL_NP;
-        case kEvent: case kEventD: case kEventHat: return (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
+        case kEvent: case kEventD: case kEventHat: case kEventHatD: return (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
         case kEventVar: return (int64_t)D.B * 2;
         case kSat: return tracking_sat_total(D);
         case kH: return (int64_t)QLN_TRACK_NY_MAX * QLN_NX;
-        case kLgain: return tracking_gain_total(D, QLN_TRACK_NY_MAX);
-        case kVnoise: case kInnov: return tracking_meas_total(D, QLN_TRACK_NY_MAX);
+        case kLgain: case kLgainD: return tracking_gain_total(D, QLN_TRACK_NY_MAX);
+        case kVnoise: case kInnov: case kInnovD: return tracking_meas_total(D, QLN_TRACK_NY_MAX);
         case kWnoise: return (int64_t)D.B * (D.N - 1) * QLN_NX;
-        case kXhat: return (int64_t)D.B * D.N * QLN_NX;
+        case kXhat: case kXhatD: return (int64_t)D.B * D.N * QLN_NX;
         case kHostRoles: break;
     }
     return 0;
@@ -1849,6 +1853,242 @@ int qln_tracking_rollout_estimated_guarded_host(qln_handle* h, const double* Zre
                                                 double* Xhat, double* innov, double* event, double* event_hat) {
     return tracking_rollout_estimated_host(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, true, event,
                                            event_hat, "qln_tracking_rollout_estimated_guarded_host");
+}
+
+// The sweeps through the estimate-feedback roll-out (k_tracking_rollout_estimated_jvp / _vjp).  What both sweeps share: the
+// roll-out's inputs and the trajectory it produced.  The checks that need no handle come first.
+// guarded: the sweeps through the two guard-triggered touchdowns, which need both of the roll-out's event records
+// want_gain: a tangent or cotangent of Lgain is asked for, which needs innov
+struct EstimatedTraj {
+    const double *Zref, *K, *Lgain, *H;
+    int32_t ny;
+    const double *model, *Zout, *Xhat, *innov, *event, *event_hat;
+};
+
+static int check_tracking_estimated_sweep_args(const qln_handle* h, const EstimatedTraj& t, bool guarded, bool want_gain,
+                                               const std::string& w) {
+    if (t.ny < 1 || t.ny > QLN_TRACK_NY_MAX)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
+    if (!t.Lgain || !t.H) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Lgain or H");
+    if (guarded && (!t.event || !t.event_hat))
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event or event_hat (the guarded roll-out's two records)");
+    if (want_gain && !t.innov)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null innov (the tangent or cotangent of Lgain needs the innovations)");
+    if (!t.Zref || !t.Zout || !t.Xhat) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref, Zout or Xhat");
+    return check_handle(h);
+}
+
+// the spans of the trajectory's arguments, for the overlap rule (innov only where it is read)
+#define QLN_ESTIMATED_TRAJ_SPANS(D, t, want_gain)                                                                             \
+    {t.Zref, D.z_total}, {t.K, tracking_k_total(D)}, {t.Lgain, tracking_gain_total(D, t.ny)}, {t.H, (int64_t)t.ny * QLN_NX}, \
+        {t.model, (int64_t)D.B * QLN_MODEL_NP}, {t.Zout, D.z_total}, {t.Xhat, (int64_t)D.B * D.N * QLN_NX},                   \
+        {want_gain ? t.innov : nullptr, tracking_meas_total(D, t.ny)},                                                        \
+        {t.event, (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE}, {t.event_hat, (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE}
+
+static int check_tracking_estimated_jvp_args(const qln_handle* h, const EstimatedTraj& t, bool guarded,
+                                             const qln::EstimatedJvpArgs& a, const char* who) {
+    const std::string w(who);
+    if (!a.Zref_dot && !a.K_dot && !a.Lgain_dot && !a.x0_dot && !a.xhat0_dot && !a.model_dot)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every tangent is NULL (no direction)");
+    if (a.K_dot && !t.K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_dot needs K (K == NULL has no gains to perturb)");
+    if (!a.Zout_dot) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zout_dot");
+    if (int rc = check_tracking_estimated_sweep_args(h, t, guarded, a.Lgain_dot != nullptr, w)) return rc;
+    const qln_dims& D = h->dims;
+    const int64_t nx = (int64_t)D.B * QLN_NX, nm = (int64_t)D.B * QLN_MODEL_NP, ne = (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
+    const bool wg = a.Lgain_dot != nullptr;
+    return check_no_overlap({{a.Zout_dot, D.z_total}, {a.Xhat_dot, (int64_t)D.B * D.N * QLN_NX},
+                             {a.innov_dot, tracking_meas_total(D, t.ny)}, {a.event_dot, ne}, {a.event_hat_dot, ne}},
+                            {QLN_ESTIMATED_TRAJ_SPANS(D, t, wg), {a.Zref_dot, D.z_total}, {a.K_dot, tracking_k_total(D)},
+                             {a.Lgain_dot, tracking_gain_total(D, t.ny)}, {a.x0_dot, nx}, {a.xhat0_dot, nx}, {a.model_dot, nm}}, w);
+}
+
+static int check_tracking_estimated_vjp_args(const qln_handle* h, const EstimatedTraj& t, bool guarded,
+                                             const qln::EstimatedVjpArgs& a, const char* who) {
+    const std::string w(who);
+    if (a.K_bar && !t.K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_bar needs K (K == NULL has no gains to differentiate)");
+    if (!a.Zbar) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zbar");
+    if (int rc = check_tracking_estimated_sweep_args(h, t, guarded, a.Lgain_bar != nullptr, w)) return rc;
+    const qln_dims& D = h->dims;
+    const int64_t nx = (int64_t)D.B * QLN_NX, nm = (int64_t)D.B * QLN_MODEL_NP;
+    const bool wg = a.Lgain_bar != nullptr;
+    return check_no_overlap({{a.Zref_bar, D.z_total}, {a.K_bar, tracking_k_total(D)}, {a.Lgain_bar, tracking_gain_total(D, t.ny)},
+                             {a.x0_bar, nx}, {a.xhat0_bar, nx}, {a.model_bar, nm}},
+                            {QLN_ESTIMATED_TRAJ_SPANS(D, t, wg), {a.Zbar, D.z_total}, {a.Xhat_bar, (int64_t)D.B * D.N * QLN_NX},
+                             {a.innov_bar, tracking_meas_total(D, t.ny)}}, w);
+}
+#undef QLN_ESTIMATED_TRAJ_SPANS
+
+static qln::EstimatedSweepIn estimated_sweep_in(const EstimatedTraj& t, bool guarded) {
+    return {t.Zref, t.K, t.Lgain, t.H, t.ny, t.model, t.Zout, t.Xhat, t.innov, guarded ? t.event : nullptr,
+            guarded ? t.event_hat : nullptr};
+}
+
+static int tracking_estimated_jvp(qln_handle* h, const EstimatedTraj& t, bool guarded, const qln::EstimatedJvpArgs& a,
+                                  const char* who) {
+    if (int rc = check_tracking_estimated_jvp_args(h, t, guarded, a, who)) return rc;
+    if (int rc = bind_device(h)) return rc;
+    QLN_HIP(qln::launch_tracking_rollout_estimated_jvp(h->p, estimated_sweep_in(t, guarded), a, h->stream));
+    return QLN_OK;
+}
+
+static int tracking_estimated_vjp(qln_handle* h, const EstimatedTraj& t, bool guarded, const qln::EstimatedVjpArgs& a,
+                                  const char* who) {
+    if (int rc = check_tracking_estimated_vjp_args(h, t, guarded, a, who)) return rc;
+    if (int rc = bind_device(h)) return rc;
+    QLN_HIP(qln::launch_tracking_rollout_estimated_vjp(h->p, estimated_sweep_in(t, guarded), a, h->stream));
+    return QLN_OK;
+}
+
+// host forms: what the device forms check, then the values of H, the models and the two records
+static int check_host_estimated_traj(const qln_handle* h, const EstimatedTraj& t, bool guarded, const char* who) {
+    for (int i = 0; i < t.ny * QLN_NX; ++i)
+        if (!std::isfinite(t.H[i]))
+            return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": H is not finite (entry " + std::to_string(i) + ")");
+    if (int rc = check_host_models(h, t.model, who)) return rc;
+    if (!guarded) return QLN_OK;
+    if (int rc = check_host_events(h, t.event, who)) return rc;
+    return check_host_events(h, t.event_hat, who);
+}
+
+// the arguments sized by the call's ny, of the roles' eight rows
+static HostArg sized(HostArg a, int64_t n) {
+    a.n = n;
+    return a;
+}
+
+// Zref is staged only when K_dot is given (the kernel reads it for nothing else); otherwise Zout's buffer stands in.  innov only
+// with Lgain_dot.
+static int tracking_estimated_jvp_host(qln_handle* h, const EstimatedTraj& t, bool guarded, const qln::EstimatedJvpArgs& a,
+                                       const char* who) {
+    if (int rc = check_tracking_estimated_jvp_args(h, t, guarded, a, who)) return rc;
+    if (int rc = check_host_estimated_traj(h, t, guarded, who)) return rc;
+    if (int rc = bind_device(h)) return rc;
+    const int64_t ng = tracking_gain_total(h->dims, t.ny), nm = tracking_meas_total(h->dims, t.ny);
+    return host_call(
+        h,
+        {copy_in(kV, t.Zout), copy_in(kZ, a.K_dot ? t.Zref : nullptr), copy_in(kK, t.K), sized(copy_in(kLgain, t.Lgain), ng),
+         sized(copy_in(kH, t.H), (int64_t)t.ny * QLN_NX), copy_in(kModel, t.model), copy_in(kXhat, t.Xhat),
+         sized(copy_in(kInnov, a.Lgain_dot ? t.innov : nullptr), nm), copy_in(kEvent, guarded ? t.event : nullptr),
+         copy_in(kEventHat, guarded ? t.event_hat : nullptr), copy_in(kZdot, a.Zref_dot), copy_in(kKdot, a.K_dot),
+         sized(copy_in(kLgainD, a.Lgain_dot), ng), copy_in(kX0, a.x0_dot), copy_in(kXhat0, a.xhat0_dot),
+         copy_in(kModelD, a.model_dot), copy_inout(kZio, a.Zout_dot), copy_out(kXhatD, a.Xhat_dot),
+         sized(copy_out(kInnovD, a.innov_dot), nm), copy_out(kEventD, guarded ? a.event_dot : nullptr),
+         copy_out(kEventHatD, guarded ? a.event_hat_dot : nullptr)},
+        [&](double* const* d, bool) {
+            const qln::EstimatedSweepIn in = {d[kZ] ? d[kZ] : d[kV], d[kK], d[kLgain], d[kH], t.ny, d[kModel], d[kV], d[kXhat],
+                                              d[kInnov], d[kEvent], d[kEventHat]};
+            const qln::EstimatedJvpArgs da = {d[kZdot], d[kKdot], d[kLgainD], d[kX0], d[kXhat0], d[kModelD], d[kZio], d[kXhatD],
+                                              d[kInnovD], d[kEventD], d[kEventHatD]};
+            return qln::launch_tracking_rollout_estimated_jvp(h->p, in, da, h->stream);
+        });
+}
+
+// Zref is staged only when K_bar asks for it; otherwise Zout's buffer stands in.  innov only with Lgain_bar.
+static int tracking_estimated_vjp_host(qln_handle* h, const EstimatedTraj& t, bool guarded, const qln::EstimatedVjpArgs& a,
+                                       const char* who) {
+    if (int rc = check_tracking_estimated_vjp_args(h, t, guarded, a, who)) return rc;
+    if (int rc = check_host_estimated_traj(h, t, guarded, who)) return rc;
+    if (int rc = bind_device(h)) return rc;
+    const int64_t ng = tracking_gain_total(h->dims, t.ny), nm = tracking_meas_total(h->dims, t.ny);
+    return host_call(
+        h,
+        {copy_in(kV, t.Zout), copy_in(kZ, a.K_bar ? t.Zref : nullptr), copy_in(kK, t.K), sized(copy_in(kLgain, t.Lgain), ng),
+         sized(copy_in(kH, t.H), (int64_t)t.ny * QLN_NX), copy_in(kModel, t.model), copy_in(kXhat, t.Xhat),
+         sized(copy_in(kInnov, a.Lgain_bar ? t.innov : nullptr), nm), copy_in(kEvent, guarded ? t.event : nullptr),
+         copy_in(kEventHat, guarded ? t.event_hat : nullptr), copy_in(kZbar, a.Zbar), copy_in(kXhatD, a.Xhat_bar),
+         sized(copy_in(kInnovD, a.innov_bar), nm), copy_inout(kZio, a.Zref_bar), copy_out(kKbar, a.K_bar),
+         sized(copy_out(kLgainD, a.Lgain_bar), ng), copy_out(kX0, a.x0_bar), copy_out(kXhat0, a.xhat0_bar),
+         copy_out(kModelD, a.model_bar)},
+        [&](double* const* d, bool) {
+            const qln::EstimatedSweepIn in = {d[kZ] ? d[kZ] : d[kV], d[kK], d[kLgain], d[kH], t.ny, d[kModel], d[kV], d[kXhat],
+                                              d[kInnov], d[kEvent], d[kEventHat]};
+            const qln::EstimatedVjpArgs da = {d[kZbar], d[kXhatD], d[kInnovD], d[kZio], d[kKbar], d[kLgainD], d[kX0], d[kXhat0],
+                                              d[kModelD]};
+            return qln::launch_tracking_rollout_estimated_vjp(h->p, in, da, h->stream);
+        });
+}
+
+int qln_tracking_rollout_estimated_jvp(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
+                                       int32_t ny, const double* model, const double* Zout, const double* Xhat,
+                                       const double* innov, const double* Zref_dot, const double* K_dot, const double* Lgain_dot,
+                                       const double* x0_dot, const double* xhat0_dot, const double* model_dot, double* Zout_dot,
+                                       double* Xhat_dot, double* innov_dot) {
+    return tracking_estimated_jvp(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, nullptr, nullptr}, false,
+                                  {Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, Zout_dot, Xhat_dot, innov_dot, nullptr,
+                                   nullptr},
+                                  "qln_tracking_rollout_estimated_jvp");
+}
+int qln_tracking_rollout_estimated_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                            const double* H, int32_t ny, const double* model, const double* Zout,
+                                            const double* Xhat, const double* innov, const double* Zref_dot, const double* K_dot,
+                                            const double* Lgain_dot, const double* x0_dot, const double* xhat0_dot,
+                                            const double* model_dot, double* Zout_dot, double* Xhat_dot, double* innov_dot) {
+    return tracking_estimated_jvp_host(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, nullptr, nullptr}, false,
+                                       {Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, Zout_dot, Xhat_dot, innov_dot,
+                                        nullptr, nullptr},
+                                       "qln_tracking_rollout_estimated_jvp_host");
+}
+int qln_tracking_rollout_estimated_guarded_jvp(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                               const double* H, int32_t ny, const double* model, const double* Zout,
+                                               const double* Xhat, const double* innov, const double* event,
+                                               const double* event_hat, const double* Zref_dot, const double* K_dot,
+                                               const double* Lgain_dot, const double* x0_dot, const double* xhat0_dot,
+                                               const double* model_dot, double* Zout_dot, double* Xhat_dot, double* innov_dot,
+                                               double* event_dot, double* event_hat_dot) {
+    return tracking_estimated_jvp(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, event, event_hat}, true,
+                                  {Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, Zout_dot, Xhat_dot, innov_dot,
+                                   event_dot, event_hat_dot},
+                                  "qln_tracking_rollout_estimated_guarded_jvp");
+}
+int qln_tracking_rollout_estimated_guarded_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                                    const double* H, int32_t ny, const double* model, const double* Zout,
+                                                    const double* Xhat, const double* innov, const double* event,
+                                                    const double* event_hat, const double* Zref_dot, const double* K_dot,
+                                                    const double* Lgain_dot, const double* x0_dot, const double* xhat0_dot,
+                                                    const double* model_dot, double* Zout_dot, double* Xhat_dot,
+                                                    double* innov_dot, double* event_dot, double* event_hat_dot) {
+    return tracking_estimated_jvp_host(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, event, event_hat}, true,
+                                       {Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, Zout_dot, Xhat_dot, innov_dot,
+                                        event_dot, event_hat_dot},
+                                       "qln_tracking_rollout_estimated_guarded_jvp_host");
+}
+int qln_tracking_rollout_estimated_vjp(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
+                                       int32_t ny, const double* model, const double* Zout, const double* Xhat,
+                                       const double* innov, const double* Zbar, const double* Xhat_bar, const double* innov_bar,
+                                       double* Zref_bar, double* K_bar, double* Lgain_bar, double* x0_bar, double* xhat0_bar,
+                                       double* model_bar) {
+    return tracking_estimated_vjp(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, nullptr, nullptr}, false,
+                                  {Zbar, Xhat_bar, innov_bar, Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar, model_bar},
+                                  "qln_tracking_rollout_estimated_vjp");
+}
+int qln_tracking_rollout_estimated_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                            const double* H, int32_t ny, const double* model, const double* Zout,
+                                            const double* Xhat, const double* innov, const double* Zbar, const double* Xhat_bar,
+                                            const double* innov_bar, double* Zref_bar, double* K_bar, double* Lgain_bar,
+                                            double* x0_bar, double* xhat0_bar, double* model_bar) {
+    return tracking_estimated_vjp_host(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, nullptr, nullptr}, false,
+                                       {Zbar, Xhat_bar, innov_bar, Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar, model_bar},
+                                       "qln_tracking_rollout_estimated_vjp_host");
+}
+int qln_tracking_rollout_estimated_guarded_vjp(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                               const double* H, int32_t ny, const double* model, const double* Zout,
+                                               const double* Xhat, const double* innov, const double* event,
+                                               const double* event_hat, const double* Zbar, const double* Xhat_bar,
+                                               const double* innov_bar, double* Zref_bar, double* K_bar, double* Lgain_bar,
+                                               double* x0_bar, double* xhat0_bar, double* model_bar) {
+    return tracking_estimated_vjp(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, event, event_hat}, true,
+                                  {Zbar, Xhat_bar, innov_bar, Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar, model_bar},
+                                  "qln_tracking_rollout_estimated_guarded_vjp");
+}
+int qln_tracking_rollout_estimated_guarded_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                                    const double* H, int32_t ny, const double* model, const double* Zout,
+                                                    const double* Xhat, const double* innov, const double* event,
+                                                    const double* event_hat, const double* Zbar, const double* Xhat_bar,
+                                                    const double* innov_bar, double* Zref_bar, double* K_bar, double* Lgain_bar,
+                                                    double* x0_bar, double* xhat0_bar, double* model_bar) {
+    return tracking_estimated_vjp_host(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, event, event_hat}, true,
+                                       {Zbar, Xhat_bar, innov_bar, Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar, model_bar},
+                                       "qln_tracking_rollout_estimated_guarded_vjp_host");
 }
 
 // ------------------------------------------------------------------ host-pointer (MOI) mode

@@ -341,6 +341,29 @@ hipError_t launch_tracking_rollout_estimated(const BatchParams& p, const double*
                                              const double* x0, const double* xhat0, const double* model, double* Zout,
                                              double* Xhat, double* innov, bool guarded, double* event, double* event_hat,
                                              hipStream_t stream);
+// The sweeps through the estimate-feedback roll-out (qln_tracking_rollout_estimated_jvp / _vjp, qln_tracking_kernels.hip).  What
+// both read: the roll-out's inputs and the trajectory it produced; event and event_hat (both or neither) select the guarded
+// blocks.  innov is read only with a tangent or cotangent of Lgain.
+struct EstimatedSweepIn {
+    const double *Zref, *K, *Lgain, *H;
+    int ny;
+    const double *model, *Zout, *Xhat, *innov, *event, *event_hat;
+};
+// the tangents (null: zero; xhat0_dot null: x_ref_dot,0) and the forward sweep's outputs (all but Zout_dot may be null)
+struct EstimatedJvpArgs {
+    const double *Zref_dot, *K_dot, *Lgain_dot, *x0_dot, *xhat0_dot, *model_dot;
+    double *Zout_dot, *Xhat_dot, *innov_dot, *event_dot, *event_hat_dot;
+};
+// the cotangents (Xhat_bar, innov_bar null: zero) and the reverse sweep's outputs (each may be null; xhat0_bar null: the
+// cotangent of xhat^-_0 is added to Zref_bar's x_0 slot)
+struct EstimatedVjpArgs {
+    const double *Zbar, *Xhat_bar, *innov_bar;
+    double *Zref_bar, *K_bar, *Lgain_bar, *x0_bar, *xhat0_bar, *model_bar;
+};
+hipError_t launch_tracking_rollout_estimated_jvp(const BatchParams& p, const EstimatedSweepIn& in, const EstimatedJvpArgs& a,
+                                                 hipStream_t stream);
+hipError_t launch_tracking_rollout_estimated_vjp(const BatchParams& p, const EstimatedSweepIn& in, const EstimatedVjpArgs& a,
+                                                 hipStream_t stream);
 // batched Gauss-Newton step on the constraint violation, CGLS per problem in LDS (qln_solver_kernels.hip)
 size_t gauss_newton_lds_bytes(int32_t N);
 hipError_t launch_gauss_newton_step(const BatchParams& p, const double* Z, const double* c, double* dZ, int max_iters,

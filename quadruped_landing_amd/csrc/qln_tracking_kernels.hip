@@ -82,6 +82,11 @@
 // k_tracking_rollout_estimated: the loop that filter designs, flown (qln_tracking_rollout_estimated / _guarded):
 // the plant and the estimator rolled out side by side in k_tracking_rollout's mapping, one lane per problem, on its step and its
 // guarded step, the forces fed back from the estimate and the noise read from the caller's samples.
+//
+// k_tracking_rollout_estimated_jvp / _vjp: the forward and reverse sweeps through that loop at fixed noise samples
+// (qln_tracking_rollout_estimated_jvp / _vjp and their _guarded forms), on the row-of-sixteen mapping of the
+// roll-out's own sweeps: a problem's two chains, the plant's along Zout and the estimator's along Xhat, each through
+// jvp_apply_row / vjp_apply_column, coupled by the measurement update (H from LDS, row j of L_k and column j of K_k per lane).
 #include "qln_row16.h"
 
 #include <utility>
@@ -2077,6 +2082,486 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, c
     }
 }
 
+// ---- k_tracking_rollout_estimated_jvp / _vjp ----
+// The sweeps through the estimate-feedback roll-out (qln_tracking_rollout_estimated_jvp / _vjp and their _guarded forms,
+// include/qln_evaluator.h), in the mapping of k_tracking_rollout_jvp / _vjp: one problem per row of sixteen
+// lanes.  A problem carries two chains, the plant's along Zout and the estimator's along Xhat, so lane j < 15 owns two
+// entries -- dx[j] and dxm[j] forward, lam[j] and lamm[j] in reverse -- and each knot applies two blocks: the plant's at
+// (x_k, u_k, model[b]) and the estimator's at (xhat_k, u_k, the handle's model), both through the siblings' jvp_apply_row /
+// vjp_apply_column, so that a chain of this sweep and the sibling sweep on the same trajectory give the same bits.
+// The measurement update couples the chains.  H is uniform over the batch and staged once per block in LDS; lane j reads
+// column j of it (conflict-free: consecutive lanes, consecutive words) and H (dx - dxm) is ny row sums.  Lane j reads row j
+// of L_k (ny consecutive doubles: the row's fifteen lanes cover the tile's 15 ny doubles as whole lines) and column j of K_k;
+// the sweeps take no RK4 step outside a touchdown knot, so nothing here is duplicated across the row's lanes but the blocks,
+// as in the siblings.  Loops over the sensor rows run to QLN_TRACK_NY_MAX under a uniform r < ny, so every value sits at a
+// compile-time position and a call with ny rows gives the bits of one with zero rows and columns behind them.
+// Every slice of a knot is loaded one knot ahead (EstimatedJvpKnot / EstimatedVjpKnot), what is uniform over the row -- the
+// controls, the innovations and their cotangents -- as one entry per lane, handed round by DPP row broadcasts when it is used;
+// loaded where they are used the kernels took 1.9 (forward; 2.9 guarded) and 1.7 to 1.8 times as long.  The two
+// chains' steps are kept apart by scheduling barriers: interleaved, two blocks' temporaries are live at once.
+
+// One chain's knot of the forward sweep: row j of [A B G] on (dx, dF, dh, md4).  kGuard: the guarded sweep's statement of the
+// knot (k_tracking_rollout_jvp), td saying that this is the chain's touchdown knot, with d tau and the clock's tangent left
+// in e_tau / e_clock there.
+template <bool kGuard, bool kModel>
+__device__ __forceinline__ double estimated_jvp_step(int j, bool own, const double (&x)[14], double F1x, double F1y, double F2x,
+                                                     double F2y, double h, const KnotMode md, bool td, double tau, const Model& M,
+                                                     double dx, const double (&dF)[4], double dh, bool want_model,
+                                                     const double (&md4)[QLN_MODEL_NP], double& e_tau, double& e_clock) {
+    if constexpr (!kGuard) {
+        const StepBlock blk = step_block(x, F1x, F1y, F2x, F2y, h, md, M);
+        return jvp_apply_row<true, true, kModel>(j, own, blk, x, F1x, F1y, F2x, F2y, h, md, M, dx, dF, dh, true, want_model, md4);
+    } else {
+        double hA = h, dhA = dh, dtau = 0.0;
+        double xm[15];
+        if (td) {
+            const bool f2 = md.f2free;  // mode 1: foot 2 is the free one
+            double xk[15];
+#pragma unroll
+            for (int i = 0; i < 14; ++i) xk[i] = x[i];
+            xk[14] = 0.0;  // the clock feeds nothing
+            const double u5[5] = {F1x, F1y, F2x, F2y, h};
+            step_mode(M, md, tau, xk, u5, xm);
+            const double y = f2 ? x[6] : x[4], Fy = f2 ? F2y : F1y, w = f2 ? xm[13] : xm[11];
+            const double dy4 = row_bcast<4>(dx), dy6 = row_bcast<6>(dx), dv11 = row_bcast<11>(dx), dv13 = row_bcast<13>(dx);
+            const double dy = f2 ? dy6 : dy4, dv = f2 ? dv13 : dv11, dFy = f2 ? dF[3] : dF[1];
+            const double da = (-dFy / M.mf + (Fy / (M.mf * M.mf)) * md4[2]) + md4[0];
+            dtau = (y <= 0.0) ? 0.0 : -((dy + tau * dv) + (0.5 * tau * tau) * da) / w;
+            e_tau = dtau;
+            e_clock = row_bcast<14>(dx) + dtau;
+            hA = tau;
+            dhA = dtau;
+        }
+        StepBlock blk = step_block(x, F1x, F1y, F2x, F2y, hA, md, M);
+        double acc = jvp_apply_row<true, true, kModel>(j, own, blk, x, F1x, F1y, F2x, F2y, hA, md, M, dx, dF, dhA, true, want_model,
+                                                       md4);
+        if (td) {
+            const bool jrow = j == 4 || j == 6 || (j >= 10 && j <= 13);
+            const double dxj = (own && !jrow) ? acc : 0.0;  // the jump map
+            jump_map(xm);
+            double xp[14];
+#pragma unroll
+            for (int i = 0; i < 14; ++i) xp[i] = xm[i];
+            const KnotMode m3 = {false, false, false, true};
+            blk = step_block(xp, F1x, F1y, F2x, F2y, h - tau, m3, M);
+            acc = jvp_apply_row<true, true, kModel>(j, own, blk, xp, F1x, F1y, F2x, F2y, h - tau, m3, M, dxj, dF, dh - dtau, true,
+                                                    want_model, md4);
+        }
+        return acc;
+    }
+}
+
+// One knot's inputs of the forward sweep, as lane ln of a row loads them: row j of L_k and of Ldot_k, and ivl: entry ln of innov_k
+// (lanes behind ny repeat the last; handed round by DPP row broadcasts), for every knot;
+// z0 / z1 / zd0 / zd1 as in JvpKnot, xh: xhat_k[j], xr: x_ref,j, kc, kd: column j of K_k and of Kdot_k (the knots with a step).
+struct EstimatedJvpKnot {
+    double l[QLN_TRACK_NY_MAX], ld[QLN_TRACK_NY_MAX], ivl;
+    double z0, z1, xh, zd0, zd1, xr, kc[4], kd[4];
+};
+
+// The forward sweep (include/qln_evaluator.h): dx_0 = x0_dot, dxm_0 = xhat0_dot (null: x_ref_dot,0), then per knot
+//   dinnov = H (dx - dxm),  dxh = dxm + L_k dinnov + Ldot_k innov_k                                  (k = 0 .. N-1)
+//   dF = Fref_dot - K_k (dxh - xref_dot) - Kdot_k (xhat_k - x_ref,k),  dh = href_dot                 (k < N-1)
+//   dx' = A^p dx + B^p (dF, dh) + G^p model_dot,   dxm' = A^e dxh + B^e (dF, dh)
+// kHasK: K is given (K_dot is a run-time argument of that path); kHasLd: Lgain_dot is, and innov with it.
+template <bool kGuard, bool kHasK, bool kHasLd>
+__global__ __launch_bounds__(kWave) void k_tracking_rollout_estimated_jvp(BatchParams P, EstimatedSweepIn in, EstimatedJvpArgs a) {
+    constexpr int NY = QLN_TRACK_NY_MAX;
+    __shared__ double Hs[NY * 15];
+    const int ny = in.ny;
+    for (int i = threadIdx.x; i < 15 * ny; i += kWave) Hs[i] = in.H[i];
+    __syncthreads();
+    const Row16 r16 = row16_of(P);  // lane 15 reads lane 14's slots and contributes nothing
+    const int ln = r16.ln, j = r16.j, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
+    const bool own = r16.own, valid = r16.valid;
+    const Model M = plant_model<true>(P, in.model, bc);   // the plant's
+    const Model Mh = plant_model<true>(P, nullptr, bc);   // the estimator's: always the handle's
+    const int64_t zo = (int64_t)bc * P.z_stride, ko = (int64_t)bc * (N - 1) * (QLN_TRACK_NU * QLN_NX);
+    const int64_t xo = (int64_t)bc * N * QLN_NX, go = xo * ny, io = (int64_t)bc * N * ny;
+    const double* __restrict__ Zo = in.Zout + zo;
+    const double* __restrict__ Xh = in.Xhat + xo;
+    const double* __restrict__ Zd = a.Zref_dot ? a.Zref_dot + zo : nullptr;
+    const double* __restrict__ Zr = a.K_dot ? in.Zref + zo : nullptr;
+    const double* __restrict__ Kb = kHasK ? in.K + ko : nullptr;
+    const double* __restrict__ Kdb = (kHasK && a.K_dot) ? a.K_dot + ko : nullptr;
+    const double* __restrict__ Lb = in.Lgain + go + (int64_t)j * ny;
+    const double* __restrict__ Ldb = kHasLd ? a.Lgain_dot + go + (int64_t)j * ny : nullptr;
+    const double* __restrict__ Ib = kHasLd ? in.innov + io : nullptr;
+    double* __restrict__ Od = a.Zout_dot + zo;
+    [[maybe_unused]] int ks = -1, ksh = -1;
+    [[maybe_unused]] double tau = 0.0, tauh = 0.0;
+    double e_tau = 0.0, e_clock = 0.0, eh_tau = 0.0, eh_clock = 0.0;
+    if constexpr (kGuard) {
+        ks = guard_knot(in.event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc], N);
+        tau = in.event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + 1];
+        ksh = guard_knot(in.event_hat[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc], N);
+        tauh = in.event_hat[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + 1];
+    }
+    double md4[QLN_MODEL_NP] = {0.0, 0.0, 0.0, 0.0};
+    const double zero4[QLN_MODEL_NP] = {0.0, 0.0, 0.0, 0.0};  // the estimator's model has no tangent
+    if (a.model_dot) {
+#pragma unroll
+        for (int q = 0; q < QLN_MODEL_NP; ++q) md4[q] = a.model_dot[(int64_t)bc * QLN_MODEL_NP + q];
+    }
+    double* __restrict__ Xd = a.Xhat_dot ? a.Xhat_dot + xo : nullptr;
+    double* __restrict__ Ido = a.innov_dot ? a.innov_dot + io : nullptr;
+    double dx = (own && a.x0_dot) ? a.x0_dot[(int64_t)bc * QLN_NX + j] : 0.0;
+    double dxm = !own ? 0.0 : a.xhat0_dot ? a.xhat0_dot[(int64_t)bc * QLN_NX + j] : Zd ? Zd[j] : 0.0;
+    // the knot's slices are loaded one knot ahead: the gains' rows for every knot, the rest for the knots that take a step
+    auto load = [&](EstimatedJvpKnot& s, int k) {
+        const double* __restrict__ Lk = Lb + (int64_t)k * (15 * ny);
+#pragma unroll
+        for (int r = 0; r < NY; ++r) s.l[r] = r < ny ? Lk[r] : 0.0;
+        if constexpr (kHasLd) {
+            const double* __restrict__ Ldk = Ldb + (int64_t)k * (15 * ny);
+            const double* __restrict__ ik = Ib + (int64_t)k * ny;
+#pragma unroll
+            for (int r = 0; r < NY; ++r) s.ld[r] = r < ny ? Ldk[r] : 0.0;
+            s.ivl = ik[min(ln, ny - 1)];
+        }
+        if (k == N - 1) return;
+        knot_load(Zo + 20 * k, ln, s.z0, s.z1);
+        s.xh = Xh[(int64_t)k * QLN_NX + j];
+        if (Zd) knot_load(Zd + 20 * k, ln, s.zd0, s.zd1);
+        if constexpr (kHasK) {
+#pragma unroll
+            for (int m = 0; m < 4; ++m) s.kc[m] = Kb[60 * (int64_t)k + 15 * m + j];
+            if (Kdb) {
+                s.xr = Zr[20 * k + j];
+#pragma unroll
+                for (int m = 0; m < 4; ++m) s.kd[m] = Kdb[60 * (int64_t)k + 15 * m + j];
+            }
+        }
+    };
+    EstimatedJvpKnot cur = {}, nxt = {};
+    load(nxt, 0);
+    for (int k = 0; k < N; ++k) {
+        cur = nxt;
+        if (k + 1 < N) load(nxt, k + 1);
+        // ---- the measurement update's tangent ----
+        const double dd = dx - dxm;
+        double din[NY];
+#pragma unroll
+        for (int r = 0; r < NY; ++r) {
+            din[r] = 0.0;
+            if (r < ny) din[r] = row_sum16(own ? Hs[15 * r + j] * dd : 0.0);
+        }
+        double dxh = dxm;
+#pragma unroll
+        for (int r = 0; r < NY; ++r)
+            if (r < ny) dxh = fma(cur.l[r], din[r], dxh);
+        if constexpr (kHasLd) {
+            double iv[NY];
+            row_bcast_first(cur.ivl, iv, std::make_integer_sequence<int, NY>{});
+#pragma unroll
+            for (int r = 0; r < NY; ++r)
+                if (r < ny) dxh = fma(cur.ld[r], iv[r], dxh);
+        }
+        dxh = own ? dxh : 0.0;
+        if (valid) {
+            if (Xd && own) Xd[(int64_t)k * QLN_NX + j] = dxh;
+            if (Ido && ln < ny) {
+                double o = din[0];
+#pragma unroll
+                for (int r = 1; r < NY; ++r) o = (ln == r) ? din[r] : o;
+                Ido[(int64_t)k * ny + ln] = o;
+            }
+        }
+        if (k == N - 1) break;
+        // ---- the knot's states and controls, in every lane ----
+        const double z0 = cur.z0, z1 = cur.z1, xhj = cur.xh;
+        double x[14], xe[14];
+        row_bcast_first(z0, x, std::make_integer_sequence<int, 14>{});
+        const double F1x = row_bcast<15>(z0), F1y = row_bcast<0>(z1), F2x = row_bcast<1>(z1), F2y = row_bcast<2>(z1),
+                     h = row_bcast<3>(z1);
+        // ---- the applied controls' tangent ----
+        double dF[4] = {0.0, 0.0, 0.0, 0.0}, dh = 0.0, xrd = 0.0;
+        if (Zd) {
+            xrd = cur.zd0;
+            dF[0] = row_bcast<15>(cur.zd0);
+            dF[1] = row_bcast<0>(cur.zd1);
+            dF[2] = row_bcast<1>(cur.zd1);
+            dF[3] = row_bcast<2>(cur.zd1);
+            dh = row_bcast<3>(cur.zd1);
+        }
+        if constexpr (kHasK) {
+            const double d = dxh - xrd;
+            const double e = Kdb ? xhj - cur.xr : 0.0;
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                double t = cur.kc[m] * d;
+                if (Kdb) t = fma(cur.kd[m], e, t);
+                dF[m] = dF[m] - row_sum16(own ? t : 0.0);
+            }
+        }
+        // ---- the two chains' steps, one after the other: two blocks live at once do not fit the registers ----
+        KnotMode md, mdh;
+        if constexpr (kGuard) {
+            md = guard_mode(k, ks, im);
+            mdh = guard_mode(k, ksh, im);
+        } else {
+            md = mdh = knot_mode(k + 1, kt - 1, im);
+        }
+        const double accp = estimated_jvp_step<kGuard, true>(j, own, x, F1x, F1y, F2x, F2y, h, md, k == ks, tau, M, dx, dF, dh,
+                                                             a.model_dot != nullptr, md4, e_tau, e_clock);
+        __builtin_amdgcn_sched_barrier(0);
+        row_bcast_first(xhj, xe, std::make_integer_sequence<int, 14>{});
+        const double acce = estimated_jvp_step<kGuard, false>(j, own, xe, F1x, F1y, F2x, F2y, h, mdh, k == ksh, tauh, Mh, dxh, dF, dh,
+                                                              false, zero4, eh_tau, eh_clock);
+        __builtin_amdgcn_sched_barrier(0);
+        if (valid) knot_store(Od + 20 * k, r16, dx, {dF[0], dF[1], dF[2], dF[3], dh});
+        dx = own ? accp : 0.0;
+        dxm = own ? acce : 0.0;
+    }
+    if (valid && own) Od[20 * (N - 1) + j] = dx;
+    if constexpr (kGuard) {
+        if (valid && ln < QLN_TOUCHDOWN_INFO_STRIDE) {
+            if (a.event_dot) a.event_dot[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + ln] = (ln == 1) ? e_tau : (ln == 2) ? e_clock : 0.0;
+            if (a.event_hat_dot)
+                a.event_hat_dot[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + ln] = (ln == 1) ? eh_tau : (ln == 2) ? eh_clock : 0.0;
+        }
+    }
+}
+
+// One knot's inputs of the reverse sweep, as lane ln of a row loads them: row j of L_k, ivl / ibl: entry ln of innov_k and of
+// innov_bar_k, xhb: Xhat_bar_k[j] and zb0: Zbar's entry ln of the knot (every knot); z0 / z1 and zb0 / zb1 as in JvpKnot, of Zout
+// and of Zbar, xh: xhat_k[j], xr: x_ref,j, kc: column j of K_k (the knots with a step).
+struct EstimatedVjpKnot {
+    double l[QLN_TRACK_NY_MAX], ivl, ibl, xhb;
+    double z0, z1, zb0, zb1, xh, xr, kc[4];
+};
+
+// One chain's knot of the reverse sweep: column j of [A B G]' on lam; returns (A'lam)[j], ub = ub0 + (B'lam, the h column's
+// product), and (kModel) adds to mbar.  kGuard: the guarded reverse sweep's statement of the knot (k_tracking_rollout_vjp),
+// td saying that this is the chain's touchdown knot; the estimator's chain (kModel false) has no model cotangent to hand
+// tau's to.
+template <bool kGuard, bool kModel>
+__device__ __forceinline__ double estimated_vjp_step(const VjpLane& lc, const double (&e)[4], const double (&sg)[4], int ln, bool own,
+                                                     double xj, double F0, double F1, double F2, double F3, double h,
+                                                     const KnotMode& md, bool td, double tau, const Model& M, double lam,
+                                                     bool want_mbar, double (&mbar)[QLN_MODEL_NP], const double (&ub0)[5],
+                                                     double (&ub)[5]) {
+    if constexpr (!kGuard) {
+        return vjp_apply_column<kModel>(lc, e, sg, xj, F0, F1, F2, F3, h, md, M, lam, want_mbar, mbar, ub0, ub);
+    } else {
+        const int j = lc.j;
+        double lamA = lam, hA = h, hb3 = 0.0, w = 1.0, y = 0.0;
+        double ubA[5] = {ub0[0], ub0[1], ub0[2], ub0[3], ub0[4]};
+        if (td) {
+            double xk[15], xm[15];
+            row_bcast_first(xj, xk, std::make_integer_sequence<int, 15>{});
+            const double u5[5] = {F0, F1, F2, F3, h};
+            step_mode(M, md, tau, xk, u5, xm);
+            y = md.f2free ? xk[6] : xk[4];
+            w = md.f2free ? xm[13] : xm[11];
+            jump_map(xm);
+            // the mode-3 leg at (x+, F, h - tau)
+            ubA[4] = 0.0;
+            double ub3[5];
+            const double a3 = vjp_apply_column<kModel>(lc, e, sg, pick15(xm, j), F0, F1, F2, F3, h - tau,
+                                                       KnotMode{false, false, false, true}, M, lam, want_mbar, mbar, ubA, ub3);
+#pragma unroll
+            for (int m = 0; m < 4; ++m) ubA[m] = ub3[m];
+            hb3 = ub3[4];
+            lamA = (own && !lc.jrow) ? a3 : 0.0;  // the jump map
+            hA = tau;
+        }
+        double alam = vjp_apply_column<kModel>(lc, e, sg, xj, F0, F1, F2, F3, hA, md, M, lamA, want_mbar, mbar, ubA, ub);
+        if (td) {
+            // tau's cotangent, and d tau = -(dy + tau dv + tau^2/2 da) / w with da = -dF_y / mf + F_y / mf^2 dmf + dg
+            const double taubar = ub[4] - hb3;
+            ub[4] = ub0[4] + hb3;
+            const bool f2 = md.f2free;
+            const double cw = (y <= 0.0) ? 0.0 : -taubar / w, ca = cw * (0.5 * tau * tau);
+            const int iy = f2 ? 6 : 4, iv = f2 ? 13 : 11;
+            alam = (j == iy) ? alam + cw : (j == iv) ? fma(cw, tau, alam) : alam;
+            const double Fy = f2 ? F3 : F1, cf = -ca / M.mf;
+            ub[1] = f2 ? ub[1] : ub[1] + cf;
+            ub[3] = f2 ? ub[3] + cf : ub[3];
+            if constexpr (kModel) {
+                if (ln == 0) {
+                    mbar[0] += ca;
+                    mbar[2] = fma(ca, Fy / (M.mf * M.mf), mbar[2]);
+                }
+            }
+        }
+        return alam;
+    }
+}
+
+// lane j's constant pattern at the model M (k_tracking_rollout_vjp forms the same before its loop)
+__device__ __forceinline__ VjpLane vjp_lane(int j, const Model& M) {
+    const bool pos = j < 7;
+    const int p = pos ? j : j - 7;
+    const int foot = (p == 3 || p == 4) ? 1 : (p == 5 || p == 6) ? 2 : 0;
+    const bool jrow = j == 4 || j == 6 || (j >= 10 && j <= 13);
+    const bool cpl = j >= 7 && j <= 13;
+    const bool kcpl = j == 11 || j == 13;
+    const double g = M.g, imb = 1.0 / M.mb, imf = 1.0 / M.mf;
+    const double iIb = 12.0 / (M.mb * (M.lb * M.lb));
+    const double inv = (p <= 1) ? imb : foot ? -imf : 0.0;
+    const double gy = (p == 1 || p == 4 || p == 6) ? g : (j == 14) ? 1.0 : 0.0;
+    return {j, pos, foot, jrow, cpl, kcpl, inv, gy, g, iIb};
+}
+
+// The reverse sweep (include/qln_evaluator.h), the exact transpose of the forward one: lam (of dx) and lamm (of dxm) start at
+// zero behind the last knot, and per knot k = N-1 .. 0
+//   k < N-1:  ubar = Zbar[u_k] + B^p'lam + B^e'lamm,  ax = A^p'lam,  model_bar += G^p'lam,
+//             xhb = Xhat_bar_k + A^e'lamm - K_k'ubar[0:4]                                   (k = N-1: ax = 0, xhb = Xhat_bar_k)
+//   ib = innov_bar_k + L_k'xhb,   Lbar_k = xhb innov_k',   lam = Zbar[x_k] + ax + H'ib,   lamm = xhb - H'ib
+// with Zref_bar[x_k] = K_k'ubar[0:4], Zref_bar[u_k] = ubar, Kbar_k = -ubar[0:4] (xhat_k - x_ref,k)'.  The plant's chain is applied
+// first, onto Zbar[u_k], as k_tracking_rollout_vjp applies it; the estimator's adds to it.
+// kHasK: K is given; kHasLb: Lgain_bar is asked for, and innov given with it.
+template <bool kGuard, bool kHasK, bool kHasLb>
+__global__ __launch_bounds__(kWave) void k_tracking_rollout_estimated_vjp(BatchParams P, EstimatedSweepIn in, EstimatedVjpArgs a) {
+    constexpr int NY = QLN_TRACK_NY_MAX;
+    __shared__ double Hs[NY * 15];
+    const int ny = in.ny;
+    for (int i = threadIdx.x; i < 15 * ny; i += kWave) Hs[i] = in.H[i];
+    __syncthreads();
+    const Row16 r16 = row16_of(P);  // lane 15 reads lane 14's slots and contributes nothing
+    const int ln = r16.ln, j = r16.j, b = r16.b, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
+    const bool own = r16.own, valid = r16.valid;
+    const Model M = plant_model<true>(P, in.model, bc);
+    const Model Mh = plant_model<true>(P, nullptr, bc);
+    const int64_t zo = (int64_t)bc * P.z_stride, ko = (int64_t)bc * (N - 1) * (QLN_TRACK_NU * QLN_NX);
+    const int64_t xo = (int64_t)bc * N * QLN_NX, go = xo * ny, io = (int64_t)bc * N * ny;
+    const double* __restrict__ Zo = in.Zout + zo;
+    const double* __restrict__ Zb = a.Zbar + zo;
+    const double* __restrict__ Xh = in.Xhat + xo;
+    const double* __restrict__ Zr = a.K_bar ? in.Zref + zo : nullptr;
+    const double* __restrict__ Kb = kHasK ? in.K + ko : nullptr;
+    const double* __restrict__ Lb = in.Lgain + go + (int64_t)j * ny;
+    const double* __restrict__ Ib = kHasLb ? in.innov + io : nullptr;
+    [[maybe_unused]] int ks = -1, ksh = -1;
+    [[maybe_unused]] double tau = 0.0, tauh = 0.0;
+    if constexpr (kGuard) {
+        ks = guard_knot(in.event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc], N);
+        tau = in.event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + 1];
+        ksh = guard_knot(in.event_hat[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc], N);
+        tauh = in.event_hat[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + 1];
+    }
+    // ---- lane j's constant pattern, at each chain's model; the sign patterns are the models' alike ----
+    const VjpLane lc = vjp_lane(j, M), lch = vjp_lane(j, Mh);
+    const int p = lc.pos ? j : j - 7;
+    double e[4], sg[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        e[m] = ((p <= 1 && (m == p || m == p + 2)) || (lc.foot && m == p - 3)) ? 1.0 : 0.0;
+        sg[m] = 0.0;
+    }
+    if (p == 0) sg[1] = sg[3] = -1.0;
+    if (p == 1) sg[0] = sg[2] = 1.0;
+    if (p == 3) sg[1] = 1.0;
+    if (p == 4) sg[0] = -1.0;
+    if (p == 5) sg[3] = 1.0;
+    if (p == 6) sg[2] = -1.0;
+
+    double mbar[QLN_MODEL_NP] = {0.0, 0.0, 0.0, 0.0};   // lane j's share of model_bar
+    double none[QLN_MODEL_NP] = {0.0, 0.0, 0.0, 0.0};   // the estimator's model has no cotangent
+    double lam = 0.0, lamm = 0.0;
+    // the knot's slices are loaded one knot ahead: the gains' row and the cotangents for every knot, the rest for the knots that
+    // take a step
+    const double* __restrict__ Xhb = a.Xhat_bar ? a.Xhat_bar + xo : nullptr;
+    const double* __restrict__ Ibb = a.innov_bar ? a.innov_bar + io : nullptr;
+    auto load = [&](EstimatedVjpKnot& s, int k) {
+        const double* __restrict__ Lk = Lb + (int64_t)k * (15 * ny);
+#pragma unroll
+        for (int r = 0; r < NY; ++r) s.l[r] = r < ny ? Lk[r] : 0.0;
+        if constexpr (kHasLb) s.ivl = Ib[(int64_t)k * ny + min(ln, ny - 1)];
+        if (Ibb) s.ibl = Ibb[(int64_t)k * ny + min(ln, ny - 1)];
+        if (Xhb) s.xhb = Xhb[(int64_t)k * QLN_NX + j];
+        if (k == N - 1) {
+            s.zb0 = Zb[20 * k + j];  // the last knot has no controls
+            return;
+        }
+        knot_load(Zo + 20 * k, ln, s.z0, s.z1);
+        knot_load(Zb + 20 * k, ln, s.zb0, s.zb1);
+        s.xh = Xh[(int64_t)k * QLN_NX + j];
+        if constexpr (kHasK) {
+#pragma unroll
+            for (int m = 0; m < 4; ++m) s.kc[m] = Kb[60 * (int64_t)k + 15 * m + j];
+        }
+        if (Zr) s.xr = Zr[20 * k + j];
+    };
+    EstimatedVjpKnot cur = {}, nxt = {};
+    load(nxt, N - 1);
+    for (int k = N - 1; k >= 0; --k) {
+        cur = nxt;
+        if (k > 0) load(nxt, k - 1);
+        double xhb = (own && Xhb) ? cur.xhb : 0.0;
+        double ax = 0.0, kub = 0.0;
+        double ub[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        if (k < N - 1) {
+            const double xj = own ? cur.z0 : row_bcast<14>(cur.z0), xhj = cur.xh;
+            const double u[5] = {row_bcast<15>(cur.z0), row_bcast<0>(cur.z1), row_bcast<1>(cur.z1), row_bcast<2>(cur.z1),
+                                 row_bcast<3>(cur.z1)};
+            const double ubz[5] = {row_bcast<15>(cur.zb0), row_bcast<0>(cur.zb1), row_bcast<1>(cur.zb1), row_bcast<2>(cur.zb1),
+                                   row_bcast<3>(cur.zb1)};
+            double ubp[5];
+            KnotMode md, mdh;
+            if constexpr (kGuard) {
+                md = guard_mode(k, ks, im);
+                mdh = guard_mode(k, ksh, im);
+            } else {
+                md = mdh = knot_mode(k + 1, kt - 1, im);
+            }
+            ax = estimated_vjp_step<kGuard, true>(lc, e, sg, ln, own, xj, u[0], u[1], u[2], u[3], u[4], md, k == ks, tau, M, lam,
+                                                  a.model_bar != nullptr, mbar, ubz, ubp);
+            __builtin_amdgcn_sched_barrier(0);  // one chain after the other: two knots' temporaries at once do not fit
+            const double axh = estimated_vjp_step<kGuard, false>(lch, e, sg, ln, own, xhj, u[0], u[1], u[2], u[3], u[4], mdh, k == ksh,
+                                                                 tauh, Mh, lamm, false, none, ubp, ub);
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (kHasK) kub = ((cur.kc[0] * ub[0] + cur.kc[1] * ub[1]) + cur.kc[2] * ub[2]) + cur.kc[3] * ub[3];
+            xhb = own ? (xhb + axh) - kub : 0.0;
+            if (kHasK && a.K_bar && valid && own) {
+                double* __restrict__ o = a.K_bar + ((int64_t)b * (N - 1) + k) * (QLN_TRACK_NU * QLN_NX);
+                const double dxr = xhj - cur.xr;
+#pragma unroll
+                for (int m = 0; m < 4; ++m) o[15 * m + j] = -ub[m] * dxr;
+            }
+        }
+        // ---- the measurement update, transposed ----
+        [[maybe_unused]] double iv[NY], ibr[NY];
+        if constexpr (kHasLb) row_bcast_first(cur.ivl, iv, std::make_integer_sequence<int, NY>{});
+        if (Ibb) row_bcast_first(cur.ibl, ibr, std::make_integer_sequence<int, NY>{});
+        double hib = 0.0;
+#pragma unroll
+        for (int r = 0; r < NY; ++r) {
+            if (r < ny) {
+                double ib = row_sum16(own ? cur.l[r] * xhb : 0.0);
+                if (Ibb) ib = ibr[r] + ib;
+                hib = fma(Hs[15 * r + j], ib, hib);
+                if constexpr (kHasLb) {
+                    if (valid && own) a.Lgain_bar[((int64_t)b * N + k) * (15 * ny) + (int64_t)j * ny + r] = xhb * iv[r];
+                }
+            }
+        }
+        const double zbx = own ? cur.zb0 : 0.0;
+        lam = own ? (zbx + ax) + hib : 0.0;
+        lamm = own ? xhb - hib : 0.0;
+        if (valid && a.Zref_bar) {
+            double* __restrict__ zk = a.Zref_bar + (int64_t)b * P.z_stride + 20 * k;
+            const double x0slot = (k == 0 && !a.xhat0_bar) ? kub + lamm : kub;  // xhat0 == NULL: xhat^-_0 is x_ref,0
+            if (k < N - 1) knot_store(zk, r16, x0slot, ub);
+            else if (own) zk[j] = x0slot;
+        }
+    }
+    if (valid && own) {
+        if (a.x0_bar) a.x0_bar[(int64_t)b * QLN_NX + j] = lam;
+        if (a.xhat0_bar) a.xhat0_bar[(int64_t)b * QLN_NX + j] = lamm;
+    }
+    if (a.model_bar) {
+        double out = 0.0;
+#pragma unroll
+        for (int q = 0; q < QLN_MODEL_NP; ++q) {
+            const double sq = row_sum16(mbar[q]);
+            out = (ln == q) ? sq : out;
+        }
+        if (valid && ln < QLN_MODEL_NP) a.model_bar[(int64_t)b * QLN_MODEL_NP + ln] = out;
+    }
+}
+
 }  // namespace
 
 // event (the guarded roll-out's records) sends the Riccati and the covariance sweep to their kGuard instantiations, which exist
@@ -2238,6 +2723,50 @@ hipError_t launch_tracking_rollout_estimated(const BatchParams& p, const double*
                            wnoise, x0, xhat0, model, Zout, Xhat, innov, event, event_hat);
     };
     guarded ? go(k_tracking_rollout_estimated<true>) : go(k_tracking_rollout_estimated<false>);
+    return hipGetLastError();
+}
+
+// The sweeps through it: eight instantiations each -- the knot schedule or the guard (both event records given), K or not,
+// and a tangent / cotangent of Lgain or not; every other optional argument is a run-time one.
+static bool estimated_sweep_in_ok(const EstimatedSweepIn& in) {
+    return in.ny >= 1 && in.ny <= QLN_TRACK_NY_MAX && in.Zref && in.Lgain && in.H && in.Zout && in.Xhat &&
+           (in.event != nullptr) == (in.event_hat != nullptr);
+}
+
+hipError_t launch_tracking_rollout_estimated_jvp(const BatchParams& p, const EstimatedSweepIn& in, const EstimatedJvpArgs& a,
+                                                 hipStream_t stream) {
+    if (!estimated_sweep_in_ok(in) || !a.Zout_dot) return hipErrorInvalidValue;
+    if ((a.K_dot && !in.K) || (a.Lgain_dot && !in.innov)) return hipErrorInvalidValue;
+    if (!in.event && (a.event_dot || a.event_hat_dot)) return hipErrorInvalidValue;
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, in, a); };
+    auto pick = [&](auto guard, auto hasK) {
+        a.Lgain_dot ? go(k_tracking_rollout_estimated_jvp<guard(), hasK(), true>)
+                    : go(k_tracking_rollout_estimated_jvp<guard(), hasK(), false>);
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (in.event)
+        in.K ? pick(yes, yes) : pick(yes, no);
+    else
+        in.K ? pick(no, yes) : pick(no, no);
+    return hipGetLastError();
+}
+
+hipError_t launch_tracking_rollout_estimated_vjp(const BatchParams& p, const EstimatedSweepIn& in, const EstimatedVjpArgs& a,
+                                                 hipStream_t stream) {
+    if (!estimated_sweep_in_ok(in) || !a.Zbar) return hipErrorInvalidValue;
+    if ((a.K_bar && !in.K) || (a.Lgain_bar && !in.innov)) return hipErrorInvalidValue;
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, in, a); };
+    auto pick = [&](auto guard, auto hasK) {
+        a.Lgain_bar ? go(k_tracking_rollout_estimated_vjp<guard(), hasK(), true>)
+                    : go(k_tracking_rollout_estimated_vjp<guard(), hasK(), false>);
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (in.event)
+        in.K ? pick(yes, yes) : pick(yes, no);
+    else
+        in.K ? pick(no, yes) : pick(no, no);
     return hipGetLastError();
 }
 

@@ -1277,6 +1277,158 @@ class HybridNLP:
         _lib.check(_lib.lib().qln_tracking_rollout_estimated_guarded_host(*args, _host_ptr(ev), _host_ptr(eh)))
         return out, Xh, iv, ev, eh
 
+    # -- forward and reverse sweeps through the estimate-feedback roll-out ----------------------------
+    def _estimated_traj(self, Zref, K, Lgain, H, Zout, Xhat, innov, model, guarded, events, events_hat, want_gain):
+        """The arguments both sweeps share, checked: (ny, the C arguments up to innov / event_hat, what must stay alive)."""
+        T = _torch()
+        Hh = self._measurement_rows(H)
+        ny = Hh.shape[0]
+        Hd = T.from_numpy(Hh).to(self._dev())
+        zr = self._check(Zref, self.dims.z_total, "Zref")
+        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        if Lgain is None or Xhat is None:
+            raise ValueError("Lgain and Xhat are required: the filter gains and the estimates tracking_rollout_estimated returned")
+        lp = self._check(Lgain, self.B * self.N * n * ny, "Lgain")
+        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
+        zo = self._check(Zout, self.dims.z_total, "Zout")
+        xh = self._check(Xhat, self.B * self.N * n, "Xhat")
+        if want_gain and innov is None:
+            raise ValueError("innov is required with a tangent or cotangent of Lgain (with_innovations=True in the roll-out)")
+        ip = self._check_opt(innov if want_gain else None, self.B * self.N * ny, "innov")
+        args = [self._h, zr, kp, lp, C.c_void_p(Hd.data_ptr()), ny, mp, zo, xh, ip]
+        if guarded:
+            if events is None or events_hat is None:
+                raise ValueError("events and events_hat are required: the two records tracking_rollout_estimated returned")
+            args += [self._events_ptr(events), self._check(events_hat, self.B * _lib.TOUCHDOWN_INFO_STRIDE, "events_hat")]
+        return ny, args, Hd
+
+    def tracking_rollout_estimated_jvp(self, Zref, K, Lgain, H, Zout, Xhat, innov=None, model=None, guarded=False, events=None,
+                                       events_hat=None, Zref_dot=None, K_dot=None, Lgain_dot=None, x0_dot=None, xhat0_dot=None,
+                                       model_dot=None, out=None, with_estimate=True, with_innovations=True, with_event_dot=True):
+        """Forward sweep of tracking_rollout_estimated at the trajectory (Zout, Xhat, innov[, events, events_hat]) it returned,
+        at fixed noise samples and fixed H: tangents of Zref, K, Lgain, x0, xhat0 and model, each None for zero -- except
+        xhat0_dot, whose None is the forward call's xhat0 = None (the estimate starts on the reference, so its tangent is
+        Zref_dot's first knot).  innov is needed only with Lgain_dot.  Returns (Zout_dot, Xhat_dot, innov_dot), and guarded
+        also (event_dot, event_hat_dot), each optional one None unless asked for (qln_evaluator.h)."""
+        T = _torch()
+        ny, args, keep = self._estimated_traj(Zref, K, Lgain, H, Zout, Xhat, innov, model, guarded, events, events_hat,
+                                              Lgain_dot is not None)
+        nk = self.B * (self.N - 1) * _lib.TRACK_NU * n
+        args += [self._check_opt(Zref_dot, self.dims.z_total, "Zref_dot"), self._check_opt(K_dot, nk, "K_dot"),
+                 self._check_opt(Lgain_dot, self.B * self.N * n * ny, "Lgain_dot"), self._check_opt(x0_dot, self.B * n, "x0_dot"),
+                 self._check_opt(xhat0_dot, self.B * n, "xhat0_dot"),
+                 self._check_opt(model_dot, self.B * _lib.MODEL_NP, "model_dot")]
+        out = self.new_Z() if out is None else out
+        new = lambda want, shape: T.zeros(shape, dtype=T.float64, device=self._dev()) if want else None  # noqa: E731
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        Xd, ivd = new(with_estimate, (self.B, self.N, n)), new(with_innovations, (self.B, self.N, ny))
+        args += [self._check(out, self.dims.z_total, "out"), ptr(Xd), ptr(ivd)]
+        if not guarded:
+            _lib.check(_lib.lib().qln_tracking_rollout_estimated_jvp(*args))
+            return out, Xd, ivd
+        ed = new(with_event_dot, (self.B, _lib.TOUCHDOWN_INFO_STRIDE))
+        ehd = new(with_event_dot, (self.B, _lib.TOUCHDOWN_INFO_STRIDE))
+        _lib.check(_lib.lib().qln_tracking_rollout_estimated_guarded_jvp(*args, ptr(ed), ptr(ehd)))
+        return out, Xd, ivd, ed, ehd
+
+    ESTIMATED_VJP_OUTPUTS = ("Zref", "K", "Lgain", "x0", "xhat0", "model")
+
+    def tracking_rollout_estimated_vjp(self, Zref, K, Lgain, H, Zout, Xhat, Zbar, innov=None, model=None, guarded=False,
+                                       events=None, events_hat=None, Xhat_bar=None, innov_bar=None, want=None):
+        """Reverse sweep of tracking_rollout_estimated, the exact adjoint of tracking_rollout_estimated_jvp: cotangents Zbar
+        (layout of Z), Xhat_bar (B, N, 15) and innov_bar (B, N, ny), the last two None for zero.  Returns (Zref_bar, K_bar,
+        Lgain_bar, x0_bar, xhat0_bar, model_bar), each None unless named in want (default: all, K_bar only when K is given,
+        Lgain_bar only when innov is).  Without "xhat0" in want the cotangent of the initial estimate is added to Zref_bar's
+        first knot: the forward call's xhat0 = None."""
+        T = _torch()
+        names = self.ESTIMATED_VJP_OUTPUTS
+        default = want is None
+        want = self._vjp_want(K, want, names)
+        if default and innov is None:
+            want = tuple(w for w in want if w != "Lgain")
+        ny, args, keep = self._estimated_traj(Zref, K, Lgain, H, Zout, Xhat, innov, model, guarded, events, events_hat,
+                                              "Lgain" in want)
+        args += [self._check(Zbar, self.dims.z_total, "Zbar"), self._check_opt(Xhat_bar, self.B * self.N * n, "Xhat_bar"),
+                 self._check_opt(innov_bar, self.B * self.N * ny, "innov_bar")]
+        new = lambda name, shape: T.zeros(shape, dtype=T.float64, device=self._dev()) if name in want else None  # noqa: E731
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        outs = (self.new_Z() if "Zref" in want else None, new("K", tracking_k_shape(self.B, self.N)),
+                new("Lgain", (self.B, self.N, n, ny)), new("x0", (self.B, n)), new("xhat0", (self.B, n)),
+                new("model", (self.B, _lib.MODEL_NP)))
+        fn = _lib.lib().qln_tracking_rollout_estimated_guarded_vjp if guarded else _lib.lib().qln_tracking_rollout_estimated_vjp
+        _lib.check(fn(*args, *(ptr(o) for o in outs)))
+        return outs
+
+    def _host_estimated_traj(self, Zref, K, Lgain, H, Zout, Xhat, innov, model, guarded, events, events_hat, want_gain):
+        Hh = self._measurement_rows(H)
+        ny = Hh.shape[0]
+
+        def flat(a, size, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
+            if a.size != size:
+                raise ValueError(f"{name} has {a.size} entries, expected {size}")
+            return a
+
+        if Lgain is None or Xhat is None:
+            raise ValueError("Lgain and Xhat are required: what tracking_rollout_estimated_host took and returned")
+        if want_gain and innov is None:
+            raise ValueError("innov is required with a tangent or cotangent of Lgain")
+        keep = [self._host_Z(Zref, "Zref"), self._host_K(K), flat(Lgain, self.B * self.N * n * ny, "Lgain"), Hh,
+                self._host_model(model), self._host_Z(Zout, "Zout"), flat(Xhat, self.B * self.N * n, "Xhat"),
+                flat(innov if want_gain else None, self.B * self.N * ny, "innov")]
+        if guarded:
+            if events is None or events_hat is None:
+                raise ValueError("events and events_hat are required: the two records the roll-out returned")
+            keep += [self._host_events(events), self._host_events(events_hat)]
+        args = [self._h] + [_host_ptr(a) for a in keep]
+        args.insert(5, ny)
+        return ny, args, keep, flat
+
+    def tracking_rollout_estimated_jvp_host(self, Zref, K, Lgain, H, Zout, Xhat, innov=None, model=None, guarded=False,
+                                            events=None, events_hat=None, Zref_dot=None, K_dot=None, Lgain_dot=None, x0_dot=None,
+                                            xhat0_dot=None, model_dot=None, with_estimate=True, with_innovations=True,
+                                            with_event_dot=True):
+        """The same with host arrays (synchronous): numpy (Zout_dot (z_total,), Xhat_dot, innov_dot) and guarded also
+        (event_dot, event_hat_dot).  A non-finite H, a model or an event record that the guarded sweeps' host forms refuse,
+        is refused."""
+        ny, args, keep, flat = self._host_estimated_traj(Zref, K, Lgain, H, Zout, Xhat, innov, model, guarded, events,
+                                                         events_hat, Lgain_dot is not None)
+        tang = [None if Zref_dot is None else self._host_Z(Zref_dot, "Zref_dot"), self._host_K(K_dot),
+                flat(Lgain_dot, self.B * self.N * n * ny, "Lgain_dot"), self._host_x0(x0_dot), self._host_x0(xhat0_dot),
+                self._host_model(model_dot, "model_dot")]
+        out = np.zeros(self.dims.z_total)
+        Xd = np.zeros((self.B, self.N, n)) if with_estimate else None
+        ivd = np.zeros((self.B, self.N, ny)) if with_innovations else None
+        args += [_host_ptr(a) for a in tang] + [out.ctypes.data, _host_ptr(Xd), _host_ptr(ivd)]
+        if not guarded:
+            _lib.check(_lib.lib().qln_tracking_rollout_estimated_jvp_host(*args))
+            return out, Xd, ivd
+        ed = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if with_event_dot else None
+        ehd = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if with_event_dot else None
+        _lib.check(_lib.lib().qln_tracking_rollout_estimated_guarded_jvp_host(*args, _host_ptr(ed), _host_ptr(ehd)))
+        return out, Xd, ivd, ed, ehd
+
+    def tracking_rollout_estimated_vjp_host(self, Zref, K, Lgain, H, Zout, Xhat, Zbar, innov=None, model=None, guarded=False,
+                                            events=None, events_hat=None, Xhat_bar=None, innov_bar=None, want=None):
+        """The same with host arrays (synchronous): numpy (Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar, model_bar)."""
+        default = want is None
+        want = self._vjp_want(K, want, self.ESTIMATED_VJP_OUTPUTS)
+        if default and innov is None:
+            want = tuple(w for w in want if w != "Lgain")
+        ny, args, keep, flat = self._host_estimated_traj(Zref, K, Lgain, H, Zout, Xhat, innov, model, guarded, events,
+                                                         events_hat, "Lgain" in want)
+        cot = [self._host_Z(Zbar, "Zbar"), flat(Xhat_bar, self.B * self.N * n, "Xhat_bar"),
+               flat(innov_bar, self.B * self.N * ny, "innov_bar")]
+        new = lambda name, shape: np.zeros(shape) if name in want else None  # noqa: E731
+        outs = (new("Zref", self.dims.z_total), new("K", tracking_k_shape(self.B, self.N)), new("Lgain", (self.B, self.N, n, ny)),
+                new("x0", (self.B, n)), new("xhat0", (self.B, n)), new("model", (self.B, _lib.MODEL_NP)))
+        fn = (_lib.lib().qln_tracking_rollout_estimated_guarded_vjp_host if guarded
+              else _lib.lib().qln_tracking_rollout_estimated_vjp_host)
+        _lib.check(fn(*args, *(_host_ptr(a) for a in cot), *(_host_ptr(o) for o in outs)))
+        return outs
+
     # -- contact-aware force limits: the roll-out, its sweeps and the gains at fixed active set ------
     def _sat_ptr(self, sat):
         if sat is None:
@@ -1467,6 +1619,19 @@ class HybridNLP:
         if model is None:
             return RolloutFunction.apply(self, Zref, K, x0)
         return ModelRolloutFunction.apply(self, Zref, K, x0, model)
+
+    def differentiable_estimated_rollout(self, Zref, K, Lgain, H, vnoise=None, wnoise=None, x0=None, xhat0=None, model=None,
+                                         guarded=False):
+        """tracking_rollout_estimated as a torch autograd op: returns (Zout, Xhat, innov), and guarded also (events,
+        events_hat).  Zout, Xhat and innov are differentiable in Zref, K, Lgain, x0, xhat0 and model (each a float64 CUDA
+        tensor; K, x0, xhat0 and model may be None) at FIXED noise samples: the backward pass is one
+        qln_tracking_rollout_estimated_vjp launch at the trajectory the forward produced, a forward-mode tangent
+        (torch.autograd.forward_ad, torch.func.jvp) one qln_tracking_rollout_estimated_jvp launch; guarded, both go through
+        the plant's and the estimator's touchdowns at fixed knots.  H, vnoise, wnoise and the event records are not
+        differentiable.  With xhat0 None the estimate starts on Zref's first knot and Zref carries its gradient."""
+        from .rollout_grad import EstimatedRolloutFunction
+
+        return EstimatedRolloutFunction.apply(self, Zref, K, Lgain, x0, xhat0, model, H, vnoise, wnoise, bool(guarded))
 
     def split_hvals(self, hvals):
         """(h_total,) values -> (step blocks (B, N-1, 55), terminal diagonals (B, 15)) as numpy arrays."""

@@ -2,7 +2,8 @@
 qln_tracking_rollout, the backward pass its reverse sweep qln_tracking_rollout_vjp and the forward-mode tangent its forward
 sweep qln_tracking_rollout_jvp (include/qln_evaluator.h).  ModelRolloutFunction is the same over the _model_ forms, with the
 per-problem plant model as a fourth differentiable input.  GuardedRolloutFunction is the roll-out with guard-triggered
-touchdown over qln_tracking_rollout_guarded and the two sweeps through the touchdown, which take its event record."""
+touchdown over qln_tracking_rollout_guarded and the two sweeps through the touchdown, which take its event record.
+EstimatedRolloutFunction is the estimate-feedback roll-out over qln_tracking_rollout_estimated and its two sweeps."""
 from __future__ import annotations
 
 import torch
@@ -171,3 +172,68 @@ class LimitedRolloutFunction(torch.autograd.Function):
             out, _ = ctx.nlp.tracking_rollout_limited_jvp(Zref, Zout, sat, (events or (None,))[0], K, model, zd, kd, xd, md,
                                                           with_event_dot=False)
             return (out, *rest)
+
+
+class EstimatedRolloutFunction(torch.autograd.Function):
+    """(Zout, Xhat, innov[, events, events_hat]) = estimate-feedback rollout(Zref, K, Lgain, x0, xhat0, model; H, vnoise, wnoise,
+    guarded): qln_tracking_rollout_estimated / _guarded.  K, x0, xhat0 and model may be None.  Zout, Xhat and innov are
+    differentiable in Zref, K, Lgain, x0, xhat0 and model through qln_tracking_rollout_estimated_vjp / _jvp at the trajectory
+    the forward produced, that is at fixed noise samples and (guarded) fixed touchdown knots; H, vnoise and wnoise take no
+    gradient and the event records are marked non-differentiable.  xhat0 None is the forward call's: the estimate starts on
+    Zref's first knot, and its gradient and tangent are Zref's there."""
+
+    @staticmethod
+    def forward(nlp, Zref, K, Lgain, x0, xhat0, model, H, vnoise, wnoise, guarded):
+        Zref, K, Lgain, x0, xhat0, model, vnoise, wnoise = _launchable((Zref, K, Lgain, x0, xhat0, model, vnoise, wnoise))
+        return nlp.tracking_rollout_estimated(Zref, K, Lgain, H, vnoise, wnoise, x0, xhat0, model, guarded=guarded,
+                                              with_innovations=True)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        nlp, Zref, K, Lgain, x0, xhat0, model, H, _, _, guarded = inputs
+        Zout, Xhat, innov, *events = output
+        ctx.nlp, ctx.H, ctx.guarded, ctx.has_xhat0 = nlp, H, guarded, xhat0 is not None
+        ctx.shapes = [None if t is None else t.shape for t in (K, Lgain, x0, xhat0, model)]
+        ctx.mark_non_differentiable(*events)
+        ctx.save_for_backward(Zref, K, Lgain, model, Zout, Xhat, innov, *events)
+        ctx.save_for_forward(Zref, K, Lgain, model, Zout, Xhat, innov, *events)
+
+    @staticmethod
+    def backward(ctx, Zbar, Xhat_bar, innov_bar, *_):
+        need = ctx.needs_input_grad[1:7]
+        names = ("Zref", "K", "Lgain", "x0", "xhat0", "model")
+        saved = (_plain(t) for t in (*ctx.saved_tensors, Zbar, Xhat_bar, innov_bar))
+        Zref, K, Lgain, model, Zout, Xhat, innov, *rest = saved
+        *events, Zbar, Xhat_bar, innov_bar = rest
+        want = [w for w, on in zip(names, need) if on and not (w == "K" and K is None)]
+        if not want:
+            return (None,) * 11
+        if ctx.has_xhat0 and "xhat0" not in want:
+            want.append("xhat0")  # a given xhat0 keeps its cotangent out of Zref_bar whether or not it is asked for
+        with torch._C._DisableFuncTorch():
+            Zref, K, Lgain, model, Zout, Xhat, innov, Zbar, Xhat_bar, innov_bar, *events = _launchable(
+                (Zref, K, Lgain, model, Zout, Xhat, innov, Zbar, Xhat_bar, innov_bar, *events))
+            ev, eh = events or (None, None)
+            zb, *bars = ctx.nlp.tracking_rollout_estimated_vjp(Zref, K, Lgain, ctx.H, Zout, Xhat, Zbar, innov, model, ctx.guarded,
+                                                               ev, eh, Xhat_bar, innov_bar, want)
+            bars = [None if b is None or shape is None or not on else b.reshape(shape)
+                    for b, shape, on in zip(bars, ctx.shapes, need[1:])]
+        return (None, zb if need[0] else None, *bars, None, None, None, None)
+
+    @staticmethod
+    def jvp(ctx, _, *dots):
+        Zref, K, Lgain, model, Zout, Xhat, innov, *events = (_plain(t) for t in ctx.saved_tensors)
+        none = (None,) * len(events)
+        with torch._C._DisableFuncTorch():
+            Zref, K, Lgain, model, Zout, Xhat, innov, *events = _launchable((Zref, K, Lgain, model, Zout, Xhat, innov, *events))
+            zd, kd, ld, xd, hd, md = _launchable(_plain(t) for t in dots[:6])
+            if K is None:
+                kd = None
+            if all(t is None for t in (zd, kd, ld, xd, hd, md)):
+                return (torch.zeros_like(Zout), torch.zeros_like(Xhat), torch.zeros_like(innov), *none)
+            if ctx.has_xhat0 and hd is None:
+                hd = torch.zeros_like(Xhat[:, 0])  # a given xhat0 without a tangent does not follow Zref_dot
+            ev, eh = events or (None, None)
+            out = ctx.nlp.tracking_rollout_estimated_jvp(Zref, K, Lgain, ctx.H, Zout, Xhat, innov, model, ctx.guarded, ev, eh, zd,
+                                                         kd, ld, xd, hd if ctx.has_xhat0 else None, md, with_event_dot=False)
+            return (*out[:3], *none)
