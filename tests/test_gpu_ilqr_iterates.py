@@ -37,9 +37,10 @@ def _solve_gpu(batch, o, Zh=None):
     return U, info.cpu().numpy().copy(), Zo
 
 
-def _hold(label, batch, o, gpu, U0=None, model=None, multi=False, witness=None):
+def _hold(label, batch, o, gpu, U0=None, model=None, multi=False, witness=None, may_leave_out=True):
     """Compare the GPU's result with the yardstick problem by problem; returns the worst ratio of the GPU's error to the
-    float64 run's own.  witness(iteration 0 of the longdouble run) -> bool: the case exercises what it is there for."""
+    float64 run's own.  witness(iteration 0 of the longdouble run) -> bool: the case exercises what it is there for.
+    may_leave_out=False: a case qualified beforehand, of which no problem may be left out as ambiguous."""
     Ug, info, _ = gpu
     worst_e, worst_ratio, left_out, seen = 0.0, 0.0, 0, False
     with IC.np_model(model):
@@ -75,6 +76,7 @@ def _hold(label, batch, o, gpu, U0=None, model=None, multi=False, witness=None):
             assert ej_gpu <= tol_j, (label, b, ej_gpu, tol_j)
     print(f"{label}: worst e = {worst_e:.2e}, worst ratio to the float64 spread = {worst_ratio:.2f}, left out {left_out} of {batch.B}")
     assert left_out * 8 <= batch.B, f"{label}: {left_out} of {batch.B} problems ambiguous"
+    assert may_leave_out or left_out == 0, f"{label}: {left_out} problems left out of a case that was qualified"
     assert witness is None or seen, f"{label}: no problem of the batch exercises the term"
     return worst_ratio
 
