@@ -904,8 +904,8 @@ int qln_tracking_kalman_guarded_host(qln_handle* h, const double* Zout, const do
  * respectively _guarded and its event record, whatever K is.
  * Refused with QLN_ERR_INVALID_ARGUMENT: a NULL h, Zref, Zout, Lgain or H; ny outside 1..QLN_TRACK_NY_MAX; an overlap.  The
  * device forms do not validate device data; the host forms also refuse a non-finite H, and a model as
- * qln_tracking_rollout_guarded_host does.  Force limits in this loop do not exist.  Its derivatives are
- * qln_tracking_rollout_estimated_jvp / _vjp below.
+ * qln_tracking_rollout_guarded_host does.  Force limits in this loop are qln_tracking_rollout_estimated_limited
+ * below; these two calls apply the forces as computed.  Their derivatives are qln_tracking_rollout_estimated_jvp / _vjp below.
  * Device pointers, stream-ordered; needs no cost table. */
 int qln_tracking_rollout_estimated(qln_handle* h, const double* Zref, const double* K /* or NULL */, const double* Lgain,
                                    const double* H, int32_t ny, const double* vnoise, const double* wnoise, const double* x0,
@@ -1025,6 +1025,95 @@ int qln_tracking_rollout_estimated_guarded_vjp_host(qln_handle* h, const double*
                                                     const double* event_hat, const double* Zbar, const double* Xhat_bar,
                                                     const double* innov_bar, double* Zref_bar, double* K_bar, double* Lgain_bar,
                                                     double* x0_bar, double* xhat0_bar, double* model_bar);
+/* CONTACT-AWARE FORCE LIMITS in the estimate-feedback roll-out and its sweeps: the loop of qln_tracking_rollout_estimated /
+ * _guarded with the clamp of qln_tracking_rollout_limited.  The forces are fed back from a noisy estimate, so this is the loop
+ * in which they chatter against stand_y_lo and the caps.  All of it is opt-in: every call above keeps its bits.  Knots are
+ * 0-based, k = 0..N-2.
+ * The loop (qln_tracking_rollout_estimated_limited).  qln_tracking_rollout_estimated (guarded == 0; event and event_hat must be
+ *   NULL) or qln_tracking_rollout_estimated_guarded (guarded != 0) statement for statement, with one added step: after
+ *   F_k = F_ref,k - K_k (xhat_k - x_ref,k) has been formed and before Zout's u_k is stored, the four forces go through the clamp
+ *   of qln_tracking_rollout_limited.  lim (a HOST array of QLN_FORCE_LIMITS_N doubles), the codes s_m and the record
+ *   sat[b][k] = sum_m s_m 4^m ([B][N-1], may be NULL: not written, the other outputs are the same) are the same as there: a NaN
+ *   passes through with s_m = 0, F == lo exactly is s_m = 0, h_k is never clamped, and with K == NULL the reference's forces are
+ *   clamped.
+ * Whose contact mode picks the limits: the PLANT's.  Knot-scheduled: the handle's schedule (the jump knot is still in
+ *   init_mode).  Guarded: the plant's current mode at the start of the knot, the landing foot counting as free for its whole
+ *   touchdown knot -- exactly qln_tracking_rollout_limited's rule.  The limits are the plant's saturation, a fact about the
+ *   ground and the actuator, not a decision of the controller; the estimator's believed mode picks nothing.
+ * Where the applied forces go.  There is one set of applied forces, used everywhere: Zout's u_k, the plant's guard and step, the
+ *   estimator's guard and step (the estimator is told what was applied, as it is above), and entry 6 of both event records.
+ *   The plant's entry 6 is therefore >= stand_y_lo.  The estimator's need not be: it may believe a foot stands that does not,
+ *   and that foot's force was clamped as a free one's.
+ * Sweeps at FIXED ACTIVE SET (qln_tracking_rollout_estimated_limited_jvp / _vjp).  sat is a REQUIRED input, and takes part in
+ *   the overlap rules.  event and event_hat both NULL select the blocks of qln_tracking_rollout_estimated_jvp / _vjp (then
+ *   event_dot and event_hat_dot must be NULL), both given those of the _guarded_ forms; the other arguments, NULL rules and
+ *   outputs are theirs.
+ *   Forward:  the recursion of qln_tracking_rollout_estimated_jvp with dF_k multiplied by mask_k[m] = (s_m == 0) before
+ *     anything reads it: Zout_dot's u_k, both chains' B applications, and both chains' dtau at their own touchdown knots.
+ *   Reverse:  ubar_k[0:4] is masked after B^p' lam, B^e' lamm and both chains' taubar have been added onto it, and before
+ *     K_k' ubar, K_bar and Zref_bar read it: the saturated channels' rows of K_bar and force slots of Zref_bar are exact zeros.
+ *     Lgain_bar needs no mask.
+ *   The two sweeps are exact adjoints: the duality identity of the estimated sweeps holds as it stands.  The one-sided-derivative
+ *   caveat of qln_tracking_rollout_limited_jvp carries over: where the active set changes the map has a kink.
+ * Exact reductions.
+ *   1. All eight limits infinite: Zout, Xhat, innov, event and event_hat are the bits of qln_tracking_rollout_estimated /
+ *      _guarded, and sat is all zeros.
+ *   2. sat all zero in a sweep: every output has the bits of qln_tracking_rollout_estimated_jvp / _vjp, or of the _guarded_ forms.
+ *   3. K == NULL and wnoise == NULL: Zout, event and sat are the bits of qln_tracking_rollout_limited(Zref, NULL, x0, model, lim,
+ *      guarded, ...), whatever Lgain, H, vnoise and xhat0 are: the estimate does not reach the plant.
+ *   4. Knot-scheduled form only: Lgain = 0, xhat0 == NULL, wnoise == NULL and Zref the output of
+ *      qln_tracking_rollout_limited(.., K = NULL, .., lim, 0) under the handle's model: the estimate stays on Zref, so Zout and sat
+ *      are the bits of qln_tracking_rollout_limited(Zref, NULL, x0, model, lim, 0) whatever K is.  In the guarded form this does
+ *      not hold: a plant that lands in another knot than the nominal picks other limits.
+ *   5. A call with ny rows equals the call with QLN_TRACK_NY_MAX rows and zero rows and columns, and every subset of optional
+ *      outputs has the bits of the full call.
+ * Errors: those of the two families, plus a NaN limit or lo > hi, a NULL lim, event or event_hat non-NULL with guarded == 0,
+ *   exactly one of event / event_hat in a sweep, event_dot / event_hat_dot without records, a NULL sat in a sweep:
+ *   QLN_ERR_INVALID_ARGUMENT.  The device forms do not validate sat; the host forms validate its codes as
+ *   qln_tracking_rollout_limited_jvp_host does.  Device pointers, stream-ordered; needs no cost table. */
+int qln_tracking_rollout_estimated_limited(qln_handle* h, const double* Zref, const double* K /* or NULL */, const double* Lgain,
+                                           const double* H, int32_t ny, const double* vnoise, const double* wnoise,
+                                           const double* x0, const double* xhat0, const double* model,
+                                           const double* lim /* host, [QLN_FORCE_LIMITS_N] */, int32_t guarded, double* Zout,
+                                           double* Xhat, double* innov, double* event /* NULL if guarded == 0 */,
+                                           double* event_hat /* NULL if guarded == 0 */, double* sat /* [B][N-1] or NULL */);
+int qln_tracking_rollout_estimated_limited_jvp(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                               const double* H, int32_t ny, const double* model, const double* Zout,
+                                               const double* Xhat, const double* innov,
+                                               const double* event /* both NULL: the knot schedule; both given: guarded */,
+                                               const double* event_hat, const double* sat /* required */,
+                                               const double* Zref_dot, const double* K_dot, const double* Lgain_dot,
+                                               const double* x0_dot, const double* xhat0_dot, const double* model_dot,
+                                               double* Zout_dot, double* Xhat_dot, double* innov_dot, double* event_dot,
+                                               double* event_hat_dot);
+int qln_tracking_rollout_estimated_limited_vjp(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                               const double* H, int32_t ny, const double* model, const double* Zout,
+                                               const double* Xhat, const double* innov, const double* event,
+                                               const double* event_hat, const double* sat /* required */, const double* Zbar,
+                                               const double* Xhat_bar, const double* innov_bar, double* Zref_bar, double* K_bar,
+                                               double* Lgain_bar, double* x0_bar, double* xhat0_bar, double* model_bar);
+/* the same as host forms (see "Host forms" above; Zout, Zout_dot and Zref_bar are in-out as in the forms they extend; lim is a
+ * host array in both) */
+int qln_tracking_rollout_estimated_limited_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                                const double* H, int32_t ny, const double* vnoise, const double* wnoise,
+                                                const double* x0, const double* xhat0, const double* model, const double* lim,
+                                                int32_t guarded, double* Zout, double* Xhat, double* innov, double* event,
+                                                double* event_hat, double* sat);
+int qln_tracking_rollout_estimated_limited_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                                    const double* H, int32_t ny, const double* model, const double* Zout,
+                                                    const double* Xhat, const double* innov, const double* event,
+                                                    const double* event_hat, const double* sat, const double* Zref_dot,
+                                                    const double* K_dot, const double* Lgain_dot, const double* x0_dot,
+                                                    const double* xhat0_dot, const double* model_dot, double* Zout_dot,
+                                                    double* Xhat_dot, double* innov_dot, double* event_dot,
+                                                    double* event_hat_dot);
+int qln_tracking_rollout_estimated_limited_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                                    const double* H, int32_t ny, const double* model, const double* Zout,
+                                                    const double* Xhat, const double* innov, const double* event,
+                                                    const double* event_hat, const double* sat, const double* Zbar,
+                                                    const double* Xhat_bar, const double* innov_bar, double* Zref_bar,
+                                                    double* K_bar, double* Lgain_bar, double* x0_bar, double* xhat0_bar,
+                                                    double* model_bar);
 /* Z <- Z + N(0, sigma^2) on every entry, step lengths h then clipped to [h_min, h_max] (redraw_h = 0) or redrawn
  * U(h_min, h_max) (redraw_h != 0) -- the evaluation point of SURVEY.md 8d from qln_initial_guess's Z0.  The normal
  * draws are Box-Muller on the sampler's stream from `stream_offset`: the recipe's distribution, not numpy's numbers. */

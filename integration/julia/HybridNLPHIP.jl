@@ -597,6 +597,73 @@ function mask_gains(K::Array{Float64,3}, sat::Vector{Float64})
     s = unpack_saturation(sat)
     return [s[m, k] == 0 ? K[j, m, k] : 0.0 for j in 1:size(K, 1), m in 1:4, k in 1:length(sat)]
 end
+# Force limits in the estimate-feedback roll-out (include/qln_evaluator.h, DESIGN.md 4.24): tracking_rollout_estimated (guarded =
+# false) or tracking_rollout_estimated_guarded (guarded = true) with the forces fed back from the estimate clamped to limits by the
+# PLANT's contact mode, before the plant, the estimator or Zout read them.  Returns (Zout, Xhat, innov, events, events_hat, sat):
+# the records nothing when not guarded, sat as tracking_rollout_limited returns it.  The sweeps at that active set take sat after
+# the trajectory, and both records for the guarded blocks (both nothing: the knot schedule's); the rest is the estimated sweeps'.
+function tracking_rollout_estimated_limited(prob::HybridNLPHIP, Zref::Vector{Float64}, limits::Vector{Float64},
+                                            L::Array{Float64,3}, H::Matrix{Float64}; K=nothing, vnoise=nothing, wnoise=nothing,
+                                            x0=nothing, xhat0=nothing, model=nothing, guarded::Bool=false)
+    length(limits) == 8 || error("limits: 8 values expected")
+    ny, Hrow = _estimated_rows(prob, L, H)
+    Zout = zeros(length(Zref))
+    Xhat = zeros(15, prob.N)
+    innov = zeros(ny, prob.N)
+    events = guarded ? zeros(8) : nothing
+    events_hat = guarded ? zeros(8) : nothing
+    sat = zeros(prob.N - 1)
+    qln_check(ccall((:qln_tracking_rollout_estimated_limited_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, _opt(K), L, Hrow, Int32(ny), _opt(vnoise), _opt(wnoise), _opt(x0), _opt(xhat0), _opt(model),
+                    limits, Int32(guarded ? 1 : 0), Zout, Xhat, innov, _opt(events), _opt(events_hat), sat))
+    return Zout, Xhat, innov, events, events_hat, sat
+end
+function tracking_rollout_estimated_limited_jvp(prob::HybridNLPHIP, Zref::Vector{Float64}, L::Array{Float64,3}, H::Matrix{Float64},
+                                                Zout::Vector{Float64}, Xhat::Matrix{Float64}, innov::Matrix{Float64},
+                                                sat::Vector{Float64}; events=nothing, events_hat=nothing, K=nothing, model=nothing,
+                                                Zref_dot=nothing, K_dot=nothing, L_dot=nothing, x0_dot=nothing,
+                                                xhat0_dot=nothing, model_dot=nothing)
+    ny, Hrow = _estimated_rows(prob, L, H)
+    (events === nothing) == (events_hat === nothing) || error("events and events_hat: both or neither")
+    Zout_dot = zeros(length(Zref))
+    Xhat_dot = zeros(15, prob.N)
+    innov_dot = zeros(ny, prob.N)
+    event_dot = events === nothing ? nothing : zeros(8)
+    event_hat_dot = events === nothing ? nothing : zeros(8)
+    qln_check(ccall((:qln_tracking_rollout_estimated_limited_jvp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, _opt(K), L, Hrow, Int32(ny), _opt(model), Zout, Xhat, innov, _opt(events), _opt(events_hat),
+                    sat, _opt(Zref_dot), _opt(K_dot), _opt(L_dot), _opt(x0_dot), _opt(xhat0_dot), _opt(model_dot), Zout_dot,
+                    Xhat_dot, innov_dot, _opt(event_dot), _opt(event_hat_dot)))
+    return Zout_dot, Xhat_dot, innov_dot, event_dot, event_hat_dot
+end
+function tracking_rollout_estimated_limited_vjp(prob::HybridNLPHIP, Zref::Vector{Float64}, L::Array{Float64,3}, H::Matrix{Float64},
+                                                Zout::Vector{Float64}, Xhat::Matrix{Float64}, innov::Matrix{Float64},
+                                                sat::Vector{Float64}, Zbar::Vector{Float64}; events=nothing, events_hat=nothing,
+                                                K=nothing, model=nothing, Xhat_bar=nothing, innov_bar=nothing,
+                                                with_xhat0::Bool=true)
+    ny, Hrow = _estimated_rows(prob, L, H)
+    (events === nothing) == (events_hat === nothing) || error("events and events_hat: both or neither")
+    Zref_bar = zeros(length(Zref))
+    K_bar = K === nothing ? nothing : zeros(size(K))
+    L_bar = zeros(ny, 15, prob.N)
+    x0_bar = zeros(15)
+    xhat0_bar = with_xhat0 ? zeros(15) : nothing
+    model_bar = zeros(4)
+    qln_check(ccall((:qln_tracking_rollout_estimated_limited_vjp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, _opt(K), L, Hrow, Int32(ny), _opt(model), Zout, Xhat, innov, _opt(events), _opt(events_hat),
+                    sat, Zbar, _opt(Xhat_bar), _opt(innov_bar), Zref_bar, _opt(K_bar), L_bar, x0_bar, _opt(xhat0_bar), model_bar))
+    return Zref_bar, K_bar, L_bar, x0_bar, xhat0_bar, model_bar
+end
 
 # ---- the reference's Ipopt solve, for this evaluator type: a method of `solve` (src/moi.jl:46-103) ------------------------
 # Same generic function, same keyword arguments and defaults, same five things handed to Ipopt.  What differs from the

@@ -199,6 +199,13 @@ SIGNATURES = {
     "qln_tracking_rollout_estimated_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 13),
     "qln_tracking_rollout_estimated_guarded_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 17),
     "qln_tracking_rollout_estimated_guarded_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 15),
+    "qln_tracking_rollout_estimated_limited": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 6 + [C.c_int32] + [_dp] * 6),
+    "qln_tracking_rollout_estimated_limited_host": (C.c_int,
+                                                    [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 6 + [C.c_int32] + [_dp] * 6),
+    "qln_tracking_rollout_estimated_limited_jvp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 18),
+    "qln_tracking_rollout_estimated_limited_vjp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 16),
+    "qln_tracking_rollout_estimated_limited_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 18),
+    "qln_tracking_rollout_estimated_limited_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 16),
     "qln_eval_constraint_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_eval_constraint_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp]),
     "qln_gauss_newton_step": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, C.c_double, _dp, _dp, _dp]),

@@ -1767,12 +1767,19 @@ int qln_tracking_kalman_guarded_host(qln_handle* h, const double* Zout, const do
 
 // the estimate-feedback roll-out (k_tracking_rollout_estimated).  The checks that need no handle come first.
 // guarded: both the plant and the estimator land by their own guards, each with an event record (may be null)
+// limited: the loop within the force limits lim, with its saturation record sat (may be null)
 static int check_tracking_estimated_args(const qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                          const double* H, int32_t ny, const double* vnoise, const double* wnoise,
                                          const double* x0, const double* xhat0, const double* model, const double* Zout,
-                                         const double* Xhat, const double* innov, const double* event, const double* event_hat,
+                                         const double* Xhat, const double* innov, bool guarded, const double* event,
+                                         const double* event_hat, bool limited, const double* lim, const double* sat,
                                          const char* who) {
     const std::string w(who);
+    if (limited) {
+        if (int rc = check_force_limits(lim, who)) return rc;
+        if (!guarded && (event || event_hat))
+            return fail(QLN_ERR_INVALID_ARGUMENT, w + ": event or event_hat with guarded == 0 (the knot schedule has no record)");
+    }
     if (ny < 1 || ny > QLN_TRACK_NY_MAX)
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
     if (!Lgain || !H) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Lgain or H");
@@ -1781,7 +1788,7 @@ static int check_tracking_estimated_args(const qln_handle* h, const double* Zref
     const qln_dims& D = h->dims;
     const int64_t nx = (int64_t)D.B * QLN_NX, ne = (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
     return check_no_overlap({{Zout, D.z_total}, {Xhat, (int64_t)D.B * D.N * QLN_NX}, {innov, tracking_meas_total(D, ny)},
-                             {event, ne}, {event_hat, ne}},
+                             {event, ne}, {event_hat, ne}, {sat, tracking_sat_total(D)}},
                             {{Zref, D.z_total}, {K, tracking_k_total(D)}, {Lgain, tracking_gain_total(D, ny)},
                              {H, (int64_t)ny * QLN_NX}, {vnoise, tracking_meas_total(D, ny)},
                              {wnoise, (int64_t)D.B * (D.N - 1) * QLN_NX}, {x0, nx}, {xhat0, nx},
@@ -1791,22 +1798,24 @@ static int check_tracking_estimated_args(const qln_handle* h, const double* Zref
 static int tracking_rollout_estimated(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
                                       int32_t ny, const double* vnoise, const double* wnoise, const double* x0,
                                       const double* xhat0, const double* model, double* Zout, double* Xhat, double* innov,
-                                      bool guarded, double* event, double* event_hat, const char* who) {
-    if (int rc = check_tracking_estimated_args(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, event,
-                                               event_hat, who))
+                                      bool guarded, double* event, double* event_hat, bool limited, const double* lim,
+                                      double* sat, const char* who) {
+    if (int rc = check_tracking_estimated_args(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, guarded,
+                                               event, event_hat, limited, lim, sat, who))
         return rc;
     if (int rc = bind_device(h)) return rc;
     QLN_HIP(qln::launch_tracking_rollout_estimated(h->p, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov,
-                                                   guarded, event, event_hat, h->stream));
+                                                   guarded, event, event_hat, limited ? lim : nullptr, sat, h->stream));
     return QLN_OK;
 }
 
 static int tracking_rollout_estimated_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                            const double* H, int32_t ny, const double* vnoise, const double* wnoise,
                                            const double* x0, const double* xhat0, const double* model, double* Zout, double* Xhat,
-                                           double* innov, bool guarded, double* event, double* event_hat, const char* who) {
-    if (int rc = check_tracking_estimated_args(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, event,
-                                               event_hat, who))
+                                           double* innov, bool guarded, double* event, double* event_hat, bool limited,
+                                           const double* lim, double* sat, const char* who) {
+    if (int rc = check_tracking_estimated_args(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, guarded,
+                                               event, event_hat, limited, lim, sat, who))
         return rc;
     for (int i = 0; i < ny * QLN_NX; ++i)
         if (!std::isfinite(H[i]))
@@ -1820,11 +1829,12 @@ static int tracking_rollout_estimated_host(qln_handle* h, const double* Zref, co
     return host_call(h,
                      {copy_in(kZ, Zref), copy_inout(kZio, Zout), copy_in(kK, K), lg, hm, vn, copy_in(kWnoise, wnoise),
                       copy_in(kX0, x0), copy_in(kXhat0, xhat0), copy_in(kModel, model), copy_out(kXhat, Xhat), in,
-                      copy_out(kEvent, event), copy_out(kEventHat, event_hat)},
+                      copy_out(kEvent, event), copy_out(kEventHat, event_hat), copy_out(kSat, sat)},
                      [&](double* const* d, bool) {
                          return qln::launch_tracking_rollout_estimated(h->p, d[kZ], d[kK], d[kLgain], d[kH], ny, d[kVnoise],
                                                                        d[kWnoise], d[kX0], d[kXhat0], d[kModel], d[kZio], d[kXhat],
-                                                                       d[kInnov], guarded, d[kEvent], d[kEventHat], h->stream);
+                                                                       d[kInnov], guarded, d[kEvent], d[kEventHat],
+                                                                       limited ? lim : nullptr, d[kSat], h->stream);
                      });
 }
 
@@ -1832,37 +1842,58 @@ int qln_tracking_rollout_estimated(qln_handle* h, const double* Zref, const doub
                                    int32_t ny, const double* vnoise, const double* wnoise, const double* x0, const double* xhat0,
                                    const double* model, double* Zout, double* Xhat, double* innov) {
     return tracking_rollout_estimated(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, false, nullptr,
-                                      nullptr, "qln_tracking_rollout_estimated");
+                                      nullptr, false, nullptr, nullptr, "qln_tracking_rollout_estimated");
 }
 int qln_tracking_rollout_estimated_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
                                         int32_t ny, const double* vnoise, const double* wnoise, const double* x0,
                                         const double* xhat0, const double* model, double* Zout, double* Xhat, double* innov) {
     return tracking_rollout_estimated_host(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, false,
-                                           nullptr, nullptr, "qln_tracking_rollout_estimated_host");
+                                           nullptr, nullptr, false, nullptr, nullptr, "qln_tracking_rollout_estimated_host");
 }
 int qln_tracking_rollout_estimated_guarded(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
                                            int32_t ny, const double* vnoise, const double* wnoise, const double* x0,
                                            const double* xhat0, const double* model, double* Zout, double* Xhat, double* innov,
                                            double* event, double* event_hat) {
     return tracking_rollout_estimated(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, true, event,
-                                      event_hat, "qln_tracking_rollout_estimated_guarded");
+                                      event_hat, false, nullptr, nullptr, "qln_tracking_rollout_estimated_guarded");
 }
 int qln_tracking_rollout_estimated_guarded_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                                 const double* H, int32_t ny, const double* vnoise, const double* wnoise,
                                                 const double* x0, const double* xhat0, const double* model, double* Zout,
                                                 double* Xhat, double* innov, double* event, double* event_hat) {
     return tracking_rollout_estimated_host(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, true, event,
-                                           event_hat, "qln_tracking_rollout_estimated_guarded_host");
+                                           event_hat, false, nullptr, nullptr, "qln_tracking_rollout_estimated_guarded_host");
+}
+// the loop within contact-aware force limits: the knot-scheduled or the guarded one, with its saturation record
+int qln_tracking_rollout_estimated_limited(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
+                                           int32_t ny, const double* vnoise, const double* wnoise, const double* x0,
+                                           const double* xhat0, const double* model, const double* lim, int32_t guarded,
+                                           double* Zout, double* Xhat, double* innov, double* event, double* event_hat,
+                                           double* sat) {
+    return tracking_rollout_estimated(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, guarded != 0,
+                                      event, event_hat, true, lim, sat, "qln_tracking_rollout_estimated_limited");
+}
+int qln_tracking_rollout_estimated_limited_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                                const double* H, int32_t ny, const double* vnoise, const double* wnoise,
+                                                const double* x0, const double* xhat0, const double* model, const double* lim,
+                                                int32_t guarded, double* Zout, double* Xhat, double* innov, double* event,
+                                                double* event_hat, double* sat) {
+    return tracking_rollout_estimated_host(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov,
+                                           guarded != 0, event, event_hat, true, lim, sat,
+                                           "qln_tracking_rollout_estimated_limited_host");
 }
 
 // The sweeps through the estimate-feedback roll-out (k_tracking_rollout_estimated_jvp / _vjp).  What both sweeps share: the
 // roll-out's inputs and the trajectory it produced.  The checks that need no handle come first.
 // guarded: the sweeps through the two guard-triggered touchdowns, which need both of the roll-out's event records
 // want_gain: a tangent or cotangent of Lgain is asked for, which needs innov
+// sat: the limited roll-out's saturation record, required by the sweeps at its active set (limited), whose event and event_hat
+// -- both or neither -- select the guarded or the knot-scheduled blocks
 struct EstimatedTraj {
     const double *Zref, *K, *Lgain, *H;
     int32_t ny;
-    const double *model, *Zout, *Xhat, *innov, *event, *event_hat;
+    const double *model, *Zout, *Xhat, *innov, *event, *event_hat, *sat = nullptr;
+    bool limited = false;
 };
 
 static int check_tracking_estimated_sweep_args(const qln_handle* h, const EstimatedTraj& t, bool guarded, bool want_gain,
@@ -1870,6 +1901,10 @@ static int check_tracking_estimated_sweep_args(const qln_handle* h, const Estima
     if (t.ny < 1 || t.ny > QLN_TRACK_NY_MAX)
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
     if (!t.Lgain || !t.H) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Lgain or H");
+    if (t.limited && !t.sat) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null sat (the limited roll-out's saturation record)");
+    if (t.limited && (t.event != nullptr) != (t.event_hat != nullptr))
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": exactly one of event and event_hat (both: the guarded blocks, neither: the "
+                                                  "knot-scheduled ones)");
     if (guarded && (!t.event || !t.event_hat))
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event or event_hat (the guarded roll-out's two records)");
     if (want_gain && !t.innov)
@@ -1883,7 +1918,8 @@ static int check_tracking_estimated_sweep_args(const qln_handle* h, const Estima
     {t.Zref, D.z_total}, {t.K, tracking_k_total(D)}, {t.Lgain, tracking_gain_total(D, t.ny)}, {t.H, (int64_t)t.ny * QLN_NX}, \
         {t.model, (int64_t)D.B * QLN_MODEL_NP}, {t.Zout, D.z_total}, {t.Xhat, (int64_t)D.B * D.N * QLN_NX},                   \
         {want_gain ? t.innov : nullptr, tracking_meas_total(D, t.ny)},                                                        \
-        {t.event, (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE}, {t.event_hat, (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE}
+        {t.event, (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE}, {t.event_hat, (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE},        \
+        {t.sat, tracking_sat_total(D)}
 
 static int check_tracking_estimated_jvp_args(const qln_handle* h, const EstimatedTraj& t, bool guarded,
                                              const qln::EstimatedJvpArgs& a, const char* who) {
@@ -1892,6 +1928,9 @@ static int check_tracking_estimated_jvp_args(const qln_handle* h, const Estimate
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every tangent is NULL (no direction)");
     if (a.K_dot && !t.K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_dot needs K (K == NULL has no gains to perturb)");
     if (!a.Zout_dot) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zout_dot");
+    if (t.limited && !t.event && !t.event_hat && (a.event_dot || a.event_hat_dot))
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": event_dot or event_hat_dot without event and event_hat (the knot-scheduled "
+                                                  "sweep has no record)");
     if (int rc = check_tracking_estimated_sweep_args(h, t, guarded, a.Lgain_dot != nullptr, w)) return rc;
     const qln_dims& D = h->dims;
     const int64_t nx = (int64_t)D.B * QLN_NX, nm = (int64_t)D.B * QLN_MODEL_NP, ne = (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
@@ -1927,7 +1966,7 @@ static int tracking_estimated_jvp(qln_handle* h, const EstimatedTraj& t, bool gu
                                   const char* who) {
     if (int rc = check_tracking_estimated_jvp_args(h, t, guarded, a, who)) return rc;
     if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout_estimated_jvp(h->p, estimated_sweep_in(t, guarded), a, h->stream));
+    QLN_HIP(qln::launch_tracking_rollout_estimated_jvp(h->p, estimated_sweep_in(t, guarded), a, t.sat, h->stream));
     return QLN_OK;
 }
 
@@ -1935,7 +1974,7 @@ static int tracking_estimated_vjp(qln_handle* h, const EstimatedTraj& t, bool gu
                                   const char* who) {
     if (int rc = check_tracking_estimated_vjp_args(h, t, guarded, a, who)) return rc;
     if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout_estimated_vjp(h->p, estimated_sweep_in(t, guarded), a, h->stream));
+    QLN_HIP(qln::launch_tracking_rollout_estimated_vjp(h->p, estimated_sweep_in(t, guarded), a, t.sat, h->stream));
     return QLN_OK;
 }
 
@@ -1945,6 +1984,7 @@ static int check_host_estimated_traj(const qln_handle* h, const EstimatedTraj& t
         if (!std::isfinite(t.H[i]))
             return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": H is not finite (entry " + std::to_string(i) + ")");
     if (int rc = check_host_models(h, t.model, who)) return rc;
+    if (int rc = check_host_sat(h, t.sat, who)) return rc;
     if (!guarded) return QLN_OK;
     if (int rc = check_host_events(h, t.event, who)) return rc;
     return check_host_events(h, t.event_hat, who);
@@ -1969,7 +2009,8 @@ static int tracking_estimated_jvp_host(qln_handle* h, const EstimatedTraj& t, bo
         {copy_in(kV, t.Zout), copy_in(kZ, a.K_dot ? t.Zref : nullptr), copy_in(kK, t.K), sized(copy_in(kLgain, t.Lgain), ng),
          sized(copy_in(kH, t.H), (int64_t)t.ny * QLN_NX), copy_in(kModel, t.model), copy_in(kXhat, t.Xhat),
          sized(copy_in(kInnov, a.Lgain_dot ? t.innov : nullptr), nm), copy_in(kEvent, guarded ? t.event : nullptr),
-         copy_in(kEventHat, guarded ? t.event_hat : nullptr), copy_in(kZdot, a.Zref_dot), copy_in(kKdot, a.K_dot),
+         copy_in(kEventHat, guarded ? t.event_hat : nullptr), copy_in(kSat, t.sat), copy_in(kZdot, a.Zref_dot),
+         copy_in(kKdot, a.K_dot),
          sized(copy_in(kLgainD, a.Lgain_dot), ng), copy_in(kX0, a.x0_dot), copy_in(kXhat0, a.xhat0_dot),
          copy_in(kModelD, a.model_dot), copy_inout(kZio, a.Zout_dot), copy_out(kXhatD, a.Xhat_dot),
          sized(copy_out(kInnovD, a.innov_dot), nm), copy_out(kEventD, guarded ? a.event_dot : nullptr),
@@ -1979,7 +2020,7 @@ static int tracking_estimated_jvp_host(qln_handle* h, const EstimatedTraj& t, bo
                                               d[kInnov], d[kEvent], d[kEventHat]};
             const qln::EstimatedJvpArgs da = {d[kZdot], d[kKdot], d[kLgainD], d[kX0], d[kXhat0], d[kModelD], d[kZio], d[kXhatD],
                                               d[kInnovD], d[kEventD], d[kEventHatD]};
-            return qln::launch_tracking_rollout_estimated_jvp(h->p, in, da, h->stream);
+            return qln::launch_tracking_rollout_estimated_jvp(h->p, in, da, d[kSat], h->stream);
         });
 }
 
@@ -1995,7 +2036,8 @@ static int tracking_estimated_vjp_host(qln_handle* h, const EstimatedTraj& t, bo
         {copy_in(kV, t.Zout), copy_in(kZ, a.K_bar ? t.Zref : nullptr), copy_in(kK, t.K), sized(copy_in(kLgain, t.Lgain), ng),
          sized(copy_in(kH, t.H), (int64_t)t.ny * QLN_NX), copy_in(kModel, t.model), copy_in(kXhat, t.Xhat),
          sized(copy_in(kInnov, a.Lgain_bar ? t.innov : nullptr), nm), copy_in(kEvent, guarded ? t.event : nullptr),
-         copy_in(kEventHat, guarded ? t.event_hat : nullptr), copy_in(kZbar, a.Zbar), copy_in(kXhatD, a.Xhat_bar),
+         copy_in(kEventHat, guarded ? t.event_hat : nullptr), copy_in(kSat, t.sat), copy_in(kZbar, a.Zbar),
+         copy_in(kXhatD, a.Xhat_bar),
          sized(copy_in(kInnovD, a.innov_bar), nm), copy_inout(kZio, a.Zref_bar), copy_out(kKbar, a.K_bar),
          sized(copy_out(kLgainD, a.Lgain_bar), ng), copy_out(kX0, a.x0_bar), copy_out(kXhat0, a.xhat0_bar),
          copy_out(kModelD, a.model_bar)},
@@ -2004,7 +2046,7 @@ static int tracking_estimated_vjp_host(qln_handle* h, const EstimatedTraj& t, bo
                                               d[kInnov], d[kEvent], d[kEventHat]};
             const qln::EstimatedVjpArgs da = {d[kZbar], d[kXhatD], d[kInnovD], d[kZio], d[kKbar], d[kLgainD], d[kX0], d[kXhat0],
                                               d[kModelD]};
-            return qln::launch_tracking_rollout_estimated_vjp(h->p, in, da, h->stream);
+            return qln::launch_tracking_rollout_estimated_vjp(h->p, in, da, d[kSat], h->stream);
         });
 }
 
@@ -2089,6 +2131,59 @@ int qln_tracking_rollout_estimated_guarded_vjp_host(qln_handle* h, const double*
     return tracking_estimated_vjp_host(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, event, event_hat}, true,
                                        {Zbar, Xhat_bar, innov_bar, Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar, model_bar},
                                        "qln_tracking_rollout_estimated_guarded_vjp_host");
+}
+
+// the sweeps at the limited loop's active set: the same path with its saturation record; event and event_hat select the guarded
+// blocks
+int qln_tracking_rollout_estimated_limited_jvp(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                               const double* H, int32_t ny, const double* model, const double* Zout,
+                                               const double* Xhat, const double* innov, const double* event,
+                                               const double* event_hat, const double* sat, const double* Zref_dot,
+                                               const double* K_dot, const double* Lgain_dot, const double* x0_dot,
+                                               const double* xhat0_dot, const double* model_dot, double* Zout_dot,
+                                               double* Xhat_dot, double* innov_dot, double* event_dot, double* event_hat_dot) {
+    return tracking_estimated_jvp(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, event, event_hat, sat, true},
+                                  event != nullptr && event_hat != nullptr,
+                                  {Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, Zout_dot, Xhat_dot, innov_dot,
+                                   event_dot, event_hat_dot},
+                                  "qln_tracking_rollout_estimated_limited_jvp");
+}
+int qln_tracking_rollout_estimated_limited_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                                    const double* H, int32_t ny, const double* model, const double* Zout,
+                                                    const double* Xhat, const double* innov, const double* event,
+                                                    const double* event_hat, const double* sat, const double* Zref_dot,
+                                                    const double* K_dot, const double* Lgain_dot, const double* x0_dot,
+                                                    const double* xhat0_dot, const double* model_dot, double* Zout_dot,
+                                                    double* Xhat_dot, double* innov_dot, double* event_dot,
+                                                    double* event_hat_dot) {
+    return tracking_estimated_jvp_host(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, event, event_hat, sat, true},
+                                       event != nullptr && event_hat != nullptr,
+                                       {Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, Zout_dot, Xhat_dot, innov_dot,
+                                        event_dot, event_hat_dot},
+                                       "qln_tracking_rollout_estimated_limited_jvp_host");
+}
+int qln_tracking_rollout_estimated_limited_vjp(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                               const double* H, int32_t ny, const double* model, const double* Zout,
+                                               const double* Xhat, const double* innov, const double* event,
+                                               const double* event_hat, const double* sat, const double* Zbar,
+                                               const double* Xhat_bar, const double* innov_bar, double* Zref_bar, double* K_bar,
+                                               double* Lgain_bar, double* x0_bar, double* xhat0_bar, double* model_bar) {
+    return tracking_estimated_vjp(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, event, event_hat, sat, true},
+                                  event != nullptr && event_hat != nullptr,
+                                  {Zbar, Xhat_bar, innov_bar, Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar, model_bar},
+                                  "qln_tracking_rollout_estimated_limited_vjp");
+}
+int qln_tracking_rollout_estimated_limited_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
+                                                    const double* H, int32_t ny, const double* model, const double* Zout,
+                                                    const double* Xhat, const double* innov, const double* event,
+                                                    const double* event_hat, const double* sat, const double* Zbar,
+                                                    const double* Xhat_bar, const double* innov_bar, double* Zref_bar,
+                                                    double* K_bar, double* Lgain_bar, double* x0_bar, double* xhat0_bar,
+                                                    double* model_bar) {
+    return tracking_estimated_vjp_host(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, event, event_hat, sat, true},
+                                       event != nullptr && event_hat != nullptr,
+                                       {Zbar, Xhat_bar, innov_bar, Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar, model_bar},
+                                       "qln_tracking_rollout_estimated_limited_vjp_host");
 }
 
 // ------------------------------------------------------------------ host-pointer (MOI) mode

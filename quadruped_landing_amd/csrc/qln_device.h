@@ -336,11 +336,13 @@ hipError_t launch_tracking_kalman(const BatchParams& p, const double* Zout, cons
 // The roll-out of the plant and the estimator side by side (qln_tracking_rollout_estimated / _guarded): Lgain [B][N][15][ny] and
 // H [ny][15] on the device; vnoise [B][N][ny], wnoise [B][N-1][15], x0, xhat0 [B][15], model and K may be null; Xhat [B][N][15],
 // innov [B][N][ny] may be null; event and event_hat [B][QLN_TOUCHDOWN_INFO_STRIDE] or null, with guarded only.
+// lim (null: none), a host array of QLN_FORCE_LIMITS_N doubles: the applied forces are clamped by the plant's contact mode
+// (qln_tracking_rollout_estimated_limited), and sat [B][N-1] (null: not written; with lim only) gets the saturation codes.
 hipError_t launch_tracking_rollout_estimated(const BatchParams& p, const double* Zref, const double* K, const double* Lgain,
                                              const double* H, int ny, const double* vnoise, const double* wnoise,
                                              const double* x0, const double* xhat0, const double* model, double* Zout,
                                              double* Xhat, double* innov, bool guarded, double* event, double* event_hat,
-                                             hipStream_t stream);
+                                             const double* lim, double* sat, hipStream_t stream);
 // The sweeps through the estimate-feedback roll-out (qln_tracking_rollout_estimated_jvp / _vjp, qln_tracking_kernels.hip).  What
 // both read: the roll-out's inputs and the trajectory it produced; event and event_hat (both or neither) select the guarded
 // blocks.  innov is read only with a tangent or cotangent of Lgain.
@@ -360,10 +362,12 @@ struct EstimatedVjpArgs {
     const double *Zbar, *Xhat_bar, *innov_bar;
     double *Zref_bar, *K_bar, *Lgain_bar, *x0_bar, *xhat0_bar, *model_bar;
 };
+// sat [B][N-1] (null: none): the limited roll-out's saturation codes, which select the sweeps at that active set
+// (qln_tracking_rollout_estimated_limited_jvp / _vjp)
 hipError_t launch_tracking_rollout_estimated_jvp(const BatchParams& p, const EstimatedSweepIn& in, const EstimatedJvpArgs& a,
-                                                 hipStream_t stream);
+                                                 const double* sat, hipStream_t stream);
 hipError_t launch_tracking_rollout_estimated_vjp(const BatchParams& p, const EstimatedSweepIn& in, const EstimatedVjpArgs& a,
-                                                 hipStream_t stream);
+                                                 const double* sat, hipStream_t stream);
 // batched Gauss-Newton step on the constraint violation, CGLS per problem in LDS (qln_solver_kernels.hip)
 size_t gauss_newton_lds_bytes(int32_t N);
 hipError_t launch_gauss_newton_step(const BatchParams& p, const double* Z, const double* c, double* dZ, int max_iters,

@@ -87,6 +87,10 @@
 // (qln_tracking_rollout_estimated_jvp / _vjp and their _guarded forms), on the row-of-sixteen mapping of the
 // roll-out's own sweeps: a problem's two chains, the plant's along Zout and the estimator's along Xhat, each through
 // jvp_apply_row / vjp_apply_column, coupled by the measurement update (H from LDS, row j of L_k and column j of K_k per lane).
+//
+// These three also exist with the flag kLimit (qln_tracking_rollout_estimated_limited and its _jvp / _vjp): the
+// forces fed back from the estimate are clamped by the PLANT's contact state before the plant, the estimator or Zout read them,
+// and the two sweeps treat the channels of that record as constants in both chains.
 #include "qln_row16.h"
 
 #include <utility>
@@ -704,13 +708,17 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout(BatchParams P, const
 // same step twice: the plant's on (x, model[b]) and the estimator's on (xhat, the handle's model).  Products are formed as
 // k_tracking_rollout forms K dx: the first product, then fma in index order.
 // kGuard: both steps are guarded_step, each on a contact mode and a Touchdown record of its own.
-template <bool kGuard>
+// kLimit (qln_tracking_rollout_estimated_limited): the forces fed back from the estimate are clamped to lim
+// before they are stored and before either system's guard and step, as k_tracking_rollout<.., kLimit> clamps them, with the
+// limits of a standing or of a free foot by the PLANT's contact mode at the knot's start (its lane's mode, or the knot
+// schedule's): the limits are the plant's saturation, whatever the estimator believes.  sat (null: not written) gets the code.
+template <bool kGuard, bool kLimit = false>
 __global__ __launch_bounds__(kWave) void k_tracking_rollout_estimated(
     BatchParams P, const double* __restrict__ Hg, int ny, const double* __restrict__ Zref, const double* __restrict__ Kg,
     const double* __restrict__ Lg, const double* __restrict__ vnoise, const double* __restrict__ wnoise,
     const double* __restrict__ x0, const double* __restrict__ xhat0, const double* __restrict__ model,
     double* __restrict__ Zout, double* __restrict__ Xhat, double* __restrict__ innov_out, double* __restrict__ event,
-    double* __restrict__ event_hat) {
+    double* __restrict__ event_hat, ForceLimits lim, double* __restrict__ sat) {
     constexpr int NY = QLN_TRACK_NY_MAX;
     __shared__ double Hs[NY * 15];
     for (int i = threadIdx.x; i < 15 * ny; i += kWave) Hs[i] = Hg[i];
@@ -800,6 +808,17 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_estimated(
                 for (int i = 1; i < 15; ++i) du = fma(Kk[15 * m + i], dx[i], du);
                 u[m] = u[m] - du;
             }
+        }
+        if constexpr (kLimit) {
+            bool stand1, stand2;
+            if constexpr (kGuard) {
+                stand1 = mode != 2, stand2 = mode != 1;
+            } else {
+                const KnotMode md = knot_mode(k + 1, kt - 1, im);
+                stand1 = !md.f1free, stand2 = !md.f2free;
+            }
+            const double code = clamp_forces(lim, stand1, stand2, u);
+            if (sat) sat[(int64_t)b * (N - 1) + k] = code;
         }
 #pragma unroll
         for (int i = 0; i < 5; ++i) Zo[20 * k + 15 + i] = u[i];
@@ -2100,6 +2119,22 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_jvp(BatchParams P, c
 // loaded where they are used the kernels took 1.9 (forward; 2.9 guarded) and 1.7 to 1.8 times as long.  The two
 // chains' steps are kept apart by scheduling barriers: interleaved, two blocks' temporaries are live at once.
 
+// knot_load of Zout's knot for the two sweeps.  kLimit: lane 4's second entry, which repeats u_1 and which nobody reads, is
+// the knot's saturation code instead (code: its address), read back by row_bcast<4>: the same number of loads and of
+// registers as without the flag.  Carried as a value of its own, loaded beside the slices, the forward sweep took 15 to 20 %
+// longer than its sibling.
+template <bool kLimit>
+__device__ __forceinline__ void estimated_knot_load(const double* __restrict__ zk, const double* __restrict__ code, int ln, double& e0,
+                                                    double& e1) {
+    if constexpr (kLimit) {
+        e0 = zk[ln];
+        const double* q = (ln == 4) ? code : zk + 16 + (ln & 3);
+        e1 = *q;
+    } else {
+        knot_load(zk, ln, e0, e1);
+    }
+}
+
 // One chain's knot of the forward sweep: row j of [A B G] on (dx, dF, dh, md4).  kGuard: the guarded sweep's statement of the
 // knot (k_tracking_rollout_jvp), td saying that this is the chain's touchdown knot, with d tau and the clock's tangent left
 // in e_tau / e_clock there.
@@ -2164,8 +2199,13 @@ struct EstimatedJvpKnot {
 //   dF = Fref_dot - K_k (dxh - xref_dot) - Kdot_k (xhat_k - x_ref,k),  dh = href_dot                 (k < N-1)
 //   dx' = A^p dx + B^p (dF, dh) + G^p model_dot,   dxm' = A^e dxh + B^e (dF, dh)
 // kHasK: K is given (K_dot is a run-time argument of that path); kHasLd: Lgain_dot is, and innov with it.
-template <bool kGuard, bool kHasK, bool kHasLd>
-__global__ __launch_bounds__(kWave) void k_tracking_rollout_estimated_jvp(BatchParams P, EstimatedSweepIn in, EstimatedJvpArgs a) {
+// kLimit (qln_tracking_rollout_estimated_limited_jvp): a channel that rode a limit at knot k (sat, the limited
+// roll-out's record) was a constant: its dF is zero before anything reads it -- Zout_dot's u_k, both chains' B and both chains'
+// d tau at their own touchdown knots.  The knot's code is loaded one knot ahead in a slot of the knot's slices
+// (estimated_knot_load).
+template <bool kGuard, bool kHasK, bool kHasLd, bool kLimit = false>
+__global__ __launch_bounds__(kWave) void k_tracking_rollout_estimated_jvp(BatchParams P, EstimatedSweepIn in, EstimatedJvpArgs a,
+                                                                          const double* __restrict__ sat) {
     constexpr int NY = QLN_TRACK_NY_MAX;
     __shared__ double Hs[NY * 15];
     const int ny = in.ny;
@@ -2207,6 +2247,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_estimated_jvp(BatchP
     double* __restrict__ Ido = a.innov_dot ? a.innov_dot + io : nullptr;
     double dx = (own && a.x0_dot) ? a.x0_dot[(int64_t)bc * QLN_NX + j] : 0.0;
     double dxm = !own ? 0.0 : a.xhat0_dot ? a.xhat0_dot[(int64_t)bc * QLN_NX + j] : Zd ? Zd[j] : 0.0;
+    [[maybe_unused]] const double* __restrict__ Sb = kLimit ? sat + (int64_t)bc * (N - 1) : nullptr;
     // the knot's slices are loaded one knot ahead: the gains' rows for every knot, the rest for the knots that take a step
     auto load = [&](EstimatedJvpKnot& s, int k) {
         const double* __restrict__ Lk = Lb + (int64_t)k * (15 * ny);
@@ -2220,7 +2261,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_estimated_jvp(BatchP
             s.ivl = ik[min(ln, ny - 1)];
         }
         if (k == N - 1) return;
-        knot_load(Zo + 20 * k, ln, s.z0, s.z1);
+        estimated_knot_load<kLimit>(Zo + 20 * k, kLimit ? Sb + k : nullptr, ln, s.z0, s.z1);
         s.xh = Xh[(int64_t)k * QLN_NX + j];
         if (Zd) knot_load(Zd + 20 * k, ln, s.zd0, s.zd1);
         if constexpr (kHasK) {
@@ -2294,6 +2335,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_estimated_jvp(BatchP
                 dF[m] = dF[m] - row_sum16(own ? t : 0.0);
             }
         }
+        if constexpr (kLimit) limit_zero4(limit_mask(row_bcast<4>(z1)), dF);
         // ---- the two chains' steps, one after the other: two blocks live at once do not fit the registers ----
         KnotMode md, mdh;
         if constexpr (kGuard) {
@@ -2412,8 +2454,13 @@ __device__ __forceinline__ VjpLane vjp_lane(int j, const Model& M) {
 // with Zref_bar[x_k] = K_k'ubar[0:4], Zref_bar[u_k] = ubar, Kbar_k = -ubar[0:4] (xhat_k - x_ref,k)'.  The plant's chain is applied
 // first, onto Zbar[u_k], as k_tracking_rollout_vjp applies it; the estimator's adds to it.
 // kHasK: K is given; kHasLb: Lgain_bar is asked for, and innov given with it.
-template <bool kGuard, bool kHasK, bool kHasLb>
-__global__ __launch_bounds__(kWave) void k_tracking_rollout_estimated_vjp(BatchParams P, EstimatedSweepIn in, EstimatedVjpArgs a) {
+// kLimit (qln_tracking_rollout_estimated_limited_vjp): ubar[0:4] of a channel that rode a limit at knot k (sat)
+// is zero after both chains' B' and taubar have been added onto it and before K_k'ubar, K_bar and Zref_bar read it, so that the
+// sweep is the exact transpose of the limited forward one.  The knot's code is loaded one knot ahead in a slot of the knot's
+// slices (estimated_knot_load).
+template <bool kGuard, bool kHasK, bool kHasLb, bool kLimit = false>
+__global__ __launch_bounds__(kWave) void k_tracking_rollout_estimated_vjp(BatchParams P, EstimatedSweepIn in, EstimatedVjpArgs a,
+                                                                          const double* __restrict__ sat) {
     constexpr int NY = QLN_TRACK_NY_MAX;
     __shared__ double Hs[NY * 15];
     const int ny = in.ny;
@@ -2464,6 +2511,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_estimated_vjp(BatchP
     // take a step
     const double* __restrict__ Xhb = a.Xhat_bar ? a.Xhat_bar + xo : nullptr;
     const double* __restrict__ Ibb = a.innov_bar ? a.innov_bar + io : nullptr;
+    [[maybe_unused]] const double* __restrict__ Sb = kLimit ? sat + (int64_t)bc * (N - 1) : nullptr;
     auto load = [&](EstimatedVjpKnot& s, int k) {
         const double* __restrict__ Lk = Lb + (int64_t)k * (15 * ny);
 #pragma unroll
@@ -2475,7 +2523,7 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_estimated_vjp(BatchP
             s.zb0 = Zb[20 * k + j];  // the last knot has no controls
             return;
         }
-        knot_load(Zo + 20 * k, ln, s.z0, s.z1);
+        estimated_knot_load<kLimit>(Zo + 20 * k, kLimit ? Sb + k : nullptr, ln, s.z0, s.z1);
         knot_load(Zb + 20 * k, ln, s.zb0, s.zb1);
         s.xh = Xh[(int64_t)k * QLN_NX + j];
         if constexpr (kHasK) {
@@ -2512,6 +2560,11 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_estimated_vjp(BatchP
             const double axh = estimated_vjp_step<kGuard, false>(lch, e, sg, ln, own, xhj, u[0], u[1], u[2], u[3], u[4], mdh, k == ksh,
                                                                  tauh, Mh, lamm, false, none, ubp, ub);
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (kLimit) {
+                const unsigned lmask = limit_mask(row_bcast<4>(cur.z1));
+#pragma unroll
+                for (int m = 0; m < 4; ++m) ub[m] = limited(lmask, m) ? 0.0 : ub[m];
+            }
             if constexpr (kHasK) kub = ((cur.kc[0] * ub[0] + cur.kc[1] * ub[1]) + cur.kc[2] * ub[2]) + cur.kc[3] * ub[3];
             xhb = own ? (xhb + axh) - kub : 0.0;
             if (kHasK && a.K_bar && valid && own) {
@@ -2710,38 +2763,52 @@ hipError_t launch_tracking_kalman(const BatchParams& p, const double* Zout, cons
     return hipGetLastError();
 }
 
-// The two instantiations of k_tracking_rollout_estimated: the knot schedule or the guard.
+// The four instantiations of k_tracking_rollout_estimated: the knot schedule or the guard, and lim (host, QLN_FORCE_LIMITS_N
+// doubles; null: none) sends it to the kLimit pair, which writes sat (null: not written).
 hipError_t launch_tracking_rollout_estimated(const BatchParams& p, const double* Zref, const double* K, const double* Lgain,
                                              const double* H, int ny, const double* vnoise, const double* wnoise,
                                              const double* x0, const double* xhat0, const double* model, double* Zout,
                                              double* Xhat, double* innov, bool guarded, double* event, double* event_hat,
-                                             hipStream_t stream) {
+                                             const double* lim, double* sat, hipStream_t stream) {
     if (ny < 1 || ny > QLN_TRACK_NY_MAX || !H || !Lgain) return hipErrorInvalidValue;
     if (!guarded && (event || event_hat)) return hipErrorInvalidValue;
+    if (sat && !lim) return hipErrorInvalidValue;
+    ForceLimits fl{};
+    if (lim)
+        for (int i = 0; i < QLN_FORCE_LIMITS_N; ++i) fl.v[i] = lim[i];
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3((p.B + kWave - 1) / kWave), dim3(kWave), 0, stream, p, H, ny, Zref, K, Lgain, vnoise,
-                           wnoise, x0, xhat0, model, Zout, Xhat, innov, event, event_hat);
+                           wnoise, x0, xhat0, model, Zout, Xhat, innov, event, event_hat, fl, sat);
     };
-    guarded ? go(k_tracking_rollout_estimated<true>) : go(k_tracking_rollout_estimated<false>);
+    if (lim)
+        guarded ? go(k_tracking_rollout_estimated<true, true>) : go(k_tracking_rollout_estimated<false, true>);
+    else
+        guarded ? go(k_tracking_rollout_estimated<true>) : go(k_tracking_rollout_estimated<false>);
     return hipGetLastError();
 }
 
 // The sweeps through it: eight instantiations each -- the knot schedule or the guard (both event records given), K or not,
-// and a tangent / cotangent of Lgain or not; every other optional argument is a run-time one.
+// and a tangent / cotangent of Lgain or not; every other optional argument is a run-time one.  sat (the limited roll-out's
+// saturation record; null: none) sends them to the eight kLimit instantiations.  It is the kernels' last argument, behind the
+// two structs, so that the instantiations without the flag read their arguments where they always did.
 static bool estimated_sweep_in_ok(const EstimatedSweepIn& in) {
     return in.ny >= 1 && in.ny <= QLN_TRACK_NY_MAX && in.Zref && in.Lgain && in.H && in.Zout && in.Xhat &&
            (in.event != nullptr) == (in.event_hat != nullptr);
 }
 
 hipError_t launch_tracking_rollout_estimated_jvp(const BatchParams& p, const EstimatedSweepIn& in, const EstimatedJvpArgs& a,
-                                                 hipStream_t stream) {
+                                                 const double* sat, hipStream_t stream) {
     if (!estimated_sweep_in_ok(in) || !a.Zout_dot) return hipErrorInvalidValue;
     if ((a.K_dot && !in.K) || (a.Lgain_dot && !in.innov)) return hipErrorInvalidValue;
     if (!in.event && (a.event_dot || a.event_hat_dot)) return hipErrorInvalidValue;
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, in, a); };
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, in, a, sat); };
     auto pick = [&](auto guard, auto hasK) {
-        a.Lgain_dot ? go(k_tracking_rollout_estimated_jvp<guard(), hasK(), true>)
-                    : go(k_tracking_rollout_estimated_jvp<guard(), hasK(), false>);
+        if (sat)
+            a.Lgain_dot ? go(k_tracking_rollout_estimated_jvp<guard(), hasK(), true, true>)
+                        : go(k_tracking_rollout_estimated_jvp<guard(), hasK(), false, true>);
+        else
+            a.Lgain_dot ? go(k_tracking_rollout_estimated_jvp<guard(), hasK(), true>)
+                        : go(k_tracking_rollout_estimated_jvp<guard(), hasK(), false>);
     };
     constexpr std::true_type yes{};
     constexpr std::false_type no{};
@@ -2753,13 +2820,17 @@ hipError_t launch_tracking_rollout_estimated_jvp(const BatchParams& p, const Est
 }
 
 hipError_t launch_tracking_rollout_estimated_vjp(const BatchParams& p, const EstimatedSweepIn& in, const EstimatedVjpArgs& a,
-                                                 hipStream_t stream) {
+                                                 const double* sat, hipStream_t stream) {
     if (!estimated_sweep_in_ok(in) || !a.Zbar) return hipErrorInvalidValue;
     if ((a.K_bar && !in.K) || (a.Lgain_bar && !in.innov)) return hipErrorInvalidValue;
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, in, a); };
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, in, a, sat); };
     auto pick = [&](auto guard, auto hasK) {
-        a.Lgain_bar ? go(k_tracking_rollout_estimated_vjp<guard(), hasK(), true>)
-                    : go(k_tracking_rollout_estimated_vjp<guard(), hasK(), false>);
+        if (sat)
+            a.Lgain_bar ? go(k_tracking_rollout_estimated_vjp<guard(), hasK(), true, true>)
+                        : go(k_tracking_rollout_estimated_vjp<guard(), hasK(), false, true>);
+        else
+            a.Lgain_bar ? go(k_tracking_rollout_estimated_vjp<guard(), hasK(), true>)
+                        : go(k_tracking_rollout_estimated_vjp<guard(), hasK(), false>);
     };
     constexpr std::true_type yes{};
     constexpr std::false_type no{};

@@ -1598,6 +1598,189 @@ class HybridNLP:
                                                             K.ctypes.data, _host_ptr(P)))
         return K, P
 
+    # -- contact-aware force limits in the estimate-feedback roll-out and its sweeps -------------------
+    def tracking_rollout_estimated_limited(self, Zref, limits, K, Lgain, H, vnoise=None, wnoise=None, x0=None, xhat0=None,
+                                           model=None, guarded=False, out=None, with_estimate=True, with_innovations=False,
+                                           with_events=True, with_sat=True):
+        """tracking_rollout_estimated with the forces fed back from the estimate clamped to `limits` (force_limits) before
+        anything reads them: Zout's controls, the plant's guard and step, the estimator's guard and step.  A foot takes the
+        standing pair where the PLANT's foot stands at the knot's start -- by the handle's knot schedule, or guarded by the
+        plant's own contact mode -- whatever the estimator believes (qln_evaluator.h).  Returns (Zout, Xhat, innov, events,
+        events_hat, sat): events and events_hat None when not guarded or without with_events, sat the (B, N-1) saturation
+        record of tracking_rollout_limited (None without with_sat), which the sweeps at this active set take."""
+        T = _torch()
+        lim = force_limits(limits)
+        Hh = self._measurement_rows(H)
+        ny = Hh.shape[0]
+        Hd = T.from_numpy(Hh).to(self._dev())
+        self._check(Zref, self.dims.z_total, "Zref")
+        out = self.new_Z() if out is None else out
+        self._check(out, self.dims.z_total, "out")
+        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        if Lgain is None:
+            raise ValueError("Lgain is required: the filter gains tracking_kalman returned")
+        lp = self._check(Lgain, self.B * self.N * n * ny, "Lgain")
+        vp = self._check_opt(vnoise, self.B * self.N * ny, "vnoise")
+        wp = self._check_opt(wnoise, self.B * (self.N - 1) * n, "wnoise")
+        xp = self._check_opt(x0, self.B * n, "x0")
+        hp = self._check_opt(xhat0, self.B * n, "xhat0")
+        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
+        new = lambda want, shape: T.zeros(shape, dtype=T.float64, device=self._dev()) if want else None  # noqa: E731
+        Xh = new(with_estimate, (self.B, self.N, n))
+        iv = new(with_innovations, (self.B, self.N, ny))
+        ev = new(guarded and with_events, (self.B, _lib.TOUCHDOWN_INFO_STRIDE))
+        eh = new(guarded and with_events, (self.B, _lib.TOUCHDOWN_INFO_STRIDE))
+        sat = new(with_sat, (self.B, self.N - 1))
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        _lib.check(_lib.lib().qln_tracking_rollout_estimated_limited(
+            self._h, Zref.data_ptr(), kp, lp, Hd.data_ptr(), ny, vp, wp, xp, hp, mp, lim.ctypes.data, int(bool(guarded)),
+            out.data_ptr(), ptr(Xh), ptr(iv), ptr(ev), ptr(eh), ptr(sat)))
+        return out, Xh, iv, ev, eh, sat
+
+    def tracking_rollout_estimated_limited_host(self, Zref, limits, K, Lgain, H, vnoise=None, wnoise=None, x0=None, xhat0=None,
+                                                model=None, guarded=False, with_estimate=True, with_innovations=False,
+                                                with_events=True, with_sat=True):
+        """The same with host arrays (synchronous): numpy (Zout (z_total,), Xhat, innov, events, events_hat, sat)."""
+        lim = force_limits(limits)
+        Hh = self._measurement_rows(H)
+        ny = Hh.shape[0]
+        Zref, K, x0, xhat0 = self._host_Z(Zref, "Zref"), self._host_K(K), self._host_x0(x0), self._host_x0(xhat0)
+        model = self._host_model(model)
+
+        def flat(a, size, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
+            if a.size != size:
+                raise ValueError(f"{name} has {a.size} entries, expected {size}")
+            return a
+
+        if Lgain is None:
+            raise ValueError("Lgain is required: the filter gains tracking_kalman_host returned")
+        Lg = flat(Lgain, self.B * self.N * n * ny, "Lgain")
+        vn = flat(vnoise, self.B * self.N * ny, "vnoise")
+        wn = flat(wnoise, self.B * (self.N - 1) * n, "wnoise")
+        out = np.zeros(self.dims.z_total)
+        Xh = np.zeros((self.B, self.N, n)) if with_estimate else None
+        iv = np.zeros((self.B, self.N, ny)) if with_innovations else None
+        ev = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if guarded and with_events else None
+        eh = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if guarded and with_events else None
+        sat = np.zeros((self.B, self.N - 1)) if with_sat else None
+        _lib.check(_lib.lib().qln_tracking_rollout_estimated_limited_host(
+            self._h, Zref.ctypes.data, _host_ptr(K), Lg.ctypes.data, Hh.ctypes.data, ny, _host_ptr(vn), _host_ptr(wn), _host_ptr(x0),
+            _host_ptr(xhat0), _host_ptr(model), lim.ctypes.data, int(bool(guarded)), out.ctypes.data, _host_ptr(Xh), _host_ptr(iv),
+            _host_ptr(ev), _host_ptr(eh), _host_ptr(sat)))
+        return out, Xh, iv, ev, eh, sat
+
+    def _estimated_limited_traj(self, Zref, K, Lgain, H, Zout, Xhat, sat, innov, model, events, events_hat, want_gain):
+        """_estimated_traj for the sweeps at fixed active set: both records or neither, then sat."""
+        if (events is None) != (events_hat is None):
+            raise ValueError("events and events_hat: both (the guarded blocks) or neither (the knot-scheduled ones)")
+        guarded = events is not None
+        ny, args, keep = self._estimated_traj(Zref, K, Lgain, H, Zout, Xhat, innov, model, guarded, events, events_hat, want_gain)
+        if not guarded:
+            args += [None, None]
+        args.append(self._sat_ptr(sat))
+        return guarded, ny, args, keep
+
+    def tracking_rollout_estimated_limited_jvp(self, Zref, K, Lgain, H, Zout, Xhat, sat, innov=None, model=None, events=None,
+                                               events_hat=None, Zref_dot=None, K_dot=None, Lgain_dot=None, x0_dot=None,
+                                               xhat0_dot=None, model_dot=None, out=None, with_estimate=True,
+                                               with_innovations=True, with_event_dot=True):
+        """Forward sweep of tracking_rollout_estimated_limited at the trajectory and the sat it returned, at fixed active set:
+        tracking_rollout_estimated_jvp with the tangent of every force that rode a limit zero, for everything that reads it.
+        events and events_hat both None: the knot-scheduled blocks, both given: the guarded ones.  Returns (Zout_dot, Xhat_dot,
+        innov_dot, event_dot, event_hat_dot), the last two None without records or with_event_dot."""
+        T = _torch()
+        guarded, ny, args, keep = self._estimated_limited_traj(Zref, K, Lgain, H, Zout, Xhat, sat, innov, model, events,
+                                                               events_hat, Lgain_dot is not None)
+        nk = self.B * (self.N - 1) * _lib.TRACK_NU * n
+        args += [self._check_opt(Zref_dot, self.dims.z_total, "Zref_dot"), self._check_opt(K_dot, nk, "K_dot"),
+                 self._check_opt(Lgain_dot, self.B * self.N * n * ny, "Lgain_dot"), self._check_opt(x0_dot, self.B * n, "x0_dot"),
+                 self._check_opt(xhat0_dot, self.B * n, "xhat0_dot"),
+                 self._check_opt(model_dot, self.B * _lib.MODEL_NP, "model_dot")]
+        out = self.new_Z() if out is None else out
+        new = lambda want, shape: T.zeros(shape, dtype=T.float64, device=self._dev()) if want else None  # noqa: E731
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        Xd, ivd = new(with_estimate, (self.B, self.N, n)), new(with_innovations, (self.B, self.N, ny))
+        ed = new(guarded and with_event_dot, (self.B, _lib.TOUCHDOWN_INFO_STRIDE))
+        ehd = new(guarded and with_event_dot, (self.B, _lib.TOUCHDOWN_INFO_STRIDE))
+        args += [self._check(out, self.dims.z_total, "out"), ptr(Xd), ptr(ivd), ptr(ed), ptr(ehd)]
+        _lib.check(_lib.lib().qln_tracking_rollout_estimated_limited_jvp(*args))
+        return out, Xd, ivd, ed, ehd
+
+    def tracking_rollout_estimated_limited_vjp(self, Zref, K, Lgain, H, Zout, Xhat, sat, Zbar, innov=None, model=None, events=None,
+                                               events_hat=None, Xhat_bar=None, innov_bar=None, want=None):
+        """Reverse sweep of tracking_rollout_estimated_limited, the exact adjoint of tracking_rollout_estimated_limited_jvp: the
+        rows of K_bar and the force entries of Zref_bar of a channel that rode a limit are exact zeros.  Arguments and returns
+        as tracking_rollout_estimated_vjp, with sat and with the records selecting the blocks."""
+        T = _torch()
+        default = want is None
+        want = self._vjp_want(K, want, self.ESTIMATED_VJP_OUTPUTS)
+        if default and innov is None:
+            want = tuple(w for w in want if w != "Lgain")
+        guarded, ny, args, keep = self._estimated_limited_traj(Zref, K, Lgain, H, Zout, Xhat, sat, innov, model, events,
+                                                               events_hat, "Lgain" in want)
+        args += [self._check(Zbar, self.dims.z_total, "Zbar"), self._check_opt(Xhat_bar, self.B * self.N * n, "Xhat_bar"),
+                 self._check_opt(innov_bar, self.B * self.N * ny, "innov_bar")]
+        new = lambda name, shape: T.zeros(shape, dtype=T.float64, device=self._dev()) if name in want else None  # noqa: E731
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        outs = (self.new_Z() if "Zref" in want else None, new("K", tracking_k_shape(self.B, self.N)),
+                new("Lgain", (self.B, self.N, n, ny)), new("x0", (self.B, n)), new("xhat0", (self.B, n)),
+                new("model", (self.B, _lib.MODEL_NP)))
+        _lib.check(_lib.lib().qln_tracking_rollout_estimated_limited_vjp(*args, *(ptr(o) for o in outs)))
+        return outs
+
+    def _host_estimated_limited_traj(self, Zref, K, Lgain, H, Zout, Xhat, sat, innov, model, events, events_hat, want_gain):
+        if (events is None) != (events_hat is None):
+            raise ValueError("events and events_hat: both (the guarded blocks) or neither (the knot-scheduled ones)")
+        guarded = events is not None
+        ny, args, keep, flat = self._host_estimated_traj(Zref, K, Lgain, H, Zout, Xhat, innov, model, guarded, events, events_hat,
+                                                         want_gain)
+        if not guarded:
+            args += [None, None]
+        keep.append(self._host_sat(sat))
+        args.append(keep[-1].ctypes.data)
+        return guarded, ny, args, keep, flat
+
+    def tracking_rollout_estimated_limited_jvp_host(self, Zref, K, Lgain, H, Zout, Xhat, sat, innov=None, model=None, events=None,
+                                                    events_hat=None, Zref_dot=None, K_dot=None, Lgain_dot=None, x0_dot=None,
+                                                    xhat0_dot=None, model_dot=None, with_estimate=True, with_innovations=True,
+                                                    with_event_dot=True):
+        """The same with host arrays (synchronous): numpy (Zout_dot (z_total,), Xhat_dot, innov_dot, event_dot, event_hat_dot).
+        A sat entry that is not a saturation code is refused."""
+        guarded, ny, args, keep, flat = self._host_estimated_limited_traj(Zref, K, Lgain, H, Zout, Xhat, sat, innov, model, events,
+                                                                          events_hat, Lgain_dot is not None)
+        tang = [None if Zref_dot is None else self._host_Z(Zref_dot, "Zref_dot"), self._host_K(K_dot),
+                flat(Lgain_dot, self.B * self.N * n * ny, "Lgain_dot"), self._host_x0(x0_dot), self._host_x0(xhat0_dot),
+                self._host_model(model_dot, "model_dot")]
+        out = np.zeros(self.dims.z_total)
+        Xd = np.zeros((self.B, self.N, n)) if with_estimate else None
+        ivd = np.zeros((self.B, self.N, ny)) if with_innovations else None
+        ed = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if guarded and with_event_dot else None
+        ehd = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if guarded and with_event_dot else None
+        args += [_host_ptr(a) for a in tang] + [out.ctypes.data, _host_ptr(Xd), _host_ptr(ivd), _host_ptr(ed), _host_ptr(ehd)]
+        _lib.check(_lib.lib().qln_tracking_rollout_estimated_limited_jvp_host(*args))
+        return out, Xd, ivd, ed, ehd
+
+    def tracking_rollout_estimated_limited_vjp_host(self, Zref, K, Lgain, H, Zout, Xhat, sat, Zbar, innov=None, model=None,
+                                                    events=None, events_hat=None, Xhat_bar=None, innov_bar=None, want=None):
+        """The same with host arrays (synchronous): numpy (Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar, model_bar)."""
+        default = want is None
+        want = self._vjp_want(K, want, self.ESTIMATED_VJP_OUTPUTS)
+        if default and innov is None:
+            want = tuple(w for w in want if w != "Lgain")
+        guarded, ny, args, keep, flat = self._host_estimated_limited_traj(Zref, K, Lgain, H, Zout, Xhat, sat, innov, model, events,
+                                                                          events_hat, "Lgain" in want)
+        cot = [self._host_Z(Zbar, "Zbar"), flat(Xhat_bar, self.B * self.N * n, "Xhat_bar"),
+               flat(innov_bar, self.B * self.N * ny, "innov_bar")]
+        new = lambda name, shape: np.zeros(shape) if name in want else None  # noqa: E731
+        outs = (new("Zref", self.dims.z_total), new("K", tracking_k_shape(self.B, self.N)), new("Lgain", (self.B, self.N, n, ny)),
+                new("x0", (self.B, n)), new("xhat0", (self.B, n)), new("model", (self.B, _lib.MODEL_NP)))
+        _lib.check(_lib.lib().qln_tracking_rollout_estimated_limited_vjp_host(
+            *args, *(_host_ptr(a) for a in cot), *(_host_ptr(o) for o in outs)))
+        return outs
+
     def differentiable_rollout(self, Zref, K=None, x0=None, model=None, guarded=False, limits=None):
         """tracking_rollout as a torch autograd op: returns Zout, differentiable in Zref, K and x0 (each a float64 CUDA
         tensor or None).  The backward pass is one qln_tracking_rollout_vjp launch at the Zout the forward produced, a
@@ -1621,16 +1804,22 @@ class HybridNLP:
         return ModelRolloutFunction.apply(self, Zref, K, x0, model)
 
     def differentiable_estimated_rollout(self, Zref, K, Lgain, H, vnoise=None, wnoise=None, x0=None, xhat0=None, model=None,
-                                         guarded=False):
+                                         guarded=False, limits=None):
         """tracking_rollout_estimated as a torch autograd op: returns (Zout, Xhat, innov), and guarded also (events,
         events_hat).  Zout, Xhat and innov are differentiable in Zref, K, Lgain, x0, xhat0 and model (each a float64 CUDA
         tensor; K, x0, xhat0 and model may be None) at FIXED noise samples: the backward pass is one
         qln_tracking_rollout_estimated_vjp launch at the trajectory the forward produced, a forward-mode tangent
         (torch.autograd.forward_ad, torch.func.jvp) one qln_tracking_rollout_estimated_jvp launch; guarded, both go through
         the plant's and the estimator's touchdowns at fixed knots.  H, vnoise, wnoise and the event records are not
-        differentiable.  With xhat0 None the estimate starts on Zref's first knot and Zref carries its gradient."""
-        from .rollout_grad import EstimatedRolloutFunction
+        differentiable.  With xhat0 None the estimate starts on Zref's first knot and Zref carries its gradient.
+        With limits (eight numbers, force_limits) it is tracking_rollout_estimated_limited and returns sat, the (B, N-1)
+        saturation record, as one more, last output, not differentiable; both autograd modes then run the sweeps at that
+        active set (tracking_rollout_estimated_limited_vjp / _jvp)."""
+        from .rollout_grad import EstimatedLimitedRolloutFunction, EstimatedRolloutFunction
 
+        if limits is not None:
+            return EstimatedLimitedRolloutFunction.apply(self, Zref, K, Lgain, x0, xhat0, model, H, vnoise, wnoise,
+                                                         force_limits(limits), bool(guarded))
         return EstimatedRolloutFunction.apply(self, Zref, K, Lgain, x0, xhat0, model, H, vnoise, wnoise, bool(guarded))
 
     def split_hvals(self, hvals):

@@ -237,3 +237,69 @@ class EstimatedRolloutFunction(torch.autograd.Function):
             out = ctx.nlp.tracking_rollout_estimated_jvp(Zref, K, Lgain, ctx.H, Zout, Xhat, innov, model, ctx.guarded, ev, eh, zd,
                                                          kd, ld, xd, hd if ctx.has_xhat0 else None, md, with_event_dot=False)
             return (*out[:3], *none)
+
+
+class EstimatedLimitedRolloutFunction(torch.autograd.Function):
+    """(Zout, Xhat, innov[, events, events_hat], sat) = estimate-feedback rollout within force limits(Zref, K, Lgain, x0, xhat0,
+    model; H, vnoise, wnoise, limits, guarded): qln_tracking_rollout_estimated_limited.  EstimatedRolloutFunction with the
+    sweeps at the active set the forward produced, qln_tracking_rollout_estimated_limited_vjp / _jvp; limits (eight numbers)
+    is not a tensor, and sat and the event records are marked non-differentiable."""
+
+    @staticmethod
+    def forward(nlp, Zref, K, Lgain, x0, xhat0, model, H, vnoise, wnoise, limits, guarded):
+        Zref, K, Lgain, x0, xhat0, model, vnoise, wnoise = _launchable((Zref, K, Lgain, x0, xhat0, model, vnoise, wnoise))
+        Zout, Xhat, innov, ev, eh, sat = nlp.tracking_rollout_estimated_limited(Zref, limits, K, Lgain, H, vnoise, wnoise, x0, xhat0,
+                                                                                model, guarded=guarded, with_innovations=True)
+        return (Zout, Xhat, innov, ev, eh, sat) if guarded else (Zout, Xhat, innov, sat)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        nlp, Zref, K, Lgain, x0, xhat0, model, H, _, _, _, guarded = inputs
+        Zout, Xhat, innov, *events, sat = output
+        ctx.nlp, ctx.H, ctx.guarded, ctx.has_xhat0 = nlp, H, guarded, xhat0 is not None
+        ctx.shapes = [None if t is None else t.shape for t in (K, Lgain, x0, xhat0, model)]
+        ctx.mark_non_differentiable(*events, sat)
+        ctx.save_for_backward(Zref, K, Lgain, model, Zout, Xhat, innov, sat, *events)
+        ctx.save_for_forward(Zref, K, Lgain, model, Zout, Xhat, innov, sat, *events)
+
+    @staticmethod
+    def backward(ctx, Zbar, Xhat_bar, innov_bar, *_):
+        need = ctx.needs_input_grad[1:7]
+        names = ("Zref", "K", "Lgain", "x0", "xhat0", "model")
+        saved = (_plain(t) for t in (*ctx.saved_tensors, Zbar, Xhat_bar, innov_bar))
+        Zref, K, Lgain, model, Zout, Xhat, innov, sat, *rest = saved
+        *events, Zbar, Xhat_bar, innov_bar = rest
+        want = [w for w, on in zip(names, need) if on and not (w == "K" and K is None)]
+        if not want:
+            return (None,) * 12
+        if ctx.has_xhat0 and "xhat0" not in want:
+            want.append("xhat0")  # a given xhat0 keeps its cotangent out of Zref_bar whether or not it is asked for
+        with torch._C._DisableFuncTorch():
+            Zref, K, Lgain, model, Zout, Xhat, innov, sat, Zbar, Xhat_bar, innov_bar, *events = _launchable(
+                (Zref, K, Lgain, model, Zout, Xhat, innov, sat, Zbar, Xhat_bar, innov_bar, *events))
+            ev, eh = events or (None, None)
+            zb, *bars = ctx.nlp.tracking_rollout_estimated_limited_vjp(Zref, K, Lgain, ctx.H, Zout, Xhat, sat, Zbar, innov, model,
+                                                                       ev, eh, Xhat_bar, innov_bar, want)
+            bars = [None if b is None or shape is None or not on else b.reshape(shape)
+                    for b, shape, on in zip(bars, ctx.shapes, need[1:])]
+        return (None, zb if need[0] else None, *bars, None, None, None, None, None)
+
+    @staticmethod
+    def jvp(ctx, _, *dots):
+        Zref, K, Lgain, model, Zout, Xhat, innov, sat, *events = (_plain(t) for t in ctx.saved_tensors)
+        none = (None,) * (len(events) + 1)
+        with torch._C._DisableFuncTorch():
+            Zref, K, Lgain, model, Zout, Xhat, innov, sat, *events = _launchable(
+                (Zref, K, Lgain, model, Zout, Xhat, innov, sat, *events))
+            zd, kd, ld, xd, hd, md = _launchable(_plain(t) for t in dots[:6])
+            if K is None:
+                kd = None
+            if all(t is None for t in (zd, kd, ld, xd, hd, md)):
+                return (torch.zeros_like(Zout), torch.zeros_like(Xhat), torch.zeros_like(innov), *none)
+            if ctx.has_xhat0 and hd is None:
+                hd = torch.zeros_like(Xhat[:, 0])  # a given xhat0 without a tangent does not follow Zref_dot
+            ev, eh = events or (None, None)
+            out = ctx.nlp.tracking_rollout_estimated_limited_jvp(Zref, K, Lgain, ctx.H, Zout, Xhat, sat, innov, model, ev, eh, zd,
+                                                                 kd, ld, xd, hd if ctx.has_xhat0 else None, md,
+                                                                 with_event_dot=False)
+            return (*out[:3], *none)
