@@ -264,7 +264,8 @@ int qln_gauss_newton_step(qln_handle* h, const double* Z, const double* c, doubl
  * f of the returned Z (the bits qln_eval_objective gives for it), violation of the returned Z (what
  * qln_constraint_violation gives for its eval_c!, and solve()'s bounds on theta and quirk Q6's on the knots after the
  * first), final penalty rho, status (0 = converged to tol_violation, 1 = iteration limit, 2 = no descent at the largest
- * penalty), augmented cost, last accepted step length, sum of h, LM mu at exit, five phase timers, 1 if the rescue phase
+ * penalty: an inner loop took twelve failed steps on end, which max_inner < 12 rules out before the rescue phase),
+ * augmented cost, last accepted step length, sum of h, LM mu at exit, five phase timers, 1 if the rescue phase
  * ran}.  f and the violation are measured on the trajectory that is handed back (the RK4 roll-out); status is the solver's
  * stop test on its own closed-form roll-out of the same controls, which differs from it by rounding (1e-15 per step): with
  * status = 0 the reported violation can exceed tol_violation by that much.  max_outer = 0 and rescue_outer = 0 make the
@@ -273,7 +274,7 @@ int qln_gauss_newton_step(qln_handle* h, const double* Z, const double* c, doubl
  * this evaluator: qln_eval_constraint + qln_constraint_violation and qln_eval_objective on the returned Z.  The iterates
  * themselves are held to a numpy restatement of the method run in double and in 80-bit extended precision
  * (tests/ilqr_ref.py, tests/test_gpu_ilqr_iterates.py): controls, counts, step lengths, mu and rho of single and of twelve
- * iterations.  The sweep differentiates the step the roll-out takes: the clock x[14] is kept through the jump, so a cost
+ * iterations, of runs to convergence, of steps without descent, a stalled inner loop and the rescue phase.  The sweep differentiates the step the roll-out takes: the clock x[14] is kept through the jump, so a cost
  * with a weight on it is handled consistently.
  * Needs a cost table.  QLN_ERR_UNSUPPORTED if a problem does not fit the LDS of a CU (N > ~650).  Stream-ordered.
  * The first call on a handle allocates the solver's device scratch, 494 N doubles per problem (158 KB at N = 40: step

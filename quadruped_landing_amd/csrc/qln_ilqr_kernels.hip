@@ -29,7 +29,11 @@
 // is checked by the evaluator itself: constraint violation and objective of the returned Z (tests/test_gpu_solve.py); the
 // iterates are held to tests/ilqr_ref.py, a numpy restatement of the method above run in float64 and in 80-bit long double:
 // single iterations, chained first iterations and twelve-iteration runs agree with it control by control within 100 times
-// the two precisions' own distance, and in every count, step length, mu and rho (tests/test_gpu_ilqr_iterates.py).
+// the two precisions' own distance, and in every count, step length, mu and rho (tests/test_gpu_ilqr_iterates.py).  So are
+// the stop tests, the failure paths and the rescue phase below, which twelve iterations never reach: runs to convergence,
+// steps without descent, a stalled inner loop with status 2, a saturating penalty and rescues of every kind, each also at
+// every shorter schedule (the FLOW_CASES of tests/ilqr_cases.py).  Not held that way: a failed pivot -- Quu is positive
+// definite in exact arithmetic, a pivot fails through rounding alone and no two precisions agree on it.
 #include "qln_row16.h"
 
 #include <cmath>
@@ -363,6 +367,10 @@ namespace {
 // solver's own measure: c rows it penalises + the bounds it penalises), 4 final rho, 5 status (0 = converged to tol,
 // 1 = outer limit reached, 2 = no descent step found at the last penalty), 6 augmented cost, 7 last accepted alpha,
 // 8 sum of h, 9 LM mu at exit
+// Status 2 needs an inner loop that stalls: mu starts at mu0 = 1e-6 in every multiplier update, a failure multiplies it by
+// 10 and an accepted step divides it by 3, so mu_max = 1e6 takes twelve failures in one inner loop.  With max_inner < 12
+// (the default is 6) the main phase can therefore neither stall nor report status 2; the rescue phase (60 iterations) can.
+// A later update whose stop test holds still turns a 2 into 0.
 template <int OCC>
 __global__ __launch_bounds__(kWave, OCC) void k_al_ilqr(BatchParams P, SolveParams S, double* __restrict__ Zio,
                                                       double* __restrict__ info, double* __restrict__ scratch) {

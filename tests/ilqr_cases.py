@@ -2,6 +2,8 @@
 and the tolerance rule of the latter: one statement, so that what the host tests establish about a case -- that it can see
 the clock row, that its twelve iterations are unambiguous -- holds for the case the kernel is then held to."""
 import contextlib
+import dataclasses
+import functools
 
 import numpy as np
 
@@ -78,6 +80,171 @@ def tolerances(r64, r80, o):
     eu = IR.control_error(r64.U, r80.U, o.h_max)
     ej = IR.relative_error(r64.J, r80.J)
     return max(TOL_MARGIN * eu, TOL_FLOOR), max(TOL_MARGIN * ej, TOL_FLOOR), eu, ej
+
+
+BRANCHES = ["stop test true", "inner_tol break", "no descent", "non-finite trial", "failed pivot", "stalled", "status 2",
+            "rho reaches rho_max", "rescue entered", "rescue cap binds", "rescue cap idle", "rescue converges",
+            "rescue ends at status 1", "rescue from the first iteration", "rescue inner loop past max_inner"]
+NOT_FOUND = ["failed pivot"]  # no unambiguous case exists (tests/test_ilqr_ref_host.py records the search)
+
+
+def branches(r, o):
+    """how often a run of the restatement takes each branch of BRANCHES (for the flags of the run as a whole: 0 or 1)"""
+    its, outs = r.iterations, r.outer_decisions
+    per_outer = {}
+    for i in its:
+        per_outer[i.outer] = per_outer.get(i.outer, 0) + 1
+    rescue_its = [n for k, n in per_outer.items() if k >= o.max_outer]
+    return {
+        "stop test true": sum(d[0] for d in outs),
+        "inner_tol break": sum(i.inner_break for i in its),
+        "no descent": sum(i.swept and not i.descent for i in its),
+        "non-finite trial": sum(i.swept and i.nonfinite > 0 for i in its),
+        "failed pivot": sum(not i.swept for i in its),
+        "stalled": sum(d[3] for d in outs),
+        "status 2": sum(d[4] == 2 for d in outs),
+        "rho reaches rho_max": sum(d[1] and d[5] >= o.rho_max for d in outs) if o.rho0 < o.rho_max else 0,  # a growth that the cap cuts or meets
+        "rescue entered": int(r.rescued),
+        "rescue cap binds": int(r.rescued and r.rho_at_rescue[0] > IR.RESCUE_RHO_CAP),
+        "rescue cap idle": int(r.rescued and r.rho_at_rescue[0] <= IR.RESCUE_RHO_CAP),
+        "rescue converges": int(r.rescued and r.status == 0),
+        "rescue ends at status 1": int(r.rescued and r.status == 1),
+        "rescue from the first iteration": int(r.rescued and o.max_outer == 0),
+        "rescue inner loop past max_inner": sum(n > o.max_inner for n in rescue_its),
+    }
+
+
+@dataclasses.dataclass(frozen=True)
+class FlowCase:
+    """a control-flow case: the problems `problems` of the batch `batch` under `options`, there for the branches `reaches`
+    (every problem of the case takes every one of them); prefixes: the case is also held at every shorter schedule"""
+    name: str
+    batch: tuple          # ("shape", name) | ("N12", seed) | ("N17", seed) | ("kt", seed)
+    problems: tuple
+    options: IR.Options
+    reaches: tuple
+    prefixes: bool = False
+
+
+_O = IR.Options
+_HARD = dict(rho0=1e6, rho_max=1e6)  # the penalty at its cap from the start: ill-conditioned sweeps, steps that do not descend
+# Every case was picked on the CPU, problem by problem: float64 and longdouble take the same decisions and no margin of the
+# longdouble run is under AMBIGUOUS (tests/test_ilqr_ref_host.py asserts it: the share of problems left out is 0).  Among the
+# problems that qualify, those with the smallest float64-longdouble distance were taken -- as long as that distance is
+# REPRESENTATIVE (flow_perturbed): the tolerance is 100 x one sample of float64's error, and at a penalty of 1e6 a sample can
+# be a hundred times smaller than the next.  N17-ragged b=2 (1e6, 1e4, 2, 16, 0) and kt-extremes b=2 (1e6, 1e4, 2, 24, 1) are
+# such problems: unambiguous, float64 spread of J 6.7e-6 and 5e-10 -- and float64 runs of the restatement from controls moved
+# by one ulp miss that tolerance by factors up to 2.3 and 1.6, as the kernel did (1.8 and 1.4, every discrete entry equal).
+# They say nothing about the kernel and are not cases; the host test holds every case and prefix to the perturbed runs.
+FLOW_CASES = [
+    # runs to convergence under the default options (about one random problem in four qualifies: the binding margin is
+    # `best`, the choice among sixteen trials, over some sixty iterations)
+    FlowCase("converges N12 seed 15", ("N12", 15), (2, 3, 5, 6, 7), _O(), ("stop test true", "inner_tol break")),
+    FlowCase("converges N12 seed 16", ("N12", 16), (0, 2, 3), _O(), ("stop test true", "inner_tol break")),
+    FlowCase("converges N17 ragged seed 3", ("N17", 3), (7,), _O(), ("stop test true", "inner_tol break")),
+    FlowCase("converges N17 ragged seed 1", ("N17", 1), (1,), _O(), ("stop test true", "inner_tol break")),
+    # kt-extremes-like batches: of the 197 problems of seeds 1 .. 190 that converge under the default options (both precisions
+    # agree in every decision of all of them) none qualifies -- their last iterations choose between two trials 1e-10 apart,
+    # the largest smallest margin is 1.7e-10 -- so the shape converges here to a tolerance it reaches before those iterations
+    FlowCase("converges kt-extremes tol 1e-4", ("shape", "kt-extremes"), (0,), _O(tol_violation=1e-4), ("stop test true", "inner_tol break")),
+    FlowCase("converges at rho_max N17 ragged seed 3", ("N17", 3), (5,), _O(), ("stop test true", "no descent", "rho reaches rho_max")),
+    # no descent: mu x 10 and the next iteration; the first one's trial costs overflow in float64
+    FlowCase("no descent N12", ("shape", "N12-kt5"), (0,), _O(**_HARD, h_prox=0.0, max_outer=2, max_inner=16),
+             ("no descent", "non-finite trial"), prefixes=True),
+    FlowCase("no descent N17 ragged", ("shape", "N17-ragged"), (4,), _O(**_HARD, max_outer=2, max_inner=16), ("no descent",), prefixes=True),
+    FlowCase("no descent kt-extremes", ("shape", "kt-extremes"), (0,), _O(**_HARD, h_prox=0.0, max_outer=2, max_inner=8), ("no descent",), prefixes=True),
+    FlowCase("no descent kt-extremes exact_h", ("shape", "kt-extremes"), (0,), _O(**_HARD, max_outer=2, max_inner=8, exact_h_gradient=1),
+             ("no descent",), prefixes=True),
+    # twelve failures on end: mu arrives at mu_max, the inner loop stalls, and with the penalty at its cap that is status 2
+    FlowCase("stalled, status 2 N12", ("shape", "N12-kt5"), (1,),
+             _O(**_HARD, exact_h_gradient=1, theta_min=-0.3, theta_max=0.3, max_outer=2, max_inner=30),
+             ("no descent", "stalled", "status 2"), prefixes=True),
+    # the penalty saturates at a small cap
+    FlowCase("rho saturates N12", ("shape", "N12-kt5"), tuple(range(8)), _O(rho0=3.0, rho_max=75.0, max_outer=6, max_inner=3), ("rho reaches rho_max",)),
+    # the rescue phase
+    FlowCase("rescue, cap idle, status 1 N12", ("shape", "N12-kt5"), (0, 2, 3, 4, 5, 7), _O(max_outer=3, max_inner=3, rescue_outer=2),
+             ("rescue entered", "rescue cap idle", "rescue ends at status 1", "rescue inner loop past max_inner", "inner_tol break"), prefixes=True),
+    FlowCase("rescue, cap idle, status 1 N17 ragged", ("shape", "N17-ragged"), (2, 5, 6), _O(max_outer=3, max_inner=3, rescue_outer=2),
+             ("rescue entered", "rescue cap idle", "rescue ends at status 1", "rescue inner loop past max_inner"), prefixes=True),
+    FlowCase("rescue from the first iteration N12", ("shape", "N12-kt5"), (5, 6, 7), _O(max_outer=0, max_inner=3, rescue_outer=2),
+             ("rescue entered", "rescue from the first iteration", "rescue inner loop past max_inner"), prefixes=True),
+    FlowCase("rescue, cap binds N12", ("shape", "N12-kt5"), (2,), _O(rho0=1e7, rho_max=1e8, max_outer=2, max_inner=3, rescue_outer=2),
+             ("rescue entered", "rescue cap binds", "rescue ends at status 1", "rescue inner loop past max_inner"), prefixes=True),
+    FlowCase("rescue, cap binds, no descent N12", ("shape", "N12-kt5"), (1,), _O(rho0=1e8, rho_max=1e8, max_outer=1, max_inner=3, rescue_outer=2),
+             ("rescue entered", "rescue cap binds", "no descent", "rescue inner loop past max_inner"), prefixes=True),
+    FlowCase("rescue converges N12 seed 14", ("N12", 14), (1,), _O(max_outer=8, rescue_outer=5),
+             ("rescue entered", "rescue cap idle", "rescue converges", "stop test true", "rescue inner loop past max_inner"), prefixes=True),
+]
+
+
+def flow_case(name):
+    return next(c for c in FLOW_CASES if c.name == name)
+
+
+@functools.lru_cache(maxsize=None)
+def flow_batch(spec):
+    kind, arg = spec
+    if kind == "shape":
+        return shape(arg)
+    if kind == "N12":
+        return PG.make_batch(8, 12, 5, 1, seed=arg, noise=0.0)
+    if kind == "N17":
+        return PG.make_batch(8, 17, seed=arg, ragged=True, noise=0.0)
+    if kind == "kt":  # kt-extremes at another seed
+        batch = PG.make_batch(4, 12, seed=arg, ragged=True, noise=0.0)
+        batch.k_trans[:] = [2, 12, 2, 12]
+        batch.init_mode[:] = [1, 1, 2, 2]
+        return batch
+    raise KeyError(spec)
+
+
+def flow_schedules(case):
+    """the case's own options last, before them (prefixes=True) every shorter schedule: the first multiplier update at every
+    smaller inner cap, every smaller max_outer without the rescue, and every smaller rescue_outer.  qln_solve reports
+    nothing per iteration: the (iters, mu, alpha, U) at the end of each prefix is what exposes the sequence of decisions."""
+    o = case.options
+    out = []
+    if case.prefixes:
+        if o.max_outer >= 1:
+            out += [dataclasses.replace(o, max_outer=1, max_inner=m, rescue_outer=0) for m in range(1, o.max_inner)]
+        out += [dataclasses.replace(o, max_outer=k, rescue_outer=0) for k in range(1, o.max_outer)]
+        out += [dataclasses.replace(o, rescue_outer=r) for r in range(o.rescue_outer)]
+    return [s for s in out if s != o] + [o]
+
+
+@functools.lru_cache(maxsize=None)
+def flow_reference(spec, b, o):
+    """(float64 run, longdouble run) of problem b of the batch under o, computed once per session and shared by the host
+    and the GPU tests (the per-iteration sweeps are dropped: a few hundred runs are kept)"""
+    P, U0 = problems(flow_batch(spec))
+    pair = reference_pair(P[b], U0[b], o, keep_trials=False)
+    for r in pair:
+        for it in r.iterations:
+            it.sweep = it.active_rows = None
+    return pair
+
+
+PERTURBED_RUNS = 4
+
+
+@functools.lru_cache(maxsize=None)
+def flow_perturbed(spec, b, o):
+    """Is the float64 run's distance from the longdouble run, which sets the tolerance, representative of float64's error on
+    this problem?  PERTURBED_RUNS float64 runs of the restatement from the guess's controls moved by -1, 0 or +1 ulp each,
+    held to the check the kernel is held to -> (all take the unperturbed run's decisions, largest e(U) / tolerance, largest
+    relative error of J / tolerance), both against the unperturbed longdouble run.  A problem whose own perturbed float64
+    runs miss the tolerance cannot tell a wrong kernel from a right one."""
+    P, U0 = problems(flow_batch(spec))
+    r64, r80 = flow_reference(spec, b, o)
+    tol_u, tol_j = tolerances(r64, r80, o)[:2]
+    rng = np.random.default_rng(1000 + b)
+    same, worst_u, worst_j = True, 0.0, 0.0
+    for _ in range(PERTURBED_RUNS):
+        r = IR.solve(P[b], U0[b] * (1 + 2.0 ** -52 * rng.integers(-1, 2, U0[b].shape)), o, np.float64, keep_trials=False)
+        same = same and r.decisions() == r64.decisions()
+        worst_u = max(worst_u, IR.control_error(r.U, r80.U, o.h_max) / tol_u)
+        worst_j = max(worst_j, IR.relative_error(r.J, r80.J) / tol_j)
+    return same, worst_u, worst_j
 
 
 def ambiguous(r64, r80):

@@ -8,7 +8,16 @@ Tolerance  per problem 100 x e(U_float64, U_longdouble), floored at 1e-13, again
            relatively by the same construction; outer, iters, rho, status, alpha, mu equal to the float64 run's exactly.
            The margin of 100 stands for the kernel's other summation order, its fused multiply-adds and refined reciprocal:
            an error of the kind and size of the float64 run's own.  A wrong term moves the controls by 1e-3 or more.
-The returned controls are the accepted trial's; the states are replaced by an RK4 roll-out and are not compared."""
+The returned controls are the accepted trial's; the states are replaced by an RK4 roll-out and are not compared.
+
+Control flow (section h): twelve iterations take none of the solver's stop tests, failure paths or its rescue phase
+(tests/test_ilqr_ref_host.py prints the table).  tests/ilqr_cases.py FLOW_CASES are problems picked on the CPU, one by one,
+that do: runs to convergence, steps without descent, a stalled inner loop and status 2, a saturating penalty, and the rescue
+phase with its penalty cap binding and idle, converging and not, from the first iteration, past max_inner.  qln_solve reports
+nothing per iteration, so a case with a failure path or a rescue is also held at every shorter schedule: the iters, mu, alpha
+and controls at the end of each prefix expose the sequence of decisions.  None of these problems may be left out, and
+info[15] (the rescue ran) is compared as well.  The hard-penalty cases are ill-conditioned: their float64 spread reaches
+2e-5, the tolerance 2e-3 of the scale; the exactly compared entries and the prefixes are what holds the control flow there."""
 import dataclasses
 
 import numpy as np
@@ -24,7 +33,7 @@ DISCRETE = [0, 1, 2, 3, 5, 6]  # positions of the discrete entries in INFO
 
 
 def _solve_gpu(batch, o, Zh=None):
-    """-> (controls (B, N-1, 5), info (B, 16), returned Z (B, n_nlp)) of HybridNLP.solve(..., rescue_outer=0)"""
+    """-> (controls (B, N-1, 5), info (B, 16), returned Z (B, n_nlp)) of HybridNLP.solve(..., rescue_outer=o.rescue_outer)"""
     import torch
     from quadruped_landing_amd import HybridNLP
 
@@ -37,17 +46,21 @@ def _solve_gpu(batch, o, Zh=None):
     return U, info.cpu().numpy().copy(), Zo
 
 
-def _hold(label, batch, o, gpu, U0=None, model=None, multi=False, witness=None, may_leave_out=True):
+def _hold(label, batch, o, gpu, U0=None, model=None, multi=False, witness=None, may_leave_out=True, only=None, reference=None,
+          rescued=False):
     """Compare the GPU's result with the yardstick problem by problem; returns the worst ratio of the GPU's error to the
     float64 run's own.  witness(iteration 0 of the longdouble run) -> bool: the case exercises what it is there for.
-    may_leave_out=False: a case qualified beforehand, of which no problem may be left out as ambiguous."""
+    may_leave_out=False: a case qualified beforehand, of which no problem may be left out as ambiguous.  only: the problems
+    of the batch that are compared (the batch is solved whole; the others were not qualified).  reference(b) -> the
+    (float64, longdouble) runs, where they are shared between tests.  rescued: info[15] is compared too."""
     Ug, info, _ = gpu
     worst_e, worst_ratio, left_out, seen = 0.0, 0.0, 0, False
     with IC.np_model(model):
         P, Uguess = IC.problems(batch)
-        for b in range(batch.B):
+        compared = list(range(batch.B)) if only is None else list(only)
+        for b in compared:
             u0 = Uguess[b] if U0 is None else U0[b]
-            r64, r80 = IC.reference_pair(P[b], u0, o)
+            r64, r80 = IC.reference_pair(P[b], u0, o) if reference is None else reference(b)
             if multi and IC.ambiguous(r64, r80):
                 left_out += 1
                 print(f"{label} b={b}: left out as ambiguous (smallest margin {r80.min_margin():.2e})")
@@ -72,9 +85,12 @@ def _hold(label, batch, o, gpu, U0=None, model=None, multi=False, witness=None, 
                   f"{ej_gpu:.2e} (tolerance {tol_j:.1e}); outer/iters/rho/status/alpha/mu = {gi[DISCRETE].tolist()}")
             worst_e, worst_ratio = max(worst_e, e), max(worst_ratio, ratio)
             assert np.array_equal(gi[DISCRETE], r64.info()[DISCRETE]), (label, b, gi.tolist(), r64.info().tolist())
+            if rescued:
+                assert info[b, 15] == float(r64.rescued), (label, b, info[b, 15], r64.rescued)
             assert e <= tol_u, (label, b, e, tol_u)
             assert ej_gpu <= tol_j, (label, b, ej_gpu, tol_j)
-    print(f"{label}: worst e = {worst_e:.2e}, worst ratio to the float64 spread = {worst_ratio:.2f}, left out {left_out} of {batch.B}")
+    print(f"{label}: worst e = {worst_e:.2e}, worst ratio to the float64 spread = {worst_ratio:.2f}, left out {left_out} of {batch.B}"
+          + ("" if only is None else f" (compared: problems {compared}, the ones qualified; the batch was solved whole)"))
     assert left_out * 8 <= batch.B, f"{label}: {left_out} of {batch.B} problems ambiguous"
     assert may_leave_out or left_out == 0, f"{label}: {left_out} problems left out of a case that was qualified"
     assert witness is None or seen, f"{label}: no problem of the batch exercises the term"
@@ -186,3 +202,20 @@ def test_one_nan_control_stays_in_its_problem():
     assert np.array_equal(Z_n[others], Z[others])
     assert np.array_equal(info_n[others, :10], info[others, :10])
     assert np.isnan(Z_n[3]).any()
+
+
+# ---- h: the control flow ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", IC.FLOW_CASES, ids=lambda c: c.name)
+def test_control_flow(case):
+    """A case of tests/ilqr_cases.py FLOW_CASES at its own schedule and at every prefix of it (flow_schedules): controls and J
+    within the module's tolerance, outer / iters / rho / status / alpha / mu and info[15] exactly, no problem left out."""
+    batch = IC.flow_batch(case.batch)
+    worst = 0.0
+    for o in IC.flow_schedules(case):
+        label = f"{case.name} [max_outer {o.max_outer} max_inner {o.max_inner} rescue_outer {o.rescue_outer}]"
+        tol = max(IC.tolerances(*IC.flow_reference(case.batch, b, o), o)[0] for b in case.problems)
+        print(f"{label}: largest tolerance on e(U) {tol:.1e}")
+        ratio = _hold(label, batch, o, _solve_gpu(batch, o), multi=True, may_leave_out=False, only=case.problems,
+                      reference=lambda b, o=o: IC.flow_reference(case.batch, b, o), rescued=True)
+        worst = max(worst, ratio)
+    print(f"{case.name}: worst ratio over {len(IC.flow_schedules(case))} schedules {worst:.2f} (bound {IC.TOL_MARGIN:g})")
