@@ -234,36 +234,45 @@ int acquire(qln_handle* h, HostRole r, bool mapped) {
     return QLN_OK;
 }
 
-// One argument of a host form: `n` doubles at `at` in its role's buffer (n < 0: the whole buffer), copied in from src
-// before the launch and back to dst after it.  Neither given: an optional argument the caller left NULL -- no buffer,
-// no copy, and the launch sees NULL.  view (out only): set to where the results can be read, the mapped buffer itself
-// (then nothing is copied to dst) or dst.
+// One argument of an entry point, declared once for both memory forms: `n` doubles at `at` in its role's buffer (n < 0: the
+// whole buffer).  Its direction is which of src and dst is given: in, out, or both.  Neither given: an optional argument the
+// caller left NULL -- no buffer, no copy, it overlaps nothing, and the launch sees NULL.  view (out only): set to where the
+// results can be read, the mapped buffer itself (then nothing is copied to dst) or dst.  ruled: the overlap rule looks at it.
+// staged: the host form stages it; where it does not, the launch sees NULL in the host form and lets another buffer stand in.
 struct HostArg {
     HostRole role;
     const double* src;
     double* dst;
     int64_t n, at;
     const double** view;
+    bool ruled = true, staged = true;
+    HostArg sized(int64_t count) const { HostArg a = *this; a.n = count; return a; }
+    HostArg ruled_if(bool on) const { HostArg a = *this; a.ruled = on; return a; }
+    HostArg staged_if(bool on) const { HostArg a = *this; a.staged = on; return a; }
+    bool passed() const { return src || dst; }
 };
+using HostArgs = std::initializer_list<HostArg>;
 HostArg copy_in(HostRole r, const double* p) { return {r, p, nullptr, -1, 0, nullptr}; }
 HostArg copy_out(HostRole r, double* p) { return {r, nullptr, p, -1, 0, nullptr}; }
 HostArg copy_inout(HostRole r, double* p) { return {r, p, p, -1, 0, nullptr}; }
+
+int64_t host_arg_size(const qln_handle* h, const HostArg& a) { return a.n < 0 ? host_role_size(h, a.role) : a.n; }
 
 // The one staging path of the host forms.  Mapped (h->zero_copy, unless the form passes may_map = false) or staged, it
 // acquires every passed argument's buffer, copies the inputs in, calls launch(d, mapped) with d[role] the device-visible
 // buffer of each passed argument (NULL for the rest), copies the outputs back and synchronises the stream once.
 template <class Launch>
-int host_call(qln_handle* h, std::initializer_list<HostArg> args, Launch&& launch, bool may_map = true) {
+int host_call(qln_handle* h, HostArgs args, Launch&& launch, bool may_map = true) {
     const bool mapped = may_map && h->zero_copy;
-    auto bytes = [&](const HostArg& a) { return (a.n < 0 ? host_role_size(h, a.role) : a.n) * sizeof(double); };
+    auto bytes = [&](const HostArg& a) { return host_arg_size(h, a) * sizeof(double); };
     double* d[kHostRoles] = {};
     for (const HostArg& a : args)
-        if (a.src || a.dst) {
+        if (a.passed() && a.staged) {
             if (int rc = acquire(h, a.role, mapped)) return rc;
             d[a.role] = mapped ? h->mapped[a.role].dev : h->staged[a.role];
         }
     for (const HostArg& a : args) {
-        if (!a.src) continue;
+        if (!a.src || !a.staged) continue;
         if (mapped) std::memcpy(h->mapped[a.role].host + a.at, a.src, bytes(a));
         else QLN_HIP(hipMemcpyAsync(d[a.role] + a.at, a.src, bytes(a), hipMemcpyHostToDevice, h->stream));
     }
@@ -288,6 +297,22 @@ int check_handle(const qln_handle* h) {
 
 int bind_device(const qln_handle* h) {
     QLN_HIP(hipSetDevice(h->device));
+    return QLN_OK;
+}
+
+// The two memory forms of an entry point: the caller's pointers are device memory, or host memory (qln_*_host).
+enum MemForm { kDeviceMem, kHostMem };
+
+// Runs one operation on its argument table.  Host form: host_call.  Device form: d[role] is the caller's own pointer of
+// every passed argument, staged by the host form or not, then the one launch -- no copy and no synchronisation.
+template <class Launch>
+int run_call(qln_handle* h, MemForm mem, HostArgs args, Launch&& launch) {
+    if (int rc = bind_device(h)) return rc;
+    if (mem == kHostMem) return host_call(h, args, launch);
+    double* d[kHostRoles] = {};
+    for (const HostArg& a : args)
+        if (a.passed()) d[a.role] = a.dst ? a.dst : const_cast<double*>(a.src);
+    QLN_HIP(launch(d, false));
     return QLN_OK;
 }
 
@@ -1128,53 +1153,24 @@ static int check_tracking_weights(const double* Q, const double* R, const double
     return QLN_OK;
 }
 
-// n doubles at p, an argument's buffer; a null p is an argument left out and overlaps nothing
-struct Span {
-    const double* p;
-    int64_t n;
-};
-
-static bool overlaps(Span a, Span b) {
-    if (!a.p || !b.p) return false;
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a.p), y = reinterpret_cast<uintptr_t>(b.p);
-    return x < y + (uintptr_t)b.n * sizeof(double) && y < x + (uintptr_t)a.n * sizeof(double);
-}
-
-// The one overlap rule of the entry points: no output may overlap an input or another output.
-static int check_no_overlap(std::initializer_list<Span> out, std::initializer_list<Span> in, const std::string& w) {
-    for (const Span& o : out) {
-        for (const Span& i : in)
-            if (overlaps(o, i)) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": an output overlaps an input");
-        for (const Span& q : out)
-            if (&q != &o && overlaps(o, q)) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": two outputs overlap");
+// The one overlap rule of the entry points, read from a call's argument table: no output -- an argument with a destination --
+// may overlap an input or another output, each over its declared extent.  An argument left NULL, or declared outside the
+// rule, overlaps nothing.
+static int check_no_overlap(const qln_handle* h, HostArgs args, const std::string& w) {
+    auto overlap = [&](const HostArg& a, const HostArg& b) {
+        if (!a.ruled || !b.ruled || !a.passed() || !b.passed()) return false;
+        const uintptr_t x = reinterpret_cast<uintptr_t>(a.dst ? a.dst : a.src);
+        const uintptr_t y = reinterpret_cast<uintptr_t>(b.dst ? b.dst : b.src);
+        return x < y + (uintptr_t)host_arg_size(h, b) * sizeof(double) && y < x + (uintptr_t)host_arg_size(h, a) * sizeof(double);
+    };
+    for (const HostArg& o : args) {
+        if (!o.dst) continue;
+        for (const HostArg& i : args)
+            if (!i.dst && overlap(o, i)) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": an output overlaps an input");
+        for (const HostArg& q : args)
+            if (q.dst && &q != &o && overlap(o, q)) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": two outputs overlap");
     }
     return QLN_OK;
-}
-
-// guarded: the sweep through the guard-triggered touchdown, which needs the roll-out's event records; its outputs may overlap
-// no input and not each other (the sweep on the handle's knot schedule has never looked)
-// limited: the design at the limited roll-out's active set, which needs its saturation record sat; event then selects the
-// guarded blocks, and without it the knot schedule's, which have no plant model
-static int check_tracking_lqr_args(const qln_handle* h, const double* Zref, const double* model, bool guarded, const double* event,
-                                   bool limited, const double* sat, const double* Q, const double* R, const double* Qf,
-                                   const double* K, const double* P, const char* who) {
-    // the limited form's checks need no handle and come first
-    if (limited && !sat)
-        return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null sat (the limited roll-out's saturation record)");
-    if (limited && !event && model)
-        return fail(QLN_ERR_INVALID_ARGUMENT,
-                    std::string(who) + ": model without event (the knot-scheduled design has no plant model)");
-    if (int rc = check_handle(h)) return rc;
-    if (!Zref || !K) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null Zref or K");
-    if (int rc = check_tracking_weights(Q, R, Qf, who)) return rc;
-    if (!limited) {
-        if (!guarded) return QLN_OK;
-        if (!event) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null event (the guarded roll-out's records)");
-    }
-    const qln_dims& D = h->dims;
-    return check_no_overlap({{K, tracking_k_total(D)}, {P, tracking_p_total(D)}},
-                            {{Zref, D.z_total}, {model, (int64_t)D.B * QLN_MODEL_NP},
-                             {event, (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE}, {sat, tracking_sat_total(D)}}, who);
 }
 
 // host forms only: every entry finite, and mb, mf, lb > 0 (the device forms do not look at the values)
@@ -1221,6 +1217,14 @@ static int check_host_sat(const qln_handle* h, const double* sat, const char* wh
     return QLN_OK;
 }
 
+// host forms only: the ny rows of the measurement matrix finite (the device forms do not look at the values)
+static int check_host_meas(const double* H, int32_t ny, const char* who) {
+    for (int i = 0; i < ny * QLN_NX; ++i)
+        if (!std::isfinite(H[i]))
+            return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": H is not finite (entry " + std::to_string(i) + ")");
+    return QLN_OK;
+}
+
 // NaN, or lo > hi, in one of the four {lo, hi} pairs of the force limits (+-inf: no limit on that side)
 static int check_force_limits(const double* lim, const char* who) {
     if (!lim) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null lim");
@@ -1231,638 +1235,641 @@ static int check_force_limits(const double* lim, const char* who) {
     return QLN_OK;
 }
 
-// The Riccati sweep: one body per memory form.  The entry point on the handle's knot schedule passes null for model and
-// event, and the launch then takes the kernel without its kGuard flag.
-static int tracking_lqr(qln_handle* h, const double* Zref, const double* model, bool guarded, const double* event, bool limited,
-                        const double* sat, const double* Qdiag, const double* Rdiag, const double* Qfdiag, double* K, double* P,
-                        const char* who) {
-    if (int rc = check_tracking_lqr_args(h, Zref, model, guarded, event, limited, sat, Qdiag, Rdiag, Qfdiag, K, P, who)) return rc;
-    if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_lqr(h->p, Qdiag, Rdiag, Qfdiag, Zref, model, event, sat, K, P, h->stream));
+// Every operation below is one argument struct, one check and one body for both memory forms.  The struct has a named field
+// per argument and is value-initialised by the entry points, so an optional they leave out is null.  The check holds what
+// needs no device, in the order the refusals have always had.  The body declares the argument table once -- role, pointer,
+// direction, extent, whether the overlap rule looks at it, whether the host form stages it -- and the rule, the staging and
+// the launch all read that table (check_no_overlap, run_call).  The host form alone then looks at the values of a model, an
+// event record, a saturation record and H, after the shared check and before it binds the device.
+
+// The Riccati sweep (k_tracking_lqr).  The entry point on the handle's knot schedule passes no model and no event, and the
+// launch then takes the kernel without its kGuard flag.
+// guarded: the sweep through the guard-triggered touchdown, which needs the roll-out's event records
+// limited: the design at the limited roll-out's active set, which needs its saturation record sat; event then selects the
+// guarded blocks, and without it the knot schedule's, which have no plant model
+struct LqrCall {
+    const double *Zref, *model, *event, *sat, *Q, *R, *Qf;
+    double *K, *P;
+    bool guarded, limited;
+};
+
+static int check_tracking_lqr_args(const qln_handle* h, const LqrCall& a, const char* who) {
+    // the limited form's checks need no handle and come first
+    if (a.limited && !a.sat)
+        return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null sat (the limited roll-out's saturation record)");
+    if (a.limited && !a.event && a.model)
+        return fail(QLN_ERR_INVALID_ARGUMENT,
+                    std::string(who) + ": model without event (the knot-scheduled design has no plant model)");
+    if (int rc = check_handle(h)) return rc;
+    if (!a.Zref || !a.K) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null Zref or K");
+    if (int rc = check_tracking_weights(a.Q, a.R, a.Qf, who)) return rc;
+    if (!a.limited && a.guarded && !a.event)
+        return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null event (the guarded roll-out's records)");
     return QLN_OK;
 }
 
-static int tracking_lqr_host(qln_handle* h, const double* Zref, const double* model, bool guarded, const double* event,
-                             bool limited, const double* sat, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
-                             double* K, double* P, const char* who) {
-    if (int rc = check_tracking_lqr_args(h, Zref, model, guarded, event, limited, sat, Qdiag, Rdiag, Qfdiag, K, P, who)) return rc;
-    if (int rc = check_host_models(h, model, who)) return rc;
-    if (int rc = check_host_events(h, event, who)) return rc;
-    if (int rc = check_host_sat(h, sat, who)) return rc;
-    if (int rc = bind_device(h)) return rc;
-    return host_call(h,
-                     {copy_in(kZ, Zref), copy_in(kModel, model), copy_in(kEvent, event), copy_in(kSat, sat), copy_out(kK, K),
-                      copy_out(kP, P)},
-                     [&](double* const* d, bool) {
-                         return qln::launch_tracking_lqr(h->p, Qdiag, Rdiag, Qfdiag, d[kZ], d[kModel], d[kEvent], d[kSat], d[kK],
-                                                         d[kP], h->stream);
-                     });
+static int tracking_lqr(qln_handle* h, MemForm mem, const LqrCall& a, const char* who) {
+    if (int rc = check_tracking_lqr_args(h, a, who)) return rc;
+    const HostArgs args = {copy_in(kZ, a.Zref), copy_in(kModel, a.model), copy_in(kEvent, a.event), copy_in(kSat, a.sat),
+                           copy_out(kK, a.K), copy_out(kP, a.P)};
+    // the sweep on the handle's knot schedule has never had an overlap rule
+    if (a.limited || a.guarded)
+        if (int rc = check_no_overlap(h, args, who)) return rc;
+    if (mem == kHostMem) {
+        if (int rc = check_host_models(h, a.model, who)) return rc;
+        if (int rc = check_host_events(h, a.event, who)) return rc;
+        if (int rc = check_host_sat(h, a.sat, who)) return rc;
+    }
+    return run_call(h, mem, args, [&](double* const* d, bool) {
+        return qln::launch_tracking_lqr(h->p, a.Q, a.R, a.Qf, d[kZ], d[kModel], d[kEvent], d[kSat], d[kK], d[kP], h->stream);
+    });
 }
 
 int qln_tracking_lqr(qln_handle* h, const double* Zref, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
                      double* K, double* P) {
-    return tracking_lqr(h, Zref, nullptr, false, nullptr, false, nullptr, Qdiag, Rdiag, Qfdiag, K, P, "qln_tracking_lqr");
+    LqrCall a{};
+    a.Zref = Zref; a.Q = Qdiag; a.R = Rdiag; a.Qf = Qfdiag; a.K = K; a.P = P;
+    return tracking_lqr(h, kDeviceMem, a, "qln_tracking_lqr");
 }
 int qln_tracking_lqr_host(qln_handle* h, const double* Zref, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
                           double* K, double* P) {
-    return tracking_lqr_host(h, Zref, nullptr, false, nullptr, false, nullptr, Qdiag, Rdiag, Qfdiag, K, P,
-                             "qln_tracking_lqr_host");
+    LqrCall a{};
+    a.Zref = Zref; a.Q = Qdiag; a.R = Rdiag; a.Qf = Qfdiag; a.K = K; a.P = P;
+    return tracking_lqr(h, kHostMem, a, "qln_tracking_lqr_host");
 }
 int qln_tracking_lqr_guarded(qln_handle* h, const double* Ztraj, const double* model, const double* event, const double* Qdiag,
                              const double* Rdiag, const double* Qfdiag, double* K, double* P) {
-    return tracking_lqr(h, Ztraj, model, true, event, false, nullptr, Qdiag, Rdiag, Qfdiag, K, P, "qln_tracking_lqr_guarded");
+    LqrCall a{};
+    a.Zref = Ztraj; a.model = model; a.event = event; a.guarded = true;
+    a.Q = Qdiag; a.R = Rdiag; a.Qf = Qfdiag; a.K = K; a.P = P;
+    return tracking_lqr(h, kDeviceMem, a, "qln_tracking_lqr_guarded");
 }
 int qln_tracking_lqr_guarded_host(qln_handle* h, const double* Ztraj, const double* model, const double* event,
                                   const double* Qdiag, const double* Rdiag, const double* Qfdiag, double* K, double* P) {
-    return tracking_lqr_host(h, Ztraj, model, true, event, false, nullptr, Qdiag, Rdiag, Qfdiag, K, P,
-                             "qln_tracking_lqr_guarded_host");
+    LqrCall a{};
+    a.Zref = Ztraj; a.model = model; a.event = event; a.guarded = true;
+    a.Q = Qdiag; a.R = Rdiag; a.Qf = Qfdiag; a.K = K; a.P = P;
+    return tracking_lqr(h, kHostMem, a, "qln_tracking_lqr_guarded_host");
 }
 // the design at the limited roll-out's active set: event selects the guarded blocks
 int qln_tracking_lqr_limited(qln_handle* h, const double* Ztraj, const double* model, const double* event, const double* sat,
                              const double* Qdiag, const double* Rdiag, const double* Qfdiag, double* K, double* P) {
-    return tracking_lqr(h, Ztraj, model, event != nullptr, event, true, sat, Qdiag, Rdiag, Qfdiag, K, P,
-                        "qln_tracking_lqr_limited");
+    LqrCall a{};
+    a.Zref = Ztraj; a.model = model; a.event = event; a.guarded = event != nullptr;
+    a.sat = sat; a.limited = true; a.Q = Qdiag; a.R = Rdiag; a.Qf = Qfdiag; a.K = K; a.P = P;
+    return tracking_lqr(h, kDeviceMem, a, "qln_tracking_lqr_limited");
 }
 int qln_tracking_lqr_limited_host(qln_handle* h, const double* Ztraj, const double* model, const double* event, const double* sat,
                                   const double* Qdiag, const double* Rdiag, const double* Qfdiag, double* K, double* P) {
-    return tracking_lqr_host(h, Ztraj, model, event != nullptr, event, true, sat, Qdiag, Rdiag, Qfdiag, K, P,
-                             "qln_tracking_lqr_limited_host");
+    LqrCall a{};
+    a.Zref = Ztraj; a.model = model; a.event = event; a.guarded = event != nullptr;
+    a.sat = sat; a.limited = true; a.Q = Qdiag; a.R = Rdiag; a.Qf = Qfdiag; a.K = K; a.P = P;
+    return tracking_lqr(h, kHostMem, a, "qln_tracking_lqr_limited_host");
 }
 
-// The roll-out and its two sweeps (k_tracking_rollout, _vjp, _jvp): one argument check and one body per operation and memory
-// form, with the per-problem plant as optional arguments.  The entry points without a model pass null for model, model_dot
-// and model_bar, and the launch then takes the kernels without their kModel flag.  The host forms validate a model's and an
-// event record's values (check_host_models, check_host_events above); the device forms do not look at them.
-// event: the guarded roll-out's records (null: none asked for)
+// The roll-out (k_tracking_rollout), with the per-problem plant as an optional argument: the entry points without a model
+// leave it null, and the launch then takes the kernel without its kModel flag.
+// guarded: the touchdown by the free foot's height, with its event records (may be null)
 // limited: the roll-out within the force limits lim, with its saturation record sat (may be null)
-static int check_tracking_rollout_args(const qln_handle* h, const double* Zref, const double* Zout, bool guarded,
-                                       const double* event, bool limited, const double* lim, const double* sat,
-                                       const char* who) {
-    if (limited) {
-        if (int rc = check_force_limits(lim, who)) return rc;
-        if (!guarded && event)
+struct RolloutCall {
+    const double *Zref, *K, *x0, *model, *lim;
+    double *Zout, *event, *sat;
+    bool guarded, limited;
+};
+
+static int check_tracking_rollout_args(const qln_handle* h, const RolloutCall& a, const char* who) {
+    if (a.limited) {
+        if (int rc = check_force_limits(a.lim, who)) return rc;
+        if (!a.guarded && a.event)
             return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": event with guarded == 0 (the knot schedule has no record)");
     }
     if (int rc = check_handle(h)) return rc;
-    if (!Zref || !Zout) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null Zref or Zout");
-    const int64_t ne = (int64_t)h->dims.B * QLN_TOUCHDOWN_INFO_STRIDE;
-    // K, x0 and model are not looked at
-    return check_no_overlap({{Zout, h->dims.z_total}, {event, ne}, {sat, tracking_sat_total(h->dims)}},
-                            {{Zref, h->dims.z_total}}, who);
-}
-
-// guarded: qln_tracking_rollout_guarded's touchdown by the free foot's height, with its event records (may be null)
-static int tracking_rollout(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
-                            double* Zout, bool guarded, double* event, bool limited, const double* lim, double* sat,
-                            const char* who) {
-    if (int rc = check_tracking_rollout_args(h, Zref, Zout, guarded, event, limited, lim, sat, who)) return rc;
-    if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout(h->p, Zref, K, x0, model, Zout, guarded, event, limited ? lim : nullptr, sat, h->stream));
+    if (!a.Zref || !a.Zout) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null Zref or Zout");
     return QLN_OK;
 }
 
-static int tracking_rollout_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
-                                 double* Zout, bool guarded, double* event, bool limited, const double* lim, double* sat,
-                                 const char* who) {
-    if (int rc = check_tracking_rollout_args(h, Zref, Zout, guarded, event, limited, lim, sat, who)) return rc;
-    if (int rc = check_host_models(h, model, who)) return rc;
-    if (int rc = bind_device(h)) return rc;
-    return host_call(h,
-                     {copy_in(kZ, Zref), copy_inout(kZio, Zout), copy_in(kK, K), copy_in(kX0, x0), copy_in(kModel, model),
-                      copy_out(kEvent, event), copy_out(kSat, sat)},
-                     [&](double* const* d, bool) {
-                         return qln::launch_tracking_rollout(h->p, d[kZ], d[kK], d[kX0], d[kModel], d[kZio], guarded, d[kEvent],
-                                                             limited ? lim : nullptr, d[kSat], h->stream);
-                     });
+static int tracking_rollout(qln_handle* h, MemForm mem, const RolloutCall& a, const char* who) {
+    if (int rc = check_tracking_rollout_args(h, a, who)) return rc;
+    // the overlap rule does not look at K, x0 and model
+    const HostArgs args = {copy_in(kZ, a.Zref), copy_inout(kZio, a.Zout), copy_in(kK, a.K).ruled_if(false),
+                           copy_in(kX0, a.x0).ruled_if(false), copy_in(kModel, a.model).ruled_if(false),
+                           copy_out(kEvent, a.event), copy_out(kSat, a.sat)};
+    if (int rc = check_no_overlap(h, args, who)) return rc;
+    if (mem == kHostMem)
+        if (int rc = check_host_models(h, a.model, who)) return rc;
+    return run_call(h, mem, args, [&](double* const* d, bool) {
+        return qln::launch_tracking_rollout(h->p, d[kZ], d[kK], d[kX0], d[kModel], d[kZio], a.guarded, d[kEvent],
+                                            a.limited ? a.lim : nullptr, d[kSat], h->stream);
+    });
 }
 
-// the reverse sweep: the handle first
-// guarded: the sweeps through the guard-triggered touchdown, which need the roll-out's event records
-// limited: the sweeps at the limited roll-out's active set, which need its saturation record sat (checked first: it needs no
-// handle); event then selects the guarded blocks
-static int check_tracking_vjp_args(const qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                   const double* model, bool guarded, const double* event, bool limited, const double* sat,
-                                   const double* Zbar, const double* Zref_bar, const double* K_bar, const double* x0_bar,
-                                   const double* model_bar, const char* who) {
-    if (limited && !sat)
-        return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null sat (the limited roll-out's saturation record)");
-    if (int rc = check_handle(h)) return rc;
-    const std::string w(who);
-    if (!Zref || !Zout || !Zbar) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref, Zout or Zbar");
-    if (guarded && !event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
-    if (K_bar && !K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_bar needs K (K == NULL has no gains to differentiate)");
-    const qln_dims& D = h->dims;
-    const int64_t nz = D.z_total, nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX, nm = (int64_t)D.B * QLN_MODEL_NP;
-    const int64_t ne = (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
-    return check_no_overlap({{Zref_bar, nz}, {K_bar, nk}, {x0_bar, nx}, {model_bar, nm}},
-                            {{Zref, nz}, {K, nk}, {Zout, nz}, {Zbar, nz}, {model, nm}, {event, ne}, {sat, tracking_sat_total(D)}},
-                            w);
-}
-
-static int tracking_rollout_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
-                                bool guarded, const double* event, bool limited, const double* sat, const double* Zbar,
-                                double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar, const char* who) {
-    if (int rc = check_tracking_vjp_args(h, Zref, K, Zout, model, guarded, event, limited, sat, Zbar, Zref_bar, K_bar, x0_bar,
-                                         model_bar, who))
-        return rc;
-    if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout_vjp(h->p, Zref, K, Zout, model, event, sat, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
-                                             h->stream));
-    return QLN_OK;
-}
-
-// Zref is staged only when K_bar asks for it (the kernel reads it for nothing else); otherwise Zout's buffer stands in.
-static int tracking_rollout_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                     const double* model, bool guarded, const double* event, bool limited, const double* sat,
-                                     const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar,
-                                     const char* who) {
-    if (int rc = check_tracking_vjp_args(h, Zref, K, Zout, model, guarded, event, limited, sat, Zbar, Zref_bar, K_bar, x0_bar,
-                                         model_bar, who))
-        return rc;
-    if (int rc = check_host_models(h, model, who)) return rc;
-    if (int rc = check_host_events(h, event, who)) return rc;
-    if (int rc = check_host_sat(h, sat, who)) return rc;
-    if (int rc = bind_device(h)) return rc;
-    return host_call(h,
-                     {copy_in(kV, Zout), copy_in(kZbar, Zbar), copy_in(kZ, K_bar ? Zref : nullptr), copy_in(kK, K),
-                      copy_in(kModel, model), copy_in(kEvent, event), copy_in(kSat, sat), copy_inout(kZio, Zref_bar),
-                      copy_out(kKbar, K_bar), copy_out(kX0, x0_bar), copy_out(kModelD, model_bar)},
-                     [&](double* const* d, bool) {
-                         return qln::launch_tracking_rollout_vjp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kModel], d[kEvent],
-                                                                 d[kSat], d[kZbar], d[kZio], d[kKbar], d[kX0], d[kModelD],
-                                                                 h->stream);
-                     });
-}
-
-// the forward sweep: the checks that need no handle come first
-static int check_tracking_jvp_args(const qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                   const double* model, bool guarded, const double* event, bool limited, const double* sat,
-                                   const double* Zref_dot, const double* K_dot, const double* x0_dot, const double* model_dot,
-                                   const double* Zout_dot, const double* event_dot, const char* who) {
-    const std::string w(who);
-    if (limited && !sat) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null sat (the limited roll-out's saturation record)");
-    if (limited && !event && event_dot)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": event_dot without event (the knot-scheduled sweep has no record)");
-    if (guarded && !event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
-    if (!Zref_dot && !K_dot && !x0_dot && !model_dot)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every tangent is NULL (no direction)");
-    if (K_dot && !K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_dot needs K (K == NULL has no gains to perturb)");
-    if (!Zref || !Zout || !Zout_dot) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref, Zout or Zout_dot");
-    if (int rc = check_handle(h)) return rc;
-    const qln_dims& D = h->dims;
-    const int64_t nz = D.z_total, nk = tracking_k_total(D), nx = (int64_t)D.B * QLN_NX, nm = (int64_t)D.B * QLN_MODEL_NP;
-    const int64_t ne = (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
-    return check_no_overlap({{Zout_dot, nz}, {event_dot, ne}},
-                            {{Zref, nz}, {K, nk}, {Zout, nz}, {model, nm}, {event, ne}, {sat, tracking_sat_total(D)}, {Zref_dot, nz},
-                             {K_dot, nk}, {x0_dot, nx}, {model_dot, nm}}, w);
-}
-
-static int tracking_rollout_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
-                                bool guarded, const double* event, bool limited, const double* sat, const double* Zref_dot,
-                                const double* K_dot, const double* x0_dot, const double* model_dot, double* Zout_dot,
-                                double* event_dot, const char* who) {
-    if (int rc = check_tracking_jvp_args(h, Zref, K, Zout, model, guarded, event, limited, sat, Zref_dot, K_dot, x0_dot, model_dot,
-                                         Zout_dot, event_dot, who))
-        return rc;
-    if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout_jvp(h->p, Zref, K, Zout, model, event, sat, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
-                                             event_dot, h->stream));
-    return QLN_OK;
-}
-
-// Zref is staged only when K_dot is given (the kernel reads it for nothing else); otherwise Zout's buffer stands in.
-static int tracking_rollout_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                     const double* model, bool guarded, const double* event, bool limited, const double* sat,
-                                     const double* Zref_dot, const double* K_dot, const double* x0_dot, const double* model_dot,
-                                     double* Zout_dot, double* event_dot, const char* who) {
-    if (int rc = check_tracking_jvp_args(h, Zref, K, Zout, model, guarded, event, limited, sat, Zref_dot, K_dot, x0_dot, model_dot,
-                                         Zout_dot, event_dot, who))
-        return rc;
-    if (int rc = check_host_models(h, model, who)) return rc;
-    if (int rc = check_host_events(h, event, who)) return rc;
-    if (int rc = check_host_sat(h, sat, who)) return rc;
-    if (int rc = bind_device(h)) return rc;
-    return host_call(h,
-                     {copy_in(kV, Zout), copy_in(kZ, K_dot ? Zref : nullptr), copy_in(kK, K), copy_in(kModel, model),
-                      copy_in(kEvent, event), copy_in(kSat, sat), copy_in(kZdot, Zref_dot), copy_in(kKdot, K_dot), copy_in(kX0, x0_dot),
-                      copy_in(kModelD, model_dot), copy_inout(kZio, Zout_dot), copy_out(kEventD, event_dot)},
-                     [&](double* const* d, bool) {
-                         return qln::launch_tracking_rollout_jvp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kModel], d[kEvent],
-                                                                 d[kSat], d[kZdot], d[kKdot], d[kX0], d[kModelD], d[kZio], d[kEventD],
-                                                                 h->stream);
-                     });
-}
-
-// the entry points: the forms without a model are the same path with null model arguments
 int qln_tracking_rollout(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout) {
-    return tracking_rollout(h, Zref, K, x0, nullptr, Zout, false, nullptr, false, nullptr, nullptr, "qln_tracking_rollout");
+    RolloutCall a{};
+    a.Zref = Zref; a.K = K; a.x0 = x0; a.Zout = Zout;
+    return tracking_rollout(h, kDeviceMem, a, "qln_tracking_rollout");
 }
 int qln_tracking_rollout_host(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout) {
-    return tracking_rollout_host(h, Zref, K, x0, nullptr, Zout, false, nullptr, false, nullptr, nullptr, "qln_tracking_rollout_host");
+    RolloutCall a{};
+    a.Zref = Zref; a.K = K; a.x0 = x0; a.Zout = Zout;
+    return tracking_rollout(h, kHostMem, a, "qln_tracking_rollout_host");
 }
 int qln_tracking_rollout_model(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
                                double* Zout) {
-    return tracking_rollout(h, Zref, K, x0, model, Zout, false, nullptr, false, nullptr, nullptr, "qln_tracking_rollout_model");
+    RolloutCall a{};
+    a.Zref = Zref; a.K = K; a.x0 = x0; a.model = model; a.Zout = Zout;
+    return tracking_rollout(h, kDeviceMem, a, "qln_tracking_rollout_model");
 }
 int qln_tracking_rollout_model_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
                                     double* Zout) {
-    return tracking_rollout_host(h, Zref, K, x0, model, Zout, false, nullptr, false, nullptr, nullptr, "qln_tracking_rollout_model_host");
+    RolloutCall a{};
+    a.Zref = Zref; a.K = K; a.x0 = x0; a.model = model; a.Zout = Zout;
+    return tracking_rollout(h, kHostMem, a, "qln_tracking_rollout_model_host");
 }
-
 int qln_tracking_rollout_guarded(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
                                  double* Zout, double* event) {
-    return tracking_rollout(h, Zref, K, x0, model, Zout, true, event, false, nullptr, nullptr, "qln_tracking_rollout_guarded");
+    RolloutCall a{};
+    a.Zref = Zref; a.K = K; a.x0 = x0; a.model = model; a.Zout = Zout; a.guarded = true; a.event = event;
+    return tracking_rollout(h, kDeviceMem, a, "qln_tracking_rollout_guarded");
 }
 int qln_tracking_rollout_guarded_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
                                       double* Zout, double* event) {
-    return tracking_rollout_host(h, Zref, K, x0, model, Zout, true, event, false, nullptr, nullptr,
-                                 "qln_tracking_rollout_guarded_host");
+    RolloutCall a{};
+    a.Zref = Zref; a.K = K; a.x0 = x0; a.model = model; a.Zout = Zout; a.guarded = true; a.event = event;
+    return tracking_rollout(h, kHostMem, a, "qln_tracking_rollout_guarded_host");
 }
 // the roll-out within contact-aware force limits: the knot-scheduled or the guarded one, with its saturation record
 int qln_tracking_rollout_limited(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
                                  const double* lim, int32_t guarded, double* Zout, double* event, double* sat) {
-    return tracking_rollout(h, Zref, K, x0, model, Zout, guarded != 0, event, true, lim, sat, "qln_tracking_rollout_limited");
+    RolloutCall a{};
+    a.Zref = Zref; a.K = K; a.x0 = x0; a.model = model; a.Zout = Zout;
+    a.guarded = guarded != 0; a.event = event; a.limited = true; a.lim = lim; a.sat = sat;
+    return tracking_rollout(h, kDeviceMem, a, "qln_tracking_rollout_limited");
 }
 int qln_tracking_rollout_limited_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
                                       const double* lim, int32_t guarded, double* Zout, double* event, double* sat) {
-    return tracking_rollout_host(h, Zref, K, x0, model, Zout, guarded != 0, event, true, lim, sat,
-                                 "qln_tracking_rollout_limited_host");
+    RolloutCall a{};
+    a.Zref = Zref; a.K = K; a.x0 = x0; a.model = model; a.Zout = Zout;
+    a.guarded = guarded != 0; a.event = event; a.limited = true; a.lim = lim; a.sat = sat;
+    return tracking_rollout(h, kHostMem, a, "qln_tracking_rollout_limited_host");
 }
+
+// Its reverse sweep (k_tracking_rollout_vjp).  model_bar goes with model, as in the roll-out.
+// guarded: the sweep through the guard-triggered touchdown, which needs the roll-out's event records
+// limited: the sweep at the limited roll-out's active set, which needs its saturation record sat (checked first: it needs no
+// handle); event then selects the guarded blocks
+struct RolloutVjpCall {
+    const double *Zref, *K, *Zout, *model, *event, *sat, *Zbar;
+    double *Zref_bar, *K_bar, *x0_bar, *model_bar;
+    bool guarded, limited;
+};
+
+static int check_tracking_vjp_args(const qln_handle* h, const RolloutVjpCall& a, const char* who) {
+    const std::string w(who);
+    if (a.limited && !a.sat) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null sat (the limited roll-out's saturation record)");
+    if (int rc = check_handle(h)) return rc;
+    if (!a.Zref || !a.Zout || !a.Zbar) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref, Zout or Zbar");
+    if (a.guarded && !a.event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
+    if (a.K_bar && !a.K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_bar needs K (K == NULL has no gains to differentiate)");
+    return QLN_OK;
+}
+
+static int tracking_rollout_vjp(qln_handle* h, MemForm mem, const RolloutVjpCall& a, const char* who) {
+    if (int rc = check_tracking_vjp_args(h, a, who)) return rc;
+    // the host form stages Zref only when K_bar asks for it (the kernel reads it for nothing else); otherwise Zout's buffer
+    // stands in
+    const HostArgs args = {copy_in(kV, a.Zout), copy_in(kZbar, a.Zbar), copy_in(kZ, a.Zref).staged_if(a.K_bar != nullptr),
+                           copy_in(kK, a.K), copy_in(kModel, a.model), copy_in(kEvent, a.event), copy_in(kSat, a.sat),
+                           copy_inout(kZio, a.Zref_bar), copy_out(kKbar, a.K_bar), copy_out(kX0, a.x0_bar),
+                           copy_out(kModelD, a.model_bar)};
+    if (int rc = check_no_overlap(h, args, who)) return rc;
+    if (mem == kHostMem) {
+        if (int rc = check_host_models(h, a.model, who)) return rc;
+        if (int rc = check_host_events(h, a.event, who)) return rc;
+        if (int rc = check_host_sat(h, a.sat, who)) return rc;
+    }
+    return run_call(h, mem, args, [&](double* const* d, bool) {
+        return qln::launch_tracking_rollout_vjp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kModel], d[kEvent], d[kSat],
+                                                d[kZbar], d[kZio], d[kKbar], d[kX0], d[kModelD], h->stream);
+    });
+}
+
 int qln_tracking_rollout_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
                              double* Zref_bar, double* K_bar, double* x0_bar) {
-    return tracking_rollout_vjp(h, Zref, K, Zout, nullptr, false, nullptr, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, nullptr, "qln_tracking_rollout_vjp");
+    RolloutVjpCall a{};
+    a.Zref = Zref; a.K = K; a.Zout = Zout; a.Zbar = Zbar; a.Zref_bar = Zref_bar; a.K_bar = K_bar; a.x0_bar = x0_bar;
+    return tracking_rollout_vjp(h, kDeviceMem, a, "qln_tracking_rollout_vjp");
 }
 int qln_tracking_rollout_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
                                   double* Zref_bar, double* K_bar, double* x0_bar) {
-    return tracking_rollout_vjp_host(h, Zref, K, Zout, nullptr, false, nullptr, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, nullptr,
-                                     "qln_tracking_rollout_vjp_host");
+    RolloutVjpCall a{};
+    a.Zref = Zref; a.K = K; a.Zout = Zout; a.Zbar = Zbar; a.Zref_bar = Zref_bar; a.K_bar = K_bar; a.x0_bar = x0_bar;
+    return tracking_rollout_vjp(h, kHostMem, a, "qln_tracking_rollout_vjp_host");
 }
 int qln_tracking_rollout_model_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
                                    const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar) {
-    return tracking_rollout_vjp(h, Zref, K, Zout, model, false, nullptr, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
-                                "qln_tracking_rollout_model_vjp");
+    RolloutVjpCall a{};
+    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.Zbar = Zbar;
+    a.Zref_bar = Zref_bar; a.K_bar = K_bar; a.x0_bar = x0_bar; a.model_bar = model_bar;
+    return tracking_rollout_vjp(h, kDeviceMem, a, "qln_tracking_rollout_model_vjp");
 }
 int qln_tracking_rollout_model_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                         const double* model, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
                                         double* model_bar) {
-    return tracking_rollout_vjp_host(h, Zref, K, Zout, model, false, nullptr, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
-                                     "qln_tracking_rollout_model_vjp_host");
-}
-
-int qln_tracking_rollout_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zref_dot,
-                             const double* K_dot, const double* x0_dot, double* Zout_dot) {
-    return tracking_rollout_jvp(h, Zref, K, Zout, nullptr, false, nullptr, false, nullptr, Zref_dot, K_dot, x0_dot, nullptr, Zout_dot, nullptr,
-                                "qln_tracking_rollout_jvp");
-}
-int qln_tracking_rollout_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                  const double* Zref_dot, const double* K_dot, const double* x0_dot, double* Zout_dot) {
-    return tracking_rollout_jvp_host(h, Zref, K, Zout, nullptr, false, nullptr, false, nullptr, Zref_dot, K_dot, x0_dot, nullptr, Zout_dot,
-                                     nullptr, "qln_tracking_rollout_jvp_host");
-}
-int qln_tracking_rollout_model_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
-                                   const double* Zref_dot, const double* K_dot, const double* x0_dot, const double* model_dot,
-                                   double* Zout_dot) {
-    return tracking_rollout_jvp(h, Zref, K, Zout, model, false, nullptr, false, nullptr, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot, nullptr,
-                                "qln_tracking_rollout_model_jvp");
-}
-int qln_tracking_rollout_model_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                        const double* model, const double* Zref_dot, const double* K_dot, const double* x0_dot,
-                                        const double* model_dot, double* Zout_dot) {
-    return tracking_rollout_jvp_host(h, Zref, K, Zout, model, false, nullptr, false, nullptr, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
-                                     nullptr, "qln_tracking_rollout_model_jvp_host");
-}
-
-// the sweeps through the guard-triggered touchdown: the same path with the roll-out's event records
-int qln_tracking_rollout_guarded_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
-                                     const double* event, const double* Zref_dot, const double* K_dot, const double* x0_dot,
-                                     const double* model_dot, double* Zout_dot, double* event_dot) {
-    return tracking_rollout_jvp(h, Zref, K, Zout, model, true, event, false, nullptr, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot, event_dot,
-                                "qln_tracking_rollout_guarded_jvp");
-}
-int qln_tracking_rollout_guarded_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                          const double* model, const double* event, const double* Zref_dot, const double* K_dot,
-                                          const double* x0_dot, const double* model_dot, double* Zout_dot, double* event_dot) {
-    return tracking_rollout_jvp_host(h, Zref, K, Zout, model, true, event, false, nullptr, Zref_dot, K_dot, x0_dot, model_dot, Zout_dot,
-                                     event_dot, "qln_tracking_rollout_guarded_jvp_host");
+    RolloutVjpCall a{};
+    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.Zbar = Zbar;
+    a.Zref_bar = Zref_bar; a.K_bar = K_bar; a.x0_bar = x0_bar; a.model_bar = model_bar;
+    return tracking_rollout_vjp(h, kHostMem, a, "qln_tracking_rollout_model_vjp_host");
 }
 int qln_tracking_rollout_guarded_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
                                      const double* event, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
                                      double* model_bar) {
-    return tracking_rollout_vjp(h, Zref, K, Zout, model, true, event, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
-                                "qln_tracking_rollout_guarded_vjp");
+    RolloutVjpCall a{};
+    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.guarded = true; a.event = event;
+    a.Zbar = Zbar; a.Zref_bar = Zref_bar; a.K_bar = K_bar; a.x0_bar = x0_bar; a.model_bar = model_bar;
+    return tracking_rollout_vjp(h, kDeviceMem, a, "qln_tracking_rollout_guarded_vjp");
 }
 int qln_tracking_rollout_guarded_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                           const double* model, const double* event, const double* Zbar, double* Zref_bar,
                                           double* K_bar, double* x0_bar, double* model_bar) {
-    return tracking_rollout_vjp_host(h, Zref, K, Zout, model, true, event, false, nullptr, Zbar, Zref_bar, K_bar, x0_bar, model_bar,
-                                     "qln_tracking_rollout_guarded_vjp_host");
+    RolloutVjpCall a{};
+    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.guarded = true; a.event = event;
+    a.Zbar = Zbar; a.Zref_bar = Zref_bar; a.K_bar = K_bar; a.x0_bar = x0_bar; a.model_bar = model_bar;
+    return tracking_rollout_vjp(h, kHostMem, a, "qln_tracking_rollout_guarded_vjp_host");
+}
+int qln_tracking_rollout_limited_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
+                                     const double* event, const double* sat, const double* Zbar, double* Zref_bar, double* K_bar,
+                                     double* x0_bar, double* model_bar) {
+    RolloutVjpCall a{};
+    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.guarded = event != nullptr; a.event = event; a.limited = true;
+    a.sat = sat; a.Zbar = Zbar; a.Zref_bar = Zref_bar; a.K_bar = K_bar; a.x0_bar = x0_bar; a.model_bar = model_bar;
+    return tracking_rollout_vjp(h, kDeviceMem, a, "qln_tracking_rollout_limited_vjp");
+}
+int qln_tracking_rollout_limited_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                          const double* model, const double* event, const double* sat, const double* Zbar,
+                                          double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar) {
+    RolloutVjpCall a{};
+    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.guarded = event != nullptr; a.event = event; a.limited = true;
+    a.sat = sat; a.Zbar = Zbar; a.Zref_bar = Zref_bar; a.K_bar = K_bar; a.x0_bar = x0_bar; a.model_bar = model_bar;
+    return tracking_rollout_vjp(h, kHostMem, a, "qln_tracking_rollout_limited_vjp_host");
 }
 
-// the sweeps at the limited roll-out's active set: the same path with its saturation record; event selects the guarded blocks
+// Its forward sweep (k_tracking_rollout_jvp).  The checks that need no handle come first.  guarded and limited as in the
+// reverse sweep; event_dot goes with event.
+struct RolloutJvpCall {
+    const double *Zref, *K, *Zout, *model, *event, *sat, *Zref_dot, *K_dot, *x0_dot, *model_dot;
+    double *Zout_dot, *event_dot;
+    bool guarded, limited;
+};
+
+static int check_tracking_jvp_args(const qln_handle* h, const RolloutJvpCall& a, const char* who) {
+    const std::string w(who);
+    if (a.limited && !a.sat) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null sat (the limited roll-out's saturation record)");
+    if (a.limited && !a.event && a.event_dot)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": event_dot without event (the knot-scheduled sweep has no record)");
+    if (a.guarded && !a.event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
+    if (!a.Zref_dot && !a.K_dot && !a.x0_dot && !a.model_dot)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every tangent is NULL (no direction)");
+    if (a.K_dot && !a.K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_dot needs K (K == NULL has no gains to perturb)");
+    if (!a.Zref || !a.Zout || !a.Zout_dot) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref, Zout or Zout_dot");
+    return check_handle(h);
+}
+
+static int tracking_rollout_jvp(qln_handle* h, MemForm mem, const RolloutJvpCall& a, const char* who) {
+    if (int rc = check_tracking_jvp_args(h, a, who)) return rc;
+    // the host form stages Zref only when K_dot is given (the kernel reads it for nothing else); otherwise Zout's buffer
+    // stands in
+    const HostArgs args = {copy_in(kV, a.Zout), copy_in(kZ, a.Zref).staged_if(a.K_dot != nullptr), copy_in(kK, a.K),
+                           copy_in(kModel, a.model), copy_in(kEvent, a.event), copy_in(kSat, a.sat), copy_in(kZdot, a.Zref_dot),
+                           copy_in(kKdot, a.K_dot), copy_in(kX0, a.x0_dot), copy_in(kModelD, a.model_dot),
+                           copy_inout(kZio, a.Zout_dot), copy_out(kEventD, a.event_dot)};
+    if (int rc = check_no_overlap(h, args, who)) return rc;
+    if (mem == kHostMem) {
+        if (int rc = check_host_models(h, a.model, who)) return rc;
+        if (int rc = check_host_events(h, a.event, who)) return rc;
+        if (int rc = check_host_sat(h, a.sat, who)) return rc;
+    }
+    return run_call(h, mem, args, [&](double* const* d, bool) {
+        return qln::launch_tracking_rollout_jvp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kModel], d[kEvent], d[kSat],
+                                                d[kZdot], d[kKdot], d[kX0], d[kModelD], d[kZio], d[kEventD], h->stream);
+    });
+}
+
+int qln_tracking_rollout_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zref_dot,
+                             const double* K_dot, const double* x0_dot, double* Zout_dot) {
+    RolloutJvpCall a{};
+    a.Zref = Zref; a.K = K; a.Zout = Zout; a.Zref_dot = Zref_dot; a.K_dot = K_dot; a.x0_dot = x0_dot; a.Zout_dot = Zout_dot;
+    return tracking_rollout_jvp(h, kDeviceMem, a, "qln_tracking_rollout_jvp");
+}
+int qln_tracking_rollout_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                  const double* Zref_dot, const double* K_dot, const double* x0_dot, double* Zout_dot) {
+    RolloutJvpCall a{};
+    a.Zref = Zref; a.K = K; a.Zout = Zout; a.Zref_dot = Zref_dot; a.K_dot = K_dot; a.x0_dot = x0_dot; a.Zout_dot = Zout_dot;
+    return tracking_rollout_jvp(h, kHostMem, a, "qln_tracking_rollout_jvp_host");
+}
+int qln_tracking_rollout_model_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
+                                   const double* Zref_dot, const double* K_dot, const double* x0_dot, const double* model_dot,
+                                   double* Zout_dot) {
+    RolloutJvpCall a{};
+    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.Zref_dot = Zref_dot;
+    a.K_dot = K_dot; a.x0_dot = x0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot;
+    return tracking_rollout_jvp(h, kDeviceMem, a, "qln_tracking_rollout_model_jvp");
+}
+int qln_tracking_rollout_model_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                        const double* model, const double* Zref_dot, const double* K_dot, const double* x0_dot,
+                                        const double* model_dot, double* Zout_dot) {
+    RolloutJvpCall a{};
+    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.Zref_dot = Zref_dot;
+    a.K_dot = K_dot; a.x0_dot = x0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot;
+    return tracking_rollout_jvp(h, kHostMem, a, "qln_tracking_rollout_model_jvp_host");
+}
+int qln_tracking_rollout_guarded_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
+                                     const double* event, const double* Zref_dot, const double* K_dot, const double* x0_dot,
+                                     const double* model_dot, double* Zout_dot, double* event_dot) {
+    RolloutJvpCall a{};
+    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.guarded = true; a.event = event; a.Zref_dot = Zref_dot;
+    a.K_dot = K_dot; a.x0_dot = x0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.event_dot = event_dot;
+    return tracking_rollout_jvp(h, kDeviceMem, a, "qln_tracking_rollout_guarded_jvp");
+}
+int qln_tracking_rollout_guarded_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
+                                          const double* model, const double* event, const double* Zref_dot, const double* K_dot,
+                                          const double* x0_dot, const double* model_dot, double* Zout_dot, double* event_dot) {
+    RolloutJvpCall a{};
+    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.guarded = true; a.event = event; a.Zref_dot = Zref_dot;
+    a.K_dot = K_dot; a.x0_dot = x0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.event_dot = event_dot;
+    return tracking_rollout_jvp(h, kHostMem, a, "qln_tracking_rollout_guarded_jvp_host");
+}
 int qln_tracking_rollout_limited_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
                                      const double* event, const double* sat, const double* Zref_dot, const double* K_dot,
                                      const double* x0_dot, const double* model_dot, double* Zout_dot, double* event_dot) {
-    return tracking_rollout_jvp(h, Zref, K, Zout, model, event != nullptr, event, true, sat, Zref_dot, K_dot, x0_dot, model_dot,
-                                Zout_dot, event_dot, "qln_tracking_rollout_limited_jvp");
+    RolloutJvpCall a{};
+    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.guarded = event != nullptr;
+    a.event = event; a.limited = true; a.sat = sat; a.Zref_dot = Zref_dot; a.K_dot = K_dot;
+    a.x0_dot = x0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.event_dot = event_dot;
+    return tracking_rollout_jvp(h, kDeviceMem, a, "qln_tracking_rollout_limited_jvp");
 }
 int qln_tracking_rollout_limited_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                           const double* model, const double* event, const double* sat, const double* Zref_dot,
                                           const double* K_dot, const double* x0_dot, const double* model_dot, double* Zout_dot,
                                           double* event_dot) {
-    return tracking_rollout_jvp_host(h, Zref, K, Zout, model, event != nullptr, event, true, sat, Zref_dot, K_dot, x0_dot,
-                                     model_dot, Zout_dot, event_dot, "qln_tracking_rollout_limited_jvp_host");
-}
-int qln_tracking_rollout_limited_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
-                                     const double* event, const double* sat, const double* Zbar, double* Zref_bar, double* K_bar,
-                                     double* x0_bar, double* model_bar) {
-    return tracking_rollout_vjp(h, Zref, K, Zout, model, event != nullptr, event, true, sat, Zbar, Zref_bar, K_bar, x0_bar,
-                                model_bar, "qln_tracking_rollout_limited_vjp");
-}
-int qln_tracking_rollout_limited_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
-                                          const double* model, const double* event, const double* sat, const double* Zbar,
-                                          double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar) {
-    return tracking_rollout_vjp_host(h, Zref, K, Zout, model, event != nullptr, event, true, sat, Zbar, Zref_bar, K_bar, x0_bar,
-                                     model_bar, "qln_tracking_rollout_limited_vjp_host");
+    RolloutJvpCall a{};
+    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.guarded = event != nullptr;
+    a.event = event; a.limited = true; a.sat = sat; a.Zref_dot = Zref_dot; a.K_dot = K_dot;
+    a.x0_dot = x0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.event_dot = event_dot;
+    return tracking_rollout_jvp(h, kHostMem, a, "qln_tracking_rollout_limited_jvp_host");
 }
 
-// the covariance sweep (k_tracking_covariance).  The checks that need no handle come first.
-// guarded: the sweep through the guard-triggered touchdown, which needs the roll-out's event records and may return event_var
-static int check_tracking_covariance_args(const qln_handle* h, const double* Zout, const double* K, const double* model,
-                                          bool guarded, const double* event, const double* Sigma0, int32_t sigma0_batch,
-                                          const double* Wdiag, const double* Sigma, const double* marg, const double* event_var,
-                                          const char* who) {
-    const std::string w(who);
-    if (!Sigma && !marg && !event_var)
-        return fail(QLN_ERR_INVALID_ARGUMENT, guarded ? w + ": Sigma, marg and event_var are all NULL (nothing to compute)"
-                                                      : w + ": Sigma and marg are both NULL (nothing to compute)");
-    if (guarded && !event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
+static int check_tracking_wdiag(const double* Wdiag, const std::string& w) {
     if (Wdiag)
         for (int i = 0; i < QLN_NX; ++i)
             if (!(std::isfinite(Wdiag[i]) && Wdiag[i] >= 0.0))
                 return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Wdiag must be finite and >= 0 (entry " + std::to_string(i) + ")");
-    if (sigma0_batch < 1) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
-    if (int rc = check_handle(h)) return rc;
-    const qln_dims& D = h->dims;
-    if (sigma0_batch != 1 && sigma0_batch != D.B) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
-    if (!Zout || !Sigma0) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zout or Sigma0");
-    return check_no_overlap({{Sigma, tracking_p_total(D)}, {marg, tracking_marg_total(D)}, {event_var, (int64_t)D.B * 2}},
-                            {{Zout, D.z_total}, {K, tracking_k_total(D)}, {Sigma0, (int64_t)sigma0_batch * QLN_TRACK_P_NNZ},
-                             {model, (int64_t)D.B * QLN_MODEL_NP}, {event, (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE}}, w);
-}
-
-static int tracking_covariance(qln_handle* h, const double* Zout, const double* K, const double* model, bool guarded,
-                               const double* event, const double* Sigma0, int32_t sigma0_batch, const double* Wdiag,
-                               double* Sigma, double* marg, double* event_var, const char* who) {
-    if (int rc = check_tracking_covariance_args(h, Zout, K, model, guarded, event, Sigma0, sigma0_batch, Wdiag, Sigma, marg,
-                                                event_var, who))
-        return rc;
-    if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_covariance(h->p, Zout, K, model, event, Sigma0, sigma0_batch, Wdiag, Sigma, marg, event_var,
-                                            h->stream));
     return QLN_OK;
 }
 
-static int tracking_covariance_host(qln_handle* h, const double* Zout, const double* K, const double* model, bool guarded,
-                                    const double* event, const double* Sigma0, int32_t sigma0_batch, const double* Wdiag,
-                                    double* Sigma, double* marg, double* event_var, const char* who) {
-    if (int rc = check_tracking_covariance_args(h, Zout, K, model, guarded, event, Sigma0, sigma0_batch, Wdiag, Sigma, marg,
-                                                event_var, who))
-        return rc;
-    if (int rc = check_host_models(h, model, who)) return rc;
-    if (int rc = check_host_events(h, event, who)) return rc;
-    if (int rc = bind_device(h)) return rc;
-    HostArg s0 = copy_in(kCov0, Sigma0);
-    s0.n = (int64_t)sigma0_batch * QLN_TRACK_P_NNZ;  // the tiles the call reads, of the role's B
-    return host_call(h,
-                     {copy_in(kV, Zout), copy_in(kK, K), copy_in(kModel, model), copy_in(kEvent, event), s0,
-                      copy_out(kCov, Sigma), copy_out(kMarg, marg), copy_out(kEventVar, event_var)},
-                     [&](double* const* d, bool) {
-                         return qln::launch_tracking_covariance(h->p, d[kV], d[kK], d[kModel], d[kEvent], d[kCov0], sigma0_batch,
-                                                                Wdiag, d[kCov], d[kMarg], d[kEventVar], h->stream);
-                     });
+// The covariance sweep (k_tracking_covariance).  The checks that need no handle come first.
+// guarded: the sweep through the guard-triggered touchdown, which needs the roll-out's event records and may return event_var
+struct CovarianceCall {
+    const double *Zout, *K, *model, *event, *Sigma0;
+    int32_t sigma0_batch;
+    const double* Wdiag;
+    double *Sigma, *marg, *event_var;
+    bool guarded;
+};
+
+static int check_tracking_covariance_args(const qln_handle* h, const CovarianceCall& a, const char* who) {
+    const std::string w(who);
+    if (!a.Sigma && !a.marg && !a.event_var)
+        return fail(QLN_ERR_INVALID_ARGUMENT, a.guarded ? w + ": Sigma, marg and event_var are all NULL (nothing to compute)"
+                                                        : w + ": Sigma and marg are both NULL (nothing to compute)");
+    if (a.guarded && !a.event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
+    if (int rc = check_tracking_wdiag(a.Wdiag, w)) return rc;
+    if (a.sigma0_batch < 1) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
+    if (int rc = check_handle(h)) return rc;
+    if (a.sigma0_batch != 1 && a.sigma0_batch != h->dims.B)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
+    if (!a.Zout || !a.Sigma0) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zout or Sigma0");
+    return QLN_OK;
+}
+
+static int tracking_covariance(qln_handle* h, MemForm mem, const CovarianceCall& a, const char* who) {
+    if (int rc = check_tracking_covariance_args(h, a, who)) return rc;
+    // Sigma0: the tiles the call reads, of the role's B
+    const HostArgs args = {copy_in(kV, a.Zout), copy_in(kK, a.K), copy_in(kModel, a.model), copy_in(kEvent, a.event),
+                           copy_in(kCov0, a.Sigma0).sized((int64_t)a.sigma0_batch * QLN_TRACK_P_NNZ), copy_out(kCov, a.Sigma),
+                           copy_out(kMarg, a.marg), copy_out(kEventVar, a.event_var)};
+    if (int rc = check_no_overlap(h, args, who)) return rc;
+    if (mem == kHostMem) {
+        if (int rc = check_host_models(h, a.model, who)) return rc;
+        if (int rc = check_host_events(h, a.event, who)) return rc;
+    }
+    return run_call(h, mem, args, [&](double* const* d, bool) {
+        return qln::launch_tracking_covariance(h->p, d[kV], d[kK], d[kModel], d[kEvent], d[kCov0], a.sigma0_batch, a.Wdiag,
+                                               d[kCov], d[kMarg], d[kEventVar], h->stream);
+    });
 }
 
 int qln_tracking_covariance(qln_handle* h, const double* Zout, const double* K, const double* Sigma0, int32_t sigma0_batch,
                             const double* Wdiag, double* Sigma, double* marg) {
-    return tracking_covariance(h, Zout, K, nullptr, false, nullptr, Sigma0, sigma0_batch, Wdiag, Sigma, marg, nullptr,
-                               "qln_tracking_covariance");
+    CovarianceCall a{};
+    a.Zout = Zout; a.K = K; a.Sigma0 = Sigma0; a.sigma0_batch = sigma0_batch; a.Wdiag = Wdiag; a.Sigma = Sigma; a.marg = marg;
+    return tracking_covariance(h, kDeviceMem, a, "qln_tracking_covariance");
 }
 int qln_tracking_covariance_host(qln_handle* h, const double* Zout, const double* K, const double* Sigma0,
                                  int32_t sigma0_batch, const double* Wdiag, double* Sigma, double* marg) {
-    return tracking_covariance_host(h, Zout, K, nullptr, false, nullptr, Sigma0, sigma0_batch, Wdiag, Sigma, marg, nullptr,
-                                    "qln_tracking_covariance_host");
+    CovarianceCall a{};
+    a.Zout = Zout; a.K = K; a.Sigma0 = Sigma0; a.sigma0_batch = sigma0_batch; a.Wdiag = Wdiag; a.Sigma = Sigma; a.marg = marg;
+    return tracking_covariance(h, kHostMem, a, "qln_tracking_covariance_host");
 }
 int qln_tracking_covariance_guarded(qln_handle* h, const double* Zout, const double* K, const double* model, const double* event,
                                     const double* Sigma0, int32_t sigma0_batch, const double* Wdiag, double* Sigma, double* marg,
                                     double* event_var) {
-    return tracking_covariance(h, Zout, K, model, true, event, Sigma0, sigma0_batch, Wdiag, Sigma, marg, event_var,
-                               "qln_tracking_covariance_guarded");
+    CovarianceCall a{};
+    a.Zout = Zout; a.K = K; a.model = model; a.guarded = true; a.event = event; a.Sigma0 = Sigma0;
+    a.sigma0_batch = sigma0_batch; a.Wdiag = Wdiag; a.Sigma = Sigma; a.marg = marg; a.event_var = event_var;
+    return tracking_covariance(h, kDeviceMem, a, "qln_tracking_covariance_guarded");
 }
 int qln_tracking_covariance_guarded_host(qln_handle* h, const double* Zout, const double* K, const double* model,
                                          const double* event, const double* Sigma0, int32_t sigma0_batch, const double* Wdiag,
                                          double* Sigma, double* marg, double* event_var) {
-    return tracking_covariance_host(h, Zout, K, model, true, event, Sigma0, sigma0_batch, Wdiag, Sigma, marg, event_var,
-                                    "qln_tracking_covariance_guarded_host");
+    CovarianceCall a{};
+    a.Zout = Zout; a.K = K; a.model = model; a.guarded = true; a.event = event; a.Sigma0 = Sigma0;
+    a.sigma0_batch = sigma0_batch; a.Wdiag = Wdiag; a.Sigma = Sigma; a.marg = marg; a.event_var = event_var;
+    return tracking_covariance(h, kHostMem, a, "qln_tracking_covariance_guarded_host");
 }
 
-// the Kalman filter and the LQG covariance (k_tracking_kalman).  The checks that need no handle come first.
+// The Kalman filter and the LQG covariance (k_tracking_kalman).  The checks that need no handle come first.
 // guarded: through the guard-triggered touchdown, which needs the roll-out's event records and may return event_var
-static int check_tracking_kalman_args(const qln_handle* h, const double* Zout, const double* K, const double* model, bool guarded,
-                                      const double* event, const double* H, int32_t ny, const double* Vdiag, const double* Sigma0,
-                                      int32_t sigma0_batch, const double* Wdiag, const double* Lgain, const double* Pest,
-                                      const double* Sigma, const double* marg, const double* event_var, const char* who) {
-    const std::string w(who);
-    if (ny < 1 || ny > QLN_TRACK_NY_MAX)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
-    if (!Lgain && !Pest && !Sigma && !marg && !event_var)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every output is NULL (nothing to compute)");
-    if (!K && (Sigma || marg || event_var))
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Sigma, marg and event_var need K (K == NULL is the filter alone: Lgain and Pest)");
-    if (guarded && !event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
-    if (!H || !Vdiag) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null H or Vdiag");
-    for (int i = 0; i < ny; ++i)
-        if (!(std::isfinite(Vdiag[i]) && Vdiag[i] > 0.0))
-            return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Vdiag must be finite and > 0 (entry " + std::to_string(i) + ")");
-    if (Wdiag)
-        for (int i = 0; i < QLN_NX; ++i)
-            if (!(std::isfinite(Wdiag[i]) && Wdiag[i] >= 0.0))
-                return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Wdiag must be finite and >= 0 (entry " + std::to_string(i) + ")");
-    if (sigma0_batch < 1) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
-    if (int rc = check_handle(h)) return rc;
-    const qln_dims& D = h->dims;
-    if (sigma0_batch != 1 && sigma0_batch != D.B) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
-    if (!Zout || !Sigma0) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zout or Sigma0");
-    return check_no_overlap({{Lgain, tracking_gain_total(D, ny)}, {Pest, tracking_p_total(D)}, {Sigma, tracking_p_total(D)},
-                             {marg, tracking_marg_total(D)}, {event_var, (int64_t)D.B * 2}},
-                            {{Zout, D.z_total}, {K, tracking_k_total(D)}, {H, (int64_t)ny * QLN_NX},
-                             {Sigma0, (int64_t)sigma0_batch * QLN_TRACK_P_NNZ}, {model, (int64_t)D.B * QLN_MODEL_NP},
-                             {event, (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE}}, w);
-}
+struct KalmanCall {
+    const double *Zout, *K, *model, *event, *H;
+    int32_t ny;
+    const double *Vdiag, *Sigma0;
+    int32_t sigma0_batch;
+    const double* Wdiag;
+    double *Lgain, *Pest, *Sigma, *marg, *event_var;
+    bool guarded;
+};
 
-static int tracking_kalman(qln_handle* h, const double* Zout, const double* K, const double* model, bool guarded,
-                           const double* event, const double* H, int32_t ny, const double* Vdiag, const double* Sigma0,
-                           int32_t sigma0_batch, const double* Wdiag, double* Lgain, double* Pest, double* Sigma, double* marg,
-                           double* event_var, const char* who) {
-    if (int rc = check_tracking_kalman_args(h, Zout, K, model, guarded, event, H, ny, Vdiag, Sigma0, sigma0_batch, Wdiag, Lgain,
-                                            Pest, Sigma, marg, event_var, who))
-        return rc;
-    if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_kalman(h->p, Zout, K, model, event, H, ny, Vdiag, Sigma0, sigma0_batch, Wdiag, Lgain, Pest, Sigma,
-                                        marg, event_var, h->stream));
+static int check_tracking_kalman_args(const qln_handle* h, const KalmanCall& a, const char* who) {
+    const std::string w(who);
+    if (a.ny < 1 || a.ny > QLN_TRACK_NY_MAX)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
+    if (!a.Lgain && !a.Pest && !a.Sigma && !a.marg && !a.event_var)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every output is NULL (nothing to compute)");
+    if (!a.K && (a.Sigma || a.marg || a.event_var))
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Sigma, marg and event_var need K (K == NULL is the filter alone: Lgain and Pest)");
+    if (a.guarded && !a.event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
+    if (!a.H || !a.Vdiag) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null H or Vdiag");
+    for (int i = 0; i < a.ny; ++i)
+        if (!(std::isfinite(a.Vdiag[i]) && a.Vdiag[i] > 0.0))
+            return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Vdiag must be finite and > 0 (entry " + std::to_string(i) + ")");
+    if (int rc = check_tracking_wdiag(a.Wdiag, w)) return rc;
+    if (a.sigma0_batch < 1) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
+    if (int rc = check_handle(h)) return rc;
+    if (a.sigma0_batch != 1 && a.sigma0_batch != h->dims.B)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
+    if (!a.Zout || !a.Sigma0) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zout or Sigma0");
     return QLN_OK;
 }
 
-static int tracking_kalman_host(qln_handle* h, const double* Zout, const double* K, const double* model, bool guarded,
-                                const double* event, const double* H, int32_t ny, const double* Vdiag, const double* Sigma0,
-                                int32_t sigma0_batch, const double* Wdiag, double* Lgain, double* Pest, double* Sigma, double* marg,
-                                double* event_var, const char* who) {
-    if (int rc = check_tracking_kalman_args(h, Zout, K, model, guarded, event, H, ny, Vdiag, Sigma0, sigma0_batch, Wdiag, Lgain,
-                                            Pest, Sigma, marg, event_var, who))
-        return rc;
-    for (int i = 0; i < ny * QLN_NX; ++i)
-        if (!std::isfinite(H[i]))
-            return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": H is not finite (entry " + std::to_string(i) + ")");
-    if (int rc = check_host_models(h, model, who)) return rc;
-    if (int rc = check_host_events(h, event, who)) return rc;
-    if (int rc = bind_device(h)) return rc;
-    HostArg s0 = copy_in(kCov0, Sigma0), hm = copy_in(kH, H), lg = copy_out(kLgain, Lgain);
-    s0.n = (int64_t)sigma0_batch * QLN_TRACK_P_NNZ;  // the tiles the call reads, of the role's B
-    hm.n = (int64_t)ny * QLN_NX;                     // the rows the call reads, and the gains it writes, of the role's eight
-    lg.n = tracking_gain_total(h->dims, ny);
-    return host_call(h,
-                     {copy_in(kV, Zout), copy_in(kK, K), copy_in(kModel, model), copy_in(kEvent, event), hm, s0, lg,
-                      copy_out(kPest, Pest), copy_out(kCov, Sigma), copy_out(kMarg, marg), copy_out(kEventVar, event_var)},
-                     [&](double* const* d, bool) {
-                         return qln::launch_tracking_kalman(h->p, d[kV], d[kK], d[kModel], d[kEvent], d[kH], ny, Vdiag, d[kCov0],
-                                                            sigma0_batch, Wdiag, d[kLgain], d[kPest], d[kCov], d[kMarg],
-                                                            d[kEventVar], h->stream);
-                     });
+static int tracking_kalman(qln_handle* h, MemForm mem, const KalmanCall& a, const char* who) {
+    if (int rc = check_tracking_kalman_args(h, a, who)) return rc;
+    // the rows the call reads and the gains it writes, of the roles' eight; the tiles it reads, of the role's B
+    const HostArgs args = {copy_in(kV, a.Zout), copy_in(kK, a.K), copy_in(kModel, a.model), copy_in(kEvent, a.event),
+                           copy_in(kH, a.H).sized((int64_t)a.ny * QLN_NX),
+                           copy_in(kCov0, a.Sigma0).sized((int64_t)a.sigma0_batch * QLN_TRACK_P_NNZ),
+                           copy_out(kLgain, a.Lgain).sized(tracking_gain_total(h->dims, a.ny)), copy_out(kPest, a.Pest),
+                           copy_out(kCov, a.Sigma), copy_out(kMarg, a.marg), copy_out(kEventVar, a.event_var)};
+    if (int rc = check_no_overlap(h, args, who)) return rc;
+    if (mem == kHostMem) {
+        if (int rc = check_host_meas(a.H, a.ny, who)) return rc;
+        if (int rc = check_host_models(h, a.model, who)) return rc;
+        if (int rc = check_host_events(h, a.event, who)) return rc;
+    }
+    return run_call(h, mem, args, [&](double* const* d, bool) {
+        return qln::launch_tracking_kalman(h->p, d[kV], d[kK], d[kModel], d[kEvent], d[kH], a.ny, a.Vdiag, d[kCov0],
+                                           a.sigma0_batch, a.Wdiag, d[kLgain], d[kPest], d[kCov], d[kMarg], d[kEventVar],
+                                           h->stream);
+    });
 }
 
 int qln_tracking_kalman(qln_handle* h, const double* Zout, const double* K, const double* H, int32_t ny, const double* Vdiag,
                         const double* Sigma0, int32_t sigma0_batch, const double* Wdiag, double* Lgain, double* Pest,
                         double* Sigma, double* marg) {
-    return tracking_kalman(h, Zout, K, nullptr, false, nullptr, H, ny, Vdiag, Sigma0, sigma0_batch, Wdiag, Lgain, Pest, Sigma, marg,
-                           nullptr, "qln_tracking_kalman");
+    KalmanCall a{};
+    a.Zout = Zout; a.K = K; a.H = H; a.ny = ny; a.Vdiag = Vdiag; a.Sigma0 = Sigma0; a.sigma0_batch = sigma0_batch;
+    a.Wdiag = Wdiag; a.Lgain = Lgain; a.Pest = Pest; a.Sigma = Sigma; a.marg = marg;
+    return tracking_kalman(h, kDeviceMem, a, "qln_tracking_kalman");
 }
 int qln_tracking_kalman_host(qln_handle* h, const double* Zout, const double* K, const double* H, int32_t ny, const double* Vdiag,
                              const double* Sigma0, int32_t sigma0_batch, const double* Wdiag, double* Lgain, double* Pest,
                              double* Sigma, double* marg) {
-    return tracking_kalman_host(h, Zout, K, nullptr, false, nullptr, H, ny, Vdiag, Sigma0, sigma0_batch, Wdiag, Lgain, Pest, Sigma,
-                                marg, nullptr, "qln_tracking_kalman_host");
+    KalmanCall a{};
+    a.Zout = Zout; a.K = K; a.H = H; a.ny = ny; a.Vdiag = Vdiag; a.Sigma0 = Sigma0; a.sigma0_batch = sigma0_batch;
+    a.Wdiag = Wdiag; a.Lgain = Lgain; a.Pest = Pest; a.Sigma = Sigma; a.marg = marg;
+    return tracking_kalman(h, kHostMem, a, "qln_tracking_kalman_host");
 }
 int qln_tracking_kalman_guarded(qln_handle* h, const double* Zout, const double* K, const double* model, const double* event,
                                 const double* H, int32_t ny, const double* Vdiag, const double* Sigma0, int32_t sigma0_batch,
                                 const double* Wdiag, double* Lgain, double* Pest, double* Sigma, double* marg, double* event_var) {
-    return tracking_kalman(h, Zout, K, model, true, event, H, ny, Vdiag, Sigma0, sigma0_batch, Wdiag, Lgain, Pest, Sigma, marg,
-                           event_var, "qln_tracking_kalman_guarded");
+    KalmanCall a{};
+    a.Zout = Zout; a.K = K; a.model = model; a.guarded = true; a.event = event; a.H = H;
+    a.ny = ny; a.Vdiag = Vdiag; a.Sigma0 = Sigma0; a.sigma0_batch = sigma0_batch; a.Wdiag = Wdiag;
+    a.Lgain = Lgain; a.Pest = Pest; a.Sigma = Sigma; a.marg = marg; a.event_var = event_var;
+    return tracking_kalman(h, kDeviceMem, a, "qln_tracking_kalman_guarded");
 }
 int qln_tracking_kalman_guarded_host(qln_handle* h, const double* Zout, const double* K, const double* model, const double* event,
                                      const double* H, int32_t ny, const double* Vdiag, const double* Sigma0, int32_t sigma0_batch,
                                      const double* Wdiag, double* Lgain, double* Pest, double* Sigma, double* marg,
                                      double* event_var) {
-    return tracking_kalman_host(h, Zout, K, model, true, event, H, ny, Vdiag, Sigma0, sigma0_batch, Wdiag, Lgain, Pest, Sigma, marg,
-                                event_var, "qln_tracking_kalman_guarded_host");
+    KalmanCall a{};
+    a.Zout = Zout; a.K = K; a.model = model; a.guarded = true; a.event = event; a.H = H;
+    a.ny = ny; a.Vdiag = Vdiag; a.Sigma0 = Sigma0; a.sigma0_batch = sigma0_batch; a.Wdiag = Wdiag;
+    a.Lgain = Lgain; a.Pest = Pest; a.Sigma = Sigma; a.marg = marg; a.event_var = event_var;
+    return tracking_kalman(h, kHostMem, a, "qln_tracking_kalman_guarded_host");
 }
 
-// the estimate-feedback roll-out (k_tracking_rollout_estimated).  The checks that need no handle come first.
+// The estimate-feedback roll-out (k_tracking_rollout_estimated).  The checks that need no handle come first.
 // guarded: both the plant and the estimator land by their own guards, each with an event record (may be null)
 // limited: the loop within the force limits lim, with its saturation record sat (may be null)
-static int check_tracking_estimated_args(const qln_handle* h, const double* Zref, const double* K, const double* Lgain,
-                                         const double* H, int32_t ny, const double* vnoise, const double* wnoise,
-                                         const double* x0, const double* xhat0, const double* model, const double* Zout,
-                                         const double* Xhat, const double* innov, bool guarded, const double* event,
-                                         const double* event_hat, bool limited, const double* lim, const double* sat,
-                                         const char* who) {
+struct EstimatedCall {
+    const double *Zref, *K, *Lgain, *H;
+    int32_t ny;
+    const double *vnoise, *wnoise, *x0, *xhat0, *model, *lim;
+    double *Zout, *Xhat, *innov, *event, *event_hat, *sat;
+    bool guarded, limited;
+};
+
+static int check_tracking_estimated_args(const qln_handle* h, const EstimatedCall& a, const char* who) {
     const std::string w(who);
-    if (limited) {
-        if (int rc = check_force_limits(lim, who)) return rc;
-        if (!guarded && (event || event_hat))
+    if (a.limited) {
+        if (int rc = check_force_limits(a.lim, who)) return rc;
+        if (!a.guarded && (a.event || a.event_hat))
             return fail(QLN_ERR_INVALID_ARGUMENT, w + ": event or event_hat with guarded == 0 (the knot schedule has no record)");
     }
-    if (ny < 1 || ny > QLN_TRACK_NY_MAX)
+    if (a.ny < 1 || a.ny > QLN_TRACK_NY_MAX)
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
-    if (!Lgain || !H) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Lgain or H");
+    if (!a.Lgain || !a.H) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Lgain or H");
     if (int rc = check_handle(h)) return rc;
-    if (!Zref || !Zout) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref or Zout");
-    const qln_dims& D = h->dims;
-    const int64_t nx = (int64_t)D.B * QLN_NX, ne = (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
-    return check_no_overlap({{Zout, D.z_total}, {Xhat, (int64_t)D.B * D.N * QLN_NX}, {innov, tracking_meas_total(D, ny)},
-                             {event, ne}, {event_hat, ne}, {sat, tracking_sat_total(D)}},
-                            {{Zref, D.z_total}, {K, tracking_k_total(D)}, {Lgain, tracking_gain_total(D, ny)},
-                             {H, (int64_t)ny * QLN_NX}, {vnoise, tracking_meas_total(D, ny)},
-                             {wnoise, (int64_t)D.B * (D.N - 1) * QLN_NX}, {x0, nx}, {xhat0, nx},
-                             {model, (int64_t)D.B * QLN_MODEL_NP}}, w);
-}
-
-static int tracking_rollout_estimated(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
-                                      int32_t ny, const double* vnoise, const double* wnoise, const double* x0,
-                                      const double* xhat0, const double* model, double* Zout, double* Xhat, double* innov,
-                                      bool guarded, double* event, double* event_hat, bool limited, const double* lim,
-                                      double* sat, const char* who) {
-    if (int rc = check_tracking_estimated_args(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, guarded,
-                                               event, event_hat, limited, lim, sat, who))
-        return rc;
-    if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout_estimated(h->p, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov,
-                                                   guarded, event, event_hat, limited ? lim : nullptr, sat, h->stream));
+    if (!a.Zref || !a.Zout) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref or Zout");
     return QLN_OK;
 }
 
-static int tracking_rollout_estimated_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
-                                           const double* H, int32_t ny, const double* vnoise, const double* wnoise,
-                                           const double* x0, const double* xhat0, const double* model, double* Zout, double* Xhat,
-                                           double* innov, bool guarded, double* event, double* event_hat, bool limited,
-                                           const double* lim, double* sat, const char* who) {
-    if (int rc = check_tracking_estimated_args(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, guarded,
-                                               event, event_hat, limited, lim, sat, who))
-        return rc;
-    for (int i = 0; i < ny * QLN_NX; ++i)
-        if (!std::isfinite(H[i]))
-            return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": H is not finite (entry " + std::to_string(i) + ")");
-    if (int rc = check_host_models(h, model, who)) return rc;
-    if (int rc = bind_device(h)) return rc;
-    HostArg hm = copy_in(kH, H), lg = copy_in(kLgain, Lgain), vn = copy_in(kVnoise, vnoise), in = copy_out(kInnov, innov);
-    hm.n = (int64_t)ny * QLN_NX;  // the rows, gains, samples and innovations of the call's ny, of the roles' eight
-    lg.n = tracking_gain_total(h->dims, ny);
-    vn.n = in.n = tracking_meas_total(h->dims, ny);
-    return host_call(h,
-                     {copy_in(kZ, Zref), copy_inout(kZio, Zout), copy_in(kK, K), lg, hm, vn, copy_in(kWnoise, wnoise),
-                      copy_in(kX0, x0), copy_in(kXhat0, xhat0), copy_in(kModel, model), copy_out(kXhat, Xhat), in,
-                      copy_out(kEvent, event), copy_out(kEventHat, event_hat), copy_out(kSat, sat)},
-                     [&](double* const* d, bool) {
-                         return qln::launch_tracking_rollout_estimated(h->p, d[kZ], d[kK], d[kLgain], d[kH], ny, d[kVnoise],
-                                                                       d[kWnoise], d[kX0], d[kXhat0], d[kModel], d[kZio], d[kXhat],
-                                                                       d[kInnov], guarded, d[kEvent], d[kEventHat],
-                                                                       limited ? lim : nullptr, d[kSat], h->stream);
-                     });
+static int tracking_rollout_estimated(qln_handle* h, MemForm mem, const EstimatedCall& a, const char* who) {
+    if (int rc = check_tracking_estimated_args(h, a, who)) return rc;
+    // the rows, gains, samples and innovations of the call's ny, of the roles' eight
+    const int64_t ng = tracking_gain_total(h->dims, a.ny), nm = tracking_meas_total(h->dims, a.ny);
+    const HostArgs args = {copy_in(kZ, a.Zref), copy_inout(kZio, a.Zout), copy_in(kK, a.K), copy_in(kLgain, a.Lgain).sized(ng),
+                           copy_in(kH, a.H).sized((int64_t)a.ny * QLN_NX), copy_in(kVnoise, a.vnoise).sized(nm),
+                           copy_in(kWnoise, a.wnoise), copy_in(kX0, a.x0), copy_in(kXhat0, a.xhat0), copy_in(kModel, a.model),
+                           copy_out(kXhat, a.Xhat), copy_out(kInnov, a.innov).sized(nm), copy_out(kEvent, a.event),
+                           copy_out(kEventHat, a.event_hat), copy_out(kSat, a.sat)};
+    if (int rc = check_no_overlap(h, args, who)) return rc;
+    if (mem == kHostMem) {
+        if (int rc = check_host_meas(a.H, a.ny, who)) return rc;
+        if (int rc = check_host_models(h, a.model, who)) return rc;
+    }
+    return run_call(h, mem, args, [&](double* const* d, bool) {
+        return qln::launch_tracking_rollout_estimated(h->p, d[kZ], d[kK], d[kLgain], d[kH], a.ny, d[kVnoise], d[kWnoise], d[kX0],
+                                                      d[kXhat0], d[kModel], d[kZio], d[kXhat], d[kInnov], a.guarded, d[kEvent],
+                                                      d[kEventHat], a.limited ? a.lim : nullptr, d[kSat], h->stream);
+    });
 }
 
 int qln_tracking_rollout_estimated(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
                                    int32_t ny, const double* vnoise, const double* wnoise, const double* x0, const double* xhat0,
                                    const double* model, double* Zout, double* Xhat, double* innov) {
-    return tracking_rollout_estimated(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, false, nullptr,
-                                      nullptr, false, nullptr, nullptr, "qln_tracking_rollout_estimated");
+    EstimatedCall a{};
+    a.Zref = Zref; a.K = K; a.Lgain = Lgain; a.H = H; a.ny = ny; a.vnoise = vnoise; a.wnoise = wnoise;
+    a.x0 = x0; a.xhat0 = xhat0; a.model = model; a.Zout = Zout; a.Xhat = Xhat; a.innov = innov;
+    return tracking_rollout_estimated(h, kDeviceMem, a, "qln_tracking_rollout_estimated");
 }
 int qln_tracking_rollout_estimated_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
                                         int32_t ny, const double* vnoise, const double* wnoise, const double* x0,
                                         const double* xhat0, const double* model, double* Zout, double* Xhat, double* innov) {
-    return tracking_rollout_estimated_host(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, false,
-                                           nullptr, nullptr, false, nullptr, nullptr, "qln_tracking_rollout_estimated_host");
+    EstimatedCall a{};
+    a.Zref = Zref; a.K = K; a.Lgain = Lgain; a.H = H; a.ny = ny; a.vnoise = vnoise; a.wnoise = wnoise;
+    a.x0 = x0; a.xhat0 = xhat0; a.model = model; a.Zout = Zout; a.Xhat = Xhat; a.innov = innov;
+    return tracking_rollout_estimated(h, kHostMem, a, "qln_tracking_rollout_estimated_host");
 }
 int qln_tracking_rollout_estimated_guarded(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
                                            int32_t ny, const double* vnoise, const double* wnoise, const double* x0,
                                            const double* xhat0, const double* model, double* Zout, double* Xhat, double* innov,
                                            double* event, double* event_hat) {
-    return tracking_rollout_estimated(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, true, event,
-                                      event_hat, false, nullptr, nullptr, "qln_tracking_rollout_estimated_guarded");
+    EstimatedCall a{};
+    a.Zref = Zref; a.K = K; a.Lgain = Lgain; a.H = H; a.ny = ny; a.vnoise = vnoise;
+    a.wnoise = wnoise; a.x0 = x0; a.xhat0 = xhat0; a.model = model; a.Zout = Zout;
+    a.Xhat = Xhat; a.innov = innov; a.guarded = true; a.event = event; a.event_hat = event_hat;
+    return tracking_rollout_estimated(h, kDeviceMem, a, "qln_tracking_rollout_estimated_guarded");
 }
 int qln_tracking_rollout_estimated_guarded_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                                 const double* H, int32_t ny, const double* vnoise, const double* wnoise,
                                                 const double* x0, const double* xhat0, const double* model, double* Zout,
                                                 double* Xhat, double* innov, double* event, double* event_hat) {
-    return tracking_rollout_estimated_host(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, true, event,
-                                           event_hat, false, nullptr, nullptr, "qln_tracking_rollout_estimated_guarded_host");
+    EstimatedCall a{};
+    a.Zref = Zref; a.K = K; a.Lgain = Lgain; a.H = H; a.ny = ny; a.vnoise = vnoise;
+    a.wnoise = wnoise; a.x0 = x0; a.xhat0 = xhat0; a.model = model; a.Zout = Zout;
+    a.Xhat = Xhat; a.innov = innov; a.guarded = true; a.event = event; a.event_hat = event_hat;
+    return tracking_rollout_estimated(h, kHostMem, a, "qln_tracking_rollout_estimated_guarded_host");
 }
 // the loop within contact-aware force limits: the knot-scheduled or the guarded one, with its saturation record
 int qln_tracking_rollout_estimated_limited(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
@@ -1870,33 +1877,38 @@ int qln_tracking_rollout_estimated_limited(qln_handle* h, const double* Zref, co
                                            const double* xhat0, const double* model, const double* lim, int32_t guarded,
                                            double* Zout, double* Xhat, double* innov, double* event, double* event_hat,
                                            double* sat) {
-    return tracking_rollout_estimated(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov, guarded != 0,
-                                      event, event_hat, true, lim, sat, "qln_tracking_rollout_estimated_limited");
+    EstimatedCall a{};
+    a.Zref = Zref; a.K = K; a.Lgain = Lgain; a.H = H; a.ny = ny; a.vnoise = vnoise; a.wnoise = wnoise;
+    a.x0 = x0; a.xhat0 = xhat0; a.model = model; a.Zout = Zout; a.Xhat = Xhat; a.innov = innov;
+    a.guarded = guarded != 0; a.event = event; a.event_hat = event_hat; a.limited = true; a.lim = lim; a.sat = sat;
+    return tracking_rollout_estimated(h, kDeviceMem, a, "qln_tracking_rollout_estimated_limited");
 }
 int qln_tracking_rollout_estimated_limited_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                                 const double* H, int32_t ny, const double* vnoise, const double* wnoise,
                                                 const double* x0, const double* xhat0, const double* model, const double* lim,
                                                 int32_t guarded, double* Zout, double* Xhat, double* innov, double* event,
                                                 double* event_hat, double* sat) {
-    return tracking_rollout_estimated_host(h, Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov,
-                                           guarded != 0, event, event_hat, true, lim, sat,
-                                           "qln_tracking_rollout_estimated_limited_host");
+    EstimatedCall a{};
+    a.Zref = Zref; a.K = K; a.Lgain = Lgain; a.H = H; a.ny = ny; a.vnoise = vnoise; a.wnoise = wnoise;
+    a.x0 = x0; a.xhat0 = xhat0; a.model = model; a.Zout = Zout; a.Xhat = Xhat; a.innov = innov;
+    a.guarded = guarded != 0; a.event = event; a.event_hat = event_hat; a.limited = true; a.lim = lim; a.sat = sat;
+    return tracking_rollout_estimated(h, kHostMem, a, "qln_tracking_rollout_estimated_limited_host");
 }
 
 // The sweeps through the estimate-feedback roll-out (k_tracking_rollout_estimated_jvp / _vjp).  What both sweeps share: the
 // roll-out's inputs and the trajectory it produced.  The checks that need no handle come first.
 // guarded: the sweeps through the two guard-triggered touchdowns, which need both of the roll-out's event records
-// want_gain: a tangent or cotangent of Lgain is asked for, which needs innov
 // sat: the limited roll-out's saturation record, required by the sweeps at its active set (limited), whose event and event_hat
 // -- both or neither -- select the guarded or the knot-scheduled blocks
 struct EstimatedTraj {
     const double *Zref, *K, *Lgain, *H;
     int32_t ny;
-    const double *model, *Zout, *Xhat, *innov, *event, *event_hat, *sat = nullptr;
-    bool limited = false;
+    const double *model, *Zout, *Xhat, *innov, *event, *event_hat, *sat;
+    bool guarded, limited;
 };
 
-static int check_tracking_estimated_sweep_args(const qln_handle* h, const EstimatedTraj& t, bool guarded, bool want_gain,
+// want_gain: a tangent or cotangent of Lgain is asked for, which needs innov
+static int check_tracking_estimated_sweep_args(const qln_handle* h, const EstimatedTraj& t, bool want_gain,
                                                const std::string& w) {
     if (t.ny < 1 || t.ny > QLN_TRACK_NY_MAX)
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
@@ -1905,7 +1917,7 @@ static int check_tracking_estimated_sweep_args(const qln_handle* h, const Estima
     if (t.limited && (t.event != nullptr) != (t.event_hat != nullptr))
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": exactly one of event and event_hat (both: the guarded blocks, neither: the "
                                                   "knot-scheduled ones)");
-    if (guarded && (!t.event || !t.event_hat))
+    if (t.guarded && (!t.event || !t.event_hat))
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event or event_hat (the guarded roll-out's two records)");
     if (want_gain && !t.innov)
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null innov (the tangent or cotangent of Lgain needs the innovations)");
@@ -1913,16 +1925,8 @@ static int check_tracking_estimated_sweep_args(const qln_handle* h, const Estima
     return check_handle(h);
 }
 
-// the spans of the trajectory's arguments, for the overlap rule (innov only where it is read)
-#define QLN_ESTIMATED_TRAJ_SPANS(D, t, want_gain)                                                                             \
-    {t.Zref, D.z_total}, {t.K, tracking_k_total(D)}, {t.Lgain, tracking_gain_total(D, t.ny)}, {t.H, (int64_t)t.ny * QLN_NX}, \
-        {t.model, (int64_t)D.B * QLN_MODEL_NP}, {t.Zout, D.z_total}, {t.Xhat, (int64_t)D.B * D.N * QLN_NX},                   \
-        {want_gain ? t.innov : nullptr, tracking_meas_total(D, t.ny)},                                                        \
-        {t.event, (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE}, {t.event_hat, (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE},        \
-        {t.sat, tracking_sat_total(D)}
-
-static int check_tracking_estimated_jvp_args(const qln_handle* h, const EstimatedTraj& t, bool guarded,
-                                             const qln::EstimatedJvpArgs& a, const char* who) {
+static int check_tracking_estimated_jvp_args(const qln_handle* h, const EstimatedTraj& t, const qln::EstimatedJvpArgs& a,
+                                             const char* who) {
     const std::string w(who);
     if (!a.Zref_dot && !a.K_dot && !a.Lgain_dot && !a.x0_dot && !a.xhat0_dot && !a.model_dot)
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every tangent is NULL (no direction)");
@@ -1931,123 +1935,79 @@ static int check_tracking_estimated_jvp_args(const qln_handle* h, const Estimate
     if (t.limited && !t.event && !t.event_hat && (a.event_dot || a.event_hat_dot))
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": event_dot or event_hat_dot without event and event_hat (the knot-scheduled "
                                                   "sweep has no record)");
-    if (int rc = check_tracking_estimated_sweep_args(h, t, guarded, a.Lgain_dot != nullptr, w)) return rc;
-    const qln_dims& D = h->dims;
-    const int64_t nx = (int64_t)D.B * QLN_NX, nm = (int64_t)D.B * QLN_MODEL_NP, ne = (int64_t)D.B * QLN_TOUCHDOWN_INFO_STRIDE;
-    const bool wg = a.Lgain_dot != nullptr;
-    return check_no_overlap({{a.Zout_dot, D.z_total}, {a.Xhat_dot, (int64_t)D.B * D.N * QLN_NX},
-                             {a.innov_dot, tracking_meas_total(D, t.ny)}, {a.event_dot, ne}, {a.event_hat_dot, ne}},
-                            {QLN_ESTIMATED_TRAJ_SPANS(D, t, wg), {a.Zref_dot, D.z_total}, {a.K_dot, tracking_k_total(D)},
-                             {a.Lgain_dot, tracking_gain_total(D, t.ny)}, {a.x0_dot, nx}, {a.xhat0_dot, nx}, {a.model_dot, nm}}, w);
+    return check_tracking_estimated_sweep_args(h, t, a.Lgain_dot != nullptr, w);
 }
 
-static int check_tracking_estimated_vjp_args(const qln_handle* h, const EstimatedTraj& t, bool guarded,
-                                             const qln::EstimatedVjpArgs& a, const char* who) {
+static int check_tracking_estimated_vjp_args(const qln_handle* h, const EstimatedTraj& t, const qln::EstimatedVjpArgs& a,
+                                             const char* who) {
     const std::string w(who);
     if (a.K_bar && !t.K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_bar needs K (K == NULL has no gains to differentiate)");
     if (!a.Zbar) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zbar");
-    if (int rc = check_tracking_estimated_sweep_args(h, t, guarded, a.Lgain_bar != nullptr, w)) return rc;
-    const qln_dims& D = h->dims;
-    const int64_t nx = (int64_t)D.B * QLN_NX, nm = (int64_t)D.B * QLN_MODEL_NP;
-    const bool wg = a.Lgain_bar != nullptr;
-    return check_no_overlap({{a.Zref_bar, D.z_total}, {a.K_bar, tracking_k_total(D)}, {a.Lgain_bar, tracking_gain_total(D, t.ny)},
-                             {a.x0_bar, nx}, {a.xhat0_bar, nx}, {a.model_bar, nm}},
-                            {QLN_ESTIMATED_TRAJ_SPANS(D, t, wg), {a.Zbar, D.z_total}, {a.Xhat_bar, (int64_t)D.B * D.N * QLN_NX},
-                             {a.innov_bar, tracking_meas_total(D, t.ny)}}, w);
-}
-#undef QLN_ESTIMATED_TRAJ_SPANS
-
-static qln::EstimatedSweepIn estimated_sweep_in(const EstimatedTraj& t, bool guarded) {
-    return {t.Zref, t.K, t.Lgain, t.H, t.ny, t.model, t.Zout, t.Xhat, t.innov, guarded ? t.event : nullptr,
-            guarded ? t.event_hat : nullptr};
+    return check_tracking_estimated_sweep_args(h, t, a.Lgain_bar != nullptr, w);
 }
 
-static int tracking_estimated_jvp(qln_handle* h, const EstimatedTraj& t, bool guarded, const qln::EstimatedJvpArgs& a,
-                                  const char* who) {
-    if (int rc = check_tracking_estimated_jvp_args(h, t, guarded, a, who)) return rc;
-    if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout_estimated_jvp(h->p, estimated_sweep_in(t, guarded), a, t.sat, h->stream));
-    return QLN_OK;
-}
-
-static int tracking_estimated_vjp(qln_handle* h, const EstimatedTraj& t, bool guarded, const qln::EstimatedVjpArgs& a,
-                                  const char* who) {
-    if (int rc = check_tracking_estimated_vjp_args(h, t, guarded, a, who)) return rc;
-    if (int rc = bind_device(h)) return rc;
-    QLN_HIP(qln::launch_tracking_rollout_estimated_vjp(h->p, estimated_sweep_in(t, guarded), a, t.sat, h->stream));
-    return QLN_OK;
-}
-
-// host forms: what the device forms check, then the values of H, the models and the two records
-static int check_host_estimated_traj(const qln_handle* h, const EstimatedTraj& t, bool guarded, const char* who) {
-    for (int i = 0; i < t.ny * QLN_NX; ++i)
-        if (!std::isfinite(t.H[i]))
-            return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": H is not finite (entry " + std::to_string(i) + ")");
+// host forms: the values of H, the models, the saturation record and the two event records
+static int check_host_estimated_traj(const qln_handle* h, const EstimatedTraj& t, const char* who) {
+    if (int rc = check_host_meas(t.H, t.ny, who)) return rc;
     if (int rc = check_host_models(h, t.model, who)) return rc;
     if (int rc = check_host_sat(h, t.sat, who)) return rc;
-    if (!guarded) return QLN_OK;
     if (int rc = check_host_events(h, t.event, who)) return rc;
     return check_host_events(h, t.event_hat, who);
 }
 
-// the arguments sized by the call's ny, of the roles' eight rows
-static HostArg sized(HostArg a, int64_t n) {
-    a.n = n;
-    return a;
+// the trajectory as the launch reads it: Zout's buffer stands in for a Zref the host form did not stage
+static qln::EstimatedSweepIn estimated_sweep_in(double* const* d, int32_t ny) {
+    return {d[kZ] ? d[kZ] : d[kV], d[kK], d[kLgain], d[kH], ny, d[kModel], d[kV], d[kXhat], d[kInnov], d[kEvent], d[kEventHat]};
 }
 
-// Zref is staged only when K_dot is given (the kernel reads it for nothing else); otherwise Zout's buffer stands in.  innov only
-// with Lgain_dot.
-static int tracking_estimated_jvp_host(qln_handle* h, const EstimatedTraj& t, bool guarded, const qln::EstimatedJvpArgs& a,
-                                       const char* who) {
-    if (int rc = check_tracking_estimated_jvp_args(h, t, guarded, a, who)) return rc;
-    if (int rc = check_host_estimated_traj(h, t, guarded, who)) return rc;
-    if (int rc = bind_device(h)) return rc;
+// The host form stages Zref only when K_dot is given (the kernel reads it for nothing else), and innov only with Lgain_dot,
+// which is also when the overlap rule looks at innov.  Lgain, H, innov and their tangents have the extent of the call's ny.
+static int tracking_estimated_jvp(qln_handle* h, MemForm mem, const EstimatedTraj& t, const qln::EstimatedJvpArgs& a,
+                                  const char* who) {
+    if (int rc = check_tracking_estimated_jvp_args(h, t, a, who)) return rc;
     const int64_t ng = tracking_gain_total(h->dims, t.ny), nm = tracking_meas_total(h->dims, t.ny);
-    return host_call(
-        h,
-        {copy_in(kV, t.Zout), copy_in(kZ, a.K_dot ? t.Zref : nullptr), copy_in(kK, t.K), sized(copy_in(kLgain, t.Lgain), ng),
-         sized(copy_in(kH, t.H), (int64_t)t.ny * QLN_NX), copy_in(kModel, t.model), copy_in(kXhat, t.Xhat),
-         sized(copy_in(kInnov, a.Lgain_dot ? t.innov : nullptr), nm), copy_in(kEvent, guarded ? t.event : nullptr),
-         copy_in(kEventHat, guarded ? t.event_hat : nullptr), copy_in(kSat, t.sat), copy_in(kZdot, a.Zref_dot),
-         copy_in(kKdot, a.K_dot),
-         sized(copy_in(kLgainD, a.Lgain_dot), ng), copy_in(kX0, a.x0_dot), copy_in(kXhat0, a.xhat0_dot),
-         copy_in(kModelD, a.model_dot), copy_inout(kZio, a.Zout_dot), copy_out(kXhatD, a.Xhat_dot),
-         sized(copy_out(kInnovD, a.innov_dot), nm), copy_out(kEventD, guarded ? a.event_dot : nullptr),
-         copy_out(kEventHatD, guarded ? a.event_hat_dot : nullptr)},
-        [&](double* const* d, bool) {
-            const qln::EstimatedSweepIn in = {d[kZ] ? d[kZ] : d[kV], d[kK], d[kLgain], d[kH], t.ny, d[kModel], d[kV], d[kXhat],
-                                              d[kInnov], d[kEvent], d[kEventHat]};
-            const qln::EstimatedJvpArgs da = {d[kZdot], d[kKdot], d[kLgainD], d[kX0], d[kXhat0], d[kModelD], d[kZio], d[kXhatD],
-                                              d[kInnovD], d[kEventD], d[kEventHatD]};
-            return qln::launch_tracking_rollout_estimated_jvp(h->p, in, da, d[kSat], h->stream);
-        });
+    const bool want_gain = a.Lgain_dot != nullptr;
+    const HostArgs args = {copy_in(kV, t.Zout), copy_in(kZ, t.Zref).staged_if(a.K_dot != nullptr), copy_in(kK, t.K),
+                           copy_in(kLgain, t.Lgain).sized(ng), copy_in(kH, t.H).sized((int64_t)t.ny * QLN_NX),
+                           copy_in(kModel, t.model), copy_in(kXhat, t.Xhat),
+                           copy_in(kInnov, t.innov).sized(nm).ruled_if(want_gain).staged_if(want_gain),
+                           copy_in(kEvent, t.event), copy_in(kEventHat, t.event_hat), copy_in(kSat, t.sat),
+                           copy_in(kZdot, a.Zref_dot), copy_in(kKdot, a.K_dot), copy_in(kLgainD, a.Lgain_dot).sized(ng),
+                           copy_in(kX0, a.x0_dot), copy_in(kXhat0, a.xhat0_dot), copy_in(kModelD, a.model_dot),
+                           copy_inout(kZio, a.Zout_dot), copy_out(kXhatD, a.Xhat_dot), copy_out(kInnovD, a.innov_dot).sized(nm),
+                           copy_out(kEventD, a.event_dot), copy_out(kEventHatD, a.event_hat_dot)};
+    if (int rc = check_no_overlap(h, args, who)) return rc;
+    if (mem == kHostMem)
+        if (int rc = check_host_estimated_traj(h, t, who)) return rc;
+    return run_call(h, mem, args, [&](double* const* d, bool) {
+        const qln::EstimatedJvpArgs da = {d[kZdot], d[kKdot], d[kLgainD], d[kX0], d[kXhat0], d[kModelD], d[kZio], d[kXhatD],
+                                          d[kInnovD], d[kEventD], d[kEventHatD]};
+        return qln::launch_tracking_rollout_estimated_jvp(h->p, estimated_sweep_in(d, t.ny), da, d[kSat], h->stream);
+    });
 }
 
-// Zref is staged only when K_bar asks for it; otherwise Zout's buffer stands in.  innov only with Lgain_bar.
-static int tracking_estimated_vjp_host(qln_handle* h, const EstimatedTraj& t, bool guarded, const qln::EstimatedVjpArgs& a,
-                                       const char* who) {
-    if (int rc = check_tracking_estimated_vjp_args(h, t, guarded, a, who)) return rc;
-    if (int rc = check_host_estimated_traj(h, t, guarded, who)) return rc;
-    if (int rc = bind_device(h)) return rc;
+// Zref with K_bar and innov with Lgain_bar, as in the forward sweep.
+static int tracking_estimated_vjp(qln_handle* h, MemForm mem, const EstimatedTraj& t, const qln::EstimatedVjpArgs& a,
+                                  const char* who) {
+    if (int rc = check_tracking_estimated_vjp_args(h, t, a, who)) return rc;
     const int64_t ng = tracking_gain_total(h->dims, t.ny), nm = tracking_meas_total(h->dims, t.ny);
-    return host_call(
-        h,
-        {copy_in(kV, t.Zout), copy_in(kZ, a.K_bar ? t.Zref : nullptr), copy_in(kK, t.K), sized(copy_in(kLgain, t.Lgain), ng),
-         sized(copy_in(kH, t.H), (int64_t)t.ny * QLN_NX), copy_in(kModel, t.model), copy_in(kXhat, t.Xhat),
-         sized(copy_in(kInnov, a.Lgain_bar ? t.innov : nullptr), nm), copy_in(kEvent, guarded ? t.event : nullptr),
-         copy_in(kEventHat, guarded ? t.event_hat : nullptr), copy_in(kSat, t.sat), copy_in(kZbar, a.Zbar),
-         copy_in(kXhatD, a.Xhat_bar),
-         sized(copy_in(kInnovD, a.innov_bar), nm), copy_inout(kZio, a.Zref_bar), copy_out(kKbar, a.K_bar),
-         sized(copy_out(kLgainD, a.Lgain_bar), ng), copy_out(kX0, a.x0_bar), copy_out(kXhat0, a.xhat0_bar),
-         copy_out(kModelD, a.model_bar)},
-        [&](double* const* d, bool) {
-            const qln::EstimatedSweepIn in = {d[kZ] ? d[kZ] : d[kV], d[kK], d[kLgain], d[kH], t.ny, d[kModel], d[kV], d[kXhat],
-                                              d[kInnov], d[kEvent], d[kEventHat]};
-            const qln::EstimatedVjpArgs da = {d[kZbar], d[kXhatD], d[kInnovD], d[kZio], d[kKbar], d[kLgainD], d[kX0], d[kXhat0],
-                                              d[kModelD]};
-            return qln::launch_tracking_rollout_estimated_vjp(h->p, in, da, d[kSat], h->stream);
-        });
+    const bool want_gain = a.Lgain_bar != nullptr;
+    const HostArgs args = {copy_in(kV, t.Zout), copy_in(kZ, t.Zref).staged_if(a.K_bar != nullptr), copy_in(kK, t.K),
+                           copy_in(kLgain, t.Lgain).sized(ng), copy_in(kH, t.H).sized((int64_t)t.ny * QLN_NX),
+                           copy_in(kModel, t.model), copy_in(kXhat, t.Xhat),
+                           copy_in(kInnov, t.innov).sized(nm).ruled_if(want_gain).staged_if(want_gain),
+                           copy_in(kEvent, t.event), copy_in(kEventHat, t.event_hat), copy_in(kSat, t.sat),
+                           copy_in(kZbar, a.Zbar), copy_in(kXhatD, a.Xhat_bar), copy_in(kInnovD, a.innov_bar).sized(nm),
+                           copy_inout(kZio, a.Zref_bar), copy_out(kKbar, a.K_bar), copy_out(kLgainD, a.Lgain_bar).sized(ng),
+                           copy_out(kX0, a.x0_bar), copy_out(kXhat0, a.xhat0_bar), copy_out(kModelD, a.model_bar)};
+    if (int rc = check_no_overlap(h, args, who)) return rc;
+    if (mem == kHostMem)
+        if (int rc = check_host_estimated_traj(h, t, who)) return rc;
+    return run_call(h, mem, args, [&](double* const* d, bool) {
+        const qln::EstimatedVjpArgs da = {d[kZbar], d[kXhatD], d[kInnovD], d[kZio], d[kKbar], d[kLgainD], d[kX0], d[kXhat0],
+                                          d[kModelD]};
+        return qln::launch_tracking_rollout_estimated_vjp(h->p, estimated_sweep_in(d, t.ny), da, d[kSat], h->stream);
+    });
 }
 
 int qln_tracking_rollout_estimated_jvp(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
@@ -2055,20 +2015,24 @@ int qln_tracking_rollout_estimated_jvp(qln_handle* h, const double* Zref, const 
                                        const double* innov, const double* Zref_dot, const double* K_dot, const double* Lgain_dot,
                                        const double* x0_dot, const double* xhat0_dot, const double* model_dot, double* Zout_dot,
                                        double* Xhat_dot, double* innov_dot) {
-    return tracking_estimated_jvp(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, nullptr, nullptr}, false,
-                                  {Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, Zout_dot, Xhat_dot, innov_dot, nullptr,
-                                   nullptr},
-                                  "qln_tracking_rollout_estimated_jvp");
+    EstimatedTraj t{};
+    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout; t.Xhat = Xhat; t.innov = innov;
+    qln::EstimatedJvpArgs a{};
+    a.Zref_dot = Zref_dot; a.K_dot = K_dot; a.Lgain_dot = Lgain_dot; a.x0_dot = x0_dot; a.xhat0_dot = xhat0_dot;
+    a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.Xhat_dot = Xhat_dot; a.innov_dot = innov_dot;
+    return tracking_estimated_jvp(h, kDeviceMem, t, a, "qln_tracking_rollout_estimated_jvp");
 }
 int qln_tracking_rollout_estimated_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                             const double* H, int32_t ny, const double* model, const double* Zout,
                                             const double* Xhat, const double* innov, const double* Zref_dot, const double* K_dot,
                                             const double* Lgain_dot, const double* x0_dot, const double* xhat0_dot,
                                             const double* model_dot, double* Zout_dot, double* Xhat_dot, double* innov_dot) {
-    return tracking_estimated_jvp_host(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, nullptr, nullptr}, false,
-                                       {Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, Zout_dot, Xhat_dot, innov_dot,
-                                        nullptr, nullptr},
-                                       "qln_tracking_rollout_estimated_jvp_host");
+    EstimatedTraj t{};
+    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout; t.Xhat = Xhat; t.innov = innov;
+    qln::EstimatedJvpArgs a{};
+    a.Zref_dot = Zref_dot; a.K_dot = K_dot; a.Lgain_dot = Lgain_dot; a.x0_dot = x0_dot; a.xhat0_dot = xhat0_dot;
+    a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.Xhat_dot = Xhat_dot; a.innov_dot = innov_dot;
+    return tracking_estimated_jvp(h, kHostMem, t, a, "qln_tracking_rollout_estimated_jvp_host");
 }
 int qln_tracking_rollout_estimated_guarded_jvp(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                                const double* H, int32_t ny, const double* model, const double* Zout,
@@ -2077,10 +2041,14 @@ int qln_tracking_rollout_estimated_guarded_jvp(qln_handle* h, const double* Zref
                                                const double* Lgain_dot, const double* x0_dot, const double* xhat0_dot,
                                                const double* model_dot, double* Zout_dot, double* Xhat_dot, double* innov_dot,
                                                double* event_dot, double* event_hat_dot) {
-    return tracking_estimated_jvp(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, event, event_hat}, true,
-                                  {Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, Zout_dot, Xhat_dot, innov_dot,
-                                   event_dot, event_hat_dot},
-                                  "qln_tracking_rollout_estimated_guarded_jvp");
+    EstimatedTraj t{};
+    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout;
+    t.Xhat = Xhat; t.innov = innov; t.guarded = true; t.event = event; t.event_hat = event_hat;
+    qln::EstimatedJvpArgs a{};
+    a.Zref_dot = Zref_dot; a.K_dot = K_dot; a.Lgain_dot = Lgain_dot; a.x0_dot = x0_dot;
+    a.xhat0_dot = xhat0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.Xhat_dot = Xhat_dot;
+    a.innov_dot = innov_dot; a.event_dot = event_dot; a.event_hat_dot = event_hat_dot;
+    return tracking_estimated_jvp(h, kDeviceMem, t, a, "qln_tracking_rollout_estimated_guarded_jvp");
 }
 int qln_tracking_rollout_estimated_guarded_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                                     const double* H, int32_t ny, const double* model, const double* Zout,
@@ -2089,28 +2057,38 @@ int qln_tracking_rollout_estimated_guarded_jvp_host(qln_handle* h, const double*
                                                     const double* Lgain_dot, const double* x0_dot, const double* xhat0_dot,
                                                     const double* model_dot, double* Zout_dot, double* Xhat_dot,
                                                     double* innov_dot, double* event_dot, double* event_hat_dot) {
-    return tracking_estimated_jvp_host(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, event, event_hat}, true,
-                                       {Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, Zout_dot, Xhat_dot, innov_dot,
-                                        event_dot, event_hat_dot},
-                                       "qln_tracking_rollout_estimated_guarded_jvp_host");
+    EstimatedTraj t{};
+    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout;
+    t.Xhat = Xhat; t.innov = innov; t.guarded = true; t.event = event; t.event_hat = event_hat;
+    qln::EstimatedJvpArgs a{};
+    a.Zref_dot = Zref_dot; a.K_dot = K_dot; a.Lgain_dot = Lgain_dot; a.x0_dot = x0_dot;
+    a.xhat0_dot = xhat0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.Xhat_dot = Xhat_dot;
+    a.innov_dot = innov_dot; a.event_dot = event_dot; a.event_hat_dot = event_hat_dot;
+    return tracking_estimated_jvp(h, kHostMem, t, a, "qln_tracking_rollout_estimated_guarded_jvp_host");
 }
 int qln_tracking_rollout_estimated_vjp(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
                                        int32_t ny, const double* model, const double* Zout, const double* Xhat,
                                        const double* innov, const double* Zbar, const double* Xhat_bar, const double* innov_bar,
                                        double* Zref_bar, double* K_bar, double* Lgain_bar, double* x0_bar, double* xhat0_bar,
                                        double* model_bar) {
-    return tracking_estimated_vjp(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, nullptr, nullptr}, false,
-                                  {Zbar, Xhat_bar, innov_bar, Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar, model_bar},
-                                  "qln_tracking_rollout_estimated_vjp");
+    EstimatedTraj t{};
+    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout; t.Xhat = Xhat; t.innov = innov;
+    qln::EstimatedVjpArgs a{};
+    a.Zbar = Zbar; a.Xhat_bar = Xhat_bar; a.innov_bar = innov_bar; a.Zref_bar = Zref_bar; a.K_bar = K_bar;
+    a.Lgain_bar = Lgain_bar; a.x0_bar = x0_bar; a.xhat0_bar = xhat0_bar; a.model_bar = model_bar;
+    return tracking_estimated_vjp(h, kDeviceMem, t, a, "qln_tracking_rollout_estimated_vjp");
 }
 int qln_tracking_rollout_estimated_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                             const double* H, int32_t ny, const double* model, const double* Zout,
                                             const double* Xhat, const double* innov, const double* Zbar, const double* Xhat_bar,
                                             const double* innov_bar, double* Zref_bar, double* K_bar, double* Lgain_bar,
                                             double* x0_bar, double* xhat0_bar, double* model_bar) {
-    return tracking_estimated_vjp_host(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, nullptr, nullptr}, false,
-                                       {Zbar, Xhat_bar, innov_bar, Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar, model_bar},
-                                       "qln_tracking_rollout_estimated_vjp_host");
+    EstimatedTraj t{};
+    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout; t.Xhat = Xhat; t.innov = innov;
+    qln::EstimatedVjpArgs a{};
+    a.Zbar = Zbar; a.Xhat_bar = Xhat_bar; a.innov_bar = innov_bar; a.Zref_bar = Zref_bar; a.K_bar = K_bar;
+    a.Lgain_bar = Lgain_bar; a.x0_bar = x0_bar; a.xhat0_bar = xhat0_bar; a.model_bar = model_bar;
+    return tracking_estimated_vjp(h, kHostMem, t, a, "qln_tracking_rollout_estimated_vjp_host");
 }
 int qln_tracking_rollout_estimated_guarded_vjp(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                                const double* H, int32_t ny, const double* model, const double* Zout,
@@ -2118,9 +2096,13 @@ int qln_tracking_rollout_estimated_guarded_vjp(qln_handle* h, const double* Zref
                                                const double* event_hat, const double* Zbar, const double* Xhat_bar,
                                                const double* innov_bar, double* Zref_bar, double* K_bar, double* Lgain_bar,
                                                double* x0_bar, double* xhat0_bar, double* model_bar) {
-    return tracking_estimated_vjp(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, event, event_hat}, true,
-                                  {Zbar, Xhat_bar, innov_bar, Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar, model_bar},
-                                  "qln_tracking_rollout_estimated_guarded_vjp");
+    EstimatedTraj t{};
+    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout;
+    t.Xhat = Xhat; t.innov = innov; t.guarded = true; t.event = event; t.event_hat = event_hat;
+    qln::EstimatedVjpArgs a{};
+    a.Zbar = Zbar; a.Xhat_bar = Xhat_bar; a.innov_bar = innov_bar; a.Zref_bar = Zref_bar; a.K_bar = K_bar;
+    a.Lgain_bar = Lgain_bar; a.x0_bar = x0_bar; a.xhat0_bar = xhat0_bar; a.model_bar = model_bar;
+    return tracking_estimated_vjp(h, kDeviceMem, t, a, "qln_tracking_rollout_estimated_guarded_vjp");
 }
 int qln_tracking_rollout_estimated_guarded_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                                     const double* H, int32_t ny, const double* model, const double* Zout,
@@ -2128,9 +2110,13 @@ int qln_tracking_rollout_estimated_guarded_vjp_host(qln_handle* h, const double*
                                                     const double* event_hat, const double* Zbar, const double* Xhat_bar,
                                                     const double* innov_bar, double* Zref_bar, double* K_bar, double* Lgain_bar,
                                                     double* x0_bar, double* xhat0_bar, double* model_bar) {
-    return tracking_estimated_vjp_host(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, event, event_hat}, true,
-                                       {Zbar, Xhat_bar, innov_bar, Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar, model_bar},
-                                       "qln_tracking_rollout_estimated_guarded_vjp_host");
+    EstimatedTraj t{};
+    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout;
+    t.Xhat = Xhat; t.innov = innov; t.guarded = true; t.event = event; t.event_hat = event_hat;
+    qln::EstimatedVjpArgs a{};
+    a.Zbar = Zbar; a.Xhat_bar = Xhat_bar; a.innov_bar = innov_bar; a.Zref_bar = Zref_bar; a.K_bar = K_bar;
+    a.Lgain_bar = Lgain_bar; a.x0_bar = x0_bar; a.xhat0_bar = xhat0_bar; a.model_bar = model_bar;
+    return tracking_estimated_vjp(h, kHostMem, t, a, "qln_tracking_rollout_estimated_guarded_vjp_host");
 }
 
 // the sweeps at the limited loop's active set: the same path with its saturation record; event and event_hat select the guarded
@@ -2142,11 +2128,14 @@ int qln_tracking_rollout_estimated_limited_jvp(qln_handle* h, const double* Zref
                                                const double* K_dot, const double* Lgain_dot, const double* x0_dot,
                                                const double* xhat0_dot, const double* model_dot, double* Zout_dot,
                                                double* Xhat_dot, double* innov_dot, double* event_dot, double* event_hat_dot) {
-    return tracking_estimated_jvp(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, event, event_hat, sat, true},
-                                  event != nullptr && event_hat != nullptr,
-                                  {Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, Zout_dot, Xhat_dot, innov_dot,
-                                   event_dot, event_hat_dot},
-                                  "qln_tracking_rollout_estimated_limited_jvp");
+    EstimatedTraj t{};
+    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout; t.Xhat = Xhat;
+    t.innov = innov; t.guarded = event && event_hat; t.event = event; t.event_hat = event_hat; t.limited = true; t.sat = sat;
+    qln::EstimatedJvpArgs a{};
+    a.Zref_dot = Zref_dot; a.K_dot = K_dot; a.Lgain_dot = Lgain_dot; a.x0_dot = x0_dot;
+    a.xhat0_dot = xhat0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.Xhat_dot = Xhat_dot;
+    a.innov_dot = innov_dot; a.event_dot = event_dot; a.event_hat_dot = event_hat_dot;
+    return tracking_estimated_jvp(h, kDeviceMem, t, a, "qln_tracking_rollout_estimated_limited_jvp");
 }
 int qln_tracking_rollout_estimated_limited_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                                     const double* H, int32_t ny, const double* model, const double* Zout,
@@ -2156,11 +2145,14 @@ int qln_tracking_rollout_estimated_limited_jvp_host(qln_handle* h, const double*
                                                     const double* xhat0_dot, const double* model_dot, double* Zout_dot,
                                                     double* Xhat_dot, double* innov_dot, double* event_dot,
                                                     double* event_hat_dot) {
-    return tracking_estimated_jvp_host(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, event, event_hat, sat, true},
-                                       event != nullptr && event_hat != nullptr,
-                                       {Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, Zout_dot, Xhat_dot, innov_dot,
-                                        event_dot, event_hat_dot},
-                                       "qln_tracking_rollout_estimated_limited_jvp_host");
+    EstimatedTraj t{};
+    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout; t.Xhat = Xhat;
+    t.innov = innov; t.guarded = event && event_hat; t.event = event; t.event_hat = event_hat; t.limited = true; t.sat = sat;
+    qln::EstimatedJvpArgs a{};
+    a.Zref_dot = Zref_dot; a.K_dot = K_dot; a.Lgain_dot = Lgain_dot; a.x0_dot = x0_dot;
+    a.xhat0_dot = xhat0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.Xhat_dot = Xhat_dot;
+    a.innov_dot = innov_dot; a.event_dot = event_dot; a.event_hat_dot = event_hat_dot;
+    return tracking_estimated_jvp(h, kHostMem, t, a, "qln_tracking_rollout_estimated_limited_jvp_host");
 }
 int qln_tracking_rollout_estimated_limited_vjp(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                                const double* H, int32_t ny, const double* model, const double* Zout,
@@ -2168,10 +2160,13 @@ int qln_tracking_rollout_estimated_limited_vjp(qln_handle* h, const double* Zref
                                                const double* event_hat, const double* sat, const double* Zbar,
                                                const double* Xhat_bar, const double* innov_bar, double* Zref_bar, double* K_bar,
                                                double* Lgain_bar, double* x0_bar, double* xhat0_bar, double* model_bar) {
-    return tracking_estimated_vjp(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, event, event_hat, sat, true},
-                                  event != nullptr && event_hat != nullptr,
-                                  {Zbar, Xhat_bar, innov_bar, Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar, model_bar},
-                                  "qln_tracking_rollout_estimated_limited_vjp");
+    EstimatedTraj t{};
+    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout; t.Xhat = Xhat;
+    t.innov = innov; t.guarded = event && event_hat; t.event = event; t.event_hat = event_hat; t.limited = true; t.sat = sat;
+    qln::EstimatedVjpArgs a{};
+    a.Zbar = Zbar; a.Xhat_bar = Xhat_bar; a.innov_bar = innov_bar; a.Zref_bar = Zref_bar; a.K_bar = K_bar;
+    a.Lgain_bar = Lgain_bar; a.x0_bar = x0_bar; a.xhat0_bar = xhat0_bar; a.model_bar = model_bar;
+    return tracking_estimated_vjp(h, kDeviceMem, t, a, "qln_tracking_rollout_estimated_limited_vjp");
 }
 int qln_tracking_rollout_estimated_limited_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                                     const double* H, int32_t ny, const double* model, const double* Zout,
@@ -2180,10 +2175,13 @@ int qln_tracking_rollout_estimated_limited_vjp_host(qln_handle* h, const double*
                                                     const double* Xhat_bar, const double* innov_bar, double* Zref_bar,
                                                     double* K_bar, double* Lgain_bar, double* x0_bar, double* xhat0_bar,
                                                     double* model_bar) {
-    return tracking_estimated_vjp_host(h, {Zref, K, Lgain, H, ny, model, Zout, Xhat, innov, event, event_hat, sat, true},
-                                       event != nullptr && event_hat != nullptr,
-                                       {Zbar, Xhat_bar, innov_bar, Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar, model_bar},
-                                       "qln_tracking_rollout_estimated_limited_vjp_host");
+    EstimatedTraj t{};
+    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout; t.Xhat = Xhat;
+    t.innov = innov; t.guarded = event && event_hat; t.event = event; t.event_hat = event_hat; t.limited = true; t.sat = sat;
+    qln::EstimatedVjpArgs a{};
+    a.Zbar = Zbar; a.Xhat_bar = Xhat_bar; a.innov_bar = innov_bar; a.Zref_bar = Zref_bar; a.K_bar = K_bar;
+    a.Lgain_bar = Lgain_bar; a.x0_bar = x0_bar; a.xhat0_bar = xhat0_bar; a.model_bar = model_bar;
+    return tracking_estimated_vjp(h, kHostMem, t, a, "qln_tracking_rollout_estimated_limited_vjp_host");
 }
 
 // ------------------------------------------------------------------ host-pointer (MOI) mode

@@ -1,0 +1,109 @@
+"""The refusals of the qln_tracking_* entry points that sit behind the handle: the overlap rule of each of the eight
+operations (the forward and the reverse sweep of the estimate-feedback roll-out counted apart), in both memory forms, and
+the value checks of the host forms.  Every call here is refused before the device is bound: no kernel runs.
+
+The pairs are the ones the overlap rule has always looked at -- every (output, input) and (output, output) of the lists
+below, which are written out from the rule's lists at commit b1a6346 -- and only those: a pair the rule accepts would launch
+and write through the alias, past the end of the smaller buffer."""
+import itertools
+
+import numpy as np
+import pytest
+
+from quadruped_landing_amd import _lib
+from tests import tracking_abi as TA
+from tests import tracking_cases as TC
+
+pytestmark = pytest.mark.gpu
+
+B, N = 3, 5
+INTS = {"ny": 2, "sigma0_batch": 1, "guarded": 1}
+TRAJ = ["Zref", "K", "Lgain", "H", "model", "Zout", "Xhat", "innov", "event", "event_hat", "sat"]  # the estimated sweeps'
+# operation -> (the entry point with every argument, the outputs the rule looks at, the inputs it looks at)
+RULE = {
+    "lqr": ("qln_tracking_lqr_limited", ["K", "P"], ["Ztraj", "model", "event", "sat"]),
+    "rollout": ("qln_tracking_rollout_limited", ["Zout", "event", "sat"], ["Zref"]),  # not K, x0 and model
+    "rollout_vjp": ("qln_tracking_rollout_limited_vjp", ["Zref_bar", "K_bar", "x0_bar", "model_bar"],
+                    ["Zref", "K", "Zout", "Zbar", "model", "event", "sat"]),
+    "rollout_jvp": ("qln_tracking_rollout_limited_jvp", ["Zout_dot", "event_dot"],
+                    ["Zref", "K", "Zout", "model", "event", "sat", "Zref_dot", "K_dot", "x0_dot", "model_dot"]),
+    "covariance": ("qln_tracking_covariance_guarded", ["Sigma", "marg", "event_var"],
+                   ["Zout", "K", "Sigma0", "model", "event"]),
+    "kalman": ("qln_tracking_kalman_guarded", ["Lgain", "Pest", "Sigma", "marg", "event_var"],
+               ["Zout", "K", "H", "Sigma0", "model", "event"]),
+    "estimated": ("qln_tracking_rollout_estimated_limited", ["Zout", "Xhat", "innov", "event", "event_hat", "sat"],
+                  ["Zref", "K", "Lgain", "H", "vnoise", "wnoise", "x0", "xhat0", "model"]),
+    # innov is in the rule because Lgain_dot / Lgain_bar is given
+    "estimated_jvp": ("qln_tracking_rollout_estimated_limited_jvp",
+                      ["Zout_dot", "Xhat_dot", "innov_dot", "event_dot", "event_hat_dot"],
+                      TRAJ + ["Zref_dot", "K_dot", "Lgain_dot", "x0_dot", "xhat0_dot", "model_dot"]),
+    "estimated_vjp": ("qln_tracking_rollout_estimated_limited_vjp",
+                      ["Zref_bar", "K_bar", "Lgain_bar", "x0_bar", "xhat0_bar", "model_bar"],
+                      TRAJ + ["Zbar", "Xhat_bar", "innov_bar"]),
+}
+# host forms: (the parameter, the entry of its buffer, the value, what the refusal says)
+VALUES = [
+    ("model", 1, 0.0, "is not finite, or a mass or the body length is not positive"),  # mb = 0
+    ("event", 0, float(N - 1), "is not a knot of the roll-out"),
+    ("event", 1, -0.5, "(tau) is not finite or is negative"),
+    ("sat", 0, 3.0, "is not a saturation code"),
+    ("H", 0, float("nan"), "H is not finite"),
+]
+
+
+@pytest.fixture(scope="module")
+def handle():
+    nlp = TC.nlp(TC.batch(B, N, 2, 1, seed=5))
+    yield nlp
+    del nlp
+
+
+def _ones(name, nlp, device):
+    """parameter -> its own buffer of ones of the right size (a host array where the parameter is one in both forms)"""
+    import torch
+
+    vals = {}
+    for p in TA.PARAMS[name]:
+        if TA.is_int(name, p):
+            vals[p] = INTS[p]
+        elif device and p not in TA.HOST_ONLY:
+            vals[p] = torch.ones(TA.size(p, B, N, nlp.dims.z_total), dtype=torch.float64, device="cuda")
+        else:
+            vals[p] = np.ones(TA.size(p, B, N, nlp.dims.z_total))
+    return vals
+
+
+def _inputs_of(name, op):
+    """The event records and sat are outputs of the two roll-outs and inputs of everything else."""
+    return [p for p in ("model", "event", "sat", "H") if p in TA.PARAMS[name] and p not in RULE[op][1]]
+
+
+@pytest.mark.parametrize("host", [False, True], ids=["device", "host"])
+@pytest.mark.parametrize("op", sorted(RULE))
+def test_every_pair_of_the_overlap_rule_is_refused(handle, op, host):
+    name, outs, ins = RULE[op]
+    name += "_host" if host else ""
+    assert set(outs) | set(ins) <= set(TA.PARAMS[name])
+    L, base = _lib.lib(), _ones(name, handle, device=not host)
+    pairs = [(o, i, "an output overlaps an input") for o in outs for i in ins]
+    pairs += [(o, q, "two outputs overlap") for o, q in itertools.combinations(outs, 2)]
+    for first, second, text in pairs:
+        vals = dict(base)
+        vals[second] = vals[first]
+        assert TA.call(handle._h, name, vals) == _lib.QLN_ERR_INVALID_ARGUMENT, (name, first, second)
+        assert L.qln_last_error().decode() == f"{name}: {text}", (name, first, second)
+
+
+@pytest.mark.parametrize("op", sorted(RULE))
+def test_host_forms_refuse_bad_values_before_they_bind_the_device(handle, op):
+    name = RULE[op][0] + "_host"
+    L, checked = _lib.lib(), _inputs_of(name, op)
+    for p, entry, value, text in VALUES:
+        if p not in checked:
+            continue
+        vals = _ones(name, handle, device=False)
+        vals[p][entry] = value
+        outs = {q: vals[q].copy() for q in RULE[op][1]}
+        assert TA.call(handle._h, name, vals) == _lib.QLN_ERR_INVALID_ARGUMENT, (name, p, value)
+        assert text in L.qln_last_error().decode(), (name, p, L.qln_last_error())
+        assert all(np.array_equal(vals[q], outs[q]) for q in outs)
