@@ -1115,6 +1115,50 @@ int qln_tracking_rollout_estimated_limited_vjp_host(qln_handle* h, const double*
                                                     const double* Xhat_bar, const double* innov_bar, double* Zref_bar,
                                                     double* K_bar, double* Lgain_bar, double* x0_bar, double* xhat0_bar,
                                                     double* model_bar);
+/* Fixed-interval SMOOTHING of a flown landing: the state at every knot given all N measurements, where the filter's Xhat_k uses
+ * the measurements up to knot k only.  The modified Bryson-Frazier sweep, backward over the record a roll-out of the
+ * estimate-feedback loop left (qln_tracking_rollout_estimated*), on the filter qln_tracking_kalman designed.  It inverts
+ * nothing: the Rauch-Tung-Striebel form needs (P^-_{k+1})^-1, which is singular in ordinary use here (a clock slot with zero
+ * initial and process variance).
+ * Knots are 0-based.  A_k are exactly the blocks of qln_tracking_kalman at Ztraj's (x_k, u_k); guarded, the blocks of
+ * qln_tracking_kalman_guarded at (Ztraj, model, event), with the touchdown knot's composite A*.  L_k = Lgain[b][k] and
+ * P^+_k = Pest[b][k] are that call's outputs.  q_{N-1} = 0, Theta_{N-1} = 0, and for k = N-1 .. 0
+ *     Xs_k     = Xhat_k + P^+_k q_k
+ *     Ps_k     = P^+_k - P^+_k Theta_k P^+_k                 (lower triangle only: exactly symmetric)
+ *     C_k      = I - L_k H
+ *     e_k      = innov_k - H (L_k innov_k)                   (the post-fit residual)
+ *     r_k      = H' (e_k ./ V) + C_k' q_k
+ *     Lambda_k = H' diag(1/V) H C_k + C_k' Theta_k C_k       (lower triangle only)
+ *     q_{k-1}  = A_{k-1}' r_k,   Theta_{k-1} = A_{k-1}' Lambda_k A_{k-1}
+ * This is the Bryson-Frazier smoother rewritten with S^-1 = V^-1 (I - H L) and (I - L H) P^- = P^+, two identities that hold for
+ * the optimal gains of qln_tracking_kalman at the same (Ztraj, H, V, Sigma0, W).  So the call needs neither Sigma0, W nor K, no
+ * ny x ny factorisation and no 15 x 15 inverse -- and it does NOT check that Lgain and Pest belong together: with other gains it
+ * returns the recursion's values, which are then not a smoother's.  First order at a fixed touchdown knot, as every sweep here.
+ * Xs is in absolute coordinates (Xhat is), so no reference is read.
+ * Inputs (all required but model): Ztraj [B] x z_stride, the trajectory the filter was designed along; Lgain [B][N][15][ny] and
+ *   Pest [B][N][120] packed, qln_tracking_kalman's; H [ny][15] and Vdiag (a HOST array, ny entries, finite and > 0) as for that
+ *   call, eight rows always, the rows behind ny being zero rows with V = 1 and zero columns of L, so a call gives the bits of the
+ *   same call with those written out; Xhat [B][N][15] and innov [B][N][ny], the roll-out's record.
+ * Outputs (each optional, at least one non-NULL; overwritten; which is asked for does not change the other's bits; none may
+ * overlap an input or the other output):
+ *   Xs: [B][N][15], the smoothed states.   Ps: [B][N][120] packed, their error covariances.
+ * At knot N-1, Xs = Xhat and Ps = Pest bit for bit.
+ * Refused with QLN_ERR_INVALID_ARGUMENT: ny outside 1..QLN_TRACK_NY_MAX, no output, a NULL event in the guarded form, a NULL
+ * input, a V entry not finite or not > 0, overlaps -- the checks that need no handle before the null handle, in the family's
+ * order.  The device forms do not validate device data; the host forms also refuse a non-finite H and validate model and event
+ * as qln_tracking_kalman_guarded_host does.  A guarded batch without a touchdown and with model == NULL gives
+ * qln_landing_smoother's bits for a handle with k_trans = N + 1.  Device pointers, stream-ordered; needs no cost table. */
+int qln_landing_smoother(qln_handle* h, const double* Ztraj, const double* Lgain, const double* Pest, const double* H, int32_t ny,
+                         const double* Vdiag /* host, ny entries, finite and > 0 */, const double* Xhat, const double* innov,
+                         double* Xs /* [B][N][15] or NULL */, double* Ps /* [B][N][120] packed, or NULL */);
+int qln_landing_smoother_host(qln_handle* h, const double* Ztraj, const double* Lgain, const double* Pest, const double* H,
+                              int32_t ny, const double* Vdiag, const double* Xhat, const double* innov, double* Xs, double* Ps);
+int qln_landing_smoother_guarded(qln_handle* h, const double* Ztraj, const double* model /* or NULL */,
+                                 const double* event /* required */, const double* Lgain, const double* Pest, const double* H,
+                                 int32_t ny, const double* Vdiag, const double* Xhat, const double* innov, double* Xs, double* Ps);
+int qln_landing_smoother_guarded_host(qln_handle* h, const double* Ztraj, const double* model, const double* event,
+                                      const double* Lgain, const double* Pest, const double* H, int32_t ny, const double* Vdiag,
+                                      const double* Xhat, const double* innov, double* Xs, double* Ps);
 /* Z <- Z + N(0, sigma^2) on every entry, step lengths h then clipped to [h_min, h_max] (redraw_h = 0) or redrawn
  * U(h_min, h_max) (redraw_h != 0) -- the evaluation point of SURVEY.md 8d from qln_initial_guess's Z0.  The normal
  * draws are Box-Muller on the sampler's stream from `stream_offset`: the recipe's distribution, not numpy's numbers. */

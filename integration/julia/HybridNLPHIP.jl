@@ -396,6 +396,43 @@ function tracking_kalman_guarded(prob::HybridNLPHIP, Zout::Vector{Float64}, even
                     marg === nothing ? C_NULL : marg, event_var === nothing ? C_NULL : event_var))
     return L, Pest, Sigma, marg, event_var
 end
+# Fixed-interval smoothing of a flown landing (include/qln_evaluator.h, DESIGN.md 4.25): the state at every knot given all N
+# measurements, by the modified Bryson-Frazier sweep, which inverts nothing.  Ztraj: the trajectory the filter was designed
+# along; L (ny, 15, N) and Pest (120, N) as tracking_kalman returns them for the same (Ztraj, H, V); Xhat (15, N) and innov
+# (ny, N): the record of tracking_rollout_estimated.  Returns (Xs, Ps): the smoothed states as (15, N) and their error
+# covariances as (120, N) packed lower triangles; at knot N, Xs = Xhat and Ps = Pest.  The call does not check that L and Pest
+# belong together.  landing_smoother_guarded is the same through the guard-triggered touchdown at (Ztraj, events, model).
+function landing_smoother(prob::HybridNLPHIP, Ztraj::Vector{Float64}, L::Array{Float64,3}, Pest::Matrix{Float64},
+                          H::Matrix{Float64}, V::Vector{Float64}, Xhat::Matrix{Float64}, innov::Matrix{Float64})
+    N = prob.N
+    ny = size(H, 1)
+    (1 <= ny <= 8 && size(H, 2) == 15 && length(V) == ny && size(L) == (ny, 15, N) && size(Pest) == (120, N) &&
+     size(Xhat) == (15, N) && size(innov) == (ny, N)) || error("H: (ny, 15), V: ny, L: (ny, 15, N), Pest: (120, N), Xhat: (15, N), innov: (ny, N)")
+    Hrow = Matrix{Float64}(transpose(H))  # row-major [ny][15]
+    Xs = zeros(15, N)
+    Ps = zeros(120, N)
+    qln_check(ccall((:qln_landing_smoother_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Ztraj, L, Pest, Hrow, Int32(ny), V, Xhat, innov, Xs, Ps))
+    return Xs, Ps
+end
+function landing_smoother_guarded(prob::HybridNLPHIP, Ztraj::Vector{Float64}, events::Vector{Float64}, L::Array{Float64,3},
+                                  Pest::Matrix{Float64}, H::Matrix{Float64}, V::Vector{Float64}, Xhat::Matrix{Float64},
+                                  innov::Matrix{Float64}; model=nothing)
+    N = prob.N
+    ny = size(H, 1)
+    (1 <= ny <= 8 && size(H, 2) == 15 && length(V) == ny && size(L) == (ny, 15, N) && size(Pest) == (120, N) &&
+     size(Xhat) == (15, N) && size(innov) == (ny, N)) || error("H: (ny, 15), V: ny, L: (ny, 15, N), Pest: (120, N), Xhat: (15, N), innov: (ny, N)")
+    Hrow = Matrix{Float64}(transpose(H))
+    Xs = zeros(15, N)
+    Ps = zeros(120, N)
+    qln_check(ccall((:qln_landing_smoother_guarded_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32,
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Ztraj, model === nothing ? C_NULL : model, events, L, Pest, Hrow, Int32(ny), V, Xhat, innov, Xs, Ps))
+    return Xs, Ps
+end
 # The estimate-feedback roll-out (include/qln_evaluator.h, DESIGN.md 4.22): the plant and the estimator flown together, the
 # forces fed back from the estimate xhat_k|k that the filter gains L of tracking_kalman build from y_k = H dx_k + v_k.  L: (ny, 15,
 # N) as tracking_kalman returns it; H: (ny, 15); vnoise: (ny, N) and wnoise: (15, N-1) samples drawn by the caller, nothing for

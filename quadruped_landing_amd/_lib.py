@@ -187,6 +187,10 @@ SIGNATURES = {
     "qln_tracking_kalman_host": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, C.c_int32] + [_dp] * 5),
     "qln_tracking_kalman_guarded": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, C.c_int32] + [_dp] * 6),
     "qln_tracking_kalman_guarded_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, C.c_int32] + [_dp] * 6),
+    "qln_landing_smoother": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 5),
+    "qln_landing_smoother_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 5),
+    "qln_landing_smoother_guarded": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 5),
+    "qln_landing_smoother_guarded_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 5),
     "qln_tracking_rollout_estimated": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 8),
     "qln_tracking_rollout_estimated_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 8),
     "qln_tracking_rollout_estimated_guarded": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 10),

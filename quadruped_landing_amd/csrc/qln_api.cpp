@@ -120,6 +120,8 @@ enum HostRole {
     kXhatD,  // out: the estimated jvp's Xhat_dot; in: the vjp's Xhat_bar   [B][N][15]
     kInnovD, // out: the estimated jvp's innov_dot; in: the vjp's innov_bar  [B][N][8]
     kEventHatD,  // out: the estimated guarded jvp's event_hat_dot          [B][8]
+    kXs,     // out: the smoother's states                                  [B][N][15]
+    kPs,     // out: the smoother's covariances                             layout of P
     kHostRoles
 };
 
@@ -189,7 +191,7 @@ int64_t host_role_size(const qln_handle* h, HostRole r) {
         case kF: case kSigma: return D.B;
         case kHvals: return (int64_t)(D.B - 1) * h->h_stride + hessian_nnz(D.N);  // no padding behind the last problem
         case kK: case kKbar: case kKdot: return tracking_k_total(D);
-        case kP: case kCov: case kPest: return tracking_p_total(D);
+        case kP: case kCov: case kPest: case kPs: return tracking_p_total(D);
         case kCov0: return (int64_t)D.B * QLN_TRACK_P_NNZ;
         case kMarg: return tracking_marg_total(D);
         case kX0: case kXhat0: return (int64_t)D.B * QLN_NX;
@@ -202,7 +204,7 @@ int64_t host_role_size(const qln_handle* h, HostRole r) {
         case kLgain: case kLgainD: return tracking_gain_total(D, QLN_TRACK_NY_MAX);
         case kVnoise: case kInnov: case kInnovD: return tracking_meas_total(D, QLN_TRACK_NY_MAX);
         case kWnoise: return (int64_t)D.B * (D.N - 1) * QLN_NX;
-        case kXhat: case kXhatD: return (int64_t)D.B * D.N * QLN_NX;
+        case kXhat: case kXhatD: case kXs: return (int64_t)D.B * D.N * QLN_NX;
         case kHostRoles: break;
     }
     return 0;
@@ -1786,6 +1788,84 @@ int qln_tracking_kalman_guarded_host(qln_handle* h, const double* Zout, const do
     a.ny = ny; a.Vdiag = Vdiag; a.Sigma0 = Sigma0; a.sigma0_batch = sigma0_batch; a.Wdiag = Wdiag;
     a.Lgain = Lgain; a.Pest = Pest; a.Sigma = Sigma; a.marg = marg; a.event_var = event_var;
     return tracking_kalman(h, kHostMem, a, "qln_tracking_kalman_guarded_host");
+}
+
+// The fixed-interval smoother (k_landing_smoother).  The checks that need no handle come first.
+// guarded: through the guard-triggered touchdown, which needs the roll-out's event records
+struct SmootherCall {
+    const double *Ztraj, *model, *event, *Lgain, *Pest, *H;
+    int32_t ny;
+    const double *Vdiag, *Xhat, *innov;
+    double *Xs, *Ps;
+    bool guarded;
+};
+
+static int check_landing_smoother_args(const qln_handle* h, const SmootherCall& a, const char* who) {
+    const std::string w(who);
+    if (a.ny < 1 || a.ny > QLN_TRACK_NY_MAX)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
+    if (!a.Xs && !a.Ps) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Xs and Ps are both NULL (nothing to compute)");
+    if (a.guarded && !a.event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
+    if (!a.H || !a.Vdiag) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null H or Vdiag");
+    for (int i = 0; i < a.ny; ++i)
+        if (!(std::isfinite(a.Vdiag[i]) && a.Vdiag[i] > 0.0))
+            return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Vdiag must be finite and > 0 (entry " + std::to_string(i) + ")");
+    if (!a.Lgain || !a.Pest) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Lgain or Pest");
+    if (!a.Xhat || !a.innov) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Xhat or innov");
+    if (int rc = check_handle(h)) return rc;
+    if (!a.Ztraj) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Ztraj");
+    return QLN_OK;
+}
+
+static int landing_smoother(qln_handle* h, MemForm mem, const SmootherCall& a, const char* who) {
+    if (int rc = check_landing_smoother_args(h, a, who)) return rc;
+    // the rows, gains and innovations of the call's ny, of the roles' eight
+    const HostArgs args = {copy_in(kV, a.Ztraj), copy_in(kModel, a.model), copy_in(kEvent, a.event),
+                           copy_in(kLgain, a.Lgain).sized(tracking_gain_total(h->dims, a.ny)), copy_in(kPest, a.Pest),
+                           copy_in(kH, a.H).sized((int64_t)a.ny * QLN_NX), copy_in(kXhat, a.Xhat),
+                           copy_in(kInnov, a.innov).sized(tracking_meas_total(h->dims, a.ny)), copy_out(kXs, a.Xs),
+                           copy_out(kPs, a.Ps)};
+    if (int rc = check_no_overlap(h, args, who)) return rc;
+    if (mem == kHostMem) {
+        if (int rc = check_host_meas(a.H, a.ny, who)) return rc;
+        if (int rc = check_host_models(h, a.model, who)) return rc;
+        if (int rc = check_host_events(h, a.event, who)) return rc;
+    }
+    return run_call(h, mem, args, [&](double* const* d, bool) {
+        return qln::launch_landing_smoother(h->p, d[kV], d[kModel], d[kEvent], d[kLgain], d[kPest], d[kH], a.ny, a.Vdiag,
+                                            d[kXhat], d[kInnov], d[kXs], d[kPs], h->stream);
+    });
+}
+
+int qln_landing_smoother(qln_handle* h, const double* Ztraj, const double* Lgain, const double* Pest, const double* H, int32_t ny,
+                         const double* Vdiag, const double* Xhat, const double* innov, double* Xs, double* Ps) {
+    SmootherCall a{};
+    a.Ztraj = Ztraj; a.Lgain = Lgain; a.Pest = Pest; a.H = H; a.ny = ny; a.Vdiag = Vdiag; a.Xhat = Xhat; a.innov = innov;
+    a.Xs = Xs; a.Ps = Ps;
+    return landing_smoother(h, kDeviceMem, a, "qln_landing_smoother");
+}
+int qln_landing_smoother_host(qln_handle* h, const double* Ztraj, const double* Lgain, const double* Pest, const double* H,
+                              int32_t ny, const double* Vdiag, const double* Xhat, const double* innov, double* Xs, double* Ps) {
+    SmootherCall a{};
+    a.Ztraj = Ztraj; a.Lgain = Lgain; a.Pest = Pest; a.H = H; a.ny = ny; a.Vdiag = Vdiag; a.Xhat = Xhat; a.innov = innov;
+    a.Xs = Xs; a.Ps = Ps;
+    return landing_smoother(h, kHostMem, a, "qln_landing_smoother_host");
+}
+int qln_landing_smoother_guarded(qln_handle* h, const double* Ztraj, const double* model, const double* event, const double* Lgain,
+                                 const double* Pest, const double* H, int32_t ny, const double* Vdiag, const double* Xhat,
+                                 const double* innov, double* Xs, double* Ps) {
+    SmootherCall a{};
+    a.Ztraj = Ztraj; a.model = model; a.guarded = true; a.event = event; a.Lgain = Lgain; a.Pest = Pest; a.H = H; a.ny = ny;
+    a.Vdiag = Vdiag; a.Xhat = Xhat; a.innov = innov; a.Xs = Xs; a.Ps = Ps;
+    return landing_smoother(h, kDeviceMem, a, "qln_landing_smoother_guarded");
+}
+int qln_landing_smoother_guarded_host(qln_handle* h, const double* Ztraj, const double* model, const double* event,
+                                      const double* Lgain, const double* Pest, const double* H, int32_t ny, const double* Vdiag,
+                                      const double* Xhat, const double* innov, double* Xs, double* Ps) {
+    SmootherCall a{};
+    a.Ztraj = Ztraj; a.model = model; a.guarded = true; a.event = event; a.Lgain = Lgain; a.Pest = Pest; a.H = H; a.ny = ny;
+    a.Vdiag = Vdiag; a.Xhat = Xhat; a.innov = innov; a.Xs = Xs; a.Ps = Ps;
+    return landing_smoother(h, kHostMem, a, "qln_landing_smoother_guarded_host");
 }
 
 // The estimate-feedback roll-out (k_tracking_rollout_estimated).  The checks that need no handle come first.

@@ -333,6 +333,12 @@ hipError_t launch_tracking_kalman(const BatchParams& p, const double* Zout, cons
                                   const double* event, const double* H, int ny, const double* Vd, const double* Sigma0,
                                   int sigma0_batch, const double* Wd, double* Lgain, double* Pest, double* Sigma, double* marg,
                                   double* event_var, hipStream_t stream);
+// The fixed-interval smoother of a flown landing (qln_landing_smoother / _guarded): Lgain [B][N][15][ny], Pest [B][N][120],
+// H [ny][15], Xhat [B][N][15] and innov [B][N][ny] on the device, Vd (ny) a host array; Xs [B][N][15] and Ps [B][N][120], either
+// may be null.  event selects the guarded blocks, and model is read with it only.
+hipError_t launch_landing_smoother(const BatchParams& p, const double* Ztraj, const double* model, const double* event,
+                                   const double* Lgain, const double* Pest, const double* H, int ny, const double* Vd,
+                                   const double* Xhat, const double* innov, double* Xs, double* Ps, hipStream_t stream);
 // The roll-out of the plant and the estimator side by side (qln_tracking_rollout_estimated / _guarded): Lgain [B][N][15][ny] and
 // H [ny][15] on the device; vnoise [B][N][ny], wnoise [B][N-1][15], x0, xhat0 [B][15], model and K may be null; Xhat [B][N][15],
 // innov [B][N][ny] may be null; event and event_hat [B][QLN_TOUCHDOWN_INFO_STRIDE] or null, with guarded only.

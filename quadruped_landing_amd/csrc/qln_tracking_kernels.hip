@@ -91,6 +91,10 @@
 // These three also exist with the flag kLimit (qln_tracking_rollout_estimated_limited and its _jvp / _vjp): the
 // forces fed back from the estimate are clamped by the PLANT's contact state before the plant, the estimator or Zout read them,
 // and the two sweeps treat the channels of that record as constants in both chains.
+//
+// k_landing_smoother: the fixed-interval smoother of a flown landing (qln_landing_smoother / _guarded), the
+// estimator's backward pass: the modified Bryson-Frazier sweep on the filter's gains and covariances, in k_tracking_kalman's
+// mapping and tiles, with the blocks and the touchdown operator applied transposed as the Riccati sweep applies them.
 #include "qln_row16.h"
 
 #include <utility>
@@ -1867,6 +1871,330 @@ __global__ __launch_bounds__(kWave) void k_tracking_kalman(BatchParams P, Kalman
 }
 
 
+// ---- k_landing_smoother ----
+// per-row LDS image (doubles): the P^+ image [15][17] (Ps_k leaves from it) | the Theta image [15][17] | the L tile [15][8] | the
+// H tile [8][16], 1/V in its column 15 | the knot's 20 entries of Ztraj | q [16] | r [16] | the knot's innovations [8]
+constexpr int kSStr = 17, kSP = 0, kSTh = 256, kSL = 512, kSH = kSL + 15 * QLN_TRACK_NY_MAX, kSZ = kSH + QLN_TRACK_NY_MAX * 16,
+              kSQ = kSZ + 20, kSR = kSQ + 16, kSI = kSR + 16, kSRow = kSI + QLN_TRACK_NY_MAX;
+static_assert(15 * kSStr <= kSTh - kSP && 15 * kSStr <= kSL - kSTh && kSH % 2 == 0 && kSZ % 2 == 0 && kSQ % 2 == 0 && kSR % 2 == 0 &&
+                  kSI % 2 == 0 && kSRow % 2 == 0 && kSRow <= kKRow,
+              "the images fit; 16-byte aligned sections; within the Kalman kernel's budget");
+
+// the reciprocals of the measurement variances; the rows behind ny carry 1
+struct SmootherNoise {
+    double iv[QLN_TRACK_NY_MAX];
+};
+
+// out = A_k' v on the knot's block: cov_apply's open-loop application with rows and columns exchanged
+__device__ __forceinline__ void block_apply_t(const StepBlock& blk, const double (&v)[15], double (&out)[15]) {
+#pragma unroll
+    for (int i = 0; i < 15; ++i) out[i] = 0.0;
+    StepBlock bk = blk;
+    asm volatile("" : "+v"(bk.wAt), "+v"(bk.wBt), "+v"(bk.wAw));  // as in cov_apply: the products are formed per application
+    for_each_rollout_entry(bk, [&](auto r, auto c, double val) {
+        if constexpr (c < 15) out[c] = fma(val, v[r], out[c]);
+    });
+}
+
+// entry (i, c) of a symmetric image, read from its lower triangle
+__host__ __device__ constexpr int sym_at(int i, int c) { return (i >= c) ? kSStr * i + c : kSStr * c + i; }
+
+// The fixed-interval smoother of a flown landing (include/qln_evaluator.h): the modified Bryson-Frazier sweep,
+// backward from knot N-1 on the filter's own gains L_k and covariances P^+_k, which inverts nothing.  The mapping of
+// k_tracking_kalman and of the Riccati sweep: one problem per row of sixteen lanes, lane j owns column j of P^+_k, of Theta and
+// of every product; the blocks A_k, the modes and the touchdown knot's operator are those sweeps', applied transposed
+// (block_apply_t, touchdown_apply_t).  Per knot k = N-1 .. 0:
+//   1. P^+_k, L_k, innov_k and Ztraj's knot k-1 (loaded one knot ahead) go to LDS; lane j reads its column p of P^+_k;
+//   2. Xs_k[j] = Xhat_k[j] + p . q (q: fifteen broadcast reads);  Ps_k column j = p - P^+ (Theta p): two dense chains on
+//      broadcast reads of the images' lower triangles, written into the P image's lower triangle, which leaves packed;
+//   3. r_k[j] = q_j + H[:, j] . ((innov - H (L innov)) ./ V - L'q): lane j's row of L against innov, sixteen row sums;
+//      Lambda_k column j = Theta c + H' (V^-1 (H c) - L' (Theta c)),  c = column j of I - L H: chains on broadcast reads of
+//      the L tile, the Theta image and the H tile; its entries on and below the diagonal replace the Theta image's;
+//   4. q_{k-1} = A' r (every lane alike, lane 0 writes it) and Theta_{k-1} = A' Lambda A by two transposed applications with a
+//      transpose through the image between them, as the covariance sweep's knot.  The body of 4 exists once per operator form.
+// The kernel is compiled for eight measurement rows, as k_tracking_kalman: zero rows of H with 1/V = 1 and zero columns of L
+// behind ny.  The vector recursion (q, r, Xs) and the matrix recursion (Theta, Lambda, Ps) share no value: each runs only when
+// its output is asked for, and neither changes the other's bits.
+template <bool kGuard>
+__global__ __launch_bounds__(kWave) void k_landing_smoother(BatchParams P, SmootherNoise Nz, const double* __restrict__ Ztraj,
+                                                            const double* __restrict__ Lg, const double* __restrict__ Pe,
+                                                            const double* __restrict__ Hg, int ny, const double* __restrict__ Xhat,
+                                                            const double* __restrict__ innov, double* __restrict__ Xs,
+                                                            double* __restrict__ Ps, const double* __restrict__ model,
+                                                            const double* __restrict__ event) {
+    constexpr int NY = QLN_TRACK_NY_MAX;
+    // rows of a dense chain whose broadcast reads are in flight together, held apart by an empty asm as K's rows in cov_apply.
+    // One wave per SIMD runs here, so a knot waits on LDS latency row by row; with three rows in flight the compiler hoisted
+    // the reads of whole chains and both instantiations went to scratch (152 and 92 bytes per lane), so it stays at one.
+    constexpr int kFlight = 1;
+    __shared__ double lds[kRows * kSRow];
+    const Row16 r16 = row16_of(P);  // lane 15 shadows column 14 and writes nothing to the images
+    const int ln = r16.ln, j = r16.j, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
+    const bool own = r16.own, valid = r16.valid;
+    const Model Mp = plant_model<kGuard>(P, model, bc);
+    const Model& M = kGuard ? Mp : r16.M;
+    [[maybe_unused]] int ks = -1;
+    [[maybe_unused]] double tau = 0.0;
+    if constexpr (kGuard) {
+        ks = guard_knot(event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc], N);
+        tau = event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + 1];
+    }
+    double* L = lds + r16.row * kSRow;
+    const bool wantX = Xs != nullptr, wantP = Ps != nullptr;
+    const double* __restrict__ Zb = Ztraj + (int64_t)bc * P.z_stride;
+    const double* __restrict__ Lb = Lg + (int64_t)bc * N * (QLN_NX * ny);
+    const double* __restrict__ Pb = Pe + (int64_t)bc * N * QLN_TRACK_P_NNZ;
+    const double* __restrict__ Xb = Xhat + (int64_t)bc * N * QLN_NX;
+    const double* __restrict__ Ib = innov + (int64_t)bc * N * ny;
+    double* __restrict__ Xo = wantX ? Xs + (int64_t)bc * N * QLN_NX : nullptr;
+    double* __restrict__ Po = wantP ? Ps + (int64_t)bc * N * QLN_TRACK_P_NNZ : nullptr;
+
+    // where the packed entries ln + 16 t lie in an image's lower triangle (relative to the image) and the entries of a knot's
+    // [15][ny] gain in the L tile (rows of eight), as in k_tracking_kalman
+    int po[8], lo[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const int i = min(ln + 16 * t, QLN_TRACK_P_NNZ - 1);
+        int r = 0;
+#pragma unroll
+        for (int q = 1; q < 15; ++q) r += (i >= q * (q + 1) / 2) ? 1 : 0;
+        po[t] = kSStr * r + (i - r * (r + 1) / 2);
+        const int g = min(ln + 16 * t, QLN_NX * ny - 1), gr = g / ny;
+        lo[t] = kSL + NY * gr + (g - ny * gr);
+    }
+    const int rowj = kSStr * j, colj = j;
+    auto sym = [&](int c) { return (c <= j) ? rowj + c : colj + kSStr * c; };  // relative to the image
+
+    // q_{N-1} = 0, Theta_{N-1} = 0; the H tile, zero rows behind ny; the L tile's columns and the innovations behind ny stay 0.0
+    {
+#pragma unroll
+        for (int t = 0; t < 16; ++t) L[kSTh + ln + 16 * t] = 0.0;
+#pragma unroll
+        for (int t = 0; t < 8; ++t)
+            if (ln + 16 * t < 15 * NY) L[kSL + ln + 16 * t] = 0.0;
+#pragma unroll
+        for (int r = 0; r < NY; ++r) L[kSH + 16 * r + ln] = own ? ((r < ny) ? Hg[15 * r + ln] : 0.0) : Nz.iv[r];  // column 15: 1/V
+        L[kSQ + ln] = 0.0;
+        L[kSR + ln] = 0.0;
+        if (ln < NY) L[kSI + ln] = 0.0;
+    }
+
+    // the knot's inputs, requested one knot ahead: P^+_k and L_k (entries ln + 16 t), Xhat_k[j], innov_k[ln] and Ztraj's knot k-1
+    double pn[8], gn[8], xn = 0.0, in = 0.0, zn[2] = {0.0, 0.0};
+    auto request = [&](int k) {
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            pn[t] = Pb[(int64_t)k * QLN_TRACK_P_NNZ + min(ln + 16 * t, QLN_TRACK_P_NNZ - 1)];
+            gn[t] = Lb[(int64_t)k * (QLN_NX * ny) + min(ln + 16 * t, QLN_NX * ny - 1)];
+        }
+        if (wantX) {
+            xn = Xb[(int64_t)k * QLN_NX + j];
+            in = Ib[(int64_t)k * ny + min(ln, ny - 1)];
+        }
+        if (k > 0) knot_load(Zb + 20 * (k - 1), ln, zn[0], zn[1]);
+    };
+    request(N - 1);
+    wave_lds_sync();
+
+    for (int k = N - 1; k >= 0; --k) {
+        // ---- 1. the knot's inputs into LDS ----
+        {
+            int le = ln;  // an opaque copy, as in k_tracking_kalman's emit: the tails' lane masks are formed here
+            asm volatile("" : "+v"(le));
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                if (le + 16 * t < QLN_TRACK_P_NNZ) L[kSP + po[t]] = pn[t];
+                if (le + 16 * t < QLN_NX * ny) L[lo[t]] = gn[t];
+            }
+            if (wantX && le < ny) L[kSI + ln] = in;
+            if (k > 0) {
+                L[kSZ + ln] = zn[0];
+                if (le < 4) L[kSZ + 16 + ln] = zn[1];
+            }
+        }
+        const double xh = xn;
+        if (k > 0) request(k - 1);
+        wave_lds_sync();  // the knot's tiles are in place
+
+        // ---- 2. Xs_k and Ps_k ----
+        {
+            double p[15];
+#pragma unroll
+            for (int c = 0; c < 15; ++c) p[c] = L[kSP + sym(c)];
+            if (wantX) {
+                double acc = p[0] * L[kSQ];
+#pragma unroll
+                for (int c = 1; c < 15; ++c) acc = fma(p[c], L[kSQ + c], acc);
+                if (valid && own) Xo[(int64_t)k * QLN_NX + j] = xh + acc;
+            }
+            if (wantP) {
+                double u[15], ps[15];
+#pragma unroll
+                for (int i = 0; i < 15; ++i) {
+                    double acc = L[kSTh + sym_at(i, 0)] * p[0];
+#pragma unroll
+                    for (int c = 1; c < 15; ++c) acc = fma(L[kSTh + sym_at(i, c)], p[c], acc);
+                    if (i % kFlight == kFlight - 1) asm volatile("" : "+v"(acc) : : "memory");  // kFlight rows in flight at a time
+                    u[i] = acc;
+                }
+#pragma unroll
+                for (int i = 0; i < 15; ++i) {
+                    double acc = L[kSP + sym_at(i, 0)] * u[0];
+#pragma unroll
+                    for (int c = 1; c < 15; ++c) acc = fma(L[kSP + sym_at(i, c)], u[c], acc);
+                    if (i % kFlight == kFlight - 1) asm volatile("" : "+v"(acc) : : "memory");
+                    ps[i] = p[i] - acc;
+                }
+                wave_lds_sync();  // every lane has read P^+_k: Ps_k may overwrite the image
+                if (own) {  // column j on and below the diagonal: the lower triangle of the stated expression
+#pragma unroll
+                    for (int i = 0; i < 15; ++i)
+                        if (i >= j) L[kSP + kSStr * i + j] = ps[i];
+                }
+                wave_lds_sync();
+                if (valid) {
+                    int le = ln;
+                    asm volatile("" : "+v"(le));
+                    double* __restrict__ o = Po + (int64_t)k * QLN_TRACK_P_NNZ;
+#pragma unroll
+                    for (int t = 0; t < 8; ++t)
+                        if (le + 16 * t < QLN_TRACK_P_NNZ) o[ln + 16 * t] = L[kSP + po[t]];
+                }
+            }
+        }
+        if (k == 0) break;
+
+        // ---- 3. r_k and Lambda_k ----
+        {
+            double x[NY], hj[NY];  // row j of L_k, column j of H
+#pragma unroll
+            for (int r = 0; r < NY; ++r) {
+                x[r] = L[kSL + NY * j + r];
+                hj[r] = L[kSH + 16 * r + j];
+            }
+            if (wantX) {
+                double y = x[0] * L[kSI];  // (L innov)[j]
+#pragma unroll
+                for (int r = 1; r < NY; ++r) y = fma(x[r], L[kSI + r], y);
+                const double qj = L[kSQ + j];
+                double rj = qj;
+#pragma unroll
+                for (int r = 0; r < NY; ++r) {
+                    const double e = L[kSI + r] - row_sum16(own ? hj[r] * y : 0.0);  // the post-fit residual
+                    const double lq = row_sum16(own ? x[r] * qj : 0.0);             // (L'q)[r]
+                    rj = fma(hj[r], fma(e, L[kSH + 16 * r + 15], -lq), rj);
+                }
+                if (own) L[kSR + j] = rj;
+            }
+            if (wantP) {
+                double cj[15], u[15], w[NY];
+                int je = j;  // an opaque copy: the fifteen masks i == j are formed here, not ahead of the loop
+                asm volatile("" : "+v"(je));
+#pragma unroll
+                for (int i = 0; i < 15; ++i) {
+                    double acc = (i == je) ? 1.0 : 0.0;
+#pragma unroll
+                    for (int r = 0; r < NY; ++r) acc = fma(-L[kSL + NY * i + r], hj[r], acc);
+                    if (i % kFlight == kFlight - 1) asm volatile("" : "+v"(acc) : : "memory");
+                    cj[i] = acc;
+                }
+#pragma unroll
+                for (int i = 0; i < 15; ++i) {
+                    double acc = L[kSTh + sym_at(i, 0)] * cj[0];
+#pragma unroll
+                    for (int c = 1; c < 15; ++c) acc = fma(L[kSTh + sym_at(i, c)], cj[c], acc);
+                    if (i % kFlight == kFlight - 1) asm volatile("" : "+v"(acc) : : "memory");
+                    u[i] = acc;
+                }
+#pragma unroll
+                for (int r = 0; r < NY; ++r) {
+                    double hc = L[kSH + 16 * r] * cj[0], lu = L[kSL + r] * u[0];
+#pragma unroll
+                    for (int c = 1; c < 15; ++c) {
+                        hc = fma(L[kSH + 16 * r + c], cj[c], hc);
+                        lu = fma(L[kSL + NY * c + r], u[c], lu);
+                    }
+                    asm volatile("" : "+v"(hc), "+v"(lu) : : "memory");
+                    w[r] = fma(hc, L[kSH + 16 * r + 15], -lu);
+                }
+#pragma unroll
+                for (int i = 0; i < 15; ++i) {
+                    double acc = u[i];
+#pragma unroll
+                    for (int r = 0; r < NY; ++r) acc = fma(L[kSH + 16 * r + i], w[r], acc);
+                    if (i % kFlight == kFlight - 1) asm volatile("" : "+v"(acc) : : "memory");
+                    u[i] = acc;
+                }
+                wave_lds_sync();  // every lane has read Theta_k: Lambda_k may overwrite the image
+                // Column j on and below the diagonal, not the whole column as a row: H' V^-1 H C is symmetric only up to the
+                // rounding of H C, which 1 / V magnifies, and the entry (i, j), i >= j, of the stated expression is column j's
+                if (own) {
+#pragma unroll
+                    for (int i = 0; i < 15; ++i)
+                        if (i >= j) L[kSTh + kSStr * i + j] = u[i];
+                }
+            }
+        }
+        wave_lds_sync();  // r_k and Lambda_k are in place
+
+        // ---- 4. q_{k-1} = A_{k-1}' r_k, Theta_{k-1} = A_{k-1}' Lambda_k A_{k-1} ----
+        // apply_t(v, out): out = A' v on the knot's operator.  The body exists once per operator -- the step block's and the
+        // touchdown knot's -- so that neither form's values stay live across the other's applications (as k_tracking_kalman).
+        auto back = [&](auto apply_t) {
+            double v[15], out[15];
+            if (wantX) {
+#pragma unroll
+                for (int c = 0; c < 15; ++c) v[c] = L[kSR + c];
+                apply_t(v, out);
+                if (ln == 0) {
+#pragma unroll
+                    for (int c = 0; c < 15; ++c) L[kSQ + c] = out[c];
+                }
+            }
+            if (wantP) {
+                // only the lower triangle of Lambda_k is read: it is exactly symmetric
+#pragma unroll
+                for (int c = 0; c < 15; ++c) v[c] = L[kSTh + sym(c)];
+                apply_t(v, out);  // column j of A' Lambda
+                wave_lds_sync();  // the image has been read
+                if (own) {
+#pragma unroll
+                    for (int i = 0; i < 15; ++i) L[kSTh + kSStr * j + i] = out[i];
+                }
+                wave_lds_sync();
+#pragma unroll
+                for (int c = 0; c < 15; ++c) v[c] = L[kSTh + kSStr * c + j];  // row j of A' Lambda = column j of Lambda A
+                apply_t(v, out);
+                wave_lds_sync();
+                if (own) {
+#pragma unroll
+                    for (int i = 0; i < 15; ++i) L[kSTh + kSStr * j + i] = out[i];
+                }
+            }
+        };
+        KnotMode md;
+        if constexpr (kGuard) md = guard_mode(k - 1, ks, im);
+        else md = knot_mode(k, kt - 1, im);
+        if (kGuard && k - 1 == ks) {  // the touchdown knot: the composite operator, transposed, in the block's place
+            double xk[15];
+#pragma unroll
+            for (int i = 0; i < 14; ++i) xk[i] = L[kSZ + i];
+            xk[14] = 0.0;  // the clock feeds nothing
+            const double u5[5] = {L[kSZ + 15], L[kSZ + 16], L[kSZ + 17], L[kSZ + 18], L[kSZ + 19]};
+            const TouchdownBlock tb = touchdown_block(M, md, tau, xk, u5);
+            back([&](const double (&v)[15], double (&out)[15]) {
+                double bf[4];
+                touchdown_apply_t(tb, M, v, out, bf);
+            });
+        } else {
+            const StepBlock blk = step_block(L + kSZ, md, M);
+            back([&](const double (&v)[15], double (&out)[15]) { block_apply_t(blk, v, out); });
+        }
+        wave_lds_sync();  // q_{k-1} and Theta_{k-1} are in place; the tiles and the knot may be rewritten
+    }
+}
+
+
 // ---- k_tracking_rollout_jvp ----
 // One knot's inputs, as lane ln of a row loads them.  z0 / zd0: entry ln of the knot's twenty in Zout / Zref_dot (lane
 // j < 15: x_j, lane 15: F1x); z1 / zd1: entry 16 + (ln & 3) (F1y, F2x, F2y, h in lanes 0-3).  xr: x_ref,j; kc, kd: column j
@@ -2760,6 +3088,22 @@ hipError_t launch_tracking_kalman(const BatchParams& p, const double* Zout, cons
         K ? go(k_tracking_kalman<true, true, true>) : go(k_tracking_kalman<false, true, true>);
     else
         K ? go(k_tracking_kalman<true, false, false>) : go(k_tracking_kalman<false, false, false>);
+    return hipGetLastError();
+}
+
+// The two instantiations of k_landing_smoother: event or the knot schedule (model is read with event only, as above).
+hipError_t launch_landing_smoother(const BatchParams& p, const double* Ztraj, const double* model, const double* event,
+                                   const double* Lgain, const double* Pest, const double* H, int ny, const double* Vd,
+                                   const double* Xhat, const double* innov, double* Xs, double* Ps, hipStream_t stream) {
+    if (ny < 1 || ny > QLN_TRACK_NY_MAX || !H || !Vd || !Ztraj || !Lgain || !Pest || !Xhat || !innov) return hipErrorInvalidValue;
+    if (!Xs && !Ps) return hipErrorInvalidValue;
+    SmootherNoise nz;
+    for (int r = 0; r < QLN_TRACK_NY_MAX; ++r) nz.iv[r] = r < ny ? 1.0 / Vd[r] : 1.0;
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, nz, Ztraj, Lgain, Pest, H, ny, Xhat, innov, Xs,
+                           Ps, model, event);
+    };
+    event ? go(k_landing_smoother<true>) : go(k_landing_smoother<false>);
     return hipGetLastError();
 }
 

@@ -1192,6 +1192,90 @@ class HybridNLP:
         we = (K is not None) if with_event_var is None else with_event_var
         return self._kalman_host(True, Zout, events, K, H, V, Sigma0, W, model, with_gains, with_pest, ws, wm, we)
 
+    # -- the fixed-interval smoother: the estimator's backward pass ------------------------------------
+    def _smoother(self, guarded, Ztraj, events, Lgain, Pest, H, V, Xhat, innov, model, with_states, with_cov):
+        T = _torch()
+        Hh, Vh = measurement_model(H, V)
+        ny = Hh.shape[0]
+        for name, t in (("Lgain", Lgain), ("Pest", Pest), ("Xhat", Xhat), ("innov", innov)):
+            if t is None:
+                raise ValueError(f"{name} is required: tracking_kalman's gains and covariances, the estimated roll-out's record")
+        zp = self._check(Ztraj, self.dims.z_total, "Ztraj")
+        lp = self._check(Lgain, self.B * self.N * n * ny, "Lgain")
+        pp = self._check(Pest, self.B * self.N * _lib.TRACK_P_NNZ, "Pest")
+        xp = self._check(Xhat, self.B * self.N * n, "Xhat")
+        ip = self._check(innov, self.B * self.N * ny, "innov")
+        Hd = T.from_numpy(Hh).to(self._dev())
+        new = lambda want, shape: T.empty(shape, dtype=T.float64, device=self._dev()) if want else None  # noqa: E731
+        Xs = new(with_states, (self.B, self.N, n))
+        Ps = new(with_cov, tracking_p_shape(self.B, self.N))
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        if not guarded:
+            _lib.check(_lib.lib().qln_landing_smoother(self._h, zp, lp, pp, Hd.data_ptr(), ny, Vh.ctypes.data, xp, ip, ptr(Xs),
+                                                       ptr(Ps)))
+        else:
+            ep = self._events_ptr(events)
+            mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
+            _lib.check(_lib.lib().qln_landing_smoother_guarded(self._h, zp, mp, ep, lp, pp, Hd.data_ptr(), ny, Vh.ctypes.data, xp,
+                                                               ip, ptr(Xs), ptr(Ps)))
+        return Xs, Ps
+
+    def _smoother_host(self, guarded, Ztraj, events, Lgain, Pest, H, V, Xhat, innov, model, with_states, with_cov):
+        Hh, Vh = measurement_model(H, V)
+        ny = Hh.shape[0]
+
+        def flat(a, size, name):
+            if a is None:
+                raise ValueError(f"{name} is required: tracking_kalman_host's gains and covariances, the estimated roll-out's record")
+            a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
+            if a.size != size:
+                raise ValueError(f"{name} has {a.size} entries, expected {size}")
+            return a
+
+        Ztraj = self._host_Z(Ztraj, "Ztraj")
+        Lg = flat(Lgain, self.B * self.N * n * ny, "Lgain")
+        Pe = flat(Pest, self.B * self.N * _lib.TRACK_P_NNZ, "Pest")
+        Xh = flat(Xhat, self.B * self.N * n, "Xhat")
+        iv = flat(innov, self.B * self.N * ny, "innov")
+        Xs = np.zeros((self.B, self.N, n)) if with_states else None
+        Ps = np.zeros(tracking_p_shape(self.B, self.N)) if with_cov else None
+        if not guarded:
+            _lib.check(_lib.lib().qln_landing_smoother_host(self._h, Ztraj.ctypes.data, Lg.ctypes.data, Pe.ctypes.data,
+                                                            Hh.ctypes.data, ny, Vh.ctypes.data, Xh.ctypes.data, iv.ctypes.data,
+                                                            _host_ptr(Xs), _host_ptr(Ps)))
+        else:
+            ev, model = self._host_events(events), self._host_model(model)
+            _lib.check(_lib.lib().qln_landing_smoother_guarded_host(self._h, Ztraj.ctypes.data, _host_ptr(model), ev.ctypes.data,
+                                                                    Lg.ctypes.data, Pe.ctypes.data, Hh.ctypes.data, ny,
+                                                                    Vh.ctypes.data, Xh.ctypes.data, iv.ctypes.data, _host_ptr(Xs),
+                                                                    _host_ptr(Ps)))
+        return Xs, Ps
+
+    def landing_smoother(self, Ztraj, Lgain, Pest, H, V, Xhat, innov, with_states=True, with_cov=True):
+        """Fixed-interval smoothing of a flown landing: the state at every knot given all N measurements (the filter's Xhat_k
+        uses those up to knot k).  The Bryson-Frazier sweep, backward over the record (Xhat, innov) of
+        tracking_rollout_estimated, on the gains Lgain (B, N, 15, ny) and covariances Pest (B, N, 120) tracking_kalman
+        returned for the same (Ztraj, H, V); it inverts nothing, so singular priors (a noiseless clock slot) are fine, and it
+        does not check that Lgain and Pest belong together (qln_evaluator.h).  Device tensors in; returns (Xs (B, N, 15), Ps
+        (B, N, 120) packed), device tensors, each None unless asked for; which is asked for does not change the other's
+        bits.  At knot N-1, Xs = Xhat and Ps = Pest.  Stream-ordered."""
+        return self._smoother(False, Ztraj, None, Lgain, Pest, H, V, Xhat, innov, None, with_states, with_cov)
+
+    def landing_smoother_host(self, Ztraj, Lgain, Pest, H, V, Xhat, innov, with_states=True, with_cov=True):
+        """The same with host arrays (synchronous): numpy (Xs, Ps)."""
+        return self._smoother_host(False, Ztraj, None, Lgain, Pest, H, V, Xhat, innov, None, with_states, with_cov)
+
+    def landing_smoother_guarded(self, Ztraj, events, Lgain, Pest, H, V, Xhat, innov, model=None, with_states=True,
+                                 with_cov=True):
+        """landing_smoother through the guarded touchdown, on the blocks of tracking_kalman_guarded at (Ztraj, events, model),
+        at fixed touchdown knot: the touchdown knot's composite operator is applied transposed."""
+        return self._smoother(True, Ztraj, events, Lgain, Pest, H, V, Xhat, innov, model, with_states, with_cov)
+
+    def landing_smoother_guarded_host(self, Ztraj, events, Lgain, Pest, H, V, Xhat, innov, model=None, with_states=True,
+                                      with_cov=True):
+        """The same with host arrays (synchronous): numpy (Xs, Ps)."""
+        return self._smoother_host(True, Ztraj, events, Lgain, Pest, H, V, Xhat, innov, model, with_states, with_cov)
+
     # -- the estimate-feedback roll-out: the plant and the estimator flown together -------------------
     @staticmethod
     def _measurement_rows(H):
