@@ -1159,6 +1159,56 @@ int qln_landing_smoother_guarded(qln_handle* h, const double* Ztraj, const doubl
 int qln_landing_smoother_guarded_host(qln_handle* h, const double* Ztraj, const double* model, const double* event,
                                       const double* Lgain, const double* Pest, const double* H, int32_t ny, const double* Vdiag,
                                       const double* Xhat, const double* innov, double* Xs, double* Ps);
+/* The FILTER on recorded data, and the score of that data under it: the estimator of qln_tracking_rollout_estimated* as a call
+ * of its own, for a landing that was flown elsewhere -- sensor readings and the forces that were applied -- where that call
+ * produces Xhat and innov only together with a plant it integrates itself.  Its outputs feed qln_landing_smoother*, and loglik
+ * says how consistent the filter (its gains, its V) is with the data.
+ * Knots are 0-based.  For k = 0 .. N-1, with xhat^-_0 = xhat0[b] (NULL: x_ref,0):
+ *     innov_k = Y[b][k] - H (xhat^-_k - x_ref,k)          yh exactly as the roll-out forms it
+ *     xhat_k  = xhat^-_k + L_k innov_k                    column by column onto each entry, as there
+ *     e_k     = innov_k - H (L_k innov_k)                 (the post-fit residual; L_k innov_k formed apart from xhat)
+ *     nis_k   = sum_r innov_k[r] e_k[r] / V[r]            (the normalised innovation squared, innov' S^-1 innov)
+ *     G_k     = lower triangle of diag(1/V) (I - H L_k)   (= S_k^-1 for the optimal gains)
+ *     ldS_k   = - sum_i log d_i,  d the pivots of the L D L' of G_k without pivoting      (= log det S_k)
+ *     if k < N-1:  u_k = the five control slots of Zrec at knot k;  xhat^-_{k+1} = Phi_k(xhat_k, u_k; the handle's model)
+ *     loglik[b] = -1/2 sum_k (nis_k + ldS_k + ny log 2 pi)
+ * Phi_k is the estimator's step of the estimate-feedback roll-out: knot-scheduled, by the handle's k_trans and init_mode; guarded,
+ * the guarded step with the estimator's own mode, guard and touchdown record, written to event_hat (entry 6 means what it means
+ * in the flight: the least vertical force asked of a foot the ESTIMATOR believed standing).  A replay of a flight -- Y its
+ * measurements, Zrec its Zout -- returns that flight's Xhat, innov and event_hat; bit for bit where Y holds the flight's bits.
+ * The score comes from the gains alone, through S^-1 = V^-1 (I - H L), which holds for the optimal gains of qln_tracking_kalman*
+ * at the same (H, V): no P^-, no Sigma0 and no W is read, and nothing is inverted but the eight pivots.  The call CANNOT check
+ * that Lgain belongs to V: with other gains score and loglik are the recursion's values, not a likelihood, and a pivot d_i that
+ * is not > 0 gives NaN in ldS_k and loglik.
+ * Inputs: Zref [B] x z_stride, of which ONLY THE STATE SLOTS are read (x_ref,k); Zrec [B] x z_stride, of which ONLY THE CONTROL
+ *   SLOTS are read: the four applied forces and h_k, laid out as in Z -- the forces after any clamp, so one call replays limited
+ *   and unlimited flights alike; its state slots are not read, so a user with real data fills nothing else.  Lgain
+ *   [B][N][15][ny] and H [ny][15] as for qln_tracking_rollout_estimated.  Y [B][N][ny]: the measurement in the form the roll-out
+ *   forms it, the reading minus H x_ref,k.  xhat0 [B][15] or NULL.  Vdiag: a HOST array, ny entries, required only when score or
+ *   loglik is asked for, then finite and > 0.  The kernel works on eight rows always, the rows behind ny being zero rows of H,
+ *   zero columns of L and V = 1, which add exact zeros (log 1), so a call gives the bits of the same call with those written out
+ *   -- in Xhat, innov's ny columns, score and event_hat; loglik counts its measurements, so the written-out call's is lower by
+ *   (8 - ny) N log(2 pi) / 2, the density of the added readings.
+ * Outputs (each optional, at least one non-NULL; overwritten; which are asked for does not change the others' bits; none may
+ * overlap an input or another output):
+ *   Xhat [B][N][15]; innov [B][N][ny]; score [B][N][2] = {nis_k, ldS_k}; loglik [B]; event_hat [B][QLN_TOUCHDOWN_INFO_STRIDE]
+ *   (guarded only).
+ * Refused with QLN_ERR_INVALID_ARGUMENT, the checks that need no handle before the null handle, in the family's order: ny outside
+ * 1..QLN_TRACK_NY_MAX, no output, a NULL Vdiag with score or loglik, a V entry not finite or not > 0 (then), a NULL H, Lgain or
+ * Y; behind the handle a NULL Zref, a NULL Zrec, overlaps.  The device forms do not validate device data; the host forms also
+ * refuse a non-finite H.  Device pointers, stream-ordered; needs no cost table. */
+int qln_landing_filter(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H, int32_t ny,
+                       const double* Vdiag /* host, ny entries, or NULL without score and loglik */, const double* Y,
+                       const double* xhat0 /* or NULL */, double* Xhat, double* innov, double* score, double* loglik);
+int qln_landing_filter_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H, int32_t ny,
+                            const double* Vdiag, const double* Y, const double* xhat0, double* Xhat, double* innov, double* score,
+                            double* loglik);
+int qln_landing_filter_guarded(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                               int32_t ny, const double* Vdiag, const double* Y, const double* xhat0, double* Xhat, double* innov,
+                               double* score, double* loglik, double* event_hat /* [B][QLN_TOUCHDOWN_INFO_STRIDE] or NULL */);
+int qln_landing_filter_guarded_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                    int32_t ny, const double* Vdiag, const double* Y, const double* xhat0, double* Xhat,
+                                    double* innov, double* score, double* loglik, double* event_hat);
 /* Z <- Z + N(0, sigma^2) on every entry, step lengths h then clipped to [h_min, h_max] (redraw_h = 0) or redrawn
  * U(h_min, h_max) (redraw_h != 0) -- the evaluation point of SURVEY.md 8d from qln_initial_guess's Z0.  The normal
  * draws are Box-Muller on the sampler's stream from `stream_offset`: the recipe's distribution, not numpy's numbers. */

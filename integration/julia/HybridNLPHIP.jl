@@ -476,6 +476,51 @@ function tracking_rollout_estimated_guarded(prob::HybridNLPHIP, Zref::Vector{Flo
                     model === nothing ? C_NULL : model, Zout, Xhat, innov, events, events_hat))
     return Zout, Xhat, innov, events, events_hat
 end
+# The filter on recorded data (include/qln_evaluator.h, DESIGN.md 4.26): the estimator of tracking_rollout_estimated run on a
+# record.  Zref: the reference (only its state slots are read); Zrec: the recorded trajectory, of which only the control slots
+# are read, the four applied forces and h_k of every knot; L: (ny, 15, N) as tracking_kalman returns it; H: (ny, 15); Y: (ny, N),
+# the readings less H x_ref,k (what the roll-out forms as y_k); V: the ny measurement variances the gains were designed for, or
+# nothing for no score; xhat0: 15 values or nothing (the reference's first knot).  Returns (Xhat, innov, score, loglik): the
+# estimates as (15, N), the innovations as (ny, N), score (2, N) = (nis_k, log det S_k) and the Gaussian log-likelihood, the last
+# two nothing without V.  The call cannot check that L belongs to V.  landing_filter_guarded lets the estimator land by its own
+# guard and also returns events_hat, its touchdown record.
+function landing_filter(prob::HybridNLPHIP, Zref::Vector{Float64}, Zrec::Vector{Float64}, L::Array{Float64,3}, H::Matrix{Float64},
+                        Y::Matrix{Float64}; V=nothing, xhat0=nothing)
+    N = prob.N
+    ny = size(H, 1)
+    (1 <= ny <= 8 && size(H, 2) == 15 && size(L) == (ny, 15, N) && size(Y) == (ny, N) && (V === nothing || length(V) == ny)) ||
+        error("H: (ny, 15) with 1 <= ny <= 8, L: (ny, 15, N), Y: (ny, N), V: ny")
+    Hrow = Matrix{Float64}(transpose(H))  # row-major [ny][15]
+    Xhat = zeros(15, N)
+    innov = zeros(ny, N)
+    score = V === nothing ? nothing : zeros(2, N)
+    loglik = V === nothing ? nothing : zeros(1)
+    qln_check(ccall((:qln_landing_filter_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, Zrec, L, Hrow, Int32(ny), V === nothing ? C_NULL : V, Y, xhat0 === nothing ? C_NULL : xhat0,
+                    Xhat, innov, score === nothing ? C_NULL : score, loglik === nothing ? C_NULL : loglik))
+    return Xhat, innov, score, loglik === nothing ? nothing : loglik[1]
+end
+function landing_filter_guarded(prob::HybridNLPHIP, Zref::Vector{Float64}, Zrec::Vector{Float64}, L::Array{Float64,3},
+                                H::Matrix{Float64}, Y::Matrix{Float64}; V=nothing, xhat0=nothing)
+    N = prob.N
+    ny = size(H, 1)
+    (1 <= ny <= 8 && size(H, 2) == 15 && size(L) == (ny, 15, N) && size(Y) == (ny, N) && (V === nothing || length(V) == ny)) ||
+        error("H: (ny, 15) with 1 <= ny <= 8, L: (ny, 15, N), Y: (ny, N), V: ny")
+    Hrow = Matrix{Float64}(transpose(H))
+    Xhat = zeros(15, N)
+    innov = zeros(ny, N)
+    score = V === nothing ? nothing : zeros(2, N)
+    loglik = V === nothing ? nothing : zeros(1)
+    events_hat = zeros(8)
+    qln_check(ccall((:qln_landing_filter_guarded_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, Zrec, L, Hrow, Int32(ny), V === nothing ? C_NULL : V, Y, xhat0 === nothing ? C_NULL : xhat0,
+                    Xhat, innov, score === nothing ? C_NULL : score, loglik === nothing ? C_NULL : loglik, events_hat))
+    return Xhat, innov, score, loglik === nothing ? nothing : loglik[1], events_hat
+end
 # The sweeps through the estimate-feedback roll-out (include/qln_evaluator.h, DESIGN.md 4.23): the derivative of
 # tracking_rollout_estimated / _guarded at the (Zout, Xhat, innov[, events, events_hat]) it returned, with respect to Zref, K, L,
 # x0, xhat0 and model, at FIXED noise samples and fixed H.  Forward: tangents as keywords, nothing for zero -- except xhat0_dot,

@@ -122,6 +122,10 @@ enum HostRole {
     kEventHatD,  // out: the estimated guarded jvp's event_hat_dot          [B][8]
     kXs,     // out: the smoother's states                                  [B][N][15]
     kPs,     // out: the smoother's covariances                             layout of P
+    kZrec,   // in: the filter's recorded trajectory (control slots read)    layout of Z
+    kY,      // in: the filter's measurements ([B][N][ny] used)             [B][N][8]
+    kScore,  // out: the filter's {nis_k, log det S_k}                      [B][N][2]
+    kLoglik, // out: the filter's log-likelihood                            [B]
     kHostRoles
 };
 
@@ -185,10 +189,10 @@ int upload(T** dst, const T* src, size_t n) {
 int64_t host_role_size(const qln_handle* h, HostRole r) {
     const qln_dims& D = h->dims;
     switch (r) {
-        case kZ: case kV: case kZbar: case kZio: case kZdot: case kZout: case kGrad: return D.z_total;
+        case kZ: case kV: case kZbar: case kZio: case kZdot: case kZout: case kGrad: case kZrec: return D.z_total;
         case kC: case kMu: return D.c_total;
         case kVals: return D.j_total;
-        case kF: case kSigma: return D.B;
+        case kF: case kSigma: case kLoglik: return D.B;
         case kHvals: return (int64_t)(D.B - 1) * h->h_stride + hessian_nnz(D.N);  // no padding behind the last problem
         case kK: case kKbar: case kKdot: return tracking_k_total(D);
         case kP: case kCov: case kPest: case kPs: return tracking_p_total(D);
@@ -202,7 +206,8 @@ int64_t host_role_size(const qln_handle* h, HostRole r) {
         case kSat: return tracking_sat_total(D);
         case kH: return (int64_t)QLN_TRACK_NY_MAX * QLN_NX;
         case kLgain: case kLgainD: return tracking_gain_total(D, QLN_TRACK_NY_MAX);
-        case kVnoise: case kInnov: case kInnovD: return tracking_meas_total(D, QLN_TRACK_NY_MAX);
+        case kVnoise: case kInnov: case kInnovD: case kY: return tracking_meas_total(D, QLN_TRACK_NY_MAX);
+        case kScore: return (int64_t)D.B * D.N * 2;
         case kWnoise: return (int64_t)D.B * (D.N - 1) * QLN_NX;
         case kXhat: case kXhatD: case kXs: return (int64_t)D.B * D.N * QLN_NX;
         case kHostRoles: break;
@@ -1866,6 +1871,87 @@ int qln_landing_smoother_guarded_host(qln_handle* h, const double* Ztraj, const 
     a.Ztraj = Ztraj; a.model = model; a.guarded = true; a.event = event; a.Lgain = Lgain; a.Pest = Pest; a.H = H; a.ny = ny;
     a.Vdiag = Vdiag; a.Xhat = Xhat; a.innov = innov; a.Xs = Xs; a.Ps = Ps;
     return landing_smoother(h, kHostMem, a, "qln_landing_smoother_guarded_host");
+}
+
+// The filter on recorded data (k_landing_filter).  The checks that need no handle come first.
+// guarded: the estimator lands by its own guard, with its event record (may be null)
+struct FilterCall {
+    const double *Zref, *Zrec, *Lgain, *H;
+    int32_t ny;
+    const double *Vdiag, *Y, *xhat0;
+    double *Xhat, *innov, *score, *loglik, *event_hat;
+    bool guarded;
+};
+
+static int check_landing_filter_args(const qln_handle* h, const FilterCall& a, const char* who) {
+    const std::string w(who);
+    if (a.ny < 1 || a.ny > QLN_TRACK_NY_MAX)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
+    if (!a.Xhat && !a.innov && !a.score && !a.loglik && !a.event_hat)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every output is NULL (nothing to compute)");
+    if (a.score || a.loglik) {
+        if (!a.Vdiag) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Vdiag with score or loglik");
+        for (int i = 0; i < a.ny; ++i)
+            if (!(std::isfinite(a.Vdiag[i]) && a.Vdiag[i] > 0.0))
+                return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Vdiag must be finite and > 0 (entry " + std::to_string(i) + ")");
+    }
+    if (!a.H || !a.Lgain || !a.Y) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null H, Lgain or Y");
+    if (int rc = check_handle(h)) return rc;
+    if (!a.Zref) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref");
+    if (!a.Zrec) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zrec");
+    return QLN_OK;
+}
+
+static int landing_filter(qln_handle* h, MemForm mem, const FilterCall& a, const char* who) {
+    if (int rc = check_landing_filter_args(h, a, who)) return rc;
+    // the rows, gains, measurements and innovations of the call's ny, of the roles' eight
+    const int64_t ng = tracking_gain_total(h->dims, a.ny), nm = tracking_meas_total(h->dims, a.ny);
+    const HostArgs args = {copy_in(kZ, a.Zref), copy_in(kZrec, a.Zrec), copy_in(kLgain, a.Lgain).sized(ng),
+                           copy_in(kH, a.H).sized((int64_t)a.ny * QLN_NX), copy_in(kY, a.Y).sized(nm), copy_in(kXhat0, a.xhat0),
+                           copy_out(kXhat, a.Xhat), copy_out(kInnov, a.innov).sized(nm), copy_out(kScore, a.score),
+                           copy_out(kLoglik, a.loglik), copy_out(kEventHat, a.event_hat)};
+    if (int rc = check_no_overlap(h, args, who)) return rc;
+    if (mem == kHostMem) {
+        if (int rc = check_host_meas(a.H, a.ny, who)) return rc;
+    }
+    return run_call(h, mem, args, [&](double* const* d, bool) {
+        return qln::launch_landing_filter(h->p, d[kZ], d[kZrec], d[kLgain], d[kH], a.ny, a.Vdiag, d[kY], d[kXhat0], d[kXhat],
+                                          d[kInnov], d[kScore], d[kLoglik], a.guarded, d[kEventHat], h->stream);
+    });
+}
+
+static FilterCall filter_call(const double* Zref, const double* Zrec, const double* Lgain, const double* H, int32_t ny,
+                              const double* Vdiag, const double* Y, const double* xhat0, double* Xhat, double* innov, double* score,
+                              double* loglik, bool guarded, double* event_hat) {
+    FilterCall a{};
+    a.Zref = Zref; a.Zrec = Zrec; a.Lgain = Lgain; a.H = H; a.ny = ny; a.Vdiag = Vdiag; a.Y = Y; a.xhat0 = xhat0;
+    a.Xhat = Xhat; a.innov = innov; a.score = score; a.loglik = loglik; a.guarded = guarded; a.event_hat = event_hat;
+    return a;
+}
+
+int qln_landing_filter(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H, int32_t ny,
+                       const double* Vdiag, const double* Y, const double* xhat0, double* Xhat, double* innov, double* score,
+                       double* loglik) {
+    return landing_filter(h, kDeviceMem, filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, false, nullptr),
+                          "qln_landing_filter");
+}
+int qln_landing_filter_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H, int32_t ny,
+                            const double* Vdiag, const double* Y, const double* xhat0, double* Xhat, double* innov, double* score,
+                            double* loglik) {
+    return landing_filter(h, kHostMem, filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, false, nullptr),
+                          "qln_landing_filter_host");
+}
+int qln_landing_filter_guarded(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                               int32_t ny, const double* Vdiag, const double* Y, const double* xhat0, double* Xhat, double* innov,
+                               double* score, double* loglik, double* event_hat) {
+    return landing_filter(h, kDeviceMem, filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, true, event_hat),
+                          "qln_landing_filter_guarded");
+}
+int qln_landing_filter_guarded_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                    int32_t ny, const double* Vdiag, const double* Y, const double* xhat0, double* Xhat,
+                                    double* innov, double* score, double* loglik, double* event_hat) {
+    return landing_filter(h, kHostMem, filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, true, event_hat),
+                          "qln_landing_filter_guarded_host");
 }
 
 // The estimate-feedback roll-out (k_tracking_rollout_estimated).  The checks that need no handle come first.

@@ -339,6 +339,13 @@ hipError_t launch_tracking_kalman(const BatchParams& p, const double* Zout, cons
 hipError_t launch_landing_smoother(const BatchParams& p, const double* Ztraj, const double* model, const double* event,
                                    const double* Lgain, const double* Pest, const double* H, int ny, const double* Vd,
                                    const double* Xhat, const double* innov, double* Xs, double* Ps, hipStream_t stream);
+// The filter on recorded data (qln_landing_filter / _guarded): Zref (state slots read), Zrec (control slots read), Lgain
+// [B][N][15][ny], H [ny][15] and Y [B][N][ny] on the device, Vd (ny) a host array read only when score or loglik is asked for;
+// xhat0 [B][15] may be null; Xhat [B][N][15], innov [B][N][ny], score [B][N][2], loglik [B] and event_hat
+// [B][QLN_TOUCHDOWN_INFO_STRIDE] (guarded only) may each be null, not all.
+hipError_t launch_landing_filter(const BatchParams& p, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                 int ny, const double* Vd, const double* Y, const double* xhat0, double* Xhat, double* innov,
+                                 double* score, double* loglik, bool guarded, double* event_hat, hipStream_t stream);
 // The roll-out of the plant and the estimator side by side (qln_tracking_rollout_estimated / _guarded): Lgain [B][N][15][ny] and
 // H [ny][15] on the device; vnoise [B][N][ny], wnoise [B][N-1][15], x0, xhat0 [B][15], model and K may be null; Xhat [B][N][15],
 // innov [B][N][ny] may be null; event and event_hat [B][QLN_TOUCHDOWN_INFO_STRIDE] or null, with guarded only.

@@ -95,6 +95,10 @@
 // k_landing_smoother: the fixed-interval smoother of a flown landing (qln_landing_smoother / _guarded), the
 // estimator's backward pass: the modified Bryson-Frazier sweep on the filter's gains and covariances, in k_tracking_kalman's
 // mapping and tiles, with the blocks and the touchdown operator applied transposed as the Riccati sweep applies them.
+//
+// k_landing_filter: the estimator on recorded data (qln_landing_filter / _guarded): the estimator's half of
+// k_tracking_rollout_estimated, measurements and applied forces read where that kernel forms them, and with kScore the
+// normalised innovation squared, log det S_k and the log-likelihood from the gains alone.
 #include "qln_row16.h"
 
 #include <utility>
@@ -2943,6 +2947,200 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_estimated_vjp(BatchP
     }
 }
 
+// ---- k_landing_filter ----
+// entry (r, c), c <= r, of a packed lower triangle of QLN_TRACK_NY_MAX rows
+__host__ __device__ constexpr int filter_tri(int r, int c) { return r * (r + 1) / 2 + c; }
+constexpr int kFilterTri = filter_tri(QLN_TRACK_NY_MAX - 1, QLN_TRACK_NY_MAX - 1) + 1;  // 36
+
+// The filter on recorded data (qln_landing_filter / _guarded, include/qln_evaluator.h): the estimator's half of
+// k_tracking_rollout_estimated in that kernel's mapping, one lane per problem, with the measurement read from Y and the applied
+// forces from Zrec where that kernel forms both from a plant it integrates.  H goes to LDS once per block, all eight rows, the
+// rows behind ny as zeros.  yh, the update xhat += L_k innov and the estimator's step are that kernel's expressions in that
+// kernel's order, and L_k is read row by row for its reason, so a replay of a flight returns the flight's bits.
+// kGuard: the step is guarded_step on the estimator's own contact mode and Touchdown record, written to event_hat.
+// kScore: nis_k, log det S_k and the log-likelihood from the gains alone, S_k^-1 = V^-1 (I - H L_k).  Under the same pass
+// over L_k's rows the lane accumulates g = L_k innov_k (apart from xhat, whose size would swamp it) and the lower triangle of
+// H L_k; then e_k = innov_k - H g, nis_k = sum_r innov_k[r] e_k[r] / V[r], and the L D L' of the lower triangle of
+// diag(1/V) (I - H L_k) without pivoting, right-looking and in place, whose pivots give log det S_k = - sum log d_i (NaN where
+// a pivot is not > 0).  The rows behind ny have a zero row of H and V = 1: pivot 1, log 1 = 0, and zeros everywhere else.
+template <bool kGuard, bool kScore>
+__global__ __launch_bounds__(kWave) void k_landing_filter(BatchParams P, SmootherNoise Nz, const double* __restrict__ Hg, int ny,
+                                                          const double* __restrict__ Zref, const double* __restrict__ Zrec,
+                                                          const double* __restrict__ Lg, const double* __restrict__ Yg,
+                                                          const double* __restrict__ xhat0, double* __restrict__ Xhat,
+                                                          double* __restrict__ innov_out, double* __restrict__ score,
+                                                          double* __restrict__ loglik, double* __restrict__ event_hat) {
+    constexpr int NY = QLN_TRACK_NY_MAX;
+    __shared__ double Hs[NY * 15];
+    for (int i = threadIdx.x; i < NY * 15; i += kWave) Hs[i] = i < 15 * ny ? Hg[i] : 0.0;
+    // 1 / V beside it: held in scalar registers over the knots, the eight took more of them than there are
+    [[maybe_unused]] __shared__ double Vs[NY];
+    if constexpr (kScore) {
+#pragma unroll
+        for (int r = 0; r < NY; ++r)
+            if ((int)threadIdx.x == r) Vs[r] = Nz.iv[r];
+    }
+    __syncthreads();
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= P.B) return;
+    const ProblemDesc pd = P.desc[b];
+    const int N = P.N, kt = pd.k_trans, im = pd.init_mode;
+    const Model Mh = plant_model<true>(P, nullptr, b);  // the estimator's: always the handle's
+    const double* __restrict__ Zr = Zref + (int64_t)b * P.z_stride;
+    const double* __restrict__ Zc = Zrec + (int64_t)b * P.z_stride;
+    const double* __restrict__ hs = xhat0 ? xhat0 + (int64_t)b * 15 : Zr;
+    const double* __restrict__ Lb = Lg + (int64_t)b * N * (15 * ny);
+    const double* __restrict__ yb = Yg + (int64_t)b * N * ny;
+    double xhat[15], u[5], xn[15];
+#pragma unroll
+    for (int i = 0; i < 15; ++i) xhat[i] = hs[i];
+    [[maybe_unused]] int mode_hat = im;
+    [[maybe_unused]] Touchdown tdh = {-1.0, 0.0, 0.0, 0.0, 0.0, 0.0, __builtin_inf()};
+    [[maybe_unused]] double ll = 0.0;
+    for (int k = 0; k < N; ++k) {
+        // innov_k = Y_k - H (xhat^-_k - x_ref,k); the rows behind ny are zeros
+        double innov[NY];
+        {
+            double e[15];
+#pragma unroll
+            for (int i = 0; i < 15; ++i) e[i] = xhat[i] - Zr[20 * k + i];
+#pragma unroll
+            for (int r = 0; r < NY; ++r) {
+                innov[r] = 0.0;
+                if (r < ny) {
+                    double yh = Hs[15 * r] * e[0];
+#pragma unroll
+                    for (int i = 1; i < 15; ++i) yh = fma(Hs[15 * r + i], e[i], yh);
+                    innov[r] = yb[(int64_t)ny * k + r] - yh;
+                    if (innov_out) innov_out[((int64_t)b * N + k) * ny + r] = innov[r];
+                }
+            }
+        }
+        // xhat_k = xhat^-_k + L_k innov_k as k_tracking_rollout_estimated forms it: row i of L_k is ny consecutive doubles, a
+        // column behind ny reads the row's last entry against a zero innovation (or a zero row of H), three rows in flight
+        [[maybe_unused]] double g[15], hl[kFilterTri];
+        if constexpr (kScore) {
+#pragma unroll
+            for (int t = 0; t < kFilterTri; ++t) hl[t] = 0.0;
+        }
+        {
+            const double* Li = Lb + (int64_t)k * (15 * ny);
+#pragma unroll
+            for (int i = 0; i < 15; ++i) {
+                if constexpr (kScore) {
+                    double lr[NY];
+#pragma unroll
+                    for (int r = 0; r < NY; ++r) lr[r] = Li[min(r, ny - 1)];
+#pragma unroll
+                    for (int r = 0; r < NY; ++r) xhat[i] = fma(lr[r], innov[r], xhat[i]);
+                    double gi = lr[0] * innov[0];
+#pragma unroll
+                    for (int r = 1; r < NY; ++r) gi = fma(lr[r], innov[r], gi);
+                    g[i] = gi;
+                    // column i of H at an offset hidden from the optimiser: H does not change over the knots, and 120 reads at
+                    // known addresses may be hoisted out of the knot loop into registers this kernel does not have
+                    int hi = i;
+                    asm volatile("" : "+v"(hi));
+#pragma unroll
+                    for (int r = 0; r < NY; ++r) {
+                        const double hr = Hs[15 * r + hi];
+#pragma unroll
+                        for (int c = 0; c <= r; ++c) hl[filter_tri(r, c)] = fma(hr, lr[c], hl[filter_tri(r, c)]);
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < NY; ++r) xhat[i] = fma(Li[min(r, ny - 1)], innov[r], xhat[i]);
+                }
+                Li += ny;
+                asm volatile("" : "+v"(Li));
+                if constexpr (kScore) {
+                    // the sums are formed where the rows are read: left to the optimiser they sank below the branches that
+                    // follow, to their first use, and L_k's 120 entries stayed live until there, which spilled
+                    asm volatile("" : "+v"(g[i]));
+                    if (i % 3 == 2) {
+#pragma unroll
+                        for (int t = 0; t < kFilterTri; ++t) asm volatile("" : "+v"(hl[t]));
+                    }
+                }
+                if (i % 3 == 2) __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        if (Xhat) {
+            double* __restrict__ Xk = Xhat + ((int64_t)b * N + k) * 15;
+#pragma unroll
+            for (int i = 0; i < 15; ++i) Xk[i] = xhat[i];
+        }
+        if constexpr (kScore) {
+            double nis = 0.0;
+#pragma unroll
+            for (int r = 0; r < NY; ++r) {
+                int hr = 15 * r;  // hidden for the same reason
+                asm volatile("" : "+v"(hr));
+                double hg = Hs[hr] * g[0];
+#pragma unroll
+                for (int i = 1; i < 15; ++i) hg = fma(Hs[hr + i], g[i], hg);
+                nis = nis + innov[r] * (innov[r] - hg) * Vs[hr - 14 * r];
+            }
+            // formed here, for the same reason: the eight logarithms below branch
+            asm volatile("" : "+v"(nis));
+            // G = the lower triangle of diag(1/V) (I - H L_k), then its L D L' in place: column j's pivot, the column scaled, and
+            // the trailing triangle less the column's outer product
+#pragma unroll
+            for (int r = 0; r < NY; ++r) {
+                int vr = r;  // hidden as H's offsets are
+                asm volatile("" : "+v"(vr));
+                const double ivr = Vs[vr];
+#pragma unroll
+                for (int c = 0; c <= r; ++c) hl[filter_tri(r, c)] = ivr * ((r == c ? 1.0 : 0.0) - hl[filter_tri(r, c)]);
+            }
+            double lds = 0.0;
+#pragma unroll
+            for (int j = 0; j < NY; ++j) {
+                const double dj = hl[filter_tri(j, j)];
+                lds = lds + (dj > 0.0 ? log(dj) : __builtin_nan(""));
+                const double inv = 1.0 / dj;
+#pragma unroll
+                for (int i = j + 1; i < NY; ++i) {
+                    const double lij = hl[filter_tri(i, j)] * inv;
+#pragma unroll
+                    for (int c = j + 1; c <= i; ++c) hl[filter_tri(i, c)] = hl[filter_tri(i, c)] - lij * hl[filter_tri(c, j)];
+                }
+            }
+            lds = -lds;
+            if (score) {
+                double* __restrict__ sk = score + ((int64_t)b * N + k) * 2;
+                sk[0] = nis;
+                sk[1] = lds;
+            }
+            ll = ll + ((nis + lds) + (double)ny * 1.8378770664093454836);  // log 2 pi
+        }
+        if (k == N - 1) break;
+        // the applied forces and the step length are the record's
+#pragma unroll
+        for (int i = 0; i < 5; ++i) u[i] = Zc[20 * k + 15 + i];
+        if constexpr (kGuard) guarded_step(Mh, k, mode_hat, xhat, u, xn, tdh);
+        else step_forward(Mh, k, kt, im, xhat, u, xn);
+#pragma unroll
+        for (int i = 0; i < 15; ++i) xhat[i] = xn[i];
+    }
+    if constexpr (kScore) {
+        if (loglik) loglik[b] = -0.5 * ll;
+    }
+    if constexpr (kGuard) {
+        if (event_hat) {
+            double* __restrict__ ev = event_hat + (int64_t)QLN_TOUCHDOWN_INFO_STRIDE * b;
+            ev[0] = tdh.knot;
+            ev[1] = tdh.tau;
+            ev[2] = tdh.clock;
+            ev[3] = tdh.px;
+            ev[4] = tdh.vx;
+            ev[5] = tdh.vy;
+            ev[6] = tdh.fmin;
+            ev[7] = 0.0;
+        }
+    }
+}
+
 }  // namespace
 
 // event (the guarded roll-out's records) sends the Riccati and the covariance sweep to their kGuard instantiations, which exist
@@ -3104,6 +3302,29 @@ hipError_t launch_landing_smoother(const BatchParams& p, const double* Ztraj, co
                            Ps, model, event);
     };
     event ? go(k_landing_smoother<true>) : go(k_landing_smoother<false>);
+    return hipGetLastError();
+}
+
+// The four instantiations of k_landing_filter: the knot schedule or the guard, and the score (score or loglik asked for, which
+// needs Vd) or not.
+hipError_t launch_landing_filter(const BatchParams& p, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                 int ny, const double* Vd, const double* Y, const double* xhat0, double* Xhat, double* innov,
+                                 double* score, double* loglik, bool guarded, double* event_hat, hipStream_t stream) {
+    if (ny < 1 || ny > QLN_TRACK_NY_MAX || !H || !Lgain || !Y || !Zref || !Zrec) return hipErrorInvalidValue;
+    if (!guarded && event_hat) return hipErrorInvalidValue;
+    if (!Xhat && !innov && !score && !loglik && !event_hat) return hipErrorInvalidValue;
+    const bool scored = score || loglik;
+    if (scored && !Vd) return hipErrorInvalidValue;
+    SmootherNoise nz;
+    for (int r = 0; r < QLN_TRACK_NY_MAX; ++r) nz.iv[r] = (scored && r < ny) ? 1.0 / Vd[r] : 1.0;
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((p.B + kWave - 1) / kWave), dim3(kWave), 0, stream, p, nz, H, ny, Zref, Zrec, Lgain, Y, xhat0,
+                           Xhat, innov, score, loglik, event_hat);
+    };
+    if (scored)
+        guarded ? go(k_landing_filter<true, true>) : go(k_landing_filter<false, true>);
+    else
+        guarded ? go(k_landing_filter<true, false>) : go(k_landing_filter<false, false>);
     return hipGetLastError();
 }
 

@@ -175,6 +175,35 @@ def measurement_model(H, V):
     return np.ascontiguousarray(H), V
 
 
+def landing_measurements(Zout, Zref, H, vnoise=None, B=None):
+    """Y (B, N, ny) in the form qln_landing_filter reads it and the estimate-feedback roll-out forms it: H (x_k - x_ref,k) + v_k,
+    from a flown or recorded state trajectory Zout and the reference Zref (both in the layout of Z: B problems, a stride of at
+    least n_nlp each; flat buffers need B, HybridNLP.landing_measurements passes it), H (ny, 15) and vnoise (B, N, ny) or None.
+    Tensors in, a tensor out (on Zout's device); numpy in, numpy out.  The products are torch's or numpy's, not the kernel's:
+    equal to the roll-out's y_k up to rounding, not bit for bit."""
+    torch_in = hasattr(Zout, "detach")
+    H = np.asarray(H.detach().cpu().numpy() if hasattr(H, "detach") else H, dtype=np.float64)
+    if H.ndim == 1:
+        H = H[None]
+    if H.ndim != 2 or H.shape[1] != n:
+        raise ValueError(f"H of shape {H.shape}: expected (ny, 15)")
+    if B is None:
+        if Zout.ndim != 2:
+            raise ValueError("a flat Zout needs B, the number of problems")
+        B = Zout.shape[0]
+    zo, zr = Zout.reshape(B, -1), Zref.reshape(B, -1)
+    N = (min(zo.shape[1], zr.shape[1]) + 5) // 20
+    if torch_in:
+        T = _torch()
+        Ht = T.from_numpy(np.ascontiguousarray(H)).to(zo.device)
+        idx = (20 * T.arange(N, device=zo.device)[:, None] + T.arange(n, device=zo.device)[None, :]).reshape(-1)
+        y = (zo[:, idx] - zr.to(zo.device)[:, idx]).reshape(B, N, n) @ Ht.T
+        return (y if vnoise is None else y + vnoise.reshape(B, N, -1)).contiguous()
+    idx = 20 * np.arange(N)[:, None] + np.arange(n)[None, :]
+    y = (np.asarray(zo)[:, idx] - np.asarray(zr)[:, idx]) @ H.T
+    return y if vnoise is None else y + np.asarray(vnoise).reshape(B, N, -1)
+
+
 def tracking_l_shape(B: int, N: int, ny: int):
     """Shape of the filter gains of qln_tracking_kalman: (B, N, 15, ny), row-major."""
     return (B, N, n, ny)
@@ -1275,6 +1304,105 @@ class HybridNLP:
                                       with_cov=True):
         """The same with host arrays (synchronous): numpy (Xs, Ps)."""
         return self._smoother_host(True, Ztraj, events, Lgain, Pest, H, V, Xhat, innov, model, with_states, with_cov)
+
+    # -- the filter on recorded data, and the score of the data under it -------------------------------
+    def _filter(self, guarded, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, with_events):
+        T = _torch()
+        score = (V is not None) if with_score is None else with_score
+        if score and V is None:
+            raise ValueError("V is required with with_score: the measurement variances the gains were designed for")
+        Hh, Vh = measurement_model(H, V) if score else (self._measurement_rows(H), None)
+        ny = Hh.shape[0]
+        for name, t in (("Lgain", Lgain), ("Y", Y)):
+            if t is None:
+                raise ValueError(f"{name} is required: tracking_kalman's gains, the recorded measurements (landing_measurements)")
+        zr = self._check(Zref, self.dims.z_total, "Zref")
+        zc = self._check(Zrec, self.dims.z_total, "Zrec")
+        lp = self._check(Lgain, self.B * self.N * n * ny, "Lgain")
+        yp = self._check(Y, self.B * self.N * ny, "Y")
+        hp = self._check_opt(xhat0, self.B * n, "xhat0")
+        Hd = T.from_numpy(Hh).to(self._dev())
+        new = lambda want, shape: T.zeros(shape, dtype=T.float64, device=self._dev()) if want else None  # noqa: E731
+        Xh, iv = new(with_estimate, (self.B, self.N, n)), new(with_innovations, (self.B, self.N, ny))
+        sc, ll = new(score, (self.B, self.N, 2)), new(score, (self.B,))
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        args = (self._h, zr, zc, lp, Hd.data_ptr(), ny, None if Vh is None else Vh.ctypes.data, yp, hp, ptr(Xh), ptr(iv), ptr(sc),
+                ptr(ll))
+        if not guarded:
+            _lib.check(_lib.lib().qln_landing_filter(*args))
+            return Xh, iv, sc, ll
+        eh = new(with_events, (self.B, _lib.TOUCHDOWN_INFO_STRIDE))
+        _lib.check(_lib.lib().qln_landing_filter_guarded(*args, ptr(eh)))
+        return Xh, iv, sc, ll, eh
+
+    def _filter_host(self, guarded, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, with_events):
+        score = (V is not None) if with_score is None else with_score
+        if score and V is None:
+            raise ValueError("V is required with with_score: the measurement variances the gains were designed for")
+        Hh, Vh = measurement_model(H, V) if score else (self._measurement_rows(H), None)
+        ny = Hh.shape[0]
+
+        def flat(a, size, name):
+            if a is None:
+                raise ValueError(f"{name} is required: tracking_kalman_host's gains, the recorded measurements")
+            a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
+            if a.size != size:
+                raise ValueError(f"{name} has {a.size} entries, expected {size}")
+            return a
+
+        Zref, Zrec, xhat0 = self._host_Z(Zref, "Zref"), self._host_Z(Zrec, "Zrec"), self._host_x0(xhat0)
+        Lg, Yh = flat(Lgain, self.B * self.N * n * ny, "Lgain"), flat(Y, self.B * self.N * ny, "Y")
+        Xh = np.zeros((self.B, self.N, n)) if with_estimate else None
+        iv = np.zeros((self.B, self.N, ny)) if with_innovations else None
+        sc = np.zeros((self.B, self.N, 2)) if score else None
+        ll = np.zeros(self.B) if score else None
+        args = (self._h, Zref.ctypes.data, Zrec.ctypes.data, Lg.ctypes.data, Hh.ctypes.data, ny, _host_ptr(Vh), Yh.ctypes.data,
+                _host_ptr(xhat0), _host_ptr(Xh), _host_ptr(iv), _host_ptr(sc), _host_ptr(ll))
+        if not guarded:
+            _lib.check(_lib.lib().qln_landing_filter_host(*args))
+            return Xh, iv, sc, ll
+        eh = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if with_events else None
+        _lib.check(_lib.lib().qln_landing_filter_guarded_host(*args, _host_ptr(eh)))
+        return Xh, iv, sc, ll, eh
+
+    def landing_measurements(self, Zout, Zref, H, vnoise=None):
+        """landing_measurements for this handle's layout: Zout and Zref as the handle's calls take and return them."""
+        if vnoise is not None:
+            vnoise = vnoise.reshape(self.B, self.N, -1)
+        if hasattr(Zout, "detach"):
+            zo, zr = (z.reshape(self.B, -1)[:, :self.n_nlp] for z in (Zout, Zref))
+        else:
+            zo, zr = (np.asarray(z).reshape(self.B, -1)[:, :self.n_nlp] for z in (Zout, Zref))
+        return landing_measurements(zo, zr, H, vnoise)
+
+    def landing_filter(self, Zref, Zrec, Lgain, H, Y, V=None, xhat0=None, with_estimate=True, with_innovations=True,
+                       with_score=None):
+        """The estimator of tracking_rollout_estimated run on a RECORD: measurements Y (B, N, ny) in the roll-out's form (the
+        reading minus H x_ref,k: landing_measurements) and the forces that were applied, the control slots of Zrec -- its state
+        slots are not read, and of Zref only the state slots are.  Lgain (B, N, 15, ny) are tracking_kalman's gains, xhat0
+        (B, 15) the initial estimate (None: the reference's first knot); the prediction is the handle's model on the knot
+        schedule.  With V (the variances the gains were designed for; with_score, default: V given) it also scores the record:
+        score (B, N, 2) = {nis_k, log det S_k} and loglik (B,), the Gaussian log-likelihood, from the gains alone -- which the
+        call cannot check belong to V (qln_evaluator.h).  Device tensors in; returns (Xhat, innov, score, loglik), each None
+        unless asked for; which are asked for does not change the others' bits.  A replay of a flight returns its Xhat and
+        innov.  Stream-ordered."""
+        return self._filter(False, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, False)
+
+    def landing_filter_host(self, Zref, Zrec, Lgain, H, Y, V=None, xhat0=None, with_estimate=True, with_innovations=True,
+                            with_score=None):
+        """The same with host arrays (synchronous): numpy (Xhat, innov, score, loglik).  A non-finite H is refused."""
+        return self._filter_host(False, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, False)
+
+    def landing_filter_guarded(self, Zref, Zrec, Lgain, H, Y, V=None, xhat0=None, with_estimate=True, with_innovations=True,
+                               with_score=None, with_events=True):
+        """landing_filter with the estimator landing by its own guard, as in tracking_rollout_estimated(guarded=True): returns
+        (Xhat, innov, score, loglik, events_hat), events_hat (B, 8) the estimator's touchdown records."""
+        return self._filter(True, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, with_events)
+
+    def landing_filter_guarded_host(self, Zref, Zrec, Lgain, H, Y, V=None, xhat0=None, with_estimate=True,
+                                    with_innovations=True, with_score=None, with_events=True):
+        """The same with host arrays (synchronous): numpy (Xhat, innov, score, loglik, events_hat)."""
+        return self._filter_host(True, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, with_events)
 
     # -- the estimate-feedback roll-out: the plant and the estimator flown together -------------------
     @staticmethod
