@@ -1209,6 +1209,113 @@ int qln_landing_filter_guarded(qln_handle* h, const double* Zref, const double* 
 int qln_landing_filter_guarded_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
                                     int32_t ny, const double* Vdiag, const double* Y, const double* xhat0, double* Xhat,
                                     double* innov, double* score, double* loglik, double* event_hat);
+/* The filter at a MODEL OF EACH RECORD'S OWN: the calls above with model [B][QLN_MODEL_NP] = {g, mb, mf, lb} per problem behind
+ * ny, in the family's order; Phi_k is taken at model[b] where the calls above take the handle's model.  model == NULL is the
+ * handle's four values, and with NULL or with rows that hold those values every output has the bits of the call above.  The host
+ * forms also refuse a model entry that is not finite, or a mass or the body length that is not positive.  Everything else --
+ * inputs, outputs, refusals -- as above. */
+int qln_landing_filter_model(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H, int32_t ny,
+                             const double* model /* [B][QLN_MODEL_NP] or NULL */, const double* Vdiag, const double* Y,
+                             const double* xhat0, double* Xhat, double* innov, double* score, double* loglik);
+int qln_landing_filter_model_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                  int32_t ny, const double* model, const double* Vdiag, const double* Y, const double* xhat0,
+                                  double* Xhat, double* innov, double* score, double* loglik);
+int qln_landing_filter_guarded_model(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                     int32_t ny, const double* model, const double* Vdiag, const double* Y, const double* xhat0,
+                                     double* Xhat, double* innov, double* score, double* loglik, double* event_hat);
+int qln_landing_filter_guarded_model_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain,
+                                          const double* H, int32_t ny, const double* model, const double* Vdiag, const double* Y,
+                                          const double* xhat0, double* Xhat, double* innov, double* score, double* loglik,
+                                          double* event_hat);
+/* The SWEEPS THROUGH THE FILTER: the forward (tangent) and the reverse (cotangent) sweep of qln_landing_filter_model* and of its
+ * score, at the record and at the trajectory the filter produced.  Nothing is re-run.
+ * Evaluation point (both sweeps): Zref; Zrec, of which only the control slots are read; Lgain, H, ny; model or NULL; Xhat, the
+ * filter's output; innov, its other output, REQUIRED EXACTLY WHEN a tangent or cotangent of Lgain or a score term is asked for;
+ * Vdiag, a HOST array of ny entries, required exactly when a score term is asked for, then finite and > 0; the guarded forms
+ * also take event_hat, the filter's record, of which only entries 0 (the knot) and 1 (tau) are read.  Zref gets no tangent and
+ * is not read: Y already is the reading minus H x_ref, so x_ref cancels out of every derivative; it keeps its place in the
+ * family's order and must not be NULL.
+ * Forward sweep.  Tangents, each optional (NULL: zero), at least one: Y_dot [B][N][ny]; Zrec_dot in the layout of Z, of which
+ * only the control slots are read (dF_k, dh_k); Lgain_dot [B][N][15][ny]; xhat0_dot [B][15] (NULL means zero: x_ref,0 is an
+ * input without a tangent here); model_dot [B][QLN_MODEL_NP].
+ *     dxm_0 = xhat0_dot
+ *     for k = 0 .. N-1:
+ *       dinnov_k  = Y_dot_k - H dxm_k
+ *       dxh_k     = dxm_k + L_k dinnov_k + Lgain_dot_k innov_k
+ *       de_k      = dinnov_k - H (L_k dinnov_k)
+ *       nis_dot_k = sum_r (dinnov_k[r] e_k[r] + innov_k[r] de_k[r]) / V[r]            (e_k as in qln_landing_filter)
+ *       if k < N-1:  dxm_{k+1} = A^e_k dxh_k + B^e_k (dF_k, dh_k) + G^e_k model_dot
+ *     loglik_dot[b] = -1/2 sum_k nis_dot_k
+ * [A^e B^e G^e] is the block of qln_tracking_rollout_model_jvp at (Xhat_k, Zrec's u_k, model[b]); guarded, the blocks of
+ * qln_tracking_rollout_guarded_jvp at the estimator's own touchdown knot and tau from event_hat: at that knot the composite
+ * step, whose d tau depends on dxh, dF and model_dot.
+ * Outputs (each optional, at least one; overwritten; which are asked for does not change the others' bits): Xhat_dot
+ * [B][N][15]; innov_dot [B][N][ny]; nis_dot [B][N]; loglik_dot [B]; guarded: event_hat_dot [B][QLN_TOUCHDOWN_INFO_STRIDE] with
+ * the entries qln_tracking_rollout_guarded_jvp defines (1: d tau, 2: the touchdown clock's tangent, the rest zeros).
+ * FIXED GAINS.  log det S_k depends on Lgain alone, and its derivative is not offered: nis_dot or loglik_dot together with
+ * Lgain_dot is refused, and loglik_dot is the EXACT derivative of loglik AT FIXED GAINS (the prediction-error gradient).  The
+ * gains of qln_tracking_kalman* themselves depend on the model: a caller to whom the total derivative matters redesigns them
+ * between outer iterations.
+ * Reverse sweep, the exact transpose.  Cotangents, each optional (NULL: zero), at least one: Xhat_bar [B][N][15]; innov_bar
+ * [B][N][ny]; nis_bar [B][N]; loglik_bar [B].  With nb_k = nis_bar_k - loglik_bar / 2 and lamm, the cotangent of dxm_{k+1}, zero
+ * behind the last knot, for k = N-1 .. 0:
+ *     k < N-1:  ubar_k = B^e' lamm;  xhb = Xhat_bar_k + A^e' lamm;  model_bar += G^e' lamm          (k = N-1: xhb = Xhat_bar_k)
+ *     ib   = innov_bar_k + L_k' xhb + nb_k (G_k + G_k') innov_k,    G_k = diag(1/V) (I - H L_k), the FULL matrix
+ *     lamm = xhb - H' ib
+ * Outputs (each optional, at least one): Y_bar [B][N][ny] = ib; Zrec_bar in the layout of Z: ubar_k in the control slots, exact
+ * zeros in the state slots, entries past n_nlp never written; Lgain_bar [B][N][15][ny] = xhb innov_k', refused together with
+ * nis_bar or loglik_bar for the reason above; xhat0_bar [B][15] = lamm after knot 0; model_bar [B][QLN_MODEL_NP].
+ * Reductions: nis_dot_k and ib are sums over the sensor rows in row order, each row's H-product a sum over a row of sixteen
+ * lanes in a fixed tree; model_bar is summed over the knots per state and then over the states.  The loops over the sensor rows
+ * run to QLN_TRACK_NY_MAX under r < ny, the rows behind ny taking V = 1, so a call with ny rows gives the bits of the call with
+ * eight rows and zeros written out.
+ * <Xhat_bar, Xhat_dot> + <innov_bar, innov_dot> + <nis_bar, nis_dot> + <loglik_bar, loglik_dot> = <Y_bar, Y_dot> + <Zrec_bar,
+ * Zrec_dot> + <Lgain_bar, Lgain_dot> + <xhat0_bar, xhat0_dot> + <model_bar, model_dot> holds in both modes.
+ * Refused with QLN_ERR_INVALID_ARGUMENT, the checks that need no handle before the null handle, in the family's order: ny outside
+ * 1..QLN_TRACK_NY_MAX, no tangent (no cotangent), no output, Lgain_dot (Lgain_bar) together with a score term, a NULL Vdiag
+ * with a score term, a V entry not finite or not > 0 (then), a NULL innov where it is required, a NULL event_hat (guarded), a
+ * NULL H or Lgain; behind the handle a NULL Zref, Zrec or Xhat, and an output that overlaps an input or another output.  The
+ * device forms do not validate device data; the host forms also refuse a non-finite H, a model as above and an event_hat whose
+ * knot is not an integer in [-1, N-2] or whose tau is not finite and >= 0.  Device pointers, stream-ordered; needs no cost
+ * table. */
+int qln_landing_filter_jvp(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H, int32_t ny,
+                           const double* model /* or NULL */, const double* Vdiag /* host, or NULL without a score term */,
+                           const double* Xhat, const double* innov /* or NULL */, const double* Y_dot, const double* Zrec_dot,
+                           const double* Lgain_dot, const double* xhat0_dot, const double* model_dot, double* Xhat_dot,
+                           double* innov_dot, double* nis_dot, double* loglik_dot);
+int qln_landing_filter_jvp_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                int32_t ny, const double* model, const double* Vdiag, const double* Xhat, const double* innov,
+                                const double* Y_dot, const double* Zrec_dot, const double* Lgain_dot, const double* xhat0_dot,
+                                const double* model_dot, double* Xhat_dot, double* innov_dot, double* nis_dot, double* loglik_dot);
+int qln_landing_filter_guarded_jvp(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                   int32_t ny, const double* model, const double* Vdiag, const double* Xhat, const double* innov,
+                                   const double* event_hat /* required */, const double* Y_dot, const double* Zrec_dot,
+                                   const double* Lgain_dot, const double* xhat0_dot, const double* model_dot, double* Xhat_dot,
+                                   double* innov_dot, double* nis_dot, double* loglik_dot, double* event_hat_dot);
+int qln_landing_filter_guarded_jvp_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                        int32_t ny, const double* model, const double* Vdiag, const double* Xhat,
+                                        const double* innov, const double* event_hat, const double* Y_dot, const double* Zrec_dot,
+                                        const double* Lgain_dot, const double* xhat0_dot, const double* model_dot,
+                                        double* Xhat_dot, double* innov_dot, double* nis_dot, double* loglik_dot,
+                                        double* event_hat_dot);
+int qln_landing_filter_vjp(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H, int32_t ny,
+                           const double* model, const double* Vdiag, const double* Xhat, const double* innov,
+                           const double* Xhat_bar, const double* innov_bar, const double* nis_bar, const double* loglik_bar,
+                           double* Y_bar, double* Zrec_bar, double* Lgain_bar, double* xhat0_bar, double* model_bar);
+int qln_landing_filter_vjp_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                int32_t ny, const double* model, const double* Vdiag, const double* Xhat, const double* innov,
+                                const double* Xhat_bar, const double* innov_bar, const double* nis_bar, const double* loglik_bar,
+                                double* Y_bar, double* Zrec_bar, double* Lgain_bar, double* xhat0_bar, double* model_bar);
+int qln_landing_filter_guarded_vjp(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                   int32_t ny, const double* model, const double* Vdiag, const double* Xhat, const double* innov,
+                                   const double* event_hat /* required */, const double* Xhat_bar, const double* innov_bar,
+                                   const double* nis_bar, const double* loglik_bar, double* Y_bar, double* Zrec_bar,
+                                   double* Lgain_bar, double* xhat0_bar, double* model_bar);
+int qln_landing_filter_guarded_vjp_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                        int32_t ny, const double* model, const double* Vdiag, const double* Xhat,
+                                        const double* innov, const double* event_hat, const double* Xhat_bar,
+                                        const double* innov_bar, const double* nis_bar, const double* loglik_bar, double* Y_bar,
+                                        double* Zrec_bar, double* Lgain_bar, double* xhat0_bar, double* model_bar);
 /* Z <- Z + N(0, sigma^2) on every entry, step lengths h then clipped to [h_min, h_max] (redraw_h = 0) or redrawn
  * U(h_min, h_max) (redraw_h != 0) -- the evaluation point of SURVEY.md 8d from qln_initial_guess's Z0.  The normal
  * draws are Box-Muller on the sampler's stream from `stream_offset`: the recipe's distribution, not numpy's numbers. */

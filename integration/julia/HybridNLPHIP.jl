@@ -483,9 +483,10 @@ end
 # nothing for no score; xhat0: 15 values or nothing (the reference's first knot).  Returns (Xhat, innov, score, loglik): the
 # estimates as (15, N), the innovations as (ny, N), score (2, N) = (nis_k, log det S_k) and the Gaussian log-likelihood, the last
 # two nothing without V.  The call cannot check that L belongs to V.  landing_filter_guarded lets the estimator land by its own
-# guard and also returns events_hat, its touchdown record.
+# guard and also returns events_hat, its touchdown record.  model: the record's own (g, mb, mf, lb), or nothing for the handle's
+# (DESIGN.md 4.27; with nothing the call has the bits of the entry without a model).
 function landing_filter(prob::HybridNLPHIP, Zref::Vector{Float64}, Zrec::Vector{Float64}, L::Array{Float64,3}, H::Matrix{Float64},
-                        Y::Matrix{Float64}; V=nothing, xhat0=nothing)
+                        Y::Matrix{Float64}; V=nothing, xhat0=nothing, model=nothing)
     N = prob.N
     ny = size(H, 1)
     (1 <= ny <= 8 && size(H, 2) == 15 && size(L) == (ny, 15, N) && size(Y) == (ny, N) && (V === nothing || length(V) == ny)) ||
@@ -495,15 +496,16 @@ function landing_filter(prob::HybridNLPHIP, Zref::Vector{Float64}, Zrec::Vector{
     innov = zeros(ny, N)
     score = V === nothing ? nothing : zeros(2, N)
     loglik = V === nothing ? nothing : zeros(1)
-    qln_check(ccall((:qln_landing_filter_host, LIBQLN), Cint,
-                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble},
+    qln_check(ccall((:qln_landing_filter_model_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
                      Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
-                    prob.handle, Zref, Zrec, L, Hrow, Int32(ny), V === nothing ? C_NULL : V, Y, xhat0 === nothing ? C_NULL : xhat0,
-                    Xhat, innov, score === nothing ? C_NULL : score, loglik === nothing ? C_NULL : loglik))
+                    prob.handle, Zref, Zrec, L, Hrow, Int32(ny), model === nothing ? C_NULL : model, V === nothing ? C_NULL : V, Y,
+                    xhat0 === nothing ? C_NULL : xhat0, Xhat, innov, score === nothing ? C_NULL : score,
+                    loglik === nothing ? C_NULL : loglik))
     return Xhat, innov, score, loglik === nothing ? nothing : loglik[1]
 end
 function landing_filter_guarded(prob::HybridNLPHIP, Zref::Vector{Float64}, Zrec::Vector{Float64}, L::Array{Float64,3},
-                                H::Matrix{Float64}, Y::Matrix{Float64}; V=nothing, xhat0=nothing)
+                                H::Matrix{Float64}, Y::Matrix{Float64}; V=nothing, xhat0=nothing, model=nothing)
     N = prob.N
     ny = size(H, 1)
     (1 <= ny <= 8 && size(H, 2) == 15 && size(L) == (ny, 15, N) && size(Y) == (ny, N) && (V === nothing || length(V) == ny)) ||
@@ -514,12 +516,105 @@ function landing_filter_guarded(prob::HybridNLPHIP, Zref::Vector{Float64}, Zrec:
     score = V === nothing ? nothing : zeros(2, N)
     loglik = V === nothing ? nothing : zeros(1)
     events_hat = zeros(8)
-    qln_check(ccall((:qln_landing_filter_guarded_host, LIBQLN), Cint,
-                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble},
+    qln_check(ccall((:qln_landing_filter_guarded_model_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
                      Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
-                    prob.handle, Zref, Zrec, L, Hrow, Int32(ny), V === nothing ? C_NULL : V, Y, xhat0 === nothing ? C_NULL : xhat0,
-                    Xhat, innov, score === nothing ? C_NULL : score, loglik === nothing ? C_NULL : loglik, events_hat))
+                    prob.handle, Zref, Zrec, L, Hrow, Int32(ny), model === nothing ? C_NULL : model, V === nothing ? C_NULL : V, Y,
+                    xhat0 === nothing ? C_NULL : xhat0, Xhat, innov, score === nothing ? C_NULL : score,
+                    loglik === nothing ? C_NULL : loglik, events_hat))
     return Xhat, innov, score, loglik === nothing ? nothing : loglik[1], events_hat
+end
+# The sweeps through the filter (include/qln_evaluator.h, DESIGN.md 4.27), host forms: the derivative of landing_filter /
+# landing_filter_guarded at the record and the (Xhat, innov[, events_hat]) it returned, with respect to Y, the control slots of
+# Zrec, L, xhat0 and model, AT FIXED GAINS in the score: V given asks for nis_dot (N) and loglik_dot (the exact derivative of
+# loglik at fixed gains) and excludes L_dot / L_bar, which need V = nothing.  Forward: tangents as keywords, nothing for zero;
+# returns (Xhat_dot (15, N), innov_dot (ny, N), nis_dot, loglik_dot), the last two nothing without V, and guarded also
+# event_hat_dot.  Reverse: cotangents as keywords (Xhat_bar (15, N), innov_bar (ny, N), and with V nis_bar (N) and loglik_bar);
+# returns (Y_bar (ny, N), Zrec_bar, L_bar or nothing with V, xhat0_bar (15), model_bar (4)).
+function _filter_sweep_rows(prob::HybridNLPHIP, L::Array{Float64,3}, H::Matrix{Float64}, V)
+    ny = size(H, 1)
+    (1 <= ny <= 8 && size(H, 2) == 15 && size(L) == (ny, 15, prob.N) && (V === nothing || length(V) == ny)) ||
+        error("H: (ny, 15) with 1 <= ny <= 8, L: (ny, 15, N), V: ny")
+    return ny, Matrix{Float64}(transpose(H))  # row-major [ny][15]
+end
+function landing_filter_jvp(prob::HybridNLPHIP, Zref::Vector{Float64}, Zrec::Vector{Float64}, L::Array{Float64,3},
+                            H::Matrix{Float64}, Xhat::Matrix{Float64}, innov::Matrix{Float64}; V=nothing, model=nothing,
+                            Y_dot=nothing, Zrec_dot=nothing, L_dot=nothing, xhat0_dot=nothing, model_dot=nothing)
+    ny, Hrow = _filter_sweep_rows(prob, L, H, V)
+    Xhat_dot = zeros(15, prob.N)
+    innov_dot = zeros(ny, prob.N)
+    nis_dot = V === nothing ? nothing : zeros(prob.N)
+    loglik_dot = V === nothing ? nothing : zeros(1)
+    qln_check(ccall((:qln_landing_filter_jvp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, Zrec, L, Hrow, Int32(ny), model === nothing ? C_NULL : model, V === nothing ? C_NULL : V, Xhat,
+                    innov, Y_dot === nothing ? C_NULL : Y_dot, Zrec_dot === nothing ? C_NULL : Zrec_dot,
+                    L_dot === nothing ? C_NULL : L_dot, xhat0_dot === nothing ? C_NULL : xhat0_dot,
+                    model_dot === nothing ? C_NULL : model_dot, Xhat_dot, innov_dot, nis_dot === nothing ? C_NULL : nis_dot,
+                    loglik_dot === nothing ? C_NULL : loglik_dot))
+    return Xhat_dot, innov_dot, nis_dot, loglik_dot === nothing ? nothing : loglik_dot[1]
+end
+function landing_filter_guarded_jvp(prob::HybridNLPHIP, Zref::Vector{Float64}, Zrec::Vector{Float64}, L::Array{Float64,3},
+                                    H::Matrix{Float64}, Xhat::Matrix{Float64}, innov::Matrix{Float64}, events_hat::Vector{Float64};
+                                    V=nothing, model=nothing, Y_dot=nothing, Zrec_dot=nothing, L_dot=nothing, xhat0_dot=nothing,
+                                    model_dot=nothing)
+    ny, Hrow = _filter_sweep_rows(prob, L, H, V)
+    Xhat_dot = zeros(15, prob.N)
+    innov_dot = zeros(ny, prob.N)
+    nis_dot = V === nothing ? nothing : zeros(prob.N)
+    loglik_dot = V === nothing ? nothing : zeros(1)
+    event_hat_dot = zeros(8)
+    qln_check(ccall((:qln_landing_filter_guarded_jvp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, Zrec, L, Hrow, Int32(ny), model === nothing ? C_NULL : model, V === nothing ? C_NULL : V, Xhat,
+                    innov, events_hat, Y_dot === nothing ? C_NULL : Y_dot, Zrec_dot === nothing ? C_NULL : Zrec_dot,
+                    L_dot === nothing ? C_NULL : L_dot, xhat0_dot === nothing ? C_NULL : xhat0_dot,
+                    model_dot === nothing ? C_NULL : model_dot, Xhat_dot, innov_dot, nis_dot === nothing ? C_NULL : nis_dot,
+                    loglik_dot === nothing ? C_NULL : loglik_dot, event_hat_dot))
+    return Xhat_dot, innov_dot, nis_dot, loglik_dot === nothing ? nothing : loglik_dot[1], event_hat_dot
+end
+function landing_filter_vjp(prob::HybridNLPHIP, Zref::Vector{Float64}, Zrec::Vector{Float64}, L::Array{Float64,3},
+                            H::Matrix{Float64}, Xhat::Matrix{Float64}, innov::Matrix{Float64}; V=nothing, model=nothing,
+                            Xhat_bar=nothing, innov_bar=nothing, nis_bar=nothing, loglik_bar=nothing)
+    ny, Hrow = _filter_sweep_rows(prob, L, H, V)
+    Y_bar = zeros(ny, prob.N)
+    Zrec_bar = zeros(length(Zrec))
+    L_bar = V === nothing ? zeros(ny, 15, prob.N) : nothing
+    xhat0_bar = zeros(15)
+    model_bar = zeros(4)
+    qln_check(ccall((:qln_landing_filter_vjp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, Zrec, L, Hrow, Int32(ny), model === nothing ? C_NULL : model, V === nothing ? C_NULL : V, Xhat,
+                    innov, Xhat_bar === nothing ? C_NULL : Xhat_bar, innov_bar === nothing ? C_NULL : innov_bar,
+                    nis_bar === nothing ? C_NULL : nis_bar, loglik_bar === nothing ? C_NULL : Float64[loglik_bar], Y_bar, Zrec_bar,
+                    L_bar === nothing ? C_NULL : L_bar, xhat0_bar, model_bar))
+    return Y_bar, Zrec_bar, L_bar, xhat0_bar, model_bar
+end
+function landing_filter_guarded_vjp(prob::HybridNLPHIP, Zref::Vector{Float64}, Zrec::Vector{Float64}, L::Array{Float64,3},
+                                    H::Matrix{Float64}, Xhat::Matrix{Float64}, innov::Matrix{Float64}, events_hat::Vector{Float64};
+                                    V=nothing, model=nothing, Xhat_bar=nothing, innov_bar=nothing, nis_bar=nothing,
+                                    loglik_bar=nothing)
+    ny, Hrow = _filter_sweep_rows(prob, L, H, V)
+    Y_bar = zeros(ny, prob.N)
+    Zrec_bar = zeros(length(Zrec))
+    L_bar = V === nothing ? zeros(ny, 15, prob.N) : nothing
+    xhat0_bar = zeros(15)
+    model_bar = zeros(4)
+    qln_check(ccall((:qln_landing_filter_guarded_vjp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zref, Zrec, L, Hrow, Int32(ny), model === nothing ? C_NULL : model, V === nothing ? C_NULL : V, Xhat,
+                    innov, events_hat, Xhat_bar === nothing ? C_NULL : Xhat_bar, innov_bar === nothing ? C_NULL : innov_bar,
+                    nis_bar === nothing ? C_NULL : nis_bar, loglik_bar === nothing ? C_NULL : Float64[loglik_bar], Y_bar, Zrec_bar,
+                    L_bar === nothing ? C_NULL : L_bar, xhat0_bar, model_bar))
+    return Y_bar, Zrec_bar, L_bar, xhat0_bar, model_bar
 end
 # The sweeps through the estimate-feedback roll-out (include/qln_evaluator.h, DESIGN.md 4.23): the derivative of
 # tracking_rollout_estimated / _guarded at the (Zout, Xhat, innov[, events, events_hat]) it returned, with respect to Zref, K, L,

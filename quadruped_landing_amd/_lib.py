@@ -195,6 +195,18 @@ SIGNATURES = {
     "qln_landing_filter_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 7),
     "qln_landing_filter_guarded": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 8),
     "qln_landing_filter_guarded_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 8),
+    "qln_landing_filter_model": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 8),
+    "qln_landing_filter_model_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 8),
+    "qln_landing_filter_guarded_model": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 9),
+    "qln_landing_filter_guarded_model_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 9),
+    "qln_landing_filter_jvp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 13),
+    "qln_landing_filter_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 13),
+    "qln_landing_filter_guarded_jvp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 15),
+    "qln_landing_filter_guarded_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 15),
+    "qln_landing_filter_vjp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 13),
+    "qln_landing_filter_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 13),
+    "qln_landing_filter_guarded_vjp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 14),
+    "qln_landing_filter_guarded_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 14),
     "qln_tracking_rollout_estimated": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 8),
     "qln_tracking_rollout_estimated_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 8),
     "qln_tracking_rollout_estimated_guarded": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 10),

@@ -125,7 +125,8 @@ enum HostRole {
     kZrec,   // in: the filter's recorded trajectory (control slots read)    layout of Z
     kY,      // in: the filter's measurements ([B][N][ny] used)             [B][N][8]
     kScore,  // out: the filter's {nis_k, log det S_k}                      [B][N][2]
-    kLoglik, // out: the filter's log-likelihood                            [B]
+    kLoglik, // out: the filter's log-likelihood; out / in: its sweeps' loglik_dot / loglik_bar  [B]
+    kNisD,   // out: the filter jvp's nis_dot; in: the vjp's nis_bar        [B][N]
     kHostRoles
 };
 
@@ -208,6 +209,7 @@ int64_t host_role_size(const qln_handle* h, HostRole r) {
         case kLgain: case kLgainD: return tracking_gain_total(D, QLN_TRACK_NY_MAX);
         case kVnoise: case kInnov: case kInnovD: case kY: return tracking_meas_total(D, QLN_TRACK_NY_MAX);
         case kScore: return (int64_t)D.B * D.N * 2;
+        case kNisD: return (int64_t)D.B * D.N;
         case kWnoise: return (int64_t)D.B * (D.N - 1) * QLN_NX;
         case kXhat: case kXhatD: case kXs: return (int64_t)D.B * D.N * QLN_NX;
         case kHostRoles: break;
@@ -1875,10 +1877,11 @@ int qln_landing_smoother_guarded_host(qln_handle* h, const double* Ztraj, const 
 
 // The filter on recorded data (k_landing_filter).  The checks that need no handle come first.
 // guarded: the estimator lands by its own guard, with its event record (may be null)
+// model: the model of each record's own (qln_landing_filter_model; null: the handle's)
 struct FilterCall {
     const double *Zref, *Zrec, *Lgain, *H;
     int32_t ny;
-    const double *Vdiag, *Y, *xhat0;
+    const double *model, *Vdiag, *Y, *xhat0;
     double *Xhat, *innov, *score, *loglik, *event_hat;
     bool guarded;
 };
@@ -1907,16 +1910,17 @@ static int landing_filter(qln_handle* h, MemForm mem, const FilterCall& a, const
     // the rows, gains, measurements and innovations of the call's ny, of the roles' eight
     const int64_t ng = tracking_gain_total(h->dims, a.ny), nm = tracking_meas_total(h->dims, a.ny);
     const HostArgs args = {copy_in(kZ, a.Zref), copy_in(kZrec, a.Zrec), copy_in(kLgain, a.Lgain).sized(ng),
-                           copy_in(kH, a.H).sized((int64_t)a.ny * QLN_NX), copy_in(kY, a.Y).sized(nm), copy_in(kXhat0, a.xhat0),
-                           copy_out(kXhat, a.Xhat), copy_out(kInnov, a.innov).sized(nm), copy_out(kScore, a.score),
-                           copy_out(kLoglik, a.loglik), copy_out(kEventHat, a.event_hat)};
+                           copy_in(kH, a.H).sized((int64_t)a.ny * QLN_NX), copy_in(kModel, a.model), copy_in(kY, a.Y).sized(nm),
+                           copy_in(kXhat0, a.xhat0), copy_out(kXhat, a.Xhat), copy_out(kInnov, a.innov).sized(nm),
+                           copy_out(kScore, a.score), copy_out(kLoglik, a.loglik), copy_out(kEventHat, a.event_hat)};
     if (int rc = check_no_overlap(h, args, who)) return rc;
     if (mem == kHostMem) {
         if (int rc = check_host_meas(a.H, a.ny, who)) return rc;
+        if (int rc = check_host_models(h, a.model, who)) return rc;
     }
     return run_call(h, mem, args, [&](double* const* d, bool) {
-        return qln::launch_landing_filter(h->p, d[kZ], d[kZrec], d[kLgain], d[kH], a.ny, a.Vdiag, d[kY], d[kXhat0], d[kXhat],
-                                          d[kInnov], d[kScore], d[kLoglik], a.guarded, d[kEventHat], h->stream);
+        return qln::launch_landing_filter(h->p, d[kZ], d[kZrec], d[kLgain], d[kH], a.ny, a.Vdiag, d[kY], d[kXhat0], d[kModel],
+                                          d[kXhat], d[kInnov], d[kScore], d[kLoglik], a.guarded, d[kEventHat], h->stream);
     });
 }
 
@@ -1952,6 +1956,249 @@ int qln_landing_filter_guarded_host(qln_handle* h, const double* Zref, const dou
                                     double* innov, double* score, double* loglik, double* event_hat) {
     return landing_filter(h, kHostMem, filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, true, event_hat),
                           "qln_landing_filter_guarded_host");
+}
+// the filter at a model of each record's own: the same path with model [B][QLN_MODEL_NP] (null: the handle's)
+static FilterCall with_model(FilterCall a, const double* model) {
+    a.model = model;
+    return a;
+}
+int qln_landing_filter_model(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H, int32_t ny,
+                             const double* model, const double* Vdiag, const double* Y, const double* xhat0, double* Xhat,
+                             double* innov, double* score, double* loglik) {
+    return landing_filter(h, kDeviceMem,
+                          with_model(filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, false, nullptr), model),
+                          "qln_landing_filter_model");
+}
+int qln_landing_filter_model_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                  int32_t ny, const double* model, const double* Vdiag, const double* Y, const double* xhat0,
+                                  double* Xhat, double* innov, double* score, double* loglik) {
+    return landing_filter(h, kHostMem,
+                          with_model(filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, false, nullptr), model),
+                          "qln_landing_filter_model_host");
+}
+int qln_landing_filter_guarded_model(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                     int32_t ny, const double* model, const double* Vdiag, const double* Y, const double* xhat0,
+                                     double* Xhat, double* innov, double* score, double* loglik, double* event_hat) {
+    return landing_filter(h, kDeviceMem,
+                          with_model(filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, true, event_hat), model),
+                          "qln_landing_filter_guarded_model");
+}
+int qln_landing_filter_guarded_model_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain,
+                                          const double* H, int32_t ny, const double* model, const double* Vdiag, const double* Y,
+                                          const double* xhat0, double* Xhat, double* innov, double* score, double* loglik,
+                                          double* event_hat) {
+    return landing_filter(h, kHostMem,
+                          with_model(filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, true, event_hat), model),
+                          "qln_landing_filter_guarded_model_host");
+}
+
+// The sweeps through the filter (k_landing_filter_jvp / _vjp).  What both share: the record and the trajectory the filter
+// produced.  The checks that need no handle come first.  guarded: the sweeps through the estimator's own touchdown, which need
+// its record event_hat.
+struct FilterTraj {
+    const double *Zref, *Zrec, *Lgain, *H;
+    int32_t ny;
+    const double *model, *Vdiag, *Xhat, *innov, *event_hat;
+    bool guarded;
+};
+
+// want_gain: a tangent or cotangent of Lgain is asked for; want_score: one of nis or loglik.  They exclude each other (log det S_k
+// depends on the gains, and its derivative is not offered), and either needs innov; the score also needs Vdiag.
+static int check_filter_sweep_args(const qln_handle* h, const FilterTraj& t, bool want_gain, bool want_score, bool forward,
+                                   const std::string& w) {
+    if (want_gain && want_score)
+        return fail(QLN_ERR_INVALID_ARGUMENT,
+                    w + (forward ? ": Lgain_dot with nis_dot or loglik_dot (the score is differentiated at fixed gains)"
+                                 : ": Lgain_bar with nis_bar or loglik_bar (the score is differentiated at fixed gains)"));
+    if (want_score) {
+        if (!t.Vdiag) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Vdiag with a score term");
+        for (int i = 0; i < t.ny; ++i)
+            if (!(std::isfinite(t.Vdiag[i]) && t.Vdiag[i] > 0.0))
+                return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Vdiag must be finite and > 0 (entry " + std::to_string(i) + ")");
+    }
+    if ((want_gain || want_score) && !t.innov)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null innov (Lgain's tangent or cotangent and the score terms need the innovations)");
+    if (t.guarded && !t.event_hat) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event_hat (the guarded filter's record)");
+    if (!t.H || !t.Lgain) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null H or Lgain");
+    if (int rc = check_handle(h)) return rc;
+    if (!t.Zref || !t.Zrec || !t.Xhat) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref, Zrec or Xhat");
+    return QLN_OK;
+}
+
+static int check_host_filter_traj(const qln_handle* h, const FilterTraj& t, const char* who) {
+    if (int rc = check_host_meas(t.H, t.ny, who)) return rc;
+    if (int rc = check_host_models(h, t.model, who)) return rc;
+    return check_host_events(h, t.event_hat, who);
+}
+
+static qln::FilterSweepIn filter_sweep_in(double* const* d, const FilterTraj& t, bool want_score) {
+    qln::FilterSweepIn in = {d[kZrec], d[kLgain], d[kH], t.ny, d[kModel], d[kXhat], d[kInnov], d[kEventHat], {}};
+    for (int r = 0; r < QLN_TRACK_NY_MAX; ++r) in.iv[r] = (want_score && r < t.ny) ? 1.0 / t.Vdiag[r] : 1.0;
+    return in;
+}
+
+// Zref is not read (it has no tangent, and Y already is the reading minus H x_ref): it is checked, ruled and never staged.
+// innov is staged, and ruled, only where it is read.
+static int landing_filter_jvp(qln_handle* h, MemForm mem, const FilterTraj& t, const qln::FilterJvpArgs& a, const char* who) {
+    const std::string w(who);
+    if (t.ny < 1 || t.ny > QLN_TRACK_NY_MAX)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
+    if (!a.Y_dot && !a.Zrec_dot && !a.Lgain_dot && !a.xhat0_dot && !a.model_dot)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every tangent is NULL (no direction)");
+    if (!a.Xhat_dot && !a.innov_dot && !a.nis_dot && !a.loglik_dot && !a.event_hat_dot)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every output is NULL (nothing to compute)");
+    const bool want_gain = a.Lgain_dot != nullptr, want_score = a.nis_dot || a.loglik_dot;
+    if (int rc = check_filter_sweep_args(h, t, want_gain, want_score, true, w)) return rc;
+    const int64_t ng = tracking_gain_total(h->dims, t.ny), nm = tracking_meas_total(h->dims, t.ny);
+    const bool want_innov = want_gain || want_score;
+    const HostArgs args = {copy_in(kZ, t.Zref).staged_if(false), copy_in(kZrec, t.Zrec), copy_in(kLgain, t.Lgain).sized(ng),
+                           copy_in(kH, t.H).sized((int64_t)t.ny * QLN_NX), copy_in(kModel, t.model), copy_in(kXhat, t.Xhat),
+                           copy_in(kInnov, t.innov).sized(nm).ruled_if(want_innov).staged_if(want_innov),
+                           copy_in(kEventHat, t.event_hat), copy_in(kY, a.Y_dot).sized(nm), copy_in(kZdot, a.Zrec_dot),
+                           copy_in(kLgainD, a.Lgain_dot).sized(ng), copy_in(kXhat0, a.xhat0_dot), copy_in(kModelD, a.model_dot),
+                           copy_out(kXhatD, a.Xhat_dot), copy_out(kInnovD, a.innov_dot).sized(nm), copy_out(kNisD, a.nis_dot),
+                           copy_out(kLoglik, a.loglik_dot), copy_out(kEventHatD, a.event_hat_dot)};
+    if (int rc = check_no_overlap(h, args, who)) return rc;
+    if (mem == kHostMem)
+        if (int rc = check_host_filter_traj(h, t, who)) return rc;
+    return run_call(h, mem, args, [&](double* const* d, bool) {
+        const qln::FilterJvpArgs da = {d[kY], d[kZdot], d[kLgainD], d[kXhat0], d[kModelD], d[kXhatD], d[kInnovD], d[kNisD],
+                                       d[kLoglik], d[kEventHatD]};
+        return qln::launch_landing_filter_jvp(h->p, filter_sweep_in(d, t, want_score), da, h->stream);
+    });
+}
+
+// Zrec_bar is in-out: the kernel never writes behind n_nlp, and that padding is the caller's.
+static int landing_filter_vjp(qln_handle* h, MemForm mem, const FilterTraj& t, const qln::FilterVjpArgs& a, const char* who) {
+    const std::string w(who);
+    if (t.ny < 1 || t.ny > QLN_TRACK_NY_MAX)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
+    if (!a.Xhat_bar && !a.innov_bar && !a.nis_bar && !a.loglik_bar)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every cotangent is NULL (nothing to pull back)");
+    if (!a.Y_bar && !a.Zrec_bar && !a.Lgain_bar && !a.xhat0_bar && !a.model_bar)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every output is NULL (nothing to compute)");
+    const bool want_gain = a.Lgain_bar != nullptr, want_score = a.nis_bar || a.loglik_bar;
+    if (int rc = check_filter_sweep_args(h, t, want_gain, want_score, false, w)) return rc;
+    const int64_t ng = tracking_gain_total(h->dims, t.ny), nm = tracking_meas_total(h->dims, t.ny);
+    const bool want_innov = want_gain || want_score;
+    const HostArgs args = {copy_in(kZ, t.Zref).staged_if(false), copy_in(kZrec, t.Zrec), copy_in(kLgain, t.Lgain).sized(ng),
+                           copy_in(kH, t.H).sized((int64_t)t.ny * QLN_NX), copy_in(kModel, t.model), copy_in(kXhat, t.Xhat),
+                           copy_in(kInnov, t.innov).sized(nm).ruled_if(want_innov).staged_if(want_innov),
+                           copy_in(kEventHat, t.event_hat), copy_in(kXhatD, a.Xhat_bar), copy_in(kInnovD, a.innov_bar).sized(nm),
+                           copy_in(kNisD, a.nis_bar), copy_in(kLoglik, a.loglik_bar), copy_out(kY, a.Y_bar).sized(nm),
+                           copy_inout(kZio, a.Zrec_bar), copy_out(kLgainD, a.Lgain_bar).sized(ng), copy_out(kXhat0, a.xhat0_bar),
+                           copy_out(kModelD, a.model_bar)};
+    if (int rc = check_no_overlap(h, args, who)) return rc;
+    if (mem == kHostMem)
+        if (int rc = check_host_filter_traj(h, t, who)) return rc;
+    return run_call(h, mem, args, [&](double* const* d, bool) {
+        const qln::FilterVjpArgs da = {d[kXhatD], d[kInnovD], d[kNisD], d[kLoglik], d[kY], d[kZio], d[kLgainD], d[kXhat0],
+                                       d[kModelD]};
+        return qln::launch_landing_filter_vjp(h->p, filter_sweep_in(d, t, want_score), da, h->stream);
+    });
+}
+
+static FilterTraj filter_traj(const double* Zref, const double* Zrec, const double* Lgain, const double* H, int32_t ny,
+                              const double* model, const double* Vdiag, const double* Xhat, const double* innov, bool guarded,
+                              const double* event_hat) {
+    FilterTraj t{};
+    t.Zref = Zref; t.Zrec = Zrec; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Vdiag = Vdiag; t.Xhat = Xhat;
+    t.innov = innov; t.guarded = guarded; t.event_hat = event_hat;
+    return t;
+}
+static qln::FilterJvpArgs filter_jvp_args(const double* Y_dot, const double* Zrec_dot, const double* Lgain_dot,
+                                          const double* xhat0_dot, const double* model_dot, double* Xhat_dot, double* innov_dot,
+                                          double* nis_dot, double* loglik_dot, double* event_hat_dot) {
+    qln::FilterJvpArgs a{};
+    a.Y_dot = Y_dot; a.Zrec_dot = Zrec_dot; a.Lgain_dot = Lgain_dot; a.xhat0_dot = xhat0_dot; a.model_dot = model_dot;
+    a.Xhat_dot = Xhat_dot; a.innov_dot = innov_dot; a.nis_dot = nis_dot; a.loglik_dot = loglik_dot; a.event_hat_dot = event_hat_dot;
+    return a;
+}
+static qln::FilterVjpArgs filter_vjp_args(const double* Xhat_bar, const double* innov_bar, const double* nis_bar,
+                                          const double* loglik_bar, double* Y_bar, double* Zrec_bar, double* Lgain_bar,
+                                          double* xhat0_bar, double* model_bar) {
+    qln::FilterVjpArgs a{};
+    a.Xhat_bar = Xhat_bar; a.innov_bar = innov_bar; a.nis_bar = nis_bar; a.loglik_bar = loglik_bar; a.Y_bar = Y_bar;
+    a.Zrec_bar = Zrec_bar; a.Lgain_bar = Lgain_bar; a.xhat0_bar = xhat0_bar; a.model_bar = model_bar;
+    return a;
+}
+
+int qln_landing_filter_jvp(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H, int32_t ny,
+                           const double* model, const double* Vdiag, const double* Xhat, const double* innov, const double* Y_dot,
+                           const double* Zrec_dot, const double* Lgain_dot, const double* xhat0_dot, const double* model_dot,
+                           double* Xhat_dot, double* innov_dot, double* nis_dot, double* loglik_dot) {
+    return landing_filter_jvp(h, kDeviceMem, filter_traj(Zref, Zrec, Lgain, H, ny, model, Vdiag, Xhat, innov, false, nullptr),
+                              filter_jvp_args(Y_dot, Zrec_dot, Lgain_dot, xhat0_dot, model_dot, Xhat_dot, innov_dot, nis_dot,
+                                              loglik_dot, nullptr),
+                              "qln_landing_filter_jvp");
+}
+int qln_landing_filter_jvp_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                int32_t ny, const double* model, const double* Vdiag, const double* Xhat, const double* innov,
+                                const double* Y_dot, const double* Zrec_dot, const double* Lgain_dot, const double* xhat0_dot,
+                                const double* model_dot, double* Xhat_dot, double* innov_dot, double* nis_dot, double* loglik_dot) {
+    return landing_filter_jvp(h, kHostMem, filter_traj(Zref, Zrec, Lgain, H, ny, model, Vdiag, Xhat, innov, false, nullptr),
+                              filter_jvp_args(Y_dot, Zrec_dot, Lgain_dot, xhat0_dot, model_dot, Xhat_dot, innov_dot, nis_dot,
+                                              loglik_dot, nullptr),
+                              "qln_landing_filter_jvp_host");
+}
+int qln_landing_filter_guarded_jvp(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                   int32_t ny, const double* model, const double* Vdiag, const double* Xhat, const double* innov,
+                                   const double* event_hat, const double* Y_dot, const double* Zrec_dot, const double* Lgain_dot,
+                                   const double* xhat0_dot, const double* model_dot, double* Xhat_dot, double* innov_dot,
+                                   double* nis_dot, double* loglik_dot, double* event_hat_dot) {
+    return landing_filter_jvp(h, kDeviceMem, filter_traj(Zref, Zrec, Lgain, H, ny, model, Vdiag, Xhat, innov, true, event_hat),
+                              filter_jvp_args(Y_dot, Zrec_dot, Lgain_dot, xhat0_dot, model_dot, Xhat_dot, innov_dot, nis_dot,
+                                              loglik_dot, event_hat_dot),
+                              "qln_landing_filter_guarded_jvp");
+}
+int qln_landing_filter_guarded_jvp_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                        int32_t ny, const double* model, const double* Vdiag, const double* Xhat,
+                                        const double* innov, const double* event_hat, const double* Y_dot, const double* Zrec_dot,
+                                        const double* Lgain_dot, const double* xhat0_dot, const double* model_dot,
+                                        double* Xhat_dot, double* innov_dot, double* nis_dot, double* loglik_dot,
+                                        double* event_hat_dot) {
+    return landing_filter_jvp(h, kHostMem, filter_traj(Zref, Zrec, Lgain, H, ny, model, Vdiag, Xhat, innov, true, event_hat),
+                              filter_jvp_args(Y_dot, Zrec_dot, Lgain_dot, xhat0_dot, model_dot, Xhat_dot, innov_dot, nis_dot,
+                                              loglik_dot, event_hat_dot),
+                              "qln_landing_filter_guarded_jvp_host");
+}
+int qln_landing_filter_vjp(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H, int32_t ny,
+                           const double* model, const double* Vdiag, const double* Xhat, const double* innov,
+                           const double* Xhat_bar, const double* innov_bar, const double* nis_bar, const double* loglik_bar,
+                           double* Y_bar, double* Zrec_bar, double* Lgain_bar, double* xhat0_bar, double* model_bar) {
+    return landing_filter_vjp(h, kDeviceMem, filter_traj(Zref, Zrec, Lgain, H, ny, model, Vdiag, Xhat, innov, false, nullptr),
+                              filter_vjp_args(Xhat_bar, innov_bar, nis_bar, loglik_bar, Y_bar, Zrec_bar, Lgain_bar, xhat0_bar,
+                                              model_bar),
+                              "qln_landing_filter_vjp");
+}
+int qln_landing_filter_vjp_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                int32_t ny, const double* model, const double* Vdiag, const double* Xhat, const double* innov,
+                                const double* Xhat_bar, const double* innov_bar, const double* nis_bar, const double* loglik_bar,
+                                double* Y_bar, double* Zrec_bar, double* Lgain_bar, double* xhat0_bar, double* model_bar) {
+    return landing_filter_vjp(h, kHostMem, filter_traj(Zref, Zrec, Lgain, H, ny, model, Vdiag, Xhat, innov, false, nullptr),
+                              filter_vjp_args(Xhat_bar, innov_bar, nis_bar, loglik_bar, Y_bar, Zrec_bar, Lgain_bar, xhat0_bar,
+                                              model_bar),
+                              "qln_landing_filter_vjp_host");
+}
+int qln_landing_filter_guarded_vjp(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                   int32_t ny, const double* model, const double* Vdiag, const double* Xhat, const double* innov,
+                                   const double* event_hat, const double* Xhat_bar, const double* innov_bar, const double* nis_bar,
+                                   const double* loglik_bar, double* Y_bar, double* Zrec_bar, double* Lgain_bar, double* xhat0_bar,
+                                   double* model_bar) {
+    return landing_filter_vjp(h, kDeviceMem, filter_traj(Zref, Zrec, Lgain, H, ny, model, Vdiag, Xhat, innov, true, event_hat),
+                              filter_vjp_args(Xhat_bar, innov_bar, nis_bar, loglik_bar, Y_bar, Zrec_bar, Lgain_bar, xhat0_bar,
+                                              model_bar),
+                              "qln_landing_filter_guarded_vjp");
+}
+int qln_landing_filter_guarded_vjp_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
+                                        int32_t ny, const double* model, const double* Vdiag, const double* Xhat,
+                                        const double* innov, const double* event_hat, const double* Xhat_bar,
+                                        const double* innov_bar, const double* nis_bar, const double* loglik_bar, double* Y_bar,
+                                        double* Zrec_bar, double* Lgain_bar, double* xhat0_bar, double* model_bar) {
+    return landing_filter_vjp(h, kHostMem, filter_traj(Zref, Zrec, Lgain, H, ny, model, Vdiag, Xhat, innov, true, event_hat),
+                              filter_vjp_args(Xhat_bar, innov_bar, nis_bar, loglik_bar, Y_bar, Zrec_bar, Lgain_bar, xhat0_bar,
+                                              model_bar),
+                              "qln_landing_filter_guarded_vjp_host");
 }
 
 // The estimate-feedback roll-out (k_tracking_rollout_estimated).  The checks that need no handle come first.

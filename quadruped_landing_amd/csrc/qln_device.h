@@ -341,11 +341,34 @@ hipError_t launch_landing_smoother(const BatchParams& p, const double* Ztraj, co
                                    const double* Xhat, const double* innov, double* Xs, double* Ps, hipStream_t stream);
 // The filter on recorded data (qln_landing_filter / _guarded): Zref (state slots read), Zrec (control slots read), Lgain
 // [B][N][15][ny], H [ny][15] and Y [B][N][ny] on the device, Vd (ny) a host array read only when score or loglik is asked for;
-// xhat0 [B][15] may be null; Xhat [B][N][15], innov [B][N][ny], score [B][N][2], loglik [B] and event_hat
+// xhat0 [B][15] may be null; model [B][QLN_MODEL_NP] (null: the handle's) is the model of each record's own
+// (qln_landing_filter_model); Xhat [B][N][15], innov [B][N][ny], score [B][N][2], loglik [B] and event_hat
 // [B][QLN_TOUCHDOWN_INFO_STRIDE] (guarded only) may each be null, not all.
 hipError_t launch_landing_filter(const BatchParams& p, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
-                                 int ny, const double* Vd, const double* Y, const double* xhat0, double* Xhat, double* innov,
-                                 double* score, double* loglik, bool guarded, double* event_hat, hipStream_t stream);
+                                 int ny, const double* Vd, const double* Y, const double* xhat0, const double* model, double* Xhat,
+                                 double* innov, double* score, double* loglik, bool guarded, double* event_hat,
+                                 hipStream_t stream);
+// The sweeps through the filter (qln_landing_filter_jvp / _vjp) at the record and the trajectory the filter
+// produced: Zrec (control slots read), Lgain, H, model (null: the handle's), Xhat; innov with a tangent or cotangent of Lgain or
+// a score term; event_hat (entries 0 and 1 read) selects the guarded blocks.  iv: 1 / V of the score terms (host; V = 1 behind ny).
+struct FilterSweepIn {
+    const double *Zrec, *Lgain, *H;
+    int ny;
+    const double *model, *Xhat, *innov, *event_hat;
+    double iv[QLN_TRACK_NY_MAX];
+};
+// the tangents (null: zero) and the forward sweep's outputs (each may be null, not all)
+struct FilterJvpArgs {
+    const double *Y_dot, *Zrec_dot, *Lgain_dot, *xhat0_dot, *model_dot;
+    double *Xhat_dot, *innov_dot, *nis_dot, *loglik_dot, *event_hat_dot;
+};
+// the cotangents (null: zero) and the reverse sweep's outputs (each may be null, not all)
+struct FilterVjpArgs {
+    const double *Xhat_bar, *innov_bar, *nis_bar, *loglik_bar;
+    double *Y_bar, *Zrec_bar, *Lgain_bar, *xhat0_bar, *model_bar;
+};
+hipError_t launch_landing_filter_jvp(const BatchParams& p, const FilterSweepIn& in, const FilterJvpArgs& a, hipStream_t stream);
+hipError_t launch_landing_filter_vjp(const BatchParams& p, const FilterSweepIn& in, const FilterVjpArgs& a, hipStream_t stream);
 // The roll-out of the plant and the estimator side by side (qln_tracking_rollout_estimated / _guarded): Lgain [B][N][15][ny] and
 // H [ny][15] on the device; vnoise [B][N][ny], wnoise [B][N-1][15], x0, xhat0 [B][15], model and K may be null; Xhat [B][N][15],
 // innov [B][N][ny] may be null; event and event_hat [B][QLN_TOUCHDOWN_INFO_STRIDE] or null, with guarded only.

@@ -98,7 +98,11 @@
 //
 // k_landing_filter: the estimator on recorded data (qln_landing_filter / _guarded): the estimator's half of
 // k_tracking_rollout_estimated, measurements and applied forces read where that kernel forms them, and with kScore the
-// normalised innovation squared, log det S_k and the log-likelihood from the gains alone.
+// normalised innovation squared, log det S_k and the log-likelihood from the gains alone.  kModel: at a model of each record's own.
+//
+// k_landing_filter_jvp / k_landing_filter_vjp: the sweeps through that filter and its score at fixed gains
+// (qln_landing_filter_jvp / _vjp): the estimator's half of k_tracking_rollout_estimated_jvp / _vjp in their row
+// mapping and on their step functions, with a model tangent on that half.
 #include "qln_row16.h"
 
 #include <utility>
@@ -2963,13 +2967,17 @@ constexpr int kFilterTri = filter_tri(QLN_TRACK_NY_MAX - 1, QLN_TRACK_NY_MAX - 1
 // H L_k; then e_k = innov_k - H g, nis_k = sum_r innov_k[r] e_k[r] / V[r], and the L D L' of the lower triangle of
 // diag(1/V) (I - H L_k) without pivoting, right-looking and in place, whose pivots give log det S_k = - sum log d_i (NaN where
 // a pivot is not > 0).  The rows behind ny have a zero row of H and V = 1: pivot 1, log 1 = 0, and zeros everywhere else.
-template <bool kGuard, bool kScore>
+// kModel (qln_landing_filter_model / _guarded_model): the step is taken at the record's own model, model[b].  Its
+// four doubles are read at the step, every knot, behind a hidden address: held over the knots, a lane's own Model would sit
+// beside the score's accumulators, which leave no register free.  A null model there is the handle's four values.
+template <bool kGuard, bool kScore, bool kModel = false>
 __global__ __launch_bounds__(kWave) void k_landing_filter(BatchParams P, SmootherNoise Nz, const double* __restrict__ Hg, int ny,
                                                           const double* __restrict__ Zref, const double* __restrict__ Zrec,
                                                           const double* __restrict__ Lg, const double* __restrict__ Yg,
                                                           const double* __restrict__ xhat0, double* __restrict__ Xhat,
                                                           double* __restrict__ innov_out, double* __restrict__ score,
-                                                          double* __restrict__ loglik, double* __restrict__ event_hat) {
+                                                          double* __restrict__ loglik, double* __restrict__ event_hat,
+                                                          const double* __restrict__ model) {
     constexpr int NY = QLN_TRACK_NY_MAX;
     __shared__ double Hs[NY * 15];
     for (int i = threadIdx.x; i < NY * 15; i += kWave) Hs[i] = i < 15 * ny ? Hg[i] : 0.0;
@@ -2985,7 +2993,7 @@ __global__ __launch_bounds__(kWave) void k_landing_filter(BatchParams P, Smoothe
     if (b >= P.B) return;
     const ProblemDesc pd = P.desc[b];
     const int N = P.N, kt = pd.k_trans, im = pd.init_mode;
-    const Model Mh = plant_model<true>(P, nullptr, b);  // the estimator's: always the handle's
+    [[maybe_unused]] const Model Mh = plant_model<true>(P, nullptr, b);  // the estimator's: the handle's without kModel
     const double* __restrict__ Zr = Zref + (int64_t)b * P.z_stride;
     const double* __restrict__ Zc = Zrec + (int64_t)b * P.z_stride;
     const double* __restrict__ hs = xhat0 ? xhat0 + (int64_t)b * 15 : Zr;
@@ -3118,8 +3126,16 @@ __global__ __launch_bounds__(kWave) void k_landing_filter(BatchParams P, Smoothe
         // the applied forces and the step length are the record's
 #pragma unroll
         for (int i = 0; i < 5; ++i) u[i] = Zc[20 * k + 15 + i];
-        if constexpr (kGuard) guarded_step(Mh, k, mode_hat, xhat, u, xn, tdh);
-        else step_forward(Mh, k, kt, im, xhat, u, xn);
+        if constexpr (kModel) {
+            const double* mp = model;
+            asm volatile("" : "+v"(mp));
+            const Model Mb = plant_model<true>(P, mp, b);
+            if constexpr (kGuard) guarded_step(Mb, k, mode_hat, xhat, u, xn, tdh);
+            else step_forward(Mb, k, kt, im, xhat, u, xn);
+        } else {
+            if constexpr (kGuard) guarded_step(Mh, k, mode_hat, xhat, u, xn, tdh);
+            else step_forward(Mh, k, kt, im, xhat, u, xn);
+        }
 #pragma unroll
         for (int i = 0; i < 15; ++i) xhat[i] = xn[i];
     }
@@ -3138,6 +3154,359 @@ __global__ __launch_bounds__(kWave) void k_landing_filter(BatchParams P, Smoothe
             ev[6] = tdh.fmin;
             ev[7] = 0.0;
         }
+    }
+}
+
+// ---- k_landing_filter_jvp / k_landing_filter_vjp ----
+// The sweeps through the filter (qln_landing_filter_jvp / _vjp, include/qln_evaluator.h): the estimator's half
+// of k_tracking_rollout_estimated_jvp / _vjp in their mapping -- one problem per row of sixteen lanes, lane j holding dxm[j] /
+// lamm[j], H staged once per block, row j of L_k, every knot slice loaded one knot ahead, what is uniform over the row handed
+// round by DPP row broadcasts -- with the model's tangent on that half: the block is estimated_jvp_step<kGuard, true> /
+// estimated_vjp_step<kGuard, true> at (Xhat_k, Zrec's u_k, model[b]).  With no tangent but xhat0's and Lgain's the estimator's
+// chain of the siblings is repeated expression for expression, so a replay of a flight returns their bits.
+// kScore: the tangent and the cotangent of nis_k.  In this mapping g = L_k innov_k and L_k dinnov_k are one fma chain per lane,
+// and H g, H (L_k dinnov_k) and L_k' (H' w) are ny row sums each: nothing is factorised.  V enters as 1 / V, 1 behind ny.
+
+// One knot's inputs of the forward sweep, as lane ln of a row loads them: row j of L_k and of Ldot_k, ivl / ydl: entry ln of
+// innov_k and of Y_dot_k (lanes behind ny repeat the last), for every knot; z0 / z1 and zd0 / zd1: Zrec's and Zrec_dot's knot as
+// knot_load takes it (only the control slots are used), xh: xhat_k[j], for the knots with a step.
+struct FilterJvpKnot {
+    double l[QLN_TRACK_NY_MAX], ld[QLN_TRACK_NY_MAX], ivl, ydl;
+    double z0, z1, xh, zd0, zd1;
+};
+
+template <bool kGuard, bool kHasLd, bool kScore>
+__global__ __launch_bounds__(kWave) void k_landing_filter_jvp(BatchParams P, FilterSweepIn in, FilterJvpArgs a) {
+    static_assert(!(kHasLd && kScore), "the score's tangent is taken at fixed gains");
+    constexpr int NY = QLN_TRACK_NY_MAX;
+    constexpr bool kInnov = kHasLd || kScore;
+    __shared__ double Hs[NY * 15];
+    const int ny = in.ny;
+    for (int i = threadIdx.x; i < 15 * ny; i += kWave) Hs[i] = in.H[i];
+    // 1 / V beside it, read at a hidden offset (k_landing_filter): held in scalar registers over the knots the eight took sixteen
+    [[maybe_unused]] __shared__ double Vs[NY];
+    if constexpr (kScore) {
+#pragma unroll
+        for (int r = 0; r < NY; ++r)
+            if ((int)threadIdx.x == r) Vs[r] = in.iv[r];
+    }
+    __syncthreads();
+    const Row16 r16 = row16_of(P);  // lane 15 reads lane 14's slots and contributes nothing
+    const int ln = r16.ln, j = r16.j, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
+    const bool own = r16.own, valid = r16.valid;
+    const Model M = plant_model<true>(P, in.model, bc);
+    const int64_t zo = (int64_t)bc * P.z_stride, xo = (int64_t)bc * N * QLN_NX, go = xo * ny, io = (int64_t)bc * N * ny;
+    const double* __restrict__ Zc = in.Zrec + zo;
+    const double* __restrict__ Xh = in.Xhat + xo;
+    const double* __restrict__ Zd = a.Zrec_dot ? a.Zrec_dot + zo : nullptr;
+    const double* __restrict__ Yd = a.Y_dot ? a.Y_dot + io : nullptr;
+    const double* __restrict__ Lb = in.Lgain + go + (int64_t)j * ny;
+    const double* __restrict__ Ldb = kHasLd ? a.Lgain_dot + go + (int64_t)j * ny : nullptr;
+    const double* __restrict__ Ib = kInnov ? in.innov + io : nullptr;
+    [[maybe_unused]] int ksh = -1;
+    [[maybe_unused]] double tauh = 0.0;
+    double eh_tau = 0.0, eh_clock = 0.0;
+    if constexpr (kGuard) {
+        ksh = guard_knot(in.event_hat[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc], N);
+        tauh = in.event_hat[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + 1];
+    }
+    double md4[QLN_MODEL_NP] = {0.0, 0.0, 0.0, 0.0};
+    if (a.model_dot) {
+#pragma unroll
+        for (int q = 0; q < QLN_MODEL_NP; ++q) md4[q] = a.model_dot[(int64_t)bc * QLN_MODEL_NP + q];
+    }
+    double* __restrict__ Xd = a.Xhat_dot ? a.Xhat_dot + xo : nullptr;
+    double* __restrict__ Ido = a.innov_dot ? a.innov_dot + io : nullptr;
+    double dxm = (own && a.xhat0_dot) ? a.xhat0_dot[(int64_t)bc * QLN_NX + j] : 0.0;
+    [[maybe_unused]] double lld = 0.0;
+    auto load = [&](FilterJvpKnot& s, int k) {
+        const double* __restrict__ Lk = Lb + (int64_t)k * (15 * ny);
+#pragma unroll
+        for (int r = 0; r < NY; ++r) s.l[r] = r < ny ? Lk[r] : 0.0;
+        if constexpr (kHasLd) {
+            const double* __restrict__ Ldk = Ldb + (int64_t)k * (15 * ny);
+#pragma unroll
+            for (int r = 0; r < NY; ++r) s.ld[r] = r < ny ? Ldk[r] : 0.0;
+        }
+        if constexpr (kInnov) s.ivl = Ib[(int64_t)k * ny + min(ln, ny - 1)];
+        if (Yd) s.ydl = Yd[(int64_t)k * ny + min(ln, ny - 1)];
+        if (k == N - 1) return;
+        knot_load(Zc + 20 * k, ln, s.z0, s.z1);
+        s.xh = Xh[(int64_t)k * QLN_NX + j];
+        if (Zd) knot_load(Zd + 20 * k, ln, s.zd0, s.zd1);
+    };
+    FilterJvpKnot cur = {}, nxt = {};
+    load(nxt, 0);
+    for (int k = 0; k < N; ++k) {
+        // the row count behind a hidden value, once per knot: the eight tests r < ny, held over the step, cost scalar registers
+        int nyk = ny;
+        asm volatile("" : "+s"(nyk));
+        cur = nxt;
+        if (k + 1 < N) load(nxt, k + 1);
+        // ---- the measurement update's tangent: dinnov = Y_dot - H dxm, formed as the siblings form H (dx - dxm) at dx = 0 ----
+        const double dd = 0.0 - dxm;
+        double din[NY];
+        [[maybe_unused]] double yd[NY], iv[NY];
+        if (Yd) row_bcast_first(cur.ydl, yd, std::make_integer_sequence<int, NY>{});
+        if constexpr (kInnov) row_bcast_first(cur.ivl, iv, std::make_integer_sequence<int, NY>{});
+#pragma unroll
+        for (int r = 0; r < NY; ++r) {
+            din[r] = 0.0;
+            if (r < nyk) {
+                din[r] = row_sum16(own ? Hs[15 * r + j] * dd : 0.0);
+                if (Yd) din[r] = yd[r] + din[r];
+            }
+        }
+        double dxh = dxm;
+#pragma unroll
+        for (int r = 0; r < NY; ++r)
+            if (r < nyk) dxh = fma(cur.l[r], din[r], dxh);
+        if constexpr (kHasLd) {
+#pragma unroll
+            for (int r = 0; r < NY; ++r)
+                if (r < nyk) dxh = fma(cur.ld[r], iv[r], dxh);
+        }
+        dxh = own ? dxh : 0.0;
+        if constexpr (kScore) {
+            // e = innov - H (L innov), de = dinnov - H (L dinnov), nis_dot = sum_r (dinnov[r] e[r] + innov[r] de[r]) / V[r]
+            double g = 0.0, gd = 0.0;
+#pragma unroll
+            for (int r = 0; r < NY; ++r)
+                if (r < nyk) {
+                    g = fma(cur.l[r], iv[r], g);
+                    gd = fma(cur.l[r], din[r], gd);
+                }
+            double nd = 0.0;
+            int vo = 0;
+            asm volatile("" : "+v"(vo));
+#pragma unroll
+            for (int r = 0; r < NY; ++r)
+                if (r < nyk) {
+                    const double e = iv[r] - row_sum16(own ? Hs[15 * r + j] * g : 0.0);
+                    const double de = din[r] - row_sum16(own ? Hs[15 * r + j] * gd : 0.0);
+                    nd = fma(fma(din[r], e, iv[r] * de), Vs[vo + r], nd);
+                }
+            lld = lld + nd;
+            if (valid && ln == 0 && a.nis_dot) a.nis_dot[(int64_t)bc * N + k] = nd;
+        }
+        if (valid) {
+            if (Xd && own) Xd[(int64_t)k * QLN_NX + j] = dxh;
+            if (Ido && ln < ny) {
+                int lk = ln;  // hidden, as the lane's index is below
+                asm volatile("" : "+v"(lk));
+                double o = din[0];
+#pragma unroll
+                for (int r = 1; r < NY; ++r) o = (lk == r) ? din[r] : o;
+                Ido[(int64_t)k * ny + ln] = o;
+            }
+        }
+        if (k == N - 1) break;
+        // ---- the estimate and the record's controls, in every lane; the controls' tangent ----
+        const double z0 = cur.z0, z1 = cur.z1;
+        double xe[14];
+        row_bcast_first(cur.xh, xe, std::make_integer_sequence<int, 14>{});
+        const double F1x = row_bcast<15>(z0), F1y = row_bcast<0>(z1), F2x = row_bcast<1>(z1), F2y = row_bcast<2>(z1),
+                     h = row_bcast<3>(z1);
+        double dF[4] = {0.0, 0.0, 0.0, 0.0}, dh = 0.0;
+        if (Zd) {
+            dF[0] = row_bcast<15>(cur.zd0);
+            dF[1] = row_bcast<0>(cur.zd1);
+            dF[2] = row_bcast<1>(cur.zd1);
+            dF[3] = row_bcast<2>(cur.zd1);
+            dh = row_bcast<3>(cur.zd1);
+        }
+        KnotMode mdh;
+        if constexpr (kGuard) mdh = guard_mode(k, ksh, im);
+        else mdh = knot_mode(k + 1, kt - 1, im);
+        // the lane's index behind a hidden value: the block's entries are picked by comparisons with it, and held over the knots
+        // as lane masks those comparisons took more scalar registers than there are
+        int jk = j;
+        asm volatile("" : "+v"(jk));
+        const double acce = estimated_jvp_step<kGuard, true>(jk, own, xe, F1x, F1y, F2x, F2y, h, mdh, k == ksh, tauh, M, dxh, dF, dh,
+                                                             a.model_dot != nullptr, md4, eh_tau, eh_clock);
+        __builtin_amdgcn_sched_barrier(0);
+        dxm = own ? acce : 0.0;
+    }
+    if constexpr (kScore) {
+        if (valid && ln == 0 && a.loglik_dot) a.loglik_dot[bc] = -0.5 * lld;
+    }
+    if constexpr (kGuard) {
+        if (valid && ln < QLN_TOUCHDOWN_INFO_STRIDE && a.event_hat_dot)
+            a.event_hat_dot[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + ln] = (ln == 1) ? eh_tau : (ln == 2) ? eh_clock : 0.0;
+    }
+}
+
+// One knot's inputs of the reverse sweep, as lane ln of a row loads them: row j of L_k, ivl / ibl: entry ln of innov_k and of
+// innov_bar_k, xhb: Xhat_bar_k[j], nb: nis_bar_k (every knot); z0 / z1: Zrec's knot, xh: xhat_k[j] (the knots with a step).
+struct FilterVjpKnot {
+    double l[QLN_TRACK_NY_MAX], ivl, ibl, xhb, nb;
+    double z0, z1, xh;
+};
+
+// The exact transpose of the forward sweep: lamm, the cotangent of dxm_{k+1}, starts at zero behind the last knot, and per knot
+//   k < N-1:  ubar = B^e'lamm,  xhb = Xhat_bar_k + A^e'lamm,  model_bar += G^e'lamm                (k = N-1: xhb = Xhat_bar_k)
+//   ib = innov_bar_k + L_k'xhb + nb_k (G_k + G_k') innov_k,   Lbar_k = xhb innov_k',   lamm = xhb - H'ib
+// with nb_k = nis_bar_k - loglik_bar / 2 and G_k = diag(1/V) (I - H L_k), the full matrix:
+//   ((G + G') innov)[r] = (e[r] / V[r] + w[r]) - (L_k' H' w)[r],   e = innov - H (L_k innov),  w = innov / V.
+// kHasLb: Lgain_bar is asked for.
+template <bool kGuard, bool kHasLb, bool kScore>
+__global__ __launch_bounds__(kWave) void k_landing_filter_vjp(BatchParams P, FilterSweepIn in, FilterVjpArgs a) {
+    static_assert(!(kHasLb && kScore), "the score's cotangent is taken at fixed gains");
+    constexpr int NY = QLN_TRACK_NY_MAX;
+    constexpr bool kInnov = kHasLb || kScore;
+    __shared__ double Hs[NY * 15];
+    const int ny = in.ny;
+    for (int i = threadIdx.x; i < 15 * ny; i += kWave) Hs[i] = in.H[i];
+    // 1 / V beside it, read at a hidden offset (k_landing_filter): held in scalar registers over the knots the eight took sixteen
+    [[maybe_unused]] __shared__ double Vs[NY];
+    if constexpr (kScore) {
+#pragma unroll
+        for (int r = 0; r < NY; ++r)
+            if ((int)threadIdx.x == r) Vs[r] = in.iv[r];
+    }
+    __syncthreads();
+    const Row16 r16 = row16_of(P);  // lane 15 reads lane 14's slots and contributes nothing
+    // A row past the batch's end leaves here, behind the barrier: every cross-lane move below stays inside a row of sixteen, so
+    // the rows that remain lose no source lane, and the flag need not be held over the knots.
+    if (!r16.valid) return;
+    const int ln = r16.ln, j = r16.j, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
+    const bool own = r16.own;
+    constexpr bool valid = true;
+    const Model M = plant_model<true>(P, in.model, bc);
+    const int64_t zo = (int64_t)bc * P.z_stride, xo = (int64_t)bc * N * QLN_NX, go = xo * ny, io = (int64_t)bc * N * ny;
+    const double* __restrict__ Zc = in.Zrec + zo;
+    const double* __restrict__ Xh = in.Xhat + xo;
+    const double* __restrict__ Lb = in.Lgain + go + (int64_t)j * ny;
+    const double* __restrict__ Ib = kInnov ? in.innov + io : nullptr;
+    [[maybe_unused]] int ksh = -1;
+    [[maybe_unused]] double tauh = 0.0;
+    if constexpr (kGuard) {
+        ksh = guard_knot(in.event_hat[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc], N);
+        tauh = in.event_hat[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + 1];
+    }
+    // ---- lane j's constant pattern (k_tracking_rollout_estimated_vjp forms the same) ----
+    const VjpLane lc = vjp_lane(j, M);
+    const int p = lc.pos ? j : j - 7;
+    double e[4], sg[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        e[m] = ((p <= 1 && (m == p || m == p + 2)) || (lc.foot && m == p - 3)) ? 1.0 : 0.0;
+        sg[m] = 0.0;
+    }
+    if (p == 0) sg[1] = sg[3] = -1.0;
+    if (p == 1) sg[0] = sg[2] = 1.0;
+    if (p == 3) sg[1] = 1.0;
+    if (p == 4) sg[0] = -1.0;
+    if (p == 5) sg[3] = 1.0;
+    if (p == 6) sg[2] = -1.0;
+
+    double mbar[QLN_MODEL_NP] = {0.0, 0.0, 0.0, 0.0};  // lane j's share of model_bar
+    const double zero5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    double lamm = 0.0;
+    const double* __restrict__ Xhb = a.Xhat_bar ? a.Xhat_bar + xo : nullptr;
+    const double* __restrict__ Ibb = a.innov_bar ? a.innov_bar + io : nullptr;
+    [[maybe_unused]] const double* __restrict__ Nbb = (kScore && a.nis_bar) ? a.nis_bar + (int64_t)bc * N : nullptr;
+    [[maybe_unused]] const double llb = (kScore && a.loglik_bar) ? a.loglik_bar[bc] : 0.0;
+    double* __restrict__ Zrb = a.Zrec_bar ? a.Zrec_bar + zo : nullptr;
+    double* __restrict__ Ybp = a.Y_bar ? a.Y_bar + io : nullptr;
+    [[maybe_unused]] double* __restrict__ Lgb = kHasLb ? a.Lgain_bar + go + (int64_t)j * ny : nullptr;
+    auto load = [&](FilterVjpKnot& s, int k) {
+        const double* __restrict__ Lk = Lb + (int64_t)k * (15 * ny);
+#pragma unroll
+        for (int r = 0; r < NY; ++r) s.l[r] = r < ny ? Lk[r] : 0.0;
+        if constexpr (kInnov) s.ivl = Ib[(int64_t)k * ny + min(ln, ny - 1)];
+        if (Ibb) s.ibl = Ibb[(int64_t)k * ny + min(ln, ny - 1)];
+        if (Xhb) s.xhb = Xhb[(int64_t)k * QLN_NX + j];
+        if constexpr (kScore) s.nb = Nbb ? Nbb[k] : 0.0;
+        if (k == N - 1) return;
+        knot_load(Zc + 20 * k, ln, s.z0, s.z1);
+        s.xh = Xh[(int64_t)k * QLN_NX + j];
+    };
+    FilterVjpKnot cur = {}, nxt = {};
+    load(nxt, N - 1);
+    for (int k = N - 1; k >= 0; --k) {
+        int nyk = ny, lnk = ln;  // hidden once per knot, as in the forward sweep; the lane's place in the row with it
+        asm volatile("" : "+s"(nyk));
+        asm volatile("" : "+v"(lnk));
+        const bool ownk = lnk < 15;
+        cur = nxt;
+        if (k > 0) load(nxt, k - 1);
+        double xhb = (ownk && Xhb) ? cur.xhb : 0.0;
+        if (k < N - 1) {
+            const double u[5] = {row_bcast<15>(cur.z0), row_bcast<0>(cur.z1), row_bcast<1>(cur.z1), row_bcast<2>(cur.z1),
+                                 row_bcast<3>(cur.z1)};
+            KnotMode mdh;
+            if constexpr (kGuard) mdh = guard_mode(k, ksh, im);
+            else mdh = knot_mode(k + 1, kt - 1, im);
+            double ub[5];
+            // the lane's index and flags behind a hidden value, for the reason given in the forward sweep
+            int jk = j;
+            asm volatile("" : "+v"(jk));
+            VjpLane lk = lc;
+            lk.j = jk;
+            lk.pos = jk < 7;
+            lk.jrow = jk == 4 || jk == 6 || (jk >= 10 && jk <= 13);
+            lk.cpl = jk >= 7 && jk <= 13;
+            lk.kcpl = jk == 11 || jk == 13;
+            const int pk = lk.pos ? jk : jk - 7;
+            lk.foot = (pk == 3 || pk == 4) ? 1 : (pk == 5 || pk == 6) ? 2 : 0;
+            const double axh = estimated_vjp_step<kGuard, true>(lk, e, sg, lnk, ownk, cur.xh, u[0], u[1], u[2], u[3], u[4], mdh, k == ksh,
+                                                                tauh, M, lamm, a.model_bar != nullptr, mbar, zero5, ub);
+            __builtin_amdgcn_sched_barrier(0);
+            xhb = ownk ? xhb + axh : 0.0;
+            if (valid && Zrb) knot_store(Zrb + 20 * k, r16, 0.0, ub);
+        } else if (valid && Zrb && ownk) {
+            Zrb[20 * k + j] = 0.0;  // the last knot has no controls
+        }
+        // ---- the measurement update, transposed ----
+        [[maybe_unused]] double iv[NY], ibr[NY];
+        if constexpr (kInnov) row_bcast_first(cur.ivl, iv, std::make_integer_sequence<int, NY>{});
+        if (Ibb) row_bcast_first(cur.ibl, ibr, std::make_integer_sequence<int, NY>{});
+        [[maybe_unused]] double g = 0.0, hw = 0.0, nbk = 0.0, w[NY];
+        if constexpr (kScore) {
+            nbk = cur.nb - 0.5 * llb;
+            int vo = 0;
+            asm volatile("" : "+v"(vo));
+#pragma unroll
+            for (int r = 0; r < NY; ++r) {
+                w[r] = 0.0;
+                if (r < nyk) {
+                    w[r] = Vs[vo + r];
+                    g = fma(cur.l[r], iv[r], g);
+                    hw = fma(Hs[15 * r + j], iv[r] * w[r], hw);
+                }
+            }
+        }
+        double hib = 0.0, ibo = 0.0;
+#pragma unroll
+        for (int r = 0; r < NY; ++r) {
+            if (r < nyk) {
+                double ib = row_sum16(ownk ? cur.l[r] * xhb : 0.0);
+                if (Ibb) ib = ibr[r] + ib;
+                if constexpr (kScore) {
+                    const double er = iv[r] - row_sum16(ownk ? Hs[15 * r + j] * g : 0.0);
+                    const double lthw = row_sum16(ownk ? cur.l[r] * hw : 0.0);
+                    ib = fma(nbk, fma(er, w[r], iv[r] * w[r]) - lthw, ib);
+                }
+                hib = fma(Hs[15 * r + j], ib, hib);
+                ibo = (lnk == r) ? ib : ibo;
+                if constexpr (kHasLb) {
+                    if (valid && ownk) Lgb[(int64_t)k * (15 * ny) + r] = xhb * iv[r];
+                }
+            }
+        }
+        if (valid && Ybp && lnk < nyk) Ybp[(int64_t)k * ny + ln] = ibo;
+        lamm = ownk ? xhb - hib : 0.0;
+    }
+    if (valid && own && a.xhat0_bar) a.xhat0_bar[(int64_t)bc * QLN_NX + j] = lamm;
+    if (a.model_bar) {
+        double out = 0.0;
+#pragma unroll
+        for (int q = 0; q < QLN_MODEL_NP; ++q) {
+            const double sq = row_sum16(mbar[q]);
+            out = (ln == q) ? sq : out;
+        }
+        if (valid && ln < QLN_MODEL_NP) a.model_bar[(int64_t)bc * QLN_MODEL_NP + ln] = out;
     }
 }
 
@@ -3305,11 +3674,12 @@ hipError_t launch_landing_smoother(const BatchParams& p, const double* Ztraj, co
     return hipGetLastError();
 }
 
-// The four instantiations of k_landing_filter: the knot schedule or the guard, and the score (score or loglik asked for, which
-// needs Vd) or not.
+// The eight instantiations of k_landing_filter: the knot schedule or the guard, the score (score or loglik asked for, which
+// needs Vd) or not, and the record's own model (model given) or the handle's.
 hipError_t launch_landing_filter(const BatchParams& p, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
-                                 int ny, const double* Vd, const double* Y, const double* xhat0, double* Xhat, double* innov,
-                                 double* score, double* loglik, bool guarded, double* event_hat, hipStream_t stream) {
+                                 int ny, const double* Vd, const double* Y, const double* xhat0, const double* model, double* Xhat,
+                                 double* innov, double* score, double* loglik, bool guarded, double* event_hat,
+                                 hipStream_t stream) {
     if (ny < 1 || ny > QLN_TRACK_NY_MAX || !H || !Lgain || !Y || !Zref || !Zrec) return hipErrorInvalidValue;
     if (!guarded && event_hat) return hipErrorInvalidValue;
     if (!Xhat && !innov && !score && !loglik && !event_hat) return hipErrorInvalidValue;
@@ -3319,12 +3689,54 @@ hipError_t launch_landing_filter(const BatchParams& p, const double* Zref, const
     for (int r = 0; r < QLN_TRACK_NY_MAX; ++r) nz.iv[r] = (scored && r < ny) ? 1.0 / Vd[r] : 1.0;
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3((p.B + kWave - 1) / kWave), dim3(kWave), 0, stream, p, nz, H, ny, Zref, Zrec, Lgain, Y, xhat0,
-                           Xhat, innov, score, loglik, event_hat);
+                           Xhat, innov, score, loglik, event_hat, model);
     };
-    if (scored)
+    if (model) {
+        if (scored)
+            guarded ? go(k_landing_filter<true, true, true>) : go(k_landing_filter<false, true, true>);
+        else
+            guarded ? go(k_landing_filter<true, false, true>) : go(k_landing_filter<false, false, true>);
+    } else if (scored)
         guarded ? go(k_landing_filter<true, true>) : go(k_landing_filter<false, true>);
     else
         guarded ? go(k_landing_filter<true, false>) : go(k_landing_filter<false, false>);
+    return hipGetLastError();
+}
+
+// The sweeps through the filter: six instantiations each -- the knot schedule or the guard (event_hat given), and a tangent /
+// cotangent of Lgain, a score term, or neither (the first two exclude each other: the score is differentiated at fixed gains).
+static bool filter_sweep_in_ok(const FilterSweepIn& in, bool want_innov) {
+    return in.ny >= 1 && in.ny <= QLN_TRACK_NY_MAX && in.Zrec && in.Lgain && in.H && in.Xhat && (!want_innov || in.innov);
+}
+
+hipError_t launch_landing_filter_jvp(const BatchParams& p, const FilterSweepIn& in, const FilterJvpArgs& a, hipStream_t stream) {
+    const bool score = a.nis_dot || a.loglik_dot;
+    if (!filter_sweep_in_ok(in, a.Lgain_dot || score) || (a.Lgain_dot && score)) return hipErrorInvalidValue;
+    if (!a.Y_dot && !a.Zrec_dot && !a.Lgain_dot && !a.xhat0_dot && !a.model_dot) return hipErrorInvalidValue;
+    if (!a.Xhat_dot && !a.innov_dot && !score && !a.event_hat_dot) return hipErrorInvalidValue;
+    if (!in.event_hat && a.event_hat_dot) return hipErrorInvalidValue;
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, in, a); };
+    auto pick = [&](auto guard) {
+        if (a.Lgain_dot) go(k_landing_filter_jvp<guard(), true, false>);
+        else if (score) go(k_landing_filter_jvp<guard(), false, true>);
+        else go(k_landing_filter_jvp<guard(), false, false>);
+    };
+    in.event_hat ? pick(std::true_type{}) : pick(std::false_type{});
+    return hipGetLastError();
+}
+
+hipError_t launch_landing_filter_vjp(const BatchParams& p, const FilterSweepIn& in, const FilterVjpArgs& a, hipStream_t stream) {
+    const bool score = a.nis_bar || a.loglik_bar;
+    if (!filter_sweep_in_ok(in, a.Lgain_bar || score) || (a.Lgain_bar && score)) return hipErrorInvalidValue;
+    if (!a.Xhat_bar && !a.innov_bar && !score) return hipErrorInvalidValue;
+    if (!a.Y_bar && !a.Zrec_bar && !a.Lgain_bar && !a.xhat0_bar && !a.model_bar) return hipErrorInvalidValue;
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, in, a); };
+    auto pick = [&](auto guard) {
+        if (a.Lgain_bar) go(k_landing_filter_vjp<guard(), true, false>);
+        else if (score) go(k_landing_filter_vjp<guard(), false, true>);
+        else go(k_landing_filter_vjp<guard(), false, false>);
+    };
+    in.event_hat ? pick(std::true_type{}) : pick(std::false_type{});
     return hipGetLastError();
 }
 

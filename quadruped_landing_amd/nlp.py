@@ -1306,7 +1306,8 @@ class HybridNLP:
         return self._smoother_host(True, Ztraj, events, Lgain, Pest, H, V, Xhat, innov, model, with_states, with_cov)
 
     # -- the filter on recorded data, and the score of the data under it -------------------------------
-    def _filter(self, guarded, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, with_events):
+    def _filter(self, guarded, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, with_events,
+                model=None):
         T = _torch()
         score = (V is not None) if with_score is None else with_score
         if score and V is None:
@@ -1326,16 +1327,20 @@ class HybridNLP:
         Xh, iv = new(with_estimate, (self.B, self.N, n)), new(with_innovations, (self.B, self.N, ny))
         sc, ll = new(score, (self.B, self.N, 2)), new(score, (self.B,))
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        args = (self._h, zr, zc, lp, Hd.data_ptr(), ny, None if Vh is None else Vh.ctypes.data, yp, hp, ptr(Xh), ptr(iv), ptr(sc),
-                ptr(ll))
+        # model None: the existing entries; a model of each record's own: the _model entries, model behind ny
+        mp = () if model is None else (self._check(model, self.B * _lib.MODEL_NP, "model"),)
+        sfx = "" if model is None else "_model"
+        args = (self._h, zr, zc, lp, Hd.data_ptr(), ny, *mp, None if Vh is None else Vh.ctypes.data, yp, hp, ptr(Xh), ptr(iv),
+                ptr(sc), ptr(ll))
         if not guarded:
-            _lib.check(_lib.lib().qln_landing_filter(*args))
+            _lib.check(getattr(_lib.lib(), "qln_landing_filter" + sfx)(*args))
             return Xh, iv, sc, ll
         eh = new(with_events, (self.B, _lib.TOUCHDOWN_INFO_STRIDE))
-        _lib.check(_lib.lib().qln_landing_filter_guarded(*args, ptr(eh)))
+        _lib.check(getattr(_lib.lib(), "qln_landing_filter_guarded" + sfx)(*args, ptr(eh)))
         return Xh, iv, sc, ll, eh
 
-    def _filter_host(self, guarded, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, with_events):
+    def _filter_host(self, guarded, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, with_events,
+                     model=None):
         score = (V is not None) if with_score is None else with_score
         if score and V is None:
             raise ValueError("V is required with with_score: the measurement variances the gains were designed for")
@@ -1356,13 +1361,16 @@ class HybridNLP:
         iv = np.zeros((self.B, self.N, ny)) if with_innovations else None
         sc = np.zeros((self.B, self.N, 2)) if score else None
         ll = np.zeros(self.B) if score else None
-        args = (self._h, Zref.ctypes.data, Zrec.ctypes.data, Lg.ctypes.data, Hh.ctypes.data, ny, _host_ptr(Vh), Yh.ctypes.data,
+        mh = self._host_model(model)
+        mp = () if mh is None else (mh.ctypes.data,)
+        sfx = "" if mh is None else "_model"
+        args = (self._h, Zref.ctypes.data, Zrec.ctypes.data, Lg.ctypes.data, Hh.ctypes.data, ny, *mp, _host_ptr(Vh), Yh.ctypes.data,
                 _host_ptr(xhat0), _host_ptr(Xh), _host_ptr(iv), _host_ptr(sc), _host_ptr(ll))
         if not guarded:
-            _lib.check(_lib.lib().qln_landing_filter_host(*args))
+            _lib.check(getattr(_lib.lib(), f"qln_landing_filter{sfx}_host")(*args))
             return Xh, iv, sc, ll
         eh = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if with_events else None
-        _lib.check(_lib.lib().qln_landing_filter_guarded_host(*args, _host_ptr(eh)))
+        _lib.check(getattr(_lib.lib(), f"qln_landing_filter_guarded{sfx}_host")(*args, _host_ptr(eh)))
         return Xh, iv, sc, ll, eh
 
     def landing_measurements(self, Zout, Zref, H, vnoise=None):
@@ -1376,7 +1384,7 @@ class HybridNLP:
         return landing_measurements(zo, zr, H, vnoise)
 
     def landing_filter(self, Zref, Zrec, Lgain, H, Y, V=None, xhat0=None, with_estimate=True, with_innovations=True,
-                       with_score=None):
+                       with_score=None, model=None):
         """The estimator of tracking_rollout_estimated run on a RECORD: measurements Y (B, N, ny) in the roll-out's form (the
         reading minus H x_ref,k: landing_measurements) and the forces that were applied, the control slots of Zrec -- its state
         slots are not read, and of Zref only the state slots are.  Lgain (B, N, 15, ny) are tracking_kalman's gains, xhat0
@@ -1385,24 +1393,136 @@ class HybridNLP:
         score (B, N, 2) = {nis_k, log det S_k} and loglik (B,), the Gaussian log-likelihood, from the gains alone -- which the
         call cannot check belong to V (qln_evaluator.h).  Device tensors in; returns (Xhat, innov, score, loglik), each None
         unless asked for; which are asked for does not change the others' bits.  A replay of a flight returns its Xhat and
-        innov.  Stream-ordered."""
-        return self._filter(False, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, False)
+        innov.  model (B, 4) = {g, mb, mf, lb} per record sends the prediction to a model of each record's own
+        (qln_landing_filter_model); None is the handle's, and the existing entry.  Stream-ordered."""
+        return self._filter(False, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, False, model)
 
     def landing_filter_host(self, Zref, Zrec, Lgain, H, Y, V=None, xhat0=None, with_estimate=True, with_innovations=True,
-                            with_score=None):
+                            with_score=None, model=None):
         """The same with host arrays (synchronous): numpy (Xhat, innov, score, loglik).  A non-finite H is refused."""
-        return self._filter_host(False, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, False)
+        return self._filter_host(False, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, False,
+                                 model)
 
     def landing_filter_guarded(self, Zref, Zrec, Lgain, H, Y, V=None, xhat0=None, with_estimate=True, with_innovations=True,
-                               with_score=None, with_events=True):
+                               with_score=None, with_events=True, model=None):
         """landing_filter with the estimator landing by its own guard, as in tracking_rollout_estimated(guarded=True): returns
         (Xhat, innov, score, loglik, events_hat), events_hat (B, 8) the estimator's touchdown records."""
-        return self._filter(True, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, with_events)
+        return self._filter(True, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, with_events,
+                            model)
 
     def landing_filter_guarded_host(self, Zref, Zrec, Lgain, H, Y, V=None, xhat0=None, with_estimate=True,
-                                    with_innovations=True, with_score=None, with_events=True):
+                                    with_innovations=True, with_score=None, with_events=True, model=None):
         """The same with host arrays (synchronous): numpy (Xhat, innov, score, loglik, events_hat)."""
-        return self._filter_host(True, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, with_events)
+        return self._filter_host(True, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, with_events,
+                                 model)
+
+    # -- the sweeps through the filter: tangents and cotangents of Xhat, innov, nis and loglik ----------
+    FILTER_JVP_OUT = ("Xhat", "innov", "nis", "loglik", "event_hat")
+    FILTER_VJP_OUT = ("Y", "Zrec", "Lgain", "xhat0", "model")
+
+    def _filter_sweep(self, host, forward, guarded, Zref, Zrec, Lgain, H, Xhat, innov, V, model, events_hat, given, want):
+        """One path for the four forms.  given: the tangents (forward) or cotangents by name, None for absent; want: the outputs
+        by name.  Returns a dict of the outputs asked for."""
+        T = None if host else _torch()
+        if guarded and events_hat is None:
+            raise ValueError("events_hat is required: the record landing_filter_guarded returned")
+        Hh, Vh = measurement_model(H, V) if V is not None else (self._measurement_rows(H), None)
+        ny = Hh.shape[0]
+        B, N = self.B, self.N
+        sizes = dict(Xhat=B * N * n, innov=B * N * ny, nis=B * N, loglik=B, event_hat=B * _lib.TOUCHDOWN_INFO_STRIDE,
+                     Y=B * N * ny, Zrec=self.dims.z_total, Lgain=B * N * n * ny, xhat0=B * n, model=B * _lib.MODEL_NP)
+        shapes = dict(Xhat=(B, N, n), innov=(B, N, ny), nis=(B, N), loglik=(B,), event_hat=(B, _lib.TOUCHDOWN_INFO_STRIDE),
+                      Y=(B, N, ny), Zrec=(self.dims.z_total,), Lgain=(B, N, n, ny), xhat0=(B, n), model=(B, _lib.MODEL_NP))
+        outs = self.FILTER_JVP_OUT if forward else self.FILTER_VJP_OUT
+        bad = set(want) - set(outs)
+        if bad or (not guarded and "event_hat" in want):
+            raise ValueError(f"want: unknown outputs {sorted(bad)} ({', '.join(outs)}; event_hat with guarded only)")
+
+        if host:
+            def inp(a, size, name):
+                if a is None:
+                    return None
+                a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
+                if a.size < size:
+                    raise ValueError(f"{name} has {a.size} entries, expected {size}")
+                return a
+            ptr = _host_ptr
+            new = lambda name: np.zeros(shapes[name])  # noqa: E731
+            Hd = Hh
+        else:
+            def inp(a, size, name):
+                return None if a is None else (self._check(a, size, name), a)[1]
+            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+            new = lambda name: T.zeros(shapes[name], dtype=T.float64, device=self._dev())  # noqa: E731
+            Hd = T.from_numpy(Hh).to(self._dev())
+        for name, a in (("Zref", Zref), ("Zrec", Zrec), ("Lgain", Lgain), ("Xhat", Xhat)):
+            if a is None:
+                raise ValueError(f"{name} is required: the record and the trajectory landing_filter produced")
+        keep = [inp(Zref, self.dims.z_total, "Zref"), inp(Zrec, self.dims.z_total, "Zrec"), inp(Lgain, sizes["Lgain"], "Lgain"),
+                inp(model, sizes["model"], "model"), inp(Xhat, sizes["Xhat"], "Xhat"), inp(innov, sizes["innov"], "innov")]
+        ev = inp(events_hat, sizes["event_hat"], "events_hat") if guarded else None
+        gnames = ("Y", "Zrec", "Lgain", "xhat0", "model") if forward else ("Xhat", "innov", "nis", "loglik")
+        gin = [inp(given.get(k), sizes[k], k + ("_dot" if forward else "_bar")) for k in gnames]
+        res = {k: new(k) for k in outs if k in want}
+        hp = Hd.ctypes.data if host else Hd.data_ptr()
+        args = [self._h, ptr(keep[0]), ptr(keep[1]), ptr(keep[2]), hp, ny, ptr(keep[3]), _host_ptr(Vh), ptr(keep[4]), ptr(keep[5])]
+        if guarded:
+            args.append(ptr(ev))
+        args += [ptr(g) for g in gin]
+        args += [ptr(res.get(k)) for k in outs if guarded or k != "event_hat"]
+        fn = "qln_landing_filter" + ("_guarded" if guarded else "") + ("_jvp" if forward else "_vjp") + ("_host" if host else "")
+        _lib.check(getattr(_lib.lib(), fn)(*args))
+        return res
+
+    def _filter_jvp_want(self, want, V, Lgain_dot, guarded):
+        if want is not None:
+            return tuple(want)
+        score = V is not None and Lgain_dot is None
+        return ("Xhat", "innov") + (("nis", "loglik") if score else ()) + (("event_hat",) if guarded else ())
+
+    def landing_filter_jvp(self, Zref, Zrec, Lgain, H, Xhat, innov=None, V=None, model=None, events_hat=None, guarded=False,
+                           Y_dot=None, Zrec_dot=None, Lgain_dot=None, xhat0_dot=None, model_dot=None, want=None):
+        """Forward sweep of landing_filter(model=...) at the record and the trajectory it produced (qln_landing_filter_jvp;
+        guarded: through the estimator's own touchdown, at the knot and tau of events_hat).  Tangents (each optional, at least
+        one): Y_dot (B, N, ny), Zrec_dot in the layout of Z (control slots read), Lgain_dot, xhat0_dot (B, 15), model_dot (B, 4).
+        want: the outputs by name, of Xhat, innov, nis, loglik and (guarded) event_hat; default Xhat and innov, the score's
+        two when V is given and Lgain_dot is not, and event_hat when guarded.  loglik's tangent is the exact derivative AT FIXED
+        GAINS, so a score term together with Lgain_dot is refused; innov is needed with Lgain_dot or a score term.  Returns a
+        dict of device tensors.  Stream-ordered."""
+        given = dict(Y=Y_dot, Zrec=Zrec_dot, Lgain=Lgain_dot, xhat0=xhat0_dot, model=model_dot)
+        return self._filter_sweep(False, True, guarded, Zref, Zrec, Lgain, H, Xhat, innov, V, model, events_hat, given,
+                                  self._filter_jvp_want(want, V, Lgain_dot, guarded))
+
+    def landing_filter_jvp_host(self, Zref, Zrec, Lgain, H, Xhat, innov=None, V=None, model=None, events_hat=None, guarded=False,
+                                Y_dot=None, Zrec_dot=None, Lgain_dot=None, xhat0_dot=None, model_dot=None, want=None):
+        """The same with host arrays (synchronous): a dict of numpy arrays."""
+        given = dict(Y=Y_dot, Zrec=Zrec_dot, Lgain=Lgain_dot, xhat0=xhat0_dot, model=model_dot)
+        return self._filter_sweep(True, True, guarded, Zref, Zrec, Lgain, H, Xhat, innov, V, model, events_hat, given,
+                                  self._filter_jvp_want(want, V, Lgain_dot, guarded))
+
+    def _filter_vjp_want(self, want, innov, nis_bar, loglik_bar):
+        if want is not None:
+            return tuple(want)
+        gain = innov is not None and nis_bar is None and loglik_bar is None
+        return ("Y", "Zrec") + (("Lgain",) if gain else ()) + ("xhat0", "model")
+
+    def landing_filter_vjp(self, Zref, Zrec, Lgain, H, Xhat, innov=None, V=None, model=None, events_hat=None, guarded=False,
+                           Xhat_bar=None, innov_bar=None, nis_bar=None, loglik_bar=None, want=None):
+        """Reverse sweep, the exact transpose of landing_filter_jvp (qln_landing_filter_vjp).  Cotangents (each optional, at
+        least one): Xhat_bar (B, N, 15), innov_bar (B, N, ny), nis_bar (B, N), loglik_bar (B,).  want: the outputs by name, of
+        Y, Zrec (layout of Z: the controls' cotangents, exact zeros in the state slots), Lgain, xhat0 and model; default all
+        that the call can give (Lgain only with innov and without a score cotangent: the score is differentiated at fixed
+        gains).  With loglik_bar = 1 the outputs are the gradient of the log-likelihood.  Returns a dict of device tensors."""
+        given = dict(Xhat=Xhat_bar, innov=innov_bar, nis=nis_bar, loglik=loglik_bar)
+        return self._filter_sweep(False, False, guarded, Zref, Zrec, Lgain, H, Xhat, innov, V, model, events_hat, given,
+                                  self._filter_vjp_want(want, innov, nis_bar, loglik_bar))
+
+    def landing_filter_vjp_host(self, Zref, Zrec, Lgain, H, Xhat, innov=None, V=None, model=None, events_hat=None, guarded=False,
+                                Xhat_bar=None, innov_bar=None, nis_bar=None, loglik_bar=None, want=None):
+        """The same with host arrays (synchronous): a dict of numpy arrays."""
+        given = dict(Xhat=Xhat_bar, innov=innov_bar, nis=nis_bar, loglik=loglik_bar)
+        return self._filter_sweep(True, False, guarded, Zref, Zrec, Lgain, H, Xhat, innov, V, model, events_hat, given,
+                                  self._filter_vjp_want(want, innov, nis_bar, loglik_bar))
 
     # -- the estimate-feedback roll-out: the plant and the estimator flown together -------------------
     @staticmethod
@@ -2014,6 +2134,20 @@ class HybridNLP:
         if model is None:
             return RolloutFunction.apply(self, Zref, K, x0)
         return ModelRolloutFunction.apply(self, Zref, K, x0, model)
+
+    def differentiable_landing_filter(self, Zref, Lgain, H, Vdiag=None, guarded=False):
+        """The filter on recorded data as a torch autograd op: returns f with f(Y, Zrec, xhat0=None, model=None) ->
+        (Xhat, innov) or, with Vdiag, (Xhat, innov, loglik); guarded, the estimator's event record follows, non-differentiable.
+        Reverse mode is landing_filter_vjp and forward mode (torch.autograd.forward_ad) landing_filter_jvp, bit for bit, at the
+        trajectory the forward produced.  Y, Zrec (its control slots), xhat0 and model are differentiable; Lgain -- pass a tensor
+        that requires grad -- only when Vdiag is None, that is without the loglik output: the likelihood is differentiated AT
+        FIXED GAINS (log det S_k depends on the gains; qln_evaluator.h), and with Vdiag a gradient or tangent of Lgain raises."""
+        from .rollout_grad import LandingFilterFunction
+
+        def f(Y, Zrec, xhat0=None, model=None):
+            return LandingFilterFunction.apply(self, Y, Zrec, xhat0, model, Lgain, Zref, H, Vdiag, bool(guarded))
+
+        return f
 
     def differentiable_estimated_rollout(self, Zref, K, Lgain, H, vnoise=None, wnoise=None, x0=None, xhat0=None, model=None,
                                          guarded=False, limits=None):

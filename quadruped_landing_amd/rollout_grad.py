@@ -303,3 +303,69 @@ class EstimatedLimitedRolloutFunction(torch.autograd.Function):
                                                                  kd, ld, xd, hd if ctx.has_xhat0 else None, md,
                                                                  with_event_dot=False)
             return (*out[:3], *none)
+
+
+class LandingFilterFunction(torch.autograd.Function):
+    """(Xhat, innov[, loglik][, events_hat]) = landing filter(Y, Zrec, xhat0, model, Lgain; Zref, H, V, guarded):
+    qln_landing_filter_model / _guarded_model on a record.  xhat0 and model may be None.  Xhat, innov and loglik are
+    differentiable in Y, Zrec (its control slots), xhat0 and model through qln_landing_filter_vjp / _jvp at the trajectory the
+    forward produced: at fixed gains and (guarded) fixed touchdown knot.  Lgain is differentiable only without V, that is without
+    the loglik output: log det S_k depends on the gains and its derivative is not offered.  Zref and H take no gradient, and the
+    event record is marked non-differentiable."""
+
+    @staticmethod
+    def forward(nlp, Y, Zrec, xhat0, model, Lgain, Zref, H, V, guarded):
+        Y, Zrec, xhat0, model, Lgain, Zref = _launchable((Y, Zrec, xhat0, model, Lgain, Zref))
+        f = nlp.landing_filter_guarded if guarded else nlp.landing_filter
+        Xhat, innov, _, loglik, *events = f(Zref, Zrec, Lgain, H, Y, V, xhat0, model=model)
+        return (Xhat, innov, *(() if V is None else (loglik,)), *events)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        nlp, Y, Zrec, xhat0, model, Lgain, Zref, H, V, guarded = inputs
+        ctx.nlp, ctx.H, ctx.V, ctx.guarded = nlp, H, V, guarded
+        ctx.shapes = [None if t is None else t.shape for t in (Y, Zrec, xhat0, model, Lgain)]
+        ctx.set_materialize_grads(False)  # an absent cotangent or tangent stays None: the sweeps tell absent from zero
+        Xhat, innov, *rest = output
+        events = rest[-1:] if guarded else []
+        ctx.mark_non_differentiable(*events)
+        ctx.save_for_backward(Zrec, model, Lgain, Zref, Xhat, innov, *events)
+        ctx.save_for_forward(Zrec, model, Lgain, Zref, Xhat, innov, *events)
+
+    @staticmethod
+    def backward(ctx, Xhat_bar, innov_bar, *rest):
+        need = ctx.needs_input_grad[1:6]
+        score = ctx.V is not None
+        if score and need[4]:
+            raise RuntimeError("Lgain is differentiable only without V: the score is differentiated at fixed gains")
+        loglik_bar = rest[0] if score else None
+        names = ("Y", "Zrec", "xhat0", "model", "Lgain")
+        want = [w for w, on, shape in zip(names, need, ctx.shapes) if on and shape is not None]
+        if not want or all(t is None for t in (Xhat_bar, innov_bar, loglik_bar)):
+            return (None,) * 10
+        saved = [_plain(t) for t in (*ctx.saved_tensors, Xhat_bar, innov_bar, loglik_bar)]
+        with torch._C._DisableFuncTorch():
+            Zrec, model, Lgain, Zref, Xhat, innov, *tail = _launchable(saved)
+            *events, Xhat_bar, innov_bar, loglik_bar = tail
+            got = ctx.nlp.landing_filter_vjp(Zref, Zrec, Lgain, ctx.H, Xhat, innov, ctx.V, model, events[0] if events else None,
+                                             ctx.guarded, Xhat_bar, innov_bar, None, loglik_bar, want)
+            bars = [got[w].reshape(shape) if w in got else None for w, shape in zip(names, ctx.shapes)]
+        return (None, *bars, None, None, None, None)
+
+    @staticmethod
+    def jvp(ctx, _, *dots):
+        Zrec, model, Lgain, Zref, Xhat, innov, *events = (_plain(t) for t in ctx.saved_tensors)
+        score = ctx.V is not None
+        none = (None,) * len(events)
+        with torch._C._DisableFuncTorch():
+            Zrec, model, Lgain, Zref, Xhat, innov, *events = _launchable((Zrec, model, Lgain, Zref, Xhat, innov, *events))
+            yd, zd, xd, md, ld = _launchable(_plain(t) for t in dots[:5])
+            if score and ld is not None:
+                raise RuntimeError("Lgain is differentiable only without V: the score is differentiated at fixed gains")
+            zeros = (torch.zeros_like(Xhat), torch.zeros_like(innov), *((torch.zeros_like(Xhat[:, 0, 0]),) if score else ()))
+            if all(t is None for t in (yd, zd, xd, md, ld)):
+                return (*zeros, *none)
+            want = ("Xhat", "innov") + (("loglik",) if score else ())
+            got = ctx.nlp.landing_filter_jvp(Zref, Zrec, Lgain, ctx.H, Xhat, innov, ctx.V, model, events[0] if events else None,
+                                             ctx.guarded, yd, zd, ld, xd, md, want)
+            return (*(got[w] for w in want), *none)
