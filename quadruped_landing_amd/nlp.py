@@ -8,6 +8,7 @@ include/qln_evaluator.h -- there is no CPU implementation of the arithmetic here
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -247,6 +248,190 @@ def _torch():
 def _host_ptr(a):
     """The address of a host array for the C ABI, None (NULL) for an optional argument left out."""
     return None if a is None else a.ctypes.data
+
+
+class _DeviceForm:
+    """The device memory form of the tracking and landing operations of HybridNLP, and with _HostForm everything in which the
+    two forms of an operation differ: how an input is checked, how an output is allocated, whether H is staged on the device,
+    the address an array is passed by, the entry point's suffix and the sibling calls a message names.  Here: inputs are
+    contiguous float64 CUDA tensors on the handle's device holding at least the elements the operation reads (TypeError /
+    ValueError of HybridNLP._check), outputs are fresh tensors or the caller's, checked like inputs."""
+
+    suffix = ""
+    MEASUREMENTS = " (landing_measurements)"
+    TRAJ = "Lgain and Xhat are required: the filter gains and the estimates tracking_rollout_estimated returned"
+    INNOV = "innov is required with a tangent or cotangent of Lgain (with_innovations=True in the roll-out)"
+    RECORDS = "events and events_hat are required: the two records tracking_rollout_estimated returned"
+
+    def __init__(self, nlp):
+        self.nlp, self.check = nlp, nlp._check
+
+    def fn(self, name):
+        return getattr(_lib.lib(), name)
+
+    @staticmethod
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+
+    def arr(self, t, size, name):
+        self.check(t, size, name)
+        return t
+
+    def opt(self, t, size, name):
+        if t is not None:
+            self.check(t, size, name)
+        return t
+
+    loose = opt  # the filter's sweeps: the host form differs
+
+    def Z(self, t, name):
+        return self.arr(t, self.nlp.dims.z_total, name)
+
+    def Z_opt(self, t, name):
+        return self.opt(t, self.nlp.dims.z_total, name)
+
+    def K(self, t, name="K"):
+        return self.opt(t, self.nlp.B * (self.nlp.N - 1) * _lib.TRACK_NU * n, name)
+
+    def x0(self, t, name="x0"):
+        return self.opt(t, self.nlp.B * n, name)
+
+    def model(self, t, name="model"):
+        return self.opt(t, self.nlp.B * _lib.MODEL_NP, name)
+
+    def events(self, t):
+        if t is None:
+            raise ValueError("events is required: the record tracking_rollout_guarded returned with Zout")
+        return self.arr(t, self.nlp.B * _lib.TOUCHDOWN_INFO_STRIDE, "events")
+
+    def events_hat(self, t):
+        return self.arr(t, self.nlp.B * _lib.TOUCHDOWN_INFO_STRIDE, "events_hat")
+
+    def sat(self, t):
+        if t is None:
+            raise ValueError("sat is required: the saturation record tracking_rollout_limited returned with Zout")
+        return self.arr(t, self.nlp.B * (self.nlp.N - 1), "sat")
+
+    def H(self, Hh):
+        return _torch().from_numpy(Hh).to(self.nlp._dev())
+
+    def sigma0(self, Sigma0):
+        """Sigma0 in any form of tracking_sigma0, or a CUDA tensor of 1 or B packed tiles -> (device tensor, sigma0_batch)."""
+        T = _torch()
+        if Sigma0 is None:
+            raise ValueError("Sigma0 is required")
+        if isinstance(Sigma0, T.Tensor) and Sigma0.is_cuda:
+            nb = Sigma0.numel() // _lib.TRACK_P_NNZ
+            if Sigma0.numel() != nb * _lib.TRACK_P_NNZ or nb not in (1, self.nlp.B):
+                raise ValueError("a device Sigma0 must hold 1 or B packed tiles of 120")
+            s0 = Sigma0
+        else:
+            host, nb = tracking_sigma0(Sigma0, self.nlp.B)
+            s0 = T.from_numpy(host).to(self.nlp._dev())
+        self.check(s0, nb * _lib.TRACK_P_NNZ, "Sigma0")
+        return s0, nb
+
+    def zeros(self, shape, want=True):
+        T = _torch()
+        return T.zeros(shape, dtype=T.float64, device=self.nlp._dev()) if want else None
+
+    def empty(self, shape, want=True):
+        T = _torch()
+        return T.empty(shape, dtype=T.float64, device=self.nlp._dev()) if want else None
+
+    def out(self, t, shape, name, empty=False):
+        """The caller's buffer, or a fresh one (empty: one the operation writes whole), checked"""
+        if t is None:
+            t = self.empty(shape) if empty else self.zeros(shape)
+        self.check(t, math.prod(shape), name)
+        return t
+
+
+class _HostForm:
+    """The host memory form (synchronous): inputs are anything numpy reads, flattened to contiguous float64 of exactly the
+    expected size (ValueError), a Z given as (B, n_nlp) rows is padded to the handle's z_stride, x0 and its like broadcast to
+    (B, 15); outputs are fresh zeroed arrays, never the caller's; H is used in place; the entry point is the _host one."""
+
+    suffix = "_host"
+    MEASUREMENTS = ""
+    TRAJ = "Lgain and Xhat are required: what tracking_rollout_estimated_host took and returned"
+    INNOV = "innov is required with a tangent or cotangent of Lgain"
+    RECORDS = "events and events_hat are required: the two records the roll-out returned"
+
+    def __init__(self, nlp):
+        self.nlp = nlp
+
+    def fn(self, name):
+        return getattr(_lib.lib(), name + "_host")
+
+    ptr = staticmethod(_host_ptr)
+
+    @staticmethod
+    def arr(a, size, name):
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
+        if a.size != size:
+            raise ValueError(f"{name} has {a.size} entries, expected {size}")
+        return a
+
+    def opt(self, a, size, name):
+        return None if a is None else self.arr(a, size, name)
+
+    @staticmethod
+    def loose(a, size, name):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
+        if a.size < size:
+            raise ValueError(f"{name} has {a.size} entries, expected {size}")
+        return a
+
+    def Z(self, a, name):
+        return self.nlp._host_Z(a, name)
+
+    def Z_opt(self, a, name):
+        return None if a is None else self.nlp._host_Z(a, name)
+
+    def K(self, a, name="K"):
+        return self.nlp._host_K(a)
+
+    def x0(self, a, name="x0"):
+        if a is None:
+            return None
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (self.nlp.B, n)))
+
+    def model(self, a, name="model"):
+        return self.opt(a, self.nlp.B * _lib.MODEL_NP, name)
+
+    def events(self, a):
+        if a is None:
+            raise ValueError("events is required: the record tracking_rollout_guarded_host returned with Zout")
+        return self.arr(a, self.nlp.B * _lib.TOUCHDOWN_INFO_STRIDE, "events")
+
+    events_hat = events
+
+    def sat(self, a):
+        if a is None:
+            raise ValueError("sat is required: the saturation record tracking_rollout_limited_host returned with Zout")
+        return self.arr(a, self.nlp.B * (self.nlp.N - 1), "sat")
+
+    @staticmethod
+    def H(Hh):
+        return Hh
+
+    def sigma0(self, Sigma0):
+        if Sigma0 is None:
+            raise ValueError("Sigma0 is required")
+        return tracking_sigma0(Sigma0, self.nlp.B)
+
+    @staticmethod
+    def zeros(shape, want=True):
+        return np.zeros(shape) if want else None
+
+    empty = zeros
+
+    @staticmethod
+    def out(a, shape, name, empty=False):
+        return np.zeros(shape)
 
 
 # layout of the step-block section of vals (include/qln_evaluator.h, QLN_JAC_FORMAT_*)
@@ -641,57 +826,39 @@ class HybridNLP:
         return out
 
     # -- TVLQR tracking along reference trajectories ---------------------------------------------
+    # Every operation from here to differentiable_estimated_rollout is stated once, as an _op_ method that takes the memory
+    # form (_DeviceForm / _HostForm) and the variant's extras as optional arguments and picks the entry point from what is
+    # present; the public methods are the wrappers that name the form (DESIGN.md "One body per operation").
+    def _op_lqr(self, f, kind, Ztraj, Q, R, Qf, name="Ztraj", events=None, sat=None, model=None, K=None, P=None,
+                with_cost_to_go=True):
+        """kind: "" (at the handle's schedule), "_guarded" (events required) or "_limited" (sat required, events optional)"""
+        Qh, Rh, Qfh = tracking_weights(Q, R, Qf)
+        Ztraj = f.Z(Ztraj, name)
+        extra = ()
+        if kind:
+            sat = f.sat(sat) if kind == "_limited" else None
+            events = f.events(events) if kind == "_guarded" or events is not None else None
+            model = f.model(model)
+            extra = (f.ptr(model), f.ptr(events)) + ((f.ptr(sat),) if kind == "_limited" else ())
+        K = f.out(K, tracking_k_shape(self.B, self.N), "K", empty=True)
+        P = f.out(P, tracking_p_shape(self.B, self.N), "P", empty=True) if with_cost_to_go else None
+        _lib.check(f.fn("qln_tracking_lqr" + kind)(self._h, f.ptr(Ztraj), *extra, Qh.ctypes.data, Rh.ctypes.data, Qfh.ctypes.data,
+                                                   f.ptr(K), f.ptr(P)))
+        return K, P
+
     def tracking_lqr(self, Zref, Q, R, Qf, K=None, P=None, with_cost_to_go=True):
         """Time-varying LQR gains along the references Zref (device tensor, layout of Z): returns (K, P) with
         K (B, N-1, 4, 15) and P (B, N, 120) packed lower triangles (None without with_cost_to_go).  Only the four forces
         are fed back, du_k = -K_k (x_k - x_ref,k); Q (15), R (4), Qf (15) are diagonal weights (qln_evaluator.h)."""
-        T = _torch()
-        Qh, Rh, Qfh = tracking_weights(Q, R, Qf)
-        self._check(Zref, self.dims.z_total, "Zref")
-        if K is None:
-            K = T.empty(tracking_k_shape(self.B, self.N), dtype=T.float64, device=self._dev())
-        self._check(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
-        if with_cost_to_go and P is None:
-            P = T.empty(tracking_p_shape(self.B, self.N), dtype=T.float64, device=self._dev())
-        if not with_cost_to_go:
-            P = None
-        pp = None if P is None else self._check(P, self.B * self.N * _lib.TRACK_P_NNZ, "P")
-        _lib.check(_lib.lib().qln_tracking_lqr(self._h, Zref.data_ptr(), Qh.ctypes.data, Rh.ctypes.data, Qfh.ctypes.data,
-                                               K.data_ptr(), pp))
-        return K, P
+        return self._op_lqr(_DeviceForm(self), "", Zref, Q, R, Qf, "Zref", K=K, P=P, with_cost_to_go=with_cost_to_go)
 
     def tracking_lqr_host(self, Zref, Q, R, Qf, with_cost_to_go=True):
         """The same with host arrays (synchronous): returns numpy (K, P)."""
-        Zref = self._host_Z(Zref, "Zref")
-        Qh, Rh, Qfh = tracking_weights(Q, R, Qf)
-        K = np.zeros(tracking_k_shape(self.B, self.N))
-        P = np.zeros(tracking_p_shape(self.B, self.N)) if with_cost_to_go else None
-        _lib.check(_lib.lib().qln_tracking_lqr_host(self._h, Zref.ctypes.data, Qh.ctypes.data, Rh.ctypes.data, Qfh.ctypes.data,
-                                                    K.ctypes.data, None if P is None else P.ctypes.data))
-        return K, P
+        return self._op_lqr(_HostForm(self), "", Zref, Q, R, Qf, "Zref", with_cost_to_go=with_cost_to_go)
 
     # -- the closed-loop roll-out and its two sweeps ------------------------------------------------
-    # One implementation per operation and memory form, with the per-problem plant as optional arguments.  `m` picks the
-    # entry point: the _model_ one, which takes model / model_dot / model_bar, or the one at the handle's model without them.
-    def _rollout_fn(self, op, m, host):
-        return getattr(_lib.lib(), "qln_tracking_rollout" + ("_model" if m else "") + op + ("_host" if host else ""))
-
-    def _check_opt(self, t, total, name):
-        return None if t is None else self._check(t, total, name)
-
-    def _host_x0(self, x0):
-        if x0 is None:
-            return None
-        return np.ascontiguousarray(np.broadcast_to(np.asarray(x0, dtype=np.float64), (self.B, n)))
-
-    def _host_model(self, m, name="model"):
-        if m is None:
-            return None
-        m = np.ascontiguousarray(np.asarray(m, dtype=np.float64).reshape(-1))
-        if m.size != self.B * _lib.MODEL_NP:
-            raise ValueError(f"{name} has {m.size} entries, expected {self.B * _lib.MODEL_NP}")
-        return m
-
+    # kind picks the entry point: "" (the handle's model), "_model" (a per-problem plant), "_guarded" (touchdown by the guard,
+    # with the event record) or "_limited" (clamped forces: limits, the guarded flag and the saturation record).
     def _vjp_want(self, K, want, names):
         want = names if want is None else tuple(want)
         bad = set(want) - set(names)
@@ -701,93 +868,101 @@ class HybridNLP:
             want = tuple(w for w in names if w != "K")  # the default asks for K_bar only where there are gains
         return want
 
-    def _rollout(self, m, Zref, K, x0, model, out):
-        self._check(Zref, self.dims.z_total, "Zref")
-        out = self.new_Z() if out is None else out
-        self._check(out, self.dims.z_total, "out")
-        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
-        xp = self._check_opt(x0, self.B * n, "x0")
-        mp = (self._check_opt(model, self.B * _lib.MODEL_NP, "model"),) if m else ()
-        _lib.check(self._rollout_fn("", m, False)(self._h, Zref.data_ptr(), kp, xp, *mp, out.data_ptr()))
-        return out
+    def _op_rollout(self, f, kind, Zref, K, x0, model=None, out=None, limits=None, guarded=False, with_events=True,
+                    with_sat=True):
+        limited = kind == "_limited"
+        lim = force_limits(limits) if limited else None
+        Zref = f.Z(Zref, "Zref")
+        out = f.out(out, (self.dims.z_total,), "out")
+        K, x0 = f.K(K), f.x0(x0)
+        args = [self._h, f.ptr(Zref), f.ptr(K), f.ptr(x0)]
+        if kind:
+            model = f.model(model)
+            args.append(f.ptr(model))
+        if limited:
+            args += [lim.ctypes.data, int(bool(guarded))]
+        args.append(f.ptr(out))
+        ev = sat = None
+        if kind in ("_guarded", "_limited"):
+            ev = f.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE), with_events and (guarded or not limited))
+            args.append(f.ptr(ev))
+        if limited:
+            sat = f.zeros((self.B, self.N - 1), with_sat)
+            args.append(f.ptr(sat))
+        _lib.check(f.fn("qln_tracking_rollout" + kind)(*args))
+        return (out, ev, sat) if limited else (out, ev) if kind == "_guarded" else out
 
-    def _rollout_host(self, m, Zref, K, x0, model):
-        Zref, K, x0 = self._host_Z(Zref, "Zref"), self._host_K(K), self._host_x0(x0)
-        mp = (_host_ptr(self._host_model(model)),) if m else ()
-        out = np.zeros(self.dims.z_total)
-        _lib.check(self._rollout_fn("", m, True)(self._h, Zref.ctypes.data, _host_ptr(K), _host_ptr(x0), *mp, out.ctypes.data))
-        return out
+    def _op_rollout_vjp(self, f, kind, Zref, Zout, Zbar, K, model, want, events=None, sat=None):
+        """Returns (Zref_bar, K_bar, x0_bar, model_bar); model_bar is None for kind ""."""
+        want = self._vjp_want(K, want, ("Zref", "K", "x0", "model") if kind else ("Zref", "K", "x0"))
+        Zref, Zout, Zbar = f.Z(Zref, "Zref"), f.Z(Zout, "Zout"), f.Z(Zbar, "Zbar")
+        sat = f.sat(sat) if kind == "_limited" else None
+        events = f.events(events) if kind == "_guarded" or events is not None else None
+        K, model = f.K(K), f.model(model)
+        zb = f.zeros((self.dims.z_total,), "Zref" in want)
+        kb = f.zeros(tracking_k_shape(self.B, self.N), "K" in want)
+        xb = f.zeros((self.B, n), "x0" in want)
+        mb = f.zeros((self.B, _lib.MODEL_NP), "model" in want)
+        args = [self._h, f.ptr(Zref), f.ptr(K), f.ptr(Zout)]
+        if kind:
+            args.append(f.ptr(model))
+        if kind in ("_guarded", "_limited"):
+            args.append(f.ptr(events))
+        if kind == "_limited":
+            args.append(f.ptr(sat))
+        args += [f.ptr(Zbar), f.ptr(zb), f.ptr(kb), f.ptr(xb)]
+        if kind:
+            args.append(f.ptr(mb))
+        _lib.check(f.fn("qln_tracking_rollout" + kind + "_vjp")(*args))
+        return zb, kb, xb, mb
+
+    def _op_rollout_jvp(self, f, kind, Zref, Zout, K, model, Zref_dot, K_dot, x0_dot, model_dot, out, events=None, sat=None,
+                        with_event_dot=True):
+        Zref, Zout = f.Z(Zref, "Zref"), f.Z(Zout, "Zout")
+        sat = f.sat(sat) if kind == "_limited" else None
+        events = f.events(events) if kind == "_guarded" or events is not None else None
+        K, model = f.K(K), f.model(model)
+        Zref_dot, K_dot, x0_dot = f.Z_opt(Zref_dot, "Zref_dot"), f.K(K_dot, "K_dot"), f.x0(x0_dot, "x0_dot")
+        model_dot = f.model(model_dot, "model_dot")
+        out = f.out(out, (self.dims.z_total,), "out")
+        args = [self._h, f.ptr(Zref), f.ptr(K), f.ptr(Zout)]
+        if kind:
+            args.append(f.ptr(model))
+        if kind in ("_guarded", "_limited"):
+            args.append(f.ptr(events))
+        if kind == "_limited":
+            args.append(f.ptr(sat))
+        args += [f.ptr(Zref_dot), f.ptr(K_dot), f.ptr(x0_dot)]
+        if kind:
+            args.append(f.ptr(model_dot))
+        args.append(f.ptr(out))
+        if kind in ("", "_model"):
+            _lib.check(f.fn("qln_tracking_rollout" + kind + "_jvp")(*args))
+            return out
+        ed = f.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE), with_event_dot and events is not None)
+        _lib.check(f.fn("qln_tracking_rollout" + kind + "_jvp")(*args, f.ptr(ed)))
+        return out, ed
+
+    # the names quadruped_landing_amd/rollout_grad.py calls: the device form, m the per-problem plant
+    def _rollout(self, m, Zref, K, x0, model, out):
+        return self._op_rollout(_DeviceForm(self), "_model" if m else "", Zref, K, x0, model, out)
 
     def _rollout_vjp(self, m, Zref, Zout, Zbar, K, model, want):
-        T = _torch()
-        want = self._vjp_want(K, want, ("Zref", "K", "x0", "model") if m else ("Zref", "K", "x0"))
-        self._check(Zref, self.dims.z_total, "Zref")
-        self._check(Zout, self.dims.z_total, "Zout")
-        self._check(Zbar, self.dims.z_total, "Zbar")
-        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
-        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
-        zb = self.new_Z() if "Zref" in want else None
-        kb = T.zeros(tracking_k_shape(self.B, self.N), dtype=T.float64, device=self._dev()) if "K" in want else None
-        xb = T.zeros((self.B, n), dtype=T.float64, device=self._dev()) if "x0" in want else None
-        mb = T.zeros((self.B, _lib.MODEL_NP), dtype=T.float64, device=self._dev()) if "model" in want else None
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        m_in, m_out = ((mp,), (ptr(mb),)) if m else ((), ())
-        _lib.check(self._rollout_fn("_vjp", m, False)(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), *m_in, Zbar.data_ptr(),
-                                                      ptr(zb), ptr(kb), ptr(xb), *m_out))
-        return zb, kb, xb, mb
-
-    def _rollout_vjp_host(self, m, Zref, Zout, Zbar, K, model, want):
-        want = self._vjp_want(K, want, ("Zref", "K", "x0", "model") if m else ("Zref", "K", "x0"))
-        Zref, Zout, Zbar = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout"), self._host_Z(Zbar, "Zbar")
-        K, model = self._host_K(K), self._host_model(model)
-        zb = np.zeros(self.dims.z_total) if "Zref" in want else None
-        kb = np.zeros(tracking_k_shape(self.B, self.N)) if "K" in want else None
-        xb = np.zeros((self.B, n)) if "x0" in want else None
-        mb = np.zeros((self.B, _lib.MODEL_NP)) if "model" in want else None
-        m_in, m_out = ((_host_ptr(model),), (_host_ptr(mb),)) if m else ((), ())
-        _lib.check(self._rollout_fn("_vjp", m, True)(self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data, *m_in,
-                                                     Zbar.ctypes.data, _host_ptr(zb), _host_ptr(kb), _host_ptr(xb), *m_out))
-        return zb, kb, xb, mb
+        return self._op_rollout_vjp(_DeviceForm(self), "_model" if m else "", Zref, Zout, Zbar, K, model, want)
 
     def _rollout_jvp(self, m, Zref, Zout, K, model, Zref_dot, K_dot, x0_dot, model_dot, out):
-        nk = self.B * (self.N - 1) * _lib.TRACK_NU * n
-        self._check(Zref, self.dims.z_total, "Zref")
-        self._check(Zout, self.dims.z_total, "Zout")
-        kp = self._check_opt(K, nk, "K")
-        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
-        zd = self._check_opt(Zref_dot, self.dims.z_total, "Zref_dot")
-        kd = self._check_opt(K_dot, nk, "K_dot")
-        xd = self._check_opt(x0_dot, self.B * n, "x0_dot")
-        md = self._check_opt(model_dot, self.B * _lib.MODEL_NP, "model_dot")
-        out = self.new_Z() if out is None else out
-        self._check(out, self.dims.z_total, "out")
-        m_in, m_dot = ((mp,), (md,)) if m else ((), ())
-        _lib.check(self._rollout_fn("_jvp", m, False)(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), *m_in, zd, kd, xd, *m_dot,
-                                                      out.data_ptr()))
-        return out
-
-    def _rollout_jvp_host(self, m, Zref, Zout, K, model, Zref_dot, K_dot, x0_dot, model_dot):
-        Zref, Zout = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout")
-        K, K_dot, x0_dot = self._host_K(K), self._host_K(K_dot), self._host_x0(x0_dot)
-        model, model_dot = self._host_model(model), self._host_model(model_dot, "model_dot")
-        if Zref_dot is not None:
-            Zref_dot = self._host_Z(Zref_dot, "Zref_dot")
-        out = np.zeros(self.dims.z_total)
-        m_in, m_dot = ((_host_ptr(model),), (_host_ptr(model_dot),)) if m else ((), ())
-        _lib.check(self._rollout_fn("_jvp", m, True)(self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data, *m_in,
-                                                     _host_ptr(Zref_dot), _host_ptr(K_dot), _host_ptr(x0_dot), *m_dot,
-                                                     out.ctypes.data))
-        return out
+        return self._op_rollout_jvp(_DeviceForm(self), "_model" if m else "", Zref, Zout, K, model, Zref_dot, K_dot, x0_dot,
+                                    model_dot, out)
 
     def tracking_rollout(self, Zref, K=None, x0=None, out=None):
         """Closed-loop roll-out of the hybrid dynamics from x0 ((B, 15) device tensor, None: the handle's x0) with
         F_k = F_ref,k - K_k (x_k - x_ref,k) and h_k = h_ref,k; K None is the open-loop roll-out.  Returns Zout in the
         layout of Z (entries past n_nlp are not written).  out must not overlap Zref."""
-        return self._rollout(False, Zref, K, x0, None, out)
+        return self._op_rollout(_DeviceForm(self), "", Zref, K, x0, out=out)
 
     def tracking_rollout_host(self, Zref, K=None, x0=None):
         """The same with host arrays (synchronous): returns a (z_total,) numpy array (zeros past n_nlp)."""
-        return self._rollout_host(False, Zref, K, x0, None)
+        return self._op_rollout(_HostForm(self), "", Zref, K, x0)
 
     # -- reverse-mode derivative of the closed-loop roll-out ---------------------------------------
     def tracking_rollout_vjp(self, Zref, Zout, Zbar, K=None, want=None):
@@ -795,11 +970,11 @@ class HybridNLP:
         (Zout's states and applied controls) -> (Zref_bar, K_bar, x0_bar), each None unless named in want (default: all
         three, K_bar only when K is given).  Zref_bar is laid out like Z (zeros past n_nlp on a fresh buffer), K_bar like K
         (B, N-1, 4, 15), x0_bar (B, 15).  Stream-ordered; semantics in include/qln_evaluator.h."""
-        return self._rollout_vjp(False, Zref, Zout, Zbar, K, None, want)[:3]
+        return self._op_rollout_vjp(_DeviceForm(self), "", Zref, Zout, Zbar, K, None, want)[:3]
 
     def tracking_rollout_vjp_host(self, Zref, Zout, Zbar, K=None, want=None):
         """The same with host arrays (synchronous): numpy (Zref_bar (z_total,), K_bar (B, N-1, 4, 15), x0_bar (B, 15))."""
-        return self._rollout_vjp_host(False, Zref, Zout, Zbar, K, None, want)[:3]
+        return self._op_rollout_vjp(_HostForm(self), "", Zref, Zout, Zbar, K, None, want)[:3]
 
     # -- forward-mode derivative of the closed-loop roll-out ---------------------------------------
     def tracking_rollout_jvp(self, Zref, Zout, K=None, Zref_dot=None, K_dot=None, x0_dot=None, out=None):
@@ -807,11 +982,11 @@ class HybridNLP:
         K_dot (B, N-1, 4, 15) and x0_dot (B, 15) -- each None for zero, at least one given, K_dot only with K -- to the
         tangent Zout_dot of Zout's states and applied controls, in the layout of Z (zeros past n_nlp on a fresh buffer; out
         must overlap no input).  Stream-ordered; semantics in include/qln_evaluator.h."""
-        return self._rollout_jvp(False, Zref, Zout, K, None, Zref_dot, K_dot, x0_dot, None, out)
+        return self._op_rollout_jvp(_DeviceForm(self), "", Zref, Zout, K, None, Zref_dot, K_dot, x0_dot, None, out)
 
     def tracking_rollout_jvp_host(self, Zref, Zout, K=None, Zref_dot=None, K_dot=None, x0_dot=None):
         """The same with host arrays (synchronous): returns a (z_total,) numpy array (zeros past n_nlp)."""
-        return self._rollout_jvp_host(False, Zref, Zout, K, None, Zref_dot, K_dot, x0_dot, None)
+        return self._op_rollout_jvp(_HostForm(self), "", Zref, Zout, K, None, Zref_dot, K_dot, x0_dot, None, None)
 
     # -- the roll-out and its sweeps with a per-problem plant model --------------------------------
     def plant_models(self, models=None):
@@ -825,33 +1000,33 @@ class HybridNLP:
         """tracking_rollout with a per-problem PLANT: model is a (B, 4) float64 device tensor of (g, mb, mf, lb) rows
         (plant_models; None: the handle's model, then bit for bit tracking_rollout).  The gains and the references stay
         what they are: only the dynamics that are rolled out read the problem's model (qln_evaluator.h)."""
-        return self._rollout(True, Zref, K, x0, model, out)
+        return self._op_rollout(_DeviceForm(self), "_model", Zref, K, x0, model, out)
 
     def tracking_rollout_model_host(self, Zref, K=None, x0=None, model=None):
         """The same with host arrays (synchronous): returns a (z_total,) numpy array (zeros past n_nlp).  A non-finite
         model entry, or mb, mf or lb <= 0, is refused."""
-        return self._rollout_host(True, Zref, K, x0, model)
+        return self._op_rollout(_HostForm(self), "_model", Zref, K, x0, model)
 
     def tracking_rollout_model_vjp(self, Zref, Zout, Zbar, K=None, model=None, want=None):
         """Reverse sweep of tracking_rollout_model at the trajectory Zout: tracking_rollout_vjp with the blocks at each
         problem's model, and a fourth output model_bar (B, 4), the cotangent of `model`.  Returns (Zref_bar, K_bar, x0_bar,
         model_bar), each None unless named in want (default: all, K_bar only when K is given)."""
-        return self._rollout_vjp(True, Zref, Zout, Zbar, K, model, want)
+        return self._op_rollout_vjp(_DeviceForm(self), "_model", Zref, Zout, Zbar, K, model, want)
 
     def tracking_rollout_model_vjp_host(self, Zref, Zout, Zbar, K=None, model=None, want=None):
         """The same with host arrays (synchronous): numpy (Zref_bar, K_bar, x0_bar, model_bar (B, 4))."""
-        return self._rollout_vjp_host(True, Zref, Zout, Zbar, K, model, want)
+        return self._op_rollout_vjp(_HostForm(self), "_model", Zref, Zout, Zbar, K, model, want)
 
     def tracking_rollout_model_jvp(self, Zref, Zout, K=None, model=None, Zref_dot=None, K_dot=None, x0_dot=None,
                                    model_dot=None, out=None):
         """Forward sweep of tracking_rollout_model at the trajectory Zout: tracking_rollout_jvp with the blocks at each
         problem's model and a fourth tangent model_dot (B, 4) -- each tangent None for zero, at least one given."""
-        return self._rollout_jvp(True, Zref, Zout, K, model, Zref_dot, K_dot, x0_dot, model_dot, out)
+        return self._op_rollout_jvp(_DeviceForm(self), "_model", Zref, Zout, K, model, Zref_dot, K_dot, x0_dot, model_dot, out)
 
     def tracking_rollout_model_jvp_host(self, Zref, Zout, K=None, model=None, Zref_dot=None, K_dot=None, x0_dot=None,
                                         model_dot=None):
         """The same with host arrays (synchronous): returns a (z_total,) numpy array (zeros past n_nlp)."""
-        return self._rollout_jvp_host(True, Zref, Zout, K, model, Zref_dot, K_dot, x0_dot, model_dot)
+        return self._op_rollout_jvp(_HostForm(self), "_model", Zref, Zout, K, model, Zref_dot, K_dot, x0_dot, model_dot, None)
 
     # -- the roll-out with guard-triggered touchdown -------------------------------------------------
     def tracking_rollout_guarded(self, Zref, K=None, x0=None, model=None, out=None, with_events=True):
@@ -862,43 +1037,14 @@ class HybridNLP:
         0}, None without with_events.  Zout is not a trajectory of the handle's schedule: its derivatives are
         tracking_rollout_guarded_jvp / _vjp, which take the events; the other jvp / vjp / covariance calls do not apply to it
         (qln_evaluator.h)."""
-        T = _torch()
-        self._check(Zref, self.dims.z_total, "Zref")
-        out = self.new_Z() if out is None else out
-        self._check(out, self.dims.z_total, "out")
-        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
-        xp = self._check_opt(x0, self.B * n, "x0")
-        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
-        ev = T.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE), dtype=T.float64, device=self._dev()) if with_events else None
-        _lib.check(_lib.lib().qln_tracking_rollout_guarded(self._h, Zref.data_ptr(), kp, xp, mp, out.data_ptr(),
-                                                           None if ev is None else ev.data_ptr()))
-        return out, ev
+        return self._op_rollout(_DeviceForm(self), "_guarded", Zref, K, x0, model, out, with_events=with_events)
 
     def tracking_rollout_guarded_host(self, Zref, K=None, x0=None, model=None, with_events=True):
         """The same with host arrays (synchronous): returns numpy (Zout (z_total,), zeros past n_nlp, events (B, 8) or None).
         A non-finite model entry, or mb, mf or lb <= 0, is refused."""
-        Zref, K, x0 = self._host_Z(Zref, "Zref"), self._host_K(K), self._host_x0(x0)
-        model = self._host_model(model)
-        out = np.zeros(self.dims.z_total)
-        ev = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if with_events else None
-        _lib.check(_lib.lib().qln_tracking_rollout_guarded_host(self._h, Zref.ctypes.data, _host_ptr(K), _host_ptr(x0),
-                                                                _host_ptr(model), out.ctypes.data, _host_ptr(ev)))
-        return out, ev
+        return self._op_rollout(_HostForm(self), "_guarded", Zref, K, x0, model, with_events=with_events)
 
     # -- forward and reverse sweeps through the guard-triggered touchdown ----------------------------
-    def _events_ptr(self, events):
-        if events is None:
-            raise ValueError("events is required: the record tracking_rollout_guarded returned with Zout")
-        return self._check(events, self.B * _lib.TOUCHDOWN_INFO_STRIDE, "events")
-
-    def _host_events(self, events):
-        if events is None:
-            raise ValueError("events is required: the record tracking_rollout_guarded_host returned with Zout")
-        e = np.ascontiguousarray(np.asarray(events, dtype=np.float64).reshape(-1))
-        if e.size != self.B * _lib.TOUCHDOWN_INFO_STRIDE:
-            raise ValueError(f"events has {e.size} entries, expected {self.B * _lib.TOUCHDOWN_INFO_STRIDE}")
-        return e
-
     def tracking_rollout_guarded_jvp(self, Zref, Zout, events, K=None, model=None, Zref_dot=None, K_dot=None, x0_dot=None,
                                      model_dot=None, out=None, with_event_dot=True):
         """Forward sweep of tracking_rollout_guarded at the trajectory (Zout, events) it returned, at fixed touchdown knot:
@@ -906,76 +1052,46 @@ class HybridNLP:
         (qln_evaluator.h).  Returns (Zout_dot, event_dot): event_dot is a (B, 8) device tensor holding d tau in entry 1 and
         the touchdown clock's tangent in entry 2, zeros elsewhere and for a problem that does not land; None without
         with_event_dot."""
-        T = _torch()
-        nk = self.B * (self.N - 1) * _lib.TRACK_NU * n
-        self._check(Zref, self.dims.z_total, "Zref")
-        self._check(Zout, self.dims.z_total, "Zout")
-        ep = self._events_ptr(events)
-        kp = self._check_opt(K, nk, "K")
-        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
-        zd = self._check_opt(Zref_dot, self.dims.z_total, "Zref_dot")
-        kd = self._check_opt(K_dot, nk, "K_dot")
-        xd = self._check_opt(x0_dot, self.B * n, "x0_dot")
-        md = self._check_opt(model_dot, self.B * _lib.MODEL_NP, "model_dot")
-        out = self.new_Z() if out is None else out
-        self._check(out, self.dims.z_total, "out")
-        ed = T.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE), dtype=T.float64, device=self._dev()) if with_event_dot else None
-        _lib.check(_lib.lib().qln_tracking_rollout_guarded_jvp(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), mp, ep, zd, kd, xd,
-                                                               md, out.data_ptr(), None if ed is None else ed.data_ptr()))
-        return out, ed
+        return self._op_rollout_jvp(_DeviceForm(self), "_guarded", Zref, Zout, K, model, Zref_dot, K_dot, x0_dot, model_dot, out,
+                                    events, with_event_dot=with_event_dot)
 
     def tracking_rollout_guarded_jvp_host(self, Zref, Zout, events, K=None, model=None, Zref_dot=None, K_dot=None, x0_dot=None,
                                           model_dot=None, with_event_dot=True):
         """The same with host arrays (synchronous): numpy (Zout_dot (z_total,), event_dot (B, 8) or None).  A knot that is
         not an integer in [-1, N-2], or a tau that is not finite or is negative, is refused."""
-        Zref, Zout, ev = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout"), self._host_events(events)
-        K, K_dot, x0_dot = self._host_K(K), self._host_K(K_dot), self._host_x0(x0_dot)
-        model, model_dot = self._host_model(model), self._host_model(model_dot, "model_dot")
-        if Zref_dot is not None:
-            Zref_dot = self._host_Z(Zref_dot, "Zref_dot")
-        out = np.zeros(self.dims.z_total)
-        ed = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if with_event_dot else None
-        _lib.check(_lib.lib().qln_tracking_rollout_guarded_jvp_host(
-            self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data, _host_ptr(model), ev.ctypes.data, _host_ptr(Zref_dot),
-            _host_ptr(K_dot), _host_ptr(x0_dot), _host_ptr(model_dot), out.ctypes.data, _host_ptr(ed)))
-        return out, ed
+        return self._op_rollout_jvp(_HostForm(self), "_guarded", Zref, Zout, K, model, Zref_dot, K_dot, x0_dot, model_dot, None,
+                                    events, with_event_dot=with_event_dot)
 
     def tracking_rollout_guarded_vjp(self, Zref, Zout, events, Zbar, K=None, model=None, want=None):
         """Reverse sweep of tracking_rollout_guarded at the trajectory (Zout, events) it returned, the exact adjoint of
         tracking_rollout_guarded_jvp: tracking_rollout_model_vjp's cotangents and rules.  Returns (Zref_bar, K_bar, x0_bar,
         model_bar), each None unless named in want (default: all, K_bar only when K is given)."""
-        T = _torch()
-        want = self._vjp_want(K, want, ("Zref", "K", "x0", "model"))
-        self._check(Zref, self.dims.z_total, "Zref")
-        self._check(Zout, self.dims.z_total, "Zout")
-        self._check(Zbar, self.dims.z_total, "Zbar")
-        ep = self._events_ptr(events)
-        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
-        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
-        zb = self.new_Z() if "Zref" in want else None
-        kb = T.zeros(tracking_k_shape(self.B, self.N), dtype=T.float64, device=self._dev()) if "K" in want else None
-        xb = T.zeros((self.B, n), dtype=T.float64, device=self._dev()) if "x0" in want else None
-        mb = T.zeros((self.B, _lib.MODEL_NP), dtype=T.float64, device=self._dev()) if "model" in want else None
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        _lib.check(_lib.lib().qln_tracking_rollout_guarded_vjp(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), mp, ep,
-                                                               Zbar.data_ptr(), ptr(zb), ptr(kb), ptr(xb), ptr(mb)))
-        return zb, kb, xb, mb
+        return self._op_rollout_vjp(_DeviceForm(self), "_guarded", Zref, Zout, Zbar, K, model, want, events)
 
     def tracking_rollout_guarded_vjp_host(self, Zref, Zout, events, Zbar, K=None, model=None, want=None):
         """The same with host arrays (synchronous): numpy (Zref_bar, K_bar, x0_bar, model_bar (B, 4))."""
-        want = self._vjp_want(K, want, ("Zref", "K", "x0", "model"))
-        Zref, Zout, Zbar = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout"), self._host_Z(Zbar, "Zbar")
-        K, model, ev = self._host_K(K), self._host_model(model), self._host_events(events)
-        zb = np.zeros(self.dims.z_total) if "Zref" in want else None
-        kb = np.zeros(tracking_k_shape(self.B, self.N)) if "K" in want else None
-        xb = np.zeros((self.B, n)) if "x0" in want else None
-        mb = np.zeros((self.B, _lib.MODEL_NP)) if "model" in want else None
-        _lib.check(_lib.lib().qln_tracking_rollout_guarded_vjp_host(
-            self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data, _host_ptr(model), ev.ctypes.data, Zbar.ctypes.data,
-            _host_ptr(zb), _host_ptr(kb), _host_ptr(xb), _host_ptr(mb)))
-        return zb, kb, xb, mb
+        return self._op_rollout_vjp(_HostForm(self), "_guarded", Zref, Zout, Zbar, K, model, want, events)
 
     # -- covariance propagation through the closed-loop roll-out -----------------------------------
+    def _op_covariance(self, f, guarded, Zout, K, Sigma0, W, with_sigma, with_marginals, Sigma=None, marg=None, events=None,
+                       model=None, with_event_var=True):
+        Zout = f.Z(Zout, "Zout")
+        events = f.events(events) if guarded else None
+        K = f.K(K)
+        model = f.model(model) if guarded else None
+        s0, nb = f.sigma0(Sigma0)
+        Wh = tracking_noise(W)
+        S = f.out(Sigma, tracking_p_shape(self.B, self.N), "Sigma", empty=True) if with_sigma else None
+        mg = f.out(marg, (self.B, self.N, _lib.TRACK_MARG_STRIDE), "marg", empty=True) if with_marginals else None
+        if not guarded:
+            _lib.check(f.fn("qln_tracking_covariance")(self._h, f.ptr(Zout), f.ptr(K), f.ptr(s0), nb, _host_ptr(Wh), f.ptr(S),
+                                                       f.ptr(mg)))
+            return S, mg
+        ev = f.zeros((self.B, 2), with_event_var)
+        _lib.check(f.fn("qln_tracking_covariance_guarded")(self._h, f.ptr(Zout), f.ptr(K), f.ptr(model), f.ptr(events), f.ptr(s0),
+                                                           nb, _host_ptr(Wh), f.ptr(S), f.ptr(mg), f.ptr(ev)))
+        return S, mg, ev
+
     def tracking_covariance(self, Zout, K=None, Sigma0=None, W=None, with_sigma=True, with_marginals=True, Sigma=None,
                             marg=None):
         """Sigma_{k+1} = (A_k - B_k K_k) Sigma_k (A_k - B_k K_k)' + diag(W) along the trajectory Zout (device tensor, layout
@@ -984,45 +1100,11 @@ class HybridNLP:
         (B, N, 120) packed lower triangles (unpack_covariance), marg (B, N, 8) = clearance variance, four force variances,
         the two foot-height variances, trace; each None unless asked for (Sigma / marg: buffers to write into instead of
         fresh ones).  Stream-ordered (qln_evaluator.h)."""
-        T = _torch()
-        if Sigma0 is None:
-            raise ValueError("Sigma0 is required")
-        self._check(Zout, self.dims.z_total, "Zout")
-        kp = None if K is None else self._check(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
-        if isinstance(Sigma0, T.Tensor) and Sigma0.is_cuda:
-            nb = Sigma0.numel() // _lib.TRACK_P_NNZ
-            if Sigma0.numel() != nb * _lib.TRACK_P_NNZ or nb not in (1, self.B):
-                raise ValueError("a device Sigma0 must hold 1 or B packed tiles of 120")
-            s0 = Sigma0
-        else:
-            host, nb = tracking_sigma0(Sigma0, self.B)
-            s0 = T.from_numpy(host).to(self._dev())
-        self._check(s0, nb * _lib.TRACK_P_NNZ, "Sigma0")
-        Wh = tracking_noise(W)
-        S = mg = None
-        if with_sigma:
-            S = T.empty(tracking_p_shape(self.B, self.N), dtype=T.float64, device=self._dev()) if Sigma is None else Sigma
-            self._check(S, self.B * self.N * _lib.TRACK_P_NNZ, "Sigma")
-        if with_marginals:
-            mg = T.empty((self.B, self.N, _lib.TRACK_MARG_STRIDE), dtype=T.float64, device=self._dev()) if marg is None else marg
-            self._check(mg, self.B * self.N * _lib.TRACK_MARG_STRIDE, "marg")
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        _lib.check(_lib.lib().qln_tracking_covariance(self._h, Zout.data_ptr(), kp, s0.data_ptr(), nb, _host_ptr(Wh), ptr(S),
-                                                      ptr(mg)))
-        return S, mg
+        return self._op_covariance(_DeviceForm(self), False, Zout, K, Sigma0, W, with_sigma, with_marginals, Sigma, marg)
 
     def tracking_covariance_host(self, Zout, K=None, Sigma0=None, W=None, with_sigma=True, with_marginals=True):
         """The same with host arrays (synchronous): numpy (Sigma (B, N, 120), marg (B, N, 8))."""
-        if Sigma0 is None:
-            raise ValueError("Sigma0 is required")
-        Zout, K = self._host_Z(Zout, "Zout"), self._host_K(K)
-        s0, nb = tracking_sigma0(Sigma0, self.B)
-        Wh = tracking_noise(W)
-        S = np.zeros(tracking_p_shape(self.B, self.N)) if with_sigma else None
-        mg = np.zeros((self.B, self.N, _lib.TRACK_MARG_STRIDE)) if with_marginals else None
-        _lib.check(_lib.lib().qln_tracking_covariance_host(self._h, Zout.ctypes.data, _host_ptr(K), s0.ctypes.data, nb,
-                                                           _host_ptr(Wh), _host_ptr(S), _host_ptr(mg)))
-        return S, mg
+        return self._op_covariance(_HostForm(self), False, Zout, K, Sigma0, W, with_sigma, with_marginals)
 
     # -- gains and covariances through the guard-triggered touchdown --------------------------------
     def tracking_lqr_guarded(self, Ztraj, events, Q, R, Qf, model=None, K=None, P=None, with_cost_to_go=True):
@@ -1030,34 +1112,14 @@ class HybridNLP:
         for the plan, with its events (B, 8), on the blocks of tracking_rollout_guarded_jvp -- the composite step with the
         derivative of tau at the touchdown knot (qln_evaluator.h).  model: (B, 4) device tensor or None (the handle's).
         Returns (K, P) as tracking_lqr."""
-        T = _torch()
-        Qh, Rh, Qfh = tracking_weights(Q, R, Qf)
-        self._check(Ztraj, self.dims.z_total, "Ztraj")
-        ep = self._events_ptr(events)
-        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
-        if K is None:
-            K = T.empty(tracking_k_shape(self.B, self.N), dtype=T.float64, device=self._dev())
-        self._check(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
-        if with_cost_to_go and P is None:
-            P = T.empty(tracking_p_shape(self.B, self.N), dtype=T.float64, device=self._dev())
-        if not with_cost_to_go:
-            P = None
-        pp = None if P is None else self._check(P, self.B * self.N * _lib.TRACK_P_NNZ, "P")
-        _lib.check(_lib.lib().qln_tracking_lqr_guarded(self._h, Ztraj.data_ptr(), mp, ep, Qh.ctypes.data, Rh.ctypes.data,
-                                                       Qfh.ctypes.data, K.data_ptr(), pp))
-        return K, P
+        return self._op_lqr(_DeviceForm(self), "_guarded", Ztraj, Q, R, Qf, events=events, model=model, K=K, P=P,
+                            with_cost_to_go=with_cost_to_go)
 
     def tracking_lqr_guarded_host(self, Ztraj, events, Q, R, Qf, model=None, with_cost_to_go=True):
         """The same with host arrays (synchronous): returns numpy (K, P).  The events' and the models' values are checked as
         by the guarded sweeps' host forms."""
-        Ztraj, ev, model = self._host_Z(Ztraj, "Ztraj"), self._host_events(events), self._host_model(model)
-        Qh, Rh, Qfh = tracking_weights(Q, R, Qf)
-        K = np.zeros(tracking_k_shape(self.B, self.N))
-        P = np.zeros(tracking_p_shape(self.B, self.N)) if with_cost_to_go else None
-        _lib.check(_lib.lib().qln_tracking_lqr_guarded_host(self._h, Ztraj.ctypes.data, _host_ptr(model), ev.ctypes.data,
-                                                            Qh.ctypes.data, Rh.ctypes.data, Qfh.ctypes.data, K.ctypes.data,
-                                                            _host_ptr(P)))
-        return K, P
+        return self._op_lqr(_HostForm(self), "_guarded", Ztraj, Q, R, Qf, events=events, model=model,
+                            with_cost_to_go=with_cost_to_go)
 
     def tracking_covariance_guarded(self, Zout, events, K=None, Sigma0=None, W=None, model=None, with_sigma=True,
                                     with_marginals=True, with_event_var=True, Sigma=None, marg=None):
@@ -1065,123 +1127,40 @@ class HybridNLP:
         touchdown knot.  Returns (Sigma, marg, event_var): the first two as tracking_covariance, event_var a (B, 2) device
         tensor with the variance of tau and of the touchdown clock (zeros for a problem that does not land); each None
         unless asked for."""
-        T = _torch()
-        if Sigma0 is None:
-            raise ValueError("Sigma0 is required")
-        self._check(Zout, self.dims.z_total, "Zout")
-        ep = self._events_ptr(events)
-        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
-        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
-        if isinstance(Sigma0, T.Tensor) and Sigma0.is_cuda:
-            nb = Sigma0.numel() // _lib.TRACK_P_NNZ
-            if Sigma0.numel() != nb * _lib.TRACK_P_NNZ or nb not in (1, self.B):
-                raise ValueError("a device Sigma0 must hold 1 or B packed tiles of 120")
-            s0 = Sigma0
-        else:
-            host, nb = tracking_sigma0(Sigma0, self.B)
-            s0 = T.from_numpy(host).to(self._dev())
-        self._check(s0, nb * _lib.TRACK_P_NNZ, "Sigma0")
-        Wh = tracking_noise(W)
-        S = mg = ev = None
-        if with_sigma:
-            S = T.empty(tracking_p_shape(self.B, self.N), dtype=T.float64, device=self._dev()) if Sigma is None else Sigma
-            self._check(S, self.B * self.N * _lib.TRACK_P_NNZ, "Sigma")
-        if with_marginals:
-            mg = T.empty((self.B, self.N, _lib.TRACK_MARG_STRIDE), dtype=T.float64, device=self._dev()) if marg is None else marg
-            self._check(mg, self.B * self.N * _lib.TRACK_MARG_STRIDE, "marg")
-        if with_event_var:
-            ev = T.zeros((self.B, 2), dtype=T.float64, device=self._dev())
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        _lib.check(_lib.lib().qln_tracking_covariance_guarded(self._h, Zout.data_ptr(), kp, mp, ep, s0.data_ptr(), nb,
-                                                              _host_ptr(Wh), ptr(S), ptr(mg), ptr(ev)))
-        return S, mg, ev
+        return self._op_covariance(_DeviceForm(self), True, Zout, K, Sigma0, W, with_sigma, with_marginals, Sigma, marg, events,
+                                   model, with_event_var)
 
     def tracking_covariance_guarded_host(self, Zout, events, K=None, Sigma0=None, W=None, model=None, with_sigma=True,
                                          with_marginals=True, with_event_var=True):
         """The same with host arrays (synchronous): numpy (Sigma (B, N, 120), marg (B, N, 8), event_var (B, 2))."""
-        if Sigma0 is None:
-            raise ValueError("Sigma0 is required")
-        Zout, K, ev, model = self._host_Z(Zout, "Zout"), self._host_K(K), self._host_events(events), self._host_model(model)
-        s0, nb = tracking_sigma0(Sigma0, self.B)
-        Wh = tracking_noise(W)
-        S = np.zeros(tracking_p_shape(self.B, self.N)) if with_sigma else None
-        mg = np.zeros((self.B, self.N, _lib.TRACK_MARG_STRIDE)) if with_marginals else None
-        var = np.zeros((self.B, 2)) if with_event_var else None
-        _lib.check(_lib.lib().qln_tracking_covariance_guarded_host(self._h, Zout.ctypes.data, _host_ptr(K), _host_ptr(model),
-                                                                   ev.ctypes.data, s0.ctypes.data, nb, _host_ptr(Wh),
-                                                                   _host_ptr(S), _host_ptr(mg), _host_ptr(var)))
-        return S, mg, var
+        return self._op_covariance(_HostForm(self), True, Zout, K, Sigma0, W, with_sigma, with_marginals, events=events,
+                                   model=model, with_event_var=with_event_var)
 
     # -- the Kalman filter and the LQG covariance: the controller feeds back an estimate -------------
-    def _device_sigma0(self, Sigma0):
-        """Sigma0 in any form of tracking_sigma0, or a CUDA tensor of 1 or B packed tiles -> (device tensor, sigma0_batch)."""
-        T = _torch()
-        if Sigma0 is None:
-            raise ValueError("Sigma0 is required")
-        if isinstance(Sigma0, T.Tensor) and Sigma0.is_cuda:
-            nb = Sigma0.numel() // _lib.TRACK_P_NNZ
-            if Sigma0.numel() != nb * _lib.TRACK_P_NNZ or nb not in (1, self.B):
-                raise ValueError("a device Sigma0 must hold 1 or B packed tiles of 120")
-            s0 = Sigma0
-        else:
-            host, nb = tracking_sigma0(Sigma0, self.B)
-            s0 = T.from_numpy(host).to(self._dev())
-        self._check(s0, nb * _lib.TRACK_P_NNZ, "Sigma0")
-        return s0, nb
-
-    def _kalman(self, guarded, Zout, events, K, H, V, Sigma0, W, model, with_gains, with_pest, with_sigma, with_marginals,
-                with_event_var):
-        T = _torch()
+    def _op_kalman(self, f, guarded, Zout, events, K, H, V, Sigma0, W, model, with_gains, with_pest, with_sigma, with_marginals,
+                   with_event_var):
+        """with_sigma, with_marginals and with_event_var: None for "where there are gains" """
         Hh, Vh = measurement_model(H, V)
         ny = Hh.shape[0]
-        self._check(Zout, self.dims.z_total, "Zout")
-        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
-        s0, nb = self._device_sigma0(Sigma0)
+        with_sigma, with_marginals, with_event_var = ((K is not None) if w is None else w
+                                                      for w in (with_sigma, with_marginals, with_event_var))
+        Zout, K = f.Z(Zout, "Zout"), f.K(K)
+        s0, nb = f.sigma0(Sigma0)
         Wh = tracking_noise(W)
-        Hd = T.from_numpy(Hh).to(self._dev())
-        new = lambda want, shape: T.empty(shape, dtype=T.float64, device=self._dev()) if want else None  # noqa: E731
-        Lg = new(with_gains, tracking_l_shape(self.B, self.N, ny))
-        Pe = new(with_pest, tracking_p_shape(self.B, self.N))
-        S = new(with_sigma, tracking_p_shape(self.B, self.N))
-        mg = new(with_marginals, (self.B, self.N, _lib.TRACK_MARG_STRIDE))
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        Hd = f.H(Hh)
+        Lg = f.empty(tracking_l_shape(self.B, self.N, ny), with_gains)
+        Pe = f.empty(tracking_p_shape(self.B, self.N), with_pest)
+        S = f.empty(tracking_p_shape(self.B, self.N), with_sigma)
+        mg = f.empty((self.B, self.N, _lib.TRACK_MARG_STRIDE), with_marginals)
+        tail = (f.ptr(Hd), ny, Vh.ctypes.data, f.ptr(s0), nb, _host_ptr(Wh), f.ptr(Lg), f.ptr(Pe), f.ptr(S), f.ptr(mg))
         if not guarded:
-            _lib.check(_lib.lib().qln_tracking_kalman(self._h, Zout.data_ptr(), kp, Hd.data_ptr(), ny, Vh.ctypes.data,
-                                                      s0.data_ptr(), nb, _host_ptr(Wh), ptr(Lg), ptr(Pe), ptr(S), ptr(mg)))
+            _lib.check(f.fn("qln_tracking_kalman")(self._h, f.ptr(Zout), f.ptr(K), *tail))
             return Lg, Pe, S, mg
-        ep = self._events_ptr(events)
-        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
-        ev = T.zeros((self.B, 2), dtype=T.float64, device=self._dev()) if with_event_var else None
-        _lib.check(_lib.lib().qln_tracking_kalman_guarded(self._h, Zout.data_ptr(), kp, mp, ep, Hd.data_ptr(), ny, Vh.ctypes.data,
-                                                          s0.data_ptr(), nb, _host_ptr(Wh), ptr(Lg), ptr(Pe), ptr(S), ptr(mg),
-                                                          ptr(ev)))
+        events, model = f.events(events), f.model(model)
+        ev = f.zeros((self.B, 2), with_event_var)
+        _lib.check(f.fn("qln_tracking_kalman_guarded")(self._h, f.ptr(Zout), f.ptr(K), f.ptr(model), f.ptr(events), *tail,
+                                                       f.ptr(ev)))
         return Lg, Pe, S, mg, ev
-
-    def _kalman_host(self, guarded, Zout, events, K, H, V, Sigma0, W, model, with_gains, with_pest, with_sigma, with_marginals,
-                     with_event_var):
-        if Sigma0 is None:
-            raise ValueError("Sigma0 is required")
-        Hh, Vh = measurement_model(H, V)
-        ny = Hh.shape[0]
-        Zout, K = self._host_Z(Zout, "Zout"), self._host_K(K)
-        s0, nb = tracking_sigma0(Sigma0, self.B)
-        Wh = tracking_noise(W)
-        Lg = np.zeros(tracking_l_shape(self.B, self.N, ny)) if with_gains else None
-        Pe = np.zeros(tracking_p_shape(self.B, self.N)) if with_pest else None
-        S = np.zeros(tracking_p_shape(self.B, self.N)) if with_sigma else None
-        mg = np.zeros((self.B, self.N, _lib.TRACK_MARG_STRIDE)) if with_marginals else None
-        if not guarded:
-            _lib.check(_lib.lib().qln_tracking_kalman_host(self._h, Zout.ctypes.data, _host_ptr(K), Hh.ctypes.data, ny,
-                                                           Vh.ctypes.data, s0.ctypes.data, nb, _host_ptr(Wh), _host_ptr(Lg),
-                                                           _host_ptr(Pe), _host_ptr(S), _host_ptr(mg)))
-            return Lg, Pe, S, mg
-        ev, model = self._host_events(events), self._host_model(model)
-        var = np.zeros((self.B, 2)) if with_event_var else None
-        _lib.check(_lib.lib().qln_tracking_kalman_guarded_host(self._h, Zout.ctypes.data, _host_ptr(K), _host_ptr(model),
-                                                               ev.ctypes.data, Hh.ctypes.data, ny, Vh.ctypes.data, s0.ctypes.data,
-                                                               nb, _host_ptr(Wh), _host_ptr(Lg), _host_ptr(Pe), _host_ptr(S),
-                                                               _host_ptr(mg), _host_ptr(var)))
-        return Lg, Pe, S, mg, var
 
     def tracking_kalman(self, Zout, H, V, K=None, Sigma0=None, W=None, with_gains=True, with_pest=True, with_sigma=None,
                         with_marginals=None):
@@ -1191,16 +1170,14 @@ class HybridNLP:
         true state's covariances X_k = M_k + P^+_k as packed (B, N, 120) tiles (unpack_covariance), and marg (B, N, 8) as
         tracking_covariance's on X_k, with the applied-force variances diag(K M K'); each None unless asked for.  K None is the
         filter alone: L and Pest only (with_sigma / with_marginals default to K being given).  Stream-ordered."""
-        ws = (K is not None) if with_sigma is None else with_sigma
-        wm = (K is not None) if with_marginals is None else with_marginals
-        return self._kalman(False, Zout, None, K, H, V, Sigma0, W, None, with_gains, with_pest, ws, wm, False)
+        return self._op_kalman(_DeviceForm(self), False, Zout, None, K, H, V, Sigma0, W, None, with_gains, with_pest, with_sigma,
+                               with_marginals, False)
 
     def tracking_kalman_host(self, Zout, H, V, K=None, Sigma0=None, W=None, with_gains=True, with_pest=True, with_sigma=None,
                              with_marginals=None):
         """The same with host arrays (synchronous): numpy (L, Pest, Sigma, marg)."""
-        ws = (K is not None) if with_sigma is None else with_sigma
-        wm = (K is not None) if with_marginals is None else with_marginals
-        return self._kalman_host(False, Zout, None, K, H, V, Sigma0, W, None, with_gains, with_pest, ws, wm, False)
+        return self._op_kalman(_HostForm(self), False, Zout, None, K, H, V, Sigma0, W, None, with_gains, with_pest, with_sigma,
+                               with_marginals, False)
 
     def tracking_kalman_guarded(self, Zout, events, H, V, K=None, Sigma0=None, W=None, model=None, with_gains=True,
                                 with_pest=True, with_sigma=None, with_marginals=None, with_event_var=None):
@@ -1208,76 +1185,38 @@ class HybridNLP:
         touchdown knot.  Returns (L, Pest, Sigma, marg, event_var): the first four as tracking_kalman, event_var a (B, 2)
         device tensor with the variance of tau and of the touchdown clock under estimate feedback (zeros for a problem that
         does not land); each None unless asked for."""
-        ws = (K is not None) if with_sigma is None else with_sigma
-        wm = (K is not None) if with_marginals is None else with_marginals
-        we = (K is not None) if with_event_var is None else with_event_var
-        return self._kalman(True, Zout, events, K, H, V, Sigma0, W, model, with_gains, with_pest, ws, wm, we)
+        return self._op_kalman(_DeviceForm(self), True, Zout, events, K, H, V, Sigma0, W, model, with_gains, with_pest, with_sigma,
+                               with_marginals, with_event_var)
 
     def tracking_kalman_guarded_host(self, Zout, events, H, V, K=None, Sigma0=None, W=None, model=None, with_gains=True,
                                      with_pest=True, with_sigma=None, with_marginals=None, with_event_var=None):
         """The same with host arrays (synchronous): numpy (L, Pest, Sigma, marg, event_var)."""
-        ws = (K is not None) if with_sigma is None else with_sigma
-        wm = (K is not None) if with_marginals is None else with_marginals
-        we = (K is not None) if with_event_var is None else with_event_var
-        return self._kalman_host(True, Zout, events, K, H, V, Sigma0, W, model, with_gains, with_pest, ws, wm, we)
+        return self._op_kalman(_HostForm(self), True, Zout, events, K, H, V, Sigma0, W, model, with_gains, with_pest, with_sigma,
+                               with_marginals, with_event_var)
 
     # -- the fixed-interval smoother: the estimator's backward pass ------------------------------------
-    def _smoother(self, guarded, Ztraj, events, Lgain, Pest, H, V, Xhat, innov, model, with_states, with_cov):
-        T = _torch()
+    def _op_smoother(self, f, guarded, Ztraj, events, Lgain, Pest, H, V, Xhat, innov, model, with_states, with_cov):
         Hh, Vh = measurement_model(H, V)
         ny = Hh.shape[0]
         for name, t in (("Lgain", Lgain), ("Pest", Pest), ("Xhat", Xhat), ("innov", innov)):
             if t is None:
-                raise ValueError(f"{name} is required: tracking_kalman's gains and covariances, the estimated roll-out's record")
-        zp = self._check(Ztraj, self.dims.z_total, "Ztraj")
-        lp = self._check(Lgain, self.B * self.N * n * ny, "Lgain")
-        pp = self._check(Pest, self.B * self.N * _lib.TRACK_P_NNZ, "Pest")
-        xp = self._check(Xhat, self.B * self.N * n, "Xhat")
-        ip = self._check(innov, self.B * self.N * ny, "innov")
-        Hd = T.from_numpy(Hh).to(self._dev())
-        new = lambda want, shape: T.empty(shape, dtype=T.float64, device=self._dev()) if want else None  # noqa: E731
-        Xs = new(with_states, (self.B, self.N, n))
-        Ps = new(with_cov, tracking_p_shape(self.B, self.N))
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        if not guarded:
-            _lib.check(_lib.lib().qln_landing_smoother(self._h, zp, lp, pp, Hd.data_ptr(), ny, Vh.ctypes.data, xp, ip, ptr(Xs),
-                                                       ptr(Ps)))
-        else:
-            ep = self._events_ptr(events)
-            mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
-            _lib.check(_lib.lib().qln_landing_smoother_guarded(self._h, zp, mp, ep, lp, pp, Hd.data_ptr(), ny, Vh.ctypes.data, xp,
-                                                               ip, ptr(Xs), ptr(Ps)))
-        return Xs, Ps
-
-    def _smoother_host(self, guarded, Ztraj, events, Lgain, Pest, H, V, Xhat, innov, model, with_states, with_cov):
-        Hh, Vh = measurement_model(H, V)
-        ny = Hh.shape[0]
-
-        def flat(a, size, name):
-            if a is None:
-                raise ValueError(f"{name} is required: tracking_kalman_host's gains and covariances, the estimated roll-out's record")
-            a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
-            if a.size != size:
-                raise ValueError(f"{name} has {a.size} entries, expected {size}")
-            return a
-
-        Ztraj = self._host_Z(Ztraj, "Ztraj")
-        Lg = flat(Lgain, self.B * self.N * n * ny, "Lgain")
-        Pe = flat(Pest, self.B * self.N * _lib.TRACK_P_NNZ, "Pest")
-        Xh = flat(Xhat, self.B * self.N * n, "Xhat")
-        iv = flat(innov, self.B * self.N * ny, "innov")
-        Xs = np.zeros((self.B, self.N, n)) if with_states else None
-        Ps = np.zeros(tracking_p_shape(self.B, self.N)) if with_cov else None
-        if not guarded:
-            _lib.check(_lib.lib().qln_landing_smoother_host(self._h, Ztraj.ctypes.data, Lg.ctypes.data, Pe.ctypes.data,
-                                                            Hh.ctypes.data, ny, Vh.ctypes.data, Xh.ctypes.data, iv.ctypes.data,
-                                                            _host_ptr(Xs), _host_ptr(Ps)))
-        else:
-            ev, model = self._host_events(events), self._host_model(model)
-            _lib.check(_lib.lib().qln_landing_smoother_guarded_host(self._h, Ztraj.ctypes.data, _host_ptr(model), ev.ctypes.data,
-                                                                    Lg.ctypes.data, Pe.ctypes.data, Hh.ctypes.data, ny,
-                                                                    Vh.ctypes.data, Xh.ctypes.data, iv.ctypes.data, _host_ptr(Xs),
-                                                                    _host_ptr(Ps)))
+                raise ValueError(f"{name} is required: tracking_kalman{f.suffix}'s gains and covariances, the estimated roll-out's "
+                                 "record")
+        Ztraj = f.Z(Ztraj, "Ztraj")
+        Lgain = f.arr(Lgain, self.B * self.N * n * ny, "Lgain")
+        Pest = f.arr(Pest, self.B * self.N * _lib.TRACK_P_NNZ, "Pest")
+        Xhat = f.arr(Xhat, self.B * self.N * n, "Xhat")
+        innov = f.arr(innov, self.B * self.N * ny, "innov")
+        Hd = f.H(Hh)
+        Xs = f.empty((self.B, self.N, n), with_states)
+        Ps = f.empty(tracking_p_shape(self.B, self.N), with_cov)
+        extra = ()
+        if guarded:
+            events, model = f.events(events), f.model(model)
+            extra = (f.ptr(model), f.ptr(events))
+        _lib.check(f.fn("qln_landing_smoother" + ("_guarded" if guarded else ""))(
+            self._h, f.ptr(Ztraj), *extra, f.ptr(Lgain), f.ptr(Pest), f.ptr(Hd), ny, Vh.ctypes.data, f.ptr(Xhat), f.ptr(innov),
+            f.ptr(Xs), f.ptr(Ps)))
         return Xs, Ps
 
     def landing_smoother(self, Ztraj, Lgain, Pest, H, V, Xhat, innov, with_states=True, with_cov=True):
@@ -1288,27 +1227,27 @@ class HybridNLP:
         does not check that Lgain and Pest belong together (qln_evaluator.h).  Device tensors in; returns (Xs (B, N, 15), Ps
         (B, N, 120) packed), device tensors, each None unless asked for; which is asked for does not change the other's
         bits.  At knot N-1, Xs = Xhat and Ps = Pest.  Stream-ordered."""
-        return self._smoother(False, Ztraj, None, Lgain, Pest, H, V, Xhat, innov, None, with_states, with_cov)
+        return self._op_smoother(_DeviceForm(self), False, Ztraj, None, Lgain, Pest, H, V, Xhat, innov, None, with_states, with_cov)
 
     def landing_smoother_host(self, Ztraj, Lgain, Pest, H, V, Xhat, innov, with_states=True, with_cov=True):
         """The same with host arrays (synchronous): numpy (Xs, Ps)."""
-        return self._smoother_host(False, Ztraj, None, Lgain, Pest, H, V, Xhat, innov, None, with_states, with_cov)
+        return self._op_smoother(_HostForm(self), False, Ztraj, None, Lgain, Pest, H, V, Xhat, innov, None, with_states, with_cov)
 
     def landing_smoother_guarded(self, Ztraj, events, Lgain, Pest, H, V, Xhat, innov, model=None, with_states=True,
                                  with_cov=True):
         """landing_smoother through the guarded touchdown, on the blocks of tracking_kalman_guarded at (Ztraj, events, model),
         at fixed touchdown knot: the touchdown knot's composite operator is applied transposed."""
-        return self._smoother(True, Ztraj, events, Lgain, Pest, H, V, Xhat, innov, model, with_states, with_cov)
+        return self._op_smoother(_DeviceForm(self), True, Ztraj, events, Lgain, Pest, H, V, Xhat, innov, model, with_states,
+                                 with_cov)
 
     def landing_smoother_guarded_host(self, Ztraj, events, Lgain, Pest, H, V, Xhat, innov, model=None, with_states=True,
                                       with_cov=True):
         """The same with host arrays (synchronous): numpy (Xs, Ps)."""
-        return self._smoother_host(True, Ztraj, events, Lgain, Pest, H, V, Xhat, innov, model, with_states, with_cov)
+        return self._op_smoother(_HostForm(self), True, Ztraj, events, Lgain, Pest, H, V, Xhat, innov, model, with_states, with_cov)
 
     # -- the filter on recorded data, and the score of the data under it -------------------------------
-    def _filter(self, guarded, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, with_events,
-                model=None):
-        T = _torch()
+    def _op_filter(self, f, guarded, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, with_events,
+                   model=None):
         score = (V is not None) if with_score is None else with_score
         if score and V is None:
             raise ValueError("V is required with with_score: the measurement variances the gains were designed for")
@@ -1316,61 +1255,26 @@ class HybridNLP:
         ny = Hh.shape[0]
         for name, t in (("Lgain", Lgain), ("Y", Y)):
             if t is None:
-                raise ValueError(f"{name} is required: tracking_kalman's gains, the recorded measurements (landing_measurements)")
-        zr = self._check(Zref, self.dims.z_total, "Zref")
-        zc = self._check(Zrec, self.dims.z_total, "Zrec")
-        lp = self._check(Lgain, self.B * self.N * n * ny, "Lgain")
-        yp = self._check(Y, self.B * self.N * ny, "Y")
-        hp = self._check_opt(xhat0, self.B * n, "xhat0")
-        Hd = T.from_numpy(Hh).to(self._dev())
-        new = lambda want, shape: T.zeros(shape, dtype=T.float64, device=self._dev()) if want else None  # noqa: E731
-        Xh, iv = new(with_estimate, (self.B, self.N, n)), new(with_innovations, (self.B, self.N, ny))
-        sc, ll = new(score, (self.B, self.N, 2)), new(score, (self.B,))
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+                raise ValueError(f"{name} is required: tracking_kalman{f.suffix}'s gains, the recorded measurements"
+                                 + f.MEASUREMENTS)
+        Zref, Zrec = f.Z(Zref, "Zref"), f.Z(Zrec, "Zrec")
+        Lgain = f.arr(Lgain, self.B * self.N * n * ny, "Lgain")
+        Y = f.arr(Y, self.B * self.N * ny, "Y")
+        xhat0 = f.x0(xhat0, "xhat0")
+        Hd = f.H(Hh)
+        Xh, iv = f.zeros((self.B, self.N, n), with_estimate), f.zeros((self.B, self.N, ny), with_innovations)
+        sc, ll = f.zeros((self.B, self.N, 2), score), f.zeros((self.B,), score)
         # model None: the existing entries; a model of each record's own: the _model entries, model behind ny
-        mp = () if model is None else (self._check(model, self.B * _lib.MODEL_NP, "model"),)
+        model = f.model(model)
+        mp = () if model is None else (f.ptr(model),)
         sfx = "" if model is None else "_model"
-        args = (self._h, zr, zc, lp, Hd.data_ptr(), ny, *mp, None if Vh is None else Vh.ctypes.data, yp, hp, ptr(Xh), ptr(iv),
-                ptr(sc), ptr(ll))
+        args = (self._h, f.ptr(Zref), f.ptr(Zrec), f.ptr(Lgain), f.ptr(Hd), ny, *mp, _host_ptr(Vh), f.ptr(Y), f.ptr(xhat0),
+                f.ptr(Xh), f.ptr(iv), f.ptr(sc), f.ptr(ll))
         if not guarded:
-            _lib.check(getattr(_lib.lib(), "qln_landing_filter" + sfx)(*args))
+            _lib.check(f.fn("qln_landing_filter" + sfx)(*args))
             return Xh, iv, sc, ll
-        eh = new(with_events, (self.B, _lib.TOUCHDOWN_INFO_STRIDE))
-        _lib.check(getattr(_lib.lib(), "qln_landing_filter_guarded" + sfx)(*args, ptr(eh)))
-        return Xh, iv, sc, ll, eh
-
-    def _filter_host(self, guarded, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, with_events,
-                     model=None):
-        score = (V is not None) if with_score is None else with_score
-        if score and V is None:
-            raise ValueError("V is required with with_score: the measurement variances the gains were designed for")
-        Hh, Vh = measurement_model(H, V) if score else (self._measurement_rows(H), None)
-        ny = Hh.shape[0]
-
-        def flat(a, size, name):
-            if a is None:
-                raise ValueError(f"{name} is required: tracking_kalman_host's gains, the recorded measurements")
-            a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
-            if a.size != size:
-                raise ValueError(f"{name} has {a.size} entries, expected {size}")
-            return a
-
-        Zref, Zrec, xhat0 = self._host_Z(Zref, "Zref"), self._host_Z(Zrec, "Zrec"), self._host_x0(xhat0)
-        Lg, Yh = flat(Lgain, self.B * self.N * n * ny, "Lgain"), flat(Y, self.B * self.N * ny, "Y")
-        Xh = np.zeros((self.B, self.N, n)) if with_estimate else None
-        iv = np.zeros((self.B, self.N, ny)) if with_innovations else None
-        sc = np.zeros((self.B, self.N, 2)) if score else None
-        ll = np.zeros(self.B) if score else None
-        mh = self._host_model(model)
-        mp = () if mh is None else (mh.ctypes.data,)
-        sfx = "" if mh is None else "_model"
-        args = (self._h, Zref.ctypes.data, Zrec.ctypes.data, Lg.ctypes.data, Hh.ctypes.data, ny, *mp, _host_ptr(Vh), Yh.ctypes.data,
-                _host_ptr(xhat0), _host_ptr(Xh), _host_ptr(iv), _host_ptr(sc), _host_ptr(ll))
-        if not guarded:
-            _lib.check(getattr(_lib.lib(), f"qln_landing_filter{sfx}_host")(*args))
-            return Xh, iv, sc, ll
-        eh = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if with_events else None
-        _lib.check(getattr(_lib.lib(), f"qln_landing_filter_guarded{sfx}_host")(*args, _host_ptr(eh)))
+        eh = f.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE), with_events)
+        _lib.check(f.fn("qln_landing_filter_guarded" + sfx)(*args, f.ptr(eh)))
         return Xh, iv, sc, ll, eh
 
     def landing_measurements(self, Zout, Zref, H, vnoise=None):
@@ -1395,35 +1299,35 @@ class HybridNLP:
         unless asked for; which are asked for does not change the others' bits.  A replay of a flight returns its Xhat and
         innov.  model (B, 4) = {g, mb, mf, lb} per record sends the prediction to a model of each record's own
         (qln_landing_filter_model); None is the handle's, and the existing entry.  Stream-ordered."""
-        return self._filter(False, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, False, model)
+        return self._op_filter(_DeviceForm(self), False, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations,
+                               with_score, False, model)
 
     def landing_filter_host(self, Zref, Zrec, Lgain, H, Y, V=None, xhat0=None, with_estimate=True, with_innovations=True,
                             with_score=None, model=None):
         """The same with host arrays (synchronous): numpy (Xhat, innov, score, loglik).  A non-finite H is refused."""
-        return self._filter_host(False, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, False,
-                                 model)
+        return self._op_filter(_HostForm(self), False, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations,
+                               with_score, False, model)
 
     def landing_filter_guarded(self, Zref, Zrec, Lgain, H, Y, V=None, xhat0=None, with_estimate=True, with_innovations=True,
                                with_score=None, with_events=True, model=None):
         """landing_filter with the estimator landing by its own guard, as in tracking_rollout_estimated(guarded=True): returns
         (Xhat, innov, score, loglik, events_hat), events_hat (B, 8) the estimator's touchdown records."""
-        return self._filter(True, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, with_events,
-                            model)
+        return self._op_filter(_DeviceForm(self), True, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations,
+                               with_score, with_events, model)
 
     def landing_filter_guarded_host(self, Zref, Zrec, Lgain, H, Y, V=None, xhat0=None, with_estimate=True,
                                     with_innovations=True, with_score=None, with_events=True, model=None):
         """The same with host arrays (synchronous): numpy (Xhat, innov, score, loglik, events_hat)."""
-        return self._filter_host(True, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations, with_score, with_events,
-                                 model)
+        return self._op_filter(_HostForm(self), True, Zref, Zrec, Lgain, H, Y, V, xhat0, with_estimate, with_innovations,
+                               with_score, with_events, model)
 
     # -- the sweeps through the filter: tangents and cotangents of Xhat, innov, nis and loglik ----------
     FILTER_JVP_OUT = ("Xhat", "innov", "nis", "loglik", "event_hat")
     FILTER_VJP_OUT = ("Y", "Zrec", "Lgain", "xhat0", "model")
 
-    def _filter_sweep(self, host, forward, guarded, Zref, Zrec, Lgain, H, Xhat, innov, V, model, events_hat, given, want):
+    def _op_filter_sweep(self, f, forward, guarded, Zref, Zrec, Lgain, H, Xhat, innov, V, model, events_hat, given, want):
         """One path for the four forms.  given: the tangents (forward) or cotangents by name, None for absent; want: the outputs
-        by name.  Returns a dict of the outputs asked for."""
-        T = None if host else _torch()
+        by name.  Returns a dict of the outputs asked for.  The inputs are checked by the form's loose rule: a Z is not padded."""
         if guarded and events_hat is None:
             raise ValueError("events_hat is required: the record landing_filter_guarded returned")
         Hh, Vh = measurement_model(H, V) if V is not None else (self._measurement_rows(H), None)
@@ -1437,41 +1341,24 @@ class HybridNLP:
         bad = set(want) - set(outs)
         if bad or (not guarded and "event_hat" in want):
             raise ValueError(f"want: unknown outputs {sorted(bad)} ({', '.join(outs)}; event_hat with guarded only)")
-
-        if host:
-            def inp(a, size, name):
-                if a is None:
-                    return None
-                a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
-                if a.size < size:
-                    raise ValueError(f"{name} has {a.size} entries, expected {size}")
-                return a
-            ptr = _host_ptr
-            new = lambda name: np.zeros(shapes[name])  # noqa: E731
-            Hd = Hh
-        else:
-            def inp(a, size, name):
-                return None if a is None else (self._check(a, size, name), a)[1]
-            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-            new = lambda name: T.zeros(shapes[name], dtype=T.float64, device=self._dev())  # noqa: E731
-            Hd = T.from_numpy(Hh).to(self._dev())
+        Hd = f.H(Hh)
         for name, a in (("Zref", Zref), ("Zrec", Zrec), ("Lgain", Lgain), ("Xhat", Xhat)):
             if a is None:
                 raise ValueError(f"{name} is required: the record and the trajectory landing_filter produced")
-        keep = [inp(Zref, self.dims.z_total, "Zref"), inp(Zrec, self.dims.z_total, "Zrec"), inp(Lgain, sizes["Lgain"], "Lgain"),
-                inp(model, sizes["model"], "model"), inp(Xhat, sizes["Xhat"], "Xhat"), inp(innov, sizes["innov"], "innov")]
-        ev = inp(events_hat, sizes["event_hat"], "events_hat") if guarded else None
+        keep = [f.loose(Zref, self.dims.z_total, "Zref"), f.loose(Zrec, self.dims.z_total, "Zrec"),
+                f.loose(Lgain, sizes["Lgain"], "Lgain"), f.loose(model, sizes["model"], "model"),
+                f.loose(Xhat, sizes["Xhat"], "Xhat"), f.loose(innov, sizes["innov"], "innov")]
+        ev = f.loose(events_hat, sizes["event_hat"], "events_hat") if guarded else None
         gnames = ("Y", "Zrec", "Lgain", "xhat0", "model") if forward else ("Xhat", "innov", "nis", "loglik")
-        gin = [inp(given.get(k), sizes[k], k + ("_dot" if forward else "_bar")) for k in gnames]
-        res = {k: new(k) for k in outs if k in want}
-        hp = Hd.ctypes.data if host else Hd.data_ptr()
-        args = [self._h, ptr(keep[0]), ptr(keep[1]), ptr(keep[2]), hp, ny, ptr(keep[3]), _host_ptr(Vh), ptr(keep[4]), ptr(keep[5])]
+        gin = [f.loose(given.get(k), sizes[k], k + ("_dot" if forward else "_bar")) for k in gnames]
+        res = {k: f.zeros(shapes[k]) for k in outs if k in want}
+        args = [self._h, f.ptr(keep[0]), f.ptr(keep[1]), f.ptr(keep[2]), f.ptr(Hd), ny, f.ptr(keep[3]), _host_ptr(Vh),
+                f.ptr(keep[4]), f.ptr(keep[5])]
         if guarded:
-            args.append(ptr(ev))
-        args += [ptr(g) for g in gin]
-        args += [ptr(res.get(k)) for k in outs if guarded or k != "event_hat"]
-        fn = "qln_landing_filter" + ("_guarded" if guarded else "") + ("_jvp" if forward else "_vjp") + ("_host" if host else "")
-        _lib.check(getattr(_lib.lib(), fn)(*args))
+            args.append(f.ptr(ev))
+        args += [f.ptr(g) for g in gin]
+        args += [f.ptr(res.get(k)) for k in outs if guarded or k != "event_hat"]
+        _lib.check(f.fn("qln_landing_filter" + ("_guarded" if guarded else "") + ("_jvp" if forward else "_vjp"))(*args))
         return res
 
     def _filter_jvp_want(self, want, V, Lgain_dot, guarded):
@@ -1490,15 +1377,15 @@ class HybridNLP:
         GAINS, so a score term together with Lgain_dot is refused; innov is needed with Lgain_dot or a score term.  Returns a
         dict of device tensors.  Stream-ordered."""
         given = dict(Y=Y_dot, Zrec=Zrec_dot, Lgain=Lgain_dot, xhat0=xhat0_dot, model=model_dot)
-        return self._filter_sweep(False, True, guarded, Zref, Zrec, Lgain, H, Xhat, innov, V, model, events_hat, given,
-                                  self._filter_jvp_want(want, V, Lgain_dot, guarded))
+        return self._op_filter_sweep(_DeviceForm(self), True, guarded, Zref, Zrec, Lgain, H, Xhat, innov, V, model, events_hat,
+                                     given, self._filter_jvp_want(want, V, Lgain_dot, guarded))
 
     def landing_filter_jvp_host(self, Zref, Zrec, Lgain, H, Xhat, innov=None, V=None, model=None, events_hat=None, guarded=False,
                                 Y_dot=None, Zrec_dot=None, Lgain_dot=None, xhat0_dot=None, model_dot=None, want=None):
         """The same with host arrays (synchronous): a dict of numpy arrays."""
         given = dict(Y=Y_dot, Zrec=Zrec_dot, Lgain=Lgain_dot, xhat0=xhat0_dot, model=model_dot)
-        return self._filter_sweep(True, True, guarded, Zref, Zrec, Lgain, H, Xhat, innov, V, model, events_hat, given,
-                                  self._filter_jvp_want(want, V, Lgain_dot, guarded))
+        return self._op_filter_sweep(_HostForm(self), True, guarded, Zref, Zrec, Lgain, H, Xhat, innov, V, model, events_hat, given,
+                                     self._filter_jvp_want(want, V, Lgain_dot, guarded))
 
     def _filter_vjp_want(self, want, innov, nis_bar, loglik_bar):
         if want is not None:
@@ -1514,15 +1401,15 @@ class HybridNLP:
         that the call can give (Lgain only with innov and without a score cotangent: the score is differentiated at fixed
         gains).  With loglik_bar = 1 the outputs are the gradient of the log-likelihood.  Returns a dict of device tensors."""
         given = dict(Xhat=Xhat_bar, innov=innov_bar, nis=nis_bar, loglik=loglik_bar)
-        return self._filter_sweep(False, False, guarded, Zref, Zrec, Lgain, H, Xhat, innov, V, model, events_hat, given,
-                                  self._filter_vjp_want(want, innov, nis_bar, loglik_bar))
+        return self._op_filter_sweep(_DeviceForm(self), False, guarded, Zref, Zrec, Lgain, H, Xhat, innov, V, model, events_hat,
+                                     given, self._filter_vjp_want(want, innov, nis_bar, loglik_bar))
 
     def landing_filter_vjp_host(self, Zref, Zrec, Lgain, H, Xhat, innov=None, V=None, model=None, events_hat=None, guarded=False,
                                 Xhat_bar=None, innov_bar=None, nis_bar=None, loglik_bar=None, want=None):
         """The same with host arrays (synchronous): a dict of numpy arrays."""
         given = dict(Xhat=Xhat_bar, innov=innov_bar, nis=nis_bar, loglik=loglik_bar)
-        return self._filter_sweep(True, False, guarded, Zref, Zrec, Lgain, H, Xhat, innov, V, model, events_hat, given,
-                                  self._filter_vjp_want(want, innov, nis_bar, loglik_bar))
+        return self._op_filter_sweep(_HostForm(self), False, guarded, Zref, Zrec, Lgain, H, Xhat, innov, V, model, events_hat,
+                                     given, self._filter_vjp_want(want, innov, nis_bar, loglik_bar))
 
     # -- the estimate-feedback roll-out: the plant and the estimator flown together -------------------
     @staticmethod
@@ -1534,6 +1421,41 @@ class HybridNLP:
             raise ValueError(f"H of shape {H.shape}: expected (ny, 15) with 1 <= ny <= {_lib.TRACK_NY_MAX}")
         return np.ascontiguousarray(H)
 
+    def _op_estimated(self, f, limited, Zref, limits, K, Lgain, H, vnoise, wnoise, x0, xhat0, model, guarded, out, with_estimate,
+                      with_innovations, with_events, with_sat=True):
+        """Returns (Zout, Xhat, innov), guarded also (events, events_hat), limited all of them and sat."""
+        lim = force_limits(limits) if limited else None
+        Hh = self._measurement_rows(H)
+        ny = Hh.shape[0]
+        Hd = f.H(Hh)
+        Zref = f.Z(Zref, "Zref")
+        out = f.out(out, (self.dims.z_total,), "out")
+        K = f.K(K)
+        if Lgain is None:
+            raise ValueError(f"Lgain is required: the filter gains tracking_kalman{f.suffix} returned")
+        Lgain = f.arr(Lgain, self.B * self.N * n * ny, "Lgain")
+        vnoise = f.opt(vnoise, self.B * self.N * ny, "vnoise")
+        wnoise = f.opt(wnoise, self.B * (self.N - 1) * n, "wnoise")
+        x0, xhat0, model = f.x0(x0), f.x0(xhat0, "xhat0"), f.model(model)
+        Xh = f.zeros((self.B, self.N, n), with_estimate)
+        iv = f.zeros((self.B, self.N, ny), with_innovations)
+        args = [self._h, f.ptr(Zref), f.ptr(K), f.ptr(Lgain), f.ptr(Hd), ny, f.ptr(vnoise), f.ptr(wnoise), f.ptr(x0), f.ptr(xhat0),
+                f.ptr(model)]
+        if limited:
+            args += [lim.ctypes.data, int(bool(guarded))]
+        args += [f.ptr(out), f.ptr(Xh), f.ptr(iv)]
+        if not (guarded or limited):
+            _lib.check(f.fn("qln_tracking_rollout_estimated")(*args))
+            return out, Xh, iv
+        ev = f.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE), guarded and with_events)
+        eh = f.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE), guarded and with_events)
+        if not limited:
+            _lib.check(f.fn("qln_tracking_rollout_estimated_guarded")(*args, f.ptr(ev), f.ptr(eh)))
+            return out, Xh, iv, ev, eh
+        sat = f.zeros((self.B, self.N - 1), with_sat)
+        _lib.check(f.fn("qln_tracking_rollout_estimated_limited")(*args, f.ptr(ev), f.ptr(eh), f.ptr(sat)))
+        return out, Xh, iv, ev, eh, sat
+
     def tracking_rollout_estimated(self, Zref, K, Lgain, H, vnoise=None, wnoise=None, x0=None, xhat0=None, model=None,
                                    guarded=False, out=None, with_estimate=True, with_innovations=False, with_events=True):
         """The closed loop that feeds back an ESTIMATE, flown on the nonlinear hybrid plant: tracking_rollout_model (guarded
@@ -1543,96 +1465,89 @@ class HybridNLP:
         noise is the caller's: vnoise (B, N, ny) and wnoise (B, N-1, 15) device tensors of samples, None for none; xhat0
         (B, 15), None: the reference's first knot.  Returns (Zout, Xhat, innov), and guarded also (events, events_hat), the
         plant's and the estimator's touchdown records: Xhat (B, N, 15), innov (B, N, ny), each None unless asked for."""
-        T = _torch()
-        Hh = self._measurement_rows(H)
-        ny = Hh.shape[0]
-        Hd = T.from_numpy(Hh).to(self._dev())
-        self._check(Zref, self.dims.z_total, "Zref")
-        out = self.new_Z() if out is None else out
-        self._check(out, self.dims.z_total, "out")
-        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
-        if Lgain is None:
-            raise ValueError("Lgain is required: the filter gains tracking_kalman returned")
-        lp = self._check(Lgain, self.B * self.N * n * ny, "Lgain")
-        vp = self._check_opt(vnoise, self.B * self.N * ny, "vnoise")
-        wp = self._check_opt(wnoise, self.B * (self.N - 1) * n, "wnoise")
-        xp = self._check_opt(x0, self.B * n, "x0")
-        hp = self._check_opt(xhat0, self.B * n, "xhat0")
-        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
-        new = lambda want, shape: T.zeros(shape, dtype=T.float64, device=self._dev()) if want else None  # noqa: E731
-        Xh = new(with_estimate, (self.B, self.N, n))
-        iv = new(with_innovations, (self.B, self.N, ny))
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        if not guarded:
-            _lib.check(_lib.lib().qln_tracking_rollout_estimated(self._h, Zref.data_ptr(), kp, lp, Hd.data_ptr(), ny, vp, wp, xp,
-                                                                 hp, mp, out.data_ptr(), ptr(Xh), ptr(iv)))
-            return out, Xh, iv
-        ev = new(with_events, (self.B, _lib.TOUCHDOWN_INFO_STRIDE))
-        eh = new(with_events, (self.B, _lib.TOUCHDOWN_INFO_STRIDE))
-        _lib.check(_lib.lib().qln_tracking_rollout_estimated_guarded(self._h, Zref.data_ptr(), kp, lp, Hd.data_ptr(), ny, vp, wp,
-                                                                     xp, hp, mp, out.data_ptr(), ptr(Xh), ptr(iv), ptr(ev),
-                                                                     ptr(eh)))
-        return out, Xh, iv, ev, eh
+        return self._op_estimated(_DeviceForm(self), False, Zref, None, K, Lgain, H, vnoise, wnoise, x0, xhat0, model, guarded, out,
+                                  with_estimate, with_innovations, with_events)
 
     def tracking_rollout_estimated_host(self, Zref, K, Lgain, H, vnoise=None, wnoise=None, x0=None, xhat0=None, model=None,
                                         guarded=False, with_estimate=True, with_innovations=False, with_events=True):
         """The same with host arrays (synchronous): numpy (Zout (z_total,), zeros past n_nlp, Xhat, innov) and guarded also
         (events, events_hat).  A non-finite H or model entry, or mb, mf or lb <= 0, is refused."""
-        Hh = self._measurement_rows(H)
-        ny = Hh.shape[0]
-        Zref, K, x0, xhat0 = self._host_Z(Zref, "Zref"), self._host_K(K), self._host_x0(x0), self._host_x0(xhat0)
-        model = self._host_model(model)
-
-        def flat(a, size, name):
-            if a is None:
-                return None
-            a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
-            if a.size != size:
-                raise ValueError(f"{name} has {a.size} entries, expected {size}")
-            return a
-
-        if Lgain is None:
-            raise ValueError("Lgain is required: the filter gains tracking_kalman_host returned")
-        Lg = flat(Lgain, self.B * self.N * n * ny, "Lgain")
-        vn = flat(vnoise, self.B * self.N * ny, "vnoise")
-        wn = flat(wnoise, self.B * (self.N - 1) * n, "wnoise")
-        out = np.zeros(self.dims.z_total)
-        Xh = np.zeros((self.B, self.N, n)) if with_estimate else None
-        iv = np.zeros((self.B, self.N, ny)) if with_innovations else None
-        args = (self._h, Zref.ctypes.data, _host_ptr(K), Lg.ctypes.data, Hh.ctypes.data, ny, _host_ptr(vn), _host_ptr(wn),
-                _host_ptr(x0), _host_ptr(xhat0), _host_ptr(model), out.ctypes.data, _host_ptr(Xh), _host_ptr(iv))
-        if not guarded:
-            _lib.check(_lib.lib().qln_tracking_rollout_estimated_host(*args))
-            return out, Xh, iv
-        ev = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if with_events else None
-        eh = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if with_events else None
-        _lib.check(_lib.lib().qln_tracking_rollout_estimated_guarded_host(*args, _host_ptr(ev), _host_ptr(eh)))
-        return out, Xh, iv, ev, eh
+        return self._op_estimated(_HostForm(self), False, Zref, None, K, Lgain, H, vnoise, wnoise, x0, xhat0, model, guarded, None,
+                                  with_estimate, with_innovations, with_events)
 
     # -- forward and reverse sweeps through the estimate-feedback roll-out ----------------------------
-    def _estimated_traj(self, Zref, K, Lgain, H, Zout, Xhat, innov, model, guarded, events, events_hat, want_gain):
-        """The arguments both sweeps share, checked: (ny, the C arguments up to innov / event_hat, what must stay alive)."""
-        T = _torch()
+    def _op_estimated_traj(self, f, limited, Zref, K, Lgain, H, Zout, Xhat, sat, innov, model, guarded, events, events_hat,
+                           want_gain):
+        """The arguments both sweeps share, checked: (guarded, ny, the C arguments up to innov / event_hat / sat, what must stay
+        alive).  limited: the sweeps at fixed active set, where both records or neither select the blocks, then sat."""
+        if limited:
+            if (events is None) != (events_hat is None):
+                raise ValueError("events and events_hat: both (the guarded blocks) or neither (the knot-scheduled ones)")
+            guarded = events is not None
         Hh = self._measurement_rows(H)
         ny = Hh.shape[0]
-        Hd = T.from_numpy(Hh).to(self._dev())
-        zr = self._check(Zref, self.dims.z_total, "Zref")
-        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
+        Hd = f.H(Hh)
+        Zref, K = f.Z(Zref, "Zref"), f.K(K)
         if Lgain is None or Xhat is None:
-            raise ValueError("Lgain and Xhat are required: the filter gains and the estimates tracking_rollout_estimated returned")
-        lp = self._check(Lgain, self.B * self.N * n * ny, "Lgain")
-        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
-        zo = self._check(Zout, self.dims.z_total, "Zout")
-        xh = self._check(Xhat, self.B * self.N * n, "Xhat")
+            raise ValueError(f.TRAJ)
+        Lgain = f.arr(Lgain, self.B * self.N * n * ny, "Lgain")
+        model = f.model(model)
+        Zout = f.Z(Zout, "Zout")
+        Xhat = f.arr(Xhat, self.B * self.N * n, "Xhat")
         if want_gain and innov is None:
-            raise ValueError("innov is required with a tangent or cotangent of Lgain (with_innovations=True in the roll-out)")
-        ip = self._check_opt(innov if want_gain else None, self.B * self.N * ny, "innov")
-        args = [self._h, zr, kp, lp, C.c_void_p(Hd.data_ptr()), ny, mp, zo, xh, ip]
+            raise ValueError(f.INNOV)
+        innov = f.opt(innov if want_gain else None, self.B * self.N * ny, "innov")
+        keep = [Zref, K, Lgain, Hd, model, Zout, Xhat, innov]
         if guarded:
             if events is None or events_hat is None:
-                raise ValueError("events and events_hat are required: the two records tracking_rollout_estimated returned")
-            args += [self._events_ptr(events), self._check(events_hat, self.B * _lib.TOUCHDOWN_INFO_STRIDE, "events_hat")]
-        return ny, args, Hd
+                raise ValueError(f.RECORDS)
+            keep += [f.events(events), f.events_hat(events_hat)]
+        elif limited:
+            keep += [None, None]
+        if limited:
+            keep.append(f.sat(sat))
+        args = [self._h] + [f.ptr(a) for a in keep]
+        args.insert(5, ny)
+        return guarded, ny, args, keep
+
+    def _op_estimated_jvp(self, f, limited, Zref, K, Lgain, H, Zout, Xhat, sat, innov, model, guarded, events, events_hat,
+                          Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, out, with_estimate, with_innovations,
+                          with_event_dot):
+        guarded, ny, args, keep = self._op_estimated_traj(f, limited, Zref, K, Lgain, H, Zout, Xhat, sat, innov, model, guarded,
+                                                          events, events_hat, Lgain_dot is not None)
+        keep += [f.Z_opt(Zref_dot, "Zref_dot"), f.K(K_dot, "K_dot"), f.opt(Lgain_dot, self.B * self.N * n * ny, "Lgain_dot"),
+                 f.x0(x0_dot, "x0_dot"), f.x0(xhat0_dot, "xhat0_dot"), f.model(model_dot, "model_dot")]
+        out = f.out(out, (self.dims.z_total,), "out")
+        Xd, ivd = f.zeros((self.B, self.N, n), with_estimate), f.zeros((self.B, self.N, ny), with_innovations)
+        args += [f.ptr(a) for a in keep[-6:]] + [f.ptr(out), f.ptr(Xd), f.ptr(ivd)]
+        if not (guarded or limited):
+            _lib.check(f.fn("qln_tracking_rollout_estimated_jvp")(*args))
+            return out, Xd, ivd
+        ed = f.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE), guarded and with_event_dot)
+        ehd = f.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE), guarded and with_event_dot)
+        _lib.check(f.fn("qln_tracking_rollout_estimated" + ("_limited" if limited else "_guarded") + "_jvp")(
+            *args, f.ptr(ed), f.ptr(ehd)))
+        return out, Xd, ivd, ed, ehd
+
+    ESTIMATED_VJP_OUTPUTS = ("Zref", "K", "Lgain", "x0", "xhat0", "model")
+
+    def _op_estimated_vjp(self, f, limited, Zref, K, Lgain, H, Zout, Xhat, sat, Zbar, innov, model, guarded, events, events_hat,
+                          Xhat_bar, innov_bar, want):
+        default = want is None
+        want = self._vjp_want(K, want, self.ESTIMATED_VJP_OUTPUTS)
+        if default and innov is None:
+            want = tuple(w for w in want if w != "Lgain")
+        guarded, ny, args, keep = self._op_estimated_traj(f, limited, Zref, K, Lgain, H, Zout, Xhat, sat, innov, model, guarded,
+                                                          events, events_hat, "Lgain" in want)
+        keep += [f.Z(Zbar, "Zbar"), f.opt(Xhat_bar, self.B * self.N * n, "Xhat_bar"),
+                 f.opt(innov_bar, self.B * self.N * ny, "innov_bar")]
+        shapes = ((self.dims.z_total,), tracking_k_shape(self.B, self.N), (self.B, self.N, n, ny), (self.B, n), (self.B, n),
+                  (self.B, _lib.MODEL_NP))
+        outs = tuple(f.zeros(shape, name in want) for name, shape in zip(self.ESTIMATED_VJP_OUTPUTS, shapes))
+        kind = "_limited" if limited else "_guarded" if guarded else ""
+        _lib.check(f.fn("qln_tracking_rollout_estimated" + kind + "_vjp")(*args, *(f.ptr(a) for a in keep[-3:]),
+                                                                        *(f.ptr(o) for o in outs)))
+        return outs
 
     def tracking_rollout_estimated_jvp(self, Zref, K, Lgain, H, Zout, Xhat, innov=None, model=None, guarded=False, events=None,
                                        events_hat=None, Zref_dot=None, K_dot=None, Lgain_dot=None, x0_dot=None, xhat0_dot=None,
@@ -1642,28 +1557,9 @@ class HybridNLP:
         xhat0_dot, whose None is the forward call's xhat0 = None (the estimate starts on the reference, so its tangent is
         Zref_dot's first knot).  innov is needed only with Lgain_dot.  Returns (Zout_dot, Xhat_dot, innov_dot), and guarded
         also (event_dot, event_hat_dot), each optional one None unless asked for (qln_evaluator.h)."""
-        T = _torch()
-        ny, args, keep = self._estimated_traj(Zref, K, Lgain, H, Zout, Xhat, innov, model, guarded, events, events_hat,
-                                              Lgain_dot is not None)
-        nk = self.B * (self.N - 1) * _lib.TRACK_NU * n
-        args += [self._check_opt(Zref_dot, self.dims.z_total, "Zref_dot"), self._check_opt(K_dot, nk, "K_dot"),
-                 self._check_opt(Lgain_dot, self.B * self.N * n * ny, "Lgain_dot"), self._check_opt(x0_dot, self.B * n, "x0_dot"),
-                 self._check_opt(xhat0_dot, self.B * n, "xhat0_dot"),
-                 self._check_opt(model_dot, self.B * _lib.MODEL_NP, "model_dot")]
-        out = self.new_Z() if out is None else out
-        new = lambda want, shape: T.zeros(shape, dtype=T.float64, device=self._dev()) if want else None  # noqa: E731
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        Xd, ivd = new(with_estimate, (self.B, self.N, n)), new(with_innovations, (self.B, self.N, ny))
-        args += [self._check(out, self.dims.z_total, "out"), ptr(Xd), ptr(ivd)]
-        if not guarded:
-            _lib.check(_lib.lib().qln_tracking_rollout_estimated_jvp(*args))
-            return out, Xd, ivd
-        ed = new(with_event_dot, (self.B, _lib.TOUCHDOWN_INFO_STRIDE))
-        ehd = new(with_event_dot, (self.B, _lib.TOUCHDOWN_INFO_STRIDE))
-        _lib.check(_lib.lib().qln_tracking_rollout_estimated_guarded_jvp(*args, ptr(ed), ptr(ehd)))
-        return out, Xd, ivd, ed, ehd
-
-    ESTIMATED_VJP_OUTPUTS = ("Zref", "K", "Lgain", "x0", "xhat0", "model")
+        return self._op_estimated_jvp(_DeviceForm(self), False, Zref, K, Lgain, H, Zout, Xhat, None, innov, model, guarded, events,
+                                      events_hat, Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, out, with_estimate,
+                                      with_innovations, with_event_dot)
 
     def tracking_rollout_estimated_vjp(self, Zref, K, Lgain, H, Zout, Xhat, Zbar, innov=None, model=None, guarded=False,
                                        events=None, events_hat=None, Xhat_bar=None, innov_bar=None, want=None):
@@ -1672,51 +1568,8 @@ class HybridNLP:
         Lgain_bar, x0_bar, xhat0_bar, model_bar), each None unless named in want (default: all, K_bar only when K is given,
         Lgain_bar only when innov is).  Without "xhat0" in want the cotangent of the initial estimate is added to Zref_bar's
         first knot: the forward call's xhat0 = None."""
-        T = _torch()
-        names = self.ESTIMATED_VJP_OUTPUTS
-        default = want is None
-        want = self._vjp_want(K, want, names)
-        if default and innov is None:
-            want = tuple(w for w in want if w != "Lgain")
-        ny, args, keep = self._estimated_traj(Zref, K, Lgain, H, Zout, Xhat, innov, model, guarded, events, events_hat,
-                                              "Lgain" in want)
-        args += [self._check(Zbar, self.dims.z_total, "Zbar"), self._check_opt(Xhat_bar, self.B * self.N * n, "Xhat_bar"),
-                 self._check_opt(innov_bar, self.B * self.N * ny, "innov_bar")]
-        new = lambda name, shape: T.zeros(shape, dtype=T.float64, device=self._dev()) if name in want else None  # noqa: E731
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        outs = (self.new_Z() if "Zref" in want else None, new("K", tracking_k_shape(self.B, self.N)),
-                new("Lgain", (self.B, self.N, n, ny)), new("x0", (self.B, n)), new("xhat0", (self.B, n)),
-                new("model", (self.B, _lib.MODEL_NP)))
-        fn = _lib.lib().qln_tracking_rollout_estimated_guarded_vjp if guarded else _lib.lib().qln_tracking_rollout_estimated_vjp
-        _lib.check(fn(*args, *(ptr(o) for o in outs)))
-        return outs
-
-    def _host_estimated_traj(self, Zref, K, Lgain, H, Zout, Xhat, innov, model, guarded, events, events_hat, want_gain):
-        Hh = self._measurement_rows(H)
-        ny = Hh.shape[0]
-
-        def flat(a, size, name):
-            if a is None:
-                return None
-            a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
-            if a.size != size:
-                raise ValueError(f"{name} has {a.size} entries, expected {size}")
-            return a
-
-        if Lgain is None or Xhat is None:
-            raise ValueError("Lgain and Xhat are required: what tracking_rollout_estimated_host took and returned")
-        if want_gain and innov is None:
-            raise ValueError("innov is required with a tangent or cotangent of Lgain")
-        keep = [self._host_Z(Zref, "Zref"), self._host_K(K), flat(Lgain, self.B * self.N * n * ny, "Lgain"), Hh,
-                self._host_model(model), self._host_Z(Zout, "Zout"), flat(Xhat, self.B * self.N * n, "Xhat"),
-                flat(innov if want_gain else None, self.B * self.N * ny, "innov")]
-        if guarded:
-            if events is None or events_hat is None:
-                raise ValueError("events and events_hat are required: the two records the roll-out returned")
-            keep += [self._host_events(events), self._host_events(events_hat)]
-        args = [self._h] + [_host_ptr(a) for a in keep]
-        args.insert(5, ny)
-        return ny, args, keep, flat
+        return self._op_estimated_vjp(_DeviceForm(self), False, Zref, K, Lgain, H, Zout, Xhat, None, Zbar, innov, model, guarded,
+                                      events, events_hat, Xhat_bar, innov_bar, want)
 
     def tracking_rollout_estimated_jvp_host(self, Zref, K, Lgain, H, Zout, Xhat, innov=None, model=None, guarded=False,
                                             events=None, events_hat=None, Zref_dot=None, K_dot=None, Lgain_dot=None, x0_dot=None,
@@ -1725,56 +1578,17 @@ class HybridNLP:
         """The same with host arrays (synchronous): numpy (Zout_dot (z_total,), Xhat_dot, innov_dot) and guarded also
         (event_dot, event_hat_dot).  A non-finite H, a model or an event record that the guarded sweeps' host forms refuse,
         is refused."""
-        ny, args, keep, flat = self._host_estimated_traj(Zref, K, Lgain, H, Zout, Xhat, innov, model, guarded, events,
-                                                         events_hat, Lgain_dot is not None)
-        tang = [None if Zref_dot is None else self._host_Z(Zref_dot, "Zref_dot"), self._host_K(K_dot),
-                flat(Lgain_dot, self.B * self.N * n * ny, "Lgain_dot"), self._host_x0(x0_dot), self._host_x0(xhat0_dot),
-                self._host_model(model_dot, "model_dot")]
-        out = np.zeros(self.dims.z_total)
-        Xd = np.zeros((self.B, self.N, n)) if with_estimate else None
-        ivd = np.zeros((self.B, self.N, ny)) if with_innovations else None
-        args += [_host_ptr(a) for a in tang] + [out.ctypes.data, _host_ptr(Xd), _host_ptr(ivd)]
-        if not guarded:
-            _lib.check(_lib.lib().qln_tracking_rollout_estimated_jvp_host(*args))
-            return out, Xd, ivd
-        ed = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if with_event_dot else None
-        ehd = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if with_event_dot else None
-        _lib.check(_lib.lib().qln_tracking_rollout_estimated_guarded_jvp_host(*args, _host_ptr(ed), _host_ptr(ehd)))
-        return out, Xd, ivd, ed, ehd
+        return self._op_estimated_jvp(_HostForm(self), False, Zref, K, Lgain, H, Zout, Xhat, None, innov, model, guarded, events,
+                                      events_hat, Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, None, with_estimate,
+                                      with_innovations, with_event_dot)
 
     def tracking_rollout_estimated_vjp_host(self, Zref, K, Lgain, H, Zout, Xhat, Zbar, innov=None, model=None, guarded=False,
                                             events=None, events_hat=None, Xhat_bar=None, innov_bar=None, want=None):
         """The same with host arrays (synchronous): numpy (Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar, model_bar)."""
-        default = want is None
-        want = self._vjp_want(K, want, self.ESTIMATED_VJP_OUTPUTS)
-        if default and innov is None:
-            want = tuple(w for w in want if w != "Lgain")
-        ny, args, keep, flat = self._host_estimated_traj(Zref, K, Lgain, H, Zout, Xhat, innov, model, guarded, events,
-                                                         events_hat, "Lgain" in want)
-        cot = [self._host_Z(Zbar, "Zbar"), flat(Xhat_bar, self.B * self.N * n, "Xhat_bar"),
-               flat(innov_bar, self.B * self.N * ny, "innov_bar")]
-        new = lambda name, shape: np.zeros(shape) if name in want else None  # noqa: E731
-        outs = (new("Zref", self.dims.z_total), new("K", tracking_k_shape(self.B, self.N)), new("Lgain", (self.B, self.N, n, ny)),
-                new("x0", (self.B, n)), new("xhat0", (self.B, n)), new("model", (self.B, _lib.MODEL_NP)))
-        fn = (_lib.lib().qln_tracking_rollout_estimated_guarded_vjp_host if guarded
-              else _lib.lib().qln_tracking_rollout_estimated_vjp_host)
-        _lib.check(fn(*args, *(_host_ptr(a) for a in cot), *(_host_ptr(o) for o in outs)))
-        return outs
+        return self._op_estimated_vjp(_HostForm(self), False, Zref, K, Lgain, H, Zout, Xhat, None, Zbar, innov, model, guarded,
+                                      events, events_hat, Xhat_bar, innov_bar, want)
 
     # -- contact-aware force limits: the roll-out, its sweeps and the gains at fixed active set ------
-    def _sat_ptr(self, sat):
-        if sat is None:
-            raise ValueError("sat is required: the saturation record tracking_rollout_limited returned with Zout")
-        return self._check(sat, self.B * (self.N - 1), "sat")
-
-    def _host_sat(self, sat):
-        if sat is None:
-            raise ValueError("sat is required: the saturation record tracking_rollout_limited_host returned with Zout")
-        s = np.ascontiguousarray(np.asarray(sat, dtype=np.float64).reshape(-1))
-        if s.size != self.B * (self.N - 1):
-            raise ValueError(f"sat has {s.size} entries, expected {self.B * (self.N - 1)}")
-        return s
-
     def tracking_rollout_limited(self, Zref, limits, K=None, x0=None, model=None, guarded=False, out=None, with_events=True,
                                  with_sat=True):
         """tracking_rollout_model (guarded False: the handle's knot schedule) or tracking_rollout_guarded (guarded True) with
@@ -1785,35 +1599,12 @@ class HybridNLP:
         s_m = 1 at the lower and 2 at the upper limit (unpack_saturation; None without with_sat).  The derivatives at this
         active set are tracking_rollout_limited_jvp / _vjp and the gains tracking_lqr_limited's, which take sat
         (qln_evaluator.h)."""
-        T = _torch()
-        lim = force_limits(limits)
-        self._check(Zref, self.dims.z_total, "Zref")
-        out = self.new_Z() if out is None else out
-        self._check(out, self.dims.z_total, "out")
-        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
-        xp = self._check_opt(x0, self.B * n, "x0")
-        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
-        ev = (T.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE), dtype=T.float64, device=self._dev())
-              if guarded and with_events else None)
-        sat = T.zeros((self.B, self.N - 1), dtype=T.float64, device=self._dev()) if with_sat else None
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        _lib.check(_lib.lib().qln_tracking_rollout_limited(self._h, Zref.data_ptr(), kp, xp, mp, lim.ctypes.data, int(bool(guarded)),
-                                                           out.data_ptr(), ptr(ev), ptr(sat)))
-        return out, ev, sat
+        return self._op_rollout(_DeviceForm(self), "_limited", Zref, K, x0, model, out, limits, guarded, with_events, with_sat)
 
     def tracking_rollout_limited_host(self, Zref, limits, K=None, x0=None, model=None, guarded=False, with_events=True,
                                       with_sat=True):
         """The same with host arrays (synchronous): numpy (Zout (z_total,), events (B, 8) or None, sat (B, N-1) or None)."""
-        lim = force_limits(limits)
-        Zref, K, x0 = self._host_Z(Zref, "Zref"), self._host_K(K), self._host_x0(x0)
-        model = self._host_model(model)
-        out = np.zeros(self.dims.z_total)
-        ev = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if guarded and with_events else None
-        sat = np.zeros((self.B, self.N - 1)) if with_sat else None
-        _lib.check(_lib.lib().qln_tracking_rollout_limited_host(self._h, Zref.ctypes.data, _host_ptr(K), _host_ptr(x0),
-                                                                _host_ptr(model), lim.ctypes.data, int(bool(guarded)),
-                                                                out.ctypes.data, _host_ptr(ev), _host_ptr(sat)))
-        return out, ev, sat
+        return self._op_rollout(_HostForm(self), "_limited", Zref, K, x0, model, None, limits, guarded, with_events, with_sat)
 
     def tracking_rollout_limited_jvp(self, Zref, Zout, sat, events=None, K=None, model=None, Zref_dot=None, K_dot=None,
                                      x0_dot=None, model_dot=None, out=None, with_event_dot=True):
@@ -1821,114 +1612,38 @@ class HybridNLP:
         touchdown knot: the tangent of a force that rode a limit is zero.  events None: the knot-scheduled blocks
         (tracking_rollout_model_jvp's), else the guarded ones.  Returns (Zout_dot, event_dot), event_dot None without events
         or with_event_dot."""
-        T = _torch()
-        nk = self.B * (self.N - 1) * _lib.TRACK_NU * n
-        self._check(Zref, self.dims.z_total, "Zref")
-        self._check(Zout, self.dims.z_total, "Zout")
-        sp = self._sat_ptr(sat)
-        ep = None if events is None else self._events_ptr(events)
-        kp = self._check_opt(K, nk, "K")
-        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
-        zd = self._check_opt(Zref_dot, self.dims.z_total, "Zref_dot")
-        kd = self._check_opt(K_dot, nk, "K_dot")
-        xd = self._check_opt(x0_dot, self.B * n, "x0_dot")
-        md = self._check_opt(model_dot, self.B * _lib.MODEL_NP, "model_dot")
-        out = self.new_Z() if out is None else out
-        self._check(out, self.dims.z_total, "out")
-        ed = (T.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE), dtype=T.float64, device=self._dev())
-              if with_event_dot and events is not None else None)
-        _lib.check(_lib.lib().qln_tracking_rollout_limited_jvp(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), mp, ep, sp, zd, kd,
-                                                               xd, md, out.data_ptr(), None if ed is None else ed.data_ptr()))
-        return out, ed
+        return self._op_rollout_jvp(_DeviceForm(self), "_limited", Zref, Zout, K, model, Zref_dot, K_dot, x0_dot, model_dot, out,
+                                    events, sat, with_event_dot)
 
     def tracking_rollout_limited_jvp_host(self, Zref, Zout, sat, events=None, K=None, model=None, Zref_dot=None, K_dot=None,
                                           x0_dot=None, model_dot=None, with_event_dot=True):
         """The same with host arrays (synchronous): numpy (Zout_dot (z_total,), event_dot (B, 8) or None).  A sat entry that is
         not a saturation code is refused."""
-        Zref, Zout, sat = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout"), self._host_sat(sat)
-        ev = None if events is None else self._host_events(events)
-        K, K_dot, x0_dot = self._host_K(K), self._host_K(K_dot), self._host_x0(x0_dot)
-        model, model_dot = self._host_model(model), self._host_model(model_dot, "model_dot")
-        if Zref_dot is not None:
-            Zref_dot = self._host_Z(Zref_dot, "Zref_dot")
-        out = np.zeros(self.dims.z_total)
-        ed = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if with_event_dot and ev is not None else None
-        _lib.check(_lib.lib().qln_tracking_rollout_limited_jvp_host(
-            self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data, _host_ptr(model), _host_ptr(ev), sat.ctypes.data,
-            _host_ptr(Zref_dot), _host_ptr(K_dot), _host_ptr(x0_dot), _host_ptr(model_dot), out.ctypes.data, _host_ptr(ed)))
-        return out, ed
+        return self._op_rollout_jvp(_HostForm(self), "_limited", Zref, Zout, K, model, Zref_dot, K_dot, x0_dot, model_dot, None,
+                                    events, sat, with_event_dot)
 
     def tracking_rollout_limited_vjp(self, Zref, Zout, sat, Zbar, events=None, K=None, model=None, want=None):
         """Reverse sweep of tracking_rollout_limited at the (Zout, events, sat) it returned, the exact adjoint of
         tracking_rollout_limited_jvp: the rows of K_bar and the force entries of Zref_bar of a channel that rode a limit are
         exact zeros.  Returns (Zref_bar, K_bar, x0_bar, model_bar), each None unless named in want (default: all, K_bar only
         when K is given)."""
-        T = _torch()
-        want = self._vjp_want(K, want, ("Zref", "K", "x0", "model"))
-        self._check(Zref, self.dims.z_total, "Zref")
-        self._check(Zout, self.dims.z_total, "Zout")
-        self._check(Zbar, self.dims.z_total, "Zbar")
-        sp = self._sat_ptr(sat)
-        ep = None if events is None else self._events_ptr(events)
-        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
-        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
-        zb = self.new_Z() if "Zref" in want else None
-        kb = T.zeros(tracking_k_shape(self.B, self.N), dtype=T.float64, device=self._dev()) if "K" in want else None
-        xb = T.zeros((self.B, n), dtype=T.float64, device=self._dev()) if "x0" in want else None
-        mb = T.zeros((self.B, _lib.MODEL_NP), dtype=T.float64, device=self._dev()) if "model" in want else None
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        _lib.check(_lib.lib().qln_tracking_rollout_limited_vjp(self._h, Zref.data_ptr(), kp, Zout.data_ptr(), mp, ep, sp,
-                                                               Zbar.data_ptr(), ptr(zb), ptr(kb), ptr(xb), ptr(mb)))
-        return zb, kb, xb, mb
+        return self._op_rollout_vjp(_DeviceForm(self), "_limited", Zref, Zout, Zbar, K, model, want, events, sat)
 
     def tracking_rollout_limited_vjp_host(self, Zref, Zout, sat, Zbar, events=None, K=None, model=None, want=None):
         """The same with host arrays (synchronous): numpy (Zref_bar, K_bar, x0_bar, model_bar (B, 4))."""
-        want = self._vjp_want(K, want, ("Zref", "K", "x0", "model"))
-        Zref, Zout, Zbar = self._host_Z(Zref, "Zref"), self._host_Z(Zout, "Zout"), self._host_Z(Zbar, "Zbar")
-        K, model, sat = self._host_K(K), self._host_model(model), self._host_sat(sat)
-        ev = None if events is None else self._host_events(events)
-        zb = np.zeros(self.dims.z_total) if "Zref" in want else None
-        kb = np.zeros(tracking_k_shape(self.B, self.N)) if "K" in want else None
-        xb = np.zeros((self.B, n)) if "x0" in want else None
-        mb = np.zeros((self.B, _lib.MODEL_NP)) if "model" in want else None
-        _lib.check(_lib.lib().qln_tracking_rollout_limited_vjp_host(
-            self._h, Zref.ctypes.data, _host_ptr(K), Zout.ctypes.data, _host_ptr(model), _host_ptr(ev), sat.ctypes.data,
-            Zbar.ctypes.data, _host_ptr(zb), _host_ptr(kb), _host_ptr(xb), _host_ptr(mb)))
-        return zb, kb, xb, mb
+        return self._op_rollout_vjp(_HostForm(self), "_limited", Zref, Zout, Zbar, K, model, want, events, sat)
 
     def tracking_lqr_limited(self, Ztraj, sat, Q, R, Qf, events=None, model=None, K=None, P=None, with_cost_to_go=True):
         """tracking_lqr (events None; model must then be None) or tracking_lqr_guarded (events given) at the active set of a
         limited roll-out: the columns of B_k of the channels that rode a limit at knot k (sat) are zero, so their rows of K_k
         are exact zeros and P is the cost-to-go of feedback on the free channels only.  Returns (K, P) as tracking_lqr."""
-        T = _torch()
-        Qh, Rh, Qfh = tracking_weights(Q, R, Qf)
-        self._check(Ztraj, self.dims.z_total, "Ztraj")
-        sp = self._sat_ptr(sat)
-        ep = None if events is None else self._events_ptr(events)
-        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
-        if K is None:
-            K = T.empty(tracking_k_shape(self.B, self.N), dtype=T.float64, device=self._dev())
-        self._check(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
-        if with_cost_to_go and P is None:
-            P = T.empty(tracking_p_shape(self.B, self.N), dtype=T.float64, device=self._dev())
-        if not with_cost_to_go:
-            P = None
-        pp = None if P is None else self._check(P, self.B * self.N * _lib.TRACK_P_NNZ, "P")
-        _lib.check(_lib.lib().qln_tracking_lqr_limited(self._h, Ztraj.data_ptr(), mp, ep, sp, Qh.ctypes.data, Rh.ctypes.data,
-                                                       Qfh.ctypes.data, K.data_ptr(), pp))
-        return K, P
+        return self._op_lqr(_DeviceForm(self), "_limited", Ztraj, Q, R, Qf, events=events, sat=sat, model=model, K=K, P=P,
+                            with_cost_to_go=with_cost_to_go)
 
     def tracking_lqr_limited_host(self, Ztraj, sat, Q, R, Qf, events=None, model=None, with_cost_to_go=True):
         """The same with host arrays (synchronous): returns numpy (K, P)."""
-        Ztraj, sat, model = self._host_Z(Ztraj, "Ztraj"), self._host_sat(sat), self._host_model(model)
-        ev = None if events is None else self._host_events(events)
-        Qh, Rh, Qfh = tracking_weights(Q, R, Qf)
-        K = np.zeros(tracking_k_shape(self.B, self.N))
-        P = np.zeros(tracking_p_shape(self.B, self.N)) if with_cost_to_go else None
-        _lib.check(_lib.lib().qln_tracking_lqr_limited_host(self._h, Ztraj.ctypes.data, _host_ptr(model), _host_ptr(ev),
-                                                            sat.ctypes.data, Qh.ctypes.data, Rh.ctypes.data, Qfh.ctypes.data,
-                                                            K.ctypes.data, _host_ptr(P)))
-        return K, P
+        return self._op_lqr(_HostForm(self), "_limited", Ztraj, Q, R, Qf, events=events, sat=sat, model=model,
+                            with_cost_to_go=with_cost_to_go)
 
     # -- contact-aware force limits in the estimate-feedback roll-out and its sweeps -------------------
     def tracking_rollout_estimated_limited(self, Zref, limits, K, Lgain, H, vnoise=None, wnoise=None, x0=None, xhat0=None,
@@ -1940,80 +1655,15 @@ class HybridNLP:
         plant's own contact mode -- whatever the estimator believes (qln_evaluator.h).  Returns (Zout, Xhat, innov, events,
         events_hat, sat): events and events_hat None when not guarded or without with_events, sat the (B, N-1) saturation
         record of tracking_rollout_limited (None without with_sat), which the sweeps at this active set take."""
-        T = _torch()
-        lim = force_limits(limits)
-        Hh = self._measurement_rows(H)
-        ny = Hh.shape[0]
-        Hd = T.from_numpy(Hh).to(self._dev())
-        self._check(Zref, self.dims.z_total, "Zref")
-        out = self.new_Z() if out is None else out
-        self._check(out, self.dims.z_total, "out")
-        kp = self._check_opt(K, self.B * (self.N - 1) * _lib.TRACK_NU * n, "K")
-        if Lgain is None:
-            raise ValueError("Lgain is required: the filter gains tracking_kalman returned")
-        lp = self._check(Lgain, self.B * self.N * n * ny, "Lgain")
-        vp = self._check_opt(vnoise, self.B * self.N * ny, "vnoise")
-        wp = self._check_opt(wnoise, self.B * (self.N - 1) * n, "wnoise")
-        xp = self._check_opt(x0, self.B * n, "x0")
-        hp = self._check_opt(xhat0, self.B * n, "xhat0")
-        mp = self._check_opt(model, self.B * _lib.MODEL_NP, "model")
-        new = lambda want, shape: T.zeros(shape, dtype=T.float64, device=self._dev()) if want else None  # noqa: E731
-        Xh = new(with_estimate, (self.B, self.N, n))
-        iv = new(with_innovations, (self.B, self.N, ny))
-        ev = new(guarded and with_events, (self.B, _lib.TOUCHDOWN_INFO_STRIDE))
-        eh = new(guarded and with_events, (self.B, _lib.TOUCHDOWN_INFO_STRIDE))
-        sat = new(with_sat, (self.B, self.N - 1))
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        _lib.check(_lib.lib().qln_tracking_rollout_estimated_limited(
-            self._h, Zref.data_ptr(), kp, lp, Hd.data_ptr(), ny, vp, wp, xp, hp, mp, lim.ctypes.data, int(bool(guarded)),
-            out.data_ptr(), ptr(Xh), ptr(iv), ptr(ev), ptr(eh), ptr(sat)))
-        return out, Xh, iv, ev, eh, sat
+        return self._op_estimated(_DeviceForm(self), True, Zref, limits, K, Lgain, H, vnoise, wnoise, x0, xhat0, model, guarded,
+                                  out, with_estimate, with_innovations, with_events, with_sat)
 
     def tracking_rollout_estimated_limited_host(self, Zref, limits, K, Lgain, H, vnoise=None, wnoise=None, x0=None, xhat0=None,
                                                 model=None, guarded=False, with_estimate=True, with_innovations=False,
                                                 with_events=True, with_sat=True):
         """The same with host arrays (synchronous): numpy (Zout (z_total,), Xhat, innov, events, events_hat, sat)."""
-        lim = force_limits(limits)
-        Hh = self._measurement_rows(H)
-        ny = Hh.shape[0]
-        Zref, K, x0, xhat0 = self._host_Z(Zref, "Zref"), self._host_K(K), self._host_x0(x0), self._host_x0(xhat0)
-        model = self._host_model(model)
-
-        def flat(a, size, name):
-            if a is None:
-                return None
-            a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
-            if a.size != size:
-                raise ValueError(f"{name} has {a.size} entries, expected {size}")
-            return a
-
-        if Lgain is None:
-            raise ValueError("Lgain is required: the filter gains tracking_kalman_host returned")
-        Lg = flat(Lgain, self.B * self.N * n * ny, "Lgain")
-        vn = flat(vnoise, self.B * self.N * ny, "vnoise")
-        wn = flat(wnoise, self.B * (self.N - 1) * n, "wnoise")
-        out = np.zeros(self.dims.z_total)
-        Xh = np.zeros((self.B, self.N, n)) if with_estimate else None
-        iv = np.zeros((self.B, self.N, ny)) if with_innovations else None
-        ev = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if guarded and with_events else None
-        eh = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if guarded and with_events else None
-        sat = np.zeros((self.B, self.N - 1)) if with_sat else None
-        _lib.check(_lib.lib().qln_tracking_rollout_estimated_limited_host(
-            self._h, Zref.ctypes.data, _host_ptr(K), Lg.ctypes.data, Hh.ctypes.data, ny, _host_ptr(vn), _host_ptr(wn), _host_ptr(x0),
-            _host_ptr(xhat0), _host_ptr(model), lim.ctypes.data, int(bool(guarded)), out.ctypes.data, _host_ptr(Xh), _host_ptr(iv),
-            _host_ptr(ev), _host_ptr(eh), _host_ptr(sat)))
-        return out, Xh, iv, ev, eh, sat
-
-    def _estimated_limited_traj(self, Zref, K, Lgain, H, Zout, Xhat, sat, innov, model, events, events_hat, want_gain):
-        """_estimated_traj for the sweeps at fixed active set: both records or neither, then sat."""
-        if (events is None) != (events_hat is None):
-            raise ValueError("events and events_hat: both (the guarded blocks) or neither (the knot-scheduled ones)")
-        guarded = events is not None
-        ny, args, keep = self._estimated_traj(Zref, K, Lgain, H, Zout, Xhat, innov, model, guarded, events, events_hat, want_gain)
-        if not guarded:
-            args += [None, None]
-        args.append(self._sat_ptr(sat))
-        return guarded, ny, args, keep
+        return self._op_estimated(_HostForm(self), True, Zref, limits, K, Lgain, H, vnoise, wnoise, x0, xhat0, model, guarded, None,
+                                  with_estimate, with_innovations, with_events, with_sat)
 
     def tracking_rollout_estimated_limited_jvp(self, Zref, K, Lgain, H, Zout, Xhat, sat, innov=None, model=None, events=None,
                                                events_hat=None, Zref_dot=None, K_dot=None, Lgain_dot=None, x0_dot=None,
@@ -2023,57 +1673,17 @@ class HybridNLP:
         tracking_rollout_estimated_jvp with the tangent of every force that rode a limit zero, for everything that reads it.
         events and events_hat both None: the knot-scheduled blocks, both given: the guarded ones.  Returns (Zout_dot, Xhat_dot,
         innov_dot, event_dot, event_hat_dot), the last two None without records or with_event_dot."""
-        T = _torch()
-        guarded, ny, args, keep = self._estimated_limited_traj(Zref, K, Lgain, H, Zout, Xhat, sat, innov, model, events,
-                                                               events_hat, Lgain_dot is not None)
-        nk = self.B * (self.N - 1) * _lib.TRACK_NU * n
-        args += [self._check_opt(Zref_dot, self.dims.z_total, "Zref_dot"), self._check_opt(K_dot, nk, "K_dot"),
-                 self._check_opt(Lgain_dot, self.B * self.N * n * ny, "Lgain_dot"), self._check_opt(x0_dot, self.B * n, "x0_dot"),
-                 self._check_opt(xhat0_dot, self.B * n, "xhat0_dot"),
-                 self._check_opt(model_dot, self.B * _lib.MODEL_NP, "model_dot")]
-        out = self.new_Z() if out is None else out
-        new = lambda want, shape: T.zeros(shape, dtype=T.float64, device=self._dev()) if want else None  # noqa: E731
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        Xd, ivd = new(with_estimate, (self.B, self.N, n)), new(with_innovations, (self.B, self.N, ny))
-        ed = new(guarded and with_event_dot, (self.B, _lib.TOUCHDOWN_INFO_STRIDE))
-        ehd = new(guarded and with_event_dot, (self.B, _lib.TOUCHDOWN_INFO_STRIDE))
-        args += [self._check(out, self.dims.z_total, "out"), ptr(Xd), ptr(ivd), ptr(ed), ptr(ehd)]
-        _lib.check(_lib.lib().qln_tracking_rollout_estimated_limited_jvp(*args))
-        return out, Xd, ivd, ed, ehd
+        return self._op_estimated_jvp(_DeviceForm(self), True, Zref, K, Lgain, H, Zout, Xhat, sat, innov, model, False, events,
+                                      events_hat, Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, out, with_estimate,
+                                      with_innovations, with_event_dot)
 
     def tracking_rollout_estimated_limited_vjp(self, Zref, K, Lgain, H, Zout, Xhat, sat, Zbar, innov=None, model=None, events=None,
                                                events_hat=None, Xhat_bar=None, innov_bar=None, want=None):
         """Reverse sweep of tracking_rollout_estimated_limited, the exact adjoint of tracking_rollout_estimated_limited_jvp: the
         rows of K_bar and the force entries of Zref_bar of a channel that rode a limit are exact zeros.  Arguments and returns
         as tracking_rollout_estimated_vjp, with sat and with the records selecting the blocks."""
-        T = _torch()
-        default = want is None
-        want = self._vjp_want(K, want, self.ESTIMATED_VJP_OUTPUTS)
-        if default and innov is None:
-            want = tuple(w for w in want if w != "Lgain")
-        guarded, ny, args, keep = self._estimated_limited_traj(Zref, K, Lgain, H, Zout, Xhat, sat, innov, model, events,
-                                                               events_hat, "Lgain" in want)
-        args += [self._check(Zbar, self.dims.z_total, "Zbar"), self._check_opt(Xhat_bar, self.B * self.N * n, "Xhat_bar"),
-                 self._check_opt(innov_bar, self.B * self.N * ny, "innov_bar")]
-        new = lambda name, shape: T.zeros(shape, dtype=T.float64, device=self._dev()) if name in want else None  # noqa: E731
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        outs = (self.new_Z() if "Zref" in want else None, new("K", tracking_k_shape(self.B, self.N)),
-                new("Lgain", (self.B, self.N, n, ny)), new("x0", (self.B, n)), new("xhat0", (self.B, n)),
-                new("model", (self.B, _lib.MODEL_NP)))
-        _lib.check(_lib.lib().qln_tracking_rollout_estimated_limited_vjp(*args, *(ptr(o) for o in outs)))
-        return outs
-
-    def _host_estimated_limited_traj(self, Zref, K, Lgain, H, Zout, Xhat, sat, innov, model, events, events_hat, want_gain):
-        if (events is None) != (events_hat is None):
-            raise ValueError("events and events_hat: both (the guarded blocks) or neither (the knot-scheduled ones)")
-        guarded = events is not None
-        ny, args, keep, flat = self._host_estimated_traj(Zref, K, Lgain, H, Zout, Xhat, innov, model, guarded, events, events_hat,
-                                                         want_gain)
-        if not guarded:
-            args += [None, None]
-        keep.append(self._host_sat(sat))
-        args.append(keep[-1].ctypes.data)
-        return guarded, ny, args, keep, flat
+        return self._op_estimated_vjp(_DeviceForm(self), True, Zref, K, Lgain, H, Zout, Xhat, sat, Zbar, innov, model, False,
+                                      events, events_hat, Xhat_bar, innov_bar, want)
 
     def tracking_rollout_estimated_limited_jvp_host(self, Zref, K, Lgain, H, Zout, Xhat, sat, innov=None, model=None, events=None,
                                                     events_hat=None, Zref_dot=None, K_dot=None, Lgain_dot=None, x0_dot=None,
@@ -2081,37 +1691,15 @@ class HybridNLP:
                                                     with_event_dot=True):
         """The same with host arrays (synchronous): numpy (Zout_dot (z_total,), Xhat_dot, innov_dot, event_dot, event_hat_dot).
         A sat entry that is not a saturation code is refused."""
-        guarded, ny, args, keep, flat = self._host_estimated_limited_traj(Zref, K, Lgain, H, Zout, Xhat, sat, innov, model, events,
-                                                                          events_hat, Lgain_dot is not None)
-        tang = [None if Zref_dot is None else self._host_Z(Zref_dot, "Zref_dot"), self._host_K(K_dot),
-                flat(Lgain_dot, self.B * self.N * n * ny, "Lgain_dot"), self._host_x0(x0_dot), self._host_x0(xhat0_dot),
-                self._host_model(model_dot, "model_dot")]
-        out = np.zeros(self.dims.z_total)
-        Xd = np.zeros((self.B, self.N, n)) if with_estimate else None
-        ivd = np.zeros((self.B, self.N, ny)) if with_innovations else None
-        ed = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if guarded and with_event_dot else None
-        ehd = np.zeros((self.B, _lib.TOUCHDOWN_INFO_STRIDE)) if guarded and with_event_dot else None
-        args += [_host_ptr(a) for a in tang] + [out.ctypes.data, _host_ptr(Xd), _host_ptr(ivd), _host_ptr(ed), _host_ptr(ehd)]
-        _lib.check(_lib.lib().qln_tracking_rollout_estimated_limited_jvp_host(*args))
-        return out, Xd, ivd, ed, ehd
+        return self._op_estimated_jvp(_HostForm(self), True, Zref, K, Lgain, H, Zout, Xhat, sat, innov, model, False, events,
+                                      events_hat, Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, None, with_estimate,
+                                      with_innovations, with_event_dot)
 
     def tracking_rollout_estimated_limited_vjp_host(self, Zref, K, Lgain, H, Zout, Xhat, sat, Zbar, innov=None, model=None,
                                                     events=None, events_hat=None, Xhat_bar=None, innov_bar=None, want=None):
         """The same with host arrays (synchronous): numpy (Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar, model_bar)."""
-        default = want is None
-        want = self._vjp_want(K, want, self.ESTIMATED_VJP_OUTPUTS)
-        if default and innov is None:
-            want = tuple(w for w in want if w != "Lgain")
-        guarded, ny, args, keep, flat = self._host_estimated_limited_traj(Zref, K, Lgain, H, Zout, Xhat, sat, innov, model, events,
-                                                                          events_hat, "Lgain" in want)
-        cot = [self._host_Z(Zbar, "Zbar"), flat(Xhat_bar, self.B * self.N * n, "Xhat_bar"),
-               flat(innov_bar, self.B * self.N * ny, "innov_bar")]
-        new = lambda name, shape: np.zeros(shape) if name in want else None  # noqa: E731
-        outs = (new("Zref", self.dims.z_total), new("K", tracking_k_shape(self.B, self.N)), new("Lgain", (self.B, self.N, n, ny)),
-                new("x0", (self.B, n)), new("xhat0", (self.B, n)), new("model", (self.B, _lib.MODEL_NP)))
-        _lib.check(_lib.lib().qln_tracking_rollout_estimated_limited_vjp_host(
-            *args, *(_host_ptr(a) for a in cot), *(_host_ptr(o) for o in outs)))
-        return outs
+        return self._op_estimated_vjp(_HostForm(self), True, Zref, K, Lgain, H, Zout, Xhat, sat, Zbar, innov, model, False, events,
+                                      events_hat, Xhat_bar, innov_bar, want)
 
     def differentiable_rollout(self, Zref, K=None, x0=None, model=None, guarded=False, limits=None):
         """tracking_rollout as a torch autograd op: returns Zout, differentiable in Zref, K and x0 (each a float64 CUDA

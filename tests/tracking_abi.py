@@ -14,12 +14,13 @@ SYMBOLS = sorted(n for n in _lib.SIGNATURES if n.startswith("qln_tracking_"))
 HOST_ONLY = {"Qdiag": 15, "Qfdiag": 15, "Rdiag": 4, "Wdiag": 15, "Vdiag": 8, "lim": 8}  # host arrays in the device forms too
 
 
-def parameter_names():
-    """name -> the parameter names of its prototype in the header, the handle left out"""
+def parameter_names(families=("tracking",)):
+    """name -> the parameter names of its prototype in the header, the handle left out; families: of qln_tracking_* and
+    qln_landing_*, the ones to read"""
     src = open(os.path.join(ROOT, "include", "qln_evaluator.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     out = {}
-    for name, params in re.findall(r"\bint\s+(qln_tracking_[a-z_]+)\s*\(([^)]*)\)\s*;", src):
+    for name, params in re.findall(r"\bint\s+(qln_(?:%s)_[a-z_]+)\s*\(([^)]*)\)\s*;" % "|".join(families), src):
         out[name] = [re.search(r"(\w+)\s*$", p).group(1) for p in params.split(",")][1:]
     return out
 
