@@ -5,6 +5,8 @@
 //   * the compact four-slots-per-column form of A = d x+/d x: a_slot, a_coupling, checked against the union pattern;
 //   * the mapping itself -- one problem per row, four problems per wave: Row16 / row16_of;
 //   * a knot's twenty doubles across a row: knot_load / knot_store.
+// What the sweeps with a symmetric 15 x 15 matrix per row in LDS add to this (the covariance sweep, the Kalman sweep) -- the
+// image, its tiles, the dense chains, the congruence step, the marginals -- is qln_image15.h, on top of this file.
 #pragma once
 
 #include "qln_kernel_common.h"

@@ -46,6 +46,12 @@
 // Expanded, that is A Sigma A' - (A G')B' - B (G A') + B M B' with G = K Sigma and M = G K', grouped so that nothing but
 // K v crosses lanes.  Zout's knot (two coalesced loads, handed out through LDS) and the K tile are loaded one knot ahead;
 // the clearance row's cosine is taken for sixteen knots at a time, one per lane.
+// The image is stated in qln_image15.h, for this sweep and k_tracking_kalman (k_landing_smoother takes the stride and sym_at
+// from it and keeps its own knot, for its launch time): its stride and triangle
+// (sym_at, Image15), the packed, K and gain tiles in and out (tile_fill / tile_store), the dense chains on broadcast reads with
+// their rows-in-flight fence (chain_rows), the knot's two applications with the transpose between them (congruence) and the
+// marginals (marginals_store).  Here stay the kernels' LDS layouts, the operators (cov_apply, cov_apply_touchdown,
+// block_apply_t) and what reads a guarded record: guard_event, touchdown_block_at, touchdown_time_forms.
 //
 // k_tracking_rollout_jvp: the forward (tangent) sweep of the roll-out, the adjoint of the reverse sweep in
 // its mapping: one problem per row of sixteen lanes, lane j < 15 owns dx[j], row j of [A_k B_k] and column j of K and Kdot;
@@ -77,7 +83,7 @@
 // (qln_tracking_kalman / _guarded), in k_tracking_covariance's mapping and on its blocks, operator and
 // applications (cov_apply, cov_apply_touchdown): per knot a measurement update of the error covariance P -- H P by chains on
 // broadcast LDS reads, S = H P H' + V by row sums, an 8 x 8 L D L' in every lane, the Joseph form through the image -- and two
-// predictions, P's open loop and the estimate covariance M's closed loop, each in an image of its own.
+// predictions, P's open loop and the estimate covariance M's closed loop, each a congruence step in an image of its own.
 //
 // k_tracking_rollout_estimated: the loop that filter designs, flown (qln_tracking_rollout_estimated / _guarded):
 // the plant and the estimator rolled out side by side in k_tracking_rollout's mapping, one lane per problem, on its step and its
@@ -103,7 +109,7 @@
 // k_landing_filter_jvp / k_landing_filter_vjp: the sweeps through that filter and its score at fixed gains
 // (qln_landing_filter_jvp / _vjp): the estimator's half of k_tracking_rollout_estimated_jvp / _vjp in their row
 // mapping and on their step functions, with a model tangent on that half.
-#include "qln_row16.h"
+#include "qln_image15.h"
 
 #include <utility>
 
@@ -190,6 +196,25 @@ __device__ __forceinline__ TouchdownBlock touchdown_block(const Model& M, const 
     T.tv = tau * iw;
     T.tF = -(0.5 * tau * tau) * iw / M.mf;
     return T;
+}
+// touchdown_block on a knot's twenty entries (x_k, u_k) in LDS
+__device__ __forceinline__ TouchdownBlock touchdown_block_at(const double* z, const Model& M, const KnotMode md, double tau) {
+    double xk[15];
+#pragma unroll
+    for (int i = 0; i < 14; ++i) xk[i] = z[i];
+    xk[14] = 0.0;  // the clock feeds nothing
+    const double u5[5] = {z[15], z[16], z[17], z[18], z[19]};
+    return touchdown_block(M, md, tau, xk, u5);
+}
+// a problem's touchdown knot and tau from its event record; without kGuard nothing is read and there is no such knot
+struct GuardEvent {
+    int ks;
+    double tau;
+};
+template <bool kGuard>
+__device__ __forceinline__ GuardEvent guard_event(const double* __restrict__ event, int bc, int N) {
+    if constexpr (kGuard) return {guard_knot(event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc], N), event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + 1]};
+    else return {-1, 0.0};
 }
 // The two legs' blocks are formed where an application uses them, one after the other, from the leg's length passed through
 // an empty asm: what stays live between a knot's applications is the TouchdownBlock, not two StepBlocks of fifty values.
@@ -347,12 +372,9 @@ __global__ __launch_bounds__(kWave) void k_tracking_lqr(BatchParams P, TrackWeig
     const bool own = r16.own, valid = r16.valid;
     const Model Mp = plant_model<kModel>(P, model, bc);
     const Model& M = kGuard ? Mp : r16.M;
-    [[maybe_unused]] int ks = -1;
-    [[maybe_unused]] double tau = 0.0;
-    if constexpr (kGuard) {
-        ks = guard_knot(event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc], N);
-        tau = event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + 1];
-    }
+    const GuardEvent ev = guard_event<kGuard>(event, bc, N);
+    [[maybe_unused]] const int ks = ev.ks;
+    [[maybe_unused]] const double tau = ev.tau;
     double* __restrict__ L = lds + r16.row * kLRow;
     const double* __restrict__ Zb = Zref + (int64_t)bc * P.z_stride;
     const int jp = a_coupling(j), jq = jp < 0 ? 0 : jp;
@@ -1016,12 +1038,9 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, c
     const double* __restrict__ Zb = Zbar + (int64_t)bc * P.z_stride;
     const double* __restrict__ Zr = Kbar ? Zref + (int64_t)bc * P.z_stride : nullptr;
     const double* __restrict__ Kb = kHasK ? Kg + (int64_t)bc * (N - 1) * (QLN_TRACK_NU * QLN_NX) : nullptr;
-    [[maybe_unused]] int ks = -1;
-    [[maybe_unused]] double tau = 0.0;
-    if constexpr (kGuard) {
-        ks = guard_knot(event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc], N);
-        tau = event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + 1];
-    }
+    const GuardEvent ev = guard_event<kGuard>(event, bc, N);
+    [[maybe_unused]] const int ks = ev.ks;
+    [[maybe_unused]] const double tau = ev.tau;
 
     // ---- lane j's constant pattern: what column j of A, row j of B and h_j are built from ----
     const bool pos = j < 7;                 // position row (h^2/2 in B) or velocity / clock row (h)
@@ -1197,14 +1216,26 @@ __global__ __launch_bounds__(kWave) void k_tracking_rollout_vjp(BatchParams P, c
 
 // ---- k_tracking_covariance ----
 // per-row LDS image (doubles): Sigma / V image [15][17] (one region: V lives there between the two applications) | K [4][16] |
-// the knot's 20 entries of Zout | the clearance derivatives of sixteen knots
-constexpr int kCStr = 17, kCImg = 0, kCK = 256, kCZ = kCK + 4 * 16, kCD = kCZ + 20, kCRow = kCD + 16;
-static_assert(15 * kCStr <= kCK && kCK % 2 == 0 && kCZ % 2 == 0 && kCD % 2 == 0 && kCRow % 2 == 0,
+// the knot's 20 entries of Zout | the clearance derivatives of sixteen knots.  The image, its tiles, the chains and the
+// congruence step of this kernel, k_tracking_kalman and k_landing_smoother: qln_image15.h.
+constexpr int kCImg = 0, kCK = 256, kCZ = kCK + 4 * 16, kCD = kCZ + 20, kCRow = kCD + 16;
+static_assert(kImgSize <= kCK - kCImg && kCK % 2 == 0 && kCZ % 2 == 0 && kCD % 2 == 0 && kCRow % 2 == 0,
               "the image fits; 16-byte aligned sections");
 
 struct CovNoise {
     double w[15];
 };
+
+// g = K v on the K tile (rows of sixteen); zeros without K
+template <bool kHasK>
+__device__ __forceinline__ void k_times(const double* Kl, const double (&v)[15], double (&g)[4]) {
+    if constexpr (kHasK) {
+        chain_rows([&](int m, int c) { return Kl[16 * m + c]; }, v, g);
+    } else {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) g[m] = 0.0;
+    }
+}
 
 // out = Acl v = A v - B (K v); g = K v (4).  The block's entries are formed where they are used (the weight x force
 // products of rows 2 and 9 included): what stays live between the knot's two applications is the StepBlock, not 70 entries.
@@ -1213,21 +1244,7 @@ __device__ __forceinline__ void cov_apply(const StepBlock& blk, const double* Kl
                                           double (&out)[15], double (&g)[4]) {
 #pragma unroll
     for (int i = 0; i < 15; ++i) out[i] = 0.0;
-    if constexpr (kHasK) {
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            double acc = Kl[16 * m] * v[0];
-#pragma unroll
-            for (int c = 1; c < 15; ++c) acc = fma(Kl[16 * m + c], v[c], acc);
-            // one row of K in flight at a time: the empty asm holds this row's sum in front of the next row's reads (left
-            // to itself the compiler issues all four rows' reads first, 120 registers)
-            asm volatile("" : "+v"(acc) : : "memory");
-            g[m] = acc;
-        }
-    } else {
-#pragma unroll
-        for (int m = 0; m < 4; ++m) g[m] = 0.0;
-    }
+    k_times<kHasK>(Kl, v, g);
     // the h-weights pass through an empty asm, as in the evaluator's tile loop: the 25 weight x force products are then
     // formed here, in each application, instead of living in 50 registers across both
     StepBlock bk = blk;
@@ -1244,19 +1261,35 @@ template <bool kHasK>
 __device__ __forceinline__ void cov_apply_touchdown(const TouchdownBlock& tb, const Model& M, const double* Kl, const double (&v)[15],
                                                     double (&out)[15], double (&g)[4]) {
     double f[4];
+    k_times<kHasK>(Kl, v, g);
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        double acc = 0.0;
-        if constexpr (kHasK) {
-            acc = Kl[16 * m] * v[0];
-#pragma unroll
-            for (int c = 1; c < 15; ++c) acc = fma(Kl[16 * m + c], v[c], acc);
-            asm volatile("" : "+v"(acc) : : "memory");  // one row of K in flight at a time, as in cov_apply
-        }
-        g[m] = acc;
-        f[m] = -acc;
-    }
+    for (int m = 0; m < 4; ++m) f[m] = -g[m];
     touchdown_apply<kHasK>(tb, M, v, f, out);
+}
+
+// The touchdown time's row against a symmetric matrix X, as lane j sees it.  r = t_x, with kWithK r = t_x - K' t_F on the free
+// foot's force row of the K tile Kl; x(i): entry i of X's column j.  q = r' X r and q14 = (r + e_14)' X (r + e_14), the variances
+// of tau and of the touchdown clock: lane j's share is r_j (r . x) and (r_j + [j == 14]) (r . x + x_14), and the row sums are
+// the quadratic forms.  kSelect14: e_14 joins r_j by a select (the covariance sweep) instead of an added 0.0 or 1.0 (the Kalman
+// sweep); the two differ in the sign of a zero, and each sweep keeps its bits.
+template <bool kWithK, bool kSelect14, class Col>
+__device__ __forceinline__ void touchdown_time_forms(const TouchdownBlock& tb, const KnotMode md, const double* Kl, Col x, int j,
+                                                     bool own, double& q, double& q14) {
+    const int iy = md.f2free ? 6 : 4, iv = md.f2free ? 13 : 11;
+    [[maybe_unused]] const double* Kf = Kl + 16 * (md.f2free ? 3 : 1);
+    double sc = 0.0, rj = 0.0, x14 = 0.0;
+#pragma unroll
+    for (int i = 0; i < 15; ++i) {
+        double ri = (i == 4 || i == 6) ? ((i == iy) ? tb.ty : 0.0) : (i == 11 || i == 13) ? ((i == iv) ? tb.tv : 0.0) : 0.0;
+        if constexpr (kWithK) ri = fma(-Kf[i], tb.tF, ri);
+        const double xi = x(i);
+        sc = fma(xi, ri, sc);
+        rj = (i == j) ? ri : rj;
+        x14 = xi;
+    }
+    q = row_sum16(own ? rj * sc : 0.0);
+    const double r14 = kSelect14 ? (j == 14 ? rj + 1.0 : rj) : rj + ((j == 14) ? 1.0 : 0.0);
+    q14 = row_sum16(own ? r14 * (sc + x14) : 0.0);
 }
 
 // Sigma_0 = Sigma0[b] (or the shared one), Sigma_{k+1} = Acl_k Sigma_k Acl_k' + diag(W) at Zout's knots; Sig gets every
@@ -1265,10 +1298,10 @@ __device__ __forceinline__ void cov_apply_touchdown(const TouchdownBlock& tb, co
 // kGuard (qln_tracking_covariance_guarded, with kModel): the blocks of the guarded sweeps at Zout's (x_k, u_k) -- the
 // problem's model (plant_model), guard_mode's modes of the touchdown knot ks read with tau from event, and at ks the knot's
 // two applications are the composite operator's (cov_apply_touchdown), Acl* = A* - B* K.  ev_var (null: not written) gets the
-// variance of tau, c' Sigma_ks c with c = t_x - K_ks' t_F, and of the touchdown clock, the same with c + e_14: lane j takes
-// Sigma's column j against c, and the row sum against c_j is the quadratic form.  Both are 0 without a touchdown.
+// variance of tau, c' Sigma_ks c with c = t_x - K_ks' t_F, and of the touchdown clock, the same with c + e_14
+// (touchdown_time_forms).  Both are 0 without a touchdown.
 template <bool kHasK, bool kModel, bool kGuard>
-__global__ __launch_bounds__(kWave) void k_tracking_covariance(BatchParams P, CovNoise Wn, const double* __restrict__ Zout,
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_tracking_covariance(BatchParams P, CovNoise Wn, const double* __restrict__ Zout,
                                                                const double* __restrict__ Kg, const double* __restrict__ Sigma0,
                                                                int sigma0_batch, double* __restrict__ Sig,
                                                                double* __restrict__ mg, const double* __restrict__ model,
@@ -1280,52 +1313,31 @@ __global__ __launch_bounds__(kWave) void k_tracking_covariance(BatchParams P, Co
     const bool own = r16.own, valid = r16.valid;
     const Model Mp = plant_model<kModel>(P, model, bc);
     const Model& M = kGuard ? Mp : r16.M;
-    [[maybe_unused]] int ks = -1;
-    [[maybe_unused]] double tau = 0.0, var_tau = 0.0, var_clock = 0.0;
-    if constexpr (kGuard) {
-        ks = guard_knot(event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc], N);
-        tau = event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + 1];
-    }
+    const GuardEvent ev = guard_event<kGuard>(event, bc, N);
+    [[maybe_unused]] double var_tau = 0.0, var_clock = 0.0;
     double* L = lds + r16.row * kCRow;
+    const Image15 Sg{L + kCImg, j, own};
     const double* __restrict__ Zb = Zout + (int64_t)bc * P.z_stride;
     const double* __restrict__ Kb = kHasK ? Kg + (int64_t)bc * (N - 1) * (QLN_TRACK_NU * QLN_NX) : nullptr;
     double* __restrict__ Sb = Sig ? Sig + (int64_t)bc * N * QLN_TRACK_P_NNZ : nullptr;
     double* __restrict__ Mb = mg ? mg + (int64_t)bc * N * QLN_TRACK_MARG_STRIDE : nullptr;
 
-    // where the packed entries ln + 16 t lie in the image's lower triangle, the K entries ln + 16 t in the K tile (rows
-    // padded to 16); sym(c): entry (max(c, j), min(c, j)) of the lane's column -- the lower triangle is the one that is read
     int po[8], ko[4];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        const int i = min(ln + 16 * t, QLN_TRACK_P_NNZ - 1);
-        int r = 0;
-#pragma unroll
-        for (int q = 1; q < 15; ++q) r += (i >= q * (q + 1) / 2) ? 1 : 0;
-        po[t] = kCImg + kCStr * r + (i - r * (r + 1) / 2);
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int i = min(ln + 16 * t, QLN_TRACK_NU * QLN_NX - 1);
-        const int m = i / 15;
-        ko[t] = kCK + 16 * m + (i - 15 * m);
-    }
-    const int rowj = kCImg + kCStr * j, colj = kCImg + j;
-    auto sym = [&](int c) { return (c <= j) ? rowj + c : colj + kCStr * c; };
+    packed_offsets(ln, po);
+    k_offsets(ln, kCK, ko);
     double wj = 0.0;
 #pragma unroll
     for (int i = 0; i < 15; ++i) wj = (i == j) ? Wn.w[i] : wj;
 
     // Sigma_0: the packed tile into the image's lower triangle
+    const TileLane tl{ln, ln};  // this sweep has the scalar registers for hoisted tail masks (TileLane)
     {
         const double* __restrict__ S0 = Sigma0 + (int64_t)(sigma0_batch == 1 ? 0 : bc) * QLN_TRACK_P_NNZ;
-#pragma unroll
-        for (int t = 0; t < 8; ++t)
-            if (ln + 16 * t < QLN_TRACK_P_NNZ) L[po[t]] = S0[ln + 16 * t];
+        tile_fill(Sg.a, po, QLN_TRACK_P_NNZ, tl, [&](int t) { return S0[ln + 16 * t]; });
     }
     wave_lds_sync();
-    double s[15];
-#pragma unroll
-    for (int c = 0; c < 15; ++c) s[c] = L[sym(c)];
+    double s[15];  // the lane's column of Sigma_k, carried from knot to knot
+    Sg.column(s);
 
     // the clearance row's derivative entry needs a cosine: lane ln takes knot k0 + ln, once every sixteen knots
     auto clearance_derivatives = [&](int k0) {
@@ -1333,124 +1345,61 @@ __global__ __launch_bounds__(kWave) void k_tracking_covariance(BatchParams P, Co
     };
     // Sigma_k and its marginals leave from the image's lower triangle; fv: the knot's force variances
     auto emit = [&](int k, const double (&fv)[4]) {
-        if (Sb && valid) {
-            double* __restrict__ o = Sb + (int64_t)k * QLN_TRACK_P_NNZ;
-#pragma unroll
-            for (int t = 0; t < 8; ++t)
-                if (ln + 16 * t < QLN_TRACK_P_NNZ) o[ln + 16 * t] = L[po[t]];
-        }
-        if (Mb) {
-            const double dth = L[kCD + (k & 15)];
-            const double s11 = L[kCImg + kCStr * 1 + 1], s21 = L[kCImg + kCStr * 2 + 1], s22 = L[kCImg + kCStr * 2 + 2];
-            double mv[QLN_TRACK_MARG_STRIDE];
-            mv[0] = fma(dth, fma(dth, s22, 2.0 * s21), s11);  // a' Sigma a, a = e_yb + dth e_theta
-#pragma unroll
-            for (int m = 0; m < 4; ++m) mv[1 + m] = fv[m];
-            mv[5] = L[kCImg + (kCStr + 1) * 4];
-            mv[6] = L[kCImg + (kCStr + 1) * 6];
-            const double dj = L[kCImg + (kCStr + 1) * j];
-            mv[7] = row_sum16(own ? dj : 0.0);
-            double v = mv[0];
-#pragma unroll
-            for (int q = 1; q < QLN_TRACK_MARG_STRIDE; ++q) v = (ln == q) ? mv[q] : v;
-            if (valid && ln < QLN_TRACK_MARG_STRIDE) Mb[(int64_t)k * QLN_TRACK_MARG_STRIDE + ln] = v;
-        }
+        const auto sat = [&](int o) { return Sg.a[o]; };
+        if (Sb && valid) tile_store(Sb + (int64_t)k * QLN_TRACK_P_NNZ, po, QLN_TRACK_P_NNZ, tl, sat);
+        if (Mb) marginals_store(Mb + (int64_t)k * QLN_TRACK_MARG_STRIDE, L[kCD + (k & 15)], fv, sat, Sg, valid, tl);
     };
 
     // Zout's knot (20 entries: lane ln takes ln and ln + 16) and the knot's K entries: requested one knot ahead
     double zn[2], kn[4];
     knot_load(Zb, ln, zn[0], zn[1]);
-    if constexpr (kHasK) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) kn[t] = Kb[min(ln + 16 * t, QLN_TRACK_NU * QLN_NX - 1)];
-    }
+    if constexpr (kHasK) k_request(Kb, ln, kn);
 
     for (int k = 0; k < N - 1; ++k) {
         if (Mb && (k & 15) == 0) clearance_derivatives(k);
         L[kCZ + ln] = zn[0];
         if (ln < 4) L[kCZ + 16 + ln] = zn[1];
-        if constexpr (kHasK) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-                if (ln + 16 * t < QLN_TRACK_NU * QLN_NX) L[ko[t]] = kn[t];
-        }
+        if constexpr (kHasK) tile_fill(L, ko, QLN_TRACK_NU * QLN_NX, tl, [&](int t) { return kn[t]; });
         if (k + 1 < N - 1) {
             knot_load(Zb + 20 * (k + 1), ln, zn[0], zn[1]);
-            if constexpr (kHasK) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-                    kn[t] = Kb[(int64_t)(k + 1) * (QLN_TRACK_NU * QLN_NX) + min(ln + 16 * t, QLN_TRACK_NU * QLN_NX - 1)];
-            }
+            if constexpr (kHasK) k_request(Kb + (int64_t)(k + 1) * (QLN_TRACK_NU * QLN_NX), ln, kn);
         }
         wave_lds_sync();  // the knot and the K tile are in place
         KnotMode md;
-        if constexpr (kGuard) md = guard_mode(k, ks, im);
+        if constexpr (kGuard) md = guard_mode(k, ev.ks, im);
         else md = knot_mode(k + 1, kt - 1, im);
-        const bool td = kGuard && k == ks;  // the touchdown knot: the composite operator in the block's place
+        const bool td = kGuard && k == ev.ks;  // the touchdown knot: the composite operator in the block's place
         [[maybe_unused]] TouchdownBlock tb;
         StepBlock blk;
-        // ---- 1. V column j = Acl Sigma column j; the force variances; Sigma_k leaves ----
-        double out[15], g[4], fv[4];
         if (td) {
-            double xk[15];
-#pragma unroll
-            for (int i = 0; i < 14; ++i) xk[i] = L[kCZ + i];
-            xk[14] = 0.0;  // the clock feeds nothing
-            const double u5[5] = {L[kCZ + 15], L[kCZ + 16], L[kCZ + 17], L[kCZ + 18], L[kCZ + 19]};
-            tb = touchdown_block(M, md, tau, xk, u5);
-            cov_apply_touchdown<kHasK>(tb, M, L + kCK, s, out, g);
-            // the variances of tau and of the touchdown clock: c = t_x - K' t_F on the free foot's force row
-            if (ev_var) {
-                const int iy = md.f2free ? 6 : 4, iv = md.f2free ? 13 : 11;
-                const double* Kf = L + kCK + 16 * (md.f2free ? 3 : 1);
-                double sc = 0.0, cj = 0.0;
-#pragma unroll
-                for (int i = 0; i < 15; ++i) {
-                    double ci = (i == 4 || i == 6) ? ((i == iy) ? tb.ty : 0.0) : (i == 11 || i == 13) ? ((i == iv) ? tb.tv : 0.0) : 0.0;
-                    if constexpr (kHasK) ci = fma(-Kf[i], tb.tF, ci);
-                    sc = fma(s[i], ci, sc);
-                    cj = (i == j) ? ci : cj;
-                }
-                const double s14 = s[14];  // Sigma column j against e_14
-                var_tau = row_sum16(own ? cj * sc : 0.0);
-                // (c + e_14)' Sigma (c + e_14): lane j's share is (c_j + [j == 14]) (sc + Sigma_{14,j})
-                var_clock = row_sum16(own ? (j == 14 ? cj + 1.0 : cj) * (sc + s14) : 0.0);
-            }
+            tb = touchdown_block_at(L + kCZ, M, md, ev.tau);
+            if (ev_var) touchdown_time_forms<kHasK, true>(tb, md, L + kCK, [&](int i) { return s[i]; }, j, own, var_tau, var_clock);
         } else {
             blk = step_block(L + kCZ, md, M);
-            cov_apply<kHasK>(blk, L + kCK, s, out, g);
         }
+        // Sigma_{k+1} = Acl Sigma_k Acl' + diag(W).  Behind the first application g = K Sigma column j, whose row sums against
+        // K column j are the force variances (diag of M = G K'), and Sigma_k leaves.
+        double g[4];
+        congruence_from(
+            Sg, s,
+            [&](const double (&v)[15], double (&out)[15]) {
+                if (td) cov_apply_touchdown<kHasK>(tb, M, L + kCK, v, out, g);
+                else cov_apply<kHasK>(blk, L + kCK, v, out, g);
+            },
+            [&] {
+                double fv[4];
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            fv[m] = 0.0;
-            if constexpr (kHasK) {
-                if (Mb) fv[m] = row_sum16(own ? L[kCK + 16 * m + j] * g[m] : 0.0);
-            }
-        }
-        emit(k, fv);
-        wave_lds_sync();  // the image has been read: V may overwrite it
-        if (own) {
-#pragma unroll
-            for (int i = 0; i < 15; ++i) L[kCImg + kCStr * j + i] = out[i];
-        }
-        wave_lds_sync();
-        // ---- 2. column j of Sigma_{k+1} = Acl (row j of V)' + W_j e_j, stored as row j of the image ----
-        double vt[15];
-#pragma unroll
-        for (int c = 0; c < 15; ++c) vt[c] = L[kCImg + kCStr * c + j];
-        if (td) cov_apply_touchdown<kHasK>(tb, M, L + kCK, vt, out, g);
-        else cov_apply<kHasK>(blk, L + kCK, vt, out, g);
-        wave_lds_sync();  // every lane holds its row of V: Sigma_{k+1} may overwrite the image
-        if (own) {
-#pragma unroll
-            for (int i = 0; i < 15; ++i) L[kCImg + kCStr * j + i] = out[i];
-            L[kCImg + (kCStr + 1) * j] = L[kCImg + (kCStr + 1) * j] + wj;
-        }
-        wave_lds_sync();
-        // only the lower triangle is read from here on: Sigma_{k+1} is exactly symmetric
-#pragma unroll
-        for (int c = 0; c < 15; ++c) s[c] = L[sym(c)];
-        // the K tile and the knot are rewritten at the top of the next knot, after this knot's last read of them
+                for (int m = 0; m < 4; ++m) {
+                    fv[m] = 0.0;
+                    if constexpr (kHasK) {
+                        if (Mb) fv[m] = row_sum16(own ? L[kCK + 16 * m + j] * g[m] : 0.0);
+                    }
+                }
+                emit(k, fv);
+            },
+            wj);
+        wave_lds_sync();  // Sigma_{k+1} is in place; the K tile and the knot may be rewritten
+        Sg.column(s);
     }
     if (Mb && ((N - 1) & 15) == 0) {
         clearance_derivatives(N - 1);
@@ -1467,9 +1416,9 @@ __global__ __launch_bounds__(kWave) void k_tracking_covariance(BatchParams P, Co
 // ---- k_tracking_kalman ----
 // per-row LDS image (doubles): the P image [15][17] | the M image [15][17] | K [4][16] | the knot's 20 entries of Zout | the
 // clearance derivatives of sixteen knots | the H tile [8][16], V in its column 15 | the L tile [15][8]
-constexpr int kKStr = 17, kKP = 0, kKM = 256, kKK = 512, kKZ = kKK + 4 * 16, kKD = kKZ + 20, kKH = kKD + 16,
+constexpr int kKP = 0, kKM = 256, kKK = 512, kKZ = kKK + 4 * 16, kKD = kKZ + 20, kKH = kKD + 16,
               kKL = kKH + QLN_TRACK_NY_MAX * 16, kKRow = kKL + 15 * QLN_TRACK_NY_MAX;
-static_assert(15 * kKStr <= kKM - kKP && 15 * kKStr <= kKK - kKM && kKZ % 2 == 0 && kKD % 2 == 0 && kKH % 2 == 0 && kKL % 2 == 0 &&
+static_assert(kImgSize <= kKM - kKP && kImgSize <= kKK - kKM && kKZ % 2 == 0 && kKD % 2 == 0 && kKH % 2 == 0 && kKL % 2 == 0 &&
                   kKRow % 2 == 0,
               "the images fit; 16-byte aligned sections");
 
@@ -1511,13 +1460,10 @@ __global__ __launch_bounds__(kWave) void k_tracking_kalman(BatchParams P, Kalman
     const bool own = r16.own, valid = r16.valid;
     const Model Mp = plant_model<kModel>(P, model, bc);
     const Model& M = kGuard ? Mp : r16.M;
-    [[maybe_unused]] int ks = -1;
-    [[maybe_unused]] double tau = 0.0, var_tau = 0.0, var_clock = 0.0;
-    if constexpr (kGuard) {
-        ks = guard_knot(event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc], N);
-        tau = event[(int64_t)QLN_TOUCHDOWN_INFO_STRIDE * bc + 1];
-    }
+    const GuardEvent ev = guard_event<kGuard>(event, bc, N);
+    [[maybe_unused]] double var_tau = 0.0, var_clock = 0.0;
     double* L = lds + r16.row * kKRow;
+    const Image15 Pm{L + kKP, j, own}, Mm{L + kKM, j, own};
     const double* __restrict__ Zb = Zout + (int64_t)bc * P.z_stride;
     const double* __restrict__ Kb = kHasK ? Kg + (int64_t)bc * (N - 1) * (QLN_TRACK_NU * QLN_NX) : nullptr;
     double* __restrict__ Lb = Lg ? Lg + (int64_t)bc * N * (QLN_NX * ny) : nullptr;
@@ -1525,37 +1471,20 @@ __global__ __launch_bounds__(kWave) void k_tracking_kalman(BatchParams P, Kalman
     double* __restrict__ Sb = (kHasK && Sig) ? Sig + (int64_t)bc * N * QLN_TRACK_P_NNZ : nullptr;
     double* __restrict__ Mb = (kHasK && mg) ? mg + (int64_t)bc * N * QLN_TRACK_MARG_STRIDE : nullptr;
 
-    // where the packed entries ln + 16 t lie in an image's lower triangle (relative to the image), the K entries in the K tile
-    // and the entries of a knot's [15][ny] gain in the L tile (rows of eight)
     int po[8], ko[4], lo[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        const int i = min(ln + 16 * t, QLN_TRACK_P_NNZ - 1);
-        int r = 0;
-#pragma unroll
-        for (int q = 1; q < 15; ++q) r += (i >= q * (q + 1) / 2) ? 1 : 0;
-        po[t] = kKStr * r + (i - r * (r + 1) / 2);
-        const int g = min(ln + 16 * t, QLN_NX * ny - 1), gr = g / ny;
-        lo[t] = kKL + NY * gr + (g - ny * gr);
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int i = min(ln + 16 * t, QLN_TRACK_NU * QLN_NX - 1);
-        const int m = i / 15;
-        ko[t] = kKK + 16 * m + (i - 15 * m);
-    }
-    const int rowj = kKStr * j, colj = j;
-    auto sym = [&](int c) { return (c <= j) ? rowj + c : colj + kKStr * c; };  // relative to the image
+    packed_offsets(ln, po);
+    k_offsets(ln, kKK, ko);
+    gain_offsets(ln, ny, kKL, lo);
     double wj = 0.0;
 #pragma unroll
     for (int i = 0; i < 15; ++i) wj = (i == j) ? Nz.w[i] : wj;
+    const auto Hrow = [&](int r, int c) { return L[kKH + 16 * r + c]; };  // H(r, c); V_r in column 15
+    const auto Lrow = [&](int i, int r) { return L[kKL + NY * i + r]; };  // the gain's L(i, r)
 
     // P^-_0 = Sigma0: the packed tile into the image's lower triangle; M^-_0 = 0; the H tile, zero rows behind ny
     {
         const double* __restrict__ S0 = Sigma0 + (int64_t)(sigma0_batch == 1 ? 0 : bc) * QLN_TRACK_P_NNZ;
-#pragma unroll
-        for (int t = 0; t < 8; ++t)
-            if (ln + 16 * t < QLN_TRACK_P_NNZ) L[kKP + po[t]] = S0[ln + 16 * t];
+        tile_fill(Pm.a, po, QLN_TRACK_P_NNZ, tile_lane(ln), [&](int t) { return S0[ln + 16 * t]; });
         if constexpr (kHasK) {
 #pragma unroll
             for (int t = 0; t < 16; ++t) L[kKM + ln + 16 * t] = 0.0;
@@ -1568,62 +1497,27 @@ __global__ __launch_bounds__(kWave) void k_tracking_kalman(BatchParams P, Kalman
     auto clearance_derivatives = [&](int k0) {
         L[kKD + ln] = clearance_dtheta(Zb[20 * min(k0 + ln, N - 1) + 2], M.lb);
     };
-    // the entry at offset o of X_k = M_k + P^+_k (the filter alone: of P^+_k)
-    auto xat = [&](int o) {
-        if constexpr (kHasK) return L[kKM + o] + L[kKP + o];
-        else return L[kKP + o];
+    // the entry at offset o of P^+_k and of X_k = M_k + P^+_k (the filter alone: of P^+_k)
+    const auto pat = [&](int o) { return Pm.a[o]; };
+    const auto xat = [&](int o) {
+        if constexpr (kHasK) return Mm.a[o] + Pm.a[o];
+        else return Pm.a[o];
     };
     // the knot's outputs leave from the L tile and the images' lower triangles; fv: the knot's force variances
     auto emit = [&](int k, const double (&fv)[4]) {
-        // the stores' predicates are formed here from an opaque copy of ln: hoisted out of the knot loop, the sixteen lane
-        // masks of the tiles' tails stayed in scalar registers through every knot and pushed other scalars out
-        int le = ln;
-        asm volatile("" : "+v"(le));
-        if (Lb && valid) {
-            double* __restrict__ o = Lb + (int64_t)k * (QLN_NX * ny);
-#pragma unroll
-            for (int t = 0; t < 8; ++t)
-                if (le + 16 * t < QLN_NX * ny) o[ln + 16 * t] = L[lo[t]];
-        }
-        if (Pb && valid) {
-            double* __restrict__ o = Pb + (int64_t)k * QLN_TRACK_P_NNZ;
-#pragma unroll
-            for (int t = 0; t < 8; ++t)
-                if (le + 16 * t < QLN_TRACK_P_NNZ) o[ln + 16 * t] = L[kKP + po[t]];
-        }
+        const TileLane tl = tile_lane(ln);
+        if (Lb && valid) tile_store(Lb + (int64_t)k * (QLN_NX * ny), lo, QLN_NX * ny, tl, [&](int o) { return L[o]; });
+        if (Pb && valid) tile_store(Pb + (int64_t)k * QLN_TRACK_P_NNZ, po, QLN_TRACK_P_NNZ, tl, pat);
         if constexpr (kHasK) {
-            if (Sb && valid) {
-                double* __restrict__ o = Sb + (int64_t)k * QLN_TRACK_P_NNZ;
-#pragma unroll
-                for (int t = 0; t < 8; ++t)
-                    if (le + 16 * t < QLN_TRACK_P_NNZ) o[ln + 16 * t] = xat(po[t]);
-            }
-            if (Mb) {
-                const double dth = L[kKD + (k & 15)];
-                const double s11 = xat(kKStr * 1 + 1), s21 = xat(kKStr * 2 + 1), s22 = xat(kKStr * 2 + 2);
-                double mv[QLN_TRACK_MARG_STRIDE];
-                mv[0] = fma(dth, fma(dth, s22, 2.0 * s21), s11);  // a' X a, a = e_yb + dth e_theta
-#pragma unroll
-                for (int m = 0; m < 4; ++m) mv[1 + m] = fv[m];
-                mv[5] = xat((kKStr + 1) * 4);
-                mv[6] = xat((kKStr + 1) * 6);
-                const double dj = xat((kKStr + 1) * j);
-                mv[7] = row_sum16(own ? dj : 0.0);
-                double v = mv[0];
-#pragma unroll
-                for (int q = 1; q < QLN_TRACK_MARG_STRIDE; ++q) v = (le == q) ? mv[q] : v;
-                if (valid && le < QLN_TRACK_MARG_STRIDE) Mb[(int64_t)k * QLN_TRACK_MARG_STRIDE + ln] = v;
-            }
+            if (Sb && valid) tile_store(Sb + (int64_t)k * QLN_TRACK_P_NNZ, po, QLN_TRACK_P_NNZ, tl, xat);
+            if (Mb) marginals_store(Mb + (int64_t)k * QLN_TRACK_MARG_STRIDE, L[kKD + (k & 15)], fv, xat, Pm, valid, tl);
         }
     };
 
     // Zout's knot and the knot's K entries: requested one knot ahead, as in k_tracking_covariance
     double zn[2] = {0.0, 0.0}, kn[4];
     if (N > 1) knot_load(Zb, ln, zn[0], zn[1]);
-    if constexpr (kHasK) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) kn[t] = Kb[min(ln + 16 * t, QLN_TRACK_NU * QLN_NX - 1)];
-    }
+    if constexpr (kHasK) k_request(Kb, ln, kn);
 
     for (int k = 0; k < N; ++k) {
         const bool last = k == N - 1;  // the last knot has an update and no step
@@ -1631,45 +1525,29 @@ __global__ __launch_bounds__(kWave) void k_tracking_kalman(BatchParams P, Kalman
         if (!last) {
             L[kKZ + ln] = zn[0];
             if (ln < 4) L[kKZ + 16 + ln] = zn[1];
-            if constexpr (kHasK) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-                    if (ln + 16 * t < QLN_TRACK_NU * QLN_NX) L[ko[t]] = kn[t];
-            }
+            if constexpr (kHasK) tile_fill(L, ko, QLN_TRACK_NU * QLN_NX, tile_lane(ln), [&](int t) { return kn[t]; });
             if (k + 1 < N - 1) {
                 knot_load(Zb + 20 * (k + 1), ln, zn[0], zn[1]);
-                if constexpr (kHasK) {
-#pragma unroll
-                    for (int t = 0; t < 4; ++t)
-                        kn[t] = Kb[(int64_t)(k + 1) * (QLN_TRACK_NU * QLN_NX) + min(ln + 16 * t, QLN_TRACK_NU * QLN_NX - 1)];
-                }
+                if constexpr (kHasK) k_request(Kb + (int64_t)(k + 1) * (QLN_TRACK_NU * QLN_NX), ln, kn);
             }
         }
         wave_lds_sync();  // the knot and the K tile are in place
 
         // ---- the measurement update: L_k, P^+_k and M_k ----
         double p[15], x[NY];
-#pragma unroll
-        for (int c = 0; c < 15; ++c) p[c] = L[kKP + sym(c)];
+        Pm.column(p);
         {
             double G[NY];
-#pragma unroll
-            for (int r = 0; r < NY; ++r) {
-                double acc = L[kKH + 16 * r] * p[0];
-#pragma unroll
-                for (int c = 1; c < 15; ++c) acc = fma(L[kKH + 16 * r + c], p[c], acc);
-                asm volatile("" : "+v"(acc) : : "memory");  // one row of H in flight at a time, as K in cov_apply
-                G[r] = acc;
-            }
+            chain_rows(Hrow, p, G);
             double S[NY][NY], dd[NY], dinv[NY];  // the lower triangle; below the diagonal it becomes the unit factor
             double hj[NY];                         // column j of H
 #pragma unroll
-            for (int r = 0; r < NY; ++r) hj[r] = L[kKH + 16 * r + j];
+            for (int r = 0; r < NY; ++r) hj[r] = Hrow(r, j);
 #pragma unroll
             for (int a = 0; a < NY; ++a) {
 #pragma unroll
                 for (int b = 0; b <= a; ++b) S[a][b] = row_sum16(own ? G[a] * hj[b] : 0.0);
-                S[a][a] += L[kKH + 16 * a + 15];
+                S[a][a] += Hrow(a, 15);
             }
 #pragma unroll
             for (int c = 0; c < NY; ++c) {
@@ -1709,60 +1587,29 @@ __global__ __launch_bounds__(kWave) void k_tracking_kalman(BatchParams P, Kalman
                 for (int r = 0; r < NY; ++r) L[kKL + NY * j + r] = x[r];
             }
             wave_lds_sync();  // the L tile is in place, and every lane holds its column of P^-
-            // column j of (I - L H) P^- -> row j of the image
             double u[15];
-#pragma unroll
-            for (int i = 0; i < 15; ++i) {
-                double acc = p[i];
-#pragma unroll
-                for (int r = 0; r < NY; ++r) acc = fma(-L[kKL + NY * i + r], G[r], acc);
-                asm volatile("" : "+v"(acc) : : "memory");  // one row of L in flight at a time
-                u[i] = acc;
-            }
-            if (own) {
-#pragma unroll
-                for (int i = 0; i < 15; ++i) L[kKP + kKStr * j + i] = u[i];
-            }
+            chain_rows_sub(Lrow, G, p, u);  // column j of (I - L H) P^- -> row j of the image
+            Pm.store_row(u);
         }
         wave_lds_sync();
         {
-            double vt[15], t[NY];
+            double vt[15], t[NY], out[15];
+            Pm.transposed(vt);
+            chain_rows(Hrow, vt, t);
 #pragma unroll
-            for (int c = 0; c < 15; ++c) vt[c] = L[kKP + kKStr * c + j];
-#pragma unroll
-            for (int r = 0; r < NY; ++r) {
-                double acc = L[kKH + 16 * r] * vt[0];
-#pragma unroll
-                for (int c = 1; c < 15; ++c) acc = fma(L[kKH + 16 * r + c], vt[c], acc);
-                asm volatile("" : "+v"(acc) : : "memory");
-                t[r] = fma(-L[kKH + 16 * r + 15], x[r], acc);  // H v - V .* (row j of L): the Joseph form's two terms share L
-            }
-            double out[15];
-#pragma unroll
-            for (int i = 0; i < 15; ++i) {
-                double acc = vt[i];
-#pragma unroll
-                for (int r = 0; r < NY; ++r) acc = fma(-L[kKL + NY * i + r], t[r], acc);
-                asm volatile("" : "+v"(acc) : : "memory");
-                out[i] = acc;
-            }
+            for (int r = 0; r < NY; ++r) t[r] = fma(-Hrow(r, 15), x[r], t[r]);  // H v - V .* (row j of L): the Joseph form's two terms share L
+            chain_rows_sub(Lrow, t, vt, out);
             wave_lds_sync();  // every lane holds its row: P^+ may overwrite the image
-            if (own) {
-#pragma unroll
-                for (int i = 0; i < 15; ++i) L[kKP + kKStr * j + i] = out[i];
-            }
+            Pm.store_row(out);
         }
         wave_lds_sync();
         // only the lower triangle of P^+_k is read from here on; M_k = M^-_k + (P^-_k - P^+_k), entry by entry
         if constexpr (kHasK) {
             double m[15];
 #pragma unroll
-            for (int c = 0; c < 15; ++c) m[c] = L[kKM + sym(c)] + (p[c] - L[kKP + sym(c)]);
+            for (int c = 0; c < 15; ++c) m[c] = Mm.a[Mm.sym(c)] + (p[c] - Pm.a[Pm.sym(c)]);
             wave_lds_sync();  // M^- has been read
-            if (own) {
-#pragma unroll
-                for (int i = 0; i < 15; ++i) L[kKM + kKStr * j + i] = m[i];
-            }
+            Mm.store_row(m);
             wave_lds_sync();
         }
         const double fv0[4] = {0.0, 0.0, 0.0, 0.0};
@@ -1772,94 +1619,44 @@ __global__ __launch_bounds__(kWave) void k_tracking_kalman(BatchParams P, Kalman
         }
 
         KnotMode md;
-        if constexpr (kGuard) md = guard_mode(k, ks, im);
+        if constexpr (kGuard) md = guard_mode(k, ev.ks, im);
         else md = knot_mode(k + 1, kt - 1, im);
-        // The two predictions of the knot, M's first (its K m gives the force variances, so the knot's outputs leave in between).
-        // apply(hasK, v, out, g): out = (A - B K) v or A v on the knot's operator.  The knot's body exists once per operator --
-        // the step block's and the touchdown knot's -- so that neither form's values stay live across the other's applications;
-        // the hand-offs through LDS stay inside a row, whose sixteen lanes take the same form.
+        // The two predictions of the knot, M's first (its K m gives the force variances, so the knot's outputs leave behind its
+        // first application).  apply(hasK, v, out, g): out = (A - B K) v or A v on the knot's operator.  The knot's body exists
+        // once per operator -- the step block's and the touchdown knot's -- so that neither form's values stay live across the
+        // other's applications; the hand-offs through LDS stay inside a row, whose sixteen lanes take the same form.
         auto predict = [&](auto apply) {
-            double out[15], g[4];
+            double g[4];
             if constexpr (kHasK) {
-                double fv[4] = {0.0, 0.0, 0.0, 0.0}, m[15];  // M_k's column, read back: nothing of the update stays live
+                congruence(
+                    Mm, [&](const double (&v)[15], double (&out)[15]) { apply(std::true_type{}, v, out, g); },
+                    [&] {
+                        double fv[4] = {0.0, 0.0, 0.0, 0.0};
+                        if (Mb) {
 #pragma unroll
-                for (int c = 0; c < 15; ++c) m[c] = L[kKM + sym(c)];
-                apply(std::true_type{}, m, out, g);
-                if (Mb) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) fv[q] = row_sum16(own ? L[kKK + 16 * q + j] * g[q] : 0.0);
-                }
-                emit(k, fv);
-                wave_lds_sync();  // the M image has been read
-                if (own) {
-#pragma unroll
-                    for (int i = 0; i < 15; ++i) L[kKM + kKStr * j + i] = out[i];
-                }
-                wave_lds_sync();
-                double vt[15];
-#pragma unroll
-                for (int c = 0; c < 15; ++c) vt[c] = L[kKM + kKStr * c + j];
-                apply(std::true_type{}, vt, out, g);
-                wave_lds_sync();
-                if (own) {
-#pragma unroll
-                    for (int i = 0; i < 15; ++i) L[kKM + kKStr * j + i] = out[i];
-                }
+                            for (int q = 0; q < 4; ++q) fv[q] = row_sum16(own ? L[kKK + 16 * q + j] * g[q] : 0.0);
+                        }
+                        emit(k, fv);
+                    });
             } else {
                 emit(k, fv0);
             }
             // P^-_{k+1} = A P^+_k A' + diag(W): k_tracking_covariance's open-loop knot
-            double s[15];
-#pragma unroll
-            for (int c = 0; c < 15; ++c) s[c] = L[kKP + sym(c)];
-            apply(std::false_type{}, s, out, g);
-            wave_lds_sync();  // the image has been read
-            if (own) {
-#pragma unroll
-                for (int i = 0; i < 15; ++i) L[kKP + kKStr * j + i] = out[i];
-            }
-            wave_lds_sync();
-#pragma unroll
-            for (int c = 0; c < 15; ++c) s[c] = L[kKP + kKStr * c + j];
-            apply(std::false_type{}, s, out, g);
-            wave_lds_sync();
-            if (own) {
-#pragma unroll
-                for (int i = 0; i < 15; ++i) L[kKP + kKStr * j + i] = out[i];
-                L[kKP + (kKStr + 1) * j] = L[kKP + (kKStr + 1) * j] + wj;
-            }
+            congruence(Pm, [&](const double (&v)[15], double (&out)[15]) { apply(std::false_type{}, v, out, g); }, [] {}, wj);
         };
-        if (kGuard && k == ks) {  // the touchdown knot: the composite operator in the block's place
-            double xk[15];
-#pragma unroll
-            for (int i = 0; i < 14; ++i) xk[i] = L[kKZ + i];
-            xk[14] = 0.0;  // the clock feeds nothing
-            const double u5[5] = {L[kKZ + 15], L[kKZ + 16], L[kKZ + 17], L[kKZ + 18], L[kKZ + 19]};
-            const TouchdownBlock tb = touchdown_block(M, md, tau, xk, u5);
+        if (kGuard && k == ev.ks) {  // the touchdown knot: the composite operator in the block's place
+            const TouchdownBlock tb = touchdown_block_at(L + kKZ, M, md, ev.tau);
             // the variances of tau and of the touchdown clock: c' M c + t_x' P^+ t_x with c = t_x - K' t_F, then with e_14 added
-            // to both; lane j takes column j of M against c and of P^+ against t_x, and the row sums are the quadratic forms
+            // to both; lane j takes column j of M against c and of P^+ against t_x (touchdown_time_forms)
             if constexpr (kHasK) {
                 if (ev_var) {
-                    const int iy = md.f2free ? 6 : 4, iv = md.f2free ? 13 : 11;
-                    const double* Kf = L + kKK + 16 * (md.f2free ? 3 : 1);
-                    double sc = 0.0, cj = 0.0, sp = 0.0, tj = 0.0, p14 = 0.0, m14 = 0.0;
-                    int je = j;  // an opaque copy, as emit's: the fifteen masks i == j are formed here, not ahead of the loop
+                    int je = j;  // an opaque copy, as a tile's lane: the fifteen masks i == j are formed here, not ahead of the loop
                     asm volatile("" : "+v"(je));
-#pragma unroll
-                    for (int i = 0; i < 15; ++i) {
-                        const double ti = (i == 4 || i == 6) ? ((i == iy) ? tb.ty : 0.0) : (i == 11 || i == 13) ? ((i == iv) ? tb.tv : 0.0) : 0.0;
-                        const double ci = fma(-Kf[i], tb.tF, ti);
-                        const double pi = L[kKP + sym(i)], mi = L[kKM + sym(i)];
-                        sc = fma(mi, ci, sc);
-                        sp = fma(pi, ti, sp);
-                        cj = (i == je) ? ci : cj;
-                        tj = (i == je) ? ti : tj;
-                        p14 = pi;
-                        m14 = mi;
-                    }
-                    const double e14 = (je == 14) ? 1.0 : 0.0;
-                    var_tau = row_sum16(own ? cj * sc : 0.0) + row_sum16(own ? tj * sp : 0.0);
-                    var_clock = row_sum16(own ? (cj + e14) * (sc + m14) : 0.0) + row_sum16(own ? (tj + e14) * (sp + p14) : 0.0);
+                    double qm, qm14, qp, qp14;
+                    touchdown_time_forms<true, false>(tb, md, L + kKK, [&](int i) { return Mm.a[Mm.sym(i)]; }, je, own, qm, qm14);
+                    touchdown_time_forms<false, false>(tb, md, L + kKK, [&](int i) { return Pm.a[Pm.sym(i)]; }, je, own, qp, qp14);
+                    var_tau = qm + qp;
+                    var_clock = qm14 + qp14;
                 }
             }
             predict([&](auto hasK, const double (&v)[15], double (&out)[15], double (&g)[4]) {
@@ -1881,8 +1678,11 @@ __global__ __launch_bounds__(kWave) void k_tracking_kalman(BatchParams P, Kalman
 
 // ---- k_landing_smoother ----
 // per-row LDS image (doubles): the P^+ image [15][17] (Ps_k leaves from it) | the Theta image [15][17] | the L tile [15][8] | the
-// H tile [8][16], 1/V in its column 15 | the knot's 20 entries of Ztraj | q [16] | r [16] | the knot's innovations [8]
-constexpr int kSStr = 17, kSP = 0, kSTh = 256, kSL = 512, kSH = kSL + 15 * QLN_TRACK_NY_MAX, kSZ = kSH + QLN_TRACK_NY_MAX * 16,
+// H tile [8][16], 1/V in its column 15 | the knot's 20 entries of Ztraj | q [16] | r [16] | the knot's innovations [8].
+// This kernel keeps its own statement of the knot, on qln_image15.h's stride and sym_at alone: on the shared accessors, tiles,
+// chains and congruence step its guarded form launched 0.3 % slower (profiles/sym_image_timing.txt), and any of the shared offset
+// tables, guard_event or touchdown_block_at changes its device assembly, which as it stands is the one it had before that header.
+constexpr int kSStr = kImgStr, kSP = 0, kSTh = 256, kSL = 512, kSH = kSL + 15 * QLN_TRACK_NY_MAX, kSZ = kSH + QLN_TRACK_NY_MAX * 16,
               kSQ = kSZ + 20, kSR = kSQ + 16, kSI = kSR + 16, kSRow = kSI + QLN_TRACK_NY_MAX;
 static_assert(15 * kSStr <= kSTh - kSP && 15 * kSStr <= kSL - kSTh && kSH % 2 == 0 && kSZ % 2 == 0 && kSQ % 2 == 0 && kSR % 2 == 0 &&
                   kSI % 2 == 0 && kSRow % 2 == 0 && kSRow <= kKRow,
@@ -1903,9 +1703,6 @@ __device__ __forceinline__ void block_apply_t(const StepBlock& blk, const double
         if constexpr (c < 15) out[c] = fma(val, v[r], out[c]);
     });
 }
-
-// entry (i, c) of a symmetric image, read from its lower triangle
-__host__ __device__ constexpr int sym_at(int i, int c) { return (i >= c) ? kSStr * i + c : kSStr * c + i; }
 
 // The fixed-interval smoother of a flown landing (include/qln_evaluator.h): the modified Bryson-Frazier sweep,
 // backward from knot N-1 on the filter's own gains L_k and covariances P^+_k, which inverts nothing.  The mapping of
