@@ -1159,6 +1159,57 @@ int qln_landing_smoother_guarded(qln_handle* h, const double* Ztraj, const doubl
 int qln_landing_smoother_guarded_host(qln_handle* h, const double* Ztraj, const double* model, const double* event,
                                       const double* Lgain, const double* Pest, const double* H, int32_t ny, const double* Vdiag,
                                       const double* Xhat, const double* innov, double* Xs, double* Ps);
+/* The forward sweep through the DESIGN of the filter: how the gains, the error covariances and log det S_k of
+ * qln_tracking_kalman* move when V, W or Sigma0 move -- the first question of noise identification and of a sensitivity study of
+ * the estimator, and with qln_landing_filter_jvp the total derivative of the likelihood through the gains' design.  (The entries
+ * stand outside the qln_tracking_ prefix, as the smoother's and the filter's do.)  It runs at what the design returned, the
+ * gains L_k = Lgain[b][k], and re-runs nothing: neither P^-, Sigma0, W nor a factorisation is read.  At the optimal gain the
+ * Joseph form is stationary in L (S L' = H P^- cancels the dL term), so with dotted quantities as tangents, for k = 0 .. N-1:
+ *     Pd^-_0     = Sigma0_dot
+ *     Gd         = H Pd^-_k                                        (ny x 15)
+ *     Sd_k       = Gd H' + diag(V_dot)                             (ny x ny, symmetric)
+ *     Sinv_k     = diag(1/V) (I - H L_k)                           (the smoother's identity; symmetric for optimal gains)
+ *     Ld_k       = (Pd^-_k H' - L_k Sd_k) Sinv_k                   (15 x ny)
+ *     logdet_dot_k = sum_ab Sinv_k[a][b] Sd_k[a][b]                (= d log det S_k)
+ *     Pd^+_k     = (I - L_k H) Pd^-_k (I - L_k H)' + L_k diag(V_dot) L_k'
+ *     Pd^-_{k+1} = A_k Pd^+_k A_k' + diag(W_dot)
+ * A_k are exactly the open-loop blocks of qln_tracking_kalman at Zout's (x_k, u_k); guarded, those of
+ * qln_tracking_kalman_guarded at (Zout, model, event), with the touchdown knot's composite A*.  First order at a fixed touchdown
+ * knot, as every sweep here.  Nothing is divided or factored, and Sigma0_dot may be indefinite.
+ * TWO CAVEATS.  The call cannot check that Lgain is optimal for (Zout, H, V, Sigma0, W): with other gains it returns the
+ * recursion's values, which are then no derivative.  And I - H L_k loses |H P^- H'| / V digits (S^-1 = V^-1 (I - H L) with H L
+ * near I when the prior dominates the sensor), the loss qln_landing_filter's score has; it reaches Ld and logdet_dot, not Pd^+.
+ * Inputs: Zout [B] x z_stride; Lgain [B][N][15][ny]; H [ny][15] and Vdiag (a HOST array, ny entries, finite and > 0) as for the
+ *   design, eight rows always, the rows behind ny being zero rows with V = 1, V_dot = 0 and zero columns of L, so a call gives the
+ *   bits of the same call with those written out.  The direction, each optional (NULL: zero), at least one: Sigma0_dot
+ *   [sigma0_batch][120] packed (sigma0_batch 1 or B; not read when Sigma0_dot is NULL), Wdiag_dot (HOST, 15) and Vdiag_dot
+ *   (HOST, ny), finite, of either sign.
+ * Outputs (each optional, at least one non-NULL; overwritten; which are asked for changes no other output's bits; none may
+ * overlap an input or another output): Lgain_dot [B][N][15][ny]; Pest_dot [B][N][120] packed; logdet_dot [B][N].
+ * With Lgain = 0 and Vdiag_dot = NULL, Pest_dot is qln_tracking_covariance*'s Sigma (K = NULL) at Sigma0 = Sigma0_dot,
+ * W = Wdiag_dot, bit for bit.
+ * Refused with QLN_ERR_INVALID_ARGUMENT, the checks that need no handle before the null handle, in this order: ny outside
+ * 1..QLN_TRACK_NY_MAX, no output, a NULL event in the guarded form, a NULL H or Vdiag, a V entry not finite or not > 0, all three
+ * tangents NULL, a non-finite entry of Wdiag_dot or Vdiag_dot, a NULL Lgain, sigma0_batch < 1 with Sigma0_dot; behind the handle
+ * sigma0_batch not 1 or B with Sigma0_dot, a NULL Zout, and an output that overlaps an input or another output.  The device
+ * forms do not validate device data; the host forms also refuse a non-finite H and validate model and event as
+ * qln_tracking_kalman_guarded_host does.  A guarded batch without a touchdown and with model == NULL gives
+ * qln_kalman_design_jvp's bits for a handle with k_trans = N + 1.  Device pointers, stream-ordered; needs no cost table. */
+int qln_kalman_design_jvp(qln_handle* h, const double* Zout, const double* Lgain, const double* H, int32_t ny,
+                          const double* Vdiag /* host, ny entries, finite and > 0 */, const double* Sigma0_dot /* or NULL */,
+                          int32_t sigma0_batch, const double* Wdiag_dot /* host, or NULL */,
+                          const double* Vdiag_dot /* host, or NULL */, double* Lgain_dot, double* Pest_dot, double* logdet_dot);
+int qln_kalman_design_jvp_host(qln_handle* h, const double* Zout, const double* Lgain, const double* H, int32_t ny,
+                               const double* Vdiag, const double* Sigma0_dot, int32_t sigma0_batch, const double* Wdiag_dot,
+                               const double* Vdiag_dot, double* Lgain_dot, double* Pest_dot, double* logdet_dot);
+int qln_kalman_design_guarded_jvp(qln_handle* h, const double* Zout, const double* model /* or NULL */,
+                                  const double* event /* required */, const double* Lgain, const double* H, int32_t ny,
+                                  const double* Vdiag, const double* Sigma0_dot, int32_t sigma0_batch, const double* Wdiag_dot,
+                                  const double* Vdiag_dot, double* Lgain_dot, double* Pest_dot, double* logdet_dot);
+int qln_kalman_design_guarded_jvp_host(qln_handle* h, const double* Zout, const double* model, const double* event,
+                                       const double* Lgain, const double* H, int32_t ny, const double* Vdiag,
+                                       const double* Sigma0_dot, int32_t sigma0_batch, const double* Wdiag_dot,
+                                       const double* Vdiag_dot, double* Lgain_dot, double* Pest_dot, double* logdet_dot);
 /* The FILTER on recorded data, and the score of that data under it: the estimator of qln_tracking_rollout_estimated* as a call
  * of its own, for a landing that was flown elsewhere -- sensor readings and the forces that were applied -- where that call
  * produces Xhat and innov only together with a plant it integrates itself.  Its outputs feed qln_landing_smoother*, and loglik
@@ -1255,7 +1306,8 @@ int qln_landing_filter_guarded_model_host(qln_handle* h, const double* Zref, con
  * FIXED GAINS.  log det S_k depends on Lgain alone, and its derivative is not offered: nis_dot or loglik_dot together with
  * Lgain_dot is refused, and loglik_dot is the EXACT derivative of loglik AT FIXED GAINS (the prediction-error gradient).  The
  * gains of qln_tracking_kalman* themselves depend on the model: a caller to whom the total derivative matters redesigns them
- * between outer iterations.
+ * between outer iterations.  For the total derivative along (Sigma0_dot, W_dot, V_dot), qln_kalman_design_jvp gives the
+ * Lgain_dot to pass here (without a score term) and the derivative of log det S_k.
  * Reverse sweep, the exact transpose.  Cotangents, each optional (NULL: zero), at least one: Xhat_bar [B][N][15]; innov_bar
  * [B][N][ny]; nis_bar [B][N]; loglik_bar [B].  With nb_k = nis_bar_k - loglik_bar / 2 and lamm, the cotangent of dxm_{k+1}, zero
  * behind the last knot, for k = N-1 .. 0:

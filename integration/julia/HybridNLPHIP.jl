@@ -396,6 +396,51 @@ function tracking_kalman_guarded(prob::HybridNLPHIP, Zout::Vector{Float64}, even
                     marg === nothing ? C_NULL : marg, event_var === nothing ? C_NULL : event_var))
     return L, Pest, Sigma, marg, event_var
 end
+# The forward sweep through the design of the filter (include/qln_evaluator.h, DESIGN.md 4.28): how L_k, P^+_k and log det S_k of
+# tracking_kalman move along a direction of the noise (Sigma0_dot a 15 x 15 symmetric matrix of either sign, W_dot 15 values,
+# V_dot ny values; nothing for zero, at least one), at the gains L (ny, 15, N) that call returned for the same (Zout, H, V) --
+# which the sweep cannot check.  Returns (L_dot (ny, 15, N), Pest_dot (120, N) packed, logdet_dot (N)).
+# tracking_kalman_guarded_jvp is the same through the guard-triggered touchdown at (Zout, events, model).
+function tracking_kalman_jvp(prob::HybridNLPHIP, Zout::Vector{Float64}, L::Array{Float64,3}, H::Matrix{Float64},
+                             V::Vector{Float64}; Sigma0_dot=nothing, W_dot=nothing, V_dot=nothing)
+    N = prob.N
+    ny = size(H, 1)
+    (1 <= ny <= 8 && size(H, 2) == 15 && length(V) == ny && size(L) == (ny, 15, N)) ||
+        error("H: (ny, 15) with 1 <= ny <= 8, V: ny variances, L: (ny, 15, N)")
+    (V_dot === nothing || length(V_dot) == ny) || error("V_dot: ny values")
+    Hrow = Matrix{Float64}(transpose(H))  # row-major [ny][15]
+    packed = Sigma0_dot === nothing ? nothing : Float64[Sigma0_dot[i, j] for i in 1:15 for j in 1:i]
+    L_dot = zeros(ny, 15, N)
+    Pest_dot = zeros(120, N)
+    logdet_dot = zeros(N)
+    qln_check(ccall((:qln_kalman_design_jvp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zout, L, Hrow, Int32(ny), V, packed === nothing ? C_NULL : packed, Int32(1),
+                    W_dot === nothing ? C_NULL : W_dot, V_dot === nothing ? C_NULL : V_dot, L_dot, Pest_dot, logdet_dot))
+    return L_dot, Pest_dot, logdet_dot
+end
+function tracking_kalman_guarded_jvp(prob::HybridNLPHIP, Zout::Vector{Float64}, events::Vector{Float64}, L::Array{Float64,3},
+                                     H::Matrix{Float64}, V::Vector{Float64}; Sigma0_dot=nothing, W_dot=nothing, V_dot=nothing,
+                                     model=nothing)
+    N = prob.N
+    ny = size(H, 1)
+    (1 <= ny <= 8 && size(H, 2) == 15 && length(V) == ny && size(L) == (ny, 15, N)) ||
+        error("H: (ny, 15) with 1 <= ny <= 8, V: ny variances, L: (ny, 15, N)")
+    (V_dot === nothing || length(V_dot) == ny) || error("V_dot: ny values")
+    Hrow = Matrix{Float64}(transpose(H))
+    packed = Sigma0_dot === nothing ? nothing : Float64[Sigma0_dot[i, j] for i in 1:15 for j in 1:i]
+    L_dot = zeros(ny, 15, N)
+    Pest_dot = zeros(120, N)
+    logdet_dot = zeros(N)
+    qln_check(ccall((:qln_kalman_design_guarded_jvp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble},
+                     Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zout, model === nothing ? C_NULL : model, events, L, Hrow, Int32(ny), V,
+                    packed === nothing ? C_NULL : packed, Int32(1), W_dot === nothing ? C_NULL : W_dot,
+                    V_dot === nothing ? C_NULL : V_dot, L_dot, Pest_dot, logdet_dot))
+    return L_dot, Pest_dot, logdet_dot
+end
 # Fixed-interval smoothing of a flown landing (include/qln_evaluator.h, DESIGN.md 4.25): the state at every knot given all N
 # measurements, by the modified Bryson-Frazier sweep, which inverts nothing.  Ztraj: the trajectory the filter was designed
 # along; L (ny, 15, N) and Pest (120, N) as tracking_kalman returns them for the same (Ztraj, H, V); Xhat (15, N) and innov

@@ -1797,6 +1797,117 @@ int qln_tracking_kalman_guarded_host(qln_handle* h, const double* Zout, const do
     return tracking_kalman(h, kHostMem, a, "qln_tracking_kalman_guarded_host");
 }
 
+// The forward sweep through the Kalman design (k_tracking_kalman_jvp).  The checks that need no handle come first.
+// guarded: through the guard-triggered touchdown, which needs the roll-out's event records
+struct KalmanJvpCall {
+    const double *Zout, *model, *event, *Lgain, *H;
+    int32_t ny;
+    const double *Vdiag, *Sigma0_dot;
+    int32_t sigma0_batch;
+    const double *Wdiag_dot, *Vdiag_dot;
+    double *Lgain_dot, *Pest_dot, *logdet_dot;
+    bool guarded;
+};
+
+static int check_kalman_design_jvp_args(const qln_handle* h, const KalmanJvpCall& a, const char* who) {
+    const std::string w(who);
+    if (a.ny < 1 || a.ny > QLN_TRACK_NY_MAX)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
+    if (!a.Lgain_dot && !a.Pest_dot && !a.logdet_dot)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every output is NULL (nothing to compute)");
+    if (a.guarded && !a.event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
+    if (!a.H || !a.Vdiag) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null H or Vdiag");
+    for (int i = 0; i < a.ny; ++i)
+        if (!(std::isfinite(a.Vdiag[i]) && a.Vdiag[i] > 0.0))
+            return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Vdiag must be finite and > 0 (entry " + std::to_string(i) + ")");
+    if (!a.Sigma0_dot && !a.Wdiag_dot && !a.Vdiag_dot)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Sigma0_dot, Wdiag_dot and Vdiag_dot are all NULL (no direction)");
+    if (a.Wdiag_dot)
+        for (int i = 0; i < QLN_NX; ++i)
+            if (!std::isfinite(a.Wdiag_dot[i]))
+                return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Wdiag_dot must be finite (entry " + std::to_string(i) + ")");
+    if (a.Vdiag_dot)
+        for (int i = 0; i < a.ny; ++i)
+            if (!std::isfinite(a.Vdiag_dot[i]))
+                return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Vdiag_dot must be finite (entry " + std::to_string(i) + ")");
+    if (!a.Lgain) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Lgain");
+    if (a.Sigma0_dot && a.sigma0_batch < 1) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
+    if (int rc = check_handle(h)) return rc;
+    if (a.Sigma0_dot && a.sigma0_batch != 1 && a.sigma0_batch != h->dims.B)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
+    if (!a.Zout) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zout");
+    return QLN_OK;
+}
+
+static int kalman_design_jvp(qln_handle* h, MemForm mem, const KalmanJvpCall& a, const char* who) {
+    if (int rc = check_kalman_design_jvp_args(h, a, who)) return rc;
+    // the rows and gains of the call's ny, of the roles' eight; the tiles it reads, of the role's B
+    const int64_t ng = tracking_gain_total(h->dims, a.ny);
+    const int32_t nb = a.Sigma0_dot ? a.sigma0_batch : 1;
+    const HostArgs args = {copy_in(kV, a.Zout), copy_in(kModel, a.model), copy_in(kEvent, a.event),
+                           copy_in(kLgain, a.Lgain).sized(ng), copy_in(kH, a.H).sized((int64_t)a.ny * QLN_NX),
+                           copy_in(kCov0, a.Sigma0_dot).sized((int64_t)nb * QLN_TRACK_P_NNZ),
+                           copy_out(kLgainD, a.Lgain_dot).sized(ng), copy_out(kPest, a.Pest_dot), copy_out(kNisD, a.logdet_dot)};
+    if (int rc = check_no_overlap(h, args, who)) return rc;
+    if (mem == kHostMem) {
+        if (int rc = check_host_meas(a.H, a.ny, who)) return rc;
+        if (int rc = check_host_models(h, a.model, who)) return rc;
+        if (int rc = check_host_events(h, a.event, who)) return rc;
+    }
+    return run_call(h, mem, args, [&](double* const* d, bool) {
+        return qln::launch_tracking_kalman_jvp(h->p, d[kV], d[kModel], d[kEvent], d[kLgain], d[kH], a.ny, a.Vdiag, d[kCov0], nb,
+                                               a.Wdiag_dot, a.Vdiag_dot, d[kLgainD], d[kPest], d[kNisD], h->stream);
+    });
+}
+
+static KalmanJvpCall kalman_jvp_call(const double* Zout, const double* Lgain, const double* H, int32_t ny, const double* Vdiag,
+                                     const double* Sigma0_dot, int32_t sigma0_batch, const double* Wdiag_dot,
+                                     const double* Vdiag_dot, double* Lgain_dot, double* Pest_dot, double* logdet_dot) {
+    KalmanJvpCall a{};
+    a.Zout = Zout; a.Lgain = Lgain; a.H = H; a.ny = ny; a.Vdiag = Vdiag; a.Sigma0_dot = Sigma0_dot; a.sigma0_batch = sigma0_batch;
+    a.Wdiag_dot = Wdiag_dot; a.Vdiag_dot = Vdiag_dot; a.Lgain_dot = Lgain_dot; a.Pest_dot = Pest_dot; a.logdet_dot = logdet_dot;
+    return a;
+}
+static KalmanJvpCall at_events(KalmanJvpCall a, const double* model, const double* event) {
+    a.guarded = true; a.model = model; a.event = event;
+    return a;
+}
+
+int qln_kalman_design_jvp(qln_handle* h, const double* Zout, const double* Lgain, const double* H, int32_t ny, const double* Vdiag,
+                          const double* Sigma0_dot, int32_t sigma0_batch, const double* Wdiag_dot, const double* Vdiag_dot,
+                          double* Lgain_dot, double* Pest_dot, double* logdet_dot) {
+    return kalman_design_jvp(h, kDeviceMem,
+                             kalman_jvp_call(Zout, Lgain, H, ny, Vdiag, Sigma0_dot, sigma0_batch, Wdiag_dot, Vdiag_dot, Lgain_dot,
+                                             Pest_dot, logdet_dot),
+                             "qln_kalman_design_jvp");
+}
+int qln_kalman_design_jvp_host(qln_handle* h, const double* Zout, const double* Lgain, const double* H, int32_t ny,
+                               const double* Vdiag, const double* Sigma0_dot, int32_t sigma0_batch, const double* Wdiag_dot,
+                               const double* Vdiag_dot, double* Lgain_dot, double* Pest_dot, double* logdet_dot) {
+    return kalman_design_jvp(h, kHostMem,
+                             kalman_jvp_call(Zout, Lgain, H, ny, Vdiag, Sigma0_dot, sigma0_batch, Wdiag_dot, Vdiag_dot, Lgain_dot,
+                                             Pest_dot, logdet_dot),
+                             "qln_kalman_design_jvp_host");
+}
+int qln_kalman_design_guarded_jvp(qln_handle* h, const double* Zout, const double* model, const double* event, const double* Lgain,
+                                  const double* H, int32_t ny, const double* Vdiag, const double* Sigma0_dot, int32_t sigma0_batch,
+                                  const double* Wdiag_dot, const double* Vdiag_dot, double* Lgain_dot, double* Pest_dot,
+                                  double* logdet_dot) {
+    return kalman_design_jvp(h, kDeviceMem,
+                             at_events(kalman_jvp_call(Zout, Lgain, H, ny, Vdiag, Sigma0_dot, sigma0_batch, Wdiag_dot, Vdiag_dot,
+                                                     Lgain_dot, Pest_dot, logdet_dot), model, event),
+                             "qln_kalman_design_guarded_jvp");
+}
+int qln_kalman_design_guarded_jvp_host(qln_handle* h, const double* Zout, const double* model, const double* event,
+                                       const double* Lgain, const double* H, int32_t ny, const double* Vdiag,
+                                       const double* Sigma0_dot, int32_t sigma0_batch, const double* Wdiag_dot,
+                                       const double* Vdiag_dot, double* Lgain_dot, double* Pest_dot, double* logdet_dot) {
+    return kalman_design_jvp(h, kHostMem,
+                             at_events(kalman_jvp_call(Zout, Lgain, H, ny, Vdiag, Sigma0_dot, sigma0_batch, Wdiag_dot, Vdiag_dot,
+                                                     Lgain_dot, Pest_dot, logdet_dot), model, event),
+                             "qln_kalman_design_guarded_jvp_host");
+}
+
 // The fixed-interval smoother (k_landing_smoother).  The checks that need no handle come first.
 // guarded: through the guard-triggered touchdown, which needs the roll-out's event records
 struct SmootherCall {

@@ -333,6 +333,14 @@ hipError_t launch_tracking_kalman(const BatchParams& p, const double* Zout, cons
                                   const double* event, const double* H, int ny, const double* Vd, const double* Sigma0,
                                   int sigma0_batch, const double* Wd, double* Lgain, double* Pest, double* Sigma, double* marg,
                                   double* event_var, hipStream_t stream);
+// The forward sweep through the Kalman design (qln_kalman_design_jvp / _guarded) at the gains it returned: Lgain
+// [B][N][15][ny] and H [ny][15] on the device, Vd (ny) a host array; the direction: Sigma0_dot [sigma0_batch][120] on the device or
+// null, Wd_dot (15) and Vd_dot (ny) host arrays or null (zeros); Lgain_dot [B][N][15][ny], Pest_dot [B][N][120] and logdet_dot
+// [B][N], each may be null, not all.  event selects the guarded blocks, and model is read with it only.
+hipError_t launch_tracking_kalman_jvp(const BatchParams& p, const double* Zout, const double* model, const double* event,
+                                      const double* Lgain, const double* H, int ny, const double* Vd, const double* Sigma0_dot,
+                                      int sigma0_batch, const double* Wd_dot, const double* Vd_dot, double* Lgain_dot,
+                                      double* Pest_dot, double* logdet_dot, hipStream_t stream);
 // The fixed-interval smoother of a flown landing (qln_landing_smoother / _guarded): Lgain [B][N][15][ny], Pest [B][N][120],
 // H [ny][15], Xhat [B][N][15] and innov [B][N][ny] on the device, Vd (ny) a host array; Xs [B][N][15] and Ps [B][N][120], either
 // may be null.  event selects the guarded blocks, and model is read with it only.

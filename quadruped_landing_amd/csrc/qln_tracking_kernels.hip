@@ -102,6 +102,10 @@
 // estimator's backward pass: the modified Bryson-Frazier sweep on the filter's gains and covariances, in k_tracking_kalman's
 // mapping and tiles, with the blocks and the touchdown operator applied transposed as the Riccati sweep applies them.
 //
+// k_tracking_kalman_jvp: the forward sweep through k_tracking_kalman's design (qln_kalman_design_jvp / _guarded_jvp, DESIGN.md
+// 4.28): the tangents of the gains, of P^+ and of log det S_k along (Sigma0_dot, W_dot, V_dot), at the gains alone, in that
+// kernel's mapping, on its blocks and on k_tracking_covariance's open-loop knot.
+//
 // k_landing_filter: the estimator on recorded data (qln_landing_filter / _guarded): the estimator's half of
 // k_tracking_rollout_estimated, measurements and applied forces read where that kernel forms them, and with kScore the
 // normalised innovation squared, log det S_k and the log-likelihood from the gains alone.  kModel: at a model of each record's own.
@@ -1673,6 +1677,220 @@ __global__ __launch_bounds__(kWave) void k_tracking_kalman(BatchParams P, Kalman
     if constexpr (kGuard) {
         if (kHasK && ev_var && valid && ln < 2) ev_var[(int64_t)2 * bc + ln] = (ln == 0) ? var_tau : var_clock;
     }
+}
+
+
+// ---- k_tracking_kalman_jvp ----
+// per-row LDS image (doubles): the Pd image [15][17] | the knot's 20 entries of Zout | the H tile [8][16], 1/V in its column 15 |
+// two L tiles [15][8] (the knot's, and the next knot's while it is staged) | the Ld tile [15][8]
+constexpr int kJTile = 15 * QLN_TRACK_NY_MAX;
+constexpr int kJP = 0, kJZ = 256, kJH = kJZ + 20, kJL = kJH + QLN_TRACK_NY_MAX * 16, kJLd = kJL + 2 * kJTile, kJRow = kJLd + kJTile;
+static_assert(kImgSize <= kJZ - kJP && kJZ % 2 == 0 && kJH % 2 == 0 && kJL % 2 == 0 && kJLd % 2 == 0 && kJRow % 2 == 0,
+              "the image fits; 16-byte aligned sections");
+
+// the tangents of the process and the measurement variances, and 1 / V; the rows behind ny carry 1 / V = 1 and V_dot = 0
+struct KalmanNoiseDot {
+    double wd[15], iv[QLN_TRACK_NY_MAX], vd[QLN_TRACK_NY_MAX];
+};
+
+// The forward sweep through k_tracking_kalman's design (include/qln_evaluator.h): how the gains L_k, the error
+// covariances P^+_k and log det S_k move along (Sigma0_dot, W_dot, V_dot), at the gains the design returned and nothing else of
+// it -- at the optimal gain the Joseph form is stationary in L, so P^+'s tangent carries no L_dot term.  In k_tracking_kalman's
+// mapping, one problem per row of sixteen lanes, lane j owns column j, and one padded image holds Pd.  Per knot:
+//   1. lane j forms Gd[:, j] = H Pd^-[:, j] and at once the first pass of the Joseph form, column j of (I - L H) Pd^-, so that
+//      its column of Pd^- is dead before the rest;
+//   2. Sd = Gd H' + diag(V_dot): 36 row sums, the same bits in every lane, each consumed where it is formed -- its share of
+//      tr(V^-1 Sd) and of row j of L Sd -- so that Sd is never held;
+//   3. d log det S = tr(Sinv Sd) = tr(V^-1 Sd) - tr(V^-1 H L Sd) with Sinv = diag(1/V) (I - H L): lane j's share of the second
+//      trace is sum_a H(a, j) / V_a (L Sd)(j, a), one more row sum.  Row j of Ld = T Sinv, T = Pd^- H' - L Sd: with
+//      tv = T(j, :) ./ V it is tv - (tv H) L, two dense chains on broadcast reads of the two tiles, and leaves through the Ld
+//      tile.  No entry of H L is formed;
+//   4. Pd^+ = (I - L H) [.]' + L diag(V_dot) L': k_tracking_kalman's second pass with V_dot where V stands;
+//   5. Pd^-_{k+1} = A Pd^+ A' + diag(W_dot): k_tracking_covariance's open-loop knot (the touchdown knot: the composite operator).
+// L_{k+1} is requested at the top of knot k and staged into the other L tile behind the update, so that its eight entries per lane
+// are not held across the prediction, where the step block peaks.  Compiled for eight measurement rows as k_tracking_kalman: zero
+// rows of H and zero columns of L behind ny change no value.  Nothing here divides or factors, and Pd may be indefinite.
+template <bool kModel, bool kGuard>
+__device__ __forceinline__ void kalman_jvp_sweep(const BatchParams& P, const KalmanNoiseDot& Nz, const double* __restrict__ Zout,
+                                                 const double* __restrict__ Lg, const double* __restrict__ Hg, int ny,
+                                                 const double* __restrict__ Sigma0d, int sigma0_batch, double* __restrict__ Ldg,
+                                                 double* __restrict__ Pdg, double* __restrict__ ldg,
+                                                 const double* __restrict__ model, const double* __restrict__ event) {
+    static_assert(kModel || !kGuard, "the guarded sweep runs on the kModel path");
+    constexpr int NY = QLN_TRACK_NY_MAX;
+    __shared__ double lds[kRows * kJRow];
+    const Row16 r16 = row16_of(P);  // lane 15 shadows column 14 and writes nothing to the image
+    const int ln = r16.ln, j = r16.j, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
+    const bool own = r16.own, valid = r16.valid;
+    const Model Mp = plant_model<kModel>(P, model, bc);
+    const Model& M = kGuard ? Mp : r16.M;
+    const GuardEvent ev = guard_event<kGuard>(event, bc, N);
+    double* L = lds + r16.row * kJRow;
+    const Image15 Pm{L + kJP, j, own};
+    const int gn = QLN_NX * ny;  // a knot's gain entries
+    const double* __restrict__ Zb = Zout + (int64_t)bc * P.z_stride;
+    const double* __restrict__ Lb = Lg + (int64_t)bc * N * gn;
+    double* __restrict__ Ldb = Ldg ? Ldg + (int64_t)bc * N * gn : nullptr;
+    double* __restrict__ Pdb = Pdg ? Pdg + (int64_t)bc * N * QLN_TRACK_P_NNZ : nullptr;
+    double* __restrict__ ldb = ldg ? ldg + (int64_t)bc * N : nullptr;
+
+    int po[8], lo[8];
+    packed_offsets(ln, po);
+    gain_offsets(ln, ny, kJL, lo);
+    double wj = 0.0;
+#pragma unroll
+    for (int i = 0; i < 15; ++i) wj = (i == j) ? Nz.wd[i] : wj;
+    const auto Hrow = [&](int r, int c) { return L[kJH + 16 * r + c]; };  // H(r, c); 1 / V_r in column 15
+
+    // Pd^-_0 = Sigma0_dot (null: zero); the three gain tiles zero, so the columns behind ny stay zero; the H tile, zero rows behind ny
+    {
+        if (Sigma0d) {
+            const double* __restrict__ S0 = Sigma0d + (int64_t)(sigma0_batch == 1 ? 0 : bc) * QLN_TRACK_P_NNZ;
+            tile_fill(Pm.a, po, QLN_TRACK_P_NNZ, tile_lane(ln), [&](int t) { return S0[ln + 16 * t]; });
+        } else {
+#pragma unroll
+            for (int t = 0; t < 16; ++t) L[kJP + ln + 16 * t] = 0.0;
+        }
+#pragma unroll
+        for (int t = 0; t < (3 * kJTile + 15) / 16; ++t)
+            if (ln + 16 * t < 3 * kJTile) L[kJL + ln + 16 * t] = 0.0;
+#pragma unroll
+        for (int r = 0; r < NY; ++r) L[kJH + 16 * r + ln] = own ? ((r < ny) ? Hg[15 * r + ln] : 0.0) : Nz.iv[r];
+    }
+    wave_lds_sync();
+
+    // a knot's gain entries ln + 16 t, requested one knot ahead like the knot itself, and staged into tile k & 1
+    auto gain_request = [&](int k, double (&lq)[8]) {
+        const double* __restrict__ Lk = Lb + (int64_t)k * gn;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) lq[t] = Lk[min(ln + 16 * t, gn - 1)];
+    };
+    double zn[2] = {0.0, 0.0}, lq[8];
+    if (N > 1) knot_load(Zb, ln, zn[0], zn[1]);
+    gain_request(0, lq);
+    tile_fill(L, lo, gn, tile_lane(ln), [&](int t) { return lq[t]; });
+
+    for (int k = 0; k < N; ++k) {
+        const double* Lt = L + kJL + kJTile * (k & 1);
+        const auto Lrow = [&](int i, int r) { return Lt[NY * i + r]; };  // the gain's L(i, r)
+        const bool last = k == N - 1;  // the last knot has an update and no step
+        if (!last) {
+            L[kJZ + ln] = zn[0];
+            if (ln < 4) L[kJZ + 16 + ln] = zn[1];
+            if (k + 1 < N - 1) knot_load(Zb + 20 * (k + 1), ln, zn[0], zn[1]);
+        }
+        if (!last) gain_request(k + 1, lq);
+        wave_lds_sync();  // the knot and the L tile are in place
+
+        // ---- the update's tangent: Ld_k, d log det S_k and Pd^+_k ----
+        double Gd[NY], ldot;
+        {
+            double p[15], u[15];
+            Pm.column(p);
+            chain_rows(Hrow, p, Gd);
+            chain_rows_sub(Lrow, Gd, p, u);  // column j of (I - L H) Pd^- -> row j of the image
+            wave_lds_sync();                 // every lane holds its column of Pd^-
+            Pm.store_row(u);
+        }
+        {
+            double hj[NY], lj[NY], LS[NY], tv[NY], ld[NY];
+#pragma unroll
+            for (int r = 0; r < NY; ++r) {
+                hj[r] = Hrow(r, j);
+                lj[r] = Lrow(j, r);  // row j of L
+            }
+            double tr = 0.0;
+#pragma unroll
+            for (int r = 0; r < NY; ++r) LS[r] = 0.0;
+            // Sd's lower triangle, entry by entry: what it adds to tr(V^-1 Sd) and to row j of L Sd (Sd is symmetric)
+#pragma unroll
+            for (int a = 0; a < NY; ++a) {
+#pragma unroll
+                for (int b = 0; b < a; ++b) {
+                    const double sd = row_sum16(own ? Gd[a] * hj[b] : 0.0);
+                    LS[b] = fma(lj[a], sd, LS[b]);
+                    LS[a] = fma(lj[b], sd, LS[a]);
+                }
+                const double sd = row_sum16(own ? Gd[a] * hj[a] : 0.0) + Nz.vd[a];
+                tr = fma(Hrow(a, 15), sd, tr);
+                LS[a] = fma(lj[a], sd, LS[a]);
+            }
+            // the second trace's share of lane j, and tv = T(j, :) ./ V
+            double c = 0.0;
+#pragma unroll
+            for (int a = 0; a < NY; ++a) {
+                const double iva = Hrow(a, 15);
+                c = fma(hj[a] * iva, LS[a], c);
+                tv[a] = (Gd[a] - LS[a]) * iva;
+            }
+            ldot = tr - row_sum16(own ? c : 0.0);
+            double w[15];
+            chain_rows([&](int i, int a) { return Hrow(a, i); }, tv, w);          // tv H
+            chain_rows_sub([&](int b, int i) { return Lrow(i, b); }, w, tv, ld);  // tv - (tv H) L
+            if (own) {
+#pragma unroll
+                for (int r = 0; r < NY; ++r) L[kJLd + NY * j + r] = ld[r];
+            }
+        }
+        wave_lds_sync();
+        {
+            double vt[15], t[NY], out[15];
+            Pm.transposed(vt);
+            chain_rows(Hrow, vt, t);
+#pragma unroll
+            for (int r = 0; r < NY; ++r) t[r] = fma(-Nz.vd[r], Lrow(j, r), t[r]);  // H v - V_dot .* (row j of L)
+            chain_rows_sub(Lrow, t, vt, out);
+            wave_lds_sync();  // every lane holds its row: Pd^+ may overwrite the image
+            Pm.store_row(out);
+        }
+        // L_{k+1} has had the update to arrive: into the other tile, which knot k - 1 read last
+        if (!last) tile_fill(L + kJTile * ((k + 1) & 1), lo, gn, tile_lane(ln), [&](int t) { return lq[t]; });
+        wave_lds_sync();
+        // only the lower triangle of Pd^+_k is read from here on; the knot's outputs leave from it and from the Ld tile
+        {
+            const TileLane tl = tile_lane(ln);
+            if (Ldb && valid) tile_store(Ldb + (int64_t)k * gn, lo, gn, tl, [&](int o) { return L[o + (kJLd - kJL)]; });
+            if (Pdb && valid) tile_store(Pdb + (int64_t)k * QLN_TRACK_P_NNZ, po, QLN_TRACK_P_NNZ, tl, [&](int o) { return Pm.a[o]; });
+            if (ldb && valid && ln == 0) ldb[k] = ldot;
+        }
+        if (last) break;
+
+        // Pd^-_{k+1} = A Pd^+_k A' + diag(W_dot): k_tracking_covariance's open-loop knot on this image
+        KnotMode md;
+        if constexpr (kGuard) md = guard_mode(k, ev.ks, im);
+        else md = knot_mode(k + 1, kt - 1, im);
+        double g[4];
+        if (kGuard && k == ev.ks) {  // the touchdown knot: the composite operator in the block's place
+            const TouchdownBlock tb = touchdown_block_at(L + kJZ, M, md, ev.tau);
+            congruence(
+                Pm, [&](const double (&v)[15], double (&out)[15]) { cov_apply_touchdown<false>(tb, M, nullptr, v, out, g); }, [] {},
+                wj);
+        } else {
+            const StepBlock blk = step_block(L + kJZ, md, M);
+            congruence(
+                Pm, [&](const double (&v)[15], double (&out)[15]) { cov_apply<false>(blk, nullptr, v, out, g); }, [] {}, wj);
+        }
+        wave_lds_sync();  // the image holds the prior's tangent of knot k + 1; the L tile and the knot may be rewritten
+    }
+}
+
+// The knot-scheduled form is asked for two waves per SIMD, which it fits without spills (its step block is the light one); the
+// guarded form stays at one, as k_tracking_kalman's: profiles/tracking_kalman_jvp_resource_usage.txt.
+template <bool kModel, bool kGuard>
+__global__ __launch_bounds__(kWave) void k_tracking_kalman_jvp(BatchParams P, KalmanNoiseDot Nz, const double* __restrict__ Zout,
+                                                               const double* __restrict__ Lg, const double* __restrict__ Hg, int ny,
+                                                               const double* __restrict__ Sigma0d, int sigma0_batch,
+                                                               double* __restrict__ Ldg, double* __restrict__ Pdg,
+                                                               double* __restrict__ ldg, const double* __restrict__ model,
+                                                               const double* __restrict__ event) {
+    kalman_jvp_sweep<kModel, kGuard>(P, Nz, Zout, Lg, Hg, ny, Sigma0d, sigma0_batch, Ldg, Pdg, ldg, model, event);
+}
+template <>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_tracking_kalman_jvp<false, false>(
+    BatchParams P, KalmanNoiseDot Nz, const double* __restrict__ Zout, const double* __restrict__ Lg, const double* __restrict__ Hg,
+    int ny, const double* __restrict__ Sigma0d, int sigma0_batch, double* __restrict__ Ldg, double* __restrict__ Pdg,
+    double* __restrict__ ldg, const double* __restrict__ model, const double* __restrict__ event) {
+    kalman_jvp_sweep<false, false>(P, Nz, Zout, Lg, Hg, ny, Sigma0d, sigma0_batch, Ldg, Pdg, ldg, model, event);
 }
 
 
@@ -3452,6 +3670,28 @@ hipError_t launch_tracking_kalman(const BatchParams& p, const double* Zout, cons
         K ? go(k_tracking_kalman<true, true, true>) : go(k_tracking_kalman<false, true, true>);
     else
         K ? go(k_tracking_kalman<true, false, false>) : go(k_tracking_kalman<false, false, false>);
+    return hipGetLastError();
+}
+
+// The two instantiations of k_tracking_kalman_jvp: event or the knot schedule (model is read with event only, as above).
+hipError_t launch_tracking_kalman_jvp(const BatchParams& p, const double* Zout, const double* model, const double* event,
+                                      const double* Lgain, const double* H, int ny, const double* Vd, const double* Sigma0_dot,
+                                      int sigma0_batch, const double* Wd_dot, const double* Vd_dot, double* Lgain_dot,
+                                      double* Pest_dot, double* logdet_dot, hipStream_t stream) {
+    if (ny < 1 || ny > QLN_TRACK_NY_MAX || !Zout || !Lgain || !H || !Vd) return hipErrorInvalidValue;
+    if (!Lgain_dot && !Pest_dot && !logdet_dot) return hipErrorInvalidValue;
+    KalmanNoiseDot nz;
+    for (int i = 0; i < 15; ++i) nz.wd[i] = Wd_dot ? Wd_dot[i] : 0.0;
+    for (int r = 0; r < QLN_TRACK_NY_MAX; ++r) {
+        nz.iv[r] = r < ny ? 1.0 / Vd[r] : 1.0;
+        nz.vd[r] = (r < ny && Vd_dot) ? Vd_dot[r] : 0.0;
+    }
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, nz, Zout, Lgain, H, ny, Sigma0_dot, sigma0_batch,
+                           Lgain_dot, Pest_dot, logdet_dot, model, event);
+    };
+    if (event) go(k_tracking_kalman_jvp<true, true>);
+    else go(k_tracking_kalman_jvp<false, false>);
     return hipGetLastError();
 }
 

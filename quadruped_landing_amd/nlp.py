@@ -1194,6 +1194,91 @@ class HybridNLP:
         return self._op_kalman(_HostForm(self), True, Zout, events, K, H, V, Sigma0, W, model, with_gains, with_pest, with_sigma,
                                with_marginals, with_event_var)
 
+    # -- the forward sweep through the filter's design ---------------------------------------------------
+    KALMAN_JVP_OUT = ("Lgain", "Pest", "logdet")
+
+    def _op_kalman_jvp(self, f, guarded, Zout, events, Lgain, H, V, Sigma0_dot, W_dot, V_dot, model, want):
+        """One path for the four forms.  Returns a dict of the outputs asked for (want None: all three)."""
+        Hh, Vh = measurement_model(H, V)
+        ny = Hh.shape[0]
+        want = self.KALMAN_JVP_OUT if want is None else tuple(want)
+        bad = set(want) - set(self.KALMAN_JVP_OUT)
+        if bad:
+            raise ValueError(f"want: unknown outputs {sorted(bad)} ({', '.join(self.KALMAN_JVP_OUT)})")
+        if Lgain is None:
+            raise ValueError(f"Lgain is required: the gains tracking_kalman{f.suffix} returned for (Zout, H, V)")
+        if Sigma0_dot is None and W_dot is None and V_dot is None:
+            raise ValueError("a direction is required: at least one of Sigma0_dot, W_dot and V_dot")
+        Wd = tracking_noise(W_dot)
+        Vd = None
+        if V_dot is not None:
+            if np.ndim(V_dot) > 1 or (np.ndim(V_dot) == 1 and np.shape(V_dot)[0] != ny):
+                raise ValueError(f"V_dot of shape {np.shape(V_dot)}: expected a scalar or ({ny},)")
+            Vd = np.ascontiguousarray(np.broadcast_to(np.asarray(V_dot, dtype=np.float64), (ny,)))
+        for name, a in (("W_dot", Wd), ("V_dot", Vd)):
+            if a is not None and not np.isfinite(a).all():
+                raise ValueError(f"{name} is not finite")
+        Zout = f.Z(Zout, "Zout")
+        Lgain = f.arr(Lgain, self.B * self.N * n * ny, "Lgain")
+        s0, nb = (None, 1) if Sigma0_dot is None else f.sigma0(Sigma0_dot)
+        Hd = f.H(Hh)
+        B, N = self.B, self.N
+        shapes = dict(Lgain=tracking_l_shape(B, N, ny), Pest=tracking_p_shape(B, N), logdet=(B, N))
+        res = {k: f.empty(shapes[k]) for k in self.KALMAN_JVP_OUT if k in want}
+        extra = ()
+        if guarded:
+            events, model = f.events(events), f.model(model)
+            extra = (f.ptr(model), f.ptr(events))
+        _lib.check(f.fn("qln_kalman_design" + ("_guarded" if guarded else "") + "_jvp")(
+            self._h, f.ptr(Zout), *extra, f.ptr(Lgain), f.ptr(Hd), ny, Vh.ctypes.data, f.ptr(s0), nb, _host_ptr(Wd), _host_ptr(Vd),
+            *(f.ptr(res.get(k)) for k in self.KALMAN_JVP_OUT)))
+        return res
+
+    def tracking_kalman_jvp(self, Zout, Lgain, H, V, Sigma0_dot=None, W_dot=None, V_dot=None, events=None, model=None,
+                            guarded=False, want=None):
+        """Forward sweep through the design of tracking_kalman (guarded: of tracking_kalman_guarded, at events and model): how
+        the gains, the error covariances P^+_k and log det S_k move along a direction (Sigma0_dot in any form Sigma0 takes and of
+        either sign, W_dot a scalar or (15,), V_dot a scalar or (ny,); each optional, at least one), at the gains Lgain the design
+        returned for (Zout, H, V) -- which the call cannot check (qln_kalman_design_jvp).  want: the outputs by name, of Lgain
+        (B, N, 15, ny), Pest (B, N, 120) packed and logdet (B, N); default all.  Returns a dict of device tensors; which are asked
+        for changes no other's bits.  Stream-ordered."""
+        return self._op_kalman_jvp(_DeviceForm(self), guarded, Zout, events, Lgain, H, V, Sigma0_dot, W_dot, V_dot, model, want)
+
+    def tracking_kalman_jvp_host(self, Zout, Lgain, H, V, Sigma0_dot=None, W_dot=None, V_dot=None, events=None, model=None,
+                                 guarded=False, want=None):
+        """The same with host arrays (synchronous): a dict of numpy arrays."""
+        return self._op_kalman_jvp(_HostForm(self), guarded, Zout, events, Lgain, H, V, Sigma0_dot, W_dot, V_dot, model, want)
+
+    def landing_loglik_jvp(self, Zout, Zref, Zrec, Lgain, H, V, Xhat, innov, Sigma0_dot=None, W_dot=None, V_dot=None, events=None,
+                           model=None, guarded_design=False, events_hat=None, guarded=False, filter_model=None):
+        """The TOTAL derivative of landing_filter's log-likelihood along a direction (Sigma0_dot, W_dot, V_dot) of the design's
+        noise, through the gains' design: tracking_kalman_jvp along the design's trajectory Zout (guarded_design: with events and
+        model), landing_filter_jvp of the record (Zref, Zrec, Xhat, innov; guarded: with events_hat; filter_model: the records'
+        own models) with that Lgain_dot and no score term, and on the device
+            nis_dot_k  = innov' Sinv innov_dot + innov_dot' Sinv innov + innov' Sinv_dot innov,   Sinv = diag(1/V) (I - H L),
+            Sinv_dot   = -diag(V_dot / V^2) (I - H L) - diag(1/V) H Lgain_dot,
+            loglik_dot = -1/2 sum_k (nis_dot_k + logdet_dot_k).
+        Device tensors in; returns (loglik_dot (B,), nis_dot (B, N), logdet_dot (B, N))."""
+        T = _torch()
+        Hh, Vh = measurement_model(H, V)
+        ny = Hh.shape[0]
+        d = self.tracking_kalman_jvp(Zout, Lgain, H, V, Sigma0_dot, W_dot, V_dot, events, model, guarded_design,
+                                     want=("Lgain", "logdet"))
+        s = self.landing_filter_jvp(Zref, Zrec, Lgain, H, Xhat, innov=innov, model=filter_model, events_hat=events_hat,
+                                    guarded=guarded, Lgain_dot=d["Lgain"], want=("innov",))
+        dev = self._dev()
+        Ht, Vt = T.from_numpy(np.array(Hh)).to(dev), T.from_numpy(np.array(Vh)).to(dev)
+        Vd = T.zeros(ny, dtype=T.float64, device=dev) if V_dot is None else T.from_numpy(
+            np.array(np.broadcast_to(np.asarray(V_dot, dtype=np.float64), (ny,)))).to(dev)
+        L, Ld = Lgain.reshape(self.B, self.N, n, ny), d["Lgain"]
+        iv, ivd = innov.reshape(self.B, self.N, ny), s["innov"]
+        G = T.eye(ny, dtype=T.float64, device=dev) - T.einsum("ri,bkis->bkrs", Ht, L)  # I - H L
+        Sinv = G / Vt[:, None]
+        Sinv_dot = -(Vd / (Vt * Vt))[:, None] * G - T.einsum("ri,bkis->bkrs", Ht, Ld) / Vt[:, None]
+        nis_dot = (T.einsum("bkr,bkrs,bks->bk", iv, Sinv, ivd) + T.einsum("bkr,bkrs,bks->bk", ivd, Sinv, iv)
+                   + T.einsum("bkr,bkrs,bks->bk", iv, Sinv_dot, iv))
+        return -0.5 * (nis_dot + d["logdet"]).sum(dim=1), nis_dot, d["logdet"]
+
     # -- the fixed-interval smoother: the estimator's backward pass ------------------------------------
     def _op_smoother(self, f, guarded, Ztraj, events, Lgain, Pest, H, V, Xhat, innov, model, with_states, with_cov):
         Hh, Vh = measurement_model(H, V)
@@ -1374,8 +1459,8 @@ class HybridNLP:
         one): Y_dot (B, N, ny), Zrec_dot in the layout of Z (control slots read), Lgain_dot, xhat0_dot (B, 15), model_dot (B, 4).
         want: the outputs by name, of Xhat, innov, nis, loglik and (guarded) event_hat; default Xhat and innov, the score's
         two when V is given and Lgain_dot is not, and event_hat when guarded.  loglik's tangent is the exact derivative AT FIXED
-        GAINS, so a score term together with Lgain_dot is refused; innov is needed with Lgain_dot or a score term.  Returns a
-        dict of device tensors.  Stream-ordered."""
+        GAINS, so a score term together with Lgain_dot is refused; innov is needed with Lgain_dot or a score term.  The total
+        derivative through the gains' design is landing_loglik_jvp.  Returns a dict of device tensors.  Stream-ordered."""
         given = dict(Y=Y_dot, Zrec=Zrec_dot, Lgain=Lgain_dot, xhat0=xhat0_dot, model=model_dot)
         return self._op_filter_sweep(_DeviceForm(self), True, guarded, Zref, Zrec, Lgain, H, Xhat, innov, V, model, events_hat,
                                      given, self._filter_jvp_want(want, V, Lgain_dot, guarded))
