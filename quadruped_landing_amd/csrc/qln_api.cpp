@@ -1244,12 +1244,90 @@ static int check_force_limits(const double* lim, const char* who) {
     return QLN_OK;
 }
 
-// Every operation below is one argument struct, one check and one body for both memory forms.  The struct has a named field
-// per argument and is value-initialised by the entry points, so an optional they leave out is null.  The check holds what
-// needs no device, in the order the refusals have always had.  The body declares the argument table once -- role, pointer,
-// direction, extent, whether the overlap rule looks at it, whether the host form stages it -- and the rule, the staging and
-// the launch all read that table (check_no_overlap, run_call).  The host form alone then looks at the values of a model, an
-// event record, a saturation record and H, after the shared check and before it binds the device.
+// host forms only: the values of every input that is a measurement matrix, a model, an event record or a saturation record,
+// in the order of the table -- so a table's order is the precedence between two bad values.  An output or an in-out of these
+// roles (the roll-outs' records) is no input; an input outside the overlap rule is still looked at.  H has ny rows: its
+// declared extent over QLN_NX.
+static int check_host_values(const qln_handle* h, HostArgs args, const char* who) {
+    for (const HostArg& a : args) {
+        if (!a.src || a.dst) continue;
+        int rc = QLN_OK;
+        if (a.role == kH) rc = check_host_meas(a.src, (int32_t)(host_arg_size(h, a) / QLN_NX), who);
+        else if (a.role == kModel) rc = check_host_models(h, a.src, who);
+        else if (a.role == kEvent || a.role == kEventHat) rc = check_host_events(h, a.src, who);
+        else if (a.role == kSat) rc = check_host_sat(h, a.src, who);
+        if (rc) return rc;
+    }
+    return QLN_OK;
+}
+
+// What every operation does after its own check: the overlap rule, in the host form the value checks, then the launch --
+// all three read the one argument table.
+extern "C++" {
+template <class Launch>
+static int run_tracking_call(qln_handle* h, MemForm mem, HostArgs args, const char* who, Launch&& launch) {
+    if (int rc = check_no_overlap(h, args, who)) return rc;
+    if (mem == kHostMem)
+        if (int rc = check_host_values(h, args, who)) return rc;
+    return run_call(h, mem, args, launch);
+}
+}
+
+// The refusals that several operations share, each stated once; an operation's check calls them in the order its refusals
+// have always had.
+static int check_tracking_wdiag(const double* Wdiag, const std::string& w) {
+    if (Wdiag)
+        for (int i = 0; i < QLN_NX; ++i)
+            if (!(std::isfinite(Wdiag[i]) && Wdiag[i] >= 0.0))
+                return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Wdiag must be finite and >= 0 (entry " + std::to_string(i) + ")");
+    return QLN_OK;
+}
+
+static int check_tracking_ny(int32_t ny, const std::string& w) {
+    if (ny < 1 || ny > QLN_TRACK_NY_MAX)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
+    return QLN_OK;
+}
+
+static int check_tracking_vdiag(const double* Vdiag, int32_t ny, const std::string& w) {
+    for (int i = 0; i < ny; ++i)
+        if (!(std::isfinite(Vdiag[i]) && Vdiag[i] > 0.0))
+            return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Vdiag must be finite and > 0 (entry " + std::to_string(i) + ")");
+    return QLN_OK;
+}
+
+// in two steps: at least 1 before the handle is looked at (h null), then 1 or the handle's B
+static int check_sigma0_batch(int32_t sigma0_batch, const qln_handle* h, const std::string& w) {
+    if (h ? sigma0_batch != 1 && sigma0_batch != h->dims.B : sigma0_batch < 1)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
+    return QLN_OK;
+}
+
+static int check_guard_event(bool guarded, const double* event, const std::string& w) {
+    if (guarded && !event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
+    return QLN_OK;
+}
+
+static int check_limited_sat(bool limited, const double* sat, const std::string& w) {
+    if (limited && !sat) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null sat (the limited roll-out's saturation record)");
+    return QLN_OK;
+}
+
+static int check_some_output(bool some, const std::string& w) {
+    if (!some) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every output is NULL (nothing to compute)");
+    return QLN_OK;
+}
+
+// Every operation below is one argument struct, its builders, one check and one body for both memory forms.  The struct has a
+// named field per argument.  A builder per prototype shape returns it value-initialised, so an optional the shape leaves out
+// is null, and a small modifier adds what a guarded, a limited or a model form adds, with the flags that follow from it; an
+// entry point is one call of the body on what they build, and the two memory forms of a pair differ in nothing but the form
+// and the name.  (The sweeps of the filter and of the estimate-feedback roll-out also take the launch's own argument struct,
+// qln::...JvpArgs / ...VjpArgs, which an entry point fills in the order of its prototype.)  The check holds what needs no
+// device, in the order the refusals have always had.  The body declares the argument table once -- role, pointer, direction,
+// extent, whether the overlap rule looks at it, whether the host form stages it -- and hands it to the runner: the rule, the
+// host form's look at the values of H, a model, an event record and a saturation record, the staging and the launch all read
+// that table (run_tracking_call).
 
 // The Riccati sweep (k_tracking_lqr).  The entry point on the handle's knot schedule passes no model and no event, and the
 // launch then takes the kernel without its kGuard flag.
@@ -1264,76 +1342,70 @@ struct LqrCall {
 
 static int check_tracking_lqr_args(const qln_handle* h, const LqrCall& a, const char* who) {
     // the limited form's checks need no handle and come first
-    if (a.limited && !a.sat)
-        return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null sat (the limited roll-out's saturation record)");
+    if (int rc = check_limited_sat(a.limited, a.sat, who)) return rc;
     if (a.limited && !a.event && a.model)
         return fail(QLN_ERR_INVALID_ARGUMENT,
                     std::string(who) + ": model without event (the knot-scheduled design has no plant model)");
     if (int rc = check_handle(h)) return rc;
     if (!a.Zref || !a.K) return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null Zref or K");
     if (int rc = check_tracking_weights(a.Q, a.R, a.Qf, who)) return rc;
-    if (!a.limited && a.guarded && !a.event)
-        return fail(QLN_ERR_INVALID_ARGUMENT, std::string(who) + ": null event (the guarded roll-out's records)");
-    return QLN_OK;
+    return check_guard_event(!a.limited && a.guarded, a.event, who);
 }
 
 static int tracking_lqr(qln_handle* h, MemForm mem, const LqrCall& a, const char* who) {
     if (int rc = check_tracking_lqr_args(h, a, who)) return rc;
-    const HostArgs args = {copy_in(kZ, a.Zref), copy_in(kModel, a.model), copy_in(kEvent, a.event), copy_in(kSat, a.sat),
-                           copy_out(kK, a.K), copy_out(kP, a.P)};
     // the sweep on the handle's knot schedule has never had an overlap rule
-    if (a.limited || a.guarded)
-        if (int rc = check_no_overlap(h, args, who)) return rc;
-    if (mem == kHostMem) {
-        if (int rc = check_host_models(h, a.model, who)) return rc;
-        if (int rc = check_host_events(h, a.event, who)) return rc;
-        if (int rc = check_host_sat(h, a.sat, who)) return rc;
-    }
-    return run_call(h, mem, args, [&](double* const* d, bool) {
+    const bool ruled = a.limited || a.guarded;
+    const HostArgs args = {copy_in(kZ, a.Zref).ruled_if(ruled), copy_in(kModel, a.model).ruled_if(ruled),
+                           copy_in(kEvent, a.event).ruled_if(ruled), copy_in(kSat, a.sat).ruled_if(ruled),
+                           copy_out(kK, a.K).ruled_if(ruled), copy_out(kP, a.P).ruled_if(ruled)};
+    return run_tracking_call(h, mem, args, who, [&](double* const* d, bool) {
         return qln::launch_tracking_lqr(h->p, a.Q, a.R, a.Qf, d[kZ], d[kModel], d[kEvent], d[kSat], d[kK], d[kP], h->stream);
     });
 }
 
+static LqrCall lqr_call(const double* Zref, const double* Q, const double* R, const double* Qf, double* K, double* P) {
+    LqrCall a{};
+    a.Zref = Zref; a.Q = Q; a.R = R; a.Qf = Qf; a.K = K; a.P = P;
+    return a;
+}
+static LqrCall at_events(LqrCall a, const double* model, const double* event) {
+    a.guarded = true; a.model = model; a.event = event;
+    return a;
+}
+static LqrCall at_active_set(LqrCall a, const double* sat) {
+    a.limited = true; a.sat = sat; a.guarded = a.event != nullptr;
+    return a;
+}
+
 int qln_tracking_lqr(qln_handle* h, const double* Zref, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
                      double* K, double* P) {
-    LqrCall a{};
-    a.Zref = Zref; a.Q = Qdiag; a.R = Rdiag; a.Qf = Qfdiag; a.K = K; a.P = P;
-    return tracking_lqr(h, kDeviceMem, a, "qln_tracking_lqr");
+    return tracking_lqr(h, kDeviceMem, lqr_call(Zref, Qdiag, Rdiag, Qfdiag, K, P), "qln_tracking_lqr");
 }
 int qln_tracking_lqr_host(qln_handle* h, const double* Zref, const double* Qdiag, const double* Rdiag, const double* Qfdiag,
                           double* K, double* P) {
-    LqrCall a{};
-    a.Zref = Zref; a.Q = Qdiag; a.R = Rdiag; a.Qf = Qfdiag; a.K = K; a.P = P;
-    return tracking_lqr(h, kHostMem, a, "qln_tracking_lqr_host");
+    return tracking_lqr(h, kHostMem, lqr_call(Zref, Qdiag, Rdiag, Qfdiag, K, P), "qln_tracking_lqr_host");
 }
 int qln_tracking_lqr_guarded(qln_handle* h, const double* Ztraj, const double* model, const double* event, const double* Qdiag,
                              const double* Rdiag, const double* Qfdiag, double* K, double* P) {
-    LqrCall a{};
-    a.Zref = Ztraj; a.model = model; a.event = event; a.guarded = true;
-    a.Q = Qdiag; a.R = Rdiag; a.Qf = Qfdiag; a.K = K; a.P = P;
-    return tracking_lqr(h, kDeviceMem, a, "qln_tracking_lqr_guarded");
+    return tracking_lqr(h, kDeviceMem, at_events(lqr_call(Ztraj, Qdiag, Rdiag, Qfdiag, K, P), model, event),
+                        "qln_tracking_lqr_guarded");
 }
 int qln_tracking_lqr_guarded_host(qln_handle* h, const double* Ztraj, const double* model, const double* event,
                                   const double* Qdiag, const double* Rdiag, const double* Qfdiag, double* K, double* P) {
-    LqrCall a{};
-    a.Zref = Ztraj; a.model = model; a.event = event; a.guarded = true;
-    a.Q = Qdiag; a.R = Rdiag; a.Qf = Qfdiag; a.K = K; a.P = P;
-    return tracking_lqr(h, kHostMem, a, "qln_tracking_lqr_guarded_host");
+    return tracking_lqr(h, kHostMem, at_events(lqr_call(Ztraj, Qdiag, Rdiag, Qfdiag, K, P), model, event),
+                        "qln_tracking_lqr_guarded_host");
 }
 // the design at the limited roll-out's active set: event selects the guarded blocks
 int qln_tracking_lqr_limited(qln_handle* h, const double* Ztraj, const double* model, const double* event, const double* sat,
                              const double* Qdiag, const double* Rdiag, const double* Qfdiag, double* K, double* P) {
-    LqrCall a{};
-    a.Zref = Ztraj; a.model = model; a.event = event; a.guarded = event != nullptr;
-    a.sat = sat; a.limited = true; a.Q = Qdiag; a.R = Rdiag; a.Qf = Qfdiag; a.K = K; a.P = P;
-    return tracking_lqr(h, kDeviceMem, a, "qln_tracking_lqr_limited");
+    return tracking_lqr(h, kDeviceMem, at_active_set(at_events(lqr_call(Ztraj, Qdiag, Rdiag, Qfdiag, K, P), model, event), sat),
+                        "qln_tracking_lqr_limited");
 }
 int qln_tracking_lqr_limited_host(qln_handle* h, const double* Ztraj, const double* model, const double* event, const double* sat,
                                   const double* Qdiag, const double* Rdiag, const double* Qfdiag, double* K, double* P) {
-    LqrCall a{};
-    a.Zref = Ztraj; a.model = model; a.event = event; a.guarded = event != nullptr;
-    a.sat = sat; a.limited = true; a.Q = Qdiag; a.R = Rdiag; a.Qf = Qfdiag; a.K = K; a.P = P;
-    return tracking_lqr(h, kHostMem, a, "qln_tracking_lqr_limited_host");
+    return tracking_lqr(h, kHostMem, at_active_set(at_events(lqr_call(Ztraj, Qdiag, Rdiag, Qfdiag, K, P), model, event), sat),
+                        "qln_tracking_lqr_limited_host");
 }
 
 // The roll-out (k_tracking_rollout), with the per-problem plant as an optional argument: the entry points without a model
@@ -1363,63 +1435,60 @@ static int tracking_rollout(qln_handle* h, MemForm mem, const RolloutCall& a, co
     const HostArgs args = {copy_in(kZ, a.Zref), copy_inout(kZio, a.Zout), copy_in(kK, a.K).ruled_if(false),
                            copy_in(kX0, a.x0).ruled_if(false), copy_in(kModel, a.model).ruled_if(false),
                            copy_out(kEvent, a.event), copy_out(kSat, a.sat)};
-    if (int rc = check_no_overlap(h, args, who)) return rc;
-    if (mem == kHostMem)
-        if (int rc = check_host_models(h, a.model, who)) return rc;
-    return run_call(h, mem, args, [&](double* const* d, bool) {
+    return run_tracking_call(h, mem, args, who, [&](double* const* d, bool) {
         return qln::launch_tracking_rollout(h->p, d[kZ], d[kK], d[kX0], d[kModel], d[kZio], a.guarded, d[kEvent],
                                             a.limited ? a.lim : nullptr, d[kSat], h->stream);
     });
 }
 
-int qln_tracking_rollout(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout) {
+static RolloutCall rollout_call(const double* Zref, const double* K, const double* x0, const double* model, double* Zout) {
     RolloutCall a{};
-    a.Zref = Zref; a.K = K; a.x0 = x0; a.Zout = Zout;
-    return tracking_rollout(h, kDeviceMem, a, "qln_tracking_rollout");
+    a.Zref = Zref; a.K = K; a.x0 = x0; a.model = model; a.Zout = Zout;
+    return a;
+}
+static RolloutCall with_touchdown(RolloutCall a, double* event) {
+    a.guarded = true; a.event = event;
+    return a;
+}
+static RolloutCall within_limits(RolloutCall a, const double* lim, int32_t guarded, double* event, double* sat) {
+    a.limited = true; a.lim = lim; a.sat = sat; a.guarded = guarded != 0; a.event = event;
+    return a;
+}
+
+int qln_tracking_rollout(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout) {
+    return tracking_rollout(h, kDeviceMem, rollout_call(Zref, K, x0, nullptr, Zout), "qln_tracking_rollout");
 }
 int qln_tracking_rollout_host(qln_handle* h, const double* Zref, const double* K, const double* x0, double* Zout) {
-    RolloutCall a{};
-    a.Zref = Zref; a.K = K; a.x0 = x0; a.Zout = Zout;
-    return tracking_rollout(h, kHostMem, a, "qln_tracking_rollout_host");
+    return tracking_rollout(h, kHostMem, rollout_call(Zref, K, x0, nullptr, Zout), "qln_tracking_rollout_host");
 }
 int qln_tracking_rollout_model(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
                                double* Zout) {
-    RolloutCall a{};
-    a.Zref = Zref; a.K = K; a.x0 = x0; a.model = model; a.Zout = Zout;
-    return tracking_rollout(h, kDeviceMem, a, "qln_tracking_rollout_model");
+    return tracking_rollout(h, kDeviceMem, rollout_call(Zref, K, x0, model, Zout), "qln_tracking_rollout_model");
 }
 int qln_tracking_rollout_model_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
                                     double* Zout) {
-    RolloutCall a{};
-    a.Zref = Zref; a.K = K; a.x0 = x0; a.model = model; a.Zout = Zout;
-    return tracking_rollout(h, kHostMem, a, "qln_tracking_rollout_model_host");
+    return tracking_rollout(h, kHostMem, rollout_call(Zref, K, x0, model, Zout), "qln_tracking_rollout_model_host");
 }
 int qln_tracking_rollout_guarded(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
                                  double* Zout, double* event) {
-    RolloutCall a{};
-    a.Zref = Zref; a.K = K; a.x0 = x0; a.model = model; a.Zout = Zout; a.guarded = true; a.event = event;
-    return tracking_rollout(h, kDeviceMem, a, "qln_tracking_rollout_guarded");
+    return tracking_rollout(h, kDeviceMem, with_touchdown(rollout_call(Zref, K, x0, model, Zout), event),
+                            "qln_tracking_rollout_guarded");
 }
 int qln_tracking_rollout_guarded_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
                                       double* Zout, double* event) {
-    RolloutCall a{};
-    a.Zref = Zref; a.K = K; a.x0 = x0; a.model = model; a.Zout = Zout; a.guarded = true; a.event = event;
-    return tracking_rollout(h, kHostMem, a, "qln_tracking_rollout_guarded_host");
+    return tracking_rollout(h, kHostMem, with_touchdown(rollout_call(Zref, K, x0, model, Zout), event),
+                            "qln_tracking_rollout_guarded_host");
 }
 // the roll-out within contact-aware force limits: the knot-scheduled or the guarded one, with its saturation record
 int qln_tracking_rollout_limited(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
                                  const double* lim, int32_t guarded, double* Zout, double* event, double* sat) {
-    RolloutCall a{};
-    a.Zref = Zref; a.K = K; a.x0 = x0; a.model = model; a.Zout = Zout;
-    a.guarded = guarded != 0; a.event = event; a.limited = true; a.lim = lim; a.sat = sat;
-    return tracking_rollout(h, kDeviceMem, a, "qln_tracking_rollout_limited");
+    return tracking_rollout(h, kDeviceMem, within_limits(rollout_call(Zref, K, x0, model, Zout), lim, guarded, event, sat),
+                            "qln_tracking_rollout_limited");
 }
 int qln_tracking_rollout_limited_host(qln_handle* h, const double* Zref, const double* K, const double* x0, const double* model,
                                       const double* lim, int32_t guarded, double* Zout, double* event, double* sat) {
-    RolloutCall a{};
-    a.Zref = Zref; a.K = K; a.x0 = x0; a.model = model; a.Zout = Zout;
-    a.guarded = guarded != 0; a.event = event; a.limited = true; a.lim = lim; a.sat = sat;
-    return tracking_rollout(h, kHostMem, a, "qln_tracking_rollout_limited_host");
+    return tracking_rollout(h, kHostMem, within_limits(rollout_call(Zref, K, x0, model, Zout), lim, guarded, event, sat),
+                            "qln_tracking_rollout_limited_host");
 }
 
 // Its reverse sweep (k_tracking_rollout_vjp).  model_bar goes with model, as in the roll-out.
@@ -1434,10 +1503,10 @@ struct RolloutVjpCall {
 
 static int check_tracking_vjp_args(const qln_handle* h, const RolloutVjpCall& a, const char* who) {
     const std::string w(who);
-    if (a.limited && !a.sat) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null sat (the limited roll-out's saturation record)");
+    if (int rc = check_limited_sat(a.limited, a.sat, w)) return rc;
     if (int rc = check_handle(h)) return rc;
     if (!a.Zref || !a.Zout || !a.Zbar) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref, Zout or Zbar");
-    if (a.guarded && !a.event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
+    if (int rc = check_guard_event(a.guarded, a.event, w)) return rc;
     if (a.K_bar && !a.K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_bar needs K (K == NULL has no gains to differentiate)");
     return QLN_OK;
 }
@@ -1450,76 +1519,83 @@ static int tracking_rollout_vjp(qln_handle* h, MemForm mem, const RolloutVjpCall
                            copy_in(kK, a.K), copy_in(kModel, a.model), copy_in(kEvent, a.event), copy_in(kSat, a.sat),
                            copy_inout(kZio, a.Zref_bar), copy_out(kKbar, a.K_bar), copy_out(kX0, a.x0_bar),
                            copy_out(kModelD, a.model_bar)};
-    if (int rc = check_no_overlap(h, args, who)) return rc;
-    if (mem == kHostMem) {
-        if (int rc = check_host_models(h, a.model, who)) return rc;
-        if (int rc = check_host_events(h, a.event, who)) return rc;
-        if (int rc = check_host_sat(h, a.sat, who)) return rc;
-    }
-    return run_call(h, mem, args, [&](double* const* d, bool) {
+    return run_tracking_call(h, mem, args, who, [&](double* const* d, bool) {
         return qln::launch_tracking_rollout_vjp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kModel], d[kEvent], d[kSat],
                                                 d[kZbar], d[kZio], d[kKbar], d[kX0], d[kModelD], h->stream);
     });
 }
 
-int qln_tracking_rollout_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
-                             double* Zref_bar, double* K_bar, double* x0_bar) {
+static RolloutVjpCall rollout_vjp_call(const double* Zref, const double* K, const double* Zout, const double* Zbar,
+                                       double* Zref_bar, double* K_bar, double* x0_bar) {
     RolloutVjpCall a{};
     a.Zref = Zref; a.K = K; a.Zout = Zout; a.Zbar = Zbar; a.Zref_bar = Zref_bar; a.K_bar = K_bar; a.x0_bar = x0_bar;
-    return tracking_rollout_vjp(h, kDeviceMem, a, "qln_tracking_rollout_vjp");
+    return a;
+}
+static RolloutVjpCall with_model(RolloutVjpCall a, const double* model, double* model_bar) {
+    a.model = model; a.model_bar = model_bar;
+    return a;
+}
+static RolloutVjpCall at_events(RolloutVjpCall a, const double* event) {
+    a.guarded = true; a.event = event;
+    return a;
+}
+static RolloutVjpCall at_active_set(RolloutVjpCall a, const double* sat) {
+    a.limited = true; a.sat = sat; a.guarded = a.event != nullptr;
+    return a;
+}
+
+int qln_tracking_rollout_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
+                             double* Zref_bar, double* K_bar, double* x0_bar) {
+    return tracking_rollout_vjp(h, kDeviceMem, rollout_vjp_call(Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar),
+                                "qln_tracking_rollout_vjp");
 }
 int qln_tracking_rollout_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zbar,
                                   double* Zref_bar, double* K_bar, double* x0_bar) {
-    RolloutVjpCall a{};
-    a.Zref = Zref; a.K = K; a.Zout = Zout; a.Zbar = Zbar; a.Zref_bar = Zref_bar; a.K_bar = K_bar; a.x0_bar = x0_bar;
-    return tracking_rollout_vjp(h, kHostMem, a, "qln_tracking_rollout_vjp_host");
+    return tracking_rollout_vjp(h, kHostMem, rollout_vjp_call(Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar),
+                                "qln_tracking_rollout_vjp_host");
 }
 int qln_tracking_rollout_model_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
                                    const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar) {
-    RolloutVjpCall a{};
-    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.Zbar = Zbar;
-    a.Zref_bar = Zref_bar; a.K_bar = K_bar; a.x0_bar = x0_bar; a.model_bar = model_bar;
-    return tracking_rollout_vjp(h, kDeviceMem, a, "qln_tracking_rollout_model_vjp");
+    return tracking_rollout_vjp(h, kDeviceMem,
+                                with_model(rollout_vjp_call(Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar), model, model_bar),
+                                "qln_tracking_rollout_model_vjp");
 }
 int qln_tracking_rollout_model_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                         const double* model, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
                                         double* model_bar) {
-    RolloutVjpCall a{};
-    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.Zbar = Zbar;
-    a.Zref_bar = Zref_bar; a.K_bar = K_bar; a.x0_bar = x0_bar; a.model_bar = model_bar;
-    return tracking_rollout_vjp(h, kHostMem, a, "qln_tracking_rollout_model_vjp_host");
+    return tracking_rollout_vjp(h, kHostMem,
+                                with_model(rollout_vjp_call(Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar), model, model_bar),
+                                "qln_tracking_rollout_model_vjp_host");
 }
 int qln_tracking_rollout_guarded_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
                                      const double* event, const double* Zbar, double* Zref_bar, double* K_bar, double* x0_bar,
                                      double* model_bar) {
-    RolloutVjpCall a{};
-    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.guarded = true; a.event = event;
-    a.Zbar = Zbar; a.Zref_bar = Zref_bar; a.K_bar = K_bar; a.x0_bar = x0_bar; a.model_bar = model_bar;
-    return tracking_rollout_vjp(h, kDeviceMem, a, "qln_tracking_rollout_guarded_vjp");
+    return tracking_rollout_vjp(h, kDeviceMem,
+                                at_events(with_model(rollout_vjp_call(Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar), model,
+                                                     model_bar), event), "qln_tracking_rollout_guarded_vjp");
 }
 int qln_tracking_rollout_guarded_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                           const double* model, const double* event, const double* Zbar, double* Zref_bar,
                                           double* K_bar, double* x0_bar, double* model_bar) {
-    RolloutVjpCall a{};
-    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.guarded = true; a.event = event;
-    a.Zbar = Zbar; a.Zref_bar = Zref_bar; a.K_bar = K_bar; a.x0_bar = x0_bar; a.model_bar = model_bar;
-    return tracking_rollout_vjp(h, kHostMem, a, "qln_tracking_rollout_guarded_vjp_host");
+    return tracking_rollout_vjp(h, kHostMem,
+                                at_events(with_model(rollout_vjp_call(Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar), model,
+                                                     model_bar), event), "qln_tracking_rollout_guarded_vjp_host");
 }
 int qln_tracking_rollout_limited_vjp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
                                      const double* event, const double* sat, const double* Zbar, double* Zref_bar, double* K_bar,
                                      double* x0_bar, double* model_bar) {
-    RolloutVjpCall a{};
-    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.guarded = event != nullptr; a.event = event; a.limited = true;
-    a.sat = sat; a.Zbar = Zbar; a.Zref_bar = Zref_bar; a.K_bar = K_bar; a.x0_bar = x0_bar; a.model_bar = model_bar;
-    return tracking_rollout_vjp(h, kDeviceMem, a, "qln_tracking_rollout_limited_vjp");
+    return tracking_rollout_vjp(h, kDeviceMem,
+                                at_active_set(at_events(with_model(rollout_vjp_call(Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar),
+                                                                   model, model_bar), event), sat),
+                                "qln_tracking_rollout_limited_vjp");
 }
 int qln_tracking_rollout_limited_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                           const double* model, const double* event, const double* sat, const double* Zbar,
                                           double* Zref_bar, double* K_bar, double* x0_bar, double* model_bar) {
-    RolloutVjpCall a{};
-    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.guarded = event != nullptr; a.event = event; a.limited = true;
-    a.sat = sat; a.Zbar = Zbar; a.Zref_bar = Zref_bar; a.K_bar = K_bar; a.x0_bar = x0_bar; a.model_bar = model_bar;
-    return tracking_rollout_vjp(h, kHostMem, a, "qln_tracking_rollout_limited_vjp_host");
+    return tracking_rollout_vjp(h, kHostMem,
+                                at_active_set(at_events(with_model(rollout_vjp_call(Zref, K, Zout, Zbar, Zref_bar, K_bar, x0_bar),
+                                                                   model, model_bar), event), sat),
+                                "qln_tracking_rollout_limited_vjp_host");
 }
 
 // Its forward sweep (k_tracking_rollout_jvp).  The checks that need no handle come first.  guarded and limited as in the
@@ -1532,10 +1608,10 @@ struct RolloutJvpCall {
 
 static int check_tracking_jvp_args(const qln_handle* h, const RolloutJvpCall& a, const char* who) {
     const std::string w(who);
-    if (a.limited && !a.sat) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null sat (the limited roll-out's saturation record)");
+    if (int rc = check_limited_sat(a.limited, a.sat, w)) return rc;
     if (a.limited && !a.event && a.event_dot)
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": event_dot without event (the knot-scheduled sweep has no record)");
-    if (a.guarded && !a.event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
+    if (int rc = check_guard_event(a.guarded, a.event, w)) return rc;
     if (!a.Zref_dot && !a.K_dot && !a.x0_dot && !a.model_dot)
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every tangent is NULL (no direction)");
     if (a.K_dot && !a.K) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": K_dot needs K (K == NULL has no gains to perturb)");
@@ -1551,88 +1627,85 @@ static int tracking_rollout_jvp(qln_handle* h, MemForm mem, const RolloutJvpCall
                            copy_in(kModel, a.model), copy_in(kEvent, a.event), copy_in(kSat, a.sat), copy_in(kZdot, a.Zref_dot),
                            copy_in(kKdot, a.K_dot), copy_in(kX0, a.x0_dot), copy_in(kModelD, a.model_dot),
                            copy_inout(kZio, a.Zout_dot), copy_out(kEventD, a.event_dot)};
-    if (int rc = check_no_overlap(h, args, who)) return rc;
-    if (mem == kHostMem) {
-        if (int rc = check_host_models(h, a.model, who)) return rc;
-        if (int rc = check_host_events(h, a.event, who)) return rc;
-        if (int rc = check_host_sat(h, a.sat, who)) return rc;
-    }
-    return run_call(h, mem, args, [&](double* const* d, bool) {
+    return run_tracking_call(h, mem, args, who, [&](double* const* d, bool) {
         return qln::launch_tracking_rollout_jvp(h->p, d[kZ] ? d[kZ] : d[kV], d[kK], d[kV], d[kModel], d[kEvent], d[kSat],
                                                 d[kZdot], d[kKdot], d[kX0], d[kModelD], d[kZio], d[kEventD], h->stream);
     });
 }
 
-int qln_tracking_rollout_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zref_dot,
-                             const double* K_dot, const double* x0_dot, double* Zout_dot) {
+static RolloutJvpCall rollout_jvp_call(const double* Zref, const double* K, const double* Zout, const double* Zref_dot,
+                                       const double* K_dot, const double* x0_dot, double* Zout_dot) {
     RolloutJvpCall a{};
     a.Zref = Zref; a.K = K; a.Zout = Zout; a.Zref_dot = Zref_dot; a.K_dot = K_dot; a.x0_dot = x0_dot; a.Zout_dot = Zout_dot;
-    return tracking_rollout_jvp(h, kDeviceMem, a, "qln_tracking_rollout_jvp");
+    return a;
+}
+static RolloutJvpCall with_model(RolloutJvpCall a, const double* model, const double* model_dot) {
+    a.model = model; a.model_dot = model_dot;
+    return a;
+}
+static RolloutJvpCall at_events(RolloutJvpCall a, const double* event, double* event_dot) {
+    a.guarded = true; a.event = event; a.event_dot = event_dot;
+    return a;
+}
+static RolloutJvpCall at_active_set(RolloutJvpCall a, const double* sat) {
+    a.limited = true; a.sat = sat; a.guarded = a.event != nullptr;
+    return a;
+}
+
+int qln_tracking_rollout_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* Zref_dot,
+                             const double* K_dot, const double* x0_dot, double* Zout_dot) {
+    return tracking_rollout_jvp(h, kDeviceMem, rollout_jvp_call(Zref, K, Zout, Zref_dot, K_dot, x0_dot, Zout_dot),
+                                "qln_tracking_rollout_jvp");
 }
 int qln_tracking_rollout_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                   const double* Zref_dot, const double* K_dot, const double* x0_dot, double* Zout_dot) {
-    RolloutJvpCall a{};
-    a.Zref = Zref; a.K = K; a.Zout = Zout; a.Zref_dot = Zref_dot; a.K_dot = K_dot; a.x0_dot = x0_dot; a.Zout_dot = Zout_dot;
-    return tracking_rollout_jvp(h, kHostMem, a, "qln_tracking_rollout_jvp_host");
+    return tracking_rollout_jvp(h, kHostMem, rollout_jvp_call(Zref, K, Zout, Zref_dot, K_dot, x0_dot, Zout_dot),
+                                "qln_tracking_rollout_jvp_host");
 }
 int qln_tracking_rollout_model_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
                                    const double* Zref_dot, const double* K_dot, const double* x0_dot, const double* model_dot,
                                    double* Zout_dot) {
-    RolloutJvpCall a{};
-    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.Zref_dot = Zref_dot;
-    a.K_dot = K_dot; a.x0_dot = x0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot;
-    return tracking_rollout_jvp(h, kDeviceMem, a, "qln_tracking_rollout_model_jvp");
+    return tracking_rollout_jvp(h, kDeviceMem,
+                                with_model(rollout_jvp_call(Zref, K, Zout, Zref_dot, K_dot, x0_dot, Zout_dot), model, model_dot),
+                                "qln_tracking_rollout_model_jvp");
 }
 int qln_tracking_rollout_model_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                         const double* model, const double* Zref_dot, const double* K_dot, const double* x0_dot,
                                         const double* model_dot, double* Zout_dot) {
-    RolloutJvpCall a{};
-    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.Zref_dot = Zref_dot;
-    a.K_dot = K_dot; a.x0_dot = x0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot;
-    return tracking_rollout_jvp(h, kHostMem, a, "qln_tracking_rollout_model_jvp_host");
+    return tracking_rollout_jvp(h, kHostMem,
+                                with_model(rollout_jvp_call(Zref, K, Zout, Zref_dot, K_dot, x0_dot, Zout_dot), model, model_dot),
+                                "qln_tracking_rollout_model_jvp_host");
 }
 int qln_tracking_rollout_guarded_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
                                      const double* event, const double* Zref_dot, const double* K_dot, const double* x0_dot,
                                      const double* model_dot, double* Zout_dot, double* event_dot) {
-    RolloutJvpCall a{};
-    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.guarded = true; a.event = event; a.Zref_dot = Zref_dot;
-    a.K_dot = K_dot; a.x0_dot = x0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.event_dot = event_dot;
-    return tracking_rollout_jvp(h, kDeviceMem, a, "qln_tracking_rollout_guarded_jvp");
+    return tracking_rollout_jvp(h, kDeviceMem,
+                                at_events(with_model(rollout_jvp_call(Zref, K, Zout, Zref_dot, K_dot, x0_dot, Zout_dot), model,
+                                                     model_dot), event, event_dot), "qln_tracking_rollout_guarded_jvp");
 }
 int qln_tracking_rollout_guarded_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                           const double* model, const double* event, const double* Zref_dot, const double* K_dot,
                                           const double* x0_dot, const double* model_dot, double* Zout_dot, double* event_dot) {
-    RolloutJvpCall a{};
-    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.guarded = true; a.event = event; a.Zref_dot = Zref_dot;
-    a.K_dot = K_dot; a.x0_dot = x0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.event_dot = event_dot;
-    return tracking_rollout_jvp(h, kHostMem, a, "qln_tracking_rollout_guarded_jvp_host");
+    return tracking_rollout_jvp(h, kHostMem,
+                                at_events(with_model(rollout_jvp_call(Zref, K, Zout, Zref_dot, K_dot, x0_dot, Zout_dot), model,
+                                                     model_dot), event, event_dot), "qln_tracking_rollout_guarded_jvp_host");
 }
 int qln_tracking_rollout_limited_jvp(qln_handle* h, const double* Zref, const double* K, const double* Zout, const double* model,
                                      const double* event, const double* sat, const double* Zref_dot, const double* K_dot,
                                      const double* x0_dot, const double* model_dot, double* Zout_dot, double* event_dot) {
-    RolloutJvpCall a{};
-    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.guarded = event != nullptr;
-    a.event = event; a.limited = true; a.sat = sat; a.Zref_dot = Zref_dot; a.K_dot = K_dot;
-    a.x0_dot = x0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.event_dot = event_dot;
-    return tracking_rollout_jvp(h, kDeviceMem, a, "qln_tracking_rollout_limited_jvp");
+    return tracking_rollout_jvp(h, kDeviceMem,
+                                at_active_set(at_events(with_model(rollout_jvp_call(Zref, K, Zout, Zref_dot, K_dot, x0_dot,
+                                                                                    Zout_dot), model, model_dot), event, event_dot),
+                                              sat), "qln_tracking_rollout_limited_jvp");
 }
 int qln_tracking_rollout_limited_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Zout,
                                           const double* model, const double* event, const double* sat, const double* Zref_dot,
                                           const double* K_dot, const double* x0_dot, const double* model_dot, double* Zout_dot,
                                           double* event_dot) {
-    RolloutJvpCall a{};
-    a.Zref = Zref; a.K = K; a.Zout = Zout; a.model = model; a.guarded = event != nullptr;
-    a.event = event; a.limited = true; a.sat = sat; a.Zref_dot = Zref_dot; a.K_dot = K_dot;
-    a.x0_dot = x0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.event_dot = event_dot;
-    return tracking_rollout_jvp(h, kHostMem, a, "qln_tracking_rollout_limited_jvp_host");
-}
-
-static int check_tracking_wdiag(const double* Wdiag, const std::string& w) {
-    if (Wdiag)
-        for (int i = 0; i < QLN_NX; ++i)
-            if (!(std::isfinite(Wdiag[i]) && Wdiag[i] >= 0.0))
-                return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Wdiag must be finite and >= 0 (entry " + std::to_string(i) + ")");
-    return QLN_OK;
+    return tracking_rollout_jvp(h, kHostMem,
+                                at_active_set(at_events(with_model(rollout_jvp_call(Zref, K, Zout, Zref_dot, K_dot, x0_dot,
+                                                                                    Zout_dot), model, model_dot), event, event_dot),
+                                              sat), "qln_tracking_rollout_limited_jvp_host");
 }
 
 // The covariance sweep (k_tracking_covariance).  The checks that need no handle come first.
@@ -1650,12 +1723,11 @@ static int check_tracking_covariance_args(const qln_handle* h, const CovarianceC
     if (!a.Sigma && !a.marg && !a.event_var)
         return fail(QLN_ERR_INVALID_ARGUMENT, a.guarded ? w + ": Sigma, marg and event_var are all NULL (nothing to compute)"
                                                         : w + ": Sigma and marg are both NULL (nothing to compute)");
-    if (a.guarded && !a.event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
+    if (int rc = check_guard_event(a.guarded, a.event, w)) return rc;
     if (int rc = check_tracking_wdiag(a.Wdiag, w)) return rc;
-    if (a.sigma0_batch < 1) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
+    if (int rc = check_sigma0_batch(a.sigma0_batch, nullptr, w)) return rc;
     if (int rc = check_handle(h)) return rc;
-    if (a.sigma0_batch != 1 && a.sigma0_batch != h->dims.B)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
+    if (int rc = check_sigma0_batch(a.sigma0_batch, h, w)) return rc;
     if (!a.Zout || !a.Sigma0) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zout or Sigma0");
     return QLN_OK;
 }
@@ -1666,44 +1738,46 @@ static int tracking_covariance(qln_handle* h, MemForm mem, const CovarianceCall&
     const HostArgs args = {copy_in(kV, a.Zout), copy_in(kK, a.K), copy_in(kModel, a.model), copy_in(kEvent, a.event),
                            copy_in(kCov0, a.Sigma0).sized((int64_t)a.sigma0_batch * QLN_TRACK_P_NNZ), copy_out(kCov, a.Sigma),
                            copy_out(kMarg, a.marg), copy_out(kEventVar, a.event_var)};
-    if (int rc = check_no_overlap(h, args, who)) return rc;
-    if (mem == kHostMem) {
-        if (int rc = check_host_models(h, a.model, who)) return rc;
-        if (int rc = check_host_events(h, a.event, who)) return rc;
-    }
-    return run_call(h, mem, args, [&](double* const* d, bool) {
+    return run_tracking_call(h, mem, args, who, [&](double* const* d, bool) {
         return qln::launch_tracking_covariance(h->p, d[kV], d[kK], d[kModel], d[kEvent], d[kCov0], a.sigma0_batch, a.Wdiag,
                                                d[kCov], d[kMarg], d[kEventVar], h->stream);
     });
 }
 
-int qln_tracking_covariance(qln_handle* h, const double* Zout, const double* K, const double* Sigma0, int32_t sigma0_batch,
-                            const double* Wdiag, double* Sigma, double* marg) {
+static CovarianceCall covariance_call(const double* Zout, const double* K, const double* Sigma0, int32_t sigma0_batch,
+                                      const double* Wdiag, double* Sigma, double* marg) {
     CovarianceCall a{};
     a.Zout = Zout; a.K = K; a.Sigma0 = Sigma0; a.sigma0_batch = sigma0_batch; a.Wdiag = Wdiag; a.Sigma = Sigma; a.marg = marg;
-    return tracking_covariance(h, kDeviceMem, a, "qln_tracking_covariance");
+    return a;
+}
+static CovarianceCall at_events(CovarianceCall a, const double* model, const double* event, double* event_var) {
+    a.guarded = true; a.model = model; a.event = event; a.event_var = event_var;
+    return a;
+}
+
+int qln_tracking_covariance(qln_handle* h, const double* Zout, const double* K, const double* Sigma0, int32_t sigma0_batch,
+                            const double* Wdiag, double* Sigma, double* marg) {
+    return tracking_covariance(h, kDeviceMem, covariance_call(Zout, K, Sigma0, sigma0_batch, Wdiag, Sigma, marg),
+                               "qln_tracking_covariance");
 }
 int qln_tracking_covariance_host(qln_handle* h, const double* Zout, const double* K, const double* Sigma0,
                                  int32_t sigma0_batch, const double* Wdiag, double* Sigma, double* marg) {
-    CovarianceCall a{};
-    a.Zout = Zout; a.K = K; a.Sigma0 = Sigma0; a.sigma0_batch = sigma0_batch; a.Wdiag = Wdiag; a.Sigma = Sigma; a.marg = marg;
-    return tracking_covariance(h, kHostMem, a, "qln_tracking_covariance_host");
+    return tracking_covariance(h, kHostMem, covariance_call(Zout, K, Sigma0, sigma0_batch, Wdiag, Sigma, marg),
+                               "qln_tracking_covariance_host");
 }
 int qln_tracking_covariance_guarded(qln_handle* h, const double* Zout, const double* K, const double* model, const double* event,
                                     const double* Sigma0, int32_t sigma0_batch, const double* Wdiag, double* Sigma, double* marg,
                                     double* event_var) {
-    CovarianceCall a{};
-    a.Zout = Zout; a.K = K; a.model = model; a.guarded = true; a.event = event; a.Sigma0 = Sigma0;
-    a.sigma0_batch = sigma0_batch; a.Wdiag = Wdiag; a.Sigma = Sigma; a.marg = marg; a.event_var = event_var;
-    return tracking_covariance(h, kDeviceMem, a, "qln_tracking_covariance_guarded");
+    return tracking_covariance(h, kDeviceMem,
+                               at_events(covariance_call(Zout, K, Sigma0, sigma0_batch, Wdiag, Sigma, marg), model, event,
+                                         event_var), "qln_tracking_covariance_guarded");
 }
 int qln_tracking_covariance_guarded_host(qln_handle* h, const double* Zout, const double* K, const double* model,
                                          const double* event, const double* Sigma0, int32_t sigma0_batch, const double* Wdiag,
                                          double* Sigma, double* marg, double* event_var) {
-    CovarianceCall a{};
-    a.Zout = Zout; a.K = K; a.model = model; a.guarded = true; a.event = event; a.Sigma0 = Sigma0;
-    a.sigma0_batch = sigma0_batch; a.Wdiag = Wdiag; a.Sigma = Sigma; a.marg = marg; a.event_var = event_var;
-    return tracking_covariance(h, kHostMem, a, "qln_tracking_covariance_guarded_host");
+    return tracking_covariance(h, kHostMem,
+                               at_events(covariance_call(Zout, K, Sigma0, sigma0_batch, Wdiag, Sigma, marg), model, event,
+                                         event_var), "qln_tracking_covariance_guarded_host");
 }
 
 // The Kalman filter and the LQG covariance (k_tracking_kalman).  The checks that need no handle come first.
@@ -1720,22 +1794,17 @@ struct KalmanCall {
 
 static int check_tracking_kalman_args(const qln_handle* h, const KalmanCall& a, const char* who) {
     const std::string w(who);
-    if (a.ny < 1 || a.ny > QLN_TRACK_NY_MAX)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
-    if (!a.Lgain && !a.Pest && !a.Sigma && !a.marg && !a.event_var)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every output is NULL (nothing to compute)");
+    if (int rc = check_tracking_ny(a.ny, w)) return rc;
+    if (int rc = check_some_output(a.Lgain || a.Pest || a.Sigma || a.marg || a.event_var, w)) return rc;
     if (!a.K && (a.Sigma || a.marg || a.event_var))
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Sigma, marg and event_var need K (K == NULL is the filter alone: Lgain and Pest)");
-    if (a.guarded && !a.event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
+    if (int rc = check_guard_event(a.guarded, a.event, w)) return rc;
     if (!a.H || !a.Vdiag) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null H or Vdiag");
-    for (int i = 0; i < a.ny; ++i)
-        if (!(std::isfinite(a.Vdiag[i]) && a.Vdiag[i] > 0.0))
-            return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Vdiag must be finite and > 0 (entry " + std::to_string(i) + ")");
+    if (int rc = check_tracking_vdiag(a.Vdiag, a.ny, w)) return rc;
     if (int rc = check_tracking_wdiag(a.Wdiag, w)) return rc;
-    if (a.sigma0_batch < 1) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
+    if (int rc = check_sigma0_batch(a.sigma0_batch, nullptr, w)) return rc;
     if (int rc = check_handle(h)) return rc;
-    if (a.sigma0_batch != 1 && a.sigma0_batch != h->dims.B)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
+    if (int rc = check_sigma0_batch(a.sigma0_batch, h, w)) return rc;
     if (!a.Zout || !a.Sigma0) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zout or Sigma0");
     return QLN_OK;
 }
@@ -1743,58 +1812,57 @@ static int check_tracking_kalman_args(const qln_handle* h, const KalmanCall& a, 
 static int tracking_kalman(qln_handle* h, MemForm mem, const KalmanCall& a, const char* who) {
     if (int rc = check_tracking_kalman_args(h, a, who)) return rc;
     // the rows the call reads and the gains it writes, of the roles' eight; the tiles it reads, of the role's B
-    const HostArgs args = {copy_in(kV, a.Zout), copy_in(kK, a.K), copy_in(kModel, a.model), copy_in(kEvent, a.event),
-                           copy_in(kH, a.H).sized((int64_t)a.ny * QLN_NX),
+    const HostArgs args = {copy_in(kV, a.Zout), copy_in(kK, a.K), copy_in(kH, a.H).sized((int64_t)a.ny * QLN_NX),
+                           copy_in(kModel, a.model), copy_in(kEvent, a.event),
                            copy_in(kCov0, a.Sigma0).sized((int64_t)a.sigma0_batch * QLN_TRACK_P_NNZ),
                            copy_out(kLgain, a.Lgain).sized(tracking_gain_total(h->dims, a.ny)), copy_out(kPest, a.Pest),
                            copy_out(kCov, a.Sigma), copy_out(kMarg, a.marg), copy_out(kEventVar, a.event_var)};
-    if (int rc = check_no_overlap(h, args, who)) return rc;
-    if (mem == kHostMem) {
-        if (int rc = check_host_meas(a.H, a.ny, who)) return rc;
-        if (int rc = check_host_models(h, a.model, who)) return rc;
-        if (int rc = check_host_events(h, a.event, who)) return rc;
-    }
-    return run_call(h, mem, args, [&](double* const* d, bool) {
+    return run_tracking_call(h, mem, args, who, [&](double* const* d, bool) {
         return qln::launch_tracking_kalman(h->p, d[kV], d[kK], d[kModel], d[kEvent], d[kH], a.ny, a.Vdiag, d[kCov0],
                                            a.sigma0_batch, a.Wdiag, d[kLgain], d[kPest], d[kCov], d[kMarg], d[kEventVar],
                                            h->stream);
     });
 }
 
-int qln_tracking_kalman(qln_handle* h, const double* Zout, const double* K, const double* H, int32_t ny, const double* Vdiag,
-                        const double* Sigma0, int32_t sigma0_batch, const double* Wdiag, double* Lgain, double* Pest,
-                        double* Sigma, double* marg) {
+static KalmanCall kalman_call(const double* Zout, const double* K, const double* H, int32_t ny, const double* Vdiag,
+                              const double* Sigma0, int32_t sigma0_batch, const double* Wdiag, double* Lgain, double* Pest,
+                              double* Sigma, double* marg) {
     KalmanCall a{};
     a.Zout = Zout; a.K = K; a.H = H; a.ny = ny; a.Vdiag = Vdiag; a.Sigma0 = Sigma0; a.sigma0_batch = sigma0_batch;
     a.Wdiag = Wdiag; a.Lgain = Lgain; a.Pest = Pest; a.Sigma = Sigma; a.marg = marg;
-    return tracking_kalman(h, kDeviceMem, a, "qln_tracking_kalman");
+    return a;
+}
+static KalmanCall at_events(KalmanCall a, const double* model, const double* event, double* event_var) {
+    a.guarded = true; a.model = model; a.event = event; a.event_var = event_var;
+    return a;
+}
+
+int qln_tracking_kalman(qln_handle* h, const double* Zout, const double* K, const double* H, int32_t ny, const double* Vdiag,
+                        const double* Sigma0, int32_t sigma0_batch, const double* Wdiag, double* Lgain, double* Pest,
+                        double* Sigma, double* marg) {
+    return tracking_kalman(h, kDeviceMem, kalman_call(Zout, K, H, ny, Vdiag, Sigma0, sigma0_batch, Wdiag, Lgain, Pest, Sigma, marg),
+                           "qln_tracking_kalman");
 }
 int qln_tracking_kalman_host(qln_handle* h, const double* Zout, const double* K, const double* H, int32_t ny, const double* Vdiag,
                              const double* Sigma0, int32_t sigma0_batch, const double* Wdiag, double* Lgain, double* Pest,
                              double* Sigma, double* marg) {
-    KalmanCall a{};
-    a.Zout = Zout; a.K = K; a.H = H; a.ny = ny; a.Vdiag = Vdiag; a.Sigma0 = Sigma0; a.sigma0_batch = sigma0_batch;
-    a.Wdiag = Wdiag; a.Lgain = Lgain; a.Pest = Pest; a.Sigma = Sigma; a.marg = marg;
-    return tracking_kalman(h, kHostMem, a, "qln_tracking_kalman_host");
+    return tracking_kalman(h, kHostMem, kalman_call(Zout, K, H, ny, Vdiag, Sigma0, sigma0_batch, Wdiag, Lgain, Pest, Sigma, marg),
+                           "qln_tracking_kalman_host");
 }
 int qln_tracking_kalman_guarded(qln_handle* h, const double* Zout, const double* K, const double* model, const double* event,
                                 const double* H, int32_t ny, const double* Vdiag, const double* Sigma0, int32_t sigma0_batch,
                                 const double* Wdiag, double* Lgain, double* Pest, double* Sigma, double* marg, double* event_var) {
-    KalmanCall a{};
-    a.Zout = Zout; a.K = K; a.model = model; a.guarded = true; a.event = event; a.H = H;
-    a.ny = ny; a.Vdiag = Vdiag; a.Sigma0 = Sigma0; a.sigma0_batch = sigma0_batch; a.Wdiag = Wdiag;
-    a.Lgain = Lgain; a.Pest = Pest; a.Sigma = Sigma; a.marg = marg; a.event_var = event_var;
-    return tracking_kalman(h, kDeviceMem, a, "qln_tracking_kalman_guarded");
+    return tracking_kalman(h, kDeviceMem,
+                           at_events(kalman_call(Zout, K, H, ny, Vdiag, Sigma0, sigma0_batch, Wdiag, Lgain, Pest, Sigma, marg),
+                                     model, event, event_var), "qln_tracking_kalman_guarded");
 }
 int qln_tracking_kalman_guarded_host(qln_handle* h, const double* Zout, const double* K, const double* model, const double* event,
                                      const double* H, int32_t ny, const double* Vdiag, const double* Sigma0, int32_t sigma0_batch,
                                      const double* Wdiag, double* Lgain, double* Pest, double* Sigma, double* marg,
                                      double* event_var) {
-    KalmanCall a{};
-    a.Zout = Zout; a.K = K; a.model = model; a.guarded = true; a.event = event; a.H = H;
-    a.ny = ny; a.Vdiag = Vdiag; a.Sigma0 = Sigma0; a.sigma0_batch = sigma0_batch; a.Wdiag = Wdiag;
-    a.Lgain = Lgain; a.Pest = Pest; a.Sigma = Sigma; a.marg = marg; a.event_var = event_var;
-    return tracking_kalman(h, kHostMem, a, "qln_tracking_kalman_guarded_host");
+    return tracking_kalman(h, kHostMem,
+                           at_events(kalman_call(Zout, K, H, ny, Vdiag, Sigma0, sigma0_batch, Wdiag, Lgain, Pest, Sigma, marg),
+                                     model, event, event_var), "qln_tracking_kalman_guarded_host");
 }
 
 // The forward sweep through the Kalman design (k_tracking_kalman_jvp).  The checks that need no handle come first.
@@ -1811,15 +1879,11 @@ struct KalmanJvpCall {
 
 static int check_kalman_design_jvp_args(const qln_handle* h, const KalmanJvpCall& a, const char* who) {
     const std::string w(who);
-    if (a.ny < 1 || a.ny > QLN_TRACK_NY_MAX)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
-    if (!a.Lgain_dot && !a.Pest_dot && !a.logdet_dot)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every output is NULL (nothing to compute)");
-    if (a.guarded && !a.event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
+    if (int rc = check_tracking_ny(a.ny, w)) return rc;
+    if (int rc = check_some_output(a.Lgain_dot || a.Pest_dot || a.logdet_dot, w)) return rc;
+    if (int rc = check_guard_event(a.guarded, a.event, w)) return rc;
     if (!a.H || !a.Vdiag) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null H or Vdiag");
-    for (int i = 0; i < a.ny; ++i)
-        if (!(std::isfinite(a.Vdiag[i]) && a.Vdiag[i] > 0.0))
-            return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Vdiag must be finite and > 0 (entry " + std::to_string(i) + ")");
+    if (int rc = check_tracking_vdiag(a.Vdiag, a.ny, w)) return rc;
     if (!a.Sigma0_dot && !a.Wdiag_dot && !a.Vdiag_dot)
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Sigma0_dot, Wdiag_dot and Vdiag_dot are all NULL (no direction)");
     if (a.Wdiag_dot)
@@ -1831,10 +1895,11 @@ static int check_kalman_design_jvp_args(const qln_handle* h, const KalmanJvpCall
             if (!std::isfinite(a.Vdiag_dot[i]))
                 return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Vdiag_dot must be finite (entry " + std::to_string(i) + ")");
     if (!a.Lgain) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Lgain");
-    if (a.Sigma0_dot && a.sigma0_batch < 1) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
+    if (a.Sigma0_dot)
+        if (int rc = check_sigma0_batch(a.sigma0_batch, nullptr, w)) return rc;
     if (int rc = check_handle(h)) return rc;
-    if (a.Sigma0_dot && a.sigma0_batch != 1 && a.sigma0_batch != h->dims.B)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": sigma0_batch must be 1 or B");
+    if (a.Sigma0_dot)
+        if (int rc = check_sigma0_batch(a.sigma0_batch, h, w)) return rc;
     if (!a.Zout) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zout");
     return QLN_OK;
 }
@@ -1844,17 +1909,11 @@ static int kalman_design_jvp(qln_handle* h, MemForm mem, const KalmanJvpCall& a,
     // the rows and gains of the call's ny, of the roles' eight; the tiles it reads, of the role's B
     const int64_t ng = tracking_gain_total(h->dims, a.ny);
     const int32_t nb = a.Sigma0_dot ? a.sigma0_batch : 1;
-    const HostArgs args = {copy_in(kV, a.Zout), copy_in(kModel, a.model), copy_in(kEvent, a.event),
-                           copy_in(kLgain, a.Lgain).sized(ng), copy_in(kH, a.H).sized((int64_t)a.ny * QLN_NX),
+    const HostArgs args = {copy_in(kV, a.Zout), copy_in(kH, a.H).sized((int64_t)a.ny * QLN_NX), copy_in(kModel, a.model),
+                           copy_in(kEvent, a.event), copy_in(kLgain, a.Lgain).sized(ng),
                            copy_in(kCov0, a.Sigma0_dot).sized((int64_t)nb * QLN_TRACK_P_NNZ),
                            copy_out(kLgainD, a.Lgain_dot).sized(ng), copy_out(kPest, a.Pest_dot), copy_out(kNisD, a.logdet_dot)};
-    if (int rc = check_no_overlap(h, args, who)) return rc;
-    if (mem == kHostMem) {
-        if (int rc = check_host_meas(a.H, a.ny, who)) return rc;
-        if (int rc = check_host_models(h, a.model, who)) return rc;
-        if (int rc = check_host_events(h, a.event, who)) return rc;
-    }
-    return run_call(h, mem, args, [&](double* const* d, bool) {
+    return run_tracking_call(h, mem, args, who, [&](double* const* d, bool) {
         return qln::launch_tracking_kalman_jvp(h->p, d[kV], d[kModel], d[kEvent], d[kLgain], d[kH], a.ny, a.Vdiag, d[kCov0], nb,
                                                a.Wdiag_dot, a.Vdiag_dot, d[kLgainD], d[kPest], d[kNisD], h->stream);
     });
@@ -1878,16 +1937,14 @@ int qln_kalman_design_jvp(qln_handle* h, const double* Zout, const double* Lgain
                           double* Lgain_dot, double* Pest_dot, double* logdet_dot) {
     return kalman_design_jvp(h, kDeviceMem,
                              kalman_jvp_call(Zout, Lgain, H, ny, Vdiag, Sigma0_dot, sigma0_batch, Wdiag_dot, Vdiag_dot, Lgain_dot,
-                                             Pest_dot, logdet_dot),
-                             "qln_kalman_design_jvp");
+                                             Pest_dot, logdet_dot), "qln_kalman_design_jvp");
 }
 int qln_kalman_design_jvp_host(qln_handle* h, const double* Zout, const double* Lgain, const double* H, int32_t ny,
                                const double* Vdiag, const double* Sigma0_dot, int32_t sigma0_batch, const double* Wdiag_dot,
                                const double* Vdiag_dot, double* Lgain_dot, double* Pest_dot, double* logdet_dot) {
     return kalman_design_jvp(h, kHostMem,
                              kalman_jvp_call(Zout, Lgain, H, ny, Vdiag, Sigma0_dot, sigma0_batch, Wdiag_dot, Vdiag_dot, Lgain_dot,
-                                             Pest_dot, logdet_dot),
-                             "qln_kalman_design_jvp_host");
+                                             Pest_dot, logdet_dot), "qln_kalman_design_jvp_host");
 }
 int qln_kalman_design_guarded_jvp(qln_handle* h, const double* Zout, const double* model, const double* event, const double* Lgain,
                                   const double* H, int32_t ny, const double* Vdiag, const double* Sigma0_dot, int32_t sigma0_batch,
@@ -1895,7 +1952,7 @@ int qln_kalman_design_guarded_jvp(qln_handle* h, const double* Zout, const doubl
                                   double* logdet_dot) {
     return kalman_design_jvp(h, kDeviceMem,
                              at_events(kalman_jvp_call(Zout, Lgain, H, ny, Vdiag, Sigma0_dot, sigma0_batch, Wdiag_dot, Vdiag_dot,
-                                                     Lgain_dot, Pest_dot, logdet_dot), model, event),
+                                                       Lgain_dot, Pest_dot, logdet_dot), model, event),
                              "qln_kalman_design_guarded_jvp");
 }
 int qln_kalman_design_guarded_jvp_host(qln_handle* h, const double* Zout, const double* model, const double* event,
@@ -1904,7 +1961,7 @@ int qln_kalman_design_guarded_jvp_host(qln_handle* h, const double* Zout, const 
                                        const double* Vdiag_dot, double* Lgain_dot, double* Pest_dot, double* logdet_dot) {
     return kalman_design_jvp(h, kHostMem,
                              at_events(kalman_jvp_call(Zout, Lgain, H, ny, Vdiag, Sigma0_dot, sigma0_batch, Wdiag_dot, Vdiag_dot,
-                                                     Lgain_dot, Pest_dot, logdet_dot), model, event),
+                                                       Lgain_dot, Pest_dot, logdet_dot), model, event),
                              "qln_kalman_design_guarded_jvp_host");
 }
 
@@ -1920,14 +1977,11 @@ struct SmootherCall {
 
 static int check_landing_smoother_args(const qln_handle* h, const SmootherCall& a, const char* who) {
     const std::string w(who);
-    if (a.ny < 1 || a.ny > QLN_TRACK_NY_MAX)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
+    if (int rc = check_tracking_ny(a.ny, w)) return rc;
     if (!a.Xs && !a.Ps) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Xs and Ps are both NULL (nothing to compute)");
-    if (a.guarded && !a.event) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null event (the guarded roll-out's records)");
+    if (int rc = check_guard_event(a.guarded, a.event, w)) return rc;
     if (!a.H || !a.Vdiag) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null H or Vdiag");
-    for (int i = 0; i < a.ny; ++i)
-        if (!(std::isfinite(a.Vdiag[i]) && a.Vdiag[i] > 0.0))
-            return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Vdiag must be finite and > 0 (entry " + std::to_string(i) + ")");
+    if (int rc = check_tracking_vdiag(a.Vdiag, a.ny, w)) return rc;
     if (!a.Lgain || !a.Pest) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Lgain or Pest");
     if (!a.Xhat || !a.innov) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Xhat or innov");
     if (int rc = check_handle(h)) return rc;
@@ -1938,52 +1992,52 @@ static int check_landing_smoother_args(const qln_handle* h, const SmootherCall& 
 static int landing_smoother(qln_handle* h, MemForm mem, const SmootherCall& a, const char* who) {
     if (int rc = check_landing_smoother_args(h, a, who)) return rc;
     // the rows, gains and innovations of the call's ny, of the roles' eight
-    const HostArgs args = {copy_in(kV, a.Ztraj), copy_in(kModel, a.model), copy_in(kEvent, a.event),
-                           copy_in(kLgain, a.Lgain).sized(tracking_gain_total(h->dims, a.ny)), copy_in(kPest, a.Pest),
-                           copy_in(kH, a.H).sized((int64_t)a.ny * QLN_NX), copy_in(kXhat, a.Xhat),
+    const HostArgs args = {copy_in(kV, a.Ztraj), copy_in(kH, a.H).sized((int64_t)a.ny * QLN_NX), copy_in(kModel, a.model),
+                           copy_in(kEvent, a.event), copy_in(kLgain, a.Lgain).sized(tracking_gain_total(h->dims, a.ny)),
+                           copy_in(kPest, a.Pest), copy_in(kXhat, a.Xhat),
                            copy_in(kInnov, a.innov).sized(tracking_meas_total(h->dims, a.ny)), copy_out(kXs, a.Xs),
                            copy_out(kPs, a.Ps)};
-    if (int rc = check_no_overlap(h, args, who)) return rc;
-    if (mem == kHostMem) {
-        if (int rc = check_host_meas(a.H, a.ny, who)) return rc;
-        if (int rc = check_host_models(h, a.model, who)) return rc;
-        if (int rc = check_host_events(h, a.event, who)) return rc;
-    }
-    return run_call(h, mem, args, [&](double* const* d, bool) {
+    return run_tracking_call(h, mem, args, who, [&](double* const* d, bool) {
         return qln::launch_landing_smoother(h->p, d[kV], d[kModel], d[kEvent], d[kLgain], d[kPest], d[kH], a.ny, a.Vdiag,
                                             d[kXhat], d[kInnov], d[kXs], d[kPs], h->stream);
     });
 }
 
-int qln_landing_smoother(qln_handle* h, const double* Ztraj, const double* Lgain, const double* Pest, const double* H, int32_t ny,
-                         const double* Vdiag, const double* Xhat, const double* innov, double* Xs, double* Ps) {
+static SmootherCall smoother_call(const double* Ztraj, const double* Lgain, const double* Pest, const double* H, int32_t ny,
+                                  const double* Vdiag, const double* Xhat, const double* innov, double* Xs, double* Ps) {
     SmootherCall a{};
     a.Ztraj = Ztraj; a.Lgain = Lgain; a.Pest = Pest; a.H = H; a.ny = ny; a.Vdiag = Vdiag; a.Xhat = Xhat; a.innov = innov;
     a.Xs = Xs; a.Ps = Ps;
-    return landing_smoother(h, kDeviceMem, a, "qln_landing_smoother");
+    return a;
+}
+static SmootherCall at_events(SmootherCall a, const double* model, const double* event) {
+    a.guarded = true; a.model = model; a.event = event;
+    return a;
+}
+
+int qln_landing_smoother(qln_handle* h, const double* Ztraj, const double* Lgain, const double* Pest, const double* H, int32_t ny,
+                         const double* Vdiag, const double* Xhat, const double* innov, double* Xs, double* Ps) {
+    return landing_smoother(h, kDeviceMem, smoother_call(Ztraj, Lgain, Pest, H, ny, Vdiag, Xhat, innov, Xs, Ps),
+                            "qln_landing_smoother");
 }
 int qln_landing_smoother_host(qln_handle* h, const double* Ztraj, const double* Lgain, const double* Pest, const double* H,
                               int32_t ny, const double* Vdiag, const double* Xhat, const double* innov, double* Xs, double* Ps) {
-    SmootherCall a{};
-    a.Ztraj = Ztraj; a.Lgain = Lgain; a.Pest = Pest; a.H = H; a.ny = ny; a.Vdiag = Vdiag; a.Xhat = Xhat; a.innov = innov;
-    a.Xs = Xs; a.Ps = Ps;
-    return landing_smoother(h, kHostMem, a, "qln_landing_smoother_host");
+    return landing_smoother(h, kHostMem, smoother_call(Ztraj, Lgain, Pest, H, ny, Vdiag, Xhat, innov, Xs, Ps),
+                            "qln_landing_smoother_host");
 }
 int qln_landing_smoother_guarded(qln_handle* h, const double* Ztraj, const double* model, const double* event, const double* Lgain,
                                  const double* Pest, const double* H, int32_t ny, const double* Vdiag, const double* Xhat,
                                  const double* innov, double* Xs, double* Ps) {
-    SmootherCall a{};
-    a.Ztraj = Ztraj; a.model = model; a.guarded = true; a.event = event; a.Lgain = Lgain; a.Pest = Pest; a.H = H; a.ny = ny;
-    a.Vdiag = Vdiag; a.Xhat = Xhat; a.innov = innov; a.Xs = Xs; a.Ps = Ps;
-    return landing_smoother(h, kDeviceMem, a, "qln_landing_smoother_guarded");
+    return landing_smoother(h, kDeviceMem,
+                            at_events(smoother_call(Ztraj, Lgain, Pest, H, ny, Vdiag, Xhat, innov, Xs, Ps), model, event),
+                            "qln_landing_smoother_guarded");
 }
 int qln_landing_smoother_guarded_host(qln_handle* h, const double* Ztraj, const double* model, const double* event,
                                       const double* Lgain, const double* Pest, const double* H, int32_t ny, const double* Vdiag,
                                       const double* Xhat, const double* innov, double* Xs, double* Ps) {
-    SmootherCall a{};
-    a.Ztraj = Ztraj; a.model = model; a.guarded = true; a.event = event; a.Lgain = Lgain; a.Pest = Pest; a.H = H; a.ny = ny;
-    a.Vdiag = Vdiag; a.Xhat = Xhat; a.innov = innov; a.Xs = Xs; a.Ps = Ps;
-    return landing_smoother(h, kHostMem, a, "qln_landing_smoother_guarded_host");
+    return landing_smoother(h, kHostMem,
+                            at_events(smoother_call(Ztraj, Lgain, Pest, H, ny, Vdiag, Xhat, innov, Xs, Ps), model, event),
+                            "qln_landing_smoother_guarded_host");
 }
 
 // The filter on recorded data (k_landing_filter).  The checks that need no handle come first.
@@ -1999,15 +2053,11 @@ struct FilterCall {
 
 static int check_landing_filter_args(const qln_handle* h, const FilterCall& a, const char* who) {
     const std::string w(who);
-    if (a.ny < 1 || a.ny > QLN_TRACK_NY_MAX)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
-    if (!a.Xhat && !a.innov && !a.score && !a.loglik && !a.event_hat)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every output is NULL (nothing to compute)");
+    if (int rc = check_tracking_ny(a.ny, w)) return rc;
+    if (int rc = check_some_output(a.Xhat || a.innov || a.score || a.loglik || a.event_hat, w)) return rc;
     if (a.score || a.loglik) {
         if (!a.Vdiag) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Vdiag with score or loglik");
-        for (int i = 0; i < a.ny; ++i)
-            if (!(std::isfinite(a.Vdiag[i]) && a.Vdiag[i] > 0.0))
-                return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Vdiag must be finite and > 0 (entry " + std::to_string(i) + ")");
+        if (int rc = check_tracking_vdiag(a.Vdiag, a.ny, w)) return rc;
     }
     if (!a.H || !a.Lgain || !a.Y) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null H, Lgain or Y");
     if (int rc = check_handle(h)) return rc;
@@ -2024,12 +2074,7 @@ static int landing_filter(qln_handle* h, MemForm mem, const FilterCall& a, const
                            copy_in(kH, a.H).sized((int64_t)a.ny * QLN_NX), copy_in(kModel, a.model), copy_in(kY, a.Y).sized(nm),
                            copy_in(kXhat0, a.xhat0), copy_out(kXhat, a.Xhat), copy_out(kInnov, a.innov).sized(nm),
                            copy_out(kScore, a.score), copy_out(kLoglik, a.loglik), copy_out(kEventHat, a.event_hat)};
-    if (int rc = check_no_overlap(h, args, who)) return rc;
-    if (mem == kHostMem) {
-        if (int rc = check_host_meas(a.H, a.ny, who)) return rc;
-        if (int rc = check_host_models(h, a.model, who)) return rc;
-    }
-    return run_call(h, mem, args, [&](double* const* d, bool) {
+    return run_tracking_call(h, mem, args, who, [&](double* const* d, bool) {
         return qln::launch_landing_filter(h->p, d[kZ], d[kZrec], d[kLgain], d[kH], a.ny, a.Vdiag, d[kY], d[kXhat0], d[kModel],
                                           d[kXhat], d[kInnov], d[kScore], d[kLoglik], a.guarded, d[kEventHat], h->stream);
     });
@@ -2047,25 +2092,29 @@ static FilterCall filter_call(const double* Zref, const double* Zrec, const doub
 int qln_landing_filter(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H, int32_t ny,
                        const double* Vdiag, const double* Y, const double* xhat0, double* Xhat, double* innov, double* score,
                        double* loglik) {
-    return landing_filter(h, kDeviceMem, filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, false, nullptr),
+    return landing_filter(h, kDeviceMem,
+                          filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, false, nullptr),
                           "qln_landing_filter");
 }
 int qln_landing_filter_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H, int32_t ny,
                             const double* Vdiag, const double* Y, const double* xhat0, double* Xhat, double* innov, double* score,
                             double* loglik) {
-    return landing_filter(h, kHostMem, filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, false, nullptr),
+    return landing_filter(h, kHostMem,
+                          filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, false, nullptr),
                           "qln_landing_filter_host");
 }
 int qln_landing_filter_guarded(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
                                int32_t ny, const double* Vdiag, const double* Y, const double* xhat0, double* Xhat, double* innov,
                                double* score, double* loglik, double* event_hat) {
-    return landing_filter(h, kDeviceMem, filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, true, event_hat),
+    return landing_filter(h, kDeviceMem,
+                          filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, true, event_hat),
                           "qln_landing_filter_guarded");
 }
 int qln_landing_filter_guarded_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
                                     int32_t ny, const double* Vdiag, const double* Y, const double* xhat0, double* Xhat,
                                     double* innov, double* score, double* loglik, double* event_hat) {
-    return landing_filter(h, kHostMem, filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, true, event_hat),
+    return landing_filter(h, kHostMem,
+                          filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, true, event_hat),
                           "qln_landing_filter_guarded_host");
 }
 // the filter at a model of each record's own: the same path with model [B][QLN_MODEL_NP] (null: the handle's)
@@ -2077,30 +2126,30 @@ int qln_landing_filter_model(qln_handle* h, const double* Zref, const double* Zr
                              const double* model, const double* Vdiag, const double* Y, const double* xhat0, double* Xhat,
                              double* innov, double* score, double* loglik) {
     return landing_filter(h, kDeviceMem,
-                          with_model(filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, false, nullptr), model),
-                          "qln_landing_filter_model");
+                          with_model(filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, false,
+                                                 nullptr), model), "qln_landing_filter_model");
 }
 int qln_landing_filter_model_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
                                   int32_t ny, const double* model, const double* Vdiag, const double* Y, const double* xhat0,
                                   double* Xhat, double* innov, double* score, double* loglik) {
     return landing_filter(h, kHostMem,
-                          with_model(filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, false, nullptr), model),
-                          "qln_landing_filter_model_host");
+                          with_model(filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, false,
+                                                 nullptr), model), "qln_landing_filter_model_host");
 }
 int qln_landing_filter_guarded_model(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
                                      int32_t ny, const double* model, const double* Vdiag, const double* Y, const double* xhat0,
                                      double* Xhat, double* innov, double* score, double* loglik, double* event_hat) {
     return landing_filter(h, kDeviceMem,
-                          with_model(filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, true, event_hat), model),
-                          "qln_landing_filter_guarded_model");
+                          with_model(filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, true,
+                                                 event_hat), model), "qln_landing_filter_guarded_model");
 }
 int qln_landing_filter_guarded_model_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain,
                                           const double* H, int32_t ny, const double* model, const double* Vdiag, const double* Y,
                                           const double* xhat0, double* Xhat, double* innov, double* score, double* loglik,
                                           double* event_hat) {
     return landing_filter(h, kHostMem,
-                          with_model(filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, true, event_hat), model),
-                          "qln_landing_filter_guarded_model_host");
+                          with_model(filter_call(Zref, Zrec, Lgain, H, ny, Vdiag, Y, xhat0, Xhat, innov, score, loglik, true,
+                                                 event_hat), model), "qln_landing_filter_guarded_model_host");
 }
 
 // The sweeps through the filter (k_landing_filter_jvp / _vjp).  What both share: the record and the trajectory the filter
@@ -2123,9 +2172,7 @@ static int check_filter_sweep_args(const qln_handle* h, const FilterTraj& t, boo
                                  : ": Lgain_bar with nis_bar or loglik_bar (the score is differentiated at fixed gains)"));
     if (want_score) {
         if (!t.Vdiag) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Vdiag with a score term");
-        for (int i = 0; i < t.ny; ++i)
-            if (!(std::isfinite(t.Vdiag[i]) && t.Vdiag[i] > 0.0))
-                return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Vdiag must be finite and > 0 (entry " + std::to_string(i) + ")");
+        if (int rc = check_tracking_vdiag(t.Vdiag, t.ny, w)) return rc;
     }
     if ((want_gain || want_score) && !t.innov)
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null innov (Lgain's tangent or cotangent and the score terms need the innovations)");
@@ -2134,12 +2181,6 @@ static int check_filter_sweep_args(const qln_handle* h, const FilterTraj& t, boo
     if (int rc = check_handle(h)) return rc;
     if (!t.Zref || !t.Zrec || !t.Xhat) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref, Zrec or Xhat");
     return QLN_OK;
-}
-
-static int check_host_filter_traj(const qln_handle* h, const FilterTraj& t, const char* who) {
-    if (int rc = check_host_meas(t.H, t.ny, who)) return rc;
-    if (int rc = check_host_models(h, t.model, who)) return rc;
-    return check_host_events(h, t.event_hat, who);
 }
 
 static qln::FilterSweepIn filter_sweep_in(double* const* d, const FilterTraj& t, bool want_score) {
@@ -2152,12 +2193,10 @@ static qln::FilterSweepIn filter_sweep_in(double* const* d, const FilterTraj& t,
 // innov is staged, and ruled, only where it is read.
 static int landing_filter_jvp(qln_handle* h, MemForm mem, const FilterTraj& t, const qln::FilterJvpArgs& a, const char* who) {
     const std::string w(who);
-    if (t.ny < 1 || t.ny > QLN_TRACK_NY_MAX)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
+    if (int rc = check_tracking_ny(t.ny, w)) return rc;
     if (!a.Y_dot && !a.Zrec_dot && !a.Lgain_dot && !a.xhat0_dot && !a.model_dot)
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every tangent is NULL (no direction)");
-    if (!a.Xhat_dot && !a.innov_dot && !a.nis_dot && !a.loglik_dot && !a.event_hat_dot)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every output is NULL (nothing to compute)");
+    if (int rc = check_some_output(a.Xhat_dot || a.innov_dot || a.nis_dot || a.loglik_dot || a.event_hat_dot, w)) return rc;
     const bool want_gain = a.Lgain_dot != nullptr, want_score = a.nis_dot || a.loglik_dot;
     if (int rc = check_filter_sweep_args(h, t, want_gain, want_score, true, w)) return rc;
     const int64_t ng = tracking_gain_total(h->dims, t.ny), nm = tracking_meas_total(h->dims, t.ny);
@@ -2169,10 +2208,7 @@ static int landing_filter_jvp(qln_handle* h, MemForm mem, const FilterTraj& t, c
                            copy_in(kLgainD, a.Lgain_dot).sized(ng), copy_in(kXhat0, a.xhat0_dot), copy_in(kModelD, a.model_dot),
                            copy_out(kXhatD, a.Xhat_dot), copy_out(kInnovD, a.innov_dot).sized(nm), copy_out(kNisD, a.nis_dot),
                            copy_out(kLoglik, a.loglik_dot), copy_out(kEventHatD, a.event_hat_dot)};
-    if (int rc = check_no_overlap(h, args, who)) return rc;
-    if (mem == kHostMem)
-        if (int rc = check_host_filter_traj(h, t, who)) return rc;
-    return run_call(h, mem, args, [&](double* const* d, bool) {
+    return run_tracking_call(h, mem, args, who, [&](double* const* d, bool) {
         const qln::FilterJvpArgs da = {d[kY], d[kZdot], d[kLgainD], d[kXhat0], d[kModelD], d[kXhatD], d[kInnovD], d[kNisD],
                                        d[kLoglik], d[kEventHatD]};
         return qln::launch_landing_filter_jvp(h->p, filter_sweep_in(d, t, want_score), da, h->stream);
@@ -2182,12 +2218,10 @@ static int landing_filter_jvp(qln_handle* h, MemForm mem, const FilterTraj& t, c
 // Zrec_bar is in-out: the kernel never writes behind n_nlp, and that padding is the caller's.
 static int landing_filter_vjp(qln_handle* h, MemForm mem, const FilterTraj& t, const qln::FilterVjpArgs& a, const char* who) {
     const std::string w(who);
-    if (t.ny < 1 || t.ny > QLN_TRACK_NY_MAX)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
+    if (int rc = check_tracking_ny(t.ny, w)) return rc;
     if (!a.Xhat_bar && !a.innov_bar && !a.nis_bar && !a.loglik_bar)
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every cotangent is NULL (nothing to pull back)");
-    if (!a.Y_bar && !a.Zrec_bar && !a.Lgain_bar && !a.xhat0_bar && !a.model_bar)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": every output is NULL (nothing to compute)");
+    if (int rc = check_some_output(a.Y_bar || a.Zrec_bar || a.Lgain_bar || a.xhat0_bar || a.model_bar, w)) return rc;
     const bool want_gain = a.Lgain_bar != nullptr, want_score = a.nis_bar || a.loglik_bar;
     if (int rc = check_filter_sweep_args(h, t, want_gain, want_score, false, w)) return rc;
     const int64_t ng = tracking_gain_total(h->dims, t.ny), nm = tracking_meas_total(h->dims, t.ny);
@@ -2199,10 +2233,7 @@ static int landing_filter_vjp(qln_handle* h, MemForm mem, const FilterTraj& t, c
                            copy_in(kNisD, a.nis_bar), copy_in(kLoglik, a.loglik_bar), copy_out(kY, a.Y_bar).sized(nm),
                            copy_inout(kZio, a.Zrec_bar), copy_out(kLgainD, a.Lgain_bar).sized(ng), copy_out(kXhat0, a.xhat0_bar),
                            copy_out(kModelD, a.model_bar)};
-    if (int rc = check_no_overlap(h, args, who)) return rc;
-    if (mem == kHostMem)
-        if (int rc = check_host_filter_traj(h, t, who)) return rc;
-    return run_call(h, mem, args, [&](double* const* d, bool) {
+    return run_tracking_call(h, mem, args, who, [&](double* const* d, bool) {
         const qln::FilterVjpArgs da = {d[kXhatD], d[kInnovD], d[kNisD], d[kLoglik], d[kY], d[kZio], d[kLgainD], d[kXhat0],
                                        d[kModelD]};
         return qln::launch_landing_filter_vjp(h->p, filter_sweep_in(d, t, want_score), da, h->stream);
@@ -2217,40 +2248,22 @@ static FilterTraj filter_traj(const double* Zref, const double* Zrec, const doub
     t.innov = innov; t.guarded = guarded; t.event_hat = event_hat;
     return t;
 }
-static qln::FilterJvpArgs filter_jvp_args(const double* Y_dot, const double* Zrec_dot, const double* Lgain_dot,
-                                          const double* xhat0_dot, const double* model_dot, double* Xhat_dot, double* innov_dot,
-                                          double* nis_dot, double* loglik_dot, double* event_hat_dot) {
-    qln::FilterJvpArgs a{};
-    a.Y_dot = Y_dot; a.Zrec_dot = Zrec_dot; a.Lgain_dot = Lgain_dot; a.xhat0_dot = xhat0_dot; a.model_dot = model_dot;
-    a.Xhat_dot = Xhat_dot; a.innov_dot = innov_dot; a.nis_dot = nis_dot; a.loglik_dot = loglik_dot; a.event_hat_dot = event_hat_dot;
-    return a;
-}
-static qln::FilterVjpArgs filter_vjp_args(const double* Xhat_bar, const double* innov_bar, const double* nis_bar,
-                                          const double* loglik_bar, double* Y_bar, double* Zrec_bar, double* Lgain_bar,
-                                          double* xhat0_bar, double* model_bar) {
-    qln::FilterVjpArgs a{};
-    a.Xhat_bar = Xhat_bar; a.innov_bar = innov_bar; a.nis_bar = nis_bar; a.loglik_bar = loglik_bar; a.Y_bar = Y_bar;
-    a.Zrec_bar = Zrec_bar; a.Lgain_bar = Lgain_bar; a.xhat0_bar = xhat0_bar; a.model_bar = model_bar;
-    return a;
-}
 
 int qln_landing_filter_jvp(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H, int32_t ny,
                            const double* model, const double* Vdiag, const double* Xhat, const double* innov, const double* Y_dot,
                            const double* Zrec_dot, const double* Lgain_dot, const double* xhat0_dot, const double* model_dot,
                            double* Xhat_dot, double* innov_dot, double* nis_dot, double* loglik_dot) {
     return landing_filter_jvp(h, kDeviceMem, filter_traj(Zref, Zrec, Lgain, H, ny, model, Vdiag, Xhat, innov, false, nullptr),
-                              filter_jvp_args(Y_dot, Zrec_dot, Lgain_dot, xhat0_dot, model_dot, Xhat_dot, innov_dot, nis_dot,
-                                              loglik_dot, nullptr),
-                              "qln_landing_filter_jvp");
+                              qln::FilterJvpArgs{Y_dot, Zrec_dot, Lgain_dot, xhat0_dot, model_dot, Xhat_dot, innov_dot, nis_dot,
+                                                 loglik_dot, nullptr}, "qln_landing_filter_jvp");
 }
 int qln_landing_filter_jvp_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
                                 int32_t ny, const double* model, const double* Vdiag, const double* Xhat, const double* innov,
                                 const double* Y_dot, const double* Zrec_dot, const double* Lgain_dot, const double* xhat0_dot,
                                 const double* model_dot, double* Xhat_dot, double* innov_dot, double* nis_dot, double* loglik_dot) {
     return landing_filter_jvp(h, kHostMem, filter_traj(Zref, Zrec, Lgain, H, ny, model, Vdiag, Xhat, innov, false, nullptr),
-                              filter_jvp_args(Y_dot, Zrec_dot, Lgain_dot, xhat0_dot, model_dot, Xhat_dot, innov_dot, nis_dot,
-                                              loglik_dot, nullptr),
-                              "qln_landing_filter_jvp_host");
+                              qln::FilterJvpArgs{Y_dot, Zrec_dot, Lgain_dot, xhat0_dot, model_dot, Xhat_dot, innov_dot, nis_dot,
+                                                 loglik_dot, nullptr}, "qln_landing_filter_jvp_host");
 }
 int qln_landing_filter_guarded_jvp(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
                                    int32_t ny, const double* model, const double* Vdiag, const double* Xhat, const double* innov,
@@ -2258,9 +2271,8 @@ int qln_landing_filter_guarded_jvp(qln_handle* h, const double* Zref, const doub
                                    const double* xhat0_dot, const double* model_dot, double* Xhat_dot, double* innov_dot,
                                    double* nis_dot, double* loglik_dot, double* event_hat_dot) {
     return landing_filter_jvp(h, kDeviceMem, filter_traj(Zref, Zrec, Lgain, H, ny, model, Vdiag, Xhat, innov, true, event_hat),
-                              filter_jvp_args(Y_dot, Zrec_dot, Lgain_dot, xhat0_dot, model_dot, Xhat_dot, innov_dot, nis_dot,
-                                              loglik_dot, event_hat_dot),
-                              "qln_landing_filter_guarded_jvp");
+                              qln::FilterJvpArgs{Y_dot, Zrec_dot, Lgain_dot, xhat0_dot, model_dot, Xhat_dot, innov_dot, nis_dot,
+                                                 loglik_dot, event_hat_dot}, "qln_landing_filter_guarded_jvp");
 }
 int qln_landing_filter_guarded_jvp_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
                                         int32_t ny, const double* model, const double* Vdiag, const double* Xhat,
@@ -2269,27 +2281,24 @@ int qln_landing_filter_guarded_jvp_host(qln_handle* h, const double* Zref, const
                                         double* Xhat_dot, double* innov_dot, double* nis_dot, double* loglik_dot,
                                         double* event_hat_dot) {
     return landing_filter_jvp(h, kHostMem, filter_traj(Zref, Zrec, Lgain, H, ny, model, Vdiag, Xhat, innov, true, event_hat),
-                              filter_jvp_args(Y_dot, Zrec_dot, Lgain_dot, xhat0_dot, model_dot, Xhat_dot, innov_dot, nis_dot,
-                                              loglik_dot, event_hat_dot),
-                              "qln_landing_filter_guarded_jvp_host");
+                              qln::FilterJvpArgs{Y_dot, Zrec_dot, Lgain_dot, xhat0_dot, model_dot, Xhat_dot, innov_dot, nis_dot,
+                                                 loglik_dot, event_hat_dot}, "qln_landing_filter_guarded_jvp_host");
 }
 int qln_landing_filter_vjp(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H, int32_t ny,
                            const double* model, const double* Vdiag, const double* Xhat, const double* innov,
                            const double* Xhat_bar, const double* innov_bar, const double* nis_bar, const double* loglik_bar,
                            double* Y_bar, double* Zrec_bar, double* Lgain_bar, double* xhat0_bar, double* model_bar) {
     return landing_filter_vjp(h, kDeviceMem, filter_traj(Zref, Zrec, Lgain, H, ny, model, Vdiag, Xhat, innov, false, nullptr),
-                              filter_vjp_args(Xhat_bar, innov_bar, nis_bar, loglik_bar, Y_bar, Zrec_bar, Lgain_bar, xhat0_bar,
-                                              model_bar),
-                              "qln_landing_filter_vjp");
+                              qln::FilterVjpArgs{Xhat_bar, innov_bar, nis_bar, loglik_bar, Y_bar, Zrec_bar, Lgain_bar, xhat0_bar,
+                                                 model_bar}, "qln_landing_filter_vjp");
 }
 int qln_landing_filter_vjp_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
                                 int32_t ny, const double* model, const double* Vdiag, const double* Xhat, const double* innov,
                                 const double* Xhat_bar, const double* innov_bar, const double* nis_bar, const double* loglik_bar,
                                 double* Y_bar, double* Zrec_bar, double* Lgain_bar, double* xhat0_bar, double* model_bar) {
     return landing_filter_vjp(h, kHostMem, filter_traj(Zref, Zrec, Lgain, H, ny, model, Vdiag, Xhat, innov, false, nullptr),
-                              filter_vjp_args(Xhat_bar, innov_bar, nis_bar, loglik_bar, Y_bar, Zrec_bar, Lgain_bar, xhat0_bar,
-                                              model_bar),
-                              "qln_landing_filter_vjp_host");
+                              qln::FilterVjpArgs{Xhat_bar, innov_bar, nis_bar, loglik_bar, Y_bar, Zrec_bar, Lgain_bar, xhat0_bar,
+                                                 model_bar}, "qln_landing_filter_vjp_host");
 }
 int qln_landing_filter_guarded_vjp(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
                                    int32_t ny, const double* model, const double* Vdiag, const double* Xhat, const double* innov,
@@ -2297,9 +2306,8 @@ int qln_landing_filter_guarded_vjp(qln_handle* h, const double* Zref, const doub
                                    const double* loglik_bar, double* Y_bar, double* Zrec_bar, double* Lgain_bar, double* xhat0_bar,
                                    double* model_bar) {
     return landing_filter_vjp(h, kDeviceMem, filter_traj(Zref, Zrec, Lgain, H, ny, model, Vdiag, Xhat, innov, true, event_hat),
-                              filter_vjp_args(Xhat_bar, innov_bar, nis_bar, loglik_bar, Y_bar, Zrec_bar, Lgain_bar, xhat0_bar,
-                                              model_bar),
-                              "qln_landing_filter_guarded_vjp");
+                              qln::FilterVjpArgs{Xhat_bar, innov_bar, nis_bar, loglik_bar, Y_bar, Zrec_bar, Lgain_bar, xhat0_bar,
+                                                 model_bar}, "qln_landing_filter_guarded_vjp");
 }
 int qln_landing_filter_guarded_vjp_host(qln_handle* h, const double* Zref, const double* Zrec, const double* Lgain, const double* H,
                                         int32_t ny, const double* model, const double* Vdiag, const double* Xhat,
@@ -2307,9 +2315,8 @@ int qln_landing_filter_guarded_vjp_host(qln_handle* h, const double* Zref, const
                                         const double* innov_bar, const double* nis_bar, const double* loglik_bar, double* Y_bar,
                                         double* Zrec_bar, double* Lgain_bar, double* xhat0_bar, double* model_bar) {
     return landing_filter_vjp(h, kHostMem, filter_traj(Zref, Zrec, Lgain, H, ny, model, Vdiag, Xhat, innov, true, event_hat),
-                              filter_vjp_args(Xhat_bar, innov_bar, nis_bar, loglik_bar, Y_bar, Zrec_bar, Lgain_bar, xhat0_bar,
-                                              model_bar),
-                              "qln_landing_filter_guarded_vjp_host");
+                              qln::FilterVjpArgs{Xhat_bar, innov_bar, nis_bar, loglik_bar, Y_bar, Zrec_bar, Lgain_bar, xhat0_bar,
+                                                 model_bar}, "qln_landing_filter_guarded_vjp_host");
 }
 
 // The estimate-feedback roll-out (k_tracking_rollout_estimated).  The checks that need no handle come first.
@@ -2330,8 +2337,7 @@ static int check_tracking_estimated_args(const qln_handle* h, const EstimatedCal
         if (!a.guarded && (a.event || a.event_hat))
             return fail(QLN_ERR_INVALID_ARGUMENT, w + ": event or event_hat with guarded == 0 (the knot schedule has no record)");
     }
-    if (a.ny < 1 || a.ny > QLN_TRACK_NY_MAX)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
+    if (int rc = check_tracking_ny(a.ny, w)) return rc;
     if (!a.Lgain || !a.H) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Lgain or H");
     if (int rc = check_handle(h)) return rc;
     if (!a.Zref || !a.Zout) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zref or Zout");
@@ -2347,53 +2353,62 @@ static int tracking_rollout_estimated(qln_handle* h, MemForm mem, const Estimate
                            copy_in(kWnoise, a.wnoise), copy_in(kX0, a.x0), copy_in(kXhat0, a.xhat0), copy_in(kModel, a.model),
                            copy_out(kXhat, a.Xhat), copy_out(kInnov, a.innov).sized(nm), copy_out(kEvent, a.event),
                            copy_out(kEventHat, a.event_hat), copy_out(kSat, a.sat)};
-    if (int rc = check_no_overlap(h, args, who)) return rc;
-    if (mem == kHostMem) {
-        if (int rc = check_host_meas(a.H, a.ny, who)) return rc;
-        if (int rc = check_host_models(h, a.model, who)) return rc;
-    }
-    return run_call(h, mem, args, [&](double* const* d, bool) {
+    return run_tracking_call(h, mem, args, who, [&](double* const* d, bool) {
         return qln::launch_tracking_rollout_estimated(h->p, d[kZ], d[kK], d[kLgain], d[kH], a.ny, d[kVnoise], d[kWnoise], d[kX0],
                                                       d[kXhat0], d[kModel], d[kZio], d[kXhat], d[kInnov], a.guarded, d[kEvent],
                                                       d[kEventHat], a.limited ? a.lim : nullptr, d[kSat], h->stream);
     });
 }
 
-int qln_tracking_rollout_estimated(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
-                                   int32_t ny, const double* vnoise, const double* wnoise, const double* x0, const double* xhat0,
-                                   const double* model, double* Zout, double* Xhat, double* innov) {
+static EstimatedCall estimated_call(const double* Zref, const double* K, const double* Lgain, const double* H, int32_t ny,
+                                    const double* vnoise, const double* wnoise, const double* x0, const double* xhat0,
+                                    const double* model, double* Zout, double* Xhat, double* innov) {
     EstimatedCall a{};
     a.Zref = Zref; a.K = K; a.Lgain = Lgain; a.H = H; a.ny = ny; a.vnoise = vnoise; a.wnoise = wnoise;
     a.x0 = x0; a.xhat0 = xhat0; a.model = model; a.Zout = Zout; a.Xhat = Xhat; a.innov = innov;
-    return tracking_rollout_estimated(h, kDeviceMem, a, "qln_tracking_rollout_estimated");
+    return a;
+}
+static EstimatedCall with_touchdown(EstimatedCall a, double* event, double* event_hat) {
+    a.guarded = true; a.event = event; a.event_hat = event_hat;
+    return a;
+}
+static EstimatedCall within_limits(EstimatedCall a, const double* lim, int32_t guarded, double* event, double* event_hat,
+                                   double* sat) {
+    a.limited = true; a.lim = lim; a.sat = sat; a.guarded = guarded != 0; a.event = event; a.event_hat = event_hat;
+    return a;
+}
+
+int qln_tracking_rollout_estimated(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
+                                   int32_t ny, const double* vnoise, const double* wnoise, const double* x0, const double* xhat0,
+                                   const double* model, double* Zout, double* Xhat, double* innov) {
+    return tracking_rollout_estimated(h, kDeviceMem,
+                                      estimated_call(Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov),
+                                      "qln_tracking_rollout_estimated");
 }
 int qln_tracking_rollout_estimated_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
                                         int32_t ny, const double* vnoise, const double* wnoise, const double* x0,
                                         const double* xhat0, const double* model, double* Zout, double* Xhat, double* innov) {
-    EstimatedCall a{};
-    a.Zref = Zref; a.K = K; a.Lgain = Lgain; a.H = H; a.ny = ny; a.vnoise = vnoise; a.wnoise = wnoise;
-    a.x0 = x0; a.xhat0 = xhat0; a.model = model; a.Zout = Zout; a.Xhat = Xhat; a.innov = innov;
-    return tracking_rollout_estimated(h, kHostMem, a, "qln_tracking_rollout_estimated_host");
+    return tracking_rollout_estimated(h, kHostMem,
+                                      estimated_call(Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout, Xhat, innov),
+                                      "qln_tracking_rollout_estimated_host");
 }
 int qln_tracking_rollout_estimated_guarded(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
                                            int32_t ny, const double* vnoise, const double* wnoise, const double* x0,
                                            const double* xhat0, const double* model, double* Zout, double* Xhat, double* innov,
                                            double* event, double* event_hat) {
-    EstimatedCall a{};
-    a.Zref = Zref; a.K = K; a.Lgain = Lgain; a.H = H; a.ny = ny; a.vnoise = vnoise;
-    a.wnoise = wnoise; a.x0 = x0; a.xhat0 = xhat0; a.model = model; a.Zout = Zout;
-    a.Xhat = Xhat; a.innov = innov; a.guarded = true; a.event = event; a.event_hat = event_hat;
-    return tracking_rollout_estimated(h, kDeviceMem, a, "qln_tracking_rollout_estimated_guarded");
+    return tracking_rollout_estimated(h, kDeviceMem,
+                                      with_touchdown(estimated_call(Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout,
+                                                                    Xhat, innov), event, event_hat),
+                                      "qln_tracking_rollout_estimated_guarded");
 }
 int qln_tracking_rollout_estimated_guarded_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                                 const double* H, int32_t ny, const double* vnoise, const double* wnoise,
                                                 const double* x0, const double* xhat0, const double* model, double* Zout,
                                                 double* Xhat, double* innov, double* event, double* event_hat) {
-    EstimatedCall a{};
-    a.Zref = Zref; a.K = K; a.Lgain = Lgain; a.H = H; a.ny = ny; a.vnoise = vnoise;
-    a.wnoise = wnoise; a.x0 = x0; a.xhat0 = xhat0; a.model = model; a.Zout = Zout;
-    a.Xhat = Xhat; a.innov = innov; a.guarded = true; a.event = event; a.event_hat = event_hat;
-    return tracking_rollout_estimated(h, kHostMem, a, "qln_tracking_rollout_estimated_guarded_host");
+    return tracking_rollout_estimated(h, kHostMem,
+                                      with_touchdown(estimated_call(Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout,
+                                                                    Xhat, innov), event, event_hat),
+                                      "qln_tracking_rollout_estimated_guarded_host");
 }
 // the loop within contact-aware force limits: the knot-scheduled or the guarded one, with its saturation record
 int qln_tracking_rollout_estimated_limited(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
@@ -2401,22 +2416,20 @@ int qln_tracking_rollout_estimated_limited(qln_handle* h, const double* Zref, co
                                            const double* xhat0, const double* model, const double* lim, int32_t guarded,
                                            double* Zout, double* Xhat, double* innov, double* event, double* event_hat,
                                            double* sat) {
-    EstimatedCall a{};
-    a.Zref = Zref; a.K = K; a.Lgain = Lgain; a.H = H; a.ny = ny; a.vnoise = vnoise; a.wnoise = wnoise;
-    a.x0 = x0; a.xhat0 = xhat0; a.model = model; a.Zout = Zout; a.Xhat = Xhat; a.innov = innov;
-    a.guarded = guarded != 0; a.event = event; a.event_hat = event_hat; a.limited = true; a.lim = lim; a.sat = sat;
-    return tracking_rollout_estimated(h, kDeviceMem, a, "qln_tracking_rollout_estimated_limited");
+    return tracking_rollout_estimated(h, kDeviceMem,
+                                      within_limits(estimated_call(Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout,
+                                                                   Xhat, innov), lim, guarded, event, event_hat, sat),
+                                      "qln_tracking_rollout_estimated_limited");
 }
 int qln_tracking_rollout_estimated_limited_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                                 const double* H, int32_t ny, const double* vnoise, const double* wnoise,
                                                 const double* x0, const double* xhat0, const double* model, const double* lim,
                                                 int32_t guarded, double* Zout, double* Xhat, double* innov, double* event,
                                                 double* event_hat, double* sat) {
-    EstimatedCall a{};
-    a.Zref = Zref; a.K = K; a.Lgain = Lgain; a.H = H; a.ny = ny; a.vnoise = vnoise; a.wnoise = wnoise;
-    a.x0 = x0; a.xhat0 = xhat0; a.model = model; a.Zout = Zout; a.Xhat = Xhat; a.innov = innov;
-    a.guarded = guarded != 0; a.event = event; a.event_hat = event_hat; a.limited = true; a.lim = lim; a.sat = sat;
-    return tracking_rollout_estimated(h, kHostMem, a, "qln_tracking_rollout_estimated_limited_host");
+    return tracking_rollout_estimated(h, kHostMem,
+                                      within_limits(estimated_call(Zref, K, Lgain, H, ny, vnoise, wnoise, x0, xhat0, model, Zout,
+                                                                   Xhat, innov), lim, guarded, event, event_hat, sat),
+                                      "qln_tracking_rollout_estimated_limited_host");
 }
 
 // The sweeps through the estimate-feedback roll-out (k_tracking_rollout_estimated_jvp / _vjp).  What both sweeps share: the
@@ -2434,10 +2447,9 @@ struct EstimatedTraj {
 // want_gain: a tangent or cotangent of Lgain is asked for, which needs innov
 static int check_tracking_estimated_sweep_args(const qln_handle* h, const EstimatedTraj& t, bool want_gain,
                                                const std::string& w) {
-    if (t.ny < 1 || t.ny > QLN_TRACK_NY_MAX)
-        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": ny must be in [1, " + std::to_string(QLN_TRACK_NY_MAX) + "]");
+    if (int rc = check_tracking_ny(t.ny, w)) return rc;
     if (!t.Lgain || !t.H) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Lgain or H");
-    if (t.limited && !t.sat) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null sat (the limited roll-out's saturation record)");
+    if (int rc = check_limited_sat(t.limited, t.sat, w)) return rc;
     if (t.limited && (t.event != nullptr) != (t.event_hat != nullptr))
         return fail(QLN_ERR_INVALID_ARGUMENT, w + ": exactly one of event and event_hat (both: the guarded blocks, neither: the "
                                                   "knot-scheduled ones)");
@@ -2470,15 +2482,6 @@ static int check_tracking_estimated_vjp_args(const qln_handle* h, const Estimate
     return check_tracking_estimated_sweep_args(h, t, a.Lgain_bar != nullptr, w);
 }
 
-// host forms: the values of H, the models, the saturation record and the two event records
-static int check_host_estimated_traj(const qln_handle* h, const EstimatedTraj& t, const char* who) {
-    if (int rc = check_host_meas(t.H, t.ny, who)) return rc;
-    if (int rc = check_host_models(h, t.model, who)) return rc;
-    if (int rc = check_host_sat(h, t.sat, who)) return rc;
-    if (int rc = check_host_events(h, t.event, who)) return rc;
-    return check_host_events(h, t.event_hat, who);
-}
-
 // the trajectory as the launch reads it: Zout's buffer stands in for a Zref the host form did not stage
 static qln::EstimatedSweepIn estimated_sweep_in(double* const* d, int32_t ny) {
     return {d[kZ] ? d[kZ] : d[kV], d[kK], d[kLgain], d[kH], ny, d[kModel], d[kV], d[kXhat], d[kInnov], d[kEvent], d[kEventHat]};
@@ -2486,6 +2489,7 @@ static qln::EstimatedSweepIn estimated_sweep_in(double* const* d, int32_t ny) {
 
 // The host form stages Zref only when K_dot is given (the kernel reads it for nothing else), and innov only with Lgain_dot,
 // which is also when the overlap rule looks at innov.  Lgain, H, innov and their tangents have the extent of the call's ny.
+// The saturation record stands before the event records: the host form has always looked at its values first.
 static int tracking_estimated_jvp(qln_handle* h, MemForm mem, const EstimatedTraj& t, const qln::EstimatedJvpArgs& a,
                                   const char* who) {
     if (int rc = check_tracking_estimated_jvp_args(h, t, a, who)) return rc;
@@ -2495,15 +2499,12 @@ static int tracking_estimated_jvp(qln_handle* h, MemForm mem, const EstimatedTra
                            copy_in(kLgain, t.Lgain).sized(ng), copy_in(kH, t.H).sized((int64_t)t.ny * QLN_NX),
                            copy_in(kModel, t.model), copy_in(kXhat, t.Xhat),
                            copy_in(kInnov, t.innov).sized(nm).ruled_if(want_gain).staged_if(want_gain),
-                           copy_in(kEvent, t.event), copy_in(kEventHat, t.event_hat), copy_in(kSat, t.sat),
+                           copy_in(kSat, t.sat), copy_in(kEvent, t.event), copy_in(kEventHat, t.event_hat),
                            copy_in(kZdot, a.Zref_dot), copy_in(kKdot, a.K_dot), copy_in(kLgainD, a.Lgain_dot).sized(ng),
                            copy_in(kX0, a.x0_dot), copy_in(kXhat0, a.xhat0_dot), copy_in(kModelD, a.model_dot),
                            copy_inout(kZio, a.Zout_dot), copy_out(kXhatD, a.Xhat_dot), copy_out(kInnovD, a.innov_dot).sized(nm),
                            copy_out(kEventD, a.event_dot), copy_out(kEventHatD, a.event_hat_dot)};
-    if (int rc = check_no_overlap(h, args, who)) return rc;
-    if (mem == kHostMem)
-        if (int rc = check_host_estimated_traj(h, t, who)) return rc;
-    return run_call(h, mem, args, [&](double* const* d, bool) {
+    return run_tracking_call(h, mem, args, who, [&](double* const* d, bool) {
         const qln::EstimatedJvpArgs da = {d[kZdot], d[kKdot], d[kLgainD], d[kX0], d[kXhat0], d[kModelD], d[kZio], d[kXhatD],
                                           d[kInnovD], d[kEventD], d[kEventHatD]};
         return qln::launch_tracking_rollout_estimated_jvp(h->p, estimated_sweep_in(d, t.ny), da, d[kSat], h->stream);
@@ -2520,18 +2521,31 @@ static int tracking_estimated_vjp(qln_handle* h, MemForm mem, const EstimatedTra
                            copy_in(kLgain, t.Lgain).sized(ng), copy_in(kH, t.H).sized((int64_t)t.ny * QLN_NX),
                            copy_in(kModel, t.model), copy_in(kXhat, t.Xhat),
                            copy_in(kInnov, t.innov).sized(nm).ruled_if(want_gain).staged_if(want_gain),
-                           copy_in(kEvent, t.event), copy_in(kEventHat, t.event_hat), copy_in(kSat, t.sat),
+                           copy_in(kSat, t.sat), copy_in(kEvent, t.event), copy_in(kEventHat, t.event_hat),
                            copy_in(kZbar, a.Zbar), copy_in(kXhatD, a.Xhat_bar), copy_in(kInnovD, a.innov_bar).sized(nm),
                            copy_inout(kZio, a.Zref_bar), copy_out(kKbar, a.K_bar), copy_out(kLgainD, a.Lgain_bar).sized(ng),
                            copy_out(kX0, a.x0_bar), copy_out(kXhat0, a.xhat0_bar), copy_out(kModelD, a.model_bar)};
-    if (int rc = check_no_overlap(h, args, who)) return rc;
-    if (mem == kHostMem)
-        if (int rc = check_host_estimated_traj(h, t, who)) return rc;
-    return run_call(h, mem, args, [&](double* const* d, bool) {
+    return run_tracking_call(h, mem, args, who, [&](double* const* d, bool) {
         const qln::EstimatedVjpArgs da = {d[kZbar], d[kXhatD], d[kInnovD], d[kZio], d[kKbar], d[kLgainD], d[kX0], d[kXhat0],
                                           d[kModelD]};
         return qln::launch_tracking_rollout_estimated_vjp(h->p, estimated_sweep_in(d, t.ny), da, d[kSat], h->stream);
     });
+}
+
+static EstimatedTraj estimated_traj(const double* Zref, const double* K, const double* Lgain, const double* H, int32_t ny,
+                                    const double* model, const double* Zout, const double* Xhat, const double* innov) {
+    EstimatedTraj t{};
+    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout; t.Xhat = Xhat; t.innov = innov;
+    return t;
+}
+static EstimatedTraj at_events(EstimatedTraj t, const double* event, const double* event_hat) {
+    t.guarded = true; t.event = event; t.event_hat = event_hat;
+    return t;
+}
+// event and event_hat -- both or neither -- then select the guarded or the knot-scheduled blocks
+static EstimatedTraj at_active_set(EstimatedTraj t, const double* sat) {
+    t.limited = true; t.sat = sat; t.guarded = t.event && t.event_hat;
+    return t;
 }
 
 int qln_tracking_rollout_estimated_jvp(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
@@ -2539,24 +2553,20 @@ int qln_tracking_rollout_estimated_jvp(qln_handle* h, const double* Zref, const 
                                        const double* innov, const double* Zref_dot, const double* K_dot, const double* Lgain_dot,
                                        const double* x0_dot, const double* xhat0_dot, const double* model_dot, double* Zout_dot,
                                        double* Xhat_dot, double* innov_dot) {
-    EstimatedTraj t{};
-    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout; t.Xhat = Xhat; t.innov = innov;
-    qln::EstimatedJvpArgs a{};
-    a.Zref_dot = Zref_dot; a.K_dot = K_dot; a.Lgain_dot = Lgain_dot; a.x0_dot = x0_dot; a.xhat0_dot = xhat0_dot;
-    a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.Xhat_dot = Xhat_dot; a.innov_dot = innov_dot;
-    return tracking_estimated_jvp(h, kDeviceMem, t, a, "qln_tracking_rollout_estimated_jvp");
+    return tracking_estimated_jvp(h, kDeviceMem, estimated_traj(Zref, K, Lgain, H, ny, model, Zout, Xhat, innov),
+                                  qln::EstimatedJvpArgs{Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, Zout_dot,
+                                                        Xhat_dot, innov_dot, nullptr, nullptr},
+                                  "qln_tracking_rollout_estimated_jvp");
 }
 int qln_tracking_rollout_estimated_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                             const double* H, int32_t ny, const double* model, const double* Zout,
                                             const double* Xhat, const double* innov, const double* Zref_dot, const double* K_dot,
                                             const double* Lgain_dot, const double* x0_dot, const double* xhat0_dot,
                                             const double* model_dot, double* Zout_dot, double* Xhat_dot, double* innov_dot) {
-    EstimatedTraj t{};
-    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout; t.Xhat = Xhat; t.innov = innov;
-    qln::EstimatedJvpArgs a{};
-    a.Zref_dot = Zref_dot; a.K_dot = K_dot; a.Lgain_dot = Lgain_dot; a.x0_dot = x0_dot; a.xhat0_dot = xhat0_dot;
-    a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.Xhat_dot = Xhat_dot; a.innov_dot = innov_dot;
-    return tracking_estimated_jvp(h, kHostMem, t, a, "qln_tracking_rollout_estimated_jvp_host");
+    return tracking_estimated_jvp(h, kHostMem, estimated_traj(Zref, K, Lgain, H, ny, model, Zout, Xhat, innov),
+                                  qln::EstimatedJvpArgs{Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, Zout_dot,
+                                                        Xhat_dot, innov_dot, nullptr, nullptr},
+                                  "qln_tracking_rollout_estimated_jvp_host");
 }
 int qln_tracking_rollout_estimated_guarded_jvp(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                                const double* H, int32_t ny, const double* model, const double* Zout,
@@ -2565,14 +2575,11 @@ int qln_tracking_rollout_estimated_guarded_jvp(qln_handle* h, const double* Zref
                                                const double* Lgain_dot, const double* x0_dot, const double* xhat0_dot,
                                                const double* model_dot, double* Zout_dot, double* Xhat_dot, double* innov_dot,
                                                double* event_dot, double* event_hat_dot) {
-    EstimatedTraj t{};
-    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout;
-    t.Xhat = Xhat; t.innov = innov; t.guarded = true; t.event = event; t.event_hat = event_hat;
-    qln::EstimatedJvpArgs a{};
-    a.Zref_dot = Zref_dot; a.K_dot = K_dot; a.Lgain_dot = Lgain_dot; a.x0_dot = x0_dot;
-    a.xhat0_dot = xhat0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.Xhat_dot = Xhat_dot;
-    a.innov_dot = innov_dot; a.event_dot = event_dot; a.event_hat_dot = event_hat_dot;
-    return tracking_estimated_jvp(h, kDeviceMem, t, a, "qln_tracking_rollout_estimated_guarded_jvp");
+    return tracking_estimated_jvp(h, kDeviceMem,
+                                  at_events(estimated_traj(Zref, K, Lgain, H, ny, model, Zout, Xhat, innov), event, event_hat),
+                                  qln::EstimatedJvpArgs{Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, Zout_dot,
+                                                        Xhat_dot, innov_dot, event_dot, event_hat_dot},
+                                  "qln_tracking_rollout_estimated_guarded_jvp");
 }
 int qln_tracking_rollout_estimated_guarded_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                                     const double* H, int32_t ny, const double* model, const double* Zout,
@@ -2581,38 +2588,29 @@ int qln_tracking_rollout_estimated_guarded_jvp_host(qln_handle* h, const double*
                                                     const double* Lgain_dot, const double* x0_dot, const double* xhat0_dot,
                                                     const double* model_dot, double* Zout_dot, double* Xhat_dot,
                                                     double* innov_dot, double* event_dot, double* event_hat_dot) {
-    EstimatedTraj t{};
-    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout;
-    t.Xhat = Xhat; t.innov = innov; t.guarded = true; t.event = event; t.event_hat = event_hat;
-    qln::EstimatedJvpArgs a{};
-    a.Zref_dot = Zref_dot; a.K_dot = K_dot; a.Lgain_dot = Lgain_dot; a.x0_dot = x0_dot;
-    a.xhat0_dot = xhat0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.Xhat_dot = Xhat_dot;
-    a.innov_dot = innov_dot; a.event_dot = event_dot; a.event_hat_dot = event_hat_dot;
-    return tracking_estimated_jvp(h, kHostMem, t, a, "qln_tracking_rollout_estimated_guarded_jvp_host");
+    return tracking_estimated_jvp(h, kHostMem,
+                                  at_events(estimated_traj(Zref, K, Lgain, H, ny, model, Zout, Xhat, innov), event, event_hat),
+                                  qln::EstimatedJvpArgs{Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, Zout_dot,
+                                                        Xhat_dot, innov_dot, event_dot, event_hat_dot},
+                                  "qln_tracking_rollout_estimated_guarded_jvp_host");
 }
 int qln_tracking_rollout_estimated_vjp(qln_handle* h, const double* Zref, const double* K, const double* Lgain, const double* H,
                                        int32_t ny, const double* model, const double* Zout, const double* Xhat,
                                        const double* innov, const double* Zbar, const double* Xhat_bar, const double* innov_bar,
                                        double* Zref_bar, double* K_bar, double* Lgain_bar, double* x0_bar, double* xhat0_bar,
                                        double* model_bar) {
-    EstimatedTraj t{};
-    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout; t.Xhat = Xhat; t.innov = innov;
-    qln::EstimatedVjpArgs a{};
-    a.Zbar = Zbar; a.Xhat_bar = Xhat_bar; a.innov_bar = innov_bar; a.Zref_bar = Zref_bar; a.K_bar = K_bar;
-    a.Lgain_bar = Lgain_bar; a.x0_bar = x0_bar; a.xhat0_bar = xhat0_bar; a.model_bar = model_bar;
-    return tracking_estimated_vjp(h, kDeviceMem, t, a, "qln_tracking_rollout_estimated_vjp");
+    return tracking_estimated_vjp(h, kDeviceMem, estimated_traj(Zref, K, Lgain, H, ny, model, Zout, Xhat, innov),
+                                  qln::EstimatedVjpArgs{Zbar, Xhat_bar, innov_bar, Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar,
+                                                        model_bar}, "qln_tracking_rollout_estimated_vjp");
 }
 int qln_tracking_rollout_estimated_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                             const double* H, int32_t ny, const double* model, const double* Zout,
                                             const double* Xhat, const double* innov, const double* Zbar, const double* Xhat_bar,
                                             const double* innov_bar, double* Zref_bar, double* K_bar, double* Lgain_bar,
                                             double* x0_bar, double* xhat0_bar, double* model_bar) {
-    EstimatedTraj t{};
-    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout; t.Xhat = Xhat; t.innov = innov;
-    qln::EstimatedVjpArgs a{};
-    a.Zbar = Zbar; a.Xhat_bar = Xhat_bar; a.innov_bar = innov_bar; a.Zref_bar = Zref_bar; a.K_bar = K_bar;
-    a.Lgain_bar = Lgain_bar; a.x0_bar = x0_bar; a.xhat0_bar = xhat0_bar; a.model_bar = model_bar;
-    return tracking_estimated_vjp(h, kHostMem, t, a, "qln_tracking_rollout_estimated_vjp_host");
+    return tracking_estimated_vjp(h, kHostMem, estimated_traj(Zref, K, Lgain, H, ny, model, Zout, Xhat, innov),
+                                  qln::EstimatedVjpArgs{Zbar, Xhat_bar, innov_bar, Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar,
+                                                        model_bar}, "qln_tracking_rollout_estimated_vjp_host");
 }
 int qln_tracking_rollout_estimated_guarded_vjp(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                                const double* H, int32_t ny, const double* model, const double* Zout,
@@ -2620,13 +2618,10 @@ int qln_tracking_rollout_estimated_guarded_vjp(qln_handle* h, const double* Zref
                                                const double* event_hat, const double* Zbar, const double* Xhat_bar,
                                                const double* innov_bar, double* Zref_bar, double* K_bar, double* Lgain_bar,
                                                double* x0_bar, double* xhat0_bar, double* model_bar) {
-    EstimatedTraj t{};
-    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout;
-    t.Xhat = Xhat; t.innov = innov; t.guarded = true; t.event = event; t.event_hat = event_hat;
-    qln::EstimatedVjpArgs a{};
-    a.Zbar = Zbar; a.Xhat_bar = Xhat_bar; a.innov_bar = innov_bar; a.Zref_bar = Zref_bar; a.K_bar = K_bar;
-    a.Lgain_bar = Lgain_bar; a.x0_bar = x0_bar; a.xhat0_bar = xhat0_bar; a.model_bar = model_bar;
-    return tracking_estimated_vjp(h, kDeviceMem, t, a, "qln_tracking_rollout_estimated_guarded_vjp");
+    return tracking_estimated_vjp(h, kDeviceMem,
+                                  at_events(estimated_traj(Zref, K, Lgain, H, ny, model, Zout, Xhat, innov), event, event_hat),
+                                  qln::EstimatedVjpArgs{Zbar, Xhat_bar, innov_bar, Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar,
+                                                        model_bar}, "qln_tracking_rollout_estimated_guarded_vjp");
 }
 int qln_tracking_rollout_estimated_guarded_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                                     const double* H, int32_t ny, const double* model, const double* Zout,
@@ -2634,13 +2629,10 @@ int qln_tracking_rollout_estimated_guarded_vjp_host(qln_handle* h, const double*
                                                     const double* event_hat, const double* Zbar, const double* Xhat_bar,
                                                     const double* innov_bar, double* Zref_bar, double* K_bar, double* Lgain_bar,
                                                     double* x0_bar, double* xhat0_bar, double* model_bar) {
-    EstimatedTraj t{};
-    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout;
-    t.Xhat = Xhat; t.innov = innov; t.guarded = true; t.event = event; t.event_hat = event_hat;
-    qln::EstimatedVjpArgs a{};
-    a.Zbar = Zbar; a.Xhat_bar = Xhat_bar; a.innov_bar = innov_bar; a.Zref_bar = Zref_bar; a.K_bar = K_bar;
-    a.Lgain_bar = Lgain_bar; a.x0_bar = x0_bar; a.xhat0_bar = xhat0_bar; a.model_bar = model_bar;
-    return tracking_estimated_vjp(h, kHostMem, t, a, "qln_tracking_rollout_estimated_guarded_vjp_host");
+    return tracking_estimated_vjp(h, kHostMem,
+                                  at_events(estimated_traj(Zref, K, Lgain, H, ny, model, Zout, Xhat, innov), event, event_hat),
+                                  qln::EstimatedVjpArgs{Zbar, Xhat_bar, innov_bar, Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar,
+                                                        model_bar}, "qln_tracking_rollout_estimated_guarded_vjp_host");
 }
 
 // the sweeps at the limited loop's active set: the same path with its saturation record; event and event_hat select the guarded
@@ -2652,14 +2644,12 @@ int qln_tracking_rollout_estimated_limited_jvp(qln_handle* h, const double* Zref
                                                const double* K_dot, const double* Lgain_dot, const double* x0_dot,
                                                const double* xhat0_dot, const double* model_dot, double* Zout_dot,
                                                double* Xhat_dot, double* innov_dot, double* event_dot, double* event_hat_dot) {
-    EstimatedTraj t{};
-    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout; t.Xhat = Xhat;
-    t.innov = innov; t.guarded = event && event_hat; t.event = event; t.event_hat = event_hat; t.limited = true; t.sat = sat;
-    qln::EstimatedJvpArgs a{};
-    a.Zref_dot = Zref_dot; a.K_dot = K_dot; a.Lgain_dot = Lgain_dot; a.x0_dot = x0_dot;
-    a.xhat0_dot = xhat0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.Xhat_dot = Xhat_dot;
-    a.innov_dot = innov_dot; a.event_dot = event_dot; a.event_hat_dot = event_hat_dot;
-    return tracking_estimated_jvp(h, kDeviceMem, t, a, "qln_tracking_rollout_estimated_limited_jvp");
+    return tracking_estimated_jvp(h, kDeviceMem,
+                                  at_active_set(at_events(estimated_traj(Zref, K, Lgain, H, ny, model, Zout, Xhat, innov), event,
+                                                          event_hat), sat),
+                                  qln::EstimatedJvpArgs{Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, Zout_dot,
+                                                        Xhat_dot, innov_dot, event_dot, event_hat_dot},
+                                  "qln_tracking_rollout_estimated_limited_jvp");
 }
 int qln_tracking_rollout_estimated_limited_jvp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                                     const double* H, int32_t ny, const double* model, const double* Zout,
@@ -2669,14 +2659,12 @@ int qln_tracking_rollout_estimated_limited_jvp_host(qln_handle* h, const double*
                                                     const double* xhat0_dot, const double* model_dot, double* Zout_dot,
                                                     double* Xhat_dot, double* innov_dot, double* event_dot,
                                                     double* event_hat_dot) {
-    EstimatedTraj t{};
-    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout; t.Xhat = Xhat;
-    t.innov = innov; t.guarded = event && event_hat; t.event = event; t.event_hat = event_hat; t.limited = true; t.sat = sat;
-    qln::EstimatedJvpArgs a{};
-    a.Zref_dot = Zref_dot; a.K_dot = K_dot; a.Lgain_dot = Lgain_dot; a.x0_dot = x0_dot;
-    a.xhat0_dot = xhat0_dot; a.model_dot = model_dot; a.Zout_dot = Zout_dot; a.Xhat_dot = Xhat_dot;
-    a.innov_dot = innov_dot; a.event_dot = event_dot; a.event_hat_dot = event_hat_dot;
-    return tracking_estimated_jvp(h, kHostMem, t, a, "qln_tracking_rollout_estimated_limited_jvp_host");
+    return tracking_estimated_jvp(h, kHostMem,
+                                  at_active_set(at_events(estimated_traj(Zref, K, Lgain, H, ny, model, Zout, Xhat, innov), event,
+                                                          event_hat), sat),
+                                  qln::EstimatedJvpArgs{Zref_dot, K_dot, Lgain_dot, x0_dot, xhat0_dot, model_dot, Zout_dot,
+                                                        Xhat_dot, innov_dot, event_dot, event_hat_dot},
+                                  "qln_tracking_rollout_estimated_limited_jvp_host");
 }
 int qln_tracking_rollout_estimated_limited_vjp(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                                const double* H, int32_t ny, const double* model, const double* Zout,
@@ -2684,13 +2672,11 @@ int qln_tracking_rollout_estimated_limited_vjp(qln_handle* h, const double* Zref
                                                const double* event_hat, const double* sat, const double* Zbar,
                                                const double* Xhat_bar, const double* innov_bar, double* Zref_bar, double* K_bar,
                                                double* Lgain_bar, double* x0_bar, double* xhat0_bar, double* model_bar) {
-    EstimatedTraj t{};
-    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout; t.Xhat = Xhat;
-    t.innov = innov; t.guarded = event && event_hat; t.event = event; t.event_hat = event_hat; t.limited = true; t.sat = sat;
-    qln::EstimatedVjpArgs a{};
-    a.Zbar = Zbar; a.Xhat_bar = Xhat_bar; a.innov_bar = innov_bar; a.Zref_bar = Zref_bar; a.K_bar = K_bar;
-    a.Lgain_bar = Lgain_bar; a.x0_bar = x0_bar; a.xhat0_bar = xhat0_bar; a.model_bar = model_bar;
-    return tracking_estimated_vjp(h, kDeviceMem, t, a, "qln_tracking_rollout_estimated_limited_vjp");
+    return tracking_estimated_vjp(h, kDeviceMem,
+                                  at_active_set(at_events(estimated_traj(Zref, K, Lgain, H, ny, model, Zout, Xhat, innov), event,
+                                                          event_hat), sat),
+                                  qln::EstimatedVjpArgs{Zbar, Xhat_bar, innov_bar, Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar,
+                                                        model_bar}, "qln_tracking_rollout_estimated_limited_vjp");
 }
 int qln_tracking_rollout_estimated_limited_vjp_host(qln_handle* h, const double* Zref, const double* K, const double* Lgain,
                                                     const double* H, int32_t ny, const double* model, const double* Zout,
@@ -2699,13 +2685,11 @@ int qln_tracking_rollout_estimated_limited_vjp_host(qln_handle* h, const double*
                                                     const double* Xhat_bar, const double* innov_bar, double* Zref_bar,
                                                     double* K_bar, double* Lgain_bar, double* x0_bar, double* xhat0_bar,
                                                     double* model_bar) {
-    EstimatedTraj t{};
-    t.Zref = Zref; t.K = K; t.Lgain = Lgain; t.H = H; t.ny = ny; t.model = model; t.Zout = Zout; t.Xhat = Xhat;
-    t.innov = innov; t.guarded = event && event_hat; t.event = event; t.event_hat = event_hat; t.limited = true; t.sat = sat;
-    qln::EstimatedVjpArgs a{};
-    a.Zbar = Zbar; a.Xhat_bar = Xhat_bar; a.innov_bar = innov_bar; a.Zref_bar = Zref_bar; a.K_bar = K_bar;
-    a.Lgain_bar = Lgain_bar; a.x0_bar = x0_bar; a.xhat0_bar = xhat0_bar; a.model_bar = model_bar;
-    return tracking_estimated_vjp(h, kHostMem, t, a, "qln_tracking_rollout_estimated_limited_vjp_host");
+    return tracking_estimated_vjp(h, kHostMem,
+                                  at_active_set(at_events(estimated_traj(Zref, K, Lgain, H, ny, model, Zout, Xhat, innov), event,
+                                                          event_hat), sat),
+                                  qln::EstimatedVjpArgs{Zbar, Xhat_bar, innov_bar, Zref_bar, K_bar, Lgain_bar, x0_bar, xhat0_bar,
+                                                        model_bar}, "qln_tracking_rollout_estimated_limited_vjp_host");
 }
 
 // ------------------------------------------------------------------ host-pointer (MOI) mode
