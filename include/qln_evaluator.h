@@ -1210,6 +1210,61 @@ int qln_kalman_design_guarded_jvp_host(qln_handle* h, const double* Zout, const 
                                        const double* Lgain, const double* H, int32_t ny, const double* Vdiag,
                                        const double* Sigma0_dot, int32_t sigma0_batch, const double* Wdiag_dot,
                                        const double* Vdiag_dot, double* Lgain_dot, double* Pest_dot, double* logdet_dot);
+/* The REVERSE sweep through the design of the filter: the transpose of qln_kalman_design_jvp*'s linear map, so that one design,
+ * one filter and two reverse sweeps give the whole gradient of a likelihood with respect to the noise (with
+ * qln_landing_filter_vjp), where forward mode takes one sweep per parameter.  Per problem that map takes (Sigma0_dot[120],
+ * Wdiag_dot[15], Vdiag_dot[ny]) to (Lgain_dot[N][15][ny], Pest_dot[N][120], logdet_dot[N]); its coefficients depend on Zout
+ * (through A_k), Lgain, H and V only.  This call is its transpose BETWEEN THE ARRAYS AS STORED: cotangents (Lgain_bar, Pest_bar,
+ * logdet_bar) in, (Sigma0_bar, Wdiag_bar, Vdiag_bar) out, PER PROBLEM -- the forward call shares Wdiag_dot and Vdiag_dot over the
+ * batch, the transpose does not sum over it (the caller does, if it wants that), so nothing is accumulated across problems and
+ * the results are deterministic.  For every direction and every cotangent, over the stored arrays and with no weights,
+ *     <Lgain_bar, Lgain_dot> + <Pest_bar, Pest_dot> + <logdet_bar, logdet_dot> = <Sigma0_bar, Sigma0_dot> + <Wdiag_bar, Wdiag_dot>
+ *                                                                               + <Vdiag_bar, Vdiag_dot>.
+ * The packed convention that makes it so: a packed off-diagonal entry stands for both (i, j) and (j, i); Pest_bar[p] enters the
+ * full symmetric cotangent as Pest_bar[p] / 2 on each side (the diagonal as it is), and Sigma0_bar[p] = Lambda_0(i, j) +
+ * Lambda_0(j, i) off the diagonal, Lambda_0(i, i) on it.  With C = I - L_k H, Sinv = diag(1/V) (I - H L_k), sym(X) = (X + X') / 2
+ * and Lambda the full symmetric cotangent of Pd^-_{k+1} (zero behind the last knot), for k = N-1 .. 0:
+ *     Wdiag_bar += diag(Lambda);   Pi = A_k' Lambda A_k + sym(Pest_bar_k)          (k = N-1: Pi = sym(Pest_bar_k))
+ *     Vdiag_bar += diag(L_k' Pi L_k)
+ *     Tb         = Lgain_bar_k Sinv'             row j: (lb_j - (lb_j L_k') H') ./ V         (15 x ny)
+ *     Sb         = -L_k' Tb + logdet_bar_k Sinv                                               (ny x ny)
+ *     Vdiag_bar += diag(Sb)
+ *     Lambda     = C' Pi C + H' sym(Sb) H + sym(Tb H)
+ * and Sigma0_bar = pack(Lambda_0).  A_k are the forward sweep's blocks; guarded, the touchdown knot's composite A*, applied
+ * transposed as qln_landing_smoother_guarded applies it.  Nothing is divided or factored, and the cotangents may have any sign.
+ * THE FORWARD CALL'S TWO CAVEATS hold here: with gains that are not optimal for (Zout, H, V, Sigma0, W) the result is the
+ * transpose of a map that is no derivative; and I - H L_k loses |H P^- H'| / V digits, a loss that here reaches every output
+ * that Lgain_bar or logdet_bar feeds.
+ * Inputs: Zout, Lgain, H, ny and Vdiag as for qln_kalman_design_jvp (Zout's last knot and padding are not read), eight rows
+ *   always, the rows behind ny being zero rows with V = 1 and zero columns of L and Lgain_bar, so a call gives the bits of the
+ *   same call with those written out.  The cotangents, each optional (NULL: zero, not read, the bits of explicit zeros), at least
+ *   one: Lgain_bar [B][N][15][ny], Pest_bar [B][N][120] packed, logdet_bar [B][N].
+ * Outputs (each optional, at least one non-NULL; overwritten; which are asked for changes no other output's bits; none may
+ * overlap an input or another output; device arrays in the device forms): Sigma0_bar [B][120] packed; Wdiag_bar [B][15];
+ * Vdiag_bar [B][ny].
+ * Refused with QLN_ERR_INVALID_ARGUMENT, the checks that need no handle before the null handle, in this order: ny outside
+ * 1..QLN_TRACK_NY_MAX, no output, a NULL event in the guarded form, a NULL H or Vdiag, a V entry not finite or not > 0, all three
+ * cotangents NULL, a NULL Lgain; behind the handle a NULL Zout, and an output that overlaps an input or another output.  The
+ * device forms do not validate device data; the host forms also refuse a non-finite H and validate model and event as
+ * qln_tracking_kalman_guarded_host does.  A guarded batch without a touchdown and with model == NULL gives
+ * qln_noise_design_vjp's bits for a handle with k_trans = N + 1.  Device pointers, stream-ordered; needs no cost table.
+ * (The entries stand outside the qln_tracking_, qln_landing_ and qln_kalman_ prefixes, whose sets are closed.) */
+int qln_noise_design_vjp(qln_handle* h, const double* Zout, const double* Lgain, const double* H, int32_t ny,
+                         const double* Vdiag /* host, ny entries, finite and > 0 */, const double* Lgain_bar /* or NULL */,
+                         const double* Pest_bar /* or NULL */, const double* logdet_bar /* or NULL */,
+                         double* Sigma0_bar /* [B][120] or NULL */, double* Wdiag_bar /* [B][15] or NULL */,
+                         double* Vdiag_bar /* [B][ny] or NULL */);
+int qln_noise_design_vjp_host(qln_handle* h, const double* Zout, const double* Lgain, const double* H, int32_t ny,
+                              const double* Vdiag, const double* Lgain_bar, const double* Pest_bar, const double* logdet_bar,
+                              double* Sigma0_bar, double* Wdiag_bar, double* Vdiag_bar);
+int qln_noise_design_guarded_vjp(qln_handle* h, const double* Zout, const double* model /* or NULL */,
+                                 const double* event /* required */, const double* Lgain, const double* H, int32_t ny,
+                                 const double* Vdiag, const double* Lgain_bar, const double* Pest_bar, const double* logdet_bar,
+                                 double* Sigma0_bar, double* Wdiag_bar, double* Vdiag_bar);
+int qln_noise_design_guarded_vjp_host(qln_handle* h, const double* Zout, const double* model, const double* event,
+                                      const double* Lgain, const double* H, int32_t ny, const double* Vdiag,
+                                      const double* Lgain_bar, const double* Pest_bar, const double* logdet_bar,
+                                      double* Sigma0_bar, double* Wdiag_bar, double* Vdiag_bar);
 /* The FILTER on recorded data, and the score of that data under it: the estimator of qln_tracking_rollout_estimated* as a call
  * of its own, for a landing that was flown elsewhere -- sensor readings and the forces that were applied -- where that call
  * produces Xhat and innov only together with a plant it integrates itself.  Its outputs feed qln_landing_smoother*, and loglik

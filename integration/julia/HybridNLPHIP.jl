@@ -441,6 +441,52 @@ function tracking_kalman_guarded_jvp(prob::HybridNLPHIP, Zout::Vector{Float64}, 
                     V_dot === nothing ? C_NULL : V_dot, L_dot, Pest_dot, logdet_dot))
     return L_dot, Pest_dot, logdet_dot
 end
+# The reverse sweep through the design of the filter (include/qln_evaluator.h, DESIGN.md 4.29): the transpose of
+# tracking_kalman_jvp's map between the arrays as stored, at the same gains L (ny, 15, N).  The cotangents L_bar (ny, 15, N),
+# Pest_bar (120, N) packed and logdet_bar (N), of any sign; nothing for zero, at least one.  Returns (Sigma0_bar (120) packed --
+# an off-diagonal entry is the cotangent of both of its sides --, W_bar (15), V_bar (ny)); with them
+# sum(L_bar .* L_dot) + sum(Pest_bar .* Pest_dot) + sum(logdet_bar .* logdet_dot) equals the three products with the packed
+# Sigma0_dot, W_dot and V_dot.  tracking_kalman_guarded_vjp is the same through the guard-triggered touchdown.
+function tracking_kalman_vjp(prob::HybridNLPHIP, Zout::Vector{Float64}, L::Array{Float64,3}, H::Matrix{Float64},
+                             V::Vector{Float64}; L_bar=nothing, Pest_bar=nothing, logdet_bar=nothing)
+    N = prob.N
+    ny = size(H, 1)
+    (1 <= ny <= 8 && size(H, 2) == 15 && length(V) == ny && size(L) == (ny, 15, N)) ||
+        error("H: (ny, 15) with 1 <= ny <= 8, V: ny variances, L: (ny, 15, N)")
+    ((L_bar === nothing || size(L_bar) == (ny, 15, N)) && (Pest_bar === nothing || size(Pest_bar) == (120, N)) &&
+     (logdet_bar === nothing || length(logdet_bar) == N)) || error("L_bar: (ny, 15, N), Pest_bar: (120, N), logdet_bar: N values")
+    Hrow = Matrix{Float64}(transpose(H))  # row-major [ny][15]
+    Sigma0_bar = zeros(120)
+    W_bar = zeros(15)
+    V_bar = zeros(ny)
+    qln_check(ccall((:qln_noise_design_vjp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zout, L, Hrow, Int32(ny), V, L_bar === nothing ? C_NULL : L_bar,
+                    Pest_bar === nothing ? C_NULL : Pest_bar, logdet_bar === nothing ? C_NULL : logdet_bar, Sigma0_bar, W_bar, V_bar))
+    return Sigma0_bar, W_bar, V_bar
+end
+function tracking_kalman_guarded_vjp(prob::HybridNLPHIP, Zout::Vector{Float64}, events::Vector{Float64}, L::Array{Float64,3},
+                                     H::Matrix{Float64}, V::Vector{Float64}; L_bar=nothing, Pest_bar=nothing, logdet_bar=nothing,
+                                     model=nothing)
+    N = prob.N
+    ny = size(H, 1)
+    (1 <= ny <= 8 && size(H, 2) == 15 && length(V) == ny && size(L) == (ny, 15, N)) ||
+        error("H: (ny, 15) with 1 <= ny <= 8, V: ny variances, L: (ny, 15, N)")
+    ((L_bar === nothing || size(L_bar) == (ny, 15, N)) && (Pest_bar === nothing || size(Pest_bar) == (120, N)) &&
+     (logdet_bar === nothing || length(logdet_bar) == N)) || error("L_bar: (ny, 15, N), Pest_bar: (120, N), logdet_bar: N values")
+    Hrow = Matrix{Float64}(transpose(H))
+    Sigma0_bar = zeros(120)
+    W_bar = zeros(15)
+    V_bar = zeros(ny)
+    qln_check(ccall((:qln_noise_design_guarded_vjp_host, LIBQLN), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    prob.handle, Zout, model === nothing ? C_NULL : model, events, L, Hrow, Int32(ny), V,
+                    L_bar === nothing ? C_NULL : L_bar, Pest_bar === nothing ? C_NULL : Pest_bar,
+                    logdet_bar === nothing ? C_NULL : logdet_bar, Sigma0_bar, W_bar, V_bar))
+    return Sigma0_bar, W_bar, V_bar
+end
 # Fixed-interval smoothing of a flown landing (include/qln_evaluator.h, DESIGN.md 4.25): the state at every knot given all N
 # measurements, by the modified Bryson-Frazier sweep, which inverts nothing.  Ztraj: the trajectory the filter was designed
 # along; L (ny, 15, N) and Pest (120, N) as tracking_kalman returns them for the same (Ztraj, H, V); Xhat (15, N) and innov

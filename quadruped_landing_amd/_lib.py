@@ -195,6 +195,10 @@ SIGNATURES = {
     "qln_kalman_design_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, C.c_int32] + [_dp] * 5),
     "qln_kalman_design_guarded_jvp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, C.c_int32] + [_dp] * 5),
     "qln_kalman_design_guarded_jvp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, C.c_int32] + [_dp] * 5),
+    "qln_noise_design_vjp": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32] + [_dp] * 7),
+    "qln_noise_design_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32] + [_dp] * 7),
+    "qln_noise_design_guarded_vjp": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 7),
+    "qln_noise_design_guarded_vjp_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 7),
     "qln_landing_filter": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 7),
     "qln_landing_filter_host": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 7),
     "qln_landing_filter_guarded": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int32] + [_dp] * 8),

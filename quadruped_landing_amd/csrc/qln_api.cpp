@@ -96,8 +96,8 @@ enum HostRole {
     kKbar,   // out: the gains' cotangent                                   layout of K
     kKdot,   // in: the jvp's tangent K_dot                                 layout of K
     kP,      // out: the cost-to-go                                         [B][N][120]
-    kX0,     // in: the roll-out's x0; out: the vjp's x0_bar                [B][15]
-    kCov0,   // in: the covariance sweep's Sigma0 (1 or B tiles used)       [B][120]
+    kX0,     // in: the roll-out's x0; out: the vjp's x0_bar, the design vjp's Wdiag_bar  [B][15]
+    kCov0,   // in: the covariance sweep's Sigma0 (1 or B tiles used); out: the design vjp's Sigma0_bar  [B][120]
     kCov,    // out: the covariances                                        layout of P
     kMarg,   // out: the marginals                                          [B][N][8]
     kMultInfo,  // out: the multiplier estimate's report                    [B][16]
@@ -109,7 +109,7 @@ enum HostRole {
     kSat,    // out: the limited roll-out's saturation codes; in: the same for its sweeps and gains  [B][N-1]
     kH,      // in: the Kalman filter's measurement matrix (ny rows used)   [8][15]
     kLgain,  // out: the filter gains ([B][N][15][ny] used)                 [B][N][15][8]
-    kPest,   // out: the error covariances P^+                              layout of P
+    kPest,   // out: the error covariances P^+; in: the design vjp's Pest_bar  layout of P
     kXhat0,  // in: the estimated roll-out's xhat0                          [B][15]
     kVnoise, // in: its measurement noise ([B][N][ny] used)                 [B][N][8]
     kWnoise, // in: its process noise                                       [B][N-1][15]
@@ -126,7 +126,8 @@ enum HostRole {
     kY,      // in: the filter's measurements ([B][N][ny] used)             [B][N][8]
     kScore,  // out: the filter's {nis_k, log det S_k}                      [B][N][2]
     kLoglik, // out: the filter's log-likelihood; out / in: its sweeps' loglik_dot / loglik_bar  [B]
-    kNisD,   // out: the filter jvp's nis_dot; in: the vjp's nis_bar        [B][N]
+    kNisD,   // out: the filter jvp's nis_dot, the design jvp's logdet_dot; in: the vjps' nis_bar and logdet_bar  [B][N]
+    kVbar,   // out: the design vjp's Vdiag_bar ([B][ny] used)              [B][8]
     kHostRoles
 };
 
@@ -210,6 +211,7 @@ int64_t host_role_size(const qln_handle* h, HostRole r) {
         case kVnoise: case kInnov: case kInnovD: case kY: return tracking_meas_total(D, QLN_TRACK_NY_MAX);
         case kScore: return (int64_t)D.B * D.N * 2;
         case kNisD: return (int64_t)D.B * D.N;
+        case kVbar: return (int64_t)D.B * QLN_TRACK_NY_MAX;
         case kWnoise: return (int64_t)D.B * (D.N - 1) * QLN_NX;
         case kXhat: case kXhatD: case kXs: return (int64_t)D.B * D.N * QLN_NX;
         case kHostRoles: break;
@@ -1963,6 +1965,88 @@ int qln_kalman_design_guarded_jvp_host(qln_handle* h, const double* Zout, const 
                              at_events(kalman_jvp_call(Zout, Lgain, H, ny, Vdiag, Sigma0_dot, sigma0_batch, Wdiag_dot, Vdiag_dot,
                                                        Lgain_dot, Pest_dot, logdet_dot), model, event),
                              "qln_kalman_design_guarded_jvp_host");
+}
+
+// The reverse sweep through the Kalman design (k_tracking_kalman_vjp).  The checks that need no handle come first.
+// guarded: through the guard-triggered touchdown, which needs the roll-out's event records
+struct KalmanVjpCall {
+    const double *Zout, *model, *event, *Lgain, *H;
+    int32_t ny;
+    const double *Vdiag, *Lgain_bar, *Pest_bar, *logdet_bar;
+    double *Sigma0_bar, *Wdiag_bar, *Vdiag_bar;
+    bool guarded;
+};
+
+static int check_noise_design_vjp_args(const qln_handle* h, const KalmanVjpCall& a, const char* who) {
+    const std::string w(who);
+    if (int rc = check_tracking_ny(a.ny, w)) return rc;
+    if (int rc = check_some_output(a.Sigma0_bar || a.Wdiag_bar || a.Vdiag_bar, w)) return rc;
+    if (int rc = check_guard_event(a.guarded, a.event, w)) return rc;
+    if (!a.H || !a.Vdiag) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null H or Vdiag");
+    if (int rc = check_tracking_vdiag(a.Vdiag, a.ny, w)) return rc;
+    if (!a.Lgain_bar && !a.Pest_bar && !a.logdet_bar)
+        return fail(QLN_ERR_INVALID_ARGUMENT, w + ": Lgain_bar, Pest_bar and logdet_bar are all NULL (no cotangent)");
+    if (!a.Lgain) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Lgain");
+    if (int rc = check_handle(h)) return rc;
+    if (!a.Zout) return fail(QLN_ERR_INVALID_ARGUMENT, w + ": null Zout");
+    return QLN_OK;
+}
+
+static int noise_design_vjp(qln_handle* h, MemForm mem, const KalmanVjpCall& a, const char* who) {
+    if (int rc = check_noise_design_vjp_args(h, a, who)) return rc;
+    // the rows, gains and variances of the call's ny, of the roles' eight
+    const int64_t ng = tracking_gain_total(h->dims, a.ny);
+    const HostArgs args = {copy_in(kV, a.Zout), copy_in(kH, a.H).sized((int64_t)a.ny * QLN_NX), copy_in(kModel, a.model),
+                           copy_in(kEvent, a.event), copy_in(kLgain, a.Lgain).sized(ng), copy_in(kLgainD, a.Lgain_bar).sized(ng),
+                           copy_in(kPest, a.Pest_bar), copy_in(kNisD, a.logdet_bar), copy_out(kCov0, a.Sigma0_bar),
+                           copy_out(kX0, a.Wdiag_bar), copy_out(kVbar, a.Vdiag_bar).sized((int64_t)h->dims.B * a.ny)};
+    return run_tracking_call(h, mem, args, who, [&](double* const* d, bool) {
+        return qln::launch_tracking_kalman_vjp(h->p, d[kV], d[kModel], d[kEvent], d[kLgain], d[kH], a.ny, a.Vdiag, d[kLgainD],
+                                               d[kPest], d[kNisD], d[kCov0], d[kX0], d[kVbar], h->stream);
+    });
+}
+
+static KalmanVjpCall kalman_vjp_call(const double* Zout, const double* Lgain, const double* H, int32_t ny, const double* Vdiag,
+                                     const double* Lgain_bar, const double* Pest_bar, const double* logdet_bar, double* Sigma0_bar,
+                                     double* Wdiag_bar, double* Vdiag_bar) {
+    KalmanVjpCall a{};
+    a.Zout = Zout; a.Lgain = Lgain; a.H = H; a.ny = ny; a.Vdiag = Vdiag; a.Lgain_bar = Lgain_bar; a.Pest_bar = Pest_bar;
+    a.logdet_bar = logdet_bar; a.Sigma0_bar = Sigma0_bar; a.Wdiag_bar = Wdiag_bar; a.Vdiag_bar = Vdiag_bar;
+    return a;
+}
+static KalmanVjpCall at_events(KalmanVjpCall a, const double* model, const double* event) {
+    a.guarded = true; a.model = model; a.event = event;
+    return a;
+}
+
+int qln_noise_design_vjp(qln_handle* h, const double* Zout, const double* Lgain, const double* H, int32_t ny, const double* Vdiag,
+                         const double* Lgain_bar, const double* Pest_bar, const double* logdet_bar, double* Sigma0_bar,
+                         double* Wdiag_bar, double* Vdiag_bar) {
+    return noise_design_vjp(h, kDeviceMem,
+                            kalman_vjp_call(Zout, Lgain, H, ny, Vdiag, Lgain_bar, Pest_bar, logdet_bar, Sigma0_bar, Wdiag_bar,
+                                            Vdiag_bar), "qln_noise_design_vjp");
+}
+int qln_noise_design_vjp_host(qln_handle* h, const double* Zout, const double* Lgain, const double* H, int32_t ny,
+                              const double* Vdiag, const double* Lgain_bar, const double* Pest_bar, const double* logdet_bar,
+                              double* Sigma0_bar, double* Wdiag_bar, double* Vdiag_bar) {
+    return noise_design_vjp(h, kHostMem,
+                            kalman_vjp_call(Zout, Lgain, H, ny, Vdiag, Lgain_bar, Pest_bar, logdet_bar, Sigma0_bar, Wdiag_bar,
+                                            Vdiag_bar), "qln_noise_design_vjp_host");
+}
+int qln_noise_design_guarded_vjp(qln_handle* h, const double* Zout, const double* model, const double* event, const double* Lgain,
+                                 const double* H, int32_t ny, const double* Vdiag, const double* Lgain_bar, const double* Pest_bar,
+                                 const double* logdet_bar, double* Sigma0_bar, double* Wdiag_bar, double* Vdiag_bar) {
+    return noise_design_vjp(h, kDeviceMem,
+                            at_events(kalman_vjp_call(Zout, Lgain, H, ny, Vdiag, Lgain_bar, Pest_bar, logdet_bar, Sigma0_bar,
+                                                      Wdiag_bar, Vdiag_bar), model, event), "qln_noise_design_guarded_vjp");
+}
+int qln_noise_design_guarded_vjp_host(qln_handle* h, const double* Zout, const double* model, const double* event,
+                                      const double* Lgain, const double* H, int32_t ny, const double* Vdiag,
+                                      const double* Lgain_bar, const double* Pest_bar, const double* logdet_bar,
+                                      double* Sigma0_bar, double* Wdiag_bar, double* Vdiag_bar) {
+    return noise_design_vjp(h, kHostMem,
+                            at_events(kalman_vjp_call(Zout, Lgain, H, ny, Vdiag, Lgain_bar, Pest_bar, logdet_bar, Sigma0_bar,
+                                                      Wdiag_bar, Vdiag_bar), model, event), "qln_noise_design_guarded_vjp_host");
 }
 
 // The fixed-interval smoother (k_landing_smoother).  The checks that need no handle come first.

@@ -341,6 +341,15 @@ hipError_t launch_tracking_kalman_jvp(const BatchParams& p, const double* Zout, 
                                       const double* Lgain, const double* H, int ny, const double* Vd, const double* Sigma0_dot,
                                       int sigma0_batch, const double* Wd_dot, const double* Vd_dot, double* Lgain_dot,
                                       double* Pest_dot, double* logdet_dot, hipStream_t stream);
+// The reverse sweep through the Kalman design (qln_noise_design_vjp / _guarded_vjp), the transpose of the forward
+// sweep's map at the same gains: Lgain [B][N][15][ny] and H [ny][15] on the device, Vd (ny) a host array; the cotangents Lgain_bar
+// [B][N][15][ny], Pest_bar [B][N][120] and logdet_bar [B][N] on the device, each may be null (zeros), not all; Sigma0_bar [B][120],
+// Wdiag_bar [B][15] and Vdiag_bar [B][ny] on the device, each may be null, not all.  event selects the guarded blocks, and model
+// is read with it only.
+hipError_t launch_tracking_kalman_vjp(const BatchParams& p, const double* Zout, const double* model, const double* event,
+                                      const double* Lgain, const double* H, int ny, const double* Vd, const double* Lgain_bar,
+                                      const double* Pest_bar, const double* logdet_bar, double* Sigma0_bar, double* Wdiag_bar,
+                                      double* Vdiag_bar, hipStream_t stream);
 // The fixed-interval smoother of a flown landing (qln_landing_smoother / _guarded): Lgain [B][N][15][ny], Pest [B][N][120],
 // H [ny][15], Xhat [B][N][15] and innov [B][N][ny] on the device, Vd (ny) a host array; Xs [B][N][15] and Ps [B][N][120], either
 // may be null.  event selects the guarded blocks, and model is read with it only.

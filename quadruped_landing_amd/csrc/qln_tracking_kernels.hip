@@ -106,6 +106,10 @@
 // 4.28): the tangents of the gains, of P^+ and of log det S_k along (Sigma0_dot, W_dot, V_dot), at the gains alone, in that
 // kernel's mapping, on its blocks and on k_tracking_covariance's open-loop knot.
 //
+// k_tracking_kalman_vjp: the reverse sweep through that design (qln_noise_design_vjp / _guarded_vjp): the transpose
+// of k_tracking_kalman_jvp's map between the arrays as stored, cotangents of the gains, of P^+ and of log det S_k in, those of
+// (Sigma0, W, V) per problem out, in the same mapping, on the smoother's transposed applications (block_apply_t, touchdown_apply_t).
+//
 // k_landing_filter: the estimator on recorded data (qln_landing_filter / _guarded): the estimator's half of
 // k_tracking_rollout_estimated, measurements and applied forces read where that kernel forms them, and with kScore the
 // normalised innovation squared, log det S_k and the log-likelihood from the gains alone.  kModel: at a model of each record's own.
@@ -2218,6 +2222,225 @@ __global__ __launch_bounds__(kWave) void k_landing_smoother(BatchParams P, Smoot
 }
 
 
+// ---- k_tracking_kalman_vjp ----
+// per-row LDS image (doubles): the Lambda image [15][17] | the knot's 20 entries of Zout | the H tile [8][16], 1/V in its column 15 |
+// the L tile [15][8] | the Lgain_bar tile [15][8], which becomes the Tb tile in place
+constexpr int kVP = 0, kVZ = 256, kVH = kVZ + 20, kVL = kVH + QLN_TRACK_NY_MAX * 16, kVB = kVL + kJTile, kVRow = kVB + kJTile;
+static_assert(kImgSize <= kVZ - kVP && kVZ % 2 == 0 && kVH % 2 == 0 && kVL % 2 == 0 && kVB % 2 == 0 && kVRow % 2 == 0 &&
+                  kVRow <= kKRow,
+              "the image fits; 16-byte aligned sections; within the Kalman kernel's budget");
+
+// The reverse sweep through k_tracking_kalman's design (include/qln_evaluator.h): the transpose of
+// k_tracking_kalman_jvp's linear map between the arrays as stored, cotangents (Lgain_bar, Pest_bar, logdet_bar) in, (Sigma0_bar,
+// Wdiag_bar, Vdiag_bar) per problem out.  That kernel's mapping, one problem per row of sixteen lanes, lane j owns column j, and
+// one padded image holds Lambda, the full symmetric cotangent of Pd^-_{k+1} (zero behind the last knot); its backbone is the
+// smoother's: A' Lambda A by two transposed applications (block_apply_t, touchdown_apply_t) and C' . C with C = I - L H.  Per
+// knot k = N-1 .. 0, with Sinv = diag(1/V) (I - H L):
+//   1. (k < N-1) Wbar_j += Lambda(j, j);  Pi = A_k' Lambda A_k: the congruence step, transposed;
+//   2. Pi += sym(Pest_bar_k): a packed off-diagonal entry stands for two, so half of it goes to the image's lower triangle, which
+//      is the one that is read;
+//   3. row j of Tb = Lgain_bar_k Sinv': (lb - (lb L') H') ./ V, two dense chains on broadcast reads of the two tiles, no entry of
+//      H L formed; it replaces row j of the Lgain_bar tile;
+//   4. sym(Sb), Sb = -L' Tb + logdet_bar_k Sinv: 36 row sums, the same bits in every lane, each consumed where it is formed --
+//      its share of y = sym(Sb) H[:, j] and, on the diagonal, of Vbar -- so that Sb is never held;
+//   5. C' Pi C by two applications of v - H' (L' v) with a transpose through the image between them; the first one's L' Pi[:, j]
+//      is row j of Pi L, whose row sums against row j of L are diag(L' Pi L), the rest of Vbar;
+//   6. column j of H' sym(Sb) H + sym(Tb H) = H' (y + Tb(j, :)' / 2) + Tb H[:, j] / 2 is added before the column is stored as
+//      row j: Lambda_k.
+// Sigma0_bar leaves from Lambda_0's lower triangle, the off-diagonal entries doubled.  Wbar (lane j's entry) and Vbar stay in
+// registers across the knots.  L_k, Lgain_bar_k, Pest_bar_k and logdet_bar_k are requested one knot ahead, behind the knot's step
+// block, and Zout's knot at the top of the knot before.  A NULL cotangent is a zero that is not read and takes the path of a
+// given one, so its bits are those of explicit zeros.  Compiled for eight measurement rows as k_tracking_kalman: zero rows of H,
+// zero columns of L and Lgain_bar and 1/V = 1 behind ny change no value.  Nothing here divides or factors.
+template <bool kModel, bool kGuard>
+__global__ __launch_bounds__(kWave) void k_tracking_kalman_vjp(BatchParams P, SmootherNoise Nz, const double* __restrict__ Zout,
+                                                               const double* __restrict__ Lg, const double* __restrict__ Hg, int ny,
+                                                               const double* __restrict__ Lbg, const double* __restrict__ Pbg,
+                                                               const double* __restrict__ ldbg, double* __restrict__ S0b,
+                                                               double* __restrict__ Wbg, double* __restrict__ Vbg,
+                                                               const double* __restrict__ model, const double* __restrict__ event) {
+    static_assert(kModel || !kGuard, "the guarded sweep runs on the kModel path");
+    constexpr int NY = QLN_TRACK_NY_MAX;
+    __shared__ double lds[kRows * kVRow];
+    const Row16 r16 = row16_of(P);  // lane 15 shadows column 14 and writes nothing to the image
+    const int ln = r16.ln, j = r16.j, bc = r16.bc, kt = r16.kt, im = r16.im, N = P.N;
+    const bool own = r16.own, valid = r16.valid;
+    const Model Mp = plant_model<kModel>(P, model, bc);
+    const Model& M = kGuard ? Mp : r16.M;
+    const GuardEvent ev = guard_event<kGuard>(event, bc, N);
+    double* L = lds + r16.row * kVRow;
+    const Image15 Lm{L + kVP, j, own};
+    const int gn = QLN_NX * ny;  // a knot's gain entries
+    const double* __restrict__ Zb = Zout + (int64_t)bc * P.z_stride;
+    const double* __restrict__ Lb = Lg + (int64_t)bc * N * gn;
+    const double* __restrict__ Bb = Lbg ? Lbg + (int64_t)bc * N * gn : nullptr;
+    const double* __restrict__ Pb = Pbg ? Pbg + (int64_t)bc * N * QLN_TRACK_P_NNZ : nullptr;
+    const double* __restrict__ lb = ldbg ? ldbg + (int64_t)bc * N : nullptr;
+
+    int po[8], lo[8];
+    packed_offsets(ln, po);
+    gain_offsets(ln, ny, kVL, lo);
+    const auto Hrow = [&](int r, int c) { return L[kVH + 16 * r + c]; };  // H(r, c); 1 / V_r in column 15
+    const auto Lrow = [&](int i, int r) { return L[kVL + NY * i + r]; };  // the gain's L(i, r)
+    const auto Brow = [&](int i, int r) { return L[kVB + NY * i + r]; };  // Lgain_bar(i, r), then Tb(i, r)
+
+    // Lambda = 0 behind the last knot; the two gain tiles zero, so the columns behind ny stay zero; the H tile, zero rows behind ny
+    {
+#pragma unroll
+        for (int t = 0; t < 16; ++t) L[kVP + ln + 16 * t] = 0.0;
+#pragma unroll
+        for (int t = 0; t < (2 * kJTile + 15) / 16; ++t)
+            if (ln + 16 * t < 2 * kJTile) L[kVL + ln + 16 * t] = 0.0;
+#pragma unroll
+        for (int r = 0; r < NY; ++r) L[kVH + 16 * r + ln] = own ? ((r < ny) ? Hg[15 * r + ln] : 0.0) : Nz.iv[r];
+    }
+
+    // a knot's entries ln + 16 t of L, Lgain_bar and Pest_bar and its logdet_bar, requested one knot ahead
+    double zn[2] = {0.0, 0.0}, lq[8], bq[8], pq[8], ldn;
+    auto request = [&](int k) {
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const int g = min(ln + 16 * t, gn - 1);
+            lq[t] = Lb[(int64_t)k * gn + g];
+            bq[t] = Bb ? Bb[(int64_t)k * gn + g] : 0.0;
+            pq[t] = Pb ? Pb[(int64_t)k * QLN_TRACK_P_NNZ + min(ln + 16 * t, QLN_TRACK_P_NNZ - 1)] : 0.0;
+        }
+        ldn = lb ? lb[k] : 0.0;
+    };
+    request(N - 1);
+    wave_lds_sync();
+
+    double wbar = 0.0, vbar[NY];
+#pragma unroll
+    for (int r = 0; r < NY; ++r) vbar[r] = 0.0;
+
+    for (int k = N - 1; k >= 0; --k) {
+        const bool last = k == N - 1;  // the last knot has an update and no step
+        tile_fill(L, lo, gn, tile_lane(ln), [&](int t) { return lq[t]; });
+        tile_fill(L + (kVB - kVL), lo, gn, tile_lane(ln), [&](int t) { return bq[t]; });
+        if (!last) {
+            L[kVZ + ln] = zn[0];
+            if (ln < 4) L[kVZ + 16 + ln] = zn[1];
+        }
+        if (k > 0) knot_load(Zb + 20 * (k - 1), ln, zn[0], zn[1]);
+        wave_lds_sync();  // the knot and the two tiles are in place
+
+        // ---- 1. Wbar and Pi = A_k' Lambda A_k ----
+        if (!last) {
+            wbar += Lm.a[(kImgStr + 1) * j];
+            KnotMode md;
+            if constexpr (kGuard) md = guard_mode(k, ev.ks, im);
+            else md = knot_mode(k + 1, kt - 1, im);
+            if (kGuard && k == ev.ks) {  // the touchdown knot: the composite operator, transposed, in the block's place
+                const TouchdownBlock tb = touchdown_block_at(L + kVZ, M, md, ev.tau);
+                congruence(
+                    Lm,
+                    [&](const double (&v)[15], double (&out)[15]) {
+                        double bf[4];
+                        touchdown_apply_t(tb, M, v, out, bf);
+                    },
+                    [] {});
+            } else {
+                const StepBlock blk = step_block(L + kVZ, md, M);
+                congruence(Lm, [&](const double (&v)[15], double (&out)[15]) { block_apply_t(blk, v, out); }, [] {});
+            }
+            wave_lds_sync();
+        }
+        // ---- 2. Pi += sym(Pest_bar_k), into the lower triangle; a diagonal entry lies at a multiple of kImgStr + 1 ----
+        {
+            const TileLane tl = tile_lane(ln);
+#pragma unroll
+            for (int t = 0; t < 8; ++t)
+                if (tl.le + 16 * t < QLN_TRACK_P_NNZ) {
+                    const double half = (po[t] % (kImgStr + 1) == 0) ? 1.0 : 0.5;
+                    Lm.a[po[t]] = fma(half, pq[t], Lm.a[po[t]]);
+                }
+        }
+        const double ldb = ldn;
+        if (k > 0) request(k - 1);
+        wave_lds_sync();
+
+        // ---- 3. and 4. Tb's row j, sym(Sb) and what hangs on it ----
+        double hj[NY], lj[NY], tb[NY], y[NY];
+#pragma unroll
+        for (int r = 0; r < NY; ++r) {
+            hj[r] = Hrow(r, j);
+            lj[r] = Lrow(j, r);  // row j of L
+            y[r] = 0.0;
+        }
+        {
+            double lbj[NY], w[15];
+#pragma unroll
+            for (int r = 0; r < NY; ++r) lbj[r] = Brow(j, r);
+            chain_rows(Lrow, lbj, w);                                             // lb L'
+            chain_rows_sub([&](int a, int i) { return Hrow(a, i); }, w, lbj, tb);  // lb - (lb L') H'
+            double q[NY];  // Tb(j, :) + logdet_bar H(:, j)' ./ V: the row sums of L(j, a) q[b] are (L' Tb + logdet_bar (H L)' / V)(a, b)
+#pragma unroll
+            for (int r = 0; r < NY; ++r) {
+                tb[r] *= Hrow(r, 15);
+                q[r] = fma(ldb * Hrow(r, 15), hj[r], tb[r]);
+            }
+            if (own) {
+#pragma unroll
+                for (int r = 0; r < NY; ++r) L[kVB + NY * j + r] = tb[r];
+            }
+#pragma unroll
+            for (int a = 0; a < NY; ++a) {
+#pragma unroll
+                for (int b = 0; b < a; ++b) {
+                    const double s = row_sum16(own ? -0.5 * fma(lj[a], q[b], lj[b] * q[a]) : 0.0);
+                    y[a] = fma(s, hj[b], y[a]);
+                    y[b] = fma(s, hj[a], y[b]);
+                }
+                const double s = fma(ldb, Hrow(a, 15), row_sum16(own ? -(lj[a] * q[a]) : 0.0));
+                vbar[a] += s;
+                y[a] = fma(s, hj[a], y[a]);
+            }
+        }
+        // ---- 5. C' Pi C, and 6. the sources ----
+        const auto Lt = [&](int a, int c) { return Lrow(c, a); };  // L'
+        const auto Ht = [&](int i, int a) { return Hrow(a, i); };  // H'
+        {
+            double p[15], u[15], t[NY];
+            Lm.column(p);
+            chain_rows(Lt, p, t);  // row j of Pi L
+#pragma unroll
+            for (int a = 0; a < NY; ++a) vbar[a] += row_sum16(own ? lj[a] * t[a] : 0.0);
+            chain_rows_sub(Ht, t, p, u);  // column j of C' Pi -> row j of the image
+            wave_lds_sync();              // every lane holds its column of Pi; the Tb tile is in place
+            Lm.store_row(u);
+        }
+        wave_lds_sync();
+        {
+            double vt[15], t[NY], out[15], z[NY], s1[15], s2[15];
+            Lm.transposed(vt);
+            chain_rows(Lt, vt, t);
+            chain_rows_sub(Ht, t, vt, out);  // column j of C' Pi C
+#pragma unroll
+            for (int a = 0; a < NY; ++a) z[a] = fma(0.5, tb[a], y[a]);
+            chain_rows(Ht, z, s1);    // H' (y + Tb(j, :)' / 2)
+            chain_rows(Brow, hj, s2);  // Tb H[:, j]
+#pragma unroll
+            for (int i = 0; i < 15; ++i) out[i] += fma(0.5, s2[i], s1[i]);
+            wave_lds_sync();  // every lane holds its row: Lambda_k may overwrite the image
+            Lm.store_row(out);
+        }
+        wave_lds_sync();  // only the lower triangle of Lambda_k is read from here on; the tiles and the knot may be rewritten
+    }
+
+    if (S0b && valid)
+        tile_store(S0b + (int64_t)bc * QLN_TRACK_P_NNZ, po, QLN_TRACK_P_NNZ, tile_lane(ln),
+                   [&](int o) { return (o % (kImgStr + 1) == 0) ? Lm.a[o] : 2.0 * Lm.a[o]; });
+    if (Wbg && valid && own) Wbg[(int64_t)bc * QLN_NX + j] = wbar;
+    if (Vbg && valid) {
+        double v = vbar[0];
+#pragma unroll
+        for (int q = 1; q < NY; ++q) v = (ln == q) ? vbar[q] : v;
+        if (ln < ny) Vbg[(int64_t)bc * ny + ln] = v;
+    }
+}
+
+
 // ---- k_tracking_rollout_jvp ----
 // One knot's inputs, as lane ln of a row loads them.  z0 / zd0: entry ln of the knot's twenty in Zout / Zref_dot (lane
 // j < 15: x_j, lane 15: F1x); z1 / zd1: entry 16 + (ln & 3) (F1y, F2x, F2y, h in lanes 0-3).  xr: x_ref,j; kc, kd: column j
@@ -3692,6 +3915,25 @@ hipError_t launch_tracking_kalman_jvp(const BatchParams& p, const double* Zout, 
     };
     if (event) go(k_tracking_kalman_jvp<true, true>);
     else go(k_tracking_kalman_jvp<false, false>);
+    return hipGetLastError();
+}
+
+// The two instantiations of k_tracking_kalman_vjp: event or the knot schedule (model is read with event only, as above).
+hipError_t launch_tracking_kalman_vjp(const BatchParams& p, const double* Zout, const double* model, const double* event,
+                                      const double* Lgain, const double* H, int ny, const double* Vd, const double* Lgain_bar,
+                                      const double* Pest_bar, const double* logdet_bar, double* Sigma0_bar, double* Wdiag_bar,
+                                      double* Vdiag_bar, hipStream_t stream) {
+    if (ny < 1 || ny > QLN_TRACK_NY_MAX || !Zout || !Lgain || !H || !Vd) return hipErrorInvalidValue;
+    if (!Lgain_bar && !Pest_bar && !logdet_bar) return hipErrorInvalidValue;
+    if (!Sigma0_bar && !Wdiag_bar && !Vdiag_bar) return hipErrorInvalidValue;
+    SmootherNoise nz;
+    for (int r = 0; r < QLN_TRACK_NY_MAX; ++r) nz.iv[r] = r < ny ? 1.0 / Vd[r] : 1.0;
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(row16_grid(p.B)), dim3(kWave), 0, stream, p, nz, Zout, Lgain, H, ny, Lgain_bar, Pest_bar,
+                           logdet_bar, Sigma0_bar, Wdiag_bar, Vdiag_bar, model, event);
+    };
+    if (event) go(k_tracking_kalman_vjp<true, true>);
+    else go(k_tracking_kalman_vjp<false, false>);
     return hipGetLastError();
 }
 

@@ -1279,6 +1279,92 @@ class HybridNLP:
                    + T.einsum("bkr,bkrs,bks->bk", iv, Sinv_dot, iv))
         return -0.5 * (nis_dot + d["logdet"]).sum(dim=1), nis_dot, d["logdet"]
 
+    # -- the reverse sweep through the filter's design ---------------------------------------------------
+    KALMAN_VJP_OUT = ("Sigma0", "W", "V")
+
+    def _op_kalman_vjp(self, f, guarded, Zout, events, Lgain, H, V, Lgain_bar, Pest_bar, logdet_bar, model, want, reduce):
+        """One path for the four forms.  Returns a dict of the outputs asked for (want None: all three)."""
+        Hh, Vh = measurement_model(H, V)
+        ny = Hh.shape[0]
+        want = self.KALMAN_VJP_OUT if want is None else tuple(want)
+        bad = set(want) - set(self.KALMAN_VJP_OUT)
+        if bad:
+            raise ValueError(f"want: unknown outputs {sorted(bad)} ({', '.join(self.KALMAN_VJP_OUT)})")
+        if not want:
+            raise ValueError(f"want: at least one of {', '.join(self.KALMAN_VJP_OUT)}")
+        if Lgain is None:
+            raise ValueError(f"Lgain is required: the gains tracking_kalman{f.suffix} returned for (Zout, H, V)")
+        if Lgain_bar is None and Pest_bar is None and logdet_bar is None:
+            raise ValueError("a cotangent is required: at least one of Lgain_bar, Pest_bar and logdet_bar")
+        B, N = self.B, self.N
+        Zout = f.Z(Zout, "Zout")
+        Lgain = f.arr(Lgain, B * N * n * ny, "Lgain")
+        Lb = f.opt(Lgain_bar, B * N * n * ny, "Lgain_bar")
+        Pb = f.opt(Pest_bar, B * N * _lib.TRACK_P_NNZ, "Pest_bar")
+        lb = f.opt(logdet_bar, B * N, "logdet_bar")
+        Hd = f.H(Hh)
+        shapes = dict(Sigma0=(B, _lib.TRACK_P_NNZ), W=(B, n), V=(B, ny))
+        res = {k: f.empty(shapes[k]) for k in self.KALMAN_VJP_OUT if k in want}
+        extra = ()
+        if guarded:
+            events, model = f.events(events), f.model(model)
+            extra = (f.ptr(model), f.ptr(events))
+        _lib.check(f.fn("qln_noise_design" + ("_guarded" if guarded else "") + "_vjp")(
+            self._h, f.ptr(Zout), *extra, f.ptr(Lgain), f.ptr(Hd), ny, Vh.ctypes.data, f.ptr(Lb), f.ptr(Pb), f.ptr(lb),
+            *(f.ptr(res.get(k)) for k in self.KALMAN_VJP_OUT)))
+        if reduce:
+            for k in ("W", "V"):
+                if k in res:
+                    res[k] = res[k].sum(0)
+        return res
+
+    def tracking_kalman_vjp(self, Zout, Lgain, H, V, Lgain_bar=None, Pest_bar=None, logdet_bar=None, events=None, model=None,
+                            guarded=False, want=None, reduce=False):
+        """Reverse sweep through the design of tracking_kalman (guarded: of tracking_kalman_guarded, at events and model): the
+        transpose of tracking_kalman_jvp's map between the arrays as stored (qln_noise_design_vjp), at the gains Lgain the design
+        returned for (Zout, H, V).  The cotangents Lgain_bar (B, N, 15, ny), Pest_bar (B, N, 120) packed and logdet_bar (B, N), of
+        any sign, each optional (None: zero), at least one.  want: the outputs by name, of Sigma0 (B, 120) packed, W (B, 15) and V
+        (B, ny), per problem; default all.  reduce: W and V summed over the batch, (15,) and (ny,), as tracking_kalman_jvp shares
+        W_dot and V_dot over it.  With the packed convention of the header, <cotangents, tracking_kalman_jvp's outputs> =
+        <these, its direction> over the stored arrays.  Returns a dict of device tensors; which are asked for changes no other's
+        bits.  Stream-ordered."""
+        return self._op_kalman_vjp(_DeviceForm(self), guarded, Zout, events, Lgain, H, V, Lgain_bar, Pest_bar, logdet_bar, model,
+                                   want, reduce)
+
+    def tracking_kalman_vjp_host(self, Zout, Lgain, H, V, Lgain_bar=None, Pest_bar=None, logdet_bar=None, events=None, model=None,
+                                 guarded=False, want=None, reduce=False):
+        """The same with host arrays (synchronous): a dict of numpy arrays."""
+        return self._op_kalman_vjp(_HostForm(self), guarded, Zout, events, Lgain, H, V, Lgain_bar, Pest_bar, logdet_bar, model,
+                                   want, reduce)
+
+    def landing_loglik_grad(self, Zout, Zref, Zrec, Lgain, H, V, Xhat, innov, events=None, model=None, guarded_design=False,
+                            events_hat=None, guarded=False, filter_model=None):
+        """The gradient of each record's landing_filter log-likelihood with respect to the design's noise (Sigma0, W, V), through
+        the gains' design, in one filter sweep and one design sweep, both reverse -- landing_loglik_jvp's arguments without the
+        direction, and its value along any direction is the inner product with this:
+            innov_bar_k  = -1/2 (Sinv + Sinv') innov_k,   Sinv = diag(1/V) (I - H L_k)     -> landing_filter_vjp, asking for Lgain
+            Lgain_bar_k += 1/2 H' (innov_k ./ V) innov_k'                                   (nis reads L_k itself)
+            tracking_kalman_vjp(Lgain_bar, logdet_bar = -1/2)                               -> Sigma0, W, V per record
+            V[a]        += 1/2 sum_k innov_k[a] ((I - H L_k) innov_k)[a] / V_a^2            (nis reads V itself)
+        Device tensors in; returns a dict of device tensors Sigma0 (B, 120) packed (an off-diagonal entry is the derivative along
+        both of its sides), W (B, 15) and V (B, ny), per record."""
+        T = _torch()
+        Hh, Vh = measurement_model(H, V)
+        ny = Hh.shape[0]
+        dev = self._dev()
+        Ht, Vt = T.from_numpy(np.array(Hh)).to(dev), T.from_numpy(np.array(Vh)).to(dev)
+        L, iv = Lgain.reshape(self.B, self.N, n, ny), innov.reshape(self.B, self.N, ny)
+        G = T.eye(ny, dtype=T.float64, device=dev) - T.einsum("ri,bkis->bkrs", Ht, L)  # I - H L
+        Sinv = G / Vt[:, None]
+        innov_bar = -0.5 * T.einsum("bkrs,bks->bkr", Sinv + Sinv.transpose(-1, -2), iv).contiguous()
+        s = self.landing_filter_vjp(Zref, Zrec, Lgain, H, Xhat, innov=innov, model=filter_model, events_hat=events_hat,
+                                    guarded=guarded, innov_bar=innov_bar, want=("Lgain",))
+        Lb = (s["Lgain"].reshape(self.B, self.N, n, ny) + 0.5 * T.einsum("ri,bkr,bks->bkis", Ht, iv / Vt, iv)).contiguous()
+        lb = T.full((self.B, self.N), -0.5, dtype=T.float64, device=dev)
+        g = self.tracking_kalman_vjp(Zout, Lgain, H, V, Lb, None, lb, events, model, guarded_design)
+        g["V"] = g["V"] + 0.5 * (iv * T.einsum("bkrs,bks->bkr", G, iv)).sum(dim=1) / (Vt * Vt)
+        return g
+
     # -- the fixed-interval smoother: the estimator's backward pass ------------------------------------
     def _op_smoother(self, f, guarded, Ztraj, events, Lgain, Pest, H, V, Xhat, innov, model, with_states, with_cov):
         Hh, Vh = measurement_model(H, V)
