@@ -7,13 +7,13 @@ call; the host forms have the bits of the device forms; the smoother takes the r
 landings flown by the library are scored: the mean normalised innovation squared is 8 at every knot, and the summed
 log-likelihood is largest at the V the sensors had."""
 import ctypes as C
-import faulthandler
 import functools
 import itertools
 
 import numpy as np
 import pytest
 
+from tests import estimation_cases as EF
 from tests import landing_filter_ref as FR
 from tests import rollout_estimated_cases as EC
 from tests import rollout_guarded_cases as GC
@@ -23,6 +23,7 @@ from tests import tracking_cases as TC
 from tests import tracking_cov_ref as CR
 
 pytestmark = pytest.mark.gpu
+_time_limit = EF.time_limit(600)
 
 BAR = 1e-10  # the family's bar (tests/test_gpu_tracking_estimated.py)
 LIM = LR.TEST_LIMITS
@@ -35,20 +36,6 @@ GUARDED = [("shape", 24, 2, 0, 1, 3), ("shape", 32, 5, 0, 2, 8), ("shape", 48, 8
            ("ragged", 70, 12, 0, 0, 3)]
 ALL = [(False,) + c for c in SCHEDULED] + [(True,) + c for c in GUARDED]
 IDS = [f"{'guarded' if c[0] else 'scheduled'}-{c[1]}-B{c[2]}-N{c[3]}-ny{c[6]}" for c in ALL]
-
-
-@pytest.fixture(autouse=True)
-def _time_limit():
-    """Every test here is a GPU step with a time limit of its own: a hang ends the process with a traceback."""
-    faulthandler.dump_traceback_later(600, exit=True)
-    yield
-    faulthandler.cancel_dump_traceback_later()
-
-
-def _dev(a):
-    import torch
-
-    return a if a is None or hasattr(a, "detach") else torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 @functools.lru_cache(maxsize=None)
@@ -78,12 +65,17 @@ def _case(guarded, kind, B, N, kt, im, ny):
     return dict(nlp=nlp, raw=raw, Zn=Zn, zn=zn, x0=x0, xhat0=zn[:, :15] + d["dxhat0"], th=th, K=K, d=d, guarded=guarded, ny=ny)
 
 
+def _gains(Lgain):
+    """Filter gains on the device: drawn ones are host arrays, the GPU's own tracking_kalman*'s are there already."""
+    return Lgain if hasattr(Lgain, "detach") else EF.dev(Lgain)
+
+
 def _fly(c, K, Lgain, xhat0, limits=None, Zref=None, plain=False):
     """One flight of the case's plant: (Zout, Xhat, innov, events_hat or None)."""
     nlp, d = c["nlp"], c["d"]
     Zref = c["Zn"] if Zref is None else Zref
-    x0, model, w = (None, None, None) if plain else (_dev(c["x0"]), _dev(c["th"]), _dev(d["wnoise"]))
-    args = (_dev(K), _dev(Lgain), d["H"], _dev(d["vnoise"]), w, x0, _dev(xhat0), model)
+    x0, model, w = (None, None, None) if plain else (EF.dev(c["x0"]), EF.dev(c["th"]), EF.dev(d["wnoise"]))
+    args = (EF.dev(K), _gains(Lgain), d["H"], EF.dev(d["vnoise"]), w, x0, EF.dev(xhat0), model)
     if limits is None:
         out = nlp.tracking_rollout_estimated(Zref, *args, guarded=c["guarded"], with_innovations=True)
         return out[0], out[1], out[2], out[4] if c["guarded"] else None
@@ -94,7 +86,7 @@ def _fly(c, K, Lgain, xhat0, limits=None, Zref=None, plain=False):
 
 def _filter(c, Zref, Zrec, Lgain, Y, V=None, xhat0=None, **kw):
     f = c["nlp"].landing_filter_guarded if c["guarded"] else c["nlp"].landing_filter
-    out = f(Zref, Zrec, Lgain if hasattr(Lgain, "detach") else _dev(Lgain), c["d"]["H"], Y, V, _dev(xhat0), **kw)
+    out = f(Zref, Zrec, _gains(Lgain), c["d"]["H"], Y, V, EF.dev(xhat0), **kw)
     return out if c["guarded"] else out + (None,)
 
 
@@ -157,7 +149,7 @@ def _closed(guarded, kind, B, N, kt, im, ny):
     c = _case(guarded, kind, B, N, kt, im, ny)
     nlp, d = c["nlp"], c["d"]
     Zout, Xhat, innov, eh = _fly(c, c["K"], d["Lgain"], c["xhat0"])
-    Y = nlp.landing_measurements(Zout, c["Zn"], d["H"], _dev(d["vnoise"]))
+    Y = nlp.landing_measurements(Zout, c["Zn"], d["H"], EF.dev(d["vnoise"]))
     V = np.full(ny, 1e-2)
     ref = FR.replay(N, nlp.init_mode, c["zn"], TC.rows(nlp, Zout), d["Lgain"], d["H"], Y.cpu().numpy(), TC.SECOND, V, c["xhat0"],
                     nlp.k_trans, guarded)
@@ -222,7 +214,7 @@ def test_three_rows_are_eight_rows_with_the_zero_rows_and_columns_written_out(gu
     Y8 = torch.zeros((B, N, 8), dtype=torch.float64, device="cuda")
     Y8[..., :3] = Y
     f = c["nlp"].landing_filter_guarded if guarded else c["nlp"].landing_filter
-    b = f(c["Zn"], Zout, _dev(L8), H8, Y8, V8, _dev(c["xhat0"]))
+    b = f(c["Zn"], Zout, EF.dev(L8), H8, Y8, V8, EF.dev(c["xhat0"]))
     assert _equal(a[0], b[0]) and _equal(a[1], b[1][..., :3].contiguous()) and not bool(b[1][..., 3:].any())
     assert _equal(a[2], b[2]) and (not guarded or _equal(a[4], b[4]))
     # loglik counts its measurements: the five rows written out are five more readings of value zero under N(0, 1) a knot, each
@@ -243,7 +235,7 @@ def test_every_subset_of_outputs_has_the_bits_of_the_full_call(guarded, kind, B,
     nlp, d = c["nlp"], c["d"]
     full = _filter(c, c["Zn"], Zout, d["Lgain"], Y, V, c["xhat0"])
     full = full if guarded else full[:4]
-    t = dict(L=_dev(d["Lgain"]), H=_dev(d["H"]), x=_dev(c["xhat0"]))
+    t = dict(L=EF.dev(d["Lgain"]), H=EF.dev(d["H"]), x=EF.dev(c["xhat0"]))
     p = lambda a: None if a is None else C.c_void_p(a.data_ptr())  # noqa: E731
     fn = _lib.lib().qln_landing_filter_guarded if guarded else _lib.lib().qln_landing_filter
     for asked in itertools.product((False, True), repeat=len(full)):
@@ -267,14 +259,14 @@ def test_host_forms_give_the_device_forms_bits_after_other_host_calls_left_nans_
         d = EC.draws(B + ny, B, N, ny)
         V = np.full(ny, 1e-3)
         xhat0 = TC.rows(nlp, Zn)[:, :15] + d["dxhat0"]
-        Zout = nlp.tracking_rollout_estimated(Zn, _dev(K), _dev(d["Lgain"]), d["H"], _dev(d["vnoise"]), None, _dev(x0), _dev(xhat0),
-                                              _dev(th), guarded=guarded)[0]
-        Y = nlp.landing_measurements(Zout, Zn, d["H"], _dev(d["vnoise"]))
+        Zout = nlp.tracking_rollout_estimated(Zn, EF.dev(K), EF.dev(d["Lgain"]), d["H"], EF.dev(d["vnoise"]), None, EF.dev(x0), EF.dev(xhat0),
+                                              EF.dev(th), guarded=guarded)[0]
+        Y = nlp.landing_measurements(Zout, Zn, d["H"], EF.dev(d["vnoise"]))
         with np.errstate(all="ignore"):  # the roles this call reads and writes now hold NaN
             nlp.landing_filter_guarded_host(nan(*zn.shape), nan(*zn.shape), nan(B, N, 15, 8), np.ones((8, 15)), nan(B, N, 8), 1.0,
                                             nan(B, 15))
         f, fh = (nlp.landing_filter_guarded, nlp.landing_filter_guarded_host) if guarded else (nlp.landing_filter, nlp.landing_filter_host)
-        dev = f(Zn, Zout, _dev(d["Lgain"]), d["H"], Y, V, _dev(xhat0))
+        dev = f(Zn, Zout, EF.dev(d["Lgain"]), d["H"], Y, V, EF.dev(xhat0))
         for _ in range(2):
             host = fh(zn, Zout.cpu().numpy(), d["Lgain"], d["H"], Y.cpu().numpy(), V, xhat0)
             for dv, h in zip(dev, host):
@@ -303,9 +295,9 @@ def _scored(guarded, V):
     else:
         L = nlp.tracking_kalman(c["Zn"], d["H"], Vd, None, S0, W)[0]
     x0 = c["zn"][:, :15] + 1e-4 * rng.normal(size=(B, 15))
-    Zout = nlp.tracking_rollout_estimated(c["Zn"], _dev(c["K"]), L, d["H"], _dev(v), None, _dev(x0), None, _dev(c["th"]),
+    Zout = nlp.tracking_rollout_estimated(c["Zn"], EF.dev(c["K"]), L, d["H"], EF.dev(v), None, EF.dev(x0), None, EF.dev(c["th"]),
                                           guarded=guarded)[0]
-    Y = nlp.landing_measurements(Zout, c["Zn"], d["H"], _dev(v))
+    Y = nlp.landing_measurements(Zout, c["Zn"], d["H"], EF.dev(v))
     got = _filter(c, c["Zn"], Zout, L, Y, Vd)
     a = (N, nlp.init_mode, c["zn"], TC.rows(nlp, Zout), L.cpu().numpy(), d["H"], Y.cpu().numpy(), TC.SECOND, Vd, None, nlp.k_trans, guarded)
     return got, FR.replay(*a), FR.replay(*a, dtype=np.longdouble)
@@ -344,14 +336,14 @@ def test_4096_flown_landings_score_as_chi_squared_and_prefer_the_sensors_own_var
     H, V = EC.sensors(), np.full(8, sd * sd)
     S0, dx0, v, w, _, _ = EC.mc_draws(seed, N, sd, W)
     x0 = np.asarray(nb.Z, dtype=np.float64)[:, :15].copy()
-    Zn = one.tracking_rollout(one.upload_Z(nb.Z), None, _dev(x0))
+    Zn = one.tracking_rollout(one.upload_Z(nb.Z), None, EF.dev(x0))
     K, _ = one.tracking_lqr(Zn, EC.Q, EC.R, EC.Q, with_cost_to_go=False)
     tile = lambda t: t.expand(S, *t.shape[1:]).contiguous()  # noqa: E731
     gains = lambda Vs: tile(one.tracking_kalman(Zn, H, Vs, K, S0, W, with_sigma=False, with_marginals=False)[0])  # noqa: E731
     Zt = many.upload_Z(np.tile(TC.rows(one, Zn)[0], (S, 1)))
     L = gains(V)
-    Zout, Xhat, innov = many.tracking_rollout_estimated(Zt, tile(K), L, H, _dev(v), _dev(w), _dev(x0 + dx0), with_innovations=True)
-    Y = many.landing_measurements(Zout, Zt, H, _dev(v))
+    Zout, Xhat, innov = many.tracking_rollout_estimated(Zt, tile(K), L, H, EF.dev(v), EF.dev(w), EF.dev(x0 + dx0), with_innovations=True)
+    Y = many.landing_measurements(Zout, Zt, H, EF.dev(v))
     xh, iv, sc, ll = many.landing_filter(Zt, Zout, L, H, Y, V)
     torch.cuda.synchronize()
     assert RR.rel(xh.cpu().numpy(), Xhat.cpu().numpy()) <= BAR and RR.rel(iv.cpu().numpy(), innov.cpu().numpy()) <= BAR
@@ -403,7 +395,7 @@ def test_overlaps_and_null_trajectories_are_refused():
     Lb, h, INV, OK = _lib.lib(), nlp._h, _lib.QLN_ERR_INVALID_ARGUMENT, _lib.QLN_OK
     B, N, ny = nlp.B, nlp.N, c["ny"]
     f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device="cuda")  # noqa: E731
-    Ld, Hd, xd = _dev(d["Lgain"]), _dev(d["H"]), _dev(c["xhat0"])
+    Ld, Hd, xd = EF.dev(d["Lgain"]), EF.dev(d["H"]), EF.dev(c["xhat0"])
     Xo, io, so, lo = f64(B, N, 15), f64(B, N, ny), f64(B, N, 2), f64(B)
     p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
     call = lambda Xh, iv, sc, ll, Zref=c["Zn"], Zrec=Zout: Lb.qln_landing_filter(  # noqa: E731

@@ -6,13 +6,13 @@ eight sensor rows with zeros written out, by every subset of optional outputs, b
 by central differences of the GPU's own filter, through torch autograd, and by the refusals through the device entries.  The
 cases and their seeds are the yardstick module's."""
 import ctypes as C
-import faulthandler
 import functools
 import itertools
 
 import numpy as np
 import pytest
 
+from tests import estimation_cases as EF
 from tests import landing_filter_sweep_ref as FS
 from tests import rollout_estimated_sweep_ref as ES
 from tests import rollout_guarded_cases as GC
@@ -20,6 +20,7 @@ from tests import rollout_ref as RR
 from tests import tracking_cases as TC
 
 pytestmark = pytest.mark.gpu
+_time_limit = EF.time_limit(300)
 
 BAR = 1e-10         # the filter's bar (tests/test_gpu_landing_filter.py)
 SWEEP_BAR = 1e-12   # the project's bar for a sweep against numpy, of max(1, |ref|) (tests/test_gpu_rollout_guarded_sweeps.py)
@@ -43,26 +44,12 @@ FD_CPU_WORST = 8.53e-10
 FD_BAR = 10 * FD_CPU_WORST
 
 
-@pytest.fixture(autouse=True)
-def _time_limit():
-    """Every test here is a GPU step with a time limit of its own: a hang ends the process with a traceback."""
-    faulthandler.dump_traceback_later(300, exit=True)
-    yield
-    faulthandler.cancel_dump_traceback_later()
-
-
-def _dev(a):
-    import torch
-
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).cuda()
-
-
 def _np(t):
     return None if t is None else t.cpu().numpy()
 
 
 def _upload(nlp, d):
-    return {k: (nlp.upload_Z(v) if k in ("Zrec_dot", "Zref", "Zrec") else _dev(v)) for k, v in d.items()}
+    return {k: (nlp.upload_Z(v) if k in ("Zrec_dot", "Zref", "Zrec") else EF.dev(v)) for k, v in d.items()}
 
 
 def _filter(nlp, d, guarded, model="own", score=True, **replace):
@@ -157,11 +144,11 @@ def test_without_a_model_and_with_the_handles_values_written_out_the_filter_has_
     r = _run(guarded, N, im, kt, B, ny)
     nlp, d = r["nlp"], r["d"]
     old = _filter(nlp, d, guarded, model=None)
-    written = _filter(nlp, d, guarded, model=_dev(np.tile(TC.SECOND, (B, 1))))
+    written = _filter(nlp, d, guarded, model=EF.dev(np.tile(TC.SECOND, (B, 1))))
     for a, b in zip(old, written):
         assert (a is None and b is None) or torch.equal(a, b)
     # the _model entry with model == NULL, which the Python layer never calls
-    Hd, Vh = _dev(d["H"]), np.ascontiguousarray(d["V"])
+    Hd, Vh = EF.dev(d["H"]), np.ascontiguousarray(d["V"])
     outs = [torch.zeros_like(t) for t in old if t is not None]
     ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     fn = getattr(_lib.lib(), "qln_landing_filter_guarded_model" if guarded else "qln_landing_filter_model")
@@ -236,14 +223,14 @@ def test_on_a_flights_record_the_sweeps_are_bitwise_the_estimators_chain_of_the_
     batch, inp = ES.case(N, im, kt, B, ny, guarded)
     nlp = TC.nlp(batch, TC.SECOND_MODEL)
     Zref = nlp.upload_Z(inp["Zref"])
-    dv = {k: _dev(inp[k]) for k in ("K", "Lgain", "vnoise", "wnoise", "x0", "xhat0", "model")}
+    dv = {k: EF.dev(inp[k]) for k in ("K", "Lgain", "vnoise", "wnoise", "x0", "xhat0", "model")}
     flown = nlp.tracking_rollout_estimated(Zref, dv["K"], dv["Lgain"], inp["H"], dv["vnoise"], dv["wnoise"], dv["x0"], dv["xhat0"],
                                            dv["model"], guarded=guarded, with_innovations=True)
     Zout, Xhat, innov = flown[:3]
     ev, eh = (flown[3], flown[4]) if guarded else (None, None)
     dirs, cot = FS.directions(5, B, N, ny)
-    xd, ld = _dev(dirs["xhat0_dot"]), _dev(dirs["Lgain_dot"])
-    Xb, Ib = _dev(cot["Xhat_bar"]), _dev(cot["innov_bar"])
+    xd, ld = EF.dev(dirs["xhat0_dot"]), EF.dev(dirs["Lgain_dot"])
+    Xb, Ib = EF.dev(cot["Xhat_bar"]), EF.dev(cot["innov_bar"])
     p = dict(Zref=Zref, Zrec=Zout, Lgain=dv["Lgain"], H=inp["H"], V=None, Xhat=Xhat, innov=innov, model=None, events_hat=eh)
     for with_l in (True, False):
         mine = _jvp(nlp, p, guarded, dict(xhat0_dot=xd, **({"Lgain_dot": ld} if with_l else {})), score=False)
@@ -273,8 +260,8 @@ def test_three_sensor_rows_are_bitwise_eight_rows_with_zeros(guarded, N, im, kt,
     d["H"], d["V"] = rec["H"], rec["V"]
     p = _point(d, _filter(nlp, d, guarded))
     pad = lambda a, axis: np.concatenate([a, np.zeros(a.shape[:axis] + (5,) + a.shape[axis + 1:])], axis=axis)  # noqa: E731
-    p8 = dict(p, Lgain=_dev(pad(rec["Lgain"], 3)), H=pad(rec["H"], 0), V=np.concatenate([rec["V"], np.ones(5)]),
-              innov=_dev(pad(_np(p["innov"]), 2)))
+    p8 = dict(p, Lgain=EF.dev(pad(rec["Lgain"], 3)), H=pad(rec["H"], 0), V=np.concatenate([rec["V"], np.ones(5)]),
+              innov=EF.dev(pad(_np(p["innov"]), 2)))
     dirs, cot = FS.directions(6, B, N, 3)
     dirs8 = dict(dirs, Lgain_dot=pad(dirs["Lgain_dot"], 3), Y_dot=pad(dirs["Y_dot"], 2))
     cot8 = dict(cot, innov_bar=pad(cot["innov_bar"], 2))
@@ -431,13 +418,13 @@ def test_central_differences_of_the_gpus_own_filter_in_the_model_and_the_measure
         nlp = TC.nlp(batch, TC.SECOND_MODEL)
         d = _upload(nlp, {k: rec[k] for k in ("Zref", "Zrec", "Lgain", "Y", "xhat0", "model")})
         d["H"], d["V"] = rec["H"], rec["V"]
-        run = lambda s: _filter(nlp, d, guarded, model=_dev(at(s)["model"]), Y=_dev(at(s)["Y"]))  # noqa: E731
+        run = lambda s: _filter(nlp, d, guarded, model=EF.dev(at(s)["model"]), Y=EF.dev(at(s)["Y"]))  # noqa: E731
         g0, gp, gm = run(0.0), run(FD_EPS), run(-FD_EPS)
         if guarded:
             assert bool((gp[4][:, 0] == g0[4][:, 0]).all()) and bool((gm[4][:, 0] == g0[4][:, 0]).all()) and bool((g0[4][:, 0] >= 0).any())
         names = dict(Xhat=0, innov=1, loglik=3)
         qg = _quotients({k: _np(gm[i]) for k, i in names.items()}, {k: _np(gp[i]) for k, i in names.items()}, FD_EPS)
-        got = _jvp(nlp, _point(d, g0), guarded, dict(Y_dot=_dev(yd), model_dot=_dev(md)))
+        got = _jvp(nlp, _point(d, g0), guarded, dict(Y_dot=EF.dev(yd), model_dot=EF.dev(md)))
         w = {k: FS.worst(qg[k], _np(got[k])) for k in qg}
         gpu_worst = max(gpu_worst, *w.values())
         print(f"guarded={guarded}: the GPU's quotient against its forward sweep {w}")
@@ -527,7 +514,7 @@ def _overlap_jvp(nlp, p, guarded, dirs):
     """Xhat_dot on top of Xhat, through the C entry"""
     from quadruped_landing_amd import _lib
 
-    Hd = _dev(p["H"])
+    Hd = EF.dev(p["H"])
     ev = (_ptr(p["events_hat"]),) if guarded else ()
     fn = getattr(_lib.lib(), "qln_landing_filter_guarded_jvp" if guarded else "qln_landing_filter_jvp")
     _lib.check(fn(nlp._h, _ptr(p["Zref"]), _ptr(p["Zrec"]), _ptr(p["Lgain"]), _ptr(Hd), Hd.shape[0], _ptr(p["model"]), None,
@@ -541,7 +528,7 @@ def _overlap_vjp(nlp, p, guarded, cot):
 
     from quadruped_landing_amd import _lib
 
-    Hd = _dev(p["H"])
+    Hd = EF.dev(p["H"])
     ev = (_ptr(p["events_hat"]),) if guarded else ()
     yb = torch.zeros(p["innov"].numel() + 15 * nlp.B, dtype=torch.float64, device="cuda")
     fn = getattr(_lib.lib(), "qln_landing_filter_guarded_vjp" if guarded else "qln_landing_filter_vjp")

@@ -8,63 +8,28 @@ bit eight rows with the zeros written out, each single output has the bits of th
 the device forms, and a guarded batch that never lands is the knot-scheduled call of a handle that never switches.  And a
 batch of 4 096 flown landings is set against the covariance the smoother returns."""
 import ctypes as C
-import faulthandler
 import functools
-import itertools
 
 import numpy as np
 import pytest
 
+from tests import estimation_cases as EF
 from tests import landing_smoother_ref as SM
 from tests import rollout_estimated_cases as EC
 from tests import rollout_guarded_cases as GC
-from tests import rollout_guarded_sweep_ref as SR
 from tests import tracking_cases as TC
 from tests import tracking_cov_ref as CR
 
 pytestmark = pytest.mark.gpu
+_time_limit = EF.time_limit(600)
 
 BAR = 1e-10  # the family's bar (tests/test_gpu_tracking_kalman.py)
 # Every problem's inputs must be well conditioned in the compared measures: the float64 yardstick within COND of its
 # longdouble restatement.  No problem is left out and nothing is drawn again: a draw that fails this needs another seed.
 COND = 1e-12
 
-
-def _shapes():
-    """tests/test_gpu_tracking_kalman.py's: N = 2 (one step), 3, 17 and 33; k_trans in {1, 2, N, N + 1}, both init_modes; B = 3
-    (a partly filled wave) and 5 (a second wave with one row); ny takes turns over 8, 3, 1."""
-    out = []
-    for i, (N, kt, im) in enumerate(itertools.product((2, 3, 17, 33), ("1", "2", "N", "N+1"), (1, 2))):
-        k_trans = {"1": 1, "2": 2, "N": N, "N+1": N + 1}[kt]
-        out.append(("shape", 3 if i % 2 else 5, N, k_trans, im, (8, 3, 1)[i % 3]))
-    return out
-
-
-CASES = _shapes() + [("ragged", 9, 17, 6, 1, 8), ("ragged", 6, 33, 12, 2, 3)]
-GUARDED = [("shape", N, im, B, wm) for (N, im, B) in GC.SHAPES for wm in (False, True)] + [("ragged", 12, 0, 70, True)]
-
-
-@pytest.fixture(autouse=True)
-def _time_limit():
-    """Every test here is a GPU step with a time limit of its own: a hang ends the process with a traceback."""
-    faulthandler.dump_traceback_later(600, exit=True)
-    yield
-    faulthandler.cancel_dump_traceback_later()
-
-
-def _dev(a):
-    import torch
-
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def measurement(rng, ny, V=None):
-    return rng.normal(size=(ny, 15)) / np.sqrt(15.0), rng.uniform(0.5, 2.0, size=ny) if V is None else np.full(ny, V)
-
-
-def vec_rel(got, ref):
-    """knot_rel on vectors (..., N, 15)"""
-    return CR.knot_rel(np.asarray(got)[..., None], np.asarray(ref)[..., None])
+CASES = EF.design_shapes() + EF.RAGGED
+GUARDED = [s + (wm,) for s in EF.GUARDED_SHAPES for wm in (False, True)] + [EF.GUARDED_RAGGED + (True,)]
 
 
 def _host(got):
@@ -76,10 +41,8 @@ def _host(got):
 
 def _yardsticks(A, Lh, Pp, H, V, Xhat, innov):
     """(the float64 yardstick's (Xs, Ps), its distance to the longdouble restatement) on blocks A (B, N-1, 15, 15)"""
-    ld = np.longdouble
-    lo = SM.bryson_frazier(A, Lh, Pp, H, V, Xhat, innov)
-    hi = SM.bryson_frazier(*(a.astype(ld) for a in (A, Lh, Pp, H, V, Xhat, innov)))
-    return lo, max(vec_rel(lo[0], hi[0]), CR.knot_rel(lo[1], hi[1]))
+    lo, hi = EF.in_both_precisions(SM.bryson_frazier, A, Lh, Pp, H, V, Xhat, innov)
+    return lo, max(EF.vec_rel(lo[0], hi[0]), CR.knot_rel(lo[1], hi[1]))
 
 
 @functools.lru_cache(maxsize=None)
@@ -88,17 +51,12 @@ def _run(kind, B, N, k_trans, im, ny, V=None):
     the same Ztraj, with the yardstick's own float64-to-longdouble distance.  Shared by the case's tests, never changed."""
     from quadruped_landing_amd import nlp as NL
 
-    seed = 100 * N + 10 * k_trans + im
-    batch = TC.batch(B, N, k_trans, im, seed=seed, ragged=kind == "ragged")
-    nlp, _, Zout, S0, W = TC.cov_setup(batch, seed, True)
-    rng = np.random.default_rng(seed + 7)
-    H, Vd = measurement(rng, ny, V)
-    L, Pe, _, _ = nlp.tracking_kalman(Zout, H, Vd, None, S0, W)
-    Xhat, innov = rng.normal(size=(B, N, 15)), rng.normal(size=(B, N, ny))
-    blocks, zo = TC.evaluator_blocks(nlp, Zout), TC.rows(nlp, Zout)
-    A = np.stack([blocks(b, zo[b])[:, :, :15] for b in range(B)])
-    ref, dist = _yardsticks(A, L.cpu().numpy(), NL.unpack_covariance(Pe), H, Vd, Xhat, innov)
-    inp = dict(Zout=Zout, L=L, Pe=Pe, H=H, V=Vd, Xhat=_dev(Xhat), innov=_dev(innov))
+    d = EF.scheduled_design(kind, B, N, k_trans, im, ny, 7, V)
+    nlp, Zout, H, Vd = d.nlp, d.Zout, d.H, d.V
+    L, Pe, _, _ = nlp.tracking_kalman(Zout, H, Vd, None, d.S0, d.W)
+    Xhat, innov = d.rng.normal(size=(B, N, 15)), d.rng.normal(size=(B, N, ny))
+    ref, dist = _yardsticks(d.A, L.cpu().numpy(), NL.unpack_covariance(Pe), H, Vd, Xhat, innov)
+    inp = dict(Zout=Zout, L=L, Pe=Pe, H=H, V=Vd, Xhat=EF.dev(Xhat), innov=EF.dev(innov))
     got = nlp.landing_smoother(Zout, L, Pe, H, Vd, inp["Xhat"], inp["innov"])
     return nlp, inp, got, _host(got), ref, dist
 
@@ -122,7 +80,7 @@ def test_smoothed_states_and_covariances_match_the_yardstick(kind, B, N, k_trans
     """Xs and Ps in knot_rel against the numpy recursion on the evaluator's dense blocks: within 1e-10, every problem included,
     the float64 yardstick itself within 1e-12 of longdouble.  Measured: profiles/landing_smoother_tests.txt."""
     nlp, inp, _, g, r, dist = _run(kind, B, N, k_trans, im, ny)
-    ex, ep = vec_rel(g[0], r[0]), CR.knot_rel(g[1], r[1])
+    ex, ep = EF.vec_rel(g[0], r[0]), CR.knot_rel(g[1], r[1])
     print(f"smoother {kind} B={B} N={N} k_trans={k_trans} mode={im} ny={ny}: Xs {ex:.2e}, Ps {ep:.2e}; yardstick to longdouble {dist:.2e}")
     assert dist <= COND, "an ill-conditioned draw: change the seed"
     assert g[0].shape == (B, N, 15) and g[1].shape == (B, N, 15, 15)
@@ -134,7 +92,7 @@ def test_one_millimetre_measurement_noise_is_held_to_the_yardsticks_own_rounding
     """V = 1e-6: H' V^-1 H (I - L H) cancels, in the yardstick as in the kernel.  The bar is 100 x the float64 yardstick's own
     distance to longdouble on these inputs, the rule of the solver-iterate tests (tests/test_gpu_ilqr_iterates.py)."""
     nlp, inp, _, g, r, dist = _run("shape", 5, 17, 6, 1, 8, 1e-6)
-    ex, ep = vec_rel(g[0], r[0]), CR.knot_rel(g[1], r[1])
+    ex, ep = EF.vec_rel(g[0], r[0]), CR.knot_rel(g[1], r[1])
     print(f"smoother V=1e-6 B=5 N=17 ny=8: Xs {ex:.2e}, Ps {ep:.2e}; yardstick to longdouble {dist:.2e}, bar {100 * dist:.2e}")
     assert ex <= 100 * dist and ep <= 100 * dist
     _check_structure(g, inp)
@@ -179,33 +137,17 @@ def test_each_single_output_has_the_bits_of_the_full_call(kind, B, N, k_trans, i
 
 
 # ---- 3. through the guarded touchdown -------------------------------------------------------------------------------------
-def _guarded_inputs(kind, N, im, B, wm):
-    if kind == "shape":
-        batch, Zref, K, x0, th = GC.case(N, im, B, True, wm)
-        return batch, Zref, K, x0, th, im, wm
-    batch, Zref, K, x0, th = GC.ragged_case()
-    return batch, Zref, K, x0, th, np.asarray(batch.init_mode), True
-
-
 @functools.lru_cache(maxsize=None)
 def _run_guarded(kind, N, im, B, wm):
     from quadruped_landing_amd import nlp as NL
 
-    batch, Zref, K, x0, th, ims, wm = _guarded_inputs(kind, N, im, B, wm)
-    B = len(x0)
-    nlp = TC.nlp(batch, TC.SECOND_MODEL)
-    dm = _dev(th) if wm else None
-    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), _dev(K), _dev(x0), dm)
-    zo, evh = TC.rows(nlp, Zout), ev.cpu().numpy()
-    rng = np.random.default_rng(GC.seed_of(N, im, True, wm) + 47)
-    ny = (8, 3, 1)[(N + B) % 3]
-    S0, W = CR.random_psd(rng, shape=(B,)), rng.uniform(0.0, 1e-2, size=15)
-    H, V = measurement(rng, ny)
-    L, Pe, _, _, _ = nlp.tracking_kalman_guarded(Zout, ev, H, V, None, S0, W, dm)
-    Xhat, innov = rng.normal(size=(B, N, 15)), rng.normal(size=(B, N, ny))
-    F, _ = SR.blocks(N, ims, zo, th, evh)
-    ref, dist = _yardsticks(F[:, :, :, :15], L.cpu().numpy(), NL.unpack_covariance(Pe), H, V, Xhat, innov)
-    inp = dict(Zout=Zout, ev=ev, model=dm, L=L, Pe=Pe, H=H, V=V, Xhat=_dev(Xhat), innov=_dev(innov), evh=evh)
+    d = EF.guarded_design(kind, N, im, B, True, wm, sensor_seed=47)
+    nlp, Zout, ev, dm, H, V = d.nlp, d.Zout, d.ev, d.model, d.H, d.V
+    ny = H.shape[0]
+    L, Pe, _, _, _ = nlp.tracking_kalman_guarded(Zout, ev, H, V, None, d.S0, d.W, dm)
+    Xhat, innov = d.rng.normal(size=(B, N, 15)), d.rng.normal(size=(B, N, ny))
+    ref, dist = _yardsticks(d.F[:, :, :, :15], L.cpu().numpy(), NL.unpack_covariance(Pe), H, V, Xhat, innov)
+    inp = dict(Zout=Zout, ev=ev, model=dm, L=L, Pe=Pe, H=H, V=V, Xhat=EF.dev(Xhat), innov=EF.dev(innov), evh=d.evh)
     got = nlp.landing_smoother_guarded(Zout, ev, L, Pe, H, V, inp["Xhat"], inp["innov"], dm)
     return nlp, inp, got, _host(got), ref, dist
 
@@ -216,7 +158,7 @@ def test_guarded_call_matches_the_yardstick(kind, N, im, B, wm):
     nlp, inp, _, g, r, dist = _run_guarded(kind, N, im, B, wm)
     land = inp["evh"][:, 0] >= 0
     assert land.any()
-    ex, ep = vec_rel(g[0], r[0]), CR.knot_rel(g[1], r[1])
+    ex, ep = EF.vec_rel(g[0], r[0]), CR.knot_rel(g[1], r[1])
     print(f"smoother guarded {kind} N={N} mode={im} B={B} models={wm} ny={inp['H'].shape[0]}: Xs {ex:.2e}, Ps {ep:.2e}; "
           f"yardstick to longdouble {dist:.2e}; {int(land.sum())} of {len(land)} problems land")
     assert dist <= COND, "an ill-conditioned draw: change the seed"
@@ -245,13 +187,13 @@ def test_a_batch_that_never_lands_is_bitwise_the_knot_scheduled_call_of_a_handle
     Zref[:, 15 + (3 if im == 1 else 1)::20] = -2.0  # every problem gets the last problem's pulling reference
     x0[:, iy], x0[:, iv] = 0.3, 0.0
     nlp, never = TC.nlp(batch, TC.SECOND_MODEL), TC.nlp(GC.with_k_trans(batch, N + 1), TC.SECOND_MODEL)
-    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), _dev(K), _dev(x0))
+    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), EF.dev(K), EF.dev(x0))
     assert bool((ev[:, 0] == -1).all())
     rng = np.random.default_rng(N)
     S0, W = CR.random_psd(rng, shape=(B,)), rng.uniform(0.0, 1e-2, size=15)
-    H, V = measurement(rng, 3)
+    H, V = EF.measurement(rng, 3)
     L, Pe, _, _ = never.tracking_kalman(Zout, H, V, None, S0, W)
-    Xhat, innov = _dev(rng.normal(size=(B, N, 15))), _dev(rng.normal(size=(B, N, 3)))
+    Xhat, innov = EF.dev(rng.normal(size=(B, N, 15))), EF.dev(rng.normal(size=(B, N, 3)))
     ref = never.landing_smoother(Zout, L, Pe, H, V, Xhat, innov)
     got = nlp.landing_smoother_guarded(Zout, ev, L, Pe, H, V, Xhat, innov)
     assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1])
@@ -264,11 +206,11 @@ def test_host_forms_equal_device_forms_after_other_host_calls_left_nans_behind(B
     N = 12
     batch, Zref, K, x0, th = GC.ragged_case(B=B, N=N)
     nlp = TC.nlp(batch, TC.SECOND_MODEL)
-    dm = _dev(th)
-    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), _dev(K), _dev(x0), dm)
+    dm = EF.dev(th)
+    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), EF.dev(K), EF.dev(x0), dm)
     rng = np.random.default_rng(B)
     S0, W = CR.random_psd(rng, shape=(B,)), rng.uniform(0.0, 1e-2, size=15)
-    H, V = measurement(rng, 3)
+    H, V = EF.measurement(rng, 3)
     Xhat, innov = rng.normal(size=(B, N, 15)), rng.normal(size=(B, N, 3))
     zh, evh = Zout.cpu().numpy(), ev.cpu().numpy()
     nan = lambda *s: np.full(s, np.nan)  # noqa: E731
@@ -276,12 +218,12 @@ def test_host_forms_equal_device_forms_after_other_host_calls_left_nans_behind(B
         nlp.tracking_kalman_host(nan(*zh.shape), np.ones((8, 15)), 1.0, None, nan(B, 120), None)
         nlp.landing_smoother_host(nan(*zh.shape), nan(B, N, 15, 8), nan(B, N, 120), np.ones((8, 15)), 1.0, nan(B, N, 15), nan(B, N, 8))
     L, Pe, _, _ = nlp.tracking_kalman(Zout, H, V, None, S0, W)
-    dev = nlp.landing_smoother(Zout, L, Pe, H, V, _dev(Xhat), _dev(innov))
+    dev = nlp.landing_smoother(Zout, L, Pe, H, V, EF.dev(Xhat), EF.dev(innov))
     host = nlp.landing_smoother_host(zh, L.cpu().numpy(), Pe.cpu().numpy(), H, V, Xhat, innov)
     for d, h in zip(dev, host):
         assert np.array_equal(h, d.cpu().numpy())
     L, Pe, _, _, _ = nlp.tracking_kalman_guarded(Zout, ev, H, V, None, S0, W, dm)
-    dev = nlp.landing_smoother_guarded(Zout, ev, L, Pe, H, V, _dev(Xhat), _dev(innov), dm)
+    dev = nlp.landing_smoother_guarded(Zout, ev, L, Pe, H, V, EF.dev(Xhat), EF.dev(innov), dm)
     host = nlp.landing_smoother_guarded_host(zh, evh, L.cpu().numpy(), Pe.cpu().numpy(), H, V, Xhat, innov, th)
     for d, h in zip(dev, host):
         assert np.array_equal(h, d.cpu().numpy())
@@ -319,13 +261,13 @@ def test_4096_flown_landings_are_smoothed_within_the_covariance_the_call_returns
     H, V = EC.sensors(), np.full(8, sd * sd)
     S0, dx0, v, w, Wx, _ = EC.mc_draws(seed, N, sd, W)
     x0 = np.asarray(nb.Z, dtype=np.float64)[:, :15].copy()
-    Zn = one.tracking_rollout(one.upload_Z(nb.Z), None, _dev(x0))
+    Zn = one.tracking_rollout(one.upload_Z(nb.Z), None, EF.dev(x0))
     K, _ = one.tracking_lqr(Zn, EC.Q, EC.R, EC.Q, with_cost_to_go=False)
     L, Pe, _, _ = one.tracking_kalman(Zn, H, V, K, S0, W, with_sigma=False, with_marginals=False)
     zn = TC.rows(one, Zn)[0]
     tile = lambda t: t.expand(S, *t.shape[1:]).contiguous()  # noqa: E731
     Zt = many.upload_Z(np.tile(zn, (S, 1)))
-    got = many.tracking_rollout_estimated(Zt, tile(K), tile(L), H, _dev(v), _dev(w), _dev(x0 + dx0), with_innovations=True)
+    got = many.tracking_rollout_estimated(Zt, tile(K), tile(L), H, EF.dev(v), EF.dev(w), EF.dev(x0 + dx0), with_innovations=True)
     torch.cuda.synchronize()
     zo, xh, iv = TC.rows(many, got[0]), got[1].cpu().numpy(), got[2].cpu().numpy()
     assert np.isfinite(zo).all() and np.isfinite(xh).all()
@@ -340,7 +282,7 @@ def test_4096_flown_landings_are_smoothed_within_the_covariance_the_call_returns
     xs, ps = Xs.cpu().numpy(), NL.unpack_covariance(Ps)
     assert np.array_equal(ps, np.broadcast_to(ps[:1], ps.shape))  # the covariances do not depend on the record
     wg, gs, gf = _band_and_rms(zo, xh, xs, ps[0], Wx)
-    print(f"  the library: worst |ratio - 1| {wg:.4f}; to the yardstick Xs {vec_rel(xs, xr):.2e}, Ps {CR.knot_rel(ps[0], pr):.2e}")
+    print(f"  the library: worst |ratio - 1| {wg:.4f}; to the yardstick Xs {EF.vec_rel(xs, xr):.2e}, Ps {CR.knot_rel(ps[0], pr):.2e}")
     assert wg <= EC.band() and (gs <= gf).all()
 
 
@@ -354,7 +296,7 @@ def test_overlaps_are_refused():
     Lb, h, INV, OK = _lib.lib(), nlp._h, _lib.QLN_ERR_INVALID_ARGUMENT, _lib.QLN_OK
     B, N, ny = nlp.B, nlp.N, inp["H"].shape[0]
     f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device="cuda")  # noqa: E731
-    Xo, Po, Hd = f64(B, N, 15), f64(B, N, 120), _dev(inp["H"])
+    Xo, Po, Hd = f64(B, N, 15), f64(B, N, 120), EF.dev(inp["H"])
     p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     V = np.ascontiguousarray(inp["V"])
     sm = lambda Xs, Ps: Lb.qln_landing_smoother(h, p(inp["Zout"]), p(inp["L"]), p(inp["Pe"]), p(Hd), ny, V.ctypes.data,  # noqa: E731

@@ -4,12 +4,12 @@ tests/test_rollout_limited_host.py; besides it the kernels are held bit for bit 
 saturation record), to each other (duality, the LQ cost of the forward sweep under the designed gains), to difference
 quotients of the GPU's own roll-out, and to a composition of the existing guarded sweeps with masked gains.  The cases and
 their seeds are tests/rollout_guarded_cases.py's, with gains and per-problem models, under LR.TEST_LIMITS."""
-import faulthandler
 import functools
 
 import numpy as np
 import pytest
 
+from tests import estimation_cases as EF
 from tests import rollout_guarded_cases as GC
 from tests import rollout_guarded_sweep_ref as SR
 from tests import rollout_limited_ref as LR
@@ -19,6 +19,7 @@ from tests import tracking_guarded_ref as TG
 from tests import tracking_ref as TR
 
 pytestmark = pytest.mark.gpu
+_time_limit = EF.time_limit(600)
 
 ROLLOUT_BAR = 1e-12      # tests/test_gpu_rollout_guarded.py
 SWEEP_BAR = 1e-12        # tests/test_gpu_rollout_guarded_sweeps.py, with its 100 x distance rule
@@ -31,20 +32,6 @@ DUALITY_BAR = 1e-12
 
 LIM = LR.TEST_LIMITS
 CASES = [("shape", N, im, B) for (N, im, B) in GC.SHAPES] + [("ragged", 12, 0, 70)]
-
-
-@pytest.fixture(autouse=True)
-def _time_limit():
-    """Every test here is a GPU step with a time limit of its own: a hang ends the process with a traceback."""
-    faulthandler.dump_traceback_later(600, exit=True)
-    yield
-    faulthandler.cancel_dump_traceback_later()
-
-
-def _dev(a):
-    import torch
-
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _inputs(kind, N, im, B):
@@ -62,7 +49,7 @@ def _run(kind, N, im, B):
     by the tests of the case; nothing here is changed afterwards."""
     batch, Zref, K, x0, th, ims = _inputs(kind, N, im, B)
     nlp = TC.nlp(batch, TC.SECOND_MODEL)
-    dev = dict(Zref=nlp.upload_Z(Zref), K=_dev(K), x0=_dev(x0), model=_dev(th))
+    dev = dict(Zref=nlp.upload_Z(Zref), K=EF.dev(K), x0=EF.dev(x0), model=EF.dev(th))
     Zout, ev, sat = nlp.tracking_rollout_limited(dev["Zref"], LIM, dev["K"], dev["x0"], dev["model"], guarded=True)
     zo, evh, sh = TC.rows(nlp, Zout), ev.cpu().numpy(), sat.cpu().numpy()
     ref = LR.rollout(N, ims, Zref, K, x0, th, LIM)
@@ -82,7 +69,7 @@ def _run(kind, N, im, B):
     gdist = (CR.knot_rel(Kr, Kl), CR.knot_rel(Pr, Pl))
     host = dict(Zref=Zref, K=K, x0=x0, th=th, ims=ims, Zout=zo, ev=evh, sat=sh, ref=ref, zd=zd, kd=kd, xd=xd, md=md, Zbar=Zbar,
                 ref_j=ref_j, ref_e=ref_e, ref_v=ref_v, Kr=Kr, Pr=Pr, gdist=gdist, batch=batch)
-    dev.update(Zout=Zout, ev=ev, sat=sat, zd=nlp.upload_Z(zd), kd=_dev(kd), xd=_dev(xd), md=_dev(md), Zbar=nlp.upload_Z(Zbar))
+    dev.update(Zout=Zout, ev=ev, sat=sat, zd=nlp.upload_Z(zd), kd=EF.dev(kd), xd=EF.dev(xd), md=EF.dev(md), Zbar=nlp.upload_Z(Zbar))
     return nlp, dev, host, max(SWEEP_BAR, 100 * dist)
 
 
@@ -174,7 +161,7 @@ def test_a_force_on_its_limit_is_free_and_a_nan_passes_through_in_its_problem_on
     Zref[0, 16], Zref[0, 18] = LIM[2], LIM[6]
     Zref[1, 16], Zref[1, 18] = np.nextafter(LIM[2], -np.inf), np.nextafter(LIM[6], -np.inf)
     Zref[2, 15] = np.nan
-    Zout, ev, sat = nlp.tracking_rollout_limited(nlp.upload_Z(Zref), LIM, None, _dev(x0), _dev(th), guarded=True)
+    Zout, ev, sat = nlp.tracking_rollout_limited(nlp.upload_Z(Zref), LIM, None, EF.dev(x0), EF.dev(th), guarded=True)
     s, zo = LR.unpack(sat.cpu().numpy()), TC.rows(nlp, Zout)
     assert s[0, 0, 1] == 0 and s[0, 0, 3] == 0 and zo[0, 16] == LIM[2] and zo[0, 18] == LIM[6]
     assert s[1, 0, 1] == 1 and s[1, 0, 3] == 1 and zo[1, 16] == LIM[2] and zo[1, 18] == LIM[6]
@@ -249,7 +236,7 @@ def test_limited_sweeps_equal_the_guarded_sweeps_on_masked_gains(kind, N, im, B)
     VJP, the same rows of K_bar and Fref_bar zeroed afterwards: an independent route to the same numbers, to SWEEP_BAR."""
     nlp, d, h, _ = _run(kind, N, im, B)
     sh = h["sat"]
-    Km, kdm, zdm = _dev(LR.mask_gains(h["K"], sh)), _dev(LR.mask_gains(h["kd"], sh)), nlp.upload_Z(LR.mask_forces(h["zd"], sh))
+    Km, kdm, zdm = EF.dev(LR.mask_gains(h["K"], sh)), EF.dev(LR.mask_gains(h["kd"], sh)), nlp.upload_Z(LR.mask_forces(h["zd"], sh))
     got, ed = nlp.tracking_rollout_limited_jvp(d["Zref"], d["Zout"], d["sat"], d["ev"], d["K"], d["model"], d["zd"], d["kd"],
                                                d["xd"], d["md"])
     ref, er = nlp.tracking_rollout_guarded_jvp(d["Zref"], d["Zout"], d["ev"], Km, d["model"], zdm, kdm, d["xd"], d["md"])
@@ -282,7 +269,7 @@ def test_limited_gains_match_the_riccati_recursion_on_masked_blocks(kind, N, im,
     assert P1 is None and np.array_equal(K1.cpu().numpy(), Kh)
     # x' P_0 x is the LQ cost of the limited forward sweep under those gains
     x = np.random.default_rng(N + B).normal(size=(B, 15))
-    zd, _ = nlp.tracking_rollout_limited_jvp(d["Zout"], d["Zout"], d["sat"], d["ev"], Kg, d["model"], x0_dot=_dev(x))
+    zd, _ = nlp.tracking_rollout_limited_jvp(d["Zout"], d["Zout"], d["sat"], d["ev"], Kg, d["model"], x0_dot=EF.dev(x))
     cost = TG.lq_cost(TC.rows(nlp, zd), N, TC.QW, TC.R, TC.QFW)
     quad = np.einsum("bi,bij,bj->b", x, Ph[:, 0], x)
     w = float(np.max(np.abs(cost - quad) / np.abs(cost)))

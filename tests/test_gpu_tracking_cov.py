@@ -1,26 +1,19 @@
 """GPU checks of qln_tracking_covariance: the numpy recursion on the evaluator's own blocks and on complex-step blocks over
 the tracking shapes and at full size, the duality with qln_tracking_rollout_vjp, the bit-for-bit parts of the contract, a
 Monte Carlo roll-out of 4 096 perturbed drops, and the host forms."""
-import faulthandler
 
 import numpy as np
 import pytest
 
+from tests import estimation_cases as EF
 from tests import tracking_cases as TC
 from tests import tracking_cov_ref as CR
 from tests.tracking_cases import SHAPES, Q, R
 
 pytestmark = pytest.mark.gpu
+_time_limit = EF.time_limit(900)
 
 BAR = 1e-10  # the project's bar for K and P (tests/test_gpu_tracking.py); the yardstick's own rounding is ~1e-14
-
-
-@pytest.fixture(autouse=True)
-def _time_limit():
-    """Every test here is a GPU step with a time limit of its own: a hang ends the process with a traceback."""
-    faulthandler.dump_traceback_later(900, exit=True)
-    yield
-    faulthandler.cancel_dump_traceback_later()
 
 
 @pytest.mark.parametrize("B,N,k_trans,init_mode", SHAPES)

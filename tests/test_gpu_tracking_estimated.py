@@ -5,12 +5,12 @@ bit for bit the roll-out it is built from, three sensor rows are bit for bit eig
 every subset of optional outputs has the bits of the full call, and the host forms have the bits of the device forms.  And the
 whole pipeline -- solve, nominal roll-out, gains, filter, the sampled loop -- is set against the covariances it predicts."""
 import ctypes as C
-import faulthandler
 import itertools
 
 import numpy as np
 import pytest
 
+from tests import estimation_cases as EF
 from tests import rollout_estimated_cases as EC
 from tests import rollout_estimated_ref as ER
 from tests import rollout_guarded_cases as GC
@@ -18,24 +18,11 @@ from tests import rollout_ref as RR
 from tests import tracking_cases as TC
 
 pytestmark = pytest.mark.gpu
+_time_limit = EF.time_limit(600)
 
 BAR = 1e-10  # the family's bar (tests/test_gpu_tracking.py, tests/test_gpu_rollout_guarded.py)
 SHAPES = [s for s in TC.SHAPES if s[1] in (2, 3, 40, 61)]
 FLAGS = list(itertools.product((False, True), repeat=4))  # with K, model, wnoise, xhat0
-
-
-@pytest.fixture(autouse=True)
-def _time_limit():
-    """Every test here is a GPU step with a time limit of its own: a hang ends the process with a traceback."""
-    faulthandler.dump_traceback_later(600, exit=True)
-    yield
-    faulthandler.cancel_dump_traceback_later()
-
-
-def _dev(a):
-    import torch
-
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _inputs(seed, B, N, ny, Zref, flags, th_all):
@@ -48,8 +35,8 @@ def _inputs(seed, B, N, ny, Zref, flags, th_all):
 
 
 def _call(nlp, Zref_d, inp, x0, guarded, **kw):
-    return nlp.tracking_rollout_estimated(Zref_d, _dev(inp["K"]), _dev(inp["Lgain"]), inp["H"], _dev(inp["vnoise"]), _dev(inp["wnoise"]),
-                                          _dev(x0), _dev(inp["xhat0"]), _dev(inp["model"]), guarded=guarded, with_innovations=True, **kw)
+    return nlp.tracking_rollout_estimated(Zref_d, EF.dev(inp["K"]), EF.dev(inp["Lgain"]), inp["H"], EF.dev(inp["vnoise"]), EF.dev(inp["wnoise"]),
+                                          EF.dev(x0), EF.dev(inp["xhat0"]), EF.dev(inp["model"]), guarded=guarded, with_innovations=True, **kw)
 
 
 def _yardstick(nlp, Zref, inp, x0, guarded):
@@ -152,12 +139,12 @@ def test_without_filter_gains_the_call_is_the_model_roll_out(B, N, k_trans, init
     Zref_d = nlp.tracking_rollout_model(nlp.upload_Z(batch.Z), None, None, None)
     Zref = TC.rows(nlp, Zref_d)
     rng = np.random.default_rng(N)
-    x0 = _dev(Zref[:, :15] + 1e-2 * rng.normal(size=(B, 15)))
+    x0 = EF.dev(Zref[:, :15] + 1e-2 * rng.normal(size=(B, 15)))
     for ny, wm in ((8, True), (3, False)):
-        model = _dev(RR.draw_models(B, N, TC.SECOND)) if wm else None
+        model = EF.dev(RR.draw_models(B, N, TC.SECOND)) if wm else None
         d = EC.draws(N, B, N, ny)
-        Zout, Xhat, innov = nlp.tracking_rollout_estimated(Zref_d, TC.gains(nlp, N), _dev(np.zeros_like(d["Lgain"])), d["H"],
-                                                           _dev(d["vnoise"]), None, x0, None, model, with_innovations=True)
+        Zout, Xhat, innov = nlp.tracking_rollout_estimated(Zref_d, TC.gains(nlp, N), EF.dev(np.zeros_like(d["Lgain"])), d["H"],
+                                                           EF.dev(d["vnoise"]), None, x0, None, model, with_innovations=True)
         assert torch.equal(Zout, nlp.tracking_rollout_model(Zref_d, None, x0, model))
         assert np.array_equal(Xhat.cpu().numpy(), np.concatenate([Zref, np.zeros((B, 5))], axis=1).reshape(B, N, 20)[:, :, :15])
         assert bool(innov.any())
@@ -171,11 +158,11 @@ def test_without_filter_gains_the_guarded_call_is_the_guarded_roll_out(N, im, B)
     nlp = TC.nlp(batch, TC.SECOND_MODEL)
     Zref_d, ev_ref = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), None, None, None)
     for ny, wm in ((8, True), (1, False)):
-        model = _dev(th) if wm else None
+        model = EF.dev(th) if wm else None
         d = EC.draws(N, B, N, ny)
-        Zout, _, _, ev, evh = nlp.tracking_rollout_estimated(Zref_d, TC.gains(nlp, N), _dev(np.zeros_like(d["Lgain"])), d["H"],
-                                                             _dev(d["vnoise"]), None, _dev(x0), None, model, guarded=True)
-        Zg, evg = nlp.tracking_rollout_guarded(Zref_d, None, _dev(x0), model)
+        Zout, _, _, ev, evh = nlp.tracking_rollout_estimated(Zref_d, TC.gains(nlp, N), EF.dev(np.zeros_like(d["Lgain"])), d["H"],
+                                                             EF.dev(d["vnoise"]), None, EF.dev(x0), None, model, guarded=True)
+        Zg, evg = nlp.tracking_rollout_guarded(Zref_d, None, EF.dev(x0), model)
         assert torch.equal(Zout, Zg) and torch.equal(ev, evg)
         assert torch.equal(evh, ev_ref)  # the estimator flies the reference's own landing
     assert bool((ev_ref[:, 0] >= 0).any())
@@ -212,8 +199,8 @@ def test_every_subset_of_optional_outputs_has_the_bits_of_the_full_call(guarded)
     full = _call(nlp, Zref_d, inp, x0, guarded)
     for we, wi, wv in itertools.product((False, True), repeat=3):
         if guarded or wv:
-            part = nlp.tracking_rollout_estimated(Zref_d, _dev(inp["K"]), _dev(inp["Lgain"]), inp["H"], _dev(inp["vnoise"]),
-                                                  _dev(inp["wnoise"]), _dev(x0), _dev(inp["xhat0"]), _dev(inp["model"]), guarded=guarded,
+            part = nlp.tracking_rollout_estimated(Zref_d, EF.dev(inp["K"]), EF.dev(inp["Lgain"]), inp["H"], EF.dev(inp["vnoise"]),
+                                                  EF.dev(inp["wnoise"]), EF.dev(x0), EF.dev(inp["xhat0"]), EF.dev(inp["model"]), guarded=guarded,
                                                   with_estimate=we, with_innovations=wi, with_events=wv)
             assert torch.equal(part[0], full[0])
             for p, f, asked in zip(part[1:], full[1:], (we, wi, wv, wv)):
@@ -224,8 +211,8 @@ def test_every_subset_of_optional_outputs_has_the_bits_of_the_full_call(guarded)
         ev = torch.zeros_like(full[3])
         out = torch.zeros_like(full[0])
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        t = {n: _dev(inp[n]) for n in ("K", "Lgain", "H", "vnoise", "wnoise", "xhat0", "model")}  # alive through the calls
-        t["x0"] = _dev(x0)
+        t = {n: EF.dev(inp[n]) for n in ("K", "Lgain", "H", "vnoise", "wnoise", "xhat0", "model")}  # alive through the calls
+        t["x0"] = EF.dev(x0)
         args = [p(t["K"]), p(t["Lgain"]), p(t["H"]), 3] + [p(t[n]) for n in ("vnoise", "wnoise", "x0", "xhat0", "model")]
         for which in (0, 1):
             recs = [None, None]
@@ -283,11 +270,11 @@ def test_monte_carlo_of_4096_noisy_landings_through_the_library(guarded):
     x0 = nb.x0.reshape(1, 15).copy()
     if guarded:
         x0[0, 6] += EC.MC_HEIGHT
-        Zn, ev = one.tracking_rollout_guarded(Zs, None, _dev(x0))
+        Zn, ev = one.tracking_rollout_guarded(Zs, None, EF.dev(x0))
         K, _ = one.tracking_lqr_guarded(Zn, ev, EC.Q, EC.R, EC.Q, with_cost_to_go=False)
         L, Pe, Sig, _, var = one.tracking_kalman_guarded(Zn, ev, H, V, K, S0, W, with_marginals=False)
     else:
-        Zn = one.tracking_rollout(Zs, None, _dev(x0))
+        Zn = one.tracking_rollout(Zs, None, EF.dev(x0))
         K, _ = one.tracking_lqr(Zn, EC.Q, EC.R, EC.Q, with_cost_to_go=False)
         L, Pe, Sig, _ = one.tracking_kalman(Zn, H, V, K, S0, W, with_marginals=False)
     zn = TC.rows(one, Zn)[0]
@@ -295,7 +282,7 @@ def test_monte_carlo_of_4096_noisy_landings_through_the_library(guarded):
     # P^+ = (I - L H) P^-: the prior, and with it S_k = H P^-_k H' + V, from what the call returns
     Pm = np.linalg.solve(np.eye(15) - Lh @ H, Pp)
     tile = lambda t: t.expand(S, *t.shape[1:]).contiguous()  # noqa: E731
-    got = many.tracking_rollout_estimated(many.upload_Z(np.tile(zn, (S, 1))), tile(K), tile(L), H, _dev(v), _dev(w), _dev(x0 + dx0),
+    got = many.tracking_rollout_estimated(many.upload_Z(np.tile(zn, (S, 1))), tile(K), tile(L), H, EF.dev(v), EF.dev(w), EF.dev(x0 + dx0),
                                           guarded=guarded, with_innovations=True)
     torch.cuda.synchronize()
     zo, xh, iv = TC.rows(many, got[0]), got[1].cpu().numpy(), got[2].cpu().numpy()
@@ -327,8 +314,8 @@ def test_invalid_arguments_are_refused():
     L, h, INV, OK = _lib.lib(), nlp._h, _lib.QLN_ERR_INVALID_ARGUMENT, _lib.QLN_OK
     f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device="cuda")  # noqa: E731
     p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-    Zr, Kd, Lg, Hd, vn, wn = nlp.upload_Z(Zref), _dev(K), f64(B, N, 15, 8), f64(8, 15), f64(B, N, 8), f64(B, N - 1, 15)
-    xd, xh, md = _dev(x0), _dev(x0), _dev(th)
+    Zr, Kd, Lg, Hd, vn, wn = nlp.upload_Z(Zref), EF.dev(K), f64(B, N, 15, 8), f64(8, 15), f64(B, N, 8), f64(B, N - 1, 15)
+    xd, xh, md = EF.dev(x0), EF.dev(x0), EF.dev(th)
     Zo, Xo, Io, ev, eh = nlp.new_Z(), f64(B, N, 15), f64(B, N, 8), f64(B, 8), f64(B, 8)
     est, gst = L.qln_tracking_rollout_estimated, L.qln_tracking_rollout_estimated_guarded
 

@@ -3,20 +3,22 @@ limits (include/qln_evaluator.h).  The yardstick is tests/rollout_estimated_limi
 tests/test_rollout_estimated_limited_host.py, which also runs every case of this module on the yardstick alone.  Besides it the
 kernels are held without an oracle: by the five exact reductions of the header, by the clamp's own properties, by the duality
 identity between the two sweeps, by exact zeros on the saturated channels, by the host forms and through torch autograd."""
-import faulthandler
 import functools
 import itertools
 
 import numpy as np
 import pytest
 
+from tests import estimation_cases as EF
 from tests import rollout_estimated_limited_ref as XR
 from tests import rollout_estimated_sweep_ref as ES
 from tests import rollout_limited_ref as LR
 from tests import rollout_ref as RR
 from tests import tracking_cases as TC
+from tests.estimation_cases import JVP_OUT, VJP_OUT
 
 pytestmark = pytest.mark.gpu
+_time_limit = EF.time_limit(600)
 
 BAR = 1e-10          # the family's bar for a roll-out, in rollout_ref.rel (tests/test_gpu_tracking_estimated.py)
 SWEEP_BAR = 1e-12    # the family's bar for a sweep against numpy, of max(1, |ref|) (tests/test_gpu_tracking_estimated_sweeps.py)
@@ -27,28 +29,12 @@ ALL = [(False,) + c for c in XR.SCHEDULED] + [(True,) + c for c in XR.GUARDED]
 SWEEPS = [(False, 5, 1, 2, 7, 3), (False, 5, 2, 4, 67, 8), (False, 5, 1, 5, 67, 1), (True, 5, 1, 2, 7, 3), (True, 5, 2, 2, 67, 8),
           (True, 5, 1, 2, 67, 1), (False, 61, 1, 21, 5, 8), (True, 61, 1, 21, 5, 3)]
 SWEEP_FLAGS = list(itertools.product((False, True), repeat=3))  # with K, model, xhat0
-
-
-@pytest.fixture(autouse=True)
-def _time_limit():
-    """Every test here is a GPU step with a time limit of its own: a hang ends the process with a traceback."""
-    faulthandler.dump_traceback_later(600, exit=True)
-    yield
-    faulthandler.cancel_dump_traceback_later()
-
-
-def _dev(a):
-    import torch
-
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 NAMES = ("Zout", "Xhat", "innov", "events", "events_hat", "sat")
 
 
 def _call(nlp, Zref_d, inp, x0, guarded, lim=LIM, **kw):
-    return nlp.tracking_rollout_estimated_limited(Zref_d, lim, _dev(inp["K"]), _dev(inp["Lgain"]), inp["H"], _dev(inp["vnoise"]),
-                                                  _dev(inp["wnoise"]), _dev(x0), _dev(inp["xhat0"]), _dev(inp["model"]),
+    return nlp.tracking_rollout_estimated_limited(Zref_d, lim, EF.dev(inp["K"]), EF.dev(inp["Lgain"]), inp["H"], EF.dev(inp["vnoise"]),
+                                                  EF.dev(inp["wnoise"]), EF.dev(x0), EF.dev(inp["xhat0"]), EF.dev(inp["model"]),
                                                   guarded=guarded, with_innovations=True, **kw)
 
 
@@ -149,8 +135,8 @@ def test_reduction_1_infinite_limits_give_the_unlimited_calls_bits(case):
     for ny, flags in ((8, XR.FLAGS[-1]), (3, XR.FLAGS[5]), (1, XR.FLAGS[0])):
         inp = XR.call_inputs(seed + ny, nlp.B, nlp.N, ny, Zref, flags, th)
         got = _call(nlp, Zref_d, inp, x0, guarded, lim=XR.NO_LIMITS)
-        ref = nlp.tracking_rollout_estimated(Zref_d, _dev(inp["K"]), _dev(inp["Lgain"]), inp["H"], _dev(inp["vnoise"]),
-                                             _dev(inp["wnoise"]), _dev(x0), _dev(inp["xhat0"]), _dev(inp["model"]), guarded=guarded,
+        ref = nlp.tracking_rollout_estimated(Zref_d, EF.dev(inp["K"]), EF.dev(inp["Lgain"]), inp["H"], EF.dev(inp["vnoise"]),
+                                             EF.dev(inp["wnoise"]), EF.dev(x0), EF.dev(inp["xhat0"]), EF.dev(inp["model"]), guarded=guarded,
                                              with_innovations=True)
         for g, r in zip(got, ref):
             assert torch.equal(g, r)
@@ -169,7 +155,7 @@ def test_reduction_3_without_gains_and_process_noise_the_plant_flies_the_limited
     for ny, wm, wx in ((8, True, True), (1, False, False)):
         inp = XR.call_inputs(seed + ny, nlp.B, nlp.N, ny, Zref, (False, wm, False, wx), th)
         got = _call(nlp, Zref_d, inp, x0, guarded)
-        zo, ev, sat = nlp.tracking_rollout_limited(Zref_d, LIM, None, _dev(x0), _dev(inp["model"]), guarded=guarded)
+        zo, ev, sat = nlp.tracking_rollout_limited(Zref_d, LIM, None, EF.dev(x0), EF.dev(inp["model"]), guarded=guarded)
         assert torch.equal(got[0], zo) and torch.equal(got[5], sat) and bool(sat.any())
         assert (ev is None and got[3] is None) or torch.equal(got[3], ev)
 
@@ -187,7 +173,7 @@ def test_reduction_4_without_filter_gains_the_scheduled_estimate_stays_on_the_li
         inp = XR.call_inputs(seed + ny, B, N, ny, Zref, (True, wm, False, False), th)
         inp["Lgain"] = np.zeros_like(inp["Lgain"])
         got = _call(nlp, nominal, inp, x0, False)
-        zo, _, sat = nlp.tracking_rollout_limited(nominal, LIM, None, _dev(x0), _dev(inp["model"]))
+        zo, _, sat = nlp.tracking_rollout_limited(nominal, LIM, None, EF.dev(x0), EF.dev(inp["model"]))
         assert torch.equal(got[0], zo) and torch.equal(got[5], sat)
         zr = np.concatenate([TC.rows(nlp, nominal), np.zeros((B, 5))], axis=1).reshape(B, N, 20)[:, :, :15]
         assert np.array_equal(got[1].cpu().numpy(), zr)
@@ -209,8 +195,8 @@ def test_reduction_5_three_rows_are_eight_rows_with_zeros_and_every_subset_of_ou
         assert (p is None and q is None) or torch.equal(p, q[..., :3] if n == "innov" else q), n
     assert bool(full[5].any())
     for we, wi, wv, ws in itertools.product((False, True), repeat=4):
-        part = nlp.tracking_rollout_estimated_limited(Zref_d, LIM, _dev(inp["K"]), _dev(inp["Lgain"]), inp["H"], _dev(inp["vnoise"]),
-                                                      _dev(inp["wnoise"]), _dev(x0), _dev(inp["xhat0"]), _dev(inp["model"]),
+        part = nlp.tracking_rollout_estimated_limited(Zref_d, LIM, EF.dev(inp["K"]), EF.dev(inp["Lgain"]), inp["H"], EF.dev(inp["vnoise"]),
+                                                      EF.dev(inp["wnoise"]), EF.dev(x0), EF.dev(inp["xhat0"]), EF.dev(inp["model"]),
                                                       guarded=guarded, with_estimate=we, with_innovations=wi, with_events=wv,
                                                       with_sat=ws)
         assert torch.equal(part[0], full[0])
@@ -219,23 +205,6 @@ def test_reduction_5_three_rows_are_eight_rows_with_zeros_and_every_subset_of_ou
 
 
 # ---- 4. the sweeps ----------------------------------------------------------------------------------------------------------
-JVP_OUT = ("Zout_dot", "Xhat_dot", "innov_dot", "event_dot", "event_hat_dot")
-VJP_OUT = ("Zref_bar", "K_bar", "Lgain_bar", "x0_bar", "xhat0_bar", "model_bar")
-
-
-def _upload(nlp, dirs):
-    return {k: (nlp.upload_Z(v) if k in ("Zref_dot", "Zbar") else _dev(v)) for k, v in dirs.items()}
-
-
-def _present(inp, dirs):
-    keep = lambda k: not ((k == "K_dot" and inp["K"] is None) or (k == "xhat0_dot" and inp["xhat0"] is None))  # noqa: E731
-    return {k: v for k, v in dirs.items() if keep(k)}
-
-
-def _want(h, wx):
-    return tuple(w for w in ("Zref", "K", "Lgain", "x0", "xhat0", "model") if not ((w == "K" and h["K"] is None) or (w == "xhat0" and not wx)))
-
-
 def _jvp(nlp, d, dirs, sat=None, limited=True, **kw):
     if limited:
         return nlp.tracking_rollout_estimated_limited_jvp(d["Zref"], d["K"], d["Lgain"], d["H"], d["Zout"], d["Xhat"],
@@ -255,10 +224,6 @@ def _vjp(nlp, d, cot, want, sat=None, limited=True):
                                               cot["innov_bar"], want)
 
 
-def _hostd(nlp, names, outs):
-    return {n: (TC.rows(nlp, o) if n in ("Zout_dot", "Zref_bar") else o.cpu().numpy()) for n, o in zip(names, outs) if o is not None}
-
-
 @functools.lru_cache(maxsize=None)
 def _run(guarded, N, im, kt, B, ny, flags):
     """One sweep case under one combination of present inputs: the GPU's limited roll-out, the yardstick's blocks at the GPU's
@@ -268,7 +233,7 @@ def _run(guarded, N, im, kt, B, ny, flags):
     batch, inp = ES.case(N, im, kt, B, ny, guarded)
     inp = dict(inp, K=inp["K"] if wk else None, model=inp["model"] if wm else None, xhat0=inp["xhat0"] if wx else None)
     nlp = TC.nlp(batch, TC.SECOND_MODEL)
-    d = {k: _dev(inp[k]) for k in ("K", "Lgain", "vnoise", "wnoise", "x0", "xhat0", "model")}
+    d = {k: EF.dev(inp[k]) for k in ("K", "Lgain", "vnoise", "wnoise", "x0", "xhat0", "model")}
     d["Zref"], d["H"] = nlp.upload_Z(inp["Zref"]), inp["H"]
     got = nlp.tracking_rollout_estimated_limited(d["Zref"], LIM, d["K"], d["Lgain"], d["H"], d["vnoise"], d["wnoise"], d["x0"],
                                                  d["xhat0"], d["model"], guarded=guarded, with_innovations=True)
@@ -280,7 +245,7 @@ def _run(guarded, N, im, kt, B, ny, flags):
                                            TC.SECOND, guarded, h["events"], h["events_hat"], ctype=ctype)
     blk, blkl = blocks(np.complex128), blocks(np.clongdouble)
     dirs, cot = ES.directions(1000 * N + 10 * kt + ny, B, N, ny)
-    dirs = _present(inp, dirs)
+    dirs = EF.present(inp, dirs)
     args = (h["sat"], h["Zref"], h["K"], h["Lgain"], h["H"], h["Zout"], h["Xhat"], h["innov"])
     ev = dict(events=h["events"], events_hat=h["events_hat"])
     ref_j, ref_v = XR.sweep_jvp(blk, *args, **dirs, **ev), XR.sweep_vjp(blk, *args, **cot, with_xhat0=wx)
@@ -289,7 +254,7 @@ def _run(guarded, N, im, kt, B, ny, flags):
     bar = max(SWEEP_BAR, 100 * dist)
     if bar > SWEEP_BAR:
         print(f"guarded={guarded} N={N} B={B} flags={flags}: the yardstick is {dist:.2e} from its longdouble restatement: bar {bar:.2e}")
-    return dict(nlp=nlp, d=d, h=h, dirs=dirs, cot=cot, ddirs=_upload(nlp, dirs), dcot=_upload(nlp, cot), ref_j=ref_j, ref_v=ref_v,
+    return dict(nlp=nlp, d=d, h=h, dirs=dirs, cot=cot, ddirs=EF.upload(nlp, dirs), dcot=EF.upload(nlp, cot), ref_j=ref_j, ref_v=ref_v,
                 bar=bar)
 
 
@@ -303,9 +268,9 @@ def test_sweeps_match_the_yardstick_and_saturated_channels_get_exact_zeros(guard
     for flags in SWEEP_FLAGS:
         r = _run(guarded, N, im, kt, B, ny, flags)
         nlp, d, h, wx = r["nlp"], r["d"], r["h"], flags[2]
-        got = _hostd(nlp, JVP_OUT, _jvp(nlp, d, r["ddirs"]))
+        got = EF.host(nlp, JVP_OUT, _jvp(nlp, d, r["ddirs"]))
         assert ("event_dot" in got) == guarded and ("event_hat_dot" in got) == guarded
-        gotv = _hostd(nlp, VJP_OUT, _vjp(nlp, d, r["dcot"], _want(h, wx)))
+        gotv = EF.host(nlp, VJP_OUT, _vjp(nlp, d, r["dcot"], EF.want(h, wx)))
         assert ("xhat0_bar" in gotv) == wx and ("K_bar" in gotv) == flags[0]
         wj = {n: ES.worst(got[n], r["ref_j"][n]) for n in got}
         wv = {n: ES.worst(gotv[n], r["ref_v"][n]) for n in gotv}
@@ -334,7 +299,7 @@ def test_duality_between_the_two_kernels(guarded, N, im, kt, B, ny, wx):
     r = _run(guarded, N, im, kt, B, ny, (True, True, wx))
     nlp, d = r["nlp"], r["d"]
     fwd = dict(zip(JVP_OUT, _jvp(nlp, d, r["ddirs"])))
-    rev = dict(zip(VJP_OUT, _vjp(nlp, d, r["dcot"], _want(r["h"], wx))))
+    rev = dict(zip(VJP_OUT, _vjp(nlp, d, r["dcot"], EF.want(r["h"], wx))))
     dot = lambda a, b_: float(torch.dot(a.reshape(-1), b_.reshape(-1)))  # noqa: E731
     lhs = sum(dot(r["dcot"][c], fwd[o]) for c, o in (("Zbar", "Zout_dot"), ("Xhat_bar", "Xhat_dot"), ("innov_bar", "innov_dot")))
     rhs = sum(dot(rev[k[:-4] + "_bar"], v) for k, v in r["ddirs"].items())
@@ -353,7 +318,7 @@ def test_reduction_2_an_empty_active_set_gives_the_estimated_sweeps_bits(guarded
         zero = torch.zeros_like(d["sat"])
         for a, b in zip(_jvp(nlp, d, r["ddirs"], sat=zero), _jvp(nlp, d, r["ddirs"], limited=False)):
             assert (a is None and b is None) or torch.equal(a, b)
-        want = _want(r["h"], flags[2])
+        want = EF.want(r["h"], flags[2])
         for a, b in zip(_vjp(nlp, d, r["dcot"], want, sat=zero), _vjp(nlp, d, r["dcot"], want, limited=False)):
             assert (a is None and b is None) or torch.equal(a, b)
         # and a sweep at the record differs from it: the mask is read
@@ -368,14 +333,14 @@ def test_reduction_5_in_the_sweeps_three_rows_are_eight_rows_with_zeros_and_subs
     nlp, d, h = r["nlp"], r["d"], r["h"]
     dirs, cot = r["dirs"], r["cot"]
     pad = lambda a, axis: np.concatenate([a, np.zeros(a.shape[:axis] + (5,) + a.shape[axis + 1:])], axis=axis)  # noqa: E731
-    d8 = dict(d, Lgain=_dev(pad(h["Lgain"], 3)), H=pad(h["H"], 0), innov=_dev(pad(h["innov"], 2)))
+    d8 = dict(d, Lgain=EF.dev(pad(h["Lgain"], 3)), H=pad(h["H"], 0), innov=EF.dev(pad(h["innov"], 2)))
     dirs8, cot8 = dict(dirs, Lgain_dot=pad(dirs["Lgain_dot"], 3)), dict(cot, innov_bar=pad(cot["innov_bar"], 2))
     full = _jvp(nlp, d, r["ddirs"])
-    for x, y, name in zip(full, _jvp(nlp, d8, _upload(nlp, dirs8)), JVP_OUT):
+    for x, y, name in zip(full, _jvp(nlp, d8, EF.upload(nlp, dirs8)), JVP_OUT):
         assert (x is None and y is None and not guarded) or torch.equal(x, y[..., :3] if name == "innov_dot" else y), name
-    want = _want(h, True)
+    want = EF.want(h, True)
     fullv = _vjp(nlp, d, r["dcot"], want)
-    for x, y, name in zip(fullv, _vjp(nlp, d8, _upload(nlp, cot8), want), VJP_OUT):
+    for x, y, name in zip(fullv, _vjp(nlp, d8, EF.upload(nlp, cot8), want), VJP_OUT):
         assert torch.equal(x, y[..., :3] if name == "Lgain_bar" else y), name
     for we, wi, wd in itertools.product((False, True), repeat=3):
         part = _jvp(nlp, d, r["ddirs"], with_estimate=we, with_innovations=wi, with_event_dot=wd)
@@ -407,10 +372,10 @@ def test_differentiable_estimated_rollout_with_limits_runs_the_limited_sweeps_in
         assert torch.equal(o, d[k]), k
     assert not any(o.requires_grad for o in out[3:]) and bool(out[-1].any())
     torch.autograd.backward(out[:3], [dc["Zbar"], dc["Xhat_bar"], dc["innov_bar"]])
-    ref = _vjp(nlp, d, dc, _want(r["h"], wx))
+    ref = _vjp(nlp, d, dc, EF.want(r["h"], wx))
     for k, g in zip(keys, ref):
         assert (leaves[k] is None and g is None) or torch.equal(leaves[k].grad.reshape(-1), g.reshape(-1)), k
-    assert not torch.equal(ref[0], _vjp(nlp, d, dc, _want(r["h"], wx), limited=False)[0])  # and not the unlimited sweep
+    assert not torch.equal(ref[0], _vjp(nlp, d, dc, EF.want(r["h"], wx), limited=False)[0])  # and not the unlimited sweep
     refj = _jvp(nlp, d, dd)
     dot = lambda k: dd[k + "_dot"].reshape(d[k].shape)  # noqa: E731
     with fwAD.dual_level():
@@ -456,17 +421,17 @@ def test_host_forms_give_the_device_forms_bits_after_a_host_call_left_nans_behin
             assert (d_ is None and h_ is None) or np.array_equal(h_.reshape(-1), d_.cpu().numpy().reshape(-1)), name
         assert host[5].any()
         # the sweeps, at that trajectory
-        d = dict(zip(NAMES, dev), Zref=Zref_d, K=_dev(inp["K"]), Lgain=_dev(inp["Lgain"]), H=inp["H"], model=_dev(inp["model"]))
+        d = dict(zip(NAMES, dev), Zref=Zref_d, K=EF.dev(inp["K"]), Lgain=EF.dev(inp["Lgain"]), H=inp["H"], model=EF.dev(inp["model"]))
         h = dict(zip(NAMES, host))
         dirs, cot = ES.directions(8, B, N, ny)
-        devj = _jvp(nlp, d, _upload(nlp, dirs))
+        devj = _jvp(nlp, d, EF.upload(nlp, dirs))
         hostj = nlp.tracking_rollout_estimated_limited_jvp_host(zr, inp["K"], inp["Lgain"], inp["H"], h["Zout"], h["Xhat"], h["sat"],
                                                                 h["innov"], inp["model"], h["events"], h["events_hat"],
                                                                 **dict(dirs, Zref_dot=pad(dirs["Zref_dot"])))
         for name, x, y in zip(JVP_OUT, hostj, devj):
             assert (x is None and y is None) or np.array_equal(x.reshape(-1), y.cpu().numpy().reshape(-1)), name
         want = ("Zref", "K", "Lgain", "x0", "xhat0", "model")
-        devv = _vjp(nlp, d, _upload(nlp, cot), want)
+        devv = _vjp(nlp, d, EF.upload(nlp, cot), want)
         hostv = nlp.tracking_rollout_estimated_limited_vjp_host(zr, inp["K"], inp["Lgain"], inp["H"], h["Zout"], h["Xhat"], h["sat"],
                                                                 pad(cot["Zbar"]), h["innov"], inp["model"], h["events"],
                                                                 h["events_hat"], cot["Xhat_bar"], cot["innov_bar"], want)

@@ -4,17 +4,19 @@ by tests/test_rollout_estimated_sweep_host.py.  Besides it the kernels are held 
 between them, bit for bit by the sibling sweeps where the filter gains are zero, by eight sensor rows with zeros written out,
 by every subset of optional outputs, by the host forms, by central differences of the GPU's own roll-out where the plant and
 the estimator land in different knots, and through torch autograd.  The cases and their seeds are the yardstick module's."""
-import faulthandler
 import functools
 import itertools
 
 import numpy as np
 import pytest
 
+from tests import estimation_cases as EF
 from tests import rollout_estimated_sweep_ref as ES
 from tests import tracking_cases as TC
+from tests.estimation_cases import JVP_OUT, VJP_OUT
 
 pytestmark = pytest.mark.gpu
+_time_limit = EF.time_limit(300)
 
 SWEEP_BAR = 1e-12  # the project's bar for a sweep against numpy, of max(1, |ref|) (tests/test_gpu_rollout_guarded_sweeps.py)
 # N = 5 with k_trans over 1..N and both init_modes, B = 7 (a part-filled wave) and 67 (several blocks, a ragged tail), ny over
@@ -35,23 +37,9 @@ FD_CPU_WORST = 6.39e-11
 FD_BAR = 10 * FD_CPU_WORST
 
 
-@pytest.fixture(autouse=True)
-def _time_limit():
-    """Every test here is a GPU step with a time limit of its own: a hang ends the process with a traceback."""
-    faulthandler.dump_traceback_later(300, exit=True)
-    yield
-    faulthandler.cancel_dump_traceback_later()
-
-
-def _dev(a):
-    import torch
-
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def _rollout(nlp, inp, guarded):
     """The GPU's roll-out of host inputs: (device dict, host dict) of its inputs and the trajectory."""
-    d = {k: _dev(inp[k]) for k in ("K", "Lgain", "vnoise", "wnoise", "x0", "xhat0", "model")}
+    d = {k: EF.dev(inp[k]) for k in ("K", "Lgain", "vnoise", "wnoise", "x0", "xhat0", "model")}
     d["Zref"], d["H"] = nlp.upload_Z(inp["Zref"]), inp["H"]
     got = nlp.tracking_rollout_estimated(d["Zref"], d["K"], d["Lgain"], d["H"], d["vnoise"], d["wnoise"], d["x0"], d["xhat0"],
                                          d["model"], guarded=guarded, with_innovations=True)
@@ -73,26 +61,6 @@ def _vjp(nlp, d, guarded, cot, want=None, innov=True):
                                               cot["Xhat_bar"], cot["innov_bar"], want)
 
 
-def _upload(nlp, dirs):
-    return {k: (nlp.upload_Z(v) if k in ("Zref_dot", "Zbar") else _dev(v)) for k, v in dirs.items()}
-
-
-JVP_OUT = ("Zout_dot", "Xhat_dot", "innov_dot", "event_dot", "event_hat_dot")
-VJP_OUT = ("Zref_bar", "K_bar", "Lgain_bar", "x0_bar", "xhat0_bar", "model_bar")
-
-
-def _host(nlp, names, outs):
-    return {n: (TC.rows(nlp, o) if n in ("Zout_dot", "Zref_bar") else o.cpu().numpy()) for n, o in zip(names, outs) if o is not None}
-
-
-def _present(inp, dirs, lgain=True):
-    """The tangents that exist for these inputs: K_dot only with K; xhat0_dot exactly when xhat0 is given (None is the xhat0 =
-    None case, whose tangent is Zref_dot's)."""
-    keep = lambda k: not ((k == "K_dot" and inp["K"] is None) or (k == "xhat0_dot" and inp["xhat0"] is None) or  # noqa: E731
-                          (k == "Lgain_dot" and not lgain))
-    return {k: v for k, v in dirs.items() if keep(k)}
-
-
 @functools.lru_cache(maxsize=None)
 def _run(guarded, N, im, kt, B, ny, flags):
     """One case under one combination of present inputs: the GPU's roll-out, the yardstick's blocks at the GPU's own trajectory
@@ -108,7 +76,7 @@ def _run(guarded, N, im, kt, B, ny, flags):
                                            TC.SECOND, guarded, h["events"], h["events_hat"], ctype=ctype)
     blk, blkl = blocks(np.complex128), blocks(np.clongdouble)
     dirs, cot = ES.directions(1000 * N + 10 * kt + ny, B, N, ny)
-    dirs = _present(inp, dirs)
+    dirs = EF.present(inp, dirs)
     args = (h["Zref"], h["K"], h["Lgain"], h["H"], h["Zout"], h["Xhat"], h["innov"])
     ev = dict(events=h["events"], events_hat=h["events_hat"])
     ref_j, ref_v = ES.sweep_jvp(blk, *args, **dirs, **ev), ES.sweep_vjp(blk, *args, **cot, with_xhat0=wx)
@@ -117,13 +85,8 @@ def _run(guarded, N, im, kt, B, ny, flags):
     bar = max(SWEEP_BAR, 100 * dist)
     if bar > SWEEP_BAR:
         print(f"guarded={guarded} N={N} B={B} flags={flags}: the yardstick is {dist:.2e} from its longdouble restatement: bar {bar:.2e}")
-    return dict(nlp=nlp, d=d, h=h, blk=blk, dirs=dirs, cot=cot, ddirs=_upload(nlp, dirs), dcot=_upload(nlp, cot), ref_j=ref_j,
+    return dict(nlp=nlp, d=d, h=h, blk=blk, dirs=dirs, cot=cot, ddirs=EF.upload(nlp, dirs), dcot=EF.upload(nlp, cot), ref_j=ref_j,
                 ref_v=ref_v, bar=bar, args=args, ev=ev, batch=batch)
-
-
-def _want(h, wx, lgain=True):
-    return tuple(w for w in ("Zref", "K", "Lgain", "x0", "xhat0", "model")
-                 if not ((w == "K" and h["K"] is None) or (w == "xhat0" and not wx) or (w == "Lgain" and not lgain)))
 
 
 # ---- 1. against the yardstick ---------------------------------------------------------------------------------------------
@@ -139,12 +102,12 @@ def test_sweeps_match_the_yardstick_in_every_combination_of_inputs(guarded, N, i
         r = _run(guarded, N, im, kt, B, ny, flags)
         nlp, d, h, wx = r["nlp"], r["d"], r["h"], flags[2]
         for lgain in (True, False):
-            dirs = _present(h, r["dirs"], lgain)
+            dirs = EF.present(h, r["dirs"], lgain)
             ref = r["ref_j"] if lgain else ES.sweep_jvp(r["blk"], *r["args"], **dirs, **r["ev"])
-            got = _host(nlp, JVP_OUT, _jvp(nlp, d, guarded, _present(h, r["ddirs"], lgain)))
+            got = EF.host(nlp, JVP_OUT, _jvp(nlp, d, guarded, EF.present(h, r["ddirs"], lgain)))
             wj = {n: ES.worst(got[n], ref[n]) for n in got}
             refv = r["ref_v"]
-            gotv = _host(nlp, VJP_OUT, _vjp(nlp, d, guarded, r["dcot"], _want(h, wx, lgain), innov=lgain))
+            gotv = EF.host(nlp, VJP_OUT, _vjp(nlp, d, guarded, r["dcot"], EF.want(h, wx, lgain), innov=lgain))
             assert ("Lgain_bar" in gotv) == lgain and ("xhat0_bar" in gotv) == wx and ("K_bar" in gotv) == flags[0]
             wv = {n: ES.worst(gotv[n], refv[n]) for n in gotv}
             w = max(*wj.values(), *wv.values())
@@ -156,7 +119,7 @@ def test_sweeps_match_the_yardstick_in_every_combination_of_inputs(guarded, N, i
                 if name != "xhat0_dot":
                     one["xhat0_dot"] = np.zeros((B, 15))  # a given xhat0 held fixed
                 ref = ES.sweep_jvp(r["blk"], *r["args"], **one, **r["ev"])
-                got = _host(nlp, JVP_OUT, _jvp(nlp, d, guarded, _upload(nlp, one)))
+                got = EF.host(nlp, JVP_OUT, _jvp(nlp, d, guarded, EF.upload(nlp, one)))
                 w = max(ES.worst(got[n], ref[n]) for n in got)
                 worst = max(worst, w)
                 assert w <= r["bar"], (name, w, r["bar"])
@@ -177,7 +140,7 @@ def test_adjoint_identity_between_the_two_kernels(guarded, N, im, kt, B, ny, wx)
     r = _run(guarded, N, im, kt, B, ny, (True, True, wx))
     nlp, d = r["nlp"], r["d"]
     fwd = dict(zip(JVP_OUT, _jvp(nlp, d, guarded, r["ddirs"])))
-    rev = dict(zip(VJP_OUT, _vjp(nlp, d, guarded, r["dcot"], _want(r["h"], wx))))
+    rev = dict(zip(VJP_OUT, _vjp(nlp, d, guarded, r["dcot"], EF.want(r["h"], wx))))
     dot = lambda a, b_: float(torch.dot(a.reshape(-1), b_.reshape(-1)))  # noqa: E731
     lhs = sum(dot(r["dcot"][c], fwd[o]) for c, o in (("Zbar", "Zout_dot"), ("Xhat_bar", "Xhat_dot"), ("innov_bar", "innov_dot")))
     rhs = sum(dot(rev[k[:-4] + "_bar"], v) for k, v in r["ddirs"].items())
@@ -204,7 +167,7 @@ def test_without_filter_gains_the_plant_chain_is_bitwise_the_sibling_sweep(guard
     zr = np.concatenate([h["Zref"], np.zeros((B, 5))], axis=1).reshape(B, N, 20)[:, :, :15]
     assert np.array_equal(h["Xhat"], zr)
     dirs, cot = ES.directions(5, B, N, ny)
-    dd = _upload(nlp, {k: dirs[k] for k in ("x0_dot", "model_dot")})
+    dd = EF.upload(nlp, {k: dirs[k] for k in ("x0_dot", "model_dot")})
     Zbar = nlp.upload_Z(cot["Zbar"])
     got = _jvp(nlp, d, guarded, dd)
     want = ("x0", "model")
@@ -232,13 +195,13 @@ def test_three_sensor_rows_are_bitwise_eight_rows_with_zeros(guarded, N, im, kt,
     d, h = _rollout(nlp, inp, guarded)
     dirs, cot = ES.directions(6, B, N, 3)
     pad = lambda a, axis: np.concatenate([a, np.zeros(a.shape[:axis] + (5,) + a.shape[axis + 1:])], axis=axis)  # noqa: E731
-    d8 = dict(d, Lgain=_dev(pad(inp["Lgain"], 3)), H=pad(inp["H"], 0), innov=_dev(pad(h["innov"], 2)))
+    d8 = dict(d, Lgain=EF.dev(pad(inp["Lgain"], 3)), H=pad(inp["H"], 0), innov=EF.dev(pad(h["innov"], 2)))
     dirs8, cot8 = dict(dirs, Lgain_dot=pad(dirs["Lgain_dot"], 3)), dict(cot, innov_bar=pad(cot["innov_bar"], 2))
-    a, b = _jvp(nlp, d, guarded, _upload(nlp, dirs)), _jvp(nlp, d8, guarded, _upload(nlp, dirs8))
+    a, b = _jvp(nlp, d, guarded, EF.upload(nlp, dirs)), _jvp(nlp, d8, guarded, EF.upload(nlp, dirs8))
     for x, y, name in zip(a, b, JVP_OUT):
         assert torch.equal(x, y[..., :3] if name == "innov_dot" else y), name
     assert not bool(b[2][..., 3:].any())
-    a, b = _vjp(nlp, d, guarded, _upload(nlp, cot)), _vjp(nlp, d8, guarded, _upload(nlp, cot8))
+    a, b = _vjp(nlp, d, guarded, EF.upload(nlp, cot)), _vjp(nlp, d8, guarded, EF.upload(nlp, cot8))
     for x, y, name in zip(a, b, VJP_OUT):
         assert torch.equal(x, y[..., :3] if name == "Lgain_bar" else y), name
     assert not bool(b[2][..., 3:].any())
@@ -279,7 +242,7 @@ def test_host_forms_equal_device_forms_and_padding_is_untouched(guarded, kw):
     dirs, cot = ES.directions(8, B, N, ny)
     pad = lambda a: np.concatenate([a, np.zeros((B, zs - n))], axis=1).reshape(-1)  # noqa: E731
     sentinel = torch.full((B * zs,), -7.25, dtype=torch.float64, device="cuda")
-    dev = _jvp(nlp, d, guarded, _upload(nlp, dirs), out=sentinel)
+    dev = _jvp(nlp, d, guarded, EF.upload(nlp, dirs), out=sentinel)
     assert dev[0] is sentinel and bool((sentinel.view(B, zs)[:, n:] == -7.25).all())
     hd = dict(dirs, Zref_dot=pad(dirs["Zref_dot"]))
     host = nlp.tracking_rollout_estimated_jvp_host(pad(h["Zref"]), h["K"], h["Lgain"], h["H"], pad(h["Zout"]), h["Xhat"], h["innov"],
@@ -291,8 +254,8 @@ def test_host_forms_equal_device_forms_and_padding_is_untouched(guarded, kw):
         else:
             assert np.array_equal(x, y.cpu().numpy()), name
     for wx in (True, False):
-        want = _want(h, wx)
-        dev = _vjp(nlp, d, guarded, _upload(nlp, cot), want)
+        want = EF.want(h, wx)
+        dev = _vjp(nlp, d, guarded, EF.upload(nlp, cot), want)
         host = nlp.tracking_rollout_estimated_vjp_host(pad(h["Zref"]), h["K"], h["Lgain"], h["H"], pad(h["Zout"]), h["Xhat"],
                                                        pad(cot["Zbar"]), h["innov"], h["model"], guarded, h["events"],
                                                        h["events_hat"], cot["Xhat_bar"], cot["innov_bar"], want)
@@ -344,12 +307,12 @@ def test_a_case_where_plant_and_estimator_land_in_different_knots():
     assert differ.sum() >= B // 4
     blk = ES.chain_blocks(N, np.asarray(batch.init_mode), None, h["Zout"], h["Xhat"], inp["model"], TC.SECOND, True, h["events"],
                           h["events_hat"])
-    dirs = _present(inp, dirs)
+    dirs = EF.present(inp, dirs)
     ref = ES.sweep_jvp(blk, inp["Zref"], inp["K"], inp["Lgain"], inp["H"], h["Zout"], h["Xhat"], h["innov"], events=h["events"],
                        events_hat=h["events_hat"], **dirs)
-    got = _host(nlp, JVP_OUT, _jvp(nlp, d, True, _upload(nlp, dirs)))
+    got = EF.host(nlp, JVP_OUT, _jvp(nlp, d, True, EF.upload(nlp, dirs)))
     w = max(ES.worst(got[n], ref[n]) for n in got)
-    got1 = _host(nlp, JVP_OUT, _jvp(nlp, d, True, _upload(nlp, one)))
+    got1 = EF.host(nlp, JVP_OUT, _jvp(nlp, d, True, EF.upload(nlp, one)))
     dp, hp = _rollout(nlp, dict(inp, x0=inp["x0"] + FD_EPS * xd), True)
     dm, hm = _rollout(nlp, dict(inp, x0=inp["x0"] - FD_EPS * xd), True)
     same = np.ones(B, dtype=bool)
@@ -380,7 +343,7 @@ def test_differentiable_estimated_rollout_backward_and_forward_ad_are_the_sweeps
         assert torch.equal(o, d[k])
     assert not any(o.requires_grad for o in out[3:])
     torch.autograd.backward(out[:3], [dc["Zbar"], dc["Xhat_bar"], dc["innov_bar"]])
-    ref = _vjp(nlp, d, guarded, dc, _want(r["h"], wx))
+    ref = _vjp(nlp, d, guarded, dc, EF.want(r["h"], wx))
     for k, g in zip(keys, ref):
         assert (leaves[k] is None and g is None) or torch.equal(leaves[k].grad.reshape(-1), g.reshape(-1)), k
     refj = _jvp(nlp, d, guarded, dd)

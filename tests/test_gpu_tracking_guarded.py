@@ -5,12 +5,12 @@ tests/test_tracking_guarded_host.py.  Besides it the kernels are held without an
 and bit for bit to qln_tracking_lqr / qln_tracking_covariance where no problem lands.  The cases and their seeds are
 tests/rollout_guarded_cases.py's."""
 import ctypes as C
-import faulthandler
 import functools
 
 import numpy as np
 import pytest
 
+from tests import estimation_cases as EF
 from tests import rollout_guarded_cases as GC
 from tests import rollout_guarded_sweep_ref as SR
 from tests import tracking_cases as TC
@@ -18,6 +18,7 @@ from tests import tracking_cov_ref as CR
 from tests import tracking_guarded_ref as TG
 
 pytestmark = pytest.mark.gpu
+_time_limit = EF.time_limit(600)
 
 BAR = 1e-10  # the unguarded tests' bar (tests/test_gpu_tracking.py, tests/test_gpu_tracking_cov.py)
 # The two comparisons between the GPU's own kernels: ten times what the same comparisons leave in numpy
@@ -28,20 +29,6 @@ DUALITY_BAR = 10 * 1.46e-14
 
 SHAPE_CASES = [("shape", N, im, B, wg) for (N, im, B) in GC.SHAPES for wg in (False, True)]
 CASES = SHAPE_CASES + [("ragged", 12, 0, 70, True), ("tau0", 5, 1, 3, False), ("tau0", 5, 2, 3, False)]
-
-
-@pytest.fixture(autouse=True)
-def _time_limit():
-    """Every test here is a GPU step with a time limit of its own: a hang ends the process with a traceback."""
-    faulthandler.dump_traceback_later(600, exit=True)
-    yield
-    faulthandler.cancel_dump_traceback_later()
-
-
-def _dev(a):
-    import torch
-
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _inputs(kind, N, im, B, wg):
@@ -65,7 +52,7 @@ def _run(kind, N, im, B, wg):
 
     batch, Zref, K, x0, th, ims, wm = _inputs(kind, N, im, B, wg)
     nlp = TC.nlp(batch, TC.SECOND_MODEL)
-    dev = dict(Zref=nlp.upload_Z(Zref), K=_dev(K), x0=_dev(x0), model=_dev(th) if wm else None)
+    dev = dict(Zref=nlp.upload_Z(Zref), K=EF.dev(K), x0=EF.dev(x0), model=EF.dev(th) if wm else None)
     Zout, ev = nlp.tracking_rollout_guarded(dev["Zref"], dev["K"], dev["x0"], dev["model"])
     zo, evh = TC.rows(nlp, Zout), ev.cpu().numpy()
     rng = np.random.default_rng(GC.seed_of(N, im, wg, wm) + 41)
@@ -125,13 +112,13 @@ def test_a_batch_that_never_lands_is_bitwise_the_knot_scheduled_calls_of_a_handl
     Zref[:, 15 + (3 if im == 1 else 1)::20] = -2.0  # every problem gets the last problem's pulling reference
     x0[:, iy], x0[:, iv] = 0.3, 0.0
     nlp, never = TC.nlp(batch, TC.SECOND_MODEL), TC.nlp(GC.with_k_trans(batch, N + 1), TC.SECOND_MODEL)
-    dZ, dK, dx = nlp.upload_Z(Zref), _dev(K), _dev(x0)
+    dZ, dK, dx = nlp.upload_Z(Zref), EF.dev(K), EF.dev(x0)
     Zout, ev = nlp.tracking_rollout_guarded(dZ, dK, dx)
     assert bool((ev[:, 0] == -1).all())
     rng = np.random.default_rng(N)
     S0, W = CR.random_psd(rng, shape=(B,)), rng.uniform(0.0, 1e-2, size=15)
     Kr, Pr = never.tracking_lqr(Zout, TC.QW, TC.R, TC.QFW)
-    for model in (None, _dev(np.tile(TC.SECOND, (B, 1)))):
+    for model in (None, EF.dev(np.tile(TC.SECOND, (B, 1)))):
         Kg, Pg = nlp.tracking_lqr_guarded(Zout, ev, TC.QW, TC.R, TC.QFW, model)
         assert torch.equal(Kg, Kr) and torch.equal(Pg, Pr)
         for k_ in (dK, None):
@@ -147,7 +134,7 @@ def test_cost_to_go_is_the_lq_cost_of_the_gpu_tangent_sweep_under_the_returned_g
     returned K: no oracle."""
     nlp, d, h, g, _ = _run(kind, N, im, B, wg)
     x = np.random.default_rng(N + B).normal(size=(B, 15))
-    zd, _ = nlp.tracking_rollout_guarded_jvp(d["Zout"], d["Zout"], d["ev"], g["K"], d["model"], x0_dot=_dev(x))
+    zd, _ = nlp.tracking_rollout_guarded_jvp(d["Zout"], d["Zout"], d["ev"], g["K"], d["model"], x0_dot=EF.dev(x))
     cost = TG.lq_cost(TC.rows(nlp, zd), N, TC.QW, TC.R, TC.QFW)
     quad = np.einsum("bi,bij,bj->b", x, g["Ph"][:, 0], x)
     w = float(np.max(np.abs(cost - quad) / np.abs(cost)))
@@ -186,7 +173,7 @@ def test_host_forms_equal_device_forms(kw):
     batch, Zref, K, x0, th = GC.ragged_case()
     B = batch.B
     nlp = TC.nlp(batch, TC.SECOND_MODEL, **kw)
-    dZ, dK, dx, dm = nlp.upload_Z(Zref), _dev(K), _dev(x0), _dev(th)
+    dZ, dK, dx, dm = nlp.upload_Z(Zref), EF.dev(K), EF.dev(x0), EF.dev(th)
     Zout, ev = nlp.tracking_rollout_guarded(dZ, dK, dx, dm)
     rng = np.random.default_rng(12)
     S0, W = CR.random_psd(rng, shape=(B,)), rng.uniform(0.0, 1e-2, size=15)
@@ -195,7 +182,7 @@ def test_host_forms_equal_device_forms(kw):
     Kh, Ph = nlp.tracking_lqr_guarded_host(zh, evh, TC.QW, TC.R, TC.QFW, th)
     assert np.array_equal(Kh, Kg.cpu().numpy()) and np.array_equal(Ph, Pg.cpu().numpy())
     for k_ in (K, None):
-        Sg, mg, vg = nlp.tracking_covariance_guarded(Zout, ev, _dev(k_), S0, W, dm)
+        Sg, mg, vg = nlp.tracking_covariance_guarded(Zout, ev, EF.dev(k_), S0, W, dm)
         Sh, mh, vh = nlp.tracking_covariance_guarded_host(zh, evh, k_, S0, W, th)
         assert np.array_equal(Sh, Sg.cpu().numpy()) and np.array_equal(mh, mg.cpu().numpy()) and np.array_equal(vh, vg.cpu().numpy())
     assert (evh[:, 0] >= 0).any() and vh[evh[:, 0] >= 0, 1].min() > 0
@@ -223,8 +210,8 @@ def test_invalid_arguments_are_refused():
     nlp = TC.nlp(batch, TC.SECOND_MODEL)
     L, h, INV, OK = _lib.lib(), nlp._h, _lib.QLN_ERR_INVALID_ARGUMENT, _lib.QLN_OK
     B, N = nlp.B, nlp.N
-    dZ, dK, dm = nlp.upload_Z(Zref), _dev(K), _dev(th)
-    Zout, ev = nlp.tracking_rollout_guarded(dZ, dK, _dev(x0), dm)
+    dZ, dK, dm = nlp.upload_Z(Zref), EF.dev(K), EF.dev(th)
+    Zout, ev = nlp.tracking_rollout_guarded(dZ, dK, EF.dev(x0), dm)
     f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device="cuda")  # noqa: E731
     Ko, Po, So, mo, vo, S0 = f64(B, N - 1, 4, 15), f64(B, N, 120), f64(B, N, 120), f64(B, N, 8), f64(B, 2), f64(120)
     p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731

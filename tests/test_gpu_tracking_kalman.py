@@ -5,20 +5,20 @@ blocks of tests/rollout_guarded_sweep_ref.py.  Besides it the kernel is held wit
 the open-loop covariance sweep, ny rows are bit for bit eight rows with zero rows written out, every subset of outputs has
 the bits of the full call, and the host forms have the bits of the device forms."""
 import ctypes as C
-import faulthandler
 import functools
 import itertools
 
 import numpy as np
 import pytest
 
+from tests import estimation_cases as EF
 from tests import rollout_guarded_cases as GC
-from tests import rollout_guarded_sweep_ref as SR
 from tests import tracking_cases as TC
 from tests import tracking_cov_ref as CR
 from tests import tracking_kalman_ref as KR
 
 pytestmark = pytest.mark.gpu
+_time_limit = EF.time_limit(600)
 
 BAR = 1e-10  # the family's bar (tests/test_gpu_tracking_cov.py, tests/test_gpu_tracking_guarded.py)
 # A problem's inputs are well conditioned in the compared measures when the float64 yardstick is itself within BAR / 100 of its
@@ -31,38 +31,9 @@ BAR = 1e-10  # the family's bar (tests/test_gpu_tracking_cov.py, tests/test_gpu_
 COND = BAR / 100
 REDRAWS = 200
 
-
-def _shapes():
-    """N = 2 (one step, two updates), 3, and 17, 33 across the sixteen-knot chunk of the clearance cosines; k_trans in
-    {1, 2, N, N + 1}, both init_modes; B = 3 (a partly filled wave) and 5 (a second wave with one row); ny and sigma0_batch
-    take turns."""
-    out = []
-    for i, (N, kt, im) in enumerate(itertools.product((2, 3, 17, 33), ("1", "2", "N", "N+1"), (1, 2))):
-        k_trans = {"1": 1, "2": 2, "N": N, "N+1": N + 1}[kt]
-        out.append(("shape", 3 if i % 2 else 5, N, k_trans, im, (8, 3, 1)[i % 3], bool(i % 4 < 2)))
-    return out
-
-
-CASES = _shapes() + [("ragged", 9, 17, 6, 1, 8, True), ("ragged", 6, 33, 12, 2, 3, False)]
-GUARDED = [("shape", N, im, B, wg) for (N, im, B) in GC.SHAPES for wg in (False, True)] + [("ragged", 12, 0, 70, True)]
-
-
-@pytest.fixture(autouse=True)
-def _time_limit():
-    """Every test here is a GPU step with a time limit of its own: a hang ends the process with a traceback."""
-    faulthandler.dump_traceback_later(600, exit=True)
-    yield
-    faulthandler.cancel_dump_traceback_later()
-
-
-def _dev(a):
-    import torch
-
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def measurement(rng, ny):
-    return rng.normal(size=(ny, 15)) / np.sqrt(15.0), rng.uniform(0.5, 2.0, size=ny)
+# EF.design_shapes() with sigma0_batch taking turns; the guarded shapes without and with gains
+CASES = [c + (i % 4 < 2,) for i, c in enumerate(EF.design_shapes())] + [EF.RAGGED[0] + (True,), EF.RAGGED[1] + (False,)]
+GUARDED = [s + (wg,) for s in EF.GUARDED_SHAPES for wg in (False, True)] + [EF.GUARDED_RAGGED + (True,)]
 
 
 def _host(t):
@@ -101,34 +72,28 @@ def _conditioned_gains(K, seed, yardsticks):
     return K, refs, worst, redrawn
 
 
+def _design(A, Bm, K, H, V, S0, W, theta, lb):
+    """The yardstick of one knot-scheduled problem in the dtype of its arrays: the recursion, and the marginals of its X and M"""
+    r = KR.recursion(A, Bm, K, H, V, S0, W)
+    r["marg"] = KR.marginals(r["X"], r["M"], K, theta, A.dtype.type(lb))
+    return r
+
+
 @functools.lru_cache(maxsize=None)
 def _run(kind, B, N, k_trans, im, ny, per_problem):
     """One knot-scheduled case: the handle, the inputs, the GPU's outputs and the yardstick's on the evaluator's dense blocks
     at the same Zout, with the yardstick's own float64-to-longdouble distance.  Shared by the case's tests, never changed."""
-    seed = 100 * N + 10 * k_trans + im
-    batch = TC.batch(B, N, k_trans, im, seed=seed, ragged=kind == "ragged")
-    nlp, K, Zout, S0, W = TC.cov_setup(batch, seed, True)
-    if not per_problem:
-        S0 = S0[0]
-    H, V = measurement(np.random.default_rng(seed + 5), ny)
-    blocks = TC.evaluator_blocks(nlp, Zout)
-    zo = TC.rows(nlp, Zout)
-    ld = np.longdouble
+    d = EF.scheduled_design(kind, B, N, k_trans, im, ny, 5)
+    nlp, Zout, H, V, W = d.nlp, d.Zout, d.H, d.V, d.W
+    S0 = d.S0 if per_problem else d.S0[0]
 
     def yardsticks(b, Kb):
-        F = blocks(b, zo[b])
-        s0 = S0[b] if per_problem else S0
-        theta = zo[b][2 + 20 * np.arange(N)]
-        out = []
-        for dt in (np.float64, ld):
-            r = KR.recursion(F[:, :, :15].astype(dt), F[:, :, 15:19].astype(dt), Kb.astype(dt), H.astype(dt), V.astype(dt),
-                             s0.astype(dt), W.astype(dt))
-            r["marg"] = KR.marginals(r["X"], r["M"], Kb.astype(dt), theta.astype(dt), dt(nlp.model.lb))
-            out.append(r)
-        return out
+        F = d.blocks(b, d.zo[b])
+        return EF.in_both_precisions(_design, F[:, :, :15], F[:, :, 15:19], Kb, H, V, S0[b] if per_problem else S0, W,
+                                     d.zo[b][2 + 20 * np.arange(N)], lb=nlp.model.lb)
 
-    Kh, refs, dist, redrawn = _conditioned_gains(TC.to_np(K), seed, yardsticks)
-    K = _dev(Kh)
+    Kh, refs, dist, redrawn = _conditioned_gains(TC.to_np(d.K), d.seed, yardsticks)
+    K = EF.dev(Kh)
     ref = {n: np.stack([r[n] for r in refs]) for n in ("L", "Pm", "Pp", "X", "marg")}
     got = nlp.tracking_kalman(Zout, H, V, K, S0, W)
     inp = dict(Zout=Zout, K=K, H=H, V=V, S0=S0, W=W, redrawn=redrawn)
@@ -214,33 +179,15 @@ def test_every_subset_of_outputs_has_the_bits_of_the_full_call(kind, B, N, k_tra
 
 
 # ---- 6. through the guarded touchdown -------------------------------------------------------------------------------------
-def _guarded_inputs(kind, N, im, B, wg):
-    if kind == "shape":
-        batch, Zref, K, x0, th = GC.case(N, im, B, wg, wg)
-        return batch, Zref, K, x0, th, im, wg
-    batch, Zref, K, x0, th = GC.ragged_case()
-    return batch, Zref, K, x0, th, np.asarray(batch.init_mode), True
-
-
 @functools.lru_cache(maxsize=None)
 def _run_guarded(kind, N, im, B, wg):
-    batch, Zref, K, x0, th, ims, wm = _guarded_inputs(kind, N, im, B, wg)
-    nlp = TC.nlp(batch, TC.SECOND_MODEL)
-    dK, dm = _dev(K), _dev(th) if wm else None
-    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), dK, _dev(x0), dm)
-    zo, evh = TC.rows(nlp, Zout), ev.cpu().numpy()
-    rng = np.random.default_rng(GC.seed_of(N, im, wg, wm) + 43)
-    ny = (8, 3, 1)[(N + B) % 3]
-    S0, W = CR.random_psd(rng, shape=(B,)), rng.uniform(0.0, 1e-2, size=15)
-    H, V = measurement(rng, ny)
-    F, T = SR.blocks(N, ims, zo, th, evh)
-    ld = np.longdouble
+    d = EF.guarded_design(kind, N, im, B, wg, wg)
+    nlp, Zout, ev, evh, H, V, S0, W, K, dK = d.nlp, d.Zout, d.ev, d.evh, d.H, d.V, d.S0, d.W, d.K, d.dK
 
     def yardsticks(b, Kb):
         s = slice(b, b + 1)
-        return [KR.guarded(F[s].astype(dt), T[s].astype(dt), evh[s], None if Kb is None else Kb[None].astype(dt), H.astype(dt),
-                           V.astype(dt), S0[s].astype(dt), W.astype(dt), zo[s, 2::20].astype(dt), th[s, 3].astype(dt))
-                for dt in (np.float64, ld)]
+        return EF.in_both_precisions(lambda F, T, *rest: KR.guarded(F, T, evh[s], *rest), d.F[s], d.T[s],
+                                     None if Kb is None else Kb[None], H, V, S0[s], W, d.zo[s, 2::20], d.th[s, 3])
 
     redrawn = 0
     if K is None:  # the filter alone: nothing of it depends on gains
@@ -249,11 +196,11 @@ def _run_guarded(kind, N, im, B, wg):
         dist = max(CR.knot_rel(lo[n], hi[n]) for lo, hi in pairs for n in ("L", "Pp"))
     else:
         # the roll-out keeps the gains it ran under; the call takes Zout and K independently, as the header says
-        K, refs, dist, redrawn = _conditioned_gains(K, GC.seed_of(N, im, wg, wm), yardsticks)
-        dK = _dev(K)
+        K, refs, dist, redrawn = _conditioned_gains(K, d.seed, yardsticks)
+        dK = EF.dev(K)
     ref = {n: np.concatenate([r[n] for r in refs]) for n in refs[0]}
-    got = nlp.tracking_kalman_guarded(Zout, ev, H, V, dK, S0, W, dm)
-    inp = dict(Zout=Zout, ev=ev, K=dK, model=dm, H=H, V=V, S0=S0, W=W, evh=evh, redrawn=redrawn)
+    got = nlp.tracking_kalman_guarded(Zout, ev, H, V, dK, S0, W, d.model)
+    inp = dict(Zout=Zout, ev=ev, K=dK, model=d.model, H=H, V=V, S0=S0, W=W, evh=evh, redrawn=redrawn)
     return nlp, inp, got, _host(got), ref, dist
 
 
@@ -314,15 +261,15 @@ def test_a_batch_that_never_lands_is_bitwise_the_knot_scheduled_call_of_a_handle
     Zref[:, 15 + (3 if im == 1 else 1)::20] = -2.0  # every problem gets the last problem's pulling reference
     x0[:, iy], x0[:, iv] = 0.3, 0.0
     nlp, never = TC.nlp(batch, TC.SECOND_MODEL), TC.nlp(GC.with_k_trans(batch, N + 1), TC.SECOND_MODEL)
-    dK = _dev(K)
-    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), dK, _dev(x0))
+    dK = EF.dev(K)
+    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), dK, EF.dev(x0))
     assert bool((ev[:, 0] == -1).all())
     rng = np.random.default_rng(N)
     S0, W = CR.random_psd(rng, shape=(B,)), rng.uniform(0.0, 1e-2, size=15)
-    H, V = measurement(rng, 3)
+    H, V = EF.measurement(rng, 3)
     for k_ in (dK, None):
         ref = never.tracking_kalman(Zout, H, V, k_, S0, W)
-        for model in (None, _dev(np.tile(TC.SECOND, (B, 1)))):
+        for model in (None, EF.dev(np.tile(TC.SECOND, (B, 1)))):
             got = nlp.tracking_kalman_guarded(Zout, ev, H, V, k_, S0, W, model)
             for g, r in zip(got[:4], ref):
                 assert (g is None and r is None) or torch.equal(g, r)
@@ -336,11 +283,11 @@ def test_host_forms_equal_device_forms_after_other_host_calls_left_nans_behind(B
     N = 12
     batch, Zref, K, x0, th = GC.ragged_case(B=B, N=N)
     nlp = TC.nlp(batch, TC.SECOND_MODEL)
-    dK, dm = _dev(K), _dev(th)
-    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), dK, _dev(x0), dm)
+    dK, dm = EF.dev(K), EF.dev(th)
+    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), dK, EF.dev(x0), dm)
     rng = np.random.default_rng(B)
     S0, W = CR.random_psd(rng, shape=(B,)), rng.uniform(0.0, 1e-2, size=15)
-    H, V = measurement(rng, 3)
+    H, V = EF.measurement(rng, 3)
     zh, evh = Zout.cpu().numpy(), ev.cpu().numpy()
     nan = lambda *s: np.full(s, np.nan)  # noqa: E731
     with np.errstate(all="ignore"):
@@ -348,11 +295,11 @@ def test_host_forms_equal_device_forms_after_other_host_calls_left_nans_behind(B
         nlp.tracking_covariance_guarded_host(nan(*zh.shape), evh, nan(*K.shape), nan(B, 120), None, th)
         nlp.tracking_kalman_host(nan(*zh.shape), np.ones((8, 15)), 1.0, nan(*K.shape), nan(B, 120), None)
     for k_ in (K, None):
-        dev = nlp.tracking_kalman(Zout, H, V, _dev(k_), S0, W)
+        dev = nlp.tracking_kalman(Zout, H, V, EF.dev(k_), S0, W)
         host = nlp.tracking_kalman_host(zh, H, V, k_, S0, W)
         for d, h in zip(dev, host):
             assert (d is None and h is None) or np.array_equal(h, d.cpu().numpy())
-        dev = nlp.tracking_kalman_guarded(Zout, ev, H, V, _dev(k_), S0[0], W, dm)
+        dev = nlp.tracking_kalman_guarded(Zout, ev, H, V, EF.dev(k_), S0[0], W, dm)
         host = nlp.tracking_kalman_guarded_host(zh, evh, H, V, k_, S0[0], W, th)
         for d, h in zip(dev, host):
             assert (d is None and h is None) or np.array_equal(h, d.cpu().numpy())
@@ -369,8 +316,8 @@ def test_invalid_arguments_are_refused():
     nlp = TC.nlp(batch, TC.SECOND_MODEL)
     L, h, INV, OK = _lib.lib(), nlp._h, _lib.QLN_ERR_INVALID_ARGUMENT, _lib.QLN_OK
     B, N = nlp.B, nlp.N
-    dK, dm = _dev(K), _dev(th)
-    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), dK, _dev(x0), dm)
+    dK, dm = EF.dev(K), EF.dev(th)
+    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), dK, EF.dev(x0), dm)
     f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device="cuda")  # noqa: E731
     Lo, Po, So, mo, vo, S0, Hd = f64(B, N, 15, 8), f64(B, N, 120), f64(B, N, 120), f64(B, N, 8), f64(B, 2), f64(120), f64(8, 15)
     p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731

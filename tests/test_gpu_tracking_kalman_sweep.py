@@ -5,61 +5,31 @@ dense blocks, and for the guarded call on the complex-step blocks of tests/rollo
 is held without an oracle: with zero gains it is bit for bit the open-loop covariance sweep, ny rows are eight rows with zeros
 written out, every subset of outputs has the full call's bits, the host forms have the device forms' bits, it is linear in the
 direction, and it agrees with central differences of the GPU's own design and of the GPU's own log-likelihood under redesign.
-Shapes: tests/test_gpu_tracking_kalman.py's.  Worst figures: profiles/tracking_kalman_jvp_tests.txt."""
+Shapes: tests/estimation_cases.py's.  Worst figures: profiles/tracking_kalman_jvp_tests.txt."""
 import ctypes as C
-import faulthandler
 import functools
 import itertools
 
 import numpy as np
 import pytest
 
+from tests import estimation_cases as EF
 from tests import landing_filter_sweep_ref as FS
 from tests import rollout_guarded_cases as GC
-from tests import rollout_guarded_sweep_ref as SR
 from tests import tracking_cases as TC
 from tests import tracking_cov_ref as CR
 from tests import tracking_guarded_ref as TG
 from tests import tracking_kalman_sweep_ref as KS
 
 pytestmark = pytest.mark.gpu
+_time_limit = EF.time_limit(300)
 
 BAR = 1e-10  # the family's bar; raised to 100 x the yardstick's own float64-to-longdouble distance where that is larger
 OUT = ("Lgain", "Pest", "logdet")
-LD = np.longdouble
 
-
-def _shapes():
-    """N = 2 (one step, two updates), 3, and 17, 33 across a sixteen-knot chunk; k_trans in {1, 2, N, N + 1}, both
-    init_modes; B = 3 (a partly filled wave) and 5 (a second wave with one row); ny and sigma0_batch take turns."""
-    out = []
-    for i, (N, kt, im) in enumerate(itertools.product((2, 3, 17, 33), ("1", "2", "N", "N+1"), (1, 2))):
-        k_trans = {"1": 1, "2": 2, "N": N, "N+1": N + 1}[kt]
-        out.append(("shape", 3 if i % 2 else 5, N, k_trans, im, (8, 3, 1)[i % 3], bool(i % 4 < 2), i == 21))
-    return out
-
-
-# (kind, B, N, k_trans, init_mode, ny, a Sigma0_dot per problem, the handle at TC.SECOND_MODEL)
-CASES = _shapes() + [("ragged", 9, 17, 6, 1, 8, True, False), ("ragged", 6, 33, 12, 2, 3, False, True)]
-GUARDED = [(N, im, B, wm) for (N, im, B) in GC.SHAPES for wm in (False, True)]
-
-
-@pytest.fixture(autouse=True)
-def _time_limit():
-    """Every test here is a GPU step with a time limit of its own: a hang ends the process with a traceback."""
-    faulthandler.dump_traceback_later(300, exit=True)
-    yield
-    faulthandler.cancel_dump_traceback_later()
-
-
-def _dev(a):
-    import torch
-
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).cuda()
-
-
-def measurement(rng, ny):
-    return rng.normal(size=(ny, 15)) / np.sqrt(15.0), rng.uniform(0.5, 2.0, size=ny)
+# EF.design_shapes() and (a Sigma0_dot per problem, the handle at TC.SECOND_MODEL): the first takes turns, the second is one case
+CASES = [c + (i % 4 < 2, i == 21) for i, c in enumerate(EF.design_shapes())] + [EF.RAGGED[0] + (True, False), EF.RAGGED[1] + (False, True)]
+GUARDED = [s[1:] + (wm,) for s in EF.GUARDED_SHAPES for wm in (False, True)]  # (N, init_mode, B, a model per problem)
 
 
 def _host(res):
@@ -74,8 +44,7 @@ def _reference(A_of, B, H, V, Lh, S0d, Wd, Vd, per_problem):
     for b in range(B):
         A = A_of(b)
         s0d = S0d[b] if per_problem else S0d
-        lo = KS.sweep(A, H, V, Lh[b], s0d, Wd, Vd)
-        hi = KS.sweep(A.astype(LD), H.astype(LD), V.astype(LD), Lh[b].astype(LD), s0d.astype(LD), Wd.astype(LD), Vd.astype(LD))
+        lo, hi = EF.in_both_precisions(KS.sweep, A, H, V, Lh[b], s0d, Wd, Vd)
         dist = np.maximum(dist, KS.errors(lo, hi))
         refs.append(lo)
     return {n: np.stack([r[n] for r in refs]) for n in ("Ld", "Pd", "logdet")}, dist
@@ -85,37 +54,26 @@ def _reference(A_of, B, H, V, Lh, S0d, Wd, Vd, per_problem):
 def _run(kind, B, N, k_trans, im, ny, per_problem, second):
     """One knot-scheduled case: the handle, the GPU's own design, one direction, the GPU's sweep and the yardstick's on the
     evaluator's dense blocks at the same Zout.  Shared by the case's tests, never changed."""
-    seed = 100 * N + 10 * k_trans + im
-    batch = TC.batch(B, N, k_trans, im, seed=seed, ragged=kind == "ragged")
-    nlp, _, Zout, S0, W = TC.cov_setup(batch, seed, True, **({"model": TC.SECOND_MODEL} if second else {}))
-    H, V = measurement(np.random.default_rng(seed + 5), ny)
+    d = EF.scheduled_design(kind, B, N, k_trans, im, ny, 5, **({"model": TC.SECOND_MODEL} if second else {}))
+    nlp, Zout, H, V, S0, W = d.nlp, d.Zout, d.H, d.V, d.S0, d.W
     L, Pe, _, _ = nlp.tracking_kalman(Zout, H, V, None, S0, W)
-    S0d, Wd, Vd = KS.directions(seed + 9, ny, (B,) if per_problem else ())
+    S0d, Wd, Vd = KS.directions(d.seed + 9, ny, (B,) if per_problem else ())
     got = nlp.tracking_kalman_jvp(Zout, L, H, V, S0d, Wd, Vd)
-    blocks, zo = TC.evaluator_blocks(nlp, Zout), TC.rows(nlp, Zout)
-    ref, dist = _reference(lambda b: blocks(b, zo[b])[:, :, :15], B, H, V, TC.to_np(L), S0d, Wd, Vd, per_problem)
-    inp = dict(Zout=Zout, L=L, H=H, V=V, S0=S0, W=W, S0d=S0d, Wd=Wd, Vd=Vd, blocks=blocks, zo=zo)
+    ref, dist = _reference(lambda b: d.blocks(b, d.zo[b])[:, :, :15], B, H, V, TC.to_np(L), S0d, Wd, Vd, per_problem)
+    inp = dict(Zout=Zout, L=L, H=H, V=V, S0=S0, W=W, S0d=S0d, Wd=Wd, Vd=Vd, blocks=d.blocks, zo=d.zo)
     return nlp, inp, got, ref, dist
 
 
 @functools.lru_cache(maxsize=None)
 def _run_guarded(N, im, B, wm):
-    batch, Zref, K, x0, th = GC.case(N, im, B, True, wm)
-    nlp = TC.nlp(batch, TC.SECOND_MODEL)
-    dm = _dev(th) if wm else None
-    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), _dev(K), _dev(x0), dm)
-    zo, evh = TC.rows(nlp, Zout), ev.cpu().numpy()
-    rng = np.random.default_rng(GC.seed_of(N, im, True, wm) + 43)
-    ny = (8, 3, 1)[(N + B) % 3]
-    S0, W = CR.random_psd(rng, shape=(B,)), rng.uniform(0.0, 1e-2, size=15)
-    H, V = measurement(rng, ny)
+    d = EF.guarded_design("shape", N, im, B, True, wm)
+    nlp, Zout, ev, dm, H, V, S0, W = d.nlp, d.Zout, d.ev, d.model, d.H, d.V, d.S0, d.W
     L, Pe = nlp.tracking_kalman_guarded(Zout, ev, H, V, None, S0, W, dm)[:2]
-    S0d, Wd, Vd = KS.directions(N + B, ny, (B,))
+    S0d, Wd, Vd = KS.directions(N + B, H.shape[0], (B,))
     got = nlp.tracking_kalman_jvp(Zout, L, H, V, S0d, Wd, Vd, events=ev, model=dm, guarded=True)
-    F, _ = SR.blocks(N, im, zo, th, evh)
-    A, _ = TG.split(F)
+    A, _ = TG.split(d.F)
     ref, dist = _reference(lambda b: A[b], B, H, V, TC.to_np(L), S0d, Wd, Vd, True)
-    inp = dict(Zout=Zout, ev=ev, evh=evh, model=dm, L=L, H=H, V=V, S0=S0, W=W, S0d=S0d, Wd=Wd, Vd=Vd)
+    inp = dict(Zout=Zout, ev=ev, evh=d.evh, model=dm, L=L, H=H, V=V, S0=S0, W=W, S0d=S0d, Wd=Wd, Vd=Vd)
     return nlp, inp, got, ref, dist
 
 
@@ -227,11 +185,11 @@ def test_host_forms_have_the_device_forms_bits_and_nan_where_nothing_is_read_cha
     N, B, ny = 12, 70, 3
     batch, Zref, K, x0, th = GC.ragged_case(B=B, N=N)
     nlp = TC.nlp(batch, TC.SECOND_MODEL, z_stride=20 * N - 5 + 2)
-    dm = _dev(th)
-    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), _dev(K), _dev(x0), dm)
+    dm = EF.dev(th)
+    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), EF.dev(K), EF.dev(x0), dm)
     rng = np.random.default_rng(B)
     S0, W = CR.random_psd(rng, shape=(B,)), rng.uniform(0.0, 1e-2, size=15)
-    H, V = measurement(rng, ny)
+    H, V = EF.measurement(rng, ny)
     S0d, Wd, Vd = KS.directions(3, ny, (B,))
     kw = dict(events=ev, model=dm, guarded=True) if guarded else {}
     L = (nlp.tracking_kalman_guarded(Zout, ev, H, V, None, S0, W, dm) if guarded else nlp.tracking_kalman(Zout, H, V, None, S0, W))[0]
@@ -263,15 +221,15 @@ def test_a_batch_that_never_lands_is_bitwise_the_knot_scheduled_call_of_a_handle
     Zref[:, 15 + (3 if im == 1 else 1)::20] = -2.0  # every problem gets the last problem's pulling reference
     x0[:, iy], x0[:, iv] = 0.3, 0.0
     nlp, never = TC.nlp(batch, TC.SECOND_MODEL), TC.nlp(GC.with_k_trans(batch, N + 1), TC.SECOND_MODEL)
-    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), _dev(K), _dev(x0))
+    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), EF.dev(K), EF.dev(x0))
     assert bool((ev[:, 0] == -1).all())
     rng = np.random.default_rng(N)
     S0, W = CR.random_psd(rng, shape=(B,)), rng.uniform(0.0, 1e-2, size=15)
-    H, V = measurement(rng, 3)
+    H, V = EF.measurement(rng, 3)
     S0d, Wd, Vd = KS.directions(N, 3, (B,))
     L = never.tracking_kalman(Zout, H, V, None, S0, W)[0]
     ref = never.tracking_kalman_jvp(Zout, L, H, V, S0d, Wd, Vd)
-    for model in (None, _dev(np.tile(TC.SECOND, (B, 1)))):
+    for model in (None, EF.dev(np.tile(TC.SECOND, (B, 1)))):
         got = nlp.tracking_kalman_jvp(Zout, L, H, V, S0d, Wd, Vd, events=ev, model=model, guarded=True)
         assert all(torch.equal(got[k], ref[k]) for k in OUT)
 
@@ -314,7 +272,7 @@ def test_a_direction_behind_ny_cannot_be_expressed_and_process_noise_alone_leave
     import torch
 
     f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device="cuda")  # noqa: E731
-    Hd, V8, vd = _dev(inp["H"]), np.ones(8), np.zeros(8)
+    Hd, V8, vd = EF.dev(inp["H"]), np.ones(8), np.zeros(8)
     V8[:ny], vd[:ny] = inp["V"], inp["Vd"]
     outs = []
     for tail in (0.0, 5.0):
@@ -387,7 +345,7 @@ def test_landing_loglik_jvp_against_the_gpus_loglik_under_redesign(N, guarded):
     S0d, Wd, Vd = KS.directions(7 + N, ny, (B,))
     S0d, Wd, Vd = 1e-4 * S0d, 1e-4 * Wd, 1e-4 * Vd
     Zref, Zrec = nlp.upload_Z(rec["Zref"]), nlp.upload_Z(rec["Zrec"])
-    Y, xh0, model = _dev(rec["Y"]), _dev(rec["xhat0"]), _dev(rec["model"])
+    Y, xh0, model = EF.dev(rec["Y"]), EF.dev(rec["xhat0"]), EF.dev(rec["model"])
     filt = nlp.landing_filter_guarded if guarded else nlp.landing_filter
 
     def gpu(s):
@@ -440,7 +398,7 @@ def test_refusals_behind_the_handle():
     f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device="cuda")  # noqa: E731
     p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
     a = lambda v: None if v is None else v.ctypes.data  # noqa: E731
-    Hd, S0d = _dev(inp["H"]), f64(B, 120)
+    Hd, S0d = EF.dev(inp["H"]), f64(B, 120)
     Ld, Pd, ld = f64(B, N, 15, ny), f64(B, N, 120), f64(B, N)
     V, Wd, Vd = inp["V"], inp["Wd"], inp["Vd"]
     jvp, gjvp = L.qln_kalman_design_jvp, L.qln_kalman_design_guarded_jvp

@@ -6,22 +6,21 @@ in advance: the kernel's distance from the longdouble yardstick is set against t
 case, the duality of the two kernels and the linearity against what the float64 numpy pair leaves, ten times each.  Besides that
 the kernel is held bit for bit: a NULL cotangent is explicit zeros, every subset of outputs has the full call's bits, ny rows are
 eight rows with zeros written out, the host forms have the device forms' bits, NaN where nothing is read changes nothing, and a
-batch that never lands is the knot-scheduled call.  Shapes: tests/test_gpu_tracking_kalman.py's kinds at N = 5 and 17, B no
+batch that never lands is the knot-scheduled call.  Shapes: tests/estimation_cases.py's kinds at N = 5 and 17, B no
 multiple of four.  Worst figures: profiles/tracking_kalman_vjp_tests.txt.
 
 The kernel reads every knot of Lgain whatever the cotangents are (a zero cotangent takes the path of a given one), so there is no
 case with NaN in the gains behind the last knot that carries a cotangent."""
 import ctypes as C
-import faulthandler
 import functools
 import itertools
 
 import numpy as np
 import pytest
 
+from tests import estimation_cases as EF
 from tests import landing_filter_sweep_ref as FS
 from tests import rollout_guarded_cases as GC
-from tests import rollout_guarded_sweep_ref as SR
 from tests import tracking_cases as TC
 from tests import tracking_cov_ref as CR
 from tests import tracking_guarded_ref as TG
@@ -29,6 +28,7 @@ from tests import tracking_kalman_sweep_ref as KS
 from tests import tracking_kalman_vjp_ref as KV
 
 pytestmark = pytest.mark.gpu
+_time_limit = EF.time_limit(300)
 
 OUT = KV.OUT
 COT = ("Lgain_bar", "Pest_bar", "logdet_bar")
@@ -42,24 +42,6 @@ CASES = [("shape", 3, 5, 3, 2, 3, False), ("shape", 5, 17, 6, 1, 8, True), ("sha
 GUARDED = [(5, 2, 6, True, 3), (17, 1, 3, False, 8), (17, 1, 3, True, 1)]
 
 
-@pytest.fixture(autouse=True)
-def _time_limit():
-    """Every test here is a GPU step with a time limit of its own: a hang ends the process with a traceback."""
-    faulthandler.dump_traceback_later(300, exit=True)
-    yield
-    faulthandler.cancel_dump_traceback_later()
-
-
-def _dev(a):
-    import torch
-
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).cuda()
-
-
-def measurement(rng, ny):
-    return rng.normal(size=(ny, 15)) / np.sqrt(15.0), rng.uniform(0.5, 2.0, size=ny)
-
-
 def _host(res):
     return {k: TC.to_np(v) for k, v in res.items()}
 
@@ -68,51 +50,33 @@ def _cast(dt, *a):
     return tuple(None if x is None else np.asarray(x).astype(dt) for x in a)
 
 
-def _yardsticks(A, H, V, Lh, cot):
-    """(the float64 yardstick, the longdouble one) on the blocks A (B, N-1, 15, 15) at the GPU's gains"""
-    lo = KV.sweep(A, H, V, Lh, *cot)
-    hi = KV.sweep(*_cast(LD, A, H, V, Lh), *_cast(LD, *cot))
-    return lo, hi
-
-
 @functools.lru_cache(maxsize=None)
 def _run(kind, B, N, k_trans, im, ny, second):
     """One knot-scheduled case: the handle, the GPU's own design, one set of cotangents, the GPU's sweep and the two yardsticks
-    on the evaluator's dense blocks at the same Zout.  Shared by the case's tests, never changed."""
-    seed = 100 * N + 10 * k_trans + im
-    batch = TC.batch(B, N, k_trans, im, seed=seed, ragged=kind == "ragged")
-    nlp, _, Zout, S0, W = TC.cov_setup(batch, seed, True, **({"model": TC.SECOND_MODEL} if second else {}))
-    H, V = measurement(np.random.default_rng(seed + 5), ny)
+    (float64 and longdouble) on the evaluator's dense blocks at the same Zout.  Shared by the case's tests, never changed."""
+    d = EF.scheduled_design(kind, B, N, k_trans, im, ny, 5, **({"model": TC.SECOND_MODEL} if second else {}))
+    nlp, Zout, H, V, S0, W = d.nlp, d.Zout, d.H, d.V, d.S0, d.W
     L = nlp.tracking_kalman(Zout, H, V, None, S0, W)[0]
-    cot = KV.cotangents(seed + 11, N, ny, (B,))
-    dcot = tuple(_dev(c) for c in cot)
+    cot = KV.cotangents(d.seed + 11, N, ny, (B,))
+    dcot = tuple(EF.dev(c) for c in cot)
     got = nlp.tracking_kalman_vjp(Zout, L, H, V, *dcot)
-    blocks, zo = TC.evaluator_blocks(nlp, Zout), TC.rows(nlp, Zout)
-    A = np.stack([blocks(b, zo[b])[:, :, :15] for b in range(B)])
-    lo, hi = _yardsticks(A, H, V, TC.to_np(L), cot)
-    inp = dict(Zout=Zout, L=L, H=H, V=V, S0=S0, W=W, cot=cot, dcot=dcot, A=A, kw={})
+    lo, hi = EF.in_both_precisions(KV.sweep, d.A, H, V, TC.to_np(L), *cot)
+    inp = dict(Zout=Zout, L=L, H=H, V=V, S0=S0, W=W, cot=cot, dcot=dcot, A=d.A, kw={})
     return nlp, inp, got, lo, hi
 
 
 @functools.lru_cache(maxsize=None)
 def _run_guarded(N, im, B, wm, ny):
-    batch, Zref, K, x0, th = GC.case(N, im, B, True, wm)
-    nlp = TC.nlp(batch, TC.SECOND_MODEL)
-    dm = _dev(th) if wm else None
-    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), _dev(K), _dev(x0), dm)
-    zo, evh = TC.rows(nlp, Zout), ev.cpu().numpy()
-    rng = np.random.default_rng(GC.seed_of(N, im, True, wm) + 43)
-    S0, W = CR.random_psd(rng, shape=(B,)), rng.uniform(0.0, 1e-2, size=15)
-    H, V = measurement(rng, ny)
+    d = EF.guarded_design("shape", N, im, B, True, wm, ny)
+    nlp, Zout, ev, dm, H, V, S0, W = d.nlp, d.Zout, d.ev, d.model, d.H, d.V, d.S0, d.W
     L = nlp.tracking_kalman_guarded(Zout, ev, H, V, None, S0, W, dm)[0]
     cot = KV.cotangents(N + B, N, ny, (B,))
-    dcot = tuple(_dev(c) for c in cot)
+    dcot = tuple(EF.dev(c) for c in cot)
     kw = dict(events=ev, model=dm, guarded=True)
     got = nlp.tracking_kalman_vjp(Zout, L, H, V, *dcot, **kw)
-    F, _ = SR.blocks(N, im, zo, th, evh)
-    A, _ = TG.split(F)
-    lo, hi = _yardsticks(A, H, V, TC.to_np(L), cot)
-    inp = dict(Zout=Zout, ev=ev, evh=evh, model=dm, th=th, L=L, H=H, V=V, S0=S0, W=W, cot=cot, dcot=dcot, A=A, kw=kw)
+    A, _ = TG.split(d.F)
+    lo, hi = EF.in_both_precisions(KV.sweep, A, H, V, TC.to_np(L), *cot)
+    inp = dict(Zout=Zout, ev=ev, evh=d.evh, model=dm, th=d.th, L=L, H=H, V=V, S0=S0, W=W, cot=cot, dcot=dcot, A=A, kw=kw)
     return nlp, inp, got, lo, hi
 
 
@@ -243,13 +207,13 @@ def test_host_forms_have_the_device_forms_bits_and_nan_where_nothing_is_read_cha
     N, B, ny = 12, 70, 3
     batch, Zref, K, x0, th = GC.ragged_case(B=B, N=N)
     nlp = TC.nlp(batch, TC.SECOND_MODEL, z_stride=20 * N - 5 + 2)
-    dm = _dev(th)
-    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), _dev(K), _dev(x0), dm)
+    dm = EF.dev(th)
+    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), EF.dev(K), EF.dev(x0), dm)
     rng = np.random.default_rng(B)
     S0, W = CR.random_psd(rng, shape=(B,)), rng.uniform(0.0, 1e-2, size=15)
-    H, V = measurement(rng, ny)
+    H, V = EF.measurement(rng, ny)
     cot = KV.cotangents(3, N, ny, (B,))
-    dcot = tuple(_dev(c) for c in cot)
+    dcot = tuple(EF.dev(c) for c in cot)
     kw = dict(events=ev, model=dm, guarded=True) if guarded else {}
     L = (nlp.tracking_kalman_guarded(Zout, ev, H, V, None, S0, W, dm) if guarded else nlp.tracking_kalman(Zout, H, V, None, S0, W))[0]
     dev = nlp.tracking_kalman_vjp(Zout, L, H, V, *dcot, **kw)
@@ -280,15 +244,15 @@ def test_a_batch_that_never_lands_is_bitwise_the_knot_scheduled_call_of_a_handle
     Zref[:, 15 + (3 if im == 1 else 1)::20] = -2.0  # every problem gets the last problem's pulling reference
     x0[:, iy], x0[:, iv] = 0.3, 0.0
     nlp, never = TC.nlp(batch, TC.SECOND_MODEL), TC.nlp(GC.with_k_trans(batch, N + 1), TC.SECOND_MODEL)
-    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), _dev(K), _dev(x0))
+    Zout, ev = nlp.tracking_rollout_guarded(nlp.upload_Z(Zref), EF.dev(K), EF.dev(x0))
     assert bool((ev[:, 0] == -1).all())
     rng = np.random.default_rng(N)
     S0, W = CR.random_psd(rng, shape=(B,)), rng.uniform(0.0, 1e-2, size=15)
-    H, V = measurement(rng, 3)
-    dcot = tuple(_dev(c) for c in KV.cotangents(N, N, 3, (B,)))
+    H, V = EF.measurement(rng, 3)
+    dcot = tuple(EF.dev(c) for c in KV.cotangents(N, N, 3, (B,)))
     L = never.tracking_kalman(Zout, H, V, None, S0, W)[0]
     ref = never.tracking_kalman_vjp(Zout, L, H, V, *dcot)
-    for model in (None, _dev(np.tile(TC.SECOND, (B, 1)))):
+    for model in (None, EF.dev(np.tile(TC.SECOND, (B, 1)))):
         got = nlp.tracking_kalman_vjp(Zout, L, H, V, *dcot, events=ev, model=model, guarded=True)
         assert all(torch.equal(got[k], ref[k]) for k in OUT)
 
@@ -317,7 +281,7 @@ def test_the_sweep_is_linear_in_the_cotangents(form):
     a, b = 0.7, -1.3
     c1, c2 = inp["cot"], KV.cotangents(4242 + N, N, ny, (B,))
     mix = tuple(a * x + b * y for x, y in zip(c1, c2))
-    dev = lambda c: _host(nlp.tracking_kalman_vjp(inp["Zout"], inp["L"], inp["H"], inp["V"], *(_dev(x) for x in c), **inp["kw"]))  # noqa: E731
+    dev = lambda c: _host(nlp.tracking_kalman_vjp(inp["Zout"], inp["L"], inp["H"], inp["V"], *(EF.dev(x) for x in c), **inp["kw"]))  # noqa: E731
     g1, g2, gm = _host(got), dev(c2), dev(mix)
     Lh = TC.to_np(inp["L"])
     y1, y2, ym = (KV.sweep(inp["A"], inp["H"], inp["V"], Lh, *c) for c in (c1, c2, mix))
@@ -341,7 +305,7 @@ def _record(guarded):
     rng = np.random.default_rng(N)
     S0, W = 1e-4 * CR.random_psd(rng, shape=(B,)), rng.uniform(0.0, 1e-6, size=15)
     Zref, Zrec = nlp.upload_Z(rec["Zref"]), nlp.upload_Z(rec["Zrec"])
-    Y, xh0, model = _dev(rec["Y"]), _dev(rec["xhat0"]), _dev(rec["model"])
+    Y, xh0, model = EF.dev(rec["Y"]), EF.dev(rec["xhat0"]), EF.dev(rec["model"])
     L = nlp.tracking_kalman(Zref, H, V, None, S0, W)[0]
     filt = nlp.landing_filter_guarded if guarded else nlp.landing_filter
     f = filt(Zref, Zrec, L, H, Y, V, xh0, model=model)
@@ -416,7 +380,7 @@ def test_refusals_behind_the_handle():
     f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device="cuda")  # noqa: E731
     p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
     a = lambda v: None if v is None else v.ctypes.data  # noqa: E731
-    Hd = _dev(inp["H"])
+    Hd = EF.dev(inp["H"])
     Lb, Pb, lb = inp["dcot"]
     S0b, Wb, Vb = f64(B, 120), f64(B, 15), f64(B, ny)
     V = inp["V"]

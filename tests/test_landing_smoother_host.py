@@ -10,14 +10,10 @@ import pytest
 from tests import landing_smoother_ref as SM
 from tests import tracking_cov_ref as CR
 from tests import tracking_kalman_ref as KR
+from tests.estimation_cases import vec_rel
 
 NX = 15
 BAND = 5 * np.sqrt(2 / 4095)  # the family's band on a sample variance of 4 096 draws: five standard deviations, 0.1105
-
-
-def vec_rel(got, ref):
-    """knot_rel on vectors (..., N, 15)"""
-    return CR.knot_rel(np.asarray(got)[..., None], np.asarray(ref)[..., None])
 
 
 def linear_problem(seed, N, ny, dt=np.float64, singular=False, V=None):

@@ -11,13 +11,9 @@ from tests import tracking_cases as TC
 from tests import tracking_cov_ref as CR
 from tests import tracking_kalman_ref as KR
 from tests import tracking_ref as TR
+from tests.estimation_cases import measurement
 
 CASES = [(40, 14, 1, 8), (61, 21, 2, 8), (40, 14, 1, 3), (12, 5, 2, 1), (2, 2, 1, 8)]  # (N, k_trans, init_mode, ny)
-
-
-def measurement(rng, ny):
-    """H = normal / sqrt(15), V in [0.5, 2]"""
-    return rng.normal(size=(ny, 15)) / np.sqrt(15.0), rng.uniform(0.5, 2.0, size=ny)
 
 
 def _problem(N, k_trans, init_mode, ny):

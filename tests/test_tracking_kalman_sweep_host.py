@@ -20,6 +20,7 @@ from tests import tracking_cases as TC
 from tests import tracking_cov_ref as CR
 from tests import tracking_guarded_ref as TG
 from tests import tracking_kalman_sweep_ref as KS
+from tests.estimation_cases import measurement
 
 LD = np.longdouble
 T_STEP = 2.0 ** -20
@@ -28,11 +29,6 @@ SCHEDULED = [(5, 3, 2), (17, 6, 1)]
 GUARDED = [(5, 2, 6), (17, 1, 3)]
 NYS = (1, 3, 8)
 ALONE = ("Sigma0", "W", "V", "all")
-
-
-def measurement(rng, ny):
-    """H = normal / sqrt(15), V in [0.5, 2]: tests/test_tracking_kalman_host.py's"""
-    return rng.normal(size=(ny, 15)) / np.sqrt(15.0), rng.uniform(0.5, 2.0, size=ny)
 
 
 @functools.lru_cache(maxsize=None)
